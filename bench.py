@@ -69,6 +69,35 @@ def make_samples(B: int, vocab: int, seed: int, device):
                 before_ids=before, after_ids=after, target_ids=tgt, target_mask=torch.ones(B, 16, dtype=torch.long))
 
 
+DUMP_PARAM_SAMPLES = 1 << 23      # 8 M fp32 values: 32 MB, half of what a dump may take
+
+
+def dump_outputs(out_dir: str, loss, store, n_sample: int = DUMP_PARAM_SAMPLES) -> None:
+    """What a caller of the timed step holds after the last one: its loss and the trainable parameters AdamW updated.
+    The parameters (115 M fp32 at the full configuration) are sampled at `n_sample` positions drawn by a fixed-seed generator
+    over the parameters concatenated in NAME order -- not the flat buffer's layout -- so that two builds of the project dump
+    the same positions.  Writes loss.npy (float64, [1]) and params_sample.npy (float32, [min(n_sample, total)])."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    names = sorted(store.p)
+    sizes = [store.p[n].numel() for n in names]
+    total = sum(sizes)
+    if total <= n_sample:
+        idx = torch.arange(total)
+    else:
+        idx = torch.sort(torch.randint(0, total, (n_sample,), generator=torch.Generator().manual_seed(1234)))[0]
+    parts, off = [], 0
+    for n, sz in zip(names, sizes):
+        lo, hi = torch.searchsorted(idx, torch.tensor([off, off + sz])).tolist()
+        if hi > lo:
+            p = store.p[n].reshape(-1)
+            parts.append(p[(idx[lo:hi] - off).to(p.device)].float().cpu())
+        off += sz
+    params = torch.cat(parts).numpy() if parts else np.zeros(0, np.float32)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([float(loss)], dtype=np.float64))
+    np.save(os.path.join(out_dir, "params_sample.npy"), params)
+
+
 KERNEL_NAMES = {1: "gemm_nt_kernel<128x128>", 2: "gemm_x8_kernel", 3: "gemm_nt_kernel<128x64>", 4: "gemm_nt_kernel<160x128>",
                 5: "gemm_nt_kernel<160x96>", 6: "gemm_nt_kernel<64x64>"}
 GEMM_OUT_F32 = 1
@@ -269,7 +298,12 @@ def main():
     ap.add_argument("--host-inputs", action="store_true",
                     help="inputs start in (pinned) host memory and every step uploads a fresh batch: the PCIe-inclusive rate "
                          "(DESIGN.md; never the headline `value`, whose inputs are resident in HBM)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/*.npy (rank 0): the loss and a fixed, "
+                         "seeded sample of the updated trainable parameters (see dump_outputs)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
 
     from myriad_amd import _lib
     from myriad_amd.myriad import MiniGPT4HIP, MyriadHIP
@@ -361,6 +395,8 @@ def main():
     dt = float(tt.item())
     ms_per_step = 1e3 * dt / a.steps
     value = a.batch * world * a.steps / dt
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, loss, model.store)      # before the probe steps below update the parameters again
 
     fl = flops_per_sample(a.arch, a.stage, cfg)
     step_tflops = a.batch * fl["total"] / (ms_per_step * 1e-3) / 1e12          # per GPU: every rank runs the same shard

@@ -472,18 +472,18 @@ def test_train_loop_looks_one_batch_ahead():
     assert train_loop(Recorder(), data_iter, 0, sched) == []
 
 
-REF = "/root/reference"
+CONFIG_YAML = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "config_yaml")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference checkout exists in the build container only")
 @pytest.mark.parametrize("rel", ["train_configs/loraadapter_simple_myriad_finetune.yaml", "train_configs/minigpt4_stage2_finetune.yaml",
                                  "eval_configs/myriad.yaml"])
 def test_config_reads_the_reference_yaml_files_unchanged(rel):
-    """`Config` (the OmegaConf-free counterpart of minigpt4/common/config.py:16-51) on the reference's own YAML files: model
-    defaults <- file <- --options, scientific-notation floats as floats, every section reachable by attribute and key."""
+    """`Config` (the OmegaConf-free counterpart of minigpt4/common/config.py:16-51) on YAML files laid out like the
+    reference's train / eval configs (tests/golden/config_yaml): model defaults <- file <- --options, scientific-notation
+    floats as floats, every section reachable by attribute and key."""
     import argparse
     from myriad_amd.config import Config
-    path = os.path.join(REF, rel)
+    path = os.path.join(CONFIG_YAML, rel)
     cfg = Config(argparse.Namespace(cfg_path=path, options=["run.max_epoch=3", "model.max_txt_len=77"]))
     m, r = cfg.model_cfg, cfg.run_cfg
     assert m.arch in ("myriad", "mini_gpt4") and m["arch"] == m.arch
