@@ -300,15 +300,16 @@ class CheckpointManager:
         os.makedirs(output_dir, exist_ok=True)
 
     def save(self, model, cur_epoch, lr: float, weight_decay: float = 0.05, config: Optional[dict] = None,
-             is_best: bool = False, dp=None) -> str:
+             is_best: bool = False, dp=None, betas=(0.9, 0.999)) -> str:
         """`dp`: the DataParallel in use.  In mode 'rs_ag' the Adam moments are sharded; with `dp` the gather (a collective:
-        every rank must then call save) happens here, without it a save of incomplete moments raises instead of writing them."""
+        every rank must then call save) happens here, without it a save of incomplete moments raises instead of writing them.
+        `betas`: the AdamW betas the updates used (recorded in the optimizer state's param_groups)."""
         if hasattr(model, "finish_update"):
             model.finish_update()                      # an overlapped optimiser step must land before parameters are read
         if dp is not None and not getattr(model.store, "moments_complete", True):
             dp.gather_state(model.store)
         save_obj = {"model": model.state_dict(),       # trainable parameters only, reference key names and layouts
-                    "optimizer": optimizer_state_dict(model.store, lr, weight_decay),
+                    "optimizer": optimizer_state_dict(model.store, lr, weight_decay, betas=betas),
                     "config": config or {}, "scaler": None, "epoch": cur_epoch}
         save_to = os.path.join(self.output_dir, "checkpoint_{}.pth".format("best" if is_best else cur_epoch))
         if len(self.saved_history) >= self.max_checkpoints:

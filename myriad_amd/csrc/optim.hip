@@ -60,13 +60,16 @@ extern "C" int mh_adamw_step(float* p, const float* g, float* m, float* v, void*
 // nothing is read back by the host.  mh_adamw_gated updates one contiguous range if *used > 0 with step = *steps + 1;
 // mh_adamw_bump then advances the counters of the used modules (launch it after the module's last range).
 __global__ void adamw_gated_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                   float* __restrict__ v, long n4, float lr, float beta1, float beta2, float eps, float wd,
-                                   float gscale, const float* __restrict__ used, const int* __restrict__ steps) {
+                                   float* __restrict__ v, long n4, float lr, double beta1_d, double beta2_d, float eps,
+                                   float wd, float gscale, const float* __restrict__ used, const int* __restrict__ steps) {
   if (*used <= 0.f) return;
+  // bias corrections and (1-beta) from the double betas, like mh_adamw_step and torch.optim.AdamW: taken from the fp32-rounded
+  // betas instead, (1-beta2) would be off by 1.3e-5 relative at beta2 = 0.999 and every stored exp_avg_sq with it
   const double st = (double)(*steps + 1);
-  const float bc1 = (float)(1.0 - pow((double)beta1, st));
-  const float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, st));
-  const float omb1 = (float)(1.0 - (double)beta1), omb2 = (float)(1.0 - (double)beta2);
+  const float bc1 = (float)(1.0 - pow(beta1_d, st));
+  const float bc2_sqrt = (float)sqrt(1.0 - pow(beta2_d, st));
+  const float omb1 = (float)(1.0 - beta1_d), omb2 = (float)(1.0 - beta2_d);
+  const float beta1 = (float)beta1_d, beta2 = (float)beta2_d;
   for (long it = blockIdx.x * (long)blockDim.x + threadIdx.x; it < n4; it += (long)gridDim.x * blockDim.x) {
     float4_t pp = *reinterpret_cast<const float4_t*>(p + it * 4);
     const float4_t gg = *reinterpret_cast<const float4_t*>(g + it * 4);
@@ -98,8 +101,8 @@ extern "C" int mh_adamw_gated(float* p, const float* g, float* m, float* v, long
   if (n % 4 || !used || !steps) return MH_ERR_ARG;
   long grid = (n / 4 + 255) / 256;
   if (grid > 256 * 16) grid = 256 * 16;
-  hipLaunchKernelGGL(adamw_gated_kernel, dim3((int)grid), dim3(256), 0, stream, p, g, m, v, n / 4, (float)lr, (float)beta1,
-                     (float)beta2, (float)eps, (float)weight_decay, (float)grad_scale, used, steps);
+  hipLaunchKernelGGL(adamw_gated_kernel, dim3((int)grid), dim3(256), 0, stream, p, g, m, v, n / 4, (float)lr, beta1, beta2,
+                     (float)eps, (float)weight_decay, (float)grad_scale, used, steps);
   MH_CHECK_LAUNCH();
   return MH_OK;
 }

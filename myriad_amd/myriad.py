@@ -697,7 +697,7 @@ class MyriadHIP(nn.Module):
                     # single-process step: the map tokenizer holds 91 % of the trainable parameters (its 105 M-weight head) and its
                     # gradient is complete here, right behind the LLaMA backward -- its AdamW (0.55 ms of HBM traffic) runs on the
                     # leaf stream beside the Q-Former backward instead of at the tail of the step.  Same kernel, same inputs.
-                    self.store.adamw_module("VETokenizer", early_adamw[0], early_adamw[1])
+                    self.store.adamw_module("VETokenizer", *early_adamw)
                     self._early_done = {"VETokenizer"}
                 if early_exchange is not None:
                     self._start_early_exchange(early_exchange)
@@ -736,7 +736,7 @@ class MyriadHIP(nn.Module):
         self._finish_backward()
 
     def _start_early_exchange(self, early_exchange) -> None:
-        """early_exchange = (dp, segment index[, (lr, weight_decay)]): start the segment's collective behind the current stream;
+        """early_exchange = (dp, segment index[, (lr, weight_decay, beta2)]): start the segment's collective behind the current stream;
         with the third item the segment's optimiser update follows its collective on the exchange's own stream order -- the gated
         AdamW on this rank's slices of the segment (its 1/world piece in 'rs_ag') with grad_scale 1/world, then in 'rs_ag' the
         all-gather of the updated parameters -- so both run under the Q-Former backward as well (finish_update() does the rest of
@@ -744,10 +744,10 @@ class MyriadHIP(nn.Module):
         dp, k = early_exchange[0], early_exchange[1]
         st = self.store
         if len(early_exchange) > 2 and getattr(dp, "supports_early_update", False):
-            lr, wd = early_exchange[2]
+            lr, wd, beta2 = early_exchange[2]
 
             def then():
-                st.adamw_pieces(dp.part_shards(st.total, k), lr, wd, grad_scale=1.0 / dp.world)
+                st.adamw_pieces(dp.part_shards(st.total, k), lr, wd, beta2=beta2, grad_scale=1.0 / dp.world)
                 dp.gather_part(st.flat_p, k)
             dp.start_part(st.flat_g_comm, st.total, k, then=then)
         else:
@@ -890,7 +890,7 @@ class MyriadHIP(nn.Module):
         return out
 
     def train_step(self, samples, lr: float, weight_decay: float = 0.05, allreduce=None, world: int = 1, dp=None,
-                   overlap: bool = True, next_samples=None, accum_grad_iters: int = 1, accum_index=None):
+                   overlap: bool = True, next_samples=None, accum_grad_iters: int = 1, accum_index=None, beta2: float = 0.999):
         """forward + backward (+ gradient all-reduce) + fused AdamW: one optimisation step of
         `BaseTask._train_inner_loop` (base_task.py:233-271) without the autograd bridge.
         With a `DataParallel` (`dp`) and overlap=True the all-reduce + AdamW of step t are hidden behind the frozen
@@ -905,7 +905,8 @@ class MyriadHIP(nn.Module):
         `accum_index` = the iteration index inside the epoch (RunnerBase passes it): the update then lands where the reference
         puts it, `(i + 1) % accum_grad_iters == 0` with i restarting every epoch (base_task.py:265), so when iters_per_epoch is
         not a multiple of accum_grad_iters the left-over gradients of an epoch's tail are folded into the next epoch's first
-        update, as the reference's un-zeroed .grad does.  Without it the window is counted in calls."""
+        update, as the reference's un-zeroed .grad does.  Without it the window is counted in calls.
+        `beta2`: AdamW's second-moment decay (run.beta2, runner_base.py:130-135); beta1 is 0.9 as in the reference."""
         with torch.no_grad():
             vit_out = self._take_prefetched_vit(samples)
             if next_samples is not None:
@@ -936,8 +937,12 @@ class MyriadHIP(nn.Module):
             due = accum_update_due(self._accum_count + 1, accum_grad_iters, accum_index)
             # no gradient exchange, no accumulation window: modules whose gradient is complete early are updated early (backward())
             # (world == 1 as well: a caller-scaled update -- `world` > 1 without dp / allreduce -- must see ONE grad_scale)
-            early = (lr, weight_decay) if (due and not accumulate and (dp is None or dp.world == 1) and allreduce is None
-                                           and world == 1 and os.environ.get("MYRIAD_EARLY_ADAMW", "1") != "0") else None
+            early = (lr, weight_decay, beta2) if (due and not accumulate and (dp is None or dp.world == 1) and allreduce is None
+                                                  and world == 1 and os.environ.get("MYRIAD_EARLY_ADAMW", "1") != "0") else None
+            if dp is not None and dp.world > 1 and self.arch == "myriad" and hasattr(dp, "set_segments"):
+                # the exchange's segmentation -- in 'rs_ag' the slices of the Adam moments each rank owns -- is fixed before the
+                # first exchange, whether or not this step overlaps it: every step then shards the optimiser state the same way
+                self._dp_segment(dp)
             # data parallel with the exchange overlapped: the tokenizer's segment of the gradient buffer starts its collective from
             # inside the backward (backward(): early_exchange); accumulation windows exchange the window's sum at its end instead
             early_x = None
@@ -945,7 +950,7 @@ class MyriadHIP(nn.Module):
                     and hasattr(dp, "start_part") and os.environ.get("MYRIAD_DP_EARLY", "1") != "0"):
                 k = self._dp_segment(dp)
                 if k is not None:
-                    early_x = (dp, k, (lr, weight_decay)) if os.environ.get("MYRIAD_DP_EARLY_ADAMW", "1") != "0" else (dp, k)
+                    early_x = (dp, k, (lr, weight_decay, beta2)) if os.environ.get("MYRIAD_DP_EARLY_ADAMW", "1") != "0" else (dp, k)
             self.backward(accumulate=accumulate, early_adamw=early, early_exchange=early_x)
             self._accum_count += 1
             if not due:
@@ -953,7 +958,7 @@ class MyriadHIP(nn.Module):
             self._accum_count = 0
             if dp is not None and dp.world > 1 and overlap:
                 dp.start(self.store.flat_g_comm, self.store.total)   # RCCL exchange on the side HIP stream (grads + use flags)
-                self._pending_update = (dp, lr, weight_decay)
+                self._pending_update = (dp, lr, weight_decay, beta2)
             else:
                 shard = None
                 if dp is not None and dp.world > 1:
@@ -962,8 +967,8 @@ class MyriadHIP(nn.Module):
                 elif allreduce is not None:
                     allreduce(self.store.flat_g_comm)
                     world = max(world, 1)
-                self.store.adamw_step(lr, weight_decay, grad_scale=1.0 / (dp.world if dp is not None else world), shard=shard,
-                                      skip=self._early_done)
+                self.store.adamw_step(lr, weight_decay, beta2=beta2, grad_scale=1.0 / (dp.world if dp is not None else world),
+                                      shard=shard, skip=self._early_done)
                 if shard is not None:
                     dp.gather_params(self.store.flat_p)
         return loss
@@ -995,16 +1000,16 @@ class MyriadHIP(nn.Module):
     def finish_update(self):
         """Apply a delayed optimiser update (overlap mode): wait for the gradient exchange, if any, then fused AdamW."""
         if self._pending_update is not None:
-            dp, lr, wd = self._pending_update
+            dp, lr, wd, beta2 = self._pending_update
             self._pending_update = None
             if dp is None:
-                self.store.adamw_step(lr, wd)
+                self.store.adamw_step(lr, wd, beta2=beta2)
                 return
             dp.wait()
             shard = self._dp_shards(dp)
             done = dp.take_early_done() if hasattr(dp, "take_early_done") else set()      # segments updated behind their collective
             segs = dp.segments(self.store.total) if done else []
-            self.store.adamw_step(lr, wd, grad_scale=1.0 / dp.world, shard=shard, exclude=[segs[k] for k in done])
+            self.store.adamw_step(lr, wd, beta2=beta2, grad_scale=1.0 / dp.world, shard=shard, exclude=[segs[k] for k in done])
             if shard is not None:
                 dp.gather_params(self.store.flat_p, skip=done) if done else dp.gather_params(self.store.flat_p)
 

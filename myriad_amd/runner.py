@@ -620,6 +620,7 @@ class RunnerBase:
         self.resume_ckpt_path = run.get("resume_ckpt_path", None)
         self.evaluate_only = bool(run.get("evaluate", False))
         self.accum_grad_iters = max(int(run.get("accum_grad_iters", 1)), 1)      # base_task.py:262-271: step every n-th iteration
+        self.beta2 = float(run.get("beta2", 0.999))                              # runner_base.py:130-135: AdamW betas (0.9, beta2)
         out_root = run.get("output_dir", "output")
         self.output_dir = os.path.join(out_root, job_id)
         if self.rank == 0:
@@ -697,7 +698,7 @@ class RunnerBase:
             lr = sched.step(cur_epoch=epoch, cur_step=i)                                    # stepped BEFORE the forward (:229)
             nxt = next(loader) if i + 1 < iters else None                                   # one batch of lookahead: its frozen
             loss = model.train_step(samples, lr, wd, dp=self.dp, next_samples=nxt,          # ViT forward runs on a side stream
-                                    accum_grad_iters=self.accum_grad_iters, accum_index=i)
+                                    accum_grad_iters=self.accum_grad_iters, accum_index=i, beta2=self.beta2)
             pending.append(loss)                          # the reference reads loss.item() every step (:276), which stalls the
             meters["lr"].update(lr)                       # launch thread behind the GPU; here the values are fetched at log points
             if i % self.log_freq == 0 or i == iters - 1:
@@ -728,7 +729,7 @@ class RunnerBase:
                 if self.rank == 0:                             # no validation split in the shipped recipes: save every epoch
                     lr = self.lr_scheduler.lr_at(cur_epoch, int(self.config.run_cfg.get("iters_per_epoch", 1)) - 1)
                     self.ckpt.save(self.model, cur_epoch, lr, float(self.config.run_cfg.get("weight_decay", 0.05)),
-                                   config=self.config.to_dict())
+                                   config=self.config.to_dict(), betas=(0.9, self.beta2))
             if self.evaluate_only:
                 break
             if self.dp is not None:

@@ -167,3 +167,57 @@ def test_a_module_that_never_stepped_has_no_optimizer_state(tmp_path):
     order, _ = C._optimizer_index(m.store)
     have = {order[i] for i in sd["state"]}
     assert have == {n for n in order if not n.startswith("VETokenizer.")}
+
+
+@pytest.mark.parametrize("beta2", [0.98, None])
+def test_run_beta2_reaches_every_update_and_the_checkpoint(tmp_path, beta2):
+    """runner_base.py:130-135 builds AdamW with betas (0.9, run_cfg.get("beta2", 0.999)): the Runner reads run.beta2 from the
+    config, hands it to every train_step (which carries it to all of its AdamW launches), and the checkpoint's optimizer state
+    records the betas the updates used; without the key, 0.999."""
+    import argparse
+    from myriad_amd.config import Config
+    from myriad_amd.runner import RunnerBase
+    path = os.path.join(os.path.dirname(__file__), "golden", "config_yaml", "train_configs", "loraadapter_simple_myriad_finetune.yaml")
+    opts = [f"run.output_dir={tmp_path}", "run.max_epoch=1", "run.iters_per_epoch=3", "run.accum_grad_iters=1"]
+    if beta2 is not None:
+        opts.append(f"run.beta2={beta2}")
+    cfg = Config(argparse.Namespace(cfg_path=path, options=opts))
+    want = 0.999 if beta2 is None else beta2
+
+    class Model(_ToyModel):
+        def __init__(self):
+            super().__init__()
+            self.calls = []
+
+        def train(self, mode=True):
+            return self
+
+        def train_step(self, samples, lr, weight_decay=0.05, **kw):
+            self.calls.append(kw.get("beta2"))
+            return torch.tensor(1.0)
+
+        def finish_update(self):
+            pass
+
+    class Loader:
+        def __len__(self):
+            return 3
+
+        def __next__(self):
+            return {}
+
+    class Sched:
+        def step(self, cur_epoch, cur_step):
+            return 1e-4
+
+        def lr_at(self, cur_epoch, cur_step):
+            return 1e-4
+
+    model = Model()
+    runner = RunnerBase(cfg, "job", model, {"ds": None}, device="cpu")
+    assert runner.beta2 == want
+    runner._sched, runner._loader = Sched(), Loader()
+    runner.train()
+    assert model.calls == [want] * 3
+    ck = torch.load(os.path.join(runner.output_dir, "checkpoint_0.pth"), map_location="cpu")
+    assert [tuple(g["betas"]) for g in ck["optimizer"]["param_groups"]] == [(0.9, want)] * len(ck["optimizer"]["param_groups"])

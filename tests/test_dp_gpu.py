@@ -63,21 +63,30 @@ def _reference(dev, wire="f32", mode="allreduce"):
     return C.snapshot(model), losses
 
 
-CASES = [("allreduce", "torch", "f32"), ("rs_ag", "torch", "f32"),
+# (mode, collective, wire, overlap per step: "1" = the exchange overlapped with the next step's ViT, "0" = a synchronous step)
+CASES = [("allreduce", "torch", "f32", "111"), ("rs_ag", "torch", "f32", "111"),
          # the path an 8-GPU node runs by default: the mh_ctx verbs, both modes, both wire types
-         ("allreduce", "ctx", "f32"), ("rs_ag", "ctx", "f32"), ("allreduce", "ctx", "bf16"), ("rs_ag", "ctx", "bf16"),
+         ("allreduce", "ctx", "f32", "111"), ("rs_ag", "ctx", "f32", "111"), ("allreduce", "ctx", "bf16", "111"),
+         ("rs_ag", "ctx", "bf16", "111"),
          # rank 0 cannot bring its context up: no rank may enter the communicator rendezvous, all fall back to torch.distributed
-         ("allreduce", "ctx_bad0", "f32")]
+         ("allreduce", "ctx_bad0", "f32", "111"),
+         # a synchronous step before overlapped ones: the rs_ag shard geometry -- which Adam-moment slices a rank
+         # owns -- must be the segmented one from the first exchange on, not change when the first overlapped step cuts segments
+         ("rs_ag", "torch", "f32", "011")]
 
 
-@pytest.mark.parametrize("mode,collective,wire", CASES)
-def test_two_ranks_on_one_gpu_equal_one_process_summing_their_gradients(mode, collective, wire, tmp_path, fake_rccl):
+def _case_id(case):
+    return "-".join(case[:3]) + ("" if case[3] == "111" else f"-overlap{case[3]}")
+
+
+@pytest.mark.parametrize("mode,collective,wire,overlap", CASES, ids=[_case_id(c) for c in CASES])
+def test_two_ranks_on_one_gpu_equal_one_process_summing_their_gradients(mode, collective, wire, overlap, tmp_path, fake_rccl):
     from tests import dp_common as C
-    port = str(29600 + (os.getpid() % 200) + 7 * CASES.index((mode, collective, wire)))
+    port = str(29600 + (os.getpid() % 200) + 7 * CASES.index((mode, collective, wire, overlap)))
     outs = [str(tmp_path / f"rank{r}.pt") for r in (0, 1)]
     env = dict(os.environ, PYTHONPATH=ROOT)
     procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "dp_worker.py"), str(r), "2", port, mode, outs[r],
-                               collective, wire, fake_rccl],
+                               collective, wire, fake_rccl, overlap],
                               env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT) for r in (0, 1)]
     logs = []
     for p in procs:

@@ -1002,19 +1002,148 @@ def test_greedy_step_in_one_launch_equals_the_two_scans(R, V, ban):
     assert int(ids[0]) == V // 3 and float(mar[0]) == 0.0
 
 
+# one sweep of the AdamW kernels' grid covers 4096 workgroups x 256 threads x 4 floats (csrc/optim.hip): this length wraps twice
+ADAMW_WRAP = 2 * 4096 * 256 * 4 + 4096 + 12
+ADAMW_STEPS = 24
+
+
+def _adamw_grad(n, step, seed):
+    """Step `step`'s gradient: fresh N(0, 1) draws every step (signs flip between steps) times a magnitude class per element --
+    exact zeros, 1e-10 (eps dominates the denominator), 1, 1e3, and 1 with a zero on about a third of the steps."""
+    gen = torch.Generator(device=DEV).manual_seed(seed * 1000 + step)
+    cls = torch.arange(n, device=DEV) % 5
+    g = torch.randn(n, generator=gen, device=DEV) * torch.tensor([0.0, 1e-10, 1.0, 1e3, 1.0], device=DEV)[cls]
+    drop = (torch.rand(n, generator=gen, device=DEV) < 1 / 3) & (cls == 4)
+    return g.masked_fill_(drop, 0.0)
+
+
+def _adamw_lrs(seed):
+    """An lr that changes every step."""
+    return (1e-3 * (0.25 + 1.5 * torch.rand(ADAMW_STEPS, generator=torch.Generator().manual_seed(seed), dtype=torch.float64))).tolist()
+
+
 def test_adamw_matches_oracle():
-    n = 4096 * 3
-    p = rnd(n, seed=101)
-    g = rnd(n, seed=102)
-    m, v = torch.zeros(n), torch.zeros(n)
-    pd, md, vd = p.clone().to(DEV), m.clone().to(DEV), v.clone().to(DEV)
-    shadow = torch.empty(n, dtype=torch.bfloat16, device=DEV)
-    for step in range(1, 4):
-        gk = g * step
-        R.adamw_step(p, gk, m, v, step, 1e-3, 0.05)
-        ops.adamw_step(pd, gk.to(DEV), md, vd, 1e-3, 0.05, step, shadow=shadow)
-    assert relerr(pd, p) < 1e-5 and relerr(md, m) < 1e-5 and relerr(vd, v) < 1e-5
-    assert relerr(shadow.float(), p) < 5e-3
+    """mh_adamw_step at (n, beta2, weight decay, grad_scale) = (4, 0.999, 0.05, 1), (12288, 0.98, 0, 0.5), (12292, 0.999, 0.05, 0.5)
+    and (2 * 4096 * 256 * 4 + 4096 + 12, 0.98, 0.05, 1): see _adamw_step_case."""
+    for case in ((4, 0.999, 0.05, 1.0), (4096 * 3, 0.98, 0.0, 0.5), (4096 * 3 + 4, 0.999, 0.05, 0.5), (ADAMW_WRAP, 0.98, 0.05, 1.0)):
+        _adamw_step_case(*case)
+
+
+def _adamw_step_case(n, beta2, wd, gscale):
+    """mh_adamw_step on a sub-range at a 4-element-aligned offset of larger buffers, 24 steps of independent gradients (see
+    _adamw_grad) with an lr that changes every step, against float64 torch.optim.AdamW fed the same (scaled) gradients: p, m and
+    v within the elementwise budgets derived in tests/adamw_ref.py, every step; the bf16 shadow is exactly round-to-nearest-even
+    of p; the elements on both sides of the range keep their bits.  The fp32 oracle (oracle.adamw_step) is held to its former
+    1e-5 of max-abs on the small lengths."""
+    from tests.adamw_ref import AdamWRef
+    off, tail = 36, 28
+    N = off + n + tail
+    p_all = rnd(N, seed=101).to(DEV)
+    g_all = rnd(N, seed=102).to(DEV)
+    m_all = rnd(N, seed=103).to(DEV)
+    v_all = rnd(N, seed=104).abs().to(DEV)
+    sh_all = bf(rnd(N, seed=105)).to(DEV)
+    bufs = (p_all, g_all, m_all, v_all, sh_all)
+    outside = lambda t: torch.cat([t[:off], t[off + n:]]).clone()
+    canaries = [outside(t) for t in bufs]
+    p, g, m, v, sh = (t[off:off + n] for t in bufs)
+    m.zero_()
+    v.zero_()
+    ref = AdamWRef([p], [wd], beta2)
+    small = n <= 4096 * 3 + 4
+    if small:
+        po, mo, vo = p.cpu().clone(), torch.zeros(n), torch.zeros(n)
+    for step, lr in enumerate(_adamw_lrs(n), start=1):
+        g.copy_(_adamw_grad(n, step, seed=n))
+        ops.adamw_step(p, g, m, v, lr, wd, step, beta2=beta2, grad_scale=gscale, shadow=sh)
+        ref.step([g * gscale], lr)
+        ref.check(0, p, m, v, f"n {n} step {step}")
+        assert torch.equal(sh, p.to(torch.bfloat16)), (n, step)
+        if small:
+            R.adamw_step(po, (g * gscale).cpu(), mo, vo, step, lr, wd, beta2=beta2)
+    if small:
+        assert relerr(p, po) < 1e-5 and relerr(m, mo) < 1e-5 and relerr(v, vo) < 1e-5
+    for t, c in zip(bufs, canaries):
+        assert torch.equal(outside(t), c), n
+
+
+@pytest.mark.parametrize("beta2,gscale", [(0.999, 0.5), (0.98, 1.0)])
+def test_adamw_gated_and_bump_match_torch_adamw_with_skipped_modules(beta2, gscale):
+    """mh_adamw_gated + mh_adamw_bump, the update the product runs (ParamStore), against float64 torch.optim.AdamW in which a
+    module unused in a step has .grad None.  Four ranges of one buffer, one per module, each with its own device-resident use
+    count and step counter, launched per step as ParamStore does (gated per range, then one bump):
+      0: 2 * 4096 * 256 * 4 + 4096 + 12 elements (the grid-stride loop wraps), wd 0.05, used = 2 (summed over two ranks) every step;
+      1: 4 elements, wd 0, unused in the first two steps (its first update comes at global step 3 and is ITS step 1);
+      2: 1000 elements, wd 0.05, starts with 5 updates behind it (moments given, bias correction of step 6 first), used on
+         even steps;
+      3: 4096 + 12 elements, wd 0, starts at step 3, never used: p, m and v keep their bits (no decay either).
+    Every step: each range within the budgets of tests/adamw_ref.py (a skipped step must leave the range bit-unchanged), the
+    counters equal torch's per-parameter step; the elements between and around the ranges keep their bits."""
+    from tests.adamw_ref import AdamWRef
+    # the bump alone: exactly the counters of the used entries advance
+    used = torch.tensor([2.0, 0.0, 1.0, 0.0], device=DEV)
+    steps = torch.tensor([7, 3, 0, 9], dtype=torch.int32, device=DEV)
+    ops.adamw_bump(used, steps)
+    assert steps.cpu().tolist() == [8, 3, 1, 9]
+
+    sizes, wds, start = [ADAMW_WRAP, 4, 1000, 4096 + 12], [0.05, 0.0, 0.05, 0.0], [0, 0, 5, 3]
+    use = lambda i, s: (2.0, 0.0 if s < 3 else 1.0, 1.0 if s % 2 == 0 else 0.0, 0.0)[i]
+    gap = 20
+    offs = [gap]
+    for k in sizes[:-1]:
+        offs.append(offs[-1] + k + gap)
+    N = offs[-1] + sizes[-1] + gap
+    p_all, g_all = rnd(N, seed=201).to(DEV), torch.zeros(N, device=DEV)
+    m_all, v_all = rnd(N, seed=202).to(DEV), rnd(N, seed=203).abs().to(DEV)
+    inside = torch.zeros(N, dtype=torch.bool, device=DEV)
+    for o, k in zip(offs, sizes):
+        inside[o:o + k] = True
+    canaries = [t[~inside].clone() for t in (p_all, m_all, v_all)]
+    sl = lambda t, i: t[offs[i]:offs[i] + sizes[i]]
+    for i in (0, 1):
+        sl(m_all, i).zero_()
+        sl(v_all, i).zero_()
+    ref = AdamWRef([sl(p_all, i) for i in range(4)], wds, beta2)
+    for i in (2, 3):
+        ref.seed_state(i, start[i], sl(m_all, i), sl(v_all, i))
+    counters = torch.tensor(start, dtype=torch.int32, device=DEV)
+    flags = torch.zeros(4, device=DEV)
+    for step, lr in enumerate(_adamw_lrs(7), start=1):
+        flags.copy_(torch.tensor([use(i, step) for i in range(4)]))
+        grads = []
+        for i in range(4):
+            gi = sl(g_all, i)
+            gi.copy_(_adamw_grad(sizes[i], step, seed=10 + i))      # an unused range still holds a (stale) nonzero gradient
+            ops.adamw_gated(sl(p_all, i), gi, sl(m_all, i), sl(v_all, i), lr, wds[i], flags[i:i + 1], counters[i:i + 1],
+                            beta2=beta2, grad_scale=gscale)
+            grads.append(gi * gscale if use(i, step) > 0 else None)
+        ops.adamw_bump(flags, counters)
+        ref.step(grads, lr)
+        for i in range(4):
+            ref.check(i, sl(p_all, i), sl(m_all, i), sl(v_all, i), f"step {step}")
+        assert counters.cpu().tolist() == [ref.steps(i) for i in range(4)], step
+    assert counters.cpu().tolist() == [ADAMW_STEPS, ADAMW_STEPS - 2, 5 + ADAMW_STEPS // 2, 3]
+    for t, c in zip((p_all, m_all, v_all), canaries):
+        assert torch.equal(t[~inside], c)
+
+
+def test_adamw_launchers_reject_a_ragged_length_and_skip_an_empty_one():
+    """n % 4 != 0 (the kernels move float4s) and step < 1 are argument errors; n = 0 launches nothing."""
+    from myriad_amd._lib import MyriadHipError
+    p, g, m, v = (rnd(8, seed=300 + i).to(DEV) for i in range(4))
+    before = [t.clone() for t in (p, g, m, v)]
+    used, steps = torch.ones(1, device=DEV), torch.zeros(1, dtype=torch.int32, device=DEV)
+    with pytest.raises(MyriadHipError):
+        ops.adamw_step(p[:6], g[:6], m[:6], v[:6], 1e-3, 0.05, 1)
+    with pytest.raises(MyriadHipError):
+        ops.adamw_step(p, g, m, v, 1e-3, 0.05, 0)
+    with pytest.raises(MyriadHipError):
+        ops.adamw_gated(p[:6], g[:6], m[:6], v[:6], 1e-3, 0.05, used, steps)
+    ops.adamw_step(p[:0], g[:0], m[:0], v[:0], 1e-3, 0.05, 1)
+    ops.adamw_gated(p[:0], g[:0], m[:0], v[:0], 1e-3, 0.05, used, steps)
+    ops.adamw_bump(used, steps[:0])
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip((p, g, m, v), before)) and int(steps) == 0
 
 
 # ------------------------------------------------------------------------------------------------ conv stack

@@ -514,8 +514,182 @@ def test_train_step_moves_parameters_like_adamw(composite):
     R.adamw_step(p_ref[:a], gflat.cpu()[:a], m[:a], v[:a], 1, 1e-3, 0.05)
     R.adamw_step(p_ref[a:], gflat.cpu()[a:], m[a:], v[a:], 1, 1e-3, 0.0)
     assert relerr(model.store.flat_p, p_ref) < 1e-5
+    # ... and elementwise: float64 torch.optim.AdamW on the two groups, within the budgets of tests/adamw_ref.py
+    from tests.adamw_ref import AdamWRef
+    ref = AdamWRef([p0[:a], p0[a:]], [0.05, 0.0])
+    ref.step([gflat[:a], gflat[a:]], 1e-3)
+    st = model.store
+    ref.check(0, st.flat_p[:a], st.flat_m[:a], st.flat_v[:a], "decay group")
+    ref.check(1, st.flat_p[a:], st.flat_m[a:], st.flat_v[a:], "no-decay group")
     loss1 = model.train_step(_samples(batch), lr=1e-3)
     assert float(loss1) < float(loss0)      # same batch, one AdamW step => loss goes down
+
+
+@pytest.mark.parametrize("accum,beta2", [(1, 0.999), (2, 0.999), (1, 0.98)])
+def test_training_trajectory_replays_on_float64_torch_adamw(accum, beta2):
+    """The default train_step path (the map tokenizer's AdamW early on the leaf stream, the rest at the tail, look-ahead ViT) of
+    the reduced-depth full-width LoRA model, replayed on the optimiser the reference builds: float64 torch.optim.AdamW, one
+    parameter per module range of the flat buffer in the reference's two groups, fed after every update the gradients and use
+    flags the step left in flat_g_comm (.grad None for a module no call of the window used) and that update's lr.
+    VEInstructor is unused in the first two steps (its first update is its own step 1 at a later global step), VETokenizer in a
+    later one; with accum_grad_iters = 2 the window's summed buffer is replayed at the due calls only.  p, m and v within the
+    budgets of tests/adamw_ref.py, per-module step counts equal torch's, the padding tail stays zero.  After every step the LoRA
+    borders of W_ext and W_ext^T hold, in every border group, bf16 of the B_q / B_v that step's forward read; the k rows' border
+    stays zero and the frozen block keeps its bits."""
+    from myriad_amd.lora import BORDER
+    from tests import dp_common as C
+    from tests.adamw_ref import AdamWRef
+    dev = torch.device(DEV)
+    model, cfg = C.build_model(dev)
+    model.lora.base_seed = 11
+    st, lora, layers = model.store, model.lora, model.llama.layers
+    for name, _, rshape in st.specs:
+        o, n = st.offsets[name]
+        assert [d for _, a, b, d in st.ranges if a <= o and o + n <= b] == [R.uses_weight_decay(name, len(rshape))], name
+    stages = [0, 0, 1, 2, 1, 0] if accum == 1 else [0, 0, 0, 1, 2, 2, 1, 0]
+    lrs = [1e-3, 7e-4, 1.2e-3, 5e-4, 9e-4, 3e-4, 8e-4, 6e-4][:len(stages)]
+    batches = [C.batch(0, i, cfg["vocab"], dev) for i in range(len(stages))]
+    torch.cuda.synchronize()
+    ref = AdamWRef([st.flat_p[a:b] for _, a, b, _ in st.ranges], [0.05 if d else 0.0 for _, _, _, d in st.ranges], beta2)
+    D, r = lora.D, lora.r
+    W = D
+    frozen = [(L["wqkv_ext"][:, :D].clone(), L["wqkvT_ext"][:D].clone()) for L in layers]
+    for i, stage in enumerate(stages):
+        torch.cuda.synchronize()
+        b_read = [(lora.P[lora.names(li)[2]].clone(), lora.P[lora.names(li)[3]].clone()) for li in range(len(layers))]
+        model.fixed_stage = stage
+        model.train_step(batches[i], lrs[i], 0.05, next_samples=batches[i + 1] if i + 1 < len(stages) else None,
+                         accum_grad_iters=accum, beta2=beta2)
+        torch.cuda.synchronize()
+        for li, L in enumerate(layers):
+            bq, bv = (t.view(W, r).to(torch.bfloat16) for t in b_read[li])
+            want = torch.zeros(3 * W, BORDER, dtype=torch.bfloat16, device=dev)
+            for grp in range(BORDER // (2 * r)):
+                want[:W, grp * 2 * r:grp * 2 * r + r] = bq
+                want[2 * W:, grp * 2 * r + r:(grp + 1) * 2 * r] = bv
+            assert torch.equal(L["wqkv_ext"][:, D:], want), (i, li)
+            assert torch.equal(L["wqkvT_ext"][D:], want.T), (i, li)
+            assert torch.equal(L["wqkv_ext"][:, :D], frozen[li][0]) and torch.equal(L["wqkvT_ext"][:D], frozen[li][1]), (i, li)
+        if (i + 1) % accum:
+            continue
+        gc = st.flat_g_comm.clone()
+        used = gc[st.total:st.total + len(st.modules)].cpu()
+        ref.step([gc[a:b] if float(used[mi]) > 0 else None for mi, a, b, _ in st.ranges], lrs[i])
+        for k, (mi, a, b, _) in enumerate(st.ranges):
+            ref.check(k, st.flat_p[a:b], st.flat_m[a:b], st.flat_v[a:b], f"call {i} {st.modules[mi]}")
+        assert st.module_steps() == {st.modules[mi]: ref.steps(k) for k, (mi, _, _, _) in enumerate(st.ranges)}, i
+        for t in (st.flat_p, st.flat_m, st.flat_v):
+            assert int(torch.count_nonzero(t[st.n_used:])) == 0
+    n_upd = len(stages) // accum
+    want_steps = {"expert_adaptor": n_upd, "lora": n_upd, "VEInstructor": n_upd - (3 if accum == 1 else 1),
+                  "VETokenizer": n_upd - 1}
+    assert st.module_steps() == want_steps
+
+
+def _store_state(st):
+    return [t.clone() for t in (st.flat_p, st.flat_m, st.flat_v, st.steps_dev)]
+
+
+def _store_load(st, state):
+    for t, s0 in zip((st.flat_p, st.flat_m, st.flat_v, st.steps_dev), state):
+        t.copy_(s0)
+
+
+@pytest.mark.parametrize("gscale,beta2", [(1.0, 0.999), (0.5, 0.98)])
+def test_param_store_splits_of_one_update_give_the_one_shot_bits(gscale, beta2):
+    """ParamStore bookkeeping.  One update of a store holding all four module kinds (odd-sized tensors: padding inside the ranges;
+    VEInstructor unused; counters at different steps) done as adamw_pieces + adamw_step(exclude=...), as adamw_module +
+    adamw_step(skip=...), and as per-rank `shard` lists (each rank from the same state: its own counters) gives the bits of the
+    one-shot adamw_step -- cut points inside a module range, on range boundaries, spanning two modules, empty pieces, and a
+    piece over the padding tail, which never changes.  The one-shot update itself is float64 torch.optim.AdamW with the
+    reference's grouping (oracle.uses_weight_decay per parameter, tests/adamw_ref.py budgets), and every range's decay flag is
+    that grouping."""
+    from myriad_amd.lora import lora_param_specs
+    from myriad_amd.myriad import ParamStore, module_of
+    from myriad_amd.networks import ve_param_specs
+    from tests.adamw_ref import AdamWRef
+    specs = ([("expert_adaptor.conv1.weight", (4, 37), (4, 37)), ("expert_adaptor.conv2.weight", (37, 4), (37, 4))]
+             + ve_param_specs("VETokenizer.", 8, 5) + [("VETokenizer.base_prompts", (9, 33), (9, 33))]
+             + ve_param_specs("VEInstructor.", 12, 1) + lora_param_specs(2, 36, 3))
+    st = ParamStore(specs, DEV)
+    for name, _, rshape in st.specs:
+        o, n = st.offsets[name]
+        dec = [d for _, a, b, d in st.ranges if a <= o and o + n <= b]
+        assert dec == [R.uses_weight_decay(name, len(rshape))], name
+    gen = torch.Generator(device=DEV).manual_seed(5)
+    st.flat_p.copy_(torch.randn(st.total, generator=gen, device=DEV))
+    st.flat_m.copy_(torch.randn(st.total, generator=gen, device=DEV) * 0.1)
+    st.flat_v.copy_(torch.rand(st.total, generator=gen, device=DEV) * 0.01)
+    st.flat_g.copy_(torch.randn(st.total, generator=gen, device=DEV))
+    flags = {"expert_adaptor": 2.0, "VETokenizer": 1.0, "VEInstructor": 0.0, "lora": 2.0}
+    st.used.copy_(torch.tensor([flags[m] for m in st.modules], device=DEV))
+    st.set_module_steps({"expert_adaptor": 3, "VETokenizer": 0, "VEInstructor": 2, "lora": 7})
+    assert st.n_used < st.total                                   # a padding tail exists: it must never change
+    s0 = _store_state(st)
+    lr = 7e-4
+    st.adamw_step(lr, 0.05, beta2=beta2, grad_scale=gscale)
+    s1 = _store_state(st)
+    torch.cuda.synchronize()
+    assert all(torch.equal(a[st.n_used:], b[st.n_used:]) for a, b in zip(s0[:3], s1[:3]))
+
+    # the one-shot update is torch's, per parameter, with the reference's weight-decay grouping
+    names = [n for n, _, _ in st.specs]
+    sl = lambda t, n: t[st.offsets[n][0]:st.offsets[n][0] + st.offsets[n][1]]
+    ref = AdamWRef([sl(s0[0], n) for n in names],
+                   [0.05 if R.uses_weight_decay(n, len(r)) else 0.0 for n, _, r in st.specs], beta2)
+    before = {"expert_adaptor": 3, "VETokenizer": 0, "VEInstructor": 2, "lora": 7}
+    for i, n in enumerate(names):                                # the moments the store holds, at each module's step count
+        ref.seed_state(i, before[module_of(n)], sl(s0[1], n), sl(s0[2], n))
+    ref.step([sl(st.flat_g, n) * gscale if flags[module_of(n)] > 0 else None for n in names], lr)
+    for i, n in enumerate(names):
+        ref.check(i, sl(s1[0], n), sl(s1[1], n), sl(s1[2], n), n)
+    assert st.module_steps() == {m: before[m] + (flags[m] > 0) for m in st.modules}
+
+    def same(what):
+        torch.cuda.synchronize()
+        for k, (a, b) in enumerate(zip(_store_state(st), s1)):
+            assert torch.equal(a, b), (what, ("p", "m", "v", "steps")[k])
+
+    rg = {st.modules[mi] + ("" if d else "/nd"): (a, b) for mi, a, b, d in st.ranges}
+    ta, tb = rg["VETokenizer"]
+    ea, eb = rg["expert_adaptor"]
+    inside = (ta + 40, ta + 1000)                                 # inside one module range
+    whole = rg["lora"]                                            # exactly one range
+    span = (eb - 8, ta + 16)                                      # across the boundary of two modules
+    tail = (st.n_used // 4 * 4, st.total)                         # over the padding tail
+    for pieces in ([inside], [whole], [span], [(ta + 4, ta + 4)], [tail],
+                   [span, (ta + 200, ta + 200), inside, whole, rg["VEInstructor/nd"], tail]):
+        _store_load(st, s0)
+        st.adamw_pieces(pieces, lr, 0.05, beta2=beta2, grad_scale=gscale)
+        st.adamw_step(lr, 0.05, beta2=beta2, grad_scale=gscale, exclude=pieces)
+        same(pieces)
+    if gscale == 1.0:                                             # adamw_module: the single-process early update (no scale)
+        for m in st.modules:
+            _store_load(st, s0)
+            st.adamw_module(m, lr, 0.05, beta2=beta2)
+            st.adamw_step(lr, 0.05, beta2=beta2, skip={m})
+            same(m)
+    for world in (2, 4):                                          # rs_ag: every rank updates its own slices, from the same state
+        cut = ta + 32 * 8
+        segs = [(0, cut), (cut, st.total)]
+        per_rank = []
+        for r in range(world):
+            mine = []
+            for lo, hi in segs:
+                per = -(-(hi - lo) // world)
+                per = (per + 3) // 4 * 4
+                a = min(lo + r * per, hi)
+                mine.append((a, min(a + per, hi)))
+            per_rank.append(mine)
+        _store_load(st, s0)
+        for mine in per_rank:
+            st.steps_dev.copy_(s0[3])
+            st.adamw_step(lr, 0.05, beta2=beta2, grad_scale=gscale, shard=mine)
+        same(("shards", world))
+        assert not st.moments_complete
+    _store_load(st, s0)
+    st.adamw_step(lr, 0.05, beta2=beta2, grad_scale=gscale, shard=(0, st.total))
+    same("one shard tuple")
 
 
 def test_ve_net_grads_vs_reference_bf16_forward_golden():
