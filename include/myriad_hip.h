@@ -236,6 +236,24 @@ int mh_decode_record(const long* nxt, const float* margin, const float* pmax, fl
    row): the step's three bookkeeping launches as one */
 int mh_decode_advance(const long* nxt, const float* margin, const float* pmax, float* rec, long* next_ids, int* step, int* pos,
                       int* kvlen, int R, mh_stream_t s);
+/* sampled decode step (HF generate(do_sample=True), conversation.py:144-168's chat call: TopK -> TopP -> multinomial, after the
+   min_length ban and TemperatureLogitsWarper), one workgroup per row, V <= 32768, ldl % 4 == 0, 16-byte aligned rows (else
+   MH_ERR_UNSUPPORTED).  params[4] f32 on the device = (inv_temp, top_p, top_k, penalty): tokens below the k-th largest tempered
+   logit go (ties at it all stay), then every token whose exclusive prefix mass in (logit desc, id asc) order reaches top_p (the
+   largest always stays); out[r] = the smallest i of that kept set with inclusive mass > u * (kept mass).  u from Philox4x32-10,
+   key = *seed (u64 on the device), counter = ((step ? *step : 0) + t_add, 0, r, 0): u = (x0 >> 8) * 2^-24, written to u_out[r]
+   when u_out is given.  margin / pmax as mh_argmax_pmax_rows (same bits); kept[r] = size of the kept set, or -1 when the tied
+   top-k set has more than 1024 members (out[r] is then the arg-max and the caller draws the row). */
+int mh_sample_rows(const float* logits, long ldl, long* out, float* margin, float* pmax, int* kept, float* u_out, int R, int V,
+                   int ban_id, const float* params, const unsigned long long* seed, const int* step, int t_add, mh_stream_t s);
+/* HF RepetitionPenaltyLogitsProcessor in place on f32 logits [R, ldl]: seen = R x ceil(V/32) u32 bitmap of the ids generated so
+   far (zeroed by the caller once per generate); prev_ids[r] (when given) is added first, then every seen id's logit becomes
+   x * p (x < 0) or x / p, p = *penalty (device scalar) -- each id once however often it was generated */
+int mh_repetition_penalty_rows(float* logits, long ldl, unsigned* seen, const long* prev_ids, int R, int V, const float* penalty,
+                               mh_stream_t s);
+/* mh_decode_advance with the sampler's kept count as a fourth record row: rec[4][R] f32 = (ids, margins, p_max, kept) */
+int mh_decode_advance_kept(const long* nxt, const float* margin, const float* pmax, const int* kept, float* rec, long* next_ids,
+                           int* step, int* pos, int* kvlen, int R, mh_stream_t s);
 
 /* K12 conv stacks of VEInstructorV2 / VETokenizer (networks.py:98-127,159-189) as im2col + mh_gemm_bf16_nt. */
 int mh_im2col_nhwc(const void* x, void* col, int B, int H, int W, int C, int kh, int kw, int pad, int Kpad,

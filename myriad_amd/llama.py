@@ -90,6 +90,9 @@ class LlamaHIP:
         # (55.7 -> 55.1 ms per step: they run beside the Q-Former backward); MYRIAD_LORA_DEFER=0 computes them in place
         self.defer_lora_wgrad = os.environ.get("MYRIAD_LORA_DEFER", "1") != "0"
         self.decode_fused = os.environ.get("MYRIAD_DECODE_FUSED", "1") != "0"
+        # do_sample with 1 <= top_k <= 1024 draws on the device inside the token step (mh_sample_rows) instead of on the host;
+        # off by default until it has been measured against the host draw (tools/decode_bench.py --sample)
+        self.device_sampling = os.environ.get("MYRIAD_DEVICE_SAMPLING", "0") != "0"
         self.last_layer_rows = os.environ.get("MYRIAD_LAST_LAYER_ROWS", "1") != "0"
         self._packed = None
         self._decode_ws = {}
@@ -356,13 +359,16 @@ class LlamaHIP:
             h = lin(li, "wd", act, residual=h2, out_dtype=F32)
         return h
 
-    def _decode_workspace(self, B: int, T_need: int, inv_temp: float):
+    def _decode_workspace(self, B: int, T_need: int, inv_temp: float, dev_sample: bool = False, penalty: bool = False):
         """Buffers (and, once captured, the hipGraph) of the single-token step for a batch size: KV caches, device-resident
         counters, id / logit / result buffers and per-step histories.  Kept across generate() calls -- an evaluation run
-        calls generate() once per batch, and re-capturing ~290 launches each time cost ~9 ms per call."""
+        calls generate() once per batch, and re-capturing ~290 launches each time cost ~9 ms per call.  The device sampler and
+        the repetition penalty read their knobs (`prm` = inv_temp, top_p, top_k, penalty) and the seed from device memory, so
+        the key holds only whether each is on; the arg-max kernel takes inv_temp as an argument, so it stays in the key there."""
         T_cap = ops.round_up(T_need + 2, 64)
-        key = (B, T_cap, float(inv_temp), id(self._packed), None if self._packed is None else self._packed.get("qkv_key"), self.decode_fused,
-               self.lora is not None)
+        key = (B, T_cap, None if dev_sample else float(inv_temp), id(self._packed),
+               None if self._packed is None else self._packed.get("qkv_key"), self.decode_fused, self.lora is not None,
+               bool(dev_sample), bool(penalty))
         ws = self._decode_ws.get(key)
         if ws is None:
             if len(self._decode_ws) >= 3:                               # a few shapes at most: evict the oldest
@@ -375,7 +381,11 @@ class LlamaHIP:
                       logits=torch.empty((B, self.V), dtype=F32, device=dev),
                       nxt=torch.empty((B,), dtype=torch.long, device=dev), mar=torch.empty((B,), dtype=F32, device=dev),
                       pmx=torch.empty((B,), dtype=F32, device=dev), step=torch.zeros((1,), dtype=i32, device=dev),
-                      rec=torch.zeros((3, B), dtype=F32, device=dev))
+                      rec=torch.zeros((4 if dev_sample else 3, B), dtype=F32, device=dev))
+            if dev_sample or penalty:
+                ws.update(prm=torch.zeros((4,), dtype=F32, device=dev), seed=torch.zeros((1,), dtype=torch.long, device=dev),
+                          kept=torch.zeros((B,), dtype=i32, device=dev),
+                          seen=torch.zeros((B, (self.V + 31) // 32), dtype=i32, device=dev))
             self._decode_ws[key] = ws
         return ws
 
@@ -384,7 +394,7 @@ class LlamaHIP:
                         stop_ids=((835,), (2277, 29937)), eos_id: int = 2, min_length: int = 1,
                         return_margins: bool = False, use_graph: bool = True, do_sample: bool = False,
                         top_p: float = 1.0, temperature: float = 1.0, generator: Optional[torch.Generator] = None,
-                        top_k: int = 50):
+                        top_k: int = 50, repetition_penalty: float = 1.0):
         """Decode from [B,S0,D] f32 embeddings with a KV cache (prefill + 1-token steps).  Same contract
         as the oracle's greedy_generate: stop when ROW 0 ends with a stop sequence (conversation.py:102-107),
         EOS banned while fewer than `min_length` tokens were generated, finished rows padded with EOS.
@@ -404,13 +414,28 @@ class LlamaHIP:
         bit-comparable with another framework's RNG) and replaces the fed-back id.  `last_generate_stats` counts such steps.
         The host draw applies HF's default `top_k = 50` filter first, then top-p; the device test p_max >= top_p is taken over the
         full vocabulary, which is the conservative side: the top-k renormalisation only raises p_max, and a row whose
-        renormalised p_max reaches top_p keeps exactly one token in the host draw -- the arg-max again."""
+        renormalised p_max reaches top_p keeps exactly one token in the host draw -- the arg-max again.
+
+        With `device_sampling` (MYRIAD_DEVICE_SAMPLING=1) and 1 <= top_k <= 1024 the whole chain runs inside the step instead
+        (mh_sample_rows: temperature, top-k with ties kept, top-p, inverse-CDF draw from Philox4x32-10 keyed by one seed drawn from
+        `generator` per call): every step is a draw, no row waits on the host, and runs are reproducible per seed but not
+        bit-comparable with torch.multinomial.  A row whose tied top-k set passes 1024 candidates is still drawn on the host.
+        `repetition_penalty` (HF RepetitionPenaltyLogitsProcessor over the generated ids; the prompt is embeddings only) is applied
+        on the device to the step's logits before any pick, greedy, host or device draw."""
         B, S0, D = inputs_embeds.shape
+        if do_sample and not float(temperature) > 0:
+            raise ValueError(f"temperature must be > 0 when sampling, got {temperature}")
+        if not float(repetition_penalty) > 0:
+            raise ValueError(f"repetition_penalty must be > 0, got {repetition_penalty}")
         scale = 1.0 / math.sqrt(self.hd)
         out_ids, margins = [], []
         unfinished = torch.ones(B, dtype=torch.long)
         inv_temp = 1.0 / float(temperature) if do_sample else 1.0
-        stats = dict(steps=0, sampled_rows=0, min_pmax=1.0)
+        top_k = 0 if top_k is None else int(top_k)
+        dev_sample = (self.device_sampling and do_sample and 1 <= top_k <= ops.SAMPLE_CAP and self.V <= 32768
+                      and self.V % 4 == 0)
+        penalty = float(repetition_penalty) != 1.0
+        stats = dict(steps=0, sampled_rows=0, min_pmax=1.0, device_sampled_rows=0, host_sampled_rows=0, graph_replays=0)
         self.last_generate_stats = stats
         if self.lora is not None:
             self.lora.refresh(self.layers)
@@ -418,8 +443,13 @@ class LlamaHIP:
             self._pack_for_decode()
         elif not self.pack_decode:
             self._packed = None                                      # MYRIAD_PACK_DECODE=0: stream the row-major matrices
-        ws = self._decode_workspace(B, S0 + max_new_tokens, inv_temp)
+        ws = self._decode_workspace(B, S0 + max_new_tokens, inv_temp, dev_sample, penalty)
         caches = ws["caches"]
+        if dev_sample or penalty:
+            ws["prm"].copy_(torch.tensor([inv_temp, top_p, float(top_k), float(repetition_penalty)], dtype=F32))
+            ws["seen"].zero_()                                       # generated ids only: the prompt is embeddings
+        if dev_sample:
+            ws["seed"].fill_(int(torch.randint(0, 2**63 - 1, (1,), generator=generator)))
 
         def sample_row(logits_row: torch.Tensor, ban: int) -> int:
             """HF TopPLogitsWarper + multinomial on one row (host)."""
@@ -436,7 +466,7 @@ class LlamaHIP:
             probs = torch.zeros_like(lg).scatter(0, idx, srt.softmax(-1))
             return int(torch.multinomial(probs, 1, generator=generator))
 
-        def record(nxt: torch.Tensor, mar: torch.Tensor, pm: torch.Tensor, ban: int, logits_of=None):
+        def record(nxt: torch.Tensor, mar: torch.Tensor, pm: torch.Tensor, ban: int, logits_of=None, kept=None):
             """Host bookkeeping of one step's picks.  Returns (done, redrawn): redrawn = a live row was re-drawn on the host
             (finished rows are fed their raw arg-max instead of EOS by the device: rows are independent and their outputs are
             overwritten with EOS here)."""
@@ -447,9 +477,15 @@ class LlamaHIP:
             if do_sample:
                 stats["min_pmax"] = min(stats["min_pmax"], float(pm[unfinished.bool()].min()) if int(unfinished.sum()) else 1.0)
                 for row in range(B):
-                    if int(unfinished[row]) and float(pm[row]) < top_p:
-                        nxt[row] = sample_row(logits_of()[row], ban)
+                    if not int(unfinished[row]):
+                        continue
+                    if float(pm[row]) < top_p:
                         stats["sampled_rows"] += 1
+                    if dev_sample and int(kept[row]) >= 0:
+                        stats["device_sampled_rows"] += 1            # drawn by the step itself
+                    elif dev_sample or float(pm[row]) < top_p:
+                        nxt[row] = sample_row(logits_of()[row], ban)
+                        stats["host_sampled_rows"] += 1
                         redrawn = True
             nxt = nxt * unfinished + eos_id * (1 - unfinished)       # HF pads finished rows with pad(=eos)
             unfinished = unfinished * (nxt != eos_id).long()
@@ -465,8 +501,12 @@ class LlamaHIP:
         last = h.view(B, S0, D)[:, -1].contiguous()
         logits0 = ops.gemm(ops.rmsnorm_fwd(last, self.norm, self.eps), self.lm_head, out_dtype=F32)
         ban0 = eos_id if 0 < min_length else -1
-        ops.argmax_pmax_rows(logits0, ws["nxt"], ws["mar"], ws["pmx"], ban_id=ban0, inv_temp=inv_temp)
-        done, _ = record(ws["nxt"].cpu(), ws["mar"].cpu(), ws["pmx"].cpu(), ban0, logits_of=lambda: logits0)
+        if dev_sample:                                               # the prefill pick is Philox step t = 0
+            ops.sample_rows(logits0, ws["nxt"], ws["mar"], ws["pmx"], ws["kept"], ws["prm"], ws["seed"], ban_id=ban0, t_add=0)
+        else:
+            ops.argmax_pmax_rows(logits0, ws["nxt"], ws["mar"], ws["pmx"], ban_id=ban0, inv_temp=inv_temp)
+        done, _ = record(ws["nxt"].cpu(), ws["mar"].cpu(), ws["pmx"].cpu(), ban0, logits_of=lambda: logits0,
+                         kept=ws["kept"].cpu() if dev_sample else None)
 
         # ---- single-token steps: everything the step reads is on the device
         ws["pos"].fill_(S0)                                          # position of the incoming token
@@ -485,6 +525,14 @@ class LlamaHIP:
                     ops.gemv_packed(hn, self._packed["lm_head"], out=ws["logits"], out_dtype=F32)
                 else:
                     ops.gemm(hn, self.lm_head, out=ws["logits"])
+            if penalty:                                              # ws["ids"] = the token fed in: it joins the seen set first
+                ops.repetition_penalty_rows(ws["logits"], ws["seen"], ws["ids"], ws["prm"][3:])
+            if dev_sample:                                           # token s (= step + 1) draws Philox step t = s
+                ops.sample_rows(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ws["kept"], ws["prm"], ws["seed"], ban_id=ban,
+                                step=ws["step"], t_add=1)
+                ops.decode_advance_kept(ws["nxt"], ws["mar"], ws["pmx"], ws["kept"], ws["rec"], ws["ids"], ws["step"], ws["pos"],
+                                        ws["kvlen"])
+                return
             ops.argmax_pmax_rows(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ban_id=ban, inv_temp=inv_temp)
             ops.decode_advance(ws["nxt"], ws["mar"], ws["pmx"], ws["rec"], ws["ids"], ws["step"], ws["pos"], ws["kvlen"])
 
@@ -492,6 +540,7 @@ class LlamaHIP:
             """Enqueue one token step: a replay of the captured graph when there is one."""
             if ban == -1 and use_graph and ws["graph"] is not None:
                 ws["graph"].replay()
+                stats["graph_replays"] += 1
                 return
             token_step(ban)
             if ban == -1 and use_graph and ws["warm"]:
@@ -510,7 +559,8 @@ class LlamaHIP:
             ban = eos_id if step < min_length else -1
             launch(ban)
             rec = ws["rec"].cpu()                                    # the one device->host copy of the step (it also waits for it)
-            done, redrawn = record(rec[0].long(), rec[1].clone(), rec[2].clone(), ban, logits_of=lambda: ws["logits"])
+            done, redrawn = record(rec[0].long(), rec[1].clone(), rec[2].clone(), ban, logits_of=lambda: ws["logits"],
+                                   kept=rec[3] if dev_sample else None)
             if redrawn and not done:
                 ws["ids"].copy_(out_ids[-1].to(self.dev))            # a host draw replaces the arg-max the step fed back to itself
             step += 1

@@ -1020,7 +1020,15 @@ class MyriadHIP(nn.Module):
         max_new_tokens, stopping_criteria (a list whose items carry `.stops` = id tensors, conversation.py:96-107, applied
         to batch row 0), do_sample + top_p + temperature (see LlamaHIP.greedy_generate: arg-max whenever p_max >= top_p,
         a host-side draw otherwise), min_length, use_cache.  Anything that would change the decoding rule and is not
-        implemented raises instead of being ignored."""
+        implemented raises instead of being ignored.
+
+        Also the chat call's sampling knobs (conversation.py:144-168): top_k (HF default 50; 0 / None = no top-k),
+        temperature (> 0 when sampling) and `generator`.  With `self.llama.device_sampling` (MYRIAD_DEVICE_SAMPLING=1, off by
+        default) and 1 <= top_k <= 1024 every draw happens on the device inside the captured token step, reproducible per seed
+        (drawn once per call from `generator`) but not bit-comparable with torch.multinomial; otherwise rows with p_max < top_p
+        are drawn on the host.  The same switch enables repetition_penalty (> 0; HF's rule over the generated ids, applied on
+        the device before every pick, greedy or sampled); with it off a penalty other than 1 raises as before.  num_beams,
+        length_penalty and num_return_sequences are not implemented and raise."""
         self.finish_update()
         kw = dict(generate_kwargs)
         stops = kw.pop("stop_ids", None)
@@ -1043,7 +1051,17 @@ class MyriadHIP(nn.Module):
             raise NotImplementedError("use_cache=False: decode here always keeps a KV cache (same tokens)")
         top_k = kw.pop("top_k", 50)                         # HF's generation default; only a sampled (host-drawn) row sees it
         top_k = 0 if top_k is None else int(top_k)
-        for k, neutral in (("num_beams", 1), ("repetition_penalty", 1.0), ("length_penalty", 1), ("num_return_sequences", 1)):
+        if do_sample and not temperature > 0:
+            raise ValueError(f"generate(temperature={temperature}): must be > 0 when do_sample=True")
+        rep_pen = kw.pop("repetition_penalty", 1.0)
+        rep_pen = 1.0 if rep_pen is None else float(rep_pen)
+        if not rep_pen > 0:
+            raise ValueError(f"generate(repetition_penalty={rep_pen}): must be > 0")
+        if rep_pen != 1.0 and not self.llama.device_sampling:
+            # opt-in like the device sampler itself: with the switch off generate() keeps its earlier contract and refuses it
+            raise NotImplementedError(f"generate(repetition_penalty={rep_pen}) needs the device sampling switch "
+                                      "(MYRIAD_DEVICE_SAMPLING=1 or model.llama.device_sampling = True)")
+        for k, neutral in (("num_beams", 1), ("length_penalty", 1), ("num_return_sequences", 1)):
             v = kw.pop(k, neutral)
             if v not in (neutral, None):
                 raise NotImplementedError(f"generate({k}={v}) is not implemented on the HIP decode path")
@@ -1064,7 +1082,7 @@ class MyriadHIP(nn.Module):
             max_new = max(1, max_len - emb.shape[1])
         ids = self.llama.greedy_generate(emb, max_new_tokens=max_new, stop_ids=stops, min_length=min_length, eos_id=eos_id,
                                          do_sample=do_sample, top_p=top_p, temperature=temperature, generator=generator,
-                                         top_k=top_k)
+                                         top_k=top_k, repetition_penalty=rep_pen)
         self.last_generate_stats = self.llama.last_generate_stats
         return {"token_ids": ids, "ve_anomaly_maps": maps}
 

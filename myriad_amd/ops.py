@@ -780,6 +780,34 @@ def decode_advance(nxt, margin, pmax, rec, next_ids, step_dev, pos, kvlen):
                                       _s()), "mh_decode_advance")
 
 
+SAMPLE_CAP = 1024      # most top-k candidates mh_sample_rows sorts on the device (include/myriad_hip.h)
+
+
+def sample_rows(logits: torch.Tensor, out, margin_out, pmax_out, kept_out, params: torch.Tensor, seed: torch.Tensor,
+                ban_id: int = -1, step=None, t_add: int = 0, u_out=None):
+    """HF top-k / top-p draw of one id per row on the device: params = f32 (inv_temp, top_p, top_k, penalty), seed = one int64,
+    Philox counter t = step[0] + t_add (t_add alone without `step`).  kept_out[r] = kept-set size, -1 = draw the row elsewhere."""
+    R, V = logits.shape
+    _lib.check(_L().mh_sample_rows(_p(logits), logits.stride(0), _p(out), _p(margin_out), _p(pmax_out), _p(kept_out), _p(u_out), R, V,
+                                   int(ban_id), _p(params), _p(seed), _p(step), int(t_add), _s()), "mh_sample_rows")
+    return out, kept_out
+
+
+def repetition_penalty_rows(logits: torch.Tensor, seen: torch.Tensor, prev_ids, penalty: torch.Tensor):
+    """In place: add prev_ids[r] to row r's seen-id bitmap (int32 [R, ceil(V/32)]), then x * p / x / p on every seen id."""
+    R, V = logits.shape
+    _lib.check(_L().mh_repetition_penalty_rows(_p(logits), logits.stride(0), _p(seen), _p(prev_ids), R, V, _p(penalty), _s()),
+               "mh_repetition_penalty_rows")
+    return logits
+
+
+def decode_advance_kept(nxt, margin, pmax, kept, rec, next_ids, step_dev, pos, kvlen):
+    """decode_advance() with the sampler's kept counts as a fourth record row (rec[4, R])."""
+    R = nxt.numel()
+    _lib.check(_L().mh_decode_advance_kept(_p(nxt), _p(margin), _p(pmax), _p(kept), _p(rec), _p(next_ids), _p(step_dev), _p(pos),
+                                           _p(kvlen), R, _s()), "mh_decode_advance_kept")
+
+
 # --------------------------------------------------------------------------- conv stack pieces
 def im2col(x_nhwc: torch.Tensor, kh: int, kw: int, pad: int, bias_col: bool = True):
     """[B*OH*OW, Kpad] bf16 patches, (ky, kx, c) order; with bias_col a column of ones follows the K patch columns (the bias

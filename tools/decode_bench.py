@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
-"""Greedy-decode throughput of the full-size model: prefill + N single-token steps with KV cache.
-python tools/decode_bench.py [--batch 1] [--new 32]"""
+"""Decode throughput of the full-size model: prefill + N single-token steps with KV cache.
+python tools/decode_bench.py [--batch 1] [--new 32] [--sample] [--penalty P] [--modes greedy,host,device] [--repeats 5]
+--sample: the chat call's do_sample=True, top_p=0.9, top_k=50 (drawn on the device when MYRIAD_DEVICE_SAMPLING=1, else on the
+host); --modes times several decodes in one process, interleaved per repeat: greedy, host (sampled, host draw), device (sampled,
+device draw); --penalty adds repetition_penalty to every mode."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -12,7 +15,12 @@ ap.add_argument("--batch", type=int, default=1)
 ap.add_argument("--new", type=int, default=32)
 ap.add_argument("--llm-layers", type=int, default=32)
 ap.add_argument("--lora", type=int, default=0, help="1: PEFT LoRA r = 8 on q_proj / v_proj attached (the fine-tuned model's generate)")
+ap.add_argument("--sample", action="store_true", help="do_sample=True, top_p=0.9, top_k=50")
+ap.add_argument("--penalty", type=float, default=1.0, help="repetition_penalty")
+ap.add_argument("--modes", default="", help="comma list of greedy / host / device, timed interleaved in one process")
+ap.add_argument("--repeats", type=int, default=1)
 a = ap.parse_args()
+modes = [m for m in a.modes.split(",") if m] or ["sample" if a.sample else "greedy"]
 dev = "cuda:0"
 cfg = full_config(llm_layers=a.llm_layers)
 model = MyriadHIP(SyntheticWeights(cfg, dev, seed=0), dict(need_backward=False, use_lora=bool(a.lora)), device=dev)
@@ -22,18 +30,37 @@ B = a.batch
 smp = dict(image=torch.randn(B, 3, 224, 224, generator=g), anomaly_maps=torch.rand(B, 1, 224, 224, generator=g),
            before_ids=torch.randint(3, 32000, (1, 4), generator=g).expand(B, -1).contiguous(),
            after_ids=torch.randint(3, 32000, (1, 28), generator=g).expand(B, -1).contiguous())
-def run(n):
+default_dev = model.llama.device_sampling
+
+
+def run(n, mode):
+    kw = {}
+    if mode != "greedy":
+        kw = dict(do_sample=True, top_p=0.9, top_k=50, generator=torch.Generator().manual_seed(0))
+    model.llama.device_sampling = {"host": False, "device": True}.get(mode, default_dev)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    out = model.generate(smp, max_new_tokens=n, stop_ids=((-1,),), min_length=0, eos_token_id=-5)
+    out = model.generate(smp, max_new_tokens=n, stop_ids=((-1,),), min_length=0, eos_token_id=-5, repetition_penalty=a.penalty, **kw)
     torch.cuda.synchronize()
     return time.perf_counter() - t0, out
 
 
-run(2); run(6)                           # warm-up: kernels, then the token-step graph of this batch size is captured
-t_short, _ = run(a.new // 4)
-t_long, out = run(a.new)
-n_long, n_short = out["token_ids"].shape[1], a.new // 4
-per_tok = (t_long - t_short) / (n_long - n_short)    # prefill / vision cancel: pure single-token decode steps
-print(f"batch {B}{' +LoRA' if a.lora else ''}: {n_long} tokens in {t_long*1e3:.1f} ms (incl. ViT+Q-Former+prefill); decode step {per_tok*1e3:.2f} ms/token "
-      f"-> {B / per_tok:.1f} tok/s steady; weight stream {13.2e9 / per_tok / 1e12:.2f} TB/s of 6.3 achievable")
+for m in modes:
+    run(2, m); run(6, m)                 # warm-up: kernels, then the token-step graph of this batch size is captured
+res = {m: [] for m in modes}
+for _ in range(a.repeats):
+    for m in modes:
+        t_short, _ = run(a.new // 4, m)
+        t_long, out = run(a.new, m)
+        n_long, n_short = out["token_ids"].shape[1], a.new // 4
+        res[m].append(((t_long - t_short) / (n_long - n_short), t_long, n_long, dict(model.last_generate_stats)))
+for m in modes:
+    ts = sorted(r[0] for r in res[m])
+    per_tok, t_long, n_long, st = res[m][-1][0], res[m][-1][1], res[m][-1][2], res[m][-1][3]
+    per_tok = ts[len(ts) // 2]                        # prefill / vision cancel: pure single-token decode steps (median)
+    extra = (f" [{m}: device-drawn rows {st.get('device_sampled_rows', 0)}, host-drawn {st.get('host_sampled_rows', 0)}, "
+             f"graph replays {st.get('graph_replays', 0)}]" if m != "greedy" or a.penalty != 1.0 else "")
+    print(f"batch {B}{' +LoRA' if a.lora else ''} {m}{f' penalty {a.penalty}' if a.penalty != 1.0 else ''}: {n_long} tokens in "
+          f"{t_long*1e3:.1f} ms (incl. ViT+Q-Former+prefill); decode step {per_tok*1e3:.3f} ms/token (median of {len(ts)}, "
+          f"min {ts[0]*1e3:.3f}, max {ts[-1]*1e3:.3f}) -> {B / per_tok:.1f} tok/s steady; weight stream "
+          f"{13.2e9 / per_tok / 1e12:.2f} TB/s of 6.3 achievable{extra}")
