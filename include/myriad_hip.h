@@ -255,6 +255,20 @@ int mh_repetition_penalty_rows(float* logits, long ldl, unsigned* seen, const lo
 int mh_decode_advance_kept(const long* nxt, const float* margin, const float* pmax, const int* kept, float* rec, long* next_ids,
                            int* step, int* pos, int* kvlen, int R, mh_stream_t s);
 
+/* beam search step (HF GenerationMixin._beam_search), nb <= 8 beams, K = 2*nb, 2*nb <= V <= 32768 (else MH_ERR_UNSUPPORTED):
+   rows b*rpi .. b*rpi+rpi-1 of fp32 logits [B*rpi, ldl] belong to item b (rpi = nb, or 1 for the step after a prefill at B rows);
+   per row score = scores[row] + ((x - max) - log(sum exp(x - max))), -inf at ban_id (< 0: none); per item the top K over its
+   rpi*V candidates, best first, ties to the lower flat index row_in_item * V + token: out_s / out_i [B, K] (the step's record).
+   part_s / part_i = caller scratch of B*rpi*K entries each.  pos / kvlen (both given or both null): += 1 for rows [0, n_adv). */
+int mh_beam_topk(const float* logits, long ldl, const float* scores, float* part_s, int* part_i, float* out_s, int* out_i, int B,
+                 int rpi, int nb, int V, int ban_id, int* pos, int* kvlen, int n_adv, mh_stream_t s);
+/* in-place KV-cache reorder of every layer in one launch: caches = device table of L pointers to [B*nb, T_cap, C] bf16 caches
+   (16-byte aligned, C % 8 == 0); cache[r, p] = old cache[src[r], p] for p in [*lo, *hi), src / lo / hi read from device memory
+   (capturable).  src[r] must name a row of r's own item (b*nb .. b*nb+nb-1; anything else is treated as src[r] == r); rows with
+   src[r] == r are not written; duplicate parents are fine (every source is read before any store of the same cell). */
+int mh_beam_reorder_kv(void* const* caches, int L, int B, int nb, long T_cap, int C, const int* src, const int* lo, const int* hi,
+                       mh_stream_t s);
+
 /* K12 conv stacks of VEInstructorV2 / VETokenizer (networks.py:98-127,159-189) as im2col + mh_gemm_bf16_nt. */
 int mh_im2col_nhwc(const void* x, void* col, int B, int H, int W, int C, int kh, int kw, int pad, int Kpad,
                    mh_stream_t s);

@@ -16,6 +16,7 @@ import math
 import os
 from typing import Dict, List, Optional
 
+import numpy as np
 import torch
 
 from . import ops
@@ -359,16 +360,20 @@ class LlamaHIP:
             h = lin(li, "wd", act, residual=h2, out_dtype=F32)
         return h
 
-    def _decode_workspace(self, B: int, T_need: int, inv_temp: float, dev_sample: bool = False, penalty: bool = False):
+    def _decode_workspace(self, B: int, T_need: int, inv_temp: float, dev_sample: bool = False, penalty: bool = False,
+                          num_beams: int = 1):
         """Buffers (and, once captured, the hipGraph) of the single-token step for a batch size: KV caches, device-resident
         counters, id / logit / result buffers and per-step histories.  Kept across generate() calls -- an evaluation run
         calls generate() once per batch, and re-capturing ~290 launches each time cost ~9 ms per call.  The device sampler and
         the repetition penalty read their knobs (`prm` = inv_temp, top_p, top_k, penalty) and the seed from device memory, so
-        the key holds only whether each is on; the arg-max kernel takes inv_temp as an argument, so it stays in the key there."""
+        the key holds only whether each is on; the arg-max kernel takes inv_temp as an argument, so it stays in the key there.
+        With num_beams > 1, B counts rows (items x beams) and the beam step's buffers join: `bupd` = the per-step upload
+        (ids int64 | parent rows int32 | running scores f32) and its pinned host twin, the top-K scratch and record, and the
+        device table of the per-layer cache pointers that mh_beam_reorder_kv walks."""
         T_cap = ops.round_up(T_need + 2, 64)
         key = (B, T_cap, None if dev_sample else float(inv_temp), id(self._packed),
                None if self._packed is None else self._packed.get("qkv_key"), self.decode_fused, self.lora is not None,
-               bool(dev_sample), bool(penalty))
+               bool(dev_sample), bool(penalty), int(num_beams))
         ws = self._decode_ws.get(key)
         if ws is None:
             if len(self._decode_ws) >= 3:                               # a few shapes at most: evict the oldest
@@ -386,6 +391,14 @@ class LlamaHIP:
                 ws.update(prm=torch.zeros((4,), dtype=F32, device=dev), seed=torch.zeros((1,), dtype=torch.long, device=dev),
                           kept=torch.zeros((B,), dtype=i32, device=dev),
                           seen=torch.zeros((B, (self.V + 31) // 32), dtype=i32, device=dev))
+            if num_beams > 1:
+                nb, K = int(num_beams), 2 * int(num_beams)
+                bupd = torch.zeros((4 * B,), dtype=i32, device=dev)
+                ws.update(bupd=bupd, bupd_host=torch.zeros((4 * B,), dtype=i32).pin_memory(),
+                          ids=bupd[:2 * B].view(torch.long), src=bupd[2 * B:3 * B], bscore=bupd[3 * B:].view(F32),
+                          part_s=torch.empty((B * K,), dtype=F32, device=dev), part_i=torch.empty((B * K,), dtype=i32, device=dev),
+                          brec=torch.zeros((2, B // nb * K), dtype=i32, device=dev), lo=torch.zeros((1,), dtype=i32, device=dev),
+                          table=torch.tensor([c.data_ptr() for c in ws["caches"]], dtype=torch.long).to(dev))
             self._decode_ws[key] = ws
         return ws
 
@@ -568,6 +581,168 @@ class LlamaHIP:
         if return_margins:
             return ids, torch.stack(margins, 1)
         return ids
+
+    @torch.no_grad()
+    def beam_generate(self, inputs_embeds: torch.Tensor, num_beams: int, max_new_tokens: int = 90, stop_ids=(), eos_id: int = 2,
+                      min_length: int = 1, length_penalty: float = 1.0, early_stopping=False, num_return_sequences: int = 1,
+                      use_graph: bool = True, return_scores: bool = False, pad_id: Optional[int] = None):
+        """Beam search from [B,S0,D] f32 embeddings: HF GenerationMixin._beam_search (tests/beam_ref.py states the rules).
+        Returns [B * num_return_sequences, L] int64 (CPU), generated ids only, the hypotheses of item b at rows
+        b * nrs .. b * nrs + nrs - 1 best first, right-padded with pad_id (default EOS); with return_scores also their
+        sequence scores (sum log-probs / len ** length_penalty), which last_generate_stats["sequences_scores"] holds either way.
+
+        Stop rule: a hypothesis finishes when its own sequence ends with EOS or with one of `stop_ids` (per hypothesis, as
+        transformers applies a criterion that returns one bool per row), or at max_new_tokens.  greedy_generate keeps the
+        reference's rule instead (the batch stops when row 0 ends with a stop sequence).
+
+        Device / host split.  The prefill runs at B rows, writing its keys / values into row b * nb of the B * nb row caches,
+        and one mh_beam_reorder_kv broadcasts them over [0, S0) to the item's other beams.  The token step (captured into a
+        hipGraph, like greedy's) is: reorder the generated positions [S0, pos) of every cache by the parent rows `src`, embed
+        the fed tokens, the decoder layers at B * nb rows (packed GEMV up to 16 rows), lm-head, mh_beam_topk (log-softmax +
+        running score + EOS ban, per item the top 2 * nb candidates), pos / kvlen += 1.  The host reads the [2, B, 2*nb]
+        record (one device->host copy), keeps the hypotheses, and writes the next step's (ids, src, running scores) with one
+        host->device copy."""
+        B, S0, D = inputs_embeds.shape
+        nb, nrs = int(num_beams), int(num_return_sequences)
+        if nb > ops.BEAM_MAX:
+            raise NotImplementedError(f"num_beams={nb}: at most {ops.BEAM_MAX} beams on the HIP decode path")
+        if nb < 1:
+            raise ValueError(f"num_beams must be >= 1, got {nb}")
+        if not 1 <= nrs <= nb:
+            raise ValueError(f"num_return_sequences={nrs} must be between 1 and num_beams={nb}")
+        if early_stopping not in (True, False, "never"):
+            raise ValueError(f"early_stopping must be True, False or 'never', got {early_stopping!r}")
+        if self.V < 2 * nb:
+            raise ValueError(f"num_beams={nb} needs a vocabulary of at least {2 * nb} tokens")
+        lp = float(length_penalty)
+        pad = eos_id if pad_id is None else int(pad_id)
+        stops = [tuple(int(t) for t in st) for st in stop_ids]
+        R, K, V, NEG = B * nb, 2 * nb, self.V, np.float32(-1.0e9)
+        scale = 1.0 / math.sqrt(self.hd)
+        stats = dict(steps=0, num_beams=nb, graph_replays=0, finished_hypotheses=0, sequences_scores=None, lengths=None)
+        self.last_generate_stats = stats
+        if self.lora is not None:
+            self.lora.refresh(self.layers)
+        if self.pack_decode and R <= 16:
+            self._pack_for_decode()
+        elif not self.pack_decode:
+            self._packed = None
+        ws = self._decode_workspace(R, S0 + max_new_tokens, 1.0, num_beams=nb)
+        caches, T_cap, C = ws["caches"], ws["T"], 2 * self.D
+        dev = self.dev
+
+        # ---- host state of the search (HF's tensors, per item, as small numpy arrays / lists)
+        run_seqs = [[()] * nb for _ in range(B)]
+        fin_scores = np.full((B, nb), NEG, dtype=np.float32)
+        fin_seqs = [[()] * nb for _ in range(B)]
+        is_fin = np.zeros((B, nb), dtype=bool)
+        unsat = np.ones((B,), dtype=bool)
+        host = ws["bupd_host"]
+        h_ids, h_src, h_sc = host[:2 * R].view(torch.long).numpy(), host[2 * R:3 * R].numpy(), host[3 * R:].view(F32).numpy()
+
+        def select(top_s: np.ndarray, top_i: np.ndarray, gen_len: int) -> bool:
+            """One step's bookkeeping from the record (top_s / top_i [B, K]); fills the upload; True = go on."""
+            nonlocal unsat
+            stats["steps"] += 1
+            all_hit = True
+            for b in range(B):
+                par, tok = top_i[b] // V, top_i[b] % V
+                cand = [run_seqs[b][int(par[k])] + (int(tok[k]),) for k in range(K)]
+                hits = np.array([c[-1] == eos_id or gen_len >= max_new_tokens
+                                 or any(len(c) >= len(st) and c[-len(st):] == st for st in stops) for c in cand])
+                all_hit &= bool(hits.all())
+                run_lp = top_s[b] + hits.astype(np.float32) * NEG
+                nxt = np.argsort(-run_lp, kind="stable")[:nb]
+                run_seqs[b] = [cand[k] for k in nxt]
+                h_ids[b * nb:(b + 1) * nb] = tok[nxt]
+                h_src[b * nb:(b + 1) * nb] = b * nb + par[nxt]
+                h_sc[b * nb:(b + 1) * nb] = run_lp[nxt]
+                did = hits.copy()
+                did[nb:] = False                                     # only the top nb candidates may enter the pool
+                sc = top_s[b] / np.float32(gen_len ** lp)
+                if is_fin[b].all() and early_stopping is True:
+                    sc = sc + NEG
+                if not unsat[b]:
+                    sc = sc + NEG
+                sc = sc + (~did).astype(np.float32) * NEG
+                merged = np.concatenate([fin_scores[b], sc])
+                keep = np.argsort(-merged, kind="stable")[:nb]
+                mseqs, mfin = fin_seqs[b] + cand, np.concatenate([is_fin[b], did])
+                fin_scores[b], fin_seqs[b], is_fin[b] = merged[keep], [mseqs[k] for k in keep], mfin[keep]
+                best_len = max_new_tokens if (early_stopping == "never" and lp > 0.0) else gen_len
+                best_run = np.float32(h_sc[b * nb]) / np.float32(best_len ** lp)
+                worst = fin_scores[b].min()
+                unsat[b] = unsat[b] and bool(np.any(np.where(is_fin[b], best_run > worst, best_run > NEG)))
+            return bool(unsat.any()) and not (bool(is_fin.all()) and early_stopping is True) and not all_hit
+
+        def read_record():
+            rec = ws["brec"].cpu()                                   # the one device->host copy of the step
+            return rec[0].view(F32).numpy().reshape(B, K), rec[1].numpy().reshape(B, K).astype(np.int64)
+
+        # ---- prefill at B rows into rows b * nb, then broadcast the prompt's keys / values to the other beams
+        pos = torch.arange(S0, dtype=torch.int32).repeat(B).to(dev)
+        h = self._decode_block(inputs_embeds.reshape(B * S0, D).contiguous(), B, S0, [c[::nb] for c in caches], scale, pos, past=0)
+        last = h.view(B, S0, D)[:, -1].contiguous()
+        logits0 = ops.gemm(ops.rmsnorm_fwd(last, self.norm, self.eps), self.lm_head, out_dtype=F32)
+        ws["bscore"].zero_()                                         # beam 0's running score; one row per item here
+        ops.beam_topk(logits0, ws["bscore"], ws["part_s"], ws["part_i"], ws["brec"][0].view(F32), ws["brec"][1], B, nb,
+                      ban_id=eos_id if 0 < min_length else -1)
+        if self.layers:
+            # a range of its own: ws["lo"] holds the previous call's S0 when the workspace is reused
+            bsrc = torch.arange(B, dtype=torch.int32).repeat_interleave(nb).mul_(nb).to(dev)
+            span = torch.tensor([0, S0], dtype=torch.int32).to(dev)
+            ops.beam_reorder_kv(ws["table"], len(caches), B, nb, T_cap, C, bsrc, span[:1], span[1:])
+        going = select(*read_record(), 1)
+
+        # ---- token steps
+        ws["pos"].fill_(S0)
+        ws["kvlen"].fill_(S0 + 1)
+        ws["lo"].fill_(S0)                                           # the prompt prefix is the same in every beam of an item
+
+        def token_step(ban):
+            ops.beam_reorder_kv(ws["table"], len(caches), B, nb, T_cap, C, ws["src"], ws["lo"], ws["pos"])
+            ops.embed_gather(self.embed, ws["ids"], ws["x_in"])
+            hh = self._decode_block(ws["x_in"], R, 1, caches, scale, ws["pos"], pos_dev=ws["pos"], kvlen_dev=ws["kvlen"])
+            done_lm = None
+            if self._packed is not None and R <= 16 and self.decode_fused:
+                done_lm = ops.gemv_packed_rmsnorm(hh, self.norm, self.eps, self._packed["lm_head"], out=ws["logits"], out_dtype=F32)
+            if done_lm is None:
+                hn = ops.rmsnorm_fwd(hh, self.norm, self.eps)
+                if self._packed is not None and R <= 16:
+                    ops.gemv_packed(hn, self._packed["lm_head"], out=ws["logits"], out_dtype=F32)
+                else:
+                    ops.gemm(hn, self.lm_head, out=ws["logits"])
+            ops.beam_topk(ws["logits"], ws["bscore"], ws["part_s"], ws["part_i"], ws["brec"][0].view(F32), ws["brec"][1], B, nb,
+                          ban_id=ban, pos=ws["pos"], kvlen=ws["kvlen"])
+
+        def launch(ban):
+            if ban == -1 and use_graph and ws["graph"] is not None:
+                ws["graph"].replay()
+                stats["graph_replays"] += 1
+                return
+            token_step(ban)
+            if ban == -1 and use_graph and ws["warm"]:
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    token_step(-1)
+                ws["graph"] = g
+            ws["warm"] = True
+
+        gen = 1                                                      # tokens generated so far
+        while going and gen < max_new_tokens:
+            ws["bupd"].copy_(ws["bupd_host"], non_blocking=True)    # ids | src | running scores: one host->device copy
+            launch(eos_id if gen < min_length else -1)
+            gen += 1
+            going = select(*read_record(), gen)
+
+        seqs = [fin_seqs[b][i] for b in range(B) for i in range(nrs)]
+        scores = torch.from_numpy(np.array([fin_scores[b, i] for b in range(B) for i in range(nrs)], dtype=np.float32))
+        ids = torch.full((len(seqs), max(1, max(len(q) for q in seqs))), pad, dtype=torch.long)
+        for r, q in enumerate(seqs):
+            ids[r, :len(q)] = torch.tensor(q, dtype=torch.long)
+        stats.update(sequences_scores=scores, finished_hypotheses=int(is_fin.sum()), lengths=[len(q) for q in seqs])
+        return (ids, scores) if return_scores else ids
 
     def embed_tokens_into(self, ids: torch.Tensor, out2d: torch.Tensor, dst_rows: Optional[torch.Tensor] = None):
         ops.embed_gather(self.embed, ids, out2d, dst_rows)

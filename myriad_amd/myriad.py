@@ -14,6 +14,7 @@ Out of scope here: the ImageBind vision expert.  Its out
 """
 from __future__ import annotations
 
+import numbers
 import os
 import random
 from collections import OrderedDict
@@ -1027,8 +1028,15 @@ class MyriadHIP(nn.Module):
         default) and 1 <= top_k <= 1024 every draw happens on the device inside the captured token step, reproducible per seed
         (drawn once per call from `generator`) but not bit-comparable with torch.multinomial; otherwise rows with p_max < top_p
         are drawn on the host.  The same switch enables repetition_penalty (> 0; HF's rule over the generated ids, applied on
-        the device before every pick, greedy or sampled); with it off a penalty other than 1 raises as before.  num_beams,
-        length_penalty and num_return_sequences are not implemented and raise."""
+        the device before every pick, greedy or sampled); with it off a penalty other than 1 raises as before.
+
+        num_beams > 1 (with do_sample=False) runs HF's beam search (LlamaHIP.beam_generate) and then also takes length_penalty,
+        early_stopping (True / False / "never") and num_return_sequences (<= num_beams, else ValueError): token_ids is
+        [B * num_return_sequences, L], item-major, best first, and last_generate_stats gains num_beams, sequences_scores,
+        finished_hypotheses and graph_replays.  Beam search applies the stop sequences per hypothesis, greedy / sampled decoding
+        keeps the reference's row-0 rule.  Refused with beams: do_sample (beam sampling), repetition_penalty != 1 and
+        num_beams > 8.  Without beams, length_penalty / num_return_sequences other than 1 raise NotImplementedError and
+        early_stopping is an unknown argument, as before."""
         self.finish_update()
         kw = dict(generate_kwargs)
         stops = kw.pop("stop_ids", None)
@@ -1061,6 +1069,29 @@ class MyriadHIP(nn.Module):
             # opt-in like the device sampler itself: with the switch off generate() keeps its earlier contract and refuses it
             raise NotImplementedError(f"generate(repetition_penalty={rep_pen}) needs the device sampling switch "
                                       "(MYRIAD_DEVICE_SAMPLING=1 or model.llama.device_sampling = True)")
+        num_beams = kw.pop("num_beams", 1)
+        num_beams = 1 if num_beams is None else num_beams
+        integral = isinstance(num_beams, numbers.Integral) or (isinstance(num_beams, numbers.Real) and float(num_beams).is_integer())
+        if not integral or num_beams < 1:                  # HF refuses these too (ValueError)
+            raise ValueError(f"generate(num_beams={num_beams!r}): must be a positive integer")
+        num_beams = int(num_beams)
+        beam_kw = {}
+        if num_beams > 1:
+            if do_sample:
+                raise NotImplementedError(f"generate(num_beams={num_beams}, do_sample=True): beam sampling is not implemented")
+            if rep_pen != 1.0:
+                raise NotImplementedError(f"generate(num_beams={num_beams}, repetition_penalty={rep_pen}) is not implemented")
+            if num_beams > ops.BEAM_MAX:
+                raise NotImplementedError(f"generate(num_beams={num_beams}): at most {ops.BEAM_MAX} beams on the HIP decode path")
+            lp = kw.pop("length_penalty", 1.0)
+            nrs = kw.pop("num_return_sequences", 1)
+            es = kw.pop("early_stopping", False)
+            beam_kw = dict(length_penalty=1.0 if lp is None else float(lp), num_return_sequences=1 if nrs is None else int(nrs),
+                           early_stopping=False if es is None else es)
+            if not 1 <= beam_kw["num_return_sequences"] <= num_beams:
+                raise ValueError(f"generate(num_return_sequences={nrs}) has to be between 1 and num_beams={num_beams}")
+            if beam_kw["early_stopping"] not in (True, False, "never"):
+                raise ValueError(f"generate(early_stopping={es!r}): True, False or 'never'")
         for k, neutral in (("num_beams", 1), ("length_penalty", 1), ("num_return_sequences", 1)):
             v = kw.pop(k, neutral)
             if v not in (neutral, None):
@@ -1080,9 +1111,13 @@ class MyriadHIP(nn.Module):
         emb = emb[:, 1:].contiguous()         # generate() wraps without BOS (myriad.py:446-449)
         if max_new is None:
             max_new = max(1, max_len - emb.shape[1])
-        ids = self.llama.greedy_generate(emb, max_new_tokens=max_new, stop_ids=stops, min_length=min_length, eos_id=eos_id,
-                                         do_sample=do_sample, top_p=top_p, temperature=temperature, generator=generator,
-                                         top_k=top_k, repetition_penalty=rep_pen)
+        if num_beams > 1:
+            ids = self.llama.beam_generate(emb, num_beams, max_new_tokens=max_new, stop_ids=stops, eos_id=eos_id,
+                                           min_length=min_length, **beam_kw)
+        else:
+            ids = self.llama.greedy_generate(emb, max_new_tokens=max_new, stop_ids=stops, min_length=min_length, eos_id=eos_id,
+                                             do_sample=do_sample, top_p=top_p, temperature=temperature, generator=generator,
+                                             top_k=top_k, repetition_penalty=rep_pen)
         self.last_generate_stats = self.llama.last_generate_stats
         return {"token_ids": ids, "ve_anomaly_maps": maps}
 

@@ -808,6 +808,30 @@ def decode_advance_kept(nxt, margin, pmax, kept, rec, next_ids, step_dev, pos, k
                                            _p(kvlen), R, _s()), "mh_decode_advance_kept")
 
 
+BEAM_MAX = 8           # most beams mh_beam_topk / mh_beam_reorder_kv take (include/myriad_hip.h)
+
+
+def beam_topk(logits: torch.Tensor, scores: torch.Tensor, part_s, part_i, out_s, out_i, B: int, nb: int, ban_id: int = -1,
+              pos=None, kvlen=None):
+    """The beam step's selection: per item b the top 2*nb of (scores[row] + log_softmax(logits[row])) over the item's rows
+    (logits [B*rpi, V], rpi = nb, or 1 for the step after a B-row prefill), best first, ties to the lower flat index
+    row_in_item * V + token, into out_s (f32) / out_i (int32) [B, 2*nb].  part_s / part_i: scratch of B*rpi*2*nb entries.
+    With pos / kvlen, every row of those buffers advances by one (the end of a token step)."""
+    R, V = logits.shape
+    rpi = R // B
+    n_adv = 0 if pos is None else pos.numel()
+    _lib.check(_L().mh_beam_topk(_p(logits), logits.stride(0), _p(scores), _p(part_s), _p(part_i), _p(out_s), _p(out_i), B, rpi, nb,
+                                 V, int(ban_id), _p(pos), _p(kvlen), n_adv, _s()), "mh_beam_topk")
+    return out_s, out_i
+
+
+def beam_reorder_kv(cache_table: torch.Tensor, L: int, B: int, nb: int, T_cap: int, C: int, src, lo, hi):
+    """In place, every layer: cache[r, p] = cache[src[r], p] for p in [lo[0], hi[0]); cache_table = int64 device tensor of the L
+    [B*nb, T_cap, C] bf16 cache base pointers; src / lo / hi int32 device tensors (read by the kernel: capturable)."""
+    _lib.check(_L().mh_beam_reorder_kv(_p(cache_table), L, B, nb, int(T_cap), C, _p(src), _p(lo), _p(hi), _s()),
+               "mh_beam_reorder_kv")
+
+
 # --------------------------------------------------------------------------- conv stack pieces
 def im2col(x_nhwc: torch.Tensor, kh: int, kw: int, pad: int, bias_col: bool = True):
     """[B*OH*OW, Kpad] bf16 patches, (ky, kx, c) order; with bias_col a column of ones follows the K patch columns (the bias
