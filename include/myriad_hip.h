@@ -325,6 +325,20 @@ int mh_gemv_packed_rmsnorm(const float* H, long ldh, const float* norm_w, float 
                            mh_stream_t s);
 int mh_gemv_packed_silu(const void* gu, long ldgu, const void* P, void* C, int ldc, int M, int N, int K, const float* bias,
                         const float* residual, int ldr, int out_f32, float alpha, mh_stream_t s);
+/* FP8 weight-only copy for the decode step (opt-in): mh_gemv_pack_fp8 writes q = e4m3fn(W / s_n) (round to nearest even,
+ * saturated to +-448) in the stream order above at one byte per weight (mh_gemv_pack_fp8_elems(N, K) bytes: each KiB holds
+ * one 64-deep step of a wave) and the row scales s_n = amax_n / 448 (1 for an all-zero row) into scale_out[N].  The three
+ * fp8 products take the same arguments and contract as their bf16 forms plus the scales, and compute
+ * C = alpha * s_n * A . q^T (+bias) (+residual): each code widened exactly to bf16, the same MFMA, s_n then alpha in the epilogue. */
+long mh_gemv_pack_fp8_elems(int N, int K);
+int mh_gemv_pack_fp8(const void* W, int ldb, int N, int K, void* q_out, float* scale_out, mh_stream_t s);
+int mh_gemv_packed_fp8(const void* A, int lda, const void* Q, const float* scale, void* C, int ldc, int M, int N, int K,
+                       const float* bias, const float* residual, int ldr, int out_f32, float alpha, mh_stream_t s);
+int mh_gemv_packed_fp8_rmsnorm(const float* H, long ldh, const float* norm_w, float eps, const void* Q, const float* scale,
+                               void* C, int ldc, int M, int N, int K, const float* bias, const float* residual, int ldr,
+                               int out_f32, float alpha, mh_stream_t s);
+int mh_gemv_packed_fp8_silu(const void* gu, long ldgu, const void* Q, const float* scale, void* C, int ldc, int M, int N, int K,
+                            const float* bias, const float* residual, int ldr, int out_f32, float alpha, mh_stream_t s);
 /* One decode token of attention (modeling_llama.py:186-222 with the KV cache): rotary on q / k, k | v appended at cache row
  * pos_dev[0], the one query against kv_len[b] keys -- mh_rope_kv_append + mh_attn_fwd(Sq = 1) in one launch, same bits.
  * qkv [B, ld_qkv] bf16 = [q | k | v] (q rotated in place), cache [B][T_cap][2 H D] rows [k | v], out [B, H D] bf16. */

@@ -13,14 +13,62 @@
 //     one (MODE 0, the first version, measured 3.9-4.2 TB/s);
 //   * the activation rows (<= 16 x K bf16, L2-resident) are read as the A operand of v_mfma_f32_16x16x32_bf16, so
 //     one MFMA retires 1 KiB of weights: the matrix pipe is idle-cheap and exact-fp32 accumulation comes for free.
+//
+// FP8 weight-only decode (opt-in, llama.py decode_fp8): the packed kernels (MODE 2 and gemv_pro_kernel) also take a copy of W
+// as OCP e4m3fn codes q [N, K] with one fp32 scale s_n per output row (mh_gemv_pack_fp8: s_n = amax_n / 448, q = e4m3fn(W / s_n),
+// round to nearest even, saturated to +-448).  Same k per lane as the bf16 copy: a lane's 16 B now hold all 16 k of a 64-deep
+// step, so one wave-instruction still reads one contiguous KiB, which is twice the k-depth.  Each code is widened exactly to
+// bf16 in registers (v_cvt_scalef32_pk_bf16_fp8, scale 1; every e4m3fn value, subnormals included, is a bf16 value) and fed to
+// the same v_mfma_f32_16x16x32_bf16, so products and the fp32 accumulation are those of x . q exactly.  s_n is applied in the
+// epilogue, once per output column, after the cross-wave sum and BEFORE alpha:  v = (sum_k x q * s_n) * alpha (+bias)(+res).
+// Activations are never quantised.
 #include "common.h"
 #include <cstdlib>
 
-template <int MODE, int UNROLL, int GV_NW>
-__global__ __launch_bounds__(GV_NW * 64) void gemv_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
+typedef unsigned char fp8_t;                                        // one OCP e4m3fn code
+typedef __attribute__((ext_vector_type(4))) unsigned gv_u4_t;
+
+// 8 e4m3fn codes (two dwords, k ascending from the low byte) -> 8 bf16 in MFMA operand order; exact
+__device__ __forceinline__ short8_t fp8x8_to_bf16(unsigned a, unsigned b) {
+  gv_u4_t r;
+  r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(a, 1.0f, false));
+  r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(a, 1.0f, true));
+  r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b, 1.0f, false));
+  r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b, 1.0f, true));
+  return __builtin_bit_cast(short8_t, r);
+}
+
+// One lane's weight fragment of one 64-deep step of a packed copy (k = 16*lg .. 16*lg+15), by weight type: the load is
+// issued early (raw bytes held in registers), the widening happens at the MFMA.  A step is 1024 elements of WT in both
+// layouts: 2 KiB of bf16 as two KiB halves (w0, w1), 1 KiB of fp8 (all 16 codes in w0; w1 is not used).
+template <typename WT>
+__device__ __forceinline__ void gv_load(const WT* wp, size_t t, short8_t& w0, short8_t& w1) {
+  if constexpr (sizeof(WT) == 1) {
+    w0 = __builtin_nontemporal_load(reinterpret_cast<const short8_t*>(wp + t * 1024));
+  } else {
+    w0 = __builtin_nontemporal_load(reinterpret_cast<const short8_t*>(wp + t * 1024));
+    w1 = __builtin_nontemporal_load(reinterpret_cast<const short8_t*>(wp + t * 1024 + 512));
+  }
+}
+template <typename WT>
+__device__ __forceinline__ float4_t gv_mfma(short8_t x0, short8_t x1, short8_t w0, short8_t w1, float4_t acc) {
+  if constexpr (sizeof(WT) == 1) {
+    const gv_u4_t q = __builtin_bit_cast(gv_u4_t, w0);
+    w0 = fp8x8_to_bf16(q[0], q[1]);
+    w1 = fp8x8_to_bf16(q[2], q[3]);
+  }
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x0, w0, acc, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1, w1, acc, 0, 0, 0);
+}
+
+template <int MODE, int UNROLL, int GV_NW, typename WT = bf16_t>
+__global__ __launch_bounds__(GV_NW * 64) void gemv_kernel(const bf16_t* __restrict__ A, const WT* __restrict__ B,
                                                           void* __restrict__ Cv, const float* __restrict__ bias,
                                                           const float* res, int M, int N, int K, int lda, int ldb,
-                                                          int ldc, int ldr, int out_f32, float alpha) {
+                                                          int ldc, int ldr, int out_f32, float alpha,
+                                                          const float* __restrict__ wscale = nullptr) {
+  constexpr bool F8 = sizeof(WT) == 1;
+  static_assert(!F8 || MODE == 2, "fp8 weights come only as the packed copy");
   __shared__ float red[GV_NW][16 * 16];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lr = lane & 15, lg = lane >> 4;
@@ -29,7 +77,7 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_kernel(const bf16_t* __restri
   nrow = nrow < N ? nrow : N - 1;
   const int mrow = lr < M ? lr : M - 1;          // rows >= M duplicate the last row; their results are never stored
   float4_t acc = (float4_t){0.f, 0.f, 0.f, 0.f};
-  if (MODE == 0) {
+  if constexpr (MODE == 0) {
     const bf16_t* wp = B + (size_t)nrow * ldb + lg * 8;
     const bf16_t* xp = A + (size_t)mrow * lda + lg * 8;
     const int nsteps = K / 32;
@@ -52,15 +100,16 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_kernel(const bf16_t* __restri
       const short8_t xv = *reinterpret_cast<const short8_t*>(xp + k);
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xv, wv, acc, 0, 0, 0);
     }
-  } else if (MODE == 2) {
+  } else if constexpr (MODE == 2) {
     // MODE 1's arithmetic on a pre-permuted weight copy (mh_gemv_pack): the bytes lane (lr, lg) of wave w needs at step t
     // sit at ((block * NW + w) * per + t) * 2 KiB + h * 1 KiB + lane * 16, so every wave-instruction reads one contiguous
     // KiB and a wave walks one contiguous region -- 6.8 TB/s against 5.8 TB/s for the row-strided order on a pure stream
     // (tools/micro/stream_pattern.hip), and bit-identical results (same k per lane, same reduction order).
+    // The fp8 copy (mh_gemv_pack_fp8): ((block * NW + w) * per + t) * 1 KiB + lane * 16, one KiB per step.
     const bf16_t* xp = A + (size_t)mrow * lda + lg * 16;
     const int nsteps = K / 64;
     const int per = (nsteps + GV_NW - 1) / GV_NW;
-    const bf16_t* wp = B + ((size_t)blockIdx.x * GV_NW + wave) * per * 1024 + lane * 8;
+    const WT* wp = B + ((size_t)blockIdx.x * GV_NW + wave) * per * 1024 + lane * (16 / sizeof(WT));
     int s = wave * per;
     const int s0 = s;
     const int s_end = (s + per) < nsteps ? (s + per) : nsteps;
@@ -69,16 +118,12 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_kernel(const bf16_t* __restri
 #pragma unroll
       for (int u = 0; u < UNROLL; ++u) {
         const int k = (s + u) * 64;
-        w0[u] = __builtin_nontemporal_load(reinterpret_cast<const short8_t*>(wp + (size_t)(s - s0 + u) * 1024));
-        w1[u] = __builtin_nontemporal_load(reinterpret_cast<const short8_t*>(wp + (size_t)(s - s0 + u) * 1024 + 512));
+        gv_load(wp, (size_t)(s - s0 + u), w0[u], w1[u]);
         x0[u] = *reinterpret_cast<const short8_t*>(xp + k);
         x1[u] = *reinterpret_cast<const short8_t*>(xp + k + 8);
       }
 #pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x0[u], w0[u], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1[u], w1[u], acc, 0, 0, 0);
-      }
+      for (int u = 0; u < UNROLL; ++u) acc = gv_mfma<WT>(x0[u], x1[u], w0[u], w1[u], acc);
     }
     if (s < s_end) {                                   // remainder as one partial batch (loads in flight together), same order
       const int rem = s_end - s;
@@ -87,17 +132,13 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_kernel(const bf16_t* __restri
       for (int u = 0; u < UNROLL; ++u)
         if (u < rem) {
           const int k = (s + u) * 64;
-          w0[u] = __builtin_nontemporal_load(reinterpret_cast<const short8_t*>(wp + (size_t)(s - s0 + u) * 1024));
-          w1[u] = __builtin_nontemporal_load(reinterpret_cast<const short8_t*>(wp + (size_t)(s - s0 + u) * 1024 + 512));
+          gv_load(wp, (size_t)(s - s0 + u), w0[u], w1[u]);
           x0[u] = *reinterpret_cast<const short8_t*>(xp + k);
           x1[u] = *reinterpret_cast<const short8_t*>(xp + k + 8);
         }
 #pragma unroll
       for (int u = 0; u < UNROLL; ++u)
-        if (u < rem) {
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x0[u], w0[u], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1[u], w1[u], acc, 0, 0, 0);
-        }
+        if (u < rem) acc = gv_mfma<WT>(x0[u], x1[u], w0[u], w1[u], acc);
     }
   } else {
     // 64-deep steps, lane holds k = 16*lg .. 16*lg+15 (32 contiguous bytes); wave w owns the contiguous K quarter
@@ -144,6 +185,7 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_kernel(const bf16_t* __restri
         float v = 0.f;
 #pragma unroll
         for (int w = 0; w < GV_NW; ++w) v += red[w][m * 16 + lr];
+        if constexpr (F8) v *= wscale[n];              // the row scale s_n first, then alpha
         v *= alpha;
         if (bias) v += bias[n];
         if (res) v += res[(size_t)m * ldr + n];
@@ -221,22 +263,114 @@ extern "C" int mh_gemv_pack(const void* W, int ldb, int N, int K, void* out, hip
   return MH_OK;
 }
 
-// C[M <= 16, N] = alpha * A . W^T (+bias) (+residual) with W given as its mh_gemv_pack copy
-extern "C" int mh_gemv_packed(const void* A, int lda, const void* P, void* C, int ldc, int M, int N, int K, const float* bias,
-                              const float* residual, int ldr, int out_f32, float alpha, hipStream_t stream) {
+// weights in flight per lane per batch: 8 steps of the bf16 copy (16 KiB per wave), 16 of the fp8 copy (the same 16 KiB)
+template <typename WT> struct GvUnroll { static constexpr int value = sizeof(WT) == 1 ? 16 : 8; };
+
+template <typename WT>
+static int launch_gemv_packed(const void* A, int lda, const void* P, const float* wscale, void* C, int ldc, int M, int N, int K,
+                              const float* bias, const float* residual, int ldr, int out_f32, float alpha, hipStream_t stream) {
   if (M <= 0 || N <= 0) return MH_OK;
   if (M > 16 || K <= 0 || (K % 64) != 0 || (lda % 8) != 0 || ((uintptr_t)A & 15) || ((uintptr_t)P & 15)) return MH_ERR_ARG;
+  constexpr int U = GvUnroll<WT>::value;
   const dim3 grid((N + 15) / 16);
   if (gv_packed_nw(N) == 8)
-    hipLaunchKernelGGL((gemv_kernel<2, 8, 8>), grid, dim3(512), 0, stream, (const bf16_t*)A, (const bf16_t*)P, C, bias, residual, M,
-                       N, K, lda, 0, ldc, ldr, out_f32, alpha);
+    hipLaunchKernelGGL((gemv_kernel<2, U, 8, WT>), grid, dim3(512), 0, stream, (const bf16_t*)A, (const WT*)P, C, bias, residual, M,
+                       N, K, lda, 0, ldc, ldr, out_f32, alpha, wscale);
   else
-    hipLaunchKernelGGL((gemv_kernel<2, 8, 4>), grid, dim3(256), 0, stream, (const bf16_t*)A, (const bf16_t*)P, C, bias, residual, M,
-                       N, K, lda, 0, ldc, ldr, out_f32, alpha);
+    hipLaunchKernelGGL((gemv_kernel<2, U, 4, WT>), grid, dim3(256), 0, stream, (const bf16_t*)A, (const WT*)P, C, bias, residual, M,
+                       N, K, lda, 0, ldc, ldr, out_f32, alpha, wscale);
   MH_CHECK_LAUNCH();
   return MH_OK;
 }
 
+// C[M <= 16, N] = alpha * A . W^T (+bias) (+residual) with W given as its mh_gemv_pack copy
+extern "C" int mh_gemv_packed(const void* A, int lda, const void* P, void* C, int ldc, int M, int N, int K, const float* bias,
+                              const float* residual, int ldr, int out_f32, float alpha, hipStream_t stream) {
+  return launch_gemv_packed<bf16_t>(A, lda, P, nullptr, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream);
+}
+
+// ---- fp8 (e4m3fn) weight-only copy: row scale, quantisation and the stream order in one kernel ----------------------------
+// q [N, K] e4m3fn in mh_gemv_pack's order at one byte per weight: lane (lr, lg) of wave w reads at step t the 16 codes
+// k = 64 t' + 16 lg .. +15 (t' = w * per + t) of row 16 * block + lr at ((block * NW + w) * per + t) * 1 KiB + lane * 16.
+// One workgroup per 16-row block: the 16 threads of a row find amax_n, then s_n = amax_n / 448 (fp32, correctly rounded;
+// 1 for an all-zero row) and q = e4m3fn(clamp(W / s_n, -448, 448)) rounded to nearest even -- torch's
+// (W.float() / s[:, None]).clamp(-448, 448).to(torch.float8_e4m3fn), bit for bit.  Rows past N repeat row N - 1 (as the bf16
+// copy); their results are never stored.
+__device__ __forceinline__ unsigned f32_to_e4m3fn(float x) {        // |x| <= 448, not NaN
+  const unsigned u = __float_as_uint(x), sign = (u >> 24) & 0x80u, a = u & 0x7fffffffu;
+  if (a < 0x3c800000u)                                              // |x| < 2^-6: subnormal codes m * 2^-9 (m = 8 is 2^-6)
+    return sign | (unsigned)rintf(__uint_as_float(a) * 512.f);      // exact scaling, rintf rounds half to even
+  const unsigned r = (a + 0x7ffffu + ((a >> 20) & 1u)) >> 20;       // 3 mantissa bits, half to even (a carry bumps the exponent)
+  return sign | (r - (120u << 3));                                  // rebias 127 -> 7
+}
+
+__global__ __launch_bounds__(256) void gemv_pack_fp8_kernel(const bf16_t* __restrict__ W, int ldb, int N, int K,
+                                                            unsigned char* __restrict__ out, float* __restrict__ scale_out, int nw,
+                                                            int per) {
+  __shared__ float srow[16];
+  const int tid = threadIdx.x, nb = blockIdx.x;
+  {
+    const int lr = tid >> 4, j = tid & 15;
+    int row = nb * 16 + lr;
+    row = row < N ? row : N - 1;
+    float amax = 0.f;
+    for (int k = j * 8; k < K; k += 128) {
+      const short8_t v = *reinterpret_cast<const short8_t*>(W + (size_t)row * ldb + k);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(bf2f((bf16_t)v[e])));
+    }
+#pragma unroll
+    for (int o = 8; o >= 1; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));   // the 16 lanes of one row
+    if (j == 0) {
+      const float sc = amax > 0.f ? amax / 448.0f : 1.0f;
+      srow[lr] = sc;
+      if (nb * 16 + lr < N) scale_out[nb * 16 + lr] = sc;
+    }
+  }
+  __syncthreads();
+  const int nsteps = K / 64, chunks = nw * per * 64;
+  for (int c = tid; c < chunks; c += 256) {
+    const int lane = c & 63, r = c >> 6;
+    const int t = r % per, q = r / per;
+    const int lr = lane & 15, lg = lane >> 4;
+    int row = nb * 16 + lr;
+    row = row < N ? row : N - 1;
+    const int step = q * per + t;
+    gv_u4_t o = {0u, 0u, 0u, 0u};
+    if (step < nsteps) {
+      const bf16_t* src = W + (size_t)row * ldb + step * 64 + lg * 16;
+      const short8_t v0 = *reinterpret_cast<const short8_t*>(src), v1 = *reinterpret_cast<const short8_t*>(src + 8);
+      const float sc = srow[lr];
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const float w = bf2f((bf16_t)(e < 8 ? v0[e] : v1[e - 8]));
+        const float x = fminf(fmaxf(w / sc, -448.f), 448.f);
+        o[e >> 2] |= f32_to_e4m3fn(x) << (8 * (e & 3));
+      }
+    }
+    *reinterpret_cast<gv_u4_t*>(out + ((size_t)nb * chunks + c) * 16) = o;
+  }
+}
+
+extern "C" long mh_gemv_pack_fp8_elems(int N, int K) { return mh_gemv_pack_elems(N, K); }   // bytes: one per bf16 element
+
+extern "C" int mh_gemv_pack_fp8(const void* W, int ldb, int N, int K, void* q_out, float* scale_out, hipStream_t stream) {
+  if (N <= 0 || K <= 0 || (K % 64) != 0 || (ldb % 8) != 0 || ldb < K || !scale_out || ((uintptr_t)W & 15) || ((uintptr_t)q_out & 15) ||
+      ((uintptr_t)scale_out & 3))
+    return MH_ERR_ARG;
+  const int nw = gv_packed_nw(N), per = (K / 64 + nw - 1) / nw;
+  hipLaunchKernelGGL(gemv_pack_fp8_kernel, dim3((N + 15) / 16), dim3(256), 0, stream, (const bf16_t*)W, ldb, N, K, (unsigned char*)q_out,
+                     scale_out, nw, per);
+  MH_CHECK_LAUNCH();
+  return MH_OK;
+}
+
+// C[M <= 16, N] = alpha * s_n * A . q^T (+bias) (+residual) with W given as its mh_gemv_pack_fp8 copy (q, s)
+extern "C" int mh_gemv_packed_fp8(const void* A, int lda, const void* Q, const float* scale, void* C, int ldc, int M, int N, int K,
+                                  const float* bias, const float* residual, int ldr, int out_f32, float alpha, hipStream_t stream) {
+  if (M > 0 && N > 0 && (!scale || ((uintptr_t)scale & 3))) return MH_ERR_ARG;
+  return launch_gemv_packed<fp8_t>(A, lda, Q, scale, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream);
+}
 
 // ---- decode GEMV with the producer of its activation operand fused in (one launch instead of two per Linear) ---------------
 // The single-token step runs ~290 launches of 3-25 us; the RMSNorm in front of the qkv / gate|up / lm_head products and the
@@ -248,11 +382,13 @@ extern "C" int mh_gemv_packed(const void* A, int lda, const void* P, void* C, in
 //   PRO 2 (RMSNorm, modeling_llama.py:66-74): A = h [M, K] f32; operand = bf16(w * (h * rsqrt(mean(h^2) + eps))): the first
 //          256 threads sum the squares in rmsnorm_fwd_kernel's order (thread t: elements 4t + 1024 j) and the block reduction
 //          adds the same four wave sums first, so the scale and every operand element carry the same bits.
-template <int UNROLL, int GV_NW, int PRO>
-__global__ __launch_bounds__(GV_NW * 64) void gemv_pro_kernel(const void* __restrict__ Ain, long lda, const bf16_t* __restrict__ B,
+template <int UNROLL, int GV_NW, int PRO, typename WT = bf16_t>
+__global__ __launch_bounds__(GV_NW * 64) void gemv_pro_kernel(const void* __restrict__ Ain, long lda, const WT* __restrict__ B,
                                                               void* __restrict__ Cv, const float* __restrict__ bias, const float* res,
                                                               int M, int N, int K, int ldc, int ldr, int out_f32, float alpha,
-                                                              const float* __restrict__ norm_w, float eps) {
+                                                              const float* __restrict__ norm_w, float eps,
+                                                              const float* __restrict__ wscale = nullptr) {
+  constexpr bool F8 = sizeof(WT) == 1;
   extern __shared__ __attribute__((aligned(16))) char gsm[];
   bf16_t* xs = reinterpret_cast<bf16_t*>(gsm);                  // [M][K] operand rows
   __shared__ float red[GV_NW][16 * 16];
@@ -262,7 +398,7 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_pro_kernel(const void* __rest
   const int n0 = blockIdx.x * 16;
   const int nsteps = K / 64;
   const int per = (nsteps + GV_NW - 1) / GV_NW;
-  const bf16_t* wp = B + ((size_t)blockIdx.x * GV_NW + wave) * per * 1024 + lane * 8;
+  const WT* wp = B + ((size_t)blockIdx.x * GV_NW + wave) * per * 1024 + lane * (16 / sizeof(WT));
   // The weight stream does not depend on the operand: the first UNROLL steps of it are put in flight BEFORE the rows are
   // built (every workgroup of a launch starts at the same time; without this the HBM pipe idles for the ~3 us the prologue
   // takes).  Vector loads retire in order, so what the prologue needs first -- the fp32 row and the norm weights -- is
@@ -280,10 +416,7 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_pro_kernel(const void* __rest
   }
   if (have) {
 #pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      w0[u] = __builtin_nontemporal_load(reinterpret_cast<const short8_t*>(wp + (size_t)u * 1024));
-      w1[u] = __builtin_nontemporal_load(reinterpret_cast<const short8_t*>(wp + (size_t)u * 1024 + 512));
-    }
+    for (int u = 0; u < UNROLL; ++u) gv_load(wp, (size_t)u, w0[u], w1[u]);
   }
   if (PRO == 1) {
     const bf16_t* gu = reinterpret_cast<const bf16_t*>(Ain);
@@ -334,17 +467,13 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_pro_kernel(const void* __rest
     for (int u = 0; u < UNROLL; ++u) {
       const int k = (s + u) * 64;
       const short8_t x0 = *reinterpret_cast<const short8_t*>(xp + k), x1 = *reinterpret_cast<const short8_t*>(xp + k + 8);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x0, w0[u], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1, w1[u], acc, 0, 0, 0);
+      acc = gv_mfma<WT>(x0, x1, w0[u], w1[u], acc);
     }
     s += UNROLL;
     have = s + UNROLL <= s_end;
     if (have) {
 #pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        w0[u] = __builtin_nontemporal_load(reinterpret_cast<const short8_t*>(wp + (size_t)(s - s0 + u) * 1024));
-        w1[u] = __builtin_nontemporal_load(reinterpret_cast<const short8_t*>(wp + (size_t)(s - s0 + u) * 1024 + 512));
-      }
+      for (int u = 0; u < UNROLL; ++u) gv_load(wp, (size_t)(s - s0 + u), w0[u], w1[u]);
     }
   }
   if (s < s_end) {
@@ -353,17 +482,13 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_pro_kernel(const void* __rest
     const int rem = s_end - s;
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u)
-      if (u < rem) {
-        w0[u] = __builtin_nontemporal_load(reinterpret_cast<const short8_t*>(wp + (size_t)(s - s0 + u) * 1024));
-        w1[u] = __builtin_nontemporal_load(reinterpret_cast<const short8_t*>(wp + (size_t)(s - s0 + u) * 1024 + 512));
-      }
+      if (u < rem) gv_load(wp, (size_t)(s - s0 + u), w0[u], w1[u]);
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u)
       if (u < rem) {
         const int k = (s + u) * 64;
         const short8_t x0 = *reinterpret_cast<const short8_t*>(xp + k), x1 = *reinterpret_cast<const short8_t*>(xp + k + 8);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x0, w0[u], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1, w1[u], acc, 0, 0, 0);
+        acc = gv_mfma<WT>(x0, x1, w0[u], w1[u], acc);
       }
   }
 #pragma unroll
@@ -377,6 +502,7 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_pro_kernel(const void* __rest
         float v = 0.f;
 #pragma unroll
         for (int w = 0; w < GV_NW; ++w) v += red[w][m * 16 + lr];
+        if constexpr (F8) v *= wscale[n];              // the row scale s_n first, then alpha
         v *= alpha;
         if (bias) v += bias[n];
         if (res) v += res[(size_t)m * ldr + n];
@@ -389,12 +515,13 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_pro_kernel(const void* __rest
 
 #define GV_PRO_LDS_MAX (64 * 1024)
 #define GV_PRO_MAX_ROWS 2
-template <int PRO>
+template <int PRO, typename WT = bf16_t>
 static int launch_gemv_pro(const void* A, long lda, const void* P, void* C, int ldc, int M, int N, int K, const float* bias,
                            const float* residual, int ldr, int out_f32, float alpha, const float* norm_w, float eps,
-                           hipStream_t stream) {
+                           hipStream_t stream, const float* wscale = nullptr) {
   if (M <= 0 || N <= 0) return MH_OK;
   if (M > 16 || K <= 0 || (K % 64) != 0 || ((uintptr_t)A & 15) || ((uintptr_t)P & 15)) return MH_ERR_ARG;
+  if (sizeof(WT) == 1 && (!wscale || ((uintptr_t)wscale & 3))) return MH_ERR_ARG;
   if (PRO == 1 && ((K % 128) != 0 || (lda % 8) != 0 || lda < 2L * K)) return MH_ERR_ARG;
   if (PRO == 2 && (!norm_w || (K % 4) != 0 || (lda % 4) != 0)) return MH_ERR_ARG;
   if (PRO == 2 && K > 4096) return MH_ERR_UNSUPPORTED;
@@ -402,16 +529,17 @@ static int launch_gemv_pro(const void* A, long lda, const void* P, void* C, int 
   // every workgroup rebuilds all M rows: measured at batch 8 (decode, M = 8) the fused step costs 6.5 ms per token against
   // 4.1 ms with the separate launches, at batch 1 it saves 0.3 ms -- fused for up to GV_PRO_MAX_ROWS rows only
   if (sh > GV_PRO_LDS_MAX || M > GV_PRO_MAX_ROWS) return MH_ERR_UNSUPPORTED;        // the caller falls back to the two-launch form
+  constexpr int U = GvUnroll<WT>::value;
   const dim3 grid((N + 15) / 16);
   static bool attr8 = false, attr4 = false;                   // once per instantiation, outside any stream capture
   if (gv_packed_nw(N) == 8) {
-    if (!attr8) { (void)hipFuncSetAttribute((const void*)gemv_pro_kernel<8, 8, PRO>, hipFuncAttributeMaxDynamicSharedMemorySize, GV_PRO_LDS_MAX); attr8 = true; }
-    hipLaunchKernelGGL((gemv_pro_kernel<8, 8, PRO>), grid, dim3(512), sh, stream, A, lda, (const bf16_t*)P, C, bias, residual, M, N, K,
-                       ldc, ldr, out_f32, alpha, norm_w, eps);
+    if (!attr8) { (void)hipFuncSetAttribute((const void*)gemv_pro_kernel<U, 8, PRO, WT>, hipFuncAttributeMaxDynamicSharedMemorySize, GV_PRO_LDS_MAX); attr8 = true; }
+    hipLaunchKernelGGL((gemv_pro_kernel<U, 8, PRO, WT>), grid, dim3(512), sh, stream, A, lda, (const WT*)P, C, bias, residual, M, N, K,
+                       ldc, ldr, out_f32, alpha, norm_w, eps, wscale);
   } else {
-    if (!attr4) { (void)hipFuncSetAttribute((const void*)gemv_pro_kernel<8, 4, PRO>, hipFuncAttributeMaxDynamicSharedMemorySize, GV_PRO_LDS_MAX); attr4 = true; }
-    hipLaunchKernelGGL((gemv_pro_kernel<8, 4, PRO>), grid, dim3(256), sh, stream, A, lda, (const bf16_t*)P, C, bias, residual, M, N, K,
-                       ldc, ldr, out_f32, alpha, norm_w, eps);
+    if (!attr4) { (void)hipFuncSetAttribute((const void*)gemv_pro_kernel<U, 4, PRO, WT>, hipFuncAttributeMaxDynamicSharedMemorySize, GV_PRO_LDS_MAX); attr4 = true; }
+    hipLaunchKernelGGL((gemv_pro_kernel<U, 4, PRO, WT>), grid, dim3(256), sh, stream, A, lda, (const WT*)P, C, bias, residual, M, N, K,
+                       ldc, ldr, out_f32, alpha, norm_w, eps, wscale);
   }
   MH_CHECK_LAUNCH();
   return MH_OK;
@@ -429,4 +557,17 @@ extern "C" int mh_gemv_packed_rmsnorm(const float* H, long ldh, const float* nor
 extern "C" int mh_gemv_packed_silu(const void* gu, long ldgu, const void* P, void* C, int ldc, int M, int N, int K,
                                    const float* bias, const float* residual, int ldr, int out_f32, float alpha, hipStream_t stream) {
   return launch_gemv_pro<1>(gu, ldgu, P, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, nullptr, 0.f, stream);
+}
+
+// the two fused forms on the fp8 copy (q, s): the same prologues, the same contract
+extern "C" int mh_gemv_packed_fp8_rmsnorm(const float* H, long ldh, const float* norm_w, float eps, const void* Q, const float* scale,
+                                          void* C, int ldc, int M, int N, int K, const float* bias, const float* residual, int ldr,
+                                          int out_f32, float alpha, hipStream_t stream) {
+  return launch_gemv_pro<2, fp8_t>(H, ldh, Q, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, norm_w, eps, stream, scale);
+}
+
+extern "C" int mh_gemv_packed_fp8_silu(const void* gu, long ldgu, const void* Q, const float* scale, void* C, int ldc, int M, int N,
+                                       int K, const float* bias, const float* residual, int ldr, int out_f32, float alpha,
+                                       hipStream_t stream) {
+  return launch_gemv_pro<1, fp8_t>(gu, ldgu, Q, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, nullptr, 0.f, stream, scale);
 }

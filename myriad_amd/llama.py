@@ -32,6 +32,11 @@ def _f32(t: torch.Tensor, dev) -> torch.Tensor:
     return t.detach().to(device=dev, dtype=F32).contiguous()
 
 
+def decode_fp8_from_env() -> bool:
+    """The default of LlamaHIP.decode_fp8: MYRIAD_DECODE_FP8=1 turns the FP8 weight-only token step on (off when unset)."""
+    return os.environ.get("MYRIAD_DECODE_FP8", "0") != "0"
+
+
 class LlamaHIP:
     def __init__(self, sd: Dict[str, torch.Tensor], n_heads: int, device, eps: float = 1e-6,
                  prefix: str = "llama_model.", max_pos: int = 2048, need_backward: bool = True):
@@ -95,20 +100,47 @@ class LlamaHIP:
         # off by default until it has been measured against the host draw (tools/decode_bench.py --sample)
         self.device_sampling = os.environ.get("MYRIAD_DEVICE_SAMPLING", "0") != "0"
         self.last_layer_rows = os.environ.get("MYRIAD_LAST_LAYER_ROWS", "1") != "0"
-        self._packed = None
+        # the packed token step streams FP8 (e4m3fn, one fp32 scale per output row) copies of the decoder matrices instead of
+        # the bf16 ones (ops.gemv_pack_fp8; half the bytes, weight rounding the only new error); off by default, the attribute
+        # wins over MYRIAD_DECODE_FP8
+        self.decode_fp8 = decode_fp8_from_env()
+        self._packed = None                                             # the packed copies of the current kind (one of _packs)
+        self._packs = {}                                                # "bf16" / "fp8" -> packed copies, each built on first use
         self._decode_ws = {}
 
     def _pack_for_decode(self) -> None:
         """(Re)build the packed copies the single-token step streams.  Frozen matrices are packed once; the bordered qkv
-        weight carries the LoRA B columns, which training moves, so it is re-packed (in place) at every generate()."""
+        weight carries the LoRA B columns, which training moves, so it is re-packed (in place) at every generate().
+        With decode_fp8 the decoder matrices wo, wgu, wd -- and wqkv while no LoRA is attached -- are fp8 copies
+        (ops.gemv_pack_fp8) in place of the bf16 ones; the bordered wqkv_ext (one row scale would be shared by W and the moving
+        B columns) and lm_head (its arg-max picks the ids) stay bf16.  Each kind is built on its first use and kept, so flipping
+        the switch between calls works, and the workspace key holds the kind: no graph captured on one is replayed on the other."""
+        kind = "fp8" if self.decode_fp8 else "bf16"
         qkv_key = "wqkv" if self.lora is None else "wqkv_ext"
-        if self._packed is None:
-            self._packed = dict(layers=[{k: ops.gemv_pack(L[k]) for k in ("wo", "wgu", "wd")} for L in self.layers],
-                                lm_head=ops.gemv_pack(self.lm_head), qkv_key=None)
-        if self._packed["qkv_key"] != qkv_key or self.lora is not None:
-            for L, P in zip(self.layers, self._packed["layers"]):
-                P["wqkv"] = ops.gemv_pack(L[qkv_key], out=P.get("wqkv") if self._packed["qkv_key"] == qkv_key else None)
-            self._packed["qkv_key"] = qkv_key
+        P = self._packs.get(kind)
+        if P is None:
+            pack = ops.gemv_pack_fp8 if kind == "fp8" else ops.gemv_pack
+            lm = next(iter(self._packs.values()))["lm_head"] if self._packs else ops.gemv_pack(self.lm_head)
+            P = dict(kind=kind, layers=[{k: pack(L[k]) for k in ("wo", "wgu", "wd")} for L in self.layers], lm_head=lm, qkv_key=None)
+            self._packs[kind] = P
+        if P["qkv_key"] != qkv_key or self.lora is not None:
+            pack = ops.gemv_pack_fp8 if kind == "fp8" and self.lora is None else ops.gemv_pack
+            for L, Pl in zip(self.layers, P["layers"]):
+                Pl["wqkv"] = pack(L[qkv_key], out=Pl.get("wqkv") if P["qkv_key"] == qkv_key else None)
+            P["qkv_key"] = qkv_key
+        self._packed = P
+
+    def _decode_weight_stats(self, rows: int) -> dict:
+        """last_generate_stats' decode_weights ("fp8" / "bf16": what the token step streams) and decode_weight_bytes (the weight
+        bytes of one token step: the packed copies, fp8 scales included, up to 16 rows; the row-major bf16 matrices above)."""
+        if self._packed is not None and rows <= 16:
+            mats = [P[k] for P in self._packed["layers"] for k in ("wqkv", "wo", "wgu", "wd")] + [self._packed["lm_head"]]
+            nbytes = sum(m.data.numel() * m.data.element_size() + (m.scales.numel() * 4 if isinstance(m, ops.PackedFp8Weight) else 0)
+                         for m in mats)
+            return dict(decode_weights=self._packed["kind"], decode_weight_bytes=int(nbytes))
+        qkv_key = "wqkv" if self.lora is None else "wqkv_ext"
+        mats = [L[k] for L in self.layers for k in (qkv_key, "wo", "wgu", "wd")] + [self.lm_head]
+        return dict(decode_weights="bf16", decode_weight_bytes=int(sum(m.numel() * m.element_size() for m in mats)))
 
     def attach_lora(self, lora) -> None:
         """Enable PEFT-style LoRA on q_proj/v_proj (myriad_amd.lora.LoraQV); replaces W_qkv by its bordered copy."""
@@ -372,7 +404,7 @@ class LlamaHIP:
         device table of the per-layer cache pointers that mh_beam_reorder_kv walks."""
         T_cap = ops.round_up(T_need + 2, 64)
         key = (B, T_cap, None if dev_sample else float(inv_temp), id(self._packed),
-               None if self._packed is None else self._packed.get("qkv_key"), self.decode_fused, self.lora is not None,
+               None if self._packed is None else (self._packed["kind"], self._packed["qkv_key"]), self.decode_fused, self.lora is not None,
                bool(dev_sample), bool(penalty), int(num_beams))
         ws = self._decode_ws.get(key)
         if ws is None:
@@ -455,7 +487,8 @@ class LlamaHIP:
         if self.pack_decode and B <= 16:
             self._pack_for_decode()
         elif not self.pack_decode:
-            self._packed = None                                      # MYRIAD_PACK_DECODE=0: stream the row-major matrices
+            self._packed, self._packs = None, {}                     # MYRIAD_PACK_DECODE=0: stream the row-major matrices
+        stats.update(self._decode_weight_stats(B))
         ws = self._decode_workspace(B, S0 + max_new_tokens, inv_temp, dev_sample, penalty)
         caches = ws["caches"]
         if dev_sample or penalty:
@@ -626,7 +659,8 @@ class LlamaHIP:
         if self.pack_decode and R <= 16:
             self._pack_for_decode()
         elif not self.pack_decode:
-            self._packed = None
+            self._packed, self._packs = None, {}
+        stats.update(self._decode_weight_stats(R))
         ws = self._decode_workspace(R, S0 + max_new_tokens, 1.0, num_beams=nb)
         caches, T_cap, C = ws["caches"], ws["T"], 2 * self.D
         dev = self.dev

@@ -198,9 +198,36 @@ def gemv_pack(w: torch.Tensor, out: Optional[PackedWeight] = None) -> PackedWeig
     return out
 
 
-def gemv_packed(a: torch.Tensor, pw: PackedWeight, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+class PackedFp8Weight:
+    """FP8 weight-only copy of a frozen [N, K] bf16 weight for the decode kernel (mh_gemv_pack_fp8): e4m3fn codes in the stream
+    order of PackedWeight at one byte per weight (`data`, uint8) and one fp32 scale per output row (`scales` [N])."""
+    __slots__ = ("data", "scales", "N", "K")
+
+    def __init__(self, data: torch.Tensor, scales: torch.Tensor, N: int, K: int):
+        self.data, self.scales, self.N, self.K = data, scales, N, K
+
+
+def gemv_pack_fp8(w: torch.Tensor, out: Optional[PackedFp8Weight] = None) -> PackedFp8Weight:
+    """Quantise w [N, K] per output row (s_n = amax_n / 448, q = e4m3fn(w / s_n), nearest even, saturated) and permute q into the
+    order the skinny-M kernel streams it in; `out` re-uses an earlier copy's storage."""
+    _chk2d(w, BF16, "gemv_pack_fp8.w")
+    N, K = w.shape
+    n = _L().mh_gemv_pack_fp8_elems(N, K)
+    if n < 0:
+        raise _lib.MyriadHipError(f"gemv_pack_fp8: unsupported dims N={N} K={K}")
+    if out is None:
+        out = PackedFp8Weight(torch.empty((n,), dtype=torch.uint8, device=w.device), torch.empty((N,), dtype=F32, device=w.device),
+                              N, K)
+    elif (out.N, out.K) != (N, K):
+        raise _lib.MyriadHipError("gemv_pack_fp8: out was packed for another shape")
+    _lib.check(_L().mh_gemv_pack_fp8(_p(w), w.stride(0), N, K, _p(out.data), _p(out.scales), _s()), "mh_gemv_pack_fp8")
+    return out
+
+
+def gemv_packed(a: torch.Tensor, pw, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
                 residual: Optional[torch.Tensor] = None, out_dtype=BF16, alpha: float = 1.0) -> torch.Tensor:
-    """out[M<=16, N] = alpha * a @ W^T (+bias) (+residual f32) with W given as its packed copy; same bits as gemm()."""
+    """out[M<=16, N] = alpha * a @ W^T (+bias) (+residual f32) with W given as its packed copy; same bits as gemm().
+    A PackedFp8Weight runs the fp8 kernel: alpha * s_n * a @ q^T, q widened exactly to bf16."""
     _chk2d(a, BF16, "gemv_packed.a")
     M, K = a.shape
     if K != pw.K or M > 16:
@@ -211,6 +238,11 @@ def gemv_packed(a: torch.Tensor, pw: PackedWeight, out: Optional[torch.Tensor] =
     if residual is not None:
         _chk2d(residual, F32, "gemv_packed.residual")
         ldr = residual.stride(0)
+    if isinstance(pw, PackedFp8Weight):
+        rc = _L().mh_gemv_packed_fp8(_p(a), a.stride(0), _p(pw.data), _p(pw.scales), _p(out), out.stride(0), M, pw.N, K, _p(bias),
+                                     _p(residual), ldr, 1 if out.dtype == F32 else 0, float(alpha), _s())
+        _lib.check(rc, f"mh_gemv_packed_fp8 M={M} N={pw.N} K={K}")
+        return out
     rc = _L().mh_gemv_packed(_p(a), a.stride(0), _p(pw.data), _p(out), out.stride(0), M, pw.N, K, _p(bias), _p(residual), ldr,
                              1 if out.dtype == F32 else 0, float(alpha), _s())
     _lib.check(rc, f"mh_gemv_packed M={M} N={pw.N} K={K}")
@@ -224,7 +256,8 @@ def _gemv_pro(fn, name, a, lda, pw, out, residual, out_dtype, alpha, M, *pre):
     if residual is not None:
         _chk2d(residual, F32, name + ".residual")
         ldr = residual.stride(0)
-    rc = fn(_p(a), lda, *pre, _p(pw.data), _p(out), out.stride(0), M, pw.N, pw.K, None, _p(residual), ldr,
+    wargs = (_p(pw.data), _p(pw.scales)) if isinstance(pw, PackedFp8Weight) else (_p(pw.data),)
+    rc = fn(_p(a), lda, *pre, *wargs, _p(out), out.stride(0), M, pw.N, pw.K, None, _p(residual), ldr,
             1 if out.dtype == F32 else 0, float(alpha), _s())
     if rc == -3:                                   # MH_ERR_UNSUPPORTED: the operand rows do not fit the kernel's LDS budget
         return None
@@ -232,7 +265,7 @@ def _gemv_pro(fn, name, a, lda, pw, out, residual, out_dtype, alpha, M, *pre):
     return out
 
 
-def gemv_packed_rmsnorm(h: torch.Tensor, norm_w: torch.Tensor, eps: float, pw: PackedWeight, out=None, residual=None,
+def gemv_packed_rmsnorm(h: torch.Tensor, norm_w: torch.Tensor, eps: float, pw, out=None, residual=None,
                         out_dtype=BF16, alpha: float = 1.0):
     """out[M<=16, N] = alpha * rmsnorm(h; norm_w, eps) @ W^T (+residual): mh_rmsnorm_fwd + mh_gemv_packed in one launch, same bits.
     Returns None when the operand rows exceed the fused kernel's LDS budget (run the two launches instead)."""
@@ -240,18 +273,19 @@ def gemv_packed_rmsnorm(h: torch.Tensor, norm_w: torch.Tensor, eps: float, pw: P
     M, K = h.shape
     if K != pw.K or M > 16:
         raise _lib.MyriadHipError(f"gemv_packed_rmsnorm: h is {tuple(h.shape)}, weight was packed as [{pw.N}, {pw.K}]")
-    return _gemv_pro(_L().mh_gemv_packed_rmsnorm, "mh_gemv_packed_rmsnorm", h, h.stride(0), pw, out, residual, out_dtype, alpha, M,
-                     _p(norm_w), float(eps))
+    name = "mh_gemv_packed_fp8_rmsnorm" if isinstance(pw, PackedFp8Weight) else "mh_gemv_packed_rmsnorm"
+    return _gemv_pro(getattr(_L(), name), name, h, h.stride(0), pw, out, residual, out_dtype, alpha, M, _p(norm_w), float(eps))
 
 
-def gemv_packed_silu(gu: torch.Tensor, pw: PackedWeight, out=None, residual=None, out_dtype=BF16, alpha: float = 1.0):
+def gemv_packed_silu(gu: torch.Tensor, pw, out=None, residual=None, out_dtype=BF16, alpha: float = 1.0):
     """out[M<=16, N] = alpha * (silu(g) * u) @ W^T (+residual) for gu [M, 2K] bf16 in the 128-blocked gate|up layout:
     mh_silu_mul_fwd_blk + mh_gemv_packed in one launch, same bits.  None when the rows exceed the LDS budget."""
     _chk2d(gu, BF16, "gemv_packed_silu.gu")
     M = gu.shape[0]
     if gu.shape[1] != 2 * pw.K or M > 16:
         raise _lib.MyriadHipError(f"gemv_packed_silu: gu is {tuple(gu.shape)}, weight was packed as [{pw.N}, {pw.K}]")
-    return _gemv_pro(_L().mh_gemv_packed_silu, "mh_gemv_packed_silu", gu, gu.stride(0), pw, out, residual, out_dtype, alpha, M)
+    name = "mh_gemv_packed_fp8_silu" if isinstance(pw, PackedFp8Weight) else "mh_gemv_packed_silu"
+    return _gemv_pro(getattr(_L(), name), name, gu, gu.stride(0), pw, out, residual, out_dtype, alpha, M)
 
 
 def attn_decode_rope(qkv2d: torch.Tensor, cache: torch.Tensor, pos: torch.Tensor, pos_dev: torch.Tensor, kv_len: torch.Tensor,

@@ -4,7 +4,8 @@ python tools/decode_bench.py [--batch 1] [--new 32] [--sample] [--penalty P] [--
 --sample: the chat call's do_sample=True, top_p=0.9, top_k=50 (drawn on the device when MYRIAD_DEVICE_SAMPLING=1, else on the
 host); --modes times several decodes in one process, interleaved per repeat: greedy, host (sampled, host draw), device (sampled,
 device draw), beam (num_beams = --beams, which also times greedy at batch * beams: the same row count); --penalty adds
-repetition_penalty to every mode but beam."""
+repetition_penalty to every mode but beam.  --weights bf16,fp8 times each mode with the token step streaming bf16 and FP8 weight
+copies (LlamaHIP.decode_fp8), interleaved in the same way; without it the kind is MYRIAD_DECODE_FP8's."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -21,10 +22,13 @@ ap.add_argument("--penalty", type=float, default=1.0, help="repetition_penalty")
 ap.add_argument("--modes", default="", help="comma list of greedy / host / device, timed interleaved in one process")
 ap.add_argument("--repeats", type=int, default=1)
 ap.add_argument("--beams", type=int, default=4, help="num_beams of the beam mode")
+ap.add_argument("--weights", default="", help="comma list of bf16 / fp8: the token step's weight copies, timed interleaved")
 a = ap.parse_args()
 modes = [m for m in a.modes.split(",") if m] or ["sample" if a.sample else "greedy"]
 if "beam" in modes and "greedy" in modes:
     modes.append("greedy_x%d" % a.beams)             # greedy at batch * beams rows: the beam step's row count
+kinds = [w for w in a.weights.split(",") if w] or [None]
+assert all(w in (None, "bf16", "fp8") for w in kinds), kinds
 dev = "cuda:0"
 cfg = full_config(llm_layers=a.llm_layers)
 model = MyriadHIP(SyntheticWeights(cfg, dev, seed=0), dict(need_backward=False, use_lora=bool(a.lora)), device=dev)
@@ -42,9 +46,10 @@ def make_samples(n):
 smp = make_samples(B)
 smp_rows = make_samples(B * a.beams) if "beam" in modes else None
 default_dev = model.llama.device_sampling
+default_fp8 = model.llama.decode_fp8
 
 
-def run(n, mode):
+def run(n, mode, kind=None):
     kw, sm = {}, smp
     if mode == "beam":
         kw = dict(num_beams=a.beams, early_stopping="never")    # no early stop: every run decodes n tokens
@@ -55,6 +60,7 @@ def run(n, mode):
     if mode != "beam":
         kw["repetition_penalty"] = a.penalty
     model.llama.device_sampling = {"host": False, "device": True}.get(mode, default_dev)
+    model.llama.decode_fp8 = default_fp8 if kind is None else kind == "fp8"
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     out = model.generate(sm, max_new_tokens=n, stop_ids=((-1,),), min_length=0, eos_token_id=-5, **kw)
@@ -62,25 +68,28 @@ def run(n, mode):
     return time.perf_counter() - t0, out
 
 
-for m in modes:
-    run(2, m); run(6, m)                 # warm-up: kernels, then the token-step graph of this batch size is captured
-res = {m: [] for m in modes}
+runs = [(m, w) for m in modes for w in kinds]
+for m, w in runs:
+    run(2, m, w); run(6, m, w)           # warm-up: kernels, then the token-step graph of this batch size is captured
+res = {r: [] for r in runs}
 for _ in range(a.repeats):
-    for m in modes:
-        t_short, _ = run(a.new // 4, m)
-        t_long, out = run(a.new, m)
+    for m, w in runs:
+        t_short, _ = run(a.new // 4, m, w)
+        t_long, out = run(a.new, m, w)
         n_long, n_short = out["token_ids"].shape[1], a.new // 4
         if m == "beam":
             n_long = model.last_generate_stats["steps"]       # hypotheses may end before the last step; the step count does not
-        res[m].append(((t_long - t_short) / (n_long - n_short), t_long, n_long, dict(model.last_generate_stats)))
-for m in modes:
-    ts = sorted(r[0] for r in res[m])
-    per_tok, t_long, n_long, st = res[m][-1][0], res[m][-1][1], res[m][-1][2], res[m][-1][3]
+        res[(m, w)].append(((t_long - t_short) / (n_long - n_short), t_long, n_long, dict(model.last_generate_stats)))
+for m, w in runs:
+    ts = sorted(r[0] for r in res[(m, w)])
+    per_tok, t_long, n_long, st = res[(m, w)][-1]
     per_tok = ts[len(ts) // 2]                        # prefill / vision cancel: pure single-token decode steps (median)
     extra = (f" [{m}: device-drawn rows {st.get('device_sampled_rows', 0)}, host-drawn {st.get('host_sampled_rows', 0)}, "
              f"graph replays {st.get('graph_replays', 0)}]" if m != "greedy" or a.penalty != 1.0 else "")
     rows = B * a.beams if m in ("beam", "greedy_x%d" % a.beams) else B
-    print(f"batch {B} rows {rows}{' +LoRA' if a.lora else ''} {m}{f' penalty {a.penalty}' if a.penalty != 1.0 else ''}: {n_long} tokens in "
+    wb = st["decode_weight_bytes"]
+    print(f"batch {B} rows {rows}{' +LoRA' if a.lora else ''} {m} weights {st['decode_weights']}"
+          f"{f' penalty {a.penalty}' if a.penalty != 1.0 else ''}: {n_long} tokens in "
           f"{t_long*1e3:.1f} ms (incl. ViT+Q-Former+prefill); decode step {per_tok*1e3:.3f} ms/token (median of {len(ts)}, "
           f"min {ts[0]*1e3:.3f}, max {ts[-1]*1e3:.3f}) -> {rows / per_tok:.1f} row-tok/s steady; weight stream "
-          f"{13.2e9 / per_tok / 1e12:.2f} TB/s of 6.3 achievable{extra}")
+          f"{wb / 1e9:.2f} GB/token, {wb / per_tok / 1e12:.2f} TB/s of 6.3 achievable{extra}")
