@@ -345,6 +345,15 @@ int mh_gemv_packed_fp8_silu(const void* gu, long ldgu, const void* Q, const floa
 int mh_attn_decode_rope(void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
                         const int* pos_dev, const int* kv_len, const float* cos_tab, const float* sin_tab, void* out, long ldo,
                         int B, int H, int D, int T_cap, float scale, mh_stream_t s);
+/* The same token step with the keys split into chunks (attn_decode_split.hip): grid (ceil(T_cap / chunk), B*H), each workgroup
+ * scores one chunk and writes fp32 (m, l, o[D]) into `partials`, a second launch merges the chunks in order and writes bf16 out
+ * (bits fixed from run to run).  q is rotated in registers (qkv is not written); the cache row at pos_dev[0] gets the bits
+ * mh_attn_decode_rope writes.  chunk = 128, 256 or 512 keys (0 = 128); partials_floats >= mh_attn_decode_split_ws_floats(). */
+long mh_attn_decode_split_ws_floats(int B, int H, int T_cap, int chunk);
+int mh_attn_decode_rope_split(const void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
+                              const int* pos_dev, const int* kv_len, const float* cos_tab, const float* sin_tab, void* out, long ldo,
+                              float* partials, long partials_floats, int B, int H, int D, int T_cap, int chunk, float scale,
+                              mh_stream_t s);
 /* K14 patch embedding operand (eva_vit.py:196-204): NCHW f32 image -> [B*np, Kpad] bf16 in (c,iy,ix) order */
 int mh_patchify_nchw(const float* img, void* out, int B, int C, int H, int W, int P, int Kpad, mh_stream_t s);
 int mh_scatter_rows_f32(const float* src, const int* rows, float* dst, long ldd, long n, int D, int accumulate,

@@ -1,0 +1,290 @@
+"""Multi-turn chat about images: the reference's `minigpt4/conversation/conversation.py` (`SeparatorStyle`, `Conversation`,
+`CONV_VISION`, `StoppingCriteriaSub`, `Chat` with `upload_img` / `ask` / `answer`) on the HIP decode path, with the KV cache kept
+across turns.
+
+Kept from the reference: the prompt format (`Conversation.get_prompt`), `ask` merging a question into a trailing image message
+(conversation.py:137-142), the context built as `get_context_emb` builds it (the prompt split on `<ImageHere>`, each segment
+tokenized, BOS on the first segment only, image embeddings in between), the stop words (835; 2277 29937: '###' tokenizes two
+ways), the truncation window `begin_idx = max(0, len + max_new_tokens - max_length)`, and the answer's post-processing (a leading
+0 / 1 token stripped, the text cut at '###' and after the last 'Assistant:').
+
+Changed, because the reference's `Chat` does not match its own model's signatures (`prepare_sample(..., do_one_class=...)`,
+`encode_img(image, maps)` do not exist with those arguments): `upload_img` maps onto this project's model calls -- the anomaly maps
+come from `extras` or the attached vision expert through `MyriadHIP._maps_for`, as `generate()` gets them, and the image tokens
+from `encode_img(image, maps, stage=1)` (MiniGPT-4 arch: the image alone, stage 0).  Path and PIL inputs go through the GPU image
+front-end (Resize(224, bicubic) + CenterCrop(224) + CLIP normalisation, what the reference's transform + processor do) unless a
+`vis_processor` is given.  `answer` also takes `do_sample` and `generator` (the reference always samples), and returns
+`(text, token_ids)` like the reference.
+
+Reuse.  Each `Chat` owns a `myriad_amd.llama.DecodeSession`: turn n prefills only the part of the context past the longest common prefix
+with what the cache holds (positions named by token ids and (image, row) keys), then decodes on the session's own buffers and
+captured graph.  `Chat.last_stats` reports what a turn reused.  The session uses the split-KV decode attention kernel where it is
+measured faster (llama.split_kv_rule).  `num_beams > 1` runs the model's beam search (LlamaHIP.beam_generate) on the full context
+without reuse (deterministic: `do_sample` does not apply to it), and leaves the session's cache as it was.
+"""
+from __future__ import annotations
+
+import dataclasses
+import hashlib
+import warnings
+from enum import Enum, auto
+from typing import Any, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import ops
+from .llama import DecodeSession
+from .myriad import StoppingCriteriaSub
+
+__all__ = ["SeparatorStyle", "Conversation", "CONV_VISION", "StoppingCriteriaSub", "Chat", "truncation_begin", "postprocess_tokens",
+           "postprocess_text"]
+
+STOP_WORDS = ((835,), (2277, 29937))          # '###' can be encoded in two different ways (conversation.py:130-131)
+
+
+class SeparatorStyle(Enum):
+    """Different separator style."""
+    SINGLE = auto()
+    TWO = auto()
+
+
+@dataclasses.dataclass
+class Conversation:
+    """A class that keeps all conversation history."""
+    system: str
+    roles: List[str]
+    messages: List[List[str]]
+    offset: int
+    sep_style: SeparatorStyle = SeparatorStyle.SINGLE
+    sep: str = "###"
+    sep2: str = None
+
+    skip_next: bool = False
+    conv_id: Any = None
+
+    def get_prompt(self):
+        if self.sep_style == SeparatorStyle.SINGLE:
+            ret = self.system + self.sep
+            for role, message in self.messages:
+                if message:
+                    ret += role + ": " + message + self.sep
+                else:
+                    ret += role + ":"
+            return ret
+        if self.sep_style == SeparatorStyle.TWO:
+            seps = [self.sep, self.sep2]
+            ret = self.system + seps[0]
+            for i, (role, message) in enumerate(self.messages):
+                if message:
+                    ret += role + ": " + message + seps[i % 2]
+                else:
+                    ret += role + ":"
+            return ret
+        raise ValueError(f"Invalid style: {self.sep_style}")
+
+    def append_message(self, role, message):
+        self.messages.append([role, message])
+
+    def to_gradio_chatbot(self):
+        ret = []
+        for i, (role, msg) in enumerate(self.messages[self.offset:]):
+            if i % 2 == 0:
+                ret.append([msg, None])
+            else:
+                ret[-1][-1] = msg
+        return ret
+
+    def copy(self):
+        return Conversation(system=self.system, roles=self.roles, messages=[[x, y] for x, y in self.messages], offset=self.offset,
+                            sep_style=self.sep_style, sep=self.sep, sep2=self.sep2, conv_id=self.conv_id)
+
+    def dict(self):
+        return {"system": self.system, "roles": self.roles, "messages": self.messages, "offset": self.offset, "sep": self.sep,
+                "sep2": self.sep2, "conv_id": self.conv_id}
+
+
+CONV_VISION = Conversation(
+    system="Give the following image: <Img>ImageContent</Img>. "
+           "You will be able to see the image once I provide it to you. Please answer my questions.",
+    roles=("Human", "Assistant"),
+    messages=[],
+    offset=2,
+    sep_style=SeparatorStyle.SINGLE,
+    sep="###",
+)
+
+
+def ask(text: str, conv: Conversation) -> None:
+    """`Chat.ask`: a question right after an image message joins that message (conversation.py:137-142)."""
+    if len(conv.messages) > 0 and conv.messages[-1][0] == conv.roles[0] and conv.messages[-1][1][-6:] == "</Img>":
+        conv.messages[-1][1] = " ".join([conv.messages[-1][1], text])
+    else:
+        conv.append_message(conv.roles[0], text)
+
+
+def truncation_begin(context_len: int, max_new_tokens: int, max_length: int) -> int:
+    """The reference's window (conversation.py:150-156): the first context position the model still sees."""
+    return max(0, context_len + max_new_tokens - max_length)
+
+
+def postprocess_tokens(ids: Sequence[int]) -> List[int]:
+    """A leading <unk> (0), then a leading <s> (1), is removed (conversation.py:170-173)."""
+    out = [int(t) for t in ids]
+    if out and out[0] == 0:
+        out = out[1:]
+    if out and out[0] == 1:
+        out = out[1:]
+    return out
+
+
+def postprocess_text(text: str) -> str:
+    """The decoded answer cut at the stop sign and after the last 'Assistant:' (conversation.py:175-176)."""
+    return text.split("###")[0].split("Assistant:")[-1].strip()
+
+
+class Chat:
+    def __init__(self, model, vis_processor=None, device="cuda:0"):
+        self.device = torch.device(device)
+        self.model = model
+        self.vis_processor = vis_processor
+        self.stopping_criteria = [StoppingCriteriaSub(stops=[torch.tensor(list(s)) for s in STOP_WORDS])]
+        self._frontend = None
+        self.session: Optional[DecodeSession] = None
+        self.last_stats = {}
+        self.last_token_ids = None
+        self._digests = {}
+
+    # ------------------------------------------------------------------ conversation
+    def ask(self, text, conv):
+        ask(text, conv)
+
+    def _image_tensor(self, image) -> torch.Tensor:
+        if isinstance(image, torch.Tensor):
+            if image.dim() == 3:
+                image = image.unsqueeze(0)
+            return image.to(self.device, torch.float32)
+        from PIL import Image
+        raw = Image.open(image).convert("RGB") if isinstance(image, str) else image
+        if not isinstance(raw, Image.Image):
+            raise TypeError(f"upload_img: a tensor, a path or a PIL image, got {type(image).__name__}")
+        if self.vis_processor is not None:
+            return self.vis_processor(raw).unsqueeze(0).to(self.device, torch.float32)
+        if self._frontend is None:
+            from .image_frontend import ImageFrontEndHIP
+            self._frontend = ImageFrontEndHIP(self.device, size=224, mode="train")   # Resize(224) + CenterCrop(224) + normalise
+        return self._frontend([np.asarray(raw.convert("RGB"), dtype=np.uint8)])
+
+    @torch.no_grad()
+    def upload_img(self, image, conv, img_list, **extras):
+        """Encode one image and add it to the conversation.  `extras`: `anomaly_maps` / `oneshot_anomaly_maps` [1, 1, 224, 224], or
+        `expert_text_feats` + `ref_images` for an attached vision expert (Myriad arch; the key generate() reads: oneshot maps when
+        k_shot > 0).  Returns ("Received.", the anomaly map used or None)."""
+        m = self.model
+        m.finish_update()
+        image = self._image_tensor(image)
+        maps = None
+        if m.arch == "myriad":
+            key = "oneshot_anomaly_maps" if m.k_shot > 0 else "anomaly_maps"
+            maps = m._maps_for(dict(extras), key, image)
+            parts = m.encode_img(image, maps, 1, False)
+        else:
+            parts = m.encode_img(image, None, 0, False)
+        emb = torch.cat([p.to(torch.float32) for p in parts], 1).contiguous()      # [1, n_img, D]: the rows _assemble places
+        img_list.append(emb)
+        conv.append_message(conv.roles[0], "<Img><ImageHere></Img>")
+        return "Received.", maps
+
+    def _image_key(self, emb: torch.Tensor):
+        """A digest of the embedding's bytes: a re-encoded or replaced image never matches the rows cached for another one.  Kept
+        per tensor (holding it, so its id is not reused) and version."""
+        hit = self._digests.get(id(emb))
+        if hit is not None and hit[0] is emb and hit[1] == emb._version:
+            return hit[2]
+        dig = hashlib.blake2b(emb.detach().float().cpu().numpy().tobytes(), digest_size=16).hexdigest()
+        if len(self._digests) > 64:
+            self._digests.clear()
+        self._digests[id(emb)] = (emb, emb._version, dig)
+        return dig
+
+    def context_tokens(self, conv, img_list):
+        """`get_context_emb`'s layout without the embeddings: a list of segments, token-id lists and image tensors in order."""
+        tok = self.model.llama_tokenizer
+        segs = conv.get_prompt().split("<ImageHere>")
+        assert len(segs) == len(img_list) + 1, "Unmatched numbers of image placeholders and images."
+        out = []
+        for i, seg in enumerate(segs):
+            out.append([int(t) for t in tok(seg, return_tensors="pt", add_special_tokens=i == 0).input_ids[0].tolist()])
+            if i < len(img_list):
+                out.append(img_list[i])
+        return out
+
+    def get_context_emb(self, conv, img_list):
+        """Returns (embeddings [1, S, D] f32 on the device, one key per position)."""
+        parts = self.context_tokens(conv, img_list)
+        llama = self.model.llama
+        S = sum(len(p) if isinstance(p, list) else p.shape[1] for p in parts)
+        emb = torch.empty((1, S, llama.D), dtype=torch.float32, device=self.device)
+        keys, ids, rows, col = [], [], [], 0
+        for p in parts:
+            if isinstance(p, list):
+                ids += p
+                rows += range(col, col + len(p))
+                keys += [("t", t) for t in p]
+                col += len(p)
+            else:
+                n = p.shape[1]
+                ops.copy3d(p.to(self.device, torch.float32), emb[:, col:col + n])
+                dig = self._image_key(p)
+                keys += [("i", dig, j) for j in range(n)]
+                col += n
+        if ids:
+            llama.embed_tokens_into(ops.h2d(torch.tensor(ids, dtype=torch.long), self.device), emb.view(S, llama.D),
+                                    ops.h2d(torch.tensor(rows, dtype=torch.int32), self.device))
+        return emb, keys
+
+    # ------------------------------------------------------------------ answer
+    @torch.no_grad()
+    def answer(self, conv, img_list, max_new_tokens=300, num_beams=1, min_length=1, top_p=0.9, repetition_penalty=1.0,
+               length_penalty=1, temperature=1.0, max_length=2000, do_sample=True, generator=None):
+        """One assistant turn (conversation.py:144-178).  The context is truncated to the reference's window; the KV cache of the
+        earlier turns is reused up to the first position whose token / image row differs.  `repetition_penalty` != 1 needs the
+        device sampling switch, as in generate().  num_beams > 1: beam search on the full context, no reuse."""
+        m = self.model
+        m.finish_update()
+        llama = m.llama
+        rep = 1.0 if repetition_penalty is None else float(repetition_penalty)
+        if rep != 1.0 and not llama.device_sampling:
+            raise NotImplementedError(f"answer(repetition_penalty={rep}) needs the device sampling switch "
+                                      "(MYRIAD_DEVICE_SAMPLING=1 or model.llama.device_sampling = True)")
+        conv.append_message(conv.roles[1], None)
+        embs, keys = self.get_context_emb(conv, img_list)
+        begin = truncation_begin(embs.shape[1], max_new_tokens, max_length)
+        if begin > 0:
+            warnings.warn("The number of tokens in current conversation exceeds the max length. "
+                          "The model will not see the contexts outside the range.", RuntimeWarning, stacklevel=2)
+        embs, keys = embs[:, begin:].contiguous(), keys[begin:]
+        S = embs.shape[1]
+        if int(num_beams) > 1:
+            if rep != 1.0:
+                raise NotImplementedError(f"answer(num_beams={num_beams}, repetition_penalty={rep}) is not implemented")
+            ids = llama.beam_generate(embs, int(num_beams), max_new_tokens=max_new_tokens, stop_ids=STOP_WORDS, eos_id=2,
+                                      min_length=min_length, length_penalty=float(length_penalty))
+            st = llama.last_generate_stats
+            self.last_stats = dict(context_tokens=S, reused_tokens=0, prefilled_tokens=S, steps=st["steps"],
+                                   graph_captures=0 if self.session is None else self.session.graph_captures,
+                                   graph_replays=st["graph_replays"], split_kv=False, full_reprefill_reason="num_beams")
+        else:
+            if self.session is None:
+                self.session = DecodeSession(llama, max_length + max_new_tokens + 2)
+            ids = self.session.generate(embs, [keys], weights_version=m.store.version,
+                                        reset_reason="window" if begin > 0 else None, max_new_tokens=max_new_tokens,
+                                        stop_ids=STOP_WORDS, eos_id=2, min_length=min_length, do_sample=bool(do_sample),
+                                        top_p=float(top_p), temperature=float(temperature), generator=generator, top_k=50,
+                                        repetition_penalty=rep)
+            self.last_stats = dict(self.session.last_stats)
+        self.last_token_ids = ids                                    # [B, L] as decoded, before the post-processing
+        out = postprocess_tokens(ids[0].tolist())
+        text = postprocess_text(m.llama_tokenizer.decode(out, add_special_tokens=False))
+        conv.messages[-1][1] = text
+        return text, np.asarray(out, dtype=np.int64)

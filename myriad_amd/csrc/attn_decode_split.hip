@@ -1,0 +1,241 @@
+// Split-KV decode attention (one query per (batch, head) over a long KV cache): the chat session's token step.
+//
+// attn_decode_kernel (attention.hip) runs ONE workgroup per (b, h): at batch 1 that is 32 workgroups on 256 CUs, each
+// streaming its head's whole K|V history alone.  Here the keys are cut into chunks of CH: grid (ceil(T_cap / CH), B*H), every
+// workgroup scores its chunk, and writes the chunk's softmax statistics and un-normalised output (m, l, o[D]) in fp32; a
+// second, small launch merges the chunks of a (b, h) in chunk order and writes bf16 o.  Fixed order everywhere: the result is
+// the same bits from run to run.
+//
+// Same contract as mh_attn_decode_rope, except that q is NOT rotated in place: many workgroups read the one q, so each rotates
+// it in registers (same arithmetic: fp32 rotate-half, one rounding to bf16, then * scale).  The workgroup whose chunk holds
+// row pos_dev[0] writes the new cache row [k | v] (bits as mh_attn_decode_rope writes them) and uses its LDS copy of that key
+// and value for its own scores: no workgroup reads a row another one writes in the same launch.  kv_len lives in device memory,
+// so one launch replays from a hipGraph while the context grows; a chunk that starts at or after kv_len[b] exits at once.
+#include "common.h"
+
+#define SPLIT_THREADS 256
+#define SPLIT_PSTRIDE 132   // floats per (b, h, chunk) partial: o[128] | m | l | 2 pad (16-byte aligned records)
+
+struct SplitParams {
+  const bf16_t* qkv;
+  long ld_qkv;
+  bf16_t* cache;
+  long cache_bs, ld_cache;
+  const int* pos;
+  const int* pos_dev;
+  const int* kv_len;
+  const float* cs;
+  const float* sn;
+  float* part;
+  bf16_t* out;
+  long ldo;
+  int B, H, D, T_cap, nch;
+  float scale;
+};
+
+template <int CH>
+__global__ __launch_bounds__(SPLIT_THREADS) void attn_decode_split_kernel(SplitParams p) {
+  __shared__ float sc[CH];                 // chunk scores
+  __shared__ float po[4][128];             // per-wave partial outputs
+  __shared__ float qs[128];                // rotated q (bf16-rounded) * scale
+  __shared__ bf16_t knew[128], vnew[128];  // the new row's k (rotated) and v, owner chunk only
+  const int c = blockIdx.x, bh = blockIdx.y;
+  const int b = bh / p.H, h = bh % p.H;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int D = p.D, W = p.H * D;
+  int len = p.kv_len[b];
+  len = len < p.T_cap ? len : p.T_cap;
+  const int j0 = c * CH;
+  const int prow = p.pos_dev[0];
+  const bool owner = prow >= j0 && prow < j0 + CH && prow < p.T_cap;
+  if (j0 >= len && !owner) return;
+  const int n = len - j0 < CH ? len - j0 : CH;   // keys of this chunk (<= 0: the owner of a row past kv_len[b])
+
+  // rotary (modeling_llama.py:186-195): q always, k | v of the new token by the owner only
+  const int half = D >> 1, items = half >> 2;
+  const bf16_t* src = p.qkv + (size_t)b * p.ld_qkv;
+  bf16_t* crow = p.cache + (size_t)b * p.cache_bs + (size_t)prow * p.ld_cache;
+  if (tid < 2 * items) {
+    const int which = tid / items, i = (tid % items) * 4;
+    if (which == 0 || owner) {
+      const bf16_t* e = src + which * W + h * D + i;
+      const int ps = p.pos[b];
+      const float4_t c4 = *reinterpret_cast<const float4_t*>(p.cs + (size_t)ps * half + i);
+      const float4_t s4 = *reinterpret_cast<const float4_t*>(p.sn + (size_t)ps * half + i);
+      const short4_t a = *reinterpret_cast<const short4_t*>(e);
+      const short4_t bb = *reinterpret_cast<const short4_t*>(e + half);
+      short4_t oa, ob;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const float x1 = bf2f((bf16_t)a[t]), x2 = bf2f((bf16_t)bb[t]);
+        oa[t] = (short)f2bf(x1 * c4[t] - x2 * s4[t]);
+        ob[t] = (short)f2bf(x2 * c4[t] + x1 * s4[t]);
+      }
+      if (which == 0) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          qs[i + t] = bf2f((bf16_t)oa[t]) * p.scale;
+          qs[i + half + t] = bf2f((bf16_t)ob[t]) * p.scale;
+        }
+      } else {
+        *reinterpret_cast<short4_t*>(crow + h * D + i) = oa;
+        *reinterpret_cast<short4_t*>(crow + h * D + i + half) = ob;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          knew[i + t] = (bf16_t)oa[t];
+          knew[i + half + t] = (bf16_t)ob[t];
+        }
+      }
+    }
+  } else if (owner && tid < 2 * items + (D >> 3)) {
+    const int cc = (tid - 2 * items) * 8;
+    const short8_t v8 = *reinterpret_cast<const short8_t*>(src + 2 * W + h * D + cc);
+    *reinterpret_cast<short8_t*>(crow + W + h * D + cc) = v8;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) vnew[cc + t] = (bf16_t)v8[t];
+  }
+  __syncthreads();
+  if (n <= 0) return;                            // the owner of a row no query of this batch row attends to
+
+  const bf16_t* kp = p.cache + (size_t)b * p.cache_bs + (size_t)j0 * p.ld_cache + h * D;
+  const bf16_t* vp = kp + W;
+  const int lrow = prow - j0;                    // the new row inside this chunk (owner), else out of [0, CH)
+
+  // phase 1: scores.  16 lanes per key (8 dims each), 16 keys per 256-thread pass, 8 passes' loads in flight
+  const int sub = lane & 15, kq = lane >> 4;
+  const bool dim_ok = sub * 8 < D;
+  float qf[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) qf[e] = dim_ok ? qs[sub * 8 + e] : 0.f;
+  constexpr int PASSES = CH / 16, UNR = PASSES < 8 ? PASSES : 8;
+  for (int u0 = 0; u0 < PASSES; u0 += UNR) {
+    short8_t kv[UNR];
+    int jj[UNR];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      jj[u] = (u0 + u) * 16 + wave * 4 + kq;
+      kv[u] = (short8_t){0, 0, 0, 0, 0, 0, 0, 0};
+      if (jj[u] < n && jj[u] != lrow && dim_ok) kv[u] = *reinterpret_cast<const short8_t*>(kp + (size_t)jj[u] * p.ld_cache + sub * 8);
+    }
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      if (jj[u] == lrow && dim_ok) kv[u] = *reinterpret_cast<const short8_t*>(knew + sub * 8);
+      float s = 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s += qf[e] * bf2f((bf16_t)kv[u][e]);
+      s += __shfl_xor(s, 1, 64);
+      s += __shfl_xor(s, 2, 64);
+      s += __shfl_xor(s, 4, 64);
+      s += __shfl_xor(s, 8, 64);
+      if (sub == 0 && jj[u] < n) sc[jj[u]] = s;
+    }
+  }
+  __syncthreads();
+  // phase 2: the chunk's softmax statistics (every wave for itself)
+  float mx = -INFINITY;
+  for (int j = lane; j < n; j += 64) mx = fmaxf(mx, sc[j]);
+  mx = wave_max(mx);
+  float sum = 0.f;
+  for (int j = lane; j < n; j += 64) sum += __expf(sc[j] - mx);
+  sum = wave_sum(sum);
+  // phase 3: o = sum_j p_j V[j]; lane owns dims 2*lane, 2*lane+1; wave w takes keys w, w+4, ...; 8 row loads in flight
+  float o0 = 0.f, o1 = 0.f;
+  const bool own = 2 * lane < D;
+  for (int j = wave; j < n; j += 32) {
+    unsigned vv[8];
+    float pj[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int jr = j + 4 * u;
+      const bool ok = jr < n;
+      vv[u] = 0u;
+      if (own && ok) vv[u] = jr == lrow ? *reinterpret_cast<const unsigned*>(vnew + 2 * lane)
+                                        : *reinterpret_cast<const unsigned*>(vp + (size_t)jr * p.ld_cache + 2 * lane);
+      pj[u] = ok ? __expf(sc[jr] - mx) : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      o0 += pj[u] * bf2f((bf16_t)(vv[u] & 0xffffu));
+      o1 += pj[u] * bf2f((bf16_t)(vv[u] >> 16));
+    }
+  }
+  po[wave][2 * lane] = o0;
+  po[wave][2 * lane + 1] = o1;
+  __syncthreads();
+  float* rec = p.part + ((size_t)bh * p.nch + c) * SPLIT_PSTRIDE;
+  if (wave == 0) {
+    if (own) {
+      rec[2 * lane] = ((po[0][2 * lane] + po[1][2 * lane]) + po[2][2 * lane]) + po[3][2 * lane];
+      rec[2 * lane + 1] = ((po[0][2 * lane + 1] + po[1][2 * lane + 1]) + po[2][2 * lane + 1]) + po[3][2 * lane + 1];
+    }
+    if (lane == 0) {
+      rec[128] = mx;
+      rec[129] = sum;
+    }
+  }
+}
+
+// merge the chunks of one (b, h) in chunk order: o = sum_c e^(m_c - M) o_c / sum_c e^(m_c - M) l_c
+template <int CH>
+__global__ __launch_bounds__(64) void attn_decode_combine_kernel(SplitParams p) {
+  const int bh = blockIdx.x, b = bh / p.H, h = bh % p.H, lane = threadIdx.x;
+  int len = p.kv_len[b];
+  len = len < p.T_cap ? len : p.T_cap;
+  const int nc = len > 0 ? (len + CH - 1) / CH : 0;
+  const float* rec = p.part + (size_t)bh * p.nch * SPLIT_PSTRIDE;
+  float M = -INFINITY;
+  for (int c = 0; c < nc; ++c) M = fmaxf(M, rec[(size_t)c * SPLIT_PSTRIDE + 128]);
+  float L = 0.f, o0 = 0.f, o1 = 0.f;
+  const bool own = 2 * lane < p.D;
+  for (int c = 0; c < nc; ++c) {
+    const float* r = rec + (size_t)c * SPLIT_PSTRIDE;
+    const float w = __expf(r[128] - M);
+    L += w * r[129];
+    if (own) {
+      o0 += w * r[2 * lane];
+      o1 += w * r[2 * lane + 1];
+    }
+  }
+  if (own) {
+    const float inv = nc > 0 ? 1.f / L : 0.f;
+    *reinterpret_cast<unsigned*>(p.out + (size_t)b * p.ldo + h * p.D + 2 * lane) = pack_bf2(o0 * inv, o1 * inv);
+  }
+}
+
+static int split_chunk(int chunk) { return chunk == 0 ? 128 : chunk; }
+
+extern "C" long mh_attn_decode_split_ws_floats(int B, int H, int T_cap, int chunk) {
+  const int ch = split_chunk(chunk);
+  if (B <= 0 || H <= 0 || T_cap <= 0 || (ch != 128 && ch != 256 && ch != 512)) return -1;
+  return (long)B * H * ((T_cap + ch - 1) / ch) * SPLIT_PSTRIDE;
+}
+
+template <int CH>
+static int launch_split(const SplitParams& p, hipStream_t s) {
+  hipLaunchKernelGGL(attn_decode_split_kernel<CH>, dim3(p.nch, p.B * p.H), dim3(SPLIT_THREADS), 0, s, p);
+  MH_CHECK_LAUNCH();
+  hipLaunchKernelGGL(attn_decode_combine_kernel<CH>, dim3(p.B * p.H), dim3(64), 0, s, p);
+  MH_CHECK_LAUNCH();
+  return MH_OK;
+}
+
+extern "C" int mh_attn_decode_rope_split(const void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
+                                         const int* pos_dev, const int* kv_len, const float* cos_tab, const float* sin_tab, void* out,
+                                         long ldo, float* partials, long partials_floats, int B, int H, int D, int T_cap, int chunk,
+                                         float scale, hipStream_t stream) {
+  if (B <= 0) return MH_OK;
+  if (!qkv || !cache || !pos || !pos_dev || !kv_len || !cos_tab || !sin_tab || !out || !partials || H <= 0) return MH_ERR_ARG;
+  if (D % 8 || D <= 0 || D > 128 || (D >> 1) % 4 || ld_qkv % 8 || ld_cache % 8 || cache_bstride % 8 || ldo % 4 || T_cap <= 0 ||
+      T_cap > 8192 || ld_qkv < 3L * H * D || ld_cache < 2L * H * D || ldo < (long)H * D)
+    return MH_ERR_ARG;
+  const long need = mh_attn_decode_split_ws_floats(B, H, T_cap, chunk);
+  if (need < 0 || partials_floats < need) return MH_ERR_ARG;
+  const int ch = split_chunk(chunk);
+  SplitParams p = {};
+  p.qkv = (const bf16_t*)qkv; p.ld_qkv = ld_qkv; p.cache = (bf16_t*)cache; p.cache_bs = cache_bstride; p.ld_cache = ld_cache;
+  p.pos = pos; p.pos_dev = pos_dev; p.kv_len = kv_len; p.cs = cos_tab; p.sn = sin_tab; p.part = partials;
+  p.out = (bf16_t*)out; p.ldo = ldo; p.B = B; p.H = H; p.D = D; p.T_cap = T_cap; p.nch = (T_cap + ch - 1) / ch; p.scale = scale;
+  if (ch == 256) return launch_split<256>(p, stream);
+  if (ch == 512) return launch_split<512>(p, stream);
+  return launch_split<128>(p, stream);
+}

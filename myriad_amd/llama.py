@@ -328,9 +328,11 @@ class LlamaHIP:
         return self._pos_cache[key]
 
     # ------------------------------------------------------------------ generation
-    def _decode_block(self, h, B, S, caches, scale, pos, past=None, pos_dev=None, kvlen_dev=None):
-        """All decoder layers for a prefill chunk (host-known `past`) or for one decode token whose position lives
-        in device memory (`pos_dev`/`kvlen_dev`), which makes the launch sequence replayable from a hipGraph."""
+    def _decode_block(self, h, B, S, caches, scale, pos, past=None, pos_dev=None, kvlen_dev=None, split_ws=None):
+        """All decoder layers for a prefill chunk (host-known `past`: the chunk's rows go to cache rows past..past+S-1, `pos` holds
+        their rotary positions, and causal masking is aligned to the bottom right) or for one decode token whose position lives
+        in device memory (`pos_dev`/`kvlen_dev`), which makes the launch sequence replayable from a hipGraph.  `split_ws` (the
+        partials buffer of ops.attn_decode_split_ws) makes the fused token step use the split-KV attention kernel."""
         H, hd, W, D = self.H, self.hd, self.D, self.D
         M = B * S
         packed = self._packed["layers"] if (pos_dev is not None and M <= 16 and self._packed is not None) else None
@@ -360,7 +362,10 @@ class LlamaHIP:
                     qkv = ops.gemv_packed_rmsnorm(h, L["ln1"], self.eps, P["wqkv"])
                     if qkv is None:
                         qkv = ops.gemv_packed(ops.rmsnorm_fwd(h, L["ln1"], self.eps), P["wqkv"])
-                o = ops.attn_decode_rope(qkv, cache, pos, pos_dev, kvlen_dev, self.cos, self.sin, H, hd, scale)
+                if split_ws is not None:
+                    o = ops.attn_decode_rope_split(qkv, cache, pos, pos_dev, kvlen_dev, self.cos, self.sin, H, hd, scale, split_ws)
+                else:
+                    o = ops.attn_decode_rope(qkv, cache, pos, pos_dev, kvlen_dev, self.cos, self.sin, H, hd, scale)
                 h2 = ops.gemv_packed(o, P["wo"], residual=h, out_dtype=F32)
                 gu = ops.gemv_packed_rmsnorm(h2, L["ln2"], self.eps, P["wgu"])
                 if gu is None:
@@ -467,6 +472,17 @@ class LlamaHIP:
         bit-comparable with torch.multinomial.  A row whose tied top-k set passes 1024 candidates is still drawn on the host.
         `repetition_penalty` (HF RepetitionPenaltyLogitsProcessor over the generated ids; the prompt is embeddings only) is applied
         on the device to the step's logits before any pick, greedy, host or device draw."""
+        return self._greedy_core(inputs_embeds, None, max_new_tokens=max_new_tokens, stop_ids=stop_ids, eos_id=eos_id,
+                                 min_length=min_length, return_margins=return_margins, use_graph=use_graph, do_sample=do_sample,
+                                 top_p=top_p, temperature=temperature, generator=generator, top_k=top_k,
+                                 repetition_penalty=repetition_penalty)
+
+    def _greedy_core(self, inputs_embeds: torch.Tensor, session, max_new_tokens: int = 90, stop_ids=((835,), (2277, 29937)),
+                     eos_id: int = 2, min_length: int = 1, return_margins: bool = False, use_graph: bool = True,
+                     do_sample: bool = False, top_p: float = 1.0, temperature: float = 1.0,
+                     generator: Optional[torch.Generator] = None, top_k: int = 50, repetition_penalty: float = 1.0):
+        """greedy_generate's body.  session=None: its workspace from the _decode_ws cache and a prefill from position 0; a
+        DecodeSession instead lends its own buffers and graphs and names the cached prefix `past` that is not prefilled again."""
         B, S0, D = inputs_embeds.shape
         if do_sample and not float(temperature) > 0:
             raise ValueError(f"temperature must be > 0 when sampling, got {temperature}")
@@ -489,7 +505,10 @@ class LlamaHIP:
         elif not self.pack_decode:
             self._packed, self._packs = None, {}                     # MYRIAD_PACK_DECODE=0: stream the row-major matrices
         stats.update(self._decode_weight_stats(B))
-        ws = self._decode_workspace(B, S0 + max_new_tokens, inv_temp, dev_sample, penalty)
+        if session is None:
+            ws, past = self._decode_workspace(B, S0 + max_new_tokens, inv_temp, dev_sample, penalty), 0
+        else:
+            ws, past = session._begin_turn(B, S0, max_new_tokens, inv_temp, dev_sample, penalty)
         caches = ws["caches"]
         if dev_sample or penalty:
             ws["prm"].copy_(torch.tensor([inv_temp, top_p, float(top_k), float(repetition_penalty)], dtype=F32))
@@ -542,9 +561,10 @@ class LlamaHIP:
             return int(unfinished.max()) == 0, redrawn
 
         # ---- prefill (eager, host-known lengths)
-        pos = torch.arange(S0, dtype=torch.int32).repeat(B).to(self.dev)
-        h = self._decode_block(inputs_embeds.reshape(B * S0, D).contiguous(), B, S0, caches, scale, pos, past=0)
-        last = h.view(B, S0, D)[:, -1].contiguous()
+        pos = torch.arange(past, S0, dtype=torch.int32).repeat(B).to(self.dev)
+        h = self._decode_block(inputs_embeds[:, past:].reshape(B * (S0 - past), D).contiguous(), B, S0 - past, caches, scale, pos,
+                               past=past)
+        last = h.view(B, S0 - past, D)[:, -1].contiguous()
         logits0 = ops.gemm(ops.rmsnorm_fwd(last, self.norm, self.eps), self.lm_head, out_dtype=F32)
         ban0 = eos_id if 0 < min_length else -1
         if dev_sample:                                               # the prefill pick is Philox step t = 0
@@ -562,7 +582,8 @@ class LlamaHIP:
         def token_step(ban):
             ops.embed_gather(self.embed, ws["ids"], ws["x_in"])
             done_lm = None
-            hh = self._decode_block(ws["x_in"], B, 1, caches, scale, ws["pos"], pos_dev=ws["pos"], kvlen_dev=ws["kvlen"])
+            hh = self._decode_block(ws["x_in"], B, 1, caches, scale, ws["pos"], pos_dev=ws["pos"], kvlen_dev=ws["kvlen"],
+                                    split_ws=ws.get("split"))
             if done_lm is None and self._packed is not None and B <= 16 and self.decode_fused:
                 done_lm = ops.gemv_packed_rmsnorm(hh, self.norm, self.eps, self._packed["lm_head"], out=ws["logits"], out_dtype=F32)
             if done_lm is None:
@@ -780,3 +801,152 @@ class LlamaHIP:
 
     def embed_tokens_into(self, ids: torch.Tensor, out2d: torch.Tensor, dst_rows: Optional[torch.Tensor] = None):
         ops.embed_gather(self.embed, ids, out2d, dst_rows)
+
+
+# The chat session's token step uses the split-KV attention kernel (mh_attn_decode_rope_split) when the single-workgroup kernel
+# leaves most CUs idle and the cached context is long enough for the chunks to pay for the merge launch: B*H workgroups < 256 (the
+# CU count) and at least SPLIT_KV_MIN_KEYS keys when the turn starts.  Measured at batch 1 on the full-size model
+# (tools/chat_bench.py): ms per token split / single = 3.04 / 2.89 at 256 keys, 3.23 / 3.33 at 1,024,
+# 3.39 / 3.86 at 2,048.  Each kernel has its own captured graph in the session; the choice is made per turn.
+SPLIT_KV_MAX_ROWHEADS = 256
+SPLIT_KV_MIN_KEYS = 1024
+
+
+def split_kv_rule(B: int, H: int, kv_len: int) -> bool:
+    return B * H < SPLIT_KV_MAX_ROWHEADS and kv_len >= SPLIT_KV_MIN_KEYS
+
+
+def common_prefix(a, b) -> int:
+    """Length of the longest common prefix of two key lists (the position keys of a context and of a cache)."""
+    n = min(len(a), len(b))
+    for i in range(n):
+        if a[i] != b[i]:
+            return i
+    return n
+
+
+class DecodeSession:
+    """A decode KV cache that outlives one call: the multi-turn chat's (myriad_amd/chat.py).  It owns its buffers -- the per-layer
+    caches, pos / kvlen / ids / records, the sampler's buffers, the split-KV partials -- and its captured token-step graphs, so no
+    other generate() (whose workspaces live in the LlamaHIP._decode_ws LRU) can evict them.
+
+    The session records one key per cached position (`keys[row][p]`): whatever the caller uses to name that position's input, a
+    ("t", token id) for text and an image-slot / index pair for image rows.  A turn (`generate`) prefills only the rows past the
+    longest common prefix of the new context's keys with the cached ones -- at their own positions, on top of the cached rows --
+    then runs greedy_generate's token step on the session's buffers.  Afterwards the cache holds the context plus every token the
+    step fed back (the last pick of a turn has no KV and is not counted; a row that finished early feeds ids the host does not
+    know, recorded as a key that matches nothing).
+
+    The whole cache is dropped (full prefill, `last_stats["full_reprefill_reason"]`) when the caller's weights version changes
+    (optimiser update, state-dict load), when the decode weights change kind (bf16 / fp8, LoRA on / off), when the batch size
+    changes, when the capacity (round_up(need + 2, 64), at most 8192) is exceeded, or when the caller says so (`reset_reason`: the
+    chat's truncation window moved)."""
+
+    def __init__(self, llama: "LlamaHIP", capacity: int, split: Optional[bool] = None):
+        self.llama = llama
+        self.capacity = min(8192, ops.round_up(int(capacity), 64))
+        self.split_choice = split                                    # None: split_kv_rule per turn; True / False force it
+        self.bufs = None
+        self.B = None
+        self.keys: List[list] = []
+        self.stamp = None
+        self.graphs, self.warm = {}, set()
+        self.graph_captures = 0
+        self.split = False
+        self.last_stats = {}
+        self._turn = None
+
+    def _alloc(self, B: int, T_cap: int) -> None:
+        L, dev, i32 = self.llama, self.llama.dev, torch.int32
+        self.bufs = dict(T=T_cap, caches=[torch.zeros((B, T_cap, 2 * L.D), dtype=BF16, device=dev) for _ in L.layers],
+                         pos=torch.zeros((B,), dtype=i32, device=dev), kvlen=torch.zeros((B,), dtype=i32, device=dev),
+                         ids=torch.zeros((B,), dtype=torch.long, device=dev), x_in=torch.empty((B, L.D), dtype=F32, device=dev),
+                         logits=torch.empty((B, L.V), dtype=F32, device=dev),
+                         nxt=torch.empty((B,), dtype=torch.long, device=dev), mar=torch.empty((B,), dtype=F32, device=dev),
+                         pmx=torch.empty((B,), dtype=F32, device=dev), step=torch.zeros((1,), dtype=i32, device=dev),
+                         rec3=torch.zeros((3, B), dtype=F32, device=dev), rec4=torch.zeros((4, B), dtype=F32, device=dev),
+                         prm=torch.zeros((4,), dtype=F32, device=dev), seed=torch.zeros((1,), dtype=torch.long, device=dev),
+                         kept=torch.zeros((B,), dtype=i32, device=dev),
+                         seen=torch.zeros((B, (L.V + 31) // 32), dtype=i32, device=dev), part=None)
+        self.B = B
+        self.graphs, self.warm = {}, set()
+
+    def _begin_turn(self, B: int, S0: int, max_new_tokens: int, inv_temp: float, dev_sample: bool, penalty: bool):
+        """Called by LlamaHIP._greedy_core once the decode weights are packed: invalidation, (re)allocation, the reused prefix.
+        Returns (workspace, past)."""
+        L = self.llama
+        keys, version, reason = self._turn
+        if S0 + max_new_tokens > L.cos.shape[0]:
+            raise ValueError(f"context {S0} + max_new_tokens {max_new_tokens} passes the rotary table ({L.cos.shape[0]} positions)")
+        if len(keys) != B or any(len(k) != S0 for k in keys):
+            raise ValueError("one key per context position and batch row is required")
+        kind = None if L._packed is None else (L._packed["kind"], L._packed["qkv_key"], id(L._packed))
+        stamp = (version, kind, L.decode_fused, L.lora is not None)
+        need = S0 + max_new_tokens + 2
+        if self.bufs is None:
+            reason = reason or "empty cache"
+        elif self.B != B:
+            reason = "batch size"
+        elif self.stamp[0] != version:
+            reason = "weights changed"
+        elif self.stamp[1:] != stamp[1:]:
+            reason = "decode weights changed"
+        elif need > self.bufs["T"]:
+            reason = "capacity"
+        if self.bufs is None or self.B != B or need > self.bufs["T"] or (self.stamp is not None and self.stamp[1:] != stamp[1:]):
+            T_cap = max(self.capacity, ops.round_up(need, 64))
+            if T_cap > 8192:
+                raise ValueError(f"a chat session holds at most 8192 positions; this turn needs {need}")
+            self.bufs = None
+            self._alloc(B, T_cap)
+        self.stamp = stamp
+        if reason is not None:
+            self.keys = [[] for _ in range(B)]
+        past = min(common_prefix(keys[r], self.keys[r]) for r in range(B))
+        past = min(past, S0 - 1)                                     # at least one row is prefilled: it gives the first logits
+        fused = L._packed is not None and B <= 16 and L.decode_fused
+        self.split = fused and (split_kv_rule(B, L.H, S0) if self.split_choice is None else bool(self.split_choice))
+        if self.split and self.bufs["part"] is None:
+            self.bufs["part"] = ops.attn_decode_split_ws(B, L.H, self.bufs["T"], L.dev)
+        cfg = (None if dev_sample else float(inv_temp), bool(dev_sample), bool(penalty), self.split)
+        ws = dict(self.bufs, rec=self.bufs["rec4" if dev_sample else "rec3"], graph=self.graphs.get(cfg), warm=cfg in self.warm,
+                  split=self.bufs["part"] if self.split else None)
+        self._ws, self._cfg = ws, cfg
+        self.last_stats = dict(context_tokens=S0, reused_tokens=past, prefilled_tokens=S0 - past, split_kv=bool(self.split),
+                               full_reprefill_reason=reason)
+        return ws, past
+
+    @torch.no_grad()
+    def generate(self, inputs_embeds: torch.Tensor, keys, weights_version=None, reset_reason: Optional[str] = None, **kw):
+        """One turn: greedy_generate's contract and arguments (`max_new_tokens`, `stop_ids`, `eos_id`, `min_length`, `do_sample`,
+        `top_p`, `temperature`, `generator`, `top_k`, `repetition_penalty`, `return_margins`) on [B, S0, D] f32 embeddings whose
+        positions are named by `keys` ([B][S0]).  `weights_version`: anything that changes when the weights do."""
+        B, S0, _ = inputs_embeds.shape
+        self._turn = ([list(k) for k in keys], weights_version, reset_reason)
+        try:
+            out = self.llama._greedy_core(inputs_embeds, self, use_graph=True, **kw)
+        except BaseException:
+            self.keys = [[] for _ in range(B)]                       # the cache may be half written
+            raise
+        finally:
+            self._turn = None
+        ws, cfg = self._ws, self._cfg
+        if ws["graph"] is not None and cfg not in self.graphs:
+            self.graphs[cfg] = ws["graph"]
+            self.graph_captures += 1
+        if ws["warm"]:
+            self.warm.add(cfg)
+        ids = out[0] if isinstance(out, tuple) else out
+        eos = int(kw.get("eos_id", 2))
+        n = ids.shape[1]
+        new_keys = []
+        for r in range(B):
+            row, fed, live = ids[r].tolist(), [], True
+            for k in range(n - 1):                                   # token step k + 1 fed pick k at position S0 + k
+                fed.append(("t", row[k]) if live else ("x",))
+                live = live and row[k] != eos
+            new_keys.append(list(keys[r]) + fed)
+        self.keys = new_keys
+        st = self.llama.last_generate_stats
+        self.last_stats.update(steps=st["steps"], graph_replays=st["graph_replays"], graph_captures=self.graph_captures)
+        return out

@@ -121,6 +121,7 @@ class ParamStore:
             self.g[name] = self.flat_g[o:o + n].view(ishape)
             self.ref_shape[name] = rshape
         self.step = 0                                             # optimiser calls so far (host)
+        self.version = 0                                          # bumped by every update / load of flat_p (decode sessions)
 
     def n_params(self) -> int:
         return sum(n for _, n in self.offsets.values())
@@ -156,6 +157,7 @@ class ParamStore:
         complete may be updated while the rest of the backward still runs; adamw_step(..., skip={module}) then leaves it out
         and bumps every module's step counter as usual)."""
         mi = self.modules.index(module)
+        self.version += 1
         for m2, a, b, decays in self.ranges:
             if m2 == mi:
                 ops.adamw_gated(self.flat_p[a:b], self.flat_g[a:b], self.flat_m[a:b], self.flat_v[a:b], lr,
@@ -165,6 +167,7 @@ class ParamStore:
         """The gated AdamW on the slices `pieces` [(lo, hi)] of the flat buffers only -- no step-counter bump: a part of the step's
         update issued early (a data-parallel segment whose exchange is complete); adamw_step(..., exclude=pieces' span) does the
         rest and bumps the counters.  Same kernel, same per-module flags and step counts as the one-shot update."""
+        self.version += 1
         for mi, a0, b0, decays in self.ranges:
             for lo, hi in pieces:
                 a, b = max(a0, lo), min(b0, hi)
@@ -181,6 +184,7 @@ class ParamStore:
         spans adamw_pieces() already updated this step.  `skip`: modules adamw_module() already
         updated this step."""
         self.step += 1
+        self.version += 1
         pieces = None
         if shard is not None:
             pieces = [tuple(shard)] if isinstance(shard[0], int) else [tuple(p) for p in shard]
@@ -372,6 +376,7 @@ class MyriadHIP(nn.Module):
 
     def load_state_dict(self, sd, strict: bool = False):
         self.finish_update()                              # a delayed update must not land on top of the loaded values
+        self.store.version += 1
         missing = []
         for name, ishape, _ in self.store.specs:
             if name in sd:

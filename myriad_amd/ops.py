@@ -303,6 +303,39 @@ def attn_decode_rope(qkv2d: torch.Tensor, cache: torch.Tensor, pos: torch.Tensor
     return out
 
 
+# keys per workgroup of mh_attn_decode_rope_split: 128 measured fastest at 256 / 1,024 / 2,048 cached keys, batch 1, 32 heads
+# (tools/chat_bench.py --chunks: 11.5 / 15.2 / 21.0 us per layer; 256 keys 16.0 / 17.8 / 22.2; 512 keys 19.9 / 27.0 / 30.6)
+SPLIT_KV_CHUNK = 128
+
+
+def attn_decode_split_ws(B: int, n_heads: int, T_cap: int, device, chunk: int = SPLIT_KV_CHUNK) -> torch.Tensor:
+    """The fp32 partials buffer mh_attn_decode_rope_split needs for a [B, T_cap] cache (one (m, l, o) record per chunk)."""
+    n = _L().mh_attn_decode_split_ws_floats(B, n_heads, T_cap, chunk)
+    if n < 0:
+        raise _lib.MyriadHipError(f"attn_decode_split_ws: bad shape B={B} H={n_heads} T_cap={T_cap} chunk={chunk}")
+    return torch.empty((n,), dtype=F32, device=device)
+
+
+def attn_decode_rope_split(qkv2d: torch.Tensor, cache: torch.Tensor, pos: torch.Tensor, pos_dev: torch.Tensor, kv_len: torch.Tensor,
+                           cos_tab: torch.Tensor, sin_tab: torch.Tensor, n_heads: int, head_dim: int, scale: float,
+                           partials: torch.Tensor, chunk: int = SPLIT_KV_CHUNK, out: Optional[torch.Tensor] = None):
+    """attn_decode_rope with the keys split into chunks over many workgroups plus an in-order merge (two launches).  qkv2d is
+    read only (q is rotated in registers); the appended cache row has attn_decode_rope's bits.  partials: attn_decode_split_ws()."""
+    _chk2d(qkv2d, BF16, "attn_decode_rope_split.qkv")
+    B, W = qkv2d.shape[0], n_heads * head_dim
+    if qkv2d.shape[1] < 3 * W or cache.shape[2] != 2 * W:
+        raise _lib.MyriadHipError("attn_decode_rope_split: qkv must be [B, >=3W] and cache [B, T, 2W]")
+    if partials.dtype != F32 or not partials.is_contiguous():
+        raise _lib.MyriadHipError("attn_decode_rope_split: partials must be a contiguous f32 buffer")
+    if out is None:
+        out = torch.empty((B, W), dtype=BF16, device=qkv2d.device)
+    _lib.check(_L().mh_attn_decode_rope_split(_p(qkv2d), qkv2d.stride(0), _p(cache), cache.stride(0), cache.stride(1), _p(pos),
+                                              _p(pos_dev), _p(kv_len), _p(cos_tab), _p(sin_tab), _p(out), out.stride(0), _p(partials),
+                                              partials.numel(), B, n_heads, head_dim, cache.shape[1], int(chunk), float(scale), _s()),
+               "mh_attn_decode_rope_split")
+    return out
+
+
 def gemm_auto_f32(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     """f32 out = a @ b^T, choosing split-K when the output is small and the reduction long (wgrad shapes)."""
     M, K = a.shape

@@ -1,0 +1,141 @@
+#!/usr/bin/env python3
+"""Chat-session decode on the full-size LLaMA (Vicuna-7B shapes, synthetic weights), batch 1:
+
+  * ms per token at cached contexts of 256 / 1,024 / 2,048 keys, with the split-KV decode attention (mh_attn_decode_rope_split)
+    and with the single-workgroup kernel (mh_attn_decode_rope), each in a DecodeSession (captured token step);
+  * time to first token of turn 2 (turn 1's context + its answer + a new question) with the cache reused and with a full
+    re-prefill;
+  * --chunks: the attention launch alone (32 launches = one token's layers, replayed from a graph) for the single-workgroup kernel
+    and the split kernel at 128 / 256 / 512 keys per chunk.
+
+python tools/chat_bench.py [--layers 32] [--tokens 32] [--repeats 3] [--chunks]   -> one JSON line per measurement"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+from myriad_amd import ops  # noqa: E402
+from myriad_amd.llama import DecodeSession, LlamaHIP  # noqa: E402
+from myriad_amd.synthetic import SyntheticWeights, full_config  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--layers", type=int, default=32)
+ap.add_argument("--tokens", type=int, default=32, help="timed token steps per measurement")
+ap.add_argument("--repeats", type=int, default=3)
+ap.add_argument("--contexts", default="256,1024,2048")
+ap.add_argument("--chunks", action="store_true", help="also time the attention launch alone per chunk size")
+ap.add_argument("--skip-model", action="store_true", help="only the --chunks launch timings")
+a = ap.parse_args()
+dev = "cuda:0"
+torch.manual_seed(0)
+
+
+def emit(**kw):
+    print(json.dumps(kw), flush=True)
+
+
+def chunk_bench():
+    B, H, D, T = 1, 32, 128, 2048 + 64
+    W = H * D
+    cache = (torch.randn((B, T, 2 * W), device=dev) * 0.5).to(torch.bfloat16)
+    qkv = (torch.randn((B, 3 * W), device=dev) * 0.5).to(torch.bfloat16)
+    fr = torch.arange(T).float()[:, None] * (1.0 / (10000.0 ** (torch.arange(0, D, 2).float() / D)))[None]
+    cos, sin = fr.cos().contiguous().to(dev), fr.sin().contiguous().to(dev)
+    part = ops.attn_decode_split_ws(B, H, T, dev, chunk=128)
+    out = torch.empty((B, W), dtype=torch.bfloat16, device=dev)
+    for kv in [int(x) for x in a.contexts.split(",")]:
+        pos = torch.full((B,), kv - 1, dtype=torch.int32, device=dev)
+        kvl = torch.full((B,), kv, dtype=torch.int32, device=dev)
+        variants = [("single", None)] + [("split", c) for c in (128, 256, 512)]
+        for name, ch in variants:
+            def one():
+                for _ in range(32):
+                    if ch is None:
+                        ops.attn_decode_rope(qkv, cache, pos, pos, kvl, cos, sin, H, D, 1.0 / D ** 0.5)
+                    else:
+                        ops.attn_decode_rope_split(qkv, cache, pos, pos, kvl, cos, sin, H, D, 1.0 / D ** 0.5, part, chunk=ch, out=out)
+            one()
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                one()
+            ts = []
+            for _ in range(5):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                g.replay()
+                e0.record()
+                for _ in range(20):
+                    g.replay()
+                e1.record()
+                e1.synchronize()
+                ts.append(e0.elapsed_time(e1) / 20 / 32 * 1000.0)
+            emit(what="attn_launch_us", kernel=name, chunk=ch, kv=kv, us_per_layer=round(statistics.median(ts), 2))
+            del g
+
+
+if a.chunks or a.skip_model:
+    chunk_bench()
+if a.skip_model:
+    sys.exit(0)
+
+cfg = full_config(llm_layers=a.layers)
+llama = LlamaHIP(SyntheticWeights(cfg, dev, seed=0), cfg["llm_heads"], dev, need_backward=False, max_pos=4096)
+D = llama.D
+gen = torch.Generator().manual_seed(1)
+
+
+def turn(sess, emb, keys, n_new, reset=None):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    ids = sess.generate(emb, [keys], weights_version=0, reset_reason=reset, max_new_tokens=n_new, stop_ids=(), eos_id=-1,
+                        min_length=0)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, ids
+
+
+def ctx(n, seed):
+    g = torch.Generator().manual_seed(seed)
+    ids = torch.randint(3, cfg["vocab"], (n,), generator=g)
+    emb = llama.embed[ids.to(dev)].float()[None].contiguous()
+    return emb, [("t", int(t)) for t in ids]
+
+
+# ---- ms per token at a cached context of L keys: (turn of 1 + W + K tokens) - (turn of 1 token), both fully prefilled
+for split in (True, False):
+    sess = DecodeSession(llama, 2048 + a.tokens + 64 + 2, split=split)
+    for L in [int(x) for x in a.contexts.split(",")]:
+        emb, keys = ctx(L, L)
+        turn(sess, emb, keys, a.tokens + 4, reset="bench")            # warm: captures the graph
+        per = []
+        for _ in range(a.repeats):
+            t_long, _ = turn(sess, emb, keys, a.tokens + 1, reset="bench")
+            t_one, _ = turn(sess, emb, keys, 1, reset="bench")
+            per.append((t_long - t_one) / a.tokens * 1000.0)
+        emit(what="ms_per_token", split_kv=sess.split, context=L, batch=1, layers=a.layers, ms=round(statistics.median(per), 3),
+             runs=[round(x, 3) for x in per])
+    del sess
+    torch.cuda.empty_cache()
+
+# ---- time to first token of turn 2: reuse vs full re-prefill
+L1, A, Q = 1000, 32, 24
+for mode in ("reuse", "full"):
+    ttft = []
+    for r in range(a.repeats):
+        sess = DecodeSession(llama, 2000 + 300 + 2)
+        emb1, keys1 = ctx(L1, 7 + r)
+        _, ids = turn(sess, emb1, keys1, A)
+        ans = ids[0].tolist()
+        q_emb, q_keys = ctx(Q, 100 + r)
+        emb2 = torch.cat([emb1, llama.embed[ids[0].to(dev)].float()[None], q_emb], 1).contiguous()
+        keys2 = keys1 + [("t", t) for t in ans] + q_keys
+        t, _ = turn(sess, emb2, keys2, 1, reset="bench" if mode == "full" else None)
+        st = sess.last_stats
+        ttft.append(t * 1000.0)
+        del sess
+    emit(what="turn2_ttft_ms", mode=mode, context=emb2.shape[1], reused=st["reused_tokens"], prefilled=st["prefilled_tokens"],
+         split_kv=st["split_kv"], ms=round(statistics.median(ttft), 3), runs=[round(x, 3) for x in ttft])
