@@ -101,6 +101,17 @@ int mh_gemm_bf16_nt_splitk(const void* A, int lda, const void* B, int ldb, float
 int mh_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const float* bias,
                 const int* kv_len, int B, int H, int Sq, int Sk, int D, long q_bs, int ldq, long k_bs, int ldk,
                 long v_bs, int ldv, long o_bs, int ldo, float scale, int causal, mh_stream_t s);
+/* Q-Former attention with attention-probability dropout (train mode): O = (P . Z) V with the LSE of the undropped P;
+ * backward dV = (P . Z)^T dO, dP = (dO V^T) . Z, delta from the dropped O.  Z[b,h,i,j] = dropout_keep(seed,
+ * ((b*H + h)*Sq + i)*Sk + j).  No bias / padding / causal mask.  p = 0 callers use mh_attn_fwd / mh_attn_bwd. */
+int mh_attn_fwd_dropout(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Sq, int Sk, int D,
+                        long q_bs, int ldq, long k_bs, int ldk, long v_bs, int ldv, long o_bs, int ldo, float scale,
+                        float drop_p, unsigned long long seed, mh_stream_t s);
+int mh_attn_bwd_dropout(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                        float* delta_ws, void* dq, void* dk, void* dv, int B, int H, int Sq, int Sk, int D, long q_bs, int ldq,
+                        long k_bs, int ldk, long v_bs, int ldv, long o_bs, int ldo, long do_bs, int lddo, long dq_bs,
+                        int lddq, long dk_bs, int lddk, long dv_bs, int lddv, float scale, float drop_p,
+                        unsigned long long seed, mh_stream_t s);
 int mh_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
                 float* delta_ws /* [B,H,Sq] f32 scratch */, void* dq, void* dk, void* dv, const float* bias,
                 const int* kv_len, int B, int H, int Sq, int Sk, int D, long q_bs, int ldq, long k_bs, int ldk,
@@ -136,6 +147,34 @@ int mh_layernorm_fwd(const float* x, const float* w, const float* b, void* y_bf1
                      float eps, mh_stream_t s);
 int mh_layernorm_bwd(const float* dy, const float* x, const float* w, const float* dres, float* dx, void* dx_bf16,
                      int M, int D, float eps, mh_stream_t s);
+/* K31 LayerNorm parameter gradients (trainable Q-Former): dgamma (+)= sum_m dy * xhat, dbeta (+)= sum_m dy, xhat recomputed
+ * from the LayerNorm input x [M,D] f32.  ws: mh_layernorm_param_grads_ws_floats(M, D) floats of scratch (per-block partials,
+ * reduced in block order: deterministic).  D % 4 == 0, D <= 4096. */
+long mh_layernorm_param_grads_ws_floats(int M, int D);
+int mh_layernorm_param_grads(const float* dy, const float* x, float* dgamma, float* dbeta, int M, int D, float eps,
+                             int accumulate, float p_out, unsigned long long seed_out, float* ws, long ws_floats,
+                             mh_stream_t s);
+/* K32 Q-Former hidden dropout fused into the LayerNorm (qf_dropout.hip).  fwd: x = z * keep(seed_in) + res (res != NULL; x
+ * written to x_out, the backward's LayerNorm input) or x = z; y = LN(x) * keep(seed_out).  bwd (x = the LayerNorm input):
+ * g = dy * keep(seed_out); dx = LN'(g) in f32 (the residual's gradient), dz_bf16 = dx * keep(seed_in) (the GEMM's).
+ * keep(seed)[m, d] = dropout_keep(seed, m * D + d): 1/(1-p) or 0, and 1 at p = 0.  mh_dropout_keep_mask writes
+ * keep(seed)[i] for i < n. */
+int mh_layernorm_fwd_dropout(const float* z, const float* res, const float* w, const float* b, float* x_out, void* y_bf16,
+                             float* y_f32, int M, int D, float eps, float p_in, unsigned long long seed_in, float p_out,
+                             unsigned long long seed_out, mh_stream_t s);
+int mh_layernorm_bwd_dropout(const float* dy, const float* x, const float* w, float* dx, void* dz_bf16, int M, int D,
+                             float eps, float p_in, unsigned long long seed_in, float p_out, unsigned long long seed_out,
+                             mh_stream_t s);
+int mh_dropout_keep_mask(float* out, long n, float p, unsigned long long seed, mh_stream_t s);
+/* K30 TN weight-gradient GEMM (trainable Q-Former): out[N,K] (+)= dy^T . x with dy [M,N] (row stride lddy) and x [M,K]
+ * (row stride ldx) row-major bf16, fp32 accumulation into out (row stride ldo); accumulate = 0 overwrites.  bias != NULL: the
+ * fused bias gradient bias[N] (+)= sum_m dy[m,:].  N % 64 == K % 64 == 0, lddy / ldx multiples of 8, dy / x 16-byte aligned;
+ * any M.  splits: M splits (0 = mh_gemm_tn_wgrad_auto_splits); splits > 1 need mh_gemm_tn_wgrad_ws_floats(...) floats of
+ * scratch in ws and reduce in split order (bit-identical run to run). */
+long mh_gemm_tn_wgrad_ws_floats(int M, int N, int K, int splits);
+int mh_gemm_tn_wgrad_auto_splits(int M, int N, int K);
+int mh_gemm_tn_wgrad(const void* dy, long lddy, const void* x, long ldx, float* out, long ldo, float* bias, int M, int N, int K,
+                     int accumulate, int splits, float* ws, long ws_floats, mh_stream_t s);
 
 /* K8 rotary, rotate-half form gathered by position id (modeling_llama.py:109-123); in place on heads
  * [col0, col0 + n_heads*head_dim) of a [n_tok, ld] bf16 buffer; tables [max_pos, head_dim/2] f32; sign=-1 = bwd. */

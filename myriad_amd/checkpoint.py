@@ -195,16 +195,35 @@ def load_reference_weights(cfg, arch: str = "myriad"):
 
 
 # ------------------------------------------------------------------------------------------------ fine-tune checkpoints
+# named_parameters() order inside one BertLayer of the Q-Former once myriad.py:151-156 deleted its text FFN (Qformer.py:378-398:
+# attention, crossattention, intermediate_query, output_query; BertSelfAttention query, key, value; BertSelfOutput dense,
+# LayerNorm).  tests/golden/qformer_train_param_order.json is the reference module's own listing.
+_QF_LAYER_ORDER = [blk + t for blk in ("attention.", "crossattention.")
+                   for t in ("self.query.weight", "self.query.bias", "self.key.weight", "self.key.bias", "self.value.weight",
+                             "self.value.bias", "output.dense.weight", "output.dense.bias", "output.LayerNorm.weight",
+                             "output.LayerNorm.bias")] + \
+    ["intermediate_query.dense.weight", "intermediate_query.dense.bias", "output_query.dense.weight",
+     "output_query.dense.bias", "output_query.LayerNorm.weight", "output_query.LayerNorm.bias"]
+
+
 def reference_param_order(names) -> List[str]:
     """The trainable parameters in the order `model.named_parameters()` yields them in the REFERENCE -- the order
     `RunnerBase.optimizer` builds its two param groups in (runner_base.py:110-119) and therefore the indices of
     torch.optim.AdamW's state_dict.  nn.Module yields a module's own parameters before its children's, children in
-    registration order: Myriad.__init__ registers expert_adaptor, VETokenizer (direct parameter `base_prompts` before
+    registration order: `query_tokens` (the model's own parameter, trainable with freeze_qformer: False) first, then
+    Myriad.__init__ registers expert_adaptor, VETokenizer (direct parameter `base_prompts` before
     `meta_net.*`), VEInstructor, Qformer, llama_model (peft: per layer q_proj.lora_A, q_proj.lora_B, v_proj.lora_A,
     v_proj.lora_B), llama_proj (myriad.py:117-125, 148, 186-207)."""
     import re
 
     def key(n: str):
+        if n == "query_tokens":                           # a direct parameter of the model: before every child's
+            return (-1, 0, 0, 0)
+        if n.startswith("Qformer."):                      # registered after VEInstructor, before llama_model / llama_proj
+            if n.startswith("Qformer.bert.embeddings."):
+                return (2.5, -1, 0 if n.endswith("weight") else 1, 0)
+            m = re.search(r"^Qformer\.bert\.encoder\.layer\.(\d+)\.(.+)$", n)
+            return (2.5, int(m.group(1)), _QF_LAYER_ORDER.index(m.group(2)), 0)
         if n.startswith("expert_adaptor."):
             return (0, 0 if ".conv1." in n else 1, 0, 0)
         for rank, pre in ((1, "VETokenizer."), (2, "VEInstructor.")):

@@ -49,7 +49,17 @@ struct AttnParams {
   const float* sn;
   const int* pos;       // [B] rotary position of the new token
   const int* pos_dev;   // [1] cache row the new token is appended at
+  // attention-probability dropout (trainable Q-Former, mh_attn_fwd_dropout / mh_attn_bwd_dropout): keep of (b, h, query i,
+  // key j) = dropout_keep(drop_seed, ((b * H + h) * Sq + i) * Sk + j); 0 everywhere else (the kernels skip it)
+  float drop_p;
+  unsigned long long drop_seed;
 };
+
+// the mask factor of (b, h, query, key): 1 / (1 - p) kept, 0 dropped
+__device__ __forceinline__ float attn_keep(const AttnParams& p, int b, int h, int qi, int key) {
+  return dropout_keep(p.drop_seed, (unsigned long long)((((long)b * p.H + h) * p.Sq + qi) * p.Sk + key), p.drop_p,
+                      1.f / (1.f - p.drop_p));
+}
 
 template <int DP>
 struct Lds {
@@ -133,7 +143,7 @@ __device__ __forceinline__ void load_row_frags(short8_t (&f)[DP / 32], const bf1
 #define NEG_INF (-__builtin_inff())
 
 // ------------------------------------------------------------------------------------------- forward
-template <int DP>
+template <int DP, bool DROP = false>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* Ks = reinterpret_cast<bf16_t*>(smem);
@@ -199,6 +209,15 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams p) {
         s[j][r] = e;
         psum += e;
       }
+    if (DROP) {                          // O = (P . Z) V; the row sum (and the LSE) stay those of the undropped P
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int key = k0 + 16 * j + 4 * lg + r;
+          if (key < p.Sk && qi < p.Sq) s[j][r] *= attn_keep(p, b, h, qi, key);
+        }
+    }
     lsum = lsum * alpha + psum;
     m = m_new;
     const short8_t pb0 = pack8(s[0], s[1]), pb1 = pack8(s[2], s[3]);
@@ -229,7 +248,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams p) {
 }
 
 // ------------------------------------------------------------------------------------------- dQ
-template <int DP>
+template <int DP, bool DROP = false>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* Ks = reinterpret_cast<bf16_t*>(smem);
@@ -300,7 +319,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnParams p) {
         float val = s[j][r] * p.scale;
         if (p.bias && ok) val += p.bias[((long)h * p.Sq + qi) * p.Sk + key];
         const float pr = ok ? __expf(val - lse) : 0.f;
-        s[j][r] = ok ? pr * (dp[j][r] - dlt) * p.scale : 0.f;  // dS (select, not multiply: masked dp may be non-finite)
+        float dpz = dp[j][r];
+        if (DROP && ok) dpz *= attn_keep(p, b, h, qi, key);
+        s[j][r] = ok ? pr * (dpz - dlt) * p.scale : 0.f;  // dS (select, not multiply: masked dp may be non-finite)
       }
     const short8_t d0 = pack8(s[0], s[1]), d1 = pack8(s[2], s[3]);
 #pragma unroll
@@ -325,7 +346,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnParams p) {
 }
 
 // ------------------------------------------------------------------------------------------- dK, dV
-template <int DP>
+template <int DP, bool DROP = false>
 __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* Qs = reinterpret_cast<bf16_t*>(smem);
@@ -394,8 +415,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnParams p) {
         float val = s[j][r] * p.scale;
         if (p.bias && ok) val += p.bias[((long)h * p.Sq + qq) * p.Sk + ki];
         const float e = ok ? __expf(val - l4[r]) : 0.f;
-        pr[j][r] = e;
-        s[j][r] = ok ? e * (dp[j][r] - d4[r]) * p.scale : 0.f;
+        if (DROP) {
+          const float z = ok ? attn_keep(p, b, h, qq, ki) : 1.f;
+          pr[j][r] = e * z;
+          s[j][r] = ok ? e * (dp[j][r] * z - d4[r]) * p.scale : 0.f;
+        } else {
+          pr[j][r] = e;
+          s[j][r] = ok ? e * (dp[j][r] - d4[r]) * p.scale : 0.f;
+        }
       }
     }
     const short8_t p0 = pack8(pr[0], pr[1]), p1 = pack8(pr[2], pr[3]);
@@ -585,23 +612,23 @@ static void allow_lds(size_t bytes) {
   done = true;
 }
 
-template <int DP>
+template <int DP, bool DROP = false>
 static int launch_fwd(const AttnParams& p, hipStream_t s) {
   const size_t sh = Lds<DP>::RM_BYTES + Lds<DP>::TR_BYTES;
-  allow_lds<attn_fwd_kernel<DP>>(sh);
-  hipLaunchKernelGGL(attn_fwd_kernel<DP>, dim3((p.Sq + TQ - 1) / TQ, p.B * p.H), dim3(256), sh, s, p);
+  allow_lds<attn_fwd_kernel<DP, DROP>>(sh);
+  hipLaunchKernelGGL((attn_fwd_kernel<DP, DROP>), dim3((p.Sq + TQ - 1) / TQ, p.B * p.H), dim3(256), sh, s, p);
   MH_CHECK_LAUNCH();
   return MH_OK;
 }
-template <int DP>
+template <int DP, bool DROP = false>
 static int launch_bwd(const AttnParams& p, hipStream_t s) {
   const size_t sh_dq = 2 * Lds<DP>::RM_BYTES + Lds<DP>::TR_BYTES;
-  allow_lds<attn_bwd_dq_kernel<DP>>(sh_dq);
-  hipLaunchKernelGGL(attn_bwd_dq_kernel<DP>, dim3((p.Sq + TQ - 1) / TQ, p.B * p.H), dim3(256), sh_dq, s, p);
+  allow_lds<attn_bwd_dq_kernel<DP, DROP>>(sh_dq);
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<DP, DROP>), dim3((p.Sq + TQ - 1) / TQ, p.B * p.H), dim3(256), sh_dq, s, p);
   MH_CHECK_LAUNCH();
   const size_t sh_kv = 2 * Lds<DP>::RM_BYTES + 2 * Lds<DP>::TR_BYTES + 512;
-  allow_lds<attn_bwd_dkv_kernel<DP>>(sh_kv);
-  hipLaunchKernelGGL(attn_bwd_dkv_kernel<DP>, dim3((p.Sk + TK - 1) / TK, p.B * p.H), dim3(256), sh_kv, s, p);
+  allow_lds<attn_bwd_dkv_kernel<DP, DROP>>(sh_kv);
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<DP, DROP>), dim3((p.Sk + TK - 1) / TK, p.B * p.H), dim3(256), sh_kv, s, p);
   MH_CHECK_LAUNCH();
   return MH_OK;
 }
@@ -687,4 +714,49 @@ extern "C" int mh_attn_bwd(const void* q, const void* k, const void* v, const vo
   if (D <= 64) return launch_bwd<64>(p, stream);
   if (D <= 96) return launch_bwd<96>(p, stream);
   return launch_bwd<128>(p, stream);
+}
+
+// Q-Former attention with attention-probability dropout (Qformer.py:258, train mode): the tiled kernels above with the
+// counter-based keep mask; no bias, no padding, not causal.  p = 0 callers use mh_attn_fwd / mh_attn_bwd.
+extern "C" int mh_attn_fwd_dropout(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Sq,
+                                   int Sk, int D, long q_bs, int ldq, long k_bs, int ldk, long v_bs, int ldv, long o_bs,
+                                   int ldo, float scale, float drop_p, unsigned long long seed, hipStream_t stream) {
+  if (!(drop_p >= 0.f && drop_p < 1.f) || !lse) return MH_ERR_ARG;
+  AttnParams p = {};
+  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = (bf16_t*)o; p.lse = lse;
+  p.B = B; p.H = H; p.Sq = Sq; p.Sk = Sk; p.D = D;
+  p.q_bs = q_bs; p.k_bs = k_bs; p.v_bs = v_bs; p.o_bs = o_bs;
+  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
+  p.scale = scale; p.q_off = Sk - Sq; p.drop_p = drop_p; p.drop_seed = seed;
+  int rc = check_common(p);
+  if (rc) return rc;
+  if (ldo % 4) return MH_ERR_ARG;
+  if (D <= 64) return launch_fwd<64, true>(p, stream);
+  if (D <= 96) return launch_fwd<96, true>(p, stream);
+  return launch_fwd<128, true>(p, stream);
+}
+
+extern "C" int mh_attn_bwd_dropout(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                                   const float* lse, float* delta_ws, void* dq, void* dk, void* dv, int B, int H, int Sq,
+                                   int Sk, int D, long q_bs, int ldq, long k_bs, int ldk, long v_bs, int ldv, long o_bs,
+                                   int ldo, long do_bs, int lddo, long dq_bs, int lddq, long dk_bs, int lddk, long dv_bs,
+                                   int lddv, float scale, float drop_p, unsigned long long seed, hipStream_t stream) {
+  if (!(drop_p >= 0.f && drop_p < 1.f)) return MH_ERR_ARG;
+  AttnParams p = {};
+  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.dout = (const bf16_t*)dout;
+  p.dq = (bf16_t*)dq; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv;
+  p.lse = const_cast<float*>(lse); p.delta = delta_ws;
+  p.B = B; p.H = H; p.Sq = Sq; p.Sk = Sk; p.D = D;
+  p.q_bs = q_bs; p.k_bs = k_bs; p.v_bs = v_bs; p.o_bs = o_bs;
+  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
+  p.do_bs = do_bs; p.lddo = lddo; p.dq_bs = dq_bs; p.lddq = lddq; p.dk_bs = dk_bs; p.lddk = lddk;
+  p.dv_bs = dv_bs; p.lddv = lddv;
+  p.scale = scale; p.q_off = Sk - Sq; p.drop_p = drop_p; p.drop_seed = seed;
+  int rc = check_common(p);
+  if (rc) return rc;
+  if (lddo % 8 || ldo % 8 || lddq % 4 || lddk % 4 || lddv % 4) return MH_ERR_ARG;
+  p.o = (bf16_t*)const_cast<void*>(o);                // the dropped O: delta = rowsum(dO * O)
+  if (D <= 64) return launch_bwd<64, true>(p, stream);
+  if (D <= 96) return launch_bwd<96, true>(p, stream);
+  return launch_bwd<128, true>(p, stream);
 }

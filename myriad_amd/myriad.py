@@ -27,7 +27,7 @@ from . import _lib, ops
 from .eva_vit import EvaViTHIP
 from .llama import LlamaHIP
 from .networks import LoraAdaptor, VENet, from_reference_layout, to_reference_layout, ve_param_specs
-from .qformer import QFormerHIP
+from .qformer import QFormerHIP, qformer_param_specs
 from .registry import registry
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -38,14 +38,18 @@ def uses_weight_decay(name: str, ndim: int) -> bool:
     return not (ndim < 2 or "bias" in name or "ln" in name or "bn" in name)
 
 
-MODULES = ("expert_adaptor", "VETokenizer", "VEInstructor", "llama_proj", "lora")
+MODULES = ("expert_adaptor", "VETokenizer", "VEInstructor", "llama_proj", "lora", "Qformer")
 
 
 def module_of(name: str) -> str:
-    """The top-level reference module a trainable parameter belongs to (the unit torch's AdamW skips when unused)."""
+    """The top-level reference module a trainable parameter belongs to (the unit torch's AdamW skips when unused).
+    `query_tokens` (a direct parameter of the reference model) is counted with the Q-Former: both are trainable exactly
+    when freeze_qformer is False (myriad.py:159-165) and both are used on every step."""
     for m in MODULES[:4]:
         if name.startswith(m + "."):
             return m
+    if name.startswith("Qformer.") or name == "query_tokens":
+        return "Qformer"
     if "lora_" in name:
         return "lora"
     raise KeyError(name)
@@ -267,10 +271,20 @@ class MyriadHIP(nn.Module):
         self.llama_tokenizer = cfg.get("tokenizer", None)
         self.prompt_list = cfg.get("prompt_list", [])
         need_bwd = cfg.get("need_backward", True)
+        # freeze_qformer: False (myriad.py:159-165): Qformer.* and query_tokens are trainable, and -- the module is no longer put
+        # in eval() -- BERT's dropout is live in training forwards: hidden_dropout_prob = attention_probs_dropout_prob = 0.1
+        # (cfg qformer_dropout).  Like lora_dropout_seed: the counter-based masks draw from torch's seed (train.py:63-72 seeds it
+        # with seed + rank, so ranks drop different elements) unless cfg qformer_dropout_seed is given.
+        self.train_qformer = cfg.get("freeze_qformer", True) is False
+        self.qformer_dropout = float(cfg.get("qformer_dropout", 0.1)) if self.train_qformer else 0.0
+        if not 0.0 <= self.qformer_dropout < 1.0:
+            raise ValueError(f"qformer_dropout {self.qformer_dropout}: must be in [0, 1)")
+        self.qformer_seed = int(cfg.get("qformer_dropout_seed", torch.initial_seed())) & ((1 << 31) - 1)
+        self._qf_step = 0                                      # training forwards so far: one mask set per forward
         ops.ensure_workspace(self._dev)                        # scratch for the automatic split-K GEMM path
         self.visual_encoder = EvaViTHIP(weights, cfg.get("vit_heads", 16), self._dev)
         self.qformer = QFormerHIP(weights, cfg.get("qf_heads", 12), self._dev,
-                                  need_backward=need_bwd and self.arch == "myriad")
+                                  need_backward=need_bwd and (self.arch == "myriad" or self.train_qformer))
         self.llama = LlamaHIP(weights, cfg.get("llm_heads", 32), self._dev, eps=float(cfg.get("llm_eps", 1e-6)),
                               need_backward=need_bwd)
         self.ln_w = weights["ln_vision.weight"].to(self._dev, F32).contiguous()
@@ -292,6 +306,8 @@ class MyriadHIP(nn.Module):
         else:
             specs.append(("llama_proj.weight", (self.Dl, self.Dq), (self.Dl, self.Dq)))
             specs.append(("llama_proj.bias", (self.Dl,), (self.Dl,)))
+        if self.train_qformer:
+            specs += qformer_param_specs(weights)
         # PEFT LoRA on q_proj/v_proj (myriad.py:170-180): off in the shipped recipe, on with cfg use_lora
         self.use_lora = bool(cfg.get("use_lora", False))
         lora_init = {}
@@ -327,6 +343,9 @@ class MyriadHIP(nn.Module):
             # take that seed, so ranks (and runs with another seed) drop different elements (cfg lora_dropout_seed overrides)
             self.lora.base_seed = int(cfg.get("lora_dropout_seed", torch.initial_seed())) & ((1 << 31) - 1)
             self.llama.attach_lora(self.lora)
+        if self.train_qformer:
+            self.query_tokens_f32 = self.store.p["query_tokens"]       # fp32 master, read in place
+            self.qformer.bind_trainable(self.store, need_denc=self.arch == "myriad")
         self._pending_update = None
         self._vit_stream, self._vit_prefetched = None, None
         self._vit_graphs, self._vit_seen, self._vit_rest = {}, {}, None
@@ -399,15 +418,16 @@ class MyriadHIP(nn.Module):
         get = cfg.get if hasattr(cfg, "get") else (lambda k, d=None: getattr(cfg, k, d))
         if get("low_resource", False):
             raise NotImplementedError("low_resource (8-bit LLaMA + ViT on the CPU, myriad.py:186-192) is not part of the MI355X path")
-        for k in ("freeze_vit", "freeze_qformer", "freeze_llama"):
+        for k in ("freeze_vit", "freeze_llama"):
             if get(k, True) is False:
-                raise NotImplementedError(f"{k}: False -- the HIP path keeps ViT / Q-Former / LLaMA frozen (dgrad only), as every "
+                raise NotImplementedError(f"{k}: False -- the HIP path keeps ViT and LLaMA frozen (dgrad only), as every "
                                           "shipped recipe does (train_configs/*.yaml)")
         if get("drop_path_rate", 0) or get("use_grad_checkpoint", False):
             raise NotImplementedError("drop_path_rate / use_grad_checkpoint only matter for an unfrozen ViT")
         keys = ("max_txt_len", "end_sym", "k_shot", "round_index", "fixed_stage", "fixed_taskstage", "tokenizer",
                 "vit_heads", "qf_heads", "llm_heads", "need_backward", "bos_token_id", "pad_token_id", "use_lora",
-                "lora_r", "lora_alpha", "lora_dropout", "lora_seed", "num_query_token", "llm_eps")
+                "lora_r", "lora_alpha", "lora_dropout", "lora_seed", "num_query_token", "llm_eps", "freeze_qformer",
+                "qformer_dropout", "qformer_dropout_seed")
         sub = {k: get(k) for k in keys if get(k) is not None}
         if get("max_txt_len") is None:
             sub["max_txt_len"] = 32                       # from_config defaults (myriad.py:483-484)
@@ -493,7 +513,15 @@ class MyriadHIP(nn.Module):
         ops.copy3d(self.query_tokens_f32.expand(B, -1, -1), q[:, :self.nq0])
         if use_ins:
             ops.copy3d(self.ve_ins.forward(maps, save), q[:, self.nq0:])
-        qo = self.qformer.forward(q, enc_b.view(B, N, self.Dv), save and self.arch == "myriad")
+        if self.train_qformer:
+            # the bf16 working copies follow the fp32 masters, whoever updated them (fused AdamW, a torch optimiser through the
+            # .grad views, load_state_dict): rewritten in place before every use
+            self.qformer.refresh()
+        drop = self.qformer_dropout if (save and self.training and self.train_qformer) else 0.0
+        if drop > 0:
+            self._qf_step += 1
+        qo = self.qformer.forward(q, enc_b.view(B, N, self.Dv), save and (self.arch == "myriad" or self.train_qformer),
+                                  dropout=drop, seed=(self.qformer_seed << 32) + self._qf_step)
         qo_b = ops.to_bf16(qo.view(B * nq, self.Dq))
         if self.arch == "myriad":
             pw, pb = self.proj_w, self.proj_b                         # frozen (myriad.py:218-219)
@@ -662,6 +690,8 @@ class MyriadHIP(nn.Module):
                 used.add("VEInstructor")
         else:
             used.add("llama_proj")
+        if self.train_qformer:
+            used.add("Qformer")
         self.store.mark_used(used)
         # modules whose parameters receive a gradient in this accumulation window (the bridge path hands torch's optimiser
         # `.grad is None` for the others, exactly what autograd leaves for a module the forward never touched)
@@ -680,6 +710,11 @@ class MyriadHIP(nn.Module):
             ops.gemm_auto_f32(ops.transpose_to_bf16(dimg_b, 64), ops.transpose_to_bf16(c["qo_b"], 64),
                               self.store.g["llama_proj.weight"])
             self.store.g["llama_proj.bias"].copy_(ops.colsum(dimg.view(B * nq, self.Dl)))
+            if self.train_qformer:                        # nothing consumes d(image tokens) here: the Q-Former's gradients only
+                pwT = ops.transpose_to_bf16(ops.to_bf16(self.store.p["llama_proj.weight"]), 64)
+                dqo = ops.gemm(dimg_b, pwT, out_dtype=F32).view(B, nq, self.Dq)
+                dq, _ = self.qformer.backward(dqo, wgrads=True, want_denc=False)
+                self._query_tokens_grad(dq)
             if self.llama.lora is not None:
                 self.llama.lora.join_wgrads()
             self._finish_backward()
@@ -713,7 +748,9 @@ class MyriadHIP(nn.Module):
             leaf_ev, leaf_keep = None, None
             if early_exchange is not None:                # unused at this rank's prompt stage: the segment's zeros travel now
                 self._start_early_exchange(early_exchange)
-        dq, denc = self.qformer.backward(dqo)
+        dq, denc = self.qformer.backward(dqo, wgrads=self.train_qformer)
+        if self.train_qformer:
+            self._query_tokens_grad(dq)
         ins_ev, ins_keep = None, None
         if c["use_ins"]:
             dins = torch.empty((B, 49, self.Dq), dtype=F32, device=self._dev)
@@ -740,6 +777,11 @@ class MyriadHIP(nn.Module):
             torch.cuda.current_stream().wait_event(ins_ev)
         del leaf_keep, ins_keep                           # freed only now: later main-stream work is ordered behind the events
         self._finish_backward()
+
+    def _query_tokens_grad(self, dq: torch.Tensor) -> None:
+        """d query_tokens = the batch sum of the Q-Former input gradient over its first nq0 (query-token) rows."""
+        B, nq, D = dq.shape
+        self.store.g["query_tokens"].view(-1).copy_(ops.colsum(dq.reshape(B, nq * D)[:, :self.nq0 * D]))
 
     def _start_early_exchange(self, early_exchange) -> None:
         """early_exchange = (dp, segment index[, (lr, weight_decay, beta2)]): start the segment's collective behind the current stream;

@@ -371,6 +371,47 @@ def attn_fwd(q, k, v, H: int, D: int, scale: float, causal: bool = False, bias=N
     return out, lse
 
 
+def attn_fwd_dropout(q, k, v, H: int, D: int, scale: float, p: float, seed: int):
+    """attn_fwd with attention-probability dropout (mask index ((b*H + h)*Sq + i)*Sk + j); p = 0 is attn_fwd itself."""
+    if p == 0.0:
+        return attn_fwd(q, k, v, H, D, scale)
+    B, Sq = q.shape[0], q.shape[1]
+    Sk = k.shape[1]
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        if t.dtype != BF16 or t.stride(2) != 1:
+            raise _lib.MyriadHipError(f"attn_fwd_dropout.{n}: need bf16 with unit inner stride")
+    out = torch.empty((B, Sq, H * D), dtype=BF16, device=q.device)
+    lse = torch.empty((B, H, Sq), dtype=F32, device=q.device)
+    rc = _L().mh_attn_fwd_dropout(_p(q), _p(k), _p(v), _p(out), _p(lse), B, H, Sq, Sk, D, q.stride(0), q.stride(1),
+                                  k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0), out.stride(1),
+                                  float(scale), float(p), int(seed), _s())
+    _lib.check(rc, f"mh_attn_fwd_dropout B={B} H={H} Sq={Sq} Sk={Sk} D={D}")
+    return out, lse
+
+
+def attn_bwd_dropout(q, k, v, o, dout, lse, H: int, D: int, scale: float, p: float, seed: int, dq=None, dk=None, dv=None):
+    """attn_bwd of attn_fwd_dropout (o = its dropped output); p = 0 is attn_bwd itself."""
+    if p == 0.0:
+        return attn_bwd(q, k, v, o, dout, lse, H, D, scale, dq=dq, dk=dk, dv=dv)
+    B, Sq = q.shape[0], q.shape[1]
+    Sk = k.shape[1]
+    dev = q.device
+    if dq is None:
+        dq = torch.empty((B, Sq, H * D), dtype=BF16, device=dev)
+    if dk is None:
+        dk = torch.empty((B, Sk, H * D), dtype=BF16, device=dev)
+    if dv is None:
+        dv = torch.empty((B, Sk, H * D), dtype=BF16, device=dev)
+    delta = torch.empty((B, H, Sq), dtype=F32, device=dev)
+    rc = _L().mh_attn_bwd_dropout(_p(q), _p(k), _p(v), _p(o), _p(dout), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv),
+                                  B, H, Sq, Sk, D, q.stride(0), q.stride(1), k.stride(0), k.stride(1),
+                                  v.stride(0), v.stride(1), o.stride(0), o.stride(1), dout.stride(0), dout.stride(1),
+                                  dq.stride(0), dq.stride(1), dk.stride(0), dk.stride(1), dv.stride(0), dv.stride(1),
+                                  float(scale), float(p), int(seed), _s())
+    _lib.check(rc, f"mh_attn_bwd_dropout B={B} H={H} Sq={Sq} Sk={Sk} D={D}")
+    return dq, dk, dv
+
+
 def attn_bwd(q, k, v, o, dout, lse, H: int, D: int, scale: float, causal: bool = False, bias=None, kv_len=None,
              dq=None, dk=None, dv=None):
     B, Sq = q.shape[0], q.shape[1]
@@ -519,6 +560,77 @@ def layernorm_bwd(dy, x, w, eps: float, dres=None, want_f32=True, want_bf16=Fals
     _lib.check(_L().mh_layernorm_bwd(_p(dy), _p(x), _p(w), _p(dres), _p(dx), _p(dxb), M, D, float(eps), _s()),
                "mh_layernorm_bwd")
     return dx, dxb
+
+
+def layernorm_param_grads(dy, x, eps: float, dgamma: torch.Tensor, dbeta: torch.Tensor, accumulate: bool = False,
+                          p_out: float = 0.0, seed_out: int = 0):
+    """dgamma (+)= sum_m dy * xhat(x), dbeta (+)= sum_m dy: the LayerNorm's parameter gradients (x = its f32 input).
+    p_out > 0: the LayerNorm's output went through dropout (mask seed_out), dy is the gradient after it."""
+    M, D = x.shape
+    _chk2d(dy, F32, "dy")
+    _chk2d(x, F32, "x")
+    if dy.shape != x.shape or dy.stride(0) != D or x.stride(0) != D:
+        raise ValueError("layernorm_param_grads: dy and x must be contiguous [M, D]")
+    if dgamma.dtype != F32 or dbeta.dtype != F32 or dgamma.numel() != D or dbeta.numel() != D:
+        raise ValueError("layernorm_param_grads: dgamma / dbeta must be f32 [D]")
+    n = _L().mh_layernorm_param_grads_ws_floats(M, D)
+    ws = torch.empty((max(n, 1),), dtype=F32, device=x.device)
+    _lib.check(_L().mh_layernorm_param_grads(_p(dy), _p(x), _p(dgamma), _p(dbeta), M, D, float(eps), int(accumulate),
+                                             float(p_out), int(seed_out), _p(ws), n, _s()), "mh_layernorm_param_grads")
+    return dgamma, dbeta
+
+
+def layernorm_fwd_dropout(z, res, w, b, eps: float, p_in: float = 0.0, seed_in: int = 0, p_out: float = 0.0,
+                          seed_out: int = 0, want_bf16=True, want_f32=True):
+    """Hidden dropout fused into a LayerNorm: x = dropout(z) + res (res given; x returned, the backward's input) or x = z;
+    y = dropout(LN(x)).  Returns (x or None, y bf16, y f32)."""
+    M, D = z.shape
+    x = torch.empty((M, D), dtype=F32, device=z.device) if res is not None else None
+    yb = torch.empty((M, D), dtype=BF16, device=z.device) if want_bf16 else None
+    yf = torch.empty((M, D), dtype=F32, device=z.device) if want_f32 else None
+    _lib.check(_L().mh_layernorm_fwd_dropout(_p(z), _p(res), _p(w), _p(b), _p(x), _p(yb), _p(yf), M, D, float(eps),
+                                             float(p_in), int(seed_in), float(p_out), int(seed_out), _s()),
+               "mh_layernorm_fwd_dropout")
+    return x, yb, yf
+
+
+def layernorm_bwd_dropout(dy, x, w, eps: float, p_in: float = 0.0, seed_in: int = 0, p_out: float = 0.0, seed_out: int = 0,
+                          want_bf16=True):
+    """Backward of layernorm_fwd_dropout: (dL/dx f32 -- the residual's gradient --, dL/dz = dL/dx * mask_in as bf16)."""
+    M, D = x.shape
+    dx = torch.empty((M, D), dtype=F32, device=x.device)
+    dzb = torch.empty((M, D), dtype=BF16, device=x.device) if want_bf16 else None
+    _lib.check(_L().mh_layernorm_bwd_dropout(_p(dy), _p(x), _p(w), _p(dx), _p(dzb), M, D, float(eps), float(p_in),
+                                             int(seed_in), float(p_out), int(seed_out), _s()), "mh_layernorm_bwd_dropout")
+    return dx, dzb
+
+
+def dropout_keep_mask(n: int, p: float, seed: int, device):
+    """The keep mask the dropout kernels use: element i = 1/(1-p) if kept, else 0 (flat index i of the masked tensor)."""
+    out = torch.empty((n,), dtype=F32, device=device)
+    _lib.check(_L().mh_dropout_keep_mask(_p(out), int(n), float(p), int(seed), _s()), "mh_dropout_keep_mask")
+    return out
+
+
+def gemm_tn_wgrad(dy: torch.Tensor, x: torch.Tensor, out: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                  accumulate: bool = False, splits: int = 0):
+    """out[N,K] (+)= dy^T . x for row-major bf16 dy [M,N] and x [M,K] (no transposed copies), fp32 into `out` (row-strided);
+    `bias` [N] f32 (+)= the column sums of dy in the same launch.  splits = 0: the library's M-split choice."""
+    _chk2d(dy, BF16, "dy")
+    _chk2d(x, BF16, "x")
+    M, N = dy.shape
+    K = x.shape[1]
+    if x.shape[0] != M or out.dtype != F32 or out.dim() != 2 or tuple(out.shape) != (N, K) or out.stride(1) != 1:
+        raise ValueError(f"gemm_tn_wgrad: dy {tuple(dy.shape)} x {tuple(x.shape)} out {tuple(out.shape)} {out.dtype}")
+    if bias is not None and (bias.dtype != F32 or bias.numel() != N or not bias.is_contiguous()):
+        raise ValueError("gemm_tn_wgrad: bias must be contiguous f32 [N]")
+    L = _L()
+    s = int(splits) if splits else L.mh_gemm_tn_wgrad_auto_splits(M, N, K)
+    n = L.mh_gemm_tn_wgrad_ws_floats(M, N, K, s)
+    ws = torch.empty((n,), dtype=F32, device=dy.device) if n > 0 else None
+    _lib.check(L.mh_gemm_tn_wgrad(_p(dy), dy.stride(0), _p(x), x.stride(0), _p(out), out.stride(0), _p(bias), M, N, K,
+                                  int(accumulate), s, _p(ws), n, _s()), f"mh_gemm_tn_wgrad M={M} N={N} K={K}")
+    return out
 
 
 # --------------------------------------------------------------------------- elementwise
