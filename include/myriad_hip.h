@@ -378,6 +378,24 @@ int mh_gemv_packed_fp8_rmsnorm(const float* H, long ldh, const float* norm_w, fl
                                int out_f32, float alpha, mh_stream_t s);
 int mh_gemv_packed_fp8_silu(const void* gu, long ldgu, const void* Q, const float* scale, void* C, int ldc, int M, int N, int K,
                             const float* bias, const float* residual, int ldr, int out_f32, float alpha, mh_stream_t s);
+/* q / v LoRA merged into the decode step's copy of the frozen qkv weight (opt-in, llama.py decode_merge_lora; PEFT merge_adapter).
+ * W [3D, D] bf16 rows [q | k | v] with leading dimension ldw (the frozen columns of the bordered wqkv_ext), Aqv [2r, D] fp32 = the
+ * masters A_q | A_v, Bq / Bv [D, r] fp32, s = alpha / r, r = 8 or 16.  Merged rule, per element:
+ *   q rows n < D:        bf16(W[n,k] + s * acc), acc = sum over j = 0 .. r-1 in order of Bq[n,j] * A_q[j,k], starting from 0
+ *   k rows D <= n < 2D:  W[n,k]
+ *   v rows n >= 2D:      the q rule with Bv[n - 2D] and A_v
+ * each product and sum a separate fp32 operation rounded to nearest even (no FMA contraction), then one round-to-nearest-even to
+ * bf16.  mh_lora_merge writes the merged matrix row-major (out [3D, ldo]); mh_lora_merge_pack writes the mh_gemv_pack copy of it
+ * (mh_gemv_pack_elems(3D, D) elements) and mh_lora_merge_pack_fp8 the mh_gemv_pack_fp8 codes and row scales of it
+ * (mh_gemv_pack_fp8_elems(3D, D) bytes, 3D scales), bit for bit, each in one pass from W.  MH_ERR_ARG on D <= 0 or D % 64 != 0,
+ * r not 8 / 16, ldw (ldo) < D or not a multiple of 8, a null pointer, W / Aqv / out / q_out not 16-byte aligned, or Bq / Bv /
+ * scale_out not 4-byte aligned. */
+int mh_lora_merge(const void* W, int ldw, const float* Aqv, const float* Bq, const float* Bv, int D, int r, float s, void* out,
+                  int ldo, mh_stream_t stream);
+int mh_lora_merge_pack(const void* W, int ldw, const float* Aqv, const float* Bq, const float* Bv, int D, int r, float s, void* out,
+                       mh_stream_t stream);
+int mh_lora_merge_pack_fp8(const void* W, int ldw, const float* Aqv, const float* Bq, const float* Bv, int D, int r, float s,
+                           void* q_out, float* scale_out, mh_stream_t stream);
 /* One decode token of attention (modeling_llama.py:186-222 with the KV cache): rotary on q / k, k | v appended at cache row
  * pos_dev[0], the one query against kv_len[b] keys -- mh_rope_kv_append + mh_attn_fwd(Sq = 1) in one launch, same bits.
  * qkv [B, ld_qkv] bf16 = [q | k | v] (q rotated in place), cache [B][T_cap][2 H D] rows [k | v], out [B, H D] bf16. */

@@ -253,6 +253,7 @@ class Chat:
         m = self.model
         m.finish_update()
         llama = m.llama
+        llama.decode_lora_version = m.store.version                 # decode_merge_lora re-merges only when the LoRA weights moved
         rep = 1.0 if repetition_penalty is None else float(repetition_penalty)
         if rep != 1.0 and not llama.device_sampling:
             raise NotImplementedError(f"answer(repetition_penalty={rep}) needs the device sampling switch "

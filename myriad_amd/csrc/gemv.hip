@@ -23,6 +23,7 @@
 // epilogue, once per output column, after the cross-wave sum and BEFORE alpha:  v = (sum_k x q * s_n) * alpha (+bias)(+res).
 // Activations are never quantised.
 #include "common.h"
+#include "gemv_pack.h"
 #include <cstdlib>
 
 typedef unsigned char fp8_t;                                        // one OCP e4m3fn code
@@ -224,7 +225,7 @@ int mh_launch_gemv(const void* A, int lda, const void* B, int ldb, void* C, int 
 }
 
 // ---- stream-ordered weight copy for decode (288 GB of HBM: a second, 13.5 GB copy of the frozen LLaMA weights is cheap) ----
-static inline int gv_packed_nw(int N) { return ((N + 15) / 16 < 512) ? 8 : 4; }   // the launch rule above, without the env knob
+// gv_packed_nw (gemv_pack.h) is the launch rule above, without the env knob
 
 __global__ void gemv_pack_kernel(const bf16_t* __restrict__ W, int ldb, int N, int K, bf16_t* __restrict__ out, int nw, int per,
                                  long chunks) {
@@ -296,14 +297,6 @@ extern "C" int mh_gemv_packed(const void* A, int lda, const void* P, void* C, in
 // 1 for an all-zero row) and q = e4m3fn(clamp(W / s_n, -448, 448)) rounded to nearest even -- torch's
 // (W.float() / s[:, None]).clamp(-448, 448).to(torch.float8_e4m3fn), bit for bit.  Rows past N repeat row N - 1 (as the bf16
 // copy); their results are never stored.
-__device__ __forceinline__ unsigned f32_to_e4m3fn(float x) {        // |x| <= 448, not NaN
-  const unsigned u = __float_as_uint(x), sign = (u >> 24) & 0x80u, a = u & 0x7fffffffu;
-  if (a < 0x3c800000u)                                              // |x| < 2^-6: subnormal codes m * 2^-9 (m = 8 is 2^-6)
-    return sign | (unsigned)rintf(__uint_as_float(a) * 512.f);      // exact scaling, rintf rounds half to even
-  const unsigned r = (a + 0x7ffffu + ((a >> 20) & 1u)) >> 20;       // 3 mantissa bits, half to even (a carry bumps the exponent)
-  return sign | (r - (120u << 3));                                  // rebias 127 -> 7
-}
-
 __global__ __launch_bounds__(256) void gemv_pack_fp8_kernel(const bf16_t* __restrict__ W, int ldb, int N, int K,
                                                             unsigned char* __restrict__ out, float* __restrict__ scale_out, int nw,
                                                             int per) {

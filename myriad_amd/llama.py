@@ -37,6 +37,12 @@ def decode_fp8_from_env() -> bool:
     return os.environ.get("MYRIAD_DECODE_FP8", "0") != "0"
 
 
+def decode_merge_lora_from_env() -> bool:
+    """The default of LlamaHIP.decode_merge_lora: MYRIAD_DECODE_MERGE_LORA=1 folds the q/v LoRA into the token step's qkv copy
+    (off when unset)."""
+    return os.environ.get("MYRIAD_DECODE_MERGE_LORA", "0") != "0"
+
+
 class LlamaHIP:
     def __init__(self, sd: Dict[str, torch.Tensor], n_heads: int, device, eps: float = 1e-6,
                  prefix: str = "llama_model.", max_pos: int = 2048, need_backward: bool = True):
@@ -104,6 +110,14 @@ class LlamaHIP:
         # the bf16 ones (ops.gemv_pack_fp8; half the bytes, weight rounding the only new error); off by default, the attribute
         # wins over MYRIAD_DECODE_FP8
         self.decode_fp8 = decode_fp8_from_env()
+        # with LoRA attached, the packed token step streams W_qkv with the q/v LoRA merged in (PEFT merge_adapter on the decode copy
+        # only: LoraQV.merge) instead of the bordered wqkv_ext -- four launches per layer instead of five, and fp8 under decode_fp8;
+        # the prefill and steps above 16 rows keep the exact bordered LoRA.  Off by default, the attribute wins over
+        # MYRIAD_DECODE_MERGE_LORA.  The merge is redone only when decode_lora_version (set by its owner before a call: MyriadHIP
+        # hands ParamStore.version) differs from the merged copy's; None re-merges at every call.
+        self.decode_merge_lora = decode_merge_lora_from_env()
+        self.decode_lora_version = None
+        self._lora_merges = 0                                           # whole-model merges so far (last_generate_stats)
         self._packed = None                                             # the packed copies of the current kind (one of _packs)
         self._packs = {}                                                # "bf16" / "fp8" -> packed copies, each built on first use
         self._decode_ws = {}
@@ -114,33 +128,51 @@ class LlamaHIP:
         With decode_fp8 the decoder matrices wo, wgu, wd -- and wqkv while no LoRA is attached -- are fp8 copies
         (ops.gemv_pack_fp8) in place of the bf16 ones; the bordered wqkv_ext (one row scale would be shared by W and the moving
         B columns) and lm_head (its arg-max picks the ids) stay bf16.  Each kind is built on its first use and kept, so flipping
-        the switch between calls works, and the workspace key holds the kind: no graph captured on one is replayed on the other."""
+        the switch between calls works, and the workspace key holds the kind: no graph captured on one is replayed on the other.
+        With decode_merge_lora and LoRA attached the qkv entry is instead the [3D, D] copy with the q/v LoRA merged in
+        (LoraQV.merge: fp8 under decode_fp8, bf16 otherwise), re-merged in place only when decode_lora_version is None or differs
+        from the one it was merged for.  The bordered and the merged copies are both kept once built (the workspace key holds
+        which one the step reads), so flipping decode_merge_lora frees no buffer that a captured graph reads."""
         kind = "fp8" if self.decode_fp8 else "bf16"
-        qkv_key = "wqkv" if self.lora is None else "wqkv_ext"
+        merge = self.lora is not None and self.decode_merge_lora
+        qkv_key = "wqkv" if self.lora is None else ("merged" if merge else "wqkv_ext")
         P = self._packs.get(kind)
         if P is None:
             pack = ops.gemv_pack_fp8 if kind == "fp8" else ops.gemv_pack
             lm = next(iter(self._packs.values()))["lm_head"] if self._packs else ops.gemv_pack(self.lm_head)
-            P = dict(kind=kind, layers=[{k: pack(L[k]) for k in ("wo", "wgu", "wd")} for L in self.layers], lm_head=lm, qkv_key=None)
+            P = dict(kind=kind, layers=[{k: pack(L[k]) for k in ("wo", "wgu", "wd")} for L in self.layers], lm_head=lm, qkv_key=None,
+                     qkv={}, merged_for=None, merge_id=None)
             self._packs[kind] = P
-        if P["qkv_key"] != qkv_key or self.lora is not None:
+        copies = P["qkv"].get(qkv_key)
+        if merge:
+            ver = self.decode_lora_version
+            if copies is None or ver is None or P["merged_for"] != ver:
+                copies = self.lora.merge(self.layers, kind, copies)
+                self._lora_merges += 1
+                P["merged_for"], P["merge_id"] = ver, self._lora_merges
+        elif copies is None or self.lora is not None:
             pack = ops.gemv_pack_fp8 if kind == "fp8" and self.lora is None else ops.gemv_pack
-            for L, Pl in zip(self.layers, P["layers"]):
-                Pl["wqkv"] = pack(L[qkv_key], out=Pl.get("wqkv") if P["qkv_key"] == qkv_key else None)
-            P["qkv_key"] = qkv_key
+            copies = [pack(L[qkv_key], out=None if copies is None else copies[i]) for i, L in enumerate(self.layers)]
+        P["qkv"][qkv_key] = copies
+        for Pl, c in zip(P["layers"], copies):
+            Pl["wqkv"] = c
+        P["qkv_key"] = qkv_key
         self._packed = P
 
     def _decode_weight_stats(self, rows: int) -> dict:
         """last_generate_stats' decode_weights ("fp8" / "bf16": what the token step streams) and decode_weight_bytes (the weight
-        bytes of one token step: the packed copies, fp8 scales included, up to 16 rows; the row-major bf16 matrices above)."""
+        bytes of one token step: the packed copies, fp8 scales included, up to 16 rows; the row-major bf16 matrices above),
+        lora_merged (the step streams the LoRA-merged qkv copy) and lora_merges (whole-model merges this model has made so far)."""
         if self._packed is not None and rows <= 16:
             mats = [P[k] for P in self._packed["layers"] for k in ("wqkv", "wo", "wgu", "wd")] + [self._packed["lm_head"]]
             nbytes = sum(m.data.numel() * m.data.element_size() + (m.scales.numel() * 4 if isinstance(m, ops.PackedFp8Weight) else 0)
                          for m in mats)
-            return dict(decode_weights=self._packed["kind"], decode_weight_bytes=int(nbytes))
+            return dict(decode_weights=self._packed["kind"], decode_weight_bytes=int(nbytes),
+                        lora_merged=self._packed["qkv_key"] == "merged", lora_merges=self._lora_merges)
         qkv_key = "wqkv" if self.lora is None else "wqkv_ext"
         mats = [L[k] for L in self.layers for k in (qkv_key, "wo", "wgu", "wd")] + [self.lm_head]
-        return dict(decode_weights="bf16", decode_weight_bytes=int(sum(m.numel() * m.element_size() for m in mats)))
+        return dict(decode_weights="bf16", decode_weight_bytes=int(sum(m.numel() * m.element_size() for m in mats)),
+                    lora_merged=False, lora_merges=self._lora_merges)
 
     def attach_lora(self, lora) -> None:
         """Enable PEFT-style LoRA on q_proj/v_proj (myriad_amd.lora.LoraQV); replaces W_qkv by its bordered copy."""
@@ -336,6 +368,8 @@ class LlamaHIP:
         H, hd, W, D = self.H, self.hd, self.D, self.D
         M = B * S
         packed = self._packed["layers"] if (pos_dev is not None and M <= 16 and self._packed is not None) else None
+        # the bordered LoRA product unless the packed qkv copy has the LoRA merged in (decode_merge_lora)
+        lora = None if packed is not None and self._packed["qkv_key"] == "merged" else self.lora
 
         def lin(li, name, x, **kw):
             if packed is not None:
@@ -348,15 +382,16 @@ class LlamaHIP:
         # to the launches it replaces (tests/test_kernels_gpu.py), MYRIAD_DECODE_FUSED=0 keeps the separate launches.
         # With LoRA attached the qkv product takes the bordered operand [xn | s A xn]: the norm and the LoRA down projection are
         # one launch (LoraQV.norm_border, <= 2 rows), the bordered packed weight the next -- five launches per layer become six.
+        # With the LoRA merged into the packed qkv copy (decode_merge_lora) the step is the no-LoRA one.
         fused = packed is not None and self.decode_fused
         for li, (L, cache) in enumerate(zip(self.layers, caches)):
             if fused:
                 P = packed[li]
-                if self.lora is not None:
-                    x_ext = self.lora.x_ext(li, M)
-                    if not self.lora.norm_border(li, h, L["ln1"], self.eps, x_ext):
+                if lora is not None:
+                    x_ext = lora.x_ext(li, M)
+                    if not lora.norm_border(li, h, L["ln1"], self.eps, x_ext):
                         ops.rmsnorm_fwd(h, L["ln1"], self.eps, out=x_ext[:, :D])
-                        self.lora.forward_border(li, x_ext, training=False)
+                        lora.forward_border(li, x_ext, training=False)
                     qkv = ops.gemv_packed(x_ext, P["wqkv"])
                 else:
                     qkv = ops.gemv_packed_rmsnorm(h, L["ln1"], self.eps, P["wqkv"])
@@ -373,13 +408,13 @@ class LlamaHIP:
                 hn = ops.gemv_packed_silu(gu, P["wd"], residual=h2, out_dtype=F32)
                 h = hn if hn is not None else ops.gemv_packed(ops.silu_mul_fwd_blk(gu), P["wd"], residual=h2, out_dtype=F32)
                 continue
-            if self.lora is None:
+            if lora is None:
                 xn = ops.rmsnorm_fwd(h, L["ln1"], self.eps)
                 qkv = lin(li, "wqkv", xn)
             else:
-                x_ext = self.lora.x_ext(li, M)
+                x_ext = lora.x_ext(li, M)
                 ops.rmsnorm_fwd(h, L["ln1"], self.eps, out=x_ext[:, :D])
-                self.lora.forward_border(li, x_ext, training=False)
+                lora.forward_border(li, x_ext, training=False)
                 qkv = lin(li, "wqkv_ext", x_ext)
             q3 = qkv.view(B, S, 3 * W)
             if pos_dev is None:
@@ -838,9 +873,9 @@ class DecodeSession:
     know, recorded as a key that matches nothing).
 
     The whole cache is dropped (full prefill, `last_stats["full_reprefill_reason"]`) when the caller's weights version changes
-    (optimiser update, state-dict load), when the decode weights change kind (bf16 / fp8, LoRA on / off), when the batch size
-    changes, when the capacity (round_up(need + 2, 64), at most 8192) is exceeded, or when the caller says so (`reset_reason`: the
-    chat's truncation window moved)."""
+    (optimiser update, state-dict load), when the decode weights change kind (bf16 / fp8, LoRA on / off, the LoRA-merged qkv copy
+    on / off or re-merged: "decode weights changed"), when the batch size changes, when the capacity (round_up(need + 2, 64), at
+    most 8192) is exceeded, or when the caller says so (`reset_reason`: the chat's truncation window moved)."""
 
     def __init__(self, llama: "LlamaHIP", capacity: int, split: Optional[bool] = None):
         self.llama = llama
@@ -880,7 +915,10 @@ class DecodeSession:
             raise ValueError(f"context {S0} + max_new_tokens {max_new_tokens} passes the rotary table ({L.cos.shape[0]} positions)")
         if len(keys) != B or any(len(k) != S0 for k in keys):
             raise ValueError("one key per context position and batch row is required")
-        kind = None if L._packed is None else (L._packed["kind"], L._packed["qkv_key"], id(L._packed))
+        # the merged qkv copy is rewritten in place by a re-merge: its merge id joins the stamp, so no KV row survives a change of
+        # the weights the step multiplies by, whether or not the caller's weights_version saw it
+        kind = None if L._packed is None else (L._packed["kind"], L._packed["qkv_key"], id(L._packed),
+                                                L._packed["merge_id"] if L._packed["qkv_key"] == "merged" else None)
         stamp = (version, kind, L.decode_fused, L.lora is not None)
         need = S0 + max_new_tokens + 2
         if self.bufs is None:

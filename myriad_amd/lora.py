@@ -41,6 +41,12 @@ def lora_param_specs(n_layers: int, D: int, r: int) -> List[Tuple[str, Tuple[int
     return specs
 
 
+def merged_qv_names(i: int) -> Tuple[str, str]:
+    """The reference LLaMA's names of layer i's q_proj / v_proj weights: the keys of a merge_and_unload state dict."""
+    p = f"llama_model.model.layers.{i}.self_attn."
+    return p + "q_proj.weight", p + "v_proj.weight"
+
+
 def init_lora_weights(n_layers: int, D: int, r: int, seed: int, device, zero_b: bool = True) -> Dict[str, torch.Tensor]:
     """peft init: lora_A kaiming_uniform(a=sqrt(5)) => U(-1/sqrt(D), 1/sqrt(D)); lora_B zeros."""
     g = torch.Generator(device="cpu").manual_seed(seed)
@@ -116,6 +122,19 @@ class LoraQV:
             self._refresh_ld, self._refresh_key = lds.pop(), key
         _lib.check(_lib.load().mh_lora_refresh_borders(self._refresh_tab.data_ptr(), len(layers), self._refresh_ld[0],
                                                        self._refresh_ld[1], W, D, r, ops._s()), "mh_lora_refresh_borders")
+
+    # ---- merged copies for the decode step (LlamaHIP.decode_merge_lora): PEFT merge_adapter on a copy, W_ext untouched ------
+    def merge_layer(self, layer_idx: int, layer: dict, kind: str = "rows", out=None):
+        """Layer `layer_idx`'s frozen qkv weight (the first D columns of wqkv_ext) with this layer's q / v LoRA folded in from the
+        fp32 masters of P: "rows" a row-major bf16 [3D, D] tensor (ops.lora_merge), "bf16" a PackedWeight (ops.lora_merge_pack),
+        "fp8" a PackedFp8Weight (ops.lora_merge_pack_fp8).  `out` re-uses an earlier result's storage."""
+        fn = {"rows": ops.lora_merge, "bf16": ops.lora_merge_pack, "fp8": ops.lora_merge_pack_fp8}[kind]
+        _, _, nbq, nbv = self.names(layer_idx)
+        return fn(layer["wqkv_ext"][:, :self.D], self._aqv(self.P, layer_idx), self.P[nbq], self.P[nbv], self.s, out=out)
+
+    def merge(self, layers: List[dict], kind: str = "rows", outs=None) -> list:
+        """merge_layer for every layer (one launch each); `outs` the list an earlier call returned, re-used in place."""
+        return [self.merge_layer(i, L, kind, None if outs is None else outs[i]) for i, L in enumerate(layers)]
 
     def _seed(self, layer_idx: int) -> int:
         return (self.base_seed * 0x9E3779B97F4A7C15 + self.step_seed * 1315423911 + layer_idx * 2654435761 + 12345) \

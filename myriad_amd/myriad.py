@@ -393,6 +393,23 @@ class MyriadHIP(nn.Module):
             out[name] = to_reference_layout(self.store.p[name].detach(), rshape).cpu()
         return out
 
+    @torch.no_grad()
+    def merged_lora_state_dict(self) -> "OrderedDict[str, torch.Tensor]":
+        """PEFT's merge_and_unload view of the q/v LoRA: per layer the merged q_proj / v_proj weights (bf16 [D, D], on the device)
+        under the reference LLaMA names llama_model.model.layers.{i}.self_attn.{q,v}_proj.weight (lora.merged_qv_names), computed
+        by the merge kernel's row-major output from the current fp32 masters (ops.lora_merge: the rule of
+        include/myriad_hip.h).  The model itself keeps its unmerged LoRA.  Raises without LoRA."""
+        if not self.use_lora:
+            raise ValueError("merged_lora_state_dict: no LoRA is attached (cfg use_lora)")
+        from .lora import merged_qv_names
+        self.finish_update()
+        out, D = OrderedDict(), self.Dl
+        for i, L in enumerate(self.llama.layers):
+            m = self.lora.merge_layer(i, L, "rows")
+            nq, nv = merged_qv_names(i)
+            out[nq], out[nv] = m[:D].clone(), m[2 * D:].clone()
+        return out
+
     def load_state_dict(self, sd, strict: bool = False):
         self.finish_update()                              # a delayed update must not land on top of the loaded values
         self.store.version += 1
@@ -1158,6 +1175,7 @@ class MyriadHIP(nn.Module):
         emb = emb[:, 1:].contiguous()         # generate() wraps without BOS (myriad.py:446-449)
         if max_new is None:
             max_new = max(1, max_len - emb.shape[1])
+        self.llama.decode_lora_version = self.store.version    # decode_merge_lora re-merges only when the LoRA weights moved
         if num_beams > 1:
             ids = self.llama.beam_generate(emb, num_beams, max_new_tokens=max_new, stop_ids=stops, eos_id=eos_id,
                                            min_length=min_length, **beam_kw)

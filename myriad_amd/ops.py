@@ -224,6 +224,64 @@ def gemv_pack_fp8(w: torch.Tensor, out: Optional[PackedFp8Weight] = None) -> Pac
     return out
 
 
+def _lora_merge_args(w: torch.Tensor, a_qv: torch.Tensor, b_q: torch.Tensor, b_v: torch.Tensor, name: str):
+    """(D, r) of a merge: w [3D, D] bf16 (unit inner stride, any leading dimension: the frozen columns of wqkv_ext), a_qv [2r, D]
+    and b_q / b_v [D, r] fp32 with contiguous rows."""
+    _chk2d(w, BF16, name + ".w")
+    N, D = w.shape
+    if N != 3 * D:
+        raise _lib.MyriadHipError(f"{name}: w must be [3D, D], got {tuple(w.shape)}")
+    r = a_qv.shape[0] // 2 if a_qv.dim() == 2 else 0
+    for t, shape, what in ((a_qv, (2 * r, D), "a_qv"), (b_q, (D, r), "b_q"), (b_v, (D, r), "b_v")):
+        if t.dtype != F32 or not t.is_cuda or tuple(t.shape) != shape or t.stride() != (shape[1], 1):
+            raise _lib.MyriadHipError(f"{name}: {what} must be a contiguous cuda f32 {shape}, got {t.dtype} {tuple(t.shape)} "
+                                      f"strides {t.stride()}")
+    return D, r
+
+
+def lora_merge(w: torch.Tensor, a_qv: torch.Tensor, b_q: torch.Tensor, b_v: torch.Tensor, s: float,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The q / v LoRA folded into the frozen qkv weight (PEFT merge_adapter), row-major bf16 [3D, D]: q rows
+    bf16(w + s * sum_j b_q[:, j] a_q[j]), v rows the same with b_v / a_v, k rows w (the rule: include/myriad_hip.h mh_lora_merge)."""
+    D, r = _lora_merge_args(w, a_qv, b_q, b_v, "lora_merge")
+    if out is None:
+        out = torch.empty((3 * D, D), dtype=BF16, device=w.device)
+    else:
+        _chk2d(out, BF16, "lora_merge.out")
+        if out.shape != (3 * D, D):
+            raise _lib.MyriadHipError(f"lora_merge: out shape {tuple(out.shape)} != {(3 * D, D)}")
+    _lib.check(_L().mh_lora_merge(_p(w), w.stride(0), _p(a_qv), _p(b_q), _p(b_v), D, r, float(s), _p(out), out.stride(0), _s()),
+               f"mh_lora_merge D={D} r={r}")
+    return out
+
+
+def lora_merge_pack(w: torch.Tensor, a_qv: torch.Tensor, b_q: torch.Tensor, b_v: torch.Tensor, s: float,
+                    out: Optional[PackedWeight] = None) -> PackedWeight:
+    """gemv_pack(lora_merge(...)) bit for bit, written in one pass from w; `out` re-uses an earlier copy's storage."""
+    D, r = _lora_merge_args(w, a_qv, b_q, b_v, "lora_merge_pack")
+    if out is None:
+        out = PackedWeight(torch.empty((_L().mh_gemv_pack_elems(3 * D, D),), dtype=BF16, device=w.device), 3 * D, D)
+    elif not isinstance(out, PackedWeight) or (out.N, out.K) != (3 * D, D):
+        raise _lib.MyriadHipError("lora_merge_pack: out is not a PackedWeight of this shape")
+    _lib.check(_L().mh_lora_merge_pack(_p(w), w.stride(0), _p(a_qv), _p(b_q), _p(b_v), D, r, float(s), _p(out.data), _s()),
+               f"mh_lora_merge_pack D={D} r={r}")
+    return out
+
+
+def lora_merge_pack_fp8(w: torch.Tensor, a_qv: torch.Tensor, b_q: torch.Tensor, b_v: torch.Tensor, s: float,
+                        out: Optional[PackedFp8Weight] = None) -> PackedFp8Weight:
+    """gemv_pack_fp8(lora_merge(...)) bit for bit (codes and row scales of the merged bf16 rows), in one pass from w."""
+    D, r = _lora_merge_args(w, a_qv, b_q, b_v, "lora_merge_pack_fp8")
+    if out is None:
+        out = PackedFp8Weight(torch.empty((_L().mh_gemv_pack_fp8_elems(3 * D, D),), dtype=torch.uint8, device=w.device),
+                              torch.empty((3 * D,), dtype=F32, device=w.device), 3 * D, D)
+    elif not isinstance(out, PackedFp8Weight) or (out.N, out.K) != (3 * D, D):
+        raise _lib.MyriadHipError("lora_merge_pack_fp8: out is not a PackedFp8Weight of this shape")
+    _lib.check(_L().mh_lora_merge_pack_fp8(_p(w), w.stride(0), _p(a_qv), _p(b_q), _p(b_v), D, r, float(s), _p(out.data),
+                                           _p(out.scales), _s()), f"mh_lora_merge_pack_fp8 D={D} r={r}")
+    return out
+
+
 def gemv_packed(a: torch.Tensor, pw, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
                 residual: Optional[torch.Tensor] = None, out_dtype=BF16, alpha: float = 1.0) -> torch.Tensor:
     """out[M<=16, N] = alpha * a @ W^T (+bias) (+residual f32) with W given as its packed copy; same bits as gemm().

@@ -5,7 +5,9 @@ python tools/decode_bench.py [--batch 1] [--new 32] [--sample] [--penalty P] [--
 host); --modes times several decodes in one process, interleaved per repeat: greedy, host (sampled, host draw), device (sampled,
 device draw), beam (num_beams = --beams, which also times greedy at batch * beams: the same row count); --penalty adds
 repetition_penalty to every mode but beam.  --weights bf16,fp8 times each mode with the token step streaming bf16 and FP8 weight
-copies (LlamaHIP.decode_fp8), interleaved in the same way; without it the kind is MYRIAD_DECODE_FP8's."""
+copies (LlamaHIP.decode_fp8), interleaved in the same way; without it the kind is MYRIAD_DECODE_FP8's.  --merge 0,1 (with --lora 1)
+times each of those with the bordered LoRA qkv product and with the LoRA merged into the step's qkv copy
+(LlamaHIP.decode_merge_lora), interleaved again, and reports the one-time cost of merging every layer (bf16 and fp8 copies)."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -23,12 +25,16 @@ ap.add_argument("--modes", default="", help="comma list of greedy / host / devic
 ap.add_argument("--repeats", type=int, default=1)
 ap.add_argument("--beams", type=int, default=4, help="num_beams of the beam mode")
 ap.add_argument("--weights", default="", help="comma list of bf16 / fp8: the token step's weight copies, timed interleaved")
+ap.add_argument("--merge", default="", help="comma list of 0 / 1: bordered / merged LoRA qkv in the token step, timed interleaved")
 a = ap.parse_args()
 modes = [m for m in a.modes.split(",") if m] or ["sample" if a.sample else "greedy"]
 if "beam" in modes and "greedy" in modes:
     modes.append("greedy_x%d" % a.beams)             # greedy at batch * beams rows: the beam step's row count
 kinds = [w for w in a.weights.split(",") if w] or [None]
 assert all(w in (None, "bf16", "fp8") for w in kinds), kinds
+merges = [int(m) for m in a.merge.split(",") if m] or [None]
+assert all(m in (None, 0, 1) for m in merges), merges
+assert a.lora or merges == [None], "--merge needs --lora 1"
 dev = "cuda:0"
 cfg = full_config(llm_layers=a.llm_layers)
 model = MyriadHIP(SyntheticWeights(cfg, dev, seed=0), dict(need_backward=False, use_lora=bool(a.lora)), device=dev)
@@ -47,9 +53,10 @@ smp = make_samples(B)
 smp_rows = make_samples(B * a.beams) if "beam" in modes else None
 default_dev = model.llama.device_sampling
 default_fp8 = model.llama.decode_fp8
+default_merge = model.llama.decode_merge_lora
 
 
-def run(n, mode, kind=None):
+def run(n, mode, kind=None, merge=None):
     kw, sm = {}, smp
     if mode == "beam":
         kw = dict(num_beams=a.beams, early_stopping="never")    # no early stop: every run decodes n tokens
@@ -61,6 +68,7 @@ def run(n, mode, kind=None):
         kw["repetition_penalty"] = a.penalty
     model.llama.device_sampling = {"host": False, "device": True}.get(mode, default_dev)
     model.llama.decode_fp8 = default_fp8 if kind is None else kind == "fp8"
+    model.llama.decode_merge_lora = default_merge if merge is None else bool(merge)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     out = model.generate(sm, max_new_tokens=n, stop_ids=((-1,),), min_length=0, eos_token_id=-5, **kw)
@@ -68,28 +76,49 @@ def run(n, mode, kind=None):
     return time.perf_counter() - t0, out
 
 
-runs = [(m, w) for m in modes for w in kinds]
-for m, w in runs:
-    run(2, m, w); run(6, m, w)           # warm-up: kernels, then the token-step graph of this batch size is captured
+runs = [(m, w, mg) for m in modes for w in kinds for mg in merges]
+for m, w, mg in runs:
+    run(2, m, w, mg); run(6, m, w, mg)   # warm-up: kernels, then the token-step graph of this batch size is captured
 res = {r: [] for r in runs}
 for _ in range(a.repeats):
-    for m, w in runs:
-        t_short, _ = run(a.new // 4, m, w)
-        t_long, out = run(a.new, m, w)
+    for m, w, mg in runs:
+        t_short, _ = run(a.new // 4, m, w, mg)
+        t_long, out = run(a.new, m, w, mg)
         n_long, n_short = out["token_ids"].shape[1], a.new // 4
         if m == "beam":
             n_long = model.last_generate_stats["steps"]       # hypotheses may end before the last step; the step count does not
-        res[(m, w)].append(((t_long - t_short) / (n_long - n_short), t_long, n_long, dict(model.last_generate_stats)))
-for m, w in runs:
-    ts = sorted(r[0] for r in res[(m, w)])
-    per_tok, t_long, n_long, st = res[(m, w)][-1]
+        res[(m, w, mg)].append(((t_long - t_short) / (n_long - n_short), t_long, n_long, dict(model.last_generate_stats)))
+for m, w, mg in runs:
+    ts = sorted(r[0] for r in res[(m, w, mg)])
+    per_tok, t_long, n_long, st = res[(m, w, mg)][-1]
     per_tok = ts[len(ts) // 2]                        # prefill / vision cancel: pure single-token decode steps (median)
     extra = (f" [{m}: device-drawn rows {st.get('device_sampled_rows', 0)}, host-drawn {st.get('host_sampled_rows', 0)}, "
              f"graph replays {st.get('graph_replays', 0)}]" if m != "greedy" or a.penalty != 1.0 else "")
     rows = B * a.beams if m in ("beam", "greedy_x%d" % a.beams) else B
     wb = st["decode_weight_bytes"]
-    print(f"batch {B} rows {rows}{' +LoRA' if a.lora else ''} {m} weights {st['decode_weights']}"
+    lora_tag = (" +LoRA merged" if st.get("lora_merged") else " +LoRA") if a.lora else ""
+    print(f"batch {B} rows {rows}{lora_tag} {m} weights {st['decode_weights']}"
           f"{f' penalty {a.penalty}' if a.penalty != 1.0 else ''}: {n_long} tokens in "
           f"{t_long*1e3:.1f} ms (incl. ViT+Q-Former+prefill); decode step {per_tok*1e3:.3f} ms/token (median of {len(ts)}, "
           f"min {ts[0]*1e3:.3f}, max {ts[-1]*1e3:.3f}) -> {rows / per_tok:.1f} row-tok/s steady; weight stream "
           f"{wb / 1e9:.2f} GB/token, {wb / per_tok / 1e12:.2f} TB/s of 6.3 achievable{extra}")
+
+if a.lora and 1 in merges:
+    # one-time cost of a merge of every layer (what generate() pays when the LoRA weights moved), median of --repeats
+    L = model.llama
+    for kind in ("bf16", "fp8"):
+        outs = L.lora.merge(L.layers, kind)
+        ts = []
+        for _ in range(max(3, a.repeats)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            L.lora.merge(L.layers, kind, outs)
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        ts.sort()
+        D, nl = L.D, len(L.layers)
+        rd, wr = nl * 3 * D * D * 2 * (2 if kind == "fp8" else 1), nl * 3 * D * D * (1 if kind == "fp8" else 2)
+        print(f"merge of {nl} layers into the {kind} copy: {ts[len(ts) // 2] * 1e3:.3f} ms (median of {len(ts)}, min "
+              f"{ts[0] * 1e3:.3f}); W read {rd / 1e9:.2f} GB (fp8: two passes), written {wr / 1e9:.2f} GB -> "
+              f"{(rd + wr) / ts[len(ts) // 2] / 1e12:.2f} TB/s")
+        del outs
