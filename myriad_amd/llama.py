@@ -112,7 +112,7 @@ class LlamaHIP:
         self.decode_fp8 = decode_fp8_from_env()
         # with LoRA attached, the packed token step streams W_qkv with the q/v LoRA merged in (PEFT merge_adapter on the decode copy
         # only: LoraQV.merge) instead of the bordered wqkv_ext -- four launches per layer instead of five, and fp8 under decode_fp8;
-        # the prefill and steps above 16 rows keep the exact bordered LoRA.  Off by default, the attribute wins over
+        # the prefill and steps above GEMV_MAX_ROWS rows keep the exact bordered LoRA.  Off by default, the attribute wins over
         # MYRIAD_DECODE_MERGE_LORA.  The merge is redone only when decode_lora_version (set by its owner before a call: MyriadHIP
         # hands ParamStore.version) differs from the merged copy's; None re-merges at every call.
         self.decode_merge_lora = decode_merge_lora_from_env()
@@ -159,11 +159,19 @@ class LlamaHIP:
         P["qkv_key"] = qkv_key
         self._packed = P
 
-    def _decode_weight_stats(self, rows: int) -> dict:
-        """last_generate_stats' decode_weights ("fp8" / "bf16": what the token step streams) and decode_weight_bytes (the weight
-        bytes of one token step: the packed copies, fp8 scales included, up to 16 rows; the row-major bf16 matrices above),
-        lora_merged (the step streams the LoRA-merged qkv copy) and lora_merges (whole-model merges this model has made so far)."""
-        if self._packed is not None and rows <= 16:
+    def _prepare_decode_weights(self, rows: int) -> dict:
+        """Before a decode call at `rows` rows: the LoRA's bordered weights refreshed, the packed copies (re)built when the step
+        can stream them (MYRIAD_PACK_DECODE=0 drops them: the step streams the row-major matrices).  Returns last_generate_stats'
+        decode_weights ("fp8" / "bf16": what the token step streams) and decode_weight_bytes (the weight bytes of one token step:
+        the packed copies, fp8 scales included, up to GEMV_MAX_ROWS rows; the row-major bf16 matrices above), lora_merged (the
+        step streams the LoRA-merged qkv copy) and lora_merges (whole-model merges this model has made so far)."""
+        if self.lora is not None:
+            self.lora.refresh(self.layers)
+        if self.pack_decode and rows <= ops.GEMV_MAX_ROWS:
+            self._pack_for_decode()
+        elif not self.pack_decode:
+            self._packed, self._packs = None, {}
+        if _packed_step(self, rows):
             mats = [P[k] for P in self._packed["layers"] for k in ("wqkv", "wo", "wgu", "wd")] + [self._packed["lm_head"]]
             nbytes = sum(m.data.numel() * m.data.element_size() + (m.scales.numel() * 4 if isinstance(m, ops.PackedFp8Weight) else 0)
                          for m in mats)
@@ -367,7 +375,7 @@ class LlamaHIP:
         partials buffer of ops.attn_decode_split_ws) makes the fused token step use the split-KV attention kernel."""
         H, hd, W, D = self.H, self.hd, self.D, self.D
         M = B * S
-        packed = self._packed["layers"] if (pos_dev is not None and M <= 16 and self._packed is not None) else None
+        packed = self._packed["layers"] if pos_dev is not None and _packed_step(self, M) else None
         # the bordered LoRA product unless the packed qkv copy has the LoRA merged in (decode_merge_lora)
         lora = None if packed is not None and self._packed["qkv_key"] == "merged" else self.lora
 
@@ -434,45 +442,65 @@ class LlamaHIP:
 
     def _decode_workspace(self, B: int, T_need: int, inv_temp: float, dev_sample: bool = False, penalty: bool = False,
                           num_beams: int = 1):
-        """Buffers (and, once captured, the hipGraph) of the single-token step for a batch size: KV caches, device-resident
-        counters, id / logit / result buffers and per-step histories.  Kept across generate() calls -- an evaluation run
-        calls generate() once per batch, and re-capturing ~290 launches each time cost ~9 ms per call.  The device sampler and
-        the repetition penalty read their knobs (`prm` = inv_temp, top_p, top_k, penalty) and the seed from device memory, so
-        the key holds only whether each is on; the arg-max kernel takes inv_temp as an argument, so it stays in the key there.
-        With num_beams > 1, B counts rows (items x beams) and the beam step's buffers join: `bupd` = the per-step upload
-        (ids int64 | parent rows int32 | running scores f32) and its pinned host twin, the top-K scratch and record, and the
-        device table of the per-layer cache pointers that mh_beam_reorder_kv walks."""
+        """_decode_buffers (and, once captured, the hipGraph) of the single-token step for a batch size, kept across generate()
+        calls -- an evaluation run calls generate() once per batch, and re-capturing ~290 launches each time cost ~9 ms per
+        call.  The device sampler and the repetition penalty read their knobs and the seed from device memory, so the key holds
+        only whether each is on; the arg-max kernel takes inv_temp as an argument, so it stays in the key there."""
         T_cap = ops.round_up(T_need + 2, 64)
-        key = (B, T_cap, None if dev_sample else float(inv_temp), id(self._packed),
-               None if self._packed is None else (self._packed["kind"], self._packed["qkv_key"]), self.decode_fused, self.lora is not None,
-               bool(dev_sample), bool(penalty), int(num_beams))
+        key = (B, T_cap, None if dev_sample else float(inv_temp), _decode_weights_id(self), bool(dev_sample), bool(penalty),
+               int(num_beams))
         ws = self._decode_ws.get(key)
         if ws is None:
             if len(self._decode_ws) >= 3:                               # a few shapes at most: evict the oldest
                 self._decode_ws.pop(next(iter(self._decode_ws)))
-            dev, i32 = self.dev, torch.int32
-            ws = dict(T=T_cap, graph=None, warm=False,
-                      caches=[torch.zeros((B, T_cap, 2 * self.D), dtype=BF16, device=dev) for _ in self.layers],
-                      pos=torch.zeros((B,), dtype=i32, device=dev), kvlen=torch.zeros((B,), dtype=i32, device=dev),
-                      ids=torch.zeros((B,), dtype=torch.long, device=dev), x_in=torch.empty((B, self.D), dtype=F32, device=dev),
-                      logits=torch.empty((B, self.V), dtype=F32, device=dev),
-                      nxt=torch.empty((B,), dtype=torch.long, device=dev), mar=torch.empty((B,), dtype=F32, device=dev),
-                      pmx=torch.empty((B,), dtype=F32, device=dev), step=torch.zeros((1,), dtype=i32, device=dev),
-                      rec=torch.zeros((4 if dev_sample else 3, B), dtype=F32, device=dev))
-            if dev_sample or penalty:
-                ws.update(prm=torch.zeros((4,), dtype=F32, device=dev), seed=torch.zeros((1,), dtype=torch.long, device=dev),
-                          kept=torch.zeros((B,), dtype=i32, device=dev),
-                          seen=torch.zeros((B, (self.V + 31) // 32), dtype=i32, device=dev))
-            if num_beams > 1:
-                nb, K = int(num_beams), 2 * int(num_beams)
-                bupd = torch.zeros((4 * B,), dtype=i32, device=dev)
-                ws.update(bupd=bupd, bupd_host=torch.zeros((4 * B,), dtype=i32).pin_memory(),
-                          ids=bupd[:2 * B].view(torch.long), src=bupd[2 * B:3 * B], bscore=bupd[3 * B:].view(F32),
-                          part_s=torch.empty((B * K,), dtype=F32, device=dev), part_i=torch.empty((B * K,), dtype=i32, device=dev),
-                          brec=torch.zeros((2, B // nb * K), dtype=i32, device=dev), lo=torch.zeros((1,), dtype=i32, device=dev),
-                          table=torch.tensor([c.data_ptr() for c in ws["caches"]], dtype=torch.long).to(dev))
-            self._decode_ws[key] = ws
+            ws = self._decode_ws[key] = _decode_buffers(self, B, T_cap, dev_sample or penalty, num_beams)
         return ws
+
+    def _prefill(self, inputs_embeds: torch.Tensor, caches, past: int = 0) -> torch.Tensor:
+        """The prefill (eager, host-known lengths) of positions past.. of [B, S0, D] f32 embeddings into `caches`, on top of the
+        `past` rows cached already; returns the last position's f32 logits [B, V]."""
+        B, S0, D = inputs_embeds.shape
+        S = S0 - past
+        pos = torch.arange(past, S0, dtype=torch.int32).repeat(B).to(self.dev)
+        h = self._decode_block(inputs_embeds[:, past:].reshape(B * S, D).contiguous(), B, S, caches, 1.0 / math.sqrt(self.hd), pos,
+                               past=past)
+        last = h.view(B, S, D)[:, -1].contiguous()
+        return ops.gemm(ops.rmsnorm_fwd(last, self.norm, self.eps), self.lm_head, out_dtype=F32)
+
+    def _step_logits(self, ws: dict) -> None:
+        """The token step up to its logits: embed the fed ids ws["ids"], every decoder layer at the device-resident position,
+        the final norm + lm-head into ws["logits"] -- one launch on the packed copy when the fused form fits, else the norm and
+        the packed GEMV, or the GEMM above GEMV_MAX_ROWS rows."""
+        ops.embed_gather(self.embed, ws["ids"], ws["x_in"])
+        rows = ws["x_in"].shape[0]
+        h = self._decode_block(ws["x_in"], rows, 1, ws["caches"], 1.0 / math.sqrt(self.hd), ws["pos"], pos_dev=ws["pos"],
+                               kvlen_dev=ws["kvlen"], split_ws=ws["split"])
+        if _packed_step(self, rows) and self.decode_fused:
+            if ops.gemv_packed_rmsnorm(h, self.norm, self.eps, self._packed["lm_head"], out=ws["logits"], out_dtype=F32) is not None:
+                return
+        hn = ops.rmsnorm_fwd(h, self.norm, self.eps)
+        if _packed_step(self, rows):
+            ops.gemv_packed(hn, self._packed["lm_head"], out=ws["logits"], out_dtype=F32)
+        else:
+            ops.gemm(hn, self.lm_head, out=ws["logits"])
+
+    @staticmethod
+    def _launch_step(ws: dict, token_step, ban: int, use_graph: bool, stats: dict) -> None:
+        """Enqueue one token step: a replay of ws's captured graph when there is one (counted in stats["graph_replays"]).  A step
+        with a ban runs eagerly; an eager ban-free step after an earlier eager one captures the next (kernels are warm, buffers
+        fixed)."""
+        if ban == -1 and use_graph and ws["graph"] is not None:
+            ws["graph"].replay()
+            stats["graph_replays"] += 1
+            return
+        token_step(ban)
+        if ban == -1 and use_graph and ws["warm"]:
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                token_step(-1)
+            ws["graph"] = g
+        ws["warm"] = True
 
     @torch.no_grad()
     def greedy_generate(self, inputs_embeds: torch.Tensor, max_new_tokens: int = 90,
@@ -518,12 +546,11 @@ class LlamaHIP:
                      generator: Optional[torch.Generator] = None, top_k: int = 50, repetition_penalty: float = 1.0):
         """greedy_generate's body.  session=None: its workspace from the _decode_ws cache and a prefill from position 0; a
         DecodeSession instead lends its own buffers and graphs and names the cached prefix `past` that is not prefilled again."""
-        B, S0, D = inputs_embeds.shape
+        B, S0, _ = inputs_embeds.shape
         if do_sample and not float(temperature) > 0:
             raise ValueError(f"temperature must be > 0 when sampling, got {temperature}")
         if not float(repetition_penalty) > 0:
             raise ValueError(f"repetition_penalty must be > 0, got {repetition_penalty}")
-        scale = 1.0 / math.sqrt(self.hd)
         out_ids, margins = [], []
         unfinished = torch.ones(B, dtype=torch.long)
         inv_temp = 1.0 / float(temperature) if do_sample else 1.0
@@ -533,18 +560,12 @@ class LlamaHIP:
         penalty = float(repetition_penalty) != 1.0
         stats = dict(steps=0, sampled_rows=0, min_pmax=1.0, device_sampled_rows=0, host_sampled_rows=0, graph_replays=0)
         self.last_generate_stats = stats
-        if self.lora is not None:
-            self.lora.refresh(self.layers)
-        if self.pack_decode and B <= 16:
-            self._pack_for_decode()
-        elif not self.pack_decode:
-            self._packed, self._packs = None, {}                     # MYRIAD_PACK_DECODE=0: stream the row-major matrices
-        stats.update(self._decode_weight_stats(B))
+        stats.update(self._prepare_decode_weights(B))
         if session is None:
             ws, past = self._decode_workspace(B, S0 + max_new_tokens, inv_temp, dev_sample, penalty), 0
         else:
             ws, past = session._begin_turn(B, S0, max_new_tokens, inv_temp, dev_sample, penalty)
-        caches = ws["caches"]
+        rec = ws["rec"][:4 if dev_sample else 3]                     # the sampler's kept counts are the fourth row
         if dev_sample or penalty:
             ws["prm"].copy_(torch.tensor([inv_temp, top_p, float(top_k), float(repetition_penalty)], dtype=F32))
             ws["seen"].zero_()                                       # generated ids only: the prompt is embeddings
@@ -595,12 +616,7 @@ class LlamaHIP:
                 return True, redrawn
             return int(unfinished.max()) == 0, redrawn
 
-        # ---- prefill (eager, host-known lengths)
-        pos = torch.arange(past, S0, dtype=torch.int32).repeat(B).to(self.dev)
-        h = self._decode_block(inputs_embeds[:, past:].reshape(B * (S0 - past), D).contiguous(), B, S0 - past, caches, scale, pos,
-                               past=past)
-        last = h.view(B, S0 - past, D)[:, -1].contiguous()
-        logits0 = ops.gemm(ops.rmsnorm_fwd(last, self.norm, self.eps), self.lm_head, out_dtype=F32)
+        logits0 = self._prefill(inputs_embeds, ws["caches"], past)
         ban0 = eos_id if 0 < min_length else -1
         if dev_sample:                                               # the prefill pick is Philox step t = 0
             ops.sample_rows(logits0, ws["nxt"], ws["mar"], ws["pmx"], ws["kept"], ws["prm"], ws["seed"], ban_id=ban0, t_add=0)
@@ -615,54 +631,27 @@ class LlamaHIP:
         ws["step"].zero_()
 
         def token_step(ban):
-            ops.embed_gather(self.embed, ws["ids"], ws["x_in"])
-            done_lm = None
-            hh = self._decode_block(ws["x_in"], B, 1, caches, scale, ws["pos"], pos_dev=ws["pos"], kvlen_dev=ws["kvlen"],
-                                    split_ws=ws.get("split"))
-            if done_lm is None and self._packed is not None and B <= 16 and self.decode_fused:
-                done_lm = ops.gemv_packed_rmsnorm(hh, self.norm, self.eps, self._packed["lm_head"], out=ws["logits"], out_dtype=F32)
-            if done_lm is None:
-                hn = ops.rmsnorm_fwd(hh, self.norm, self.eps)
-                if self._packed is not None and B <= 16:
-                    ops.gemv_packed(hn, self._packed["lm_head"], out=ws["logits"], out_dtype=F32)
-                else:
-                    ops.gemm(hn, self.lm_head, out=ws["logits"])
+            self._step_logits(ws)
             if penalty:                                              # ws["ids"] = the token fed in: it joins the seen set first
                 ops.repetition_penalty_rows(ws["logits"], ws["seen"], ws["ids"], ws["prm"][3:])
             if dev_sample:                                           # token s (= step + 1) draws Philox step t = s
                 ops.sample_rows(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ws["kept"], ws["prm"], ws["seed"], ban_id=ban,
                                 step=ws["step"], t_add=1)
-                ops.decode_advance_kept(ws["nxt"], ws["mar"], ws["pmx"], ws["kept"], ws["rec"], ws["ids"], ws["step"], ws["pos"],
+                ops.decode_advance_kept(ws["nxt"], ws["mar"], ws["pmx"], ws["kept"], rec, ws["ids"], ws["step"], ws["pos"],
                                         ws["kvlen"])
                 return
             ops.argmax_pmax_rows(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ban_id=ban, inv_temp=inv_temp)
-            ops.decode_advance(ws["nxt"], ws["mar"], ws["pmx"], ws["rec"], ws["ids"], ws["step"], ws["pos"], ws["kvlen"])
-
-        def launch(ban):
-            """Enqueue one token step: a replay of the captured graph when there is one."""
-            if ban == -1 and use_graph and ws["graph"] is not None:
-                ws["graph"].replay()
-                stats["graph_replays"] += 1
-                return
-            token_step(ban)
-            if ban == -1 and use_graph and ws["warm"]:
-                # the eager step above was this batch size's second: capture the next one (kernels are warm, buffers fixed)
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    token_step(-1)
-                ws["graph"] = g
-            ws["warm"] = True
+            ops.decode_advance(ws["nxt"], ws["mar"], ws["pmx"], rec, ws["ids"], ws["step"], ws["pos"], ws["kvlen"])
 
         step = 1                                                     # tokens generated so far (= index of the next one)
         if not done and step < max_new_tokens:
             ws["ids"].copy_(out_ids[-1].to(self.dev))
         while not done and step < max_new_tokens:
             ban = eos_id if step < min_length else -1
-            launch(ban)
-            rec = ws["rec"].cpu()                                    # the one device->host copy of the step (it also waits for it)
-            done, redrawn = record(rec[0].long(), rec[1].clone(), rec[2].clone(), ban, logits_of=lambda: ws["logits"],
-                                   kept=rec[3] if dev_sample else None)
+            self._launch_step(ws, token_step, ban, use_graph, stats)
+            r = rec.cpu()                                            # the one device->host copy of the step (it also waits for it)
+            done, redrawn = record(r[0].long(), r[1].clone(), r[2].clone(), ban, logits_of=lambda: ws["logits"],
+                                   kept=r[3] if dev_sample else None)
             if redrawn and not done:
                 ws["ids"].copy_(out_ids[-1].to(self.dev))            # a host draw replaces the arg-max the step fed back to itself
             step += 1
@@ -687,11 +676,11 @@ class LlamaHIP:
         Device / host split.  The prefill runs at B rows, writing its keys / values into row b * nb of the B * nb row caches,
         and one mh_beam_reorder_kv broadcasts them over [0, S0) to the item's other beams.  The token step (captured into a
         hipGraph, like greedy's) is: reorder the generated positions [S0, pos) of every cache by the parent rows `src`, embed
-        the fed tokens, the decoder layers at B * nb rows (packed GEMV up to 16 rows), lm-head, mh_beam_topk (log-softmax +
+        the fed tokens, the decoder layers at B * nb rows (packed GEMV up to GEMV_MAX_ROWS), lm-head, mh_beam_topk (log-softmax +
         running score + EOS ban, per item the top 2 * nb candidates), pos / kvlen += 1.  The host reads the [2, B, 2*nb]
         record (one device->host copy), keeps the hypotheses, and writes the next step's (ids, src, running scores) with one
         host->device copy."""
-        B, S0, D = inputs_embeds.shape
+        B, S0, _ = inputs_embeds.shape
         nb, nrs = int(num_beams), int(num_return_sequences)
         if nb > ops.BEAM_MAX:
             raise NotImplementedError(f"num_beams={nb}: at most {ops.BEAM_MAX} beams on the HIP decode path")
@@ -707,16 +696,9 @@ class LlamaHIP:
         pad = eos_id if pad_id is None else int(pad_id)
         stops = [tuple(int(t) for t in st) for st in stop_ids]
         R, K, V, NEG = B * nb, 2 * nb, self.V, np.float32(-1.0e9)
-        scale = 1.0 / math.sqrt(self.hd)
         stats = dict(steps=0, num_beams=nb, graph_replays=0, finished_hypotheses=0, sequences_scores=None, lengths=None)
         self.last_generate_stats = stats
-        if self.lora is not None:
-            self.lora.refresh(self.layers)
-        if self.pack_decode and R <= 16:
-            self._pack_for_decode()
-        elif not self.pack_decode:
-            self._packed, self._packs = None, {}
-        stats.update(self._decode_weight_stats(R))
+        stats.update(self._prepare_decode_weights(R))
         ws = self._decode_workspace(R, S0 + max_new_tokens, 1.0, num_beams=nb)
         caches, T_cap, C = ws["caches"], ws["T"], 2 * self.D
         dev = self.dev
@@ -770,10 +752,7 @@ class LlamaHIP:
             return rec[0].view(F32).numpy().reshape(B, K), rec[1].numpy().reshape(B, K).astype(np.int64)
 
         # ---- prefill at B rows into rows b * nb, then broadcast the prompt's keys / values to the other beams
-        pos = torch.arange(S0, dtype=torch.int32).repeat(B).to(dev)
-        h = self._decode_block(inputs_embeds.reshape(B * S0, D).contiguous(), B, S0, [c[::nb] for c in caches], scale, pos, past=0)
-        last = h.view(B, S0, D)[:, -1].contiguous()
-        logits0 = ops.gemm(ops.rmsnorm_fwd(last, self.norm, self.eps), self.lm_head, out_dtype=F32)
+        logits0 = self._prefill(inputs_embeds, [c[::nb] for c in caches])
         ws["bscore"].zero_()                                         # beam 0's running score; one row per item here
         ops.beam_topk(logits0, ws["bscore"], ws["part_s"], ws["part_i"], ws["brec"][0].view(F32), ws["brec"][1], B, nb,
                       ban_id=eos_id if 0 < min_length else -1)
@@ -791,38 +770,14 @@ class LlamaHIP:
 
         def token_step(ban):
             ops.beam_reorder_kv(ws["table"], len(caches), B, nb, T_cap, C, ws["src"], ws["lo"], ws["pos"])
-            ops.embed_gather(self.embed, ws["ids"], ws["x_in"])
-            hh = self._decode_block(ws["x_in"], R, 1, caches, scale, ws["pos"], pos_dev=ws["pos"], kvlen_dev=ws["kvlen"])
-            done_lm = None
-            if self._packed is not None and R <= 16 and self.decode_fused:
-                done_lm = ops.gemv_packed_rmsnorm(hh, self.norm, self.eps, self._packed["lm_head"], out=ws["logits"], out_dtype=F32)
-            if done_lm is None:
-                hn = ops.rmsnorm_fwd(hh, self.norm, self.eps)
-                if self._packed is not None and R <= 16:
-                    ops.gemv_packed(hn, self._packed["lm_head"], out=ws["logits"], out_dtype=F32)
-                else:
-                    ops.gemm(hn, self.lm_head, out=ws["logits"])
+            self._step_logits(ws)
             ops.beam_topk(ws["logits"], ws["bscore"], ws["part_s"], ws["part_i"], ws["brec"][0].view(F32), ws["brec"][1], B, nb,
                           ban_id=ban, pos=ws["pos"], kvlen=ws["kvlen"])
-
-        def launch(ban):
-            if ban == -1 and use_graph and ws["graph"] is not None:
-                ws["graph"].replay()
-                stats["graph_replays"] += 1
-                return
-            token_step(ban)
-            if ban == -1 and use_graph and ws["warm"]:
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    token_step(-1)
-                ws["graph"] = g
-            ws["warm"] = True
 
         gen = 1                                                      # tokens generated so far
         while going and gen < max_new_tokens:
             ws["bupd"].copy_(ws["bupd_host"], non_blocking=True)    # ids | src | running scores: one host->device copy
-            launch(eos_id if gen < min_length else -1)
+            self._launch_step(ws, token_step, eos_id if gen < min_length else -1, use_graph, stats)
             gen += 1
             going = select(*read_record(), gen)
 
@@ -836,6 +791,52 @@ class LlamaHIP:
 
     def embed_tokens_into(self, ids: torch.Tensor, out2d: torch.Tensor, dst_rows: Optional[torch.Tensor] = None):
         ops.embed_gather(self.embed, ids, out2d, dst_rows)
+
+
+# Decode helpers shared by LlamaHIP and DecodeSession.  They read only the model's fields, so the session needs no more of the
+# model than those.
+def _packed_step(lm: "LlamaHIP", rows: int) -> bool:
+    """The token step at `rows` rows streams the packed copies (ops.gemv_packed takes at most GEMV_MAX_ROWS rows)."""
+    return lm._packed is not None and rows <= ops.GEMV_MAX_ROWS
+
+
+def _decode_weights_id(lm: "LlamaHIP") -> tuple:
+    """What the token step multiplies by: the packed copies (which object, its kind, which qkv copy is live), the fused
+    launches and the LoRA.  The workspace key holds it, so no graph captured on one set of weights is replayed on another."""
+    P = lm._packed
+    return id(P), None if P is None else (P["kind"], P["qkv_key"]), lm.decode_fused, lm.lora is not None
+
+
+def _decode_buffers(lm: "LlamaHIP", B: int, T_cap: int, sampler: bool = False, num_beams: int = 1) -> dict:
+    """Buffers of the single-token step at B rows: KV caches of T_cap positions, device-resident counters, id / logit /
+    result buffers and the [4, B] per-step record (the arg-max step writes its first three rows); `graph` / `warm` hold the
+    captured step once there is one (_launch_step), `split` the split-KV partials when the step uses them.  With `sampler`
+    the device sampler's and the repetition penalty's buffers join: their knobs (`prm` = inv_temp, top_p, top_k, penalty),
+    the seed, the kept counts and the seen-id bitmaps.  With num_beams > 1, B counts rows (items x beams) and the beam step's
+    buffers join: `bupd` = the per-step upload (ids int64 | parent rows int32 | running scores f32) and its pinned host twin,
+    the top-K scratch and record, and the device table of the per-layer cache pointers that mh_beam_reorder_kv walks."""
+    dev, i32 = lm.dev, torch.int32
+    ws = dict(T=T_cap, graph=None, warm=False, split=None,
+              caches=[torch.zeros((B, T_cap, 2 * lm.D), dtype=BF16, device=dev) for _ in lm.layers],
+              pos=torch.zeros((B,), dtype=i32, device=dev), kvlen=torch.zeros((B,), dtype=i32, device=dev),
+              ids=torch.zeros((B,), dtype=torch.long, device=dev), x_in=torch.empty((B, lm.D), dtype=F32, device=dev),
+              logits=torch.empty((B, lm.V), dtype=F32, device=dev),
+              nxt=torch.empty((B,), dtype=torch.long, device=dev), mar=torch.empty((B,), dtype=F32, device=dev),
+              pmx=torch.empty((B,), dtype=F32, device=dev), step=torch.zeros((1,), dtype=i32, device=dev),
+              rec=torch.zeros((4, B), dtype=F32, device=dev))
+    if sampler:
+        ws.update(prm=torch.zeros((4,), dtype=F32, device=dev), seed=torch.zeros((1,), dtype=torch.long, device=dev),
+                  kept=torch.zeros((B,), dtype=i32, device=dev),
+                  seen=torch.zeros((B, (lm.V + 31) // 32), dtype=i32, device=dev))
+    if num_beams > 1:
+        nb, K = int(num_beams), 2 * int(num_beams)
+        bupd = torch.zeros((4 * B,), dtype=i32, device=dev)
+        ws.update(bupd=bupd, bupd_host=torch.zeros((4 * B,), dtype=i32).pin_memory(),
+                  ids=bupd[:2 * B].view(torch.long), src=bupd[2 * B:3 * B], bscore=bupd[3 * B:].view(F32),
+                  part_s=torch.empty((B * K,), dtype=F32, device=dev), part_i=torch.empty((B * K,), dtype=i32, device=dev),
+                  brec=torch.zeros((2, B // nb * K), dtype=i32, device=dev), lo=torch.zeros((1,), dtype=i32, device=dev),
+                  table=torch.tensor([c.data_ptr() for c in ws["caches"]], dtype=torch.long).to(dev))
+    return ws
 
 
 # The chat session's token step uses the split-KV attention kernel (mh_attn_decode_rope_split) when the single-workgroup kernel
@@ -885,26 +886,11 @@ class DecodeSession:
         self.B = None
         self.keys: List[list] = []
         self.stamp = None
-        self.graphs, self.warm = {}, set()
+        self.views = {}                                              # cfg -> workspace view of bufs, with its graph / warm flag
         self.graph_captures = 0
         self.split = False
         self.last_stats = {}
         self._turn = None
-
-    def _alloc(self, B: int, T_cap: int) -> None:
-        L, dev, i32 = self.llama, self.llama.dev, torch.int32
-        self.bufs = dict(T=T_cap, caches=[torch.zeros((B, T_cap, 2 * L.D), dtype=BF16, device=dev) for _ in L.layers],
-                         pos=torch.zeros((B,), dtype=i32, device=dev), kvlen=torch.zeros((B,), dtype=i32, device=dev),
-                         ids=torch.zeros((B,), dtype=torch.long, device=dev), x_in=torch.empty((B, L.D), dtype=F32, device=dev),
-                         logits=torch.empty((B, L.V), dtype=F32, device=dev),
-                         nxt=torch.empty((B,), dtype=torch.long, device=dev), mar=torch.empty((B,), dtype=F32, device=dev),
-                         pmx=torch.empty((B,), dtype=F32, device=dev), step=torch.zeros((1,), dtype=i32, device=dev),
-                         rec3=torch.zeros((3, B), dtype=F32, device=dev), rec4=torch.zeros((4, B), dtype=F32, device=dev),
-                         prm=torch.zeros((4,), dtype=F32, device=dev), seed=torch.zeros((1,), dtype=torch.long, device=dev),
-                         kept=torch.zeros((B,), dtype=i32, device=dev),
-                         seen=torch.zeros((B, (L.V + 31) // 32), dtype=i32, device=dev), part=None)
-        self.B = B
-        self.graphs, self.warm = {}, set()
 
     def _begin_turn(self, B: int, S0: int, max_new_tokens: int, inv_temp: float, dev_sample: bool, penalty: bool):
         """Called by LlamaHIP._greedy_core once the decode weights are packed: invalidation, (re)allocation, the reused prefix.
@@ -917,9 +903,8 @@ class DecodeSession:
             raise ValueError("one key per context position and batch row is required")
         # the merged qkv copy is rewritten in place by a re-merge: its merge id joins the stamp, so no KV row survives a change of
         # the weights the step multiplies by, whether or not the caller's weights_version saw it
-        kind = None if L._packed is None else (L._packed["kind"], L._packed["qkv_key"], id(L._packed),
-                                                L._packed["merge_id"] if L._packed["qkv_key"] == "merged" else None)
-        stamp = (version, kind, L.decode_fused, L.lora is not None)
+        P = L._packed
+        stamp = (version, _decode_weights_id(L), P["merge_id"] if P is not None and P["qkv_key"] == "merged" else None)
         need = S0 + max_new_tokens + 2
         if self.bufs is None:
             reason = reason or "empty cache"
@@ -935,21 +920,22 @@ class DecodeSession:
             T_cap = max(self.capacity, ops.round_up(need, 64))
             if T_cap > 8192:
                 raise ValueError(f"a chat session holds at most 8192 positions; this turn needs {need}")
-            self.bufs = None
-            self._alloc(B, T_cap)
+            self.bufs, self.views = None, {}
+            self.bufs, self.B = _decode_buffers(L, B, T_cap, sampler=True), B
         self.stamp = stamp
         if reason is not None:
             self.keys = [[] for _ in range(B)]
         past = min(common_prefix(keys[r], self.keys[r]) for r in range(B))
         past = min(past, S0 - 1)                                     # at least one row is prefilled: it gives the first logits
-        fused = L._packed is not None and B <= 16 and L.decode_fused
+        fused = _packed_step(L, B) and L.decode_fused
         self.split = fused and (split_kv_rule(B, L.H, S0) if self.split_choice is None else bool(self.split_choice))
-        if self.split and self.bufs["part"] is None:
-            self.bufs["part"] = ops.attn_decode_split_ws(B, L.H, self.bufs["T"], L.dev)
+        if self.split and self.bufs["split"] is None:
+            self.bufs["split"] = ops.attn_decode_split_ws(B, L.H, self.bufs["T"], L.dev)
         cfg = (None if dev_sample else float(inv_temp), bool(dev_sample), bool(penalty), self.split)
-        ws = dict(self.bufs, rec=self.bufs["rec4" if dev_sample else "rec3"], graph=self.graphs.get(cfg), warm=cfg in self.warm,
-                  split=self.bufs["part"] if self.split else None)
-        self._ws, self._cfg = ws, cfg
+        ws = self.views.get(cfg)
+        if ws is None:
+            ws = self.views[cfg] = dict(self.bufs, split=self.bufs["split"] if self.split else None)
+        self._ws, self._ws_graph = ws, ws["graph"]
         self.last_stats = dict(context_tokens=S0, reused_tokens=past, prefilled_tokens=S0 - past, split_kv=bool(self.split),
                                full_reprefill_reason=reason)
         return ws, past
@@ -960,7 +946,7 @@ class DecodeSession:
         `top_p`, `temperature`, `generator`, `top_k`, `repetition_penalty`, `return_margins`) on [B, S0, D] f32 embeddings whose
         positions are named by `keys` ([B][S0]).  `weights_version`: anything that changes when the weights do."""
         B, S0, _ = inputs_embeds.shape
-        self._turn = ([list(k) for k in keys], weights_version, reset_reason)
+        self._turn, self._ws = ([list(k) for k in keys], weights_version, reset_reason), None
         try:
             out = self.llama._greedy_core(inputs_embeds, self, use_graph=True, **kw)
         except BaseException:
@@ -968,12 +954,8 @@ class DecodeSession:
             raise
         finally:
             self._turn = None
-        ws, cfg = self._ws, self._cfg
-        if ws["graph"] is not None and cfg not in self.graphs:
-            self.graphs[cfg] = ws["graph"]
-            self.graph_captures += 1
-        if ws["warm"]:
-            self.warm.add(cfg)
+            if self._ws is not None and self._ws["graph"] is not self._ws_graph:    # this turn captured its view's step
+                self.graph_captures += 1
         ids = out[0] if isinstance(out, tuple) else out
         eos = int(kw.get("eos_id", 2))
         n = ids.shape[1]

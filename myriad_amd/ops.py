@@ -284,12 +284,13 @@ def lora_merge_pack_fp8(w: torch.Tensor, a_qv: torch.Tensor, b_q: torch.Tensor, 
 
 def gemv_packed(a: torch.Tensor, pw, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
                 residual: Optional[torch.Tensor] = None, out_dtype=BF16, alpha: float = 1.0) -> torch.Tensor:
-    """out[M<=16, N] = alpha * a @ W^T (+bias) (+residual f32) with W given as its packed copy; same bits as gemm().
+    """out[M <= GEMV_MAX_ROWS, N] = alpha * a @ W^T (+bias) (+residual f32) with W given as its packed copy; same bits as gemm().
     A PackedFp8Weight runs the fp8 kernel: alpha * s_n * a @ q^T, q widened exactly to bf16."""
     _chk2d(a, BF16, "gemv_packed.a")
     M, K = a.shape
-    if K != pw.K or M > 16:
-        raise _lib.MyriadHipError(f"gemv_packed: a is {tuple(a.shape)}, weight was packed as [{pw.N}, {pw.K}], M must be <= 16")
+    if K != pw.K or M > GEMV_MAX_ROWS:
+        raise _lib.MyriadHipError(f"gemv_packed: a is {tuple(a.shape)}, weight was packed as [{pw.N}, {pw.K}], "
+                                  f"M must be <= {GEMV_MAX_ROWS}")
     if out is None:
         out = torch.empty((M, pw.N), dtype=out_dtype, device=a.device)
     ldr = 0
@@ -325,22 +326,23 @@ def _gemv_pro(fn, name, a, lda, pw, out, residual, out_dtype, alpha, M, *pre):
 
 def gemv_packed_rmsnorm(h: torch.Tensor, norm_w: torch.Tensor, eps: float, pw, out=None, residual=None,
                         out_dtype=BF16, alpha: float = 1.0):
-    """out[M<=16, N] = alpha * rmsnorm(h; norm_w, eps) @ W^T (+residual): mh_rmsnorm_fwd + mh_gemv_packed in one launch, same bits.
+    """out[M <= GEMV_MAX_ROWS, N] = alpha * rmsnorm(h; norm_w, eps) @ W^T (+residual): mh_rmsnorm_fwd + mh_gemv_packed in one
+    launch, same bits.
     Returns None when the operand rows exceed the fused kernel's LDS budget (run the two launches instead)."""
     _chk2d(h, F32, "gemv_packed_rmsnorm.h")
     M, K = h.shape
-    if K != pw.K or M > 16:
+    if K != pw.K or M > GEMV_MAX_ROWS:
         raise _lib.MyriadHipError(f"gemv_packed_rmsnorm: h is {tuple(h.shape)}, weight was packed as [{pw.N}, {pw.K}]")
     name = "mh_gemv_packed_fp8_rmsnorm" if isinstance(pw, PackedFp8Weight) else "mh_gemv_packed_rmsnorm"
     return _gemv_pro(getattr(_L(), name), name, h, h.stride(0), pw, out, residual, out_dtype, alpha, M, _p(norm_w), float(eps))
 
 
 def gemv_packed_silu(gu: torch.Tensor, pw, out=None, residual=None, out_dtype=BF16, alpha: float = 1.0):
-    """out[M<=16, N] = alpha * (silu(g) * u) @ W^T (+residual) for gu [M, 2K] bf16 in the 128-blocked gate|up layout:
+    """out[M <= GEMV_MAX_ROWS, N] = alpha * (silu(g) * u) @ W^T (+residual) for gu [M, 2K] bf16 in the 128-blocked gate|up layout:
     mh_silu_mul_fwd_blk + mh_gemv_packed in one launch, same bits.  None when the rows exceed the LDS budget."""
     _chk2d(gu, BF16, "gemv_packed_silu.gu")
     M = gu.shape[0]
-    if gu.shape[1] != 2 * pw.K or M > 16:
+    if gu.shape[1] != 2 * pw.K or M > GEMV_MAX_ROWS:
         raise _lib.MyriadHipError(f"gemv_packed_silu: gu is {tuple(gu.shape)}, weight was packed as [{pw.N}, {pw.K}]")
     name = "mh_gemv_packed_fp8_silu" if isinstance(pw, PackedFp8Weight) else "mh_gemv_packed_silu"
     return _gemv_pro(getattr(_L(), name), name, gu, gu.stride(0), pw, out, residual, out_dtype, alpha, M)
@@ -1017,6 +1019,7 @@ def decode_advance(nxt, margin, pmax, rec, next_ids, step_dev, pos, kvlen):
                                       _s()), "mh_decode_advance")
 
 
+GEMV_MAX_ROWS = 16     # most rows mh_gemv_packed and its fused forms take (include/myriad_hip.h)
 SAMPLE_CAP = 1024      # most top-k candidates mh_sample_rows sorts on the device (include/myriad_hip.h)
 
 
