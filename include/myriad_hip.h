@@ -80,6 +80,14 @@ int mh_gemm_residual_layernorm(const void* A, int lda, const void* B, int ldb, f
  * mh_gemm_bf16_nt(..., MH_GEMM_OUT_F32) + mh_rmsnorm_bwd; one launch and one pass over dY less when K is split. */
 int mh_gemm_rmsnorm_bwd(const void* A, int lda, const void* B, int ldb, float* dy_buf, const float* x, const float* w,
                         const float* dres, float* dx, void* dx_bf16, int M, int N, int K, float eps, mh_stream_t s);
+/* The LayerNorm counterpart (the backward of mh_gemm_residual_layernorm): dY = A.B^T, dx = d layernorm(x; w)(dY) + dres as
+ * f32 (dx) and/or bf16 (dx_bf16).  dy_buf: [M, N] f32 scratch; it holds dY on return when dgamma != NULL.  dgamma / dbeta
+ * (f32 [N], both or neither, N <= 4096): the LayerNorm's parameter gradients, (+)= when accumulate, from per-block partials in
+ * ws (mh_layernorm_param_grads_ws_floats(M, N) floats) reduced in block order.  Same bits as mh_gemm_bf16_nt(...,
+ * MH_GEMM_OUT_F32) + mh_layernorm_bwd (+ mh_layernorm_param_grads); the split-K partials are summed inside the norm kernel. */
+int mh_gemm_layernorm_bwd(const void* A, int lda, const void* B, int ldb, float* dy_buf, const float* x, const float* w,
+                          const float* dres, float* dx, void* dx_bf16, float* dgamma, float* dbeta, int accumulate, float* ws,
+                          long ws_floats, int M, int N, int K, float eps, mh_stream_t s);
 
 /* Scratch for the automatic split-K path of mh_gemm_bf16_nt (used for shapes whose tile count under-fills the
  * 256 CUs).  The caller owns the buffer; pass NULL to disable.  Not needed for correctness. */

@@ -843,6 +843,54 @@ extern "C" int mh_gemm_rmsnorm_bwd(const void* A, int lda, const void* B, int ld
   return mh_launch_rmsnorm_bwd(dy_buf, 0, 1, 0, N, x, w, dres, dx, dx_bf16, M, N, eps, stream);
 }
 
+int mh_launch_layernorm_bwd(const void* dy, int slab_bf16, int nslab, long slab, long ldy, const float* x, const float* w,
+                            const float* dres, float* dx, void* dx_bf16, float* dy_out, int M, int D, float eps,
+                            hipStream_t stream);
+extern "C" int mh_layernorm_bwd(const float* dy, const float* x, const float* w, const float* dres, float* dx, void* dx_bf16,
+                                int M, int D, float eps, hipStream_t stream);
+extern "C" long mh_layernorm_param_grads_ws_floats(int M, int D);
+extern "C" int mh_layernorm_param_grads(const float* dy, const float* x, float* dgamma, float* dbeta, int M, int D, float eps,
+                                        int accumulate, float p_out, unsigned long long seed_out, float* ws, long ws_floats,
+                                        hipStream_t stream);
+
+// The LayerNorm counterpart of mh_gemm_rmsnorm_bwd and the backward of mh_gemm_residual_layernorm (eva_vit.py:173-180 under
+// autograd): dY = A.B^T, dx = d layernorm(x; w)(dY) + dres.  When the policy splits K the norm kernel sums the partial slabs
+// itself; otherwise dY goes through dy_buf [M, N] f32 and mh_layernorm_bwd reads it.  dgamma != NULL: the parameter gradients
+// too -- the norm kernel leaves the summed dY in dy_buf and mh_layernorm_param_grads reduces its per-block partials (ws) in
+// block order.  Bit-identical to mh_gemm_bf16_nt(..., MH_GEMM_OUT_F32) + mh_layernorm_bwd (+ mh_layernorm_param_grads).
+extern "C" int mh_gemm_layernorm_bwd(const void* A, int lda, const void* B, int ldb, float* dy_buf, const float* x, const float* w,
+                                     const float* dres, float* dx, void* dx_bf16, float* dgamma, float* dbeta, int accumulate,
+                                     float* ws, long ws_floats, int M, int N, int K, float eps, hipStream_t stream) {
+  if (M <= 0 || N <= 0) return MH_OK;
+  if (!dy_buf || !x || !w || (N % 4) != 0 || N > 8192) return MH_ERR_ARG;
+  const bool params = dgamma != nullptr;
+  if (params && (!dbeta || N > 4096 || !ws || ws_floats < mh_layernorm_param_grads_ws_floats(M, N))) return MH_ERR_ARG;
+  int kernel = 1, splits = 1;
+  if (K > 0) gemm_plan(M, N, K, MH_GEMM_OUT_F32, &kernel, &splits);
+  int rc;
+  if (splits > 1 && kernel != 0 && (K % 64) == 0 && (lda % 8) == 0 && (ldb % 8) == 0 &&
+      !(((uintptr_t)A | (uintptr_t)B) & 15)) {
+    GemmArgs g = {A, lda, B, ldb, (void*)dy_buf, N, M, N, K, nullptr, nullptr, 0, MH_GEMM_OUT_F32, 1.0f, 1, K / 64, 0L};
+    g.flags |= plan_variant(kernel) << MH_GEMM_VARIANT_SHIFT;
+    const int nt = K / 64;                          // the split count run_splitk will settle on
+    int sp = splits > nt ? nt : splits;
+    const int tps = (nt + sp - 1) / sp;
+    sp = (nt + tps - 1) / tps;
+    float* wsp = ws_for(stream);
+    int sbf = 0;
+    rc = run_splitk(g, splits, wsp, stream, /*reduce=*/false, &sbf);
+    if (rc) return rc;
+    rc = mh_launch_layernorm_bwd(wsp, sbf, sp, (long)M * N, N, x, w, dres, dx, dx_bf16, params ? dy_buf : nullptr, M, N, eps,
+                                 stream);
+  } else {
+    rc = mh_gemm_bf16_nt(A, lda, B, ldb, dy_buf, N, M, N, K, nullptr, nullptr, 0, MH_GEMM_OUT_F32, 1.0f, stream);
+    if (rc) return rc;
+    rc = mh_layernorm_bwd(dy_buf, x, w, dres, dx, dx_bf16, M, N, eps, stream);
+  }
+  if (rc || !params) return rc;
+  return mh_layernorm_param_grads(dy_buf, x, dgamma, dbeta, M, N, eps, accumulate, 0.f, 0ULL, ws, ws_floats, stream);
+}
+
 int mh_launch_lora_dx(const void* dx_ext, int slab_bf16, long ld, int nslab, long slab, const float* A, float* out, float* border_out,
                       int M, int D, int R2_, float s, float p, unsigned long long seed, hipStream_t stream);
 

@@ -224,6 +224,94 @@ __global__ __launch_bounds__(NT) void layernorm_bwd_kernel(const float* __restri
   }
 }
 
+// layernorm_bwd_kernel for a dY given as `nslab` split-K partial slabs [nslab][M][ldy] of the dgrad GEMM that produced it
+// (mh_gemm_layernorm_bwd), summed in slab order exactly as splitk_reduce_kernel sums them.  The row's x and summed dY stay in
+// registers (NIT float4 chunks a thread), so each operand is read once; the row sums, the per-element expressions and their
+// order are layernorm_bwd_kernel's, which makes the pair bit-identical to GEMM -> reduce -> layernorm_bwd.  dy_out != NULL
+// also receives the summed dY (the input of the LayerNorm parameter gradients).
+template <int NIT>
+__global__ __launch_bounds__(NT) void layernorm_bwd_slab_kernel(const void* __restrict__ dy, int nslab, long slab, long ldy,
+                                                                const float* __restrict__ x, const float* __restrict__ w,
+                                                                const float* dres, float* dx, bf16_t* dx_bf, float* dy_out,
+                                                                int D, float eps, int sbf) {
+  __shared__ float red[NW];
+  const size_t row = blockIdx.x;
+  const float* xr = x + row * D;
+  const long g0 = (long)row * ldy;
+  float4_t xv[NIT], gv[NIT];
+  float s = 0.f;
+#pragma unroll
+  for (int c = 0; c < NIT; ++c) {
+    const int i = threadIdx.x * 4 + c * NT * 4;
+    if (i < D) {
+      xv[c] = *reinterpret_cast<const float4_t*>(xr + i);
+      float4_t g = slab_load4(dy, g0 + i, sbf);
+      for (int k = 1; k < nslab; ++k) {
+        const float4_t p = slab_load4(dy, g0 + (long)k * slab + i, sbf);
+        g[0] += p[0]; g[1] += p[1]; g[2] += p[2]; g[3] += p[3];
+      }
+      gv[c] = g;                                       // (splitk_reduce_kernel's alpha is 1 here: exact)
+      if (dy_out) *reinterpret_cast<float4_t*>(dy_out + row * D + i) = g;
+      const float4_t v = xv[c];
+      s += v[0] + v[1] + v[2] + v[3];
+    }
+  }
+  const float mean = block_sum<NW>(s, red) / D;
+  float ss = 0.f;
+#pragma unroll
+  for (int c = 0; c < NIT; ++c) {
+    const int i = threadIdx.x * 4 + c * NT * 4;
+    if (i < D) {
+      const float4_t v = xv[c];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ss += (v[e] - mean) * (v[e] - mean);
+    }
+  }
+  const float r = rsqrtf(block_sum<NW>(ss, red) / D + eps);
+  float sg = 0.f, sgx = 0.f;
+#pragma unroll
+  for (int c = 0; c < NIT; ++c) {
+    const int i = threadIdx.x * 4 + c * NT * 4;
+    if (i < D) {
+      const float4_t v = xv[c];
+      const float4_t g = gv[c];
+      const float4_t ww = *reinterpret_cast<const float4_t*>(w + i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float gg = g[e] * ww[e];
+        sg += gg;
+        sgx += gg * (v[e] - mean) * r;
+      }
+    }
+  }
+  sg = block_sum<NW>(sg, red) / D;
+  sgx = block_sum<NW>(sgx, red) / D;
+#pragma unroll
+  for (int c = 0; c < NIT; ++c) {
+    const int i = threadIdx.x * 4 + c * NT * 4;
+    if (i < D) {
+      const float4_t v = xv[c];
+      const float4_t g = gv[c];
+      const float4_t ww = *reinterpret_cast<const float4_t*>(w + i);
+      float4_t o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = r * (g[e] * ww[e] - sg - (v[e] - mean) * r * sgx);
+      if (dres) {
+        const float4_t d = *reinterpret_cast<const float4_t*>(dres + row * D + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] += d[e];
+      }
+      if (dx) *reinterpret_cast<float4_t*>(dx + row * D + i) = o;
+      if (dx_bf) {
+        uint2 pk;
+        pk.x = pack_bf2(o[0], o[1]);
+        pk.y = pack_bf2(o[2], o[3]);
+        *reinterpret_cast<uint2*>(dx_bf + row * D + i) = pk;
+      }
+    }
+  }
+}
+
 extern "C" int mh_rmsnorm_fwd(const float* x, const float* w, void* y_bf16, long ldy, int M, int D, float eps,
                               hipStream_t stream) {
   if (M <= 0) return MH_OK;
@@ -270,6 +358,23 @@ extern "C" int mh_layernorm_bwd(const float* dy, const float* x, const float* w,
   if (D % 4) return MH_ERR_ARG;
   hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(M), dim3(NT), 0, stream, dy, x, w, dres, dx, (bf16_t*)dx_bf16, D,
                      eps);
+  MH_CHECK_LAUNCH();
+  return MH_OK;
+}
+
+// dy as nslab partial slabs [nslab][M][ldy] (mh_gemm_layernorm_bwd, gemm.hip); dy_out: optional f32 [M, D] summed dY
+int mh_launch_layernorm_bwd(const void* dy, int slab_bf16, int nslab, long slab, long ldy, const float* x, const float* w,
+                            const float* dres, float* dx, void* dx_bf16, float* dy_out, int M, int D, float eps,
+                            hipStream_t stream) {
+  if (M <= 0) return MH_OK;
+  if ((D % 4) || D > 8192 || (ldy % 4) || ldy < D || nslab < 1) return MH_ERR_ARG;
+#define LNB_LAUNCH(NIT_)                                                                                                   \
+  hipLaunchKernelGGL(layernorm_bwd_slab_kernel<NIT_>, dim3(M), dim3(NT), 0, stream, dy, nslab, slab, ldy, x, w, dres, dx,   \
+                     (bf16_t*)dx_bf16, dy_out, D, eps, slab_bf16)
+  if (D <= 2 * NT * 4) LNB_LAUNCH(2);
+  else if (D <= 4 * NT * 4) LNB_LAUNCH(4);
+  else LNB_LAUNCH(8);
+#undef LNB_LAUNCH
   MH_CHECK_LAUNCH();
   return MH_OK;
 }

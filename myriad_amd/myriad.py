@@ -287,8 +287,9 @@ class MyriadHIP(nn.Module):
                                   need_backward=need_bwd and (self.arch == "myriad" or self.train_qformer))
         self.llama = LlamaHIP(weights, cfg.get("llm_heads", 32), self._dev, eps=float(cfg.get("llm_eps", 1e-6)),
                               need_backward=need_bwd)
-        self.ln_w = weights["ln_vision.weight"].to(self._dev, F32).contiguous()
-        self.ln_b = weights["ln_vision.bias"].to(self._dev, F32).contiguous()
+        # copies: _load_vision_keys writes them in place
+        self.ln_w = weights["ln_vision.weight"].to(self._dev, F32, copy=True).contiguous()
+        self.ln_b = weights["ln_vision.bias"].to(self._dev, F32, copy=True).contiguous()
         self.query_tokens_f32 = weights["query_tokens"].to(self._dev, F32).contiguous()      # frozen (myriad.py:165)
         self.proj_w = weights["llama_proj.weight"].to(self._dev, BF16).contiguous()
         self.proj_b = weights["llama_proj.bias"].to(self._dev, F32).contiguous()
@@ -419,9 +420,26 @@ class MyriadHIP(nn.Module):
                 self.store.p[name].copy_(from_reference_layout(sd[name].to(self._dev, F32), ishape))
             else:
                 missing.append(name)
+        self._load_vision_keys(sd)
         if strict and missing:
             raise KeyError(missing)
         return missing
+
+    @torch.no_grad()
+    def _load_vision_keys(self, sd) -> None:
+        """visual_encoder.* / ln_vision.* entries go into the ViT and ln_vision even while they are frozen: the reference's
+        load_state_dict(strict=False) of a checkpoint from a run that trained them.  Written in place (captured ViT graphs
+        keep their storage); a look-ahead forward made with the old weights is dropped.  Nothing happens without such keys."""
+        if not any(k.startswith(("visual_encoder.", "ln_vision.")) for k in sd.keys()):
+            return
+        main = torch.cuda.current_stream()
+        self._vit_rest, self._vit_prefetched = None, None  # a pending or finished look-ahead of the old weights: dropped
+        if self._vit_stream is not None:
+            main.wait_stream(self._vit_stream)            # nothing on the side stream still reads the weights being replaced
+        self.visual_encoder.load_weights(sd)
+        for key, dst in (("ln_vision.weight", self.ln_w), ("ln_vision.bias", self.ln_b)):
+            if key in sd:
+                dst.copy_(sd[key].to(self._dev, F32).reshape(dst.shape))
 
     @classmethod
     def from_config(cls, cfg):

@@ -605,6 +605,38 @@ def gemm_rmsnorm_bwd(a, b, x, w, eps: float, dres=None, want_f32=True, want_bf16
     return dx, dxb
 
 
+def gemm_layernorm_bwd(a, b, x, w, eps: float, dres=None, want_f32=True, want_bf16=True, dgamma=None, dbeta=None,
+                       accumulate: bool = False):
+    """dY = a @ b^T (f32), then layernorm_bwd(dY, x, w) + dres -> (dx f32, dx bf16); with dgamma / dbeta (f32 [N]) also the
+    LayerNorm's parameter gradients ((+)= when accumulate).  The split-K partials are summed inside the norm kernel.  Same bits
+    as gemm(out f32) + layernorm_bwd (+ layernorm_param_grads)."""
+    _chk2d(a, BF16, "gemm_layernorm_bwd.a")
+    _chk2d(b, BF16, "gemm_layernorm_bwd.b")
+    M, K = a.shape
+    N = b.shape[0]
+    if x.shape != (M, N) or b.shape[1] != K or x.dtype != F32 or not x.is_contiguous():
+        raise _lib.MyriadHipError(f"gemm_layernorm_bwd: a {tuple(a.shape)} b {tuple(b.shape)} x {tuple(x.shape)}")
+    if w.dtype != F32 or w.numel() != N or not w.is_contiguous() or w.device != a.device:
+        raise ValueError("gemm_layernorm_bwd: w must be contiguous f32 [N] on a's device")
+    if (dgamma is None) != (dbeta is None):
+        raise ValueError("gemm_layernorm_bwd: dgamma and dbeta go together")
+    if dgamma is not None and (dgamma.dtype != F32 or dbeta.dtype != F32 or dgamma.numel() != N or dbeta.numel() != N
+                               or not dgamma.is_contiguous() or not dbeta.is_contiguous()):
+        raise ValueError("gemm_layernorm_bwd: dgamma / dbeta must be contiguous f32 [N]")
+    if dres is not None and (dres.shape != (M, N) or dres.dtype != F32 or not dres.is_contiguous()):
+        raise ValueError("gemm_layernorm_bwd: dres must be contiguous f32 [M, N]")
+    L = _L()
+    dy = torch.empty((M, N), dtype=F32, device=a.device)
+    dx = torch.empty((M, N), dtype=F32, device=a.device) if want_f32 else None
+    dxb = torch.empty((M, N), dtype=BF16, device=a.device) if want_bf16 else None
+    n = L.mh_layernorm_param_grads_ws_floats(M, N) if dgamma is not None else 0
+    ws = torch.empty((max(n, 1),), dtype=F32, device=a.device) if dgamma is not None else None
+    rc = L.mh_gemm_layernorm_bwd(_p(a), a.stride(0), _p(b), b.stride(0), _p(dy), _p(x), _p(w), _p(dres), _p(dx), _p(dxb),
+                                 _p(dgamma), _p(dbeta), int(accumulate), _p(ws), n, M, N, K, float(eps), _s())
+    _lib.check(rc, f"mh_gemm_layernorm_bwd M={M} N={N} K={K}")
+    return dx, dxb
+
+
 def layernorm_fwd(x, w, b, eps: float, want_bf16=True, want_f32=False):
     M, D = x.shape
     yb = torch.empty((M, D), dtype=BF16, device=x.device) if want_bf16 else None
