@@ -103,6 +103,7 @@ def _rope_case(B, H, S, kv, monkeypatch, split, via_gemm=None):
     q, k, v = (_heads(qkv[:, :, i * W:(i + 1) * W].float(), B, S, H, D) for i in range(3))
     qr, qe = fb.rope_bf16(q, pl, cos, sin)
     kr, ke = fb.rope_bf16(k, pl, cos, sin)
+    fb.assert_rope_exempt_share(qe, "q"), fb.assert_rope_exempt_share(ke, "k")
     valid = torch.arange(S, device=DEV)[None] < kv_len[:, None]
     dout = _rnd(B, S, W, seed=7).to(BF16).to(DEV) * valid[..., None]
     if via_gemm is not None:                               # dO = a bw^T inside mh_gemm_attn_rope_bwd
@@ -331,6 +332,7 @@ def test_attn_decode_rope_per_row_positions_and_lengths(monkeypatch):
     knew = qkv0[:, W:2 * W].float().view(B, 1, H, D).transpose(1, 2)
     qr, qe = fb.rope_bf16(q, pl, cos, sin)
     kr_new, ke_new = fb.rope_bf16(knew, pl, cos, sin)
+    fb.assert_rope_exempt_share(qe, "q"), fb.assert_rope_exempt_share(ke_new, "appended k")
     fb.assert_within(qkv[:, :W].view(B, 1, H, D).transpose(1, 2), qr, qe, "q rotated in place")
     assert torch.equal(qkv[:, W:], qkv0[:, W:]), "k / v columns and the border of qkv must not change"
     fb.assert_within(cache[:, app, :W].view(B, 1, H, D).transpose(1, 2), kr_new, ke_new, "appended k")

@@ -206,3 +206,626 @@ def test_attention_emulation_is_within_the_bound():
 def test_attention_mutant_fails_the_bound(mutant):
     with pytest.raises(AssertionError, match="out of bound"):
         _attn_case(mutant)
+
+
+# ------------------------------------------------------------------------------------------------------------ row kernels
+def emu_row_sum(terms, skip_last_chunk=False):
+    """Sum over the last axis of fp32 terms [M, D] (D % 4 == 0) in the row kernels' order: thread t adds its float4 chunks
+    (columns 4 t + 1024 k) serially, each chunk as ((a + b) + c) + d; a 64-lane butterfly; the four wave values in order."""
+    M, D = terms.shape
+    if skip_last_chunk:
+        terms = terms.clone()
+        terms[:, D - 4:] = 0
+    K = -(-D // 1024)
+    t = torch.zeros(M, K * 1024, dtype=F32)
+    t[:, :D] = terms
+    t = t.view(M, K, 256, 4)
+    chunk = ((t[..., 0] + t[..., 1]) + t[..., 2]) + t[..., 3]
+    s = torch.zeros(M, 256, dtype=F32)
+    for k in range(K):
+        s = s + chunk[:, k]
+    v = s.view(M, 4, 64)
+    lane = torch.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        v = v + v[:, :, lane ^ o]
+    out = torch.zeros(M, dtype=F32)
+    for w in range(4):
+        out = out + v[:, w, 0]
+    return out[:, None]
+
+
+def emu_block_sum(part):
+    """block_sum of per-thread fp32 values [M, 64 NW]: a 64-lane butterfly in each wave, then the NW wave values in order."""
+    M = part.shape[0]
+    v = part.view(M, -1, 64)
+    lane = torch.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        v = v + v[:, :, lane ^ o]
+    out = torch.zeros(M, dtype=F32)
+    for w in range(v.shape[1]):
+        out = out + v[:, w, 0]
+    return out[:, None]
+
+
+def emu_strided_sum(terms, nt=256):
+    """Thread t adds elements t, t + nt, ... serially (sum_kernel, pmax_kernel, the low-rank dot products); then block_sum."""
+    M, n = terms.shape
+    K = -(-n // nt)
+    t = torch.zeros(M, K * nt, dtype=F32)
+    t[:, :n] = terms
+    t = t.view(M, K, nt)
+    part = torch.zeros(M, nt, dtype=F32)
+    for k in range(K):
+        part = part + t[:, k]
+    return emu_block_sum(part)
+
+
+def emu_rmsnorm_fwd(x, w, eps, out, mutant=None):
+    M, D = x.shape
+    ss = emu_row_sum(x * x, mutant == "skip_last_float4")
+    if mutant == "eps_dropped":
+        r = torch.rsqrt(ss / D)
+    elif mutant == "eps_outside":
+        r = torch.rsqrt(ss / D) + eps
+    else:
+        r = torch.rsqrt(ss / D + eps)
+    y = (w * (x * r)).to(BF16)
+    rows = [m for m in range(M) if not (mutant == "skip_row" and m == M // 2)]
+    if mutant == "ldy_as_D":                                  # row m lands at flat offset m * D of the window's storage
+        flat = out.as_strided((M * D,), (1,), out.storage_offset())
+        flat[:] = y.reshape(-1)
+        return
+    out[rows] = y[rows]
+
+
+def emu_rmsnorm_bwd(dy, x, w, eps, dres, dx, dxb, mutant=None):
+    M, D = x.shape
+    ss = emu_row_sum(x * x, mutant == "skip_last_float4")
+    dot = emu_row_sum(x * w * dy, mutant == "skip_last_float4")
+    r = torch.rsqrt(ss / D + eps)
+    cc = r * r * r * dot / D
+    o = (r * w) * dy - x * cc
+    ob = o + dres
+    if mutant != "dres_not_added":
+        o = o + dres
+    if mutant != "bf16_before_dres":
+        ob = o
+    else:
+        ob = ob - dres
+    dx[:] = o
+    dxb[:] = ob.to(BF16)
+
+
+def emu_layernorm(x, w, b, eps, dy, dres, mutant=None):
+    """(y f32, y bf16, dx f32, dx bf16) as layernorm_fwd_kernel / layernorm_bwd_kernel compute them."""
+    M, D = x.shape
+    skip = mutant == "skip_last_float4"
+    mean = emu_row_sum(x, skip) / D
+    if mutant == "mean_of_previous_row":
+        mean = torch.roll(mean, 1, 0)
+    d = x - mean
+    var = emu_row_sum(d * d, skip) / D
+    if mutant == "eps_dropped":
+        r = torch.rsqrt(var)
+    elif mutant == "eps_outside":
+        r = torch.rsqrt(var) + eps
+    else:
+        r = torch.rsqrt(var + eps)
+    y = d * r * w + b
+    gw = dy * w
+    sg = emu_row_sum(gw, skip) / D
+    sgx = emu_row_sum(gw * d * r, skip) / D
+    dx = r * (gw - sg - d * r * sgx)
+    if mutant != "dres_not_added":
+        dx = dx + dres
+    return y, y.to(BF16), dx, dx.to(BF16)
+
+
+NORM_EPS = [1e-6, 1e-5, 1e-12]
+NORM_CPU_CASES = [(7, 252, 1e-6), (13, 1028, 1e-12), (6, 4100, 1e-5), (1, 4, 1e-6)]
+RMS_FWD_MUTANTS = ["skip_last_float4", "eps_dropped", "eps_outside", "skip_row", "ldy_as_D"]
+RMS_BWD_MUTANTS = ["skip_last_float4", "dres_not_added", "bf16_before_dres"]
+LN_MUTANTS = ["skip_last_float4", "eps_dropped", "eps_outside", "mean_of_previous_row", "dres_not_added"]
+
+
+def _rms_case(M, D, eps, mutant, which):
+    x, w = fb.norm_rows(M, D, seed=21), fb.norm_weight(D, seed=22)
+    dy, dres = fb.rnd(M, D, seed=23), fb.rnd(M, D, seed=24)
+    r = fb.rmsnorm_ref_bound(x, w, eps, dy=dy, dres=dres)
+    ratios = []
+    if which == "fwd":
+        buf = fb.poisoned((M + 2, D + 72), BF16, "cpu")
+        win = buf[1:M + 1, 8:8 + D]
+        emu_rmsnorm_fwd(x, w, eps, win, mutant)
+        ratios.append(fb.assert_within(win, r["y"], r["y_bf16_bound"], "rmsnorm fwd"))
+        fb.assert_frame_untouched(buf, slice(1, M + 1), slice(8, 8 + D), "rmsnorm fwd")
+    else:
+        dx, dxb = fb.poisoned((M, D), F32, "cpu"), fb.poisoned((M, D), BF16, "cpu")
+        emu_rmsnorm_bwd(dy, x, w, eps, dres, dx, dxb, mutant)
+        ratios.append(fb.assert_within(dx, r["dx"], r["dx_bound"], "rmsnorm bwd f32"))
+        ratios.append(fb.assert_within(dxb, r["dx"], r["dx_bf16_bound"], "rmsnorm bwd bf16"))
+    return ratios
+
+
+def _ln_case(M, D, eps, mutant):
+    x, w, b = fb.norm_rows(M, D, seed=31), fb.norm_weight(D, seed=32), 0.1 * fb.rnd(D, seed=33)
+    dy, dres = fb.rnd(M, D, seed=34), fb.rnd(M, D, seed=35)
+    r = fb.layernorm_ref_bound(x, w, b, eps, dy=dy, dres=dres)
+    y, yb, dx, dxb = emu_layernorm(x, w, b, eps, dy, dres, mutant)
+    return [fb.assert_within(y, r["y"], r["y_bound"], "layernorm y f32"),
+            fb.assert_within(yb, r["y"], r["y_bf16_bound"], "layernorm y bf16"),
+            fb.assert_within(dx, r["dx"], r["dx_bound"], "layernorm dx f32"),
+            fb.assert_within(dxb, r["dx"], r["dx_bf16_bound"], "layernorm dx bf16")]
+
+
+@pytest.mark.parametrize("M,D,eps", NORM_CPU_CASES)
+def test_norm_emulations_are_within_the_bound(M, D, eps):
+    ratios = _rms_case(M, D, eps, None, "fwd") + _rms_case(M, D, eps, None, "bwd") + _ln_case(M, D, eps, None)
+    assert max(ratios) > 1e-3, "the bounds are so loose that the emulation's rounding does not register"
+
+
+@pytest.mark.parametrize("mutant", RMS_FWD_MUTANTS)
+def test_rmsnorm_fwd_mutant_fails(mutant):
+    with pytest.raises(AssertionError):
+        _rms_case(13, 1028, 1e-6, mutant, "fwd")
+
+
+@pytest.mark.parametrize("mutant", RMS_BWD_MUTANTS)
+def test_rmsnorm_bwd_mutant_fails(mutant):
+    with pytest.raises(AssertionError):
+        _rms_case(13, 1028, 1e-6, mutant, "bwd")
+
+
+@pytest.mark.parametrize("mutant", LN_MUTANTS)
+def test_layernorm_mutant_fails(mutant):
+    with pytest.raises(AssertionError):
+        _ln_case(13, 1028, 1e-6, mutant)
+
+
+def test_norm_generators_keep_every_row_well_defined():
+    """The condition on the inputs: no row's variance is lost to the mean's rounding unless the row is constant
+    (layernorm_ref_bound raises otherwise), at every width and eps the GPU module uses."""
+    for D in (4, 252, 256, 1028, 1408, 4096, 4100, 8192):
+        for eps in NORM_EPS:
+            x = fb.norm_rows(12, D, seed=D)
+            fb.layernorm_ref_bound(x, fb.norm_weight(D, seed=1), torch.zeros(D), eps)
+
+
+# -------------------------------------------------------------------------------------------------------------- clamp-CE
+def emu_clamp_ce(x, labels, gscale, row_loss, dlog, V, mutant=None):
+    """clamp_ce_wide_kernel's arithmetic on fp32 logits [R, V]; dlog is the [R, ldd] window (pad columns zeroed)."""
+    R = x.shape[0]
+    ldd = dlog.shape[1]
+    Vs = V - V % 4 if mutant == "tail_dropped" else V
+    m = x[:, :Vs].amax(1, keepdim=True)
+    e = torch.exp(x - m)
+    assert V <= 8 * 4096
+    terms = torch.zeros(R, 8, 1024, 4, dtype=F32)            # chunk i of thread t: columns (i * 1024 + t) * 4 .. + 3
+    terms.view(R, -1)[:, :Vs] = e[:, :Vs]
+    part = torch.zeros(R, 1024, dtype=F32)
+    for i in range(8):                                       # the thread's 32 exponentials, serially
+        for q in range(4):
+            part = part + terms[:, i, :, q]
+    se = emu_block_sum(part)
+    inv = 1.0 / se
+    for i in range(R):
+        t = int(labels[i])
+        gate = 0.0
+        if 0 <= t < V:
+            pt = torch.exp(x[i, t] - m[i, 0]) * inv[i, 0]
+            row_loss[i] = -torch.log(pt.clamp(fb.CE_LO, fb.CE_HI))
+            gate = gscale if (fb.CE_LO <= float(pt) <= fb.CE_HI or mutant == "gate_not_applied") else 0.0
+        else:
+            row_loss[i] = 0.0
+            if mutant == "ignored_row_gets_gradient":
+                gate, t = gscale, 0
+        g = torch.zeros(ldd, dtype=F32)
+        if gate != 0.0:
+            g[:V] = gate * (e[i] * inv[i, 0])
+            g[t + (1 if mutant == "onehot_off_by_one" and t + 1 < V else 0)] -= gate
+        n = V if mutant == "pad_not_zeroed" else ldd
+        dlog[i, :n] = g[:n].to(BF16)
+
+
+CE_MUTANTS = ["tail_dropped", "pad_not_zeroed", "gate_not_applied", "ignored_row_gets_gradient", "onehot_off_by_one"]
+
+
+def _ce_case(V, ldd, mutant):
+    R = 12
+    x, y = fb.ce_case(R, V, seed=V)
+    if mutant == "tail_dropped":
+        x[9, V - 1] = x[9].max() + 3                          # the row's maximum sits in the scalar tail
+    loss = fb.poisoned((R,), F32, "cpu")
+    buf = fb.poisoned((R + 2, ldd + 16), BF16, "cpu")
+    win = buf[1:R + 1, 8:8 + ldd]
+    emu_clamp_ce(x, y, 0.125, loss, win, V, mutant)
+    r = fb.clamp_ce_ref_bound(x, y, 0.125, ldd=ldd)
+    assert int(r["amb"].sum()) == 0                          # the generator keeps every row decisively off the thresholds
+    ratios = fb.clamp_ce_check(loss, win, r)
+    fb.assert_frame_untouched(buf, slice(1, R + 1), slice(8, 8 + ldd), "clamp_ce")
+    return ratios
+
+
+@pytest.mark.parametrize("V,ldd", [(1001, 1024), (320, 320), (1003, 1007)])
+def test_clamp_ce_emulation_is_within_the_bound(V, ldd):
+    assert max(_ce_case(V, ldd, None)) > 1e-3
+
+
+@pytest.mark.parametrize("mutant", CE_MUTANTS)
+def test_clamp_ce_mutant_fails(mutant):
+    with pytest.raises(AssertionError):
+        _ce_case(1001, 1024, mutant)
+
+
+def test_clamp_ce_threshold_row_may_take_either_branch_and_nothing_else():
+    """A row with p_t on the lower threshold is ambiguous: gradient or zeros both pass; a wrong loss still fails."""
+    V = 64
+    x = torch.zeros(2, V)
+    x[0, 5] = float(torch.log(torch.tensor(fb.CE_LO * (V - 1) / (1 - fb.CE_LO), dtype=torch.float64)))
+    y = torch.tensor([5, 7])
+    r = fb.clamp_ce_ref_bound(x, y, 1.0)
+    assert r["amb"].tolist() == [True, False]
+    for branch in ("live", "dead"):
+        loss, d = fb.poisoned((2,), F32, "cpu"), fb.poisoned((2, V), BF16, "cpu")
+        emu_clamp_ce(x, y, 1.0, loss, d, V)
+        d[0] = (r["dlog"][0] if bool(r["inside"][0]) == (branch == "live") else r["dlog_alt"][0]).to(BF16)
+        fb.clamp_ce_check(loss, d, r)
+    loss[0] = loss[0] * 1.01
+    with pytest.raises(AssertionError, match="neither branch"):
+        fb.clamp_ce_check(loss, d, r)
+
+
+@pytest.mark.parametrize("V", [320, 1001, 32000, 32001, 32768, 32772, 50000])
+def test_clamp_ce_generator_has_no_threshold_rows(V):
+    """The condition on the inputs: at every vocabulary size the GPU module uses, no generated row is a threshold row."""
+    x, y = fb.ce_case(12, V, seed=V)
+    r = fb.clamp_ce_ref_bound(x, y, 0.125)
+    assert int(r["amb"].sum()) == 0
+    assert r["has"].tolist() == [True] * 3 + [False] * 2 + [True] * 7 and not bool(r["inside"][6:9].any())
+
+
+# ----------------------------------------------------------------------------------------------------------- elementwise
+def emu_silu(gu, I, blk, dh=None, read_blk=None, drop_term=False, sweep_limit=None):
+    """silu_mul fwd (dh None) or bwd on bf16 gu [M, 2 I] in the plain (blk 0) or interleaved layout, fp32 arithmetic."""
+    read_blk = blk if read_blk is None else read_blk
+    M = gu.shape[0]
+    c = torch.arange(I)
+    gc = c if read_blk == 0 else (c // read_blk) * 2 * read_blk + c % read_blk
+    us = I if read_blk == 0 else read_blk
+    g, u = gu[:, gc].float(), gu[:, gc + us].float()
+    s = 1.0 / (1.0 + torch.exp(-g))
+    if dh is None:
+        out = fb.poisoned((M, I), BF16, "cpu")
+        res = (g * s * u).to(BF16)
+        n = M * I if sweep_limit is None else sweep_limit
+        out.view(-1)[:n] = res.view(-1)[:n]
+        return out
+    d = dh.float()
+    silu = g * s
+    dgu = fb.poisoned((M, 2 * I), BF16, "cpu")
+    dgu[:, gc] = (d * u * (s if drop_term else s + silu * (1 - s))).to(BF16)
+    dgu[:, gc + us] = (d * silu).to(BF16)
+    return dgu
+
+
+def ew_values(*shape, seed):
+    """bf16 values spanning +-30 (saturation on both sides) with N(0, 1) in between."""
+    x = fb.rnd(*shape, seed=seed)
+    flat = x.view(-1)
+    flat[::7] *= 10
+    flat[0], flat[1], flat[2], flat[3] = 30.0, -30.0, 0.0, -0.0
+    return x.to(BF16)
+
+
+def _silu_case(blk, mutant):
+    M, I = 9, 256
+    gu, dh = ew_values(M, 2 * I, seed=41), ew_values(M, I, seed=42)
+    c = torch.arange(I)
+    gc = c if blk == 0 else (c // blk) * 2 * blk + c % blk
+    us = I if blk == 0 else blk
+    h, hb, dg, dgb, du, dub = fb.silu_mul_ref_bound(gu[:, gc], gu[:, gc + us], dh)
+    kw = dict(read_blk=0) if mutant == "blk_read_as_plain" else {}
+    got = emu_silu(gu, I, blk, sweep_limit=M * I // 2 if mutant == "second_sweep_skipped" else None, **kw)
+    ratios = [fb.assert_within(got, h, hb, "silu fwd")]
+    dgu = emu_silu(gu, I, blk, dh, drop_term=mutant == "silu_grad_term_dropped", **kw)
+    ratios.append(fb.assert_within(dgu[:, gc], dg, dgb, "silu bwd dg"))
+    ratios.append(fb.assert_within(dgu[:, gc + us], du, dub, "silu bwd du"))
+    return ratios
+
+
+@pytest.mark.parametrize("blk", [0, 128])
+def test_silu_emulation_is_within_the_bound(blk):
+    assert max(_silu_case(blk, None)) > 1e-3
+
+
+@pytest.mark.parametrize("blk,mutant", [(0, "second_sweep_skipped"), (0, "silu_grad_term_dropped"), (128, "blk_read_as_plain")])
+def test_silu_mutant_fails(blk, mutant):
+    with pytest.raises(AssertionError):
+        _silu_case(blk, mutant)
+
+
+def test_gelu_emulation_is_within_the_bound_and_a_tanh_form_is_not():
+    x, dy = ew_values(16, 64, seed=43), ew_values(16, 64, seed=44)
+    xf = x.float().requires_grad_(True)
+    y = torch.nn.functional.gelu(xf)
+    (y * dy.float()).sum().backward()
+    ref, bnd = fb.gelu_ref_bound(x)
+    fb.assert_within(y.detach().to(BF16), ref, bnd, "gelu fwd")
+    rb, bb = fb.gelu_ref_bound(x, dy)
+    fb.assert_within(xf.grad.to(BF16), rb, bb, "gelu bwd")
+    with pytest.raises(AssertionError):
+        fb.assert_within(torch.nn.functional.gelu(x.float(), approximate="tanh").to(BF16), ref, bnd, "gelu tanh")
+
+
+def _rope_case(sign, mutant):
+    n, nh, d, col0, ld = 37, 3, 88, 8, 3 * 88 + 24
+    x = fb.rnd(n, ld, seed=51).to(BF16)
+    cos, sin = fb.rope_tables(d, 64)
+    pos = torch.randint(0, 64, (n,), generator=torch.Generator().manual_seed(5)).int()          # non-monotone, repeated
+    ref, amb = fb.rope_rows_ref(x, col0, nh, d, pos, cos, sin, sign)
+    assert float((amb > 0).double().mean()) <= 0.01
+    xs = x[:, col0:col0 + nh * d].float().reshape(1, n, nh, d).transpose(1, 2)
+    got = fb.rope64(xs, pos.long()[None], cos, sin, 1.0 if mutant == "sign_ignored" else sign).to(BF16)
+    return fb.assert_within(got.transpose(1, 2).reshape(n, -1), ref, amb, "rope")
+
+
+def test_rope_emulation_matches_and_an_ignored_sign_does_not():
+    _rope_case(1.0, None)
+    _rope_case(-1.0, None)
+    with pytest.raises(AssertionError):
+        _rope_case(-1.0, "sign_ignored")
+
+
+# --------------------------------------------------------------------------------------------------------------- gathers
+def emu_expand_rows(src, inv, M, mutant=None):
+    out = fb.poisoned((M, src.shape[1]), src.dtype, "cpu")
+    for m in range(M):
+        i = int(inv[m * 2] if mutant == "index_stride" else inv[m])
+        if i >= 0:
+            out[m] = src[i]
+        elif mutant != "negative_left_unwritten":
+            out[m] = 0
+    return out
+
+
+@pytest.mark.parametrize("mutant", [None, "negative_left_unwritten", "index_stride"])
+def test_expand_rows_reference_catches_unwritten_and_misindexed_rows(mutant):
+    src = fb.rnd(5, 8, seed=61)
+    inv = torch.tensor([3, -1, 0, 0, 4, -1, 2, 1, -1, 3, 3, -1, 0, 2], dtype=torch.int32)
+    M = 7
+    want = torch.where((inv[:M] >= 0)[:, None], src[inv[:M].clamp_min(0).long()], torch.zeros(M, 8))
+
+    def check():
+        got = emu_expand_rows(src, inv, M, mutant)
+        assert not bool(fb.untouched(got).any()) and torch.equal(got, want)
+
+    if mutant is None:
+        check()
+    else:
+        with pytest.raises(AssertionError):
+            check()
+
+
+# ------------------------------------------------------------------------------- l2norm, sum, arg-max / p_max, dropout, GELU'
+L2_MUTANTS = ["skip_last_float4", "eps_inside_sqrt", "clamp_omitted"]
+
+
+def _l2norm_case(M, D, mutant):
+    x = fb.norm_rows(M, D, seed=71)
+    ss = emu_row_sum(x * x, mutant == "skip_last_float4")
+    if mutant == "eps_inside_sqrt":
+        n = torch.sqrt(ss + 1e-6)
+    elif mutant == "clamp_omitted":
+        n = torch.sqrt(ss)
+    else:
+        n = torch.sqrt(ss).clamp_min(1e-6)
+    y = x * (1.0 / n)
+    ref, e, eb = fb.l2norm_ref_bound(x, 1e-6)
+    return [fb.assert_within(y, ref, e, "l2norm f32"), fb.assert_within(y.to(BF16), ref, eb, "l2norm bf16")]
+
+
+@pytest.mark.parametrize("M,D", [(7, 252), (6, 1028), (1, 4)])
+def test_l2norm_emulation_is_within_the_bound(M, D):
+    assert max(_l2norm_case(M, D, None)) > 1e-3
+
+
+@pytest.mark.parametrize("mutant", L2_MUTANTS)
+def test_l2norm_mutant_fails(mutant):
+    with pytest.raises(AssertionError):
+        _l2norm_case(7, 252, mutant)
+
+
+def _sum_case(mutant):
+    n = 1003
+    x = fb.rnd(n, seed=72)
+    x[1::2] = -x[::2][:n // 2] * (1 + 2 ** -10)              # nearly cancelling pairs: |sum| << sum |x|
+    terms = x[None].clone()
+    if mutant == "tail_dropped":
+        terms[:, n - n % 256:] = 0
+    got = emu_strided_sum(terms)[0] * torch.tensor(3.0)
+    ref, b = fb.sum_ref_bound(x, 3.0)
+    return fb.assert_within(got, ref.reshape(1), b.reshape(1), "sum_f32")
+
+
+def test_sum_emulation_is_within_the_bound_and_a_dropped_tail_is_not():
+    assert _sum_case(None) > 1e-3
+    with pytest.raises(AssertionError):
+        _sum_case("tail_dropped")
+
+
+def _pmax_case(mutant, inv_temp=0.7):
+    R, V, ban = 4, 1001, 999
+    x = fb.rnd(R, V, seed=73) * 3
+    x[1, 300] = x[1].max() + 1.0
+    x[1, 307] = x[1, 300]                                    # a tie
+    x[2, ban] = x[2].max() + 5.0
+    ids_r, mar_r, mar_b, pm_r, pm_b = fb.argmax_ref(x, ban, inv_temp)
+    xb = x.clone()
+    xb[:, ban] = float("-inf")
+    top = xb.topk(2, 1).values
+    ids = xb.argmax(1)
+    if mutant == "tie_to_later_index":
+        ids[1] = 307
+    assert torch.equal(ids, ids_r), "arg-max ids"
+    fb.assert_within(top[:, 0] - top[:, 1], mar_r, mar_b, "margin")
+    a = (xb - top[:, :1]) * (1.0 if mutant == "inv_temp_ignored" else torch.tensor(inv_temp))
+    if mutant == "ban_counted":
+        a[:, ban] = (x[:, ban] - top[:, 0]) * inv_temp
+    pm = 1.0 / emu_strided_sum(torch.exp(a))[:, 0]
+    return fb.assert_within(pm, pm_r, pm_b, "p_max")
+
+
+def test_pmax_emulation_is_within_the_bound():
+    assert _pmax_case(None) > 1e-3 and int(fb.argmax_ref(fb.rnd(2, 8, seed=1) * 0, -1)[0][0]) == 0
+
+
+@pytest.mark.parametrize("mutant", ["inv_temp_ignored", "tie_to_later_index", "ban_counted"])
+def test_pmax_mutant_fails(mutant):
+    with pytest.raises(AssertionError):
+        _pmax_case(mutant)
+
+
+def _dropout_case(mutant):
+    p = 0.1
+    x, acc, dy = ew_values(8, 64, seed=74), fb.rnd(8, 64, seed=75), fb.rnd(8, 64, seed=76)
+    keep = (torch.rand(8, 64, generator=torch.Generator().manual_seed(7)) >= p).float() * torch.tensor(1 / (1 - p))
+    used = (keep > 0).float() if mutant == "scale_missing" else (torch.roll(keep, 1, 1) if mutant == "mask_shifted" else keep)
+    ref = x.double() * keep.double()
+    r1 = fb.assert_within((x.float() * used).to(BF16), ref, fb.bf16_out(ref, fb.U32 * ref.abs()), "dropout_bf16")
+    add = dy.double() * keep.double()
+    ref2 = acc.double() + add
+    r2 = fb.assert_within(acc + dy * used, ref2, fb.U32 * (add.abs() + ref2.abs()), "dropout_add_")
+    return max(r1, r2)
+
+
+def test_dropout_emulation_is_within_the_bound_and_wrong_masks_are_not():
+    assert _dropout_case(None) > 1e-3
+    for mutant in ("scale_missing", "mask_shifted"):
+        with pytest.raises(AssertionError):
+            _dropout_case(mutant)
+
+
+def test_gelu_backward_mutants_fail():
+    x, dy = ew_values(16, 64, seed=43), ew_values(16, 64, seed=44)
+    ref, bnd = fb.gelu_ref_bound(x, dy)
+    xf = x.float()
+    cdf = 0.5 * torch.special.erfc(-xf / 2 ** 0.5)
+    pdf = torch.exp(-xf * xf / 2) * 0.3989422804014327
+    fb.assert_within((dy.float() * (cdf + xf * pdf)).to(BF16), ref, bnd, "gelu bwd")
+    for wrong in (cdf, cdf + pdf, cdf - xf * pdf):           # the x pdf term dropped, without its x, with the wrong sign
+        with pytest.raises(AssertionError):
+            fb.assert_within((dy.float() * wrong).to(BF16), ref, bnd, "gelu bwd mutant")
+
+
+# ------------------------------------------------------------------------------------------------ LayerNorm parameter gradients
+def emu_param_grads(dy, x, eps, keep=None, prev=None, mutant=None):
+    """layernorm_param_partial_kernel + reduce: the row statistics as the LayerNorm kernels compute them, a column summed
+    serially over the 16 rows of a block, then the blocks in order."""
+    M, D = x.shape
+    mean = emu_row_sum(x) / D
+    d = x - mean
+    r = torch.rsqrt(emu_row_sum(d * d) / D + eps)
+    if mutant == "mean_not_subtracted":
+        d = x
+    g = dy * keep if keep is not None and mutant != "mask_ignored" else dy
+    tg, tb = g * (d * r), g
+    dg, db = torch.zeros(D), torch.zeros(D)
+    nblk = -(-M // 16)
+    for blk in range(nblk - (1 if mutant == "last_block_dropped" else 0)):
+        pg, pb = torch.zeros(D), torch.zeros(D)
+        for m in range(16 * blk, min(M, 16 * blk + 16)):
+            pg, pb = pg + tg[m], pb + tb[m]
+        dg, db = dg + pg, db + pb
+    if prev is not None and mutant != "accumulate_overwrites":
+        dg, db = prev[0] + dg, prev[1] + db
+    return dg, db
+
+
+PG_MUTANTS = ["mean_not_subtracted", "mask_ignored", "last_block_dropped", "accumulate_overwrites"]
+
+
+def _pg_case(M, D, eps, mutant):
+    x, dy = fb.norm_rows(M, D, seed=81), fb.rnd(M, D, seed=82)
+    keep = (torch.rand(M, D, generator=torch.Generator().manual_seed(8)) >= 0.1).float() * torch.tensor(1 / 0.9)
+    prev = (fb.rnd(D, seed=83), fb.rnd(D, seed=84))
+    dg, db = emu_param_grads(dy, x, eps, keep, prev, mutant)
+    rg, eg, rb, eb = fb.layernorm_param_grads_ref_bound(dy, x, eps, keep, prev)
+    return [fb.assert_within(dg, rg, eg, "dgamma"), fb.assert_within(db, rb, eb, "dbeta")]
+
+
+@pytest.mark.parametrize("M,D,eps", [(37, 252, 1e-6), (1, 4, 1e-12), (20, 1028, 1e-5)])
+def test_param_grads_emulation_is_within_the_bound(M, D, eps):
+    assert max(_pg_case(M, D, eps, None)) > 1e-3
+
+
+@pytest.mark.parametrize("mutant", PG_MUTANTS)
+def test_param_grads_mutant_fails(mutant):
+    with pytest.raises(AssertionError):
+        _pg_case(37, 252, 1e-6, mutant)
+
+
+# ------------------------------------------------------------------------------------------------------- low-rank adaptor
+def lowrank_case_inputs(M, D, R, seed):
+    """x, A, Bm, dy with a gradient that cancels over the rows: rows come in (g, -g (1 + 2^-10)) pairs."""
+    x = fb.rnd(M, D, seed=seed)
+    A, Bm = fb.rnd(R, D, seed=seed + 1) * 0.05, fb.rnd(D, R, seed=seed + 2) * 0.05
+    dy = fb.rnd(M, D, seed=seed + 3)
+    dy[1::2] = -dy[::2][:M // 2] * (1 + 2 ** -10)
+    return x, A, Bm, dy
+
+
+def emu_lowrank(x, A, Bm, dy, mutant=None):
+    M, D = x.shape
+    R = A.shape[0]
+    t = torch.cat([emu_strided_sum(x * A[r]) for r in range(R)], 1)
+    y = x.clone()
+    for r in range(R):
+        y = y + t[:, r:r + 1] * Bm[:, r]
+    dt = torch.cat([emu_strided_sum(dy * Bm[:, r]) for r in range(R)], 1)
+    dx = torch.zeros_like(dy) if mutant == "dx_without_dy" else dy.clone()
+    for r in range(R):
+        dx = dx + dt[:, r:r + 1] * A[r]
+    rows_per = -(-M // 16)
+    dA, dB = torch.zeros(R, D), torch.zeros(D, R)
+    Dk = D - D % 64 if mutant == "ragged_columns_dropped" else D
+    for c in range(16):
+        if mutant == "last_chunk_dropped" and c == (M - 1) // rows_per:      # the last chunk that holds rows
+            continue
+        pa, pb = [torch.zeros(R, D) for _ in range(4)], [torch.zeros(D, R) for _ in range(4)]
+        for m in range(c * rows_per, min(M, (c + 1) * rows_per)):
+            ty = (m - c * rows_per) % 4
+            pa[ty] = pa[ty] + dt[m][:, None] * x[m][None]
+            pb[ty] = pb[ty] + dy[m][:, None] * t[m][None]
+        dA = dA + (((pa[0] + pa[1]) + pa[2]) + pa[3])
+        dB = dB + (((pb[0] + pb[1]) + pb[2]) + pb[3])
+    dA[:, Dk:], dB[Dk:] = 0, 0
+    return t, y, dx, dA, dB
+
+
+LR_MUTANTS = ["dx_without_dy", "ragged_columns_dropped", "last_chunk_dropped"]
+
+
+def _lowrank_case(M, D, R, mutant):
+    x, A, Bm, dy = lowrank_case_inputs(M, D, R, seed=91)
+    t, y, dx, dA, dB = emu_lowrank(x, A, Bm, dy, mutant)
+    r = fb.lowrank_ref_bound(x, A, Bm, dy, t_in=t)
+    return [fb.assert_within(got, r[k], r[k + "_bound"], "lowrank " + k)
+            for k, got in (("t", t), ("y", y), ("dx", dx), ("dA", dA), ("dB", dB))]
+
+
+@pytest.mark.parametrize("M,D,R", [(37, 300, 4), (1, 68, 2), (130, 1408, 4)])
+def test_lowrank_emulation_is_within_the_bound(M, D, R):
+    assert max(_lowrank_case(M, D, R, None)) > 1e-3
+
+
+@pytest.mark.parametrize("mutant", LR_MUTANTS)
+def test_lowrank_mutant_fails(mutant):
+    with pytest.raises(AssertionError):
+        _lowrank_case(37, 300, 4, mutant)
+
+
+def test_attention_case_rope_ambiguity_stays_rare():
+    q = fb.rnd(2, 2, 150, 64, seed=11).to(BF16)
+    pos = torch.arange(150)[None] + 5 * torch.arange(2)[:, None]
+    cos, sin = fb.rope_tables(64)
+    fb.assert_rope_exempt_share(fb.rope_bf16(q.float(), pos, cos, sin)[1], "q")

@@ -431,7 +431,8 @@ def test_gemm_residual_layernorm_is_bit_identical_to_two_launches(M, N, K):
     assert relerr(y.float(), ref) < 1e-2
 
 
-@pytest.mark.parametrize("M,N,K", [(1184, 4096, 22016), (1184, 4096, 4096), (300, 512, 256), (148, 4096, 11008), (37, 64, 128)])
+@pytest.mark.parametrize("M,N,K", [(1184, 4096, 22016), (1184, 4096, 4096), (300, 512, 256), (148, 4096, 11008), (37, 64, 128),
+                                   (1028, 5120, 4096), (77, 8192, 512)])       # N > 4096: rmsnorm_bwd_kernel<8>, split and unsplit
 def test_gemm_rmsnorm_bwd_is_bit_identical_to_two_launches(M, N, K):
     """A dgrad Linear and the RMSNorm backward that consumes it: the split-K slabs are summed inside the norm kernel (split
     shapes) or the GEMM writes dY and the norm kernel reads it (the rest) -- same bits either way; and against torch autograd."""

@@ -62,7 +62,7 @@ def test_gemm_layernorm_bwd_bits_equal_the_unfused_launches(M, K, params):
 
 
 @pytest.mark.parametrize("M,N,K,params", [(1028, 3072, 4096, True), (257, 3072, 1024, True), (1028, 5120, 4096, False),
-                                          (77, 8192, 512, False)])
+                                          (77, 8192, 512, False), (514, 4096, 4096, True), (257, 6144, 2048, False)])
 def test_gemm_layernorm_bwd_wide_rows_bits(M, N, K, params):
     """Rows wider than 2048 (4 and 8 float4 chunks a thread in the slab kernel), split and unsplit."""
     ops.ensure_workspace(DEV)
