@@ -426,6 +426,20 @@ int mh_scatter_rows_f32(const float* src, const int* rows, float* dst, long ldd,
 int mh_cast_f32_to_bf16(const float* x, void* y, long n, mh_stream_t s);
 int mh_cast_bf16_to_f32(const void* x, float* y, long n, mh_stream_t s);
 int mh_transpose_to_bf16(const void* in, int in_is_f32, long ldi, void* out, long ldo, int R, int C, mh_stream_t s);
+/* Master -> working-copy refresh of trainable weight matrices (freeze_vit: False), batched.  From a row-major contiguous f32
+ * [R, C] source one pass writes the bf16 row-major copy dst (row stride ld_dst >= C elements) and the bf16 transposed copy
+ * dst_t [C, R] (row stride ld_t >= R); either destination may be NULL, not both.  Only elements inside [R, C] are written (the
+ * padding of a wider destination keeps its contents); the bits are those of mh_cast_f32_to_bf16 / mh_transpose_to_bf16.
+ * One launch walks a DEVICE-resident table of n_desc descriptors (mh_refresh_bf16_pair_desc_bytes() bytes each, 16-byte
+ * aligned), built on the host: mh_refresh_bf16_pair_pack writes entry `index` of a host table for a matrix whose first tile is
+ * `first_tile` (0 for the first matrix) and returns the next matrix's first tile -- after the last matrix the launch's
+ * total_tiles -- or MH_ERR_ARG (< 0) for a NULL / misaligned pointer, R or C <= 0, or a destination row shorter than the
+ * source's.  Entries must be packed in index order.  mh_refresh_bf16_pair returns MH_ERR_ARG before any launch for a NULL or
+ * misaligned table or counts that cannot belong to one. */
+long mh_refresh_bf16_pair_desc_bytes(void);
+long mh_refresh_bf16_pair_pack(void* host_table, int index, long first_tile, const float* src, void* dst, long ld_dst,
+                               void* dst_t, long ld_t, int R, int C);
+int mh_refresh_bf16_pair(const void* dev_table, int n_desc, long total_tiles, mh_stream_t s);
 int mh_colsum_f32(const float* in, long ld, float* out, long R, int C, mh_stream_t s);
 int mh_scale_f32(float* x, float a, long n, mh_stream_t s);
 

@@ -206,6 +206,14 @@ _QF_LAYER_ORDER = [blk + t for blk in ("attention.", "crossattention.")
      "output_query.dense.bias", "output_query.LayerNorm.weight", "output_query.LayerNorm.bias"]
 
 
+# named_parameters() order inside one Block of the EVA ViT (eva_vit.py:153-180: norm1, attn, norm2, mlp; Attention's own
+# q_bias / v_bias come before its children qkv, proj, :76-116).  tests/golden/vit_param_order.json is the reference module's listing.
+_VIT_BLOCK_ORDER = ["norm1.weight", "norm1.bias", "attn.q_bias", "attn.v_bias", "attn.qkv.weight", "attn.proj.weight",
+                    "attn.proj.bias", "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight",
+                    "mlp.fc2.bias"]
+_VIT_TOP_ORDER = ["cls_token", "pos_embed", "patch_embed.proj.weight", "patch_embed.proj.bias"]
+
+
 def reference_param_order(names) -> List[str]:
     """The trainable parameters in the order `model.named_parameters()` yields them in the REFERENCE -- the order
     `RunnerBase.optimizer` builds its two param groups in (runner_base.py:110-119) and therefore the indices of
@@ -213,12 +221,22 @@ def reference_param_order(names) -> List[str]:
     registration order: `query_tokens` (the model's own parameter, trainable with freeze_qformer: False) first, then
     Myriad.__init__ registers expert_adaptor, VETokenizer (direct parameter `base_prompts` before
     `meta_net.*`), VEInstructor, Qformer, llama_model (peft: per layer q_proj.lora_A, q_proj.lora_B, v_proj.lora_A,
-    v_proj.lora_B), llama_proj (myriad.py:117-125, 148, 186-207)."""
+    v_proj.lora_B), llama_proj (myriad.py:117-125, 148, 186-207).  With freeze_vit: False, visual_encoder and ln_vision
+    (registered first, myriad.py:108) come right after `query_tokens`: the ViT's own cls_token and pos_embed, patch_embed, then
+    the blocks (_VIT_BLOCK_ORDER)."""
     import re
 
     def key(n: str):
         if n == "query_tokens":                           # a direct parameter of the model: before every child's
             return (-1, 0, 0, 0)
+        if n.startswith("visual_encoder."):               # the first child module registered (myriad.py:108)
+            rest = n[len("visual_encoder."):]
+            m = re.search(r"^blocks\.(\d+)\.(.+)$", rest)
+            if m:
+                return (-0.6, int(m.group(1)), _VIT_BLOCK_ORDER.index(m.group(2)), 0)
+            return (-0.6, -1, _VIT_TOP_ORDER.index(rest), 0)
+        if n.startswith("ln_vision."):
+            return (-0.5, 0 if n.endswith("weight") else 1, 0, 0)
         if n.startswith("Qformer."):                      # registered after VEInstructor, before llama_model / llama_proj
             if n.startswith("Qformer.bert.embeddings."):
                 return (2.5, -1, 0 if n.endswith("weight") else 1, 0)

@@ -26,6 +26,26 @@ from . import ops
 BF16, F32 = torch.bfloat16, torch.float32
 
 
+def vit_param_shapes(D: int, C: int, P: int, n_tok: int, hidden: List[int], prefix: str = "visual_encoder.") -> Dict[str, tuple]:
+    """Reference names -> shapes of an EVA ViT's parameters (hidden: the MLP width of each block), in the order the flat
+    parameter buffer keeps them: q_bias and v_bias of a block adjacent, every block laid out alike."""
+    pre = prefix
+    out = {pre + "cls_token": (1, 1, D), pre + "pos_embed": (1, n_tok, D),
+           pre + "patch_embed.proj.weight": (D, C, P, P), pre + "patch_embed.proj.bias": (D,)}
+    for i, Hd in enumerate(hidden):
+        b = pre + f"blocks.{i}."
+        out.update({b + "norm1.weight": (D,), b + "norm1.bias": (D,), b + "attn.q_bias": (D,), b + "attn.v_bias": (D,),
+                    b + "attn.qkv.weight": (3 * D, D), b + "attn.proj.weight": (D, D), b + "attn.proj.bias": (D,),
+                    b + "norm2.weight": (D,), b + "norm2.bias": (D,), b + "mlp.fc1.weight": (Hd, D),
+                    b + "mlp.fc1.bias": (Hd,), b + "mlp.fc2.weight": (D, Hd), b + "mlp.fc2.bias": (D,)})
+    return out
+
+
+def vit_param_specs(shapes: Dict[str, tuple]):
+    """ParamStore specs (name, internal shape, reference shape): the ViT's masters keep the reference's own layout."""
+    return [(n, tuple(shp), tuple(shp)) for n, shp in shapes.items()]
+
+
 class EvaViTHIP:
     def __init__(self, sd: Dict[str, torch.Tensor], n_heads: int, device, eps: float = 1e-6,
                  prefix: str = "visual_encoder."):
@@ -77,6 +97,7 @@ class EvaViTHIP:
             i += 1
         self._T: Optional[List[dict]] = None       # transposed bf16 weights for the dgrad GEMMs (built by the first backward)
         self._ctx = None
+        self.trainable = False
 
     @torch.no_grad()
     def forward(self, image: torch.Tensor, rel_pos_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -192,6 +213,83 @@ class EvaViTHIP:
             self._refresh_T()
         return done
 
+    # ------------------------------------------------------------------ trainable ViT (freeze_vit: False)
+    def param_specs(self):
+        """ParamStore specs (name, internal shape, reference shape) of the trainable ViT: the reference's names and shapes
+        (grad_shapes()), held in the reference's own layout."""
+        return vit_param_specs(self.grad_shapes())
+
+    @torch.no_grad()
+    def bind_trainable(self, store, need_backward: bool = True) -> None:
+        """The ViT's parameters are `store`'s fp32 masters from now on (a ParamStore holding param_specs()).
+        The bf16 weight matrices -- wqkv, wproj, w1, w2, patch_w, with their padding -- keep their storage and their transposed
+        copies for the dgrad GEMMs exist from here on; refresh() rewrites both from the masters in one launch
+        (ops.RefreshTable).  Norm weights, biases, cls_token and pos_embed are read in place (fp32 views of the flat buffer;
+        pos_patches is rows 1.. of the pos_embed master); what is assembled from two tensors -- bqkv = q_bias | 0 | v_bias of
+        every block in one [blocks, 3, D] buffer, cls_row = cls_token + pos_embed[0] -- and a zero-padded fc1 bias are rewritten
+        by refresh() with the copy kernels.  grad_views maps every parameter to its gradient view for backward(grads=...)."""
+        pre, D, P = self.prefix, self.D, store.p
+        self._store = store
+        self.grad_views = {n: store.g[n] for n in self.grad_shapes()}
+        self.cls_f32 = P[pre + "cls_token"].view(1, D)
+        self.pos_f32 = P[pre + "pos_embed"].view(-1, D)
+        if self.pos_patches is not None:
+            self.pos_patches = self.pos_f32[1:]
+        self.patch_b = P[pre + "patch_embed.proj.bias"]
+        K = self.C * self.P * self.P
+        entries = [(P[pre + "patch_embed.proj.weight"].view(D, K), self.patch_w, None)]
+        if need_backward and self._T is None:
+            # zeros: the rows / columns of a padded hidden width are never written and must read as zero
+            self._T = [{k: torch.zeros((blk[k].shape[1], blk[k].shape[0]), dtype=BF16, device=self.dev)
+                        for k in ("wqkv", "wproj", "w1", "w2")} for blk in self.blocks]
+        nb = len(self.blocks)
+        self._bqkv_all = torch.zeros((max(nb, 1), 3, D), dtype=F32, device=self.dev)
+        self._b1_padded = []
+        q_off = []
+        for i, blk in enumerate(self.blocks):
+            b = pre + f"blocks.{i}."
+            for key, name in (("n1w", "norm1.weight"), ("n1b", "norm1.bias"), ("bproj", "attn.proj.bias"),
+                              ("n2w", "norm2.weight"), ("n2b", "norm2.bias"), ("b2", "mlp.fc2.bias")):
+                blk[key] = P[b + name]
+            if blk["Hd"] == blk["w1"].shape[0]:
+                blk["b1"] = P[b + "mlp.fc1.bias"]
+            else:
+                # the master's slot in the flat buffer is rounded up to four elements and its tail is zero for good (no
+                # gradient, no weight decay on a bias): copying the whole slot keeps the copy kernel's 16-byte granule and
+                # writes zeros into the working bias's zero padding
+                o, n4 = store.offsets[b + "mlp.fc1.bias"][0], ops.round_up(blk["Hd"], 4)
+                self._b1_padded.append((store.flat_p[o:o + n4].view(1, n4), blk["b1"][:n4].view(1, n4)))
+            blk["bqkv"] = self._bqkv_all[i].view(3 * D)
+            oq, ov = store.offsets[b + "attn.q_bias"][0], store.offsets[b + "attn.v_bias"][0]
+            if ov != oq + D:
+                raise RuntimeError(f"{b}attn.q_bias / v_bias: not adjacent in the flat buffer")
+            q_off.append(oq)
+            for key, name in (("wqkv", "attn.qkv.weight"), ("wproj", "attn.proj.weight"), ("w1", "mlp.fc1.weight"),
+                              ("w2", "mlp.fc2.weight")):
+                entries.append((P[b + name], blk[key], self._T[i][key] if self._T is not None else None))
+        step = (q_off[1] - q_off[0]) if nb > 1 else 2 * D
+        if any(q_off[i + 1] - q_off[i] != step for i in range(nb - 1)):
+            raise RuntimeError("the blocks' q_bias / v_bias are not evenly spaced in the flat buffer")
+        # [blocks, 2, D]: q_bias, v_bias of every block, read where they lie in the flat buffer
+        self._qv_src = torch.as_strided(store.flat_p, (nb, 2, D), (step, D, 1), q_off[0]) if nb else None
+        self._table = ops.RefreshTable(entries, self.dev)
+        self.trainable = True
+        self.refresh()
+
+    @torch.no_grad()
+    def refresh(self) -> None:
+        """Rewrite everything the forward / backward read that is not the masters themselves, in place, on the current stream:
+        all bf16 matrices and their transposed copies (one launch), bqkv of all blocks (one), cls_row (two)."""
+        D = self.D
+        self._table.run()
+        if self._qv_src is not None:
+            ops.copy3d(self._qv_src, self._bqkv_all[:len(self.blocks), 0::2])
+        row = self.cls_row.view(1, D)
+        ops.copy2d(self.cls_f32, row)
+        ops.copy2d(self.pos_f32[:1], row, accumulate=True)
+        for src, dst in self._b1_padded:
+            ops.copy2d(src, dst)
+
     def _refresh_T(self) -> None:
         """The transposed bf16 copies the dgrad GEMMs read, rewritten in place from the working weights."""
         for blk, T in zip(self.blocks, self._T):
@@ -236,16 +334,7 @@ class EvaViTHIP:
 
     def grad_shapes(self) -> Dict[str, tuple]:
         """Reference names and shapes of the ViT's parameters (the keys backward() fills)."""
-        D, C, P, pre = self.D, self.C, self.P, self.prefix
-        out = {pre + "cls_token": (1, 1, D), pre + "pos_embed": (1, self.pos_f32.shape[0], D),
-               pre + "patch_embed.proj.weight": (D, C, P, P), pre + "patch_embed.proj.bias": (D,)}
-        for i, blk in enumerate(self.blocks):
-            b, Hd = pre + f"blocks.{i}.", blk["Hd"]
-            out.update({b + "norm1.weight": (D,), b + "norm1.bias": (D,), b + "attn.q_bias": (D,), b + "attn.v_bias": (D,),
-                        b + "attn.qkv.weight": (3 * D, D), b + "attn.proj.weight": (D, D), b + "attn.proj.bias": (D,),
-                        b + "norm2.weight": (D,), b + "norm2.bias": (D,), b + "mlp.fc1.weight": (Hd, D),
-                        b + "mlp.fc1.bias": (Hd,), b + "mlp.fc2.weight": (D, Hd), b + "mlp.fc2.bias": (D,)})
-        return out
+        return vit_param_shapes(self.D, self.C, self.P, self.pos_f32.shape[0], [blk["Hd"] for blk in self.blocks], self.prefix)
 
     @torch.no_grad()
     def backward(self, dout: torch.Tensor, grads: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:

@@ -39,13 +39,19 @@ def uses_weight_decay(name: str, ndim: int) -> bool:
 
 
 MODULES = ("expert_adaptor", "VETokenizer", "VEInstructor", "llama_proj", "lora", "Qformer")
+# freeze_vit: False adds two modules BEHIND those (myriad.py:134-144 trains visual_encoder.* and ln_vision.*): the flat-buffer
+# layout of every earlier recipe stays as it was.  MODULE_ORDER is the order the ParamStore lays modules out in.  The two tuples
+# are kept apart on purpose: MODULES is the set a model without a trainable ViT can hold, and
+# tests/test_qformer_train_cpu.py pins its last entry ("Qformer"); do not merge them.
+VIT_MODULES = ("visual_encoder", "ln_vision")
+MODULE_ORDER = MODULES + VIT_MODULES
 
 
 def module_of(name: str) -> str:
     """The top-level reference module a trainable parameter belongs to (the unit torch's AdamW skips when unused).
     `query_tokens` (a direct parameter of the reference model) is counted with the Q-Former: both are trainable exactly
     when freeze_qformer is False (myriad.py:159-165) and both are used on every step."""
-    for m in MODULES[:4]:
+    for m in MODULES[:4] + VIT_MODULES:
         if name.startswith(m + "."):
             return m
     if name.startswith("Qformer.") or name == "query_tokens":
@@ -78,8 +84,8 @@ class ParamStore:
 
     def __init__(self, specs: List[Tuple[str, Tuple[int, ...], Tuple[int, ...]]], device):
         self.dev = torch.device(device)
-        order = {m: i for i, m in enumerate(MODULES)}
-        self.modules = [m for m in MODULES if any(module_of(s[0]) == m for s in specs)]
+        order = {m: i for i, m in enumerate(MODULE_ORDER)}
+        self.modules = [m for m in MODULE_ORDER if any(module_of(s[0]) == m for s in specs)]
         midx = {m: i for i, m in enumerate(self.modules)}
         key = lambda s: order[module_of(s[0])]                    # stable: keeps each module's own order
         wd = sorted([s for s in specs if uses_weight_decay(s[0], len(s[2]))], key=key)
@@ -255,6 +261,11 @@ class _LossBridge(torch.autograd.Function):
 
 
 class MyriadHIP(nn.Module):
+    """The model.  `self.vit` is the HIP vision encoder (EvaViTHIP) in every configuration: use it to reach the encoder's blocks,
+    forward or backward.  `self.visual_encoder` is the same object only while the ViT is frozen; with freeze_vit: False that name
+    belongs to the nn.Module node that carries the `visual_encoder.*` parameters, so that named_parameters() / an external
+    optimiser see the reference's names (as `Qformer`, `ln_vision`, `expert_adaptor`, ... are parameter nodes), and it has no
+    `blocks` list or `forward` of the encoder."""
     arch = "myriad"
 
     def __init__(self, weights, cfg: Optional[dict] = None, device="cuda:0"):
@@ -281,10 +292,19 @@ class MyriadHIP(nn.Module):
             raise ValueError(f"qformer_dropout {self.qformer_dropout}: must be in [0, 1)")
         self.qformer_seed = int(cfg.get("qformer_dropout_seed", torch.initial_seed())) & ((1 << 31) - 1)
         self._qf_step = 0                                      # training forwards so far: one mask set per forward
+        # freeze_vit: False (myriad.py:134-144): visual_encoder.* and ln_vision.* are trainable -- fp32 masters in the flat
+        # buffer, bf16 working copies (the reference's fp32 ViT under autocast: vit_precision "fp32"); use_grad_checkpoint keeps
+        # only each block's input and recomputes the block in the backward (eva_vit.py:176-180)
+        self.train_vit = cfg.get("freeze_vit", True) is False
+        self.vit_checkpoint = self.train_vit and bool(cfg.get("use_grad_checkpoint", False))
         ops.ensure_workspace(self._dev)                        # scratch for the automatic split-K GEMM path
-        self.visual_encoder = EvaViTHIP(weights, cfg.get("vit_heads", 16), self._dev)
+        # the HIP encoder.  Frozen, it is also `visual_encoder`; with freeze_vit: False that name is the nn.Module node that
+        # carries the visual_encoder.* parameters (named_parameters() yields the reference's names)
+        self.vit = EvaViTHIP(weights, cfg.get("vit_heads", 16), self._dev)
+        if not self.train_vit:
+            self.visual_encoder = self.vit
         self.qformer = QFormerHIP(weights, cfg.get("qf_heads", 12), self._dev,
-                                  need_backward=need_bwd and (self.arch == "myriad" or self.train_qformer))
+                                  need_backward=need_bwd and (self.arch == "myriad" or self.train_qformer or self.train_vit))
         self.llama = LlamaHIP(weights, cfg.get("llm_heads", 32), self._dev, eps=float(cfg.get("llm_eps", 1e-6)),
                               need_backward=need_bwd)
         # copies: _load_vision_keys writes them in place
@@ -294,7 +314,7 @@ class MyriadHIP(nn.Module):
         self.proj_w = weights["llama_proj.weight"].to(self._dev, BF16).contiguous()
         self.proj_b = weights["llama_proj.bias"].to(self._dev, F32).contiguous()
         self.proj_wT = self.proj_w.t().contiguous()
-        self.Dv, self.Dq, self.Dl = self.visual_encoder.D, self.qformer.D, self.llama.D
+        self.Dv, self.Dq, self.Dl = self.vit.D, self.qformer.D, self.llama.D
         self.nq0 = self.query_tokens_f32.shape[1]
         # ---- trainables
         specs = []
@@ -309,6 +329,9 @@ class MyriadHIP(nn.Module):
             specs.append(("llama_proj.bias", (self.Dl,), (self.Dl,)))
         if self.train_qformer:
             specs += qformer_param_specs(weights)
+        if self.train_vit:
+            specs += self.vit.param_specs()
+            specs += [("ln_vision.weight", (self.Dv,), (self.Dv,)), ("ln_vision.bias", (self.Dv,), (self.Dv,))]
         # PEFT LoRA on q_proj/v_proj (myriad.py:170-180): off in the shipped recipe, on with cfg use_lora
         self.use_lora = bool(cfg.get("use_lora", False))
         lora_init = {}
@@ -346,7 +369,10 @@ class MyriadHIP(nn.Module):
             self.llama.attach_lora(self.lora)
         if self.train_qformer:
             self.query_tokens_f32 = self.store.p["query_tokens"]       # fp32 master, read in place
-            self.qformer.bind_trainable(self.store, need_denc=self.arch == "myriad")
+            self.qformer.bind_trainable(self.store, need_denc=self.arch == "myriad" or self.train_vit)
+        if self.train_vit:
+            self.ln_w, self.ln_b = self.store.p["ln_vision.weight"], self.store.p["ln_vision.bias"]   # fp32 masters, in place
+            self.vit.bind_trainable(self.store, need_backward=need_bwd)
         self._pending_update = None
         self._vit_stream, self._vit_prefetched = None, None
         self._vit_graphs, self._vit_seen, self._vit_rest = {}, {}, None
@@ -420,7 +446,10 @@ class MyriadHIP(nn.Module):
                 self.store.p[name].copy_(from_reference_layout(sd[name].to(self._dev, F32), ishape))
             else:
                 missing.append(name)
-        self._load_vision_keys(sd)
+        if self.train_vit:
+            self.vit.refresh()                 # the masters took the visual_encoder.* / ln_vision.* keys above
+        else:
+            self._load_vision_keys(sd)
         if strict and missing:
             raise KeyError(missing)
         return missing
@@ -436,7 +465,7 @@ class MyriadHIP(nn.Module):
         self._vit_rest, self._vit_prefetched = None, None  # a pending or finished look-ahead of the old weights: dropped
         if self._vit_stream is not None:
             main.wait_stream(self._vit_stream)            # nothing on the side stream still reads the weights being replaced
-        self.visual_encoder.load_weights(sd)
+        self.vit.load_weights(sd)
         for key, dst in (("ln_vision.weight", self.ln_w), ("ln_vision.bias", self.ln_b)):
             if key in sd:
                 dst.copy_(sd[key].to(self._dev, F32).reshape(dst.shape))
@@ -453,16 +482,25 @@ class MyriadHIP(nn.Module):
         get = cfg.get if hasattr(cfg, "get") else (lambda k, d=None: getattr(cfg, k, d))
         if get("low_resource", False):
             raise NotImplementedError("low_resource (8-bit LLaMA + ViT on the CPU, myriad.py:186-192) is not part of the MI355X path")
-        for k in ("freeze_vit", "freeze_llama"):
-            if get(k, True) is False:
-                raise NotImplementedError(f"{k}: False -- the HIP path keeps ViT and LLaMA frozen (dgrad only), as every "
-                                          "shipped recipe does (train_configs/*.yaml)")
-        if get("drop_path_rate", 0) or get("use_grad_checkpoint", False):
-            raise NotImplementedError("drop_path_rate / use_grad_checkpoint only matter for an unfrozen ViT")
+        if get("freeze_llama", True) is False:
+            raise NotImplementedError("freeze_llama: False -- the HIP path keeps LLaMA frozen (dgrad only), as every "
+                                      "shipped recipe does (train_configs/*.yaml)")
+        train_vit = get("freeze_vit", True) is False
+        if train_vit and get("vit_precision", "fp16") != "fp32":
+            # the HIP path trains fp32 masters with bf16 working copies: the reference's fp32 ViT under autocast.  With
+            # vit_precision fp16 (the default) the reference trains fp16 parameters directly (eva_vit.py:397-412,439-441),
+            # which GradScaler.unscale_ refuses under amp: nothing to mirror
+            raise NotImplementedError("freeze_vit: False needs vit_precision: fp32 (fp32 masters, bf16 working copies); "
+                                      f"vit_precision: {get('vit_precision', 'fp16')} (fp16 masters) is not implemented")
+        if get("drop_path_rate", 0):
+            raise NotImplementedError("drop_path_rate > 0 (stochastic depth in the ViT's training forward) is not implemented"
+                                      if train_vit else "drop_path_rate only matters for an unfrozen ViT")
+        if get("use_grad_checkpoint", False) and not train_vit:
+            raise NotImplementedError("use_grad_checkpoint only matters for an unfrozen ViT (freeze_vit: False)")
         keys = ("max_txt_len", "end_sym", "k_shot", "round_index", "fixed_stage", "fixed_taskstage", "tokenizer",
                 "vit_heads", "qf_heads", "llm_heads", "need_backward", "bos_token_id", "pad_token_id", "use_lora",
                 "lora_r", "lora_alpha", "lora_dropout", "lora_seed", "num_query_token", "llm_eps", "freeze_qformer",
-                "qformer_dropout", "qformer_dropout_seed")
+                "qformer_dropout", "qformer_dropout_seed", "freeze_vit", "use_grad_checkpoint")
         sub = {k: get(k) for k in keys if get(k) is not None}
         if get("max_txt_len") is None:
             sub["max_txt_len"] = 32                       # from_config defaults (myriad.py:483-484)
@@ -524,7 +562,16 @@ class MyriadHIP(nn.Module):
     def encode_img(self, image, maps, stage, save=True, vit_out=None):
         """`Myriad.encode_img` (myriad.py:241-272).  Returns img tokens [B, n_img, Dl] f32."""
         B = image.shape[0]
-        x = vit_out if vit_out is not None else self.visual_encoder.forward(image)   # [B,257,Dv] f32, frozen
+        if vit_out is not None:
+            x = vit_out
+        elif self.train_vit:
+            # the working copies follow the fp32 masters, whoever changed them (fused AdamW, a torch optimiser through the .grad
+            # views, load_state_dict): rewritten in place before every use
+            self.vit.refresh()
+            x = (self.vit.forward_train(image, checkpoint=self.vit_checkpoint) if save
+                 else self.vit.forward(image))
+        else:
+            x = self.vit.forward(image)                                    # [B,257,Dv] f32, frozen
         N = x.shape[1]
         x2 = x.view(B * N, self.Dv)
         y = self.adaptor.forward(x2, save) if self.arch == "myriad" else x2
@@ -555,7 +602,7 @@ class MyriadHIP(nn.Module):
         drop = self.qformer_dropout if (save and self.training and self.train_qformer) else 0.0
         if drop > 0:
             self._qf_step += 1
-        qo = self.qformer.forward(q, enc_b.view(B, N, self.Dv), save and (self.arch == "myriad" or self.train_qformer),
+        qo = self.qformer.forward(q, enc_b.view(B, N, self.Dv), save and (self.arch == "myriad" or self.train_qformer or self.train_vit),
                                   dropout=drop, seed=(self.qformer_seed << 32) + self._qf_step)
         qo_b = ops.to_bf16(qo.view(B * nq, self.Dq))
         if self.arch == "myriad":
@@ -727,6 +774,8 @@ class MyriadHIP(nn.Module):
             used.add("llama_proj")
         if self.train_qformer:
             used.add("Qformer")
+        if self.train_vit:
+            used.update(("visual_encoder", "ln_vision"))
         self.store.mark_used(used)
         # modules whose parameters receive a gradient in this accumulation window (the bridge path hands torch's optimiser
         # `.grad is None` for the others, exactly what autograd leaves for a module the forward never touched)
@@ -745,11 +794,17 @@ class MyriadHIP(nn.Module):
             ops.gemm_auto_f32(ops.transpose_to_bf16(dimg_b, 64), ops.transpose_to_bf16(c["qo_b"], 64),
                               self.store.g["llama_proj.weight"])
             self.store.g["llama_proj.bias"].copy_(ops.colsum(dimg.view(B * nq, self.Dl)))
-            if self.train_qformer:                        # nothing consumes d(image tokens) here: the Q-Former's gradients only
+            # dqo feeds the Q-Former's weight gradients (trainable Q-Former) and, through it, d(image tokens) = denc, which only
+            # a trainable ViT consumes; with both frozen nothing below llama_proj needs a gradient
+            if self.train_qformer or self.train_vit:
                 pwT = ops.transpose_to_bf16(ops.to_bf16(self.store.p["llama_proj.weight"]), 64)
                 dqo = ops.gemm(dimg_b, pwT, out_dtype=F32).view(B, nq, self.Dq)
-                dq, _ = self.qformer.backward(dqo, wgrads=True, want_denc=False)
-                self._query_tokens_grad(dq)
+                dq, denc = self.qformer.backward(dqo, wgrads=self.train_qformer, want_denc=self.train_vit)
+                if self.train_qformer:
+                    self._query_tokens_grad(dq)
+                if self.train_vit:
+                    dy = self._ln_vision_backward(denc, c)
+                    self.vit.backward(dy.view(B, c["N"], self.Dv), grads=self.vit.grad_views)
             if self.llama.lora is not None:
                 self.llama.lora.join_wgrads()
             self._finish_backward()
@@ -802,8 +857,11 @@ class MyriadHIP(nn.Module):
                     ins_ev.record()
             else:
                 self.ve_ins.backward(dins)
-        dy, _ = ops.layernorm_bwd(denc.view(B * c["N"], self.Dv), c["y"], self.ln_w, 1e-5)
-        self.adaptor.backward(dy)
+        dy = self._ln_vision_backward(denc, c)
+        dx = self.adaptor.backward(dy, need_dx=self.train_vit)
+        if self.train_vit:
+            # the ViT's backward: on the main stream, last -- its gradients complete the buffer
+            self.vit.backward(dx.view(B, c["N"], self.Dv), grads=self.vit.grad_views)
         if self.llama.lora is not None:
             self.llama.lora.join_wgrads()                 # the side-stream LoRA weight gradients land before anyone reads flat_g
         if leaf_ev is not None:
@@ -812,6 +870,13 @@ class MyriadHIP(nn.Module):
             torch.cuda.current_stream().wait_event(ins_ev)
         del leaf_keep, ins_keep                           # freed only now: later main-stream work is ordered behind the events
         self._finish_backward()
+
+    def _ln_vision_backward(self, denc: torch.Tensor, c) -> torch.Tensor:
+        """ln_vision's backward: d(its input) [B*N, Dv] f32; with a trainable ViT also ln_vision.weight / .bias gradients."""
+        d2 = denc.view(c["B"] * c["N"], self.Dv)
+        if self.train_vit:
+            ops.layernorm_param_grads(d2, c["y"], 1e-5, self.store.g["ln_vision.weight"], self.store.g["ln_vision.bias"])
+        return ops.layernorm_bwd(d2, c["y"], self.ln_w, 1e-5)[0]
 
     def _query_tokens_grad(self, dq: torch.Tensor) -> None:
         """d query_tokens = the batch sum of the Q-Former input gradient over its first nq0 (query-token) rows."""
@@ -880,7 +945,12 @@ class MyriadHIP(nn.Module):
         _prefetch_vit_rest(), which backward() calls once the LLaMA backward is enqueued.
         From the second batch of a given size on, both pieces are replayed from hipGraphs captured on that stream (fixed
         shapes, frozen weights, no host-side arguments): enqueueing ~290 launches costs the launch thread ~0.2 ms instead of
-        ~2.8 ms during which the main stream had nothing to run (MYRIAD_VIT_GRAPH=0 disables)."""
+        ~2.8 ms during which the main stream had nothing to run (MYRIAD_VIT_GRAPH=0 disables).
+
+        With a trainable ViT (freeze_vit: False) there is no look-ahead -- a forward of batch t+1 issued during step t would
+        read weights step t is about to change -- and this is a no-op."""
+        if self.train_vit:
+            return
         if self._vit_stream is None:
             self._vit_stream = self._side_stream("vit")
         self._prefetch_vit_rest()                        # a look-ahead that was never consumed / finished: finish it first
@@ -891,7 +961,7 @@ class MyriadHIP(nn.Module):
         if graph is None and self._vit_graph_on and self._vit_seen.get(key, 0) >= 1 and image.dtype == F32:
             graph = self._capture_vit(image)
         self._vit_seen[key] = self._vit_seen.get(key, 0) + 1
-        nb = len(self.visual_encoder.blocks)
+        nb = len(self.vit.blocks)
         split = min(max(self._vit_split, 0), nb)
         self._vit_stream.wait_stream(main)               # inputs uploaded / buffers freed on the main stream so far
         with torch.cuda.stream(self._vit_stream), torch.no_grad():
@@ -900,7 +970,7 @@ class MyriadHIP(nn.Module):
                 graph["a"].replay()
                 state = None
             else:
-                state = self.visual_encoder.run_blocks(self.visual_encoder.embed(image), 0, split)
+                state = self.vit.run_blocks(self.vit.embed(image), 0, split)
         self._vit_rest = (samples, graph, state, split)
 
     def _prefetch_vit_rest(self) -> None:
@@ -916,7 +986,7 @@ class MyriadHIP(nn.Module):
                     graph["b"].replay()
                 out = graph["out"].clone()               # the next replay overwrites it while this step's backward reads `out`
             else:
-                ve = self.visual_encoder
+                ve = self.vit
                 out = ve.finish(ve.run_blocks(state, split, len(ve.blocks)))
             ev = torch.cuda.Event()
             ev.record()
@@ -925,6 +995,8 @@ class MyriadHIP(nn.Module):
     def prepare_vit_graph(self, samples) -> None:
         """Capture the look-ahead graphs for this batch's image shape now (one eager pass + the capture: ~0.1 s), so that no
         later train_step pays for it.  Without this call the capture happens at the second look-ahead of a shape."""
+        if self.train_vit:
+            return                                         # no look-ahead, no captured forward (prefetch_vit)
         image = self._image_of(samples)
         key = tuple(image.shape)
         if not self._vit_graph_on or key in self._vit_graphs or image.dtype != F32:
@@ -933,7 +1005,7 @@ class MyriadHIP(nn.Module):
             self._vit_stream = self._side_stream("vit")
         self._vit_stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self._vit_stream), torch.no_grad():
-            self.visual_encoder.forward(image)            # first-call set-up of every kernel happens outside the capture
+            self.vit.forward(image)            # first-call set-up of every kernel happens outside the capture
         self._vit_seen[key] = max(1, self._vit_seen.get(key, 0))
         self._capture_vit(image)
 
@@ -942,7 +1014,7 @@ class MyriadHIP(nn.Module):
         split-K scratch the captured launches keep using on replay).  Called after one eager pass at the shape, so no kernel
         does first-call set-up inside the capture.  The pieces share one memory pool: piece b reads piece a's state."""
         torch.cuda.synchronize()
-        ve = self.visual_encoder
+        ve = self.vit
         split = min(max(self._vit_split, 0), len(ve.blocks))
         static_in = torch.empty_like(image).contiguous()
         static_in.copy_(image)
@@ -996,10 +1068,12 @@ class MyriadHIP(nn.Module):
                 self.prefetch_vit(next_samples)         # runs beside everything below
             if self._pending_update is not None and vit_out is not None:
                 self.finish_update()
+            elif self._pending_update is not None and self.train_vit:
+                self.finish_update()                    # this step's ViT forward reads the weights that update writes
             elif self._pending_update is not None:
                 # The previous step's gradient all-reduce is still in flight on the side stream: run this step's
                 # frozen ViT forward (independent of the update) under it, then apply the delayed AdamW.
-                vit_out = self.visual_encoder.forward(self._image_of(samples))
+                vit_out = self.vit.forward(self._image_of(samples))
                 self.finish_update()
             if (self._accum_count == 0 and self._leaf_aside and self._dev.type == "cuda"
                     and os.environ.get("MYRIAD_EARLY_ZERO", "1") != "0"):

@@ -31,13 +31,15 @@ def ve_param_specs(prefix: str, head_out: int, head_k: int) -> List[Tuple[str, T
 
 
 def from_reference_layout(t: torch.Tensor, internal_shape) -> torch.Tensor:
-    if t.dim() == 4:   # [Cout,Cin,kh,kw] -> [Cout, (ky,kx,ci)]
+    """A 4-D internal shape is the reference's own layout (the ViT's patch embedding is held as [D, C, P, P]: its GEMM reads
+    (c, iy, ix) order, which is that tensor flattened)."""
+    if t.dim() == 4 and len(internal_shape) != 4:   # [Cout,Cin,kh,kw] -> [Cout, (ky,kx,ci)]
         return t.permute(0, 2, 3, 1).reshape(internal_shape).contiguous()
     return t.reshape(internal_shape).contiguous()
 
 
 def to_reference_layout(t: torch.Tensor, ref_shape) -> torch.Tensor:
-    if len(ref_shape) == 4:
+    if len(ref_shape) == 4 and t.dim() != 4:
         co, ci, kh, kw = ref_shape
         return t.reshape(co, kh, kw, ci).permute(0, 3, 1, 2).contiguous()
     return t.reshape(ref_shape).contiguous()
@@ -162,7 +164,9 @@ class LoraAdaptor:
             self._saved = (x2d, t)
         return y
 
-    def backward(self, dy2d: torch.Tensor):
+    def backward(self, dy2d: torch.Tensor, need_dx: bool = False):
+        """Writes the two weight gradients; need_dx: also returns d x (a trainable ViT sits below the adaptor)."""
         x2d, t = self._saved
-        ops.lowrank_bwd(dy2d, x2d, t, self.A, self.Bm, self.gA, self.gB, need_dx=False)
+        dx = ops.lowrank_bwd(dy2d, x2d, t, self.A, self.Bm, self.gA, self.gB, need_dx=need_dx)
         self._saved = None
+        return dx

@@ -866,6 +866,51 @@ def transpose_to_bf16(x2d: torch.Tensor, pad_to: int = 64, out=None):
     return out
 
 
+class RefreshTable:
+    """The fp32 master -> bf16 working copy (+ transposed copy) refresh of a list of matrices as ONE launch
+    (mh_refresh_bf16_pair).  entries = [(src f32 [R, C] contiguous, dst bf16 [>= R, >= C] or None, dst_t bf16 [>= C, >= R] or None)];
+    only the [R, C] part of a wider destination is written.  The descriptor table is built and uploaded once, here; run()
+    rewrites the copies from whatever the masters hold now, on the current stream.  The tensors must outlive the table."""
+
+    def __init__(self, entries, device):
+        L = _L()
+        nb = int(L.mh_refresh_bf16_pair_desc_bytes())
+        self.n = len(entries)
+        self.tiles = 0
+        self._keep = list(entries)
+        self.weights = 0
+        if not self.n:
+            self.table = None
+            return
+        host = torch.zeros((self.n * nb,), dtype=torch.uint8)
+        for i, (src, dst, dst_t) in enumerate(entries):
+            if src.dtype != F32 or src.dim() != 2 or not src.is_contiguous():
+                raise _lib.MyriadHipError(f"RefreshTable entry {i}: the source must be a contiguous f32 matrix")
+            R, C = src.shape
+            for t, rows, cols, name in ((dst, R, C, "dst"), (dst_t, C, R, "dst_t")):
+                if t is not None and (t.dtype != BF16 or t.dim() != 2 or t.stride(1) != 1 or t.shape[0] < rows
+                                      or t.shape[1] < cols or t.device != src.device):
+                    raise _lib.MyriadHipError(f"RefreshTable entry {i}: {name} must be bf16 [>= {rows}, >= {cols}] with unit "
+                                              "inner stride, on the source's device")
+            nxt = int(L.mh_refresh_bf16_pair_pack(host.data_ptr(), i, self.tiles, _p(src), _p(dst),
+                                                  0 if dst is None else dst.stride(0), _p(dst_t),
+                                                  0 if dst_t is None else dst_t.stride(0), R, C))
+            if nxt < 0:
+                _lib.check(nxt, f"mh_refresh_bf16_pair_pack (entry {i})")
+            self.tiles = nxt
+            self.weights += R * C
+        self.table = host.to(device)
+
+    def run(self) -> None:
+        if self.n:
+            _lib.check(_L().mh_refresh_bf16_pair(_p(self.table), self.n, self.tiles, _s()), "mh_refresh_bf16_pair")
+
+
+def refresh_bf16_pair(src: torch.Tensor, dst: Optional[torch.Tensor] = None, dst_t: Optional[torch.Tensor] = None) -> None:
+    """One matrix through mh_refresh_bf16_pair (tests, one-off uses: the table is built and uploaded per call)."""
+    RefreshTable([(src, dst, dst_t)], src.device).run()
+
+
 def copy2d(src: torch.Tensor, dst: torch.Tensor, accumulate: bool = False):
     rows, cols = src.shape
     _lib.check(_L().mh_copy2d_f32(_p(src), src.stride(0), _p(dst), dst.stride(0), rows, cols, int(accumulate), _s()),
