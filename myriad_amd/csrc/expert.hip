@@ -109,12 +109,14 @@ __global__ __launch_bounds__(EX_NT) void rowmax_skip_kernel(const float* __restr
 __global__ void bilinear_ac_kernel(const float* __restrict__ in, float* __restrict__ out, int B, int h, int w_in, int H, int W,
                                    int one_minus) {
   const long total = (long)B * H * W;
-  const float sy = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f, sx = W > 1 ? (float)(w_in - 1) / (float)(W - 1) : 0.f;
+  // source position o (n_in - 1) / (n_out - 1) as one correctly rounded division of exact integers: o * fl(step) carries two
+  // roundings of a value up to n_in - 1, which a steep cell turns into the largest part of the output's error
+  const float dy = H > 1 ? (float)(H - 1) : 1.f, dx = W > 1 ? (float)(W - 1) : 1.f;
   for (long it = blockIdx.x * (long)blockDim.x + threadIdx.x; it < total; it += (long)gridDim.x * blockDim.x) {
     const int b = (int)(it / ((long)H * W));
     const int rem = (int)(it - (long)b * H * W);
     const int oy = rem / W, ox = rem - oy * W;
-    const float fy = oy * sy, fx = ox * sx;
+    const float fy = (float)(oy * (h - 1)) / dy, fx = (float)(ox * (w_in - 1)) / dx;
     int y0 = (int)fy, x0 = (int)fx;
     y0 = y0 < h - 1 ? y0 : (h > 1 ? h - 2 : 0);
     x0 = x0 < w_in - 1 ? x0 : (w_in > 1 ? w_in - 2 : 0);

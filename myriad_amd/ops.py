@@ -1152,10 +1152,13 @@ def beam_reorder_kv(cache_table: torch.Tensor, L: int, B: int, nb: int, T_cap: i
 # --------------------------------------------------------------------------- conv stack pieces
 def im2col(x_nhwc: torch.Tensor, kh: int, kw: int, pad: int, bias_col: bool = True):
     """[B*OH*OW, Kpad] bf16 patches, (ky, kx, c) order; with bias_col a column of ones follows the K patch columns (the bias
-    then rides the GEMM as one more weight column)."""
+    then rides the GEMM as one more weight column).  Without it K = kh*kw*C must be a multiple of 64: the kernel marks column K
+    of a padded row with 1.0, so a padded row always carries the ones column and is refused here."""
     B, H, W, C = x_nhwc.shape
     OH, OW = H + 2 * pad - kh + 1, W + 2 * pad - kw + 1
     Kpad = round_up(kh * kw * C + (1 if bias_col else 0), 64)
+    if not bias_col and Kpad != kh * kw * C:
+        raise _lib.MyriadHipError(f"im2col: bias_col=False needs kh*kw*C % 64 == 0, got {kh * kw * C}")
     col = torch.empty((B * OH * OW, Kpad), dtype=BF16, device=x_nhwc.device)
     _lib.check(_L().mh_im2col_nhwc(_p(x_nhwc), _p(col), B, H, W, C, kh, kw, pad, Kpad, _s()), "mh_im2col_nhwc")
     return col

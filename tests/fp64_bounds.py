@@ -77,6 +77,38 @@ Elementwise (elementwise.hip; bf16 in, fp32 arithmetic, one bf16 rounding out):
         (u32 |ref| then bf16) or the sum's (u32 |dy keep| + u32 |ref|).
     Data movement (copies, gathers, scatters, casts, transposes, patchify, decode records): no bound, torch.equal; accumulate
         forms u32 (|a| + |b|).
+Conv stack (conv.hip).  Data movement, compared by value with torch.equal (bit equality but for the sign of a zero):
+    im2col: an index gather in (ky, kx, c) order (im2col_ref; not F.unfold, whose columns are channel-major): column K is exactly
+        1.0 with the bias column, every other column >= K exactly 0, every out-of-image tap exactly 0.
+    conv_pack: bf16(W) rounded to nearest even, the bf16 bias at column K (if any), zeros after it.  conv_unpack_grad: a copy of
+        the columns < K and of column K.
+    relu_pool_fwd: bf16(max(0, max of the four)).  fmaxf(0.f, -0.f) may return either zero, so a window whose maximum is a
+        zero is compared by value (torch.equal does: -0 == 0).
+    relu_pool_bwd: bf16(dp) at the first maximum of the window in the order (0,0), (0,1), (1,0), (1,1) iff that maximum is > 0
+        (an argmax over a [.., 4] view, first index on ties; -0.0 == 0.0 is a tie and neither is > 0); zero at the other three
+        cells and in the pad columns.
+    col2im: the fp64 fold of the bf16 dcol.  The kernel adds up to kh kw exact bf16 values serially in fp32:
+        (kh kw) u32 sum_taps |dcol| per element (an element no tap reaches, or whose taps are all zero, is exactly 0).
+Map heads (expert.hip):
+    pair_logits: scale <p, t_j> / ||p||.  A lane sums 4 ceil(C/256) products serially, then the 64-lane butterfly (no wave
+        values to add: g_sum(4 ceil(C/256), 0)); the same sum gives ||p||^2 (all terms positive: relative, halved by the square
+        root), then sqrtf, one division and the product:
+        (scale / ||p||) g_sum sum_i |p_i t_i| + |ref| (g_sum / 2 + (2 C_FN + 2) u32).
+    bilinear_ac: the reference's source position is the exact rational oy (h-1) / (H-1) in fp64; a kernel's is oy fl(step) in
+        fp32 (zs_accumulate; bilinear_ac divides the exact integers once), a relative error of at most 2 u32 of a value <= h - 1.  The interpolant is continuous and piecewise linear, so a
+        position error d moves it by at most d times the slope |in[y1] - in[y0]| (interpolated along the other axis) of the cell
+        the position lies in or of the cell next to it -- the largest over the 3 x 3 neighbourhood of cells is taken, so an
+        (int)fy that lands in the neighbouring cell needs no exemption.  The lerp itself: 6 u32 on the sum of the four weighted
+        magnitudes (1 - w, the product, the inner sum, 1 - v, the product, the outer sum); one_minus: + u32 |1 - v|.
+    zs_accumulate, map: d = l1 - l0 is rounded (u32 |d|, interpolated with the same weights: one more u32 on the weighted
+        magnitudes), then the position and lerp errors above give e_d; through the sigmoid (slope s (1 - s) e^e_d <= 1/4) plus
+        the sigmoid's own relative error (_sigmoid_rel: the __expf allowance and three roundings); then acc + w s:
+        u32 (|acc| + |w s|).  mask: the same with e_d = u32 |d| (no interpolation).
+    rowmax_skip: the maximum over the kept columns is exact; acc + w m has two roundings: 2 u32 (|acc| + |w m|).  A row whose
+        kept maximum is -inf gives exactly -inf.
+    Pool routing in a chain (conv GEMM -> pool): a window whose fp64 runner-up lies within the GEMM bounds of the maximum, or
+        whose maximum lies within its bound of 0, may route either way (pool_decisions); the chain test gives such windows no
+        gradient and asserts they are at most 1 % of all windows.
 """
 from __future__ import annotations
 
@@ -705,3 +737,316 @@ def frame_of(buf, win_rows: slice, win_cols: slice):
 def assert_frame_untouched(buf, win_rows: slice, win_cols: slice, what=""):
     for i, f in enumerate(frame_of(buf, win_rows, win_cols)):
         assert_untouched(f, f"{what} frame part {i}")
+
+
+# ---------------------------------------------------------------------------------------------------------------- conv stack
+def conv_out_hw(H, W, kh, kw, pad):
+    return H + 2 * pad - kh + 1, W + 2 * pad - kw + 1
+
+
+def im2col_ref(x, kh, kw, pad, Kpad, bias_col):
+    """[B*OH*OW, Kpad] in x's dtype from x [B, H, W, C]: column (ky*kw + kx)*C + c of row (b, oy, ox) is x[b, oy+ky-pad, ox+kx-pad, c],
+    0 outside the image; column K is 1 with bias_col; every other column >= K is 0."""
+    B, H, W, C = x.shape
+    OH, OW = conv_out_hw(H, W, kh, kw, pad)
+    K = kh * kw * C
+    xp = torch.zeros((B, H + 2 * pad, W + 2 * pad, C), dtype=x.dtype, device=x.device)
+    xp[:, pad:pad + H, pad:pad + W] = x
+    col = torch.zeros((B, OH, OW, Kpad), dtype=x.dtype, device=x.device)
+    for ky in range(kh):
+        for kx in range(kw):
+            t = ky * kw + kx
+            col[..., t * C:(t + 1) * C] = xp[:, ky:ky + OH, kx:kx + OW]
+    if bias_col:
+        col[..., K] = 1.0
+    return col.view(B * OH * OW, Kpad)
+
+
+def col2im_fold(t, B, H, W, C, kh, kw, pad):
+    """The fp64 transpose of im2col_ref: [B, H, W, C] with out[b, y, x, c] = sum_taps t[(b, y+pad-ky, x+pad-kx), tap*C + c] (t [M, ld],
+    only its first kh*kw*C columns are read)."""
+    OH, OW = conv_out_hw(H, W, kh, kw, pad)
+    t = t.double().reshape(B, OH, OW, -1)
+    out = torch.zeros((B, H + 2 * pad, W + 2 * pad, C), dtype=torch.float64, device=t.device)
+    for ky in range(kh):
+        for kx in range(kw):
+            k0 = (ky * kw + kx) * C
+            out[:, ky:ky + OH, kx:kx + OW] += t[..., k0:k0 + C]
+    return out[:, pad:pad + H, pad:pad + W]
+
+
+def col2im_ref_bound(dcol, B, H, W, C, kh, kw, pad):
+    return col2im_fold(dcol, B, H, W, C, kh, kw, pad), kh * kw * U32 * col2im_fold(dcol.double().abs(), B, H, W, C, kh, kw, pad)
+
+
+def pool_windows(y2d, B, H, W, C):
+    """[B, H/2, W/2, C, 4] view-copy of y2d [B*H*W, >= C]: the 2x2 windows in the order (0,0), (0,1), (1,0), (1,1)."""
+    return y2d[:, :C].reshape(B, H // 2, 2, W // 2, 2, C).permute(0, 1, 3, 5, 2, 4).reshape(B, H // 2, W // 2, C, 4)
+
+
+def _pool_values(y2d):
+    return y2d.float() if y2d.dtype == torch.bfloat16 else y2d               # bf16 -> fp32 is exact; fp32 / fp64 stay as they are
+
+
+def relu_pool_fwd_ref(y2d, B, H, W, C):
+    return pool_windows(_pool_values(y2d), B, H, W, C).amax(-1).clamp_min(0.0).to(torch.bfloat16)
+
+
+def relu_pool_bwd_ref(dp, y2d, B, H, W, C, cpad=None):
+    """dy [B*H*W, cpad] bf16: bf16(dp) at the first maximum of each window iff that maximum is > 0, zero elsewhere."""
+    cpad = C if cpad is None else cpad
+    w = pool_windows(_pool_values(y2d), B, H, W, C)
+    arg = w.argmax(-1, keepdim=True)                                       # torch: the first index on ties
+    g = torch.where(w.amax(-1) > 0, dp.reshape(B, H // 2, W // 2, C).to(torch.bfloat16), torch.zeros((), dtype=torch.bfloat16, device=dp.device))
+    d4 = torch.zeros(w.shape, dtype=torch.bfloat16, device=dp.device).scatter_(-1, arg, g[..., None])
+    dy = d4.reshape(B, H // 2, W // 2, C, 2, 2).permute(0, 1, 4, 2, 5, 3).reshape(B * H * W, C)
+    return torch.nn.functional.pad(dy, (0, cpad - C))
+
+
+def pool_edge_windows(B, H, W, C, seed, dtype=torch.float32):
+    """y [B*H*W, C] in `dtype` (values exact in it) with twelve constructed windows in a row (in the flat [B, H/2, W/2, C] window order),
+    repeated at up to 64 places spread over the images, rows and channels: all four equal and positive; the six two-way ties; all negative; maximum exactly 0.0; maximum -0.0; a maximum one
+    ulp of `dtype` above the runner-up -- in fp32 far below bf16's resolution -- once with the runner-up first and once with the
+    maximum first and last; the rest random.  Needs B (H/2) (W/2) C >= 12 windows."""
+    y = rnd(B * H * W, C, seed=seed).to(dtype).float()
+    w = pool_windows(y, B, H, W, C).reshape(-1, 4).clone()
+    n = w.shape[0]
+    pairs = [(0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3)]
+    rows = []
+    rows.append([0.75, 0.75, 0.75, 0.75])
+    for a, b in pairs:
+        r = [-0.5, 0.25, -1.0, 0.125]
+        r[a] = r[b] = 1.5
+        rows.append(r)
+    rows.append([-0.5, -2.0, -0.25, -1.0])
+    rows.append([-1.0, 0.0, -0.5, -3.0])
+    rows.append([-1.0, -2.0, -0.0, -0.5])
+    one = torch.tensor(1.0, dtype=dtype)
+    up = float(torch.nextafter(one, one * 2)) if dtype == torch.float32 else 1.0 + 2.0 ** -7
+    rows.append([1.0, 0.5, up, 1.0])
+    rows.append([up, 1.0, 1.0, up])
+    pat = torch.tensor(rows, dtype=torch.float32)
+    reps = min(n // pat.shape[0], 64)
+    stride = max(1, n // max(reps, 1))
+    for r in range(reps):                                                      # spread over images, rows and channels
+        i0 = r * stride
+        if i0 + pat.shape[0] <= n:
+            w[i0:i0 + pat.shape[0]] = pat
+    y = w.reshape(B, H // 2, W // 2, C, 2, 2).permute(0, 1, 4, 2, 5, 3).reshape(B * H * W, C)
+    return y.to(dtype)
+
+
+def conv_pack_ref(Wm, bias, Kpad):
+    Cout, K = Wm.shape
+    out = torch.zeros((Cout, Kpad), dtype=torch.bfloat16, device=Wm.device)
+    out[:, :K] = Wm.to(torch.bfloat16)
+    if bias is not None:
+        out[:, K] = bias.to(torch.bfloat16)
+    return out
+
+
+def pool_decisions(y64, e_y, B, H, W, C):
+    """Windows [B, H/2, W/2, C] (bool) of a conv pre-activation y64 [B*H*W, C] known to within e_y whose pooling is a decision:
+    the runner-up lies within the two bounds of the maximum, or the maximum lies within its bound of 0."""
+    w, e = pool_windows(y64, B, H, W, C), pool_windows(e_y, B, H, W, C)
+    top, arg = w.max(-1, keepdim=True)
+    e_top = e.gather(-1, arg)
+    other = torch.ones_like(w, dtype=torch.bool).scatter_(-1, arg, False)
+    close = (other & (w + e >= top - e_top)).any(-1)
+    return close | (top[..., 0].abs() <= e_top[..., 0])
+
+
+# ---------------------------------------------------------------------------------------------------------------- map heads
+def pair_logits_ref_bound(p, text, rows_per_batch, scale):
+    """fp64 [rows, 2] = scale <p, t_j> / ||p|| of fp32 p [rows, C] and text [B, 2, C], row r against pair r // rows_per_batch."""
+    p64 = p.double()
+    rows, C = p64.shape
+    t = text.double()[torch.arange(rows, device=p.device) // rows_per_batch]          # [rows, 2, C]
+    dot = (p64[:, None] * t).sum(-1)
+    mag = (p64[:, None] * t).abs().sum(-1)
+    n = (p64 * p64).sum(1, keepdim=True).sqrt()
+    s = f32_value(scale)
+    ref = s * dot / n
+    g = g_sum(4 * -(-C // 256), 0)
+    return ref, abs(s) / n * g * mag + ref.abs() * (g / 2 + (2 * C_FN + 2) * U32)
+
+
+def _ac_axis(n_in, n_out, device):
+    """align_corners=True source positions of n_out samples over n_in cells: (pos, i0, i1, t) with pos = o (n_in-1)/(n_out-1)."""
+    o = torch.arange(n_out, dtype=torch.float64, device=device)
+    pos = o * (n_in - 1) / (n_out - 1) if n_out > 1 else torch.zeros_like(o)
+    i0 = pos.floor().long().clamp(max=max(n_in - 2, 0))
+    return pos, i0, i0 + (1 if n_in > 1 else 0), pos - i0
+
+
+def _nbr_max(s):
+    """Max of s [B, a, b] over the 3 x 3 neighbourhood (a or b may be 0: returned as is)."""
+    if s.numel() == 0:
+        return s
+    return torch.nn.functional.max_pool2d(s[:, None], 3, stride=1, padding=1)[:, 0]
+
+
+def bilinear_ref_bound(x, H, W, one_minus=False, extra_rel=0.0):
+    """fp64 align_corners=True resize of x [B, h, w] to [B, H, W] and its bound (module docstring); extra_rel: a relative error the
+    input values themselves carry (zs_accumulate's rounded difference)."""
+    x = x.double()
+    B, h, w = x.shape
+    py, y0, y1, ty = _ac_axis(h, H, x.device)
+    px, x0, x1, tx = _ac_axis(w, W, x.device)
+    ty, tx = ty[None, :, None], tx[None, None, :]
+
+    def lerp(a):
+        a00, a01 = a[:, y0][:, :, x0], a[:, y0][:, :, x1]
+        a10, a11 = a[:, y1][:, :, x0], a[:, y1][:, :, x1]
+        return (1 - ty) * ((1 - tx) * a00 + tx * a01) + ty * ((1 - tx) * a10 + tx * a11)
+
+    v, mag = lerp(x), lerp(x.abs())
+    e = (6 * U32 + extra_rel) * mag
+    if h > 1:                                                   # slope along y of cell row i, at every column; 3 x 3 neighbourhood
+        sy = _nbr_max((x[:, 1:] - x[:, :-1]).abs())
+        slope = torch.maximum(sy[:, y0][:, :, x0], sy[:, y0][:, :, x1])
+        e = e + 2 * U32 * py[None, :, None] * slope
+    if w > 1:
+        sx = _nbr_max((x[:, :, 1:] - x[:, :, :-1]).abs())
+        slope = torch.maximum(sx[:, y0][:, :, x0], sx[:, y1][:, :, x0])
+        e = e + 2 * U32 * px[None, None, :] * slope
+    if one_minus:
+        v = 1 - v
+        e = e + U32 * v.abs()
+    return v, e
+
+
+def _sigmoid_through(d, e_d):
+    """(sigmoid(d), absolute bound) for the kernel's 1 / (1 + __expf(-d')) with |d' - d| <= e_d."""
+    s, rel = _sigmoid_rel(d)
+    slope = (s * (1 - s) * torch.exp(e_d)).clamp(max=0.25)
+    return s, slope * e_d + s * rel + F32_TINY
+
+
+def zs_accumulate_ref_bound(logits, mask_prev, map_prev, w):
+    """fp64 (mask, mask bound, map, map bound) after mask_prev [B, h, h] += w sigmoid(l1 - l0), map_prev [B, S, S] +=
+    w sigmoid(bilinear_ac(l1 - l0)) for fp32 logits [B, h*h, 2]."""
+    B, h, S = mask_prev.shape[0], mask_prev.shape[-1], map_prev.shape[-1]
+    w = f32_value(w)
+    d = (logits.double()[..., 1] - logits.double()[..., 0]).reshape(B, h, h)
+    s, e_s = _sigmoid_through(d, U32 * d.abs())
+    mask = mask_prev.double() + w * s
+    e_mask = abs(w) * e_s + U32 * (mask_prev.double().abs() + (w * s).abs())
+    di, e_di = bilinear_ref_bound(d, S, S, extra_rel=U32)
+    si, e_si = _sigmoid_through(di, e_di)
+    amap = map_prev.double() + w * si
+    e_map = abs(w) * e_si + U32 * (map_prev.double().abs() + (w * si).abs())
+    return mask, e_mask, amap, e_map
+
+
+def rowmax_skip_ref_bound(s, acc_prev, period, w):
+    """fp64 acc_prev[row] + w max_{c % period != 0} s[row, c] (period <= 0: every column) and its bound; -inf where no finite
+    column is kept (compare those rows with rowmax_check)."""
+    s = s.double()
+    w = f32_value(w)
+    c = torch.arange(s.shape[1], device=s.device)
+    keep = (c % period != 0) if period > 0 else torch.ones_like(c, dtype=torch.bool)
+    m = s.masked_fill(~keep[None], float("-inf")).amax(1) if bool(keep.any()) else torch.full_like(s[:, 0], float("-inf"))
+    ref = acc_prev.double() + w * m
+    return ref, 2 * U32 * (acc_prev.double().abs() + (w * m).abs())
+
+
+def rowmax_check(got, ref, bound, what="rowmax_skip"):
+    """assert_within where the reference is finite; an infinite reference must be met exactly."""
+    inf = torch.isinf(ref)
+    assert torch.equal(got.double()[inf], ref[inf]), f"{what}: a row without a finite kept column is not {ref[inf][:1].tolist()}"
+    return assert_within(got[~inf], ref[~inf], bound[~inf], what)
+
+
+# ---------------------------------------------------------------------------------------------------------------- stem chain
+CHAIN_CASES = [(1, 4, 2, 32, 32, 901), (4, 16, 2, 16, 24, 902)]            # ci, co, B, H, W, seed: VENet's first two stem layers
+
+
+def stem_chain_case(ci, co, B, H, W, seed):
+    """(x [B, H, W, ci] bf16, wm [co, 9 ci] f32 in GEMM order, bias [co] f32, dp [B, H/2, W/2, co] f32 with bf16 values)."""
+    return (rnd(B, H, W, ci, seed=seed).to(torch.bfloat16), rnd(co, 9 * ci, seed=seed + 1) * 0.3, rnd(co, seed=seed + 2) * 0.1,
+            bf16_round(rnd(B, H // 2, W // 2, co, seed=seed + 3)))
+
+
+def stem_chain_ref(x, wm, bias, dp, wgrad_splits=1):
+    """One stem layer in fp64 -- conv2d(3x3, pad 1) -> relu -> max_pool2d(2) and its autograd -- on the operands the kernels
+    multiply (bf16 x, bf16-rounded weight and bias), with the bounds composed from gemm_ref_bound, the pooling's decisions and
+    col2im's fold.  Windows whose routing is a decision (pool_decisions) get no gradient: dp_used is dp with those zeroed.
+    Returns a dict (all [rows, cols] in the kernels' layouts)."""
+    F = torch.nn.functional
+    B, H, W, ci = x.shape
+    co, K = wm.shape
+    Kpad = (K + 1 + 63) // 64 * 64
+    M = B * H * W
+    xr = x.double().permute(0, 3, 1, 2).clone().requires_grad_(True)
+    wr = bf16_round(wm).double().reshape(co, 3, 3, ci).permute(0, 3, 1, 2).clone().requires_grad_(True)
+    br = bf16_round(bias).double().clone().requires_grad_(True)
+    y = F.conv2d(xr, wr, br, padding=1)
+    y2d = y.detach().permute(0, 2, 3, 1).reshape(M, co)
+    col, wp = im2col_ref(x, 3, 3, 1, Kpad, True), conv_pack_ref(wm, bias, Kpad)
+    y_gemm, e_y = gemm_ref_bound(col, wp)
+    dec = pool_decisions(y2d, e_y, B, H, W, co)
+    dp_used = torch.where(dec, torch.zeros_like(dp), dp)
+    pool = F.max_pool2d(F.relu(y), 2)
+    (pool * dp_used.double().permute(0, 3, 1, 2)).sum().backward()
+    e_p = pool_windows(e_y, B, H, W, co).amax(-1)
+    p_ref = pool.detach().permute(0, 2, 3, 1)
+    dy = relu_pool_bwd_ref(dp_used, y2d, B, H, W, co, 64)                                  # [M, 64] bf16, exact
+    Mpad = (M + 63) // 64 * 64
+    dyT = F.pad(dy[:, :co].T, (0, Mpad - M))
+    colT = F.pad(col.T, (0, Mpad - M))
+    dwp, e_dwp = gemm_ref_bound(dyT, colT, splits=wgrad_splits)
+    wpT = F.pad(wp.T, (0, 64 - co))                                                         # [Kpad, 64]
+    dcol, e_dcol = gemm_ref_bound(dy, wpT, out_bf16=True)
+    dx = xr.grad.permute(0, 2, 3, 1)
+    e_dx = col2im_fold(e_dcol, B, H, W, ci, 3, 3, 1) + 9 * U32 * col2im_fold(dcol.abs() + e_dcol, B, H, W, ci, 3, 3, 1)
+    return dict(col=col, wp=wp, y=y2d, y_gemm=y_gemm, y_bound=e_y, decisions=dec, dp_used=dp_used, p=p_ref, p_bound=bf16_out(p_ref, e_p),
+                dy=dy, dwp=dwp, dwp_bound=e_dwp, dW=wr.grad.permute(0, 2, 3, 1).reshape(co, K), db=br.grad, dcol=dcol,
+                dcol_bound=e_dcol, dx=dx, dx_bound=e_dx, dx_fold=col2im_fold(dcol, B, H, W, ci, 3, 3, 1), K=K, Kpad=Kpad)
+
+
+# ---------------------------------------------------------------------------------------------------------------- inputs
+BF16 = torch.bfloat16
+
+
+def col2im_input(B, H, W, C, kh, kw, pad, seed, device="cpu"):
+    """A random bf16 dcol [M, Kpad] whose bias and pad columns hold large values (a tap that reads them shows)."""
+    OH, OW = conv_out_hw(H, W, kh, kw, pad)
+    K = kh * kw * C
+    Kpad = (K + 64) // 64 * 64
+    d = rnd(B * OH * OW, Kpad, seed=seed).to(BF16)
+    d[:, K:] = 1e4
+    return d.to(device)
+
+
+def pair_inputs(rows, C, rpb, seed):
+    """p [rows, C] with rows scaled by 1e-4 and 1e4 next to each other (row % 3 == 1, 2) and the text pairs [ceil(rows/rpb), 2, C]."""
+    p = rnd(rows, C, seed=seed)
+    k = torch.arange(rows) % 3
+    p[k == 1] *= 1e-4
+    p[k == 2] *= 1e4
+    text = rnd(-(-rows // rpb), 2, C, seed=seed + 1)
+    return p, text / text.norm(dim=-1, keepdim=True)
+
+
+def zs_inputs(B, h, S, seed):
+    """Logits [B, h*h, 2] whose differences reach +-60, and non-zero accumulators."""
+    lg = rnd(B, h * h, 2, seed=seed) * 3
+    lg[:, 0::5, 1] += torch.linspace(-60, 60, lg[:, 0::5].shape[1])[None]
+    return lg, rnd(B, h, h, seed=seed + 1).abs(), rnd(B, S, S, seed=seed + 2).abs()
+
+
+def rowmax_inputs(rows, cols, wide, seed):
+    """scores [rows, cols] as a window of a [rows, wide] matrix whose excluded columns hold the row's largest values; row 0's
+    maximum sits in column 0, row 1's in the last column, row 2 is -inf but for one entry, row 3's maximum sits in a multiple-of-5 column; and a non-zero accumulator."""
+    full = rnd(rows, wide, seed=seed)
+    full[:, cols:] = 50.0
+    full[0, 0] = 9.0
+    if rows > 1:
+        full[1, cols - 1] = 8.0
+    if rows > 2:
+        full[2, :cols] = float("-inf")
+        full[2, cols // 2] = -1.5
+    if rows > 3:
+        full[3, (cols - 1) // 5 * 5] = 9.5                   # a multiple of 5: skipped at period 5
+    return full, rnd(rows, seed=seed + 1)

@@ -829,3 +829,427 @@ def test_attention_case_rope_ambiguity_stays_rare():
     pos = torch.arange(150)[None] + 5 * torch.arange(2)[:, None]
     cos, sin = fb.rope_tables(64)
     fb.assert_rope_exempt_share(fb.rope_bf16(q.float(), pos, cos, sin)[1], "q")
+
+
+# ------------------------------------------------------------------------------------------------------------- conv stack
+def _raises(fn, *a, **k):
+    with pytest.raises(AssertionError):
+        fn(*a, **k)
+
+
+def emu_im2col(x, kh, kw, pad, Kpad, bias_col, mutant=None):
+    """im2col_kernel's index arithmetic on a poisoned output: item (m, 4-column group), k -> (tap, c) -> (ky, kx) -> (iy, ix)."""
+    B, H, W, C = x.shape
+    OH, OW = fb.conv_out_hw(H, W, kh, kw, pad)
+    K, M = kh * kw * C, B * OH * OW
+    col = fb.poisoned((M, Kpad), BF16, "cpu")
+    groups = Kpad // 4 - (1 if mutant == "last_group_unwritten" else 0)
+    m, k = torch.arange(M)[:, None], torch.arange(groups * 4)[None]
+    ox, oy, b = m % OW, (m // OW) % OH, m // (OW * OH)
+    tap = k // C
+    c = k - tap * C
+    ky, kx = tap // kw, tap - (tap // kw) * kw
+    if mutant == "kxky_swapped":
+        ky, kx = kx, ky
+    iy, ix = oy + ky - pad, ox + kx - pad
+    if mutant == "pad_ignored_at_top":
+        iy = iy.clamp_min(0)
+    ok = (k < K) & (iy >= 0) & (iy < H) & (ix >= 0) & (ix < W)
+    flat = ((b * H + iy.clamp(0, H - 1)) * W + ix.clamp(0, W - 1)) * C + c
+    val = torch.where(ok, x.reshape(-1)[flat.clamp(0, x.numel() - 1)], torch.zeros((), dtype=BF16))
+    ones_at = K - 1 if mutant == "ones_at_K_minus_1" else K
+    if bias_col or mutant == "ones_without_bias_col":
+        val = torch.where(k == ones_at, torch.ones((), dtype=BF16), val)
+    col[:, :groups * 4] = val
+    return col
+
+
+IM2COL_CPU_CASES = [(2, 6, 10, 8, 3, 3, 1), (1, 8, 8, 1, 3, 3, 1), (2, 7, 7, 16, 5, 5, 0), (1, 2, 2, 4, 3, 3, 1), (1, 5, 5, 64, 5, 5, 0)]
+IM2COL_MUTANTS = ["pad_ignored_at_top", "kxky_swapped", "ones_at_K_minus_1", "ones_without_bias_col", "last_group_unwritten"]
+
+
+def _im2col_case(B, H, W, C, kh, kw, pad, bias_col, mutant=None):
+    x = fb.rnd(B, H, W, C, seed=31).to(BF16)
+    K = kh * kw * C
+    Kpad = (K + 64) // 64 * 64                        # a padded row in both forms, as a caller with K % 64 != 0 would get
+    got = emu_im2col(x, kh, kw, pad, Kpad, bias_col, mutant)
+    ref = fb.im2col_ref(x, kh, kw, pad, Kpad, bias_col)
+    assert torch.equal(got, ref), "im2col differs"
+    assert bool((ref[:, K + 1:] == 0).all()) and bool((ref[:, K] == (1.0 if bias_col else 0.0)).all())
+
+
+@pytest.mark.parametrize("case", IM2COL_CPU_CASES)
+@pytest.mark.parametrize("bias_col", [True, False])
+def test_im2col_emulation_equals_the_gather(case, bias_col):
+    _im2col_case(*case, bias_col)
+
+
+@pytest.mark.parametrize("mutant", IM2COL_MUTANTS)
+def test_im2col_mutant_fails(mutant):
+    # the non-square 3x3 case; (kx, ky) swapped needs a non-symmetric image, the ones column the form without a bias column
+    _raises(_im2col_case, 2, 6, 10, 8, 3, 3, 1, mutant != "ones_without_bias_col", mutant)
+
+
+def test_im2col_reference_is_not_unfold_order():
+    """F.unfold's columns are channel-major (c, ky, kx); the kernel's are (ky, kx, c): the reference must be the latter."""
+    x = fb.rnd(1, 4, 4, 3, seed=32).to(BF16)
+    ref = fb.im2col_ref(x, 3, 3, 1, 28, False)[:, :27].float()
+    unf = torch.nn.functional.unfold(x.float().permute(0, 3, 1, 2), 3, padding=1)[0].T
+    assert not torch.equal(ref, unf)
+    assert torch.equal(ref.view(16, 9, 3).permute(0, 2, 1).reshape(16, 27), unf)
+
+
+def emu_col2im(dcol, B, H, W, C, kh, kw, pad, mutant=None):
+    """col2im_kernel: the gather form, taps added serially in fp32 in (ky, kx) order onto 0."""
+    OH, OW = fb.conv_out_hw(H, W, kh, kw, pad)
+    ld = dcol.shape[1]
+    K = kh * kw * C
+    it = torch.arange(B * H * W * C)
+    c, p = it % C, it // C
+    ix, iy, b = p % W, (p // W) % H, p // (W * H)
+    s = torch.zeros(it.numel(), dtype=F32)
+    flat = dcol.reshape(-1)
+    for ky in range(kh):
+        for kx in range(kw):
+            oy, ox = iy + pad - ky, ix + pad - kx
+            if mutant == "correlation":
+                oy, ox = iy - pad + ky, ix - pad + kx
+            elif mutant == "ox_plus_pad_plus_kx":
+                ox = ix + pad + kx
+            ok = (oy >= 0) & (oy < OH) & (ox >= 0) & (ox < OW)
+            if mutant == "corner_tap_dropped" and (ky, kx) == (kh - 1, kw - 1):
+                ok = ok & ~((iy == H - 1) & (ix == W - 1))
+            kcol = (ky * kw + kx) * C + c
+            if mutant == "bias_column_as_tap" and (ky, kx) == (kh - 1, kw - 1):
+                kcol = torch.where(c == C - 1, torch.full_like(kcol, K), kcol)
+            idx = ((b * OH + oy.clamp(0, OH - 1)) * OW + ox.clamp(0, OW - 1)) * ld + kcol
+            s = s + torch.where(ok, flat[idx].float(), torch.zeros(()))
+    return s.view(B, H, W, C)
+
+
+COL2IM_MUTANTS = ["correlation", "ox_plus_pad_plus_kx", "corner_tap_dropped", "bias_column_as_tap"]
+
+
+def _col2im_case(B, H, W, C, kh, kw, pad, mutant=None):
+    d = fb.col2im_input(B, H, W, C, kh, kw, pad, seed=33)
+    ref, bound = fb.col2im_ref_bound(d, B, H, W, C, kh, kw, pad)
+    return fb.assert_within(emu_col2im(d, B, H, W, C, kh, kw, pad, mutant), ref, bound, "col2im")
+
+
+@pytest.mark.parametrize("case", IM2COL_CPU_CASES)
+def test_col2im_emulation_is_within_the_bound(case):
+    assert _col2im_case(*case) <= 0.5        # often 0: a few bf16 values of like size add exactly in fp32
+
+
+@pytest.mark.parametrize("mutant", COL2IM_MUTANTS)
+@pytest.mark.parametrize("case", [(2, 6, 10, 8, 3, 3, 1), (2, 7, 7, 16, 5, 5, 0)])
+def test_col2im_mutant_fails(case, mutant):
+    _raises(_col2im_case, *case, mutant)
+
+
+def emu_relu_pool(dp, y2d, B, H, W, C, cpad, mutant=None):
+    """relu_pool_fwd / _bwd kernels on y2d [M, >= C] (fp32 or bf16): fmaxf from the 0 floor; strict > scan from the first cell,
+    gradient iff the maximum is > 0; the wrapper's dy buffer is zero-filled when it has pad columns, else the kernel owns all of it."""
+    w = fb.pool_windows(y2d.float(), B, H, W, C)
+    if mutant == "y_rounded_to_bf16":
+        w = w.to(BF16).float()
+    m = torch.zeros(w.shape[:-1])
+    for e in range(4):
+        m = torch.maximum(m, w[..., e])
+    p = m.to(BF16)
+    best, arg = w[..., 0].clone(), torch.zeros(w.shape[:-1], dtype=torch.long)
+    for e in range(1, 4):
+        take = w[..., e] >= best if mutant == "last_maximum_wins" else w[..., e] > best
+        best, arg = torch.where(take, w[..., e], best), torch.where(take, torch.full_like(arg, e), arg)
+    live = best >= 0 if mutant == "gradient_at_zero" else best > 0
+    g = torch.where(live, dp.reshape(best.shape), torch.zeros(())).to(BF16)
+    d4 = torch.zeros(w.shape, dtype=BF16).scatter_(-1, arg[..., None], g[..., None])
+    full = fb.poisoned((B * H * W, cpad), BF16, "cpu")
+    if cpad != C and mutant != "pad_columns_unwritten":
+        full.zero_()
+    full[:, :C] = d4.reshape(B, H // 2, W // 2, C, 2, 2).permute(0, 1, 4, 2, 5, 3).reshape(B * H * W, C)
+    return p, full
+
+
+POOL_MUTANTS = ["last_maximum_wins", "gradient_at_zero", "y_rounded_to_bf16", "pad_columns_unwritten"]
+
+
+def _pool_case(dtype, C, cpad, mutant=None):
+    B, H, W = 2, 4, 6
+    y = fb.pool_edge_windows(B, H, W, C, seed=34, dtype=dtype)
+    wide = fb.rnd(B * H * W, C + 8, seed=35).to(dtype)                  # y as a column window of a wider buffer
+    wide[:, :C] = y
+    dp = fb.rnd(B, H // 2, W // 2, C, seed=36) + 3.0                    # no zero gradients: a wrong route or gate always shows
+    p, dy = emu_relu_pool(dp, wide[:, :C], B, H, W, C, cpad, mutant)
+    assert torch.equal(p, fb.relu_pool_fwd_ref(y, B, H, W, C)), "relu_pool_fwd differs"
+    assert torch.equal(dy, fb.relu_pool_bwd_ref(dp, y, B, H, W, C, cpad)), "relu_pool_bwd differs"
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16])
+@pytest.mark.parametrize("C,cpad", [(4, 4), (4, 64), (16, 64), (64, 64)])
+def test_relu_pool_emulation_equals_the_reference(dtype, C, cpad):
+    _pool_case(dtype, C, cpad)
+
+
+@pytest.mark.parametrize("mutant", POOL_MUTANTS)
+def test_relu_pool_mutant_fails(mutant):
+    _raises(_pool_case, F32, 4, 64, mutant)
+
+
+def test_pool_edge_windows_hold_every_constructed_case():
+    for dtype in (F32, BF16):
+        w = fb.pool_windows(fb.pool_edge_windows(2, 4, 6, 4, seed=34, dtype=dtype).float(), 2, 4, 6, 4).reshape(-1, 4)
+        top = w.amax(1, keepdim=True)
+        ties = (w == top).sum(1)
+        assert bool((ties == 4).any()) and bool((top[:, 0] < 0).any())
+        for a, b in [(0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3)]:
+            assert bool(((ties == 2) & (w[:, a] == top[:, 0]) & (w[:, b] == top[:, 0]) & (top[:, 0] > 0)).any()), (a, b)
+        zero = (top[:, 0] == 0)
+        neg0 = zero & torch.signbit(w).any(1) & ~(w == 0).logical_and(~torch.signbit(w)).any(1)
+        assert bool((zero & ~neg0).any()) and bool(neg0.any())
+        if dtype == F32:
+            second = w.topk(2, 1).values[:, 1:2]
+            assert bool(((top > second) & (top.to(BF16) == second.to(BF16)) & (top > 0)).any())
+
+
+def emu_conv_pack(Wm, bias, Kpad, mutant=None):
+    """conv_pack_kernel: 8-element chunks; two float4 loads where K % 4 == 0 and the chunk lies inside the row, else the scalar
+    form, which also places the bias and the zeros."""
+    Cout, K = Wm.shape
+    out = fb.poisoned((Cout, Kpad), BF16, "cpu")
+    vec = K % 4 == 0
+    for k0 in range(0, Kpad, 8):
+        v = torch.zeros(Cout, 8)
+        if vec and k0 + 8 <= K:
+            v = Wm[:, k0:k0 + 8].clone()
+        else:
+            for e in range(8):
+                k = k0 + e
+                if k < K:
+                    v[:, e] = Wm[:, k]
+                elif k == K and bias is not None and not (mutant == "bias_lost_in_tail_chunk" and vec and k0 < K):
+                    v[:, e] = bias
+        if mutant == "truncation":
+            out[:, k0:k0 + 8] = (v.view(torch.int32) & -65536).view(F32).to(BF16)
+        else:
+            out[:, k0:k0 + 8] = v.to(BF16)
+    return out
+
+
+def _pack_case(K, Cout, with_bias, mutant=None):
+    Wm, bias = fb.rnd(Cout, K, seed=37), (fb.rnd(Cout, seed=38) + 2.0 if with_bias else None)
+    Kpad = (K + 64) // 64 * 64
+    assert torch.equal(emu_conv_pack(Wm, bias, Kpad, mutant), fb.conv_pack_ref(Wm, bias, Kpad)), "conv_pack differs"
+
+
+@pytest.mark.parametrize("K", [9, 36, 63, 64, 144])
+@pytest.mark.parametrize("with_bias", [True, False])
+def test_conv_pack_emulation_equals_the_reference(K, with_bias):
+    _pack_case(K, 5, with_bias)
+
+
+def test_conv_pack_mutants_fail():
+    _raises(_pack_case, 36, 5, True, "bias_lost_in_tail_chunk")            # K % 4 == 0, K % 8 != 0: the bias sits in the tail chunk
+    _pack_case(64, 5, True, "bias_lost_in_tail_chunk")                      # ... and only there: at K % 8 == 0 the mutant is the kernel
+    _raises(_pack_case, 36, 5, True, "truncation")
+
+
+def test_conv_unpack_reference_and_a_bias_read_one_column_early():
+    for K in (9, 36):
+        dWp = fb.rnd(5, 64, seed=39)
+        for col, ok in ((K, True), (K - 1, False)):
+            dW, db = fb.poisoned((5, K), F32, "cpu"), fb.poisoned((5,), F32, "cpu")
+            dW.copy_(dWp[:, :K]), db.copy_(dWp[:, col])
+            assert torch.equal(dW, dWp[:, :K]) and torch.equal(db, dWp[:, K]) == ok
+
+
+@pytest.mark.parametrize("case", fb.CHAIN_CASES)
+def test_stem_chain_reference_is_consistent_and_decisions_are_rare(case):
+    """The chain test's fp64 pieces are the autograd's (the wgrad GEMM of the routed dy is conv2d's weight gradient, its bias
+    column the bias gradient, the fold of the dgrad GEMM the input gradient), and the windows whose routing is a decision are at
+    most 1 % -- from the fp64 reference and the bf16-rounded operands alone."""
+    r = fb.stem_chain_ref(*fb.stem_chain_case(*case), wgrad_splits=8)
+    K = r["K"]
+    share = float(r["decisions"].double().mean())
+    assert share <= 0.01, f"{share:.3%} of the windows are decisions"
+    assert float((r["dp_used"] != 0).double().mean()) > 0.98
+    for a, b in ((r["y"], r["y_gemm"]), (r["dwp"][:, :K], r["dW"]), (r["dwp"][:, K], r["db"]), (r["dx_fold"], r["dx"])):
+        assert float((a - b).abs().max()) <= 1e-12 * float(b.abs().max())
+    assert bool((r["dwp"][:, K + 1:] == 0).all())
+
+
+def test_pool_decisions_flags_close_runner_ups_and_maxima_near_zero():
+    y = torch.tensor([[1.0], [1.0 - 1e-7], [0.2], [0.1],     # window 0 (H = W = 2, C = 1): runner-up within the bounds
+                      [1.0], [0.5], [0.2], [0.1],            # 1: clear
+                      [1e-8], [-1.0], [-2.0], [-3.0],        # 2: maximum within its bound of 0
+                      [-1.0], [-1.0], [-2.0], [-3.0]]).double()   # 3: a tie below zero -- no gradient either way, but flagged
+    y = y.reshape(4, 2, 2, 1).reshape(16, 1)
+    dec = fb.pool_decisions(y, torch.full_like(y, 6e-8), 4, 2, 2, 1)
+    assert dec.reshape(-1).tolist() == [True, False, True, True]
+
+
+# ---------------------------------------------------------------------------------------------------------------- map heads
+def emu_pair_logits(p, text, rpb, scale, mutant=None):
+    """pair_logits_kernel: lane l adds the products of its float4 chunks (columns 4 l + 256 j) serially, a 64-lane butterfly, then
+    scale / sqrtf(nn) and one product."""
+    rows, C = p.shape
+    tidx = torch.arange(rows) // (rpb + 1 if mutant == "pair_index_off" else rpb)
+    t = text[tidx.clamp(max=text.shape[0] - 1)]
+    J = -(-C // 256)
+    if mutant == "last_float4_dropped" and C % 256:
+        J -= 1
+
+    def lanes(a, b):
+        prod = torch.zeros(rows, J * 256 if J else 256)
+        n = min(C, J * 256)
+        prod[:, :n] = (a * b)[:, :n]
+        prod = prod.view(rows, max(J, 1), 64, 4)
+        s = torch.zeros(rows, 64)
+        for j in range(max(J, 1)):
+            for e in range(4):
+                s = s + prod[:, j, :, e]
+        lane = torch.arange(64)
+        for o in (32, 16, 8, 4, 2, 1):
+            s = s + s[:, lane ^ o]
+        return s[:, 0]
+
+    d0, d1 = lanes(p, t[:, 0]), lanes(p, t[:, 1])
+    nn = lanes(t[:, 0], t[:, 0]) if mutant == "norm_of_text" else lanes(p, p)
+    inv = torch.tensor(scale, dtype=F32) / torch.sqrt(nn)
+    return torch.stack([d0 * inv, d1 * inv], 1)
+
+
+PAIR_MUTANTS = ["pair_index_off", "last_float4_dropped", "norm_of_text"]
+
+
+def _pair_case(rows, C, rpb, mutant=None):
+    p, text = fb.pair_inputs(rows, C, rpb, seed=41)
+    ref, bound = fb.pair_logits_ref_bound(p, text, rpb, 100.0)
+    return fb.assert_within(emu_pair_logits(p, text, rpb, 100.0, mutant), ref, bound, "pair_logits")
+
+
+@pytest.mark.parametrize("rows,C,rpb", [(7, 4, 1), (9, 252, 3), (13, 772, 3), (5, 1024, 257)])
+def test_pair_logits_emulation_is_within_the_bound(rows, C, rpb):
+    assert 1e-3 < _pair_case(rows, C, rpb) <= 0.5
+
+
+@pytest.mark.parametrize("mutant", PAIR_MUTANTS)
+def test_pair_logits_mutant_fails(mutant):
+    _raises(_pair_case, 13, 772, 3, mutant)
+
+
+def emu_bilinear(x, H, W, one_minus=False, mutant=None, quotient=True):
+    """bilinear_ac_kernel in fp32: position fl(o (n_in - 1) / (n_out - 1)), one division of exact integers (quotient=False:
+    zs_accumulate_kernel's o * fl((n_in - 1) / (n_out - 1))), truncated and clamped to the last cell."""
+    B, h, w = x.shape
+    if mutant == "h_w_swapped":
+        x = x.reshape(B, w, h)
+        h, w = w, h
+
+    def axis(n_in, n_out):
+        o = torch.arange(n_out, dtype=F32)
+        if mutant == "align_corners_false":
+            f = ((o + 0.5) * torch.tensor(n_in / n_out, dtype=F32) - 0.5).clamp_min(0.0)
+        else:
+            step = torch.tensor(float(n_in - 1), dtype=F32) / torch.tensor(float(n_out - 1), dtype=F32) if n_out > 1 else torch.zeros(())
+            f = (o * float(n_in - 1)) / torch.tensor(float(max(n_out - 1, 1)), dtype=F32) if quotient else o * step
+        i0 = f.to(torch.int32).long()
+        i0 = torch.where(i0 < n_in - 1, i0, torch.full_like(i0, n_in - 2 if n_in > 1 else 0))
+        return i0, i0 + (1 if n_in > 1 else 0), f - i0.float()
+
+    y0, y1, wy = axis(h, H)
+    x0, x1, wx = axis(w, W)
+    wy, wx = wy[None, :, None], wx[None, None, :]
+    g = lambda yi, xi: x[:, yi][:, :, xi]
+    v = (1 - wy) * ((1 - wx) * g(y0, x0) + wx * g(y0, x1)) + wy * ((1 - wx) * g(y1, x0) + wx * g(y1, x1))
+    return 1 - v if one_minus else v
+
+
+BILINEAR_CASES = [(5, 9, 33, 20), (16, 16, 224, 224), (16, 16, 7, 7), (1, 1, 7, 7), (2, 2, 3, 3), (7, 7, 7, 7), (5, 9, 1, 20), (5, 9, 33, 1)]
+
+
+def _bilinear_case(h, w, H, W, one_minus, mutant=None):
+    x = fb.rnd(2, h, w, seed=42)
+    ref, bound = fb.bilinear_ref_bound(x, H, W, one_minus)
+    return fb.assert_within(emu_bilinear(x, H, W, one_minus, mutant), ref, bound, "bilinear_ac")
+
+
+@pytest.mark.parametrize("case", BILINEAR_CASES)
+@pytest.mark.parametrize("one_minus", [False, True])
+def test_bilinear_emulation_is_within_the_bound(case, one_minus):
+    assert _bilinear_case(*case, one_minus) <= 0.5
+
+
+@pytest.mark.parametrize("mutant", ["align_corners_false", "h_w_swapped"])
+def test_bilinear_mutant_fails(mutant):
+    _raises(_bilinear_case, 5, 9, 33, 20, False, mutant)
+
+
+def test_bilinear_reference_is_torch_interpolate_in_fp64():
+    x = fb.rnd(2, 5, 9, seed=43)
+    ref, _ = fb.bilinear_ref_bound(x, 33, 20)
+    it = torch.nn.functional.interpolate(x.double()[:, None], size=(33, 20), mode="bilinear", align_corners=True)[:, 0]
+    assert float((ref - it).abs().max()) < 1e-13
+
+
+def emu_zs(logits, mask, amap, w, mutant=None):
+    B, h, S = mask.shape[0], mask.shape[-1], amap.shape[-1]
+    d = (logits[..., 1] - logits[..., 0]).reshape(B, h, h)
+    sig = lambda v: 1.0 / (1.0 + torch.exp(-v))
+    wt = torch.tensor(w, dtype=F32)
+    geo = "align_corners_false" if mutant == "align_corners_false" else None
+    si = (emu_bilinear(sig(d), S, S, quotient=False) if mutant == "softmax_before_interpolation"
+          else sig(emu_bilinear(d, S, S, mutant=geo, quotient=False)))
+    if mutant == "overwrite":
+        return wt * sig(d), wt * si
+    return mask + wt * sig(d), amap + wt * si
+
+
+ZS_CASES = [(16, 224), (16, 16), (1, 7), (2, 3), (7, 224)]
+ZS_MUTANTS = ["align_corners_false", "softmax_before_interpolation", "overwrite"]
+
+
+def _zs_case(h, S, mutant=None):
+    lg, mask, amap = fb.zs_inputs(2, h, S, seed=44)
+    rm, em, ra, ea = fb.zs_accumulate_ref_bound(lg, mask, amap, 0.37)
+    gm, ga = emu_zs(lg, mask, amap, 0.37, mutant)
+    return max(fb.assert_within(gm, rm, em, "zs mask"), fb.assert_within(ga, ra, ea, "zs map"))
+
+
+@pytest.mark.parametrize("h,S", ZS_CASES)
+def test_zs_accumulate_emulation_is_within_the_bound(h, S):
+    assert (1e-3 if h > 1 else 0.0) <= _zs_case(h, S) <= 1.0     # h = 1: its one difference is -60, sigmoid ~ 1e-26 onto O(1)
+
+
+@pytest.mark.parametrize("mutant", ZS_MUTANTS)
+def test_zs_accumulate_mutant_fails(mutant):
+    _raises(_zs_case, 7, 224, mutant)
+
+
+def emu_rowmax(s, acc, period, w, mutant=None):
+    rows, cols = s.shape
+    c = torch.arange(cols)
+    keep = (c % period != 0) if period > 0 else torch.ones(cols, dtype=torch.bool)
+    if mutant == "column_0_kept":
+        keep[0] = True
+    if mutant == "only_first_64":
+        keep = keep & (c < 64)
+    m = s.masked_fill(~keep[None], float("-inf")).amax(1) if cols else torch.full((rows,), float("-inf"))
+    return acc + torch.tensor(w, dtype=F32) * m
+
+
+def _rowmax_case(rows, cols, period, mutant=None):
+    full, acc = fb.rowmax_inputs(rows, cols, cols + 8, seed=45)
+    ref, bound = fb.rowmax_skip_ref_bound(full[:, :cols], acc, period, 0.61)
+    return fb.rowmax_check(emu_rowmax(full[:, :cols], acc, period, 0.61, mutant), ref, bound)
+
+
+@pytest.mark.parametrize("cols", [1, 63, 64, 65, 514])
+@pytest.mark.parametrize("period", [0, 257, 5])
+def test_rowmax_emulation_is_within_the_bound(cols, period):
+    _rowmax_case(7, cols, period)          # an accumulate form: the bound is its two roundings and nothing else
+
+
+@pytest.mark.parametrize("mutant", ["column_0_kept", "only_first_64"])
+def test_rowmax_mutant_fails(mutant):
+    _raises(_rowmax_case, 7, 514, 257, mutant)
