@@ -313,10 +313,17 @@ int mh_launch_gemm_256(const void* A, int lda, const void* B, int ldb, void* C, 
                        const float* bias, const float* residual, int ldr, int flags, float alpha, int splits, int tps,
                        long split_stride, hipStream_t stream, void* aux = nullptr, int ldaux = 0);
 
+// (defined below: dispatch stays the first user, so the kernel instances are emitted in the order they always were)
+static int launch_variant(int variant, const GemmArgs& g, hipStream_t stream);
+
 static int dispatch(const GemmArgs& g, hipStream_t stream) {
-  int variant = (g.flags >> MH_GEMM_VARIANT_SHIFT) & 15;
+  const int variant = (g.flags >> MH_GEMM_VARIANT_SHIFT) & 15;
   if (g.flags & MH_GEMM_REGSTAGE) return launch_gemm<1, 2, 128, 2>(g, stream);
-  if (variant == 0) variant = 1;   // measured best on every shape of the step (profiles/r01_gemm_variants.md)
+  return launch_variant(variant ? variant : 1, g, stream);   // 0 -> 1: measured best on every shape of the step (profiles/r01_gemm_variants.md)
+}
+
+// forced-variant number -> kernel instance: the one map, for unsplit launches (dispatch) and K-split ones (run_splitk)
+static int launch_variant(int variant, const GemmArgs& g, hipStream_t stream) {
   switch (variant) {
     case 1: return launch_gemm<0, 2, 128, 2>(g, stream);   // 64 KiB, 2 blocks/CU
     case 2: return launch_gemm<0, 4, 128, 1>(g, stream);   // 128 KiB, 1 block/CU, 3 tiles in flight
@@ -498,38 +505,33 @@ __global__ __launch_bounds__(256, NIT <= 4 ? 5 : 2) void splitk_reduce_norm_kern
   }
 }
 
+// What a product left for the kernel that reads it: `nslab` partial slabs of [M, N], `slab` elements apart (split-K, in the
+// workspace), or one dense matrix (nslab 1, slab 0); bf16 or fp32 elements.
+struct Product { const void* p; int bf16; int nslab; long slab; };
+
 // Slabs of the 256x256 kernel and of the 160-row tiles are bf16 (MYRIAD_SLAB_BF16=0: fp32): these are the K <= 22016 forward / dgrad products of the
 // LLaMA and ViT Linears, whose results are rounded to bf16 (or added to the fp32 residual stream) anyway; the partial sums cost
 // 2 x 4 B per output element per split in fp32 -- 9 GB per step at batch 8.  The 128x128 kernel's slabs (weight gradients: long
-// cancelling reductions over tokens) stay fp32.  *slab_bf16 tells the caller which it got.
-
-static int run_splitk(const GemmArgs& g0, int splits, float* ws, hipStream_t stream, bool reduce = true, int* slab_bf16 = nullptr) {
+// cancelling reductions over tokens) stay fp32.
+// The one place that settles the split count (no empty split).  slabs != NULL: the caller's kernel sums the slabs itself -- no
+// reduce launch, *slabs says what was written.
+static int run_splitk(const GemmArgs& g0, int splits, float* ws, hipStream_t stream, Product* slabs = nullptr) {
   const int g_slab_bf16 = mh_opt(MH_OPT_SLAB_BF16);
   const int nt = g0.K / 64;
   if (splits > nt) splits = nt;
   const int tps = (nt + splits - 1) / splits;
   splits = (nt + tps - 1) / tps;
-  const int var0 = (g0.flags >> MH_GEMM_VARIANT_SHIFT) & 15;
-  const bool big = var0 == 12;
-  const bool row_tile = var0 == 14 || var0 == 15;       // the 160-row tiles (batch-1 step): the same forward / dgrad products
-  const int sbf = ((big || row_tile) && g_slab_bf16 && (g0.N % 8) == 0) ? 1 : 0;
-  if (slab_bf16) *slab_bf16 = sbf;
+  const int var = (g0.flags >> MH_GEMM_VARIANT_SHIFT) & 15;
+  // the 256x256 kernel and the 160-row tiles (batch-1 step: the same forward / dgrad products) split K themselves; a K-split
+  // launch of any other variant runs on the 128x128 instance (gemm_plan reports it so)
+  const bool own_tile = var == 12 || var == 14 || var == 15;
+  const int sbf = (own_tile && g_slab_bf16 && (g0.N % 8) == 0) ? 1 : 0;
   GemmArgs g = g0;
   g.C = (void*)ws; g.ldc = g0.N; g.bias = nullptr; g.residual = nullptr; g.ldr = 0;
   g.flags = (sbf ? 0 : MH_GEMM_OUT_F32) | (g0.flags & MH_GEMM_PACKED_B); g.alpha = 1.0f; g.splits = splits; g.tps = tps; g.split_stride = (long)g0.M * g0.N;
-  int rc;
-  const int var = (g0.flags >> MH_GEMM_VARIANT_SHIFT) & 15;
-  if (big)
-    rc = mh_launch_gemm_256(g.A, g.lda, g.B, g.ldb, g.C, g.ldc, g.M, g.N, g.K, nullptr, nullptr, 0, g.flags, 1.0f,
-                            g.splits, g.tps, g.split_stride, stream);
-  else if (var == 14)
-    rc = launch_gemm<0, 4, 128, 1, 64, 4, 160>(g, stream);
-  else if (var == 15)
-    rc = launch_gemm<0, 4, 96, 1, 64, 4, 160>(g, stream);
-  else
-    rc = launch_gemm<0, 2, 128, 2>(g, stream);
+  const int rc = launch_variant(own_tile ? var : 1, g, stream);
   if (rc) return rc;
-  if (!reduce) return MH_OK;                        // the caller consumes the slabs itself
+  if (slabs) { *slabs = {ws, sbf, splits, g.split_stride}; return MH_OK; }
   long gsz = ((long)g0.M * g0.N / 4 + 255) / 256;
   if (gsz > 4096) gsz = 4096;
   if (sbf)
@@ -756,6 +758,27 @@ extern "C" int mh_gemm_bf16_nt(const void* A, int lda, const void* B, int ldb, v
   return dispatch(g, stream);
 }
 
+// The planned product A.B^T [M, N] for an entry whose next kernel can sum split-K slabs itself.  When the policy splits K and the
+// entry may read slabs (`slabs_ok`: its own shape / alignment conditions), the partial slabs stay in the stream's workspace and
+// no reduce is launched; otherwise the product goes through mh_gemm_bf16_nt -- which may itself split and reduce, and carries the
+// debug flags (the slab launch does not) -- into the dense C [M, ldc], fp32 (`c_f32`) or bf16, with bias / residual in its
+// epilogue (a slab consumer applies its own).  *pr says which: pr->slab != 0 means slabs.  gemm_plan reads none of the output
+// flags, so one plan serves every entry.
+static int planned_product(const void* A, int lda, const void* B, int ldb, void* C, int ldc, bool c_f32, const float* bias,
+                           const float* residual, int ldr, bool slabs_ok, int M, int N, int K, hipStream_t stream, Product* pr) {
+  int kernel = 1, splits = 1;
+  if (K > 0) gemm_plan(M, N, K, 0, &kernel, &splits);
+  if (slabs_ok && splits > 1 && kernel != 0 && (K % 64) == 0 && (lda % 8) == 0 && (ldb % 8) == 0 &&
+      !(((uintptr_t)A | (uintptr_t)B) & 15)) {
+    GemmArgs g = {A, lda, B, ldb, nullptr, N, M, N, K, nullptr, nullptr, 0, plan_variant(kernel) << MH_GEMM_VARIANT_SHIFT, 1.0f,
+                  1, K / 64, 0L};
+    return run_splitk(g, splits, ws_for(stream), stream, pr);
+  }
+  if (!C) return MH_ERR_ARG;
+  *pr = {C, c_f32 ? 0 : 1, 1, 0L};
+  return mh_gemm_bf16_nt(A, lda, B, ldb, C, ldc, M, N, K, bias, residual, ldr, c_f32 ? MH_GEMM_OUT_F32 : 0, 1.0f, stream);
+}
+
 extern "C" int mh_rmsnorm_fwd(const float* x, const float* w, void* y_bf16, long ldy, int M, int D, float eps, hipStream_t stream);
 extern "C" int mh_layernorm_fwd(const float* x, const float* w, const float* b, void* y_bf16, float* y_f32, int M, int D,
                                 float eps, hipStream_t stream);
@@ -766,34 +789,23 @@ static int gemm_residual_norm(int norm, const void* A, int lda, const void* B, i
                               long ldy, int M, int N, int K, hipStream_t stream) {
   if (M <= 0 || N <= 0) return MH_OK;
   if (!norm_w || !H || !Y || (N % 4) != 0 || (ldy % 4) != 0 || (norm == 1 && (!norm_b || ldy != N))) return MH_ERR_ARG;
-  int kernel = 1, splits = 1;
-  if (K > 0) gemm_plan(M, N, K, MH_GEMM_OUT_F32, &kernel, &splits);
-  if (splits > 1 && kernel != 0 && N <= 8192 && (ldh % 4) == 0 && (!residual || (ldr % 4) == 0) && (K % 64) == 0 &&
-      (lda % 8) == 0 && (ldb % 8) == 0 && !(((uintptr_t)A | (uintptr_t)B | (uintptr_t)H) & 15)) {
-    GemmArgs g = {A, lda, B, ldb, (void*)H, ldh, M, N, K, nullptr, residual, ldr, MH_GEMM_OUT_F32, 1.0f, 1, K / 64, 0L};
-    g.flags |= plan_variant(kernel) << MH_GEMM_VARIANT_SHIFT;
-    const int nt = K / 64;                          // the split count run_splitk will settle on
-    int sp = splits > nt ? nt : splits;
-    const int tps = (nt + sp - 1) / sp;
-    sp = (nt + tps - 1) / tps;
-    float* wsp = ws_for(stream);
-    int sbf = 0;
-    int rc = run_splitk(g, splits, wsp, stream, /*reduce=*/false, &sbf);
-    if (rc) return rc;
+  Product pr;
+  const bool slabs_ok = N <= 8192 && (ldh % 4) == 0 && (!residual || (ldr % 4) == 0) && !((uintptr_t)H & 15);
+  const int rc = planned_product(A, lda, B, ldb, H, ldh, true, bias, residual, ldr, slabs_ok, M, N, K, stream, &pr);
+  if (rc) return rc;
+  if (pr.slab) {
 #define RN_LAUNCH1(NORM_, SBF_, NIT_)                                                                                       \
-  hipLaunchKernelGGL((splitk_reduce_norm_kernel<NORM_, SBF_, NIT_>), dim3(M), dim3(256), 0, stream, (const void*)wsp, bias, residual, H, \
-                     norm_w, norm_b, (bf16_t*)Y, N, (long)ldr, (long)ldh, ldy, (long)M * N, sp, eps)
+  hipLaunchKernelGGL((splitk_reduce_norm_kernel<NORM_, SBF_, NIT_>), dim3(M), dim3(256), 0, stream, pr.p, bias, residual, H,            \
+                     norm_w, norm_b, (bf16_t*)Y, N, (long)ldr, (long)ldh, ldy, pr.slab, pr.nslab, eps)
 #define RN_LAUNCH(NORM_, SBF_)                                                                                              \
   do { if (N <= 4096) RN_LAUNCH1(NORM_, SBF_, 4); else RN_LAUNCH1(NORM_, SBF_, 8); } while (0)
-    if (norm == 0) { if (sbf) RN_LAUNCH(0, 1); else RN_LAUNCH(0, 0); }
-    else { if (sbf) RN_LAUNCH(1, 1); else RN_LAUNCH(1, 0); }
+    if (norm == 0) { if (pr.bf16) RN_LAUNCH(0, 1); else RN_LAUNCH(0, 0); }
+    else { if (pr.bf16) RN_LAUNCH(1, 1); else RN_LAUNCH(1, 0); }
 #undef RN_LAUNCH
 #undef RN_LAUNCH1
     MH_CHECK_LAUNCH();
     return MH_OK;
   }
-  int rc = mh_gemm_bf16_nt(A, lda, B, ldb, H, ldh, M, N, K, bias, residual, ldr, MH_GEMM_OUT_F32, 1.0f, stream);
-  if (rc) return rc;
   if (ldh != N) return MH_ERR_ARG;                  // the norm kernels read a dense [M, N] stream
   if (norm == 0) return mh_rmsnorm_fwd(H, norm_w, Y, ldy, M, N, eps, stream);
   return mh_layernorm_fwd(H, norm_w, norm_b, Y, nullptr, M, N, eps, stream);
@@ -822,25 +834,10 @@ extern "C" int mh_gemm_rmsnorm_bwd(const void* A, int lda, const void* B, int ld
                                    hipStream_t stream) {
   if (M <= 0 || N <= 0) return MH_OK;
   if (!dy_buf || !x || !w || (N % 4) != 0 || N > 8192) return MH_ERR_ARG;
-  int kernel = 1, splits = 1;
-  if (K > 0) gemm_plan(M, N, K, MH_GEMM_OUT_F32, &kernel, &splits);
-  if (splits > 1 && kernel != 0 && (K % 64) == 0 && (lda % 8) == 0 && (ldb % 8) == 0 &&
-      !(((uintptr_t)A | (uintptr_t)B) & 15)) {
-    GemmArgs g = {A, lda, B, ldb, (void*)dy_buf, N, M, N, K, nullptr, nullptr, 0, MH_GEMM_OUT_F32, 1.0f, 1, K / 64, 0L};
-    g.flags |= plan_variant(kernel) << MH_GEMM_VARIANT_SHIFT;
-    const int nt = K / 64;                          // the split count run_splitk will settle on
-    int sp = splits > nt ? nt : splits;
-    const int tps = (nt + sp - 1) / sp;
-    sp = (nt + tps - 1) / tps;
-    float* wsp = ws_for(stream);
-    int sbf = 0;
-    const int rc = run_splitk(g, splits, wsp, stream, /*reduce=*/false, &sbf);
-    if (rc) return rc;
-    return mh_launch_rmsnorm_bwd(wsp, sbf, sp, (long)M * N, N, x, w, dres, dx, dx_bf16, M, N, eps, stream);
-  }
-  const int rc = mh_gemm_bf16_nt(A, lda, B, ldb, dy_buf, N, M, N, K, nullptr, nullptr, 0, MH_GEMM_OUT_F32, 1.0f, stream);
+  Product pr;
+  const int rc = planned_product(A, lda, B, ldb, dy_buf, N, true, nullptr, nullptr, 0, true, M, N, K, stream, &pr);
   if (rc) return rc;
-  return mh_launch_rmsnorm_bwd(dy_buf, 0, 1, 0, N, x, w, dres, dx, dx_bf16, M, N, eps, stream);
+  return mh_launch_rmsnorm_bwd(pr.p, pr.bf16, pr.nslab, pr.slab, N, x, w, dres, dx, dx_bf16, M, N, eps, stream);
 }
 
 int mh_launch_layernorm_bwd(const void* dy, int slab_bf16, int nslab, long slab, long ldy, const float* x, const float* w,
@@ -865,28 +862,14 @@ extern "C" int mh_gemm_layernorm_bwd(const void* A, int lda, const void* B, int 
   if (!dy_buf || !x || !w || (N % 4) != 0 || N > 8192) return MH_ERR_ARG;
   const bool params = dgamma != nullptr;
   if (params && (!dbeta || N > 4096 || !ws || ws_floats < mh_layernorm_param_grads_ws_floats(M, N))) return MH_ERR_ARG;
-  int kernel = 1, splits = 1;
-  if (K > 0) gemm_plan(M, N, K, MH_GEMM_OUT_F32, &kernel, &splits);
-  int rc;
-  if (splits > 1 && kernel != 0 && (K % 64) == 0 && (lda % 8) == 0 && (ldb % 8) == 0 &&
-      !(((uintptr_t)A | (uintptr_t)B) & 15)) {
-    GemmArgs g = {A, lda, B, ldb, (void*)dy_buf, N, M, N, K, nullptr, nullptr, 0, MH_GEMM_OUT_F32, 1.0f, 1, K / 64, 0L};
-    g.flags |= plan_variant(kernel) << MH_GEMM_VARIANT_SHIFT;
-    const int nt = K / 64;                          // the split count run_splitk will settle on
-    int sp = splits > nt ? nt : splits;
-    const int tps = (nt + sp - 1) / sp;
-    sp = (nt + tps - 1) / tps;
-    float* wsp = ws_for(stream);
-    int sbf = 0;
-    rc = run_splitk(g, splits, wsp, stream, /*reduce=*/false, &sbf);
-    if (rc) return rc;
-    rc = mh_launch_layernorm_bwd(wsp, sbf, sp, (long)M * N, N, x, w, dres, dx, dx_bf16, params ? dy_buf : nullptr, M, N, eps,
+  Product pr;
+  int rc = planned_product(A, lda, B, ldb, dy_buf, N, true, nullptr, nullptr, 0, true, M, N, K, stream, &pr);
+  if (rc) return rc;
+  if (pr.slab)
+    rc = mh_launch_layernorm_bwd(pr.p, pr.bf16, pr.nslab, pr.slab, N, x, w, dres, dx, dx_bf16, params ? dy_buf : nullptr, M, N, eps,
                                  stream);
-  } else {
-    rc = mh_gemm_bf16_nt(A, lda, B, ldb, dy_buf, N, M, N, K, nullptr, nullptr, 0, MH_GEMM_OUT_F32, 1.0f, stream);
-    if (rc) return rc;
+  else
     rc = mh_layernorm_bwd(dy_buf, x, w, dres, dx, dx_bf16, M, N, eps, stream);
-  }
   if (rc || !params) return rc;
   return mh_layernorm_param_grads(dy_buf, x, dgamma, dbeta, M, N, eps, accumulate, 0.f, 0ULL, ws, ws_floats, stream);
 }
@@ -905,26 +888,11 @@ extern "C" int mh_gemm_lora_dx(const void* A, int lda, const void* Bw, int ldb, 
   if (M <= 0) return MH_OK;
   const int N = D + 64;
   if (!loraA || !dxn || D <= 0 || (D % 4) != 0) return MH_ERR_ARG;
-  int kernel = 1, splits = 1;
-  if (K > 0) gemm_plan(M, N, K, MH_GEMM_OUT_F32, &kernel, &splits);
-  if (splits > 1 && kernel != 0 && border_out && (K % 64) == 0 && (lda % 8) == 0 && (ldb % 8) == 0 &&
-      !(((uintptr_t)A | (uintptr_t)Bw) & 15)) {
-    GemmArgs g = {A, lda, Bw, ldb, (void*)dx_ext_buf, N, M, N, K, nullptr, nullptr, 0, MH_GEMM_OUT_F32, 1.0f, 1, K / 64, 0L};
-    g.flags |= plan_variant(kernel) << MH_GEMM_VARIANT_SHIFT;
-    const int nt = K / 64;                          // the split count run_splitk will settle on
-    int sp = splits > nt ? nt : splits;
-    const int tps = (nt + sp - 1) / sp;
-    sp = (nt + tps - 1) / tps;
-    float* wsp = ws_for(stream);
-    int sbf = 0;
-    const int rc = run_splitk(g, splits, wsp, stream, /*reduce=*/false, &sbf);
-    if (rc) return rc;
-    return mh_launch_lora_dx(wsp, sbf, N, sp, (long)M * N, loraA, dxn, border_out, M, D, R2, s, p, seed, stream);
-  }
-  if (!dx_ext_buf) return MH_ERR_ARG;
-  const int rc = mh_gemm_bf16_nt(A, lda, Bw, ldb, dx_ext_buf, N, M, N, K, nullptr, nullptr, 0, MH_GEMM_OUT_F32, 1.0f, stream);
+  Product pr;
+  const int rc = planned_product(A, lda, Bw, ldb, dx_ext_buf, N, true, nullptr, nullptr, 0, border_out != nullptr, M, N, K, stream, &pr);
   if (rc) return rc;
-  return mh_launch_lora_dx(dx_ext_buf, 0, N, 1, 0, loraA, dxn, nullptr, M, D, R2, s, p, seed, stream);
+  return mh_launch_lora_dx(pr.p, pr.bf16, N, pr.nslab, pr.slab, loraA, dxn, pr.slab ? border_out : nullptr, M, D, R2, s, p, seed,
+                           stream);
 }
 
 int mh_launch_lora_dx_rmsnorm_bwd(const void* dx_ext, int slab_bf16, long ld, int nslab, long slab, const float* A, const float* x,
@@ -942,36 +910,17 @@ extern "C" int mh_gemm_lora_rmsnorm_bwd(const void* A, int lda, const void* Bw, 
   if (M <= 0) return MH_OK;
   const int N = D + 64;
   if (!loraA || !x || !w || D <= 0 || (D % 4) != 0) return MH_ERR_ARG;
-  int kernel = 1, splits = 1;
-  if (K > 0) gemm_plan(M, N, K, MH_GEMM_OUT_F32, &kernel, &splits);
-  const void* prod = dx_ext_buf;
-  int sbf = 0, sp = 1;
-  long slab = 0;
-  float* bout = nullptr;
-  if (splits > 1 && kernel != 0 && border_out && (K % 64) == 0 && (lda % 8) == 0 && (ldb % 8) == 0 &&
-      !(((uintptr_t)A | (uintptr_t)Bw) & 15)) {
-    GemmArgs g = {A, lda, Bw, ldb, (void*)dx_ext_buf, N, M, N, K, nullptr, nullptr, 0, MH_GEMM_OUT_F32, 1.0f, 1, K / 64, 0L};
-    g.flags |= plan_variant(kernel) << MH_GEMM_VARIANT_SHIFT;
-    const int nt = K / 64;                          // the split count run_splitk will settle on
-    sp = splits > nt ? nt : splits;
-    const int tps = (nt + sp - 1) / sp;
-    sp = (nt + tps - 1) / tps;
-    float* wsp = ws_for(stream);
-    const int rc = run_splitk(g, splits, wsp, stream, /*reduce=*/false, &sbf);
-    if (rc) return rc;
-    prod = wsp; slab = (long)M * N; bout = border_out;
-  } else {
-    if (!dx_ext_buf) return MH_ERR_ARG;
-    const int rc = mh_gemm_bf16_nt(A, lda, Bw, ldb, dx_ext_buf, N, M, N, K, nullptr, nullptr, 0, MH_GEMM_OUT_F32, 1.0f, stream);
-    if (rc) return rc;
-  }
+  Product pr;
+  int rc = planned_product(A, lda, Bw, ldb, dx_ext_buf, N, true, nullptr, nullptr, 0, border_out != nullptr, M, N, K, stream, &pr);
+  if (rc) return rc;
+  float* bout = pr.slab ? border_out : nullptr;
   if (mh_opt(MH_OPT_LORA_NORM_FUSED)) {
-    const int rc = mh_launch_lora_dx_rmsnorm_bwd(prod, sbf, N, sp, slab, loraA, x, w, dres, dx, dx_bf16, bout, M, D, R2, s, p, seed,
-                                                 eps, stream);
+    rc = mh_launch_lora_dx_rmsnorm_bwd(pr.p, pr.bf16, N, pr.nslab, pr.slab, loraA, x, w, dres, dx, dx_bf16, bout, M, D, R2, s, p, seed,
+                                       eps, stream);
     if (rc != MH_ERR_UNSUPPORTED) return rc;
   }
   if (!dxn_buf) return MH_ERR_ARG;
-  const int rc = mh_launch_lora_dx(prod, sbf, N, sp, slab, loraA, dxn_buf, bout, M, D, R2, s, p, seed, stream);
+  rc = mh_launch_lora_dx(pr.p, pr.bf16, N, pr.nslab, pr.slab, loraA, dxn_buf, bout, M, D, R2, s, p, seed, stream);
   if (rc) return rc;
   return mh_launch_rmsnorm_bwd(dxn_buf, 0, 1, 0, D, x, w, dres, dx, dx_bf16, M, D, eps, stream);
 }
@@ -992,27 +941,11 @@ extern "C" int mh_gemm_attn_rope_bwd(const void* A, int lda, const void* Bw, int
   const int M = B * S, N = H * D;
   if (M <= 0 || N <= 0) return MH_OK;
   if (!do_buf) return MH_ERR_ARG;
-  int kernel = 1, splits = 1;
-  if (K > 0) gemm_plan(M, N, K, MH_GEMM_OUT_F32, &kernel, &splits);
-  if (splits > 1 && kernel != 0 && (K % 64) == 0 && (lda % 8) == 0 && (ldb % 8) == 0 && (N % 8) == 0 &&
-      !(((uintptr_t)A | (uintptr_t)Bw) & 15)) {
-    GemmArgs g = {A, lda, Bw, ldb, do_buf, N, M, N, K, nullptr, nullptr, 0, MH_GEMM_OUT_F32, 1.0f, 1, K / 64, 0L};
-    g.flags |= plan_variant(kernel) << MH_GEMM_VARIANT_SHIFT;
-    const int nt = K / 64;                          // the split count run_splitk will settle on
-    int sp = splits > nt ? nt : splits;
-    const int tps = (nt + sp - 1) / sp;
-    sp = (nt + tps - 1) / tps;
-    float* wsp = ws_for(stream);
-    int sbf = 0;
-    const int rc = run_splitk(g, splits, wsp, stream, /*reduce=*/false, &sbf);
-    if (rc) return rc;
-    return mh_launch_attn_rope_bwd(qkv, ld, o, ldo, wsp, sbf, sp, (long)M * N, N, lse, dqkv, pos, cos_tab, sin_tab, kv_len, B, H, S,
-                                   D, scale, stream);
-  }
-  const int rc = mh_gemm_bf16_nt(A, lda, Bw, ldb, do_buf, N, M, N, K, nullptr, nullptr, 0, 0, 1.0f, stream);
+  Product pr;
+  const int rc = planned_product(A, lda, Bw, ldb, do_buf, N, false, nullptr, nullptr, 0, (N % 8) == 0, M, N, K, stream, &pr);
   if (rc) return rc;
-  return mh_launch_attn_rope_bwd(qkv, ld, o, ldo, do_buf, 1, 1, 0, N, lse, dqkv, pos, cos_tab, sin_tab, kv_len, B, H, S, D, scale,
-                                 stream);
+  return mh_launch_attn_rope_bwd(qkv, ld, o, ldo, pr.p, pr.bf16, pr.nslab, pr.slab, N, lse, dqkv, pos, cos_tab, sin_tab, kv_len, B, H,
+                                 S, D, scale, stream);
 }
 
 // ---- SiLU-gated MLP (modeling_llama.py:139-140) fused into the two GEMMs around it -------------------------------------------
@@ -1086,27 +1019,11 @@ extern "C" int mh_gemm_swiglu_bwd(const void* dH, int lddh, const void* WdT, int
     return mh_launch_gemm_256(dH, lddh, WdT, ldw, dgu, lddgu, M, I, K, nullptr, nullptr, 0, MH_GEMM_SWIGLU_BWD, 1.0f, 1, K / 64,
                               0L, stream, const_cast<void*>(gu), ldgu);
   if (!dact_buf || ldgu != 2 * I || lddgu != 2 * I) return MH_ERR_ARG;
-  {
-    // K-split product (the batch-1 step's 160-row tiles): the gate backward sums the slabs itself -- no reduce launch, same bits
-    int kernel = 1, splits = 1;
-    gemm_plan(M, I, K, 0, &kernel, &splits);
-    if (splits > 1 && kernel != 0 && (I % 8) == 0 && (K % 64) == 0 && (lddh % 8) == 0 && (ldw % 8) == 0 &&
-        !(((uintptr_t)dH | (uintptr_t)WdT) & 15)) {
-      GemmArgs g = {dH, lddh, WdT, ldw, dact_buf, I, M, I, K, nullptr, nullptr, 0, 0, 1.0f, 1, K / 64, 0L};
-      g.flags |= plan_variant(kernel) << MH_GEMM_VARIANT_SHIFT;
-      const int nt = K / 64;
-      int sp = splits > nt ? nt : splits;
-      const int tps = (nt + sp - 1) / sp;
-      sp = (nt + tps - 1) / tps;
-      float* wsp = ws_for(stream);
-      int sbf = 0;
-      const int rc = run_splitk(g, splits, wsp, stream, /*reduce=*/false, &sbf);
-      if (rc) return rc;
-      return mh_launch_silu_mul_bwd_slabs(wsp, sbf, sp, (long)M * I, gu, dgu, M, I, 128, stream);
-    }
-  }
-  const int rc = mh_gemm_bf16_nt(dH, lddh, WdT, ldw, dact_buf, I, M, I, K, nullptr, nullptr, 0, 0, 1.0f, stream);
+  // K-split product (the batch-1 step's 160-row tiles): the gate backward sums the slabs itself -- no reduce launch, same bits
+  Product pr;
+  const int rc = planned_product(dH, lddh, WdT, ldw, dact_buf, I, false, nullptr, nullptr, 0, (I % 8) == 0, M, I, K, stream, &pr);
   if (rc) return rc;
+  if (pr.slab) return mh_launch_silu_mul_bwd_slabs(pr.p, pr.bf16, pr.nslab, pr.slab, gu, dgu, M, I, 128, stream);
   return mh_silu_mul_bwd_blk(dact_buf, gu, dgu, M, I, 128, stream);
 }
 

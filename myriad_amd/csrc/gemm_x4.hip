@@ -1,21 +1,26 @@
-// K1, four-wave form of the 256 x 256 tile (round 4): BK = 64, two 64-KiB LDS buffers, ONE wave per SIMD owning a 128 x 128
-// sub-tile (8 x 8 fragments of mfma_f32_16x16x32_bf16, 256 accumulator registers in the AGPR half of the unified file), the
-// whole K loop one hand-scheduled instruction stream (gemm_x4_loop.inc, written by gen_gemm_x4.py: MFMA slots with the
-// fragment reads, the LDS-DMA requests, two counted waits and two barriers per 128 MFMAs pinned behind them).
+// K1, the 256 x 256 tile as a hand-scheduled 64-deep loop (round 4): BK = 64, two 64-KiB LDS buffers, 8 waves = 2 x 4 (two per
+// SIMD), each owning a 128 x 64 sub-tile (8 x 4 fragments of mfma_f32_16x16x32_bf16: 128 accumulator registers in the AGPR half
+// of the unified file beside 108 VGPRs), the whole K loop one hand-scheduled instruction stream (gemm_x4_loop.inc, written by
+// gen_gemm_x4.py: per wave and k-tile 64 MFMA slots with the fragment reads, the wave's 4 + 4 of the k-tile's 64 LDS-DMA
+// requests, two counted waits and two barriers pinned behind them).
 //
-// Why (profiles/r04_gemm_x4.md): the eight-wave kernel (gemm_256.hip) reads 96 KiB of fragments out of LDS per 32-KiB k-tile
-// and lands at 0.75 us per 32-deep k-tile whatever is done to its schedule (rounds 2-3); with 128 x 128 per wave every
-// fragment is read twice instead of four / two times (64 KiB), a 64-deep k-tile makes every LDS-DMA request eight whole
-// 128-byte lines, and requests are `buffer_load_dwordx4 ... lds` with one address VGPR each and a shared scalar k offset
-// (no per-request 64-bit address arithmetic).  Round 3's four-wave attempt left the order to the compiler and lost; here the
-// order is written down.
+// Why (profiles/r04_gemm_x4.md): the 32-deep kernel (gemm_256.hip) lands at 0.75 us per 32-deep k-tile whatever is done to its
+// schedule (rounds 2-3); a 64-deep k-tile makes every LDS-DMA request eight whole 128-byte lines, and requests are
+// `buffer_load_dwordx4 ... lds` with one address VGPR each and a shared scalar k offset (no per-request 64-bit address
+// arithmetic).  Round 3's attempt at this structure left the order to the compiler and lost; here the order is written down.
+//
+// The x4 in the names: the loop was first written for four waves (2 x 2, 128 x 128 per wave, one wave per SIMD).  That form
+// reached the loop rate but cost twice as much outside the loop, and what one wave cannot hide under its own MFMAs -- the issue
+// time of its LDS-DMA requests (~60 cycles each) and fragment reads -- a SIMD's second wave fills: the eight-wave form won on
+// every shape of the step, so the four-wave kernel was never instantiated in the library and has been dropped (its numbers
+// and knock-outs: profiles/r04_gemm_x4.md).
 //
 // LDS image of a buffer: [A: 256 rows x 128 B | B: 256 rows x 128 B]; row r keeps its eight 16-byte chunks at physical
 // position c ^ ((r >> 1) & 7): a ds_read_b128 lane group (16 lanes: rows {0-3, 12-15} at chunk c and rows {4-11} at chunk
 // c ^ 1, MI355X_MICROARCH.md LDS table) then touches 16 distinct 16-byte slots of the 256-byte bank row -- conflict-free --
 // and the LDS-DMA, which writes lane-linearly, gets the same permutation on its per-lane SOURCE chunk (whole lines either way).
-// Request i of wave w covers rows (w + 4 i) * 8 .. + 7: the swizzle term ((row >> 1) & 7) = 4 (w & 1) + (lane >> 4) does not
-// depend on i, and m0 advances by 4096 per request.
+// Request i of wave w covers rows (w + 8 i) * 8 .. + 7: the swizzle term ((row >> 1) & 7) = 4 (w & 1) + (lane >> 4) does not
+// depend on i, and m0 advances by 8192 per request.
 //
 // Same k order per output element as gemm_256.hip / gemm.hip (32-deep MFMA steps in ascending k): results are bit-identical.
 #include "common.h"
@@ -46,23 +51,8 @@ typedef __attribute__((ext_vector_type(4))) int int4v_t;
 
 #include "gemm_x4_loop.inc"
 
-// the K loop: outputs = the 8 x 32 accumulator registers; in/out = the registers the loop advances; inputs pinned where the
-// instruction stream names them (gen_gemm_x4.py: register map)
-#define X4_ASM(LOOP)                                                                                                            \
-  asm volatile(LOOP                                                                                                             \
-               : "={a[0:31]}"(c[0]), "={a[32:63]}"(c[1]), "={a[64:95]}"(c[2]), "={a[96:127]}"(c[3]), "={a[128:159]}"(c[4]),     \
-                 "={a[160:191]}"(c[5]), "={a[192:223]}"(c[6]), "={a[224:255]}"(c[7]), "+{v144}"(ra0), "+{v145}"(ra1),           \
-                 "+{v146}"(rb0), "+{v147}"(rb1), "+{s44}"(koff), "+{s45}"(cnt), "+{s46}"(wr)                                    \
-               : "{v[128:135]}"(voa), "{v[136:143]}"(vob), "{s[36:39]}"(sa), "{s[40:43]}"(sb)                                   \
-               /* m0 is written inside (24 times) but cannot be named here: it is a RESERVED register to the compiler ('inline asm
-                  clobber list contains reserved registers: m0'), which never keeps a value live in it across a statement and
-                  sets it up again in front of each of its own uses (LDS-DMA, movrel, sendmsg) -- ADVICE r4 */ \
-               : "memory", "scc", "v0", "v1", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", X4_CLOB8(1), X4_CLOB8(2),         \
-                 X4_CLOB8(3), X4_CLOB8(4), X4_CLOB8(5), X4_CLOB8(6), X4_CLOB8(7), X4_CLOB8(8), X4_CLOB8(9), X4_CLOB8(10),       \
-                 X4_CLOB8(11), "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127")
-
 // Read-out of one 64 x 64 block of a wave's tile from its LDS slice `ep` ([64 rows][16 chunks of 16 B], chunk ^= row & 15, fp32,
-// un-scaled accumulators) to global memory, shared by the four- and eight-wave forms; the same expressions as gemm_256.hip's
+// un-scaled accumulators) to global memory; the same expressions as gemm_256.hip's
 // epilogue (alpha applied here, on the way out of LDS).  mbase: global row of the block's row 0; wc: the block's 64-column
 // index inside the 256-column tile.  SwiGLU forward pairs the wave holding gate columns (slice g_slice) with the one holding
 // the matching up columns (g_slice + u_step); each turns rows pair_half * 32 .. + 31 into act columns (n0 / 2) + act_cb * 64 ..
@@ -311,115 +301,11 @@ __device__ __forceinline__ void x_readout(char* smem, char* ep, int lane, int mb
   }
 }
 
-template <int V>
-__global__ __launch_bounds__(256) void gemm_x4_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, void* Cv,
-                                                      const float* __restrict__ bias, const float* res, int M, int N, int K,
-                                                      int lda, int ldb, int ldc, int ldr, int flags, float alpha, int tiles_m,
-                                                      int kt_per_split, long split_stride, void* aux, int ldaux) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];   // [2 buffers][A 32K | B 32K]; reused by the epilogue
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int lr = lane & 15, lg = lane >> 4;
-
-  // tile order of gemm_256.hip: an XCD's concurrent workgroups walk 8 tile-rows before the next tile-column
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-  const int lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  const int tiles_n = nwg / tiles_m;
-  const int per_group = 8 * tiles_n;
-  const int first_m = (lid / per_group) * 8;
-  const int gsz = (tiles_m - first_m) < 8 ? (tiles_m - first_m) : 8;
-  const int tm = first_m + (lid % per_group) % gsz, tn = (lid % per_group) / gsz;
-  const int m0 = tm * X4_BM, n0 = tn * X4_BN;
-
-  const int nt_all = K >> 6;
-  const int kt0 = blockIdx.y * kt_per_split;
-  const int nt = (nt_all - kt0) < kt_per_split ? (nt_all - kt0) : kt_per_split;
-  if (gridDim.y > 1)
-    Cv = (flags & MH_GEMM_OUT_F32) ? (void*)(reinterpret_cast<float*>(Cv) + blockIdx.y * split_stride)
-                                   : (void*)(reinterpret_cast<bf16_t*>(Cv) + blockIdx.y * split_stride);
-
-  float32_t c[8];
-  {
-    // per-lane byte offsets of this wave's requests: request i stages rows (wave + 4 i) * 8 + (lane >> 3), the lane brings
-    // the logical chunk that belongs at physical position lane & 7 (rows past the edge re-read the last row: never stored)
-    int8v_t voa, vob;
-    // Rows past M / N: one row past the end lies outside the descriptor's range (num_records = rows * ld * 2; the scalar k offset
-    // is not part of the range check) and reads as ZERO instead of a copy of the last row.  Same results (those rows are never
-    // stored), but the MFMAs of the padding multiply zeros: the chip is power-limited under this loop, and 96 of the 1280 padded
-    // LLaMA rows doing no switching is worth 1.5-2.3 % on the M = 1184 launches (profiles/r04_gemm_x4.md).
-    const int zp = (flags & X4_F_ZERO_PAD) ? 1 : 0;
-    const int swz = (4 * (wave & 1) + (lane >> 4)) & 7;
-    const int ch = ((lane & 7) ^ swz) << 4;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int row = (wave + 4 * i) * 8 + (lane >> 3);
-      int ra = m0 + row, rb = n0 + row;
-      ra = ra < M ? ra : M - 1 + zp;               // zp: one row past the end = outside the descriptor's range: reads as zero
-      rb = rb < N ? rb : N - 1 + zp;
-      voa[i] = ra * lda * 2 + ch;
-      vob[i] = rb * ldb * 2 + ch;
-    }
-    const int sw = (lr >> 1) & 7;
-    const unsigned sbase = (unsigned)(uintptr_t)smem;
-    unsigned ra0 = sbase + (wm * 128 + lr) * 128 + ((lg ^ sw) << 4);
-    unsigned ra1 = sbase + (wm * 128 + lr) * 128 + (((4 + lg) ^ sw) << 4);
-    unsigned rb0 = sbase + X4_BREG + (wn * 128 + lr) * 128 + ((lg ^ sw) << 4);
-    unsigned rb1 = sbase + X4_BREG + (wn * 128 + lr) * 128 + (((4 + lg) ^ sw) << 4);
-    int4v_t sa, sb;
-    sa[0] = (int)(unsigned)(uintptr_t)A;
-    sa[1] = (int)((unsigned)((uintptr_t)A >> 32) & 0xffffu);
-    sa[2] = zp ? (int)((unsigned)M * (unsigned)lda * 2u) : -1;
-    sa[3] = 0x00020000;
-    sb[0] = (int)(unsigned)(uintptr_t)B;
-    sb[1] = (int)((unsigned)((uintptr_t)B >> 32) & 0xffffu);
-    sb[2] = zp ? (int)((unsigned)N * (unsigned)ldb * 2u) : -1;
-    sb[3] = 0x00020000;
-    unsigned koff = (unsigned)kt0 * 128u, cnt = (unsigned)nt, wr = sbase + wave * 1024;
-    X4_DISPATCH4(V);
-  }
-
-  // ---- epilogue: the 128 x 128 wave tile leaves in four 64 x 64 blocks (column half cb, row half h), each transposed
-  // through the wave's private 16-KiB LDS slice as gemm_256.hip does it (whole-line stores, bias / GELU / residual / SwiGLU
-  // forms on the way out).  The accumulators go to LDS straight from the AGPRs (ds_write_b128 takes accumulator data: 16
-  // instructions per block, X4_WR_n in gemm_x4_loop.inc) and the read-out is ONE runtime loop over the blocks -- the first
-  // version indexed the accumulator vectors from C++, which unrolled everything four times (24 k instructions, 256
-  // v_accvgpr_read, SGPR spills: 21 us of fixed cost per launch against the eight-wave kernel's 10.6).  alpha is applied on
-  // the way out of LDS (the same fp32 product).  The loop's last barrier sits after every wave's last fragment read and no
-  // LDS-DMA is in flight (the tail iterations request nothing), so the buffers are free.
-  char* ep = smem + wave * 16384;                      // [64 rows][16 chunks of 16 B], chunk ^= row & 15
-  // fragment (ii, jj) of a block: row ii * 16 + lr, 16-byte chunk (jj * 4 + lg) ^ lr -> one address per jj, ii in the offset
-  unsigned wa0, wa1, wa2, wa3;
-  {
-    const unsigned b0 = (unsigned)(uintptr_t)ep + lr * 256 + ((lg ^ (lr & 3)) << 4);
-    wa0 = b0 + ((0 ^ (lr >> 2)) << 6);
-    wa1 = b0 + ((1 ^ (lr >> 2)) << 6);
-    wa2 = b0 + ((2 ^ (lr >> 2)) << 6);
-    wa3 = b0 + ((3 ^ (lr >> 2)) << 6);
-  }
-#define X4_WRITE(TXT)                                                                                                        \
-  asm volatile(TXT ::"v"(wa0), "v"(wa1), "v"(wa2), "v"(wa3), "{a[0:31]}"(c[0]), "{a[32:63]}"(c[1]), "{a[64:95]}"(c[2]),      \
-               "{a[96:127]}"(c[3]), "{a[128:159]}"(c[4]), "{a[160:191]}"(c[5]), "{a[192:223]}"(c[6]), "{a[224:255]}"(c[7])   \
-               : "memory")
-#pragma unroll 1
-  for (int blk = 0; blk < 4; ++blk) {
-    const int cb = blk >> 1, h = blk & 1;
-    if (blk == 0) X4_WRITE(X4_WR_0);
-    else if (blk == 1) X4_WRITE(X4_WR_1);
-    else if (blk == 2) X4_WRITE(X4_WR_2);
-    else X4_WRITE(X4_WR_3);
-    // 64-column block wn * 2 + cb of the tile, as gemm_256.hip numbers them; SwiGLU: wave (wm, 0) holds gate, (wm, 1) up columns
-    x_readout(smem, ep, lane, m0 + wm * 128 + h * 64, wn * 2 + cb, n0, wm * 2, 1, wn, cb, Cv, bias, res, M, N, ldc, ldr, flags,
-              alpha, aux, ldaux);
-  }
-}
-
-// ---- eight-wave form: 2 x 4 waves, 128 x 64 per wave (128 accumulators, 108 VGPRs: two waves per SIMD), the same buffers,
-// LDS image, request pattern (each wave issues 4 + 4 of the 64 requests of a k-tile) and loop structure at half the slots per
-// wave.  What one wave cannot hide under its own MFMAs -- the issue time of its LDS-DMA requests (~60 cycles each) and
-// fragment reads -- the SIMD's other wave fills (profiles/r04_gemm_x4.md: knock-outs of the four-wave loop).
+// the K loop: outputs = the 4 x 32 accumulator registers; in/out = the registers the loop advances; inputs pinned where the
+// instruction stream names them (gen_gemm_x4.py: register map)
+// m0 is written inside but cannot be named in the clobber list: it is a RESERVED register to the compiler ('inline asm clobber
+// list contains reserved registers: m0'), which never keeps a value live in it across a statement and sets it up again in front
+// of each of its own uses (LDS-DMA, movrel, sendmsg) -- ADVICE r4
 #define X8_ASM(LOOP)                                                                                                            \
   asm volatile(LOOP                                                                                                             \
                : "={a[0:31]}"(c[0]), "={a[32:63]}"(c[1]), "={a[64:95]}"(c[2]), "={a[96:127]}"(c[3]), "+{v104}"(ra0),            \
@@ -531,7 +417,15 @@ __global__ __launch_bounds__(512) void gemm_x8_kernel(const bf16_t* __restrict__
     if (probe) pr2 = (long long)__builtin_amdgcn_s_memrealtime();
   }
 
-  char* ep = smem + wave * 16384;
+  // ---- epilogue: the 128 x 64 wave tile leaves in two 64 x 64 blocks (row half h), each transposed through the wave's private
+  // 16-KiB LDS slice as gemm_256.hip does it (whole-line stores, bias / GELU / residual / SwiGLU forms on the way out).  The
+  // accumulators go to LDS straight from the AGPRs (ds_write_b128 takes accumulator data: 16 instructions per block, X8_WR_n in
+  // gemm_x4_loop.inc) and the read-out is ONE runtime loop over the blocks -- indexing the accumulator vectors from C++ unrolled
+  // everything (256 v_accvgpr_read, SGPR spills: 21 us of fixed cost per launch against gemm_256.hip's 10.6).  alpha is applied on
+  // the way out of LDS (the same fp32 product).  The loop's last barrier sits after every wave's last fragment read and no
+  // LDS-DMA is in flight (the tail iterations request nothing), so the buffers are free.
+  char* ep = smem + wave * 16384;                      // [64 rows][16 chunks of 16 B], chunk ^= row & 15
+  // fragment (ii, jj) of a block: row ii * 16 + lr, 16-byte chunk (jj * 4 + lg) ^ lr -> one address per jj, ii in the offset
   unsigned wa0, wa1, wa2, wa3;
   {
     const unsigned b0 = (unsigned)(uintptr_t)ep + lr * 256 + ((lg ^ (lr & 3)) << 4);
@@ -583,7 +477,7 @@ int mh_launch_gemm_x4(const void* A, int lda, const void* B, int ldb, void* C, i
       return MH_ERR_ARG;
   }
   const int tiles_m = (M + X4_BM - 1) / X4_BM, tiles_n = (N + X4_BN - 1) / X4_BN;
-  const size_t shmem = 2 * X4_BUF;   // 128 KiB -> one 4-wave workgroup per CU
+  const size_t shmem = 2 * X4_BUF;   // 128 KiB -> one workgroup per CU
   const dim3 grid(tiles_m * tiles_n, splits);
   if (x4_same_panel) flags |= X4_F_SAME_PANEL;
   if (mh_opt(MH_OPT_GEMM_ZERO_PAD)) flags |= X4_F_ZERO_PAD;
@@ -592,16 +486,6 @@ int mh_launch_gemm_x4(const void* A, int lda, const void* B, int ldb, void* C, i
   if (x4_no_stores) flags |= X4_F_NO_STORES;
   if (x4_clock_probe && !aux && !(flags & (MH_GEMM_SWIGLU_FWD | MH_GEMM_SWIGLU_BWD))) { flags |= X4_F_CLOCK_PROBE; aux = x4_clock_probe; }
   if (g_mh_prof_on) mh_prof_pre(stream, 2, M, N, K, splits, flags);
-#define X4_LAUNCH(V)                                                                                                           \
-  {                                                                                                                            \
-    static bool attr_set = false;                                                                                              \
-    if (!attr_set) {                                                                                                           \
-      (void)hipFuncSetAttribute((const void*)gemm_x4_kernel<V>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);       \
-      attr_set = true;                                                                                                         \
-    }                                                                                                                          \
-    hipLaunchKernelGGL(gemm_x4_kernel<V>, grid, dim3(256), shmem, stream, (const bf16_t*)A, (const bf16_t*)B, C, bias, residual,   \
-                       M, N, K, lda, ldb, ldc, ldr, flags, alpha, tiles_m, tps, split_stride, aux, ldaux);                     \
-  }
 #define X8_LAUNCH(V)                                                                                                           \
   {                                                                                                                            \
     static bool attr_set = false;                                                                                              \

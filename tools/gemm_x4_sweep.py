@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Schedule variants / timing-only knock-outs of the four-wave GEMM loop (build with `python myriad_amd/csrc/gen_gemm_x4.py
+"""Schedule variants / timing-only knock-outs of the hand-scheduled 64-deep GEMM loop (build with `python myriad_amd/csrc/gen_gemm_x4.py
 --sweep` first): time per launch on the step's shapes, and the per-k-tile time + fixed cost per launch from a K sweep on a
 one-round grid (4096 x 4096 outputs = 256 tiles).  Variants with `ko` compute wrong results by construction."""
 import sys, os, ctypes
