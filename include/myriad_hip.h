@@ -150,7 +150,10 @@ int mh_gemm_attn_rope_bwd(const void* A, int lda, const void* Bw, int ldb, void*
 int mh_rmsnorm_fwd(const float* x, const float* w, void* y_bf16, long ldy, int M, int D, float eps, mh_stream_t s);
 int mh_rmsnorm_bwd(const float* dy, const float* x, const float* w, const float* dres, float* dx, void* dx_bf16,
                    int M, int D, float eps, mh_stream_t s);
-/* K6 LayerNorm (eva_vit.py:175-176; blip2.py:119-125; Qformer.py:106,288,374) f32 in -> bf16 and/or f32 out. */
+/* K6 LayerNorm (eva_vit.py:175-176; blip2.py:119-125; Qformer.py:106,288,374) f32 in -> bf16 and/or f32 out.
+ * mh_layernorm_bwd is dgrad-only (+ optional residual-grad add, optional bf16 copy of dx): one kernel, the one that
+ * mh_gemm_layernorm_bwd feeds split-K slabs, here with a single slab.  It holds the row in registers, so D % 4 == 0 and
+ * D <= 8192 (MH_ERR_ARG otherwise, nothing written); the forward takes any D % 4 == 0. */
 int mh_layernorm_fwd(const float* x, const float* w, const float* b, void* y_bf16, float* y_f32, int M, int D,
                      float eps, mh_stream_t s);
 int mh_layernorm_bwd(const float* dy, const float* x, const float* w, const float* dres, float* dx, void* dx_bf16,

@@ -15,7 +15,7 @@
 //   already in MFMA B-operand layout for O^T = V^T.P^T / dQ^T = K^T.dS^T -- P never touches LDS.
 //   dK/dV computes S = Q.K^T (lane owns one key column) for the same reason.  The only transposed LDS images
 //   are V^T / K^T / Q^T / dO^T, built while staging.  Softmax statistics and accumulators are fp32.
-#include "common.h"
+#include "attn_frag.h"
 
 #define TQ 64
 #define TK 64
@@ -123,10 +123,6 @@ __device__ __forceinline__ short8_t frag_tr(const bf16_t* lds, int jd, int c, in
   const short4_t a = *reinterpret_cast<const short4_t*>(p);
   const short4_t b = *reinterpret_cast<const short4_t*>(p + 16);
   return (short8_t){a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
-__device__ __forceinline__ short8_t pack8(const float4_t& a, const float4_t& b) {
-  return (short8_t){(short)f2bf(a[0]), (short)f2bf(a[1]), (short)f2bf(a[2]), (short)f2bf(a[3]),
-                    (short)f2bf(b[0]), (short)f2bf(b[1]), (short)f2bf(b[2]), (short)f2bf(b[3])};
 }
 // B-operand fragments straight from global: token row `row` (or zeros), chunk kk*32 + g*8
 template <int DP>
@@ -633,6 +629,49 @@ static int launch_bwd(const AttnParams& p, hipStream_t s) {
   return MH_OK;
 }
 
+// The tiled entries' shared front: AttnParams from the pointer, shape and stride arguments (the backward's fields stay null / 0
+// for a forward; bias, kv_len, causal and the dropout fields are the caller's to add), then check_common and the forward's or
+// the backward's stride test.
+struct AttnGrads {
+  const void* dout; float* delta; void* dq; void* dk; void* dv;
+  long do_bs; int lddo; long dq_bs; int lddq; long dk_bs; int lddk; long dv_bs; int lddv;
+};
+static int fill_params(AttnParams& p, const void* q, const void* k, const void* v, const void* o, const float* lse, int B, int H,
+                       int Sq, int Sk, int D, long q_bs, int ldq, long k_bs, int ldk, long v_bs, int ldv, long o_bs, int ldo,
+                       float scale, const AttnGrads* g = nullptr) {
+  p = {};
+  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v;
+  p.o = (bf16_t*)const_cast<void*>(o);                // a backward only reads it: the dQ kernel derives delta from it
+  p.lse = const_cast<float*>(lse);
+  p.B = B; p.H = H; p.Sq = Sq; p.Sk = Sk; p.D = D;
+  p.q_bs = q_bs; p.k_bs = k_bs; p.v_bs = v_bs; p.o_bs = o_bs;
+  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
+  p.scale = scale; p.q_off = Sk - Sq;
+  if (g) {
+    p.dout = (const bf16_t*)g->dout; p.delta = g->delta;
+    p.dq = (bf16_t*)g->dq; p.dk = (bf16_t*)g->dk; p.dv = (bf16_t*)g->dv;
+    p.do_bs = g->do_bs; p.lddo = g->lddo; p.dq_bs = g->dq_bs; p.lddq = g->lddq; p.dk_bs = g->dk_bs; p.lddk = g->lddk;
+    p.dv_bs = g->dv_bs; p.lddv = g->lddv;
+  }
+  const int rc = check_common(p);
+  if (rc) return rc;
+  if (g ? (p.lddo % 8 || ldo % 8 || p.lddq % 4 || p.lddk % 4 || p.lddv % 4) : ldo % 4) return MH_ERR_ARG;
+  return MH_OK;
+}
+
+template <bool DROP>
+static int dispatch_fwd(const AttnParams& p, hipStream_t s) {
+  if (p.D <= 64) return launch_fwd<64, DROP>(p, s);
+  if (p.D <= 96) return launch_fwd<96, DROP>(p, s);
+  return launch_fwd<128, DROP>(p, s);
+}
+template <bool DROP>
+static int dispatch_bwd(const AttnParams& p, hipStream_t s) {
+  if (p.D <= 64) return launch_bwd<64, DROP>(p, s);
+  if (p.D <= 96) return launch_bwd<96, DROP>(p, s);
+  return launch_bwd<128, DROP>(p, s);
+}
+
 int mh_launch_attn_full_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Sq, int Sk, int D,
                             long q_bs, int ldq, long k_bs, int ldk, long v_bs, int ldv, long o_bs, int ldo, float scale,
                             hipStream_t stream);
@@ -641,16 +680,10 @@ extern "C" int mh_attn_fwd(const void* q, const void* k, const void* v, void* o,
                            const int* kv_len, int B, int H, int Sq, int Sk, int D, long q_bs, int ldq, long k_bs,
                            int ldk, long v_bs, int ldv, long o_bs, int ldo, float scale, int causal,
                            hipStream_t stream) {
-  AttnParams p = {};
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = (bf16_t*)o;
-  p.lse = lse; p.bias = bias; p.kv_len = kv_len;
-  p.B = B; p.H = H; p.Sq = Sq; p.Sk = Sk; p.D = D;
-  p.q_bs = q_bs; p.k_bs = k_bs; p.v_bs = v_bs; p.o_bs = o_bs;
-  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-  p.scale = scale; p.causal = causal; p.q_off = Sk - Sq;
-  int rc = check_common(p);
+  AttnParams p;
+  int rc = fill_params(p, q, k, v, o, lse, B, H, Sq, Sk, D, q_bs, ldq, k_bs, ldk, v_bs, ldv, o_bs, ldo, scale);
   if (rc) return rc;
-  if (ldo % 4) return MH_ERR_ARG;
+  p.bias = bias; p.kv_len = kv_len; p.causal = causal;
   if (Sq == 1 && !bias && Sk <= 8192 && (ldv % 2) == 0) {   // KV-cache decode (causal or not: the one query sees every valid key)
     const size_t sh = (((size_t)Sk + 63) & ~(size_t)63) * 4 + DNW * 128 * 4;
     hipLaunchKernelGGL(attn_decode_kernel, dim3(B * H), dim3(DNW * 64), sh, stream, p);
@@ -662,9 +695,7 @@ extern "C" int mh_attn_fwd(const void* q, const void* k, const void* v, void* o,
     rc = mh_launch_attn_full_fwd(q, k, v, o, lse, B, H, Sq, Sk, D, q_bs, ldq, k_bs, ldk, v_bs, ldv, o_bs, ldo, scale, stream);
     if (rc != MH_ERR_UNSUPPORTED) return rc;
   }
-  if (D <= 64) return launch_fwd<64>(p, stream);
-  if (D <= 96) return launch_fwd<96>(p, stream);
-  return launch_fwd<128>(p, stream);
+  return dispatch_fwd<false>(p, stream);
 }
 
 // One decode token: rotary on q / k, k | v appended to the cache at row pos_dev[0], attention of the one query over
@@ -697,23 +728,12 @@ extern "C" int mh_attn_bwd(const void* q, const void* k, const void* v, const vo
                            int ldk, long v_bs, int ldv, long o_bs, int ldo, long do_bs, int lddo, long dq_bs,
                            int lddq, long dk_bs, int lddk, long dv_bs, int lddv, float scale, int causal,
                            hipStream_t stream) {
-  AttnParams p = {};
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.dout = (const bf16_t*)dout;
-  p.dq = (bf16_t*)dq; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv;
-  p.lse = const_cast<float*>(lse); p.delta = delta_ws; p.bias = bias; p.kv_len = kv_len;
-  p.B = B; p.H = H; p.Sq = Sq; p.Sk = Sk; p.D = D;
-  p.q_bs = q_bs; p.k_bs = k_bs; p.v_bs = v_bs; p.o_bs = o_bs;
-  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-  p.do_bs = do_bs; p.lddo = lddo; p.dq_bs = dq_bs; p.lddq = lddq; p.dk_bs = dk_bs; p.lddk = lddk;
-  p.dv_bs = dv_bs; p.lddv = lddv;
-  p.scale = scale; p.causal = causal; p.q_off = Sk - Sq;
-  int rc = check_common(p);
+  const AttnGrads g = {dout, delta_ws, dq, dk, dv, do_bs, lddo, dq_bs, lddq, dk_bs, lddk, dv_bs, lddv};
+  AttnParams p;
+  const int rc = fill_params(p, q, k, v, o, lse, B, H, Sq, Sk, D, q_bs, ldq, k_bs, ldk, v_bs, ldv, o_bs, ldo, scale, &g);
   if (rc) return rc;
-  if (lddo % 8 || ldo % 8 || lddq % 4 || lddk % 4 || lddv % 4) return MH_ERR_ARG;
-  p.o = (bf16_t*)const_cast<void*>(o);                // read-only here: the dQ kernel derives delta from it
-  if (D <= 64) return launch_bwd<64>(p, stream);
-  if (D <= 96) return launch_bwd<96>(p, stream);
-  return launch_bwd<128>(p, stream);
+  p.bias = bias; p.kv_len = kv_len; p.causal = causal;
+  return dispatch_bwd<false>(p, stream);
 }
 
 // Q-Former attention with attention-probability dropout (Qformer.py:258, train mode): the tiled kernels above with the
@@ -722,41 +742,24 @@ extern "C" int mh_attn_fwd_dropout(const void* q, const void* k, const void* v, 
                                    int Sk, int D, long q_bs, int ldq, long k_bs, int ldk, long v_bs, int ldv, long o_bs,
                                    int ldo, float scale, float drop_p, unsigned long long seed, hipStream_t stream) {
   if (!(drop_p >= 0.f && drop_p < 1.f) || !lse) return MH_ERR_ARG;
-  AttnParams p = {};
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = (bf16_t*)o; p.lse = lse;
-  p.B = B; p.H = H; p.Sq = Sq; p.Sk = Sk; p.D = D;
-  p.q_bs = q_bs; p.k_bs = k_bs; p.v_bs = v_bs; p.o_bs = o_bs;
-  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-  p.scale = scale; p.q_off = Sk - Sq; p.drop_p = drop_p; p.drop_seed = seed;
-  int rc = check_common(p);
+  AttnParams p;
+  const int rc = fill_params(p, q, k, v, o, lse, B, H, Sq, Sk, D, q_bs, ldq, k_bs, ldk, v_bs, ldv, o_bs, ldo, scale);
   if (rc) return rc;
-  if (ldo % 4) return MH_ERR_ARG;
-  if (D <= 64) return launch_fwd<64, true>(p, stream);
-  if (D <= 96) return launch_fwd<96, true>(p, stream);
-  return launch_fwd<128, true>(p, stream);
+  p.drop_p = drop_p; p.drop_seed = seed;
+  return dispatch_fwd<true>(p, stream);
 }
 
+// (o is the dropped O: delta = rowsum(dO * O))
 extern "C" int mh_attn_bwd_dropout(const void* q, const void* k, const void* v, const void* o, const void* dout,
                                    const float* lse, float* delta_ws, void* dq, void* dk, void* dv, int B, int H, int Sq,
                                    int Sk, int D, long q_bs, int ldq, long k_bs, int ldk, long v_bs, int ldv, long o_bs,
                                    int ldo, long do_bs, int lddo, long dq_bs, int lddq, long dk_bs, int lddk, long dv_bs,
                                    int lddv, float scale, float drop_p, unsigned long long seed, hipStream_t stream) {
   if (!(drop_p >= 0.f && drop_p < 1.f)) return MH_ERR_ARG;
-  AttnParams p = {};
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.dout = (const bf16_t*)dout;
-  p.dq = (bf16_t*)dq; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv;
-  p.lse = const_cast<float*>(lse); p.delta = delta_ws;
-  p.B = B; p.H = H; p.Sq = Sq; p.Sk = Sk; p.D = D;
-  p.q_bs = q_bs; p.k_bs = k_bs; p.v_bs = v_bs; p.o_bs = o_bs;
-  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-  p.do_bs = do_bs; p.lddo = lddo; p.dq_bs = dq_bs; p.lddq = lddq; p.dk_bs = dk_bs; p.lddk = lddk;
-  p.dv_bs = dv_bs; p.lddv = lddv;
-  p.scale = scale; p.q_off = Sk - Sq; p.drop_p = drop_p; p.drop_seed = seed;
-  int rc = check_common(p);
+  const AttnGrads g = {dout, delta_ws, dq, dk, dv, do_bs, lddo, dq_bs, lddq, dk_bs, lddk, dv_bs, lddv};
+  AttnParams p;
+  const int rc = fill_params(p, q, k, v, o, lse, B, H, Sq, Sk, D, q_bs, ldq, k_bs, ldk, v_bs, ldv, o_bs, ldo, scale, &g);
   if (rc) return rc;
-  if (lddo % 8 || ldo % 8 || lddq % 4 || lddk % 4 || lddv % 4) return MH_ERR_ARG;
-  p.o = (bf16_t*)const_cast<void*>(o);                // the dropped O: delta = rowsum(dO * O)
-  if (D <= 64) return launch_bwd<64, true>(p, stream);
-  if (D <= 96) return launch_bwd<96, true>(p, stream);
-  return launch_bwd<128, true>(p, stream);
+  p.drop_p = drop_p; p.drop_seed = seed;
+  return dispatch_bwd<true>(p, stream);
 }

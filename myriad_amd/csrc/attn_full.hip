@@ -12,10 +12,9 @@
 //
 // MFMA mapping as attn_seq.hip: S^T = K.Q^T (keys in the accumulator rows, one query per lane column), O^T = V^T.P^T.
 // Head dims that are not a multiple of 32 (ViT: 88) are zero-padded to DP = 96 in the LDS images and in the Q fragments.
-#include "common.h"
+#include "attn_frag.h"
 
 #define AF_NW 8              // waves per workgroup
-typedef __attribute__((address_space(3))) short4_t af_lds_s4;
 
 struct AttnFullParams {
   const bf16_t* q; const bf16_t* k; const bf16_t* v; bf16_t* o; float* lse;
@@ -25,19 +24,6 @@ struct AttnFullParams {
   float scale;
   int frag_per_wg;                 // query fragments (16 rows) per workgroup of one (batch, head)
 };
-
-template <int DP>
-__device__ __forceinline__ short8_t af_frag_rm(const bf16_t* img, int j, int kk, int lr, int lg) {
-  return *reinterpret_cast<const short8_t*>(img + (16 * j + lr) * (DP + 16) + kk * 32 + lg * 8);
-}
-// A operand of V^T.P^T out of the key-major V image (see attn_seq.hip as_frag_tr)
-template <int DP>
-__device__ __forceinline__ short8_t af_frag_tr(const bf16_t* img, int jd, int c, int lr, int lg) {
-  const bf16_t* p = img + (32 * c + 4 * lg + (lr >> 2)) * (DP + 16) + 16 * jd + 4 * (lr & 3);
-  const short4_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((af_lds_s4*)p);
-  const short4_t b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((af_lds_s4*)(p + 16 * (DP + 16)));
-  return (short8_t){a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
 
 #define AF_NEG_INF (-__builtin_inff())
 
@@ -117,7 +103,7 @@ __global__ __launch_bounds__(AF_NW * 64) void attn_full_fwd_kernel(AttnFullParam
           s[u] = (float4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int kk = 0; kk < NKK; ++kk)
-            s[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af_frag_rm<DP>(Ks, j, kk, lr, lg), qa[kk], s[u], 0, 0, 0);
+            s[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_frag_rm<RS>(Ks, j, kk, lr, lg), qa[kk], s[u], 0, 0, 0);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int key = 16 * j + 4 * lg + r;
@@ -140,12 +126,11 @@ __global__ __launch_bounds__(AF_NW * 64) void attn_full_fwd_kernel(AttnFullParam
           }
         lsum = lsum * alpha + psum;
         mrun = m_new;
-        const short8_t pb = {(short)f2bf(s[0][0]), (short)f2bf(s[0][1]), (short)f2bf(s[0][2]), (short)f2bf(s[0][3]),
-                             (short)f2bf(s[1][0]), (short)f2bf(s[1][1]), (short)f2bf(s[1][2]), (short)f2bf(s[1][3])};
+        const short8_t pb = pack8(s[0], s[1]);
 #pragma unroll
         for (int jd = 0; jd < NJD; ++jd) {
           acc[jd] *= alpha;
-          acc[jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af_frag_tr<DP>(Vs, jd, c, lr, lg), pb, acc[jd], 0, 0, 0);
+          acc[jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_frag_tr<RS>(Vs, jd, c, lr, lg), pb, acc[jd], 0, 0, 0);
         }
       }
       lsum += __shfl_xor(lsum, 16, 64);

@@ -19,15 +19,13 @@
 // keys {16j + 4*(lane>>4) + r} in the accumulator registers, so softmax statistics are per-lane scalars (+2 xor
 // shuffles) and P is already the B operand of O^T = V^T.P^T.  The V^T A-operand (row d = lane & 15, reduction elements
 // = keys {32c + 4g + r} U {32c + 16 + 4g + r}) is two transpose reads of [4 keys][16 d] blocks of the key-major image.
-#include "common.h"
+#include "attn_frag.h"
 #include <cstdlib>
 
 #define AS_D 128
 #define AS_RS 144            // LDS row stride in elements
 #define AS_MAXF 10           // query / key fragments of 16 (S <= 160)
 #define AS_NW 8              // waves per workgroup
-
-typedef __attribute__((address_space(3))) short4_t as_lds_s4;
 
 struct AttnSeqParams {
   const bf16_t* qkv;     // [B, S, ld]  q | k | v, pre-rotary
@@ -63,24 +61,6 @@ __device__ __forceinline__ void as_rope_pair(short8_t& a, short8_t& b, const flo
   }
   a = oa;
   b = ob;
-}
-
-// A operand of the X^T.Y products: X is a key-major (row-major) LDS image, the operand row is column d = 16*jd + lr
-// of X and its 8 reduction elements are rows {32c + 4g + r} U {32c + 16 + 4g + r}.  ds_read_b64_tr_b16: lane i of a
-// 16-lane group addresses row (i >> 2), columns 4*(i & 3).. of a [4][16] block and receives column i of that block
-// (tools/micro/tr_probe.hip).
-__device__ __forceinline__ short8_t as_frag_tr(const bf16_t* img, int jd, int c, int lr, int lg) {
-  const bf16_t* p = img + (32 * c + 4 * lg + (lr >> 2)) * AS_RS + 16 * jd + 4 * (lr & 3);
-  const short4_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((as_lds_s4*)p);
-  const short4_t b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((as_lds_s4*)(p + 16 * AS_RS));
-  return (short8_t){a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
-__device__ __forceinline__ short8_t as_frag_rm(const bf16_t* img, int j, int kk, int lr, int lg) {
-  return *reinterpret_cast<const short8_t*>(img + (16 * j + lr) * AS_RS + kk * 32 + lg * 8);
-}
-__device__ __forceinline__ short8_t as_pack8(const float4_t& a, const float4_t& b) {
-  return (short8_t){(short)f2bf(a[0]), (short)f2bf(a[1]), (short)f2bf(a[2]), (short)f2bf(a[3]),
-                    (short)f2bf(b[0]), (short)f2bf(b[1]), (short)f2bf(b[2]), (short)f2bf(b[3])};
 }
 
 // Staging of one head's K (rotated) and V into the LDS images, rows [0, 16 * nfe) with nfe = nf rounded up to even (the
@@ -228,7 +208,7 @@ __global__ __launch_bounds__(AS_NW * 64) void attn_seq_fwd_kernel(AttnSeqParams 
           if (j <= f) {
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk)
-              s[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag_rm(Ks, j, kk, lr, lg), qa[kk], s[u], 0, 0, 0);
+              s[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_frag_rm<AS_RS>(Ks, j, kk, lr, lg), qa[kk], s[u], 0, 0, 0);
           }
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
@@ -253,11 +233,11 @@ __global__ __launch_bounds__(AS_NW * 64) void attn_seq_fwd_kernel(AttnSeqParams 
           }
         lsum = lsum * alpha + psum;
         mrun = m_new;
-        const short8_t pb = as_pack8(s[0], s[1]);
+        const short8_t pb = pack8(s[0], s[1]);
 #pragma unroll
         for (int jd = 0; jd < 8; ++jd) {
           acc[jd] *= alpha;
-          acc[jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag_tr(Vs, jd, c, lr, lg), pb, acc[jd], 0, 0, 0);
+          acc[jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_frag_tr<AS_RS>(Vs, jd, c, lr, lg), pb, acc[jd], 0, 0, 0);
         }
       }
       lsum += __shfl_xor(lsum, 16, 64);
@@ -325,7 +305,7 @@ __device__ __forceinline__ void as_dout_frags(short8_t (&f)[4], const AttnSeqPar
     }
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk)
-      f[kk] = as_pack8((float4_t){v[kk][0], v[kk][1], v[kk][2], v[kk][3]}, (float4_t){v[kk][4], v[kk][5], v[kk][6], v[kk][7]});
+      f[kk] = pack8((float4_t){v[kk][0], v[kk][1], v[kk][2], v[kk][3]}, (float4_t){v[kk][4], v[kk][5], v[kk][6], v[kk][7]});
   } else {
     const float* src = p.dout + tok * p.ldd + col;
     float4_t a[4], c[4];
@@ -353,7 +333,7 @@ __device__ __forceinline__ void as_dout_frags(short8_t (&f)[4], const AttnSeqPar
       }
     }
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) f[kk] = as_pack8(a[kk], c[kk]);
+    for (int kk = 0; kk < 4; ++kk) f[kk] = pack8(a[kk], c[kk]);
   }
 }
 
@@ -484,8 +464,8 @@ __global__ __launch_bounds__(AS_NW * 64) void attn_seq_bwd_kernel(AttnSeqParams 
           float4_t sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int kk = 0; kk < 4; ++kk) {
-            sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag_rm(I0, j, kk, lr, lg), qf0[kk], sc, 0, 0, 0);
-            dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag_rm(I1, j, kk, lr, lg), gf0[kk], dp, 0, 0, 0);
+            sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_frag_rm<AS_RS>(I0, j, kk, lr, lg), qf0[kk], sc, 0, 0, 0);
+            dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_frag_rm<AS_RS>(I1, j, kk, lr, lg), gf0[kk], dp, 0, 0, 0);
           }
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
@@ -495,10 +475,10 @@ __global__ __launch_bounds__(AS_NW * 64) void attn_seq_bwd_kernel(AttnSeqParams 
             ds[u][r] = ok ? pr * (dp[r] - dlt) * p.scale : 0.f;
           }
         }
-        const short8_t db = as_pack8(ds[0], ds[1]);
+        const short8_t db = pack8(ds[0], ds[1]);
 #pragma unroll
         for (int jd = 0; jd < 8; ++jd)
-          acc[jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag_tr(I0, jd, c, lr, lg), db, acc[jd], 0, 0, 0);
+          acc[jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_frag_tr<AS_RS>(I0, jd, c, lr, lg), db, acc[jd], 0, 0, 0);
       }
       if (qi < S) {
         const int ps = pos[qi];
@@ -528,8 +508,8 @@ __global__ __launch_bounds__(AS_NW * 64) void attn_seq_bwd_kernel(AttnSeqParams 
       kf[kk] = (short8_t){0, 0, 0, 0, 0, 0, 0, 0};
       vf[kk] = kf[kk];
       if (f >= 0) {
-        kf[kk] = as_frag_rm(I0, f, kk, lr, lg);
-        vf[kk] = as_frag_rm(I1, f, kk, lr, lg);
+        kf[kk] = lds_frag_rm<AS_RS>(I0, f, kk, lr, lg);
+        vf[kk] = lds_frag_rm<AS_RS>(I1, f, kk, lr, lg);
       }
     }
   }
@@ -573,8 +553,8 @@ __global__ __launch_bounds__(AS_NW * 64) void attn_seq_bwd_kernel(AttnSeqParams 
           float4_t sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int kk = 0; kk < 4; ++kk) {
-            sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag_rm(I0, j, kk, lr, lg), kf0[kk], sc, 0, 0, 0);
-            dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag_rm(I1, j, kk, lr, lg), vf0[kk], dp, 0, 0, 0);
+            sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_frag_rm<AS_RS>(I0, j, kk, lr, lg), kf0[kk], sc, 0, 0, 0);
+            dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_frag_rm<AS_RS>(I1, j, kk, lr, lg), vf0[kk], dp, 0, 0, 0);
           }
           const float4_t l4 = *reinterpret_cast<const float4_t*>(lse_s + 16 * j + 4 * lg);
           const float4_t d4 = *reinterpret_cast<const float4_t*>(dlt_s + 16 * j + 4 * lg);
@@ -587,11 +567,11 @@ __global__ __launch_bounds__(AS_NW * 64) void attn_seq_bwd_kernel(AttnSeqParams 
             ds[u][r] = ok ? e * (dp[r] - d4[r]) * p.scale : 0.f;
           }
         }
-        const short8_t pb = as_pack8(pr[0], pr[1]), db = as_pack8(ds[0], ds[1]);
+        const short8_t pb = pack8(pr[0], pr[1]), db = pack8(ds[0], ds[1]);
 #pragma unroll
         for (int jd = 0; jd < 8; ++jd) {
-          adv[jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag_tr(I1, jd, c, lr, lg), pb, adv[jd], 0, 0, 0);
-          adk[jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag_tr(I0, jd, c, lr, lg), db, adk[jd], 0, 0, 0);
+          adv[jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_frag_tr<AS_RS>(I1, jd, c, lr, lg), pb, adv[jd], 0, 0, 0);
+          adk[jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_frag_tr<AS_RS>(I0, jd, c, lr, lg), db, adk[jd], 0, 0, 0);
         }
       }
       if (ki < S) {

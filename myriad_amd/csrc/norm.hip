@@ -167,73 +167,17 @@ __global__ __launch_bounds__(NT) void layernorm_fwd_kernel(const float* __restri
   }
 }
 
-// dx = r * (g - mean(g) - xhat * mean(g*xhat)),  g = dy*w   (+ dres)
-__global__ __launch_bounds__(NT) void layernorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                           const float* __restrict__ w, const float* dres, float* dx,
-                                                           bf16_t* dx_bf, int D, float eps) {
-  __shared__ float red[NW];
-  const size_t row = blockIdx.x;
-  const float* xr = x + row * D;
-  const float* gr = dy + row * D;
-  float s = 0.f;
-  for (int i = threadIdx.x * 4; i < D; i += NT * 4) {
-    const float4_t v = *reinterpret_cast<const float4_t*>(xr + i);
-    s += v[0] + v[1] + v[2] + v[3];
-  }
-  const float mean = block_sum<NW>(s, red) / D;
-  float ss = 0.f;
-  for (int i = threadIdx.x * 4; i < D; i += NT * 4) {
-    const float4_t v = *reinterpret_cast<const float4_t*>(xr + i);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ss += (v[e] - mean) * (v[e] - mean);
-  }
-  const float r = rsqrtf(block_sum<NW>(ss, red) / D + eps);
-  float sg = 0.f, sgx = 0.f;
-  for (int i = threadIdx.x * 4; i < D; i += NT * 4) {
-    const float4_t v = *reinterpret_cast<const float4_t*>(xr + i);
-    const float4_t g = *reinterpret_cast<const float4_t*>(gr + i);
-    const float4_t ww = *reinterpret_cast<const float4_t*>(w + i);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float gg = g[e] * ww[e];
-      sg += gg;
-      sgx += gg * (v[e] - mean) * r;
-    }
-  }
-  sg = block_sum<NW>(sg, red) / D;
-  sgx = block_sum<NW>(sgx, red) / D;
-  for (int i = threadIdx.x * 4; i < D; i += NT * 4) {
-    const float4_t v = *reinterpret_cast<const float4_t*>(xr + i);
-    const float4_t g = *reinterpret_cast<const float4_t*>(gr + i);
-    const float4_t ww = *reinterpret_cast<const float4_t*>(w + i);
-    float4_t o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = r * (g[e] * ww[e] - sg - (v[e] - mean) * r * sgx);
-    if (dres) {
-      const float4_t d = *reinterpret_cast<const float4_t*>(dres + row * D + i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] += d[e];
-    }
-    if (dx) *reinterpret_cast<float4_t*>(dx + row * D + i) = o;
-    if (dx_bf) {
-      uint2 pk;
-      pk.x = pack_bf2(o[0], o[1]);
-      pk.y = pack_bf2(o[2], o[3]);
-      *reinterpret_cast<uint2*>(dx_bf + row * D + i) = pk;
-    }
-  }
-}
-
-// layernorm_bwd_kernel for a dY given as `nslab` split-K partial slabs [nslab][M][ldy] of the dgrad GEMM that produced it
-// (mh_gemm_layernorm_bwd), summed in slab order exactly as splitk_reduce_kernel sums them.  The row's x and summed dY stay in
-// registers (NIT float4 chunks a thread), so each operand is read once; the row sums, the per-element expressions and their
-// order are layernorm_bwd_kernel's, which makes the pair bit-identical to GEMM -> reduce -> layernorm_bwd.  dy_out != NULL
-// also receives the summed dY (the input of the LayerNorm parameter gradients).
+// dx = r * (g - mean(g) - xhat * mean(g*xhat)),  g = dy*w   (+ dres) ; optional bf16 copy for the next dgrad GEMM.
+// The row's x and dY stay in registers (NIT float4 chunks a thread, D <= 8192), so each operand is read once.  dY may be given
+// as `nslab` split-K partial slabs [nslab][M][ldy] of the dgrad GEMM that produced it (mh_gemm_layernorm_bwd): they are summed in
+// slab order exactly as splitk_reduce_kernel sums them, which makes the fused form bit-identical to GEMM -> reduce ->
+// mh_layernorm_bwd (this kernel with nslab = 1).  dy_out != NULL also receives the summed dY (the input of the LayerNorm
+// parameter gradients).
 template <int NIT>
-__global__ __launch_bounds__(NT) void layernorm_bwd_slab_kernel(const void* __restrict__ dy, int nslab, long slab, long ldy,
-                                                                const float* __restrict__ x, const float* __restrict__ w,
-                                                                const float* dres, float* dx, bf16_t* dx_bf, float* dy_out,
-                                                                int D, float eps, int sbf) {
+__global__ __launch_bounds__(NT) void layernorm_bwd_kernel(const void* __restrict__ dy, int nslab, long slab, long ldy,
+                                                           const float* __restrict__ x, const float* __restrict__ w,
+                                                           const float* dres, float* dx, bf16_t* dx_bf, float* dy_out,
+                                                           int D, float eps, int sbf) {
   __shared__ float red[NW];
   const size_t row = blockIdx.x;
   const float* xr = x + row * D;
@@ -352,24 +296,15 @@ extern "C" int mh_layernorm_fwd(const float* x, const float* w, const float* b, 
   return MH_OK;
 }
 
-extern "C" int mh_layernorm_bwd(const float* dy, const float* x, const float* w, const float* dres, float* dx,
-                                void* dx_bf16, int M, int D, float eps, hipStream_t stream) {
-  if (M <= 0) return MH_OK;
-  if (D % 4) return MH_ERR_ARG;
-  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(M), dim3(NT), 0, stream, dy, x, w, dres, dx, (bf16_t*)dx_bf16, D,
-                     eps);
-  MH_CHECK_LAUNCH();
-  return MH_OK;
-}
-
-// dy as nslab partial slabs [nslab][M][ldy] (mh_gemm_layernorm_bwd, gemm.hip); dy_out: optional f32 [M, D] summed dY
+// dy as nslab partial slabs [nslab][M][ldy] (nslab = 1: a plain [M, ldy] matrix); dy_out: optional f32 [M, D] summed dY;
+// called from gemm.hip too (mh_gemm_layernorm_bwd)
 int mh_launch_layernorm_bwd(const void* dy, int slab_bf16, int nslab, long slab, long ldy, const float* x, const float* w,
                             const float* dres, float* dx, void* dx_bf16, float* dy_out, int M, int D, float eps,
                             hipStream_t stream) {
   if (M <= 0) return MH_OK;
   if ((D % 4) || D > 8192 || (ldy % 4) || ldy < D || nslab < 1) return MH_ERR_ARG;
 #define LNB_LAUNCH(NIT_)                                                                                                   \
-  hipLaunchKernelGGL(layernorm_bwd_slab_kernel<NIT_>, dim3(M), dim3(NT), 0, stream, dy, nslab, slab, ldy, x, w, dres, dx,   \
+  hipLaunchKernelGGL(layernorm_bwd_kernel<NIT_>, dim3(M), dim3(NT), 0, stream, dy, nslab, slab, ldy, x, w, dres, dx,        \
                      (bf16_t*)dx_bf16, dy_out, D, eps, slab_bf16)
   if (D <= 2 * NT * 4) LNB_LAUNCH(2);
   else if (D <= 4 * NT * 4) LNB_LAUNCH(4);
@@ -377,4 +312,10 @@ int mh_launch_layernorm_bwd(const void* dy, int slab_bf16, int nslab, long slab,
 #undef LNB_LAUNCH
   MH_CHECK_LAUNCH();
   return MH_OK;
+}
+
+extern "C" int mh_layernorm_bwd(const float* dy, const float* x, const float* w, const float* dres, float* dx,
+                                void* dx_bf16, int M, int D, float eps, hipStream_t stream) {
+  if (M <= 0) return MH_OK;
+  return mh_launch_layernorm_bwd(dy, 0, 1, 0, D, x, w, dres, dx, dx_bf16, nullptr, M, D, eps, stream);
 }

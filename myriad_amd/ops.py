@@ -413,20 +413,41 @@ def gemm_auto_f32(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.
 
 
 # --------------------------------------------------------------------------- attention
+def _attn_fwd_outputs(name, q, k, v, H, D, out=None, need_lse=True):
+    """The forward pair's q / k / v check and its (o, lse) allocation."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        if t.dtype != BF16 or t.stride(2) != 1:
+            raise _lib.MyriadHipError(f"{name}.{n}: need bf16 with unit inner stride")
+    B, Sq = q.shape[0], q.shape[1]
+    if out is None:
+        out = torch.empty((B, Sq, H * D), dtype=BF16, device=q.device)
+    return out, (torch.empty((B, H, Sq), dtype=F32, device=q.device) if need_lse else None)
+
+
+def _attn_bwd_outputs(q, k, H, D, dq, dk, dv):
+    """The backward pair's (dq, dk, dv, delta): the gradients the caller did not pass, and the delta scratch."""
+    B, Sq, Sk, dev = q.shape[0], q.shape[1], k.shape[1], q.device
+    if dq is None:
+        dq = torch.empty((B, Sq, H * D), dtype=BF16, device=dev)
+    if dk is None:
+        dk = torch.empty((B, Sk, H * D), dtype=BF16, device=dev)
+    if dv is None:
+        dv = torch.empty((B, Sk, H * D), dtype=BF16, device=dev)
+    return dq, dk, dv, torch.empty((B, H, Sq), dtype=F32, device=dev)
+
+
+def _strides(*ts):
+    """(batch stride, token stride) of each tensor, flattened: the order the attention entries take them in."""
+    return [t.stride(i) for t in ts for i in (0, 1)]
+
+
 def attn_fwd(q, k, v, H: int, D: int, scale: float, causal: bool = False, bias=None, kv_len=None, out=None,
              need_lse: bool = True):
     """q [B,Sq,Wq], k/v [B,Sk,W*] bf16 views (head h at cols h*D..), returns (o [B,Sq,H*D] bf16, lse [B,H,Sq] f32)."""
-    B, Sq = q.shape[0], q.shape[1]
-    Sk = k.shape[1]
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        if t.dtype != BF16 or t.stride(2) != 1:
-            raise _lib.MyriadHipError(f"attn_fwd.{n}: need bf16 with unit inner stride")
-    if out is None:
-        out = torch.empty((B, Sq, H * D), dtype=BF16, device=q.device)
-    lse = torch.empty((B, H, Sq), dtype=F32, device=q.device) if need_lse else None
+    B, Sq, Sk = q.shape[0], q.shape[1], k.shape[1]
+    out, lse = _attn_fwd_outputs("attn_fwd", q, k, v, H, D, out, need_lse)
     rc = _L().mh_attn_fwd(_p(q), _p(k), _p(v), _p(out), _p(lse), _p(bias), _p(kv_len), B, H, Sq, Sk, D,
-                          q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
-                          out.stride(0), out.stride(1), float(scale), int(causal), _s())
+                          *_strides(q, k, v, out), float(scale), int(causal), _s())
     _lib.check(rc, f"mh_attn_fwd B={B} H={H} Sq={Sq} Sk={Sk} D={D}")
     return out, lse
 
@@ -435,15 +456,9 @@ def attn_fwd_dropout(q, k, v, H: int, D: int, scale: float, p: float, seed: int)
     """attn_fwd with attention-probability dropout (mask index ((b*H + h)*Sq + i)*Sk + j); p = 0 is attn_fwd itself."""
     if p == 0.0:
         return attn_fwd(q, k, v, H, D, scale)
-    B, Sq = q.shape[0], q.shape[1]
-    Sk = k.shape[1]
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        if t.dtype != BF16 or t.stride(2) != 1:
-            raise _lib.MyriadHipError(f"attn_fwd_dropout.{n}: need bf16 with unit inner stride")
-    out = torch.empty((B, Sq, H * D), dtype=BF16, device=q.device)
-    lse = torch.empty((B, H, Sq), dtype=F32, device=q.device)
-    rc = _L().mh_attn_fwd_dropout(_p(q), _p(k), _p(v), _p(out), _p(lse), B, H, Sq, Sk, D, q.stride(0), q.stride(1),
-                                  k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0), out.stride(1),
+    B, Sq, Sk = q.shape[0], q.shape[1], k.shape[1]
+    out, lse = _attn_fwd_outputs("attn_fwd_dropout", q, k, v, H, D)
+    rc = _L().mh_attn_fwd_dropout(_p(q), _p(k), _p(v), _p(out), _p(lse), B, H, Sq, Sk, D, *_strides(q, k, v, out),
                                   float(scale), float(p), int(seed), _s())
     _lib.check(rc, f"mh_attn_fwd_dropout B={B} H={H} Sq={Sq} Sk={Sk} D={D}")
     return out, lse
@@ -453,42 +468,22 @@ def attn_bwd_dropout(q, k, v, o, dout, lse, H: int, D: int, scale: float, p: flo
     """attn_bwd of attn_fwd_dropout (o = its dropped output); p = 0 is attn_bwd itself."""
     if p == 0.0:
         return attn_bwd(q, k, v, o, dout, lse, H, D, scale, dq=dq, dk=dk, dv=dv)
-    B, Sq = q.shape[0], q.shape[1]
-    Sk = k.shape[1]
-    dev = q.device
-    if dq is None:
-        dq = torch.empty((B, Sq, H * D), dtype=BF16, device=dev)
-    if dk is None:
-        dk = torch.empty((B, Sk, H * D), dtype=BF16, device=dev)
-    if dv is None:
-        dv = torch.empty((B, Sk, H * D), dtype=BF16, device=dev)
-    delta = torch.empty((B, H, Sq), dtype=F32, device=dev)
+    B, Sq, Sk = q.shape[0], q.shape[1], k.shape[1]
+    dq, dk, dv, delta = _attn_bwd_outputs(q, k, H, D, dq, dk, dv)
     rc = _L().mh_attn_bwd_dropout(_p(q), _p(k), _p(v), _p(o), _p(dout), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv),
-                                  B, H, Sq, Sk, D, q.stride(0), q.stride(1), k.stride(0), k.stride(1),
-                                  v.stride(0), v.stride(1), o.stride(0), o.stride(1), dout.stride(0), dout.stride(1),
-                                  dq.stride(0), dq.stride(1), dk.stride(0), dk.stride(1), dv.stride(0), dv.stride(1),
-                                  float(scale), float(p), int(seed), _s())
+                                  B, H, Sq, Sk, D, *_strides(q, k, v, o, dout, dq, dk, dv), float(scale), float(p), int(seed),
+                                  _s())
     _lib.check(rc, f"mh_attn_bwd_dropout B={B} H={H} Sq={Sq} Sk={Sk} D={D}")
     return dq, dk, dv
 
 
 def attn_bwd(q, k, v, o, dout, lse, H: int, D: int, scale: float, causal: bool = False, bias=None, kv_len=None,
              dq=None, dk=None, dv=None):
-    B, Sq = q.shape[0], q.shape[1]
-    Sk = k.shape[1]
-    dev = q.device
-    if dq is None:
-        dq = torch.empty((B, Sq, H * D), dtype=BF16, device=dev)
-    if dk is None:
-        dk = torch.empty((B, Sk, H * D), dtype=BF16, device=dev)
-    if dv is None:
-        dv = torch.empty((B, Sk, H * D), dtype=BF16, device=dev)
-    delta = torch.empty((B, H, Sq), dtype=F32, device=dev)
+    B, Sq, Sk = q.shape[0], q.shape[1], k.shape[1]
+    dq, dk, dv, delta = _attn_bwd_outputs(q, k, H, D, dq, dk, dv)
     rc = _L().mh_attn_bwd(_p(q), _p(k), _p(v), _p(o), _p(dout), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), _p(bias),
-                          _p(kv_len), B, H, Sq, Sk, D, q.stride(0), q.stride(1), k.stride(0), k.stride(1),
-                          v.stride(0), v.stride(1), o.stride(0), o.stride(1), dout.stride(0), dout.stride(1),
-                          dq.stride(0), dq.stride(1), dk.stride(0), dk.stride(1), dv.stride(0), dv.stride(1),
-                          float(scale), int(causal), _s())
+                          _p(kv_len), B, H, Sq, Sk, D, *_strides(q, k, v, o, dout, dq, dk, dv), float(scale), int(causal),
+                          _s())
     _lib.check(rc, f"mh_attn_bwd B={B} H={H} Sq={Sq} Sk={Sk} D={D}")
     return dq, dk, dv
 

@@ -6,8 +6,8 @@ that a torch emulation passes each bound and that the plausible mistakes fail it
 
 Launch paths only these tests reach (each can only pass through the named kernel):
     rmsnorm_bwd_kernel<8>            test_rmsnorm_rows at D = 4100, 8192 (mh_rmsnorm_bwd launches <8> for every D > 4096)
-    layernorm_bwd_slab_kernel<4>/<8> test_layernorm_slab_backward_wide_rows at N = 3072 / 5120 (ops.gemm_layernorm_bwd is the slab
-                                     kernel's only caller; <4> for 2048 < N <= 4096, <8> above)
+    layernorm_bwd_kernel<4>/<8>,     test_layernorm_slab_backward_wide_rows at N = 3072 / 5120 (ops.gemm_layernorm_bwd is the only
+      more than one slab             caller that hands the kernel split-K slabs; <4> for 2048 < N <= 4096, <8> above)
     clamp_ce_kernel (256 threads)    test_clamp_ce_edges: V = 50000 and 32772 (> 32768), the `ldl % 4 != 0` view and the
                                      4-byte-offset base at every V (the launcher's conditions for the register-resident kernel fail)
 
@@ -167,8 +167,8 @@ def _layernorm_rows(M, D, eps, x, w, dy, dres, monkeypatch):
 
 @pytest.mark.parametrize("M,N,K", [(1028, 3072, 4096), (1028, 5120, 4096)])
 def test_layernorm_slab_backward_wide_rows(M, N, K, monkeypatch):
-    """ops.gemm_layernorm_bwd with a split K at 2048 < N <= 4096 (layernorm_bwd_slab_kernel<4>) and N > 4096 (<8>): the bits of
-    gemm + layernorm_bwd, and that within the float64 bound given the dY the GEMM produced."""
+    """ops.gemm_layernorm_bwd with a split K at 2048 < N <= 4096 (layernorm_bwd_kernel<4>) and N > 4096 (<8>): the bits of
+    gemm + layernorm_bwd (the same kernel with one slab), and that within the float64 bound given the dY the GEMM produced."""
     ops.ensure_workspace(DEV)
     assert ops.gemm_plan(M, N, K, out_f32=True)[1] > 1                      # K is split: the norm kernel reads the slabs
     a, bw = dev(fb.rnd(M, K, seed=1).to(BF16)), dev((fb.rnd(N, K, seed=2) * 0.05).to(BF16))
@@ -182,6 +182,22 @@ def test_layernorm_slab_backward_wide_rows(M, N, K, monkeypatch):
     r = fb.layernorm_ref_bound(x, w, None, 1e-6, dy=dy, dres=dres)
     note("layernorm_bwd_slab f32", assert_within(dx, r["dx"], r["dx_bound"], "gemm_layernorm_bwd dx"))
     note("layernorm_bwd_slab bf16", assert_within(dxb, r["dx"], r["dx_bf16_bound"], "gemm_layernorm_bwd dx bf16"))
+
+
+@pytest.mark.parametrize("D", [768, 1408, 2052, 8192])
+def test_layernorm_backward_single_slab_every_instantiation(D, monkeypatch):
+    """ops.layernorm_bwd (layernorm_bwd_kernel with one slab) with and without dres at the product's widths (768: Q-Former,
+    1408: ViT; both <2>) and at the first width of <4> (2052) and the last of <8> (8192), against the float64 bound."""
+    M, eps = 37, 1e-6
+    x, w, dy, dres = _norm_inputs(M, D)
+    with poisoned_allocations(monkeypatch):
+        dx, dxb = ops.layernorm_bwd(dy, x, w, eps, dres=dres, want_bf16=True)
+        dx0, dxb0 = ops.layernorm_bwd(dy, x, w, eps, want_bf16=True)
+    sync()
+    for got, gotb, r, what in ((dx, dxb, fb.layernorm_ref_bound(x, w, None, eps, dy=dy, dres=dres), "dres"),
+                               (dx0, dxb0, fb.layernorm_ref_bound(x, w, None, eps, dy=dy), "no dres")):
+        note("layernorm_bwd f32", assert_within(got, r["dx"], r["dx_bound"], f"layernorm_bwd dx ({what})"))
+        note("layernorm_bwd bf16", assert_within(gotb, r["dx"], r["dx_bf16_bound"], f"layernorm_bwd dx bf16 ({what})"))
 
 
 @pytest.mark.parametrize("D", NORM_D)
@@ -283,7 +299,15 @@ def test_norm_launchers_reject_bad_widths_and_leave_the_output_alone():
     with pytest.raises(_lib.MyriadHipError):                                # the slab backward's D <= 8192
         ops.gemm_layernorm_bwd(a, torch.zeros(8256, 64, dtype=BF16, device=DEV), torch.ones(M, 8256, device=DEV),
                                torch.ones(8256, device=DEV), 1e-6)
+    # mh_layernorm_bwd holds the row in registers: D > 8192 is MH_ERR_ARG (-1) at the entry itself, outputs untouched
+    dx, dxb = poisoned((M, 8196), F32, DEV), poisoned((M, 8196), BF16, DEV)
+    rc = ops._L().mh_layernorm_bwd(x8196.data_ptr(), x8196.data_ptr(), w.data_ptr(), 0, dx.data_ptr(), dxb.data_ptr(), M, 8196,
+                                   1e-6, torch.cuda.current_stream().cuda_stream)
+    assert rc == -1
+    with pytest.raises(_lib.MyriadHipError):
+        ops.layernorm_bwd(x8196, x8196, w, 1e-6)
     sync()
+    assert_untouched(dx, "layernorm_bwd dx at D = 8196"), assert_untouched(dxb, "layernorm_bwd dx bf16 at D = 8196")
     assert_untouched(out, "rmsnorm_fwd out after rejected launches")
 
 
