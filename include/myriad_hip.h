@@ -389,6 +389,35 @@ int mh_gemv_packed_fp8_rmsnorm(const float* H, long ldh, const float* norm_w, fl
                                int out_f32, float alpha, mh_stream_t s);
 int mh_gemv_packed_fp8_silu(const void* gu, long ldgu, const void* Q, const float* scale, void* C, int ldc, int M, int N, int K,
                             const float* bias, const float* residual, int ldr, int out_f32, float alpha, mh_stream_t s);
+/* MXFP4 weight-only copy for the decode step (opt-in; OCP microscaling, e2m1 codes).  The format, for W [N, K] bf16, finite,
+ * K % 128 == 0 (non-finite weights are outside the contract: their codes and scales are unspecified):
+ *   block  = 32 consecutive k within a row;
+ *   E      = the biased bf16 exponent field of the block's largest |w| (0 for a zero or subnormal maximum);
+ *   b      = max(2, E - 2), the scale byte, X = 2^(b-127): the OCP rule floor(log2 amax) - emax(e2m1), clamped below so that
+ *            every dequantised value is zero or a normal bf16; b <= 252;
+ *   code   = sign | index into {0, 0.5, 1, 1.5, 2, 3, 4, 6} of w / X rounded to nearest, ties to the even code, saturated at
+ *            +-6; the sign bit is copied from w, zeros included;
+ *   byte   = two codes, the lower k in the low nibble;   dq = code * X, exact in bf16.
+ * mh_gemv_pack_fp4 writes the codes in the stream order above at 128-deep steps (mh_gemv_pack_fp4_elems(N, K) bytes: lane
+ * (lr, lg) of wave w reads at step t the 32 codes k = 128 (w per + t) + 32 lg .. +31 of row 16 block + lr, 16 B at
+ * ((block*NW + w)*per + t)*1 KiB + lane*16, per = ceil(K / 128 / NW)) and the scale bytes beside them
+ * (mh_gemv_pack_fp4_scale_elems(N, K) bytes: that lane's byte at ((block*NW + w)*ceil(per / 4) + t / 4)*256 + lane*4 + t % 4).
+ * Steps past K and the bytes that pad a scale dword are zero blocks (codes 0, b = 2); rows past N repeat row N - 1.  Both
+ * _elems return -1 on N <= 0, K <= 0 or K % 128 != 0; the packer returns MH_ERR_ARG on those, on ldb < K or ldb % 8 != 0, a
+ * null scale_out, W / q_out not 16-byte or scale_out not 4-byte aligned, and writes nothing then.  The three fp4 products take
+ * the arguments and the contract of their fp8 forms (<= 16 rows, MH_ERR_UNSUPPORTED of the fused forms above the LDS budget)
+ * with the scale bytes in place of the row scales and K % 128 == 0, and compute C = alpha * A . dq(W)^T (+bias) (+residual):
+ * each pair of codes widened exactly to bf16 with its block scale, the same MFMA, no epilogue scale. */
+long mh_gemv_pack_fp4_elems(int N, int K);
+long mh_gemv_pack_fp4_scale_elems(int N, int K);
+int mh_gemv_pack_fp4(const void* W, int ldb, int N, int K, void* q_out, void* scale_out, mh_stream_t s);
+int mh_gemv_packed_fp4(const void* A, int lda, const void* Q, const void* scale, void* C, int ldc, int M, int N, int K,
+                       const float* bias, const float* residual, int ldr, int out_f32, float alpha, mh_stream_t s);
+int mh_gemv_packed_fp4_rmsnorm(const float* H, long ldh, const float* norm_w, float eps, const void* Q, const void* scale,
+                               void* C, int ldc, int M, int N, int K, const float* bias, const float* residual, int ldr,
+                               int out_f32, float alpha, mh_stream_t s);
+int mh_gemv_packed_fp4_silu(const void* gu, long ldgu, const void* Q, const void* scale, void* C, int ldc, int M, int N, int K,
+                            const float* bias, const float* residual, int ldr, int out_f32, float alpha, mh_stream_t s);
 /* q / v LoRA merged into the decode step's copy of the frozen qkv weight (opt-in, llama.py decode_merge_lora; PEFT merge_adapter).
  * W [3D, D] bf16 rows [q | k | v] with leading dimension ldw (the frozen columns of the bordered wqkv_ext), Aqv [2r, D] fp32 = the
  * masters A_q | A_v, Bq / Bv [D, r] fp32, s = alpha / r, r = 8 or 16.  Merged rule, per element:

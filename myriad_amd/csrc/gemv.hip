@@ -22,11 +22,22 @@
 // the same v_mfma_f32_16x16x32_bf16, so products and the fp32 accumulation are those of x . q exactly.  s_n is applied in the
 // epilogue, once per output column, after the cross-wave sum and BEFORE alpha:  v = (sum_k x q * s_n) * alpha (+bias)(+res).
 // Activations are never quantised.
+//
+// MXFP4 weight-only decode (opt-in, llama.py decode_fp4): a third packed copy, OCP microscaling e2m1 codes with one power-of-two
+// scale byte per 32 consecutive k of a row (mh_gemv_pack_fp4; the format rule is in include/myriad_hip.h).  A wave's step is
+// 128 deep: lane (lr, lg) holds k = 32*lg .. 32*lg+31 of it in 16 B, so one wave-instruction still reads one contiguous KiB
+// and a lane needs exactly one scale byte per step.  The scale bytes of four consecutive steps of a lane share one dword, so a
+// 16-step batch costs four scale loads beside its sixteen code loads.  Each pair of codes is widened to bf16 in registers by
+// v_cvt_scalef32_pk_bf16_fp4 with the block scale 2^(b-127) as its scale operand -- exact, every code * scale is a normal bf16
+// or zero -- and fed to four v_mfma_f32_16x16x32_bf16 per step: products and fp32 sums are those of x . dq(W), no epilogue scale.
 #include "common.h"
 #include "gemv_pack.h"
 #include <cstdlib>
 
 typedef unsigned char fp8_t;                                        // one OCP e4m3fn code
+struct fp4_t { unsigned char v; };                                  // two OCP e2m1 codes, the lower k in the low nibble
+template <typename WT> constexpr bool gv_is_fp4 = false;
+template <> constexpr bool gv_is_fp4<fp4_t> = true;
 typedef __attribute__((ext_vector_type(4))) unsigned gv_u4_t;
 
 // 8 e4m3fn codes (two dwords, k ascending from the low byte) -> 8 bf16 in MFMA operand order; exact
@@ -62,14 +73,54 @@ __device__ __forceinline__ float4_t gv_mfma(short8_t x0, short8_t x1, short8_t w
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1, w1, acc, 0, 0, 0);
 }
 
+// One lane's 128-deep fp4 step: x = its 32 activations (k = 32*lg .. +31 of the step, global memory or LDS), q = its 32 codes,
+// b = the block's scale byte.  Eight codes (one dword, one byte_sel each pair) make the B operand of one MFMA.
+__device__ __forceinline__ float4_t gv_mfma_fp4(const bf16_t* x, short8_t q16, unsigned b, float4_t acc) {
+  const gv_u4_t q = __builtin_bit_cast(gv_u4_t, q16);
+  const float sc = __uint_as_float(b << 23);                        // 2^(b-127), b in 2..252
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    gv_u4_t r;
+    r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q[i], sc, 0));
+    r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q[i], sc, 1));
+    r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q[i], sc, 2));
+    r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q[i], sc, 3));
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const short8_t*>(x + 8 * i), __builtin_bit_cast(short8_t, r), acc,
+                                                  0, 0, 0);
+  }
+  return acc;
+}
+// One batch of fp4 steps of a wave: n <= UNROLL live steps starting at step t0 of the wave's range (a multiple of 4; FULL: n =
+// UNROLL, no guards).  The load puts the raw codes (16 B per step) and the scale dwords (four steps each) in registers; the
+// product walks the steps in order, x = the lane's activations at the batch's first step (128 elements per step).
+template <int UNROLL, bool FULL>
+__device__ __forceinline__ void gv_fp4_load(const fp4_t* wp, const unsigned* sp, int t0, int n, short8_t (&w)[UNROLL],
+                                            unsigned (&sc)[UNROLL / 4]) {
+#pragma unroll
+  for (int u = 0; u < UNROLL; ++u)
+    if (FULL || u < n) w[u] = __builtin_nontemporal_load(reinterpret_cast<const short8_t*>(wp + (size_t)(t0 + u) * 1024));
+#pragma unroll
+  for (int g = 0; g < UNROLL / 4; ++g)
+    if (FULL || 4 * g < n) sc[g] = __builtin_nontemporal_load(sp + (size_t)(t0 / 4 + g) * 64);
+}
+template <int UNROLL, bool FULL>
+__device__ __forceinline__ float4_t gv_fp4_mfma(const bf16_t* x, int n, const short8_t (&w)[UNROLL], const unsigned (&sc)[UNROLL / 4],
+                                                float4_t acc) {
+#pragma unroll
+  for (int u = 0; u < UNROLL; ++u)
+    if (FULL || u < n) acc = gv_mfma_fp4(x + u * 128, w[u], (sc[u >> 2] >> (8 * (u & 3))) & 0xffu, acc);
+  return acc;
+}
+
 template <int MODE, int UNROLL, int GV_NW, typename WT = bf16_t>
 __global__ __launch_bounds__(GV_NW * 64) void gemv_kernel(const bf16_t* __restrict__ A, const WT* __restrict__ B,
                                                           void* __restrict__ Cv, const float* __restrict__ bias,
                                                           const float* res, int M, int N, int K, int lda, int ldb,
                                                           int ldc, int ldr, int out_f32, float alpha,
                                                           const float* __restrict__ wscale = nullptr) {
-  constexpr bool F8 = sizeof(WT) == 1;
-  static_assert(!F8 || MODE == 2, "fp8 weights come only as the packed copy");
+  constexpr bool F4 = gv_is_fp4<WT>, F8 = sizeof(WT) == 1 && !F4;
+  constexpr int KS = F4 ? 128 : 64;                                // k-depth of one step of the packed copy
+  static_assert(!(F8 || F4) || MODE == 2, "fp8 / fp4 weights come only as the packed copy");
   __shared__ float red[GV_NW][16 * 16];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lr = lane & 15, lg = lane >> 4;
@@ -107,39 +158,55 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_kernel(const bf16_t* __restri
     // KiB and a wave walks one contiguous region -- 6.8 TB/s against 5.8 TB/s for the row-strided order on a pure stream
     // (tools/micro/stream_pattern.hip), and bit-identical results (same k per lane, same reduction order).
     // The fp8 copy (mh_gemv_pack_fp8): ((block * NW + w) * per + t) * 1 KiB + lane * 16, one KiB per step.
-    const bf16_t* xp = A + (size_t)mrow * lda + lg * 16;
-    const int nsteps = K / 64;
+    // The fp4 copy (mh_gemv_pack_fp4): the same KiB per step at twice the depth, steps counted in 128; the scale bytes come as
+    // dwords from wscale: ((block * NW + w) * ceil(per / 4) + t / 4) * 256 B + lane * 4, byte t % 4.
+    const bf16_t* xp = A + (size_t)mrow * lda + lg * (KS / 4);
+    const int nsteps = K / KS;
     const int per = (nsteps + GV_NW - 1) / GV_NW;
     const WT* wp = B + ((size_t)blockIdx.x * GV_NW + wave) * per * 1024 + lane * (16 / sizeof(WT));
     int s = wave * per;
     const int s0 = s;
     const int s_end = (s + per) < nsteps ? (s + per) : nsteps;
-    for (; s + UNROLL <= s_end; s += UNROLL) {
-      short8_t w0[UNROLL], w1[UNROLL], x0[UNROLL], x1[UNROLL];
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int k = (s + u) * 64;
-        gv_load(wp, (size_t)(s - s0 + u), w0[u], w1[u]);
-        x0[u] = *reinterpret_cast<const short8_t*>(xp + k);
-        x1[u] = *reinterpret_cast<const short8_t*>(xp + k + 8);
+    if constexpr (F4) {
+      const unsigned* sp = reinterpret_cast<const unsigned*>(wscale) + ((size_t)blockIdx.x * GV_NW + wave) * ((per + 3) / 4) * 64 + lane;
+      short8_t w[UNROLL];
+      unsigned sc[UNROLL / 4];
+      for (; s + UNROLL <= s_end; s += UNROLL) {
+        gv_fp4_load<UNROLL, true>(wp, sp, s - s0, UNROLL, w, sc);
+        acc = gv_fp4_mfma<UNROLL, true>(xp + (size_t)s * 128, UNROLL, w, sc, acc);
       }
+      if (s < s_end) {                                 // remainder as one partial batch, same order
+        gv_fp4_load<UNROLL, false>(wp, sp, s - s0, s_end - s, w, sc);
+        acc = gv_fp4_mfma<UNROLL, false>(xp + (size_t)s * 128, s_end - s, w, sc, acc);
+      }
+    } else {
+      for (; s + UNROLL <= s_end; s += UNROLL) {
+        short8_t w0[UNROLL], w1[UNROLL], x0[UNROLL], x1[UNROLL];
 #pragma unroll
-      for (int u = 0; u < UNROLL; ++u) acc = gv_mfma<WT>(x0[u], x1[u], w0[u], w1[u], acc);
-    }
-    if (s < s_end) {                                   // remainder as one partial batch (loads in flight together), same order
-      const int rem = s_end - s;
-      short8_t w0[UNROLL], w1[UNROLL], x0[UNROLL], x1[UNROLL];
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u)
-        if (u < rem) {
+        for (int u = 0; u < UNROLL; ++u) {
           const int k = (s + u) * 64;
           gv_load(wp, (size_t)(s - s0 + u), w0[u], w1[u]);
           x0[u] = *reinterpret_cast<const short8_t*>(xp + k);
           x1[u] = *reinterpret_cast<const short8_t*>(xp + k + 8);
         }
 #pragma unroll
-      for (int u = 0; u < UNROLL; ++u)
-        if (u < rem) acc = gv_mfma<WT>(x0[u], x1[u], w0[u], w1[u], acc);
+        for (int u = 0; u < UNROLL; ++u) acc = gv_mfma<WT>(x0[u], x1[u], w0[u], w1[u], acc);
+      }
+      if (s < s_end) {                                   // remainder as one partial batch (loads in flight together), same order
+        const int rem = s_end - s;
+        short8_t w0[UNROLL], w1[UNROLL], x0[UNROLL], x1[UNROLL];
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u)
+          if (u < rem) {
+            const int k = (s + u) * 64;
+            gv_load(wp, (size_t)(s - s0 + u), w0[u], w1[u]);
+            x0[u] = *reinterpret_cast<const short8_t*>(xp + k);
+            x1[u] = *reinterpret_cast<const short8_t*>(xp + k + 8);
+          }
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u)
+          if (u < rem) acc = gv_mfma<WT>(x0[u], x1[u], w0[u], w1[u], acc);
+      }
     }
   } else {
     // 64-deep steps, lane holds k = 16*lg .. 16*lg+15 (32 contiguous bytes); wave w owns the contiguous K quarter
@@ -265,13 +332,15 @@ extern "C" int mh_gemv_pack(const void* W, int ldb, int N, int K, void* out, hip
 }
 
 // weights in flight per lane per batch: 8 steps of the bf16 copy (16 KiB per wave), 16 of the fp8 copy (the same 16 KiB)
+// (the fp4 copy: 16 steps of twice the depth, again 16 KiB)
 template <typename WT> struct GvUnroll { static constexpr int value = sizeof(WT) == 1 ? 16 : 8; };
+template <typename WT> constexpr int gv_kstep = gv_is_fp4<WT> ? 128 : 64;
 
 template <typename WT>
 static int launch_gemv_packed(const void* A, int lda, const void* P, const float* wscale, void* C, int ldc, int M, int N, int K,
                               const float* bias, const float* residual, int ldr, int out_f32, float alpha, hipStream_t stream) {
   if (M <= 0 || N <= 0) return MH_OK;
-  if (M > 16 || K <= 0 || (K % 64) != 0 || (lda % 8) != 0 || ((uintptr_t)A & 15) || ((uintptr_t)P & 15)) return MH_ERR_ARG;
+  if (M > 16 || K <= 0 || (K % gv_kstep<WT>) != 0 || (lda % 8) != 0 || ((uintptr_t)A & 15) || ((uintptr_t)P & 15)) return MH_ERR_ARG;
   constexpr int U = GvUnroll<WT>::value;
   const dim3 grid((N + 15) / 16);
   if (gv_packed_nw(N) == 8)
@@ -381,7 +450,8 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_pro_kernel(const void* __rest
                                                               int M, int N, int K, int ldc, int ldr, int out_f32, float alpha,
                                                               const float* __restrict__ norm_w, float eps,
                                                               const float* __restrict__ wscale = nullptr) {
-  constexpr bool F8 = sizeof(WT) == 1;
+  constexpr bool F4 = gv_is_fp4<WT>, F8 = sizeof(WT) == 1 && !F4;
+  constexpr int KS = F4 ? 128 : 64;                                // k-depth of one step of the packed copy
   extern __shared__ __attribute__((aligned(16))) char gsm[];
   bf16_t* xs = reinterpret_cast<bf16_t*>(gsm);                  // [M][K] operand rows
   __shared__ float red[GV_NW][16 * 16];
@@ -389,9 +459,12 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_pro_kernel(const void* __rest
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 15, lg = lane >> 4;
   const int n0 = blockIdx.x * 16;
-  const int nsteps = K / 64;
+  const int nsteps = K / KS;
   const int per = (nsteps + GV_NW - 1) / GV_NW;
   const WT* wp = B + ((size_t)blockIdx.x * GV_NW + wave) * per * 1024 + lane * (16 / sizeof(WT));
+  // fp4: this wave's scale dwords (gemv_kernel<2>); not read otherwise
+  const unsigned* sp =
+      F4 ? reinterpret_cast<const unsigned*>(wscale) + ((size_t)blockIdx.x * GV_NW + wave) * ((per + 3) / 4) * 64 + lane : nullptr;
   // The weight stream does not depend on the operand: the first UNROLL steps of it are put in flight BEFORE the rows are
   // built (every workgroup of a launch starts at the same time; without this the HBM pipe idles for the ~3 us the prologue
   // takes).  Vector loads retire in order, so what the prologue needs first -- the fp32 row and the norm weights -- is
@@ -401,6 +474,7 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_pro_kernel(const void* __rest
   const int s_end = (s + per) < nsteps ? (s + per) : nsteps;
   bool have = s + UNROLL <= s_end;
   short8_t w0[UNROLL], w1[UNROLL];
+  unsigned sc[UNROLL / 4];                                      // fp4 only
   float4_t hv[4];                                               // PRO 2: K <= 4096 (checked by the launcher)
   if (PRO == 2 && tid < 256) {
     const float* xr = reinterpret_cast<const float*>(Ain);
@@ -408,8 +482,11 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_pro_kernel(const void* __rest
     for (int i = tid * 4; i < K; i += 1024, ++c) hv[c] = *reinterpret_cast<const float4_t*>(xr + i);
   }
   if (have) {
+    if constexpr (F4) gv_fp4_load<UNROLL, true>(wp, sp, 0, UNROLL, w0, sc);
+    else {
 #pragma unroll
-    for (int u = 0; u < UNROLL; ++u) gv_load(wp, (size_t)u, w0[u], w1[u]);
+      for (int u = 0; u < UNROLL; ++u) gv_load(wp, (size_t)u, w0[u], w1[u]);
+    }
   }
   if (PRO == 1) {
     const bf16_t* gu = reinterpret_cast<const bf16_t*>(Ain);
@@ -453,36 +530,47 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_pro_kernel(const void* __rest
   }
   __syncthreads();
   const int mrow = lr < M ? lr : M - 1;
-  const bf16_t* xp = xs + (size_t)mrow * K + lg * 16;
+  const bf16_t* xp = xs + (size_t)mrow * K + lg * (KS / 4);
   float4_t acc = (float4_t){0.f, 0.f, 0.f, 0.f};
   while (have) {
+    if constexpr (F4) acc = gv_fp4_mfma<UNROLL, true>(xp + (size_t)s * 128, UNROLL, w0, sc, acc);
+    else {
 #pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const int k = (s + u) * 64;
-      const short8_t x0 = *reinterpret_cast<const short8_t*>(xp + k), x1 = *reinterpret_cast<const short8_t*>(xp + k + 8);
-      acc = gv_mfma<WT>(x0, x1, w0[u], w1[u], acc);
+      for (int u = 0; u < UNROLL; ++u) {
+        const int k = (s + u) * 64;
+        const short8_t x0 = *reinterpret_cast<const short8_t*>(xp + k), x1 = *reinterpret_cast<const short8_t*>(xp + k + 8);
+        acc = gv_mfma<WT>(x0, x1, w0[u], w1[u], acc);
+      }
     }
     s += UNROLL;
     have = s + UNROLL <= s_end;
     if (have) {
+      if constexpr (F4) gv_fp4_load<UNROLL, true>(wp, sp, s - s0, UNROLL, w0, sc);
+      else {
 #pragma unroll
-      for (int u = 0; u < UNROLL; ++u) gv_load(wp, (size_t)(s - s0 + u), w0[u], w1[u]);
+        for (int u = 0; u < UNROLL; ++u) gv_load(wp, (size_t)(s - s0 + u), w0[u], w1[u]);
+      }
     }
   }
   if (s < s_end) {
     // the remainder of this wave's K range (K = 11008: 22 steps = 2 batches + 6) as ONE partial batch: its loads fly together
     // instead of one load latency per step; same accumulation order
     const int rem = s_end - s;
+    if constexpr (F4) {
+      gv_fp4_load<UNROLL, false>(wp, sp, s - s0, rem, w0, sc);
+      acc = gv_fp4_mfma<UNROLL, false>(xp + (size_t)s * 128, rem, w0, sc, acc);
+    } else {
 #pragma unroll
-    for (int u = 0; u < UNROLL; ++u)
-      if (u < rem) gv_load(wp, (size_t)(s - s0 + u), w0[u], w1[u]);
+      for (int u = 0; u < UNROLL; ++u)
+        if (u < rem) gv_load(wp, (size_t)(s - s0 + u), w0[u], w1[u]);
 #pragma unroll
-    for (int u = 0; u < UNROLL; ++u)
-      if (u < rem) {
-        const int k = (s + u) * 64;
-        const short8_t x0 = *reinterpret_cast<const short8_t*>(xp + k), x1 = *reinterpret_cast<const short8_t*>(xp + k + 8);
-        acc = gv_mfma<WT>(x0, x1, w0[u], w1[u], acc);
-      }
+      for (int u = 0; u < UNROLL; ++u)
+        if (u < rem) {
+          const int k = (s + u) * 64;
+          const short8_t x0 = *reinterpret_cast<const short8_t*>(xp + k), x1 = *reinterpret_cast<const short8_t*>(xp + k + 8);
+          acc = gv_mfma<WT>(x0, x1, w0[u], w1[u], acc);
+        }
+    }
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) red[wave][(4 * lg + r) * 16 + lr] = acc[r];
@@ -513,7 +601,7 @@ static int launch_gemv_pro(const void* A, long lda, const void* P, void* C, int 
                            const float* residual, int ldr, int out_f32, float alpha, const float* norm_w, float eps,
                            hipStream_t stream, const float* wscale = nullptr) {
   if (M <= 0 || N <= 0) return MH_OK;
-  if (M > 16 || K <= 0 || (K % 64) != 0 || ((uintptr_t)A & 15) || ((uintptr_t)P & 15)) return MH_ERR_ARG;
+  if (M > 16 || K <= 0 || (K % gv_kstep<WT>) != 0 || ((uintptr_t)A & 15) || ((uintptr_t)P & 15)) return MH_ERR_ARG;
   if (sizeof(WT) == 1 && (!wscale || ((uintptr_t)wscale & 3))) return MH_ERR_ARG;
   if (PRO == 1 && ((K % 128) != 0 || (lda % 8) != 0 || lda < 2L * K)) return MH_ERR_ARG;
   if (PRO == 2 && (!norm_w || (K % 4) != 0 || (lda % 4) != 0)) return MH_ERR_ARG;
@@ -563,4 +651,92 @@ extern "C" int mh_gemv_packed_fp8_silu(const void* gu, long ldgu, const void* Q,
                                        int K, const float* bias, const float* residual, int ldr, int out_f32, float alpha,
                                        hipStream_t stream) {
   return launch_gemv_pro<1, fp8_t>(gu, ldgu, Q, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, nullptr, 0.f, stream, scale);
+}
+
+// ---- MXFP4 weight-only copy: block amax, scale byte, e2m1 codes and the stream order in one kernel --------------------------
+// Codes: mh_gemv_pack's order at half a byte per weight and 128-deep steps: lane (lr, lg) of wave w reads at step t the 32 codes
+// k = 128 t' + 32 lg .. +31 (t' = w * per + t, per = ceil(K / 128 / NW)) of row 16 * block + lr at
+// ((block * NW + w) * per + t) * 1 KiB + lane * 16, byte j = codes of k + 2j (low nibble) and k + 2j + 1.
+// Scale bytes: that lane's block at step t at ((block * NW + w) * ceil(per / 4) + t / 4) * 256 + lane * 4 + t % 4.
+// Steps past K / 128 (and the bytes that pad a scale dword) are zero blocks: codes 0, scale byte 2.  Rows past N repeat row N - 1.
+// One thread quantises one block: 64 B in, 16 B and one byte out (the rule: gemv_pack.h bf16_to_e2m1, include/myriad_hip.h).
+__global__ __launch_bounds__(256) void gemv_pack_fp4_kernel(const bf16_t* __restrict__ W, int ldb, int N, int K,
+                                                            unsigned char* __restrict__ out, unsigned char* __restrict__ scale_out,
+                                                            int nw, int per) {
+  const int nb = blockIdx.x, nsteps = K / 128, per4 = (per + 3) / 4;
+  const int chunks = nw * per4 * 4 * 64;
+  for (int c = threadIdx.x; c < chunks; c += 256) {
+    const int lane = c & 63, r = c >> 6;
+    const int t = r % (per4 * 4), q = r / (per4 * 4);
+    const int lr = lane & 15, lg = lane >> 4;
+    int row = nb * 16 + lr;
+    row = row < N ? row : N - 1;
+    const int step = q * per + t;
+    int b = 2;
+    gv_u4_t o = {0u, 0u, 0u, 0u};
+    if (t < per && step < nsteps) {
+      const bf16_t* src = W + (size_t)row * ldb + step * 128 + lg * 32;
+      short8_t v[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = *reinterpret_cast<const short8_t*>(src + 8 * i);
+      int amax = 0;                                                  // of the magnitude bits: monotonic in |w| for finite w
+#pragma unroll
+      for (int e = 0; e < 32; ++e) {
+        const int a = v[e >> 3][e & 7] & 0x7fff;
+        amax = a > amax ? a : amax;
+      }
+      b = mxfp4_scale_byte(amax >> 7);
+#pragma unroll
+      for (int e = 0; e < 32; ++e) o[e >> 3] |= bf16_to_e2m1((unsigned short)v[e >> 3][e & 7], b) << (4 * (e & 7));
+    }
+    scale_out[((size_t)(nb * nw + q) * per4 + (t >> 2)) * 256 + lane * 4 + (t & 3)] = (unsigned char)b;
+    if (t < per) *reinterpret_cast<gv_u4_t*>(out + (((size_t)(nb * nw + q) * per + t) * 64 + lane) * 16) = o;
+  }
+}
+
+static bool gv_fp4_dims(int N, int K) { return N > 0 && K > 0 && (K % 128) == 0; }
+
+extern "C" long mh_gemv_pack_fp4_elems(int N, int K) {
+  if (!gv_fp4_dims(N, K)) return -1;
+  const int nw = gv_packed_nw(N), per = (K / 128 + nw - 1) / nw;
+  return (long)((N + 15) / 16) * nw * per * 1024;
+}
+
+extern "C" long mh_gemv_pack_fp4_scale_elems(int N, int K) {
+  if (!gv_fp4_dims(N, K)) return -1;
+  const int nw = gv_packed_nw(N), per = (K / 128 + nw - 1) / nw;
+  return (long)((N + 15) / 16) * nw * ((per + 3) / 4) * 256;
+}
+
+extern "C" int mh_gemv_pack_fp4(const void* W, int ldb, int N, int K, void* q_out, void* scale_out, hipStream_t stream) {
+  if (!gv_fp4_dims(N, K) || (ldb % 8) != 0 || ldb < K || !scale_out || ((uintptr_t)W & 15) || ((uintptr_t)q_out & 15) ||
+      ((uintptr_t)scale_out & 3))
+    return MH_ERR_ARG;
+  const int nw = gv_packed_nw(N), per = (K / 128 + nw - 1) / nw;
+  hipLaunchKernelGGL(gemv_pack_fp4_kernel, dim3((N + 15) / 16), dim3(256), 0, stream, (const bf16_t*)W, ldb, N, K, (unsigned char*)q_out,
+                     (unsigned char*)scale_out, nw, per);
+  MH_CHECK_LAUNCH();
+  return MH_OK;
+}
+
+// C[M <= 16, N] = alpha * A . dq(W)^T (+bias) (+residual) with W given as its mh_gemv_pack_fp4 copy (codes, scale bytes); the
+// kernels take the scale stream through their wscale argument
+extern "C" int mh_gemv_packed_fp4(const void* A, int lda, const void* Q, const void* scale, void* C, int ldc, int M, int N, int K,
+                                  const float* bias, const float* residual, int ldr, int out_f32, float alpha, hipStream_t stream) {
+  if (M > 0 && N > 0 && (!scale || ((uintptr_t)scale & 3))) return MH_ERR_ARG;
+  return launch_gemv_packed<fp4_t>(A, lda, Q, (const float*)scale, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream);
+}
+
+extern "C" int mh_gemv_packed_fp4_rmsnorm(const float* H, long ldh, const float* norm_w, float eps, const void* Q, const void* scale,
+                                          void* C, int ldc, int M, int N, int K, const float* bias, const float* residual, int ldr,
+                                          int out_f32, float alpha, hipStream_t stream) {
+  return launch_gemv_pro<2, fp4_t>(H, ldh, Q, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, norm_w, eps, stream,
+                                   (const float*)scale);
+}
+
+extern "C" int mh_gemv_packed_fp4_silu(const void* gu, long ldgu, const void* Q, const void* scale, void* C, int ldc, int M, int N,
+                                       int K, const float* bias, const float* residual, int ldr, int out_f32, float alpha,
+                                       hipStream_t stream) {
+  return launch_gemv_pro<1, fp4_t>(gu, ldgu, Q, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, nullptr, 0.f, stream,
+                                   (const float*)scale);
 }

@@ -19,7 +19,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -35,6 +35,11 @@ def _f32(t: torch.Tensor, dev) -> torch.Tensor:
 def decode_fp8_from_env() -> bool:
     """The default of LlamaHIP.decode_fp8: MYRIAD_DECODE_FP8=1 turns the FP8 weight-only token step on (off when unset)."""
     return os.environ.get("MYRIAD_DECODE_FP8", "0") != "0"
+
+
+def decode_fp4_from_env() -> bool:
+    """The default of LlamaHIP.decode_fp4: MYRIAD_DECODE_FP4=1 turns the MXFP4 weight-only token step on (off when unset)."""
+    return os.environ.get("MYRIAD_DECODE_FP4", "0") != "0"
 
 
 def decode_merge_lora_from_env() -> bool:
@@ -110,6 +115,10 @@ class LlamaHIP:
         # the bf16 ones (ops.gemv_pack_fp8; half the bytes, weight rounding the only new error); off by default, the attribute
         # wins over MYRIAD_DECODE_FP8
         self.decode_fp8 = decode_fp8_from_env()
+        # the same with MXFP4 copies (ops.gemv_pack_fp4: e2m1 codes, one power-of-two scale byte per 32 k; 0.53 bytes per weight,
+        # 4-bit round-to-nearest weights the only new error); off by default, the attribute wins over MYRIAD_DECODE_FP4, and it
+        # excludes decode_fp8 (both on: ValueError when a decode call starts)
+        self.decode_fp4 = decode_fp4_from_env()
         # with LoRA attached, the packed token step streams W_qkv with the q/v LoRA merged in (PEFT merge_adapter on the decode copy
         # only: LoraQV.merge) instead of the bordered wqkv_ext -- four launches per layer instead of five, and fp8 under decode_fp8;
         # the prefill and steps above GEMV_MAX_ROWS rows keep the exact bordered LoRA.  Off by default, the attribute wins over
@@ -119,8 +128,24 @@ class LlamaHIP:
         self.decode_lora_version = None
         self._lora_merges = 0                                           # whole-model merges so far (last_generate_stats)
         self._packed = None                                             # the packed copies of the current kind (one of _packs)
-        self._packs = {}                                                # "bf16" / "fp8" -> packed copies, each built on first use
+        self._packs = {}                                                # "bf16" / "fp8" / "fp4" -> packed copies, each built on first use
+        self._merge_rows = None                                         # fp4 merge: the row-major merged qkv of one layer (scratch)
         self._decode_ws = {}
+
+    def _decode_kind(self) -> str:
+        """What the packed token step streams: "fp8" / "fp4" under decode_fp8 / decode_fp4, else "bf16"; both on is an error."""
+        if self.decode_fp8 and self.decode_fp4:
+            raise ValueError("decode_fp8 and decode_fp4 are both on: the token step streams one kind of weight copy, turn one off")
+        return "fp8" if self.decode_fp8 else "fp4" if self.decode_fp4 else "bf16"
+
+    def _pack_quantised(self, kind: str, w: torch.Tensor, what: str, out=None):
+        """The packed copy of one decoder matrix in `kind`; a matrix the fp4 packer does not take is an error that names it."""
+        if kind == "fp4":
+            if w.shape[1] % 128 != 0:
+                raise _lib.MyriadHipError(f"decode_fp4: {what} has K = {w.shape[1]}, the MXFP4 copy needs a multiple of 128 "
+                                          "(there is no fallback to another kind)")
+            return ops.gemv_pack_fp4(w, out=out)
+        return (ops.gemv_pack_fp8 if kind == "fp8" else ops.gemv_pack)(w, out=out)
 
     def _pack_for_decode(self) -> None:
         """(Re)build the packed copies the single-token step streams.  Frozen matrices are packed once; the bordered qkv
@@ -132,27 +157,38 @@ class LlamaHIP:
         With decode_merge_lora and LoRA attached the qkv entry is instead the [3D, D] copy with the q/v LoRA merged in
         (LoraQV.merge: fp8 under decode_fp8, bf16 otherwise), re-merged in place only when decode_lora_version is None or differs
         from the one it was merged for.  The bordered and the merged copies are both kept once built (the workspace key holds
-        which one the step reads), so flipping decode_merge_lora frees no buffer that a captured graph reads."""
-        kind = "fp8" if self.decode_fp8 else "bf16"
+        which one the step reads), so flipping decode_merge_lora frees no buffer that a captured graph reads.
+        decode_fp4 is decode_fp8 with MXFP4 copies (ops.gemv_pack_fp4) -- the same matrices, the same ones left bf16 -- except that
+        its merged qkv copy takes two launches per layer, ops.lora_merge into one row-major scratch and the packer."""
+        kind = self._decode_kind()
         merge = self.lora is not None and self.decode_merge_lora
         qkv_key = "wqkv" if self.lora is None else ("merged" if merge else "wqkv_ext")
         P = self._packs.get(kind)
         if P is None:
-            pack = ops.gemv_pack_fp8 if kind == "fp8" else ops.gemv_pack
             lm = next(iter(self._packs.values()))["lm_head"] if self._packs else ops.gemv_pack(self.lm_head)
-            P = dict(kind=kind, layers=[{k: pack(L[k]) for k in ("wo", "wgu", "wd")} for L in self.layers], lm_head=lm, qkv_key=None,
+            P = dict(kind=kind, layers=[{k: self._pack_quantised(kind, L[k], f"layer {i} {k}") for k in ("wo", "wgu", "wd")}
+                                        for i, L in enumerate(self.layers)], lm_head=lm, qkv_key=None,
                      qkv={}, merged_for=None, merge_id=None)
             self._packs[kind] = P
         copies = P["qkv"].get(qkv_key)
         if merge:
             ver = self.decode_lora_version
             if copies is None or ver is None or P["merged_for"] != ver:
-                copies = self.lora.merge(self.layers, kind, copies)
+                if kind == "fp4":
+                    rows = []
+                    for i, L in enumerate(self.layers):
+                        self._merge_rows = self.lora.merge_layer(i, L, "rows", self._merge_rows)
+                        rows.append(self._pack_quantised(kind, self._merge_rows, f"layer {i} merged wqkv",
+                                                         None if copies is None else copies[i]))
+                    copies = rows
+                else:
+                    copies = self.lora.merge(self.layers, kind, copies)
                 self._lora_merges += 1
                 P["merged_for"], P["merge_id"] = ver, self._lora_merges
         elif copies is None or self.lora is not None:
-            pack = ops.gemv_pack_fp8 if kind == "fp8" and self.lora is None else ops.gemv_pack
-            copies = [pack(L[qkv_key], out=None if copies is None else copies[i]) for i, L in enumerate(self.layers)]
+            qkind = kind if self.lora is None else "bf16"
+            copies = [self._pack_quantised(qkind, L[qkv_key], f"layer {i} {qkv_key}", None if copies is None else copies[i])
+                      for i, L in enumerate(self.layers)]
         P["qkv"][qkv_key] = copies
         for Pl, c in zip(P["layers"], copies):
             Pl["wqkv"] = c
@@ -162,9 +198,10 @@ class LlamaHIP:
     def _prepare_decode_weights(self, rows: int) -> dict:
         """Before a decode call at `rows` rows: the LoRA's bordered weights refreshed, the packed copies (re)built when the step
         can stream them (MYRIAD_PACK_DECODE=0 drops them: the step streams the row-major matrices).  Returns last_generate_stats'
-        decode_weights ("fp8" / "bf16": what the token step streams) and decode_weight_bytes (the weight bytes of one token step:
-        the packed copies, fp8 scales included, up to GEMV_MAX_ROWS rows; the row-major bf16 matrices above), lora_merged (the
+        decode_weights ("fp8" / "fp4" / "bf16": what the token step streams) and decode_weight_bytes (the weight bytes of one token
+        step: the packed copies, fp8 row scales / fp4 scale bytes included, up to GEMV_MAX_ROWS rows; the row-major bf16 matrices above), lora_merged (the
         step streams the LoRA-merged qkv copy) and lora_merges (whole-model merges this model has made so far)."""
+        self._decode_kind()                                             # both kinds on: an error whatever this call streams
         if self.lora is not None:
             self.lora.refresh(self.layers)
         if self.pack_decode and rows <= ops.GEMV_MAX_ROWS:
@@ -173,8 +210,8 @@ class LlamaHIP:
             self._packed, self._packs = None, {}
         if _packed_step(self, rows):
             mats = [P[k] for P in self._packed["layers"] for k in ("wqkv", "wo", "wgu", "wd")] + [self._packed["lm_head"]]
-            nbytes = sum(m.data.numel() * m.data.element_size() + (m.scales.numel() * 4 if isinstance(m, ops.PackedFp8Weight) else 0)
-                         for m in mats)
+            nbytes = sum(m.data.numel() * m.data.element_size()
+                         + (m.scales.numel() * m.scales.element_size() if hasattr(m, "scales") else 0) for m in mats)
             return dict(decode_weights=self._packed["kind"], decode_weight_bytes=int(nbytes),
                         lora_merged=self._packed["qkv_key"] == "merged", lora_merges=self._lora_merges)
         qkv_key = "wqkv" if self.lora is None else "wqkv_ext"
@@ -874,7 +911,7 @@ class DecodeSession:
     know, recorded as a key that matches nothing).
 
     The whole cache is dropped (full prefill, `last_stats["full_reprefill_reason"]`) when the caller's weights version changes
-    (optimiser update, state-dict load), when the decode weights change kind (bf16 / fp8, LoRA on / off, the LoRA-merged qkv copy
+    (optimiser update, state-dict load), when the decode weights change kind (bf16 / fp8 / fp4, LoRA on / off, the LoRA-merged qkv copy
     on / off or re-merged: "decode weights changed"), when the batch size changes, when the capacity (round_up(need + 2, 64), at
     most 8192) is exceeded, or when the caller says so (`reset_reason`: the chat's truncation window moved)."""
 

@@ -224,6 +224,40 @@ def gemv_pack_fp8(w: torch.Tensor, out: Optional[PackedFp8Weight] = None) -> Pac
     return out
 
 
+class PackedFp4Weight:
+    """MXFP4 weight-only copy of a frozen [N, K] bf16 weight for the decode kernel (mh_gemv_pack_fp4): e2m1 codes, two per byte,
+    in the stream order of PackedWeight at 128-deep steps (`data`, uint8) and one power-of-two scale byte per 32 consecutive k of
+    a row beside them (`scales`, uint8, in the stream order of include/myriad_hip.h)."""
+    __slots__ = ("data", "scales", "N", "K")
+
+    def __init__(self, data: torch.Tensor, scales: torch.Tensor, N: int, K: int):
+        self.data, self.scales, self.N, self.K = data, scales, N, K
+
+
+def gemv_pack_fp4(w: torch.Tensor, out: Optional[PackedFp4Weight] = None) -> PackedFp4Weight:
+    """Quantise w [N, K] (finite, K % 128 == 0) to MXFP4 -- per block of 32 k the scale byte b = max(2, E - 2) of the block's
+    largest exponent field E and the e2m1 codes of w / 2^(b-127), nearest, ties to the even code, saturated at +-6 -- and permute
+    codes and scale bytes into the order the skinny-M kernel streams them in; `out` re-uses an earlier copy's storage."""
+    _chk2d(w, BF16, "gemv_pack_fp4.w")
+    N, K = w.shape
+    n, ns = _L().mh_gemv_pack_fp4_elems(N, K), _L().mh_gemv_pack_fp4_scale_elems(N, K)
+    if n < 0 or ns < 0:
+        raise _lib.MyriadHipError(f"gemv_pack_fp4: unsupported dims N={N} K={K} (K must be a multiple of 128)")
+    if out is None:
+        out = PackedFp4Weight(torch.empty((n,), dtype=torch.uint8, device=w.device),
+                              torch.empty((ns,), dtype=torch.uint8, device=w.device), N, K)
+    elif not isinstance(out, PackedFp4Weight) or (out.N, out.K) != (N, K):
+        raise _lib.MyriadHipError("gemv_pack_fp4: out was packed for another shape")
+    _lib.check(_L().mh_gemv_pack_fp4(_p(w), w.stride(0), N, K, _p(out.data), _p(out.scales), _s()), "mh_gemv_pack_fp4")
+    return out
+
+
+def _packed_entry(base: str, pw) -> str:
+    """The library entry of a packed product for this weight class: base, base with _fp8 or with _fp4 after mh_gemv_packed."""
+    kind = "_fp8" if isinstance(pw, PackedFp8Weight) else "_fp4" if isinstance(pw, PackedFp4Weight) else ""
+    return "mh_gemv_packed" + kind + base
+
+
 def _lora_merge_args(w: torch.Tensor, a_qv: torch.Tensor, b_q: torch.Tensor, b_v: torch.Tensor, name: str):
     """(D, r) of a merge: w [3D, D] bf16 (unit inner stride, any leading dimension: the frozen columns of wqkv_ext), a_qv [2r, D]
     and b_q / b_v [D, r] fp32 with contiguous rows."""
@@ -285,7 +319,8 @@ def lora_merge_pack_fp8(w: torch.Tensor, a_qv: torch.Tensor, b_q: torch.Tensor, 
 def gemv_packed(a: torch.Tensor, pw, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
                 residual: Optional[torch.Tensor] = None, out_dtype=BF16, alpha: float = 1.0) -> torch.Tensor:
     """out[M <= GEMV_MAX_ROWS, N] = alpha * a @ W^T (+bias) (+residual f32) with W given as its packed copy; same bits as gemm().
-    A PackedFp8Weight runs the fp8 kernel: alpha * s_n * a @ q^T, q widened exactly to bf16."""
+    A PackedFp8Weight runs the fp8 kernel: alpha * s_n * a @ q^T, q widened exactly to bf16; a PackedFp4Weight the fp4 kernel:
+    alpha * a @ dq(W)^T, each code widened exactly to bf16 with its block scale."""
     _chk2d(a, BF16, "gemv_packed.a")
     M, K = a.shape
     if K != pw.K or M > GEMV_MAX_ROWS:
@@ -297,10 +332,11 @@ def gemv_packed(a: torch.Tensor, pw, out: Optional[torch.Tensor] = None, bias: O
     if residual is not None:
         _chk2d(residual, F32, "gemv_packed.residual")
         ldr = residual.stride(0)
-    if isinstance(pw, PackedFp8Weight):
-        rc = _L().mh_gemv_packed_fp8(_p(a), a.stride(0), _p(pw.data), _p(pw.scales), _p(out), out.stride(0), M, pw.N, K, _p(bias),
-                                     _p(residual), ldr, 1 if out.dtype == F32 else 0, float(alpha), _s())
-        _lib.check(rc, f"mh_gemv_packed_fp8 M={M} N={pw.N} K={K}")
+    if isinstance(pw, (PackedFp8Weight, PackedFp4Weight)):
+        name = _packed_entry("", pw)
+        rc = getattr(_L(), name)(_p(a), a.stride(0), _p(pw.data), _p(pw.scales), _p(out), out.stride(0), M, pw.N, K, _p(bias),
+                                 _p(residual), ldr, 1 if out.dtype == F32 else 0, float(alpha), _s())
+        _lib.check(rc, f"{name} M={M} N={pw.N} K={K}")
         return out
     rc = _L().mh_gemv_packed(_p(a), a.stride(0), _p(pw.data), _p(out), out.stride(0), M, pw.N, K, _p(bias), _p(residual), ldr,
                              1 if out.dtype == F32 else 0, float(alpha), _s())
@@ -315,7 +351,7 @@ def _gemv_pro(fn, name, a, lda, pw, out, residual, out_dtype, alpha, M, *pre):
     if residual is not None:
         _chk2d(residual, F32, name + ".residual")
         ldr = residual.stride(0)
-    wargs = (_p(pw.data), _p(pw.scales)) if isinstance(pw, PackedFp8Weight) else (_p(pw.data),)
+    wargs = (_p(pw.data), _p(pw.scales)) if isinstance(pw, (PackedFp8Weight, PackedFp4Weight)) else (_p(pw.data),)
     rc = fn(_p(a), lda, *pre, *wargs, _p(out), out.stride(0), M, pw.N, pw.K, None, _p(residual), ldr,
             1 if out.dtype == F32 else 0, float(alpha), _s())
     if rc == -3:                                   # MH_ERR_UNSUPPORTED: the operand rows do not fit the kernel's LDS budget
@@ -333,7 +369,7 @@ def gemv_packed_rmsnorm(h: torch.Tensor, norm_w: torch.Tensor, eps: float, pw, o
     M, K = h.shape
     if K != pw.K or M > GEMV_MAX_ROWS:
         raise _lib.MyriadHipError(f"gemv_packed_rmsnorm: h is {tuple(h.shape)}, weight was packed as [{pw.N}, {pw.K}]")
-    name = "mh_gemv_packed_fp8_rmsnorm" if isinstance(pw, PackedFp8Weight) else "mh_gemv_packed_rmsnorm"
+    name = _packed_entry("_rmsnorm", pw)
     return _gemv_pro(getattr(_L(), name), name, h, h.stride(0), pw, out, residual, out_dtype, alpha, M, _p(norm_w), float(eps))
 
 
@@ -344,7 +380,7 @@ def gemv_packed_silu(gu: torch.Tensor, pw, out=None, residual=None, out_dtype=BF
     M = gu.shape[0]
     if gu.shape[1] != 2 * pw.K or M > GEMV_MAX_ROWS:
         raise _lib.MyriadHipError(f"gemv_packed_silu: gu is {tuple(gu.shape)}, weight was packed as [{pw.N}, {pw.K}]")
-    name = "mh_gemv_packed_fp8_silu" if isinstance(pw, PackedFp8Weight) else "mh_gemv_packed_silu"
+    name = _packed_entry("_silu", pw)
     return _gemv_pro(getattr(_L(), name), name, gu, gu.stride(0), pw, out, residual, out_dtype, alpha, M)
 
 

@@ -4,10 +4,12 @@ python tools/decode_bench.py [--batch 1] [--new 32] [--sample] [--penalty P] [--
 --sample: the chat call's do_sample=True, top_p=0.9, top_k=50 (drawn on the device when MYRIAD_DEVICE_SAMPLING=1, else on the
 host); --modes times several decodes in one process, interleaved per repeat: greedy, host (sampled, host draw), device (sampled,
 device draw), beam (num_beams = --beams, which also times greedy at batch * beams: the same row count); --penalty adds
-repetition_penalty to every mode but beam.  --weights bf16,fp8 times each mode with the token step streaming bf16 and FP8 weight
-copies (LlamaHIP.decode_fp8), interleaved in the same way; without it the kind is MYRIAD_DECODE_FP8's.  --merge 0,1 (with --lora 1)
+repetition_penalty to every mode but beam.  --weights bf16,fp8,fp4 times each mode with the token step streaming bf16, FP8
+and MXFP4 weight copies (LlamaHIP.decode_fp8 / decode_fp4), interleaved in the same way; without it the kind is the one
+MYRIAD_DECODE_FP8 / MYRIAD_DECODE_FP4 set.  --merge 0,1 (with --lora 1)
 times each of those with the bordered LoRA qkv product and with the LoRA merged into the step's qkv copy
-(LlamaHIP.decode_merge_lora), interleaved again, and reports the one-time cost of merging every layer (bf16 and fp8 copies)."""
+(LlamaHIP.decode_merge_lora), interleaved again, and reports the one-time cost of packing every decoder matrix into each kind named by --weights and of merging every layer (bf16,
+fp8 and fp4 copies)."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -24,14 +26,14 @@ ap.add_argument("--penalty", type=float, default=1.0, help="repetition_penalty")
 ap.add_argument("--modes", default="", help="comma list of greedy / host / device, timed interleaved in one process")
 ap.add_argument("--repeats", type=int, default=1)
 ap.add_argument("--beams", type=int, default=4, help="num_beams of the beam mode")
-ap.add_argument("--weights", default="", help="comma list of bf16 / fp8: the token step's weight copies, timed interleaved")
+ap.add_argument("--weights", default="", help="comma list of bf16 / fp8 / fp4: the token step's weight copies, timed interleaved")
 ap.add_argument("--merge", default="", help="comma list of 0 / 1: bordered / merged LoRA qkv in the token step, timed interleaved")
 a = ap.parse_args()
 modes = [m for m in a.modes.split(",") if m] or ["sample" if a.sample else "greedy"]
 if "beam" in modes and "greedy" in modes:
     modes.append("greedy_x%d" % a.beams)             # greedy at batch * beams rows: the beam step's row count
 kinds = [w for w in a.weights.split(",") if w] or [None]
-assert all(w in (None, "bf16", "fp8") for w in kinds), kinds
+assert all(w in (None, "bf16", "fp8", "fp4") for w in kinds), kinds
 merges = [int(m) for m in a.merge.split(",") if m] or [None]
 assert all(m in (None, 0, 1) for m in merges), merges
 assert a.lora or merges == [None], "--merge needs --lora 1"
@@ -52,7 +54,7 @@ def make_samples(n):
 smp = make_samples(B)
 smp_rows = make_samples(B * a.beams) if "beam" in modes else None
 default_dev = model.llama.device_sampling
-default_fp8 = model.llama.decode_fp8
+default_fp8, default_fp4 = model.llama.decode_fp8, model.llama.decode_fp4
 default_merge = model.llama.decode_merge_lora
 
 
@@ -68,6 +70,7 @@ def run(n, mode, kind=None, merge=None):
         kw["repetition_penalty"] = a.penalty
     model.llama.device_sampling = {"host": False, "device": True}.get(mode, default_dev)
     model.llama.decode_fp8 = default_fp8 if kind is None else kind == "fp8"
+    model.llama.decode_fp4 = default_fp4 if kind is None else kind == "fp4"
     model.llama.decode_merge_lora = default_merge if merge is None else bool(merge)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -103,22 +106,53 @@ for m, w, mg in runs:
           f"min {ts[0]*1e3:.3f}, max {ts[-1]*1e3:.3f}) -> {rows / per_tok:.1f} row-tok/s steady; weight stream "
           f"{wb / 1e9:.2f} GB/token, {wb / per_tok / 1e12:.2f} TB/s of 6.3 achievable{extra}")
 
-if a.lora and 1 in merges:
-    # one-time cost of a merge of every layer (what generate() pays when the LoRA weights moved), median of --repeats
+if kinds != [None]:
+    # one-time cost of packing wo, gate|up and down of every layer (and wqkv without LoRA) into each kind, median of --repeats
     L = model.llama
-    for kind in ("bf16", "fp8"):
-        outs = L.lora.merge(L.layers, kind)
+    names = ("wo", "wgu", "wd") + (() if a.lora else ("wqkv",))
+    for kind in kinds:
+        outs = [L._pack_quantised(kind, Lr[k], k) for Lr in L.layers for k in names]
         ts = []
         for _ in range(max(3, a.repeats)):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            L.lora.merge(L.layers, kind, outs)
+            it = iter(outs)
+            for Lr in L.layers:
+                for k in names:
+                    L._pack_quantised(kind, Lr[k], k, next(it))
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        ts.sort()
+        rd = sum(Lr[k].numel() * 2 for Lr in L.layers for k in names)
+        print(f"pack of {len(outs)} matrices into the {kind} copy: {ts[len(ts) // 2] * 1e3:.3f} ms (median of {len(ts)}, min "
+              f"{ts[0] * 1e3:.3f}); {rd / 1e9:.2f} GB of bf16 rows read")
+        del outs
+
+if a.lora and 1 in merges:
+    # one-time cost of a merge of every layer (what generate() pays when the LoRA weights moved), median of --repeats
+    L = model.llama
+    for kind in ("bf16", "fp8", "fp4"):
+        def merge_all(outs=None, kind=kind):
+            if kind != "fp4":
+                return L.lora.merge(L.layers, kind, outs)
+            res = []                                  # two launches per layer: the row-major merge into one scratch, then the packer
+            for i, Lr in enumerate(L.layers):
+                L._merge_rows = L.lora.merge_layer(i, Lr, "rows", L._merge_rows)
+                res.append(L._pack_quantised(kind, L._merge_rows, "merged wqkv", None if outs is None else outs[i]))
+            return res
+        outs = merge_all()
+        ts = []
+        for _ in range(max(3, a.repeats)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            merge_all(outs)
             torch.cuda.synchronize()
             ts.append(time.perf_counter() - t0)
         ts.sort()
         D, nl = L.D, len(L.layers)
-        rd, wr = nl * 3 * D * D * 2 * (2 if kind == "fp8" else 1), nl * 3 * D * D * (1 if kind == "fp8" else 2)
+        rd = nl * 3 * D * D * 2 * (2 if kind != "bf16" else 1)
+        wr = nl * 3 * D * D * {"bf16": 2, "fp8": 1, "fp4": 2.53}[kind]        # fp4: the bf16 rows, then codes and scale bytes
         print(f"merge of {nl} layers into the {kind} copy: {ts[len(ts) // 2] * 1e3:.3f} ms (median of {len(ts)}, min "
-              f"{ts[0] * 1e3:.3f}); W read {rd / 1e9:.2f} GB (fp8: two passes), written {wr / 1e9:.2f} GB -> "
+              f"{ts[0] * 1e3:.3f}); W read {rd / 1e9:.2f} GB (fp8: two passes; fp4: W, then the merged rows), written {wr / 1e9:.2f} GB -> "
               f"{(rd + wr) / ts[len(ts) // 2] / 1e12:.2f} TB/s")
         del outs
