@@ -43,6 +43,8 @@ def parse_args(argv=None):
     parser.add_argument("--world", type=int, default=1)
     parser.add_argument("--rank", type=int, default=0)
     parser.add_argument("--limit", type=int, default=0, help="evaluate only the first N batches (smoke runs)")
+    parser.add_argument("--slots", type=int, default=0, help="N > 0: stream the test set through N decode slots "
+                        "(model.generate_stream: per-sample positions and stop rule); 0: one generate() per batch")
     return parser.parse_args(argv)
 
 
@@ -97,6 +99,8 @@ def main(argv=None):
                        "min_length": 1, "top_p": 0.01, "temperature": 1.0}           # evaluation_aqa_dataset.py:289-301
 
     model.eval()
+    if args.slots > 0:
+        return save_path, _run_slots(args, model, loader, generate_kwargs, save_path)
     records, all_time, sampled = [], 0.0, 0
     for testid, data_sample in enumerate(loader):
         if testid < args.start:
@@ -124,6 +128,46 @@ def main(argv=None):
     if sampled:
         print(f"note: {sampled} generated tokens had p_max < top_p and were drawn, not arg-maxed (see LlamaHIP.greedy_generate)")
     return save_path, records
+
+
+def _run_slots(args, model, loader, generate_kwargs, save_path):
+    """The evaluation loop over model.generate_stream: the same records, in the dataset's order."""
+    import torch
+    from myriad_amd import eval_protocol as EP
+
+    meta = []                                            # per sample, in input order: what its record needs besides the text
+
+    def batches():
+        for testid, data_sample in enumerate(loader):
+            if testid < args.start:
+                continue
+            if args.limit and testid >= args.start + args.limit:
+                break
+            for ind in range(len(data_sample["image_id"])):
+                meta.append((int(data_sample["image_id"][ind]), data_sample["img_path"][ind], bool(data_sample["is_anomaly"][ind])))
+            yield data_sample
+
+    records = []
+    with torch.no_grad():
+        t1 = time.time()
+        for out in model.generate_stream(batches(), slots=args.slots, **generate_kwargs):
+            text = EP.postprocess_generation(out["token_ids"][None], model.llama_tokenizer)[0]
+            amax = None
+            if out["ve_anomaly_map"] is not None:        # anomaly_map_handler (:93-104): uint8(map * 255) then max
+                amax = float((out["ve_anomaly_map"].detach().float().cpu() * 255.0).to(torch.uint8).max())
+            records.append(EP.make_ad_record(*meta[out["index"]], text, amax))
+        torch.cuda.synchronize()
+        all_time = time.time() - t1
+    EP.write_jsonl(save_path, records)
+    st = model.last_generate_stats
+    n_batches = max(1, len(records) // max(1, args.bs))
+    print("CUDA Memory:", torch.cuda.max_memory_allocated() / (1024 * 1024))
+    print("Mean Time: ", all_time / n_batches, f" decode slots {args.slots}: occupancy {st.get('occupancy', 0.0):.3f} over "
+          f"{st.get('steps', 0)} token steps, {st.get('prefills', 0)} prefills")
+    if st.get("host_sampled_rows"):
+        print(f"note: {st['host_sampled_rows']} generated tokens had p_max < top_p and were drawn, not arg-maxed "
+              "(see LlamaHIP.greedy_generate)")
+    return records
 
 
 if __name__ == "__main__":

@@ -304,6 +304,10 @@ int mh_repetition_penalty_rows(float* logits, long ldl, unsigned* seen, const lo
 /* mh_decode_advance with the sampler's kept count as a fourth record row: rec[4][R] f32 = (ids, margins, p_max, kept) */
 int mh_decode_advance_kept(const long* nxt, const float* margin, const float* pmax, const int* kept, float* rec, long* next_ids,
                            int* step, int* pos, int* kvlen, int R, mh_stream_t s);
+/* mh_decode_advance under a row mask (the slot engine's token step, live int[R] on the device): a row with live[r] != 0 advances
+   as above; an idle row records (-1, 0, 0) and keeps next_ids[r], pos[r] and kvlen[r].  *step += 1 once per launch. */
+int mh_decode_advance_rows(const long* nxt, const float* margin, const float* pmax, float* rec, long* next_ids, int* step,
+                           int* pos, int* kvlen, const int* live, int R, mh_stream_t s);
 
 /* beam search step (HF GenerationMixin._beam_search), nb <= 8 beams, K = 2*nb, 2*nb <= V <= 32768 (else MH_ERR_UNSUPPORTED):
    rows b*rpi .. b*rpi+rpi-1 of fp32 logits [B*rpi, ldl] belong to item b (rpi = nb, or 1 for the step after a prefill at B rows);
@@ -442,6 +446,13 @@ int mh_lora_merge_pack_fp8(const void* W, int ldw, const float* Aqv, const float
 int mh_attn_decode_rope(void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
                         const int* pos_dev, const int* kv_len, const float* cos_tab, const float* sin_tab, void* out, long ldo,
                         int B, int H, int D, int T_cap, float scale, mh_stream_t s);
+/* The same token step with per-row state (decode slots): row b rotates q / k at pos[b] and appends k | v at cache row pos[b]
+ * (the host keeps pos[b] < T_cap), the query sees kv_len[b] keys; a live row's out, rotated q and cache row have the bits of
+ * mh_attn_decode_rope on that row alone with pos_dev[0] = pos[b].  live int[B] on the device: a row with live[b] == 0 reads no
+ * cache row, writes neither qkv nor the cache, and gets a zero out row. */
+int mh_attn_decode_rope_rows(void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
+                             const int* kv_len, const int* live, const float* cos_tab, const float* sin_tab, void* out, long ldo,
+                             int B, int H, int D, int T_cap, float scale, mh_stream_t s);
 /* The same token step with the keys split into chunks (attn_decode_split.hip): grid (ceil(T_cap / chunk), B*H), each workgroup
  * scores one chunk and writes fp32 (m, l, o[D]) into `partials`, a second launch merges the chunks in order and writes bf16 out
  * (bits fixed from run to run).  q is rotated in registers (qkv is not written); the cache row at pos_dev[0] gets the bits

@@ -48,7 +48,8 @@ struct AttnParams {
   const float* cs;
   const float* sn;
   const int* pos;       // [B] rotary position of the new token
-  const int* pos_dev;   // [1] cache row the new token is appended at
+  const int* pos_dev;   // [1] cache row the new token is appended at ([B], one per row, in the rows form)
+  const int* live;      // rows form (mh_attn_decode_rope_rows) only: [B], 0 = the row is idle
   // attention-probability dropout (trainable Q-Former, mh_attn_fwd_dropout / mh_attn_bwd_dropout): keep of (b, h, query i,
   // key j) = dropout_keep(drop_seed, ((b * H + h) * Sq + i) * Sk + j); 0 everywhere else (the kernels skip it)
   float drop_p;
@@ -459,11 +460,20 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnParams p) {
 //   softmax: every wave reduces the LDS scores itself (len <= a few hundred)
 //   PV: lane owns two head dims, waves take keys round-robin, up to 8 independent 256-B row loads in flight per wave
 // fp32 throughout (the tile kernel rounds P to bf16 for its MFMA), output rounded to bf16 once.
+// ROWS (mh_attn_decode_rope_rows, the slot engine's token step): every batch row carries its own state -- it appends at cache
+// row pos_dev[b] (< T_cap: the host's to keep) instead of the shared pos_dev[0], and a row with live[b] == 0 touches
+// neither qkv nor the cache and writes a zero output row.  live[b] is uniform over the workgroup, so the idle exit is a
+// scalar branch taken by all 16 waves, ahead of the first barrier.  ROWS = false compiles to the code it was before.
 #define DNW 16
+template <bool ROWS>
 __global__ __launch_bounds__(DNW * 64) void attn_decode_kernel(AttnParams p) {
   extern __shared__ float dsm[];                 // [Sk] scores, then [DNW][128] partial outputs
   const int b = blockIdx.x / p.H, h = blockIdx.x % p.H;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (ROWS && !p.live[b]) {
+    if (wave == 0 && 2 * lane < p.D) *reinterpret_cast<unsigned*>(p.o + (size_t)b * p.o_bs + h * p.D + 2 * lane) = 0u;
+    return;
+  }
   int len = p.kv_len ? p.kv_len[b] : p.Sk;
   len = len < p.Sk ? len : p.Sk;
   const int D = p.D;
@@ -472,7 +482,7 @@ __global__ __launch_bounds__(DNW * 64) void attn_decode_kernel(AttnParams p) {
     // token (modeling_llama.py:186-195), same arithmetic (fp32 rotate-half, one rounding to bf16), per (b, h) here
     const int half = D >> 1, items = half >> 2, W = p.H * D;
     bf16_t* src = p.qkv + (size_t)b * p.ld_qkv;
-    bf16_t* crow = const_cast<bf16_t*>(p.k) + (size_t)b * p.k_bs + (size_t)p.pos_dev[0] * p.ldk;
+    bf16_t* crow = const_cast<bf16_t*>(p.k) + (size_t)b * p.k_bs + (size_t)p.pos_dev[ROWS ? b : 0] * p.ldk;
     if (tid < 2 * items) {
       const int which = tid / items, i = (tid % items) * 4;
       bf16_t* e = src + which * W + h * D + i;
@@ -686,7 +696,7 @@ extern "C" int mh_attn_fwd(const void* q, const void* k, const void* v, void* o,
   p.bias = bias; p.kv_len = kv_len; p.causal = causal;
   if (Sq == 1 && !bias && Sk <= 8192 && (ldv % 2) == 0) {   // KV-cache decode (causal or not: the one query sees every valid key)
     const size_t sh = (((size_t)Sk + 63) & ~(size_t)63) * 4 + DNW * 128 * 4;
-    hipLaunchKernelGGL(attn_decode_kernel, dim3(B * H), dim3(DNW * 64), sh, stream, p);
+    hipLaunchKernelGGL(attn_decode_kernel<false>, dim3(B * H), dim3(DNW * 64), sh, stream, p);
     MH_CHECK_LAUNCH();
     return MH_OK;
   }
@@ -701,11 +711,10 @@ extern "C" int mh_attn_fwd(const void* q, const void* k, const void* v, void* o,
 // One decode token: rotary on q / k, k | v appended to the cache at row pos_dev[0], attention of the one query over
 // kv_len[b] keys -- mh_rope_kv_append + mh_attn_fwd(Sq = 1) in one launch, bit-identical to the pair.
 // qkv [B, ld_qkv] bf16 = [q | k | v] (q is rotated in place); cache [B][T_cap][2W] bf16 rows [k | v]; out [B, W] bf16.
-extern "C" int mh_attn_decode_rope(void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
-                                   const int* pos_dev, const int* kv_len, const float* cos_tab, const float* sin_tab, void* out,
-                                   long ldo, int B, int H, int D, int T_cap, float scale, hipStream_t stream) {
-  if (B <= 0) return MH_OK;
-  if (!qkv || !cache || !pos || !pos_dev || !kv_len || !cos_tab || !sin_tab || !out) return MH_ERR_ARG;
+// live == nullptr: every row appends at pos_dev[0]; otherwise the rows form (pos_dev is per row, see attn_decode_kernel)
+static int launch_decode_rope(void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
+                              const int* pos_dev, const int* kv_len, const int* live, const float* cos_tab, const float* sin_tab,
+                              void* out, long ldo, int B, int H, int D, int T_cap, float scale, hipStream_t stream) {
   if (D % 8 || D > 128 || (D >> 1) % 4 || ld_qkv % 8 || ld_cache % 8 || cache_bstride % 8 || ldo % 4 || T_cap <= 0 || T_cap > 8192)
     return MH_ERR_ARG;
   const int W = H * D;
@@ -715,11 +724,33 @@ extern "C" int mh_attn_decode_rope(void* qkv, long ld_qkv, void* cache, long cac
   p.q_bs = ld_qkv; p.k_bs = cache_bstride; p.v_bs = cache_bstride; p.o_bs = ldo;
   p.ldq = (int)ld_qkv; p.ldk = (int)ld_cache; p.ldv = (int)ld_cache; p.ldo = (int)ldo;
   p.scale = scale; p.causal = 0; p.q_off = T_cap - 1;
-  p.qkv = (bf16_t*)qkv; p.ld_qkv = ld_qkv; p.cs = cos_tab; p.sn = sin_tab; p.pos = pos; p.pos_dev = pos_dev;
+  p.qkv = (bf16_t*)qkv; p.ld_qkv = ld_qkv; p.cs = cos_tab; p.sn = sin_tab; p.pos = pos; p.pos_dev = pos_dev; p.live = live;
   const size_t sh = (((size_t)T_cap + 63) & ~(size_t)63) * 4 + DNW * 128 * 4;
-  hipLaunchKernelGGL(attn_decode_kernel, dim3(B * H), dim3(DNW * 64), sh, stream, p);
+  if (live) hipLaunchKernelGGL(attn_decode_kernel<true>, dim3(B * H), dim3(DNW * 64), sh, stream, p);
+  else hipLaunchKernelGGL(attn_decode_kernel<false>, dim3(B * H), dim3(DNW * 64), sh, stream, p);
   MH_CHECK_LAUNCH();
   return MH_OK;
+}
+
+extern "C" int mh_attn_decode_rope(void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
+                                   const int* pos_dev, const int* kv_len, const float* cos_tab, const float* sin_tab, void* out,
+                                   long ldo, int B, int H, int D, int T_cap, float scale, hipStream_t stream) {
+  if (B <= 0) return MH_OK;
+  if (!qkv || !cache || !pos || !pos_dev || !kv_len || !cos_tab || !sin_tab || !out) return MH_ERR_ARG;
+  return launch_decode_rope(qkv, ld_qkv, cache, cache_bstride, ld_cache, pos, pos_dev, kv_len, nullptr, cos_tab, sin_tab, out, ldo,
+                            B, H, D, T_cap, scale, stream);
+}
+
+// The same token step with per-row state (the slot engine): row b rotates and appends at pos[b] (< T_cap, the host's to keep),
+// attends over kv_len[b] keys; a row with live[b] == 0 reads no cache row, leaves qkv and the cache alone and gets out = 0.
+// A live row's bits are those of mh_attn_decode_rope on that row alone with pos_dev[0] = pos[b].
+extern "C" int mh_attn_decode_rope_rows(void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
+                                        const int* kv_len, const int* live, const float* cos_tab, const float* sin_tab, void* out,
+                                        long ldo, int B, int H, int D, int T_cap, float scale, hipStream_t stream) {
+  if (B <= 0) return MH_OK;
+  if (!qkv || !cache || !pos || !kv_len || !live || !cos_tab || !sin_tab || !out) return MH_ERR_ARG;
+  return launch_decode_rope(qkv, ld_qkv, cache, cache_bstride, ld_cache, pos, pos, kv_len, live, cos_tab, sin_tab, out, ldo, B, H,
+                            D, T_cap, scale, stream);
 }
 
 extern "C" int mh_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout,

@@ -238,6 +238,38 @@ extern "C" int mh_decode_advance(const long* nxt, const float* margin, const flo
   MH_CHECK_LAUNCH();
   return MH_OK;
 }
+// decode_advance_kernel for the slot engine: only rows with live[r] != 0 advance; an idle row records id = -1 with margin and
+// p_max 0 and keeps its next id, position and length.
+__global__ void decode_advance_rows_kernel(const long* __restrict__ nxt, const float* __restrict__ margin,
+                                           const float* __restrict__ pmax, float* __restrict__ rec, long* __restrict__ next_ids,
+                                           int* __restrict__ step, int* __restrict__ pos, int* __restrict__ kvlen,
+                                           const int* __restrict__ live, int R) {
+  for (int r = threadIdx.x; r < R; r += blockDim.x) {
+    if (live[r]) {
+      const long id = nxt[r];
+      rec[r] = (float)id;
+      rec[R + r] = margin[r];
+      rec[2 * R + r] = pmax[r];
+      next_ids[r] = id;
+      pos[r] += 1;
+      kvlen[r] += 1;
+    } else {
+      rec[r] = -1.f;
+      rec[R + r] = 0.f;
+      rec[2 * R + r] = 0.f;
+    }
+  }
+  if (threadIdx.x == 0) *step += 1;
+}
+extern "C" int mh_decode_advance_rows(const long* nxt, const float* margin, const float* pmax, float* rec, long* next_ids, int* step,
+                                      int* pos, int* kvlen, const int* live, int R, hipStream_t stream) {
+  if (R <= 0) return MH_OK;
+  if (!nxt || !margin || !pmax || !rec || !next_ids || !step || !pos || !kvlen || !live) return MH_ERR_ARG;
+  hipLaunchKernelGGL(decode_advance_rows_kernel, dim3(1), dim3(64), 0, stream, nxt, margin, pmax, rec, next_ids, step, pos, kvlen,
+                     live, R);
+  MH_CHECK_LAUNCH();
+  return MH_OK;
+}
 extern "C" int mh_decode_record(const long* nxt, const float* margin, const float* pmax, float* rec, long* next_ids, int* step,
                                 int R, hipStream_t stream) {
   if (R <= 0) return MH_OK;

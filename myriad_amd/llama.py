@@ -405,14 +405,18 @@ class LlamaHIP:
         return self._pos_cache[key]
 
     # ------------------------------------------------------------------ generation
-    def _decode_block(self, h, B, S, caches, scale, pos, past=None, pos_dev=None, kvlen_dev=None, split_ws=None):
+    def _decode_block(self, h, B, S, caches, scale, pos, past=None, pos_dev=None, kvlen_dev=None, split_ws=None, live=None):
         """All decoder layers for a prefill chunk (host-known `past`: the chunk's rows go to cache rows past..past+S-1, `pos` holds
         their rotary positions, and causal masking is aligned to the bottom right) or for one decode token whose position lives
         in device memory (`pos_dev`/`kvlen_dev`), which makes the launch sequence replayable from a hipGraph.  `split_ws` (the
-        partials buffer of ops.attn_decode_split_ws) makes the fused token step use the split-KV attention kernel."""
+        partials buffer of ops.attn_decode_split_ws) makes the fused token step use the split-KV attention kernel.  `live` (int32
+        [B] on the device, the slot engine's) makes it the rows kernel instead: every row appends at its own pos[b], idle rows
+        are skipped; only the fused step has that form."""
         H, hd, W, D = self.H, self.hd, self.D, self.D
         M = B * S
         packed = self._packed["layers"] if pos_dev is not None and _packed_step(self, M) else None
+        if live is not None and not (packed is not None and self.decode_fused and split_ws is None):
+            raise ValueError("per-row decode state needs the fused packed token step with the single-workgroup attention")
         # the bordered LoRA product unless the packed qkv copy has the LoRA merged in (decode_merge_lora)
         lora = None if packed is not None and self._packed["qkv_key"] == "merged" else self.lora
 
@@ -442,7 +446,9 @@ class LlamaHIP:
                     qkv = ops.gemv_packed_rmsnorm(h, L["ln1"], self.eps, P["wqkv"])
                     if qkv is None:
                         qkv = ops.gemv_packed(ops.rmsnorm_fwd(h, L["ln1"], self.eps), P["wqkv"])
-                if split_ws is not None:
+                if live is not None:
+                    o = ops.attn_decode_rope_rows(qkv, cache, pos, kvlen_dev, live, self.cos, self.sin, H, hd, scale)
+                elif split_ws is not None:
                     o = ops.attn_decode_rope_split(qkv, cache, pos, pos_dev, kvlen_dev, self.cos, self.sin, H, hd, scale, split_ws)
                 else:
                     o = ops.attn_decode_rope(qkv, cache, pos, pos_dev, kvlen_dev, self.cos, self.sin, H, hd, scale)
@@ -511,7 +517,7 @@ class LlamaHIP:
         ops.embed_gather(self.embed, ws["ids"], ws["x_in"])
         rows = ws["x_in"].shape[0]
         h = self._decode_block(ws["x_in"], rows, 1, ws["caches"], 1.0 / math.sqrt(self.hd), ws["pos"], pos_dev=ws["pos"],
-                               kvlen_dev=ws["kvlen"], split_ws=ws["split"])
+                               kvlen_dev=ws["kvlen"], split_ws=ws["split"], live=ws.get("live"))
         if _packed_step(self, rows) and self.decode_fused:
             if ops.gemv_packed_rmsnorm(h, self.norm, self.eps, self._packed["lm_head"], out=ws["logits"], out_dtype=F32) is not None:
                 return
@@ -610,19 +616,7 @@ class LlamaHIP:
             ws["seed"].fill_(int(torch.randint(0, 2**63 - 1, (1,), generator=generator)))
 
         def sample_row(logits_row: torch.Tensor, ban: int) -> int:
-            """HF TopPLogitsWarper + multinomial on one row (host)."""
-            lg = logits_row.float().cpu() * inv_temp
-            if ban >= 0:
-                lg[ban] = float("-inf")
-            if top_k and 0 < top_k < lg.numel():                     # HF applies TopKLogitsWarper (default top_k = 50) before top-p
-                lg = lg.masked_fill(lg < torch.topk(lg, top_k).values[-1], float("-inf"))
-            srt, idx = torch.sort(lg, descending=False)
-            cum = srt.softmax(-1).cumsum(-1)
-            remove = cum <= (1.0 - top_p)
-            remove[-1:] = False                                      # min_tokens_to_keep = 1
-            srt = srt.masked_fill(remove, float("-inf"))
-            probs = torch.zeros_like(lg).scatter(0, idx, srt.softmax(-1))
-            return int(torch.multinomial(probs, 1, generator=generator))
+            return _host_draw(logits_row, ban, inv_temp, top_k, top_p, generator)
 
         def record(nxt: torch.Tensor, mar: torch.Tensor, pm: torch.Tensor, ban: int, logits_of=None, kept=None):
             """Host bookkeeping of one step's picks.  Returns (done, redrawn): redrawn = a live row was re-drawn on the host
@@ -826,8 +820,29 @@ class LlamaHIP:
         stats.update(sequences_scores=scores, finished_hypotheses=int(is_fin.sum()), lengths=[len(q) for q in seqs])
         return (ids, scores) if return_scores else ids
 
+    def slot_decoder(self, slots: int, capacity: int) -> "SlotDecoder":
+        """A decode-slot engine over this model: `slots` rows of one captured token step, each decoding its own request of up to
+        `capacity` positions (prompt + generated).  See SlotDecoder."""
+        return SlotDecoder(self, slots, capacity)
+
     def embed_tokens_into(self, ids: torch.Tensor, out2d: torch.Tensor, dst_rows: Optional[torch.Tensor] = None):
         ops.embed_gather(self.embed, ids, out2d, dst_rows)
+
+
+def _host_draw(logits_row: torch.Tensor, ban: int, inv_temp: float, top_k: int, top_p: float, generator) -> int:
+    """HF TopKLogitsWarper + TopPLogitsWarper + multinomial on one row (host)."""
+    lg = logits_row.float().cpu() * inv_temp
+    if ban >= 0:
+        lg[ban] = float("-inf")
+    if top_k and 0 < top_k < lg.numel():                             # HF applies TopKLogitsWarper (default top_k = 50) before top-p
+        lg = lg.masked_fill(lg < torch.topk(lg, top_k).values[-1], float("-inf"))
+    srt, idx = torch.sort(lg, descending=False)
+    cum = srt.softmax(-1).cumsum(-1)
+    remove = cum <= (1.0 - top_p)
+    remove[-1:] = False                                              # min_tokens_to_keep = 1
+    srt = srt.masked_fill(remove, float("-inf"))
+    probs = torch.zeros_like(lg).scatter(0, idx, srt.softmax(-1))
+    return int(torch.multinomial(probs, 1, generator=generator))
 
 
 # Decode helpers shared by LlamaHIP and DecodeSession.  They read only the model's fields, so the session needs no more of the
@@ -1007,3 +1022,221 @@ class DecodeSession:
         st = self.llama.last_generate_stats
         self.last_stats.update(steps=st["steps"], graph_replays=st["graph_replays"], graph_captures=self.graph_captures)
         return out
+
+
+class SlotScheduler:
+    """The bookkeeping of a decode-slot run, on plain Python values (no device in sight, so a scripted step can drive it): which
+    free slot takes which request, each slot's own ids and margins, when a slot finishes -- EOS, a stop sequence at the end of
+    ITS ids (kept in the output, as greedy_generate keeps row 0's), or max_new_tokens -- and the order results leave in.
+
+    One round of a run: `admit` requests into `free()` slots until none is free or the requests run out (a request whose first
+    pick already ends it never occupies a slot), then, while `live()`, one token step whose per-slot picks go to `step`.
+    `pop()` hands out finished (index, ids, margins): in completion order, or with `ordered` in admission (= input) order, a
+    result waiting for every earlier one."""
+
+    def __init__(self, slots: int, max_new_tokens: int, stop_ids=(), eos_id: int = 2, ordered: bool = False):
+        if slots < 1 or max_new_tokens < 1:
+            raise ValueError(f"slots and max_new_tokens must be >= 1, got {slots} and {max_new_tokens}")
+        self.slots, self.max_new_tokens, self.eos_id, self.ordered = int(slots), int(max_new_tokens), int(eos_id), bool(ordered)
+        self.stops = [tuple(int(t) for t in st) for st in stop_ids]
+        self.rows = [None] * self.slots                              # per slot: [index, ids, margins] while it decodes
+        self.admitted = 0
+        self._done, self._next_out = {}, 0
+        self.steps = self.live_row_steps = 0
+
+    def free(self) -> list:
+        return [s for s in range(self.slots) if self.rows[s] is None]
+
+    def live(self) -> list:
+        return [s for s in range(self.slots) if self.rows[s] is not None]
+
+    def _ended(self, ids: list) -> bool:
+        return (ids[-1] == self.eos_id or len(ids) >= self.max_new_tokens
+                or any(len(ids) >= len(st) and tuple(ids[-len(st):]) == st for st in self.stops))
+
+    def _finish(self, row) -> None:
+        self._done[row[0]] = (row[0], row[1], row[2])
+
+    def admit(self, slot: int, first_id: int, margin: float) -> bool:
+        """The next request (index = how many were admitted before it) with its prefill pick.  True: it decodes on in `slot`."""
+        if self.rows[slot] is not None:
+            raise ValueError(f"slot {slot} is busy")
+        row = [self.admitted, [int(first_id)], [float(margin)]]
+        self.admitted += 1
+        if self._ended(row[1]):
+            self._finish(row)
+            return False
+        self.rows[slot] = row
+        return True
+
+    def step(self, ids, margins) -> list:
+        """One token step's picks, indexed by slot (idle slots' entries are ignored).  Returns the slots that finished."""
+        live = self.live()
+        self.steps += 1
+        self.live_row_steps += len(live)
+        finished = []
+        for s in live:
+            row = self.rows[s]
+            row[1].append(int(ids[s]))
+            row[2].append(float(margins[s]))
+            if self._ended(row[1]):
+                self._finish(row)
+                self.rows[s] = None
+                finished.append(s)
+        return finished
+
+    def pop(self) -> list:
+        if not self.ordered:
+            out = [self._done.pop(k) for k in list(self._done)]      # dicts keep insertion (= completion) order
+        else:
+            out = []
+            while self._next_out in self._done:
+                out.append(self._done.pop(self._next_out))
+                self._next_out += 1
+        return out
+
+    @property
+    def occupancy(self) -> float:
+        return self.live_row_steps / (self.steps * self.slots) if self.steps else 0.0
+
+
+class SlotDecoder:
+    """Streams requests through `slots` rows of ONE captured token step (LlamaHIP.slot_decoder).  Each slot holds one request with
+    its own prompt length, position and stop rule; a slot whose request ends is refilled with the next one while the others go on
+    decoding, so no row is computed and thrown away for long and no request is cut short by another's stop.
+
+    The step is greedy_generate's fused packed step (bf16 / FP8 / MXFP4 copies, merged or bordered LoRA alike) with two launches
+    swapped: the attention is mh_attn_decode_rope_rows (row b appends at pos[b], idle rows skipped) and the bookkeeping is
+    mh_decode_advance_rows (idle rows record id -1).  A refill is the existing B = 1 prefill into the slot's slice of every cache.
+    Between two replays the host writes only a finished slot's live flag, a refilled slot's (id, pos, kvlen, live) and a host
+    draw's id.  greedy_generate and its row-0 rule are untouched; this path is opt-in."""
+
+    def __init__(self, llama: "LlamaHIP", slots: int, capacity: int):
+        slots = int(slots)
+        if slots < 1 or slots > ops.GEMV_MAX_ROWS:
+            raise ValueError(f"slots={slots}: the slot engine runs the packed token step, 1 to {ops.GEMV_MAX_ROWS} rows")
+        self.llama, self.slots = llama, slots
+        self.T_cap = ops.round_up(int(capacity), 64)
+        if not 0 < self.T_cap <= 8192:
+            raise ValueError(f"capacity={capacity}: a slot holds at most 8192 positions")
+        self.bufs = None                                             # the step's buffers, shared by every view
+        self.views = {}                                              # inv_temp -> workspace view of bufs with its own graph
+        self.ws = None                                               # the view of the current / last run
+        self._weights = None
+        self.graph_captures = 0
+        self.last_stats = {}
+
+    def _workspace(self, inv_temp: float) -> dict:
+        """The step's buffers, kept while the decode weights stay the ones the captured graphs read, and over them one view (its
+        own graph / warm flag) per inv_temp: the arg-max kernel takes inv_temp as a launch argument, so a captured step is fixed
+        to one value (LlamaHIP._decode_workspace keys its workspaces the same way)."""
+        L = self.llama
+        L._prepare_decode_weights(self.slots)
+        if not (_packed_step(L, self.slots) and L.decode_fused):
+            raise ValueError("the slot engine needs the fused packed token step (MYRIAD_PACK_DECODE and MYRIAD_DECODE_FUSED on)")
+        wid = _decode_weights_id(L)
+        if self.bufs is None or self._weights != wid:
+            self.bufs, self.views, self.ws = None, {}, None
+            self.bufs = _decode_buffers(L, self.slots, self.T_cap)
+            self.bufs["live"] = torch.zeros((self.slots,), dtype=torch.int32, device=L.dev)
+            self._weights = wid
+        key = float(inv_temp)
+        if key not in self.views:
+            if len(self.views) >= 4:                                 # a few temperatures at most: drop the oldest graph
+                self.views.pop(next(iter(self.views)))
+            self.views[key] = dict(self.bufs, graph=None, warm=False)
+        self.ws = self.views[key]
+        return self.ws
+
+    @torch.no_grad()
+    def run(self, requests, max_new_tokens: int = 90, stop_ids=((835,), (2277, 29937)), eos_id: int = 2, min_length: int = 1,
+            do_sample: bool = False, top_p: float = 1.0, temperature: float = 1.0, top_k: int = 50,
+            generator: Optional[torch.Generator] = None, ordered: bool = False):
+        """Decode every request of `requests` (an iterable of [S0_i, D] f32 embeddings, lengths free) and yield
+        (index, ids[L_i] int64 on the CPU, margins[L_i] f32) as each finishes -- or, with `ordered`, in input order.  The
+        arguments are greedy_generate's; the stop rule is per request.  `last_stats` holds the run's counters."""
+        L = self.llama
+        if min_length > 1:
+            raise NotImplementedError("decode slots: min_length > 1 needs a per-row ban, which the captured step does not have")
+        if do_sample and L.device_sampling:
+            raise NotImplementedError("decode slots: device sampling is not supported (rows below top_p are drawn on the host)")
+        if do_sample and not float(temperature) > 0:
+            raise ValueError(f"temperature must be > 0 when sampling, got {temperature}")
+        inv_temp = 1.0 / float(temperature) if do_sample else 1.0
+        top_k = 0 if top_k is None else int(top_k)
+        ws = self._workspace(inv_temp)
+        sched = SlotScheduler(self.slots, max_new_tokens, stop_ids, eos_id, ordered=ordered)
+        stats = dict(steps=0, graph_replays=0, graph_captures=self.graph_captures, prefills=0, live_row_steps=0, occupancy=0.0,
+                     host_sampled_rows=0)
+        self.last_stats = stats
+        ban0 = eos_id if 0 < min_length else -1
+        rec = ws["rec"][:3]
+        ws["live"].zero_()                                           # an abandoned run may have left slots live
+        ws["step"].zero_()
+
+        def token_step(_ban):
+            L._step_logits(ws)
+            ops.argmax_pmax_rows(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ban_id=-1, inv_temp=inv_temp)
+            ops.decode_advance_rows(ws["nxt"], ws["mar"], ws["pmx"], rec, ws["ids"], ws["step"], ws["pos"], ws["kvlen"], ws["live"])
+
+        def results():
+            for index, ids, mar in sched.pop():
+                yield index, torch.tensor(ids, dtype=torch.long), torch.tensor(mar, dtype=F32)
+
+        def refill(s: int, emb: torch.Tensor) -> None:
+            """Prefill one request alone into slot s and take its first pick; the slot goes live if the request goes on."""
+            S0 = emb.shape[0]
+            if emb.dim() != 2 or S0 < 1 or S0 + max_new_tokens > min(self.T_cap, L.cos.shape[0]):
+                raise ValueError(f"request of shape {tuple(emb.shape)} + max_new_tokens {max_new_tokens} does not fit a slot of "
+                                 f"{min(self.T_cap, L.cos.shape[0])} positions")
+            logits0 = L._prefill(emb[None].to(L.dev), [c[s:s + 1] for c in ws["caches"]])
+            stats["prefills"] += 1
+            sl = slice(s, s + 1)
+            ops.argmax_pmax_rows(logits0, ws["nxt"][sl], ws["mar"][sl], ws["pmx"][sl], ban_id=ban0, inv_temp=inv_temp)
+            first, mar, pm = torch.cat([ws["nxt"][sl].to(torch.float64), ws["mar"][sl].double(), ws["pmx"][sl].double()]).tolist()
+            first = int(first)                                       # one device->host copy for the three
+            if do_sample and pm < top_p:
+                first = _host_draw(logits0[0], ban0, inv_temp, top_k, top_p, generator)
+                stats["host_sampled_rows"] += 1
+            if sched.admit(s, first, mar):
+                ws["ids"][sl].fill_(first)
+                ws["pos"][sl].fill_(S0)                              # position of the incoming token
+                ws["kvlen"][sl].fill_(S0 + 1)                        # valid keys after the append
+                ws["live"][sl].fill_(1)
+
+        it, more = iter(requests), True
+        try:
+            while True:
+                for s in sched.free():
+                    while more and sched.rows[s] is None:
+                        try:
+                            emb = next(it)
+                        except StopIteration:
+                            more = False
+                            break
+                        refill(s, emb)
+                yield from results()
+                live = sched.live()
+                if not live:
+                    break
+                before = ws["graph"]
+                L._launch_step(ws, token_step, -1, True, stats)
+                if ws["graph"] is not before:
+                    self.graph_captures += 1
+                r = rec.cpu()                                        # the one device->host copy of the step (it also waits for it)
+                ids = r[0].long().tolist()
+                if do_sample:
+                    for s in live:
+                        if float(r[2][s]) < top_p:                   # greedy_generate's rule per row: below top_p the host draws
+                            ids[s] = _host_draw(ws["logits"][s], -1, inv_temp, top_k, top_p, generator)
+                            stats["host_sampled_rows"] += 1
+                finished = sched.step(ids, r[1].tolist())
+                for s in live:
+                    if s in finished:
+                        ws["live"][s:s + 1].zero_()
+                    elif ids[s] != int(r[0][s]):
+                        ws["ids"][s:s + 1].fill_(ids[s])             # a host draw replaces the arg-max the step fed back
+                yield from results()
+        finally:
+            stats.update(steps=sched.steps, live_row_steps=sched.live_row_steps, occupancy=sched.occupancy,
+                         graph_captures=self.graph_captures)

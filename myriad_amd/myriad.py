@@ -276,6 +276,9 @@ class MyriadHIP(nn.Module):
         self.max_txt_len = cfg.get("max_txt_len", 160)
         self.end_sym = cfg.get("end_sym", "###")
         self.k_shot = cfg.get("k_shot", 0)
+        # generate_stream's decode slots: positions (prompt + generated) one slot's KV cache holds, and the engine once built
+        self.slot_capacity = int(cfg.get("slot_capacity", 512))
+        self._slot_decoder = None
         self.fixed_stage = cfg.get("fixed_stage", None)        # None => random.choice like the reference
         self.fixed_taskstage = cfg.get("fixed_taskstage", None)
         self.bos_id, self.pad_id = cfg.get("bos_token_id", 1), cfg.get("pad_token_id", 2)
@@ -1170,30 +1173,8 @@ class MyriadHIP(nn.Module):
             if shard is not None:
                 dp.gather_params(self.store.flat_p, skip=done) if done else dp.gather_params(self.store.flat_p)
 
-    @torch.no_grad()
-    def generate(self, samples, **generate_kwargs):
-        """`Myriad.generate` (myriad.py:433-454): stage-1 prompt layout, then the HF `generate(inputs_embeds=..., **kw)`
-        contract for the arguments the evaluation script passes (evaluation_aqa_dataset.py:289-301):
-        max_new_tokens, stopping_criteria (a list whose items carry `.stops` = id tensors, conversation.py:96-107, applied
-        to batch row 0), do_sample + top_p + temperature (see LlamaHIP.greedy_generate: arg-max whenever p_max >= top_p,
-        a host-side draw otherwise), min_length, use_cache.  Anything that would change the decoding rule and is not
-        implemented raises instead of being ignored.
-
-        Also the chat call's sampling knobs (conversation.py:144-168): top_k (HF default 50; 0 / None = no top-k),
-        temperature (> 0 when sampling) and `generator`.  With `self.llama.device_sampling` (MYRIAD_DEVICE_SAMPLING=1, off by
-        default) and 1 <= top_k <= 1024 every draw happens on the device inside the captured token step, reproducible per seed
-        (drawn once per call from `generator`) but not bit-comparable with torch.multinomial; otherwise rows with p_max < top_p
-        are drawn on the host.  The same switch enables repetition_penalty (> 0; HF's rule over the generated ids, applied on
-        the device before every pick, greedy or sampled); with it off a penalty other than 1 raises as before.
-
-        num_beams > 1 (with do_sample=False) runs HF's beam search (LlamaHIP.beam_generate) and then also takes length_penalty,
-        early_stopping (True / False / "never") and num_return_sequences (<= num_beams, else ValueError): token_ids is
-        [B * num_return_sequences, L], item-major, best first, and last_generate_stats gains num_beams, sequences_scores,
-        finished_hypotheses and graph_replays.  Beam search applies the stop sequences per hypothesis, greedy / sampled decoding
-        keeps the reference's row-0 rule.  Refused with beams: do_sample (beam sampling), repetition_penalty != 1 and
-        num_beams > 8.  Without beams, length_penalty / num_return_sequences other than 1 raise NotImplementedError and
-        early_stopping is an unknown argument, as before."""
-        self.finish_update()
+    def _generate_args(self, generate_kwargs) -> dict:
+        """generate()'s keyword arguments, checked and with their defaults (its docstring states the contract)."""
         kw = dict(generate_kwargs)
         stops = kw.pop("stop_ids", None)
         crit = kw.pop("stopping_criteria", None)
@@ -1255,6 +1236,39 @@ class MyriadHIP(nn.Module):
         generator = kw.pop("generator", None)
         if kw:
             raise TypeError(f"generate() got unsupported arguments: {sorted(kw)}")
+        return dict(stops=stops, max_new=max_new, max_len=None if max_new is not None else max_len, do_sample=do_sample,
+                    top_p=top_p, temperature=temperature, min_length=min_length, eos_id=eos_id, top_k=top_k, rep_pen=rep_pen,
+                    num_beams=num_beams, beam_kw=beam_kw, generator=generator)
+
+    @torch.no_grad()
+    def generate(self, samples, **generate_kwargs):
+        """`Myriad.generate` (myriad.py:433-454): stage-1 prompt layout, then the HF `generate(inputs_embeds=..., **kw)`
+        contract for the arguments the evaluation script passes (evaluation_aqa_dataset.py:289-301):
+        max_new_tokens, stopping_criteria (a list whose items carry `.stops` = id tensors, conversation.py:96-107, applied
+        to batch row 0), do_sample + top_p + temperature (see LlamaHIP.greedy_generate: arg-max whenever p_max >= top_p,
+        a host-side draw otherwise), min_length, use_cache.  Anything that would change the decoding rule and is not
+        implemented raises instead of being ignored.
+
+        Also the chat call's sampling knobs (conversation.py:144-168): top_k (HF default 50; 0 / None = no top-k),
+        temperature (> 0 when sampling) and `generator`.  With `self.llama.device_sampling` (MYRIAD_DEVICE_SAMPLING=1, off by
+        default) and 1 <= top_k <= 1024 every draw happens on the device inside the captured token step, reproducible per seed
+        (drawn once per call from `generator`) but not bit-comparable with torch.multinomial; otherwise rows with p_max < top_p
+        are drawn on the host.  The same switch enables repetition_penalty (> 0; HF's rule over the generated ids, applied on
+        the device before every pick, greedy or sampled); with it off a penalty other than 1 raises as before.
+
+        num_beams > 1 (with do_sample=False) runs HF's beam search (LlamaHIP.beam_generate) and then also takes length_penalty,
+        early_stopping (True / False / "never") and num_return_sequences (<= num_beams, else ValueError): token_ids is
+        [B * num_return_sequences, L], item-major, best first, and last_generate_stats gains num_beams, sequences_scores,
+        finished_hypotheses and graph_replays.  Beam search applies the stop sequences per hypothesis, greedy / sampled decoding
+        keeps the reference's row-0 rule.  Refused with beams: do_sample (beam sampling), repetition_penalty != 1 and
+        num_beams > 8.  Without beams, length_penalty / num_return_sequences other than 1 raise NotImplementedError and
+        early_stopping is an unknown argument, as before."""
+        self.finish_update()
+        a = self._generate_args(generate_kwargs)
+        stops, max_new, max_len, do_sample, top_p, temperature = (a[k] for k in ("stops", "max_new", "max_len", "do_sample", "top_p",
+                                                                                 "temperature"))
+        min_length, eos_id, top_k, rep_pen, num_beams, beam_kw, generator = (a[k] for k in ("min_length", "eos_id", "top_k", "rep_pen",
+                                                                                            "num_beams", "beam_kw", "generator"))
         stage = 1 if self.arch == "myriad" else 0
         image = samples["image"].to(self._dev, F32)
         maps = None
@@ -1277,6 +1291,84 @@ class MyriadHIP(nn.Module):
                                              top_k=top_k, repetition_penalty=rep_pen)
         self.last_generate_stats = self.llama.last_generate_stats
         return {"token_ids": ids, "ve_anomaly_maps": maps}
+
+    def _prompt_ids_rows(self, samples, B: int, stage: int):
+        """_tokenize for an inference batch, one row at a time: lists of B 1-D id tensors whose lengths may differ."""
+        if "before_ids" in samples:
+            return [samples["before_ids"][i] for i in range(B)], [samples["after_ids"][i] for i in range(B)]
+        tok = self.llama_tokenizer
+        if tok is None:
+            raise RuntimeError("no tokenizer: pass integer ids (before_ids/after_ids) in samples")
+        key = {0: "question", 1: "question2", 2: "question3"}[stage] if self.arch == "myriad" else "question"
+        bs, as_ = [], []
+        for q in samples[key]:
+            pb, pa = ("###Human: " + q + " ###Assistant: ").split("<ImageHere>")
+            bs.append(tok(pb, return_tensors="pt", add_special_tokens=False).input_ids[0])
+            as_.append(tok(pa, return_tensors="pt", add_special_tokens=False).input_ids[0])
+        return bs, as_
+
+    def generate_stream(self, batches, slots: int = 8, **generate_kwargs):
+        """generate() for a whole run: `batches` (an iterable of generate()'s sample dicts, e.g. a DataLoader) streams through
+        `slots` decode slots (LlamaHIP.slot_decoder).  Each batch is encoded as generate() encodes it (image, maps, encode_img at
+        the batch's own size), each of its rows is tokenised and assembled on its own -- questions of different lengths are fine,
+        `before_ids` / `after_ids` may be lists of 1-D tensors -- and decodes with its own position and its own stop rule: a row
+        ends on EOS, on a stop sequence at the end of ITS ids or at max_new_tokens, and its slot takes the next row at once.
+
+        Yields {"index", "token_ids": [L] int64 (CPU), "ve_anomaly_map"} per sample in input order (index counts samples
+        over all batches), so a sampled run is reproducible per `generator`.  Takes generate()'s keyword arguments; refuses
+        (NotImplementedError) what the captured per-row step has no form of: repetition_penalty != 1, num_beams > 1,
+        min_length > 1 and device sampling.  An unknown argument is a TypeError.  `last_generate_stats` holds the engine's
+        counters (steps, prefills, graph_replays, graph_captures, live_row_steps, occupancy) once the stream is exhausted."""
+        self.finish_update()
+        a = self._generate_args(generate_kwargs)
+        if a["rep_pen"] != 1.0:
+            raise NotImplementedError(f"generate_stream(repetition_penalty={a['rep_pen']}) is not implemented in decode slots")
+        if a["num_beams"] > 1:
+            raise NotImplementedError(f"generate_stream(num_beams={a['num_beams']}): decode slots have no beam search")
+        if a["min_length"] > 1:
+            raise NotImplementedError(f"generate_stream(min_length={a['min_length']}): decode slots ban EOS for the first token only")
+        if a["do_sample"] and self.llama.device_sampling:
+            raise NotImplementedError("generate_stream: device sampling is not implemented in decode slots")
+        max_new = a["max_new"]
+        if max_new is None:
+            raise NotImplementedError("generate_stream(max_length=...): pass max_new_tokens, the prompts differ in length")
+        stage = 1 if self.arch == "myriad" else 0
+        side = []                                                      # per sample, in input order: its anomaly map
+
+        def rows():
+            for samples in batches:
+                image = samples["image"].to(self._dev, F32)
+                maps = None
+                if self.arch == "myriad":
+                    key = "oneshot_anomaly_maps" if self.k_shot > 0 else "anomaly_maps"
+                    maps = self._maps_for(samples, key, image)
+                B = image.shape[0]
+                before, after = self._prompt_ids_rows(samples, B, stage)
+                parts = self.encode_img(image, maps, stage, False)
+                for i in range(B):
+                    emb, _, _, _ = self._assemble([p[i:i + 1] for p in parts], before[i][None], after[i][None], None, None)
+                    side.append(None if maps is None else maps[i])
+                    yield emb[0, 1:].contiguous()                       # generate() wraps without BOS (myriad.py:446-449)
+
+        self.llama.decode_lora_version = self.store.version
+        # one engine (its caches and its captured step) per slot count, kept across calls; a slot holds slot_capacity positions
+        # (prompt + generated: a few hundred in an evaluation run), a longer request is a ValueError that names the attribute
+        key = (int(slots), min(int(self.slot_capacity), self.llama.cos.shape[0]))
+        if self._slot_decoder is None or self._slot_decoder[0] != key:
+            self._slot_decoder = None
+            self._slot_decoder = (key, self.llama.slot_decoder(*key))
+        dec = self._slot_decoder[1]
+
+        def stream():
+            for index, ids, _ in dec.run(rows(), max_new_tokens=max_new, stop_ids=a["stops"], eos_id=a["eos_id"],
+                                         min_length=a["min_length"], do_sample=a["do_sample"], top_p=a["top_p"],
+                                         temperature=a["temperature"], top_k=a["top_k"], generator=a["generator"], ordered=True):
+                self.last_generate_stats = dec.last_stats
+                yield {"index": index, "token_ids": ids, "ve_anomaly_map": side[index]}
+                side[index] = None
+            self.last_generate_stats = dec.last_stats
+
+        return stream()
 
 
 class StoppingCriteriaSub:

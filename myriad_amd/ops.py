@@ -399,6 +399,24 @@ def attn_decode_rope(qkv2d: torch.Tensor, cache: torch.Tensor, pos: torch.Tensor
     return out
 
 
+def attn_decode_rope_rows(qkv2d: torch.Tensor, cache: torch.Tensor, pos: torch.Tensor, kv_len: torch.Tensor, live: torch.Tensor,
+                          cos_tab: torch.Tensor, sin_tab: torch.Tensor, n_heads: int, head_dim: int, scale: float):
+    """attn_decode_rope with per-row state (decode slots): row b rotates and appends at pos[b], sees kv_len[b] keys; a row with
+    live[b] == 0 (int32 [B]) touches neither qkv2d nor the cache and gets a zero row of o.  A live row has attn_decode_rope's bits."""
+    _chk2d(qkv2d, BF16, "attn_decode_rope_rows.qkv")
+    B, W = qkv2d.shape[0], n_heads * head_dim
+    if qkv2d.shape[1] < 3 * W or cache.shape[2] != 2 * W or cache.shape[0] != B:
+        raise _lib.MyriadHipError("attn_decode_rope_rows: qkv must be [B, >=3W] and cache [B, T, 2W]")
+    for name, t in (("pos", pos), ("kv_len", kv_len), ("live", live)):
+        if t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous():
+            raise _lib.MyriadHipError(f"attn_decode_rope_rows: {name} must be a contiguous int32 [B]")
+    out = torch.empty((B, W), dtype=BF16, device=qkv2d.device)
+    _lib.check(_L().mh_attn_decode_rope_rows(_p(qkv2d), qkv2d.stride(0), _p(cache), cache.stride(0), cache.stride(1), _p(pos),
+                                             _p(kv_len), _p(live), _p(cos_tab), _p(sin_tab), _p(out), out.stride(0), B, n_heads,
+                                             head_dim, cache.shape[1], float(scale), _s()), "mh_attn_decode_rope_rows")
+    return out
+
+
 # keys per workgroup of mh_attn_decode_rope_split: 128 measured fastest at 256 / 1,024 / 2,048 cached keys, batch 1, 32 heads
 # (tools/chat_bench.py --chunks: 11.5 / 15.2 / 21.0 us per layer; 256 keys 16.0 / 17.8 / 22.2; 512 keys 19.9 / 27.0 / 30.6)
 SPLIT_KV_CHUNK = 128
@@ -1125,6 +1143,13 @@ def decode_advance(nxt, margin, pmax, rec, next_ids, step_dev, pos, kvlen):
     R = nxt.numel()
     _lib.check(_L().mh_decode_advance(_p(nxt), _p(margin), _p(pmax), _p(rec), _p(next_ids), _p(step_dev), _p(pos), _p(kvlen), R,
                                       _s()), "mh_decode_advance")
+
+
+def decode_advance_rows(nxt, margin, pmax, rec, next_ids, step_dev, pos, kvlen, live):
+    """decode_advance() for the rows with live[r] != 0 (int32 [R]); an idle row records (-1, 0, 0) and keeps next_ids / pos / kvlen."""
+    R = nxt.numel()
+    _lib.check(_L().mh_decode_advance_rows(_p(nxt), _p(margin), _p(pmax), _p(rec), _p(next_ids), _p(step_dev), _p(pos), _p(kvlen),
+                                           _p(live), R, _s()), "mh_decode_advance_rows")
 
 
 GEMV_MAX_ROWS = 16     # most rows mh_gemv_packed and its fused forms take (include/myriad_hip.h)

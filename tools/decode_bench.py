@@ -9,7 +9,12 @@ and MXFP4 weight copies (LlamaHIP.decode_fp8 / decode_fp4), interleaved in the s
 MYRIAD_DECODE_FP8 / MYRIAD_DECODE_FP4 set.  --merge 0,1 (with --lora 1)
 times each of those with the bordered LoRA qkv product and with the LoRA merged into the step's qkv copy
 (LlamaHIP.decode_merge_lora), interleaved again, and reports the one-time cost of packing every decoder matrix into each kind named by --weights and of merging every layer (bf16,
-fp8 and fp4 copies)."""
+fp8 and fp4 copies).
+--slots N measures a run instead of a call: a fixed synthetic request list (--requests of them, prompt lengths mixed between 24
+and 160 rows, each answer's length between 8 and --new tokens forced by a stop id of its own) decoded three ways, interleaved per
+repeat -- streamed through N decode slots (LlamaHIP.slot_decoder), greedy_generate at batch N over consecutive groups of N (the
+row-0 rule: a group runs until its first request stops, later rows are cut or idle), and greedy_generate at batch 1 -- as
+generated tokens per second and samples per second (the tokens each request is due, i.e. what batch 1 produces, count for all)."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -27,6 +32,8 @@ ap.add_argument("--modes", default="", help="comma list of greedy / host / devic
 ap.add_argument("--repeats", type=int, default=1)
 ap.add_argument("--beams", type=int, default=4, help="num_beams of the beam mode")
 ap.add_argument("--weights", default="", help="comma list of bf16 / fp8 / fp4: the token step's weight copies, timed interleaved")
+ap.add_argument("--slots", type=int, default=0, help="N > 0: the run-level comparison slots / batch N / batch 1 (see above)")
+ap.add_argument("--requests", type=int, default=64, help="requests of the --slots run")
 ap.add_argument("--merge", default="", help="comma list of 0 / 1: bordered / merged LoRA qkv in the token step, timed interleaved")
 a = ap.parse_args()
 modes = [m for m in a.modes.split(",") if m] or ["sample" if a.sample else "greedy"]
@@ -50,6 +57,67 @@ def make_samples(n):
                 before_ids=torch.randint(3, 32000, (1, 4), generator=g).expand(n, -1).contiguous(),
                 after_ids=torch.randint(3, 32000, (1, 28), generator=g).expand(n, -1).contiguous())
 
+
+if a.slots:
+    L, N, new = model.llama, a.slots, a.new
+    gq = torch.Generator().manual_seed(11)
+    lens = [int(x) for x in torch.randint(24, 161, (a.requests,), generator=gq)]
+    due = [int(x) for x in torch.randint(8, new + 1, (a.requests,), generator=gq)]
+    # Answer lengths are forced by a countdown chain written into the embedding / lm-head rows of ids 1000..1000+new (the
+    # peaked construction of tests/golden_utils.decode_chain_weights): token 1000+k is followed by 1000+k-1 with a margin of
+    # several logits, and 1000 is the stop id.  A prompt whose last row is the embedding of 1000+d answers d tokens, then stops.
+    D = L.D
+    dirs = torch.nn.functional.normalize(torch.randn(new + 1, D, generator=gq), dim=1)
+    emb_rows = (dirs * (D ** 0.5) * 2.0)
+    L.embed[1000:1001 + new].copy_(emb_rows.to(L.embed.dtype).to(dev))
+    head = L.lm_head[1000:1001 + new].float().cpu()
+    head[:new] += 2.5 * dirs[1:]
+    L.lm_head[1000:1001 + new].copy_(head.to(L.lm_head.dtype).to(dev))
+    reqs = []
+    for n, d in zip(lens, due):
+        x = torch.randn(n, D, generator=gq) * 0.02
+        x[-1] = emb_rows[d]
+        reqs.append(x.to(dev))
+    kw = dict(max_new_tokens=new, stop_ids=((1000,),), eos_id=-5, min_length=0)
+    dec = L.slot_decoder(N, 64 * ((160 + new + 63) // 64))
+
+    def run_slots():
+        out = {i: ids for i, ids, _ in dec.run(reqs, **kw)}
+        return [len(out[i]) for i in range(len(reqs))]
+
+    def run_batch(n):
+        got = []
+        for g0 in range(0, len(reqs), n):
+            grp = reqs[g0:g0 + n]
+            S = max(x.shape[0] for x in grp)                       # one stacked prompt per group: left-pad with the first row
+            emb = torch.stack([torch.cat([x[:1].expand(S - x.shape[0], -1), x]) for x in grp])
+            ids = L.greedy_generate(emb, **kw)
+            got += [ids.shape[1]] * len(grp)
+        return got
+
+    modes = (("slots %d" % N, run_slots), ("batch %d" % N, lambda: run_batch(N)), ("batch 1", lambda: run_batch(1)))
+    for _, fn in modes:
+        fn()                                                       # warm-up: kernels, graphs
+    want = modes[2][1]()
+    res = {name: [] for name, _ in modes}
+    for _ in range(max(1, a.repeats)):
+        for name, fn in modes:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got = fn()
+            torch.cuda.synchronize()
+            res[name].append((time.perf_counter() - t0, got))
+    print(f"{len(reqs)} requests, prompts {min(lens)}..{max(lens)} rows, {sum(want)} tokens due ({min(want)}..{max(want)} per request), "
+          f"weights {L._packed['kind'] if L._packed else 'bf16'}")
+    for name, _ in modes:
+        ts = sorted(t for t, _ in res[name])
+        t, got = ts[len(ts) // 2], res[name][-1][1]
+        whole = sum(g >= w for g, w in zip(got, want))
+        tail = f"; occupancy {dec.last_stats['occupancy']:.3f}, {dec.last_stats['steps']} steps" if name.startswith("slots") else ""
+        print(f"{name}: {t * 1e3:.1f} ms (median of {len(ts)}, min {ts[0] * 1e3:.1f}, max {ts[-1] * 1e3:.1f}) -> "
+              f"{sum(min(g, w) for g, w in zip(got, want)) / t:.0f} due tokens/s, {len(reqs) / t:.1f} samples/s; "
+              f"{whole}/{len(reqs)} requests decoded to their own stop{tail}")
+    sys.exit(0)
 
 smp = make_samples(B)
 smp_rows = make_samples(B * a.beams) if "beam" in modes else None
