@@ -45,6 +45,10 @@ def parse_args(argv=None):
     parser.add_argument("--limit", type=int, default=0, help="evaluate only the first N batches (smoke runs)")
     parser.add_argument("--slots", type=int, default=0, help="N > 0: stream the test set through N decode slots "
                         "(model.generate_stream: per-sample positions and stop rule); 0: one generate() per batch")
+    parser.add_argument("--prefill-batch", type=int, default=1, help="with --slots: P > 1 prefills up to P waiting samples in one "
+                        "packed pass when slots are free (1: every sample is prefilled alone)")
+    parser.add_argument("--refill-min", type=int, default=1, help="with --slots: hold a refill back until this many slots are free "
+                        "(fuller packed passes at the price of occupancy)")
     return parser.parse_args(argv)
 
 
@@ -150,7 +154,8 @@ def _run_slots(args, model, loader, generate_kwargs, save_path):
     records = []
     with torch.no_grad():
         t1 = time.time()
-        for out in model.generate_stream(batches(), slots=args.slots, **generate_kwargs):
+        for out in model.generate_stream(batches(), slots=args.slots, prefill_batch=args.prefill_batch, refill_min=args.refill_min,
+                                         **generate_kwargs):
             text = EP.postprocess_generation(out["token_ids"][None], model.llama_tokenizer)[0]
             amax = None
             if out["ve_anomaly_map"] is not None:        # anomaly_map_handler (:93-104): uint8(map * 255) then max
@@ -163,7 +168,7 @@ def _run_slots(args, model, loader, generate_kwargs, save_path):
     n_batches = max(1, len(records) // max(1, args.bs))
     print("CUDA Memory:", torch.cuda.max_memory_allocated() / (1024 * 1024))
     print("Mean Time: ", all_time / n_batches, f" decode slots {args.slots}: occupancy {st.get('occupancy', 0.0):.3f} over "
-          f"{st.get('steps', 0)} token steps, {st.get('prefills', 0)} prefills")
+          f"{st.get('steps', 0)} token steps, {st.get('prefills', 0)} prefills in {st.get('prefill_passes', 0)} passes")
     if st.get("host_sampled_rows"):
         print(f"note: {st['host_sampled_rows']} generated tokens had p_max < top_p and were drawn, not arg-maxed "
               "(see LlamaHIP.greedy_generate)")

@@ -453,6 +453,19 @@ int mh_attn_decode_rope(void* qkv, long ld_qkv, void* cache, long cache_bstride,
 int mh_attn_decode_rope_rows(void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
                              const int* kv_len, const int* live, const float* cos_tab, const float* sin_tab, void* out, long ldo,
                              int B, int H, int D, int T_cap, float scale, mh_stream_t s);
+/* Packed prefill of several decode slots (attn_ragged.hip): causal self-attention over R sequences packed row-wise into qkv
+ * [M, ld_qkv] bf16 = [q | k | v] (pre-rotary, only read), with the rotary at pos[row] and the KV-cache write fused in.  seg is the
+ * device table int[R][3] of (row0, len, slot) and seg_host the host's copy of it: segment i is rows row0 .. row0 + len - 1, its
+ * rotated k | v go to cache[slot] rows 0 .. len - 1 (cache [n_slots][T_cap][2 H D], addressed as in mh_attn_decode_rope_rows), its
+ * queries see its own keys only, and its out rows ([M, ldo] bf16) and cache rows have the bits of mh_rope_inplace +
+ * mh_copy3d_bf16 + mh_attn_fwd(causal) on that segment as a B = 1 batch.  Rows of qkv / out outside every segment, cache rows
+ * >= len and unnamed slots are not touched.  cos / sin tables [max_pos, D / 2]; a position outside them is clamped.
+ * MH_ERR_ARG, nothing launched, unless 0 < len <= T_cap, 0 <= slot < n_slots, the slots are distinct and the segments disjoint
+ * and inside [0, M) (the kernel repeats the per-segment bounds on the device table); MH_ERR_UNSUPPORTED unless D % 16 == 0 and
+ * D <= 128. */
+int mh_attn_prefill_ragged(const void* qkv, long ld_qkv, const int* pos, const int* seg, const int* seg_host, int R, void* cache,
+                           long cache_bstride, long ld_cache, int n_slots, int T_cap, const float* cos_tab, const float* sin_tab,
+                           int max_pos, void* out, long ldo, int M, int H, int D, float scale, mh_stream_t s);
 /* The same token step with the keys split into chunks (attn_decode_split.hip): grid (ceil(T_cap / chunk), B*H), each workgroup
  * scores one chunk and writes fp32 (m, l, o[D]) into `partials`, a second launch merges the chunks in order and writes bf16 out
  * (bits fixed from run to run).  q is rotated in registers (qkv is not written); the cache row at pos_dev[0] gets the bits

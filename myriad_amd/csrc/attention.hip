@@ -15,10 +15,7 @@
 //   already in MFMA B-operand layout for O^T = V^T.P^T / dQ^T = K^T.dS^T -- P never touches LDS.
 //   dK/dV computes S = Q.K^T (lane owns one key column) for the same reason.  The only transposed LDS images
 //   are V^T / K^T / Q^T / dO^T, built while staging.  Softmax statistics and accumulators are fp32.
-#include "attn_frag.h"
-
-#define TQ 64
-#define TK 64
+#include "attn_tile.h"
 
 struct AttnParams {
   const bf16_t* q;
@@ -62,14 +59,6 @@ __device__ __forceinline__ float attn_keep(const AttnParams& p, int b, int h, in
                       1.f / (1.f - p.drop_p));
 }
 
-template <int DP>
-struct Lds {
-  static constexpr int ROW = DP + 8;   // row-major tile row stride (elements)
-  static constexpr int TROW = TK + 8;  // transposed tile row stride (elements)
-  static constexpr int RM_BYTES = 64 * ROW * 2;
-  static constexpr int TR_BYTES = DP * TROW * 2;
-};
-
 // stage a [64 x D] tile (rows r0.., head column offset already applied to base) row-major into LDS, zero padded
 template <int DP>
 __device__ __forceinline__ void stage_rowmajor(bf16_t* lds, const bf16_t* base, long ld, int r0, int nrows, int D) {
@@ -111,20 +100,6 @@ __device__ __forceinline__ void stage_both(bf16_t* lds_rm, bf16_t* lds_tr, const
   }
 }
 
-// A-operand fragment from a row-major tile: row = 16*j + (lane&15), k-chunk (kk*4 + lane>>4)
-template <int DP>
-__device__ __forceinline__ short8_t frag_rm(const bf16_t* lds, int j, int kk, int lr, int lg) {
-  return *reinterpret_cast<const short8_t*>(lds + (16 * j + lr) * Lds<DP>::ROW + kk * 32 + lg * 8);
-}
-// A-operand fragment from a transposed tile: row d = 16*jd + (lane&15); reduction elements
-// {32c+4g+r} U {32c+16+4g+r}, r=0..3 -- matches the register order of a packed S^T / S accumulator pair.
-template <int DP>
-__device__ __forceinline__ short8_t frag_tr(const bf16_t* lds, int jd, int c, int lr, int lg) {
-  const bf16_t* p = lds + (16 * jd + lr) * Lds<DP>::TROW + 32 * c + 4 * lg;
-  const short4_t a = *reinterpret_cast<const short4_t*>(p);
-  const short4_t b = *reinterpret_cast<const short4_t*>(p + 16);
-  return (short8_t){a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
 // B-operand fragments straight from global: token row `row` (or zeros), chunk kk*32 + g*8
 template <int DP>
 __device__ __forceinline__ void load_row_frags(short8_t (&f)[DP / 32], const bf16_t* base, long ld, int row, int nrows,
@@ -137,7 +112,6 @@ __device__ __forceinline__ void load_row_frags(short8_t (&f)[DP / 32], const bf1
   }
 }
 
-#define NEG_INF (-__builtin_inff())
 
 // ------------------------------------------------------------------------------------------- forward
 template <int DP, bool DROP = false>

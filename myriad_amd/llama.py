@@ -405,13 +405,16 @@ class LlamaHIP:
         return self._pos_cache[key]
 
     # ------------------------------------------------------------------ generation
-    def _decode_block(self, h, B, S, caches, scale, pos, past=None, pos_dev=None, kvlen_dev=None, split_ws=None, live=None):
+    def _decode_block(self, h, B, S, caches, scale, pos, past=None, pos_dev=None, kvlen_dev=None, split_ws=None, live=None,
+                      ragged=None):
         """All decoder layers for a prefill chunk (host-known `past`: the chunk's rows go to cache rows past..past+S-1, `pos` holds
         their rotary positions, and causal masking is aligned to the bottom right) or for one decode token whose position lives
         in device memory (`pos_dev`/`kvlen_dev`), which makes the launch sequence replayable from a hipGraph.  `split_ws` (the
         partials buffer of ops.attn_decode_split_ws) makes the fused token step use the split-KV attention kernel.  `live` (int32
         [B] on the device, the slot engine's) makes it the rows kernel instead: every row appends at its own pos[b], idle rows
-        are skipped; only the fused step has that form."""
+        are skipped; only the fused step has that form.  `ragged` = (segment table on the device, its host copy) makes a prefill
+        the packed one (_prefill_packed): B = 1, the S rows hold several requests, `caches` are the whole slot caches, and the
+        three attention launches become one mh_attn_prefill_ragged."""
         H, hd, W, D = self.H, self.hd, self.D, self.D
         M = B * S
         packed = self._packed["layers"] if pos_dev is not None and _packed_step(self, M) else None
@@ -468,7 +471,9 @@ class LlamaHIP:
                 lora.forward_border(li, x_ext, training=False)
                 qkv = lin(li, "wqkv_ext", x_ext)
             q3 = qkv.view(B, S, 3 * W)
-            if pos_dev is None:
+            if ragged is not None:
+                o = ops.attn_prefill_ragged(qkv, pos, ragged[0], ragged[1], cache, self.cos, self.sin, H, hd, scale)
+            elif pos_dev is None:
                 ops.rope_(qkv, 0, 2 * H, hd, pos, self.cos, self.sin, 1.0)
                 ops.copy3d_bf16(q3[:, :, W:], cache[:, past:past + S])       # append k|v (modeling_llama.py:190-195)
                 kc = cache[:, :past + S]
@@ -509,6 +514,32 @@ class LlamaHIP:
                                past=past)
         last = h.view(B, S, D)[:, -1].contiguous()
         return ops.gemm(ops.rmsnorm_fwd(last, self.norm, self.eps), self.lm_head, out_dtype=F32)
+
+    def _prefill_packed(self, embs, slots, caches) -> torch.Tensor:
+        """The prefill of several requests in ONE pass over the decoder weights (the slot engine's prefill_batch > 1): `embs` is a
+        list of [S_i, D] f32 embeddings, request i goes to positions 0 .. S_i - 1 of slot slots[i] of `caches` (the slot engine's
+        [slots, T, 2D] caches, whole).  The rows are packed one request after the other, `pos` = each row's index within its
+        request, and the row count is rounded up to a multiple of 64 with zero rows that belong to no segment (LoraQV.x_ext keeps
+        a buffer per row count and the GEMM planner keys on it: a run meets a handful of shapes).  The layers are the prefill
+        branch of _decode_block -- norms, GEMMs, the bordered LoRA, MLP -- with its three attention launches replaced by
+        mh_attn_prefill_ragged; then the R last rows are gathered for the final norm and the lm-head.  Returns [R, V] f32 logits.
+        A request's rows differ from its solo _prefill only through the GEMMs' row-count-dependent plans."""
+        lens = [int(e.shape[0]) for e in embs]
+        M, D = ops.round_up(sum(lens), 64), self.D
+        x = torch.zeros((M, D), dtype=F32, device=self.dev)
+        pos = torch.zeros((M,), dtype=torch.int32)
+        seg, row = [], 0
+        for e, n, s in zip(embs, lens, slots):
+            x[row:row + n].copy_(e)
+            pos[row:row + n] = torch.arange(n, dtype=torch.int32)
+            seg.append((row, n, int(s)))
+            row += n
+        seg_host = torch.tensor(seg, dtype=torch.int32)
+        last = torch.tensor([r0 + n - 1 for r0, n, _ in seg], dtype=torch.int32)
+        h = self._decode_block(x, 1, M, caches, 1.0 / math.sqrt(self.hd), ops.h2d(pos, self.dev),
+                               ragged=(ops.h2d(seg_host, self.dev), seg_host))
+        hl = ops.gather_rows_f32(h, ops.h2d(last, self.dev))
+        return ops.gemm(ops.rmsnorm_fwd(hl, self.norm, self.eps), self.lm_head, out_dtype=F32)
 
     def _step_logits(self, ws: dict) -> None:
         """The token step up to its logits: embed the fed ids ws["ids"], every decoder layer at the device-resident position,
@@ -1100,6 +1131,78 @@ class SlotScheduler:
         return self.live_row_steps / (self.steps * self.slots) if self.steps else 0.0
 
 
+class RefillPlanner:
+    """Which waiting requests are prefilled together, and when: the host side of the slot engine's packed prefill, on plain Python
+    values like SlotScheduler (whose free / live slots it reads), so a scripted run can drive it.
+
+    `next_pass()` is asked at every refill point until it answers []: it hands out [(slot, request), ...] for ONE prefill pass --
+    the next waiting requests in input order, one per free slot in ascending slot order, at most `prefill_batch` of them and as
+    many as keep the pass's row count (the lengths' sum rounded up to 64) within `prefill_rows`; the first always goes, so a
+    request too long to share a pass, or longer than the cap, gets a pass of its own.  `refill_min` = k holds a pass back while
+    fewer than k slots are free, unless nothing is live or the requests have run out (the input ended and everything left is
+    waiting already: the planner looks one request past the pass it could fill).  prefill_batch = 1, refill_min = 1 is the
+    engine's one-request refill: the lowest free slot takes the next request, again if that one ended on its first pick."""
+
+    def __init__(self, sched: "SlotScheduler", requests, prefill_batch: int = 1, prefill_rows: int = 2048, refill_min: int = 1,
+                 length=len):
+        if prefill_batch < 1 or refill_min < 1 or prefill_rows < 1:
+            raise ValueError(f"prefill_batch, refill_min and prefill_rows must be >= 1, got {prefill_batch}, {refill_min} and "
+                             f"{prefill_rows}")
+        self.sched, self.it, self.more, self.waiting, self.length = sched, iter(requests), True, [], length
+        self.prefill_batch, self.prefill_rows = int(prefill_batch), int(prefill_rows)
+        self.refill_min = min(int(refill_min), sched.slots)
+        self.passes = self.packed_rows = 0
+
+    def next_pass(self) -> list:
+        free = self.sched.free()
+        if not free:
+            return []
+        want = min(self.prefill_batch, len(free))
+        while self.more and len(self.waiting) < want + (self.refill_min > 1):    # refill_min = 1 never needs to look ahead
+            try:
+                self.waiting.append(next(self.it))
+            except StopIteration:
+                self.more = False
+        if not self.waiting or (len(free) < self.refill_min and self.sched.live() and self.more):
+            return []
+        n, rows = 0, 0
+        for req in self.waiting[:want]:
+            if n and ops.round_up(rows + self.length(req), 64) > self.prefill_rows:
+                break
+            n, rows = n + 1, rows + self.length(req)
+        group, self.waiting = self.waiting[:n], self.waiting[n:]
+        self.passes += 1
+        self.packed_rows += rows
+        return list(zip(free, group))
+
+
+def replay_slot_run(lengths, ids, slots: int, max_new_tokens: int, stop_ids=(), eos_id: int = 2, prefill_batch: int = 1,
+                    prefill_rows: int = 2048, refill_min: int = 1) -> dict:
+    """The counters of a slot run whose picks are known: request i has a prompt of lengths[i] rows and generates ids[i] (which must
+    end where the stop rule ends it).  SlotScheduler + RefillPlanner driven as SlotDecoder.run drives them, without a device."""
+    sched = SlotScheduler(slots, max_new_tokens, stop_ids, eos_id)
+    plan = RefillPlanner(sched, range(len(lengths)), prefill_batch, prefill_rows, refill_min, length=lambda i: lengths[i])
+    owner, prefills = [None] * slots, 0
+    while True:
+        group = plan.next_pass()
+        while group:
+            for s, i in group:
+                prefills += 1
+                if sched.admit(s, ids[i][0], 0.0):
+                    owner[s] = [i, 1]
+            group = plan.next_pass()
+        live = sched.live()
+        if not live:
+            break
+        picks = [0] * slots
+        for s in live:
+            picks[s] = ids[owner[s][0]][owner[s][1]]
+            owner[s][1] += 1
+        sched.step(picks, [0.0] * slots)
+    return dict(prefills=prefills, prefill_passes=plan.passes, packed_rows=plan.packed_rows, steps=sched.steps,
+                live_row_steps=sched.live_row_steps, occupancy=sched.occupancy)
+
+
 class SlotDecoder:
     """Streams requests through `slots` rows of ONE captured token step (LlamaHIP.slot_decoder).  Each slot holds one request with
     its own prompt length, position and stop rule; a slot whose request ends is refilled with the next one while the others go on
@@ -1109,7 +1212,12 @@ class SlotDecoder:
     swapped: the attention is mh_attn_decode_rope_rows (row b appends at pos[b], idle rows skipped) and the bookkeeping is
     mh_decode_advance_rows (idle rows record id -1).  A refill is the existing B = 1 prefill into the slot's slice of every cache.
     Between two replays the host writes only a finished slot's live flag, a refilled slot's (id, pos, kvlen, live) and a host
-    draw's id.  greedy_generate and its row-0 rule are untouched; this path is opt-in."""
+    draw's id.  greedy_generate and its row-0 rule are untouched; this path is opt-in.
+
+    Packed prefill (opt-in, `run(prefill_batch=P > 1)` or `refill_min > 1`): at a refill point up to min(P, free slots) waiting
+    requests are prefilled in ONE pass over the weights (LlamaHIP._prefill_packed, one mh_attn_prefill_ragged per layer writing
+    each request's keys / values into its own slot), one arg-max launch and one device->host copy give all their first picks, and
+    they are admitted in input order.  RefillPlanner decides which requests go together and when."""
 
     def __init__(self, llama: "LlamaHIP", slots: int, capacity: int):
         slots = int(slots)
@@ -1151,10 +1259,13 @@ class SlotDecoder:
     @torch.no_grad()
     def run(self, requests, max_new_tokens: int = 90, stop_ids=((835,), (2277, 29937)), eos_id: int = 2, min_length: int = 1,
             do_sample: bool = False, top_p: float = 1.0, temperature: float = 1.0, top_k: int = 50,
-            generator: Optional[torch.Generator] = None, ordered: bool = False):
+            generator: Optional[torch.Generator] = None, ordered: bool = False, prefill_batch: int = 1, refill_min: int = 1,
+            prefill_rows: int = 2048):
         """Decode every request of `requests` (an iterable of [S0_i, D] f32 embeddings, lengths free) and yield
         (index, ids[L_i] int64 on the CPU, margins[L_i] f32) as each finishes -- or, with `ordered`, in input order.  The
-        arguments are greedy_generate's; the stop rule is per request.  `last_stats` holds the run's counters."""
+        arguments are greedy_generate's; the stop rule is per request.  `last_stats` holds the run's counters: `prefills` counts
+        requests, `prefill_passes` passes over the weights and `packed_rows` the request rows they held (padding not counted).
+        `prefill_batch`, `refill_min`, `prefill_rows`: RefillPlanner's; at 1, 1 every refill is the one-request prefill."""
         L = self.llama
         if min_length > 1:
             raise NotImplementedError("decode slots: min_length > 1 needs a per-row ban, which the captured step does not have")
@@ -1167,7 +1278,9 @@ class SlotDecoder:
         ws = self._workspace(inv_temp)
         sched = SlotScheduler(self.slots, max_new_tokens, stop_ids, eos_id, ordered=ordered)
         stats = dict(steps=0, graph_replays=0, graph_captures=self.graph_captures, prefills=0, live_row_steps=0, occupancy=0.0,
-                     host_sampled_rows=0)
+                     host_sampled_rows=0, prefill_passes=0, packed_rows=0)
+        packed = int(prefill_batch) != 1 or int(refill_min) != 1
+        plan = RefillPlanner(sched, requests, prefill_batch, prefill_rows, refill_min, length=lambda e: int(e.shape[0]))
         self.last_stats = stats
         ban0 = eos_id if 0 < min_length else -1
         rec = ws["rec"][:3]
@@ -1183,12 +1296,39 @@ class SlotDecoder:
             for index, ids, mar in sched.pop():
                 yield index, torch.tensor(ids, dtype=torch.long), torch.tensor(mar, dtype=F32)
 
-        def refill(s: int, emb: torch.Tensor) -> None:
-            """Prefill one request alone into slot s and take its first pick; the slot goes live if the request goes on."""
-            S0 = emb.shape[0]
-            if emb.dim() != 2 or S0 < 1 or S0 + max_new_tokens > min(self.T_cap, L.cos.shape[0]):
+        def fits(emb: torch.Tensor) -> int:
+            S0 = emb.shape[0] if emb.dim() == 2 else 0
+            if S0 < 1 or S0 + max_new_tokens > min(self.T_cap, L.cos.shape[0]):
                 raise ValueError(f"request of shape {tuple(emb.shape)} + max_new_tokens {max_new_tokens} does not fit a slot of "
                                  f"{min(self.T_cap, L.cos.shape[0])} positions")
+            return S0
+
+        def go_live(s: int, first: int, S0: int) -> None:
+            sl = slice(s, s + 1)
+            ws["ids"][sl].fill_(first)
+            ws["pos"][sl].fill_(S0)                                  # position of the incoming token
+            ws["kvlen"][sl].fill_(S0 + 1)                            # valid keys after the append
+            ws["live"][sl].fill_(1)
+
+        def refill_packed(group) -> None:
+            """Prefill the group's requests in one packed pass, each into its slot; one arg-max launch and one device->host copy
+            for all first picks; admission in input order."""
+            R, lens = len(group), [fits(emb) for _, emb in group]
+            logits0 = L._prefill_packed([emb for _, emb in group], [s for s, _ in group], ws["caches"])
+            stats["prefills"] += R
+            ops.argmax_pmax_rows(logits0, ws["nxt"][:R], ws["mar"][:R], ws["pmx"][:R], ban_id=ban0, inv_temp=inv_temp)
+            picks = torch.stack([ws["nxt"][:R].to(torch.float64), ws["mar"][:R].double(), ws["pmx"][:R].double()]).tolist()
+            for i, (s, _) in enumerate(group):
+                first = int(picks[0][i])
+                if do_sample and picks[2][i] < top_p:
+                    first = _host_draw(logits0[i], ban0, inv_temp, top_k, top_p, generator)
+                    stats["host_sampled_rows"] += 1
+                if sched.admit(s, first, picks[1][i]):
+                    go_live(s, first, lens[i])
+
+        def refill(s: int, emb: torch.Tensor) -> None:
+            """Prefill one request alone into slot s and take its first pick; the slot goes live if the request goes on."""
+            S0 = fits(emb)
             logits0 = L._prefill(emb[None].to(L.dev), [c[s:s + 1] for c in ws["caches"]])
             stats["prefills"] += 1
             sl = slice(s, s + 1)
@@ -1199,22 +1339,17 @@ class SlotDecoder:
                 first = _host_draw(logits0[0], ban0, inv_temp, top_k, top_p, generator)
                 stats["host_sampled_rows"] += 1
             if sched.admit(s, first, mar):
-                ws["ids"][sl].fill_(first)
-                ws["pos"][sl].fill_(S0)                              # position of the incoming token
-                ws["kvlen"][sl].fill_(S0 + 1)                        # valid keys after the append
-                ws["live"][sl].fill_(1)
+                go_live(s, first, S0)
 
-        it, more = iter(requests), True
         try:
             while True:
-                for s in sched.free():
-                    while more and sched.rows[s] is None:
-                        try:
-                            emb = next(it)
-                        except StopIteration:
-                            more = False
-                            break
-                        refill(s, emb)
+                group = plan.next_pass()
+                while group:
+                    if packed:
+                        refill_packed(group)
+                    else:
+                        refill(*group[0])
+                    group = plan.next_pass()
                 yield from results()
                 live = sched.live()
                 if not live:
@@ -1239,4 +1374,4 @@ class SlotDecoder:
                 yield from results()
         finally:
             stats.update(steps=sched.steps, live_row_steps=sched.live_row_steps, occupancy=sched.occupancy,
-                         graph_captures=self.graph_captures)
+                         graph_captures=self.graph_captures, prefill_passes=plan.passes, packed_rows=plan.packed_rows)

@@ -1307,7 +1307,7 @@ class MyriadHIP(nn.Module):
             as_.append(tok(pa, return_tensors="pt", add_special_tokens=False).input_ids[0])
         return bs, as_
 
-    def generate_stream(self, batches, slots: int = 8, **generate_kwargs):
+    def generate_stream(self, batches, slots: int = 8, prefill_batch: int = 1, refill_min: int = 1, **generate_kwargs):
         """generate() for a whole run: `batches` (an iterable of generate()'s sample dicts, e.g. a DataLoader) streams through
         `slots` decode slots (LlamaHIP.slot_decoder).  Each batch is encoded as generate() encodes it (image, maps, encode_img at
         the batch's own size), each of its rows is tokenised and assembled on its own -- questions of different lengths are fine,
@@ -1318,7 +1318,9 @@ class MyriadHIP(nn.Module):
         over all batches), so a sampled run is reproducible per `generator`.  Takes generate()'s keyword arguments; refuses
         (NotImplementedError) what the captured per-row step has no form of: repetition_penalty != 1, num_beams > 1,
         min_length > 1 and device sampling.  An unknown argument is a TypeError.  `last_generate_stats` holds the engine's
-        counters (steps, prefills, graph_replays, graph_captures, live_row_steps, occupancy) once the stream is exhausted."""
+        counters (steps, prefills, graph_replays, graph_captures, live_row_steps, occupancy, prefill_passes, packed_rows) once the
+        stream is exhausted.  `prefill_batch` = P > 1 prefills up to P waiting samples in one packed pass whenever slots are free
+        and `refill_min` = k holds a refill back until k slots are free (SlotDecoder.run); both default to 1, the one-sample refill."""
         self.finish_update()
         a = self._generate_args(generate_kwargs)
         if a["rep_pen"] != 1.0:
@@ -1362,7 +1364,8 @@ class MyriadHIP(nn.Module):
         def stream():
             for index, ids, _ in dec.run(rows(), max_new_tokens=max_new, stop_ids=a["stops"], eos_id=a["eos_id"],
                                          min_length=a["min_length"], do_sample=a["do_sample"], top_p=a["top_p"],
-                                         temperature=a["temperature"], top_k=a["top_k"], generator=a["generator"], ordered=True):
+                                         temperature=a["temperature"], top_k=a["top_k"], generator=a["generator"], ordered=True,
+                                         prefill_batch=prefill_batch, refill_min=refill_min):
                 self.last_generate_stats = dec.last_stats
                 yield {"index": index, "token_ids": ids, "ve_anomaly_map": side[index]}
                 side[index] = None

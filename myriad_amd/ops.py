@@ -417,6 +417,47 @@ def attn_decode_rope_rows(qkv2d: torch.Tensor, cache: torch.Tensor, pos: torch.T
     return out
 
 
+def attn_prefill_ragged(qkv2d: torch.Tensor, pos: torch.Tensor, seg: torch.Tensor, seg_host: torch.Tensor, cache: torch.Tensor,
+                        cos_tab: torch.Tensor, sin_tab: torch.Tensor, n_heads: int, head_dim: int, scale: float,
+                        out: Optional[torch.Tensor] = None):
+    """Packed prefill attention of several decode slots in one launch.  qkv2d [M, >=3W] bf16 = [q | k | v], pre-rotary and only
+    read; pos int32 [M] the rotary position of each row; seg int32 [R, 3] on the device = (row0, len, slot) per segment and
+    seg_host the same table on the CPU (the entry sizes its grid and validates by it); cache [n_slots, T, 2W].  Per segment:
+    rope_ + copy3d_bf16 into cache[slot, :len] + attn_fwd(causal=True) on its rows as a B = 1 batch, same bits.  Returns
+    o [M, W] bf16; rows outside every segment are not written (zeros when `out` is allocated here)."""
+    _chk2d(qkv2d, BF16, "attn_prefill_ragged.qkv")
+    M, W = qkv2d.shape[0], n_heads * head_dim
+    if qkv2d.shape[1] < 3 * W:
+        raise _lib.MyriadHipError(f"attn_prefill_ragged: qkv must be [M, >=3W], got {tuple(qkv2d.shape)} for W = {W}")
+    if cache.dtype != BF16 or not cache.is_cuda or cache.dim() != 3 or cache.shape[2] != 2 * W or cache.stride(2) != 1:
+        raise _lib.MyriadHipError(f"attn_prefill_ragged: cache must be a cuda bf16 [n_slots, T, 2W] with unit inner stride, got "
+                                  f"{cache.dtype} {tuple(cache.shape)}")
+    if pos.dtype != torch.int32 or not pos.is_cuda or pos.shape != (M,) or not pos.is_contiguous():
+        raise _lib.MyriadHipError("attn_prefill_ragged: pos must be a contiguous cuda int32 [M]")
+    for name, t, cuda in (("seg", seg, True), ("seg_host", seg_host, False)):
+        if t.dtype != torch.int32 or t.is_cuda != cuda or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous():
+            raise _lib.MyriadHipError(f"attn_prefill_ragged: {name} must be a contiguous {'cuda' if cuda else 'cpu'} int32 [R, 3]")
+    if seg.shape != seg_host.shape:
+        raise _lib.MyriadHipError("attn_prefill_ragged: seg and seg_host must hold the same table")
+    for name, t in (("cos", cos_tab), ("sin", sin_tab)):
+        if t.dtype != F32 or not t.is_cuda or t.dim() != 2 or t.shape[1] != head_dim // 2 or not t.is_contiguous():
+            raise _lib.MyriadHipError(f"attn_prefill_ragged: {name} must be a contiguous cuda f32 [max_pos, D / 2]")
+    if cos_tab.shape != sin_tab.shape:
+        raise _lib.MyriadHipError("attn_prefill_ragged: cos and sin tables differ in shape")
+    if out is None:
+        out = torch.zeros((M, W), dtype=BF16, device=qkv2d.device)
+    else:
+        _chk2d(out, BF16, "attn_prefill_ragged.out")
+        if out.shape != (M, W):
+            raise _lib.MyriadHipError(f"attn_prefill_ragged: out shape {tuple(out.shape)} != {(M, W)}")
+    R = seg_host.shape[0]
+    _lib.check(_L().mh_attn_prefill_ragged(_p(qkv2d), qkv2d.stride(0), _p(pos), _p(seg), seg_host.data_ptr(), R, _p(cache),
+                                           cache.stride(0), cache.stride(1), cache.shape[0], cache.shape[1], _p(cos_tab),
+                                           _p(sin_tab), cos_tab.shape[0], _p(out), out.stride(0), M, n_heads, head_dim, float(scale),
+                                           _s()), f"mh_attn_prefill_ragged M={M} R={R} H={n_heads} D={head_dim}")
+    return out
+
+
 # keys per workgroup of mh_attn_decode_rope_split: 128 measured fastest at 256 / 1,024 / 2,048 cached keys, batch 1, 32 heads
 # (tools/chat_bench.py --chunks: 11.5 / 15.2 / 21.0 us per layer; 256 keys 16.0 / 17.8 / 22.2; 512 keys 19.9 / 27.0 / 30.6)
 SPLIT_KV_CHUNK = 128

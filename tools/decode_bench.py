@@ -14,7 +14,9 @@ fp8 and fp4 copies).
 and 160 rows, each answer's length between 8 and --new tokens forced by a stop id of its own) decoded three ways, interleaved per
 repeat -- streamed through N decode slots (LlamaHIP.slot_decoder), greedy_generate at batch N over consecutive groups of N (the
 row-0 rule: a group runs until its first request stops, later rows are cut or idle), and greedy_generate at batch 1 -- as
-generated tokens per second and samples per second (the tokens each request is due, i.e. what batch 1 produces, count for all)."""
+generated tokens per second and samples per second (the tokens each request is due, i.e. what batch 1 produces, count for all).
+--prefill-batch 1,8 --refill-min 1,2,4 (with --slots) adds one slots mode per pair, interleaved with the others: the packed prefill
+of SlotDecoder.run (prefill_batch = 1, refill_min = 1 is the one-request refill, the baseline)."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -34,6 +36,8 @@ ap.add_argument("--beams", type=int, default=4, help="num_beams of the beam mode
 ap.add_argument("--weights", default="", help="comma list of bf16 / fp8 / fp4: the token step's weight copies, timed interleaved")
 ap.add_argument("--slots", type=int, default=0, help="N > 0: the run-level comparison slots / batch N / batch 1 (see above)")
 ap.add_argument("--requests", type=int, default=64, help="requests of the --slots run")
+ap.add_argument("--prefill-batch", default="1", help="comma list: prefill_batch of the --slots run, timed interleaved")
+ap.add_argument("--refill-min", default="1", help="comma list: refill_min of the --slots run, timed interleaved")
 ap.add_argument("--merge", default="", help="comma list of 0 / 1: bordered / merged LoRA qkv in the token step, timed interleaved")
 a = ap.parse_args()
 modes = [m for m in a.modes.split(",") if m] or ["sample" if a.sample else "greedy"]
@@ -81,8 +85,11 @@ if a.slots:
     kw = dict(max_new_tokens=new, stop_ids=((1000,),), eos_id=-5, min_length=0)
     dec = L.slot_decoder(N, 64 * ((160 + new + 63) // 64))
 
-    def run_slots():
-        out = {i: ids for i, ids, _ in dec.run(reqs, **kw)}
+    slot_stats = {}
+
+    def run_slots(pb=1, rm=1):
+        out = {i: ids for i, ids, _ in dec.run(reqs, prefill_batch=pb, refill_min=rm, **kw)}
+        slot_stats[(pb, rm)] = dict(dec.last_stats)
         return [len(out[i]) for i in range(len(reqs))]
 
     def run_batch(n):
@@ -95,7 +102,12 @@ if a.slots:
             got += [ids.shape[1]] * len(grp)
         return got
 
+    pairs = [(pb, rm) for pb in (int(x) for x in a.prefill_batch.split(",")) for rm in (int(x) for x in a.refill_min.split(","))
+             if (pb, rm) != (1, 1)]
+    slot_modes = {"slots %d" % N: (1, 1)}
+    slot_modes.update({"slots %d prefill_batch %d refill_min %d" % (N, pb, rm): (pb, rm) for pb, rm in pairs})
     modes = (("slots %d" % N, run_slots), ("batch %d" % N, lambda: run_batch(N)), ("batch 1", lambda: run_batch(1)))
+    modes += tuple((name, lambda pr=pr: run_slots(*pr)) for name, pr in slot_modes.items() if pr != (1, 1))
     for _, fn in modes:
         fn()                                                       # warm-up: kernels, graphs
     want = modes[2][1]()
@@ -113,7 +125,9 @@ if a.slots:
         ts = sorted(t for t, _ in res[name])
         t, got = ts[len(ts) // 2], res[name][-1][1]
         whole = sum(g >= w for g, w in zip(got, want))
-        tail = f"; occupancy {dec.last_stats['occupancy']:.3f}, {dec.last_stats['steps']} steps" if name.startswith("slots") else ""
+        st = slot_stats.get(slot_modes.get(name))
+        tail = (f"; occupancy {st['occupancy']:.3f}, {st['steps']} steps, {st['prefills']} prefills in {st['prefill_passes']} passes "
+                f"of {st['packed_rows']} rows") if st else ""
         print(f"{name}: {t * 1e3:.1f} ms (median of {len(ts)}, min {ts[0] * 1e3:.1f}, max {ts[-1] * 1e3:.1f}) -> "
               f"{sum(min(g, w) for g, w in zip(got, want)) / t:.0f} due tokens/s, {len(reqs) / t:.1f} samples/s; "
               f"{whole}/{len(reqs)} requests decoded to their own stop{tail}")
