@@ -308,6 +308,27 @@ int mh_decode_advance_kept(const long* nxt, const float* margin, const float* pm
    as above; an idle row records (-1, 0, 0) and keeps next_ids[r], pos[r] and kvlen[r].  *step += 1 once per launch. */
 int mh_decode_advance_rows(const long* nxt, const float* margin, const float* pmax, float* rec, long* next_ids, int* step,
                            int* pos, int* kvlen, const int* live, int R, mh_stream_t s);
+/* The sampled step of the decode-slot engine: mh_sample_rows with per-row state on the device.  params[6] f32 = (inv_temp, top_p,
+   top_k, penalty, min_length, eos_id); seed[r] (u64) is row r's Philox key and gen[r] (the tokens its request has generated so
+   far) the step of its draw, counter = (gen[r], 0, 0, 0) -- the draw of mh_sample_rows for row 0 of a one-row call with that seed
+   at t = gen[r], whatever slot the request sits in.  Row r bans eos_id iff gen[r] < min_length.  A row with live[r] == 0 (live
+   may be null: every row is live) writes out = -1, margin = pmax = 0, kept = 0 and nothing else.  margin and pmax are required;
+   the shape limits are mh_sample_rows'. */
+int mh_sample_rows_slots(const float* logits, long ldl, long* out, float* margin, float* pmax, int* kept, float* u_out, int R, int V,
+                         const float* params, const unsigned long long* seed, const int* gen, const int* live, mh_stream_t s);
+/* the greedy pick with the same per-row ban: arg-max, margin and p_max (at params[0] = inv_temp) as mh_argmax_pmax_rows computes
+   them on the wide path, row r banning eos_id iff gen[r] < min_length; idle rows as above.  Same shape limits. */
+int mh_argmax_pmax_rows_slots(const float* logits, long ldl, long* out, float* margin, float* pmax, int R, int V, const float* params,
+                              const int* gen, const int* live, mh_stream_t s);
+/* mh_repetition_penalty_rows under the row mask: a row with live[r] == 0 changes neither its logits nor its bitmap (the caller
+   zeroes a row's bitmap words when the row takes a new request) */
+int mh_repetition_penalty_rows_slots(float* logits, long ldl, unsigned* seen, const long* prev_ids, int R, int V, const float* penalty,
+                                     const int* live, mh_stream_t s);
+/* mh_decode_advance_kept under the row mask, with the per-row token count: a live row records (id, margin, p_max, kept) in
+   rec[4][R], feeds its id back and advances pos[r], kvlen[r] and gen[r]; an idle row records (-1, 0, 0, 0) and keeps all its
+   state.  kept may be null (a greedy pick): the fourth record row is then 0.  *step += 1 once per launch. */
+int mh_decode_advance_kept_rows(const long* nxt, const float* margin, const float* pmax, const int* kept, float* rec, long* next_ids,
+                                int* step, int* pos, int* kvlen, int* gen, const int* live, int R, mh_stream_t s);
 
 /* beam search step (HF GenerationMixin._beam_search), nb <= 8 beams, K = 2*nb, 2*nb <= V <= 32768 (else MH_ERR_UNSUPPORTED):
    rows b*rpi .. b*rpi+rpi-1 of fp32 logits [B*rpi, ldl] belong to item b (rpi = nb, or 1 for the step after a prefill at B rows);

@@ -9,6 +9,11 @@
 // Random numbers: Philox4x32-10 (Salmon et al., SC'11), key = the 64-bit seed, counter = (t, 0, row, 0), u = (x0 >> 8) * 2^-24.
 // The seed, the step counter and (inv_temp, top_p, top_k, penalty) are read from device memory: graph replays draw fresh numbers
 // and a change of the knobs needs no re-capture.
+// The decode-slot engine runs the same three launches in a per-row ("slots") form: row r has its own live flag, its own seed and its
+// own generated-token count gen[r], which is both the Philox step of its next draw -- counter = (gen[r], 0, 0, 0), so a request's
+// stream depends on (its seed, the token index) only, not on the slot it sits in or on its neighbours -- and what decides its EOS
+// ban (gen[r] < min_length); min_length and eos_id follow the four knobs in `params` (six floats).  The uniform entry points are
+// instances of the same bodies with the per-row reads compiled out.
 #include "common.h"
 
 #define SNT 1024                // threads per row
@@ -73,11 +78,17 @@ __device__ __forceinline__ SmpTop smp_combine(const SmpTop& a, const SmpTop& b) 
 }
 
 // params = (inv_temp, top_p, top_k, penalty) f32 on the device; seed = one u64; step = the decode step counter (or null): t = *step + t_add.
-__global__ __launch_bounds__(SNT) void sample_rows_kernel(const float* __restrict__ logits, long ldl, long* __restrict__ out,
-                                                          float* __restrict__ margin, float* __restrict__ pmax, int* __restrict__ kept,
-                                                          float* __restrict__ u_out, int V, int ban_id, const float* __restrict__ params,
-                                                          const unsigned long long* __restrict__ seed, const int* __restrict__ step,
-                                                          int t_add) {
+// ROWS: the slot form -- params = (inv_temp, top_p, top_k, penalty, min_length, eos_id), seed[row] and gen[row] per row, t = gen[row],
+// the ban is eos_id while gen[row] < min_length (ban_id, step and t_add are unused); a row with live[row] == 0 (live may be null:
+// every row is live) leaves before the first barrier -- live[row] is uniform over the workgroup, one scalar branch -- and writes
+// out = -1, margin = p_max = 0, kept = 0.  DRAW = false stops after the arg-max, margin and p_max: the greedy pick with the same
+// per-row ban (kept, u_out and seed are not touched).
+template <bool ROWS, bool DRAW>
+__global__ __launch_bounds__(SNT) void sample_rows_kernel_t(const float* __restrict__ logits, long ldl, long* __restrict__ out,
+                                                float* __restrict__ margin, float* __restrict__ pmax, int* __restrict__ kept,
+                                                float* __restrict__ u_out, int V, int ban_id, const float* __restrict__ params,
+                                                const unsigned long long* __restrict__ seed, const int* __restrict__ step, int t_add,
+                                                const int* __restrict__ gen, const int* __restrict__ live) {
   __shared__ float sb[SNW], s2[SNW], red[SNW], fsum[SNW];
   __shared__ int si[SNW], isum[SNW];
   __shared__ unsigned hist[256];
@@ -92,10 +103,22 @@ __global__ __launch_bounds__(SNT) void sample_rows_kernel(const float* __restric
   const float inv_temp = params[0], top_p = params[1];
   int k = (int)params[2];
   k = k < 1 ? 1 : (k > V ? V : k);
+  if (ROWS) {
+    if (live && !live[row]) {
+      if (tid == 0) {
+        out[row] = -1;
+        margin[row] = 0.f;
+        pmax[row] = 0.f;
+        if (DRAW) kept[row] = 0;
+      }
+      return;
+    }
+    ban_id = gen[row] < (int)params[4] ? (int)params[5] : -1;
+  }
 
-  if (tid == 0) {
-    const unsigned long long sd = *seed;
-    unsigned c[4] = {(unsigned)((step ? *step : 0) + t_add), 0u, (unsigned)row, 0u};
+  if (DRAW && tid == 0) {
+    const unsigned long long sd = ROWS ? seed[row] : *seed;
+    unsigned c[4] = {ROWS ? (unsigned)gen[row] : (unsigned)((step ? *step : 0) + t_add), 0u, ROWS ? 0u : (unsigned)row, 0u};
     philox4x32_10(c, (unsigned)sd, (unsigned)(sd >> 32));
     sh_u = (float)(c[0] >> 8) * (1.0f / 16777216.0f);
   }
@@ -145,8 +168,10 @@ __global__ __launch_bounds__(SNT) void sample_rows_kernel(const float* __restric
     if (tid == 0) {
       if (margin) margin[row] = all.best - all.second;
       if (pmax) pmax[row] = 1.f / s;
+      if (!DRAW) out[row] = all.idx;
     }
   }
+  if (!DRAW) return;
 
   // 2. temperature (HF TemperatureLogitsWarper), then the k-th largest tempered logit: radix select over the ordered keys, 8 bits
   //    a pass from the top; past-V and banned entries are -inf, the smallest key, so they never move the k-th value of a row
@@ -260,8 +285,36 @@ extern "C" int mh_sample_rows(const float* logits, long ldl, long* out, float* m
   if (R <= 0) return MH_OK;
   if (!logits || !out || !kept || !params || !seed || V <= 0 || ldl < V) return MH_ERR_ARG;
   if (V > 8 * SNT * 4 || (ldl % 4) != 0 || ((uintptr_t)logits & 15)) return MH_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(sample_rows_kernel, dim3(R), dim3(SNT), 0, stream, logits, ldl, out, margin, pmax, kept, u_out, V, ban_id, params,
-                     seed, step, t_add);
+  hipLaunchKernelGGL((sample_rows_kernel_t<false, true>), dim3(R), dim3(SNT), 0, stream, logits, ldl, out, margin, pmax, kept, u_out, V,
+                     ban_id, params, seed, step, t_add, (const int*)nullptr, (const int*)nullptr);
+  MH_CHECK_LAUNCH();
+  return MH_OK;
+}
+
+// The slot forms: what the uniform sampler refuses they refuse; margin and pmax are required (an idle row writes them).
+static int slots_args(const float* logits, long ldl, int V) {
+  if (V <= 0 || ldl < V) return MH_ERR_ARG;
+  if (V > 8 * SNT * 4 || (ldl % 4) != 0 || ((uintptr_t)logits & 15)) return MH_ERR_UNSUPPORTED;
+  return MH_OK;
+}
+extern "C" int mh_sample_rows_slots(const float* logits, long ldl, long* out, float* margin, float* pmax, int* kept, float* u_out, int R,
+                                    int V, const float* params, const unsigned long long* seed, const int* gen, const int* live,
+                                    hipStream_t stream) {
+  if (R <= 0) return MH_OK;
+  if (!logits || !out || !margin || !pmax || !kept || !params || !seed || !gen) return MH_ERR_ARG;
+  if (const int e = slots_args(logits, ldl, V)) return e;
+  hipLaunchKernelGGL((sample_rows_kernel_t<true, true>), dim3(R), dim3(SNT), 0, stream, logits, ldl, out, margin, pmax, kept, u_out, V, -1,
+                     params, seed, (const int*)nullptr, 0, gen, live);
+  MH_CHECK_LAUNCH();
+  return MH_OK;
+}
+extern "C" int mh_argmax_pmax_rows_slots(const float* logits, long ldl, long* out, float* margin, float* pmax, int R, int V,
+                                         const float* params, const int* gen, const int* live, hipStream_t stream) {
+  if (R <= 0) return MH_OK;
+  if (!logits || !out || !margin || !pmax || !params || !gen) return MH_ERR_ARG;
+  if (const int e = slots_args(logits, ldl, V)) return e;
+  hipLaunchKernelGGL((sample_rows_kernel_t<true, false>), dim3(R), dim3(SNT), 0, stream, logits, ldl, out, margin, pmax, (int*)nullptr,
+                     (float*)nullptr, V, -1, params, (const unsigned long long*)nullptr, (const int*)nullptr, 0, gen, live);
   MH_CHECK_LAUNCH();
   return MH_OK;
 }
@@ -269,10 +322,13 @@ extern "C" int mh_sample_rows(const float* logits, long ldl, long* out, float* m
 // ---------------------------------------------------------------------------------------------------- repetition penalty
 // HF RepetitionPenaltyLogitsProcessor on the generated tokens (generate(inputs_embeds=...) starts input_ids empty): each id once,
 // however often it was generated.  The thread that owns the bitmap word of prev_ids[row] sets its bit, so no other thread races it.
-__global__ __launch_bounds__(256) void repetition_penalty_kernel(float* __restrict__ logits, long ldl, unsigned* __restrict__ seen,
-                                                                 const long* __restrict__ prev_ids, int V, int W,
-                                                                 const float* __restrict__ penalty) {
+// ROWS: the slot form, a row with live[row] == 0 changes neither its logits nor its bitmap.
+template <bool ROWS>
+__device__ __forceinline__ void repetition_penalty_body(float* __restrict__ logits, long ldl, unsigned* __restrict__ seen,
+                                                        const long* __restrict__ prev_ids, int V, int W,
+                                                        const float* __restrict__ penalty, const int* __restrict__ live) {
   const long row = blockIdx.x;
+  if (ROWS && !live[row]) return;
   const float pen = *penalty;
   float* x = logits + row * ldl;
   unsigned* sr = seen + row * W;
@@ -294,11 +350,32 @@ __global__ __launch_bounds__(256) void repetition_penalty_kernel(float* __restri
   }
 }
 
+__global__ __launch_bounds__(256) void repetition_penalty_kernel(float* __restrict__ logits, long ldl, unsigned* __restrict__ seen,
+                                                                 const long* __restrict__ prev_ids, int V, int W,
+                                                                 const float* __restrict__ penalty) {
+  repetition_penalty_body<false>(logits, ldl, seen, prev_ids, V, W, penalty, nullptr);
+}
+__global__ __launch_bounds__(256) void repetition_penalty_slots_kernel(float* __restrict__ logits, long ldl, unsigned* __restrict__ seen,
+                                                                       const long* __restrict__ prev_ids, int V, int W,
+                                                                       const float* __restrict__ penalty, const int* __restrict__ live) {
+  repetition_penalty_body<true>(logits, ldl, seen, prev_ids, V, W, penalty, live);
+}
+
 extern "C" int mh_repetition_penalty_rows(float* logits, long ldl, unsigned* seen, const long* prev_ids, int R, int V,
                                           const float* penalty, hipStream_t stream) {
   if (R <= 0) return MH_OK;
   if (!logits || !seen || !penalty || V <= 0 || ldl < V) return MH_ERR_ARG;
   hipLaunchKernelGGL(repetition_penalty_kernel, dim3(R), dim3(256), 0, stream, logits, ldl, seen, prev_ids, V, (V + 31) / 32, penalty);
+  MH_CHECK_LAUNCH();
+  return MH_OK;
+}
+
+extern "C" int mh_repetition_penalty_rows_slots(float* logits, long ldl, unsigned* seen, const long* prev_ids, int R, int V,
+                                                const float* penalty, const int* live, hipStream_t stream) {
+  if (R <= 0) return MH_OK;
+  if (!logits || !seen || !penalty || !live || V <= 0 || ldl < V) return MH_ERR_ARG;
+  hipLaunchKernelGGL(repetition_penalty_slots_kernel, dim3(R), dim3(256), 0, stream, logits, ldl, seen, prev_ids, V, (V + 31) / 32,
+                     penalty, live);
   MH_CHECK_LAUNCH();
   return MH_OK;
 }
@@ -327,6 +404,45 @@ extern "C" int mh_decode_advance_kept(const long* nxt, const float* margin, cons
   if (!nxt || !margin || !pmax || !kept || !rec || !next_ids || !step || !pos || !kvlen) return MH_ERR_ARG;
   hipLaunchKernelGGL(decode_advance_kept_kernel, dim3(1), dim3(64), 0, stream, nxt, margin, pmax, kept, rec, next_ids, step, pos, kvlen,
                      R);
+  MH_CHECK_LAUNCH();
+  return MH_OK;
+}
+
+// The slot engine's form (mh_decode_advance_rows with the kept row and the per-row token count): a row with live[r] != 0 records
+// (id, margin, p_max, kept), feeds its id back and advances pos, kvlen and gen; an idle row records (-1, 0, 0, 0) and keeps all its
+// state.  kept may be null (the greedy pick has no kept set): the fourth record row is then 0.
+__global__ void decode_advance_kept_rows_kernel(const long* __restrict__ nxt, const float* __restrict__ margin,
+                                                const float* __restrict__ pmax, const int* __restrict__ kept, float* __restrict__ rec,
+                                                long* __restrict__ next_ids, int* __restrict__ step, int* __restrict__ pos,
+                                                int* __restrict__ kvlen, int* __restrict__ gen, const int* __restrict__ live, int R) {
+  for (int r = threadIdx.x; r < R; r += blockDim.x) {
+    if (live[r]) {
+      const long id = nxt[r];
+      rec[r] = (float)id;
+      rec[R + r] = margin[r];
+      rec[2 * R + r] = pmax[r];
+      rec[3 * R + r] = kept ? (float)kept[r] : 0.f;
+      next_ids[r] = id;
+      pos[r] += 1;
+      kvlen[r] += 1;
+      gen[r] += 1;
+    } else {
+      rec[r] = -1.f;
+      rec[R + r] = 0.f;
+      rec[2 * R + r] = 0.f;
+      rec[3 * R + r] = 0.f;
+    }
+  }
+  if (threadIdx.x == 0) *step += 1;
+}
+
+extern "C" int mh_decode_advance_kept_rows(const long* nxt, const float* margin, const float* pmax, const int* kept, float* rec,
+                                           long* next_ids, int* step, int* pos, int* kvlen, int* gen, const int* live, int R,
+                                           hipStream_t stream) {
+  if (R <= 0) return MH_OK;
+  if (!nxt || !margin || !pmax || !rec || !next_ids || !step || !pos || !kvlen || !gen || !live) return MH_ERR_ARG;
+  hipLaunchKernelGGL(decode_advance_kept_rows_kernel, dim3(1), dim3(64), 0, stream, nxt, margin, pmax, kept, rec, next_ids, step, pos,
+                     kvlen, gen, live, R);
   MH_CHECK_LAUNCH();
   return MH_OK;
 }

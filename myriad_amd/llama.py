@@ -1176,6 +1176,34 @@ class RefillPlanner:
         return list(zip(free, group))
 
 
+def seeded_requests(requests, generator: Optional[torch.Generator] = None, seeds=None):
+    """Pairs every request with the seed of its own random stream: yields (request, seed) in input order.  The seed is drawn when
+    the request is taken from the input -- torch.randint(0, 2**63 - 1, (1,), generator=generator), the draw greedy_generate makes
+    once per call -- so request i gets the i-th draw however RefillPlanner groups or holds back the refills; `seeds` (an iterable
+    of ints in [0, 2**63), one per request in input order) replaces the draws and leaves `generator` untouched.  No device in
+    sight, like SlotScheduler and RefillPlanner."""
+    given = None if seeds is None else iter(seeds)
+    for req in requests:
+        if given is None:
+            seed = int(torch.randint(0, 2**63 - 1, (1,), generator=generator))
+        else:
+            seed = next(given, None)
+            if seed is None:
+                raise ValueError("seeds: fewer seeds than requests")
+            seed = int(seed)
+            if not 0 <= seed < 2**63:
+                raise ValueError(f"seeds: {seed} is outside [0, 2**63)")
+        yield req, seed
+
+
+def _request_generator(seed: int, t: int) -> torch.Generator:
+    """The host generator for token t of the request with `seed`: the rare row the device sampler hands back (kept = -1) is drawn
+    from it, never from the run's shared generator, so it cannot shift another request's stream."""
+    g = torch.Generator()
+    g.manual_seed((int(seed) * 0x9E3779B1 + int(t)) % 2**63)
+    return g
+
+
 def replay_slot_run(lengths, ids, slots: int, max_new_tokens: int, stop_ids=(), eos_id: int = 2, prefill_batch: int = 1,
                     prefill_rows: int = 2048, refill_min: int = 1) -> dict:
     """The counters of a slot run whose picks are known: request i has a prompt of lengths[i] rows and generates ids[i] (which must
@@ -1214,6 +1242,14 @@ class SlotDecoder:
     Between two replays the host writes only a finished slot's live flag, a refilled slot's (id, pos, kvlen, live) and a host
     draw's id.  greedy_generate and its row-0 rule are untouched; this path is opt-in.
 
+    Device sampling, repetition_penalty != 1 and min_length > 1 run the step's per-row tail instead: mh_repetition_penalty_rows_slots
+    (with a penalty), mh_sample_rows_slots or -- greedy and host draw -- mh_argmax_pmax_rows_slots, then mh_decode_advance_kept_rows.
+    Slot row r then also has gen[r] on the device, the count of tokens its request has generated, which decides its EOS ban
+    (gen[r] < min_length) and, with device sampling, is the Philox step of its draw from its own seed[r]: every request draws from
+    its own counter-based stream (seeded_requests), so its answer does not depend on its neighbours, the slot count or the refill
+    settings.  The knobs (temperature, top_p, top_k, penalty, min_length, eos_id) are read from device memory: one graph per
+    (device-sampled or not, penalty or not).  A refill there also writes the slot's seed and gen = 1 and clears its bitmap row.
+
     Packed prefill (opt-in, `run(prefill_batch=P > 1)` or `refill_min > 1`): at a refill point up to min(P, free slots) waiting
     requests are prefilled in ONE pass over the weights (LlamaHIP._prefill_packed, one mh_attn_prefill_ragged per layer writing
     each request's keys / values into its own slot), one arg-max launch and one device->host copy give all their first picks, and
@@ -1234,10 +1270,13 @@ class SlotDecoder:
         self.graph_captures = 0
         self.last_stats = {}
 
-    def _workspace(self, inv_temp: float) -> dict:
+    def _workspace(self, inv_temp: float, rows_tail=None) -> dict:
         """The step's buffers, kept while the decode weights stay the ones the captured graphs read, and over them one view (its
         own graph / warm flag) per inv_temp: the arg-max kernel takes inv_temp as a launch argument, so a captured step is fixed
-        to one value (LlamaHIP._decode_workspace keys its workspaces the same way)."""
+        to one value (LlamaHIP._decode_workspace keys its workspaces the same way).  `rows_tail` = (device-sampled, penalty) asks
+        for the step with the per-row tail: its buffers join on first use (the knobs `prm`, per-slot `seed` / `gen` / `kept` /
+        `seen`, and `seed0` / `gen0` for the refills' first picks), and a device-sampled view is keyed without inv_temp, which the
+        sampler reads from `prm`."""
         L = self.llama
         L._prepare_decode_weights(self.slots)
         if not (_packed_step(L, self.slots) and L.decode_fused):
@@ -1249,6 +1288,14 @@ class SlotDecoder:
             self.bufs["live"] = torch.zeros((self.slots,), dtype=torch.int32, device=L.dev)
             self._weights = wid
         key = float(inv_temp)
+        if rows_tail is not None:
+            if "prm" not in self.bufs:
+                n, i32 = self.slots, torch.int32
+                self.bufs.update(prm=torch.zeros((6,), dtype=F32, device=L.dev), seed=torch.zeros((n,), dtype=torch.long, device=L.dev),
+                                 seed0=torch.zeros((n,), dtype=torch.long, device=L.dev), gen=torch.zeros((n,), dtype=i32, device=L.dev),
+                                 gen0=torch.zeros((n,), dtype=i32, device=L.dev), kept=torch.zeros((n,), dtype=i32, device=L.dev),
+                                 seen=torch.zeros((n, (L.V + 31) // 32), dtype=i32, device=L.dev))
+            key = (None if rows_tail[0] else key, bool(rows_tail[0]), bool(rows_tail[1]))
         if key not in self.views:
             if len(self.views) >= 4:                                 # a few temperatures at most: drop the oldest graph
                 self.views.pop(next(iter(self.views)))
@@ -1260,37 +1307,68 @@ class SlotDecoder:
     def run(self, requests, max_new_tokens: int = 90, stop_ids=((835,), (2277, 29937)), eos_id: int = 2, min_length: int = 1,
             do_sample: bool = False, top_p: float = 1.0, temperature: float = 1.0, top_k: int = 50,
             generator: Optional[torch.Generator] = None, ordered: bool = False, prefill_batch: int = 1, refill_min: int = 1,
-            prefill_rows: int = 2048):
+            prefill_rows: int = 2048, repetition_penalty: float = 1.0, seeds=None):
         """Decode every request of `requests` (an iterable of [S0_i, D] f32 embeddings, lengths free) and yield
         (index, ids[L_i] int64 on the CPU, margins[L_i] f32) as each finishes -- or, with `ordered`, in input order.  The
         arguments are greedy_generate's; the stop rule is per request.  `last_stats` holds the run's counters: `prefills` counts
         requests, `prefill_passes` passes over the weights and `packed_rows` the request rows they held (padding not counted).
-        `prefill_batch`, `refill_min`, `prefill_rows`: RefillPlanner's; at 1, 1 every refill is the one-request prefill."""
+        `prefill_batch`, `refill_min`, `prefill_rows`: RefillPlanner's; at 1, 1 every refill is the one-request prefill.
+
+        With `device_sampling` (and greedy_generate's conditions on top_k and the vocabulary) every pick is drawn on the device
+        from the request's own stream: request i takes the i-th seed drawn from `generator`, or the i-th of `seeds`, and token t
+        of it is Philox step t -- what greedy_generate draws for that request alone with that seed.  `device_sampled_rows`
+        counts those picks; a row the sampler hands back (kept = -1) is drawn on the host from a generator derived from the
+        request's seed and t (`host_sampled_rows`).  `repetition_penalty` != 1 needs the switch, as in generate(); `min_length`
+        is a per-request EOS ban on every path.  A second run with other values of the knobs replays the same graph."""
         L = self.llama
-        if min_length > 1:
-            raise NotImplementedError("decode slots: min_length > 1 needs a per-row ban, which the captured step does not have")
-        if do_sample and L.device_sampling:
-            raise NotImplementedError("decode slots: device sampling is not supported (rows below top_p are drawn on the host)")
         if do_sample and not float(temperature) > 0:
             raise ValueError(f"temperature must be > 0 when sampling, got {temperature}")
+        if not float(repetition_penalty) > 0:
+            raise ValueError(f"repetition_penalty must be > 0, got {repetition_penalty}")
+        penalty = float(repetition_penalty) != 1.0
+        if penalty and not L.device_sampling:
+            raise NotImplementedError(f"decode slots: repetition_penalty={repetition_penalty} needs the device sampling switch "
+                                      "(MYRIAD_DEVICE_SAMPLING=1 or llama.device_sampling = True)")
         inv_temp = 1.0 / float(temperature) if do_sample else 1.0
         top_k = 0 if top_k is None else int(top_k)
-        ws = self._workspace(inv_temp)
+        dev_sample = bool(L.device_sampling and do_sample and 1 <= top_k <= ops.SAMPLE_CAP and L.V <= 32768 and L.V % 4 == 0)
+        if seeds is not None and not dev_sample:
+            raise ValueError("seeds= names the device sampler's per-request streams: it needs do_sample with device_sampling on")
+        rows_tail = dev_sample or penalty or min_length > 1          # else exactly the launches of the plain slot step
+        ws = self._workspace(inv_temp, (dev_sample, penalty) if rows_tail else None)
         sched = SlotScheduler(self.slots, max_new_tokens, stop_ids, eos_id, ordered=ordered)
         stats = dict(steps=0, graph_replays=0, graph_captures=self.graph_captures, prefills=0, live_row_steps=0, occupancy=0.0,
-                     host_sampled_rows=0, prefill_passes=0, packed_rows=0)
+                     host_sampled_rows=0, device_sampled_rows=0, prefill_passes=0, packed_rows=0)
         packed = int(prefill_batch) != 1 or int(refill_min) != 1
-        plan = RefillPlanner(sched, requests, prefill_batch, prefill_rows, refill_min, length=lambda e: int(e.shape[0]))
+        # a request travels with the seed of its own stream (None unless the device draws)
+        reqs = seeded_requests(requests, generator, seeds) if dev_sample else ((emb, None) for emb in requests)
+        plan = RefillPlanner(sched, reqs, prefill_batch, prefill_rows, refill_min, length=lambda q: int(q[0].shape[0]))
         self.last_stats = stats
         ban0 = eos_id if 0 < min_length else -1
-        rec = ws["rec"][:3]
+        rec = ws["rec"] if rows_tail else ws["rec"][:3]
+        seed_of = {}                                                 # slot -> its request's seed
         ws["live"].zero_()                                           # an abandoned run may have left slots live
         ws["step"].zero_()
+        if rows_tail:
+            ws["prm"].copy_(torch.tensor([inv_temp, top_p, float(top_k), float(repetition_penalty), float(min_length), float(eos_id)],
+                                         dtype=F32))
 
         def token_step(_ban):
             L._step_logits(ws)
-            ops.argmax_pmax_rows(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ban_id=-1, inv_temp=inv_temp)
-            ops.decode_advance_rows(ws["nxt"], ws["mar"], ws["pmx"], rec, ws["ids"], ws["step"], ws["pos"], ws["kvlen"], ws["live"])
+            if not rows_tail:
+                ops.argmax_pmax_rows(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ban_id=-1, inv_temp=inv_temp)
+                ops.decode_advance_rows(ws["nxt"], ws["mar"], ws["pmx"], rec, ws["ids"], ws["step"], ws["pos"], ws["kvlen"],
+                                        ws["live"])
+                return
+            if penalty:                                              # ws["ids"] = the token fed in: it joins the seen set first
+                ops.repetition_penalty_rows_slots(ws["logits"], ws["seen"], ws["ids"], ws["prm"][3:], ws["live"])
+            if dev_sample:                                           # row r draws Philox step gen[r] of seed[r]
+                ops.sample_rows_slots(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ws["kept"], ws["prm"], ws["seed"], ws["gen"],
+                                      ws["live"])
+            else:
+                ops.argmax_pmax_rows_slots(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ws["prm"], ws["gen"], ws["live"])
+            ops.decode_advance_kept_rows(ws["nxt"], ws["mar"], ws["pmx"], ws["kept"] if dev_sample else None, rec, ws["ids"],
+                                         ws["step"], ws["pos"], ws["kvlen"], ws["gen"], ws["live"])
 
         def results():
             for index, ids, mar in sched.pop():
@@ -1303,43 +1381,70 @@ class SlotDecoder:
                                  f"{min(self.T_cap, L.cos.shape[0])} positions")
             return S0
 
-        def go_live(s: int, first: int, S0: int) -> None:
+        def go_live(s: int, first: int, S0: int, seed) -> None:
             sl = slice(s, s + 1)
             ws["ids"][sl].fill_(first)
             ws["pos"][sl].fill_(S0)                                  # position of the incoming token
             ws["kvlen"][sl].fill_(S0 + 1)                            # valid keys after the append
+            if rows_tail:
+                ws["gen"][sl].fill_(1)                               # the prefill pick was token 0
+                if dev_sample:
+                    ws["seed"][sl].fill_(seed)
+                    seed_of[s] = seed
+                if penalty:
+                    ws["seen"][sl].zero_()                           # generated ids only, and the last request's are gone
             ws["live"][sl].fill_(1)
 
-        def refill_packed(group) -> None:
-            """Prefill the group's requests in one packed pass, each into its slot; one arg-max launch and one device->host copy
-            for all first picks; admission in input order."""
-            R, lens = len(group), [fits(emb) for _, emb in group]
-            logits0 = L._prefill_packed([emb for _, emb in group], [s for s, _ in group], ws["caches"])
-            stats["prefills"] += R
-            ops.argmax_pmax_rows(logits0, ws["nxt"][:R], ws["mar"][:R], ws["pmx"][:R], ban_id=ban0, inv_temp=inv_temp)
-            picks = torch.stack([ws["nxt"][:R].to(torch.float64), ws["mar"][:R].double(), ws["pmx"][:R].double()]).tolist()
-            for i, (s, _) in enumerate(group):
-                first = int(picks[0][i])
-                if do_sample and picks[2][i] < top_p:
-                    first = _host_draw(logits0[i], ban0, inv_temp, top_k, top_p, generator)
-                    stats["host_sampled_rows"] += 1
-                if sched.admit(s, first, picks[1][i]):
-                    go_live(s, first, lens[i])
+        def first_picks(logits0: torch.Tensor, sl: slice, seeds_) -> list:
+            """The first pick of each prefilled request (rows of logits0) in one launch into the step's result buffers at `sl` and
+            one device->host copy: rows of [id, margin, p_max, kept].  The per-row tail's pick is its step kernel at gen = 0."""
+            out = [ws["nxt"][sl], ws["mar"][sl], ws["pmx"][sl]]
+            R = logits0.shape[0]
+            if dev_sample:
+                ws["seed0"][:R].copy_(torch.tensor(seeds_, dtype=torch.long))
+                ops.sample_rows_slots(logits0, *out, ws["kept"][sl], ws["prm"], ws["seed0"][:R], ws["gen0"][:R])
+                out.append(ws["kept"][sl])
+            elif rows_tail:
+                ops.argmax_pmax_rows_slots(logits0, *out, ws["prm"], ws["gen0"][:R])
+            else:
+                ops.argmax_pmax_rows(logits0, *out, ban_id=ban0, inv_temp=inv_temp)
+            return torch.stack([o.to(torch.float64) for o in out], 1).tolist()
 
-        def refill(s: int, emb: torch.Tensor) -> None:
+        def first_id(pick, logits_row: torch.Tensor, seed) -> int:
+            """The request's first token from its pick: the device's draw, or the host's where the rules hand the row to it."""
+            first = int(pick[0])
+            if dev_sample and pick[3] >= 0:
+                stats["device_sampled_rows"] += 1
+            elif dev_sample:
+                first = _host_draw(logits_row, ban0, inv_temp, top_k, top_p, _request_generator(seed, 0))
+                stats["host_sampled_rows"] += 1
+            elif do_sample and pick[2] < top_p:
+                first = _host_draw(logits_row, ban0, inv_temp, top_k, top_p, generator)
+                stats["host_sampled_rows"] += 1
+            return first
+
+        def refill_packed(group) -> None:
+            """Prefill the group's requests in one packed pass, each into its slot; one pick launch and one device->host copy
+            for all first picks; admission in input order."""
+            R, lens = len(group), [fits(emb) for _, (emb, _) in group]
+            logits0 = L._prefill_packed([emb for _, (emb, _) in group], [s for s, _ in group], ws["caches"])
+            stats["prefills"] += R
+            picks = first_picks(logits0, slice(0, R), [seed for _, (_, seed) in group])
+            for i, (s, (_, seed)) in enumerate(group):
+                first = first_id(picks[i], logits0[i], seed)
+                if sched.admit(s, first, picks[i][1]):
+                    go_live(s, first, lens[i], seed)
+
+        def refill(s: int, req) -> None:
             """Prefill one request alone into slot s and take its first pick; the slot goes live if the request goes on."""
+            emb, seed = req
             S0 = fits(emb)
             logits0 = L._prefill(emb[None].to(L.dev), [c[s:s + 1] for c in ws["caches"]])
             stats["prefills"] += 1
-            sl = slice(s, s + 1)
-            ops.argmax_pmax_rows(logits0, ws["nxt"][sl], ws["mar"][sl], ws["pmx"][sl], ban_id=ban0, inv_temp=inv_temp)
-            first, mar, pm = torch.cat([ws["nxt"][sl].to(torch.float64), ws["mar"][sl].double(), ws["pmx"][sl].double()]).tolist()
-            first = int(first)                                       # one device->host copy for the three
-            if do_sample and pm < top_p:
-                first = _host_draw(logits0[0], ban0, inv_temp, top_k, top_p, generator)
-                stats["host_sampled_rows"] += 1
-            if sched.admit(s, first, mar):
-                go_live(s, first, S0)
+            pick = first_picks(logits0, slice(s, s + 1), [seed])[0]
+            first = first_id(pick, logits0[0], seed)
+            if sched.admit(s, first, pick[1]):
+                go_live(s, first, S0, seed)
 
         try:
             while True:
@@ -1360,10 +1465,20 @@ class SlotDecoder:
                     self.graph_captures += 1
                 r = rec.cpu()                                        # the one device->host copy of the step (it also waits for it)
                 ids = r[0].long().tolist()
-                if do_sample:
+                if dev_sample:
+                    for s in live:
+                        if float(r[3][s]) >= 0:
+                            stats["device_sampled_rows"] += 1        # drawn by the step itself
+                            continue
+                        t = len(sched.rows[s][1])                    # the row's gen when the step ran
+                        ids[s] = _host_draw(ws["logits"][s], eos_id if t < min_length else -1, inv_temp, top_k, top_p,
+                                            _request_generator(seed_of[s], t))
+                        stats["host_sampled_rows"] += 1
+                elif do_sample:
                     for s in live:
                         if float(r[2][s]) < top_p:                   # greedy_generate's rule per row: below top_p the host draws
-                            ids[s] = _host_draw(ws["logits"][s], -1, inv_temp, top_k, top_p, generator)
+                            ban = eos_id if len(sched.rows[s][1]) < min_length else -1
+                            ids[s] = _host_draw(ws["logits"][s], ban, inv_temp, top_k, top_p, generator)
                             stats["host_sampled_rows"] += 1
                 finished = sched.step(ids, r[1].tolist())
                 for s in live:

@@ -1307,7 +1307,7 @@ class MyriadHIP(nn.Module):
             as_.append(tok(pa, return_tensors="pt", add_special_tokens=False).input_ids[0])
         return bs, as_
 
-    def generate_stream(self, batches, slots: int = 8, prefill_batch: int = 1, refill_min: int = 1, **generate_kwargs):
+    def generate_stream(self, batches, slots: int = 8, prefill_batch: int = 1, refill_min: int = 1, seeds=None, **generate_kwargs):
         """generate() for a whole run: `batches` (an iterable of generate()'s sample dicts, e.g. a DataLoader) streams through
         `slots` decode slots (LlamaHIP.slot_decoder).  Each batch is encoded as generate() encodes it (image, maps, encode_img at
         the batch's own size), each of its rows is tokenised and assembled on its own -- questions of different lengths are fine,
@@ -1315,25 +1315,27 @@ class MyriadHIP(nn.Module):
         ends on EOS, on a stop sequence at the end of ITS ids or at max_new_tokens, and its slot takes the next row at once.
 
         Yields {"index", "token_ids": [L] int64 (CPU), "ve_anomaly_map"} per sample in input order (index counts samples
-        over all batches), so a sampled run is reproducible per `generator`.  Takes generate()'s keyword arguments; refuses
-        (NotImplementedError) what the captured per-row step has no form of: repetition_penalty != 1, num_beams > 1,
-        min_length > 1 and device sampling.  An unknown argument is a TypeError.  `last_generate_stats` holds the engine's
-        counters (steps, prefills, graph_replays, graph_captures, live_row_steps, occupancy, prefill_passes, packed_rows) once the
+        over all batches), so a sampled run is reproducible per `generator`.  Takes generate()'s keyword arguments without beams:
+        num_beams > 1 is refused (NotImplementedError), repetition_penalty != 1 needs the device sampling switch, as in
+        generate(), and so does min_length > 1 here (SlotDecoder.run itself takes it on every path).  With that switch on, a
+        sampled run draws every token on the device and each sample from its own stream: sample i takes the i-th seed drawn from `generator` (or the i-th of `seeds`, an iterable of ints), so its answer does not
+        depend on the slot count, the refill settings or its neighbours (SlotDecoder.run).  min_length is a per-sample EOS ban.
+        An unknown argument is a TypeError.  `last_generate_stats` holds the engine's counters (steps, prefills, graph_replays,
+        graph_captures, live_row_steps, occupancy, prefill_passes, packed_rows, host_sampled_rows, device_sampled_rows) once the
         stream is exhausted.  `prefill_batch` = P > 1 prefills up to P waiting samples in one packed pass whenever slots are free
         and `refill_min` = k holds a refill back until k slots are free (SlotDecoder.run); both default to 1, the one-sample refill."""
         self.finish_update()
         a = self._generate_args(generate_kwargs)
-        if a["rep_pen"] != 1.0:
-            raise NotImplementedError(f"generate_stream(repetition_penalty={a['rep_pen']}) is not implemented in decode slots")
         if a["num_beams"] > 1:
             raise NotImplementedError(f"generate_stream(num_beams={a['num_beams']}): decode slots have no beam search")
-        if a["min_length"] > 1:
-            raise NotImplementedError(f"generate_stream(min_length={a['min_length']}): decode slots ban EOS for the first token only")
-        if a["do_sample"] and self.llama.device_sampling:
-            raise NotImplementedError("generate_stream: device sampling is not implemented in decode slots")
         max_new = a["max_new"]
         if max_new is None:
             raise NotImplementedError("generate_stream(max_length=...): pass max_new_tokens, the prompts differ in length")
+        if a["min_length"] > 1 and not self.llama.device_sampling:
+            # the slot engine takes the per-row ban on every path (SlotDecoder.run); this entry keeps its earlier refusal
+            # unless the device sampling switch is on, the same condition as the penalty's
+            raise NotImplementedError(f"generate_stream(min_length={a['min_length']}) needs the device sampling switch "
+                                      "(MYRIAD_DEVICE_SAMPLING=1 or model.llama.device_sampling = True)")
         stage = 1 if self.arch == "myriad" else 0
         side = []                                                      # per sample, in input order: its anomaly map
 
@@ -1365,7 +1367,8 @@ class MyriadHIP(nn.Module):
             for index, ids, _ in dec.run(rows(), max_new_tokens=max_new, stop_ids=a["stops"], eos_id=a["eos_id"],
                                          min_length=a["min_length"], do_sample=a["do_sample"], top_p=a["top_p"],
                                          temperature=a["temperature"], top_k=a["top_k"], generator=a["generator"], ordered=True,
-                                         prefill_batch=prefill_batch, refill_min=refill_min):
+                                         prefill_batch=prefill_batch, refill_min=refill_min, repetition_penalty=a["rep_pen"],
+                                         seeds=seeds):
                 self.last_generate_stats = dec.last_stats
                 yield {"index": index, "token_ids": ids, "ve_anomaly_map": side[index]}
                 side[index] = None

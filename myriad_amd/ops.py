@@ -1222,6 +1222,41 @@ def decode_advance_kept(nxt, margin, pmax, kept, rec, next_ids, step_dev, pos, k
                                            _p(kvlen), R, _s()), "mh_decode_advance_kept")
 
 
+def sample_rows_slots(logits: torch.Tensor, out, margin_out, pmax_out, kept_out, params: torch.Tensor, seed: torch.Tensor,
+                      gen: torch.Tensor, live=None, u_out=None):
+    """sample_rows() with per-row state (the slot engine's): params = f32 (inv_temp, top_p, top_k, penalty, min_length, eos_id),
+    seed = int64 [R], gen = int32 [R] (Philox step of row r's draw; eos_id is banned while gen[r] < min_length), live = int32 [R]
+    or None (every row live).  An idle row gets out = -1, margin = p_max = 0, kept = 0."""
+    R, V = logits.shape
+    _lib.check(_L().mh_sample_rows_slots(_p(logits), logits.stride(0), _p(out), _p(margin_out), _p(pmax_out), _p(kept_out), _p(u_out),
+                                         R, V, _p(params), _p(seed), _p(gen), _p(live), _s()), "mh_sample_rows_slots")
+    return out, kept_out
+
+
+def argmax_pmax_rows_slots(logits: torch.Tensor, out, margin_out, pmax_out, params: torch.Tensor, gen: torch.Tensor, live=None):
+    """argmax_pmax_rows() with sample_rows_slots' per-row EOS ban and idle rows; inv_temp is params[0]."""
+    R, V = logits.shape
+    _lib.check(_L().mh_argmax_pmax_rows_slots(_p(logits), logits.stride(0), _p(out), _p(margin_out), _p(pmax_out), R, V, _p(params),
+                                              _p(gen), _p(live), _s()), "mh_argmax_pmax_rows_slots")
+    return out, margin_out, pmax_out
+
+
+def repetition_penalty_rows_slots(logits: torch.Tensor, seen: torch.Tensor, prev_ids, penalty: torch.Tensor, live: torch.Tensor):
+    """repetition_penalty_rows() for the rows with live[r] != 0; an idle row keeps its logits and its bitmap."""
+    R, V = logits.shape
+    _lib.check(_L().mh_repetition_penalty_rows_slots(_p(logits), logits.stride(0), _p(seen), _p(prev_ids), R, V, _p(penalty), _p(live),
+                                                     _s()), "mh_repetition_penalty_rows_slots")
+    return logits
+
+
+def decode_advance_kept_rows(nxt, margin, pmax, kept, rec, next_ids, step_dev, pos, kvlen, gen, live):
+    """decode_advance_kept() for the rows with live[r] != 0, which also advance gen[r]; an idle row records (-1, 0, 0, 0) and keeps
+    its state.  kept may be None (fourth record row 0)."""
+    R = (nxt if live is None else live).numel()
+    _lib.check(_L().mh_decode_advance_kept_rows(_p(nxt), _p(margin), _p(pmax), _p(kept), _p(rec), _p(next_ids), _p(step_dev), _p(pos),
+                                                _p(kvlen), _p(gen), _p(live), R, _s()), "mh_decode_advance_kept_rows")
+
+
 BEAM_MAX = 8           # most beams mh_beam_topk / mh_beam_reorder_kv take (include/myriad_hip.h)
 
 

@@ -16,7 +16,14 @@ repeat -- streamed through N decode slots (LlamaHIP.slot_decoder), greedy_genera
 row-0 rule: a group runs until its first request stops, later rows are cut or idle), and greedy_generate at batch 1 -- as
 generated tokens per second and samples per second (the tokens each request is due, i.e. what batch 1 produces, count for all).
 --prefill-batch 1,8 --refill-min 1,2,4 (with --slots) adds one slots mode per pair, interleaved with the others: the packed prefill
-of SlotDecoder.run (prefill_batch = 1, refill_min = 1 is the one-request refill, the baseline)."""
+of SlotDecoder.run (prefill_batch = 1, refill_min = 1 is the one-request refill, the baseline).
+--slots N --sample [--modes host,device] [--penalty P] times the sampled slots run instead (do_sample=True, top_p=0.9, top_k=50, one
+generator seed per run), interleaved per repeat: host = the device sampling switch off, rows below top_p drawn on the host from the
+shared generator; device = the switch on, every pick drawn inside the step from the request's own stream, with --penalty as its
+repetition_penalty (the host mode has none: the switch is off there).  A sampled answer leaves the countdown chain, so requests
+run to --new tokens or their stop id, whichever the draws meet first; the generated tokens are counted.  The chain's logits are
+peaked (p_max >= 0.9 at temperature 1, so the host mode never draws there); --temperature T flattens them until rows fall below
+top_p and the host mode draws them."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -30,6 +37,7 @@ ap.add_argument("--llm-layers", type=int, default=32)
 ap.add_argument("--lora", type=int, default=0, help="1: PEFT LoRA r = 8 on q_proj / v_proj attached (the fine-tuned model's generate)")
 ap.add_argument("--sample", action="store_true", help="do_sample=True, top_p=0.9, top_k=50")
 ap.add_argument("--penalty", type=float, default=1.0, help="repetition_penalty")
+ap.add_argument("--temperature", type=float, default=1.0, help="with --slots --sample: the sampled run's temperature")
 ap.add_argument("--modes", default="", help="comma list of greedy / host / device, timed interleaved in one process")
 ap.add_argument("--repeats", type=int, default=1)
 ap.add_argument("--beams", type=int, default=4, help="num_beams of the beam mode")
@@ -84,6 +92,42 @@ if a.slots:
         reqs.append(x.to(dev))
     kw = dict(max_new_tokens=new, stop_ids=((1000,),), eos_id=-5, min_length=0)
     dec = L.slot_decoder(N, 64 * ((160 + new + 63) // 64))
+
+    if a.sample:
+        smodes = [m for m in a.modes.split(",") if m] or ["host", "device"]
+        assert all(m in ("host", "device") for m in smodes), smodes
+        default_dev, sstats = L.device_sampling, {}
+
+        def run_sampled(mode):
+            L.device_sampling = mode == "device"
+            pen = a.penalty if mode == "device" else 1.0
+            out = [len(ids) for _, ids, _ in dec.run(reqs, do_sample=True, top_p=0.9, top_k=50, repetition_penalty=pen, temperature=a.temperature,
+                                                     generator=torch.Generator().manual_seed(0), **kw)]
+            sstats[mode] = dict(dec.last_stats)
+            return sum(out)
+
+        for m in smodes:
+            run_sampled(m)                                         # warm-up: kernels, the mode's graph
+        res = {m: [] for m in smodes}
+        for _ in range(max(1, a.repeats)):
+            for m in smodes:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                n = run_sampled(m)
+                torch.cuda.synchronize()
+                res[m].append((time.perf_counter() - t0, n))
+        L.device_sampling = default_dev
+        print(f"{len(reqs)} requests, prompts {min(lens)}..{max(lens)} rows, sampled top_p 0.9 top_k 50 temperature {a.temperature}, {N} slots, "
+              f"weights {L._packed['kind'] if L._packed else 'bf16'}")
+        for m in smodes:
+            ts = sorted(t for t, _ in res[m])
+            t, n, st = ts[len(ts) // 2], res[m][-1][1], sstats[m]
+            pen = f" penalty {a.penalty}" if m == "device" and a.penalty != 1.0 else ""
+            print(f"slots {N} sampled {m}{pen}: {t * 1e3:.1f} ms (median of {len(ts)}, min {ts[0] * 1e3:.1f}, max {ts[-1] * 1e3:.1f}) -> "
+                  f"{n / t:.0f} tokens/s ({n} tokens), {len(reqs) / t:.1f} samples/s (min {len(reqs) / ts[-1]:.1f}, max "
+                  f"{len(reqs) / ts[0]:.1f}); host-drawn rows {st['host_sampled_rows']}, device-drawn {st['device_sampled_rows']}, "
+                  f"{st['steps']} steps, graph replays {st['graph_replays']}, occupancy {st['occupancy']:.3f}")
+        sys.exit(0)
 
     slot_stats = {}
 
