@@ -443,6 +443,20 @@ int mh_gemv_packed_fp4_rmsnorm(const float* H, long ldh, const float* norm_w, fl
                                int out_f32, float alpha, mh_stream_t s);
 int mh_gemv_packed_fp4_silu(const void* gu, long ldgu, const void* Q, const void* scale, void* C, int ldc, int M, int N, int K,
                             const float* bias, const float* residual, int ldr, int out_f32, float alpha, mh_stream_t s);
+/* The packed products at up to 64 rows (the decode slots above 16 rows): C[M <= 64, N] = alpha * A . W^T (+bias) (+residual)
+ * on the copy mh_gemv_pack / mh_gemv_pack_fp8 / mh_gemv_pack_fp4 wrote -- no other layout.  Each takes the arguments of its
+ * 16-row counterpart.  M > 64 is MH_ERR_ARG; M <= 0 or N <= 0 is MH_OK with nothing written; the alignment and K-step refusals
+ * are the 16-row entries' (K % 64, K % 128 for fp4; lda % 8; A, the copy 16-byte and the scales 4-byte aligned).  M <= 16 runs
+ * the 16-row kernel.  Bit contract: row m of a wide product carries the bits the 16-row entry gives that row on the same copy,
+ * for every M, output type, bias, residual and alpha: per output element the K split over the waves, the step and MFMA order,
+ * the cross-wave sum order and the epilogue order (fp8 row scale, alpha, bias, residual) are the 16-row kernel's; a workgroup
+ * owns several adjacent column blocks so that one activation fragment feeds them all (csrc/gemv.hip). */
+int mh_gemv_packed_wide(const void* A, int lda, const void* P, void* C, int ldc, int M, int N, int K, const float* bias,
+                        const float* residual, int ldr, int out_f32, float alpha, mh_stream_t s);
+int mh_gemv_packed_fp8_wide(const void* A, int lda, const void* Q, const float* scale, void* C, int ldc, int M, int N, int K,
+                            const float* bias, const float* residual, int ldr, int out_f32, float alpha, mh_stream_t s);
+int mh_gemv_packed_fp4_wide(const void* A, int lda, const void* Q, const void* scale, void* C, int ldc, int M, int N, int K,
+                            const float* bias, const float* residual, int ldr, int out_f32, float alpha, mh_stream_t s);
 /* q / v LoRA merged into the decode step's copy of the frozen qkv weight (opt-in, llama.py decode_merge_lora; PEFT merge_adapter).
  * W [3D, D] bf16 rows [q | k | v] with leading dimension ldw (the frozen columns of the bordered wqkv_ext), Aqv [2r, D] fp32 = the
  * masters A_q | A_v, Bq / Bv [D, r] fp32, s = alpha / r, r = 8 or 16.  Merged rule, per element:

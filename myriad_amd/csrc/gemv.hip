@@ -33,6 +33,7 @@
 #include "common.h"
 #include "gemv_pack.h"
 #include <cstdlib>
+#include <type_traits>
 
 typedef unsigned char fp8_t;                                        // one OCP e4m3fn code
 struct fp4_t { unsigned char v; };                                  // two OCP e2m1 codes, the lower k in the low nibble
@@ -739,4 +740,282 @@ extern "C" int mh_gemv_packed_fp4_silu(const void* gu, long ldgu, const void* Q,
                                        hipStream_t stream) {
   return launch_gemv_pro<1, fp4_t>(gu, ldgu, Q, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, nullptr, 0.f, stream,
                                    (const float*)scale);
+}
+
+// ---- 17 .. 64 rows on the same packed copies (the decode slots above 16 rows) ------------------------------------------------
+// mh_gemv_packed_wide / _fp8_wide / _fp4_wide: C[M <= 64, N] on the copy their 16-row counterparts read, no new layout.
+//
+// Bit contract: row m of a wide launch carries the bits the 16-row kernel gives that row (any M, output type, bias, residual,
+// alpha).  A row of v_mfma_f32_16x16x32_bf16 depends on its own A row only, so it is enough to keep, per output element, the
+// K split over the gv_packed_nw(N) waves (per = ceil(nsteps / NW)), the step order inside a wave and the MFMA order inside a
+// step (two; four for fp4), the cross-wave sum w = 0 .. NW-1 starting from 0.f, and the epilogue (fp8 row scale, alpha, bias,
+// residual -- gv_finish below is gemv_kernel's epilogue text).  Which workgroup owns which columns is free, and is the design:
+//
+// A workgroup of the 16-row kernel reads all M x K activations from L2 for 16 columns.  Per workgroup that is M / 16 times its
+// bf16 weight bytes (x2 for fp8, x4 for fp4), so at 64 rows the L2 side carries 4 / 8 / 16 times the HBM stream, against an L2
+// rate of ~70 GB/s per CU (17-19 TB/s chip-wide) beside ~25 GB/s per CU of HBM: L2-bound from ~32 rows on bf16, earlier on the
+// narrow copies.  The region of (column block b, wave w) is `per` contiguous KiB-steps at ((b * NW + w) * per) * 1024 elements,
+// so a workgroup takes G ADJACENT column blocks: wave w walks its K range once, loads each activation fragment once per
+// row tile and feeds it to the weight fragments of all G blocks.  Activation bytes per weight byte fall to M / (16 G).
+//   VGPRs:  ceil(M/16) x G accumulator quads (64 registers at 64 rows, G = 4) + G x U x 8 weight registers of a batch of U steps
+//           (x 4 for fp8) + ceil(M/16) x U x 8 activation registers.  The variants the rule launches, as compiled at 64 rows
+//           (VGPRs, waves per SIMD under __launch_bounds__(.., 2)):  G = 1, U = 2: 76-82, 6;  G = 2, U = 2: 112-126, 4;
+//           G = 4, U = 4, fp8: 220, 2;  G = 4, fp4 (4-step batches of codes, one scale dword each, the 128-deep activation
+//           fragments loaded step by step): 211, 2;  G = 4, U = 4, bf16 (the lm-head alone): 256 with 9 registers (24 B per
+//           lane) spilled to scratch, 2 -- the batch holds 128 weight + 128 activation registers beside 64 accumulators.  It
+//           is kept because it measures faster than the spill-free U = 2 build (138-164 registers, 3 waves: 86.9 us on the
+//           lm-head at 64 rows against 64.7); loading the bf16 activations step by step, as fp4 does, would remove the spill.
+//   Workgroups: ceil(N / 16 / G).  N = 4096 has 256 column blocks, 12288 has 768, 22016 has 1376, 32000 has 2000: any G > 1
+//           leaves CUs without a workgroup at N = 4096, which already under-fills the chip (hence its 8 waves).
+//   LDS:    the cross-wave reduction goes one row tile at a time through red[NW][G][256] (32 KiB at NW = 8, G = 4); wave g
+//           finishes column block g.
+// Measured (MI355X, one product per launch, the weights rotated through 4-12 copies so that none is found in a cache, us per
+// launch, best U of 2 / 4 steps per batch; the 16-row kernel at 16 rows for scale; G and U were build-time sweep settings,
+// only the variants of the rule below are compiled in):
+//                          16 rows |  32 rows: G=1    G=2    G=4 |  64 rows: G=1    G=2    G=4
+//   bf16 qkv   12288x4096    23.7  |          32.5   28.3   36.1 |          52.0   39.5   43.3
+//   bf16 wo     4096x4096    10.9  |          13.1   15.4   23.8 |          21.5   24.9   30.4
+//   bf16 g|u   22016x4096    41.8  |          62.4   43.0   47.2 |         101.0   58.5   57.7
+//   bf16 down  4096x11008    22.9  |          31.4   36.6   55.7 |          49.4   59.9   71.2
+//   bf16 head  32000x4096    55.4  |          80.3   59.0   56.8 |         136.8   77.5   64.7
+//   fp8  qkv                 18.5  |          27.7   21.2   21.8 |          52.1   37.3   30.5
+//   fp8  wo                   7.9  |          11.9   12.9   18.7 |          20.6   22.4   26.5
+//   fp8  g|u                 34.2  |          51.3   32.6   29.9 |          98.4   53.9   45.3
+//   fp8  down                17.9  |          24.8   29.6   41.9 |          47.0   52.7   58.6
+//   fp4  qkv                 16.2  |          31.3   24.6   16.0 |          49.1   44.3   29.0
+//   fp4  wo                   7.5  |          13.3   14.4   16.4 |          19.9   25.2   28.0
+//   fp4  g|u                 27.6  |          65.0   36.8   29.2 |         107.3   65.2   49.7
+//   fp4  down                15.4  |          31.8   32.5   38.1 |          48.9   59.1   65.4
+// So the L2 argument holds where there are column blocks to spare -- the plain "more accumulators" form (G = 1) is 1.3 to 2.2
+// times slower than the grouped one on qkv, gate|up and the lm-head at 64 rows -- and loses to the workgroup count at N = 4096,
+// where grouping halves the CUs at work and G = 1 wins by 14-35 %.  The rule (gv_wide_group): the largest G of 4, 2, 1 that
+// still leaves 384 workgroups on the bf16 copy and 192 on the one-byte copies (their weight bytes per column block are a half
+// and a quarter, so the shared activation read is worth more workgroups there), G = 1 when not even G = 2 does:
+//   bf16: wo / down 1, qkv / gate|up 2, lm-head 4;   fp8, fp4: wo / down 1, qkv / gate|up 4.
+// U = 4 steps per batch with G = 4 (16 KiB of bf16 weights in flight per wave, the 16-row kernel's figure; 64.7 against 86.9 us
+// on the lm-head at 64 rows), 2 otherwise (no gain measured, more registers).  What is left on the table is N = 4096: down at 64 rows costs 2.2 times
+// its 16-row launch, all of it the 1.4 MB of activations every one of its 256 workgroups reads.
+// Rows past M in the last row tile duplicate row M - 1 and column blocks past the last one duplicate the last block; neither
+// is stored.
+__device__ __forceinline__ void gv_finish(float v, int m, int n, void* Cv, const float* bias, const float* res, int ldc, int ldr,
+                                          int out_f32, float alpha) {
+  v *= alpha;
+  if (bias) v += bias[n];
+  if (res) v += res[(size_t)m * ldr + n];
+  if (out_f32) reinterpret_cast<float*>(Cv)[(size_t)m * ldc + n] = v;
+  else reinterpret_cast<bf16_t*>(Cv)[(size_t)m * ldc + n] = f2bf(v);
+}
+
+template <int MT, int G, int UNROLL, int GV_NW, typename WT>
+__global__ __launch_bounds__(GV_NW * 64, 2) void gemv_wide_kernel(const bf16_t* __restrict__ A, const WT* __restrict__ B,
+                                                                  void* __restrict__ Cv, const float* __restrict__ bias,
+                                                                  const float* res, int M, int N, int K, int lda, int ldc, int ldr,
+                                                                  int out_f32, float alpha, const float* __restrict__ wscale) {
+  constexpr bool F4 = gv_is_fp4<WT>, F8 = sizeof(WT) == 1 && !F4;
+  constexpr int KS = F4 ? 128 : 64;
+  static_assert(G <= GV_NW && (!F4 || UNROLL == 4), "wave g finishes block g; an fp4 batch is one scale dword");
+  __shared__ float red[GV_NW][G][16 * 16];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lr = lane & 15, lg = lane >> 4;
+  const int nblocks = (N + 15) / 16, b0 = blockIdx.x * G;
+  const int glive = nblocks - b0 < G ? nblocks - b0 : G;
+  const int nsteps = K / KS;
+  const int per = (nsteps + GV_NW - 1) / GV_NW;
+  const bf16_t* xp[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    const int m = t * 16 + lr;
+    xp[t] = A + (size_t)(m < M ? m : M - 1) * lda + lg * (KS / 4);
+  }
+  const WT* wp[G];
+  const unsigned* sp[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const int b = g < glive ? b0 + g : nblocks - 1;
+    wp[g] = B + ((size_t)b * GV_NW + wave) * per * 1024 + lane * (16 / sizeof(WT));
+    sp[g] = F4 ? reinterpret_cast<const unsigned*>(wscale) + ((size_t)b * GV_NW + wave) * ((per + 3) / 4) * 64 + lane : nullptr;
+  }
+  float4_t acc[MT][G];
+#pragma unroll
+  for (int t = 0; t < MT; ++t)
+#pragma unroll
+    for (int g = 0; g < G; ++g) acc[t][g] = (float4_t){0.f, 0.f, 0.f, 0.f};
+  int s = wave * per;
+  const int s0 = s;
+  const int s_end = (s + per) < nsteps ? (s + per) : nsteps;
+  // one batch of n <= UNROLL steps from step s (full: n = UNROLL, no guards): every load of the batch in flight, then the
+  // products step by step
+  auto batch = [&](auto full_c, int n) {
+    constexpr bool FULL = decltype(full_c)::value;
+    if constexpr (F4) {
+      short8_t w[G][UNROLL];
+      unsigned sc[G];
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u)
+          if (FULL || u < n) w[g][u] = __builtin_nontemporal_load(reinterpret_cast<const short8_t*>(wp[g] + (size_t)(s - s0 + u) * 1024));
+        sc[g] = __builtin_nontemporal_load(sp[g] + (size_t)((s - s0) / 4) * 64);
+      }
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u)
+        if (FULL || u < n) {
+          short8_t x[MT][4];
+#pragma unroll
+          for (int t = 0; t < MT; ++t)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) x[t][i] = *reinterpret_cast<const short8_t*>(xp[t] + (size_t)(s + u) * 128 + 8 * i);
+#pragma unroll
+          for (int g = 0; g < G; ++g) {
+            const gv_u4_t q = __builtin_bit_cast(gv_u4_t, w[g][u]);
+            const float scl = __uint_as_float(((sc[g] >> (8 * u)) & 0xffu) << 23);     // 2^(b-127), gv_mfma_fp4
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              gv_u4_t r;
+              r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q[i], scl, 0));
+              r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q[i], scl, 1));
+              r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q[i], scl, 2));
+              r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q[i], scl, 3));
+#pragma unroll
+              for (int t = 0; t < MT; ++t)
+                acc[t][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x[t][i], __builtin_bit_cast(short8_t, r), acc[t][g], 0, 0, 0);
+            }
+          }
+        }
+    } else {
+      short8_t w0[UNROLL][G], w1[UNROLL][G], x0[UNROLL][MT], x1[UNROLL][MT];
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u)
+        if (FULL || u < n) {
+#pragma unroll
+          for (int g = 0; g < G; ++g) gv_load(wp[g], (size_t)(s - s0 + u), w0[u][g], w1[u][g]);
+#pragma unroll
+          for (int t = 0; t < MT; ++t) {
+            x0[u][t] = *reinterpret_cast<const short8_t*>(xp[t] + (size_t)(s + u) * 64);
+            x1[u][t] = *reinterpret_cast<const short8_t*>(xp[t] + (size_t)(s + u) * 64 + 8);
+          }
+        }
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u)
+        if (FULL || u < n) {
+#pragma unroll
+          for (int g = 0; g < G; ++g) {
+            short8_t a = w0[u][g], b = w1[u][g];
+            if constexpr (F8) {                                        // widened once, used by every row tile
+              const gv_u4_t q = __builtin_bit_cast(gv_u4_t, a);
+              a = fp8x8_to_bf16(q[0], q[1]);
+              b = fp8x8_to_bf16(q[2], q[3]);
+            }
+            // each accumulator takes x0 . w0 before x1 . w1; the row tiles in between keep dependent MFMAs apart
+#pragma unroll
+            for (int t = 0; t < MT; ++t) acc[t][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x0[u][t], a, acc[t][g], 0, 0, 0);
+#pragma unroll
+            for (int t = 0; t < MT; ++t) acc[t][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1[u][t], b, acc[t][g], 0, 0, 0);
+          }
+        }
+    }
+  };
+  for (; s + UNROLL <= s_end; s += UNROLL) batch(std::true_type{}, UNROLL);
+  if (s < s_end) batch(std::false_type{}, s_end - s);
+  // D layout: row m = 4*lg + r, col n = lr.  One row tile at a time through LDS; wave g finishes column block g.
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    if (t) __syncthreads();
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[wave][g][(4 * lg + r) * 16 + lr] = acc[t][g][r];
+    __syncthreads();
+    if (wave < glive) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int ml = 4 * lg + r, m = t * 16 + ml, n = (b0 + wave) * 16 + lr;
+        if (m < M && n < N) {
+          float v = 0.f;
+#pragma unroll
+          for (int w = 0; w < GV_NW; ++w) v += red[w][wave][ml * 16 + lr];
+          if constexpr (F8) v *= wscale[n];              // the row scale s_n first, then alpha
+          gv_finish(v, m, n, Cv, bias, res, ldc, ldr, out_f32, alpha);
+        }
+      }
+    }
+  }
+}
+
+// One launch of the variant (row tiles, column group, waves).  Steps per batch: an fp4 batch is the four steps of one scale
+// dword; bf16 / fp8 take 4 with groups of 4 and 2 otherwise (the header comment above).
+template <int MT, int G, int NW, typename WT>
+static void launch_gemv_wide_v(const dim3 grid, hipStream_t stream, const void* A, const void* P, void* C, const float* bias,
+                               const float* residual, int M, int N, int K, int lda, int ldc, int ldr, int out_f32, float alpha,
+                               const float* wscale) {
+  constexpr int U = gv_is_fp4<WT> || G == 4 ? 4 : 2;
+  hipLaunchKernelGGL((gemv_wide_kernel<MT, G, U, NW, WT>), grid, dim3(NW * 64), 0, stream, (const bf16_t*)A, (const WT*)P, C, bias,
+                     residual, M, N, K, lda, ldc, ldr, out_f32, alpha, wscale);
+}
+
+// column blocks per workgroup: the largest group that leaves min_wg workgroups (the header comment above)
+static int gv_wide_group(int N, bool one_byte) {
+  const int nblocks = (N + 15) / 16, min_wg = one_byte ? 192 : 384;
+  return nblocks / 4 >= min_wg ? 4 : nblocks / 2 >= min_wg ? 2 : 1;
+}
+
+// The (G, NW) pairs the rule reaches -- only these are instantiated.  NW = 8 means fewer than 512 column blocks: G = 1, or 2 on
+// the one-byte copies from 384 blocks.  NW = 4: bf16 G = 1 (512..767 blocks), 2, 4; one-byte G = 2 (512..767), 4.
+template <int MT, typename WT>
+static void launch_gemv_wide_mt(int G, bool nw8, const dim3 grid, hipStream_t stream, const void* A, const void* P, void* C,
+                                const float* bias, const float* residual, int M, int N, int K, int lda, int ldc, int ldr, int out_f32,
+                                float alpha, const float* wscale) {
+  constexpr bool ONE = sizeof(WT) == 1;
+#define GV_WIDE_V(GV, NWV) launch_gemv_wide_v<MT, GV, NWV, WT>(grid, stream, A, P, C, bias, residual, M, N, K, lda, ldc, ldr, out_f32, alpha, wscale)
+  if (nw8) {
+    if constexpr (ONE) {
+      if (G == 2) { GV_WIDE_V(2, 8); return; }
+    }
+    GV_WIDE_V(1, 8);
+  } else if (G == 4) {
+    GV_WIDE_V(4, 4);
+  } else if (ONE || G == 2) {
+    GV_WIDE_V(2, 4);
+  } else {
+    if constexpr (!ONE) GV_WIDE_V(1, 4);
+  }
+#undef GV_WIDE_V
+}
+
+template <typename WT>
+static int launch_gemv_wide(const void* A, int lda, const void* P, const float* wscale, void* C, int ldc, int M, int N, int K,
+                            const float* bias, const float* residual, int ldr, int out_f32, float alpha, hipStream_t stream) {
+  if (M <= 0 || N <= 0) return MH_OK;
+  if (M > 64) return MH_ERR_ARG;
+  if (M <= 16) return launch_gemv_packed<WT>(A, lda, P, wscale, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream);
+  if (K <= 0 || (K % gv_kstep<WT>) != 0 || (lda % 8) != 0 || ((uintptr_t)A & 15) || ((uintptr_t)P & 15)) return MH_ERR_ARG;
+  const int G = gv_wide_group(N, sizeof(WT) == 1), MT = (M + 15) / 16;
+  const dim3 grid(((N + 15) / 16 + G - 1) / G);
+  const bool nw8 = gv_packed_nw(N) == 8;
+#define GV_WIDE_ARGS G, nw8, grid, stream, A, P, C, bias, residual, M, N, K, lda, ldc, ldr, out_f32, alpha, wscale
+  if (MT == 2) launch_gemv_wide_mt<2, WT>(GV_WIDE_ARGS);
+  else if (MT == 3) launch_gemv_wide_mt<3, WT>(GV_WIDE_ARGS);
+  else launch_gemv_wide_mt<4, WT>(GV_WIDE_ARGS);
+#undef GV_WIDE_ARGS
+  MH_CHECK_LAUNCH();
+  return MH_OK;
+}
+
+extern "C" int mh_gemv_packed_wide(const void* A, int lda, const void* P, void* C, int ldc, int M, int N, int K, const float* bias,
+                                   const float* residual, int ldr, int out_f32, float alpha, hipStream_t stream) {
+  return launch_gemv_wide<bf16_t>(A, lda, P, nullptr, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream);
+}
+
+extern "C" int mh_gemv_packed_fp8_wide(const void* A, int lda, const void* Q, const float* scale, void* C, int ldc, int M, int N, int K,
+                                       const float* bias, const float* residual, int ldr, int out_f32, float alpha,
+                                       hipStream_t stream) {
+  if (M > 0 && N > 0 && (!scale || ((uintptr_t)scale & 3))) return MH_ERR_ARG;
+  return launch_gemv_wide<fp8_t>(A, lda, Q, scale, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream);
+}
+
+extern "C" int mh_gemv_packed_fp4_wide(const void* A, int lda, const void* Q, const void* scale, void* C, int ldc, int M, int N, int K,
+                                       const float* bias, const float* residual, int ldr, int out_f32, float alpha,
+                                       hipStream_t stream) {
+  if (M > 0 && N > 0 && (!scale || ((uintptr_t)scale & 3))) return MH_ERR_ARG;
+  return launch_gemv_wide<fp4_t>(A, lda, Q, (const float*)scale, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream);
 }

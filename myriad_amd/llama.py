@@ -195,20 +195,20 @@ class LlamaHIP:
         P["qkv_key"] = qkv_key
         self._packed = P
 
-    def _prepare_decode_weights(self, rows: int) -> dict:
+    def _prepare_decode_weights(self, rows: int, wide: bool = False) -> dict:
         """Before a decode call at `rows` rows: the LoRA's bordered weights refreshed, the packed copies (re)built when the step
         can stream them (MYRIAD_PACK_DECODE=0 drops them: the step streams the row-major matrices).  Returns last_generate_stats'
         decode_weights ("fp8" / "fp4" / "bf16": what the token step streams) and decode_weight_bytes (the weight bytes of one token
-        step: the packed copies, fp8 row scales / fp4 scale bytes included, up to GEMV_MAX_ROWS rows; the row-major bf16 matrices above), lora_merged (the
+        step: the packed copies, fp8 row scales / fp4 scale bytes included, up to GEMV_MAX_ROWS rows -- GEMV_WIDE_MAX_ROWS with `wide`, the slot engine's call; the row-major bf16 matrices above), lora_merged (the
         step streams the LoRA-merged qkv copy) and lora_merges (whole-model merges this model has made so far)."""
         self._decode_kind()                                             # both kinds on: an error whatever this call streams
         if self.lora is not None:
             self.lora.refresh(self.layers)
-        if self.pack_decode and rows <= ops.GEMV_MAX_ROWS:
-            self._pack_for_decode()
+        if self.pack_decode and rows <= (ops.GEMV_WIDE_MAX_ROWS if wide else ops.GEMV_MAX_ROWS):
+            self._pack_for_decode()                                     # wide: the slot engine's route to the copies above 16 rows
         elif not self.pack_decode:
             self._packed, self._packs = None, {}
-        if _packed_step(self, rows):
+        if _packed_step(self, rows, wide):
             mats = [P[k] for P in self._packed["layers"] for k in ("wqkv", "wo", "wgu", "wd")] + [self._packed["lm_head"]]
             nbytes = sum(m.data.numel() * m.data.element_size()
                          + (m.scales.numel() * m.scales.element_size() if hasattr(m, "scales") else 0) for m in mats)
@@ -406,7 +406,7 @@ class LlamaHIP:
 
     # ------------------------------------------------------------------ generation
     def _decode_block(self, h, B, S, caches, scale, pos, past=None, pos_dev=None, kvlen_dev=None, split_ws=None, live=None,
-                      ragged=None):
+                      ragged=None, wide=False):
         """All decoder layers for a prefill chunk (host-known `past`: the chunk's rows go to cache rows past..past+S-1, `pos` holds
         their rotary positions, and causal masking is aligned to the bottom right) or for one decode token whose position lives
         in device memory (`pos_dev`/`kvlen_dev`), which makes the launch sequence replayable from a hipGraph.  `split_ws` (the
@@ -414,10 +414,15 @@ class LlamaHIP:
         [B] on the device, the slot engine's) makes it the rows kernel instead: every row appends at its own pos[b], idle rows
         are skipped; only the fused step has that form.  `ragged` = (segment table on the device, its host copy) makes a prefill
         the packed one (_prefill_packed): B = 1, the S rows hold several requests, `caches` are the whole slot caches, and the
-        three attention launches become one mh_attn_prefill_ragged."""
+        three attention launches become one mh_attn_prefill_ragged.  `wide` (the slot engine above GEMV_MAX_ROWS slots) keeps the
+        token step on the packed copies up to GEMV_WIDE_MAX_ROWS rows: the fused step's launch sequence with
+        ops.gemv_packed_wide as the product and the two-launch forms of the norm / SiLU products, as at 3 to 16 rows.  Every
+        other caller leaves it off and keeps the row-major GEMMs above GEMV_MAX_ROWS rows."""
         H, hd, W, D = self.H, self.hd, self.D, self.D
         M = B * S
-        packed = self._packed["layers"] if pos_dev is not None and _packed_step(self, M) else None
+        packed = self._packed["layers"] if pos_dev is not None and _packed_step(self, M, wide) else None
+        wide = packed is not None and M > ops.GEMV_MAX_ROWS
+        gemv = ops.gemv_packed_wide if wide else ops.gemv_packed
         if live is not None and not (packed is not None and self.decode_fused and split_ws is None):
             raise ValueError("per-row decode state needs the fused packed token step with the single-workgroup attention")
         # the bordered LoRA product unless the packed qkv copy has the LoRA merged in (decode_merge_lora)
@@ -444,23 +449,23 @@ class LlamaHIP:
                     if not lora.norm_border(li, h, L["ln1"], self.eps, x_ext):
                         ops.rmsnorm_fwd(h, L["ln1"], self.eps, out=x_ext[:, :D])
                         lora.forward_border(li, x_ext, training=False)
-                    qkv = ops.gemv_packed(x_ext, P["wqkv"])
+                    qkv = gemv(x_ext, P["wqkv"])
                 else:
-                    qkv = ops.gemv_packed_rmsnorm(h, L["ln1"], self.eps, P["wqkv"])
+                    qkv = None if wide else ops.gemv_packed_rmsnorm(h, L["ln1"], self.eps, P["wqkv"])
                     if qkv is None:
-                        qkv = ops.gemv_packed(ops.rmsnorm_fwd(h, L["ln1"], self.eps), P["wqkv"])
+                        qkv = gemv(ops.rmsnorm_fwd(h, L["ln1"], self.eps), P["wqkv"])
                 if live is not None:
                     o = ops.attn_decode_rope_rows(qkv, cache, pos, kvlen_dev, live, self.cos, self.sin, H, hd, scale)
                 elif split_ws is not None:
                     o = ops.attn_decode_rope_split(qkv, cache, pos, pos_dev, kvlen_dev, self.cos, self.sin, H, hd, scale, split_ws)
                 else:
                     o = ops.attn_decode_rope(qkv, cache, pos, pos_dev, kvlen_dev, self.cos, self.sin, H, hd, scale)
-                h2 = ops.gemv_packed(o, P["wo"], residual=h, out_dtype=F32)
-                gu = ops.gemv_packed_rmsnorm(h2, L["ln2"], self.eps, P["wgu"])
+                h2 = gemv(o, P["wo"], residual=h, out_dtype=F32)
+                gu = None if wide else ops.gemv_packed_rmsnorm(h2, L["ln2"], self.eps, P["wgu"])
                 if gu is None:
-                    gu = ops.gemv_packed(ops.rmsnorm_fwd(h2, L["ln2"], self.eps), P["wgu"])
-                hn = ops.gemv_packed_silu(gu, P["wd"], residual=h2, out_dtype=F32)
-                h = hn if hn is not None else ops.gemv_packed(ops.silu_mul_fwd_blk(gu), P["wd"], residual=h2, out_dtype=F32)
+                    gu = gemv(ops.rmsnorm_fwd(h2, L["ln2"], self.eps), P["wgu"])
+                hn = None if wide else ops.gemv_packed_silu(gu, P["wd"], residual=h2, out_dtype=F32)
+                h = hn if hn is not None else gemv(ops.silu_mul_fwd_blk(gu), P["wd"], residual=h2, out_dtype=F32)
                 continue
             if lora is None:
                 xn = ops.rmsnorm_fwd(h, L["ln1"], self.eps)
@@ -544,17 +549,21 @@ class LlamaHIP:
     def _step_logits(self, ws: dict) -> None:
         """The token step up to its logits: embed the fed ids ws["ids"], every decoder layer at the device-resident position,
         the final norm + lm-head into ws["logits"] -- one launch on the packed copy when the fused form fits, else the norm and
-        the packed GEMV, or the GEMM above GEMV_MAX_ROWS rows."""
+        the packed GEMV, or the GEMM above GEMV_MAX_ROWS rows (the wide packed GEMV there for a workspace marked `wide`: the
+        slot engine's)."""
         ops.embed_gather(self.embed, ws["ids"], ws["x_in"])
         rows = ws["x_in"].shape[0]
+        wide = bool(ws.get("wide"))
         h = self._decode_block(ws["x_in"], rows, 1, ws["caches"], 1.0 / math.sqrt(self.hd), ws["pos"], pos_dev=ws["pos"],
-                               kvlen_dev=ws["kvlen"], split_ws=ws["split"], live=ws.get("live"))
+                               kvlen_dev=ws["kvlen"], split_ws=ws["split"], live=ws.get("live"), wide=wide)
         if _packed_step(self, rows) and self.decode_fused:
             if ops.gemv_packed_rmsnorm(h, self.norm, self.eps, self._packed["lm_head"], out=ws["logits"], out_dtype=F32) is not None:
                 return
         hn = ops.rmsnorm_fwd(h, self.norm, self.eps)
         if _packed_step(self, rows):
             ops.gemv_packed(hn, self._packed["lm_head"], out=ws["logits"], out_dtype=F32)
+        elif _packed_step(self, rows, wide):
+            ops.gemv_packed_wide(hn, self._packed["lm_head"], out=ws["logits"], out_dtype=F32)
         else:
             ops.gemm(hn, self.lm_head, out=ws["logits"])
 
@@ -878,9 +887,11 @@ def _host_draw(logits_row: torch.Tensor, ban: int, inv_temp: float, top_k: int, 
 
 # Decode helpers shared by LlamaHIP and DecodeSession.  They read only the model's fields, so the session needs no more of the
 # model than those.
-def _packed_step(lm: "LlamaHIP", rows: int) -> bool:
-    """The token step at `rows` rows streams the packed copies (ops.gemv_packed takes at most GEMV_MAX_ROWS rows)."""
-    return lm._packed is not None and rows <= ops.GEMV_MAX_ROWS
+def _packed_step(lm: "LlamaHIP", rows: int, wide: bool = False) -> bool:
+    """The token step at `rows` rows streams the packed copies (ops.gemv_packed takes at most GEMV_MAX_ROWS rows).  `wide`: the
+    caller is the slot engine, which stays on them up to GEMV_WIDE_MAX_ROWS rows (ops.gemv_packed_wide); the other decode
+    loops never pass it, so their routing above GEMV_MAX_ROWS rows is the row-major GEMM as before."""
+    return lm._packed is not None and rows <= (ops.GEMV_WIDE_MAX_ROWS if wide else ops.GEMV_MAX_ROWS)
 
 
 def _decode_weights_id(lm: "LlamaHIP") -> tuple:
@@ -1236,6 +1247,8 @@ class SlotDecoder:
     its own prompt length, position and stop rule; a slot whose request ends is refilled with the next one while the others go on
     decoding, so no row is computed and thrown away for long and no request is cut short by another's stop.
 
+    1 to GEMV_WIDE_MAX_ROWS slots.  Above GEMV_MAX_ROWS slots the products are ops.gemv_packed_wide on the same packed copies, whose
+    rows carry the 16-row kernel's bits: a request's ids and margins do not depend on the slot count.
     The step is greedy_generate's fused packed step (bf16 / FP8 / MXFP4 copies, merged or bordered LoRA alike) with two launches
     swapped: the attention is mh_attn_decode_rope_rows (row b appends at pos[b], idle rows skipped) and the bookkeeping is
     mh_decode_advance_rows (idle rows record id -1).  A refill is the existing B = 1 prefill into the slot's slice of every cache.
@@ -1257,8 +1270,8 @@ class SlotDecoder:
 
     def __init__(self, llama: "LlamaHIP", slots: int, capacity: int):
         slots = int(slots)
-        if slots < 1 or slots > ops.GEMV_MAX_ROWS:
-            raise ValueError(f"slots={slots}: the slot engine runs the packed token step, 1 to {ops.GEMV_MAX_ROWS} rows")
+        if slots < 1 or slots > ops.GEMV_WIDE_MAX_ROWS:
+            raise ValueError(f"slots={slots}: the slot engine runs the packed token step, 1 to {ops.GEMV_WIDE_MAX_ROWS} rows")
         self.llama, self.slots = llama, slots
         self.T_cap = ops.round_up(int(capacity), 64)
         if not 0 < self.T_cap <= 8192:
@@ -1278,14 +1291,15 @@ class SlotDecoder:
         `seen`, and `seed0` / `gen0` for the refills' first picks), and a device-sampled view is keyed without inv_temp, which the
         sampler reads from `prm`."""
         L = self.llama
-        L._prepare_decode_weights(self.slots)
-        if not (_packed_step(L, self.slots) and L.decode_fused):
+        L._prepare_decode_weights(self.slots, wide=True)
+        if not (_packed_step(L, self.slots, True) and L.decode_fused):
             raise ValueError("the slot engine needs the fused packed token step (MYRIAD_PACK_DECODE and MYRIAD_DECODE_FUSED on)")
         wid = _decode_weights_id(L)
         if self.bufs is None or self._weights != wid:
             self.bufs, self.views, self.ws = None, {}, None
             self.bufs = _decode_buffers(L, self.slots, self.T_cap)
             self.bufs["live"] = torch.zeros((self.slots,), dtype=torch.int32, device=L.dev)
+            self.bufs["wide"] = True                                 # above GEMV_MAX_ROWS slots the step stays on the packed copies
             self._weights = wid
         key = float(inv_temp)
         if rows_tail is not None:

@@ -344,6 +344,29 @@ def gemv_packed(a: torch.Tensor, pw, out: Optional[torch.Tensor] = None, bias: O
     return out
 
 
+def gemv_packed_wide(a: torch.Tensor, pw, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                     residual: Optional[torch.Tensor] = None, out_dtype=BF16, alpha: float = 1.0) -> torch.Tensor:
+    """gemv_packed() for up to GEMV_WIDE_MAX_ROWS rows on the same packed copy (mh_gemv_packed*_wide): row m carries the bits
+    gemv_packed() gives that row, whatever M; a workgroup shares each activation fragment over several column blocks."""
+    _chk2d(a, BF16, "gemv_packed_wide.a")
+    M, K = a.shape
+    if K != pw.K or M > GEMV_WIDE_MAX_ROWS:
+        raise _lib.MyriadHipError(f"gemv_packed_wide: a is {tuple(a.shape)}, weight was packed as [{pw.N}, {pw.K}], "
+                                  f"M must be <= {GEMV_WIDE_MAX_ROWS}")
+    if out is None:
+        out = torch.empty((M, pw.N), dtype=out_dtype, device=a.device)
+    ldr = 0
+    if residual is not None:
+        _chk2d(residual, F32, "gemv_packed_wide.residual")
+        ldr = residual.stride(0)
+    name = _packed_entry("_wide", pw)
+    wargs = (_p(pw.data), _p(pw.scales)) if isinstance(pw, (PackedFp8Weight, PackedFp4Weight)) else (_p(pw.data),)
+    rc = getattr(_L(), name)(_p(a), a.stride(0), *wargs, _p(out), out.stride(0), M, pw.N, K, _p(bias), _p(residual), ldr,
+                             1 if out.dtype == F32 else 0, float(alpha), _s())
+    _lib.check(rc, f"{name} M={M} N={pw.N} K={K}")
+    return out
+
+
 def _gemv_pro(fn, name, a, lda, pw, out, residual, out_dtype, alpha, M, *pre):
     if out is None:
         out = torch.empty((M, pw.N), dtype=out_dtype, device=a.device)
@@ -1194,6 +1217,7 @@ def decode_advance_rows(nxt, margin, pmax, rec, next_ids, step_dev, pos, kvlen, 
 
 
 GEMV_MAX_ROWS = 16     # most rows mh_gemv_packed and its fused forms take (include/myriad_hip.h)
+GEMV_WIDE_MAX_ROWS = 64    # most rows mh_gemv_packed*_wide take: the slot engine's row limit
 SAMPLE_CAP = 1024      # most top-k candidates mh_sample_rows sorts on the device (include/myriad_hip.h)
 
 

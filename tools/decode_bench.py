@@ -23,7 +23,14 @@ shared generator; device = the switch on, every pick drawn inside the step from 
 repetition_penalty (the host mode has none: the switch is off there).  A sampled answer leaves the countdown chain, so requests
 run to --new tokens or their stop id, whichever the draws meet first; the generated tokens are counted.  The chain's logits are
 peaked (p_max >= 0.9 at temperature 1, so the host mode never draws there); --temperature T flattens them until rows fall below
-top_p and the host mode draws them."""
+top_p and the host mode draws them.
+--slots 8,16,32,64 (a comma list) times the greedy slots run at each slot count in ONE process, interleaved per repeat, each with
+the one-request refill and with every --prefill-batch / --refill-min pair; batch 1 runs once, as the answers every column must
+reproduce.  Give it --requests 256 or more: one wave of 64 slots would otherwise be the whole run.
+--step-rows 16,32,48,64 times the slot engine's captured token step alone, every row live at --step-keys cached keys, for each
+kind of --weights, interleaved per repeat (--repeats rounds of --step-replays replays each): up to 16 rows the 16-row kernel,
+above it ops.gemv_packed_wide.  --step-gemm 32,64 adds greedy_generate's step at those row counts: the row-major bf16 GEMMs that
+every decode loop but the slot engine runs above 16 rows."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -42,12 +49,20 @@ ap.add_argument("--modes", default="", help="comma list of greedy / host / devic
 ap.add_argument("--repeats", type=int, default=1)
 ap.add_argument("--beams", type=int, default=4, help="num_beams of the beam mode")
 ap.add_argument("--weights", default="", help="comma list of bf16 / fp8 / fp4: the token step's weight copies, timed interleaved")
-ap.add_argument("--slots", type=int, default=0, help="N > 0: the run-level comparison slots / batch N / batch 1 (see above)")
+ap.add_argument("--slots", default="0", help="N > 0: the run-level comparison slots / batch N / batch 1; a comma list: the slots "
+                "run at each count, interleaved (see above)")
+ap.add_argument("--step-rows", default="", help="comma list of row counts: time the slot engine's token step alone at each")
+ap.add_argument("--step-gemm", default="", help="with --step-rows: row counts at which greedy_generate's (row-major GEMM) step is timed too")
+ap.add_argument("--step-keys", type=int, default=128, help="with --step-rows: cached keys per row when the timing starts")
+ap.add_argument("--step-replays", type=int, default=40, help="with --step-rows: graph replays per timed round")
 ap.add_argument("--requests", type=int, default=64, help="requests of the --slots run")
 ap.add_argument("--prefill-batch", default="1", help="comma list: prefill_batch of the --slots run, timed interleaved")
 ap.add_argument("--refill-min", default="1", help="comma list: refill_min of the --slots run, timed interleaved")
 ap.add_argument("--merge", default="", help="comma list of 0 / 1: bordered / merged LoRA qkv in the token step, timed interleaved")
 a = ap.parse_args()
+# --slots is a string so that it can be a list; from here on a.slots is the single count (0: none or a list) and slot_counts the list
+slot_counts = [int(x) for x in a.slots.split(",") if x]
+a.slots = slot_counts[0] if len(slot_counts) == 1 else 0
 modes = [m for m in a.modes.split(",") if m] or ["sample" if a.sample else "greedy"]
 if "beam" in modes and "greedy" in modes:
     modes.append("greedy_x%d" % a.beams)             # greedy at batch * beams rows: the beam step's row count
@@ -70,8 +85,86 @@ def make_samples(n):
                 after_ids=torch.randint(3, 32000, (1, 28), generator=g).expand(n, -1).contiguous())
 
 
-if a.slots:
-    L, N, new = model.llama, a.slots, a.new
+if a.step_rows:
+    # The timed step is assembled here from the engine's own pieces (SlotDecoder._workspace for the buffers and weights,
+    # LlamaHIP._step_logits, the plain arg-max + mh_decode_advance_rows tail of SlotDecoder.run's greedy token_step): the same
+    # launches as the step run() captures, but a copy of its three lines -- if run()'s greedy tail changes, change it here too.
+    from myriad_amd import ops
+    from myriad_amd.llama import _decode_buffers
+    L = model.llama
+    rows_list = [int(x) for x in a.step_rows.split(",") if x]
+    gemm_rows = [int(x) for x in a.step_gemm.split(",") if x]
+    rounds, n_rep = max(1, a.repeats) + 1, a.step_replays           # round 0 is the warm-up of the graph itself
+    T_cap = 64 * ((a.step_keys + rounds * n_rep + 8 + 63) // 64)
+    gi = torch.Generator().manual_seed(3)
+
+    def capture(ws, step):
+        R = ws["ids"].shape[0]
+        ws["ids"].copy_(torch.randint(3, 32000, (R,), generator=gi))
+        ws["pos"].fill_(a.step_keys)
+        ws["kvlen"].fill_(a.step_keys + 1)
+        for c in ws["caches"]:
+            c[:, :a.step_keys].normal_(0.0, 0.5)
+        step()                                                       # eager once: kernels loaded, attributes set
+        torch.cuda.synchronize()
+        g_ = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g_):
+            step()
+        return g_
+
+    configs = []                                                     # (label, kind, rows, graph)
+    keep = []
+    for kind in (kinds if kinds != [None] else ["bf16"]):
+        L.decode_fp8, L.decode_fp4 = kind == "fp8", kind == "fp4"
+        for R in rows_list:
+            dec = L.slot_decoder(R, T_cap)
+            ws = dec._workspace(1.0)
+            ws["live"].fill_(1)
+
+            def step(ws=ws):
+                L._step_logits(ws)
+                ops.argmax_pmax_rows(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ban_id=-1, inv_temp=1.0)
+                ops.decode_advance_rows(ws["nxt"], ws["mar"], ws["pmx"], ws["rec"][:3], ws["ids"], ws["step"], ws["pos"], ws["kvlen"],
+                                        ws["live"])
+            configs.append((f"slots step, weights {kind}", kind, R, capture(ws, step)))
+            keep.append((dec, ws))
+    L.decode_fp8 = L.decode_fp4 = False
+    for R in gemm_rows:                                              # greedy_generate's step: row-major GEMMs above 16 rows
+        L._prepare_decode_weights(R)
+        ws = _decode_buffers(L, R, T_cap)
+
+        def step(ws=ws):
+            L._step_logits(ws)
+            ops.argmax_pmax_rows(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ban_id=-1, inv_temp=1.0)
+            ops.decode_advance(ws["nxt"], ws["mar"], ws["pmx"], ws["rec"][:3], ws["ids"], ws["step"], ws["pos"], ws["kvlen"])
+        configs.append(("greedy step, row-major bf16 GEMM", "bf16", R, capture(ws, step)))
+        keep.append((None, ws))
+    res = {i: [] for i in range(len(configs))}
+    for rnd in range(rounds):
+        for i, (_, _, _, g_) in enumerate(configs):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(n_rep):
+                g_.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            if rnd:
+                res[i].append(e0.elapsed_time(e1) / n_rep)
+    base = {}
+    print(f"token step, every row live, {a.step_keys}+ keys, {len(L.layers)} layers; median of {rounds - 1} rounds of {n_rep} replays")
+    for i, (label, kind, R, _) in enumerate(configs):
+        ts = sorted(res[i])
+        t = ts[len(ts) // 2]
+        if label.startswith("slots") and R == 16:
+            base[kind] = t
+        ratio = ""
+        if label.startswith("slots") and kind in base and R > 16:
+            ratio = f"; {t / base[kind]:.3f}x the 16-row step, R/16 = {R / 16:.2f} -> ratio to R/16: {t / base[kind] / (R / 16):.3f}"
+        print(f"{label} rows {R}: {t:.3f} ms/step (min {ts[0]:.3f}, max {ts[-1]:.3f}), {R / t * 1e3:.0f} row-tok/s{ratio}")
+    sys.exit(0)
+
+if a.slots or len(slot_counts) > 1:
+    L, N, new = model.llama, a.slots or slot_counts[0], a.new
     gq = torch.Generator().manual_seed(11)
     lens = [int(x) for x in torch.randint(24, 161, (a.requests,), generator=gq)]
     due = [int(x) for x in torch.randint(8, new + 1, (a.requests,), generator=gq)]
@@ -127,6 +220,44 @@ if a.slots:
                   f"{n / t:.0f} tokens/s ({n} tokens), {len(reqs) / t:.1f} samples/s (min {len(reqs) / ts[-1]:.1f}, max "
                   f"{len(reqs) / ts[0]:.1f}); host-drawn rows {st['host_sampled_rows']}, device-drawn {st['device_sampled_rows']}, "
                   f"{st['steps']} steps, graph replays {st['graph_replays']}, occupancy {st['occupancy']:.3f}")
+        sys.exit(0)
+
+    if len(slot_counts) > 1:
+        assert not a.sample, "a list of slot counts times the greedy run"
+        cap = 64 * ((160 + new + 63) // 64)
+        decs = {n: L.slot_decoder(n, cap) for n in slot_counts}
+        pairs = [(1, 1)] + [(pb, rm) for pb in (int(x) for x in a.prefill_batch.split(","))
+                            for rm in (int(x) for x in a.refill_min.split(",")) if (pb, rm) != (1, 1)]
+        cols = [(n, pb, rm) for n in slot_counts for pb, rm in pairs]
+        cstats = {}
+
+        def run_col(c):
+            n, pb, rm = c
+            out = {i: ids for i, ids, _ in decs[n].run(reqs, prefill_batch=pb, refill_min=rm, **kw)}
+            cstats[c] = dict(decs[n].last_stats)
+            return [len(out[i]) for i in range(len(reqs))]
+
+        want = [L.greedy_generate(x[None], **kw).shape[1] for x in reqs]      # batch 1: the answers every column must reproduce
+        for c in cols:
+            run_col(c)                                                 # warm-up: kernels, graphs, GEMM plans
+        res = {c: [] for c in cols}
+        for _ in range(max(1, a.repeats)):
+            for c in cols:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                got = run_col(c)
+                torch.cuda.synchronize()
+                res[c].append((time.perf_counter() - t0, got))
+        print(f"{len(reqs)} requests, prompts {min(lens)}..{max(lens)} rows, {sum(want)} tokens due ({min(want)}..{max(want)} per request), "
+              f"weights {L._packed['kind'] if L._packed else 'bf16'}")
+        for c in cols:
+            ts = sorted(t for t, _ in res[c])
+            t, got, st = ts[len(ts) // 2], res[c][-1][1], cstats[c]
+            whole = sum(g == w for g, w in zip(got, want))
+            print(f"slots {c[0]} prefill_batch {c[1]} refill_min {c[2]}: {t * 1e3:.1f} ms (median of {len(ts)}, min {ts[0] * 1e3:.1f}, max "
+                  f"{ts[-1] * 1e3:.1f}) -> {len(reqs) / t:.1f} samples/s (min {len(reqs) / ts[-1]:.1f}, max {len(reqs) / ts[0]:.1f}), "
+                  f"{sum(want) / t:.0f} due tokens/s; {whole}/{len(reqs)} answers complete; occupancy {st['occupancy']:.3f}, "
+                  f"{st['steps']} steps, {st['prefills']} prefills in {st['prefill_passes']} passes")
         sys.exit(0)
 
     slot_stats = {}
