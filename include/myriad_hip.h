@@ -501,6 +501,18 @@ int mh_attn_decode_rope_rows(void* qkv, long ld_qkv, void* cache, long cache_bst
 int mh_attn_prefill_ragged(const void* qkv, long ld_qkv, const int* pos, const int* seg, const int* seg_host, int R, void* cache,
                            long cache_bstride, long ld_cache, int n_slots, int T_cap, const float* cos_tab, const float* sin_tab,
                            int max_pos, void* out, long ldo, int M, int H, int D, float scale, mh_stream_t s);
+/* The same pass on top of a cached prefix (a chat turn's new rows after the reused part of its context): seg / seg_host are
+ * int[R][4] of (row0, len, slot, past).  Segment i holds the len NEW rows of a request whose keys 0 .. past - 1 are rows of
+ * cache[slot] already (rotated k | v, as every writer of these caches leaves them); its rotated k | v go to cache rows past ..
+ * past + len - 1 and its out rows and those cache rows have the bits of mh_rope_inplace + mh_copy3d_bf16 into
+ * cache[slot][past ..] + mh_attn_fwd(causal, Sq = len, Sk = past + len, q_off = past) on that segment at B = 1 (for len = 1 and
+ * past < 8192 that is mh_attn_fwd's decode kernel, whose arithmetic the launch repeats for such a segment).  pos[] stays the
+ * caller's.  No cache row >= past is read, rows < past and >= past + len are not written.  With past = 0 everywhere the results
+ * are mh_attn_prefill_ragged's bits.  MH_ERR_ARG as there, and unless 0 <= past and past + len <= T_cap. */
+int mh_attn_prefill_ragged_past(const void* qkv, long ld_qkv, const int* pos, const int* seg, const int* seg_host, int R,
+                                void* cache, long cache_bstride, long ld_cache, int n_slots, int T_cap, const float* cos_tab,
+                                const float* sin_tab, int max_pos, void* out, long ldo, int M, int H, int D, float scale,
+                                mh_stream_t s);
 /* The same token step with the keys split into chunks (attn_decode_split.hip): grid (ceil(T_cap / chunk), B*H), each workgroup
  * scores one chunk and writes fp32 (m, l, o[D]) into `partials`, a second launch merges the chunks in order and writes bf16 out
  * (bits fixed from run to run).  q is rotated in registers (qkv is not written); the cache row at pos_dev[0] gets the bits

@@ -21,6 +21,11 @@ with what the cache holds (positions named by token ids and (image, row) keys), 
 captured graph.  `Chat.last_stats` reports what a turn reused.  The session uses the split-KV decode attention kernel where it is
 measured faster (llama.split_kv_rule).  `num_beams > 1` runs the model's beam search (LlamaHIP.beam_generate) on the full context
 without reuse (deterministic: `do_sample` does not apply to it), and leaves the session's cache as it was.
+
+Several conversations at once.  `ChatPool` serves up to `slots` conversations on the decode slots (llama.SlotDecoder.run_turns):
+one captured token step for all of them, each conversation's KV cache kept in its own slot across turns, a turn's new rows
+prefilled on top of the reused prefix -- several conversations per pass over the weights.  `answer_many` does per conversation
+what `Chat.answer` does; both classes share the conversation side (`_ChatBase`).
 """
 from __future__ import annotations
 
@@ -37,8 +42,8 @@ from . import ops
 from .llama import DecodeSession
 from .myriad import StoppingCriteriaSub
 
-__all__ = ["SeparatorStyle", "Conversation", "CONV_VISION", "StoppingCriteriaSub", "Chat", "truncation_begin", "postprocess_tokens",
-           "postprocess_text"]
+__all__ = ["SeparatorStyle", "Conversation", "CONV_VISION", "StoppingCriteriaSub", "Chat", "ChatPool", "truncation_begin",
+           "postprocess_tokens", "postprocess_text"]
 
 STOP_WORDS = ((835,), (2277, 29937))          # '###' can be encoded in two different ways (conversation.py:130-131)
 
@@ -143,14 +148,15 @@ def postprocess_text(text: str) -> str:
     return text.split("###")[0].split("Assistant:")[-1].strip()
 
 
-class Chat:
+class _ChatBase:
+    """The conversation side shared by Chat and ChatPool: images in, the context's embeddings and position keys out."""
+
     def __init__(self, model, vis_processor=None, device="cuda:0"):
         self.device = torch.device(device)
         self.model = model
         self.vis_processor = vis_processor
         self.stopping_criteria = [StoppingCriteriaSub(stops=[torch.tensor(list(s)) for s in STOP_WORDS])]
         self._frontend = None
-        self.session: Optional[DecodeSession] = None
         self.last_stats = {}
         self.last_token_ids = None
         self._digests = {}
@@ -243,6 +249,30 @@ class Chat:
                                     ops.h2d(torch.tensor(rows, dtype=torch.int32), self.device))
         return emb, keys
 
+    def _turn_context(self, conv, img_list, max_new_tokens, max_length):
+        """The start of an assistant turn (conversation.py:144-156): the assistant role appended, the context's embeddings and
+        keys cut to the reference's window.  Returns (embs [1, S, D], keys [S], begin)."""
+        conv.append_message(conv.roles[1], None)
+        embs, keys = self.get_context_emb(conv, img_list)
+        begin = truncation_begin(embs.shape[1], max_new_tokens, max_length)
+        if begin > 0:
+            warnings.warn("The number of tokens in current conversation exceeds the max length. "
+                          "The model will not see the contexts outside the range.", RuntimeWarning, stacklevel=3)
+        return embs[:, begin:].contiguous(), keys[begin:], begin
+
+    def _finish_turn(self, conv, ids):
+        """The end of one (conversation.py:170-177): post-processing, the answer written into the conversation."""
+        out = postprocess_tokens(ids)
+        text = postprocess_text(self.model.llama_tokenizer.decode(out, add_special_tokens=False))
+        conv.messages[-1][1] = text
+        return text, np.asarray(out, dtype=np.int64)
+
+
+class Chat(_ChatBase):
+    def __init__(self, model, vis_processor=None, device="cuda:0"):
+        super().__init__(model, vis_processor, device)
+        self.session: Optional[DecodeSession] = None
+
     # ------------------------------------------------------------------ answer
     @torch.no_grad()
     def answer(self, conv, img_list, max_new_tokens=300, num_beams=1, min_length=1, top_p=0.9, repetition_penalty=1.0,
@@ -258,13 +288,7 @@ class Chat:
         if rep != 1.0 and not llama.device_sampling:
             raise NotImplementedError(f"answer(repetition_penalty={rep}) needs the device sampling switch "
                                       "(MYRIAD_DEVICE_SAMPLING=1 or model.llama.device_sampling = True)")
-        conv.append_message(conv.roles[1], None)
-        embs, keys = self.get_context_emb(conv, img_list)
-        begin = truncation_begin(embs.shape[1], max_new_tokens, max_length)
-        if begin > 0:
-            warnings.warn("The number of tokens in current conversation exceeds the max length. "
-                          "The model will not see the contexts outside the range.", RuntimeWarning, stacklevel=2)
-        embs, keys = embs[:, begin:].contiguous(), keys[begin:]
+        embs, keys, begin = self._turn_context(conv, img_list, max_new_tokens, max_length)
         S = embs.shape[1]
         if int(num_beams) > 1:
             if rep != 1.0:
@@ -285,7 +309,61 @@ class Chat:
                                         repetition_penalty=rep)
             self.last_stats = dict(self.session.last_stats)
         self.last_token_ids = ids                                    # [B, L] as decoded, before the post-processing
-        out = postprocess_tokens(ids[0].tolist())
-        text = postprocess_text(m.llama_tokenizer.decode(out, add_special_tokens=False))
-        conv.messages[-1][1] = text
-        return text, np.asarray(out, dtype=np.int64)
+        return self._finish_turn(conv, ids[0].tolist())
+
+
+class ChatPool(_ChatBase):
+    """Several conversations at once on the decode slots: `slots` conversations share ONE captured token step (each weight is
+    streamed once per step for all of them) and each keeps its KV cache in its own slot across turns, as a `Chat` keeps its
+    session's.  The session id is the `Conversation` object; the pool holds it until `close(conv)` frees its slot, and a
+    conversation beyond `slots` open ones is a ValueError.  `upload_img` / `ask` are Chat's.  No beam search (decode slots have
+    none), and the step's attention is the single-workgroup rows kernel at every length: a conversation past ~1,024 keys decodes
+    slower here than in a solo Chat, which switches to split-KV."""
+
+    def __init__(self, model, slots=8, capacity=2000 + 300 + 2, device=None, vis_processor=None):
+        super().__init__(model, vis_processor, model.llama.dev if device is None else device)
+        self.decoder = model.llama.slot_decoder(int(slots), int(capacity))
+        self.last_stats = []
+
+    def close(self, conv) -> None:
+        self.decoder.close(conv)
+
+    @torch.no_grad()
+    def answer_many(self, items, max_new_tokens=300, num_beams=1, min_length=1, top_p=0.9, repetition_penalty=1.0, temperature=1.0,
+                    max_length=2000, do_sample=True, generator=None, seeds=None, prefill_batch=8):
+        """One assistant turn for each (conv, img_list) of `items`, Chat.answer's per conversation (the assistant role, the
+        context and its truncation window -- a moved window resets that session, reason "window" --, the post-processing, the
+        answer written into conv.messages) through SlotDecoder.run_turns.  Returns [(text, ids)] in the items' order;
+        `last_stats` is a list of per-conversation dicts with Chat.last_stats' keys where they apply.  `seeds`: with device
+        sampling, the i-th item's random stream (else drawn from `generator`), so an answer does not depend on its neighbours."""
+        m = self.model
+        if int(num_beams) > 1:
+            raise NotImplementedError(f"answer_many(num_beams={num_beams}): decode slots have no beam search; use Chat.answer")
+        m.finish_update()
+        llama = m.llama
+        llama.decode_lora_version = m.store.version
+        rep = 1.0 if repetition_penalty is None else float(repetition_penalty)
+        if rep != 1.0 and not llama.device_sampling:
+            raise NotImplementedError(f"answer_many(repetition_penalty={rep}) needs the device sampling switch "
+                                      "(MYRIAD_DEVICE_SAMPLING=1 or model.llama.device_sampling = True)")
+        items = list(items)
+        if len({id(c) for c, _ in items}) != len(items):             # refused before any conversation is touched
+            raise ValueError("answer_many: at most one turn per conversation in one call")
+        new = [c for c, _ in items if c not in self.decoder.sessions]
+        if len(self.decoder.sessions) + len(new) > self.decoder.slots:
+            raise ValueError(f"{len(self.decoder.sessions)} open conversations + {len(new)} new ones do not fit "
+                             f"{self.decoder.slots} slots: close() some")
+        turns = []
+        for conv, img_list in items:
+            embs, keys, begin = self._turn_context(conv, img_list, max_new_tokens, max_length)
+            turns.append((conv, embs[0], keys, "window" if begin > 0 else None))
+        kw = dict(seeds=seeds) if seeds is not None else {}
+        got = list(self.decoder.run_turns(turns, weights_version=m.store.version, max_new_tokens=max_new_tokens,
+                                          stop_ids=STOP_WORDS, eos_id=2, min_length=min_length, do_sample=bool(do_sample),
+                                          top_p=float(top_p), temperature=float(temperature), generator=generator, top_k=50,
+                                          repetition_penalty=rep, prefill_batch=int(prefill_batch), ordered=True, **kw))
+        st = self.decoder.last_stats
+        shared = {k: st[k] for k in ("steps", "graph_captures", "graph_replays")}
+        self.last_stats = [dict(t, split_kv=False, **shared) for t in st["turns"]]
+        self.last_token_ids = [ids for _, ids, _ in got]
+        return [self._finish_turn(conv, ids.tolist()) for (conv, _), (_, ids, _) in zip(items, got)]

@@ -438,6 +438,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnParams p) {
 // row pos_dev[b] (< T_cap: the host's to keep) instead of the shared pos_dev[0], and a row with live[b] == 0 touches
 // neither qkv nor the cache and writes a zero output row.  live[b] is uniform over the workgroup, so the idle exit is a
 // scalar branch taken by all 16 waves, ahead of the first barrier.  ROWS = false compiles to the code it was before.
+// attn_ragged.hip (one_row_attention) repeats phases 1 to 3 expression for expression for a one-row prefill segment, and
+// tests/test_ragged_past_gpu.py holds the two to the same bits: change them together.
 #define DNW 16
 template <bool ROWS>
 __global__ __launch_bounds__(DNW * 64) void attn_decode_kernel(AttnParams p) {

@@ -12,6 +12,16 @@
 // its causal loop) also stores that tile's rotated k and v rows to cache[slot]; every key tile below len has exactly one such
 // workgroup, so each cache row is written once and no workgroup reads the cache.  A workgroup whose query tile lies past its
 // segment's len leaves before the first barrier on a workgroup-uniform branch.
+//
+// mh_attn_prefill_ragged_past (the PAST = true form of the kernel) is the same pass on top of a cached prefix: a segment is
+// (row0, len, slot, past), its len rows are the NEW rows of a request whose keys 0 .. past-1 lie in cache[slot] already (rotated
+// k | v, as every writer of these caches leaves them), and the bits are those of the prefill branch of _decode_block with that
+// `past` (mh_attn_fwd(causal) with Sq = len over Sk = past + len keys, q_off = past).  The key loop runs over ABSOLUTE 64-key
+// tiles from key 0: a staged row below past is copied from the cache, a row at or above it is qkv row key - past, rotated while
+// loading; with past % 64 != 0 one tile mixes both.  No workgroup reads a cache row >= past, so workgroups need no order and
+// nothing stale in the slot is seen.  New cache row past + c is written by the workgroup whose query tile owns chunk row c (that
+// key always lies in its causal range), exactly once; rows below past and at or above past + len are never written.
+// A segment of one row takes one_row_attention below, as mh_attn_fwd takes the decode kernel for Sq == 1.
 #include "attn_tile.h"
 
 #include <algorithm>
@@ -20,7 +30,7 @@
 struct RaggedParams {
   const bf16_t* qkv;    // [M, ld_qkv] = [q | k | v], pre-rotary
   const int* pos;       // [M] rotary position of each packed row
-  const int* seg;       // [R, 3] (row0, len, slot)
+  const int* seg;       // [R, 3] (row0, len, slot); the PAST form [R, 4] (row0, len, slot, past)
   bf16_t* cache;        // [n_slots][T_cap][ld_cache] rows [k | v]
   const float* cs;      // [max_pos, D / 2]
   const float* sn;
@@ -28,6 +38,7 @@ struct RaggedParams {
   long ld_qkv, cache_bs, ld_cache, ldo;
   int M, H, D, n_slots, T_cap, max_pos;
   float scale;
+  int lds_bytes;        // PAST form: the launch's dynamic LDS, which a one-row segment's scores must fit
 };
 
 // One rotate-half pair in the form rope_kernel compiles to (x1 c - x2 s and x2 c + x1 s, each one product rounded and one FMA),
@@ -59,24 +70,179 @@ __device__ __forceinline__ short8_t rope8(const bf16_t* head, int c, int half, c
   return out;
 }
 
-template <int DP>
+// A segment of ONE new row on top of `past` cached keys.  mh_attn_fwd sends Sq == 1 (Sk <= 8192) to attn_decode_kernel
+// (attention.hip), not to the tile kernel, so the bits the prefill branch of _decode_block gives such a segment are that kernel's:
+// fp32 throughout, 16 lanes per key for the scores, every wave its own softmax statistics, the keys dealt round-robin to 16 waves
+// for P.V (eight at a time, then a remainder of seven) and the 16 partial outputs summed in wave order.  This is that arithmetic,
+// expression for expression, with each of this workgroup's 4 waves taking 4 of the 16 in turn (ONE_ROW_WAVES is attention.hip's
+// DNW); the scores' LDS is reused for the partial outputs.  The new row's rotated k and its v are written to cache row `past` and
+// kept in LDS: key `past` is read from there, so no cache row >= past is read here either.
+// KEEP IN STEP with attn_decode_kernel (attention.hip): a change to its phases, to DNW, to the 8 + 7 unroll of its P.V loop or to
+// mh_attn_fwd's Sq == 1 rule (Sk <= 8192) must be made here too; tests/test_ragged_past_gpu.py (the one-row segments on long
+// prefixes) compares the two bit for bit at sizes that turn every loop.
+#define ONE_ROW_WAVES 16
+#define ONE_ROW_MAX_KEYS 8192
+__host__ __device__ __forceinline__ int one_row_score_floats(int keys) {
+  const int n = (keys + 63) & ~63;
+  return n > ONE_ROW_WAVES * 128 ? n : ONE_ROW_WAVES * 128;
+}
+__device__ __forceinline__ void one_row_attention(const RaggedParams& p, char* smem, const bf16_t* xb, bf16_t* cb, int row, int past,
+                                                  int h) {
+  const int tid = threadIdx.x, lane = tid & 63, rw = tid >> 6;
+  const int D = p.D, half = D >> 1, W = p.H * D, len = past + 1;
+  float* sc = reinterpret_cast<float*>(smem);
+  bf16_t* krow = reinterpret_cast<bf16_t*>(smem + (size_t)one_row_score_floats(len) * 4);
+  bf16_t* vrow = krow + 128;
+  int ps = p.pos[row];
+  ps = ps < 0 ? 0 : (ps < p.max_pos ? ps : p.max_pos - 1);
+  const float* cs_row = p.cs + (size_t)ps * half;
+  const float* sn_row = p.sn + (size_t)ps * half;
+  if (tid < (D >> 3)) {
+    const short8_t v = rope8(xb + W, tid * 8, half, cs_row, sn_row);
+    *reinterpret_cast<short8_t*>(krow + tid * 8) = v;
+    *reinterpret_cast<short8_t*>(cb + (long)past * p.ld_cache + tid * 8) = v;
+  } else if (tid >= 64 && tid - 64 < (D >> 3)) {
+    const int c = (tid - 64) * 8;
+    const short8_t v = *reinterpret_cast<const short8_t*>(xb + 2 * W + c);
+    *reinterpret_cast<short8_t*>(vrow + c) = v;
+    *reinterpret_cast<short8_t*>(cb + (long)past * p.ld_cache + W + c) = v;
+  }
+  __syncthreads();
+  const bf16_t* kp = cb;
+  const bf16_t* vp = cb + W;
+  // phase 1: scores
+  const int sub = lane & 15, kq = lane >> 4;
+  float qf[8];
+  const bool dim_ok = sub * 8 < D;
+  {
+    short8_t qv = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (dim_ok) qv = rope8(xb, sub * 8, half, cs_row, sn_row);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) qf[e] = bf2f((bf16_t)qv[e]) * p.scale;
+  }
+  for (int i = 0; i < 4; ++i) {
+    const int wave = rw * 4 + i;
+    for (int j0 = 0; j0 < len; j0 += 2 * ONE_ROW_WAVES * 4) {
+      short8_t kv[2];
+      int jj[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        jj[u] = j0 + u * ONE_ROW_WAVES * 4 + wave * 4 + kq;
+        kv[u] = (short8_t){0, 0, 0, 0, 0, 0, 0, 0};
+        if (jj[u] < len && dim_ok)
+          kv[u] = jj[u] < past ? *reinterpret_cast<const short8_t*>(kp + (size_t)jj[u] * p.ld_cache + sub * 8)
+                               : *reinterpret_cast<const short8_t*>(krow + sub * 8);
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        float s = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s += qf[e] * bf2f((bf16_t)kv[u][e]);
+        s += __shfl_xor(s, 1, 64);
+        s += __shfl_xor(s, 2, 64);
+        s += __shfl_xor(s, 4, 64);
+        s += __shfl_xor(s, 8, 64);
+        if (sub == 0 && jj[u] < len) sc[jj[u]] = s;
+      }
+    }
+  }
+  __syncthreads();
+  // phase 2: softmax statistics (the same in every wave)
+  float mx = -INFINITY;
+  for (int j = lane; j < len; j += 64) mx = fmaxf(mx, sc[j]);
+  mx = wave_max(mx);
+  float sum = 0.f;
+  for (int j = lane; j < len; j += 64) sum += __expf(sc[j] - mx);
+  sum = wave_sum(sum);
+  // phase 3: o = sum_j p_j V[j]; lane owns dims 2*lane, 2*lane+1; wave w takes keys w, w+16, ...
+  const bool own = 2 * lane < D;
+  float po0[4], po1[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float o0 = 0.f, o1 = 0.f;
+    int j = rw * 4 + i;
+    for (; j + 7 * ONE_ROW_WAVES < len; j += 8 * ONE_ROW_WAVES) {
+      unsigned vv[8];
+      float pj[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int jr = j + ONE_ROW_WAVES * u;
+        vv[u] = own ? (jr < past ? *reinterpret_cast<const unsigned*>(vp + (size_t)jr * p.ld_cache + 2 * lane)
+                                 : *reinterpret_cast<const unsigned*>(vrow + 2 * lane)) : 0u;
+        pj[u] = __expf(sc[jr] - mx);
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        o0 += pj[u] * bf2f((bf16_t)(vv[u] & 0xffffu));
+        o1 += pj[u] * bf2f((bf16_t)(vv[u] >> 16));
+      }
+    }
+    {                                              // remainder: up to 7 keys
+      unsigned vv[7];
+      float pj[7];
+#pragma unroll
+      for (int u = 0; u < 7; ++u) {
+        const int jr = j + ONE_ROW_WAVES * u;
+        const bool ok = jr < len;
+        vv[u] = (own && ok) ? (jr < past ? *reinterpret_cast<const unsigned*>(vp + (size_t)jr * p.ld_cache + 2 * lane)
+                                         : *reinterpret_cast<const unsigned*>(vrow + 2 * lane)) : 0u;
+        pj[u] = ok ? __expf(sc[jr] - mx) : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < 7; ++u) {
+        o0 += pj[u] * bf2f((bf16_t)(vv[u] & 0xffffu));
+        o1 += pj[u] * bf2f((bf16_t)(vv[u] >> 16));
+      }
+    }
+    po0[i] = o0;
+    po1[i] = o1;
+  }
+  __syncthreads();                                 // every wave is done with the scores: their LDS takes the partial outputs
+  float* part = sc;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    part[(rw * 4 + i) * 128 + 2 * lane] = po0[i];
+    part[(rw * 4 + i) * 128 + 2 * lane + 1] = po1[i];
+  }
+  __syncthreads();
+  if (rw == 0 && own) {
+    const float inv = len > 0 ? 1.f / sum : 0.f;
+    float r0 = 0.f, r1 = 0.f;
+#pragma unroll
+    for (int w = 0; w < ONE_ROW_WAVES; ++w) {
+      r0 += part[w * 128 + 2 * lane];
+      r1 += part[w * 128 + 2 * lane + 1];
+    }
+    *reinterpret_cast<unsigned*>(p.o + (long)row * p.ldo + h * D + 2 * lane) = pack_bf2(r0 * inv, r1 * inv);
+  }
+}
+
+template <int DP, bool PAST>
 __global__ __launch_bounds__(256) void attn_prefill_ragged_kernel(RaggedParams p) {
+  constexpr int SW = PAST ? 4 : 3;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* Ks = reinterpret_cast<bf16_t*>(smem);
   bf16_t* Vt = reinterpret_cast<bf16_t*>(smem + Lds<DP>::RM_BYTES);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 15, lg = lane >> 4;
   const int sg = blockIdx.y / p.H, h = blockIdx.y % p.H;
-  const int row0 = p.seg[3 * sg], len = p.seg[3 * sg + 1], slot = p.seg[3 * sg + 2];
+  const int row0 = p.seg[SW * sg], len = p.seg[SW * sg + 1], slot = p.seg[SW * sg + 2];
+  const int past = PAST ? p.seg[SW * sg + 3] : 0;                // keys 0 .. past-1 are cache[slot]'s rows
   const int q0 = blockIdx.x * TQ;
   // the host entry validated its copy of the table; the same bounds again on the device's (all uniform over the workgroup), so
   // that no table can index outside qkv, o or the cache
   if (row0 < 0 || len <= 0 || len > p.T_cap || (long)row0 + len > p.M || slot < 0 || slot >= p.n_slots) return;
+  if (PAST && (past < 0 || past > p.T_cap - len)) return;
   if (q0 >= len) return;
   const int D = p.D, half = D >> 1, W = p.H * D;
   const int qi = q0 + wave * 16 + lr;  // this lane's query row within the segment
   const bf16_t* xb = p.qkv + (long)row0 * p.ld_qkv + h * D;   // the segment's rows, this head's q columns
   bf16_t* cb = p.cache + (long)slot * p.cache_bs + h * D;
-  const int kv_end = len < q0 + TQ ? len : q0 + TQ;           // causal: keys 0 .. the tile's last query
+  if (PAST && len == 1 && past < ONE_ROW_MAX_KEYS) {            // mh_attn_fwd's own rule for Sq == 1: the decode kernel's bits
+    if (one_row_score_floats(past + 1) * 4 + 512 > p.lds_bytes) return;   // workgroup-uniform, like every test above
+    one_row_attention(p, smem, xb, cb, row0, past, h);
+    return;
+  }
+  const int kv_end = past + (len < q0 + TQ ? len : q0 + TQ);  // causal: keys 0 .. the tile's last query (absolute keys)
 
   short8_t qf[DP / 32];
   {
@@ -99,26 +265,34 @@ __global__ __launch_bounds__(256) void attn_prefill_ragged_kernel(RaggedParams p
 
   for (int k0 = 0; k0 < kv_end; k0 += TK) {
     const bool diag = k0 == q0;
+    const auto own = [&](int c) { return PAST ? (c >= q0 && c < q0 + TQ) : diag; };   // this workgroup stores chunk row c
     __syncthreads();
-    // K tile, rotated, row-major (stage_rowmajor's image); rows >= len are zero-filled
+    // K tile, rotated, row-major (stage_rowmajor's image); rows >= past + len are zero-filled.  Key k0 + row is chunk row c =
+    // key - past; this workgroup stores the rows of its own query tile (without a prefix: the diagonal tile, k0 == q0)
     for (int idx = threadIdx.x; idx < 64 * CH; idx += 256) {
       const int row = idx / CH, ch = idx - row * CH;
+      const int c = k0 + row - past;
       short8_t v = (short8_t){0, 0, 0, 0, 0, 0, 0, 0};
-      if (k0 + row < len && ch * 8 < D) {
-        int ps = p.pos[row0 + k0 + row];
+      if (PAST && c < 0) {
+        if (ch * 8 < D) v = *reinterpret_cast<const short8_t*>(cb + (long)(k0 + row) * p.ld_cache + ch * 8);
+      } else if (c < len && ch * 8 < D) {
+        int ps = p.pos[row0 + c];
         ps = ps < 0 ? 0 : (ps < p.max_pos ? ps : p.max_pos - 1);
-        v = rope8(xb + (long)(k0 + row) * p.ld_qkv + W, ch * 8, half, p.cs + (size_t)ps * half, p.sn + (size_t)ps * half);
-        if (diag) *reinterpret_cast<short8_t*>(cb + (long)(k0 + row) * p.ld_cache + ch * 8) = v;
+        v = rope8(xb + (long)c * p.ld_qkv + W, ch * 8, half, p.cs + (size_t)ps * half, p.sn + (size_t)ps * half);
+        if (own(c)) *reinterpret_cast<short8_t*>(cb + (long)(k0 + row) * p.ld_cache + ch * 8) = v;
       }
       *reinterpret_cast<short8_t*>(Ks + row * Lds<DP>::ROW + ch * 8) = v;
     }
     // V tile, transposed (stage_transposed's image)
     for (int idx = threadIdx.x; idx < 64 * CH; idx += 256) {
       const int row = idx & 63, ch = idx >> 6;
+      const int c = k0 + row - past;
       short8_t v = (short8_t){0, 0, 0, 0, 0, 0, 0, 0};
-      if (k0 + row < len && ch * 8 < D) {
-        v = *reinterpret_cast<const short8_t*>(xb + (long)(k0 + row) * p.ld_qkv + 2 * W + ch * 8);
-        if (diag) *reinterpret_cast<short8_t*>(cb + (long)(k0 + row) * p.ld_cache + W + ch * 8) = v;
+      if (PAST && c < 0) {
+        if (ch * 8 < D) v = *reinterpret_cast<const short8_t*>(cb + (long)(k0 + row) * p.ld_cache + W + ch * 8);
+      } else if (c < len && ch * 8 < D) {
+        v = *reinterpret_cast<const short8_t*>(xb + (long)c * p.ld_qkv + 2 * W + ch * 8);
+        if (own(c)) *reinterpret_cast<short8_t*>(cb + (long)(k0 + row) * p.ld_cache + W + ch * 8) = v;
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e) Vt[(ch * 8 + e) * Lds<DP>::TROW + row] = (bf16_t)v[e];
@@ -138,7 +312,7 @@ __global__ __launch_bounds__(256) void attn_prefill_ragged_kernel(RaggedParams p
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = k0 + 16 * j + 4 * lg + r;
-        const bool ok = key < len && key <= qi && qi < len;
+        const bool ok = key < past + len && key <= past + qi && qi < len;
         const float val = s[j][r] * p.scale;
         s[j][r] = ok ? val : NEG_INF;
         tmax = fmaxf(tmax, s[j][r]);
@@ -184,18 +358,21 @@ __global__ __launch_bounds__(256) void attn_prefill_ragged_kernel(RaggedParams p
   }
 }
 
-template <int DP>
-static int launch_ragged(const RaggedParams& p, int tiles, int R, hipStream_t s) {
-  const size_t sh = Lds<DP>::RM_BYTES + Lds<DP>::TR_BYTES;   // <= 35,840 bytes: no opt-in needed
-  hipLaunchKernelGGL((attn_prefill_ragged_kernel<DP>), dim3(tiles, R * p.H), dim3(256), sh, s, p);
+template <int DP, bool PAST>
+static int launch_ragged(RaggedParams p, int tiles, int R, hipStream_t s) {
+  size_t sh = Lds<DP>::RM_BYTES + Lds<DP>::TR_BYTES;         // <= 35,840 bytes: no opt-in needed
+  if (PAST && (size_t)p.lds_bytes > sh) sh = p.lds_bytes;    // a one-row segment's scores: <= 33,280 bytes
+  p.lds_bytes = (int)sh;
+  hipLaunchKernelGGL((attn_prefill_ragged_kernel<DP, PAST>), dim3(tiles, R * p.H), dim3(256), sh, s, p);
   MH_CHECK_LAUNCH();
   return MH_OK;
 }
 
-extern "C" int mh_attn_prefill_ragged(const void* qkv, long ld_qkv, const int* pos, const int* seg, const int* seg_host, int R,
-                                      void* cache, long cache_bstride, long ld_cache, int n_slots, int T_cap, const float* cos_tab,
-                                      const float* sin_tab, int max_pos, void* out, long ldo, int M, int H, int D, float scale,
-                                      hipStream_t stream) {
+// Both entries: `sw` = 3 or 4 ints per segment (without / with `past`).
+static int prefill_ragged(int sw, const void* qkv, long ld_qkv, const int* pos, const int* seg, const int* seg_host, int R,
+                          void* cache, long cache_bstride, long ld_cache, int n_slots, int T_cap, const float* cos_tab,
+                          const float* sin_tab, int max_pos, void* out, long ldo, int M, int H, int D, float scale,
+                          hipStream_t stream) {
   if (R == 0) return MH_OK;
   if (R < 0 || M <= 0 || H <= 0 || n_slots <= 0 || T_cap <= 0 || max_pos <= 0) return MH_ERR_ARG;
   if (D <= 0 || D % 16 || D > 128) return MH_ERR_UNSUPPORTED;
@@ -206,13 +383,19 @@ extern "C" int mh_attn_prefill_ragged(const void* qkv, long ld_qkv, const int* p
     return MH_ERR_ARG;
   if ((uintptr_t)qkv % 16 || (uintptr_t)cache % 16 || (uintptr_t)cos_tab % 16 || (uintptr_t)sin_tab % 16 || (uintptr_t)out % 8)
     return MH_ERR_ARG;
-  // the segment table: 0 < len <= T_cap, 0 <= slot < n_slots, rows inside [0, M), slots distinct, segments disjoint
+  // the segment table: 0 < len <= T_cap, 0 <= slot < n_slots, rows inside [0, M), slots distinct, segments disjoint; with a
+  // prefix 0 <= past and past + len <= T_cap
   std::vector<std::pair<long, long>> rows(R);
   std::vector<int> slots(R);
-  int max_len = 0;
+  int max_len = 0, one_row_lds = 0;
   for (int i = 0; i < R; ++i) {
-    const int row0 = seg_host[3 * i], len = seg_host[3 * i + 1], slot = seg_host[3 * i + 2];
+    const int row0 = seg_host[sw * i], len = seg_host[sw * i + 1], slot = seg_host[sw * i + 2];
     if (len <= 0 || len > T_cap || slot < 0 || slot >= n_slots || row0 < 0 || (long)row0 + len > M) return MH_ERR_ARG;
+    if (sw == 4) {
+      const int past = seg_host[sw * i + 3];
+      if (past < 0 || past > T_cap - len) return MH_ERR_ARG;
+      if (len == 1 && past < ONE_ROW_MAX_KEYS) one_row_lds = std::max(one_row_lds, one_row_score_floats(past + 1) * 4 + 512);
+    }
     rows[i] = {row0, (long)row0 + len};
     slots[i] = slot;
     max_len = std::max(max_len, len);
@@ -227,8 +410,31 @@ extern "C" int mh_attn_prefill_ragged(const void* qkv, long ld_qkv, const int* p
   p.o = (bf16_t*)out;
   p.ld_qkv = ld_qkv; p.cache_bs = cache_bstride; p.ld_cache = ld_cache; p.ldo = ldo;
   p.M = M; p.H = H; p.D = D; p.n_slots = n_slots; p.T_cap = T_cap; p.max_pos = max_pos; p.scale = scale;
+  p.lds_bytes = one_row_lds;
   const int tiles = (max_len + TQ - 1) / TQ;
-  if (D <= 64) return launch_ragged<64>(p, tiles, R, stream);
-  if (D <= 96) return launch_ragged<96>(p, tiles, R, stream);
-  return launch_ragged<128>(p, tiles, R, stream);
+  if (sw == 4) {
+    if (D <= 64) return launch_ragged<64, true>(p, tiles, R, stream);
+    if (D <= 96) return launch_ragged<96, true>(p, tiles, R, stream);
+    return launch_ragged<128, true>(p, tiles, R, stream);
+  }
+  if (D <= 64) return launch_ragged<64, false>(p, tiles, R, stream);
+  if (D <= 96) return launch_ragged<96, false>(p, tiles, R, stream);
+  return launch_ragged<128, false>(p, tiles, R, stream);
+}
+
+extern "C" int mh_attn_prefill_ragged(const void* qkv, long ld_qkv, const int* pos, const int* seg, const int* seg_host, int R,
+                                      void* cache, long cache_bstride, long ld_cache, int n_slots, int T_cap, const float* cos_tab,
+                                      const float* sin_tab, int max_pos, void* out, long ldo, int M, int H, int D, float scale,
+                                      hipStream_t stream) {
+  return prefill_ragged(3, qkv, ld_qkv, pos, seg, seg_host, R, cache, cache_bstride, ld_cache, n_slots, T_cap, cos_tab, sin_tab,
+                        max_pos, out, ldo, M, H, D, scale, stream);
+}
+
+// The same pass on top of a cached prefix: segment tables [R, 4] = (row0, len, slot, past).
+extern "C" int mh_attn_prefill_ragged_past(const void* qkv, long ld_qkv, const int* pos, const int* seg, const int* seg_host,
+                                           int R, void* cache, long cache_bstride, long ld_cache, int n_slots, int T_cap,
+                                           const float* cos_tab, const float* sin_tab, int max_pos, void* out, long ldo, int M,
+                                           int H, int D, float scale, hipStream_t stream) {
+  return prefill_ragged(4, qkv, ld_qkv, pos, seg, seg_host, R, cache, cache_bstride, ld_cache, n_slots, T_cap, cos_tab, sin_tab,
+                        max_pos, out, ldo, M, H, D, scale, stream);
 }

@@ -414,7 +414,8 @@ class LlamaHIP:
         [B] on the device, the slot engine's) makes it the rows kernel instead: every row appends at its own pos[b], idle rows
         are skipped; only the fused step has that form.  `ragged` = (segment table on the device, its host copy) makes a prefill
         the packed one (_prefill_packed): B = 1, the S rows hold several requests, `caches` are the whole slot caches, and the
-        three attention launches become one mh_attn_prefill_ragged.  `wide` (the slot engine above GEMV_MAX_ROWS slots) keeps the
+        three attention launches become one mh_attn_prefill_ragged (mh_attn_prefill_ragged_past for a table with a fourth column,
+        the rows cached already).  `wide` (the slot engine above GEMV_MAX_ROWS slots) keeps the
         token step on the packed copies up to GEMV_WIDE_MAX_ROWS rows: the fused step's launch sequence with
         ops.gemv_packed_wide as the product and the two-launch forms of the norm / SiLU products, as at 3 to 16 rows.  Every
         other caller leaves it off and keeps the row-major GEMMs above GEMV_MAX_ROWS rows."""
@@ -477,7 +478,8 @@ class LlamaHIP:
                 qkv = lin(li, "wqkv_ext", x_ext)
             q3 = qkv.view(B, S, 3 * W)
             if ragged is not None:
-                o = ops.attn_prefill_ragged(qkv, pos, ragged[0], ragged[1], cache, self.cos, self.sin, H, hd, scale)
+                attn = ops.attn_prefill_ragged_past if ragged[1].shape[1] == 4 else ops.attn_prefill_ragged
+                o = attn(qkv, pos, ragged[0], ragged[1], cache, self.cos, self.sin, H, hd, scale)
             elif pos_dev is None:
                 ops.rope_(qkv, 0, 2 * H, hd, pos, self.cos, self.sin, 1.0)
                 ops.copy3d_bf16(q3[:, :, W:], cache[:, past:past + S])       # append k|v (modeling_llama.py:190-195)
@@ -520,7 +522,7 @@ class LlamaHIP:
         last = h.view(B, S, D)[:, -1].contiguous()
         return ops.gemm(ops.rmsnorm_fwd(last, self.norm, self.eps), self.lm_head, out_dtype=F32)
 
-    def _prefill_packed(self, embs, slots, caches) -> torch.Tensor:
+    def _prefill_packed(self, embs, slots, caches, pasts=None) -> torch.Tensor:
         """The prefill of several requests in ONE pass over the decoder weights (the slot engine's prefill_batch > 1): `embs` is a
         list of [S_i, D] f32 embeddings, request i goes to positions 0 .. S_i - 1 of slot slots[i] of `caches` (the slot engine's
         [slots, T, 2D] caches, whole).  The rows are packed one request after the other, `pos` = each row's index within its
@@ -528,19 +530,32 @@ class LlamaHIP:
         a buffer per row count and the GEMM planner keys on it: a run meets a handful of shapes).  The layers are the prefill
         branch of _decode_block -- norms, GEMMs, the bordered LoRA, MLP -- with its three attention launches replaced by
         mh_attn_prefill_ragged; then the R last rows are gathered for the final norm and the lm-head.  Returns [R, V] f32 logits.
-        A request's rows differ from its solo _prefill only through the GEMMs' row-count-dependent plans."""
+        A request's rows differ from its solo _prefill only through the GEMMs' row-count-dependent plans.
+
+        `pasts` (SlotDecoder.run_turns): request i has its first pasts[i] rows in slot slots[i] already, so only embs[i][pasts[i]:]
+        is packed, at positions pasts[i] .., and the attention launch is mh_attn_prefill_ragged_past -- the packed form of
+        _prefill(emb, cache, past).  Without it the launches are the ones above."""
+        if pasts is not None:
+            pasts = [int(p) for p in pasts]
+            if len(pasts) != len(embs) or any(not 0 <= p < int(e.shape[0]) for p, e in zip(pasts, embs)):
+                raise ValueError("pasts: one per request, 0 <= past < its rows")
+            embs = [e[p:] for e, p in zip(embs, pasts)]
         lens = [int(e.shape[0]) for e in embs]
         M, D = ops.round_up(sum(lens), 64), self.D
         x = torch.zeros((M, D), dtype=F32, device=self.dev)
         pos = torch.zeros((M,), dtype=torch.int32)
         seg, row = [], 0
-        for e, n, s in zip(embs, lens, slots):
+        for i, (e, n, s) in enumerate(zip(embs, lens, slots)):
             x[row:row + n].copy_(e)
-            pos[row:row + n] = torch.arange(n, dtype=torch.int32)
-            seg.append((row, n, int(s)))
+            if pasts is None:
+                pos[row:row + n] = torch.arange(n, dtype=torch.int32)
+                seg.append((row, n, int(s)))
+            else:
+                pos[row:row + n] = torch.arange(pasts[i], pasts[i] + n, dtype=torch.int32)
+                seg.append((row, n, int(s), pasts[i]))
             row += n
         seg_host = torch.tensor(seg, dtype=torch.int32)
-        last = torch.tensor([r0 + n - 1 for r0, n, _ in seg], dtype=torch.int32)
+        last = torch.tensor([t[0] + t[1] - 1 for t in seg], dtype=torch.int32)
         h = self._decode_block(x, 1, M, caches, 1.0 / math.sqrt(self.hd), ops.h2d(pos, self.dev),
                                ragged=(ops.h2d(seg_host, self.dev), seg_host))
         hl = ops.gather_rows_f32(h, ops.h2d(last, self.dev))
@@ -1187,6 +1202,138 @@ class RefillPlanner:
         return list(zip(free, group))
 
 
+class TurnPlanner:
+    """RefillPlanner's place in SlotDecoder.run_turns: every turn has ITS session's slot, so the passes are fixed when the call
+    starts -- the turns in list order, up to `prefill_batch` per pass and as many as keep the pass's NEW rows (rounded up to 64)
+    within `prefill_rows`; the first of a pass always goes.  `items` = [(slot, request)], `length(request)` = its new rows."""
+
+    def __init__(self, items, prefill_batch: int = 1, prefill_rows: int = 2048, length=len):
+        if prefill_batch < 1 or prefill_rows < 1:
+            raise ValueError(f"prefill_batch and prefill_rows must be >= 1, got {prefill_batch} and {prefill_rows}")
+        self.groups, self.passes, self.packed_rows = [], 0, 0
+        rows = 0
+        for item in items:
+            n = length(item[1])
+            if not self.groups or len(self.groups[-1]) >= int(prefill_batch) or ops.round_up(rows + n, 64) > int(prefill_rows):
+                self.groups.append([])
+                rows = 0
+            self.groups[-1].append(item)
+            rows += n
+        self._length = length
+
+    def next_pass(self) -> list:
+        if not self.groups:
+            return []
+        group = self.groups.pop(0)
+        self.passes += 1
+        self.packed_rows += sum(self._length(req) for _, req in group)
+        return group
+
+
+class SessionTable:
+    """Which conversation lives in which decode slot, and what its slot's cache holds: the host side of SlotDecoder.run_turns, on
+    plain Python values like SlotScheduler (no device in sight).
+
+    At most `slots` sessions are open; a session (any object: hashable ones by value, others by identity, held until `close`)
+    is pinned to one slot from its first turn until `close(session)` frees it.  Per session the table keeps one key per cached
+    position, DecodeSession's convention: `begin(session, keys)` answers (slot, past, reason) with past =
+    min(common_prefix(keys, cached), len(keys) - 1) -- at least one row is always prefilled, it gives the first logits -- and
+    `end(session, keys, ids)` records the context's keys plus ("t", id) for ids[:-1]: the last pick of a turn has no KV, and a slot
+    row goes idle the moment its turn ends, so no id the host does not know is ever fed (DecodeSession's ("x",) case does not
+    arise).  Between `begin` and `end` the session's keys are dropped: a turn that fails or is abandoned midway leaves a cache
+    nobody trusts.
+
+    `sync(stamp)` is called with what the cached rows depend on -- (the caller's weights_version, _decode_weights_id, the merge
+    id of a merged qkv copy) -- before the turns of a call: whenever it moves, every session's keys are dropped, with
+    DecodeSession's reasons ("weights changed" / "decode weights changed").  `clear()` drops them all ("empty cache"): the
+    caches were overwritten.  `reason` is None when the cached rows were usable, whatever `past` came out."""
+
+    def __init__(self, slots: int):
+        if slots < 1:
+            raise ValueError(f"slots must be >= 1, got {slots}")
+        self.slots = int(slots)
+        self.stamp = None
+        self._open = {}                                              # key -> [session, slot, keys, why the keys are empty]
+
+    @staticmethod
+    def _key(session):
+        try:
+            hash(session)
+            return ("v", session)
+        except TypeError:
+            return ("id", id(session))                               # the entry holds the object, so the id stays its own
+
+    def __len__(self) -> int:
+        return len(self._open)
+
+    def __contains__(self, session) -> bool:
+        return self._key(session) in self._open
+
+    def slot_of(self, session) -> int:
+        return self._open[self._key(session)][1]
+
+    def keys_of(self, session) -> list:
+        return list(self._open[self._key(session)][2])
+
+    def open(self, session) -> int:
+        """The session's slot; a new session takes the lowest free one."""
+        k = self._key(session)
+        if k not in self._open:
+            used = {e[1] for e in self._open.values()}
+            if len(used) >= self.slots:
+                raise ValueError(f"all {self.slots} slots hold an open session: close() one before opening another")
+            self._open[k] = [session, min(set(range(self.slots)) - used), [], "empty cache"]
+        return self._open[k][1]
+
+    def close(self, session) -> None:
+        self._open.pop(self._key(session), None)
+
+    def drop(self, session, reason: str = "empty cache") -> None:
+        e = self._open.get(self._key(session))
+        if e is not None:
+            e[2], e[3] = [], reason
+
+    def clear(self, reason: str = "empty cache") -> None:
+        for e in self._open.values():
+            e[2], e[3] = [], reason
+
+    def sync(self, stamp) -> None:
+        if self.stamp is not None and stamp != self.stamp:
+            self.clear("weights changed" if stamp[0] != self.stamp[0] else "decode weights changed")
+        self.stamp = stamp
+
+    def begin(self, session, keys, reset_reason: Optional[str] = None):
+        slot = self.open(session)
+        e = self._open[self._key(session)]
+        if len(keys) < 1:
+            raise ValueError("a turn needs at least one context position")
+        reason = reset_reason if reset_reason is not None else (None if e[2] else e[3])
+        cached = [] if reason is not None else e[2]
+        past = min(common_prefix(keys, cached), len(keys) - 1)
+        e[2], e[3] = [], "empty cache"                               # until end(): the slot is being written
+        return slot, past, reason
+
+    def end(self, session, keys, ids) -> None:
+        e = self._open.get(self._key(session))
+        if e is not None:
+            e[2], e[3] = list(keys) + [("t", int(t)) for t in list(ids)[:-1]], None
+
+    def plan(self, turns, stamp):
+        """One run_turns call: `turns` = [(session, keys) or (session, keys, reset_reason)], at most one per session.  Syncs
+        the stamp and begins every turn; returns [(slot, past, reason)] in the turns' order."""
+        seen = set()
+        for t in turns:
+            k = self._key(t[0])
+            if k in seen:
+                raise ValueError("at most one turn per session in one call")
+            seen.add(k)
+        new = [k for k in seen if k not in self._open]
+        if len(self._open) + len(new) > self.slots:
+            raise ValueError(f"{len(self._open)} open sessions + {len(new)} new ones do not fit {self.slots} slots: close() some")
+        self.sync(stamp)
+        return [self.begin(t[0], t[1], t[2] if len(t) > 2 else None) for t in turns]
+
+
 def seeded_requests(requests, generator: Optional[torch.Generator] = None, seeds=None):
     """Pairs every request with the seed of its own random stream: yields (request, seed) in input order.  The seed is drawn when
     the request is taken from the input -- torch.randint(0, 2**63 - 1, (1,), generator=generator), the draw greedy_generate makes
@@ -1266,7 +1413,13 @@ class SlotDecoder:
     Packed prefill (opt-in, `run(prefill_batch=P > 1)` or `refill_min > 1`): at a refill point up to min(P, free slots) waiting
     requests are prefilled in ONE pass over the weights (LlamaHIP._prefill_packed, one mh_attn_prefill_ragged per layer writing
     each request's keys / values into its own slot), one arg-max launch and one device->host copy give all their first picks, and
-    they are admitted in input order.  RefillPlanner decides which requests go together and when."""
+    they are admitted in input order.  RefillPlanner decides which requests go together and when.
+
+    Conversations (opt-in, `run_turns`; the chat pool's, myriad_amd/chat.py ChatPool): a session keeps ITS slot and the rows the
+    slot caches from call to call (`sessions`, a SessionTable), a turn prefills only the rows past the prefix its new context
+    shares with them -- solo with `past`, or several turns per pass through _prefill_packed(..., pasts), one
+    mh_attn_prefill_ragged_past per layer -- and then decodes in the same captured step as `run`.  `run` itself starts every slot
+    at row 0, so it drops what the sessions had cached."""
 
     def __init__(self, llama: "LlamaHIP", slots: int, capacity: int):
         slots = int(slots)
@@ -1282,6 +1435,11 @@ class SlotDecoder:
         self._weights = None
         self.graph_captures = 0
         self.last_stats = {}
+        self.sessions = SessionTable(slots)                          # run_turns: which conversation each slot's cache holds
+
+    def close(self, session) -> None:
+        """Free the slot of a run_turns session."""
+        self.sessions.close(session)
 
     def _workspace(self, inv_temp: float, rows_tail=None) -> dict:
         """The step's buffers, kept while the decode weights stay the ones the captured graphs read, and over them one view (its
@@ -1334,6 +1492,40 @@ class SlotDecoder:
         counts those picks; a row the sampler hands back (kept = -1) is drawn on the host from a generator derived from the
         request's seed and t (`host_sampled_rows`).  `repetition_penalty` != 1 needs the switch, as in generate(); `min_length`
         is a per-request EOS ban on every path.  A second run with other values of the knobs replays the same graph."""
+        self.sessions.clear()                                        # the slots' caches are overwritten from row 0
+        yield from self._run(requests, None, None, max_new_tokens, stop_ids, eos_id, min_length, do_sample, top_p, temperature,
+                             top_k, generator, ordered, prefill_batch, refill_min, prefill_rows, repetition_penalty, seeds)
+
+    def run_turns(self, turns, weights_version=None, **kw):
+        """One turn each of several conversations, every one in ITS OWN slot on top of what that slot's cache holds of it
+        (`sessions`, a SessionTable).  `turns` = [(session, emb [S0, D] f32, keys [S0])] or with a fourth item `reset_reason`; at
+        most one turn per session per call (ValueError), at most `slots` open sessions (`close(session)` frees one).  `kw` are
+        `run`'s arguments but `refill_min` (prefill_batch, prefill_rows, the sampling knobs, repetition_penalty, min_length,
+        seeds: with device sampling the i-th turn of the call takes the i-th seed).  Only the rows past the prefix the slot
+        shares with the new context are prefilled: with prefill_batch = 1 a solo _prefill(emb, slot cache, past) per turn,
+        otherwise passes of up to prefill_batch turns / prefill_rows new rows through _prefill_packed(..., pasts).  Then `run`'s
+        captured step (same graphs and views) runs until every turn has stopped under its own stop rule.  Yields (session, ids,
+        margins) as `run` does, `ordered=True` in the list's order; `last_stats["turns"]` holds per turn `context_tokens`,
+        `reused_tokens`, `prefilled_tokens` and `full_reprefill_reason`.  `weights_version`: anything that changes when the
+        weights do; with it, a change of the decode weights or a `run()` on this decoder drops every session's cached rows.  The
+        step's attention is the single-workgroup rows kernel at every context length (no split-KV)."""
+        turns = [tuple(t) for t in turns]
+        if "refill_min" in kw:
+            raise ValueError("run_turns: refill_min does not apply, every turn has its own slot")
+        for t in turns:
+            if len(t) not in (3, 4) or t[1].dim() != 2 or len(t[2]) != t[1].shape[0]:
+                raise ValueError("run_turns: a turn is (session, emb [S0, D], keys [S0]) or (session, emb, keys, reset_reason)")
+        keys = [SessionTable._key(t[0]) for t in turns]
+        if len(set(keys)) != len(keys):
+            raise ValueError("run_turns: at most one turn per session in one call")
+        return self._run(None, turns, weights_version, **kw)
+
+    @torch.no_grad()
+    def _run(self, requests, turns, weights_version, max_new_tokens: int = 90, stop_ids=((835,), (2277, 29937)), eos_id: int = 2,
+             min_length: int = 1, do_sample: bool = False, top_p: float = 1.0, temperature: float = 1.0, top_k: int = 50,
+             generator: Optional[torch.Generator] = None, ordered: bool = False, prefill_batch: int = 1, refill_min: int = 1,
+             prefill_rows: int = 2048, repetition_penalty: float = 1.0, seeds=None):
+        """`run` (requests) and `run_turns` (turns + weights_version): one engine, two admission rules."""
         L = self.llama
         if do_sample and not float(temperature) > 0:
             raise ValueError(f"temperature must be > 0 when sampling, got {temperature}")
@@ -1355,8 +1547,20 @@ class SlotDecoder:
                      host_sampled_rows=0, device_sampled_rows=0, prefill_passes=0, packed_rows=0)
         packed = int(prefill_batch) != 1 or int(refill_min) != 1
         # a request travels with the seed of its own stream (None unless the device draws)
-        reqs = seeded_requests(requests, generator, seeds) if dev_sample else ((emb, None) for emb in requests)
-        plan = RefillPlanner(sched, reqs, prefill_batch, prefill_rows, refill_min, length=lambda q: int(q[0].shape[0]))
+        if turns is None:
+            reqs = seeded_requests(requests, generator, seeds) if dev_sample else ((emb, None) for emb in requests)
+            plan = RefillPlanner(sched, reqs, prefill_batch, prefill_rows, refill_min, length=lambda q: int(q[0].shape[0]))
+        else:
+            # the stamp of DecodeSession: no cached row survives a change of the weights the step multiplies by
+            P = L._packed
+            stamp = (weights_version, _decode_weights_id(L), P["merge_id"] if P["qkv_key"] == "merged" else None)
+            begun = self.sessions.plan([(t[0], list(t[2])) + t[3:] for t in turns], stamp)
+            seeds_ = [sd for _, sd in seeded_requests(turns, generator, seeds)] if dev_sample else [None] * len(turns)
+            # a turn travels as (emb, seed, past) and is admitted in list order: its index is its place in `turns`
+            plan = TurnPlanner([(slot, (t[1], sd, past)) for t, sd, (slot, past, _) in zip(turns, seeds_, begun)], prefill_batch,
+                               prefill_rows, length=lambda q: int(q[0].shape[0]) - q[2])
+            stats["turns"] = [dict(context_tokens=int(t[1].shape[0]), reused_tokens=past, prefilled_tokens=int(t[1].shape[0]) - past,
+                                   full_reprefill_reason=reason) for t, (_, past, reason) in zip(turns, begun)]
         self.last_stats = stats
         ban0 = eos_id if 0 < min_length else -1
         rec = ws["rec"] if rows_tail else ws["rec"][:3]
@@ -1386,6 +1590,9 @@ class SlotDecoder:
 
         def results():
             for index, ids, mar in sched.pop():
+                if turns is not None:                                # the slot now holds the context and every id but the last
+                    self.sessions.end(turns[index][0], turns[index][2], ids)
+                    index = turns[index][0]
                 yield index, torch.tensor(ids, dtype=torch.long), torch.tensor(mar, dtype=F32)
 
         def fits(emb: torch.Tensor) -> int:
@@ -1440,20 +1647,22 @@ class SlotDecoder:
         def refill_packed(group) -> None:
             """Prefill the group's requests in one packed pass, each into its slot; one pick launch and one device->host copy
             for all first picks; admission in input order."""
-            R, lens = len(group), [fits(emb) for _, (emb, _) in group]
-            logits0 = L._prefill_packed([emb for _, (emb, _) in group], [s for s, _ in group], ws["caches"])
+            R, lens = len(group), [fits(req[0]) for _, req in group]
+            pasts = None if turns is None else [req[2] for _, req in group]
+            logits0 = L._prefill_packed([req[0] for _, req in group], [s for s, _ in group], ws["caches"], pasts)
             stats["prefills"] += R
-            picks = first_picks(logits0, slice(0, R), [seed for _, (_, seed) in group])
-            for i, (s, (_, seed)) in enumerate(group):
+            picks = first_picks(logits0, slice(0, R), [req[1] for _, req in group])
+            for i, (s, req) in enumerate(group):
+                seed = req[1]
                 first = first_id(picks[i], logits0[i], seed)
                 if sched.admit(s, first, picks[i][1]):
                     go_live(s, first, lens[i], seed)
 
         def refill(s: int, req) -> None:
             """Prefill one request alone into slot s and take its first pick; the slot goes live if the request goes on."""
-            emb, seed = req
+            emb, seed = req[0], req[1]
             S0 = fits(emb)
-            logits0 = L._prefill(emb[None].to(L.dev), [c[s:s + 1] for c in ws["caches"]])
+            logits0 = L._prefill(emb[None].to(L.dev), [c[s:s + 1] for c in ws["caches"]], req[2] if turns is not None else 0)
             stats["prefills"] += 1
             pick = first_picks(logits0, slice(s, s + 1), [seed])[0]
             first = first_id(pick, logits0[0], seed)

@@ -440,6 +440,42 @@ def attn_decode_rope_rows(qkv2d: torch.Tensor, cache: torch.Tensor, pos: torch.T
     return out
 
 
+def _attn_prefill_ragged(sw: int, qkv2d, pos, seg, seg_host, cache, cos_tab, sin_tab, n_heads, head_dim, scale, out):
+    """attn_prefill_ragged (sw = 3 ints per segment) and attn_prefill_ragged_past (sw = 4): one set of checks."""
+    name_ = "attn_prefill_ragged" + ("_past" if sw == 4 else "")
+    _chk2d(qkv2d, BF16, name_ + ".qkv")
+    M, W = qkv2d.shape[0], n_heads * head_dim
+    if qkv2d.shape[1] < 3 * W:
+        raise _lib.MyriadHipError(f"{name_}: qkv must be [M, >=3W], got {tuple(qkv2d.shape)} for W = {W}")
+    if cache.dtype != BF16 or not cache.is_cuda or cache.dim() != 3 or cache.shape[2] != 2 * W or cache.stride(2) != 1:
+        raise _lib.MyriadHipError(f"{name_}: cache must be a cuda bf16 [n_slots, T, 2W] with unit inner stride, got "
+                                  f"{cache.dtype} {tuple(cache.shape)}")
+    if pos.dtype != torch.int32 or not pos.is_cuda or pos.shape != (M,) or not pos.is_contiguous():
+        raise _lib.MyriadHipError(f"{name_}: pos must be a contiguous cuda int32 [M]")
+    for name, t, cuda in (("seg", seg, True), ("seg_host", seg_host, False)):
+        if t.dtype != torch.int32 or t.is_cuda != cuda or t.dim() != 2 or t.shape[1] != sw or not t.is_contiguous():
+            raise _lib.MyriadHipError(f"{name_}: {name} must be a contiguous {'cuda' if cuda else 'cpu'} int32 [R, {sw}]")
+    if seg.shape != seg_host.shape:
+        raise _lib.MyriadHipError(f"{name_}: seg and seg_host must hold the same table")
+    for name, t in (("cos", cos_tab), ("sin", sin_tab)):
+        if t.dtype != F32 or not t.is_cuda or t.dim() != 2 or t.shape[1] != head_dim // 2 or not t.is_contiguous():
+            raise _lib.MyriadHipError(f"{name_}: {name} must be a contiguous cuda f32 [max_pos, D / 2]")
+    if cos_tab.shape != sin_tab.shape:
+        raise _lib.MyriadHipError(f"{name_}: cos and sin tables differ in shape")
+    if out is None:
+        out = torch.zeros((M, W), dtype=BF16, device=qkv2d.device)
+    else:
+        _chk2d(out, BF16, name_ + ".out")
+        if out.shape != (M, W):
+            raise _lib.MyriadHipError(f"{name_}: out shape {tuple(out.shape)} != {(M, W)}")
+    R = seg_host.shape[0]
+    fn = _L().mh_attn_prefill_ragged_past if sw == 4 else _L().mh_attn_prefill_ragged
+    _lib.check(fn(_p(qkv2d), qkv2d.stride(0), _p(pos), _p(seg), seg_host.data_ptr(), R, _p(cache), cache.stride(0), cache.stride(1),
+                  cache.shape[0], cache.shape[1], _p(cos_tab), _p(sin_tab), cos_tab.shape[0], _p(out), out.stride(0), M, n_heads,
+                  head_dim, float(scale), _s()), f"mh_{name_} M={M} R={R} H={n_heads} D={head_dim}")
+    return out
+
+
 def attn_prefill_ragged(qkv2d: torch.Tensor, pos: torch.Tensor, seg: torch.Tensor, seg_host: torch.Tensor, cache: torch.Tensor,
                         cos_tab: torch.Tensor, sin_tab: torch.Tensor, n_heads: int, head_dim: int, scale: float,
                         out: Optional[torch.Tensor] = None):
@@ -448,37 +484,17 @@ def attn_prefill_ragged(qkv2d: torch.Tensor, pos: torch.Tensor, seg: torch.Tenso
     seg_host the same table on the CPU (the entry sizes its grid and validates by it); cache [n_slots, T, 2W].  Per segment:
     rope_ + copy3d_bf16 into cache[slot, :len] + attn_fwd(causal=True) on its rows as a B = 1 batch, same bits.  Returns
     o [M, W] bf16; rows outside every segment are not written (zeros when `out` is allocated here)."""
-    _chk2d(qkv2d, BF16, "attn_prefill_ragged.qkv")
-    M, W = qkv2d.shape[0], n_heads * head_dim
-    if qkv2d.shape[1] < 3 * W:
-        raise _lib.MyriadHipError(f"attn_prefill_ragged: qkv must be [M, >=3W], got {tuple(qkv2d.shape)} for W = {W}")
-    if cache.dtype != BF16 or not cache.is_cuda or cache.dim() != 3 or cache.shape[2] != 2 * W or cache.stride(2) != 1:
-        raise _lib.MyriadHipError(f"attn_prefill_ragged: cache must be a cuda bf16 [n_slots, T, 2W] with unit inner stride, got "
-                                  f"{cache.dtype} {tuple(cache.shape)}")
-    if pos.dtype != torch.int32 or not pos.is_cuda or pos.shape != (M,) or not pos.is_contiguous():
-        raise _lib.MyriadHipError("attn_prefill_ragged: pos must be a contiguous cuda int32 [M]")
-    for name, t, cuda in (("seg", seg, True), ("seg_host", seg_host, False)):
-        if t.dtype != torch.int32 or t.is_cuda != cuda or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous():
-            raise _lib.MyriadHipError(f"attn_prefill_ragged: {name} must be a contiguous {'cuda' if cuda else 'cpu'} int32 [R, 3]")
-    if seg.shape != seg_host.shape:
-        raise _lib.MyriadHipError("attn_prefill_ragged: seg and seg_host must hold the same table")
-    for name, t in (("cos", cos_tab), ("sin", sin_tab)):
-        if t.dtype != F32 or not t.is_cuda or t.dim() != 2 or t.shape[1] != head_dim // 2 or not t.is_contiguous():
-            raise _lib.MyriadHipError(f"attn_prefill_ragged: {name} must be a contiguous cuda f32 [max_pos, D / 2]")
-    if cos_tab.shape != sin_tab.shape:
-        raise _lib.MyriadHipError("attn_prefill_ragged: cos and sin tables differ in shape")
-    if out is None:
-        out = torch.zeros((M, W), dtype=BF16, device=qkv2d.device)
-    else:
-        _chk2d(out, BF16, "attn_prefill_ragged.out")
-        if out.shape != (M, W):
-            raise _lib.MyriadHipError(f"attn_prefill_ragged: out shape {tuple(out.shape)} != {(M, W)}")
-    R = seg_host.shape[0]
-    _lib.check(_L().mh_attn_prefill_ragged(_p(qkv2d), qkv2d.stride(0), _p(pos), _p(seg), seg_host.data_ptr(), R, _p(cache),
-                                           cache.stride(0), cache.stride(1), cache.shape[0], cache.shape[1], _p(cos_tab),
-                                           _p(sin_tab), cos_tab.shape[0], _p(out), out.stride(0), M, n_heads, head_dim, float(scale),
-                                           _s()), f"mh_attn_prefill_ragged M={M} R={R} H={n_heads} D={head_dim}")
-    return out
+    return _attn_prefill_ragged(3, qkv2d, pos, seg, seg_host, cache, cos_tab, sin_tab, n_heads, head_dim, scale, out)
+
+
+def attn_prefill_ragged_past(qkv2d: torch.Tensor, pos: torch.Tensor, seg: torch.Tensor, seg_host: torch.Tensor,
+                             cache: torch.Tensor, cos_tab: torch.Tensor, sin_tab: torch.Tensor, n_heads: int, head_dim: int,
+                             scale: float, out: Optional[torch.Tensor] = None):
+    """attn_prefill_ragged on top of a cached prefix: seg / seg_host are int32 [R, 4] = (row0, len, slot, past) per segment, the
+    segment's rows are the len NEW rows of a request whose keys 0 .. past - 1 are cache[slot]'s rows already.  Per segment:
+    rope_ + copy3d_bf16 into cache[slot, past:past + len] + attn_fwd(causal=True) over the past + len keys, same bits; no cache
+    row >= past is read, none outside [past, past + len) written.  With past = 0 everywhere it is attn_prefill_ragged's bits."""
+    return _attn_prefill_ragged(4, qkv2d, pos, seg, seg_host, cache, cos_tab, sin_tab, n_heads, head_dim, scale, out)
 
 
 # keys per workgroup of mh_attn_decode_rope_split: 128 measured fastest at 256 / 1,024 / 2,048 cached keys, batch 1, 32 heads

@@ -6,9 +6,16 @@
   * time to first token of turn 2 (turn 1's context + its answer + a new question) with the cache reused and with a full
     re-prefill;
   * --chunks: the attention launch alone (32 launches = one token's layers, replayed from a graph) for the single-workgroup kernel
-    and the split kernel at 128 / 256 / 512 keys per chunk.
+    and the split kernel at 128 / 256 / 512 keys per chunk;
+  * --ragged-past: mh_attn_prefill_ragged_past alone against the three launches per request it replaces (rope, cache copy,
+    causal attention over past + len keys), R = 8 requests, at (past, len) = (256, 32) and (1024, 32);
+  * --pool N[,N...]: N conversations of 3 turns each (a context of --pool-context keys, then per turn the answer of --tokens
+    tokens and a 24-token question) through SlotDecoder.run_turns on N slots -- what ChatPool.answer_many runs -- against the same
+    turns through N DecodeSessions one after the other -- what N Chat objects run; tokenising and image encoding are the same on
+    both sides and left out.  The two are interleaved per repeat; wall ms per turn, median of --repeats with min and max.
 
-python tools/chat_bench.py [--layers 32] [--tokens 32] [--repeats 3] [--chunks]   -> one JSON line per measurement"""
+python tools/chat_bench.py [--layers 32] [--tokens 32] [--repeats 3] [--chunks] [--ragged-past] [--pool 1,4,8,16]
+-> one JSON line per measurement"""
 import argparse
 import json
 import os
@@ -29,7 +36,10 @@ ap.add_argument("--tokens", type=int, default=32, help="timed token steps per me
 ap.add_argument("--repeats", type=int, default=3)
 ap.add_argument("--contexts", default="256,1024,2048")
 ap.add_argument("--chunks", action="store_true", help="also time the attention launch alone per chunk size")
-ap.add_argument("--skip-model", action="store_true", help="only the --chunks launch timings")
+ap.add_argument("--skip-model", action="store_true", help="only the --chunks / --ragged-past launch timings")
+ap.add_argument("--ragged-past", action="store_true", help="time mh_attn_prefill_ragged_past against the launches it replaces")
+ap.add_argument("--pool", default="", help="conversation counts for the pool-against-sequential-sessions comparison")
+ap.add_argument("--pool-context", type=int, default=256, help="keys of a conversation's first context")
 a = ap.parse_args()
 dev = "cuda:0"
 torch.manual_seed(0)
@@ -78,8 +88,55 @@ def chunk_bench():
             del g
 
 
-if a.chunks or a.skip_model:
+def ragged_past_bench():
+    R, H, D, T = 8, 32, 128, 2048
+    W, scale = H * D, 1.0 / D ** 0.5
+    fr = torch.arange(T).float()[:, None] * (1.0 / (10000.0 ** (torch.arange(0, D, 2).float() / D)))[None]
+    cos, sin = fr.cos().contiguous().to(dev), fr.sin().contiguous().to(dev)
+    cache = (torch.randn((R, T, 2 * W), device=dev) * 0.5).to(torch.bfloat16)
+    for past, n in ((256, 32), (1024, 32)):
+        M = R * n
+        qkv = (torch.randn((M, 3 * W), device=dev) * 0.5).to(torch.bfloat16)
+        work = qkv.clone()
+        seg_host = torch.tensor([(i * n, n, i, past) for i in range(R)], dtype=torch.int32)
+        seg = seg_host.to(dev)
+        pos = (torch.arange(n, dtype=torch.int32) + past).repeat(R).to(dev)
+        pos1 = pos[:n].contiguous()
+        out = torch.empty((M, W), dtype=torch.bfloat16, device=dev)
+
+        def fused():
+            ops.attn_prefill_ragged_past(qkv, pos, seg, seg_host, cache, cos, sin, H, D, scale, out=out)
+
+        def three():                                                 # per request, as R solo _prefill(emb, cache, past) calls do
+            for i in range(R):
+                x = work[i * n:(i + 1) * n]
+                ops.rope_(x, 0, 2 * H, D, pos1, cos, sin, 1.0)
+                q3 = x.view(1, n, 3 * W)
+                ops.copy3d_bf16(q3[:, :, W:], cache[i:i + 1, past:past + n])
+                kc = cache[i:i + 1, :past + n]
+                ops.attn_fwd(q3[:, :, :W], kc[:, :, :W], kc[:, :, W:], H, D, scale, causal=True, need_lse=False)
+
+        for name, fn in (("ragged_past", fused), ("three_launches_per_request", three)):
+            for _ in range(5):
+                fn()
+            torch.cuda.synchronize()
+            ts = []
+            for _ in range(5):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(20):
+                    fn()
+                e1.record()
+                e1.synchronize()
+                ts.append(e0.elapsed_time(e1) / 20 * 1000.0)
+            emit(what="prefill_attn_us", kernel=name, past=past, len=n, R=R, H=H, D=D, us=round(statistics.median(ts), 1),
+                 min=round(min(ts), 1), max=round(max(ts), 1))
+
+
+if a.chunks or (a.skip_model and not a.ragged_past):
     chunk_bench()
+if a.ragged_past:
+    ragged_past_bench()
 if a.skip_model:
     sys.exit(0)
 
@@ -104,6 +161,50 @@ def ctx(n, seed):
     emb = llama.embed[ids.to(dev)].float()[None].contiguous()
     return emb, [("t", int(t)) for t in ids]
 
+
+def pool_bench(N):
+    """3 turns of N conversations: the pool (one run_turns call per turn) against N sessions one after the other."""
+    n_new, Q = a.tokens, 24
+    kw = dict(max_new_tokens=n_new, stop_ids=(), eos_id=-1, min_length=0)
+    dec = llama.slot_decoder(N, a.pool_context + 3 * (n_new + Q) + 2)
+    sess = [DecodeSession(llama, a.pool_context + 3 * (n_new + Q) + 2) for _ in range(N)]     # kept, as a Chat keeps its own
+    times = {"pool": [[], [], []], "sessions": [[], [], []]}
+    for r in range(a.repeats + 1):                                   # repeat 0 warms both sides up (graph captures)
+        first = [ctx(a.pool_context, 1000 * N + 10 * c + r) for c in range(N)]
+        for mode in ("pool", "sessions"):
+            state = [(e[0], list(k)) for e, k in first]
+            for t in range(3):
+                reset = "bench" if t == 0 else None                  # a new conversation: nothing of the last repeat is reused
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                if mode == "pool":
+                    got = {c: ids for c, ids, _ in dec.run_turns([(c, e, k, reset) for c, (e, k) in enumerate(state)], weights_version=0,
+                                                                 prefill_batch=8, **kw)}
+                else:
+                    got = {c: sess[c].generate(e[None], [k], weights_version=0, reset_reason=reset, **kw)[0].cpu() for c, (e, k) in enumerate(state)}
+                torch.cuda.synchronize()
+                if r:
+                    times[mode][t].append((time.perf_counter() - t0) * 1000.0)
+                for c, (e, k) in enumerate(state):
+                    q_emb, q_keys = ctx(Q, 7000 + 100 * c + 10 * t + r)
+                    state[c] = (torch.cat([e, llama.embed[got[c].to(dev)].float(), q_emb[0]], 0).contiguous(),
+                                k + [("t", int(i)) for i in got[c]] + q_keys)
+            if mode == "pool":
+                reused = [s["reused_tokens"] for s in dec.last_stats["turns"]]
+    for mode in times:
+        for t in range(3):
+            ts = times[mode][t]
+            emit(what="pool_turn_ms", mode=mode, conversations=N, turn=t + 1, first_context=a.pool_context, tokens=n_new,
+                 ms=round(statistics.median(ts), 2), min=round(min(ts), 2), max=round(max(ts), 2),
+                 **(dict(turn3_reused=reused[:2]) if mode == "pool" else {}))
+    del dec, sess
+    torch.cuda.empty_cache()
+
+
+if a.pool:
+    for N in [int(x) for x in a.pool.split(",")]:
+        pool_bench(N)
+    sys.exit(0)
 
 # ---- ms per token at a cached context of L keys: (turn of 1 + W + K tokens) - (turn of 1 token), both fully prefilled
 for split in (True, False):
