@@ -109,6 +109,31 @@ Map heads (expert.hip):
     Pool routing in a chain (conv GEMM -> pool): a window whose fp64 runner-up lies within the GEMM bounds of the maximum, or
         whose maximum lies within its bound of 0, may route either way (pool_decisions); the chain test gives such windows no
         gradient and asserts they are at most 1 % of all windows.
+LoRA (lora.hip).  The dropout mask is stated independently of the library: keep_mask_ref restates common.h's dropout_hash /
+    dropout_hash2 / dropout_keep in integer arithmetic; v_proj's mask is the second draw of q_proj's hash (seed bit 63).  The
+    kernels multiply by bf16(A) (the forward's MFMA operand), so every reference does.  ik = 1 / (1 - p) is an fp32 quotient,
+    allowed C_FN ulp like every division here.
+    lora_down: group g < G, column j holds s ik sum_{d in [g D/G, (g+1) D/G)} keep(m,d) x[m,d] bf16(A)[j,d] (q mask for j < R2/2,
+        v mask otherwise; dropped elements are zeroed, exact).  A workgroup's 8 waves split the group's k-steps, each an MFMA
+        chain of 32-product blocks; the 8 partial sums are added like split-K slabs:
+        s ik g_acc(D/G, 8) sum |keep x bf16(A)| + (C_FN + 3) u32 |ref| (ik, the scale, the product), then the bf16 rounding.  The
+        sum across the groups (the qkv GEMM forms it) carries the sum of the groups' bounds.
+    lora_dx: base + s (kq sum_{j<r} g_j a_j + kv sum_{j>=r} g_j a_j), a = bf16(A): each half is r serial FMAs, then the two mask
+        products folded into one FMA and the outer FMA: (r + 3) u32 s (kq sum |g_j a_j| + kv sum |g_j a_j|), + (C_FN + 1) u32 on
+        the same term when p > 0 (ik), + u32 |ref|.  base and g enter as given (the slab sums that form them are exact in the
+        tests: integer products).
+    lora_wgrad, as a function of what it reads (bf16 x, the fp32 border gradient g, the bf16 border summed over its 64 / R2
+        groups, bf16 dq / dv): dA[j,d] = sum_m s g[m,j] keep(m,d) x[m,d], dB_q[d,j] = sum_m dq[m,d] st[m,j], dB_v likewise.
+        st = the groups added in order: 3 u32 sum |groups|, carried through |dq| / |dv|.  Thread-per-column kernel: 64 row chunks,
+        a chunk's ceil(M/64) rows added serially, the chunks added in order, + 4 for the scalar, the mask product and the FMA:
+        (ceil(M/64) + 64 + 4) u32 on sum_m of the magnitudes.  MFMA kernel (r = 8, D % 128 == 0): the per-row scalars are a bf16
+        head plus a bf16 remainder (relative error u16^2), two MFMAs per 32-row step at two roundings each as g_acc counts them,
+        16 chunks, ik applied to the finished sum: (u16^2 + (4 ceil(ceil(M/16)/32) + 16 + C_FN + 4) u32) on the same magnitudes.
+        A gradient that cancels over the rows keeps the bound of its terms.
+    lora_refresh_border(s): data movement, torch.equal against bf16(B) in every group of W_ext and W_ext^T; every other cell
+        untouched (lora_refresh_check).
+    rmsnorm backward behind lora_dx: rmsnorm_ref_bound(dy_err=...) carries the bound of d(xn) through the norm (dx is linear in
+        dy): r |w| e + |x| r^3 / D sum |x w| e.
 """
 from __future__ import annotations
 
@@ -409,8 +434,10 @@ def norm_weight(D: int, seed: int) -> torch.Tensor:
     return w
 
 
-def rmsnorm_ref_bound(x, w, eps, dy=None, dres=None):
-    """fp64 RMSNorm of fp32 x [M, D]: dict y, y_bound (fp32 value), y_bf16_bound; with dy also dx, dx_bound, dx_bf16_bound."""
+def rmsnorm_ref_bound(x, w, eps, dy=None, dres=None, dy_err=None):
+    """fp64 RMSNorm of fp32 x [M, D]: dict y, y_bound (fp32 value), y_bf16_bound; with dy also dx, dx_bound, dx_bf16_bound.
+    dy_err: an element-wise bound on an error dy itself carries (dx is linear in dy: it enters as r |w| e and
+    |x| r^3 / D sum |x w| e)."""
     x, w = x.double(), w.double()
     D = x.shape[1]
     eps = f32_value(eps)
@@ -431,6 +458,9 @@ def rmsnorm_ref_bound(x, w, eps, dy=None, dres=None):
     if dres is not None:
         dx = dx + dres.double()
     e = (rel_r + 4 * U32) * t1.abs() + x.abs() * (e_cc + 2 * U32 * cc.abs()) + 2 * U32 * dx.abs()
+    if dy_err is not None:
+        de = dy_err.double()
+        e = e + r * w.abs() * de + x.abs() * r ** 3 / D * ((x * w).abs() * de).sum(1, keepdim=True)
     out.update(dx=dx, dx_bound=e, dx_bf16_bound=bf16_out(dx, e))
     return out
 
@@ -1050,3 +1080,156 @@ def rowmax_inputs(rows, cols, wide, seed):
     if rows > 3:
         full[3, (cols - 1) // 5 * 5] = 9.5                   # a multiple of 5: skipped at period 5
     return full, rnd(rows, seed=seed + 1)
+
+
+# ---------------------------------------------------------------------------------------------------------------- LoRA
+LORA_BORDER = 64
+LORA_V_TAG = 1 << 63
+LORA_DOWN_WAVES = 8        # waves of a lora_down workgroup: each sums its own k-steps, the partial sums are added like slabs
+LORA_WG_CHUNKS = 64        # row chunks of the thread-per-column weight-gradient kernel
+LORA_WG_MFMA_CHUNKS = 16   # row chunks of the MFMA weight-gradient kernel
+
+
+def keep_mask_ref(seed, M, D, p, second=False):
+    """The dropout keep mask [M, D] fp32 of csrc/common.h restated in integer arithmetic (numpy uint64, masked to 32 bits after
+    every product): element (m, d) hashes the flat index m D + d with the seed's low 63 bits; second (or bit 63 of the seed) takes
+    dropout_hash2 of that hash.  u = (h >> 8) 2^-24 (exact in fp32); kept iff float32(u) >= float32(p); the value is the fp32
+    quotient 1 / (1 - p), and 1.0 everywhere for p == 0."""
+    import numpy as np
+    p32 = np.float32(p)
+    if not p32 > 0:
+        return torch.ones(M, D, dtype=torch.float32)
+    seed = int(seed)
+    second = bool(second) or bool((seed >> 63) & 1)
+    m32 = np.uint64(0xFFFFFFFF)
+    idx = np.arange(M * D, dtype=np.uint64)
+    lo, hi = idx & m32, idx >> np.uint64(32)
+    s_lo, s_hi = np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0x7FFFFFFF)
+    h = (lo * np.uint64(0x9E3779B1) + (s_lo ^ ((hi * np.uint64(0x85EBCA77)) & m32))) & m32
+    h = h ^ s_hi
+    h = h ^ (h >> np.uint64(16))
+    h = (h * np.uint64(0x85EBCA6B)) & m32
+    h = h ^ (h >> np.uint64(13))
+    h = (h * np.uint64(0xC2B2AE35)) & m32
+    h = h ^ (h >> np.uint64(16))
+    if second:
+        h = ((h ^ np.uint64(0x68E31DA4)) * np.uint64(0x2C1B3C6D)) & m32
+        h = h ^ (h >> np.uint64(15))
+    u = (h >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    ik = np.float32(1.0) / (np.float32(1.0) - p32)
+    keep = np.where(u >= p32, ik, np.float32(0.0)).astype(np.float32)
+    return torch.from_numpy(keep).reshape(M, D)
+
+
+def _lora_ik(p) -> float:
+    """1 / (1 - p) of the fp32 p, in double: what the kernels' fp32 quotient approximates."""
+    return 1.0 / (1.0 - f32_value(p))
+
+
+def lora_groups(D: int, R2: int) -> int:
+    """Border groups mh_lora_down fills: 64 / R2, halved until every group's range of D is whole 32-element k-steps."""
+    G = LORA_BORDER // R2
+    while G > 1 and D % (32 * G):
+        G >>= 1
+    return G
+
+
+def lora_rows(M: int, C: int, seed: int, scale: float = 1.0) -> torch.Tensor:
+    """fp32 [M, C] token rows, by row index mod 4: N(0,1); 1e-3 N(0,1); 1e2 N(0,1); all zeros (times scale)."""
+    x = rnd(M, C, seed=seed) * scale
+    k = torch.arange(M) % 4
+    x[k == 1] *= 1e-3
+    x[k == 2] *= 1e2
+    x[k == 3] = 0.0
+    return x
+
+
+def lora_adaptor(R2: int, D: int, seed: int) -> torch.Tensor:
+    """fp32 A [R2, D] ~ 0.05 N(0,1) with one all-zero row (the last q row) and one row of 1.0 (the first v row)."""
+    A = rnd(R2, D, seed=seed) * 0.05
+    A[R2 // 2 - 1] = 0.0
+    A[R2 // 2] = 1.0
+    return A
+
+
+def lora_down_ref_bound(x, A, s, p, keep_q, keep_v, R2, G):
+    """fp64 partial borders of mh_lora_down (module docstring): dict part [M, G R2], part_bound, total [M, R2], total_bound."""
+    x64, a64 = x.double(), A.to(torch.bfloat16).double()
+    M, D = x64.shape
+    r = R2 // 2
+    ik = _lora_ik(p) if f32_value(p) > 0 else 1.0
+    s = f32_value(s)
+    xq, xv = x64 * (keep_q > 0), x64 * (keep_v > 0)
+    w = D // G
+    parts, bounds = [], []
+    for g in range(G):
+        c = slice(g * w, (g + 1) * w)
+        sq, sv = xq[:, c] @ a64[:r, c].T, xv[:, c] @ a64[r:, c].T
+        mq, mv = xq[:, c].abs() @ a64[:r, c].abs().T, xv[:, c].abs() @ a64[r:, c].abs().T
+        ref = s * ik * torch.cat([sq, sv], 1)
+        e = abs(s) * ik * g_acc(w, LORA_DOWN_WAVES) * torch.cat([mq, mv], 1) + (C_FN + 3) * U32 * ref.abs()
+        parts.append(ref)
+        bounds.append(bf16_out(ref, e))
+    part, part_bound = torch.cat(parts, 1), torch.cat(bounds, 1)
+    return dict(part=part, part_bound=part_bound, total=part.reshape(M, G, R2).sum(1), total_bound=part_bound.reshape(M, G, R2).sum(1))
+
+
+def lora_dx_ref_bound(base, g, A, s, p, keep_q, keep_v):
+    """fp64 (ref, bound) of mh_lora_dx: base [M, D], the border gradient g [M, R2], A [R2, D] fp32 (module docstring)."""
+    b64, g64, a64 = base.double(), g.double(), A.to(torch.bfloat16).double()
+    r = A.shape[0] // 2
+    drop = f32_value(p) > 0
+    ik = _lora_ik(p) if drop else 1.0
+    s = f32_value(s)
+    kq, kv = (keep_q > 0) * ik, (keep_v > 0) * ik
+    tq, tv = g64[:, :r] @ a64[:r], g64[:, r:] @ a64[r:]
+    mag = abs(s) * (kq * (g64[:, :r].abs() @ a64[:r].abs()) + kv * (g64[:, r:].abs() @ a64[r:].abs()))
+    ref = b64 + s * (kq * tq + kv * tv)
+    e = ((r + 3) + ((C_FN + 1) if drop else 0)) * U32 * mag + U32 * ref.abs()
+    return ref, e
+
+
+def lora_wgrad_ref_bound(x, keep_q, keep_v, sg_in, border, dq, dv, s, R2, mfma):
+    """fp64 weight gradients of mh_lora_wgrad from what the kernel reads (module docstring): dict dA [R2, D], dBq, dBv [D, r] and
+    *_bound."""
+    x64, q64, v64 = x.double(), dq.double(), dv.double()
+    M, D = x64.shape
+    r = R2 // 2
+    s = f32_value(s)
+    sg = s * sg_in.double()
+    grp = border.double().reshape(M, LORA_BORDER // R2, R2)
+    st, e_st = grp.sum(1), 3 * U32 * grp.abs().sum(1)
+    xq, xv = x64 * keep_q.double(), x64 * keep_v.double()          # the masks carry the fp32 quotient the kernels form too
+    dA = torch.cat([sg[:, :r].T @ xq, sg[:, r:].T @ xv], 0)
+    mA = torch.cat([sg[:, :r].abs().T @ xq.abs(), sg[:, r:].abs().T @ xv.abs()], 0)
+    dBq, dBv = q64.T @ st[:, :r], v64.T @ st[:, r:]
+    mBq, mBv = q64.abs().T @ st[:, :r].abs(), v64.abs().T @ st[:, r:].abs()
+    if mfma:
+        n = U16 * U16 + (4 * -(-(-(-M // LORA_WG_MFMA_CHUNKS)) // 32) + LORA_WG_MFMA_CHUNKS + C_FN + 4) * U32
+    else:
+        n = (-(-M // LORA_WG_CHUNKS) + LORA_WG_CHUNKS + 4) * U32
+    return dict(dA=dA, dA_bound=n * mA, dBq=dBq, dBq_bound=n * mBq + q64.abs().T @ e_st[:, :r],
+                dBv=dBv, dBv_bound=n * mBv + v64.abs().T @ e_st[:, r:])
+
+
+def lora_refresh_check(ext, extT, Bq, Bv, W, D, r, what="lora_refresh"):
+    """ext [>= 3W, >= D + 64] and extT [>= D + 64, >= 3W] (or None) started poisoned: every group of the border holds
+    [bf16(B_q) | bf16(B_v)] -- B_q in the q rows (0..W), B_v in the v rows (2W..3W) -- and everything else is untouched: the k
+    rows, the q rows' v columns and the v rows' q columns, the first D columns, the pad rows and columns."""
+    q, v = Bq.to(torch.bfloat16), Bv.to(torch.bfloat16)
+    own = torch.zeros(ext.shape, dtype=torch.bool, device=ext.device)
+    ownT = None if extT is None else torch.zeros(extT.shape, dtype=torch.bool, device=extT.device)
+    for g in range(LORA_BORDER // (2 * r)):
+        c = D + g * 2 * r
+        assert torch.equal(ext[:W, c:c + r], q), f"{what}: W_ext group {g} q"
+        assert torch.equal(ext[2 * W:3 * W, c + r:c + 2 * r], v), f"{what}: W_ext group {g} v"
+        own[:W, c:c + r] = True
+        own[2 * W:3 * W, c + r:c + 2 * r] = True
+        if extT is not None:
+            assert torch.equal(extT[c:c + r, :W], q.T), f"{what}: W_ext^T group {g} q"
+            assert torch.equal(extT[c + r:c + 2 * r, 2 * W:3 * W], v.T), f"{what}: W_ext^T group {g} v"
+            ownT[c:c + r, :W] = True
+            ownT[c + r:c + 2 * r, 2 * W:3 * W] = True
+    assert bool(untouched(ext)[~own].all()), f"{what}: W_ext written outside the border's own cells"
+    if extT is not None:
+        assert bool(untouched(extT)[~ownT].all()), f"{what}: W_ext^T written outside the border's own cells"

@@ -1253,3 +1253,287 @@ def test_rowmax_emulation_is_within_the_bound(cols, period):
 @pytest.mark.parametrize("mutant", ["column_0_kept", "only_first_64"])
 def test_rowmax_mutant_fails(mutant):
     _raises(_rowmax_case, 7, 514, 257, mutant)
+
+
+# ------------------------------------------------------------------------------------------------------------------- LoRA
+LORA_SEED = 0x7A5C3E1F90B2D486            # 63 bits, high bits set
+LORA_S = 2.0
+
+
+def _fma(a, b, c):
+    """One fp32 rounding of a * b + c (the product of two fp32 values is exact in fp64)."""
+    return (torch.as_tensor(a).double() * b.double() + c.double()).float()
+
+
+def _ik32(p):
+    one = torch.tensor(1.0, dtype=F32)
+    return one / (one - torch.tensor(p, dtype=F32))
+
+
+def _lora_masks(M, D, p, seed=LORA_SEED):
+    return fb.keep_mask_ref(seed, M, D, p), fb.keep_mask_ref(seed, M, D, p, second=True)
+
+
+def emu_lora_down(x, A, out, s, p, kq, kv, R2, mutant=None):
+    """lora_down_kernel's arithmetic: a workgroup per (16 rows, group); wave w of 8 owns ceil(steps/8) 32-element k-steps of the
+    group's range and adds one 32-product block per step to its fp32 accumulator (dropped elements zeroed, A rounded to bf16); the
+    8 wave sums are added in order, scaled by s ik and rounded to bf16.  out: a [>= M, >= 64] window of a poisoned buffer."""
+    M, D = x.shape
+    r, G = R2 // 2, fb.lora_groups(D, R2)
+    a = A.to(BF16).float()
+    xf = x.float()
+    xq = torch.where(kq > 0, xf, torch.zeros_like(xf))
+    xv = xq if mutant == "v_rows_use_q_mask" else torch.where(kv > 0, xf, torch.zeros_like(xf))
+    scale = torch.tensor(s, dtype=F32) * _ik32(p) if (p > 0 and mutant != "scale_without_ik") else torch.tensor(s, dtype=F32)
+    steps = D // 32 // G
+    per = -(-steps // 8)
+
+    def block(st):
+        c = slice(st * 32, st * 32 + 32)
+        return torch.cat([xq[:, c] @ a[:r, c].T, xv[:, c] @ a[r:, c].T], 1)
+
+    for g in range(G):
+        tot = torch.zeros(M, R2, dtype=F32)
+        for w in range(8):
+            s0 = g * steps + w * per
+            s1 = min(s0 + per, g * steps + steps)
+            acc = torch.zeros(M, R2, dtype=F32)
+            for st in range(s0, s1):
+                acc = acc + block(st)
+            if mutant == "tail_step_counted" and s1 > s0:              # the UN = 4 tail re-reads the last step: not zeroed
+                for _ in range(-(s1 - s0) % 4):
+                    acc = acc + block(s1 - 1)
+            tot = tot + acc
+        val = (scale * tot).to(BF16)
+        col = 0 if mutant == "group_into_group_0" else g * R2
+        out[:M, col:col + R2] = val
+        if mutant == "row_clamp_written":                              # rows >= M of the last 16-row block store row M - 1
+            out[M:min(out.shape[0], -(-M // 16) * 16), col:col + R2] = val[M - 1]
+
+
+LORA_DOWN_CPU_CASES = [(5, 64, 16, 0.0), (17, 96, 32, 0.25), (33, 1152, 16, 0.25), (3, 5120, 16, 0.25), (16, 2048, 32, 0.0)]
+LORA_DOWN_MUTANTS = ["tail_step_counted", "v_rows_use_q_mask", "row_clamp_written", "group_into_group_0", "scale_without_ik"]
+
+
+def _lora_down_case(M, D, R2, p, mutant=None):
+    x = fb.lora_rows(M, D, seed=11).to(BF16)
+    A = fb.lora_adaptor(R2, D, seed=12)
+    kq, kv = _lora_masks(M, D, p)
+    G = fb.lora_groups(D, R2)
+    buf = fb.poisoned((M + 3, 64 + 8), BF16, "cpu")
+    emu_lora_down(x, A, buf, LORA_S, p, kq, kv, R2, mutant)
+    r = fb.lora_down_ref_bound(x, A, LORA_S, p, kq, kv, R2, G)
+    ratio = fb.assert_within(buf[:M, :G * R2], r["part"], r["part_bound"], f"lora_down {M}x{D} R2={R2}")
+    fb.assert_within(buf[:M, :G * R2].double().reshape(M, G, R2).sum(1), r["total"], r["total_bound"], "lora_down sum of groups")
+    fb.assert_untouched(buf[M:], "rows past M")
+    fb.assert_untouched(buf[:M, G * R2:], "groups past G")
+    return ratio
+
+
+@pytest.mark.parametrize("case", LORA_DOWN_CPU_CASES)
+def test_lora_down_emulation_is_within_the_bound(case):
+    assert _lora_down_case(*case) > 1e-3
+
+
+@pytest.mark.parametrize("mutant", LORA_DOWN_MUTANTS)
+def test_lora_down_mutant_fails(mutant):
+    with pytest.raises(AssertionError):
+        _lora_down_case(33, 1152, 16, 0.25, mutant)
+
+
+def emu_lora_dx(base, g, A, out, s, p, kq, kv, mutant=None):
+    """lora_dx_kernel: r serial FMAs per half against bf16(A), then fma(s, fma(acc_q, kq, acc_v * kv), base)."""
+    M, D = base.shape
+    r = A.shape[0] // 2
+    a = A if mutant == "A_not_rounded" else A.to(BF16).float()
+    acc, accv = torch.zeros(M, D, dtype=F32), torch.zeros(M, D, dtype=F32)
+    for j in range(r):
+        acc = _fma(g[:, j:j + 1], a[j][None], acc)
+        if mutant != "v_half_dropped":
+            accv = _fma(g[:, r + j:r + j + 1], a[r + j][None], accv)
+    inner = _fma(acc, kq, accv * kv)
+    b = base * (kq > 0) if mutant == "mask_on_base" else base
+    o = _fma(torch.tensor(s, dtype=F32), inner, b)
+    w = D - 4 if mutant == "last_float4_dropped" else D
+    out[:, :w] = o[:, :w]
+
+
+LORA_DX_MUTANTS = ["A_not_rounded", "mask_on_base", "v_half_dropped", "last_float4_dropped"]
+
+
+def _lora_dx_case(M, D, R2, p, mutant=None):
+    ext = fb.lora_rows(M, D + R2, seed=21)
+    base, g = ext[:, :D].contiguous(), ext[:, D:].contiguous()
+    A = fb.lora_adaptor(R2, D, seed=22)
+    kq, kv = _lora_masks(M, D, p)
+    buf = fb.poisoned((M + 1, D), F32, "cpu")
+    emu_lora_dx(base, g, A, buf[:M], LORA_S, p, kq, kv, mutant)
+    ref, bnd = fb.lora_dx_ref_bound(base, g, A, LORA_S, p, kq, kv)
+    ratio = fb.assert_within(buf[:M], ref, bnd, f"lora_dx {M}x{D} R2={R2}")
+    fb.assert_untouched(buf[M:], "row past M")
+    return ratio
+
+
+@pytest.mark.parametrize("case", [(1, 4, 16, 0.25), (7, 68, 16, 0.0), (9, 132, 32, 0.25)])
+def test_lora_dx_emulation_is_within_the_bound(case):
+    assert _lora_dx_case(*case) > 1e-3
+
+
+@pytest.mark.parametrize("mutant", LORA_DX_MUTANTS)
+def test_lora_dx_mutant_fails(mutant):
+    with pytest.raises(AssertionError):
+        _lora_dx_case(9, 132, 32, 0.25, mutant)
+
+
+def emu_lora_wgrad(x, kq, kv, sg_in, border, dq, dv, s, p, R2, mfma, mutant=None):
+    """(dA [R2, D], dBq [D, r], dBv [D, r]) as mh_lora_wgrad forms them.  Thread-per-column kernel: 64 row chunks, a chunk's rows
+    added serially in fp32, the chunks added in order.  MFMA kernel (R2 = 16): 16 row chunks, per 32-row step two products per
+    sum -- the per-row scalars' bf16 heads, then their bf16 remainders -- against x with its dropped elements zeroed; 1 / (1 - p)
+    multiplies the chunk's finished sum."""
+    M, D = x.shape
+    r = R2 // 2
+    grp = border.float().reshape(M, 64 // R2, R2)
+    st = torch.zeros(M, R2, dtype=F32)
+    for g in range(1 if mutant == "border_group_0_only" else 64 // R2):
+        st = st + grp[:, g]
+    sg = torch.tensor(s, dtype=F32) * sg_in
+    xf, qf, vf = x.float(), dq.float(), dv.float()
+    ik = _ik32(p) if (p > 0 and mutant != "ik_missing") else torch.tensor(1.0, dtype=F32)
+    nch = 16 if mfma else 64
+    rows_per = -(-M // nch)
+    chunks = [(c * rows_per, min(c * rows_per + rows_per, M)) for c in range(nch)]
+    live = [c for c, (m0, m1) in enumerate(chunks) if m1 > m0]
+    parts = []
+    for c, (m0, m1) in enumerate(chunks):
+        a, bq, bv = torch.zeros(R2, D, dtype=F32), torch.zeros(D, r, dtype=F32), torch.zeros(D, r, dtype=F32)
+        if mutant == "last_chunk_dropped" and c == live[-1]:
+            m1 = m0
+        if mfma:
+            xq = torch.where(kq > 0, xf, torch.zeros_like(xf))
+            xv = torch.where(kv > 0, xf, torch.zeros_like(xf))
+            gh, th = fb.bf16_round(sg), fb.bf16_round(st)
+            gl, tl = fb.bf16_round(sg - gh), fb.bf16_round(st - th)
+            if mutant == "remainder_dropped":
+                gl, tl = torch.zeros_like(gl), torch.zeros_like(tl)
+            for mb in range(m0, m1, 32):
+                rs = slice(mb, min(mb + 32, m1))
+                for sc_g, sc_t in ((gh, th), (gl, tl)):
+                    a[:r] = a[:r] + sc_g[rs, :r].T @ xq[rs]
+                    a[r:] = a[r:] + sc_g[rs, r:].T @ xv[rs]
+                    bq = bq + qf[rs].T @ sc_t[rs, :r]
+                    bv = bv + vf[rs].T @ sc_t[rs, r:]
+            a = a * ik
+        else:
+            rows = list(range(m0, m1))
+            if mutant == "clamped_row_counted_twice" and rows:          # the trip of three's clamped loads are not skipped
+                rows += [m1 - 1] * (-len(rows) % 3)
+            for m in rows:
+                xd, xw = xf[m] * (ik * (kq[m] > 0)), xf[m] * (ik * (kv[m] > 0))
+                a[:r] = a[:r] + sg[m, :r, None] * xd[None]
+                a[r:] = a[r:] + sg[m, r:, None] * xw[None]
+                bq = bq + qf[m][:, None] * st[m, None, :r]
+                bv = bv + vf[m][:, None] * st[m, None, r:]
+        parts.append((a, bq, bv))
+    out = [torch.zeros_like(t) for t in parts[0]]
+    for pa in parts:
+        out = [o + t for o, t in zip(out, pa)]
+    return out
+
+
+LORA_WGRAD_CPU_CASES = [(1, 128, 16, 1, 0.25), (37, 128, 16, 1, 0.0), (530, 128, 16, 1, 0.25), (37, 128, 16, 0, 0.25),
+                        (71, 132, 16, 0, 0.25), (200, 68, 32, 0, 0.0)]
+LORA_WGRAD_MUTANTS = [("last_chunk_dropped", 0), ("last_chunk_dropped", 1), ("clamped_row_counted_twice", 0), ("border_group_0_only", 0),
+                      ("border_group_0_only", 1), ("remainder_dropped", 1), ("ik_missing", 0), ("ik_missing", 1)]
+
+
+def _lora_wgrad_case(M, D, R2, mfma, p, mutant=None):
+    r = R2 // 2
+    x = fb.lora_rows(M, D, seed=31).to(BF16)
+    sg_in = fb.rnd(M, R2, seed=32) * 0.1
+    border = fb.rnd(M, 64, seed=33).to(BF16)
+    dq, dv = fb.rnd(M, D, seed=34).to(BF16), fb.rnd(M, D, seed=35).to(BF16)
+    kq, kv = _lora_masks(M, D, p)
+    dA, dBq, dBv = emu_lora_wgrad(x, kq, kv, sg_in, border, dq, dv, LORA_S, p, R2, mfma, mutant)
+    ref = fb.lora_wgrad_ref_bound(x, kq, kv, sg_in, border, dq, dv, LORA_S, R2, bool(mfma))
+    what = f"lora_wgrad {M}x{D} R2={R2} mfma={mfma}"
+    return max(fb.assert_within(dA[:r], ref["dA"][:r], ref["dA_bound"][:r], what + " dA_q"),
+               fb.assert_within(dA[r:], ref["dA"][r:], ref["dA_bound"][r:], what + " dA_v"),
+               fb.assert_within(dBq, ref["dBq"], ref["dBq_bound"], what + " dB_q"),
+               fb.assert_within(dBv, ref["dBv"], ref["dBv_bound"], what + " dB_v"))
+
+
+@pytest.mark.parametrize("case", LORA_WGRAD_CPU_CASES)
+def test_lora_wgrad_emulation_is_within_the_bound(case):
+    assert _lora_wgrad_case(*case) > 1e-3
+
+
+@pytest.mark.parametrize("mutant,mfma", LORA_WGRAD_MUTANTS)
+def test_lora_wgrad_mutant_fails(mutant, mfma):
+    with pytest.raises(AssertionError):
+        _lora_wgrad_case(71, 128, 16, mfma, 0.25, mutant)
+
+
+def emu_lora_refresh(Bq, Bv, ext, extT, W, D, r, mutant=None):
+    q, v = Bq.to(BF16), Bv.to(BF16)
+    for g in range(1 if mutant == "one_group_only" else 64 // (2 * r)):
+        c = D + g * 2 * r
+        ext[:W, c:c + r] = q
+        vc = c if mutant == "v_into_q_columns" else c + r
+        ext[2 * W:3 * W, vc:vc + r] = v
+        if extT is not None:
+            extT[c:c + r, :W] = q.reshape(r, W) if mutant == "transpose_missing" else q.T
+            extT[vc:vc + r, 2 * W:3 * W] = v.reshape(r, W) if mutant == "transpose_missing" else v.T
+
+
+def _lora_refresh_case(W, D, r, mutant=None, with_T=True):
+    Bq, Bv = fb.rnd(W, r, seed=41), fb.rnd(W, r, seed=42)
+    ext = fb.poisoned((3 * W + 1, D + 64 + 8), BF16, "cpu")
+    extT = fb.poisoned((D + 64 + 1, 3 * W + 8), BF16, "cpu") if with_T else None
+    emu_lora_refresh(Bq, Bv, ext, extT, W, D, r, mutant)
+    fb.lora_refresh_check(ext, extT, Bq, Bv, W, D, r)
+
+
+@pytest.mark.parametrize("W,D,r", [(12, 32, 8), (100, 64, 16)])
+@pytest.mark.parametrize("with_T", [True, False])
+def test_lora_refresh_emulation_passes_the_check(W, D, r, with_T):
+    _lora_refresh_case(W, D, r, with_T=with_T)
+
+
+@pytest.mark.parametrize("mutant", ["v_into_q_columns", "one_group_only", "transpose_missing"])
+def test_lora_refresh_mutant_fails(mutant):
+    with pytest.raises(AssertionError):
+        _lora_refresh_case(12, 32, 8, mutant)
+
+
+def test_keep_mask_ref_is_a_deterministic_fair_draw_with_two_streams():
+    n, p = 1 << 20, 0.25
+    q = fb.keep_mask_ref(LORA_SEED, 1024, 1024, p)
+    assert torch.equal(q, fb.keep_mask_ref(LORA_SEED, 1024, 1024, p))
+    assert torch.equal(q.reshape(-1), fb.keep_mask_ref(LORA_SEED, 1, n, p).reshape(-1)), "the mask is a function of the flat index"
+    v = fb.keep_mask_ref(LORA_SEED, 1024, 1024, p, second=True)
+    assert torch.equal(v, fb.keep_mask_ref(LORA_SEED | fb.LORA_V_TAG, 1024, 1024, p)), "bit 63 of the seed selects the second draw"
+    assert not torch.equal(q, v)
+    both = float(((q > 0) & (v > 0)).double().mean())
+    tol = 4 * (p * (1 - p) / n) ** 0.5
+    for m in (q, v):
+        assert set(m.unique().tolist()) == {0.0, float(_ik32(p))}
+        assert abs(float((m > 0).double().mean()) - (1 - p)) <= tol
+    assert abs(both - (1 - p) ** 2) <= 2 * tol, "the two draws are not independent"
+    assert not torch.equal(q, fb.keep_mask_ref(LORA_SEED ^ 1, 1024, 1024, p))
+    for second in (False, True):
+        assert bool((fb.keep_mask_ref(LORA_SEED, 7, 36, 0.0, second=second) == 1.0).all())
+
+
+def test_rmsnorm_bound_carries_an_error_of_dy_and_leaves_the_default_unchanged():
+    x, w = fb.norm_rows(7, 252, seed=51), fb.norm_weight(252, seed=52)
+    dy, dres = fb.rnd(7, 252, seed=53), fb.rnd(7, 252, seed=54)
+    r0 = fb.rmsnorm_ref_bound(x, w, 1e-6, dy=dy, dres=dres)
+    e = 1e-3 * dy.abs() + 1e-6
+    r1 = fb.rmsnorm_ref_bound(x, w, 1e-6, dy=dy, dres=dres, dy_err=e)
+    assert torch.equal(r0["dx"], r1["dx"]) and bool((r1["dx_bound"] >= r0["dx_bound"]).all())
+    assert torch.equal(fb.rmsnorm_ref_bound(x, w, 1e-6, dy=dy, dres=dres, dy_err=torch.zeros_like(dy))["dx_bound"], r0["dx_bound"])
+    # a dy moved by its whole allowance, with either sign per element, stays inside the widened bound around the original dx
+    sign = torch.where(fb.rnd(7, 252, seed=55) > 0, 1.0, -1.0)
+    moved = fb.rmsnorm_ref_bound(x, w, 1e-6, dy=dy.double() + sign * e.double(), dres=dres)["dx"]
+    # (the allowance is attained exactly on an all-zero row: 1e-9 relative for the fp64 evaluation of the two sides)
+    fb.assert_within(moved, r1["dx"], (r1["dx_bound"] - r0["dx_bound"]) * (1 + 1e-9) + 1e-300, "dy_err")
