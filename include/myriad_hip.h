@@ -522,6 +522,16 @@ int mh_attn_decode_rope_split(const void* qkv, long ld_qkv, void* cache, long ca
                               const int* pos_dev, const int* kv_len, const float* cos_tab, const float* sin_tab, void* out, long ldo,
                               float* partials, long partials_floats, int B, int H, int D, int T_cap, int chunk, float scale,
                               mh_stream_t s);
+/* The split token step with per-row state (decode slots), the same kernels with their ROWS flag on: row b rotates at pos[b] and
+ * appends k | v at cache row pos[b] (the host keeps pos[b] < T_cap), the query sees kv_len[b] keys; a live row's out and cache
+ * row have the bits of mh_attn_decode_rope_split at B = 1 on that row with pos_dev[0] = pos[b] and the same chunk.  qkv is read
+ * only (mh_attn_decode_rope_rows rotates q in place; this entry does not).  live int[B] on the device: a row with live[b] == 0
+ * reads neither qkv nor the cache, writes neither the cache nor a partial record, and gets a zero out row.  kv_len, pos and live
+ * are read on the device, so one captured launch pair replays while contexts grow and rows go idle and live again. */
+int mh_attn_decode_rope_split_rows(const void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
+                                   const int* kv_len, const int* live, const float* cos_tab, const float* sin_tab, void* out,
+                                   long ldo, float* partials, long partials_floats, int B, int H, int D, int T_cap, int chunk,
+                                   float scale, mh_stream_t s);
 /* K14 patch embedding operand (eva_vit.py:196-204): NCHW f32 image -> [B*np, Kpad] bf16 in (c,iy,ix) order */
 int mh_patchify_nchw(const float* img, void* out, int B, int C, int H, int W, int P, int Kpad, mh_stream_t s);
 int mh_scatter_rows_f32(const float* src, const int* rows, float* dst, long ldd, long n, int D, int accumulate,

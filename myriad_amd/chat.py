@@ -317,12 +317,14 @@ class ChatPool(_ChatBase):
     streamed once per step for all of them) and each keeps its KV cache in its own slot across turns, as a `Chat` keeps its
     session's.  The session id is the `Conversation` object; the pool holds it until `close(conv)` frees its slot, and a
     conversation beyond `slots` open ones is a ValueError.  `upload_img` / `ask` are Chat's.  No beam search (decode slots have
-    none), and the step's attention is the single-workgroup rows kernel at every length: a conversation past ~1,024 keys decodes
-    slower here than in a solo Chat, which switches to split-KV."""
+    none).  `split_kv` picks the step's attention kernel (SlotDecoder's argument): False, the default, is the single-workgroup
+    rows kernel at every length; True the split-KV rows kernel, which a few long conversations want (a solo Chat switches to
+    split-KV past ~1,024 keys); None chooses per answer_many call by llama.split_kv_rows_rule.  `last_stats[i]["split_kv"]`
+    reports the choice."""
 
-    def __init__(self, model, slots=8, capacity=2000 + 300 + 2, device=None, vis_processor=None):
+    def __init__(self, model, slots=8, capacity=2000 + 300 + 2, split_kv=False, device=None, vis_processor=None):
         super().__init__(model, vis_processor, model.llama.dev if device is None else device)
-        self.decoder = model.llama.slot_decoder(int(slots), int(capacity))
+        self.decoder = model.llama.slot_decoder(int(slots), int(capacity), split_kv=split_kv)
         self.last_stats = []
 
     def close(self, conv) -> None:
@@ -364,6 +366,6 @@ class ChatPool(_ChatBase):
                                           repetition_penalty=rep, prefill_batch=int(prefill_batch), ordered=True, **kw))
         st = self.decoder.last_stats
         shared = {k: st[k] for k in ("steps", "graph_captures", "graph_replays")}
-        self.last_stats = [dict(t, split_kv=False, **shared) for t in st["turns"]]
+        self.last_stats = [dict(t, split_kv=st["split_kv"], **shared) for t in st["turns"]]
         self.last_token_ids = [ids for _, ids, _ in got]
         return [self._finish_turn(conv, ids.tolist()) for (conv, _), (_, ids, _) in zip(items, got)]

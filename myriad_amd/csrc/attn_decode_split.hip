@@ -11,6 +11,14 @@
 // row pos_dev[0] writes the new cache row [k | v] (bits as mh_attn_decode_rope writes them) and uses its LDS copy of that key
 // and value for its own scores: no workgroup reads a row another one writes in the same launch.  kv_len lives in device memory,
 // so one launch replays from a hipGraph while the context grows; a chunk that starts at or after kv_len[b] exits at once.
+//
+// ROWS (mh_attn_decode_rope_split_rows, the decode slots' form): per-row state as in mh_attn_decode_rope_rows.  Row b appends at
+// cache row pos[b] (its rotary position too) instead of the shared pos_dev[0], and a row with live[b] == 0 is skipped: its chunk
+// workgroups exit before they touch qkv, the cache or the partials, and the merge writes a zero out row without reading a
+// record.  live[b] is uniform over a workgroup, so the exit is a scalar branch.  Everything per (row, head) -- chunking, score
+// and softmax order, the four-wave sum, the in-order merge -- is the ROWS = false code, so a live row has the bits of
+// mh_attn_decode_rope_split at B = 1 on that row with pos_dev[0] = pos[b].  One difference from the non-split rows kernel: that
+// one rotates q in place in qkv, this one leaves qkv alone (nothing downstream reads q after the attention).
 #include "common.h"
 
 #define SPLIT_THREADS 256
@@ -24,6 +32,7 @@ struct SplitParams {
   const int* pos;
   const int* pos_dev;
   const int* kv_len;
+  const int* live;
   const float* cs;
   const float* sn;
   float* part;
@@ -33,7 +42,7 @@ struct SplitParams {
   float scale;
 };
 
-template <int CH>
+template <int CH, bool ROWS>
 __global__ __launch_bounds__(SPLIT_THREADS) void attn_decode_split_kernel(SplitParams p) {
   __shared__ float sc[CH];                 // chunk scores
   __shared__ float po[4][128];             // per-wave partial outputs
@@ -43,10 +52,11 @@ __global__ __launch_bounds__(SPLIT_THREADS) void attn_decode_split_kernel(SplitP
   const int b = bh / p.H, h = bh % p.H;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int D = p.D, W = p.H * D;
+  if (ROWS && p.live[b] == 0) return;              // idle slot: nothing read, nothing written
   int len = p.kv_len[b];
   len = len < p.T_cap ? len : p.T_cap;
   const int j0 = c * CH;
-  const int prow = p.pos_dev[0];
+  const int prow = ROWS ? p.pos[b] : p.pos_dev[0];
   const bool owner = prow >= j0 && prow < j0 + CH && prow < p.T_cap;
   if (j0 >= len && !owner) return;
   const int n = len - j0 < CH ? len - j0 : CH;   // keys of this chunk (<= 0: the owner of a row past kv_len[b])
@@ -176,9 +186,13 @@ __global__ __launch_bounds__(SPLIT_THREADS) void attn_decode_split_kernel(SplitP
 }
 
 // merge the chunks of one (b, h) in chunk order: o = sum_c e^(m_c - M) o_c / sum_c e^(m_c - M) l_c
-template <int CH>
+template <int CH, bool ROWS>
 __global__ __launch_bounds__(64) void attn_decode_combine_kernel(SplitParams p) {
   const int bh = blockIdx.x, b = bh / p.H, h = bh % p.H, lane = threadIdx.x;
+  if (ROWS && p.live[b] == 0) {                    // idle slot: a zero row, no partial record read
+    if (2 * lane < p.D) *reinterpret_cast<unsigned*>(p.out + (size_t)b * p.ldo + h * p.D + 2 * lane) = 0u;
+    return;
+  }
   int len = p.kv_len[b];
   len = len < p.T_cap ? len : p.T_cap;
   const int nc = len > 0 ? (len + CH - 1) / CH : 0;
@@ -210,21 +224,24 @@ extern "C" long mh_attn_decode_split_ws_floats(int B, int H, int T_cap, int chun
   return (long)B * H * ((T_cap + ch - 1) / ch) * SPLIT_PSTRIDE;
 }
 
-template <int CH>
+template <int CH, bool ROWS>
 static int launch_split(const SplitParams& p, hipStream_t s) {
-  hipLaunchKernelGGL(attn_decode_split_kernel<CH>, dim3(p.nch, p.B * p.H), dim3(SPLIT_THREADS), 0, s, p);
+  hipLaunchKernelGGL((attn_decode_split_kernel<CH, ROWS>), dim3(p.nch, p.B * p.H), dim3(SPLIT_THREADS), 0, s, p);
   MH_CHECK_LAUNCH();
-  hipLaunchKernelGGL(attn_decode_combine_kernel<CH>, dim3(p.B * p.H), dim3(64), 0, s, p);
+  hipLaunchKernelGGL((attn_decode_combine_kernel<CH, ROWS>), dim3(p.B * p.H), dim3(64), 0, s, p);
   MH_CHECK_LAUNCH();
   return MH_OK;
 }
 
-extern "C" int mh_attn_decode_rope_split(const void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
-                                         const int* pos_dev, const int* kv_len, const float* cos_tab, const float* sin_tab, void* out,
-                                         long ldo, float* partials, long partials_floats, int B, int H, int D, int T_cap, int chunk,
-                                         float scale, hipStream_t stream) {
+// the two entries: pos_dev (one shared cache row) for ROWS = false, live (per-row state) for ROWS = true
+template <bool ROWS>
+static int split_entry(const void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos, const int* pos_dev,
+                       const int* kv_len, const int* live, const float* cos_tab, const float* sin_tab, void* out, long ldo,
+                       float* partials, long partials_floats, int B, int H, int D, int T_cap, int chunk, float scale,
+                       hipStream_t stream) {
   if (B <= 0) return MH_OK;
-  if (!qkv || !cache || !pos || !pos_dev || !kv_len || !cos_tab || !sin_tab || !out || !partials || H <= 0) return MH_ERR_ARG;
+  if (!qkv || !cache || !pos || !(ROWS ? live : pos_dev) || !kv_len || !cos_tab || !sin_tab || !out || !partials || H <= 0)
+    return MH_ERR_ARG;
   if (D % 8 || D <= 0 || D > 128 || (D >> 1) % 4 || ld_qkv % 8 || ld_cache % 8 || cache_bstride % 8 || ldo % 4 || T_cap <= 0 ||
       T_cap > 8192 || ld_qkv < 3L * H * D || ld_cache < 2L * H * D || ldo < (long)H * D)
     return MH_ERR_ARG;
@@ -233,9 +250,25 @@ extern "C" int mh_attn_decode_rope_split(const void* qkv, long ld_qkv, void* cac
   const int ch = split_chunk(chunk);
   SplitParams p = {};
   p.qkv = (const bf16_t*)qkv; p.ld_qkv = ld_qkv; p.cache = (bf16_t*)cache; p.cache_bs = cache_bstride; p.ld_cache = ld_cache;
-  p.pos = pos; p.pos_dev = pos_dev; p.kv_len = kv_len; p.cs = cos_tab; p.sn = sin_tab; p.part = partials;
+  p.pos = pos; p.pos_dev = pos_dev; p.kv_len = kv_len; p.live = live; p.cs = cos_tab; p.sn = sin_tab; p.part = partials;
   p.out = (bf16_t*)out; p.ldo = ldo; p.B = B; p.H = H; p.D = D; p.T_cap = T_cap; p.nch = (T_cap + ch - 1) / ch; p.scale = scale;
-  if (ch == 256) return launch_split<256>(p, stream);
-  if (ch == 512) return launch_split<512>(p, stream);
-  return launch_split<128>(p, stream);
+  if (ch == 256) return launch_split<256, ROWS>(p, stream);
+  if (ch == 512) return launch_split<512, ROWS>(p, stream);
+  return launch_split<128, ROWS>(p, stream);
+}
+
+extern "C" int mh_attn_decode_rope_split(const void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
+                                         const int* pos_dev, const int* kv_len, const float* cos_tab, const float* sin_tab, void* out,
+                                         long ldo, float* partials, long partials_floats, int B, int H, int D, int T_cap, int chunk,
+                                         float scale, hipStream_t stream) {
+  return split_entry<false>(qkv, ld_qkv, cache, cache_bstride, ld_cache, pos, pos_dev, kv_len, nullptr, cos_tab, sin_tab, out, ldo,
+                            partials, partials_floats, B, H, D, T_cap, chunk, scale, stream);
+}
+
+extern "C" int mh_attn_decode_rope_split_rows(const void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache,
+                                              const int* pos, const int* kv_len, const int* live, const float* cos_tab,
+                                              const float* sin_tab, void* out, long ldo, float* partials, long partials_floats, int B,
+                                              int H, int D, int T_cap, int chunk, float scale, hipStream_t stream) {
+  return split_entry<true>(qkv, ld_qkv, cache, cache_bstride, ld_cache, pos, nullptr, kv_len, live, cos_tab, sin_tab, out, ldo,
+                           partials, partials_floats, B, H, D, T_cap, chunk, scale, stream);
 }

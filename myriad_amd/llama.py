@@ -412,8 +412,9 @@ class LlamaHIP:
         in device memory (`pos_dev`/`kvlen_dev`), which makes the launch sequence replayable from a hipGraph.  `split_ws` (the
         partials buffer of ops.attn_decode_split_ws) makes the fused token step use the split-KV attention kernel.  `live` (int32
         [B] on the device, the slot engine's) makes it the rows kernel instead: every row appends at its own pos[b], idle rows
-        are skipped; only the fused step has that form.  `ragged` = (segment table on the device, its host copy) makes a prefill
-        the packed one (_prefill_packed): B = 1, the S rows hold several requests, `caches` are the whole slot caches, and the
+        are skipped; only the fused step has that form.  Both together: the split-KV kernel in its rows form
+        (ops.attn_decode_rope_split_rows), at 1 to GEMV_WIDE_MAX_ROWS rows alike.
+        `ragged` = (segment table on the device, its host copy) makes a prefill the packed one (_prefill_packed): B = 1, the S rows hold several requests, `caches` are the whole slot caches, and the
         three attention launches become one mh_attn_prefill_ragged (mh_attn_prefill_ragged_past for a table with a fourth column,
         the rows cached already).  `wide` (the slot engine above GEMV_MAX_ROWS slots) keeps the
         token step on the packed copies up to GEMV_WIDE_MAX_ROWS rows: the fused step's launch sequence with
@@ -424,8 +425,8 @@ class LlamaHIP:
         packed = self._packed["layers"] if pos_dev is not None and _packed_step(self, M, wide) else None
         wide = packed is not None and M > ops.GEMV_MAX_ROWS
         gemv = ops.gemv_packed_wide if wide else ops.gemv_packed
-        if live is not None and not (packed is not None and self.decode_fused and split_ws is None):
-            raise ValueError("per-row decode state needs the fused packed token step with the single-workgroup attention")
+        if live is not None and not (packed is not None and self.decode_fused):
+            raise ValueError("per-row decode state needs the fused packed token step")
         # the bordered LoRA product unless the packed qkv copy has the LoRA merged in (decode_merge_lora)
         lora = None if packed is not None and self._packed["qkv_key"] == "merged" else self.lora
 
@@ -455,7 +456,9 @@ class LlamaHIP:
                     qkv = None if wide else ops.gemv_packed_rmsnorm(h, L["ln1"], self.eps, P["wqkv"])
                     if qkv is None:
                         qkv = gemv(ops.rmsnorm_fwd(h, L["ln1"], self.eps), P["wqkv"])
-                if live is not None:
+                if live is not None and split_ws is not None:
+                    o = ops.attn_decode_rope_split_rows(qkv, cache, pos, kvlen_dev, live, self.cos, self.sin, H, hd, scale, split_ws)
+                elif live is not None:
                     o = ops.attn_decode_rope_rows(qkv, cache, pos, kvlen_dev, live, self.cos, self.sin, H, hd, scale)
                 elif split_ws is not None:
                     o = ops.attn_decode_rope_split(qkv, cache, pos, pos_dev, kvlen_dev, self.cos, self.sin, H, hd, scale, split_ws)
@@ -875,10 +878,11 @@ class LlamaHIP:
         stats.update(sequences_scores=scores, finished_hypotheses=int(is_fin.sum()), lengths=[len(q) for q in seqs])
         return (ids, scores) if return_scores else ids
 
-    def slot_decoder(self, slots: int, capacity: int) -> "SlotDecoder":
+    def slot_decoder(self, slots: int, capacity: int, split_kv: Optional[bool] = False) -> "SlotDecoder":
         """A decode-slot engine over this model: `slots` rows of one captured token step, each decoding its own request of up to
-        `capacity` positions (prompt + generated).  See SlotDecoder."""
-        return SlotDecoder(self, slots, capacity)
+        `capacity` positions (prompt + generated).  `split_kv`: the step's attention kernel (False: the single-workgroup rows
+        kernel, True: the split-KV rows kernel, None: split_kv_rows_rule per call).  See SlotDecoder."""
+        return SlotDecoder(self, slots, capacity, split_kv=split_kv)
 
     def embed_tokens_into(self, ids: torch.Tensor, out2d: torch.Tensor, dst_rows: Optional[torch.Tensor] = None):
         ops.embed_gather(self.embed, ids, out2d, dst_rows)
@@ -959,6 +963,21 @@ SPLIT_KV_MIN_KEYS = 1024
 
 def split_kv_rule(B: int, H: int, kv_len: int) -> bool:
     return B * H < SPLIT_KV_MAX_ROWHEADS and kv_len >= SPLIT_KV_MIN_KEYS
+
+
+# The slot engine's form of the rule (SlotDecoder(split_kv=None)): `live_rows` conversations decode in one call, the longest has
+# `max_kv_len` keys when it is admitted.  It says yes only where the split rows kernel was measured faster than the single-workgroup
+# rows kernel on the full-size model (tools/chat_bench.py --pool-split, DESIGN.md section 5, "Chat pool"; ms per token step,
+# split_kv False / True, both pools interleaved in one process): N = 1: 3.390 / 3.218 at 1,136 keys, 3.961 / 3.463 at 2,160;
+# N = 2: 3.688 / 3.578 and 4.235 / 3.875; N = 4: 3.982 / 3.987 and 4.562 / 4.619 -- at 128 row-heads the split kernel no longer
+# wins.  So: at most 64 row-heads (the largest product at which split won) and at least 1,024 keys (the shortest context at which
+# it won; the section 5 table says what was measured below that).
+SPLIT_KV_ROWS_MAX_ROWHEADS = 64
+SPLIT_KV_ROWS_MIN_KEYS = 1024
+
+
+def split_kv_rows_rule(live_rows: int, H: int, max_kv_len: int) -> bool:
+    return live_rows * H <= SPLIT_KV_ROWS_MAX_ROWHEADS and max_kv_len >= SPLIT_KV_ROWS_MIN_KEYS
 
 
 def common_prefix(a, b) -> int:
@@ -1398,7 +1417,10 @@ class SlotDecoder:
     rows carry the 16-row kernel's bits: a request's ids and margins do not depend on the slot count.
     The step is greedy_generate's fused packed step (bf16 / FP8 / MXFP4 copies, merged or bordered LoRA alike) with two launches
     swapped: the attention is mh_attn_decode_rope_rows (row b appends at pos[b], idle rows skipped) and the bookkeeping is
-    mh_decode_advance_rows (idle rows record id -1).  A refill is the existing B = 1 prefill into the slot's slice of every cache.
+    mh_decode_advance_rows (idle rows record id -1).  `split_kv` (opt-in) swaps the attention for the split-KV kernel's rows
+    form, mh_attn_decode_rope_split_rows -- the solo chat session's kernel for long contexts, a live row has its bits: False
+    (default) never, True always, None by split_kv_rows_rule once per run / run_turns call.  Each kernel has its own views and
+    captured graphs, so toggling evicts nothing.  A refill is the existing B = 1 prefill into the slot's slice of every cache.
     Between two replays the host writes only a finished slot's live flag, a refilled slot's (id, pos, kvlen, live) and a host
     draw's id.  greedy_generate and its row-0 rule are untouched; this path is opt-in.
 
@@ -1421,10 +1443,13 @@ class SlotDecoder:
     mh_attn_prefill_ragged_past per layer -- and then decodes in the same captured step as `run`.  `run` itself starts every slot
     at row 0, so it drops what the sessions had cached."""
 
-    def __init__(self, llama: "LlamaHIP", slots: int, capacity: int):
+    def __init__(self, llama: "LlamaHIP", slots: int, capacity: int, split_kv: Optional[bool] = False):
         slots = int(slots)
         if slots < 1 or slots > ops.GEMV_WIDE_MAX_ROWS:
             raise ValueError(f"slots={slots}: the slot engine runs the packed token step, 1 to {ops.GEMV_WIDE_MAX_ROWS} rows")
+        if split_kv is not None and not isinstance(split_kv, bool):
+            raise ValueError(f"split_kv={split_kv!r}: False (the single-workgroup rows kernel), True (split-KV) or None (the rule)")
+        self.split_kv = split_kv
         self.llama, self.slots = llama, slots
         self.T_cap = ops.round_up(int(capacity), 64)
         if not 0 < self.T_cap <= 8192:
@@ -1441,13 +1466,23 @@ class SlotDecoder:
         """Free the slot of a run_turns session."""
         self.sessions.close(session)
 
-    def _workspace(self, inv_temp: float, rows_tail=None) -> dict:
+    @staticmethod
+    def _view_key(inv_temp: float, rows_tail=None, split: bool = False):
+        """The key of a view (one captured graph each).  Without split-KV it is what it was before the engine had the choice --
+        inv_temp, or (inv_temp or None, device-sampled, penalty) for the per-row tail -- and a split view is ("split", that)."""
+        key = float(inv_temp)
+        if rows_tail is not None:
+            key = (None if rows_tail[0] else key, bool(rows_tail[0]), bool(rows_tail[1]))
+        return ("split", key) if split else key
+
+    def _workspace(self, inv_temp: float, rows_tail=None, split: bool = False) -> dict:
         """The step's buffers, kept while the decode weights stay the ones the captured graphs read, and over them one view (its
         own graph / warm flag) per inv_temp: the arg-max kernel takes inv_temp as a launch argument, so a captured step is fixed
         to one value (LlamaHIP._decode_workspace keys its workspaces the same way).  `rows_tail` = (device-sampled, penalty) asks
         for the step with the per-row tail: its buffers join on first use (the knobs `prm`, per-slot `seed` / `gen` / `kept` /
         `seen`, and `seed0` / `gen0` for the refills' first picks), and a device-sampled view is keyed without inv_temp, which the
-        sampler reads from `prm`."""
+        sampler reads from `prm`.  `split`: the view's step runs the split-KV rows kernel; the partials buffer joins on first use,
+        a split view holds it and a non-split view holds None, so each (key, split) has its own graph."""
         L = self.llama
         L._prepare_decode_weights(self.slots, wide=True)
         if not (_packed_step(L, self.slots, True) and L.decode_fused):
@@ -1459,7 +1494,9 @@ class SlotDecoder:
             self.bufs["live"] = torch.zeros((self.slots,), dtype=torch.int32, device=L.dev)
             self.bufs["wide"] = True                                 # above GEMV_MAX_ROWS slots the step stays on the packed copies
             self._weights = wid
-        key = float(inv_temp)
+        key = self._view_key(inv_temp, rows_tail, split)
+        if split and self.bufs["split"] is None:
+            self.bufs["split"] = ops.attn_decode_split_ws(self.slots, L.H, self.T_cap, L.dev)
         if rows_tail is not None:
             if "prm" not in self.bufs:
                 n, i32 = self.slots, torch.int32
@@ -1467,11 +1504,11 @@ class SlotDecoder:
                                  seed0=torch.zeros((n,), dtype=torch.long, device=L.dev), gen=torch.zeros((n,), dtype=i32, device=L.dev),
                                  gen0=torch.zeros((n,), dtype=i32, device=L.dev), kept=torch.zeros((n,), dtype=i32, device=L.dev),
                                  seen=torch.zeros((n, (L.V + 31) // 32), dtype=i32, device=L.dev))
-            key = (None if rows_tail[0] else key, bool(rows_tail[0]), bool(rows_tail[1]))
         if key not in self.views:
-            if len(self.views) >= 4:                                 # a few temperatures at most: drop the oldest graph
-                self.views.pop(next(iter(self.views)))
-            self.views[key] = dict(self.bufs, graph=None, warm=False)
+            same = [k for k in self.views if (isinstance(k, tuple) and k[0] == "split") == bool(split)]
+            if len(same) >= 4:                                       # a few temperatures at most per kernel: drop its oldest graph
+                self.views.pop(same[0])
+            self.views[key] = dict(self.bufs, graph=None, warm=False, split=self.bufs["split"] if split else None)
         self.ws = self.views[key]
         return self.ws
 
@@ -1491,7 +1528,9 @@ class SlotDecoder:
         of it is Philox step t -- what greedy_generate draws for that request alone with that seed.  `device_sampled_rows`
         counts those picks; a row the sampler hands back (kept = -1) is drawn on the host from a generator derived from the
         request's seed and t (`host_sampled_rows`).  `repetition_penalty` != 1 needs the switch, as in generate(); `min_length`
-        is a per-request EOS ban on every path.  A second run with other values of the knobs replays the same graph."""
+        is a per-request EOS ban on every path.  A second run with other values of the knobs replays the same graph.
+        `last_stats["split_kv"]`: the attention kernel of the call's token steps.  With the decoder's split_kv=None the rule sees
+        `slots` live rows and a longest context of 0 -- the lengths are not known up front -- so None never splits here."""
         self.sessions.clear()                                        # the slots' caches are overwritten from row 0
         yield from self._run(requests, None, None, max_new_tokens, stop_ids, eos_id, min_length, do_sample, top_p, temperature,
                              top_k, generator, ordered, prefill_batch, refill_min, prefill_rows, repetition_penalty, seeds)
@@ -1508,7 +1547,8 @@ class SlotDecoder:
         margins) as `run` does, `ordered=True` in the list's order; `last_stats["turns"]` holds per turn `context_tokens`,
         `reused_tokens`, `prefilled_tokens` and `full_reprefill_reason`.  `weights_version`: anything that changes when the
         weights do; with it, a change of the decode weights or a `run()` on this decoder drops every session's cached rows.  The
-        step's attention is the single-workgroup rows kernel at every context length (no split-KV)."""
+        step's attention kernel is the decoder's `split_kv` choice, made once per call (`last_stats["split_kv"]`): with None,
+        split_kv_rows_rule(turns in the call, heads, the longest context at admission)."""
         turns = [tuple(t) for t in turns]
         if "refill_min" in kw:
             raise ValueError("run_turns: refill_min does not apply, every turn has its own slot")
@@ -1541,10 +1581,16 @@ class SlotDecoder:
         if seeds is not None and not dev_sample:
             raise ValueError("seeds= names the device sampler's per-request streams: it needs do_sample with device_sampling on")
         rows_tail = dev_sample or penalty or min_length > 1          # else exactly the launches of the plain slot step
-        ws = self._workspace(inv_temp, (dev_sample, penalty) if rows_tail else None)
+        # the attention kernel of every token step of this call, chosen once: `run` does not know its lengths up front
+        if self.split_kv is None:
+            split = split_kv_rows_rule(self.slots, L.H, 0) if turns is None else \
+                split_kv_rows_rule(len(turns), L.H, max([int(t[1].shape[0]) for t in turns], default=0))
+        else:
+            split = self.split_kv
+        ws = self._workspace(inv_temp, (dev_sample, penalty) if rows_tail else None, split)
         sched = SlotScheduler(self.slots, max_new_tokens, stop_ids, eos_id, ordered=ordered)
         stats = dict(steps=0, graph_replays=0, graph_captures=self.graph_captures, prefills=0, live_row_steps=0, occupancy=0.0,
-                     host_sampled_rows=0, device_sampled_rows=0, prefill_passes=0, packed_rows=0)
+                     host_sampled_rows=0, device_sampled_rows=0, prefill_passes=0, packed_rows=0, split_kv=bool(split))
         packed = int(prefill_batch) != 1 or int(refill_min) != 1
         # a request travels with the seed of its own stream (None unless the device draws)
         if turns is None:

@@ -530,6 +530,31 @@ def attn_decode_rope_split(qkv2d: torch.Tensor, cache: torch.Tensor, pos: torch.
     return out
 
 
+def attn_decode_rope_split_rows(qkv2d: torch.Tensor, cache: torch.Tensor, pos: torch.Tensor, kv_len: torch.Tensor, live: torch.Tensor,
+                                cos_tab: torch.Tensor, sin_tab: torch.Tensor, n_heads: int, head_dim: int, scale: float,
+                                partials: torch.Tensor, chunk: int = SPLIT_KV_CHUNK, out: Optional[torch.Tensor] = None):
+    """attn_decode_rope_split with per-row state (decode slots): row b rotates and appends at pos[b], sees kv_len[b] keys; a row
+    with live[b] == 0 (int32 [B]) touches neither qkv2d, the cache nor the partials and gets a zero row of o.  A live row has the
+    bits of attn_decode_rope_split at B = 1 on that row.  qkv2d is read only (attn_decode_rope_rows rotates q in place, this
+    does not).  partials: attn_decode_split_ws()."""
+    _chk2d(qkv2d, BF16, "attn_decode_rope_split_rows.qkv")
+    B, W = qkv2d.shape[0], n_heads * head_dim
+    if qkv2d.shape[1] < 3 * W or cache.shape[2] != 2 * W or cache.shape[0] != B:
+        raise _lib.MyriadHipError("attn_decode_rope_split_rows: qkv must be [B, >=3W] and cache [B, T, 2W]")
+    for name, t in (("pos", pos), ("kv_len", kv_len), ("live", live)):
+        if t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous():
+            raise _lib.MyriadHipError(f"attn_decode_rope_split_rows: {name} must be a contiguous int32 [B]")
+    if partials.dtype != F32 or not partials.is_contiguous():
+        raise _lib.MyriadHipError("attn_decode_rope_split_rows: partials must be a contiguous f32 buffer")
+    if out is None:
+        out = torch.empty((B, W), dtype=BF16, device=qkv2d.device)
+    _lib.check(_L().mh_attn_decode_rope_split_rows(_p(qkv2d), qkv2d.stride(0), _p(cache), cache.stride(0), cache.stride(1), _p(pos),
+                                                   _p(kv_len), _p(live), _p(cos_tab), _p(sin_tab), _p(out), out.stride(0),
+                                                   _p(partials), partials.numel(), B, n_heads, head_dim, cache.shape[1], int(chunk),
+                                                   float(scale), _s()), "mh_attn_decode_rope_split_rows")
+    return out
+
+
 def gemm_auto_f32(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     """f32 out = a @ b^T, choosing split-K when the output is small and the reduction long (wgrad shapes)."""
     M, K = a.shape

@@ -12,9 +12,15 @@
   * --pool N[,N...]: N conversations of 3 turns each (a context of --pool-context keys, then per turn the answer of --tokens
     tokens and a 24-token question) through SlotDecoder.run_turns on N slots -- what ChatPool.answer_many runs -- against the same
     turns through N DecodeSessions one after the other -- what N Chat objects run; tokenising and image encoding are the same on
-    both sides and left out.  The two are interleaved per repeat; wall ms per turn, median of --repeats with min and max.
+    both sides and left out.  The two are interleaved per repeat; wall ms per turn, median of --repeats with min and max;
+  * --pool-split: the --pool protocol on two SlotDecoders, split_kv=False (the single-workgroup rows kernel) and split_kv=True
+    (mh_attn_decode_rope_split_rows), interleaved per repeat in one process, for N in --pool (default 1,2,4,7,8) and first
+    contexts in --pool-contexts (default 512,1024,2048,4096): wall ms per turn and ms per token step -- (a turn of --tokens + 1
+    tokens) - (a turn of 1 token) on the cached third context --, median of --repeats (default 5 here) with min and max.  Before
+    it, the two attention launches alone (32 launches = one token's layers, from a graph) at R = 1, 4, 8 live rows on 1,024 /
+    4,096 cached keys.
 
-python tools/chat_bench.py [--layers 32] [--tokens 32] [--repeats 3] [--chunks] [--ragged-past] [--pool 1,4,8,16]
+python tools/chat_bench.py [--layers 32] [--tokens 32] [--repeats 3] [--chunks] [--ragged-past] [--pool 1,4,8,16] [--pool-split]
 -> one JSON line per measurement"""
 import argparse
 import json
@@ -33,14 +39,20 @@ from myriad_amd.synthetic import SyntheticWeights, full_config  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--layers", type=int, default=32)
 ap.add_argument("--tokens", type=int, default=32, help="timed token steps per measurement")
-ap.add_argument("--repeats", type=int, default=3)
+ap.add_argument("--repeats", type=int, default=None, help="default 3, 5 with --pool-split")
 ap.add_argument("--contexts", default="256,1024,2048")
 ap.add_argument("--chunks", action="store_true", help="also time the attention launch alone per chunk size")
 ap.add_argument("--skip-model", action="store_true", help="only the --chunks / --ragged-past launch timings")
 ap.add_argument("--ragged-past", action="store_true", help="time mh_attn_prefill_ragged_past against the launches it replaces")
 ap.add_argument("--pool", default="", help="conversation counts for the pool-against-sequential-sessions comparison")
 ap.add_argument("--pool-context", type=int, default=256, help="keys of a conversation's first context")
+ap.add_argument("--pool-split", action="store_true", help="the pool with split_kv=False against split_kv=True")
+ap.add_argument("--pool-contexts", default="512,1024,2048,4096", help="first contexts of the --pool-split comparison")
 a = ap.parse_args()
+if a.repeats is None:
+    a.repeats = 5 if a.pool_split else 3
+if a.pool_split and not a.pool:
+    a.pool = "1,2,4,7,8"
 dev = "cuda:0"
 torch.manual_seed(0)
 
@@ -133,15 +145,67 @@ def ragged_past_bench():
                  min=round(min(ts), 1), max=round(max(ts), 1))
 
 
-if a.chunks or (a.skip_model and not a.ragged_past):
+def rows_bench():
+    """mh_attn_decode_rope_rows against mh_attn_decode_rope_split_rows, R live rows of kv cached keys each."""
+    H, D = 32, 128
+    W = H * D
+    for kv in (1024, 4096):
+        T = kv + 64
+        fr = torch.arange(T).float()[:, None] * (1.0 / (10000.0 ** (torch.arange(0, D, 2).float() / D)))[None]
+        cos, sin = fr.cos().contiguous().to(dev), fr.sin().contiguous().to(dev)
+        for R in (1, 4, 8):
+            cache = (torch.randn((R, T, 2 * W), device=dev) * 0.5).to(torch.bfloat16)
+            qkv = (torch.randn((R, 3 * W), device=dev) * 0.5).to(torch.bfloat16)
+            work = qkv.clone()
+            pos = torch.full((R,), kv - 1, dtype=torch.int32, device=dev)
+            kvl = torch.full((R,), kv, dtype=torch.int32, device=dev)
+            live = torch.ones((R,), dtype=torch.int32, device=dev)
+            part = ops.attn_decode_split_ws(R, H, T, dev)
+            out = torch.empty((R, W), dtype=torch.bfloat16, device=dev)
+            res = {}
+            for name in ("rows", "split_rows"):
+                def one():
+                    for _ in range(32):
+                        if name == "rows":                           # rotates q in place: a scratch copy, the values do not matter
+                            ops.attn_decode_rope_rows(work, cache, pos, kvl, live, cos, sin, H, D, 1.0 / D ** 0.5)
+                        else:
+                            ops.attn_decode_rope_split_rows(qkv, cache, pos, kvl, live, cos, sin, H, D, 1.0 / D ** 0.5, part, out=out)
+                one()
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    one()
+                ts = []
+                for _ in range(5):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    g.replay()
+                    e0.record()
+                    for _ in range(20):
+                        g.replay()
+                    e1.record()
+                    e1.synchronize()
+                    ts.append(e0.elapsed_time(e1) / 20 / 32 * 1000.0)
+                emit(what="attn_rows_launch_us", kernel=name, rows=R, kv=kv, us_per_layer=round(statistics.median(ts), 2),
+                     min=round(min(ts), 2), max=round(max(ts), 2))
+                del g
+            del cache, part
+            torch.cuda.empty_cache()
+
+
+if a.chunks or (a.skip_model and not a.ragged_past and not a.pool_split):
     chunk_bench()
+if a.pool_split:
+    rows_bench()
 if a.ragged_past:
     ragged_past_bench()
 if a.skip_model:
     sys.exit(0)
 
 cfg = full_config(llm_layers=a.layers)
-llama = LlamaHIP(SyntheticWeights(cfg, dev, seed=0), cfg["llm_heads"], dev, need_backward=False, max_pos=4096)
+max_pos = 4096
+if a.pool_split:                                                     # the rotary table covers the longest conversation
+    max_pos = max(4096, 256 + max(int(x) for x in a.pool_contexts.split(",")) + 3 * (a.tokens + 24) + 2)
+llama = LlamaHIP(SyntheticWeights(cfg, dev, seed=0), cfg["llm_heads"], dev, need_backward=False, max_pos=max_pos)
 D = llama.D
 gen = torch.Generator().manual_seed(1)
 
@@ -200,6 +264,63 @@ def pool_bench(N):
     del dec, sess
     torch.cuda.empty_cache()
 
+
+def pool_split_bench(N, context):
+    """3 turns of N conversations through run_turns on two decoders of N slots, split_kv False and True, interleaved per repeat;
+    then, on the cached third context, (a turn of n_new + 1 tokens) - (a turn of 1 token): both prefill one row."""
+    n_new, Q = a.tokens, 24
+    kw = dict(stop_ids=(), eos_id=-1, min_length=0, weights_version=0, prefill_batch=8)
+    cap = context + 3 * (n_new + Q) + n_new + 4
+    decs = {mode: llama.slot_decoder(N, cap, split_kv=mode) for mode in (False, True)}
+    turn_ms = {mode: [[], [], []] for mode in decs}
+    step_ms = {mode: [] for mode in decs}
+
+    def timed(dec, turns, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        got = {c: ids for c, ids, _ in dec.run_turns(turns, max_new_tokens=n, **kw)}
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1000.0, got
+
+    for r in range(a.repeats + 1):                                   # repeat 0 warms both sides up (graph captures)
+        first = [ctx(context, 1000 * N + 10 * c + r) for c in range(N)]
+        for mode, dec in decs.items():
+            state = [(e[0], list(k)) for e, k in first]
+            for t in range(3):
+                reset = ("bench",) if t == 0 else ()                 # a new conversation: nothing of the last repeat is reused
+                ms, got = timed(dec, [(c, e, k) + reset for c, (e, k) in enumerate(state)], n_new)
+                assert dec.last_stats["split_kv"] is mode
+                if r:
+                    turn_ms[mode][t].append(ms)
+                if t < 2:
+                    for c, (e, k) in enumerate(state):
+                        q_emb, q_keys = ctx(Q, 7000 + 100 * c + 10 * t + r)
+                        state[c] = (torch.cat([e, llama.embed[got[c].to(dev)].float(), q_emb[0]], 0).contiguous(),
+                                    k + [("t", int(i)) for i in got[c]] + q_keys)
+            turns = [(c, e, k) for c, (e, k) in enumerate(state)]    # the third context again: cached, one row prefilled
+            t_one, _ = timed(dec, turns, 1)
+            t_long, _ = timed(dec, turns, n_new + 1)
+            assert all(s["prefilled_tokens"] == 1 for s in dec.last_stats["turns"])
+            if r:
+                step_ms[mode].append((t_long - t_one) / n_new)
+    keys3 = state[0][0].shape[0]
+    for mode in decs:
+        for t in range(3):
+            ts = turn_ms[mode][t]
+            emit(what="pool_split_turn_ms", split_kv=mode, conversations=N, turn=t + 1, first_context=context, tokens=n_new,
+                 ms=round(statistics.median(ts), 2), min=round(min(ts), 2), max=round(max(ts), 2))
+        ts = step_ms[mode]
+        emit(what="pool_split_step_ms", split_kv=mode, conversations=N, first_context=context, keys=keys3, tokens=n_new,
+             ms=round(statistics.median(ts), 3), min=round(min(ts), 3), max=round(max(ts), 3))
+    del decs
+    torch.cuda.empty_cache()
+
+
+if a.pool_split:
+    for context in [int(x) for x in a.pool_contexts.split(",")]:
+        for N in [int(x) for x in a.pool.split(",")]:
+            pool_split_bench(N, context)
+    sys.exit(0)
 
 if a.pool:
     for N in [int(x) for x in a.pool.split(",")]:
