@@ -16,13 +16,13 @@ front-end (Resize(224, bicubic) + CenterCrop(224) + CLIP normalisation, what the
 `vis_processor` is given.  `answer` also takes `do_sample` and `generator` (the reference always samples), and returns
 `(text, token_ids)` like the reference.
 
-Reuse.  Each `Chat` owns a `myriad_amd.llama.DecodeSession`: turn n prefills only the part of the context past the longest common prefix
+Reuse.  Each `Chat` owns a `myriad_amd.decode.DecodeSession`: turn n prefills only the part of the context past the longest common prefix
 with what the cache holds (positions named by token ids and (image, row) keys), then decodes on the session's own buffers and
 captured graph.  `Chat.last_stats` reports what a turn reused.  The session uses the split-KV decode attention kernel where it is
-measured faster (llama.split_kv_rule).  `num_beams > 1` runs the model's beam search (LlamaHIP.beam_generate) on the full context
+measured faster (decode_host.split_kv_rule).  `num_beams > 1` runs the model's beam search (LlamaHIP.beam_generate) on the full context
 without reuse (deterministic: `do_sample` does not apply to it), and leaves the session's cache as it was.
 
-Several conversations at once.  `ChatPool` serves up to `slots` conversations on the decode slots (llama.SlotDecoder.run_turns):
+Several conversations at once.  `ChatPool` serves up to `slots` conversations on the decode slots (decode.SlotDecoder.run_turns):
 one captured token step for all of them, each conversation's KV cache kept in its own slot across turns, a turn's new rows
 prefilled on top of the reused prefix -- several conversations per pass over the weights.  `answer_many` does per conversation
 what `Chat.answer` does; both classes share the conversation side (`_ChatBase`).
@@ -39,7 +39,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .llama import DecodeSession
+from .decode import DecodeSession
 from .myriad import StoppingCriteriaSub
 
 __all__ = ["SeparatorStyle", "Conversation", "CONV_VISION", "StoppingCriteriaSub", "Chat", "ChatPool", "truncation_begin",
@@ -319,7 +319,7 @@ class ChatPool(_ChatBase):
     conversation beyond `slots` open ones is a ValueError.  `upload_img` / `ask` are Chat's.  No beam search (decode slots have
     none).  `split_kv` picks the step's attention kernel (SlotDecoder's argument): False, the default, is the single-workgroup
     rows kernel at every length; True the split-KV rows kernel, which a few long conversations want (a solo Chat switches to
-    split-KV past ~1,024 keys); None chooses per answer_many call by llama.split_kv_rows_rule.  `last_stats[i]["split_kv"]`
+    split-KV past ~1,024 keys); None chooses per answer_many call by decode_host.split_kv_rows_rule.  `last_stats[i]["split_kv"]`
     reports the choice."""
 
     def __init__(self, model, slots=8, capacity=2000 + 300 + 2, split_kv=False, device=None, vis_processor=None):

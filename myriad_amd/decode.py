@@ -1,0 +1,1036 @@
+"""KV-cache decode on the HIP kernels: the prefills and the single-token step of the LLaMA decoder, the greedy and beam loops
+(LlamaDecode, the mixin LlamaHIP inherits), the multi-turn chat's DecodeSession and the decode-slot engine SlotDecoder.  The
+weights, their packed decode copies and the training path are myriad_amd/llama.py's; what never sees a device is
+myriad_amd/decode_host.py's."""
+from __future__ import annotations
+
+import math
+from typing import List, Optional
+
+import numpy as np
+import torch
+
+from . import ops
+from .decode_host import (RefillPlanner, SessionTable, SlotScheduler, TurnPlanner, _host_draw, _request_generator, common_prefix,
+                          seeded_requests, split_kv_rows_rule, split_kv_rule)
+
+BF16, F32 = torch.bfloat16, torch.float32
+
+
+# Decode helpers shared by LlamaHIP and DecodeSession.  They read only the model's fields, so the session needs no more of the
+# model than those.
+def _packed_step(lm: "LlamaHIP", rows: int, row_limit: int = ops.GEMV_MAX_ROWS) -> bool:
+    """The token step at `rows` rows streams the packed copies.  `row_limit` is the caller's: GEMV_MAX_ROWS (what ops.gemv_packed
+    takes) for every decode loop, so their routing above it is the row-major GEMM; GEMV_WIDE_MAX_ROWS for the slot engine, which
+    stays on the copies up to there (ops.gemv_packed_wide)."""
+    return lm._packed is not None and rows <= row_limit
+
+
+def _wide_step(lm: "LlamaHIP", rows: int, row_limit: int) -> bool:
+    """The packed token step above GEMV_MAX_ROWS rows (the slot engine's, whose row limit lets it be): the fused step's launch
+    sequence with ops.gemv_packed_wide as the product and the two-launch forms of the norm / SiLU products, as at 3 to 16 rows."""
+    return _packed_step(lm, rows, row_limit) and rows > ops.GEMV_MAX_ROWS
+
+
+def _decode_weights_id(lm: "LlamaHIP") -> tuple:
+    """What the token step multiplies by: the packed copies (which object, its kind, which qkv copy is live), the fused
+    launches and the LoRA.  The workspace key holds it, so no graph captured on one set of weights is replayed on another."""
+    P = lm._packed
+    return id(P), None if P is None else (P["kind"], P["qkv_key"]), lm.decode_fused, lm.lora is not None
+
+
+def _decode_buffers(lm: "LlamaHIP", B: int, T_cap: int, sampler: bool = False, num_beams: int = 1,
+                    row_limit: int = ops.GEMV_MAX_ROWS) -> dict:
+    """Buffers of the single-token step at B rows: KV caches of T_cap positions, device-resident counters, id / logit /
+    result buffers and the [4, B] per-step record (the arg-max step writes its first three rows); `graph` / `warm` hold the
+    captured step once there is one (_launch_step), `split` the split-KV partials when the step uses them, `row_limit` the rows
+    up to which the step stays on the packed copies (_packed_step).  With `sampler`
+    the device sampler's and the repetition penalty's buffers join: their knobs (`prm` = inv_temp, top_p, top_k, penalty),
+    the seed, the kept counts and the seen-id bitmaps.  With num_beams > 1, B counts rows (items x beams) and the beam step's
+    buffers join: `bupd` = the per-step upload (ids int64 | parent rows int32 | running scores f32) and its pinned host twin,
+    the top-K scratch and record, and the device table of the per-layer cache pointers that mh_beam_reorder_kv walks."""
+    dev, i32 = lm.dev, torch.int32
+    ws = dict(T=T_cap, graph=None, warm=False, split=None, row_limit=row_limit,
+              caches=[torch.zeros((B, T_cap, 2 * lm.D), dtype=BF16, device=dev) for _ in lm.layers],
+              pos=torch.zeros((B,), dtype=i32, device=dev), kvlen=torch.zeros((B,), dtype=i32, device=dev),
+              ids=torch.zeros((B,), dtype=torch.long, device=dev), x_in=torch.empty((B, lm.D), dtype=F32, device=dev),
+              logits=torch.empty((B, lm.V), dtype=F32, device=dev),
+              nxt=torch.empty((B,), dtype=torch.long, device=dev), mar=torch.empty((B,), dtype=F32, device=dev),
+              pmx=torch.empty((B,), dtype=F32, device=dev), step=torch.zeros((1,), dtype=i32, device=dev),
+              rec=torch.zeros((4, B), dtype=F32, device=dev))
+    if sampler:
+        ws.update(prm=torch.zeros((4,), dtype=F32, device=dev), seed=torch.zeros((1,), dtype=torch.long, device=dev),
+                  kept=torch.zeros((B,), dtype=i32, device=dev),
+                  seen=torch.zeros((B, (lm.V + 31) // 32), dtype=i32, device=dev))
+    if num_beams > 1:
+        nb, K = int(num_beams), 2 * int(num_beams)
+        bupd = torch.zeros((4 * B,), dtype=i32, device=dev)
+        ws.update(bupd=bupd, bupd_host=torch.zeros((4 * B,), dtype=i32).pin_memory(),
+                  ids=bupd[:2 * B].view(torch.long), src=bupd[2 * B:3 * B], bscore=bupd[3 * B:].view(F32),
+                  part_s=torch.empty((B * K,), dtype=F32, device=dev), part_i=torch.empty((B * K,), dtype=i32, device=dev),
+                  brec=torch.zeros((2, B // nb * K), dtype=i32, device=dev), lo=torch.zeros((1,), dtype=i32, device=dev),
+                  table=torch.tensor([c.data_ptr() for c in ws["caches"]], dtype=torch.long).to(dev))
+    return ws
+
+
+def _cache_stamp(lm: "LlamaHIP", weights_version) -> tuple:
+    """What cached KV rows depend on: the caller's weights version and the weights the step multiplies by.  The merged qkv copy is
+    rewritten in place by a re-merge: its merge id joins the stamp, so no KV row survives a change of the weights the step
+    multiplies by, whether or not the caller's weights_version saw it."""
+    P = lm._packed
+    return weights_version, _decode_weights_id(lm), P["merge_id"] if P is not None and P["qkv_key"] == "merged" else None
+
+
+def _sampling_args(lm: "LlamaHIP", do_sample: bool = False, temperature: float = 1.0, top_k=50, repetition_penalty: float = 1.0,
+                   **_others):
+    """The decode loops' checks of their sampling arguments (greedy_generate's, with its defaults; its other arguments pass
+    through unread) and what they derive from them: (inv_temp, top_k, dev_sample -- the device draws inside the token step --,
+    penalty -- the repetition penalty is on)."""
+    if do_sample and not float(temperature) > 0:
+        raise ValueError(f"temperature must be > 0 when sampling, got {temperature}")
+    if not float(repetition_penalty) > 0:
+        raise ValueError(f"repetition_penalty must be > 0, got {repetition_penalty}")
+    top_k = 0 if top_k is None else int(top_k)
+    dev_sample = bool(do_sample and lm.device_sampling and 1 <= top_k <= ops.SAMPLE_CAP and lm.V <= 32768 and lm.V % 4 == 0)
+    return 1.0 / float(temperature) if do_sample else 1.0, top_k, dev_sample, float(repetition_penalty) != 1.0
+
+
+def _buffer_view(lm: "LlamaHIP", bufs: dict, split: bool) -> dict:
+    """A workspace view of a buffer set: the buffers with a graph / warm flag of its own.  `split`: the view's step runs a split-KV
+    attention kernel; the partials buffer joins the set on first use, a split view holds it and a non-split view holds None."""
+    if split and bufs["split"] is None:
+        bufs["split"] = ops.attn_decode_split_ws(bufs["ids"].shape[0], lm.H, bufs["T"], lm.dev)
+    return dict(bufs, graph=None, warm=False, split=bufs["split"] if split else None)
+
+
+class LlamaDecode:
+    """The decode methods of LlamaHIP (myriad_amd/llama.py), which holds the weights and their packed copies they read."""
+
+    # ------------------------------------------------------------------ generation
+    def _gemm_lin(self, li: int, name: str, x, **kw):
+        return ops.gemm(x, self.layers[li][name], **kw)
+
+    def _lora_operand(self, lora, li: int, h, fused: bool):
+        """The bordered operand [xn | s A xn] of layer li's qkv product with LoRA attached.  `fused`: the norm and the LoRA down
+        projection are one launch where that form exists (LoraQV.norm_border, <= 2 rows)."""
+        L, x_ext = self.layers[li], lora.x_ext(li, h.shape[0])
+        if not (fused and lora.norm_border(li, h, L["ln1"], self.eps, x_ext)):
+            ops.rmsnorm_fwd(h, L["ln1"], self.eps, out=x_ext[:, :self.D])
+            lora.forward_border(li, x_ext, training=False)
+        return x_ext
+
+    def _decode_layers(self, h, lin, attention, lora):
+        """All decoder layers on [M, D] f32 rows, every launch of its own: norm, qkv product (the bordered one with `lora`),
+        `attention(li, qkv)` -> [.., D] bf16, o_proj with the residual, norm, gate|up, SiLU, down.  `lin(li, name, x, **kw)` is the
+        caller's product with layer li's matrix `name`.  The prefills and the unfused token step are this with their own attention."""
+        M = h.shape[0]
+        for li, L in enumerate(self.layers):
+            if lora is None:
+                qkv = lin(li, "wqkv", ops.rmsnorm_fwd(h, L["ln1"], self.eps))
+            else:
+                qkv = lin(li, "wqkv_ext", self._lora_operand(lora, li, h, False))
+            o = attention(li, qkv)
+            h2 = lin(li, "wo", o.view(M, self.D), residual=h, out_dtype=F32)
+            xn2 = ops.rmsnorm_fwd(h2, L["ln2"], self.eps)
+            act = ops.silu_mul_fwd_blk(lin(li, "wgu", xn2))
+            h = lin(li, "wd", act, residual=h2, out_dtype=F32)
+        return h
+
+    def _last_rows_logits(self, last, out=None):
+        """The final norm and the row-major lm-head product of [R, D] f32 rows: f32 logits [R, V]."""
+        return ops.gemm(ops.rmsnorm_fwd(last, self.norm, self.eps), self.lm_head, out=out, out_dtype=F32)
+
+    def _decode_workspace(self, B: int, T_need: int, inv_temp: float, dev_sample: bool = False, penalty: bool = False,
+                          num_beams: int = 1):
+        """_decode_buffers (and, once captured, the hipGraph) of the single-token step for a batch size, kept across generate()
+        calls -- an evaluation run calls generate() once per batch, and re-capturing ~290 launches each time cost ~9 ms per
+        call.  The device sampler and the repetition penalty read their knobs and the seed from device memory, so the key holds
+        only whether each is on; the arg-max kernel takes inv_temp as an argument, so it stays in the key there."""
+        T_cap = ops.round_up(T_need + 2, 64)
+        key = (B, T_cap, None if dev_sample else float(inv_temp), _decode_weights_id(self), bool(dev_sample), bool(penalty),
+               int(num_beams))
+        ws = self._decode_ws.get(key)
+        if ws is None:
+            if len(self._decode_ws) >= 3:                               # a few shapes at most: evict the oldest
+                self._decode_ws.pop(next(iter(self._decode_ws)))
+            ws = self._decode_ws[key] = _decode_buffers(self, B, T_cap, dev_sample or penalty, num_beams)
+        return ws
+
+    def _prefill(self, inputs_embeds: torch.Tensor, caches, past: int = 0) -> torch.Tensor:
+        """The prefill (eager, host-known lengths) of positions past.. of [B, S0, D] f32 embeddings into `caches`, on top of the
+        `past` rows cached already; returns the last position's f32 logits [B, V].  The chunk's rows go to cache rows
+        past..S0-1, `pos` holds their rotary positions, and causal masking is aligned to the bottom right."""
+        B, S0, D = inputs_embeds.shape
+        S, H, hd, W = S0 - past, self.H, self.hd, self.D
+        scale = 1.0 / math.sqrt(hd)
+        pos = torch.arange(past, S0, dtype=torch.int32).repeat(B).to(self.dev)
+
+        def attention(li, qkv):
+            q3, cache = qkv.view(B, S, 3 * W), caches[li]
+            ops.rope_(qkv, 0, 2 * H, hd, pos, self.cos, self.sin, 1.0)
+            ops.copy3d_bf16(q3[:, :, W:], cache[:, past:S0])             # append k|v (modeling_llama.py:190-195)
+            kc = cache[:, :S0]
+            return ops.attn_fwd(q3[:, :, :W], kc[:, :, :W], kc[:, :, W:], H, hd, scale, causal=True, need_lse=False)[0]
+
+        h = self._decode_layers(inputs_embeds[:, past:].reshape(B * S, D).contiguous(), self._gemm_lin, attention, self.lora)
+        return self._last_rows_logits(h.view(B, S, D)[:, -1].contiguous())
+
+    def _prefill_packed(self, embs, slots, caches, pasts=None) -> torch.Tensor:
+        """The prefill of several requests in ONE pass over the decoder weights (the slot engine's prefill_batch > 1): `embs` is a
+        list of [S_i, D] f32 embeddings, request i goes to positions 0 .. S_i - 1 of slot slots[i] of `caches` (the slot engine's
+        [slots, T, 2D] caches, whole).  The rows are packed one request after the other, `pos` = each row's index within its
+        request, and the row count is rounded up to a multiple of 64 with zero rows that belong to no segment (LoraQV.x_ext keeps
+        a buffer per row count and the GEMM planner keys on it: a run meets a handful of shapes).  The layers are _prefill's
+        (_decode_layers) -- norms, GEMMs, the bordered LoRA, MLP -- with its three attention launches replaced by
+        mh_attn_prefill_ragged; then the R last rows are gathered for the final norm and the lm-head.  Returns [R, V] f32 logits.
+        A request's rows differ from its solo _prefill only through the GEMMs' row-count-dependent plans.
+
+        `pasts` (SlotDecoder.run_turns): request i has its first pasts[i] rows in slot slots[i] already, so only embs[i][pasts[i]:]
+        is packed, at positions pasts[i] .., and the attention launch is mh_attn_prefill_ragged_past -- the packed form of
+        _prefill(emb, cache, past).  Without it the launches are the ones above."""
+        if pasts is not None:
+            pasts = [int(p) for p in pasts]
+            if len(pasts) != len(embs) or any(not 0 <= p < int(e.shape[0]) for p, e in zip(pasts, embs)):
+                raise ValueError("pasts: one per request, 0 <= past < its rows")
+            embs = [e[p:] for e, p in zip(embs, pasts)]
+        lens = [int(e.shape[0]) for e in embs]
+        M, D = ops.round_up(sum(lens), 64), self.D
+        x = torch.zeros((M, D), dtype=F32, device=self.dev)
+        pos = torch.zeros((M,), dtype=torch.int32)
+        seg, row = [], 0
+        for i, (e, n, s) in enumerate(zip(embs, lens, slots)):
+            x[row:row + n].copy_(e)
+            past = 0 if pasts is None else pasts[i]
+            pos[row:row + n] = torch.arange(past, past + n, dtype=torch.int32)
+            seg.append((row, n, int(s)) if pasts is None else (row, n, int(s), past))
+            row += n
+        seg_host = torch.tensor(seg, dtype=torch.int32)
+        last = torch.tensor([t[0] + t[1] - 1 for t in seg], dtype=torch.int32)
+        pos, seg_dev, scale = ops.h2d(pos, self.dev), ops.h2d(seg_host, self.dev), 1.0 / math.sqrt(self.hd)
+
+        def attention(li, qkv):                                          # a table with a fourth column: the rows cached already
+            attn = ops.attn_prefill_ragged if pasts is None else ops.attn_prefill_ragged_past
+            return attn(qkv, pos, seg_dev, seg_host, caches[li], self.cos, self.sin, self.H, self.hd, scale)
+
+        h = self._decode_layers(x, self._gemm_lin, attention, self.lora)
+        return self._last_rows_logits(ops.gather_rows_f32(h, ops.h2d(last, self.dev)))
+
+    def _step_layers(self, ws: dict) -> torch.Tensor:
+        """All decoder layers for one decode token per row of ws["x_in"], whose position lives in device memory (ws["pos"] /
+        ws["kvlen"]), which makes the launch sequence replayable from a hipGraph: the fused packed step when the workspace's rows
+        stream the packed copies and decode_fused is on, else every launch of its own (_decode_layers)."""
+        rows = ws["x_in"].shape[0]
+        packed = self._packed["layers"] if _packed_step(self, rows, ws["row_limit"]) else None
+        # the bordered LoRA product unless the packed qkv copy has the LoRA merged in (decode_merge_lora)
+        lora = None if packed is not None and self._packed["qkv_key"] == "merged" else self.lora
+        if packed is not None and self.decode_fused:
+            return self._fused_step_layers(ws, packed, lora)
+        if ws.get("live") is not None:
+            raise ValueError("per-row decode state needs the fused packed token step")
+        H, hd, W, pos, scale = self.H, self.hd, self.D, ws["pos"], 1.0 / math.sqrt(self.hd)
+
+        def lin(li, name, x, **kw):
+            return ops.gemv_packed(x, packed[li]["wqkv" if name.startswith("wqkv") else name], **kw)
+
+        def attention(li, qkv):
+            q3, cache = qkv.view(rows, 1, 3 * W), ws["caches"][li]
+            ops.rope_kv_append(qkv, H, hd, pos, self.cos, self.sin, cache, pos)       # rotary + append, one launch
+            return ops.attn_fwd(q3[:, :, :W], cache[:, :, :W], cache[:, :, W:], H, hd, scale, causal=False, kv_len=ws["kvlen"],
+                                need_lse=False)[0]
+
+        return self._decode_layers(ws["x_in"], self._gemm_lin if packed is None else lin, attention, lora)
+
+    def _fused_step_layers(self, ws: dict, packed, lora) -> torch.Tensor:
+        """Single-token step on the packed copies: four launches per layer instead of nine -- the two RMSNorms
+        and the SiLU gate are rebuilt by every workgroup of the product that consumes them (mh_gemv_packed_rmsnorm /
+        _silu), rotary + KV append ride the attention launch (mh_attn_decode_rope); each fused form is bit-identical
+        to the launches it replaces (tests/test_kernels_gpu.py), MYRIAD_DECODE_FUSED=0 keeps the separate launches.
+        With LoRA attached the qkv product takes the bordered operand [xn | s A xn]: the norm and the LoRA down projection are
+        one launch (LoraQV.norm_border, <= 2 rows), the bordered packed weight the next -- five launches per layer become six.
+        With the LoRA merged into the packed qkv copy (decode_merge_lora) the step is the no-LoRA one.
+
+        The attention kernel is chosen once, from what the workspace holds.  ws["split"] (the partials buffer of
+        ops.attn_decode_split_ws) makes it the split-KV kernel.  ws["live"] (int32 [rows] on the device, the slot engine's) makes
+        it the rows kernel instead: every row appends at its own pos[b], idle rows are skipped; only the fused step has that
+        form.  Both together: the split-KV kernel in its rows form (ops.attn_decode_rope_split_rows), at 1 to GEMV_WIDE_MAX_ROWS
+        rows alike.  Above GEMV_MAX_ROWS rows (_wide_step) the products are ops.gemv_packed_wide and the norm / SiLU products take
+        their two-launch forms."""
+        H, hd, scale, cos, sin = self.H, self.hd, 1.0 / math.sqrt(self.hd), self.cos, self.sin
+        pos, kvlen, live, split = ws["pos"], ws["kvlen"], ws.get("live"), ws["split"]
+        wide = _wide_step(self, ws["x_in"].shape[0], ws["row_limit"])
+        if live is not None:                                             # per-row state: (pos, kvlen, live)
+            attention, state = ops.attn_decode_rope_rows if split is None else ops.attn_decode_rope_split_rows, (pos, kvlen, live)
+        else:                                                            # one position for all rows: (pos, pos_dev, kvlen)
+            attention, state = ops.attn_decode_rope if split is None else ops.attn_decode_rope_split, (pos, pos, kvlen)
+        partials = () if split is None else (split,)
+
+        def gemv(x, w, **kw):
+            return (ops.gemv_packed_wide if wide else ops.gemv_packed)(x, w, **kw)
+
+        def norm_gemv(x, norm_w, w):                                     # one launch where the fused form fits, else two
+            y = None if wide else ops.gemv_packed_rmsnorm(x, norm_w, self.eps, w)
+            return y if y is not None else gemv(ops.rmsnorm_fwd(x, norm_w, self.eps), w)
+
+        h = ws["x_in"]
+        for li, (L, P, cache) in enumerate(zip(self.layers, packed, ws["caches"])):
+            qkv = norm_gemv(h, L["ln1"], P["wqkv"]) if lora is None else gemv(self._lora_operand(lora, li, h, True), P["wqkv"])
+            o = attention(qkv, cache, *state, cos, sin, H, hd, scale, *partials)
+            h2 = gemv(o, P["wo"], residual=h, out_dtype=F32)
+            gu = norm_gemv(h2, L["ln2"], P["wgu"])
+            hn = None if wide else ops.gemv_packed_silu(gu, P["wd"], residual=h2, out_dtype=F32)
+            h = hn if hn is not None else gemv(ops.silu_mul_fwd_blk(gu), P["wd"], residual=h2, out_dtype=F32)
+        return h
+
+    def _step_logits(self, ws: dict) -> None:
+        """The token step up to its logits: embed the fed ids ws["ids"], every decoder layer at the device-resident position,
+        the final norm + lm-head into ws["logits"] -- one launch on the packed copy when the fused form fits, else the norm and
+        the packed GEMV, or the GEMM above the workspace's row limit (the wide packed GEMV above GEMV_MAX_ROWS rows within it:
+        the slot engine's)."""
+        ops.embed_gather(self.embed, ws["ids"], ws["x_in"])
+        rows = ws["x_in"].shape[0]
+        h = self._step_layers(ws)
+        if not _packed_step(self, rows, ws["row_limit"]):
+            self._last_rows_logits(h, out=ws["logits"])
+            return
+        wide, lm_head = _wide_step(self, rows, ws["row_limit"]), self._packed["lm_head"]
+        if not wide and self.decode_fused and \
+                ops.gemv_packed_rmsnorm(h, self.norm, self.eps, lm_head, out=ws["logits"], out_dtype=F32) is not None:
+            return
+        hn = ops.rmsnorm_fwd(h, self.norm, self.eps)
+        (ops.gemv_packed_wide if wide else ops.gemv_packed)(hn, lm_head, out=ws["logits"], out_dtype=F32)
+
+    @staticmethod
+    def _launch_step(ws: dict, token_step, ban: int, use_graph: bool, stats: dict) -> bool:
+        """Enqueue one token step: a replay of ws's captured graph when there is one (counted in stats["graph_replays"]).  A step
+        with a ban runs eagerly; an eager ban-free step after an earlier eager one captures the next (kernels are warm, buffers
+        fixed).  Returns whether this call captured."""
+        if ban == -1 and use_graph and ws["graph"] is not None:
+            ws["graph"].replay()
+            stats["graph_replays"] += 1
+            return False
+        token_step(ban)
+        captured = ban == -1 and use_graph and ws["warm"]
+        if captured:
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                token_step(-1)
+            ws["graph"] = g
+        ws["warm"] = True
+        return captured
+
+    @torch.no_grad()
+    def greedy_generate(self, inputs_embeds: torch.Tensor, max_new_tokens: int = 90,
+                        stop_ids=((835,), (2277, 29937)), eos_id: int = 2, min_length: int = 1,
+                        return_margins: bool = False, use_graph: bool = True, do_sample: bool = False,
+                        top_p: float = 1.0, temperature: float = 1.0, generator: Optional[torch.Generator] = None,
+                        top_k: int = 50, repetition_penalty: float = 1.0):
+        """Decode from [B,S0,D] f32 embeddings with a KV cache (prefill + 1-token steps).  Same contract
+        as the oracle's greedy_generate: stop when ROW 0 ends with a stop sequence (conversation.py:102-107),
+        EOS banned while fewer than `min_length` tokens were generated, finished rows padded with EOS.
+
+        The single-token step (~290 launches) is captured into a hipGraph once per batch size, kept across generate() calls
+        (an evaluation run calls generate() once per batch) and replayed; everything it needs lives on the device -- position /
+        valid-length counters, and the token it just picked is fed back as the next input by the step itself
+        (mh_decode_record), which packs the step's picks into one small record: between two steps the host makes ONE
+        device->host copy.  (Measured and dropped: launching step t+1 before reading step t -- back-to-back launches of one
+        executable graph cost more than the host's 0.07 ms per step; writing the record straight into pinned host memory --
+        +0.2 ms per token.)
+
+        `do_sample=True, top_p, temperature` are the eval script's arguments (evaluation_aqa_dataset.py:289-301).  HF's
+        top-p warper keeps the smallest descending-probability set whose mass reaches top_p (at least one token), so a
+        step whose p_max >= top_p IS the arg-max; the kernel reports p_max per row and only a row below the threshold is
+        drawn on the host from that row's logits (a genuine sample: reproducible here through `generator`, never
+        bit-comparable with another framework's RNG) and replaces the fed-back id.  `last_generate_stats` counts such steps.
+        The host draw applies HF's default `top_k = 50` filter first, then top-p; the device test p_max >= top_p is taken over the
+        full vocabulary, which is the conservative side: the top-k renormalisation only raises p_max, and a row whose
+        renormalised p_max reaches top_p keeps exactly one token in the host draw -- the arg-max again.
+
+        With `device_sampling` (MYRIAD_DEVICE_SAMPLING=1) and 1 <= top_k <= 1024 the whole chain runs inside the step instead
+        (mh_sample_rows: temperature, top-k with ties kept, top-p, inverse-CDF draw from Philox4x32-10 keyed by one seed drawn from
+        `generator` per call): every step is a draw, no row waits on the host, and runs are reproducible per seed but not
+        bit-comparable with torch.multinomial.  A row whose tied top-k set passes 1024 candidates is still drawn on the host.
+        `repetition_penalty` (HF RepetitionPenaltyLogitsProcessor over the generated ids; the prompt is embeddings only) is applied
+        on the device to the step's logits before any pick, greedy, host or device draw."""
+        B, S0, _ = inputs_embeds.shape
+        inv_temp, _, dev_sample, penalty = _sampling_args(self, do_sample, temperature, top_k, repetition_penalty)
+        weight_stats = self._prepare_decode_weights(B)
+        ws = self._decode_workspace(B, S0 + max_new_tokens, inv_temp, dev_sample, penalty)
+        return self._greedy_core(inputs_embeds, ws, 0, weight_stats, max_new_tokens, stop_ids, eos_id, min_length, return_margins,
+                                 use_graph, do_sample, top_p, temperature, generator, top_k, repetition_penalty)
+
+    def _greedy_core(self, inputs_embeds: torch.Tensor, ws: dict, past: int, weight_stats: dict, max_new_tokens: int = 90,
+                     stop_ids=((835,), (2277, 29937)), eos_id: int = 2, min_length: int = 1, return_margins: bool = False,
+                     use_graph: bool = True, do_sample: bool = False, top_p: float = 1.0, temperature: float = 1.0,
+                     generator: Optional[torch.Generator] = None, top_k: int = 50, repetition_penalty: float = 1.0):
+        """greedy_generate's body on the caller's workspace `ws` (greedy_generate's from the _decode_ws cache, a DecodeSession's
+        own buffers and graphs), on top of the cached prefix `past` that is not prefilled again; `weight_stats` is what
+        _prepare_decode_weights answered for this call.  The other arguments are greedy_generate's, in its order."""
+        B, S0, _ = inputs_embeds.shape
+        inv_temp, top_k, dev_sample, penalty = _sampling_args(self, do_sample, temperature, top_k, repetition_penalty)
+        out_ids, margins = [], []
+        unfinished = torch.ones(B, dtype=torch.long)
+        stats = dict(steps=0, sampled_rows=0, min_pmax=1.0, device_sampled_rows=0, host_sampled_rows=0, graph_replays=0, **weight_stats)
+        self.last_generate_stats = stats
+        rec = ws["rec"][:4 if dev_sample else 3]                     # the sampler's kept counts are the fourth row
+        if dev_sample or penalty:
+            ws["prm"].copy_(torch.tensor([inv_temp, top_p, float(top_k), float(repetition_penalty)], dtype=F32))
+            ws["seen"].zero_()                                       # generated ids only: the prompt is embeddings
+        if dev_sample:
+            ws["seed"].fill_(int(torch.randint(0, 2**63 - 1, (1,), generator=generator)))
+
+        def record(nxt: torch.Tensor, mar: torch.Tensor, pm: torch.Tensor, ban: int, logits_of=None, kept=None):
+            """Host bookkeeping of one step's picks.  Returns (done, redrawn): redrawn = a live row was re-drawn on the host
+            (finished rows are fed their raw arg-max instead of EOS by the device: rows are independent and their outputs are
+            overwritten with EOS here)."""
+            nonlocal unfinished
+            margins.append(mar)
+            stats["steps"] += 1
+            redrawn = False
+            if do_sample:
+                stats["min_pmax"] = min(stats["min_pmax"], float(pm[unfinished.bool()].min()) if int(unfinished.sum()) else 1.0)
+                for row in range(B):
+                    if not int(unfinished[row]):
+                        continue
+                    if float(pm[row]) < top_p:
+                        stats["sampled_rows"] += 1
+                    if dev_sample and int(kept[row]) >= 0:
+                        stats["device_sampled_rows"] += 1            # drawn by the step itself
+                    elif dev_sample or float(pm[row]) < top_p:
+                        nxt[row] = _host_draw(logits_of()[row], ban, inv_temp, top_k, top_p, generator)
+                        stats["host_sampled_rows"] += 1
+                        redrawn = True
+            nxt = nxt * unfinished + eos_id * (1 - unfinished)       # HF pads finished rows with pad(=eos)
+            unfinished = unfinished * (nxt != eos_id).long()
+            out_ids.append(nxt)
+            row0 = [int(t[0]) for t in out_ids]
+            if any(len(row0) >= len(st) and row0[-len(st):] == list(st) for st in stop_ids):
+                return True, redrawn
+            return int(unfinished.max()) == 0, redrawn
+
+        logits0 = self._prefill(inputs_embeds, ws["caches"], past)
+        ban0 = eos_id if 0 < min_length else -1
+        if dev_sample:                                               # the prefill pick is Philox step t = 0
+            ops.sample_rows(logits0, ws["nxt"], ws["mar"], ws["pmx"], ws["kept"], ws["prm"], ws["seed"], ban_id=ban0, t_add=0)
+        else:
+            ops.argmax_pmax_rows(logits0, ws["nxt"], ws["mar"], ws["pmx"], ban_id=ban0, inv_temp=inv_temp)
+        done, _ = record(ws["nxt"].cpu(), ws["mar"].cpu(), ws["pmx"].cpu(), ban0, logits_of=lambda: logits0,
+                         kept=ws["kept"].cpu() if dev_sample else None)
+
+        # ---- single-token steps: everything the step reads is on the device
+        ws["pos"].fill_(S0)                                          # position of the incoming token
+        ws["kvlen"].fill_(S0 + 1)                                    # valid keys after the append
+        ws["step"].zero_()
+
+        def token_step(ban):
+            self._step_logits(ws)
+            if penalty:                                              # ws["ids"] = the token fed in: it joins the seen set first
+                ops.repetition_penalty_rows(ws["logits"], ws["seen"], ws["ids"], ws["prm"][3:])
+            if dev_sample:                                           # token s (= step + 1) draws Philox step t = s
+                ops.sample_rows(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ws["kept"], ws["prm"], ws["seed"], ban_id=ban,
+                                step=ws["step"], t_add=1)
+                ops.decode_advance_kept(ws["nxt"], ws["mar"], ws["pmx"], ws["kept"], rec, ws["ids"], ws["step"], ws["pos"],
+                                        ws["kvlen"])
+                return
+            ops.argmax_pmax_rows(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ban_id=ban, inv_temp=inv_temp)
+            ops.decode_advance(ws["nxt"], ws["mar"], ws["pmx"], rec, ws["ids"], ws["step"], ws["pos"], ws["kvlen"])
+
+        step = 1                                                     # tokens generated so far (= index of the next one)
+        if not done and step < max_new_tokens:
+            ws["ids"].copy_(out_ids[-1].to(self.dev))
+        while not done and step < max_new_tokens:
+            ban = eos_id if step < min_length else -1
+            self._launch_step(ws, token_step, ban, use_graph, stats)
+            r = rec.cpu()                                            # the one device->host copy of the step (it also waits for it)
+            done, redrawn = record(r[0].long(), r[1].clone(), r[2].clone(), ban, logits_of=lambda: ws["logits"],
+                                   kept=r[3] if dev_sample else None)
+            if redrawn and not done:
+                ws["ids"].copy_(out_ids[-1].to(self.dev))            # a host draw replaces the arg-max the step fed back to itself
+            step += 1
+        ids = torch.stack(out_ids, 1)
+        return (ids, torch.stack(margins, 1)) if return_margins else ids
+
+    @torch.no_grad()
+    def beam_generate(self, inputs_embeds: torch.Tensor, num_beams: int, max_new_tokens: int = 90, stop_ids=(), eos_id: int = 2,
+                      min_length: int = 1, length_penalty: float = 1.0, early_stopping=False, num_return_sequences: int = 1,
+                      use_graph: bool = True, return_scores: bool = False, pad_id: Optional[int] = None):
+        """Beam search from [B,S0,D] f32 embeddings: HF GenerationMixin._beam_search (tests/beam_ref.py states the rules).
+        Returns [B * num_return_sequences, L] int64 (CPU), generated ids only, the hypotheses of item b at rows
+        b * nrs .. b * nrs + nrs - 1 best first, right-padded with pad_id (default EOS); with return_scores also their
+        sequence scores (sum log-probs / len ** length_penalty), which last_generate_stats["sequences_scores"] holds either way.
+
+        Stop rule: a hypothesis finishes when its own sequence ends with EOS or with one of `stop_ids` (per hypothesis, as
+        transformers applies a criterion that returns one bool per row), or at max_new_tokens.  greedy_generate keeps the
+        reference's rule instead (the batch stops when row 0 ends with a stop sequence).
+
+        Device / host split.  The prefill runs at B rows, writing its keys / values into row b * nb of the B * nb row caches,
+        and one mh_beam_reorder_kv broadcasts them over [0, S0) to the item's other beams.  The token step (captured into a
+        hipGraph, like greedy's) is: reorder the generated positions [S0, pos) of every cache by the parent rows `src`, embed
+        the fed tokens, the decoder layers at B * nb rows (packed GEMV up to GEMV_MAX_ROWS), lm-head, mh_beam_topk (log-softmax +
+        running score + EOS ban, per item the top 2 * nb candidates), pos / kvlen += 1.  The host reads the [2, B, 2*nb]
+        record (one device->host copy), keeps the hypotheses, and writes the next step's (ids, src, running scores) with one
+        host->device copy."""
+        B, S0, _ = inputs_embeds.shape
+        nb, nrs = int(num_beams), int(num_return_sequences)
+        if nb > ops.BEAM_MAX:
+            raise NotImplementedError(f"num_beams={nb}: at most {ops.BEAM_MAX} beams on the HIP decode path")
+        if nb < 1:
+            raise ValueError(f"num_beams must be >= 1, got {nb}")
+        if not 1 <= nrs <= nb:
+            raise ValueError(f"num_return_sequences={nrs} must be between 1 and num_beams={nb}")
+        if early_stopping not in (True, False, "never"):
+            raise ValueError(f"early_stopping must be True, False or 'never', got {early_stopping!r}")
+        if self.V < 2 * nb:
+            raise ValueError(f"num_beams={nb} needs a vocabulary of at least {2 * nb} tokens")
+        lp = float(length_penalty)
+        pad = eos_id if pad_id is None else int(pad_id)
+        stops = [tuple(int(t) for t in st) for st in stop_ids]
+        R, K, V, NEG = B * nb, 2 * nb, self.V, np.float32(-1.0e9)
+        stats = dict(steps=0, num_beams=nb, graph_replays=0, finished_hypotheses=0, sequences_scores=None, lengths=None)
+        self.last_generate_stats = stats
+        stats.update(self._prepare_decode_weights(R))
+        ws = self._decode_workspace(R, S0 + max_new_tokens, 1.0, num_beams=nb)
+        caches, T_cap, C = ws["caches"], ws["T"], 2 * self.D
+        dev = self.dev
+
+        # ---- host state of the search (HF's tensors, per item, as small numpy arrays / lists)
+        run_seqs = [[()] * nb for _ in range(B)]
+        fin_scores = np.full((B, nb), NEG, dtype=np.float32)
+        fin_seqs = [[()] * nb for _ in range(B)]
+        is_fin = np.zeros((B, nb), dtype=bool)
+        unsat = np.ones((B,), dtype=bool)
+        host = ws["bupd_host"]
+        h_ids, h_src, h_sc = host[:2 * R].view(torch.long).numpy(), host[2 * R:3 * R].numpy(), host[3 * R:].view(F32).numpy()
+
+        def select(top_s: np.ndarray, top_i: np.ndarray, gen_len: int) -> bool:
+            """One step's bookkeeping from the record (top_s / top_i [B, K]); fills the upload; True = go on."""
+            nonlocal unsat
+            stats["steps"] += 1
+            all_hit = True
+            for b in range(B):
+                par, tok = top_i[b] // V, top_i[b] % V
+                cand = [run_seqs[b][int(par[k])] + (int(tok[k]),) for k in range(K)]
+                hits = np.array([c[-1] == eos_id or gen_len >= max_new_tokens
+                                 or any(len(c) >= len(st) and c[-len(st):] == st for st in stops) for c in cand])
+                all_hit &= bool(hits.all())
+                run_lp = top_s[b] + hits.astype(np.float32) * NEG
+                nxt = np.argsort(-run_lp, kind="stable")[:nb]
+                run_seqs[b] = [cand[k] for k in nxt]
+                h_ids[b * nb:(b + 1) * nb] = tok[nxt]
+                h_src[b * nb:(b + 1) * nb] = b * nb + par[nxt]
+                h_sc[b * nb:(b + 1) * nb] = run_lp[nxt]
+                did = hits.copy()
+                did[nb:] = False                                     # only the top nb candidates may enter the pool
+                sc = top_s[b] / np.float32(gen_len ** lp)
+                if is_fin[b].all() and early_stopping is True:
+                    sc = sc + NEG
+                if not unsat[b]:
+                    sc = sc + NEG
+                sc = sc + (~did).astype(np.float32) * NEG
+                merged = np.concatenate([fin_scores[b], sc])
+                keep = np.argsort(-merged, kind="stable")[:nb]
+                mseqs, mfin = fin_seqs[b] + cand, np.concatenate([is_fin[b], did])
+                fin_scores[b], fin_seqs[b], is_fin[b] = merged[keep], [mseqs[k] for k in keep], mfin[keep]
+                best_len = max_new_tokens if (early_stopping == "never" and lp > 0.0) else gen_len
+                best_run = np.float32(h_sc[b * nb]) / np.float32(best_len ** lp)
+                worst = fin_scores[b].min()
+                unsat[b] = unsat[b] and bool(np.any(np.where(is_fin[b], best_run > worst, best_run > NEG)))
+            return bool(unsat.any()) and not (bool(is_fin.all()) and early_stopping is True) and not all_hit
+
+        def read_record():
+            rec = ws["brec"].cpu()                                   # the one device->host copy of the step
+            return rec[0].view(F32).numpy().reshape(B, K), rec[1].numpy().reshape(B, K).astype(np.int64)
+
+        # ---- prefill at B rows into rows b * nb, then broadcast the prompt's keys / values to the other beams
+        logits0 = self._prefill(inputs_embeds, [c[::nb] for c in caches])
+        ws["bscore"].zero_()                                         # beam 0's running score; one row per item here
+        ops.beam_topk(logits0, ws["bscore"], ws["part_s"], ws["part_i"], ws["brec"][0].view(F32), ws["brec"][1], B, nb,
+                      ban_id=eos_id if 0 < min_length else -1)
+        if self.layers:
+            # a range of its own: ws["lo"] holds the previous call's S0 when the workspace is reused
+            bsrc = torch.arange(B, dtype=torch.int32).repeat_interleave(nb).mul_(nb).to(dev)
+            span = torch.tensor([0, S0], dtype=torch.int32).to(dev)
+            ops.beam_reorder_kv(ws["table"], len(caches), B, nb, T_cap, C, bsrc, span[:1], span[1:])
+        going = select(*read_record(), 1)
+
+        # ---- token steps
+        ws["pos"].fill_(S0)
+        ws["kvlen"].fill_(S0 + 1)
+        ws["lo"].fill_(S0)                                           # the prompt prefix is the same in every beam of an item
+
+        def token_step(ban):
+            ops.beam_reorder_kv(ws["table"], len(caches), B, nb, T_cap, C, ws["src"], ws["lo"], ws["pos"])
+            self._step_logits(ws)
+            ops.beam_topk(ws["logits"], ws["bscore"], ws["part_s"], ws["part_i"], ws["brec"][0].view(F32), ws["brec"][1], B, nb,
+                          ban_id=ban, pos=ws["pos"], kvlen=ws["kvlen"])
+
+        gen = 1                                                      # tokens generated so far
+        while going and gen < max_new_tokens:
+            ws["bupd"].copy_(ws["bupd_host"], non_blocking=True)    # ids | src | running scores: one host->device copy
+            self._launch_step(ws, token_step, eos_id if gen < min_length else -1, use_graph, stats)
+            gen += 1
+            going = select(*read_record(), gen)
+
+        seqs = [fin_seqs[b][i] for b in range(B) for i in range(nrs)]
+        scores = torch.from_numpy(np.array([fin_scores[b, i] for b in range(B) for i in range(nrs)], dtype=np.float32))
+        ids = torch.full((len(seqs), max(1, max(len(q) for q in seqs))), pad, dtype=torch.long)
+        for r, q in enumerate(seqs):
+            ids[r, :len(q)] = torch.tensor(q, dtype=torch.long)
+        stats.update(sequences_scores=scores, finished_hypotheses=int(is_fin.sum()), lengths=[len(q) for q in seqs])
+        return (ids, scores) if return_scores else ids
+
+    def slot_decoder(self, slots: int, capacity: int, split_kv: Optional[bool] = False) -> "SlotDecoder":
+        """A decode-slot engine over this model: `slots` rows of one captured token step, each decoding its own request of up to
+        `capacity` positions (prompt + generated).  `split_kv`: the step's attention kernel (False: the single-workgroup rows
+        kernel, True: the split-KV rows kernel, None: split_kv_rows_rule per call).  See SlotDecoder."""
+        return SlotDecoder(self, slots, capacity, split_kv=split_kv)
+
+
+class DecodeSession:
+    """A decode KV cache that outlives one call: the multi-turn chat's (myriad_amd/chat.py).  It owns its buffers -- the per-layer
+    caches, pos / kvlen / ids / records, the sampler's buffers, the split-KV partials -- and its captured token-step graphs, so no
+    other generate() (whose workspaces live in the LlamaHIP._decode_ws LRU) can evict them.
+
+    The session records one key per cached position (`keys[row][p]`): whatever the caller uses to name that position's input, a
+    ("t", token id) for text and an image-slot / index pair for image rows.  A turn (`generate`) prefills only the rows past the
+    longest common prefix of the new context's keys with the cached ones -- at their own positions, on top of the cached rows --
+    then runs greedy_generate's token step on the session's buffers.  Afterwards the cache holds the context plus every token the
+    step fed back (the last pick of a turn has no KV and is not counted; a row that finished early feeds ids the host does not
+    know, recorded as a key that matches nothing).
+
+    The whole cache is dropped (full prefill, `last_stats["full_reprefill_reason"]`) when the caller's weights version changes
+    (optimiser update, state-dict load), when the decode weights change kind (bf16 / fp8 / fp4, LoRA on / off, the LoRA-merged qkv copy
+    on / off or re-merged: "decode weights changed"), when the batch size changes, when the capacity (round_up(need + 2, 64), at
+    most 8192) is exceeded, or when the caller says so (`reset_reason`: the chat's truncation window moved)."""
+
+    def __init__(self, llama: "LlamaHIP", capacity: int, split: Optional[bool] = None):
+        self.llama = llama
+        self.capacity = min(8192, ops.round_up(int(capacity), 64))
+        self.split_choice = split                                    # None: split_kv_rule per turn; True / False force it
+        self.bufs = self.B = self.stamp = None
+        self.keys: List[list] = []
+        self.views = {}                                              # cfg -> workspace view of bufs, with its graph / warm flag
+        self.graph_captures = 0
+        self.split = False
+        self.last_stats = {}
+
+    def _begin_turn(self, keys, version, reason, B: int, S0: int, max_new_tokens: int, inv_temp: float, dev_sample: bool,
+                    penalty: bool):
+        """A turn's setup, once the decode weights are packed: invalidation, (re)allocation, the reused prefix.
+        Returns (workspace, past)."""
+        L = self.llama
+        if S0 + max_new_tokens > L.cos.shape[0]:
+            raise ValueError(f"context {S0} + max_new_tokens {max_new_tokens} passes the rotary table ({L.cos.shape[0]} positions)")
+        if len(keys) != B or any(len(k) != S0 for k in keys):
+            raise ValueError("one key per context position and batch row is required")
+        stamp = _cache_stamp(L, version)
+        need = S0 + max_new_tokens + 2
+        if self.bufs is None:
+            reason = reason or "empty cache"
+        elif self.B != B:
+            reason = "batch size"
+        elif self.stamp[0] != version:
+            reason = "weights changed"
+        elif self.stamp[1:] != stamp[1:]:
+            reason = "decode weights changed"
+        elif need > self.bufs["T"]:
+            reason = "capacity"
+        if self.bufs is None or self.B != B or need > self.bufs["T"] or (self.stamp is not None and self.stamp[1:] != stamp[1:]):
+            T_cap = max(self.capacity, ops.round_up(need, 64))
+            if T_cap > 8192:
+                raise ValueError(f"a chat session holds at most 8192 positions; this turn needs {need}")
+            self.bufs, self.views = None, {}
+            self.bufs, self.B = _decode_buffers(L, B, T_cap, sampler=True), B
+        self.stamp = stamp
+        if reason is not None:
+            self.keys = [[] for _ in range(B)]
+        past = min(common_prefix(keys[r], self.keys[r]) for r in range(B))
+        past = min(past, S0 - 1)                                     # at least one row is prefilled: it gives the first logits
+        fused = _packed_step(L, B) and L.decode_fused
+        self.split = fused and (split_kv_rule(B, L.H, S0) if self.split_choice is None else bool(self.split_choice))
+        cfg = (None if dev_sample else float(inv_temp), bool(dev_sample), bool(penalty), self.split)
+        if cfg not in self.views:
+            self.views[cfg] = _buffer_view(L, self.bufs, self.split)
+        self.last_stats = dict(context_tokens=S0, reused_tokens=past, prefilled_tokens=S0 - past, split_kv=bool(self.split),
+                               full_reprefill_reason=reason)
+        return self.views[cfg], past
+
+    @torch.no_grad()
+    def generate(self, inputs_embeds: torch.Tensor, keys, weights_version=None, reset_reason: Optional[str] = None,
+                 max_new_tokens: int = 90, **kw):
+        """One turn: greedy_generate's contract and arguments (`max_new_tokens`, `stop_ids`, `eos_id`, `min_length`, `do_sample`,
+        `top_p`, `temperature`, `generator`, `top_k`, `repetition_penalty`, `return_margins`) on [B, S0, D] f32 embeddings whose
+        positions are named by `keys` ([B][S0]).  `weights_version`: anything that changes when the weights do."""
+        L = self.llama
+        B, S0, _ = inputs_embeds.shape
+        ws = None
+        try:
+            inv_temp, _, dev_sample, penalty = _sampling_args(L, **kw)
+            weight_stats = L._prepare_decode_weights(B)              # packed before the stamp, which names the packed copies
+            ws, past = self._begin_turn([list(k) for k in keys], weights_version, reset_reason, B, S0, max_new_tokens, inv_temp,
+                                        dev_sample, penalty)
+            graph = ws["graph"]
+            out = L._greedy_core(inputs_embeds, ws, past, weight_stats, max_new_tokens=max_new_tokens, use_graph=True, **kw)
+        except BaseException:
+            self.keys = [[] for _ in range(B)]                       # the cache may be half written
+            raise
+        finally:
+            if ws is not None and ws["graph"] is not graph:          # this turn captured its view's step
+                self.graph_captures += 1
+        ids = out[0] if isinstance(out, tuple) else out
+        eos = int(kw.get("eos_id", 2))
+        new_keys = []
+        for r in range(B):
+            row, fed, live = ids[r].tolist(), [], True
+            for k in range(len(row) - 1):                                  # token step k + 1 fed pick k at position S0 + k
+                fed.append(("t", row[k]) if live else ("x",))
+                live = live and row[k] != eos
+            new_keys.append(list(keys[r]) + fed)
+        self.keys = new_keys
+        st = self.llama.last_generate_stats
+        self.last_stats.update(steps=st["steps"], graph_replays=st["graph_replays"], graph_captures=self.graph_captures)
+        return out
+
+
+class SlotDecoder:
+    """Streams requests through `slots` rows of ONE captured token step (LlamaHIP.slot_decoder).  Each slot holds one request with
+    its own prompt length, position and stop rule; a slot whose request ends is refilled with the next one while the others go on
+    decoding, so no row is computed and thrown away for long and no request is cut short by another's stop.
+
+    1 to GEMV_WIDE_MAX_ROWS slots.  Above GEMV_MAX_ROWS slots the products are ops.gemv_packed_wide on the same packed copies, whose
+    rows carry the 16-row kernel's bits: a request's ids and margins do not depend on the slot count.
+    The step is greedy_generate's fused packed step (bf16 / FP8 / MXFP4 copies, merged or bordered LoRA alike) with two launches
+    swapped: the attention is mh_attn_decode_rope_rows (row b appends at pos[b], idle rows skipped) and the bookkeeping is
+    mh_decode_advance_rows (idle rows record id -1).  `split_kv` (opt-in) swaps the attention for the split-KV kernel's rows
+    form, mh_attn_decode_rope_split_rows -- the solo chat session's kernel for long contexts, a live row has its bits: False
+    (default) never, True always, None by split_kv_rows_rule once per run / run_turns call.  Each kernel has its own views and
+    captured graphs, so toggling evicts nothing.  A refill is the existing B = 1 prefill into the slot's slice of every cache.
+    Between two replays the host writes only a finished slot's live flag, a refilled slot's (id, pos, kvlen, live) and a host
+    draw's id.  greedy_generate and its row-0 rule are untouched; this path is opt-in.
+
+    Device sampling, repetition_penalty != 1 and min_length > 1 run the step's per-row tail instead: mh_repetition_penalty_rows_slots
+    (with a penalty), mh_sample_rows_slots or -- greedy and host draw -- mh_argmax_pmax_rows_slots, then mh_decode_advance_kept_rows.
+    Slot row r then also has gen[r] on the device, the count of tokens its request has generated, which decides its EOS ban
+    (gen[r] < min_length) and, with device sampling, is the Philox step of its draw from its own seed[r]: every request draws from
+    its own counter-based stream (seeded_requests), so its answer does not depend on its neighbours, the slot count or the refill
+    settings.  The knobs (temperature, top_p, top_k, penalty, min_length, eos_id) are read from device memory: one graph per
+    (device-sampled or not, penalty or not).  A refill there also writes the slot's seed and gen = 1 and clears its bitmap row.
+
+    Packed prefill (opt-in, `run(prefill_batch=P > 1)` or `refill_min > 1`): at a refill point up to min(P, free slots) waiting
+    requests are prefilled in ONE pass over the weights (LlamaHIP._prefill_packed, one mh_attn_prefill_ragged per layer writing
+    each request's keys / values into its own slot), one arg-max launch and one device->host copy give all their first picks, and
+    they are admitted in input order.  RefillPlanner decides which requests go together and when.
+
+    Conversations (opt-in, `run_turns`; the chat pool's, myriad_amd/chat.py ChatPool): a session keeps ITS slot and the rows the
+    slot caches from call to call (`sessions`, a SessionTable), a turn prefills only the rows past the prefix its new context
+    shares with them -- solo with `past`, or several turns per pass through _prefill_packed(..., pasts), one
+    mh_attn_prefill_ragged_past per layer -- and then decodes in the same captured step as `run`.  `run` itself starts every slot
+    at row 0, so it drops what the sessions had cached."""
+
+    def __init__(self, llama: "LlamaHIP", slots: int, capacity: int, split_kv: Optional[bool] = False):
+        slots = int(slots)
+        if slots < 1 or slots > ops.GEMV_WIDE_MAX_ROWS:
+            raise ValueError(f"slots={slots}: the slot engine runs the packed token step, 1 to {ops.GEMV_WIDE_MAX_ROWS} rows")
+        if split_kv is not None and not isinstance(split_kv, bool):
+            raise ValueError(f"split_kv={split_kv!r}: False (the single-workgroup rows kernel), True (split-KV) or None (the rule)")
+        self.split_kv = split_kv
+        self.llama, self.slots = llama, slots
+        self.T_cap = ops.round_up(int(capacity), 64)
+        if not 0 < self.T_cap <= 8192:
+            raise ValueError(f"capacity={capacity}: a slot holds at most 8192 positions")
+        self.bufs = None                                             # the step's buffers, shared by every view
+        self.views = {}                                              # inv_temp -> workspace view of bufs with its own graph
+        self.ws = None                                               # the view of the current / last run
+        self._weights = None
+        self.graph_captures = 0
+        self.last_stats = {}
+        self.sessions = SessionTable(slots)                          # run_turns: which conversation each slot's cache holds
+
+    def close(self, session) -> None:
+        """Free the slot of a run_turns session."""
+        self.sessions.close(session)
+
+    @staticmethod
+    def _view_key(inv_temp: float, rows_tail=None, split: bool = False):
+        """The key of a view (one captured graph each).  Without split-KV it is what it was before the engine had the choice --
+        inv_temp, or (inv_temp or None, device-sampled, penalty) for the per-row tail -- and a split view is ("split", that)."""
+        key = float(inv_temp)
+        if rows_tail is not None:
+            key = (None if rows_tail[0] else key, bool(rows_tail[0]), bool(rows_tail[1]))
+        return ("split", key) if split else key
+
+    def _workspace(self, inv_temp: float, rows_tail=None, split: bool = False) -> dict:
+        """The step's buffers, kept while the decode weights stay the ones the captured graphs read, and over them one view (its
+        own graph / warm flag) per inv_temp: the arg-max kernel takes inv_temp as a launch argument, so a captured step is fixed
+        to one value (LlamaHIP._decode_workspace keys its workspaces the same way).  `rows_tail` = (device-sampled, penalty) asks
+        for the step with the per-row tail: its buffers join on first use (the knobs `prm`, per-slot `seed` / `gen` / `kept` /
+        `seen`, and `seed0` / `gen0` for the refills' first picks), and a device-sampled view is keyed without inv_temp, which the
+        sampler reads from `prm`.  `split`: the view's step runs the split-KV rows kernel; the partials buffer joins on first use,
+        a split view holds it and a non-split view holds None, so each (key, split) has its own graph."""
+        L = self.llama
+        L._prepare_decode_weights(self.slots, ops.GEMV_WIDE_MAX_ROWS)
+        if not (_packed_step(L, self.slots, ops.GEMV_WIDE_MAX_ROWS) and L.decode_fused):
+            raise ValueError("the slot engine needs the fused packed token step (MYRIAD_PACK_DECODE and MYRIAD_DECODE_FUSED on)")
+        wid = _decode_weights_id(L)
+        if self.bufs is None or self._weights != wid:
+            self.bufs, self.views, self.ws = None, {}, None
+            # its row limit: above GEMV_MAX_ROWS slots the step stays on the packed copies
+            self.bufs = _decode_buffers(L, self.slots, self.T_cap, row_limit=ops.GEMV_WIDE_MAX_ROWS)
+            self.bufs["live"] = torch.zeros((self.slots,), dtype=torch.int32, device=L.dev)
+            self._weights = wid
+        if rows_tail is not None and "prm" not in self.bufs:
+            n, i32 = self.slots, torch.int32
+            self.bufs.update(prm=torch.zeros((6,), dtype=F32, device=L.dev), seed=torch.zeros((n,), dtype=torch.long, device=L.dev),
+                             seed0=torch.zeros((n,), dtype=torch.long, device=L.dev), gen=torch.zeros((n,), dtype=i32, device=L.dev),
+                             gen0=torch.zeros((n,), dtype=i32, device=L.dev), kept=torch.zeros((n,), dtype=i32, device=L.dev),
+                             seen=torch.zeros((n, (L.V + 31) // 32), dtype=i32, device=L.dev))
+        key = self._view_key(inv_temp, rows_tail, split)
+        if key not in self.views:
+            same = [k for k in self.views if (isinstance(k, tuple) and k[0] == "split") == bool(split)]
+            if len(same) >= 4:                                       # a few temperatures at most per kernel: drop its oldest graph
+                self.views.pop(same[0])
+            self.views[key] = _buffer_view(L, self.bufs, split)
+        self.ws = self.views[key]
+        return self.ws
+
+    @torch.no_grad()
+    def run(self, requests, max_new_tokens: int = 90, stop_ids=((835,), (2277, 29937)), eos_id: int = 2, min_length: int = 1,
+            do_sample: bool = False, top_p: float = 1.0, temperature: float = 1.0, top_k: int = 50,
+            generator: Optional[torch.Generator] = None, ordered: bool = False, prefill_batch: int = 1, refill_min: int = 1,
+            prefill_rows: int = 2048, repetition_penalty: float = 1.0, seeds=None):
+        """Decode every request of `requests` (an iterable of [S0_i, D] f32 embeddings, lengths free) and yield
+        (index, ids[L_i] int64 on the CPU, margins[L_i] f32) as each finishes -- or, with `ordered`, in input order.  The
+        arguments are greedy_generate's; the stop rule is per request.  `last_stats` holds the run's counters: `prefills` counts
+        requests, `prefill_passes` passes over the weights and `packed_rows` the request rows they held (padding not counted).
+        `prefill_batch`, `refill_min`, `prefill_rows`: RefillPlanner's; at 1, 1 every refill is the one-request prefill.
+
+        With `device_sampling` (and greedy_generate's conditions on top_k and the vocabulary) every pick is drawn on the device
+        from the request's own stream: request i takes the i-th seed drawn from `generator`, or the i-th of `seeds`, and token t
+        of it is Philox step t -- what greedy_generate draws for that request alone with that seed.  `device_sampled_rows`
+        counts those picks; a row the sampler hands back (kept = -1) is drawn on the host from a generator derived from the
+        request's seed and t (`host_sampled_rows`).  `repetition_penalty` != 1 needs the switch, as in generate(); `min_length`
+        is a per-request EOS ban on every path.  A second run with other values of the knobs replays the same graph.
+        `last_stats["split_kv"]`: the attention kernel of the call's token steps.  With the decoder's split_kv=None the rule sees
+        `slots` live rows and a longest context of 0 -- the lengths are not known up front -- so None never splits here."""
+        self.sessions.clear()                                        # the slots' caches are overwritten from row 0
+        yield from self._run(requests, None, None, max_new_tokens, stop_ids, eos_id, min_length, do_sample, top_p, temperature,
+                             top_k, generator, ordered, prefill_batch, refill_min, prefill_rows, repetition_penalty, seeds)
+
+    def run_turns(self, turns, weights_version=None, **kw):
+        """One turn each of several conversations, every one in ITS OWN slot on top of what that slot's cache holds of it
+        (`sessions`, a SessionTable).  `turns` = [(session, emb [S0, D] f32, keys [S0])] or with a fourth item `reset_reason`; at
+        most one turn per session per call (ValueError), at most `slots` open sessions (`close(session)` frees one).  `kw` are
+        `run`'s arguments but `refill_min` (prefill_batch, prefill_rows, the sampling knobs, repetition_penalty, min_length,
+        seeds: with device sampling the i-th turn of the call takes the i-th seed).  Only the rows past the prefix the slot
+        shares with the new context are prefilled: with prefill_batch = 1 a solo _prefill(emb, slot cache, past) per turn,
+        otherwise passes of up to prefill_batch turns / prefill_rows new rows through _prefill_packed(..., pasts).  Then `run`'s
+        captured step (same graphs and views) runs until every turn has stopped under its own stop rule.  Yields (session, ids,
+        margins) as `run` does, `ordered=True` in the list's order; `last_stats["turns"]` holds per turn `context_tokens`,
+        `reused_tokens`, `prefilled_tokens` and `full_reprefill_reason`.  `weights_version`: anything that changes when the
+        weights do; with it, a change of the decode weights or a `run()` on this decoder drops every session's cached rows.  The
+        step's attention kernel is the decoder's `split_kv` choice, made once per call (`last_stats["split_kv"]`): with None,
+        split_kv_rows_rule(turns in the call, heads, the longest context at admission)."""
+        turns = [tuple(t) for t in turns]
+        if "refill_min" in kw:
+            raise ValueError("run_turns: refill_min does not apply, every turn has its own slot")
+        for t in turns:
+            if len(t) not in (3, 4) or t[1].dim() != 2 or len(t[2]) != t[1].shape[0]:
+                raise ValueError("run_turns: a turn is (session, emb [S0, D], keys [S0]) or (session, emb, keys, reset_reason)")
+        keys = [SessionTable._key(t[0]) for t in turns]
+        if len(set(keys)) != len(keys):
+            raise ValueError("run_turns: at most one turn per session in one call")
+        return self._run(None, turns, weights_version, **kw)
+
+    @torch.no_grad()
+    def _run(self, requests, turns, weights_version, max_new_tokens: int = 90, stop_ids=((835,), (2277, 29937)), eos_id: int = 2,
+             min_length: int = 1, do_sample: bool = False, top_p: float = 1.0, temperature: float = 1.0, top_k: int = 50,
+             generator: Optional[torch.Generator] = None, ordered: bool = False, prefill_batch: int = 1, refill_min: int = 1,
+             prefill_rows: int = 2048, repetition_penalty: float = 1.0, seeds=None):
+        """`run` (requests) and `run_turns` (turns + weights_version): one engine, two admission rules."""
+        L = self.llama
+        inv_temp, top_k, dev_sample, penalty = _sampling_args(L, do_sample, temperature, top_k, repetition_penalty)
+        if penalty and not L.device_sampling:
+            raise NotImplementedError(f"decode slots: repetition_penalty={repetition_penalty} needs the device sampling switch "
+                                      "(MYRIAD_DEVICE_SAMPLING=1 or llama.device_sampling = True)")
+        if seeds is not None and not dev_sample:
+            raise ValueError("seeds= names the device sampler's per-request streams: it needs do_sample with device_sampling on")
+        rows_tail = dev_sample or penalty or min_length > 1          # else exactly the launches of the plain slot step
+        # the attention kernel of every token step of this call, chosen once: `run` does not know its lengths up front
+        split = self.split_kv
+        if split is None:
+            live_rows, longest = (self.slots, 0) if turns is None else (len(turns), max([int(t[1].shape[0]) for t in turns], default=0))
+            split = split_kv_rows_rule(live_rows, L.H, longest)
+        ws = self._workspace(inv_temp, (dev_sample, penalty) if rows_tail else None, split)
+        sched = SlotScheduler(self.slots, max_new_tokens, stop_ids, eos_id, ordered=ordered)
+        stats = dict(steps=0, graph_replays=0, graph_captures=self.graph_captures, prefills=0, live_row_steps=0, occupancy=0.0,
+                     host_sampled_rows=0, device_sampled_rows=0, prefill_passes=0, packed_rows=0, split_kv=bool(split))
+        packed = int(prefill_batch) != 1 or int(refill_min) != 1
+        # a request travels with the seed of its own stream (None unless the device draws)
+        if turns is None:
+            reqs = seeded_requests(requests, generator, seeds) if dev_sample else ((emb, None) for emb in requests)
+            plan = RefillPlanner(sched, reqs, prefill_batch, prefill_rows, refill_min, length=lambda q: int(q[0].shape[0]))
+        else:
+            # the stamp of DecodeSession: no cached row survives a change of the weights the step multiplies by
+            begun = self.sessions.plan([(t[0], list(t[2])) + t[3:] for t in turns], _cache_stamp(L, weights_version))
+            seeds_ = [sd for _, sd in seeded_requests(turns, generator, seeds)] if dev_sample else [None] * len(turns)
+            # a turn travels as (emb, seed, past) and is admitted in list order: its index is its place in `turns`
+            plan = TurnPlanner([(slot, (t[1], sd, past)) for t, sd, (slot, past, _) in zip(turns, seeds_, begun)], prefill_batch,
+                               prefill_rows, length=lambda q: int(q[0].shape[0]) - q[2])
+            stats["turns"] = [dict(context_tokens=int(t[1].shape[0]), reused_tokens=past, prefilled_tokens=int(t[1].shape[0]) - past,
+                                   full_reprefill_reason=reason) for t, (_, past, reason) in zip(turns, begun)]
+        self.last_stats = stats
+        run = _SlotRun(self, ws, sched, stats, turns, max_new_tokens=max_new_tokens, eos_id=eos_id, min_length=min_length,
+                       do_sample=do_sample, top_p=top_p, inv_temp=inv_temp, top_k=top_k, dev_sample=dev_sample, penalty=penalty,
+                       rows_tail=rows_tail, generator=generator)
+        ws["live"].zero_()                                           # an abandoned run may have left slots live
+        ws["step"].zero_()
+        if rows_tail:
+            ws["prm"].copy_(torch.tensor([inv_temp, top_p, float(top_k), float(repetition_penalty), float(min_length), float(eos_id)],
+                                         dtype=F32))
+        try:
+            while True:
+                group = plan.next_pass()
+                while group:
+                    run.refill(group, packed)
+                    group = plan.next_pass()
+                yield from run.results()
+                live = sched.live()
+                if not live:
+                    break
+                if L._launch_step(ws, run.token_step, -1, True, stats):
+                    self.graph_captures += 1
+                r = run.rec.cpu()                                    # the one device->host copy of the step (it also waits for it)
+                ids = run.host_draws(live, r)
+                finished = sched.step(ids, r[1].tolist())
+                for s in live:
+                    if s in finished:
+                        ws["live"][s:s + 1].zero_()
+                    elif ids[s] != int(r[0][s]):
+                        ws["ids"][s:s + 1].fill_(ids[s])             # a host draw replaces the arg-max the step fed back
+                yield from run.results()
+        finally:
+            stats.update(steps=sched.steps, live_row_steps=sched.live_row_steps, occupancy=sched.occupancy,
+                         graph_captures=self.graph_captures, prefill_passes=plan.passes, packed_rows=plan.packed_rows)
+
+
+class _SlotRun:
+    """One SlotDecoder._run call: its workspace view, scheduler, counters and knobs, and the pieces of its loop -- the token step,
+    the refill of free slots, the results that leave, the host's draws."""
+
+    def __init__(self, dec, ws, sched, stats, turns, **knobs):
+        self.dec, self.L, self.ws, self.sched, self.stats, self.turns = dec, dec.llama, ws, sched, stats, turns
+        # max_new_tokens, eos_id, min_length, do_sample, top_p, inv_temp, top_k, dev_sample, penalty, rows_tail, generator
+        vars(self).update(knobs)
+        self.ban0 = self.eos_id if 0 < self.min_length else -1
+        self.rec = ws["rec"] if self.rows_tail else ws["rec"][:3]
+        self.seed_of = {}                                            # slot -> its request's seed
+
+    def token_step(self, _ban):
+        ws, rec = self.ws, self.rec
+        self.L._step_logits(ws)
+        if not self.rows_tail:
+            ops.argmax_pmax_rows(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ban_id=-1, inv_temp=self.inv_temp)
+            ops.decode_advance_rows(ws["nxt"], ws["mar"], ws["pmx"], rec, ws["ids"], ws["step"], ws["pos"], ws["kvlen"],
+                                    ws["live"])
+            return
+        if self.penalty:                                             # ws["ids"] = the token fed in: it joins the seen set first
+            ops.repetition_penalty_rows_slots(ws["logits"], ws["seen"], ws["ids"], ws["prm"][3:], ws["live"])
+        if self.dev_sample:                                          # row r draws Philox step gen[r] of seed[r]
+            ops.sample_rows_slots(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ws["kept"], ws["prm"], ws["seed"], ws["gen"],
+                                  ws["live"])
+        else:
+            ops.argmax_pmax_rows_slots(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ws["prm"], ws["gen"], ws["live"])
+        ops.decode_advance_kept_rows(ws["nxt"], ws["mar"], ws["pmx"], ws["kept"] if self.dev_sample else None, rec, ws["ids"],
+                                     ws["step"], ws["pos"], ws["kvlen"], ws["gen"], ws["live"])
+
+    def results(self):
+        for index, ids, mar in self.sched.pop():
+            if self.turns is not None:                               # the slot now holds the context and every id but the last
+                session, _, keys = self.turns[index][:3]
+                self.dec.sessions.end(session, keys, ids)
+                index = session
+            yield index, torch.tensor(ids, dtype=torch.long), torch.tensor(mar, dtype=F32)
+
+    def fits(self, emb: torch.Tensor) -> int:
+        S0 = emb.shape[0] if emb.dim() == 2 else 0
+        room = min(self.dec.T_cap, self.L.cos.shape[0])
+        if S0 < 1 or S0 + self.max_new_tokens > room:
+            raise ValueError(f"request of shape {tuple(emb.shape)} + max_new_tokens {self.max_new_tokens} does not fit a slot of "
+                             f"{room} positions")
+        return S0
+
+    def go_live(self, s: int, first: int, S0: int, seed) -> None:
+        ws, sl = self.ws, slice(s, s + 1)
+        ws["ids"][sl].fill_(first)
+        ws["pos"][sl].fill_(S0)                                      # position of the incoming token
+        ws["kvlen"][sl].fill_(S0 + 1)                                # valid keys after the append
+        if self.rows_tail:
+            ws["gen"][sl].fill_(1)                                   # the prefill pick was token 0
+            if self.dev_sample:
+                ws["seed"][sl].fill_(seed)
+                self.seed_of[s] = seed
+            if self.penalty:
+                ws["seen"][sl].zero_()                               # generated ids only, and the last request's are gone
+        ws["live"][sl].fill_(1)
+
+    def first_picks(self, logits0: torch.Tensor, sl: slice, seeds_) -> list:
+        """The first pick of each prefilled request (rows of logits0) in one launch into the step's result buffers at `sl` and
+        one device->host copy: rows of [id, margin, p_max, kept].  The per-row tail's pick is its step kernel at gen = 0."""
+        ws = self.ws
+        out = [ws["nxt"][sl], ws["mar"][sl], ws["pmx"][sl]]
+        R = logits0.shape[0]
+        if self.dev_sample:
+            ws["seed0"][:R].copy_(torch.tensor(seeds_, dtype=torch.long))
+            ops.sample_rows_slots(logits0, *out, ws["kept"][sl], ws["prm"], ws["seed0"][:R], ws["gen0"][:R])
+            out.append(ws["kept"][sl])
+        elif self.rows_tail:
+            ops.argmax_pmax_rows_slots(logits0, *out, ws["prm"], ws["gen0"][:R])
+        else:
+            ops.argmax_pmax_rows(logits0, *out, ban_id=self.ban0, inv_temp=self.inv_temp)
+        return torch.stack([o.to(torch.float64) for o in out], 1).tolist()
+
+    def host_draw(self, logits_row: torch.Tensor, t: int, seed) -> int:
+        """Token t of a request, drawn on the host: from a generator derived from the request's seed and t where the device
+        sampler handed the row back, else from the run's own; the EOS ban is the step's for that t."""
+        self.stats["host_sampled_rows"] += 1
+        return _host_draw(logits_row, self.eos_id if t < self.min_length else -1, self.inv_temp, self.top_k, self.top_p,
+                          _request_generator(seed, t) if self.dev_sample else self.generator)
+
+    def first_id(self, pick, logits_row: torch.Tensor, seed) -> int:
+        """The request's first token from its pick: the device's draw, or the host's where the rules hand the row to it."""
+        if self.dev_sample and pick[3] >= 0:
+            self.stats["device_sampled_rows"] += 1
+        elif self.dev_sample or (self.do_sample and pick[2] < self.top_p):
+            return self.host_draw(logits_row, 0, seed)
+        return int(pick[0])
+
+    def refill(self, group, packed: bool) -> None:
+        """Prefill the group's requests, each into its slot: one request alone into the slot's slice of every cache (_prefill), or
+        -- `packed` -- the group in one packed pass (_prefill_packed; their GEMM plans differ).  Then one pick launch and one
+        device->host copy for all first picks, and admission in input order; a slot goes live if its request goes on."""
+        L, ws, turns = self.L, self.ws, self.turns
+        lens = [self.fits(req[0]) for _, req in group]
+        if packed:
+            pasts = None if turns is None else [req[2] for _, req in group]
+            logits0 = L._prefill_packed([req[0] for _, req in group], [s for s, _ in group], ws["caches"], pasts)
+        else:
+            (s, req), = group
+            logits0 = L._prefill(req[0][None].to(L.dev), [c[s:s + 1] for c in ws["caches"]], req[2] if turns is not None else 0)
+        sl = slice(0, len(group)) if packed else slice(s, s + 1)
+        self.stats["prefills"] += len(group)
+        picks = self.first_picks(logits0, sl, [req[1] for _, req in group])
+        for i, (s, req) in enumerate(group):
+            first = self.first_id(picks[i], logits0[i], req[1])
+            if self.sched.admit(s, first, picks[i][1]):
+                self.go_live(s, first, lens[i], req[1])
+
+    def host_draws(self, live, r) -> list:
+        """The ids of one token step's record `r`, with the rows the rules hand to the host drawn there."""
+        ids = r[0].long().tolist()
+        for s in live if self.do_sample else ():
+            if self.dev_sample and float(r[3][s]) >= 0:
+                self.stats["device_sampled_rows"] += 1               # drawn by the step itself
+            elif self.dev_sample or float(r[2][s]) < self.top_p:     # greedy_generate's rule per row: below top_p the host draws
+                t = len(self.sched.rows[s][1])                       # the row's gen when the step ran
+                ids[s] = self.host_draw(self.ws["logits"][s], t, self.seed_of.get(s))
+        return ids

@@ -1,0 +1,374 @@
+"""The host side of the decode loops, on plain Python values: nothing here sees a device or the HIP library, so a scripted run can
+drive every class.  The slot engine's bookkeeping (SlotScheduler), its refill and turn planners (RefillPlanner, TurnPlanner), the
+chat pool's session table (SessionTable), the per-request random streams (seeded_requests), the replay of a known run
+(replay_slot_run), the split-KV rules with their measurements, and the host draw of one row (_host_draw)."""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+
+
+def round_up(x: int, m: int) -> int:
+    return (x + m - 1) // m * m                                      # ops.round_up, restated: importing ops would load the library binding
+
+
+def _host_draw(logits_row: torch.Tensor, ban: int, inv_temp: float, top_k: int, top_p: float, generator) -> int:
+    """HF TopKLogitsWarper + TopPLogitsWarper + multinomial on one row (host)."""
+    lg = logits_row.float().cpu() * inv_temp
+    if ban >= 0:
+        lg[ban] = float("-inf")
+    if top_k and 0 < top_k < lg.numel():                             # HF applies TopKLogitsWarper (default top_k = 50) before top-p
+        lg = lg.masked_fill(lg < torch.topk(lg, top_k).values[-1], float("-inf"))
+    srt, idx = torch.sort(lg, descending=False)
+    cum = srt.softmax(-1).cumsum(-1)
+    remove = cum <= (1.0 - top_p)
+    remove[-1:] = False                                              # min_tokens_to_keep = 1
+    srt = srt.masked_fill(remove, float("-inf"))
+    probs = torch.zeros_like(lg).scatter(0, idx, srt.softmax(-1))
+    return int(torch.multinomial(probs, 1, generator=generator))
+
+
+# The chat session's token step uses the split-KV attention kernel (mh_attn_decode_rope_split) when the single-workgroup kernel
+# leaves most CUs idle and the cached context is long enough for the chunks to pay for the merge launch: B*H workgroups < 256 (the
+# CU count) and at least SPLIT_KV_MIN_KEYS keys when the turn starts.  Measured at batch 1 on the full-size model
+# (tools/chat_bench.py): ms per token split / single = 3.04 / 2.89 at 256 keys, 3.23 / 3.33 at 1,024,
+# 3.39 / 3.86 at 2,048.  Each kernel has its own captured graph in the session; the choice is made per turn.
+SPLIT_KV_MAX_ROWHEADS = 256
+SPLIT_KV_MIN_KEYS = 1024
+
+
+def split_kv_rule(B: int, H: int, kv_len: int) -> bool:
+    return B * H < SPLIT_KV_MAX_ROWHEADS and kv_len >= SPLIT_KV_MIN_KEYS
+
+
+# The slot engine's form of the rule (SlotDecoder(split_kv=None)): `live_rows` conversations decode in one call, the longest has
+# `max_kv_len` keys when it is admitted.  It says yes only where the split rows kernel was measured faster than the single-workgroup
+# rows kernel on the full-size model (tools/chat_bench.py --pool-split, DESIGN.md section 5, "Chat pool"; ms per token step,
+# split_kv False / True, both pools interleaved in one process): N = 1: 3.390 / 3.218 at 1,136 keys, 3.961 / 3.463 at 2,160;
+# N = 2: 3.688 / 3.578 and 4.235 / 3.875; N = 4: 3.982 / 3.987 and 4.562 / 4.619 -- at 128 row-heads the split kernel no longer
+# wins.  So: at most 64 row-heads (the largest product at which split won) and at least 1,024 keys (the shortest context at which
+# it won; the section 5 table says what was measured below that).
+SPLIT_KV_ROWS_MAX_ROWHEADS = 64
+SPLIT_KV_ROWS_MIN_KEYS = 1024
+
+
+def split_kv_rows_rule(live_rows: int, H: int, max_kv_len: int) -> bool:
+    return live_rows * H <= SPLIT_KV_ROWS_MAX_ROWHEADS and max_kv_len >= SPLIT_KV_ROWS_MIN_KEYS
+
+
+def common_prefix(a, b) -> int:
+    """Length of the longest common prefix of two key lists (the position keys of a context and of a cache)."""
+    n = min(len(a), len(b))
+    for i in range(n):
+        if a[i] != b[i]:
+            return i
+    return n
+
+
+class SlotScheduler:
+    """The bookkeeping of a decode-slot run, on plain Python values (no device in sight, so a scripted step can drive it): which
+    free slot takes which request, each slot's own ids and margins, when a slot finishes -- EOS, a stop sequence at the end of
+    ITS ids (kept in the output, as greedy_generate keeps row 0's), or max_new_tokens -- and the order results leave in.
+
+    One round of a run: `admit` requests into `free()` slots until none is free or the requests run out (a request whose first
+    pick already ends it never occupies a slot), then, while `live()`, one token step whose per-slot picks go to `step`.
+    `pop()` hands out finished (index, ids, margins): in completion order, or with `ordered` in admission (= input) order, a
+    result waiting for every earlier one."""
+
+    def __init__(self, slots: int, max_new_tokens: int, stop_ids=(), eos_id: int = 2, ordered: bool = False):
+        if slots < 1 or max_new_tokens < 1:
+            raise ValueError(f"slots and max_new_tokens must be >= 1, got {slots} and {max_new_tokens}")
+        self.slots, self.max_new_tokens, self.eos_id, self.ordered = int(slots), int(max_new_tokens), int(eos_id), bool(ordered)
+        self.stops = [tuple(int(t) for t in st) for st in stop_ids]
+        self.rows = [None] * self.slots                              # per slot: [index, ids, margins] while it decodes
+        self.admitted = 0
+        self._done, self._next_out = {}, 0
+        self.steps = self.live_row_steps = 0
+
+    def free(self) -> list:
+        return [s for s in range(self.slots) if self.rows[s] is None]
+
+    def live(self) -> list:
+        return [s for s in range(self.slots) if self.rows[s] is not None]
+
+    def _ended(self, ids: list) -> bool:
+        return (ids[-1] == self.eos_id or len(ids) >= self.max_new_tokens
+                or any(len(ids) >= len(st) and tuple(ids[-len(st):]) == st for st in self.stops))
+
+    def _finish(self, row) -> None:
+        self._done[row[0]] = (row[0], row[1], row[2])
+
+    def admit(self, slot: int, first_id: int, margin: float) -> bool:
+        """The next request (index = how many were admitted before it) with its prefill pick.  True: it decodes on in `slot`."""
+        if self.rows[slot] is not None:
+            raise ValueError(f"slot {slot} is busy")
+        row = [self.admitted, [int(first_id)], [float(margin)]]
+        self.admitted += 1
+        if self._ended(row[1]):
+            self._finish(row)
+            return False
+        self.rows[slot] = row
+        return True
+
+    def step(self, ids, margins) -> list:
+        """One token step's picks, indexed by slot (idle slots' entries are ignored).  Returns the slots that finished."""
+        live = self.live()
+        self.steps += 1
+        self.live_row_steps += len(live)
+        finished = []
+        for s in live:
+            row = self.rows[s]
+            row[1].append(int(ids[s]))
+            row[2].append(float(margins[s]))
+            if self._ended(row[1]):
+                self._finish(row)
+                self.rows[s] = None
+                finished.append(s)
+        return finished
+
+    def pop(self) -> list:
+        if not self.ordered:
+            out = [self._done.pop(k) for k in list(self._done)]      # dicts keep insertion (= completion) order
+        else:
+            out = []
+            while self._next_out in self._done:
+                out.append(self._done.pop(self._next_out))
+                self._next_out += 1
+        return out
+
+    @property
+    def occupancy(self) -> float:
+        return self.live_row_steps / (self.steps * self.slots) if self.steps else 0.0
+
+
+class RefillPlanner:
+    """Which waiting requests are prefilled together, and when: the host side of the slot engine's packed prefill, on plain Python
+    values like SlotScheduler (whose free / live slots it reads), so a scripted run can drive it.
+
+    `next_pass()` is asked at every refill point until it answers []: it hands out [(slot, request), ...] for ONE prefill pass --
+    the next waiting requests in input order, one per free slot in ascending slot order, at most `prefill_batch` of them and as
+    many as keep the pass's row count (the lengths' sum rounded up to 64) within `prefill_rows`; the first always goes, so a
+    request too long to share a pass, or longer than the cap, gets a pass of its own.  `refill_min` = k holds a pass back while
+    fewer than k slots are free, unless nothing is live or the requests have run out (the input ended and everything left is
+    waiting already: the planner looks one request past the pass it could fill).  prefill_batch = 1, refill_min = 1 is the
+    engine's one-request refill: the lowest free slot takes the next request, again if that one ended on its first pick."""
+
+    def __init__(self, sched: "SlotScheduler", requests, prefill_batch: int = 1, prefill_rows: int = 2048, refill_min: int = 1,
+                 length=len):
+        if prefill_batch < 1 or refill_min < 1 or prefill_rows < 1:
+            raise ValueError(f"prefill_batch, refill_min and prefill_rows must be >= 1, got {prefill_batch}, {refill_min} and "
+                             f"{prefill_rows}")
+        self.sched, self.it, self.more, self.waiting, self.length = sched, iter(requests), True, [], length
+        self.prefill_batch, self.prefill_rows = int(prefill_batch), int(prefill_rows)
+        self.refill_min = min(int(refill_min), sched.slots)
+        self.passes = self.packed_rows = 0
+
+    def next_pass(self) -> list:
+        free = self.sched.free()
+        if not free:
+            return []
+        want = min(self.prefill_batch, len(free))
+        while self.more and len(self.waiting) < want + (self.refill_min > 1):    # refill_min = 1 never needs to look ahead
+            try:
+                self.waiting.append(next(self.it))
+            except StopIteration:
+                self.more = False
+        if not self.waiting or (len(free) < self.refill_min and self.sched.live() and self.more):
+            return []
+        n, rows = 0, 0
+        for req in self.waiting[:want]:
+            if n and round_up(rows + self.length(req), 64) > self.prefill_rows:
+                break
+            n, rows = n + 1, rows + self.length(req)
+        group, self.waiting = self.waiting[:n], self.waiting[n:]
+        self.passes += 1
+        self.packed_rows += rows
+        return list(zip(free, group))
+
+
+class TurnPlanner:
+    """RefillPlanner's place in SlotDecoder.run_turns: every turn has ITS session's slot, so the passes are fixed when the call
+    starts -- the turns in list order, up to `prefill_batch` per pass and as many as keep the pass's NEW rows (rounded up to 64)
+    within `prefill_rows`; the first of a pass always goes.  `items` = [(slot, request)], `length(request)` = its new rows."""
+
+    def __init__(self, items, prefill_batch: int = 1, prefill_rows: int = 2048, length=len):
+        if prefill_batch < 1 or prefill_rows < 1:
+            raise ValueError(f"prefill_batch and prefill_rows must be >= 1, got {prefill_batch} and {prefill_rows}")
+        self.groups, self.passes, self.packed_rows = [], 0, 0
+        rows = 0
+        for item in items:
+            n = length(item[1])
+            if not self.groups or len(self.groups[-1]) >= int(prefill_batch) or round_up(rows + n, 64) > int(prefill_rows):
+                self.groups.append([])
+                rows = 0
+            self.groups[-1].append(item)
+            rows += n
+        self._length = length
+
+    def next_pass(self) -> list:
+        if not self.groups:
+            return []
+        group = self.groups.pop(0)
+        self.passes += 1
+        self.packed_rows += sum(self._length(req) for _, req in group)
+        return group
+
+
+class SessionTable:
+    """Which conversation lives in which decode slot, and what its slot's cache holds: the host side of SlotDecoder.run_turns, on
+    plain Python values like SlotScheduler (no device in sight).
+
+    At most `slots` sessions are open; a session (any object: hashable ones by value, others by identity, held until `close`)
+    is pinned to one slot from its first turn until `close(session)` frees it.  Per session the table keeps one key per cached
+    position, DecodeSession's convention: `begin(session, keys)` answers (slot, past, reason) with past =
+    min(common_prefix(keys, cached), len(keys) - 1) -- at least one row is always prefilled, it gives the first logits -- and
+    `end(session, keys, ids)` records the context's keys plus ("t", id) for ids[:-1]: the last pick of a turn has no KV, and a slot
+    row goes idle the moment its turn ends, so no id the host does not know is ever fed (DecodeSession's ("x",) case does not
+    arise).  Between `begin` and `end` the session's keys are dropped: a turn that fails or is abandoned midway leaves a cache
+    nobody trusts.
+
+    `sync(stamp)` is called with what the cached rows depend on -- (the caller's weights_version, _decode_weights_id, the merge
+    id of a merged qkv copy) -- before the turns of a call: whenever it moves, every session's keys are dropped, with
+    DecodeSession's reasons ("weights changed" / "decode weights changed").  `clear()` drops them all ("empty cache"): the
+    caches were overwritten.  `reason` is None when the cached rows were usable, whatever `past` came out."""
+
+    def __init__(self, slots: int):
+        if slots < 1:
+            raise ValueError(f"slots must be >= 1, got {slots}")
+        self.slots = int(slots)
+        self.stamp = None
+        self._open = {}                                              # key -> [session, slot, keys, why the keys are empty]
+
+    @staticmethod
+    def _key(session):
+        try:
+            hash(session)
+            return ("v", session)
+        except TypeError:
+            return ("id", id(session))                               # the entry holds the object, so the id stays its own
+
+    def __len__(self) -> int:
+        return len(self._open)
+
+    def __contains__(self, session) -> bool:
+        return self._key(session) in self._open
+
+    def slot_of(self, session) -> int:
+        return self._open[self._key(session)][1]
+
+    def keys_of(self, session) -> list:
+        return list(self._open[self._key(session)][2])
+
+    def open(self, session) -> int:
+        """The session's slot; a new session takes the lowest free one."""
+        k = self._key(session)
+        if k not in self._open:
+            used = {e[1] for e in self._open.values()}
+            if len(used) >= self.slots:
+                raise ValueError(f"all {self.slots} slots hold an open session: close() one before opening another")
+            self._open[k] = [session, min(set(range(self.slots)) - used), [], "empty cache"]
+        return self._open[k][1]
+
+    def close(self, session) -> None:
+        self._open.pop(self._key(session), None)
+
+    def drop(self, session, reason: str = "empty cache") -> None:
+        e = self._open.get(self._key(session))
+        if e is not None:
+            e[2], e[3] = [], reason
+
+    def clear(self, reason: str = "empty cache") -> None:
+        for e in self._open.values():
+            e[2], e[3] = [], reason
+
+    def sync(self, stamp) -> None:
+        if self.stamp is not None and stamp != self.stamp:
+            self.clear("weights changed" if stamp[0] != self.stamp[0] else "decode weights changed")
+        self.stamp = stamp
+
+    def begin(self, session, keys, reset_reason: Optional[str] = None):
+        slot = self.open(session)
+        e = self._open[self._key(session)]
+        if len(keys) < 1:
+            raise ValueError("a turn needs at least one context position")
+        reason = reset_reason if reset_reason is not None else (None if e[2] else e[3])
+        cached = [] if reason is not None else e[2]
+        past = min(common_prefix(keys, cached), len(keys) - 1)
+        e[2], e[3] = [], "empty cache"                               # until end(): the slot is being written
+        return slot, past, reason
+
+    def end(self, session, keys, ids) -> None:
+        e = self._open.get(self._key(session))
+        if e is not None:
+            e[2], e[3] = list(keys) + [("t", int(t)) for t in list(ids)[:-1]], None
+
+    def plan(self, turns, stamp):
+        """One run_turns call: `turns` = [(session, keys) or (session, keys, reset_reason)], at most one per session.  Syncs
+        the stamp and begins every turn; returns [(slot, past, reason)] in the turns' order."""
+        seen = set()
+        for t in turns:
+            k = self._key(t[0])
+            if k in seen:
+                raise ValueError("at most one turn per session in one call")
+            seen.add(k)
+        new = [k for k in seen if k not in self._open]
+        if len(self._open) + len(new) > self.slots:
+            raise ValueError(f"{len(self._open)} open sessions + {len(new)} new ones do not fit {self.slots} slots: close() some")
+        self.sync(stamp)
+        return [self.begin(t[0], t[1], t[2] if len(t) > 2 else None) for t in turns]
+
+
+def seeded_requests(requests, generator: Optional[torch.Generator] = None, seeds=None):
+    """Pairs every request with the seed of its own random stream: yields (request, seed) in input order.  The seed is drawn when
+    the request is taken from the input -- torch.randint(0, 2**63 - 1, (1,), generator=generator), the draw greedy_generate makes
+    once per call -- so request i gets the i-th draw however RefillPlanner groups or holds back the refills; `seeds` (an iterable
+    of ints in [0, 2**63), one per request in input order) replaces the draws and leaves `generator` untouched.  No device in
+    sight, like SlotScheduler and RefillPlanner."""
+    given = None if seeds is None else iter(seeds)
+    for req in requests:
+        if given is None:
+            seed = int(torch.randint(0, 2**63 - 1, (1,), generator=generator))
+        else:
+            seed = next(given, None)
+            if seed is None:
+                raise ValueError("seeds: fewer seeds than requests")
+            seed = int(seed)
+            if not 0 <= seed < 2**63:
+                raise ValueError(f"seeds: {seed} is outside [0, 2**63)")
+        yield req, seed
+
+
+def _request_generator(seed: int, t: int) -> torch.Generator:
+    """The host generator for token t of the request with `seed`: the rare row the device sampler hands back (kept = -1) is drawn
+    from it, never from the run's shared generator, so it cannot shift another request's stream."""
+    g = torch.Generator()
+    g.manual_seed((int(seed) * 0x9E3779B1 + int(t)) % 2**63)
+    return g
+
+
+def replay_slot_run(lengths, ids, slots: int, max_new_tokens: int, stop_ids=(), eos_id: int = 2, prefill_batch: int = 1,
+                    prefill_rows: int = 2048, refill_min: int = 1) -> dict:
+    """The counters of a slot run whose picks are known: request i has a prompt of lengths[i] rows and generates ids[i] (which must
+    end where the stop rule ends it).  SlotScheduler + RefillPlanner driven as SlotDecoder.run drives them, without a device."""
+    sched = SlotScheduler(slots, max_new_tokens, stop_ids, eos_id)
+    plan = RefillPlanner(sched, range(len(lengths)), prefill_batch, prefill_rows, refill_min, length=lambda i: lengths[i])
+    owner, prefills = [None] * slots, 0
+    while True:
+        group = plan.next_pass()
+        while group:
+            for s, i in group:
+                prefills += 1
+                if sched.admit(s, ids[i][0], 0.0):
+                    owner[s] = [i, 1]
+            group = plan.next_pass()
+        live = sched.live()
+        if not live:
+            break
+        picks = [0] * slots
+        for s in live:
+            picks[s] = ids[owner[s][0]][owner[s][1]]
+            owner[s][1] += 1
+        sched.step(picks, [0.0] * slots)
+    return dict(prefills=prefills, prefill_passes=plan.passes, packed_rows=plan.packed_rows, steps=sched.steps,
+                live_row_steps=sched.live_row_steps, occupancy=sched.occupancy)

@@ -86,7 +86,7 @@ def test_split_kv_rule():
 
 
 class _FakeLlama:
-    """What DecodeSession reads of LlamaHIP, on the CPU; _greedy_core returns scripted ids after the session's turn setup."""
+    """What DecodeSession reads of LlamaHIP, on the CPU; _greedy_core returns scripted ids once the session has set its turn up."""
 
     def __init__(self):
         self.H, self.D, self.V, self.layers, self.dev = 2, 8, 50, [None], torch.device("cpu")
@@ -94,9 +94,10 @@ class _FakeLlama:
         self.cos = torch.zeros((4096, 4))
         self.script = []
 
-    def _greedy_core(self, emb, session, max_new_tokens=90, **kw):
-        B, S0, _ = emb.shape
-        ws, past = session._begin_turn(B, S0, max_new_tokens, 1.0, False, False)
+    def _prepare_decode_weights(self, rows):
+        return {}
+
+    def _greedy_core(self, emb, ws, past, weight_stats, max_new_tokens=90, **kw):
         self.last_past = past
         ids = self.script.pop(0)
         self.last_generate_stats = dict(steps=ids.shape[1], graph_replays=0)

@@ -33,7 +33,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from myriad_amd import ops  # noqa: E402
-from myriad_amd.llama import DecodeSession, LlamaHIP  # noqa: E402
+from myriad_amd.decode import DecodeSession  # noqa: E402
+from myriad_amd.llama import LlamaHIP  # noqa: E402
 from myriad_amd.synthetic import SyntheticWeights, full_config  # noqa: E402
 
 ap = argparse.ArgumentParser()

@@ -3,7 +3,7 @@
 to both kinds of step, and every step's logits are compared (max |delta logit|, relative to the step's max |logit|, and top-1
 agreement).  Random weights: a sanity figure for the arithmetic, not a quality claim for a trained model.
 python tools/fp8_decode_drift.py [--steps 64] [--batch 1] [--prompt 32] [--llm-layers 32]"""
-import argparse, math, os, sys
+import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from myriad_amd import ops
@@ -31,15 +31,14 @@ def forced_logits(fp8: bool, feed: torch.Tensor) -> torch.Tensor:
     lm.decode_fp8 = fp8
     lm._pack_for_decode()
     caches = [torch.zeros((B, S0 + n + 2, 2 * D), dtype=torch.bfloat16, device=dev) for _ in lm.layers]
-    scale = 1.0 / math.sqrt(lm.hd)
-    pos = torch.arange(S0, dtype=torch.int32).repeat(B).to(dev)
-    lm._decode_block(emb.reshape(B * S0, D).contiguous(), B, S0, caches, scale, pos, past=0)
+    lm._prefill(emb, caches)                                          # fills the caches; its logits are not needed
     pos_dev = torch.full((B,), S0, dtype=torch.int32, device=dev)
     kvlen = torch.full((B,), S0 + 1, dtype=torch.int32, device=dev)
+    ws = dict(caches=caches, pos=pos_dev, kvlen=kvlen, split=None, row_limit=ops.GEMV_MAX_ROWS)   # what _step_layers reads
     out = []
     for t in range(n):
-        x = lm.embed[feed[:, t]].float().contiguous()
-        h = lm._decode_block(x, B, 1, caches, scale, pos_dev, pos_dev=pos_dev, kvlen_dev=kvlen)
+        ws["x_in"] = lm.embed[feed[:, t]].float().contiguous()
+        h = lm._step_layers(ws)
         out.append(ops.gemv_packed(ops.rmsnorm_fwd(h, lm.norm, lm.eps), lm._packed["lm_head"], out_dtype=torch.float32))
         pos_dev += 1
         kvlen += 1

@@ -38,7 +38,8 @@ def wrap(obj, attr, name):
 
 wrap(model, "encode_img", "encode_img (ViT + Q-Former + VE nets)")
 wrap(model.llama, "_pack_for_decode", "pack_for_decode")
-wrap(model.llama, "_decode_block", "decode_block (prefill / eager token step)")
+wrap(model.llama, "_prefill", "prefill (layers + last rows' lm-head)")
+wrap(model.llama, "_step_layers", "eager token step (layers)")
 if model.llama.lora is not None:
     wrap(model.llama.lora, "refresh", "lora.refresh")
 _g = torch.cuda.graph
