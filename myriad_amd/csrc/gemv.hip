@@ -10,7 +10,7 @@
 //     trip -- the operand is read once and never shared between waves).  The dot product does not care which k a
 //     lane holds as long as both operands agree, so lane (row, lg) takes 32 CONTIGUOUS bytes (k = 16*lg .. +15 of a
 //     64-deep step, two MFMAs): the four lanes of a row then cover one whole 128-B line per step instead of half of
-//     one (MODE 0, the first version, measured 3.9-4.2 TB/s);
+//     one (the first version, 16 B per lane of a 32-deep step, measured 3.9-4.2 TB/s; superseded in round 1 and since removed);
 //   * the activation rows (<= 16 x K bf16, L2-resident) are read as the A operand of v_mfma_f32_16x16x32_bf16, so
 //     one MFMA retires 1 KiB of weights: the matrix pipe is idle-cheap and exact-fp32 accumulation comes for free.
 //
@@ -30,9 +30,20 @@
 // 16-step batch costs four scale loads beside its sixteen code loads.  Each pair of codes is widened to bf16 in registers by
 // v_cvt_scalef32_pk_bf16_fp4 with the block scale 2^(b-127) as its scale operand -- exact, every code * scale is a normal bf16
 // or zero -- and fed to four v_mfma_f32_16x16x32_bf16 per step: products and fp32 sums are those of x . dq(W), no epilogue scale.
+//
+// Structure.  The three decode kernels -- gemv_kernel<2> (16 rows), gemv_pro_kernel (16 rows, the operand built in LDS by a
+// fused prologue) and gemv_wide_kernel (17..64 rows, G column blocks per workgroup) -- share
+//   gv_load / gv_mfma, gv_mfma_fp4, gv_fp4_widen, fp8x8_to_bf16   one step of a lane, by weight type;
+//   gv_fp4_load / gv_fp4_mfma   one batch of up to UNROLL fp4 steps (gemv_kernel<2> and gemv_pro_kernel).  The bf16 / fp8 batch
+//                    loops of those two kernels and the wide kernel's batch keep their own text: folded into shared helpers they
+//                    no longer compile to today's instruction streams;
+//   gv_red_put / gv_red_finish / gv_finish   the cross-wave sum through LDS and the epilogue (fp8 row scale, alpha, bias,
+//                    residual, store), one text for all three kernels and the row-major MODE 1.
+// Host side: the twelve product entries {plain, RMSNorm, SiLU, wide} x {bf16, fp8, fp4} are one argument record (GvArgs) and one
+// entry body (gv_entry) in front of the three launchers; the layout rule of the packed copies (waves, steps per wave, column
+// blocks) is gv_layout in gemv_pack.h, shared with every packer and with lora_merge.hip.
 #include "common.h"
 #include "gemv_pack.h"
-#include <cstdlib>
 #include <type_traits>
 
 typedef unsigned char fp8_t;                                        // one OCP e4m3fn code
@@ -74,6 +85,16 @@ __device__ __forceinline__ float4_t gv_mfma(short8_t x0, short8_t x1, short8_t w
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1, w1, acc, 0, 0, 0);
 }
 
+// 8 e2m1 codes (one dword, k ascending from the low nibble, one byte_sel each pair) times the block scale -> 8 bf16 in MFMA
+// operand order; exact
+__device__ __forceinline__ short8_t gv_fp4_widen(unsigned q, float sc) {
+  gv_u4_t r;
+  r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 0));
+  r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 1));
+  r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 2));
+  r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 3));
+  return __builtin_bit_cast(short8_t, r);
+}
 // One lane's 128-deep fp4 step: x = its 32 activations (k = 32*lg .. +31 of the step, global memory or LDS), q = its 32 codes,
 // b = the block's scale byte.  Eight codes (one dword, one byte_sel each pair) make the B operand of one MFMA.
 __device__ __forceinline__ float4_t gv_mfma_fp4(const bf16_t* x, short8_t q16, unsigned b, float4_t acc) {
@@ -81,13 +102,8 @@ __device__ __forceinline__ float4_t gv_mfma_fp4(const bf16_t* x, short8_t q16, u
   const float sc = __uint_as_float(b << 23);                        // 2^(b-127), b in 2..252
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    gv_u4_t r;
-    r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q[i], sc, 0));
-    r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q[i], sc, 1));
-    r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q[i], sc, 2));
-    r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q[i], sc, 3));
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const short8_t*>(x + 8 * i), __builtin_bit_cast(short8_t, r), acc,
-                                                  0, 0, 0);
+    const short8_t w = gv_fp4_widen(q[i], sc);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const short8_t*>(x + 8 * i), w, acc, 0, 0, 0);
   }
   return acc;
 }
@@ -113,6 +129,35 @@ __device__ __forceinline__ float4_t gv_fp4_mfma(const bf16_t* x, int n, const sh
   return acc;
 }
 
+// The epilogue of one output element of all three kernels: v is the cross-wave sum (times the fp8 row scale)
+__device__ __forceinline__ void gv_finish(float v, int m, int n, void* Cv, const float* bias, const float* res, int ldc, int ldr,
+                                          int out_f32, float alpha) {
+  v *= alpha;
+  if (bias) v += bias[n];
+  if (res) v += res[(size_t)m * ldr + n];
+  if (out_f32) reinterpret_cast<float*>(Cv)[(size_t)m * ldc + n] = v;
+  else reinterpret_cast<bf16_t*>(Cv)[(size_t)m * ldc + n] = f2bf(v);
+}
+// The cross-wave K reduction through LDS, red[wave][column block of the group][16 x 16].  D layout: row 4*lg + r, col lr.
+// gv_red_put: a wave's partial sums of block g (a barrier follows).  gv_red_finish: element (ml, lr) of block g, summed over
+// w = 0 .. NW-1 from 0.f, the fp8 row scale s_n first, then gv_finish.
+template <int NW, int G>
+__device__ __forceinline__ void gv_red_put(float (&red)[NW][G][16 * 16], int wave, int g, int lr, int lg, float4_t acc) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) red[wave][g][(4 * lg + r) * 16 + lr] = acc[r];
+}
+template <int NW, int G, bool F8>
+__device__ __forceinline__ void gv_red_finish(const float (&red)[NW][G][16 * 16], int g, int ml, int lr, int m, int n, void* Cv,
+                                              const float* bias, const float* res, int ldc, int ldr, int out_f32, float alpha,
+                                              const float* wscale) {
+  float v = 0.f;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) v += red[w][g][ml * 16 + lr];
+  if constexpr (F8) v *= wscale[n];              // the row scale s_n first, then alpha
+  gv_finish(v, m, n, Cv, bias, res, ldc, ldr, out_f32, alpha);
+}
+
+// MODE 1: B row-major [N, ldb] (the M <= 16 path of mh_gemm_bf16_nt).  MODE 2: B as a packed copy (bf16, fp8 or fp4).
 template <int MODE, int UNROLL, int GV_NW, typename WT = bf16_t>
 __global__ __launch_bounds__(GV_NW * 64) void gemv_kernel(const bf16_t* __restrict__ A, const WT* __restrict__ B,
                                                           void* __restrict__ Cv, const float* __restrict__ bias,
@@ -121,8 +166,9 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_kernel(const bf16_t* __restri
                                                           const float* __restrict__ wscale = nullptr) {
   constexpr bool F4 = gv_is_fp4<WT>, F8 = sizeof(WT) == 1 && !F4;
   constexpr int KS = F4 ? 128 : 64;                                // k-depth of one step of the packed copy
+  static_assert(MODE == 1 || MODE == 2, "row-major or the packed copy");
   static_assert(!(F8 || F4) || MODE == 2, "fp8 / fp4 weights come only as the packed copy");
-  __shared__ float red[GV_NW][16 * 16];
+  __shared__ float red[GV_NW][1][16 * 16];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lr = lane & 15, lg = lane >> 4;
   const int n0 = blockIdx.x * 16;
@@ -130,30 +176,7 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_kernel(const bf16_t* __restri
   nrow = nrow < N ? nrow : N - 1;
   const int mrow = lr < M ? lr : M - 1;          // rows >= M duplicate the last row; their results are never stored
   float4_t acc = (float4_t){0.f, 0.f, 0.f, 0.f};
-  if constexpr (MODE == 0) {
-    const bf16_t* wp = B + (size_t)nrow * ldb + lg * 8;
-    const bf16_t* xp = A + (size_t)mrow * lda + lg * 8;
-    const int nsteps = K / 32;
-    // wave w takes 32-deep steps w, w+4, w+8, ...; UNROLL independent loads in flight per lane
-    int s = wave;
-    for (; s + (UNROLL - 1) * GV_NW < nsteps; s += UNROLL * GV_NW) {
-      short8_t wv[UNROLL], xv[UNROLL];
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int k = (s + u * GV_NW) * 32;
-        wv[u] = __builtin_nontemporal_load(reinterpret_cast<const short8_t*>(wp + k));   // streamed once
-        xv[u] = *reinterpret_cast<const short8_t*>(xp + k);
-      }
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xv[u], wv[u], acc, 0, 0, 0);
-    }
-    for (; s < nsteps; s += GV_NW) {
-      const int k = s * 32;
-      const short8_t wv = *reinterpret_cast<const short8_t*>(wp + k);
-      const short8_t xv = *reinterpret_cast<const short8_t*>(xp + k);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xv, wv, acc, 0, 0, 0);
-    }
-  } else if constexpr (MODE == 2) {
+  if constexpr (MODE == 2) {
     // MODE 1's arithmetic on a pre-permuted weight copy (mh_gemv_pack): the bytes lane (lr, lg) of wave w needs at step t
     // sit at ((block * NW + w) * per + t) * 2 KiB + h * 1 KiB + lane * 16, so every wave-instruction reads one contiguous
     // KiB and a wave walks one contiguous region -- 6.8 TB/s against 5.8 TB/s for the row-strided order on a pure stream
@@ -243,57 +266,33 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_kernel(const bf16_t* __restri
     }
   }
   // D layout: row m = 4*lg + r, col n = lr.  Cross-wave K reduction through LDS, then wave 0 finishes.
-#pragma unroll
-  for (int r = 0; r < 4; ++r) red[wave][(4 * lg + r) * 16 + lr] = acc[r];
+  gv_red_put(red, wave, 0, lr, lg, acc);         // one column block: wave 0 finishes it
   __syncthreads();
   if (wave == 0) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int m = 4 * lg + r, n = n0 + lr;
-      if (m < M && n < N) {
-        float v = 0.f;
-#pragma unroll
-        for (int w = 0; w < GV_NW; ++w) v += red[w][m * 16 + lr];
-        if constexpr (F8) v *= wscale[n];              // the row scale s_n first, then alpha
-        v *= alpha;
-        if (bias) v += bias[n];
-        if (res) v += res[(size_t)m * ldr + n];
-        if (out_f32) reinterpret_cast<float*>(Cv)[(size_t)m * ldc + n] = v;
-        else reinterpret_cast<bf16_t*>(Cv)[(size_t)m * ldc + n] = f2bf(v);
-      }
+      if (m < M && n < N) gv_red_finish<GV_NW, 1, F8>(red, 0, m, lr, m, n, Cv, bias, res, ldc, ldr, out_f32, alpha, wscale);
     }
   }
 }
 
-// called from mh_gemm_bf16_nt for M <= 16 (no GELU epilogue on this path)
+// called from mh_gemm_bf16_nt for M <= 16 (no GELU epilogue on this path): 8 waves when N / 16 workgroups under-fill the chip
+// (N = 4096, K = 11008: 4.12 vs 3.86 TB/s with 8 waves), else 4 -- gv_packed_nw, the rule of the packed copies
 int mh_launch_gemv(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
                    const float* bias, const float* residual, int ldr, int out_f32, float alpha, hipStream_t stream) {
-  static int mode = -1;
-  if (mode < 0) {
-    const char* e = getenv("MYRIAD_GEMV_MODE");   // debug: A/B of the load patterns
-    mode = e ? atoi(e) : 1;
-  }
-  static int nw_small = -1;
-  if (nw_small < 0) {
-    const char* e = getenv("MYRIAD_GEMV_NW");     // debug: waves per workgroup when N/16 under-fills the chip
-    nw_small = e ? atoi(e) : 8;                   // N = 4096, K = 11008: 4.12 vs 3.86 TB/s with 8 waves
-  }
   const dim3 grid((N + 15) / 16);
-#define GV_LAUNCH(MODE, UNR, NW)                                                                                      \
-  hipLaunchKernelGGL((gemv_kernel<MODE, UNR, NW>), grid, dim3(NW * 64), 0, stream, (const bf16_t*)A, (const bf16_t*)B, \
-                     C, bias, residual, M, N, K, lda, ldb, ldc, ldr, out_f32, alpha)
-  const bool small = (N + 15) / 16 < 512;
-  if (mode == 0) GV_LAUNCH(0, 8, 4);
-  else if (small && nw_small == 8) GV_LAUNCH(1, 8, 8);
-  else if (small && nw_small == 16) GV_LAUNCH(1, 4, 16);
-  else GV_LAUNCH(1, 8, 4);
+#define GV_LAUNCH(NW)                                                                                                \
+  hipLaunchKernelGGL((gemv_kernel<1, 8, NW>), grid, dim3(NW * 64), 0, stream, (const bf16_t*)A, (const bf16_t*)B, C, \
+                     bias, residual, M, N, K, lda, ldb, ldc, ldr, out_f32, alpha)
+  if (gv_packed_nw(N) == 8) GV_LAUNCH(8);
+  else GV_LAUNCH(4);
 #undef GV_LAUNCH
   MH_CHECK_LAUNCH();
   return MH_OK;
 }
 
 // ---- stream-ordered weight copy for decode (288 GB of HBM: a second, 13.5 GB copy of the frozen LLaMA weights is cheap) ----
-// gv_packed_nw (gemv_pack.h) is the launch rule above, without the env knob
 
 __global__ void gemv_pack_kernel(const bf16_t* __restrict__ W, int ldb, int N, int K, bf16_t* __restrict__ out, int nw, int per,
                                  long chunks) {
@@ -316,17 +315,17 @@ __global__ void gemv_pack_kernel(const bf16_t* __restrict__ W, int ldb, int N, i
 
 extern "C" long mh_gemv_pack_elems(int N, int K) {
   if (N <= 0 || K <= 0 || (K % 64) != 0) return -1;
-  const int nw = gv_packed_nw(N), per = (K / 64 + nw - 1) / nw;
-  return (long)((N + 15) / 16) * nw * per * 1024;
+  const GvLayout L = gv_layout(N, K, 64);
+  return (long)L.blocks * L.nw * L.per * 1024;
 }
 
 extern "C" int mh_gemv_pack(const void* W, int ldb, int N, int K, void* out, hipStream_t stream) {
   if (N <= 0 || K <= 0 || (K % 64) != 0 || (ldb % 8) != 0 || ((uintptr_t)W & 15) || ((uintptr_t)out & 15)) return MH_ERR_ARG;
-  const int nw = gv_packed_nw(N), per = (K / 64 + nw - 1) / nw;
-  const long chunks = (long)((N + 15) / 16) * nw * per * 128;
+  const GvLayout L = gv_layout(N, K, 64);
+  const long chunks = (long)L.blocks * L.nw * L.per * 128;
   long grid = (chunks + 255) / 256;
   if (grid > 65536) grid = 65536;
-  hipLaunchKernelGGL(gemv_pack_kernel, dim3((int)grid), dim3(256), 0, stream, (const bf16_t*)W, ldb, N, K, (bf16_t*)out, nw, per,
+  hipLaunchKernelGGL(gemv_pack_kernel, dim3((int)grid), dim3(256), 0, stream, (const bf16_t*)W, ldb, N, K, (bf16_t*)out, L.nw, L.per,
                      chunks);
   MH_CHECK_LAUNCH();
   return MH_OK;
@@ -337,27 +336,41 @@ extern "C" int mh_gemv_pack(const void* W, int ldb, int N, int K, void* out, hip
 template <typename WT> struct GvUnroll { static constexpr int value = sizeof(WT) == 1 ? 16 : 8; };
 template <typename WT> constexpr int gv_kstep = gv_is_fp4<WT> ? 128 : 64;
 
+// ---- the product entries' host side: one argument record, one launcher per kernel, one entry body ---------------------------
+// The arguments of a product entry.  A: the activations (bf16 rows; the fused forms: f32 rows h or bf16 gate|up rows), lda in
+// elements; P / wscale: the packed copy and its fp8 row scales or fp4 scale bytes (null for bf16); norm_w / eps: RMSNorm only.
+struct GvArgs {
+  const void* A;
+  long lda;                  // the fused forms' leading dimension is a long; the bf16-row forms get an int and pass one on
+  const void* P;
+  const void* wscale;
+  void* C;
+  int ldc, M, N, K;
+  const float* bias;
+  const float* residual;
+  int ldr, out_f32;
+  float alpha;
+  hipStream_t stream;
+  const float* norm_w = nullptr;
+  float eps = 0.f;
+};
+// what is in front of the product.  GV_SILU / GV_RMSNORM are gemv_pro_kernel's PRO; GV_PLAIN and GV_WIDE never reach that kernel
+enum { GV_PLAIN = 0, GV_SILU = 1, GV_RMSNORM = 2, GV_WIDE = 3 };
+
 template <typename WT>
-static int launch_gemv_packed(const void* A, int lda, const void* P, const float* wscale, void* C, int ldc, int M, int N, int K,
-                              const float* bias, const float* residual, int ldr, int out_f32, float alpha, hipStream_t stream) {
-  if (M <= 0 || N <= 0) return MH_OK;
-  if (M > 16 || K <= 0 || (K % gv_kstep<WT>) != 0 || (lda % 8) != 0 || ((uintptr_t)A & 15) || ((uintptr_t)P & 15)) return MH_ERR_ARG;
+static int launch_gemv_packed(const GvArgs& a) {
+  if (a.M > 16 || a.K <= 0 || (a.K % gv_kstep<WT>) != 0 || (a.lda % 8) != 0 || ((uintptr_t)a.A & 15) || ((uintptr_t)a.P & 15))
+    return MH_ERR_ARG;
   constexpr int U = GvUnroll<WT>::value;
-  const dim3 grid((N + 15) / 16);
-  if (gv_packed_nw(N) == 8)
-    hipLaunchKernelGGL((gemv_kernel<2, U, 8, WT>), grid, dim3(512), 0, stream, (const bf16_t*)A, (const WT*)P, C, bias, residual, M,
-                       N, K, lda, 0, ldc, ldr, out_f32, alpha, wscale);
-  else
-    hipLaunchKernelGGL((gemv_kernel<2, U, 4, WT>), grid, dim3(256), 0, stream, (const bf16_t*)A, (const WT*)P, C, bias, residual, M,
-                       N, K, lda, 0, ldc, ldr, out_f32, alpha, wscale);
+  const GvLayout L = gv_layout(a.N, a.K, gv_kstep<WT>);
+#define GV_LAUNCH(NW)                                                                                                            \
+  hipLaunchKernelGGL((gemv_kernel<2, U, NW, WT>), dim3(L.blocks), dim3(NW * 64), 0, a.stream, (const bf16_t*)a.A, (const WT*)a.P, \
+                     a.C, a.bias, a.residual, a.M, a.N, a.K, (int)a.lda, 0, a.ldc, a.ldr, a.out_f32, a.alpha, (const float*)a.wscale)
+  if (L.nw == 8) GV_LAUNCH(8);
+  else GV_LAUNCH(4);
+#undef GV_LAUNCH
   MH_CHECK_LAUNCH();
   return MH_OK;
-}
-
-// C[M <= 16, N] = alpha * A . W^T (+bias) (+residual) with W given as its mh_gemv_pack copy
-extern "C" int mh_gemv_packed(const void* A, int lda, const void* P, void* C, int ldc, int M, int N, int K, const float* bias,
-                              const float* residual, int ldr, int out_f32, float alpha, hipStream_t stream) {
-  return launch_gemv_packed<bf16_t>(A, lda, P, nullptr, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream);
 }
 
 // ---- fp8 (e4m3fn) weight-only copy: row scale, quantisation and the stream order in one kernel ----------------------------
@@ -421,18 +434,11 @@ extern "C" int mh_gemv_pack_fp8(const void* W, int ldb, int N, int K, void* q_ou
   if (N <= 0 || K <= 0 || (K % 64) != 0 || (ldb % 8) != 0 || ldb < K || !scale_out || ((uintptr_t)W & 15) || ((uintptr_t)q_out & 15) ||
       ((uintptr_t)scale_out & 3))
     return MH_ERR_ARG;
-  const int nw = gv_packed_nw(N), per = (K / 64 + nw - 1) / nw;
-  hipLaunchKernelGGL(gemv_pack_fp8_kernel, dim3((N + 15) / 16), dim3(256), 0, stream, (const bf16_t*)W, ldb, N, K, (unsigned char*)q_out,
-                     scale_out, nw, per);
+  const GvLayout L = gv_layout(N, K, 64);
+  hipLaunchKernelGGL(gemv_pack_fp8_kernel, dim3(L.blocks), dim3(256), 0, stream, (const bf16_t*)W, ldb, N, K, (unsigned char*)q_out,
+                     scale_out, L.nw, L.per);
   MH_CHECK_LAUNCH();
   return MH_OK;
-}
-
-// C[M <= 16, N] = alpha * s_n * A . q^T (+bias) (+residual) with W given as its mh_gemv_pack_fp8 copy (q, s)
-extern "C" int mh_gemv_packed_fp8(const void* A, int lda, const void* Q, const float* scale, void* C, int ldc, int M, int N, int K,
-                                  const float* bias, const float* residual, int ldr, int out_f32, float alpha, hipStream_t stream) {
-  if (M > 0 && N > 0 && (!scale || ((uintptr_t)scale & 3))) return MH_ERR_ARG;
-  return launch_gemv_packed<fp8_t>(A, lda, Q, scale, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream);
 }
 
 // ---- decode GEMV with the producer of its activation operand fused in (one launch instead of two per Linear) ---------------
@@ -455,7 +461,7 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_pro_kernel(const void* __rest
   constexpr int KS = F4 ? 128 : 64;                                // k-depth of one step of the packed copy
   extern __shared__ __attribute__((aligned(16))) char gsm[];
   bf16_t* xs = reinterpret_cast<bf16_t*>(gsm);                  // [M][K] operand rows
-  __shared__ float red[GV_NW][16 * 16];
+  __shared__ float red[GV_NW][1][16 * 16];
   __shared__ float bred[GV_NW];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 15, lg = lane >> 4;
@@ -573,85 +579,44 @@ __global__ __launch_bounds__(GV_NW * 64) void gemv_pro_kernel(const void* __rest
         }
     }
   }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) red[wave][(4 * lg + r) * 16 + lr] = acc[r];
+  gv_red_put(red, wave, 0, lr, lg, acc);         // one column block: wave 0 finishes it
   __syncthreads();
   if (wave == 0) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int m = 4 * lg + r, n = n0 + lr;
-      if (m < M && n < N) {
-        float v = 0.f;
-#pragma unroll
-        for (int w = 0; w < GV_NW; ++w) v += red[w][m * 16 + lr];
-        if constexpr (F8) v *= wscale[n];              // the row scale s_n first, then alpha
-        v *= alpha;
-        if (bias) v += bias[n];
-        if (res) v += res[(size_t)m * ldr + n];
-        if (out_f32) reinterpret_cast<float*>(Cv)[(size_t)m * ldc + n] = v;
-        else reinterpret_cast<bf16_t*>(Cv)[(size_t)m * ldc + n] = f2bf(v);
-      }
+      if (m < M && n < N) gv_red_finish<GV_NW, 1, F8>(red, 0, m, lr, m, n, Cv, bias, res, ldc, ldr, out_f32, alpha, wscale);
     }
   }
 }
 
 #define GV_PRO_LDS_MAX (64 * 1024)
 #define GV_PRO_MAX_ROWS 2
-template <int PRO, typename WT = bf16_t>
-static int launch_gemv_pro(const void* A, long lda, const void* P, void* C, int ldc, int M, int N, int K, const float* bias,
-                           const float* residual, int ldr, int out_f32, float alpha, const float* norm_w, float eps,
-                           hipStream_t stream, const float* wscale = nullptr) {
-  if (M <= 0 || N <= 0) return MH_OK;
-  if (M > 16 || K <= 0 || (K % gv_kstep<WT>) != 0 || ((uintptr_t)A & 15) || ((uintptr_t)P & 15)) return MH_ERR_ARG;
-  if (sizeof(WT) == 1 && (!wscale || ((uintptr_t)wscale & 3))) return MH_ERR_ARG;
-  if (PRO == 1 && ((K % 128) != 0 || (lda % 8) != 0 || lda < 2L * K)) return MH_ERR_ARG;
-  if (PRO == 2 && (!norm_w || (K % 4) != 0 || (lda % 4) != 0)) return MH_ERR_ARG;
-  if (PRO == 2 && K > 4096) return MH_ERR_UNSUPPORTED;
+template <int PRO, typename WT>
+static int launch_gemv_pro(const GvArgs& a) {
+  const int M = a.M, K = a.K;
+  if (M > 16 || K <= 0 || (K % gv_kstep<WT>) != 0 || ((uintptr_t)a.A & 15) || ((uintptr_t)a.P & 15)) return MH_ERR_ARG;
+  if (PRO == GV_SILU && ((K % 128) != 0 || (a.lda % 8) != 0 || a.lda < 2L * K)) return MH_ERR_ARG;
+  if (PRO == GV_RMSNORM && (!a.norm_w || (K % 4) != 0 || (a.lda % 4) != 0)) return MH_ERR_ARG;
+  if (PRO == GV_RMSNORM && K > 4096) return MH_ERR_UNSUPPORTED;
   const size_t sh = (size_t)M * K * 2;
   // every workgroup rebuilds all M rows: measured at batch 8 (decode, M = 8) the fused step costs 6.5 ms per token against
   // 4.1 ms with the separate launches, at batch 1 it saves 0.3 ms -- fused for up to GV_PRO_MAX_ROWS rows only
   if (sh > GV_PRO_LDS_MAX || M > GV_PRO_MAX_ROWS) return MH_ERR_UNSUPPORTED;        // the caller falls back to the two-launch form
   constexpr int U = GvUnroll<WT>::value;
-  const dim3 grid((N + 15) / 16);
+  const GvLayout L = gv_layout(a.N, K, gv_kstep<WT>);
   static bool attr8 = false, attr4 = false;                   // once per instantiation, outside any stream capture
-  if (gv_packed_nw(N) == 8) {
-    if (!attr8) { (void)hipFuncSetAttribute((const void*)gemv_pro_kernel<U, 8, PRO, WT>, hipFuncAttributeMaxDynamicSharedMemorySize, GV_PRO_LDS_MAX); attr8 = true; }
-    hipLaunchKernelGGL((gemv_pro_kernel<U, 8, PRO, WT>), grid, dim3(512), sh, stream, A, lda, (const WT*)P, C, bias, residual, M, N, K,
-                       ldc, ldr, out_f32, alpha, norm_w, eps, wscale);
-  } else {
-    if (!attr4) { (void)hipFuncSetAttribute((const void*)gemv_pro_kernel<U, 4, PRO, WT>, hipFuncAttributeMaxDynamicSharedMemorySize, GV_PRO_LDS_MAX); attr4 = true; }
-    hipLaunchKernelGGL((gemv_pro_kernel<U, 4, PRO, WT>), grid, dim3(256), sh, stream, A, lda, (const WT*)P, C, bias, residual, M, N, K,
-                       ldc, ldr, out_f32, alpha, norm_w, eps, wscale);
-  }
+#define GV_LAUNCH(NW, attr)                                                                                                        \
+  do {                                                                                                                             \
+    if (!attr) { (void)hipFuncSetAttribute((const void*)gemv_pro_kernel<U, NW, PRO, WT>, hipFuncAttributeMaxDynamicSharedMemorySize, GV_PRO_LDS_MAX); attr = true; } \
+    hipLaunchKernelGGL((gemv_pro_kernel<U, NW, PRO, WT>), dim3(L.blocks), dim3(NW * 64), sh, a.stream, a.A, a.lda, (const WT*)a.P, a.C, \
+                       a.bias, a.residual, M, a.N, K, a.ldc, a.ldr, a.out_f32, a.alpha, a.norm_w, a.eps, (const float*)a.wscale);   \
+  } while (0)
+  if (L.nw == 8) GV_LAUNCH(8, attr8);
+  else GV_LAUNCH(4, attr4);
+#undef GV_LAUNCH
   MH_CHECK_LAUNCH();
   return MH_OK;
-}
-
-// C[M <= 16, N] = alpha * rmsnorm(H; norm_w, eps) . W^T (+bias) (+residual), W as its mh_gemv_pack copy; H [M, K] f32.
-// MH_ERR_UNSUPPORTED when M * K * 2 bytes of operand do not fit the kernel's LDS budget (64 KiB).
-extern "C" int mh_gemv_packed_rmsnorm(const float* H, long ldh, const float* norm_w, float eps, const void* P, void* C, int ldc,
-                                      int M, int N, int K, const float* bias, const float* residual, int ldr, int out_f32,
-                                      float alpha, hipStream_t stream) {
-  return launch_gemv_pro<2>(H, ldh, P, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, norm_w, eps, stream);
-}
-
-// C[M <= 16, N] = alpha * (silu(g) * u) . W^T (+bias) (+residual): gu [M, >= 2K] bf16, gate / up interleaved in blocks of 128.
-extern "C" int mh_gemv_packed_silu(const void* gu, long ldgu, const void* P, void* C, int ldc, int M, int N, int K,
-                                   const float* bias, const float* residual, int ldr, int out_f32, float alpha, hipStream_t stream) {
-  return launch_gemv_pro<1>(gu, ldgu, P, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, nullptr, 0.f, stream);
-}
-
-// the two fused forms on the fp8 copy (q, s): the same prologues, the same contract
-extern "C" int mh_gemv_packed_fp8_rmsnorm(const float* H, long ldh, const float* norm_w, float eps, const void* Q, const float* scale,
-                                          void* C, int ldc, int M, int N, int K, const float* bias, const float* residual, int ldr,
-                                          int out_f32, float alpha, hipStream_t stream) {
-  return launch_gemv_pro<2, fp8_t>(H, ldh, Q, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, norm_w, eps, stream, scale);
-}
-
-extern "C" int mh_gemv_packed_fp8_silu(const void* gu, long ldgu, const void* Q, const float* scale, void* C, int ldc, int M, int N,
-                                       int K, const float* bias, const float* residual, int ldr, int out_f32, float alpha,
-                                       hipStream_t stream) {
-  return launch_gemv_pro<1, fp8_t>(gu, ldgu, Q, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, nullptr, 0.f, stream, scale);
 }
 
 // ---- MXFP4 weight-only copy: block amax, scale byte, e2m1 codes and the stream order in one kernel --------------------------
@@ -699,47 +664,25 @@ static bool gv_fp4_dims(int N, int K) { return N > 0 && K > 0 && (K % 128) == 0;
 
 extern "C" long mh_gemv_pack_fp4_elems(int N, int K) {
   if (!gv_fp4_dims(N, K)) return -1;
-  const int nw = gv_packed_nw(N), per = (K / 128 + nw - 1) / nw;
-  return (long)((N + 15) / 16) * nw * per * 1024;
+  const GvLayout L = gv_layout(N, K, 128);
+  return (long)L.blocks * L.nw * L.per * 1024;
 }
 
 extern "C" long mh_gemv_pack_fp4_scale_elems(int N, int K) {
   if (!gv_fp4_dims(N, K)) return -1;
-  const int nw = gv_packed_nw(N), per = (K / 128 + nw - 1) / nw;
-  return (long)((N + 15) / 16) * nw * ((per + 3) / 4) * 256;
+  const GvLayout L = gv_layout(N, K, 128);
+  return (long)L.blocks * L.nw * L.per4 * 256;
 }
 
 extern "C" int mh_gemv_pack_fp4(const void* W, int ldb, int N, int K, void* q_out, void* scale_out, hipStream_t stream) {
   if (!gv_fp4_dims(N, K) || (ldb % 8) != 0 || ldb < K || !scale_out || ((uintptr_t)W & 15) || ((uintptr_t)q_out & 15) ||
       ((uintptr_t)scale_out & 3))
     return MH_ERR_ARG;
-  const int nw = gv_packed_nw(N), per = (K / 128 + nw - 1) / nw;
-  hipLaunchKernelGGL(gemv_pack_fp4_kernel, dim3((N + 15) / 16), dim3(256), 0, stream, (const bf16_t*)W, ldb, N, K, (unsigned char*)q_out,
-                     (unsigned char*)scale_out, nw, per);
+  const GvLayout L = gv_layout(N, K, 128);
+  hipLaunchKernelGGL(gemv_pack_fp4_kernel, dim3(L.blocks), dim3(256), 0, stream, (const bf16_t*)W, ldb, N, K, (unsigned char*)q_out,
+                     (unsigned char*)scale_out, L.nw, L.per);
   MH_CHECK_LAUNCH();
   return MH_OK;
-}
-
-// C[M <= 16, N] = alpha * A . dq(W)^T (+bias) (+residual) with W given as its mh_gemv_pack_fp4 copy (codes, scale bytes); the
-// kernels take the scale stream through their wscale argument
-extern "C" int mh_gemv_packed_fp4(const void* A, int lda, const void* Q, const void* scale, void* C, int ldc, int M, int N, int K,
-                                  const float* bias, const float* residual, int ldr, int out_f32, float alpha, hipStream_t stream) {
-  if (M > 0 && N > 0 && (!scale || ((uintptr_t)scale & 3))) return MH_ERR_ARG;
-  return launch_gemv_packed<fp4_t>(A, lda, Q, (const float*)scale, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream);
-}
-
-extern "C" int mh_gemv_packed_fp4_rmsnorm(const float* H, long ldh, const float* norm_w, float eps, const void* Q, const void* scale,
-                                          void* C, int ldc, int M, int N, int K, const float* bias, const float* residual, int ldr,
-                                          int out_f32, float alpha, hipStream_t stream) {
-  return launch_gemv_pro<2, fp4_t>(H, ldh, Q, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, norm_w, eps, stream,
-                                   (const float*)scale);
-}
-
-extern "C" int mh_gemv_packed_fp4_silu(const void* gu, long ldgu, const void* Q, const void* scale, void* C, int ldc, int M, int N,
-                                       int K, const float* bias, const float* residual, int ldr, int out_f32, float alpha,
-                                       hipStream_t stream) {
-  return launch_gemv_pro<1, fp4_t>(gu, ldgu, Q, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, nullptr, 0.f, stream,
-                                   (const float*)scale);
 }
 
 // ---- 17 .. 64 rows on the same packed copies (the decode slots above 16 rows) ------------------------------------------------
@@ -749,7 +692,7 @@ extern "C" int mh_gemv_packed_fp4_silu(const void* gu, long ldgu, const void* Q,
 // alpha).  A row of v_mfma_f32_16x16x32_bf16 depends on its own A row only, so it is enough to keep, per output element, the
 // K split over the gv_packed_nw(N) waves (per = ceil(nsteps / NW)), the step order inside a wave and the MFMA order inside a
 // step (two; four for fp4), the cross-wave sum w = 0 .. NW-1 starting from 0.f, and the epilogue (fp8 row scale, alpha, bias,
-// residual -- gv_finish below is gemv_kernel's epilogue text).  Which workgroup owns which columns is free, and is the design:
+// residual -- gv_finish, the 16-row kernels' own epilogue).  Which workgroup owns which columns is free, and is the design:
 //
 // A workgroup of the 16-row kernel reads all M x K activations from L2 for 16 columns.  Per workgroup that is M / 16 times its
 // bf16 weight bytes (x2 for fp8, x4 for fp4), so at 64 rows the L2 side carries 4 / 8 / 16 times the HBM stream, against an L2
@@ -797,15 +740,6 @@ extern "C" int mh_gemv_packed_fp4_silu(const void* gu, long ldgu, const void* Q,
 // its 16-row launch, all of it the 1.4 MB of activations every one of its 256 workgroups reads.
 // Rows past M in the last row tile duplicate row M - 1 and column blocks past the last one duplicate the last block; neither
 // is stored.
-__device__ __forceinline__ void gv_finish(float v, int m, int n, void* Cv, const float* bias, const float* res, int ldc, int ldr,
-                                          int out_f32, float alpha) {
-  v *= alpha;
-  if (bias) v += bias[n];
-  if (res) v += res[(size_t)m * ldr + n];
-  if (out_f32) reinterpret_cast<float*>(Cv)[(size_t)m * ldc + n] = v;
-  else reinterpret_cast<bf16_t*>(Cv)[(size_t)m * ldc + n] = f2bf(v);
-}
-
 template <int MT, int G, int UNROLL, int GV_NW, typename WT>
 __global__ __launch_bounds__(GV_NW * 64, 2) void gemv_wide_kernel(const bf16_t* __restrict__ A, const WT* __restrict__ B,
                                                                   void* __restrict__ Cv, const float* __restrict__ bias,
@@ -871,14 +805,9 @@ __global__ __launch_bounds__(GV_NW * 64, 2) void gemv_wide_kernel(const bf16_t* 
             const float scl = __uint_as_float(((sc[g] >> (8 * u)) & 0xffu) << 23);     // 2^(b-127), gv_mfma_fp4
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-              gv_u4_t r;
-              r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q[i], scl, 0));
-              r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q[i], scl, 1));
-              r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q[i], scl, 2));
-              r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q[i], scl, 3));
+              const short8_t r = gv_fp4_widen(q[i], scl);             // widened once, used by every row tile
 #pragma unroll
-              for (int t = 0; t < MT; ++t)
-                acc[t][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x[t][i], __builtin_bit_cast(short8_t, r), acc[t][g], 0, 0, 0);
+              for (int t = 0; t < MT; ++t) acc[t][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x[t][i], r, acc[t][g], 0, 0, 0);
             }
           }
         }
@@ -922,21 +851,13 @@ __global__ __launch_bounds__(GV_NW * 64, 2) void gemv_wide_kernel(const bf16_t* 
   for (int t = 0; t < MT; ++t) {
     if (t) __syncthreads();
 #pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) red[wave][g][(4 * lg + r) * 16 + lr] = acc[t][g][r];
+    for (int g = 0; g < G; ++g) gv_red_put(red, wave, g, lr, lg, acc[t][g]);
     __syncthreads();
     if (wave < glive) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int ml = 4 * lg + r, m = t * 16 + ml, n = (b0 + wave) * 16 + lr;
-        if (m < M && n < N) {
-          float v = 0.f;
-#pragma unroll
-          for (int w = 0; w < GV_NW; ++w) v += red[w][wave][ml * 16 + lr];
-          if constexpr (F8) v *= wscale[n];              // the row scale s_n first, then alpha
-          gv_finish(v, m, n, Cv, bias, res, ldc, ldr, out_f32, alpha);
-        }
+        if (m < M && n < N) gv_red_finish<GV_NW, G, F8>(red, wave, ml, lr, m, n, Cv, bias, res, ldc, ldr, out_f32, alpha, wscale);
       }
     }
   }
@@ -945,12 +866,10 @@ __global__ __launch_bounds__(GV_NW * 64, 2) void gemv_wide_kernel(const bf16_t* 
 // One launch of the variant (row tiles, column group, waves).  Steps per batch: an fp4 batch is the four steps of one scale
 // dword; bf16 / fp8 take 4 with groups of 4 and 2 otherwise (the header comment above).
 template <int MT, int G, int NW, typename WT>
-static void launch_gemv_wide_v(const dim3 grid, hipStream_t stream, const void* A, const void* P, void* C, const float* bias,
-                               const float* residual, int M, int N, int K, int lda, int ldc, int ldr, int out_f32, float alpha,
-                               const float* wscale) {
+static void launch_gemv_wide_v(const dim3 grid, const GvArgs& a) {
   constexpr int U = gv_is_fp4<WT> || G == 4 ? 4 : 2;
-  hipLaunchKernelGGL((gemv_wide_kernel<MT, G, U, NW, WT>), grid, dim3(NW * 64), 0, stream, (const bf16_t*)A, (const WT*)P, C, bias,
-                     residual, M, N, K, lda, ldc, ldr, out_f32, alpha, wscale);
+  hipLaunchKernelGGL((gemv_wide_kernel<MT, G, U, NW, WT>), grid, dim3(NW * 64), 0, a.stream, (const bf16_t*)a.A, (const WT*)a.P, a.C,
+                     a.bias, a.residual, a.M, a.N, a.K, (int)a.lda, a.ldc, a.ldr, a.out_f32, a.alpha, (const float*)a.wscale);
 }
 
 // column blocks per workgroup: the largest group that leaves min_wg workgroups (the header comment above)
@@ -962,60 +881,118 @@ static int gv_wide_group(int N, bool one_byte) {
 // The (G, NW) pairs the rule reaches -- only these are instantiated.  NW = 8 means fewer than 512 column blocks: G = 1, or 2 on
 // the one-byte copies from 384 blocks.  NW = 4: bf16 G = 1 (512..767 blocks), 2, 4; one-byte G = 2 (512..767), 4.
 template <int MT, typename WT>
-static void launch_gemv_wide_mt(int G, bool nw8, const dim3 grid, hipStream_t stream, const void* A, const void* P, void* C,
-                                const float* bias, const float* residual, int M, int N, int K, int lda, int ldc, int ldr, int out_f32,
-                                float alpha, const float* wscale) {
+static void launch_gemv_wide_mt(int G, bool nw8, const dim3 grid, const GvArgs& a) {
   constexpr bool ONE = sizeof(WT) == 1;
-#define GV_WIDE_V(GV, NWV) launch_gemv_wide_v<MT, GV, NWV, WT>(grid, stream, A, P, C, bias, residual, M, N, K, lda, ldc, ldr, out_f32, alpha, wscale)
   if (nw8) {
     if constexpr (ONE) {
-      if (G == 2) { GV_WIDE_V(2, 8); return; }
+      if (G == 2) { launch_gemv_wide_v<MT, 2, 8, WT>(grid, a); return; }
     }
-    GV_WIDE_V(1, 8);
+    launch_gemv_wide_v<MT, 1, 8, WT>(grid, a);
   } else if (G == 4) {
-    GV_WIDE_V(4, 4);
+    launch_gemv_wide_v<MT, 4, 4, WT>(grid, a);
   } else if (ONE || G == 2) {
-    GV_WIDE_V(2, 4);
+    launch_gemv_wide_v<MT, 2, 4, WT>(grid, a);
   } else {
-    if constexpr (!ONE) GV_WIDE_V(1, 4);
+    if constexpr (!ONE) launch_gemv_wide_v<MT, 1, 4, WT>(grid, a);
   }
-#undef GV_WIDE_V
 }
 
 template <typename WT>
-static int launch_gemv_wide(const void* A, int lda, const void* P, const float* wscale, void* C, int ldc, int M, int N, int K,
-                            const float* bias, const float* residual, int ldr, int out_f32, float alpha, hipStream_t stream) {
-  if (M <= 0 || N <= 0) return MH_OK;
-  if (M > 64) return MH_ERR_ARG;
-  if (M <= 16) return launch_gemv_packed<WT>(A, lda, P, wscale, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream);
-  if (K <= 0 || (K % gv_kstep<WT>) != 0 || (lda % 8) != 0 || ((uintptr_t)A & 15) || ((uintptr_t)P & 15)) return MH_ERR_ARG;
-  const int G = gv_wide_group(N, sizeof(WT) == 1), MT = (M + 15) / 16;
-  const dim3 grid(((N + 15) / 16 + G - 1) / G);
-  const bool nw8 = gv_packed_nw(N) == 8;
-#define GV_WIDE_ARGS G, nw8, grid, stream, A, P, C, bias, residual, M, N, K, lda, ldc, ldr, out_f32, alpha, wscale
-  if (MT == 2) launch_gemv_wide_mt<2, WT>(GV_WIDE_ARGS);
-  else if (MT == 3) launch_gemv_wide_mt<3, WT>(GV_WIDE_ARGS);
-  else launch_gemv_wide_mt<4, WT>(GV_WIDE_ARGS);
-#undef GV_WIDE_ARGS
+static int launch_gemv_wide(const GvArgs& a) {
+  if (a.M > 64) return MH_ERR_ARG;
+  if (a.M <= 16) return launch_gemv_packed<WT>(a);
+  if (a.K <= 0 || (a.K % gv_kstep<WT>) != 0 || (a.lda % 8) != 0 || ((uintptr_t)a.A & 15) || ((uintptr_t)a.P & 15)) return MH_ERR_ARG;
+  const GvLayout L = gv_layout(a.N, a.K, gv_kstep<WT>);
+  const int G = gv_wide_group(a.N, sizeof(WT) == 1), MT = (a.M + 15) / 16;
+  const dim3 grid((L.blocks + G - 1) / G);
+  if (MT == 2) launch_gemv_wide_mt<2, WT>(G, L.nw == 8, grid, a);
+  else if (MT == 3) launch_gemv_wide_mt<3, WT>(G, L.nw == 8, grid, a);
+  else launch_gemv_wide_mt<4, WT>(G, L.nw == 8, grid, a);
   MH_CHECK_LAUNCH();
   return MH_OK;
 }
 
-extern "C" int mh_gemv_packed_wide(const void* A, int lda, const void* P, void* C, int ldc, int M, int N, int K, const float* bias,
-                                   const float* residual, int ldr, int out_f32, float alpha, hipStream_t stream) {
-  return launch_gemv_wide<bf16_t>(A, lda, P, nullptr, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream);
+// ---- the twelve product entries: {plain, RMSNorm, SiLU, wide} x {bf16, fp8, fp4} ----------------------------------------------
+// An empty product is MH_OK; a missing or misaligned scale pointer of a one-byte copy is MH_ERR_ARG, like every malformed
+// argument, before any launch; MH_ERR_UNSUPPORTED is the fused forms' "run the two launches instead".
+template <int FORM, typename WT>
+static int gv_entry(const GvArgs& a) {
+  if (a.M <= 0 || a.N <= 0) return MH_OK;
+  if (sizeof(WT) == 1 && (!a.wscale || ((uintptr_t)a.wscale & 3))) return MH_ERR_ARG;
+  if constexpr (FORM == GV_PLAIN) return launch_gemv_packed<WT>(a);
+  else if constexpr (FORM == GV_WIDE) return launch_gemv_wide<WT>(a);
+  else return launch_gemv_pro<FORM, WT>(a);
 }
 
-extern "C" int mh_gemv_packed_fp8_wide(const void* A, int lda, const void* Q, const float* scale, void* C, int ldc, int M, int N, int K,
-                                       const float* bias, const float* residual, int ldr, int out_f32, float alpha,
-                                       hipStream_t stream) {
-  if (M > 0 && N > 0 && (!scale || ((uintptr_t)scale & 3))) return MH_ERR_ARG;
-  return launch_gemv_wide<fp8_t>(A, lda, Q, scale, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream);
+// C[M <= 16, N] = alpha * A . W^T (+bias) (+residual) with W given as its mh_gemv_pack copy
+extern "C" int mh_gemv_packed(const void* A, int lda, const void* P, void* C, int ldc, int M, int N, int K, const float* bias,
+                              const float* residual, int ldr, int out_f32, float alpha, hipStream_t stream) {
+  return gv_entry<GV_PLAIN, bf16_t>({A, lda, P, nullptr, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream});
 }
 
-extern "C" int mh_gemv_packed_fp4_wide(const void* A, int lda, const void* Q, const void* scale, void* C, int ldc, int M, int N, int K,
-                                       const float* bias, const float* residual, int ldr, int out_f32, float alpha,
+// C[M <= 16, N] = alpha * rmsnorm(H; norm_w, eps) . W^T (+bias) (+residual), W as its mh_gemv_pack copy; H [M, K] f32.
+// MH_ERR_UNSUPPORTED when M * K * 2 bytes of operand do not fit the kernel's LDS budget (64 KiB), above GV_PRO_MAX_ROWS rows and
+// for K > 4096.
+extern "C" int mh_gemv_packed_rmsnorm(const float* H, long ldh, const float* norm_w, float eps, const void* P, void* C, int ldc,
+                                      int M, int N, int K, const float* bias, const float* residual, int ldr, int out_f32,
+                                      float alpha, hipStream_t stream) {
+  return gv_entry<GV_RMSNORM, bf16_t>({H, ldh, P, nullptr, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream, norm_w, eps});
+}
+
+// C[M <= 16, N] = alpha * (silu(g) * u) . W^T (+bias) (+residual): gu [M, >= 2K] bf16, gate / up interleaved in blocks of 128.
+extern "C" int mh_gemv_packed_silu(const void* gu, long ldgu, const void* P, void* C, int ldc, int M, int N, int K,
+                                   const float* bias, const float* residual, int ldr, int out_f32, float alpha,
+                                   hipStream_t stream) {
+  return gv_entry<GV_SILU, bf16_t>({gu, ldgu, P, nullptr, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream});
+}
+
+// C[M <= 64, N] on the same copy: up to 16 rows the 16-row kernel, above it gemv_wide_kernel; row m carries the 16-row bits
+extern "C" int mh_gemv_packed_wide(const void* A, int lda, const void* P, void* C, int ldc, int M, int N, int K,
+                                   const float* bias, const float* residual, int ldr, int out_f32, float alpha,
+                                   hipStream_t stream) {
+  return gv_entry<GV_WIDE, bf16_t>({A, lda, P, nullptr, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream});
+}
+
+// the fp8 copy (q, s) of mh_gemv_pack_fp8: C = alpha * s_n * op(A) . q^T (+bias) (+residual); the same four forms, the same contract
+extern "C" int mh_gemv_packed_fp8(const void* A, int lda, const void* Q, const float* scale, void* C, int ldc, int M, int N,
+                                  int K, const float* bias, const float* residual, int ldr, int out_f32, float alpha,
+                                  hipStream_t stream) {
+  return gv_entry<GV_PLAIN, fp8_t>({A, lda, Q, scale, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream});
+}
+extern "C" int mh_gemv_packed_fp8_rmsnorm(const float* H, long ldh, const float* norm_w, float eps, const void* Q,
+                                          const float* scale, void* C, int ldc, int M, int N, int K, const float* bias,
+                                          const float* residual, int ldr, int out_f32, float alpha, hipStream_t stream) {
+  return gv_entry<GV_RMSNORM, fp8_t>({H, ldh, Q, scale, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream, norm_w, eps});
+}
+extern "C" int mh_gemv_packed_fp8_silu(const void* gu, long ldgu, const void* Q, const float* scale, void* C, int ldc, int M,
+                                       int N, int K, const float* bias, const float* residual, int ldr, int out_f32, float alpha,
                                        hipStream_t stream) {
-  if (M > 0 && N > 0 && (!scale || ((uintptr_t)scale & 3))) return MH_ERR_ARG;
-  return launch_gemv_wide<fp4_t>(A, lda, Q, (const float*)scale, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream);
+  return gv_entry<GV_SILU, fp8_t>({gu, ldgu, Q, scale, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream});
+}
+extern "C" int mh_gemv_packed_fp8_wide(const void* A, int lda, const void* Q, const float* scale, void* C, int ldc, int M, int N,
+                                       int K, const float* bias, const float* residual, int ldr, int out_f32, float alpha,
+                                       hipStream_t stream) {
+  return gv_entry<GV_WIDE, fp8_t>({A, lda, Q, scale, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream});
+}
+
+// the fp4 copy (codes, scale bytes) of mh_gemv_pack_fp4: C = alpha * op(A) . dq(W)^T (+bias) (+residual); the kernels take the scale
+// stream through their wscale argument
+extern "C" int mh_gemv_packed_fp4(const void* A, int lda, const void* Q, const void* scale, void* C, int ldc, int M, int N, int K,
+                                  const float* bias, const float* residual, int ldr, int out_f32, float alpha, hipStream_t stream) {
+  return gv_entry<GV_PLAIN, fp4_t>({A, lda, Q, scale, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream});
+}
+extern "C" int mh_gemv_packed_fp4_rmsnorm(const float* H, long ldh, const float* norm_w, float eps, const void* Q,
+                                          const void* scale, void* C, int ldc, int M, int N, int K, const float* bias,
+                                          const float* residual, int ldr, int out_f32, float alpha, hipStream_t stream) {
+  return gv_entry<GV_RMSNORM, fp4_t>({H, ldh, Q, scale, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream, norm_w, eps});
+}
+extern "C" int mh_gemv_packed_fp4_silu(const void* gu, long ldgu, const void* Q, const void* scale, void* C, int ldc, int M,
+                                       int N, int K, const float* bias, const float* residual, int ldr, int out_f32, float alpha,
+                                       hipStream_t stream) {
+  return gv_entry<GV_SILU, fp4_t>({gu, ldgu, Q, scale, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream});
+}
+extern "C" int mh_gemv_packed_fp4_wide(const void* A, int lda, const void* Q, const void* scale, void* C, int ldc, int M, int N,
+                                       int K, const float* bias, const float* residual, int ldr, int out_f32, float alpha,
+                                       hipStream_t stream) {
+  return gv_entry<GV_WIDE, fp4_t>({A, lda, Q, scale, C, ldc, M, N, K, bias, residual, ldr, out_f32, alpha, stream});
 }

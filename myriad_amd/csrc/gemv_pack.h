@@ -3,9 +3,21 @@
 #pragma once
 #include "common.h"
 
-// waves per workgroup of the packed kernels: 8 when N / 16 workgroups under-fill the chip, else 4 (gemv.hip's launch rule,
-// without the env knob)
+// waves per workgroup of the packed kernels: 8 when N / 16 workgroups under-fill the chip, else 4 (gemv.hip's launch rule)
 static inline int gv_packed_nw(int N) { return ((N + 15) / 16 < 512) ? 8 : 4; }
+
+// The layout of a packed copy of W [N, K] whose steps are kstep deep (64: bf16 and fp8, 128: fp4): `blocks` column blocks of 16
+// rows, each split over nw waves of `per` steps (the last wave's tail past K is zero padding), a step being 1024 elements;
+// per4: the scale dwords of a wave's fp4 steps, four steps each.  Every packer, element count and launcher takes it from here.
+struct GvLayout { int nw, per, per4, blocks; };
+static inline GvLayout gv_layout(int N, int K, int kstep) {
+  GvLayout L;
+  L.nw = gv_packed_nw(N);
+  L.per = (K / kstep + L.nw - 1) / L.nw;
+  L.per4 = (L.per + 3) / 4;
+  L.blocks = (N + 15) / 16;
+  return L;
+}
 
 // fp32 -> OCP e4m3fn code, round to nearest even; |x| <= 448, not NaN
 __device__ __forceinline__ unsigned f32_to_e4m3fn(float x) {

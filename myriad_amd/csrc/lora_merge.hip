@@ -181,7 +181,8 @@ static int lm_check(const void* W, int ldw, const float* Aqv, const float* Bq, c
 template <int OUT>
 static int lm_launch(const void* W, int ldw, const float* Aqv, const float* Bq, const float* Bv, int D, int r, float s, void* out,
                      int ldo, float* scale_out, hipStream_t stream) {
-  const int N = 3 * D, nw = gv_packed_nw(N), per = (D / 64 + nw - 1) / nw, steps = nw * per;
+  const GvLayout L = gv_layout(3 * D, D, 64);
+  const int N = 3 * D, steps = L.nw * L.per;
   const int KC = OUT == 2 ? 256 : 128;
   const int rounds = ((OUT == 0 ? D : steps * 64) + KC - 1) / KC;      // >= 1; a row-major round may be partial
   // up to 4 workgroups per row block when the blocks alone leave the CUs short of work (bf16 outputs only)

@@ -316,6 +316,26 @@ def lora_merge_pack_fp8(w: torch.Tensor, a_qv: torch.Tensor, b_q: torch.Tensor, 
     return out
 
 
+def _gemv_product(base: str, name: Optional[str], a: torch.Tensor, pw, out, bias, residual, out_dtype, alpha, M: int, *pre):
+    """The shared part of the packed products: the library entry mh_gemv_packed[_fp8|_fp4]<base> for this weight class, the
+    output, the residual check, the weight arguments by class, the call.  `pre` goes between the operand and the weight (the
+    fused forms' norm weight and eps); the fused forms (base _rmsnorm / _silu) answer MH_ERR_UNSUPPORTED with None."""
+    entry = _packed_entry(base, pw)
+    if out is None:
+        out = torch.empty((M, pw.N), dtype=out_dtype, device=a.device)
+    ldr = 0
+    if residual is not None:
+        _chk2d(residual, F32, (name or entry) + ".residual")          # the fused forms name their entry, as they always did
+        ldr = residual.stride(0)
+    wargs = (_p(pw.data), _p(pw.scales)) if isinstance(pw, (PackedFp8Weight, PackedFp4Weight)) else (_p(pw.data),)
+    rc = getattr(_L(), entry)(_p(a), a.stride(0), *pre, *wargs, _p(out), out.stride(0), M, pw.N, pw.K, _p(bias), _p(residual), ldr,
+                              1 if out.dtype == F32 else 0, float(alpha), _s())
+    if rc == -3 and base in ("_rmsnorm", "_silu"):     # MH_ERR_UNSUPPORTED: the operand rows do not fit the fused kernel
+        return None
+    _lib.check(rc, f"{entry} M={M} N={pw.N} K={pw.K}")
+    return out
+
+
 def gemv_packed(a: torch.Tensor, pw, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
                 residual: Optional[torch.Tensor] = None, out_dtype=BF16, alpha: float = 1.0) -> torch.Tensor:
     """out[M <= GEMV_MAX_ROWS, N] = alpha * a @ W^T (+bias) (+residual f32) with W given as its packed copy; same bits as gemm().
@@ -326,22 +346,7 @@ def gemv_packed(a: torch.Tensor, pw, out: Optional[torch.Tensor] = None, bias: O
     if K != pw.K or M > GEMV_MAX_ROWS:
         raise _lib.MyriadHipError(f"gemv_packed: a is {tuple(a.shape)}, weight was packed as [{pw.N}, {pw.K}], "
                                   f"M must be <= {GEMV_MAX_ROWS}")
-    if out is None:
-        out = torch.empty((M, pw.N), dtype=out_dtype, device=a.device)
-    ldr = 0
-    if residual is not None:
-        _chk2d(residual, F32, "gemv_packed.residual")
-        ldr = residual.stride(0)
-    if isinstance(pw, (PackedFp8Weight, PackedFp4Weight)):
-        name = _packed_entry("", pw)
-        rc = getattr(_L(), name)(_p(a), a.stride(0), _p(pw.data), _p(pw.scales), _p(out), out.stride(0), M, pw.N, K, _p(bias),
-                                 _p(residual), ldr, 1 if out.dtype == F32 else 0, float(alpha), _s())
-        _lib.check(rc, f"{name} M={M} N={pw.N} K={K}")
-        return out
-    rc = _L().mh_gemv_packed(_p(a), a.stride(0), _p(pw.data), _p(out), out.stride(0), M, pw.N, K, _p(bias), _p(residual), ldr,
-                             1 if out.dtype == F32 else 0, float(alpha), _s())
-    _lib.check(rc, f"mh_gemv_packed M={M} N={pw.N} K={K}")
-    return out
+    return _gemv_product("", "gemv_packed", a, pw, out, bias, residual, out_dtype, alpha, M)
 
 
 def gemv_packed_wide(a: torch.Tensor, pw, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
@@ -353,34 +358,7 @@ def gemv_packed_wide(a: torch.Tensor, pw, out: Optional[torch.Tensor] = None, bi
     if K != pw.K or M > GEMV_WIDE_MAX_ROWS:
         raise _lib.MyriadHipError(f"gemv_packed_wide: a is {tuple(a.shape)}, weight was packed as [{pw.N}, {pw.K}], "
                                   f"M must be <= {GEMV_WIDE_MAX_ROWS}")
-    if out is None:
-        out = torch.empty((M, pw.N), dtype=out_dtype, device=a.device)
-    ldr = 0
-    if residual is not None:
-        _chk2d(residual, F32, "gemv_packed_wide.residual")
-        ldr = residual.stride(0)
-    name = _packed_entry("_wide", pw)
-    wargs = (_p(pw.data), _p(pw.scales)) if isinstance(pw, (PackedFp8Weight, PackedFp4Weight)) else (_p(pw.data),)
-    rc = getattr(_L(), name)(_p(a), a.stride(0), *wargs, _p(out), out.stride(0), M, pw.N, K, _p(bias), _p(residual), ldr,
-                             1 if out.dtype == F32 else 0, float(alpha), _s())
-    _lib.check(rc, f"{name} M={M} N={pw.N} K={K}")
-    return out
-
-
-def _gemv_pro(fn, name, a, lda, pw, out, residual, out_dtype, alpha, M, *pre):
-    if out is None:
-        out = torch.empty((M, pw.N), dtype=out_dtype, device=a.device)
-    ldr = 0
-    if residual is not None:
-        _chk2d(residual, F32, name + ".residual")
-        ldr = residual.stride(0)
-    wargs = (_p(pw.data), _p(pw.scales)) if isinstance(pw, (PackedFp8Weight, PackedFp4Weight)) else (_p(pw.data),)
-    rc = fn(_p(a), lda, *pre, *wargs, _p(out), out.stride(0), M, pw.N, pw.K, None, _p(residual), ldr,
-            1 if out.dtype == F32 else 0, float(alpha), _s())
-    if rc == -3:                                   # MH_ERR_UNSUPPORTED: the operand rows do not fit the kernel's LDS budget
-        return None
-    _lib.check(rc, f"{name} M={M} N={pw.N} K={pw.K}")
-    return out
+    return _gemv_product("_wide", "gemv_packed_wide", a, pw, out, bias, residual, out_dtype, alpha, M)
 
 
 def gemv_packed_rmsnorm(h: torch.Tensor, norm_w: torch.Tensor, eps: float, pw, out=None, residual=None,
@@ -392,8 +370,7 @@ def gemv_packed_rmsnorm(h: torch.Tensor, norm_w: torch.Tensor, eps: float, pw, o
     M, K = h.shape
     if K != pw.K or M > GEMV_MAX_ROWS:
         raise _lib.MyriadHipError(f"gemv_packed_rmsnorm: h is {tuple(h.shape)}, weight was packed as [{pw.N}, {pw.K}]")
-    name = _packed_entry("_rmsnorm", pw)
-    return _gemv_pro(getattr(_L(), name), name, h, h.stride(0), pw, out, residual, out_dtype, alpha, M, _p(norm_w), float(eps))
+    return _gemv_product("_rmsnorm", None, h, pw, out, None, residual, out_dtype, alpha, M, _p(norm_w), float(eps))
 
 
 def gemv_packed_silu(gu: torch.Tensor, pw, out=None, residual=None, out_dtype=BF16, alpha: float = 1.0):
@@ -403,8 +380,7 @@ def gemv_packed_silu(gu: torch.Tensor, pw, out=None, residual=None, out_dtype=BF
     M = gu.shape[0]
     if gu.shape[1] != 2 * pw.K or M > GEMV_MAX_ROWS:
         raise _lib.MyriadHipError(f"gemv_packed_silu: gu is {tuple(gu.shape)}, weight was packed as [{pw.N}, {pw.K}]")
-    name = _packed_entry("_silu", pw)
-    return _gemv_pro(getattr(_L(), name), name, gu, gu.stride(0), pw, out, residual, out_dtype, alpha, M)
+    return _gemv_product("_silu", None, gu, pw, out, None, residual, out_dtype, alpha, M)
 
 
 def attn_decode_rope(qkv2d: torch.Tensor, cache: torch.Tensor, pos: torch.Tensor, pos_dev: torch.Tensor, kv_len: torch.Tensor,

@@ -182,7 +182,36 @@ def test_fp4_gemv_refusals(packed_case):
     assert L.mh_gemv_packed_fp4(*args(1, K, None)) == -1
 
 
-@pytest.fixture(scope="module", params=[(1000, 4096), (8200, 1024)], ids=["nw8", "nw4"])
+def test_fp4_four_waves_with_a_whole_batch():
+    """N = 8200 runs four waves; K = 8576 is 67 steps: 17 in waves 0-2 (a whole 16-step batch and a remainder of one) and 16 in
+    the last wave, a whole batch clipped at K -- deeper than any decoder matrix is on four waves.  The weights are fp4 values
+    already (e2m1 magnitudes, a 6 in every block: scale byte 127), so dq(W) = W and the reference needs no host quantiser: the
+    16-row kernel within test_fp4_gemv_against_float64's bound of float64 x @ W^T, the fused SiLU form equal to the two launches."""
+    N, K = 8200, 8576
+    g = torch.Generator().manual_seed(N + K)
+    mags = torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0])
+    w = mags[torch.randint(0, 8, (N, K), generator=g)] * (1.0 - 2.0 * torch.randint(0, 2, (N, K), generator=g))
+    w[:, ::32] = 6.0
+    w = w.to(BF16).to(DEV)
+    pw = ops.gemv_pack_fp4(w)
+    wd = w.double()
+    for M_ in (1, 16):
+        x = (torch.randn(M_, K, generator=g) * 0.5).to(BF16).to(DEV)
+        out = torch.full((M_, N), float("nan"), dtype=F32, device=DEV)
+        ops.gemv_packed(x, pw, out=out)
+        err = (out.double() - x.double() @ wd.t()).abs()
+        tol = 2.0 ** -16 * (x.double().abs() @ wd.abs().t()) + 1e-30
+        assert bool((err <= tol).all()), (M_, float((err / tol).max()))
+    gu_ = (torch.randn(1, 2 * K, generator=g) * 2.0).to(BF16).to(DEV)
+    res = torch.randn(1, N, generator=g).to(DEV)
+    for kw in (dict(), dict(residual=res, out_dtype=F32)):
+        fused = ops.gemv_packed_silu(gu_, pw, **kw)
+        assert fused is not None
+        assert torch.equal(fused, ops.gemv_packed(ops.silu_mul_fwd_blk(gu_), pw, **kw)), kw
+
+
+# (1000, 256): 2 steps over eight waves, waves 2-7 with an empty range
+@pytest.fixture(scope="module", params=[(1000, 4096), (8200, 1024), (1000, 256)], ids=["nw8", "nw4", "nw8_empty_waves"])
 def fused_case(request):
     N, K = request.param
     g = torch.Generator().manual_seed(K)

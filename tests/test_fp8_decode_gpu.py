@@ -166,7 +166,10 @@ def test_fp8_gemv_refusals(packed_case):
                                 None, None, 0, 1, 1.0, st) == -1
 
 
-@pytest.fixture(scope="module", params=[(1000, 4096), (8200, 1024)], ids=["nw8", "nw4"])
+# (8200, 4096): the smallest N on four waves at the production K: 16 steps per wave, one whole batch and no remainder;
+# (1000, 256): 4 steps over eight waves, waves 4-7 with an empty range
+@pytest.fixture(scope="module", params=[(1000, 4096), (8200, 1024), (8200, 4096), (1000, 256)],
+                ids=["nw8", "nw4", "nw4_whole_batch", "nw8_empty_waves"])
 def fused_case(request):
     N, K = request.param
     g = torch.Generator().manual_seed(K)
@@ -191,6 +194,23 @@ def test_fp8_fused_forms_bit_identical_to_the_unfused_launches(fused_case, M):
         assert fused is not None
         two = ops.gemv_packed(ops.silu_mul_fwd_blk(gu_), pw, **kw)
         assert torch.equal(fused, two), kw
+
+
+@pytest.mark.parametrize("M", [1, 2])
+def test_fp8_fused_silu_whole_batch_remainder_and_clipped_last_wave(M):
+    """The down projection's depth on eight waves: K = 11008 is 172 steps, 22 per wave (one whole batch of 16 and a remainder of
+    6) and 18 in the last wave, clipped at K.  Two rows of operand are 44 KiB of LDS."""
+    N, K = 48, 11008
+    g = torch.Generator().manual_seed(N + K)
+    pw = ops.gemv_pack_fp8((torch.randn(N, K, generator=g) * 0.03).to(BF16).to(DEV))
+    res = torch.randn(M, N, generator=g).to(DEV)
+    gu_ = (torch.randn(M, 2 * K, generator=g) * 2.0).to(BF16).to(DEV)
+    act = ops.silu_mul_fwd_blk(gu_)
+    for out_dtype in (BF16, F32):
+        for residual in (None, res):
+            fused = ops.gemv_packed_silu(gu_, pw, residual=residual, out_dtype=out_dtype)
+            assert fused is not None
+            assert torch.equal(fused, ops.gemv_packed(act, pw, residual=residual, out_dtype=out_dtype)), (out_dtype, residual is None)
 
 
 def test_fp8_fused_forms_return_none_above_two_rows(fused_case):

@@ -330,7 +330,11 @@ def test_decode_kernel_on_the_packed_weight_copy_is_bit_identical(M, N, K):
         ops.gemv_packed(bf(rnd(17, K)).to(DEV), pw)
 
 
-@pytest.mark.parametrize("M,N,K", [(1, 12288, 4096), (2, 4096, 4096), (2, 22016, 4096), (1, 32000, 4096), (1, 1000, 2048)])
+# (2, 8200, 3136): 49 steps over four waves, 13 each (a whole 8-step batch and a remainder of 5 in one wave) and 10 in the last
+# wave, clipped at K; (1, 1000, 256): 4 steps over eight waves, waves 4-7 with an empty range; the other shapes are whole
+# batches or one partial batch
+@pytest.mark.parametrize("M,N,K", [(1, 12288, 4096), (2, 4096, 4096), (2, 22016, 4096), (1, 32000, 4096), (1, 1000, 2048),
+                                   (2, 8200, 3136), (1, 1000, 256)])
 def test_decode_gemv_with_the_rmsnorm_fused_in_is_bit_identical(M, N, K):
     """mh_gemv_packed_rmsnorm: every workgroup rebuilds the normalised rows (rmsnorm_fwd_kernel's summation order and
     expression) in LDS, then streams the packed weight -- the SAME bits as mh_rmsnorm_fwd + mh_gemv_packed, with / without the
@@ -372,6 +376,21 @@ def test_decode_gemv_with_the_silu_gate_fused_in_is_bit_identical(M):
     assert torch.equal(got, ops.gemv_packed(act, pw, residual=res, out_dtype=torch.float32))
     assert torch.equal(ops.gemv_packed_silu(gu, pw), ops.gemv_packed(act, pw))
     assert ops.gemv_packed_silu(bf(rnd(4, 2 * I, seed=84)).to(DEV), pw) is None           # 4 x 22 KiB: does not fit
+
+
+@pytest.mark.parametrize("M", [1, 2])
+def test_decode_gemv_with_the_silu_gate_fused_in_on_four_waves(M):
+    """The SiLU form above 512 column blocks (four waves per workgroup; the down projection itself runs on eight): K = 2176 is
+    34 steps, 9 per wave (a whole 8-step batch and a remainder of one) and 7 in the last wave, one partial batch clipped at K."""
+    I, N = 2176, 8200
+    gu = bf(rnd(M, 2 * I, seed=85) * 2.0).to(DEV)
+    res = rnd(M, N, seed=86).to(DEV)
+    pw = ops.gemv_pack(bf(rnd(N, I, seed=87) * 0.05).to(DEV))
+    act = ops.silu_mul_fwd_blk(gu)
+    got = ops.gemv_packed_silu(gu, pw, residual=res, out_dtype=torch.float32)
+    assert got is not None
+    assert torch.equal(got, ops.gemv_packed(act, pw, residual=res, out_dtype=torch.float32))
+    assert torch.equal(ops.gemv_packed_silu(gu, pw), ops.gemv_packed(act, pw))
 
 
 @pytest.mark.parametrize("B", [1, 3])

@@ -69,3 +69,29 @@ logits = rnd(128, 32000, seed=30, scale=2.0)
 labels = torch.randint(0, 32000, (128,), generator=torch.Generator().manual_seed(31)).to(dev)
 r = ops.clamp_ce(logits, labels, 1.0)
 show("clamp_ce", *[t for t in (r if isinstance(r, (tuple, list)) else (r,)) if isinstance(t, torch.Tensor)])
+# the decode GEMV family: the three packed copies and every product form on them (16-row, fused prologues, wide)
+for (N, K) in ((12288, 4096), (4096, 11008), (32000, 4096)):
+    wg = rnd(N, K, seed=40 + N % 83, scale=0.03, dtype=BF)
+    xs = rnd(64, K, seed=41, scale=0.5, dtype=BF)
+    hs = rnd(2, K, seed=42, scale=3.0)
+    nwt = rnd(K, seed=43, scale=0.1) + 1.0
+    gus = rnd(2, 2 * K, seed=44, scale=2.0, dtype=BF)
+    rs = rnd(64, N, seed=45)
+    bs = rnd(N, seed=46, scale=0.1)
+    for kind, pack in (("bf16", ops.gemv_pack), ("fp8", ops.gemv_pack_fp8), ("fp4", ops.gemv_pack_fp4)):
+        pw = pack(wg)
+        tag = f"{kind} {N}x{K}"
+        show(f"gemv_pack {tag}", pw.data, getattr(pw, "scales", None))
+        for m in (1, 8, 16):
+            show(f"gemv_packed {tag} M={m}", ops.gemv_packed(xs[:m], pw),
+                 ops.gemv_packed(xs[:m], pw, bias=bs, residual=rs[:m], out_dtype=F32, alpha=0.5))
+        for m in (1, 2):
+            if K <= 4096:                                               # the fused RMSNorm holds a row of at most 4096 in registers
+                show(f"gemv_packed_rmsnorm {tag} M={m}", ops.gemv_packed_rmsnorm(hs[:m], nwt, 1e-6, pw),
+                     ops.gemv_packed_rmsnorm(hs[:m], nwt, 1e-6, pw, residual=rs[:m], out_dtype=F32, alpha=0.5))
+            show(f"gemv_packed_silu {tag} M={m}", ops.gemv_packed_silu(gus[:m], pw),
+                 ops.gemv_packed_silu(gus[:m], pw, residual=rs[:m], out_dtype=F32, alpha=0.5))
+        for m in (17, 64):
+            show(f"gemv_packed_wide {tag} M={m}", ops.gemv_packed_wide(xs[:m], pw),
+                 ops.gemv_packed_wide(xs[:m], pw, bias=bs, residual=rs[:m], out_dtype=F32, alpha=0.5))
+        del pw
