@@ -49,7 +49,15 @@ def parse_args(argv=None):
                         "packed pass when slots are free (1: every sample is prefilled alone)")
     parser.add_argument("--refill-min", type=int, default=1, help="with --slots: hold a refill back until this many slots are free "
                         "(fuller packed passes at the price of occupancy)")
+    parser.add_argument("--llm-score", action="store_true", help="also write llm_anomaly_score = p(Yes) / (p(Yes) + p(No)) at the "
+                        "first generated token (generate(output_scores=True): the language model's own anomaly score)")
     return parser.parse_args(argv)
+
+
+def llm_watch_ids(tokenizer):
+    """The ids the training labels teach as the answer's first token: (Yes, No) of ABNORMAL_DESCRIBE / NORMAL_DESCRIBE."""
+    from myriad_amd import datasets as D
+    return [int(tokenizer(t, add_special_tokens=False).input_ids[0]) for t in (D.ABNORMAL_DESCRIBE, D.NORMAL_DESCRIBE)]
 
 
 def main(argv=None):
@@ -102,6 +110,9 @@ def main(argv=None):
     generate_kwargs = {"max_new_tokens": 90, "stopping_criteria": stopping_criteria, "do_sample": True, "use_cache": True,
                        "min_length": 1, "top_p": 0.01, "temperature": 1.0}           # evaluation_aqa_dataset.py:289-301
 
+    if args.llm_score:
+        generate_kwargs.update(output_scores=True, watch_ids=llm_watch_ids(model.llama_tokenizer))
+
     model.eval()
     if args.slots > 0:
         return save_path, _run_slots(args, model, loader, generate_kwargs, save_path)
@@ -123,8 +134,9 @@ def main(argv=None):
             amax = None
             if maps is not None:                         # anomaly_map_handler (:93-104): uint8(map * 255) then max
                 amax = float((maps[ind].detach().float().cpu() * 255.0).to(torch.uint8).max())
+            llm = EP.llm_anomaly_score(outputs["watch_logprobs"][ind, 0]) if args.llm_score else None
             records.append(EP.make_ad_record(int(data_sample["image_id"][ind]), data_sample["img_path"][ind],
-                                             bool(data_sample["is_anomaly"][ind]), text, amax))
+                                             bool(data_sample["is_anomaly"][ind]), text, amax, llm))
     EP.write_jsonl(save_path, records)
     n_batches = max(1, len(records) // max(1, args.bs))
     print("CUDA Memory:", torch.cuda.max_memory_allocated() / (1024 * 1024))
@@ -160,7 +172,8 @@ def _run_slots(args, model, loader, generate_kwargs, save_path):
             amax = None
             if out["ve_anomaly_map"] is not None:        # anomaly_map_handler (:93-104): uint8(map * 255) then max
                 amax = float((out["ve_anomaly_map"].detach().float().cpu() * 255.0).to(torch.uint8).max())
-            records.append(EP.make_ad_record(*meta[out["index"]], text, amax))
+            llm = EP.llm_anomaly_score(out["watch_logprobs"][0]) if args.llm_score else None
+            records.append(EP.make_ad_record(*meta[out["index"]], text, amax, llm))
         torch.cuda.synchronize()
         all_time = time.time() - t1
     EP.write_jsonl(save_path, records)

@@ -329,6 +329,17 @@ int mh_repetition_penalty_rows_slots(float* logits, long ldl, unsigned* seen, co
    state.  kept may be null (a greedy pick): the fourth record row is then 0.  *step += 1 once per launch. */
 int mh_decode_advance_kept_rows(const long* nxt, const float* margin, const float* pmax, const int* kept, float* rec, long* next_ids,
                                 int* step, int* pos, int* kvlen, int* gen, const int* live, int R, mh_stream_t s);
+/* token log-probabilities of a decode step: the log-softmax at temperature 1 of the f32 logits [R, ldl] a pick was made from (after
+   the in-place repetition penalty when it is on; temperature, top-k, top-p and the EOS ban do not enter).  ids[r] = the pick of row
+   r; watch = 8 int32 ids on the device (-1 or any id outside [0, V): unused, its entries are 0.0), read by the kernel so one
+   captured graph serves every watch set.  out = 10 rows of R floats, row stride ldo >= R (rows of a step's record, say):
+   out[0][r] = lse = m + log(sum_j exp(x_j - m)) with m the row maximum, f32 in a fixed order; out[1][r] = x[ids[r]] - lse;
+   out[2 + w][r] = x[watch[w]] - lse.  A row with live[r] == 0 (live may be null: every row is live) or ids[r] < 0 writes 0.0 to
+   its ten entries and reads no logits.  One 1024-thread workgroup per row with the row in registers when V <= 32768, ldl % 4 == 0
+   and the base is 16-byte aligned; one strided workgroup per row otherwise.  A null logits / ids / watch / out, V < 1 or ldo < R
+   is MH_ERR_ARG before any launch. */
+int mh_token_scores_rows(const float* logits, long ldl, const long* ids, const int* watch, float* out, long ldo, int R, int V,
+                         const int* live, mh_stream_t s);
 
 /* beam search step (HF GenerationMixin._beam_search), nb <= 8 beams, K = 2*nb, 2*nb <= V <= 32768 (else MH_ERR_UNSUPPORTED):
    rows b*rpi .. b*rpi+rpi-1 of fp32 logits [B*rpi, ldl] belong to item b (rpi = nb, or 1 for the step after a prefill at B rows);

@@ -40,7 +40,7 @@ def _decode_weights_id(lm: "LlamaHIP") -> tuple:
 
 
 def _decode_buffers(lm: "LlamaHIP", B: int, T_cap: int, sampler: bool = False, num_beams: int = 1,
-                    row_limit: int = ops.GEMV_MAX_ROWS) -> dict:
+                    row_limit: int = ops.GEMV_MAX_ROWS, scores: bool = False) -> dict:
     """Buffers of the single-token step at B rows: KV caches of T_cap positions, device-resident counters, id / logit /
     result buffers and the [4, B] per-step record (the arg-max step writes its first three rows); `graph` / `warm` hold the
     captured step once there is one (_launch_step), `split` the split-KV partials when the step uses them, `row_limit` the rows
@@ -48,7 +48,8 @@ def _decode_buffers(lm: "LlamaHIP", B: int, T_cap: int, sampler: bool = False, n
     the device sampler's and the repetition penalty's buffers join: their knobs (`prm` = inv_temp, top_p, top_k, penalty),
     the seed, the kept counts and the seen-id bitmaps.  With num_beams > 1, B counts rows (items x beams) and the beam step's
     buffers join: `bupd` = the per-step upload (ids int64 | parent rows int32 | running scores f32) and its pinned host twin,
-    the top-K scratch and record, and the device table of the per-layer cache pointers that mh_beam_reorder_kv walks."""
+    the top-K scratch and record, and the device table of the per-layer cache pointers that mh_beam_reorder_kv walks.  With
+    `scores` the record is the one with the token scores' rows behind its four (_score_buffers)."""
     dev, i32 = lm.dev, torch.int32
     ws = dict(T=T_cap, graph=None, warm=False, split=None, row_limit=row_limit,
               caches=[torch.zeros((B, T_cap, 2 * lm.D), dtype=BF16, device=dev) for _ in lm.layers],
@@ -70,7 +71,20 @@ def _decode_buffers(lm: "LlamaHIP", B: int, T_cap: int, sampler: bool = False, n
                   part_s=torch.empty((B * K,), dtype=F32, device=dev), part_i=torch.empty((B * K,), dtype=i32, device=dev),
                   brec=torch.zeros((2, B // nb * K), dtype=i32, device=dev), lo=torch.zeros((1,), dtype=i32, device=dev),
                   table=torch.tensor([c.data_ptr() for c in ws["caches"]], dtype=torch.long).to(dev))
+    if scores:
+        ws["rec"] = _score_buffers(lm, ws)["srec"]
     return ws
+
+
+def _score_buffers(lm: "LlamaHIP", bufs: dict) -> dict:
+    """The token scores' buffers, joined to a buffer set on first use: `srec`, a step record of 4 + SCORE_ROWS rows whose last
+    SCORE_ROWS mh_token_scores_rows writes (lse, the pick's log-prob, one row per watch slot), so a step with scores is still ONE
+    device->host copy; `watch`, the watched ids on the device (-1: unused), which the kernel reads from memory."""
+    if "srec" not in bufs:
+        B = bufs["ids"].shape[0]
+        bufs.update(srec=torch.zeros((4 + ops.SCORE_ROWS, B), dtype=F32, device=lm.dev),
+                    watch=torch.full((ops.SCORE_WATCH_MAX,), -1, dtype=torch.int32, device=lm.dev))
+    return bufs
 
 
 def _cache_stamp(lm: "LlamaHIP", weights_version) -> tuple:
@@ -95,12 +109,16 @@ def _sampling_args(lm: "LlamaHIP", do_sample: bool = False, temperature: float =
     return 1.0 / float(temperature) if do_sample else 1.0, top_k, dev_sample, float(repetition_penalty) != 1.0
 
 
-def _buffer_view(lm: "LlamaHIP", bufs: dict, split: bool) -> dict:
+def _buffer_view(lm: "LlamaHIP", bufs: dict, split: bool, scores: bool = False) -> dict:
     """A workspace view of a buffer set: the buffers with a graph / warm flag of its own.  `split`: the view's step runs a split-KV
-    attention kernel; the partials buffer joins the set on first use, a split view holds it and a non-split view holds None."""
+    attention kernel; the partials buffer joins the set on first use, a split view holds it and a non-split view holds None.
+    `scores`: the view's step also writes the token scores; its record is the set's `srec` (_score_buffers)."""
     if split and bufs["split"] is None:
         bufs["split"] = ops.attn_decode_split_ws(bufs["ids"].shape[0], lm.H, bufs["T"], lm.dev)
-    return dict(bufs, graph=None, warm=False, split=bufs["split"] if split else None)
+    view = dict(bufs, graph=None, warm=False, split=bufs["split"] if split else None)
+    if scores:
+        view.update(rec=_score_buffers(lm, bufs)["srec"], watch=bufs["watch"])
+    return view
 
 
 class LlamaDecode:
@@ -141,19 +159,21 @@ class LlamaDecode:
         return ops.gemm(ops.rmsnorm_fwd(last, self.norm, self.eps), self.lm_head, out=out, out_dtype=F32)
 
     def _decode_workspace(self, B: int, T_need: int, inv_temp: float, dev_sample: bool = False, penalty: bool = False,
-                          num_beams: int = 1):
+                          num_beams: int = 1, scores: bool = False):
         """_decode_buffers (and, once captured, the hipGraph) of the single-token step for a batch size, kept across generate()
         calls -- an evaluation run calls generate() once per batch, and re-capturing ~290 launches each time cost ~9 ms per
         call.  The device sampler and the repetition penalty read their knobs and the seed from device memory, so the key holds
-        only whether each is on; the arg-max kernel takes inv_temp as an argument, so it stays in the key there."""
+        only whether each is on; the arg-max kernel takes inv_temp as an argument, so it stays in the key there.  A step that also
+        writes the token scores (`scores`) is another launch sequence and a larger record: its key carries one more item, so a call
+        without scores finds the workspace, the graph and the launches it had."""
         T_cap = ops.round_up(T_need + 2, 64)
         key = (B, T_cap, None if dev_sample else float(inv_temp), _decode_weights_id(self), bool(dev_sample), bool(penalty),
-               int(num_beams))
+               int(num_beams)) + (("scores",) if scores else ())
         ws = self._decode_ws.get(key)
         if ws is None:
             if len(self._decode_ws) >= 3:                               # a few shapes at most: evict the oldest
                 self._decode_ws.pop(next(iter(self._decode_ws)))
-            ws = self._decode_ws[key] = _decode_buffers(self, B, T_cap, dev_sample or penalty, num_beams)
+            ws = self._decode_ws[key] = _decode_buffers(self, B, T_cap, dev_sample or penalty, num_beams, scores=scores)
         return ws
 
     def _prefill(self, inputs_embeds: torch.Tensor, caches, past: int = 0) -> torch.Tensor:
@@ -324,7 +344,7 @@ class LlamaDecode:
                         stop_ids=((835,), (2277, 29937)), eos_id: int = 2, min_length: int = 1,
                         return_margins: bool = False, use_graph: bool = True, do_sample: bool = False,
                         top_p: float = 1.0, temperature: float = 1.0, generator: Optional[torch.Generator] = None,
-                        top_k: int = 50, repetition_penalty: float = 1.0):
+                        top_k: int = 50, repetition_penalty: float = 1.0, return_scores: bool = False, watch_ids=()):
         """Decode from [B,S0,D] f32 embeddings with a KV cache (prefill + 1-token steps).  Same contract
         as the oracle's greedy_generate: stop when ROW 0 ends with a stop sequence (conversation.py:102-107),
         EOS banned while fewer than `min_length` tokens were generated, finished rows padded with EOS.
@@ -351,18 +371,29 @@ class LlamaDecode:
         `generator` per call): every step is a draw, no row waits on the host, and runs are reproducible per seed but not
         bit-comparable with torch.multinomial.  A row whose tied top-k set passes 1024 candidates is still drawn on the host.
         `repetition_penalty` (HF RepetitionPenaltyLogitsProcessor over the generated ids; the prompt is embeddings only) is applied
-        on the device to the step's logits before any pick, greedy, host or device draw."""
+        on the device to the step's logits before any pick, greedy, host or device draw.
+
+        `return_scores` (opt-in; a workspace and a captured step of its own) appends a dict to the return: `token_logprobs` [B, L]
+        f32, the log-probability of every returned id, and `watch_logprobs` [B, L, W], that of each of the W <= 8 `watch_ids` at
+        the same step.  Both are the log-softmax at temperature 1 of the logits the pick was made from -- after the repetition
+        penalty when it is on; temperature, top-k, top-p and the EOS ban do not enter -- computed inside the step
+        (mh_token_scores_rows, after the pick and before the advance) into rows of the step's record, so a step is still one
+        device->host copy.  Positions padded after a row finished are 0.0.  A row the host re-draws takes its log-prob from the
+        logits row the host reads for the draw and the recorded normaliser."""
         B, S0, _ = inputs_embeds.shape
         inv_temp, _, dev_sample, penalty = _sampling_args(self, do_sample, temperature, top_k, repetition_penalty)
+        ops.score_watch_ids(watch_ids if return_scores else (), self.V)
         weight_stats = self._prepare_decode_weights(B)
-        ws = self._decode_workspace(B, S0 + max_new_tokens, inv_temp, dev_sample, penalty)
+        ws = self._decode_workspace(B, S0 + max_new_tokens, inv_temp, dev_sample, penalty, scores=bool(return_scores))
         return self._greedy_core(inputs_embeds, ws, 0, weight_stats, max_new_tokens, stop_ids, eos_id, min_length, return_margins,
-                                 use_graph, do_sample, top_p, temperature, generator, top_k, repetition_penalty)
+                                 use_graph, do_sample, top_p, temperature, generator, top_k, repetition_penalty, return_scores,
+                                 watch_ids)
 
     def _greedy_core(self, inputs_embeds: torch.Tensor, ws: dict, past: int, weight_stats: dict, max_new_tokens: int = 90,
                      stop_ids=((835,), (2277, 29937)), eos_id: int = 2, min_length: int = 1, return_margins: bool = False,
                      use_graph: bool = True, do_sample: bool = False, top_p: float = 1.0, temperature: float = 1.0,
-                     generator: Optional[torch.Generator] = None, top_k: int = 50, repetition_penalty: float = 1.0):
+                     generator: Optional[torch.Generator] = None, top_k: int = 50, repetition_penalty: float = 1.0,
+                     return_scores: bool = False, watch_ids=()):
         """greedy_generate's body on the caller's workspace `ws` (greedy_generate's from the _decode_ws cache, a DecodeSession's
         own buffers and graphs), on top of the cached prefix `past` that is not prefilled again; `weight_stats` is what
         _prepare_decode_weights answered for this call.  The other arguments are greedy_generate's, in its order."""
@@ -372,21 +403,30 @@ class LlamaDecode:
         unfinished = torch.ones(B, dtype=torch.long)
         stats = dict(steps=0, sampled_rows=0, min_pmax=1.0, device_sampled_rows=0, host_sampled_rows=0, graph_replays=0, **weight_stats)
         self.last_generate_stats = stats
-        rec = ws["rec"][:4 if dev_sample else 3]                     # the sampler's kept counts are the fourth row
+        scores = bool(return_scores)
+        if scores:                                                   # ws is a scores workspace / view: its record has the rows
+            watch = ops.score_watch_table(watch_ids, self.V)
+            if ws["rec"].shape[0] != 4 + ops.SCORE_ROWS:
+                raise ValueError("return_scores needs a workspace whose record holds the score rows")
+            ws["watch"].copy_(watch)
+            W, srec, tok_lp, watch_lp = int((watch >= 0).sum()), ws["rec"][4:], [], []
+        rec = ws["rec"] if scores else ws["rec"][:4 if dev_sample else 3]      # the sampler's kept counts are the fourth row
         if dev_sample or penalty:
             ws["prm"].copy_(torch.tensor([inv_temp, top_p, float(top_k), float(repetition_penalty)], dtype=F32))
             ws["seen"].zero_()                                       # generated ids only: the prompt is embeddings
         if dev_sample:
             ws["seed"].fill_(int(torch.randint(0, 2**63 - 1, (1,), generator=generator)))
 
-        def record(nxt: torch.Tensor, mar: torch.Tensor, pm: torch.Tensor, ban: int, logits_of=None, kept=None):
+        def record(nxt: torch.Tensor, mar: torch.Tensor, pm: torch.Tensor, ban: int, logits_of=None, kept=None, sc=None):
             """Host bookkeeping of one step's picks.  Returns (done, redrawn): redrawn = a live row was re-drawn on the host
             (finished rows are fed their raw arg-max instead of EOS by the device: rows are independent and their outputs are
-            overwritten with EOS here)."""
+            overwritten with EOS here).  `sc` = the step's score rows [SCORE_ROWS, B] on the host, with scores on."""
             nonlocal unfinished
             margins.append(mar)
             stats["steps"] += 1
             redrawn = False
+            alive = unfinished.bool()                                # rows whose pick of this step is part of their answer
+            lp = sc[1].clone() if scores else None
             if do_sample:
                 stats["min_pmax"] = min(stats["min_pmax"], float(pm[unfinished.bool()].min()) if int(unfinished.sum()) else 1.0)
                 for row in range(B):
@@ -400,6 +440,12 @@ class LlamaDecode:
                         nxt[row] = _host_draw(logits_of()[row], ban, inv_temp, top_k, top_p, generator)
                         stats["host_sampled_rows"] += 1
                         redrawn = True
+                        if scores:                                   # x[id] - lse in f32, from the row the draw read
+                            lp[row] = logits_of()[row, int(nxt[row])].cpu() - sc[0, row]
+            if scores:
+                tok_lp.append(torch.where(alive, lp, torch.zeros_like(lp)))
+                wl = sc[2:2 + W].t()
+                watch_lp.append(torch.where(alive[:, None], wl, torch.zeros_like(wl)))
             nxt = nxt * unfinished + eos_id * (1 - unfinished)       # HF pads finished rows with pad(=eos)
             unfinished = unfinished * (nxt != eos_id).long()
             out_ids.append(nxt)
@@ -414,8 +460,10 @@ class LlamaDecode:
             ops.sample_rows(logits0, ws["nxt"], ws["mar"], ws["pmx"], ws["kept"], ws["prm"], ws["seed"], ban_id=ban0, t_add=0)
         else:
             ops.argmax_pmax_rows(logits0, ws["nxt"], ws["mar"], ws["pmx"], ban_id=ban0, inv_temp=inv_temp)
+        if scores:
+            ops.token_scores_rows(logits0, ws["nxt"], ws["watch"], srec)
         done, _ = record(ws["nxt"].cpu(), ws["mar"].cpu(), ws["pmx"].cpu(), ban0, logits_of=lambda: logits0,
-                         kept=ws["kept"].cpu() if dev_sample else None)
+                         kept=ws["kept"].cpu() if dev_sample else None, sc=srec.cpu() if scores else None)
 
         # ---- single-token steps: everything the step reads is on the device
         ws["pos"].fill_(S0)                                          # position of the incoming token
@@ -429,10 +477,14 @@ class LlamaDecode:
             if dev_sample:                                           # token s (= step + 1) draws Philox step t = s
                 ops.sample_rows(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ws["kept"], ws["prm"], ws["seed"], ban_id=ban,
                                 step=ws["step"], t_add=1)
+                if scores:
+                    ops.token_scores_rows(ws["logits"], ws["nxt"], ws["watch"], srec)
                 ops.decode_advance_kept(ws["nxt"], ws["mar"], ws["pmx"], ws["kept"], rec, ws["ids"], ws["step"], ws["pos"],
                                         ws["kvlen"])
                 return
             ops.argmax_pmax_rows(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ban_id=ban, inv_temp=inv_temp)
+            if scores:
+                ops.token_scores_rows(ws["logits"], ws["nxt"], ws["watch"], srec)
             ops.decode_advance(ws["nxt"], ws["mar"], ws["pmx"], rec, ws["ids"], ws["step"], ws["pos"], ws["kvlen"])
 
         step = 1                                                     # tokens generated so far (= index of the next one)
@@ -443,12 +495,15 @@ class LlamaDecode:
             self._launch_step(ws, token_step, ban, use_graph, stats)
             r = rec.cpu()                                            # the one device->host copy of the step (it also waits for it)
             done, redrawn = record(r[0].long(), r[1].clone(), r[2].clone(), ban, logits_of=lambda: ws["logits"],
-                                   kept=r[3] if dev_sample else None)
+                                   kept=r[3] if dev_sample else None, sc=r[4:] if scores else None)
             if redrawn and not done:
                 ws["ids"].copy_(out_ids[-1].to(self.dev))            # a host draw replaces the arg-max the step fed back to itself
             step += 1
         ids = torch.stack(out_ids, 1)
-        return (ids, torch.stack(margins, 1)) if return_margins else ids
+        out = (ids, torch.stack(margins, 1)) if return_margins else (ids,)
+        if scores:
+            out += (dict(token_logprobs=torch.stack(tok_lp, 1), watch_logprobs=torch.stack(watch_lp, 1)),)
+        return out if len(out) > 1 else ids
 
     @torch.no_grad()
     def beam_generate(self, inputs_embeds: torch.Tensor, num_beams: int, max_new_tokens: int = 90, stop_ids=(), eos_id: int = 2,
@@ -615,9 +670,10 @@ class DecodeSession:
         self.last_stats = {}
 
     def _begin_turn(self, keys, version, reason, B: int, S0: int, max_new_tokens: int, inv_temp: float, dev_sample: bool,
-                    penalty: bool):
+                    penalty: bool, scores: bool = False):
         """A turn's setup, once the decode weights are packed: invalidation, (re)allocation, the reused prefix.
-        Returns (workspace, past)."""
+        Returns (workspace, past).  `scores`: the turn's step writes the token scores -- a view (and graph) of its own, whose key
+        carries one more item, so the views of turns without scores are the ones they were."""
         L = self.llama
         if S0 + max_new_tokens > L.cos.shape[0]:
             raise ValueError(f"context {S0} + max_new_tokens {max_new_tokens} passes the rotary table ({L.cos.shape[0]} positions)")
@@ -648,9 +704,9 @@ class DecodeSession:
         past = min(past, S0 - 1)                                     # at least one row is prefilled: it gives the first logits
         fused = _packed_step(L, B) and L.decode_fused
         self.split = fused and (split_kv_rule(B, L.H, S0) if self.split_choice is None else bool(self.split_choice))
-        cfg = (None if dev_sample else float(inv_temp), bool(dev_sample), bool(penalty), self.split)
+        cfg = (None if dev_sample else float(inv_temp), bool(dev_sample), bool(penalty), self.split) + (("scores",) if scores else ())
         if cfg not in self.views:
-            self.views[cfg] = _buffer_view(L, self.bufs, self.split)
+            self.views[cfg] = _buffer_view(L, self.bufs, self.split, scores)
         self.last_stats = dict(context_tokens=S0, reused_tokens=past, prefilled_tokens=S0 - past, split_kv=bool(self.split),
                                full_reprefill_reason=reason)
         return self.views[cfg], past
@@ -659,16 +715,19 @@ class DecodeSession:
     def generate(self, inputs_embeds: torch.Tensor, keys, weights_version=None, reset_reason: Optional[str] = None,
                  max_new_tokens: int = 90, **kw):
         """One turn: greedy_generate's contract and arguments (`max_new_tokens`, `stop_ids`, `eos_id`, `min_length`, `do_sample`,
-        `top_p`, `temperature`, `generator`, `top_k`, `repetition_penalty`, `return_margins`) on [B, S0, D] f32 embeddings whose
+        `top_p`, `temperature`, `generator`, `top_k`, `repetition_penalty`, `return_margins`, `return_scores`, `watch_ids`) on
+        [B, S0, D] f32 embeddings whose
         positions are named by `keys` ([B][S0]).  `weights_version`: anything that changes when the weights do."""
         L = self.llama
         B, S0, _ = inputs_embeds.shape
         ws = None
         try:
             inv_temp, _, dev_sample, penalty = _sampling_args(L, **kw)
+            scores = bool(kw.get("return_scores", False))
+            ops.score_watch_ids(kw.get("watch_ids", ()) if scores else (), L.V)
             weight_stats = L._prepare_decode_weights(B)              # packed before the stamp, which names the packed copies
             ws, past = self._begin_turn([list(k) for k in keys], weights_version, reset_reason, B, S0, max_new_tokens, inv_temp,
-                                        dev_sample, penalty)
+                                        dev_sample, penalty, scores)
             graph = ws["graph"]
             out = L._greedy_core(inputs_embeds, ws, past, weight_stats, max_new_tokens=max_new_tokens, use_graph=True, **kw)
         except BaseException:
@@ -751,22 +810,26 @@ class SlotDecoder:
         self.sessions.close(session)
 
     @staticmethod
-    def _view_key(inv_temp: float, rows_tail=None, split: bool = False):
+    def _view_key(inv_temp: float, rows_tail=None, split: bool = False, scores: bool = False):
         """The key of a view (one captured graph each).  Without split-KV it is what it was before the engine had the choice --
-        inv_temp, or (inv_temp or None, device-sampled, penalty) for the per-row tail -- and a split view is ("split", that)."""
+        inv_temp, or (inv_temp or None, device-sampled, penalty) for the per-row tail -- and a split view is ("split", that).  A
+        view whose step writes the token scores wraps the first of those in ("scores", ...): every other key is what it was."""
         key = float(inv_temp)
         if rows_tail is not None:
             key = (None if rows_tail[0] else key, bool(rows_tail[0]), bool(rows_tail[1]))
+        if scores:
+            key = ("scores", key)
         return ("split", key) if split else key
 
-    def _workspace(self, inv_temp: float, rows_tail=None, split: bool = False) -> dict:
+    def _workspace(self, inv_temp: float, rows_tail=None, split: bool = False, scores: bool = False) -> dict:
         """The step's buffers, kept while the decode weights stay the ones the captured graphs read, and over them one view (its
         own graph / warm flag) per inv_temp: the arg-max kernel takes inv_temp as a launch argument, so a captured step is fixed
         to one value (LlamaHIP._decode_workspace keys its workspaces the same way).  `rows_tail` = (device-sampled, penalty) asks
         for the step with the per-row tail: its buffers join on first use (the knobs `prm`, per-slot `seed` / `gen` / `kept` /
         `seen`, and `seed0` / `gen0` for the refills' first picks), and a device-sampled view is keyed without inv_temp, which the
         sampler reads from `prm`.  `split`: the view's step runs the split-KV rows kernel; the partials buffer joins on first use,
-        a split view holds it and a non-split view holds None, so each (key, split) has its own graph."""
+        a split view holds it and a non-split view holds None, so each (key, split) has its own graph.  `scores`: the view's step
+        also writes the token scores into a record of its own (_score_buffers; `sc0` takes the refills' first picks' scores)."""
         L = self.llama
         L._prepare_decode_weights(self.slots, ops.GEMV_WIDE_MAX_ROWS)
         if not (_packed_step(L, self.slots, ops.GEMV_WIDE_MAX_ROWS) and L.decode_fused):
@@ -784,12 +847,14 @@ class SlotDecoder:
                              seed0=torch.zeros((n,), dtype=torch.long, device=L.dev), gen=torch.zeros((n,), dtype=i32, device=L.dev),
                              gen0=torch.zeros((n,), dtype=i32, device=L.dev), kept=torch.zeros((n,), dtype=i32, device=L.dev),
                              seen=torch.zeros((n, (L.V + 31) // 32), dtype=i32, device=L.dev))
-        key = self._view_key(inv_temp, rows_tail, split)
+        if scores and "sc0" not in self.bufs:
+            self.bufs["sc0"] = torch.zeros((ops.SCORE_ROWS, self.slots), dtype=F32, device=L.dev)
+        key = self._view_key(inv_temp, rows_tail, split, scores)
         if key not in self.views:
             same = [k for k in self.views if (isinstance(k, tuple) and k[0] == "split") == bool(split)]
             if len(same) >= 4:                                       # a few temperatures at most per kernel: drop its oldest graph
                 self.views.pop(same[0])
-            self.views[key] = _buffer_view(L, self.bufs, split)
+            self.views[key] = _buffer_view(L, self.bufs, split, scores)
         self.ws = self.views[key]
         return self.ws
 
@@ -797,7 +862,7 @@ class SlotDecoder:
     def run(self, requests, max_new_tokens: int = 90, stop_ids=((835,), (2277, 29937)), eos_id: int = 2, min_length: int = 1,
             do_sample: bool = False, top_p: float = 1.0, temperature: float = 1.0, top_k: int = 50,
             generator: Optional[torch.Generator] = None, ordered: bool = False, prefill_batch: int = 1, refill_min: int = 1,
-            prefill_rows: int = 2048, repetition_penalty: float = 1.0, seeds=None):
+            prefill_rows: int = 2048, repetition_penalty: float = 1.0, seeds=None, return_scores: bool = False, watch_ids=()):
         """Decode every request of `requests` (an iterable of [S0_i, D] f32 embeddings, lengths free) and yield
         (index, ids[L_i] int64 on the CPU, margins[L_i] f32) as each finishes -- or, with `ordered`, in input order.  The
         arguments are greedy_generate's; the stop rule is per request.  `last_stats` holds the run's counters: `prefills` counts
@@ -811,18 +876,24 @@ class SlotDecoder:
         request's seed and t (`host_sampled_rows`).  `repetition_penalty` != 1 needs the switch, as in generate(); `min_length`
         is a per-request EOS ban on every path.  A second run with other values of the knobs replays the same graph.
         `last_stats["split_kv"]`: the attention kernel of the call's token steps.  With the decoder's split_kv=None the rule sees
-        `slots` live rows and a longest context of 0 -- the lengths are not known up front -- so None never splits here."""
+        `slots` live rows and a longest context of 0 -- the lengths are not known up front -- so None never splits here.
+
+        `return_scores`, `watch_ids` (greedy_generate's; a view and a graph of their own): every yielded tuple gains a fourth
+        item, dict(token_logprobs [L_i] f32, watch_logprobs [L_i, W] f32) of that request -- what greedy_generate returns for it
+        alone."""
         self.sessions.clear()                                        # the slots' caches are overwritten from row 0
         yield from self._run(requests, None, None, max_new_tokens, stop_ids, eos_id, min_length, do_sample, top_p, temperature,
-                             top_k, generator, ordered, prefill_batch, refill_min, prefill_rows, repetition_penalty, seeds)
+                             top_k, generator, ordered, prefill_batch, refill_min, prefill_rows, repetition_penalty, seeds,
+                             return_scores, watch_ids)
 
     def run_turns(self, turns, weights_version=None, **kw):
         """One turn each of several conversations, every one in ITS OWN slot on top of what that slot's cache holds of it
         (`sessions`, a SessionTable).  `turns` = [(session, emb [S0, D] f32, keys [S0])] or with a fourth item `reset_reason`; at
         most one turn per session per call (ValueError), at most `slots` open sessions (`close(session)` frees one).  `kw` are
         `run`'s arguments but `refill_min` (prefill_batch, prefill_rows, the sampling knobs, repetition_penalty, min_length,
-        seeds: with device sampling the i-th turn of the call takes the i-th seed).  Only the rows past the prefix the slot
-        shares with the new context are prefilled: with prefill_batch = 1 a solo _prefill(emb, slot cache, past) per turn,
+        seeds: with device sampling the i-th turn of the call takes the i-th seed; return_scores, watch_ids: the yielded tuples
+        gain the scores dict).  Only the rows past the prefix the slot shares with the new context are prefilled: with
+        prefill_batch = 1 a solo _prefill(emb, slot cache, past) per turn,
         otherwise passes of up to prefill_batch turns / prefill_rows new rows through _prefill_packed(..., pasts).  Then `run`'s
         captured step (same graphs and views) runs until every turn has stopped under its own stop rule.  Yields (session, ids,
         margins) as `run` does, `ordered=True` in the list's order; `last_stats["turns"]` holds per turn `context_tokens`,
@@ -845,9 +916,11 @@ class SlotDecoder:
     def _run(self, requests, turns, weights_version, max_new_tokens: int = 90, stop_ids=((835,), (2277, 29937)), eos_id: int = 2,
              min_length: int = 1, do_sample: bool = False, top_p: float = 1.0, temperature: float = 1.0, top_k: int = 50,
              generator: Optional[torch.Generator] = None, ordered: bool = False, prefill_batch: int = 1, refill_min: int = 1,
-             prefill_rows: int = 2048, repetition_penalty: float = 1.0, seeds=None):
+             prefill_rows: int = 2048, repetition_penalty: float = 1.0, seeds=None, return_scores: bool = False, watch_ids=()):
         """`run` (requests) and `run_turns` (turns + weights_version): one engine, two admission rules."""
         L = self.llama
+        scores = bool(return_scores)
+        watch = ops.score_watch_table(watch_ids if scores else (), L.V)
         inv_temp, top_k, dev_sample, penalty = _sampling_args(L, do_sample, temperature, top_k, repetition_penalty)
         if penalty and not L.device_sampling:
             raise NotImplementedError(f"decode slots: repetition_penalty={repetition_penalty} needs the device sampling switch "
@@ -860,7 +933,7 @@ class SlotDecoder:
         if split is None:
             live_rows, longest = (self.slots, 0) if turns is None else (len(turns), max([int(t[1].shape[0]) for t in turns], default=0))
             split = split_kv_rows_rule(live_rows, L.H, longest)
-        ws = self._workspace(inv_temp, (dev_sample, penalty) if rows_tail else None, split)
+        ws = self._workspace(inv_temp, (dev_sample, penalty) if rows_tail else None, split, scores)
         sched = SlotScheduler(self.slots, max_new_tokens, stop_ids, eos_id, ordered=ordered)
         stats = dict(steps=0, graph_replays=0, graph_captures=self.graph_captures, prefills=0, live_row_steps=0, occupancy=0.0,
                      host_sampled_rows=0, device_sampled_rows=0, prefill_passes=0, packed_rows=0, split_kv=bool(split))
@@ -881,7 +954,9 @@ class SlotDecoder:
         self.last_stats = stats
         run = _SlotRun(self, ws, sched, stats, turns, max_new_tokens=max_new_tokens, eos_id=eos_id, min_length=min_length,
                        do_sample=do_sample, top_p=top_p, inv_temp=inv_temp, top_k=top_k, dev_sample=dev_sample, penalty=penalty,
-                       rows_tail=rows_tail, generator=generator)
+                       rows_tail=rows_tail, generator=generator, scores=scores, W=int((watch >= 0).sum()))
+        if scores:
+            ws["watch"].copy_(watch)
         ws["live"].zero_()                                           # an abandoned run may have left slots live
         ws["step"].zero_()
         if rows_tail:
@@ -901,6 +976,7 @@ class SlotDecoder:
                     self.graph_captures += 1
                 r = run.rec.cpu()                                    # the one device->host copy of the step (it also waits for it)
                 ids = run.host_draws(live, r)
+                run.note_scores(live, r, ids)
                 finished = sched.step(ids, r[1].tolist())
                 for s in live:
                     if s in finished:
@@ -919,17 +995,21 @@ class _SlotRun:
 
     def __init__(self, dec, ws, sched, stats, turns, **knobs):
         self.dec, self.L, self.ws, self.sched, self.stats, self.turns = dec, dec.llama, ws, sched, stats, turns
-        # max_new_tokens, eos_id, min_length, do_sample, top_p, inv_temp, top_k, dev_sample, penalty, rows_tail, generator
+        # max_new_tokens, eos_id, min_length, do_sample, top_p, inv_temp, top_k, dev_sample, penalty, rows_tail, generator, scores,
+        # W (the watch ids in use)
         vars(self).update(knobs)
         self.ban0 = self.eos_id if 0 < self.min_length else -1
-        self.rec = ws["rec"] if self.rows_tail else ws["rec"][:3]
+        self.rec = ws["rec"] if self.rows_tail or self.scores else ws["rec"][:3]      # with scores: the score rows behind the four
         self.seed_of = {}                                            # slot -> its request's seed
+        self.sc_of = {}                                              # request index -> its [pick log-prob, watch log-probs] per token
 
     def token_step(self, _ban):
         ws, rec = self.ws, self.rec
         self.L._step_logits(ws)
         if not self.rows_tail:
             ops.argmax_pmax_rows(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ban_id=-1, inv_temp=self.inv_temp)
+            if self.scores:
+                ops.token_scores_rows(ws["logits"], ws["nxt"], ws["watch"], rec[4:], ws["live"])
             ops.decode_advance_rows(ws["nxt"], ws["mar"], ws["pmx"], rec, ws["ids"], ws["step"], ws["pos"], ws["kvlen"],
                                     ws["live"])
             return
@@ -940,16 +1020,23 @@ class _SlotRun:
                                   ws["live"])
         else:
             ops.argmax_pmax_rows_slots(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ws["prm"], ws["gen"], ws["live"])
+        if self.scores:
+            ops.token_scores_rows(ws["logits"], ws["nxt"], ws["watch"], rec[4:], ws["live"])
         ops.decode_advance_kept_rows(ws["nxt"], ws["mar"], ws["pmx"], ws["kept"] if self.dev_sample else None, rec, ws["ids"],
                                      ws["step"], ws["pos"], ws["kvlen"], ws["gen"], ws["live"])
 
     def results(self):
         for index, ids, mar in self.sched.pop():
+            n = index                                                # the request's place in the input: what sc_of is keyed by
             if self.turns is not None:                               # the slot now holds the context and every id but the last
                 session, _, keys = self.turns[index][:3]
                 self.dec.sessions.end(session, keys, ids)
                 index = session
-            yield index, torch.tensor(ids, dtype=torch.long), torch.tensor(mar, dtype=F32)
+            out = (index, torch.tensor(ids, dtype=torch.long), torch.tensor(mar, dtype=F32))
+            if self.scores:
+                sc = torch.tensor(self.sc_of.pop(n), dtype=torch.float64).to(F32).view(len(ids), 1 + self.W)
+                out += (dict(token_logprobs=sc[:, 0].contiguous(), watch_logprobs=sc[:, 1:].contiguous()),)
+            yield out
 
     def fits(self, emb: torch.Tensor) -> int:
         S0 = emb.shape[0] if emb.dim() == 2 else 0
@@ -975,7 +1062,8 @@ class _SlotRun:
 
     def first_picks(self, logits0: torch.Tensor, sl: slice, seeds_) -> list:
         """The first pick of each prefilled request (rows of logits0) in one launch into the step's result buffers at `sl` and
-        one device->host copy: rows of [id, margin, p_max, kept].  The per-row tail's pick is its step kernel at gen = 0."""
+        one device->host copy: rows of [id, margin, p_max, kept].  The per-row tail's pick is its step kernel at gen = 0.  With
+        scores the SCORE_ROWS entries of mh_token_scores_rows on the same logits are the last items of each row."""
         ws = self.ws
         out = [ws["nxt"][sl], ws["mar"][sl], ws["pmx"][sl]]
         R = logits0.shape[0]
@@ -987,6 +1075,9 @@ class _SlotRun:
             ops.argmax_pmax_rows_slots(logits0, *out, ws["prm"], ws["gen0"][:R])
         else:
             ops.argmax_pmax_rows(logits0, *out, ban_id=self.ban0, inv_temp=self.inv_temp)
+        if self.scores:
+            sc0 = ops.token_scores_rows(logits0, out[0], ws["watch"], ws["sc0"][:, :R])
+            out.extend(sc0[i] for i in range(ops.SCORE_ROWS))
         return torch.stack([o.to(torch.float64) for o in out], 1).tolist()
 
     def host_draw(self, logits_row: torch.Tensor, t: int, seed) -> int:
@@ -1021,8 +1112,27 @@ class _SlotRun:
         picks = self.first_picks(logits0, sl, [req[1] for _, req in group])
         for i, (s, req) in enumerate(group):
             first = self.first_id(picks[i], logits0[i], req[1])
+            if self.scores:
+                self.sc_of[self.sched.admitted] = [self.score_entry(picks[i][-ops.SCORE_ROWS:], first != int(picks[i][0]), logits0[i],
+                                                                    first)]
             if self.sched.admit(s, first, picks[i][1]):
                 self.go_live(s, first, lens[i], req[1])
+
+    def score_entry(self, sc, redrawn: bool, logits_row: torch.Tensor, tok: int) -> list:
+        """One token's [pick log-prob, watch log-probs] from its SCORE_ROWS entries `sc` (lse, pick, watch slots); a token the host
+        drew instead takes x[id] - lse in f32 from the logits row the draw read."""
+        lp = float(logits_row[tok].cpu() - torch.tensor(sc[0], dtype=F32)) if redrawn else float(sc[1])
+        return [lp] + [float(v) for v in sc[2:2 + self.W]]
+
+    def note_scores(self, live, r, ids) -> None:
+        """The scores of one token step's record `r` join their requests' lists (before the scheduler retires finished rows);
+        `ids` = host_draws' answer for the step."""
+        if not self.scores:
+            return
+        sc = r[4:].tolist()
+        for s in live:
+            index = self.sched.rows[s][0]
+            self.sc_of[index].append(self.score_entry([row[s] for row in sc], ids[s] != int(r[0][s]), self.ws["logits"][s], ids[s]))
 
     def host_draws(self, live, r) -> list:
         """The ids of one token step's record `r`, with the rows the rules hand to the host drawn there."""

@@ -72,16 +72,19 @@ def auroc(gt: Sequence[int], score: Sequence[float]) -> float:
     return float((ranks[gt == 1].sum() - n_pos * (n_pos + 1) / 2.0) / (n_pos * n_neg))
 
 
-def scene_performance(records: Iterable[dict], rules: Optional[AnswerRules] = None) -> Tuple[float, float, float]:
+def scene_performance(records: Iterable[dict], rules: Optional[AnswerRules] = None,
+                      score_key: Optional[str] = None) -> Tuple[float, float, float]:
     """(mean accuracy, mean AUROC, mean thresholded accuracy) over scenes (summary_results.py:126-182).
-    Undecided answers (-1) are dropped from all three; the threshold is the largest score of a normal sample."""
+    Undecided answers (-1) are dropped from all three; the threshold is the largest score of a normal sample.
+    `score_key` names the record field AUROC and the threshold are taken from ("llm_anomaly_score": the language model's own
+    score, make_ad_record's llm_score); the default is the reference's choice, the vision expert's score."""
     rules = rules or AnswerRules.default()
     scenes: Dict[str, Dict[str, list]] = {}
     for r in records:
         pred = classify_answer(r["output"], 0, rules)
         scene = r["scene"] if "scene" in r else r["image_path"].split("/")[1]
         s = scenes.setdefault(scene, {"gt": [], "pred": [], "score": []})
-        key = "anomaly_map_scores" if "anomaly_map_scores" in r else "anomaly_score"
+        key = score_key or ("anomaly_map_scores" if "anomaly_map_scores" in r else "anomaly_score")
         if pred != -1:
             s["gt"].append(1 if r["is_anomaly"] else 0)
             s["pred"].append(pred)
@@ -105,16 +108,30 @@ def postprocess_generation(token_ids, tokenizer) -> List[str]:
 
 
 def make_ad_record(image_id: int, img_path: str, is_anomaly: bool, output_text: str,
-                   anomaly_map_max: Optional[float] = None) -> dict:
+                   anomaly_map_max: Optional[float] = None, llm_score: Optional[float] = None) -> dict:
     """One jsonl line for the 'ad' / '1cls' / 'shot' task types (evaluation_aqa_dataset.py:361-384).  `output_text`
-    is already cut at '###'; `anomaly_map_max` is the maximum of the 0..255 expert map."""
+    is already cut at '###'; `anomaly_map_max` is the maximum of the 0..255 expert map.  `llm_score` (an addition of this build,
+    absent by default) is the language model's own anomaly score p(Yes) / (p(Yes) + p(No)) at the first generated token, written
+    as "llm_anomaly_score" in the format of "anomaly_score"."""
     item = {"image_id": int(image_id), "image_path": "/".join(img_path.split("/")[-5:]), "is_anomaly": bool(is_anomaly)}
     if anomaly_map_max is not None:
         ok = ("Yes" in output_text and bool(is_anomaly)) or ("No" in output_text and not bool(is_anomaly))
         item["error"] = "0" if ok else "1"
         item["output"] = output_text
         item["anomaly_score"] = str(round(float(anomaly_map_max) / 255.0, 4))
+    if llm_score is not None:
+        item["llm_anomaly_score"] = str(round(float(llm_score), 4))
     return item
+
+
+def llm_anomaly_score(watch_logprobs_first) -> float:
+    """p_yes / (p_yes + p_no) from the first token step's log-probs of the (Yes, No) ids (generate(output_scores=True,
+    watch_ids=[yes, no])["watch_logprobs"][row, 0]): the softmax over the two, taken in float64."""
+    ly, ln = (float(v) for v in watch_logprobs_first[:2])
+    if ly == ln:                                         # also both -inf
+        return 0.5
+    with np.errstate(over="ignore"):
+        return float(1.0 / (1.0 + np.exp(np.float64(ln) - np.float64(ly))))
 
 
 def write_jsonl(path: str, records: Iterable[dict]) -> None:

@@ -1234,11 +1234,20 @@ class MyriadHIP(nn.Module):
             if v not in (neutral, None):
                 raise NotImplementedError(f"generate({k}={v}) is not implemented on the HIP decode path")
         generator = kw.pop("generator", None)
+        output_scores = bool(kw.pop("output_scores", False))
+        watch_ids = kw.pop("watch_ids", None)
+        watch_ids = () if watch_ids is None else tuple(watch_ids)
+        if watch_ids and not output_scores:
+            raise ValueError("generate(watch_ids=...) names the ids whose log-probs output_scores=True returns: pass both")
+        watch_ids = tuple(ops.score_watch_ids(watch_ids, self.llama.V))     # at most 8 integers in [0, V): ValueError otherwise
+        if output_scores and num_beams > 1:
+            raise NotImplementedError(f"generate(num_beams={num_beams}, output_scores=True): beam search reports "
+                                      "sequences_scores (last_generate_stats); per-token scores are not implemented with beams")
         if kw:
             raise TypeError(f"generate() got unsupported arguments: {sorted(kw)}")
         return dict(stops=stops, max_new=max_new, max_len=None if max_new is not None else max_len, do_sample=do_sample,
                     top_p=top_p, temperature=temperature, min_length=min_length, eos_id=eos_id, top_k=top_k, rep_pen=rep_pen,
-                    num_beams=num_beams, beam_kw=beam_kw, generator=generator)
+                    num_beams=num_beams, beam_kw=beam_kw, generator=generator, output_scores=output_scores, watch_ids=watch_ids)
 
     @torch.no_grad()
     def generate(self, samples, **generate_kwargs):
@@ -1262,7 +1271,15 @@ class MyriadHIP(nn.Module):
         finished_hypotheses and graph_replays.  Beam search applies the stop sequences per hypothesis, greedy / sampled decoding
         keeps the reference's row-0 rule.  Refused with beams: do_sample (beam sampling), repetition_penalty != 1 and
         num_beams > 8.  Without beams, length_penalty / num_return_sequences other than 1 raise NotImplementedError and
-        early_stopping is an unknown argument, as before."""
+        early_stopping is an unknown argument, as before.
+
+        output_scores=True (opt-in, with watch_ids = up to 8 token ids) adds "token_logprobs" [B, L] f32, the log-probability of
+        every returned id, and "watch_logprobs" [B, L, W], that of each watched id at the same step: the log-softmax at
+        temperature 1 of the logits the pick was made from (after the repetition penalty when on; temperature, top-k, top-p and
+        the EOS ban do not enter), computed inside the captured token step (LlamaHIP.greedy_generate).  Positions padded after
+        a row finished are 0.0.  watch_logprobs[:, 0] of the "Yes" / "No" ids is the model's own anomaly score
+        (eval_aqa.py --llm-score).  With num_beams > 1 it raises NotImplementedError; more than 8 ids, a non-integer or an id
+        outside the vocabulary is a ValueError."""
         self.finish_update()
         a = self._generate_args(generate_kwargs)
         stops, max_new, max_len, do_sample, top_p, temperature = (a[k] for k in ("stops", "max_new", "max_len", "do_sample", "top_p",
@@ -1288,8 +1305,12 @@ class MyriadHIP(nn.Module):
         else:
             ids = self.llama.greedy_generate(emb, max_new_tokens=max_new, stop_ids=stops, min_length=min_length, eos_id=eos_id,
                                              do_sample=do_sample, top_p=top_p, temperature=temperature, generator=generator,
-                                             top_k=top_k, repetition_penalty=rep_pen)
+                                             top_k=top_k, repetition_penalty=rep_pen, return_scores=a["output_scores"],
+                                             watch_ids=a["watch_ids"])
         self.last_generate_stats = self.llama.last_generate_stats
+        if a["output_scores"]:
+            ids, sc = ids
+            return {"token_ids": ids, "ve_anomaly_maps": maps, **sc}
         return {"token_ids": ids, "ve_anomaly_maps": maps}
 
     def _prompt_ids_rows(self, samples, B: int, stage: int):
@@ -1323,7 +1344,8 @@ class MyriadHIP(nn.Module):
         An unknown argument is a TypeError.  `last_generate_stats` holds the engine's counters (steps, prefills, graph_replays,
         graph_captures, live_row_steps, occupancy, prefill_passes, packed_rows, host_sampled_rows, device_sampled_rows) once the
         stream is exhausted.  `prefill_batch` = P > 1 prefills up to P waiting samples in one packed pass whenever slots are free
-        and `refill_min` = k holds a refill back until k slots are free (SlotDecoder.run); both default to 1, the one-sample refill."""
+        and `refill_min` = k holds a refill back until k slots are free (SlotDecoder.run); both default to 1, the one-sample refill.
+        output_scores / watch_ids as in generate(): each yielded dict gains "token_logprobs" [L] and "watch_logprobs" [L, W]."""
         self.finish_update()
         a = self._generate_args(generate_kwargs)
         if a["num_beams"] > 1:
@@ -1364,13 +1386,13 @@ class MyriadHIP(nn.Module):
         dec = self._slot_decoder[1]
 
         def stream():
-            for index, ids, _ in dec.run(rows(), max_new_tokens=max_new, stop_ids=a["stops"], eos_id=a["eos_id"],
-                                         min_length=a["min_length"], do_sample=a["do_sample"], top_p=a["top_p"],
-                                         temperature=a["temperature"], top_k=a["top_k"], generator=a["generator"], ordered=True,
-                                         prefill_batch=prefill_batch, refill_min=refill_min, repetition_penalty=a["rep_pen"],
-                                         seeds=seeds):
+            for index, ids, _, *sc in dec.run(rows(), max_new_tokens=max_new, stop_ids=a["stops"], eos_id=a["eos_id"],
+                                              min_length=a["min_length"], do_sample=a["do_sample"], top_p=a["top_p"],
+                                              temperature=a["temperature"], top_k=a["top_k"], generator=a["generator"], ordered=True,
+                                              prefill_batch=prefill_batch, refill_min=refill_min, repetition_penalty=a["rep_pen"],
+                                              seeds=seeds, return_scores=a["output_scores"], watch_ids=a["watch_ids"]):
                 self.last_generate_stats = dec.last_stats
-                yield {"index": index, "token_ids": ids, "ve_anomaly_map": side[index]}
+                yield {"index": index, "token_ids": ids, "ve_anomaly_map": side[index], **(sc[0] if sc else {})}
                 side[index] = None
             self.last_generate_stats = dec.last_stats
 

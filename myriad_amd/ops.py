@@ -3,6 +3,7 @@ and the current HIP stream; all arithmetic happens in libmyriad_hip.so.  No fall
 from __future__ import annotations
 
 import math
+import numbers
 from typing import Optional
 
 import os
@@ -1296,6 +1297,39 @@ def decode_advance_kept_rows(nxt, margin, pmax, kept, rec, next_ids, step_dev, p
     R = (nxt if live is None else live).numel()
     _lib.check(_L().mh_decode_advance_kept_rows(_p(nxt), _p(margin), _p(pmax), _p(kept), _p(rec), _p(next_ids), _p(step_dev), _p(pos),
                                                 _p(kvlen), _p(gen), _p(live), R, _s()), "mh_decode_advance_kept_rows")
+
+
+SCORE_WATCH_MAX = 8    # watch slots of mh_token_scores_rows (include/myriad_hip.h)
+SCORE_ROWS = 2 + SCORE_WATCH_MAX    # rows of its output: lse, the pick's log-prob, one per watch slot
+
+
+def score_watch_ids(watch_ids, V: int) -> list:
+    """The decode loops' check of `watch_ids`: at most SCORE_WATCH_MAX integers in [0, V) (ValueError otherwise), as a list."""
+    watch = list(watch_ids)
+    if len(watch) > SCORE_WATCH_MAX:
+        raise ValueError(f"watch_ids: at most {SCORE_WATCH_MAX} ids, got {len(watch)}")
+    for w in watch:
+        if isinstance(w, bool) or not isinstance(w, numbers.Integral) or not 0 <= int(w) < V:
+            raise ValueError(f"watch_ids: integers in [0, {V}), got {w!r}")
+    return [int(w) for w in watch]
+
+
+def score_watch_table(watch_ids, V: int) -> torch.Tensor:
+    """score_watch_ids as the int32 [SCORE_WATCH_MAX] host table the kernel reads once uploaded: unused slots hold -1."""
+    watch = score_watch_ids(watch_ids, V)
+    return torch.tensor(watch + [-1] * (SCORE_WATCH_MAX - len(watch)), dtype=torch.int32)
+
+
+def token_scores_rows(logits: torch.Tensor, ids: torch.Tensor, watch: torch.Tensor, out: torch.Tensor, live=None):
+    """Log-softmax (temperature 1) of each row of f32 logits [R, V] at its pick ids[r] and at the SCORE_WATCH_MAX int32 ids of the
+    device table `watch` (-1 = unused: 0.0) into out [SCORE_ROWS, >= R] f32 (any row stride): lse, the pick's log-prob, one row per
+    watch slot.  A row with live[r] == 0 or ids[r] < 0 gets zeros and its logits are not read."""
+    R, V = logits.shape
+    if watch.numel() != SCORE_WATCH_MAX or watch.dtype != torch.int32 or out.shape[0] != SCORE_ROWS or out.stride(1) != 1:
+        raise _lib.MyriadHipError(f"token_scores_rows: watch is int32 [{SCORE_WATCH_MAX}] and out f32 [{SCORE_ROWS}, >= R]")
+    _lib.check(_L().mh_token_scores_rows(_p(logits), logits.stride(0), _p(ids), _p(watch), _p(out), out.stride(0), R, V, _p(live),
+                                         _s()), "mh_token_scores_rows")
+    return out
 
 
 BEAM_MAX = 8           # most beams mh_beam_topk / mh_beam_reorder_kv take (include/myriad_hip.h)

@@ -30,7 +30,12 @@ reproduce.  Give it --requests 256 or more: one wave of 64 slots would otherwise
 --step-rows 16,32,48,64 times the slot engine's captured token step alone, every row live at --step-keys cached keys, for each
 kind of --weights, interleaved per repeat (--repeats rounds of --step-replays replays each): up to 16 rows the 16-row kernel,
 above it ops.gemv_packed_wide.  --step-gemm 32,64 adds greedy_generate's step at those row counts: the row-major bf16 GEMMs that
-every decode loop but the slot engine runs above 16 rows."""
+every decode loop but the slot engine runs above 16 rows.
+--scores (with --slots 8,64, the default there) measures what return_scores costs: the same request list decoded at batch 1 (the
+first --requests / 8 requests), and through each slot count, with and without the token scores (two watched ids), interleaved per
+repeat in one process, as run time and samples/s; then the captured token step of each of those views alone, every row live,
+replayed --step-replays times per round from --step-keys keys (fewer where the view's cache is shorter); then mh_token_scores_rows alone at 1 and 64 rows of the model's
+vocabulary.  min / median / max of both sides."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -58,10 +63,13 @@ ap.add_argument("--step-replays", type=int, default=40, help="with --step-rows: 
 ap.add_argument("--requests", type=int, default=64, help="requests of the --slots run")
 ap.add_argument("--prefill-batch", default="1", help="comma list: prefill_batch of the --slots run, timed interleaved")
 ap.add_argument("--refill-min", default="1", help="comma list: refill_min of the --slots run, timed interleaved")
+ap.add_argument("--scores", action="store_true", help="the cost of return_scores: batch 1 and each --slots count, with and without")
 ap.add_argument("--merge", default="", help="comma list of 0 / 1: bordered / merged LoRA qkv in the token step, timed interleaved")
 a = ap.parse_args()
 # --slots is a string so that it can be a list; from here on a.slots is the single count (0: none or a list) and slot_counts the list
 slot_counts = [int(x) for x in a.slots.split(",") if x]
+if a.scores and slot_counts in ([], [0]):
+    slot_counts = [8, 64]
 a.slots = slot_counts[0] if len(slot_counts) == 1 else 0
 modes = [m for m in a.modes.split(",") if m] or ["sample" if a.sample else "greedy"]
 if "beam" in modes and "greedy" in modes:
@@ -163,7 +171,7 @@ if a.step_rows:
         print(f"{label} rows {R}: {t:.3f} ms/step (min {ts[0]:.3f}, max {ts[-1]:.3f}), {R / t * 1e3:.0f} row-tok/s{ratio}")
     sys.exit(0)
 
-if a.slots or len(slot_counts) > 1:
+if a.slots or len(slot_counts) > 1 or a.scores:
     L, N, new = model.llama, a.slots or slot_counts[0], a.new
     gq = torch.Generator().manual_seed(11)
     lens = [int(x) for x in torch.randint(24, 161, (a.requests,), generator=gq)]
@@ -184,6 +192,93 @@ if a.slots or len(slot_counts) > 1:
         x[-1] = emb_rows[d]
         reqs.append(x.to(dev))
     kw = dict(max_new_tokens=new, stop_ids=((1000,),), eos_id=-5, min_length=0)
+    if a.scores:
+        from myriad_amd import ops
+        cap, skw = 64 * ((160 + new + 63) // 64), dict(return_scores=True, watch_ids=[1000, 1001])
+        decs = {n: L.slot_decoder(n, cap) for n in slot_counts}
+        # batch 1: requests of one workspace capacity (greedy_generate keeps three workspaces; here two, with and without scores)
+        few = [x for x in reqs if 64 < x.shape[0] + new + 2 <= 128][:max(1, len(reqs) // 8)]
+        cols = [("batch 1", 0)] + [(f"slots {n}", n) for n in slot_counts]
+
+        def run_col(n, on):
+            extra = skw if on else {}
+            if n == 0:
+                return sum(L.greedy_generate(x[None], **kw, **extra)[0].shape[-1] for x in few), len(few)
+            return sum(len(out[1]) for out in decs[n].run(reqs, **kw, **extra)), len(reqs)
+
+        for _, n in cols:
+            for on in (False, True):
+                run_col(n, on)                                         # warm-up: kernels, both graphs of every column
+        res = {(name, on): [] for name, _ in cols for on in (False, True)}
+        for _ in range(max(1, a.repeats)):
+            for name, n in cols:
+                for on in (False, True):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    toks, samples = run_col(n, on)
+                    torch.cuda.synchronize()
+                    res[(name, on)].append((time.perf_counter() - t0, toks, samples))
+
+        def mmm(ts, scale=1.0, fmt="{:.3f}"):
+            ts = sorted(ts)
+            return " / ".join(fmt.format(v * scale) for v in (ts[0], ts[len(ts) // 2], ts[-1]))
+
+        print(f"{len(reqs)} requests (batch 1: the first {len(few)}), prompts {min(lens)}..{max(lens)} rows, {len(L.layers)} layers, "
+              f"weights {L._packed['kind'] if L._packed else 'bf16'}; min / median / max of {max(1, a.repeats)} interleaved repeats")
+        for name, _ in cols:
+            for on in (False, True):
+                r = res[(name, on)]
+                print(f"{name} scores {'on ' if on else 'off'}: run {mmm([t for t, _, _ in r], 1e3, '{:.1f}')} ms, "
+                      f"{mmm([sm / t for t, _, sm in r], 1.0, '{:.2f}')} samples/s, {r[-1][1]} tokens")
+        # the captured step of each view alone: every row live at --step-keys keys, reset before each round
+        views = [("batch 1", on, next(w for k, w in L._decode_ws.items() if (k[-1] == "scores") == on and k[0] == 1))
+                 for on in (False, True)]
+        for n in slot_counts:
+            views += [(f"slots {n}", on, decs[n].views[decs[n]._view_key(1.0, None, False, on)]) for on in (False, True)]
+        n_rep, step_t = a.step_replays, {}
+        for rnd in range(max(1, a.repeats) + 1):                       # round 0 warms the replays up
+            for name, on, ws in views:
+                keys = min(a.step_keys, ws["T"] - n_rep - 2)            # the round's appends stay inside the cache
+                assert keys > 0, (ws["T"], n_rep)
+                ws["pos"].fill_(keys)
+                ws["kvlen"].fill_(keys + 1)
+                if "live" in ws:
+                    ws["live"].fill_(1)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(n_rep):
+                    ws["graph"].replay()
+                e1.record()
+                torch.cuda.synchronize()
+                if rnd:
+                    step_t.setdefault((name, on), []).append(e0.elapsed_time(e1) / n_rep)
+        for name, on, _ in views:
+            print(f"{name} token step, scores {'on ' if on else 'off'}: {mmm(step_t[(name, on)])} ms/step ({n_rep} replays per round)")
+        for name in dict.fromkeys(v[0] for v in views):
+            off, on_ = sorted(step_t[(name, False)]), sorted(step_t[(name, True)])
+            print(f"{name}: median step +{(on_[len(on_) // 2] - off[len(off) // 2]) * 1e3:.1f} us with scores "
+                  f"({on_[len(on_) // 2] / off[len(off) // 2] - 1:+.2%})")
+        for rows in (1, 64):                                           # the launch alone, 50 per captured graph
+            lg = torch.randn(rows, L.V, device=dev)
+            ids = torch.randint(0, L.V, (rows,), device=dev)
+            wt, out = ops.score_watch_table([1000, 1001], L.V).to(dev), torch.zeros(ops.SCORE_ROWS, rows, device=dev)
+            ops.token_scores_rows(lg, ids, wt, out)
+            torch.cuda.synchronize()
+            g_ = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g_):
+                for _ in range(50):
+                    ops.token_scores_rows(lg, ids, wt, out)
+            ts = []
+            for rnd in range(max(1, a.repeats) + 1):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                g_.replay()
+                e1.record()
+                torch.cuda.synchronize()
+                if rnd:
+                    ts.append(e0.elapsed_time(e1) / 50)
+            print(f"mh_token_scores_rows, {rows} rows of V = {L.V}: {mmm(ts, 1e3, '{:.2f}')} us per launch (50 back to back in a graph)")
+        sys.exit(0)
     dec = L.slot_decoder(N, 64 * ((160 + new + 63) // 64))
 
     if a.sample:
