@@ -134,6 +134,25 @@ LoRA (lora.hip).  The dropout mask is stated independently of the library: keep_
         untouched (lora_refresh_check).
     rmsnorm backward behind lora_dx: rmsnorm_ref_bound(dy_err=...) carries the bound of d(xn) through the norm (dx is linear in
         dy): r |w| e + |x| r^3 / D sum |x w| e.
+Q-Former training (the DROP instances of attention.hip, qf_dropout.hip, wgrad.hip's TN GEMM).  Every mask is keep_mask_ref; its
+    factor Z is 0 or the fp32 quotient 1 / (1 - p) (a correctly rounded division: the same value on both sides).
+    attention dropout, attn_ref_bound(keep=Z [B, H, Sq, Sk]): the forward sums the undropped exponentials e (lse is unchanged),
+        forms e z in fp32 (one more rounding: c_o gains u32), rounds to bf16 and multiplies by v: o = (P o Z) v with
+        c_o (P o Z)|v|.  Backward, from the dropped o it is handed: delta = rowsum(o dO) = sum_j P_ij Z_ij (dO v^T)_ij, so
+        dS = P (Z o dP - delta) with dP = dO v^T; the kernels form dP z in fp32: e_dP = Z o ((g_acc(D) + u32) |dO||v|^T), a
+        dout_err term likewise times Z; e_dS, dq and dk follow unchanged.  dv = bf16(P_b o Z)^T dO: the error terms carry P_b o Z
+        and u32 (the product e z) beside u16.  An element whose mask is flipped moves dS by P ik |dP| there: out of bound where
+        P is not small (tests/test_fp64_bounds_cpu.py).
+    layernorm dropout: x = z keep_in + res: 2 u32 (|z keep_in| + |x|) (a product and a sum, or one fused operation); the
+        statistics come from the fp32 x the kernel wrote, so the LayerNorm reference takes that x_out as its input;
+        y = LN(x_out) keep_out: keep_out y_bound + u32 |y|, then the bf16 rounding.  The sums are per-thread serial sums of
+        ceil(D / 256) scalar terms -- never more than g_row's 4 ceil(D / 1024).  Backward: g = dy keep_out is one product,
+        dy_err = u32 |g| through layernorm_ref_bound(dy_err=...): dx is linear in dy, a dy moved by e moves it by at most
+        r (|w| e + mean(|w| e) + |xh| mean(|w| e |xh|)); dz = bf16(dx keep_in): keep_in e + u32 |dz|, then the rounding.
+    tn_wgrad: dW = dy^T x over the rows: a split adds one MFMA (32 exact products, one rounding; g_acc counts two) per 32-row
+        step and the splits are added in split order: g_acc(M, splits) |dy|^T |x| (+ u32 |dW| onto an earlier value).  db: a
+        staging thread adds its column over the steps of its split, the 32 staging rows are added in order, then the splits:
+        (ceil(rows_per / 32) + 32 + splits + 1) u32 sum_m |dy| (+ u32 |db| onto an earlier value).
 """
 from __future__ import annotations
 
@@ -294,13 +313,16 @@ def _out_round(ref, e):
     return e + U16 * (ref.abs() + e)
 
 
-def attn_ref_bound(q, k, v, scale, mask, q_err=None, k_err=None, dout=None, dout_err=None, o_in=None, lse_in=None):
+def attn_ref_bound(q, k, v, scale, mask, q_err=None, k_err=None, dout=None, dout_err=None, o_in=None, lse_in=None, keep=None):
     """fp64 attention of bf16-valued q, k, v [B, H, S, D] (q, k as the kernel multiplies them: rotated and rounded, with the
     per-element uncertainties q_err / k_err of rope_bf16) and the visibility mask [B, 1, Sq, Sk].  Returns a dict: o, lse and
     their bounds; with dout [B, H, Sq, D] also dq, dk, dv (w.r.t. the given q, k, v) and their bounds -- the backward of the
     o / lse it is handed (o_in, lse_in: what the kernel's backward reads; default the exact ones).  dout_err bounds an error
-    dout itself carries (a product rounded to bf16).  *_bound_acc: the bounds before the output's bf16 rounding."""
+    dout itself carries (a product rounded to bf16).  *_bound_acc: the bounds before the output's bf16 rounding.
+    keep: the attention-probability dropout factor Z [B, H, Sq, Sk] (0 or the fp32 quotient 1 / (1 - p)): o = (P o Z) v with
+    the lse of the undropped P, and the backward of that (module docstring); o_in is then the dropped output."""
     q, k, v = q.double(), k.double(), v.double()
+    Z = None if keep is None else keep.double()
     qe = torch.zeros_like(q) if q_err is None else q_err.double()
     ke = torch.zeros_like(k) if k_err is None else k_err.double()
     D, Sq, Sk = q.shape[-1], q.shape[-2], k.shape[-2]
@@ -309,14 +331,17 @@ def attn_ref_bound(q, k, v, scale, mask, q_err=None, k_err=None, dout=None, dout
     s = s.masked_fill(~mask, float("-inf"))
     lse = torch.logsumexp(s, -1)
     P = torch.exp(s - lse[..., None])
-    o = P @ v
+    PZ = P if Z is None else P * Z
+    o = PZ @ v
     Vabs = v.abs()
-    PV = P @ Vabs
+    PV = PZ @ Vabs
     ds = (g_acc(D) * (q.abs() @ k.abs().transpose(-1, -2)) + qe @ k.abs().transpose(-1, -2) + q.abs() @ ke.transpose(-1, -2)
           + qe @ ke.transpose(-1, -2)) * scale
     ds = (ds + 2 * U32 * s.abs().masked_fill(~mask, 0.0)).masked_fill(~mask, 0.0)
     ds_row = ds.amax(-1)                                                             # [B, H, Sq]
     c_o = 2 * U16 + g_acc(Sk) + 2 * ds_row
+    if Z is not None:
+        c_o = c_o + U32                                                              # the fp32 product e z
     out = dict(o=o, lse=lse, o_bound=c_o[..., None] * PV + U32 * U16 * PV,
                lse_bound=ds_row + g_acc(Sk) + 4 * U32 * (lse.abs() + 1))
     if dout is None:
@@ -328,26 +353,35 @@ def attn_ref_bound(q, k, v, scale, mask, q_err=None, k_err=None, dout=None, dout
     Pb = torch.exp(s - lse_b[..., None])                                            # masked: exp(-inf) = 0
     rho = (ds + 2 * U32 * (s - lse_b[..., None]).abs().masked_fill(~mask, 0.0) + 4 * U32).masked_fill(~mask, 0.0)
     dP = g @ v.transpose(-1, -2)
+    if Z is not None:
+        dP = Z * dP
     delta = (g * o_b).sum(-1, keepdim=True)
     T = dP - delta
     dS = Pb * T
-    e_dP = g_acc(D) * (gabs @ Vabs.transpose(-1, -2))
+    GV = gabs @ Vabs.transpose(-1, -2)
+    e_dP = g_acc(D) * GV
     e_delta = g_acc(D) * (gabs * o_b.abs()).sum(-1, keepdim=True)
     if dout_err is not None:                                                         # dS is linear in dO
         e = dout_err.double()
         e_dP = e_dP + e @ Vabs.transpose(-1, -2)
         e_delta = e_delta + (e * o_b.abs()).sum(-1, keepdim=True)
+    if Z is not None:                                                                # dP z: one more fp32 product
+        e_dP = Z * (e_dP + U32 * GV)
     e_dS = rho * Pb * T.abs() + Pb * (e_dP + e_delta)
     e_dS = e_dS + U16 * (dS.abs() + e_dS)                                            # dS rounded to bf16
     dSa = dS.abs()
     dq = scale * dS @ k
     dk = scale * dS.transpose(-1, -2) @ q
-    dv = Pb.transpose(-1, -2) @ g
+    PbZ = Pb if Z is None else Pb * Z                                                # what the dV product multiplies, before its bf16 rounding
+    dv = PbZ.transpose(-1, -2) @ g
     e_dq = scale * (e_dS @ k.abs() + g_acc(Sk) * (dSa @ k.abs()) + dSa @ ke)
     e_dk = scale * (e_dS.transpose(-1, -2) @ q.abs() + g_acc(Sq) * (dSa.transpose(-1, -2) @ q.abs()) + dSa.transpose(-1, -2) @ qe)
-    e_dv = (((U16 + rho * (1 + U16)) * Pb).transpose(-1, -2) @ gabs + g_acc(Sq) * (Pb.transpose(-1, -2) @ gabs))
+    if Z is None:
+        e_dv = (((U16 + rho * (1 + U16)) * Pb).transpose(-1, -2) @ gabs + g_acc(Sq) * (Pb.transpose(-1, -2) @ gabs))
+    else:                                                                            # + u32: the fp32 product e z
+        e_dv = (((U16 + U32 + rho * (1 + U16)) * PbZ).transpose(-1, -2) @ gabs + g_acc(Sq) * (PbZ.transpose(-1, -2) @ gabs))
     if dout_err is not None:
-        e_dv = e_dv + Pb.transpose(-1, -2) @ dout_err.double()
+        e_dv = e_dv + PbZ.transpose(-1, -2) @ dout_err.double()
     out.update(dq=dq, dk=dk, dv=dv, dq_bound_acc=e_dq, dk_bound_acc=e_dk, dv_bound_acc=e_dv,
                dq_bound=_out_round(dq, e_dq), dk_bound=_out_round(dk, e_dk), dv_bound=_out_round(dv, e_dv))
     return out
@@ -465,9 +499,12 @@ def rmsnorm_ref_bound(x, w, eps, dy=None, dres=None, dy_err=None):
     return out
 
 
-def layernorm_ref_bound(x, w, b, eps, dy=None, dres=None):
+def layernorm_ref_bound(x, w, b, eps, dy=None, dres=None, dy_err=None):
     """fp64 LayerNorm of fp32 x [M, D] (b may be None for the backward only): dict y, y_bound, y_bf16_bound; with dy also dx,
-    dx_bound, dx_bf16_bound.  Raises if a row's variance is lost to the mean's rounding although the row is not constant."""
+    dx_bound, dx_bf16_bound.  Raises if a row's variance is lost to the mean's rounding although the row is not constant.
+    dy_err: an element-wise bound on an error dy itself carries.  dx = r (gw - mean(gw) - xh mean(gw xh)), gw = dy w, is linear in
+    dy, so a dy moved by at most e moves it by at most r (|w| e + mean(|w| e) + |xh| mean(|w| e |xh|)); what the other terms of
+    the bound change when they are evaluated at the moved dy is of the order u32 e and left out."""
     x, w = x.double(), w.double()
     D = x.shape[1]
     eps = f32_value(eps)
@@ -500,8 +537,93 @@ def layernorm_ref_bound(x, w, b, eps, dy=None, dres=None):
     dr = dres.double() if dres is not None else torch.zeros_like(core)
     dx = core + dr
     e = r * e_inner + core.abs() * (rel_r + U32) + 2 * U32 * (dx.abs() + dr.abs())
+    if dy_err is not None:
+        we = w.abs() * dy_err.double()
+        e = e + r * (we + we.mean(1, keepdim=True) + xh.abs() * (we * xh.abs()).mean(1, keepdim=True))
     out.update(dx=dx, dx_bound=e, dx_bf16_bound=bf16_out(dx, e))
     return out
+
+
+def ln_dropout_fwd_ref_bound(z, res, w, b, eps, keep_in=None, keep_out=None, x_out=None):
+    """fp64 references of mh_layernorm_fwd_dropout (module docstring): dict x, x_bound (res given: x = z keep_in + res) and y,
+    y_bound, y_bf16_bound of y = LN(x_in) keep_out, where x_in is the fp32 x_out the kernel wrote and re-reads (res given) or
+    z itself.  keep_* : [M, D] factors (0 or the fp32 quotient), None for p = 0."""
+    z64 = z.double()
+    out = {}
+    x_in = z
+    if res is not None:
+        zk = z64 * keep_in.double() if keep_in is not None else z64
+        x = zk + res.double()
+        out.update(x=x, x_bound=2 * U32 * (zk.abs() + x.abs()))
+        x_in = x_out
+    r = layernorm_ref_bound(x_in, w, b, eps)
+    y, e = r["y"], r["y_bound"]
+    if keep_out is not None:
+        ko = keep_out.double()
+        y = y * ko
+        e = ko * e + U32 * y.abs()
+    out.update(y=y, y_bound=e, y_bf16_bound=bf16_out(y, e))
+    return out
+
+
+def ln_dropout_bwd_ref_bound(dy, x, w, eps, keep_in=None, keep_out=None):
+    """fp64 references of mh_layernorm_bwd_dropout: g = dy keep_out (one fp32 product: dy_err = u32 |g|) through
+    layernorm_ref_bound gives dx (the residual's gradient, unmasked) and dx_bound; dz = bf16(dx keep_in) with
+    dz_bound = bf16_out(dz, keep_in e + u32 |dz|)."""
+    g, ge = dy.double(), None
+    if keep_out is not None:
+        g = g * keep_out.double()
+        ge = U32 * g.abs()
+    r = layernorm_ref_bound(x, w, None, eps, dy=g, dy_err=ge)
+    dx, e = r["dx"], r["dx_bound"]
+    dz, ez = dx, e
+    if keep_in is not None:
+        ki = keep_in.double()
+        dz = dx * ki
+        ez = ki * e + U32 * dz.abs()
+    return dict(dx=dx, dx_bound=e, dz=dz, dz_bound=bf16_out(dz, ez))
+
+
+def ln_dropout_inputs(M: int, D: int, form: str, seed: int):
+    """(z, res, w, b, dy, p_in, p_out) fp32 on the host for the four forms mh_layernorm_fwd_dropout is called in: "a" the
+    embeddings form (no residual, output mask; z = norm_rows), "b" the sublayer form (res = norm_rows, z ~ N(0,1), input mask),
+    "c" both masks, "d" a residual and no mask.  The weight has a zero and negative entries where D allows."""
+    w = norm_weight(D, seed=seed + 2) if D >= 8 else 1 + 0.5 * rnd(D, seed=seed + 2)
+    b, dy = 0.1 * rnd(D, seed=seed + 3), rnd(M, D, seed=seed + 4)
+    if form == "a":
+        return norm_rows(M, D, seed=seed), None, w, b, dy, 0.0, 0.1
+    p_in, p_out = {"b": (0.1, 0.0), "c": (0.1, 0.5), "d": (0.0, 0.0)}[form]
+    return rnd(M, D, seed=seed + 1), norm_rows(M, D, seed=seed), w, b, dy, p_in, p_out
+
+
+TN_BM = 32                 # reduction rows one step of mh_gemm_tn_wgrad stages: one MFMA per step and output tile
+
+
+def tn_rows_per(M: int, splits: int) -> int:
+    """Rows a split of mh_gemm_tn_wgrad covers: ceil(M / splits) rounded up to whole 32-row steps (at least one)."""
+    return max(TN_BM, -(-(-(-M // splits)) // TN_BM) * TN_BM)
+
+
+def tn_wgrad_ref_bound(dy, x, splits, prev=None, prev_bias=None):
+    """fp64 (dW, bound, db, bound) of mh_gemm_tn_wgrad: dW [N, K] = dy^T x (+ prev), db [N] = sum_m dy (+ prev_bias), from
+    bf16 dy [M, N], x [M, K].  A split adds one 16x16x32 MFMA per 32-row step to its fp32 accumulator (32 exact bf16 products
+    and one rounding each; g_acc counts two per 32) and the splits are summed in split order: g_acc(M, splits) |dy|^T |x|, and
+    u32 |dW| for the sum onto prev.  db: a staging thread adds its column's value at every step of its split serially
+    (rows_per / 32 terms), the 32 staging rows are added in order, then the splits:
+    (ceil(rows_per / 32) + 32 + splits + 1) u32 sum_m |dy| (+ u32 |db| for the sum onto prev_bias)."""
+    d64, x64 = dy.double(), x.double()
+    M = d64.shape[0]
+    dW = d64.T @ x64
+    e_W = g_acc(M, splits) * (d64.abs().T @ x64.abs())
+    db = d64.sum(0)
+    e_b = (-(-tn_rows_per(M, splits) // TN_BM) + TN_BM + splits + 1) * U32 * d64.abs().sum(0)
+    if prev is not None:
+        dW = dW + prev.double()
+        e_W = e_W + U32 * dW.abs()
+    if prev_bias is not None:
+        db = db + prev_bias.double()
+        e_b = e_b + U32 * db.abs()
+    return dW, e_W, db, e_b
 
 
 LNP_ROWS = 16              # rows a partial block of mh_layernorm_param_grads sums serially
@@ -767,6 +889,17 @@ def frame_of(buf, win_rows: slice, win_cols: slice):
 def assert_frame_untouched(buf, win_rows: slice, win_cols: slice, what=""):
     for i, f in enumerate(frame_of(buf, win_rows, win_cols)):
         assert_untouched(f, f"{what} frame part {i}")
+
+
+def out_window(B, S, W, device):
+    """A poisoned bf16 [B, S, W] view of a [B, S + 4, W + 8] buffer (the extra rows and columns must stay untouched)."""
+    buf = poisoned((B, S + 4, W + 8), torch.bfloat16, device)
+    return buf, buf[:, :S, :W]
+
+
+def check_outside(buf, S, W, what):
+    assert_untouched(buf[:, S:], what + " rows past S")
+    assert_untouched(buf[:, :, W:], what + " columns past W")
 
 
 # ---------------------------------------------------------------------------------------------------------------- conv stack

@@ -1537,3 +1537,329 @@ def test_rmsnorm_bound_carries_an_error_of_dy_and_leaves_the_default_unchanged()
     moved = fb.rmsnorm_ref_bound(x, w, 1e-6, dy=dy.double() + sign * e.double(), dres=dres)["dx"]
     # (the allowance is attained exactly on an all-zero row: 1e-9 relative for the fp64 evaluation of the two sides)
     fb.assert_within(moved, r1["dx"], (r1["dx_bound"] - r0["dx_bound"]) * (1 + 1e-9) + 1e-300, "dy_err")
+
+
+def test_layernorm_bound_carries_an_error_of_dy_and_leaves_the_default_unchanged():
+    x, w = fb.norm_rows(7, 252, seed=56), fb.norm_weight(252, seed=57)
+    dy, dres = fb.rnd(7, 252, seed=58), fb.rnd(7, 252, seed=59)
+    r0 = fb.layernorm_ref_bound(x, w, None, 1e-12, dy=dy, dres=dres)
+    e = 1e-3 * dy.abs() + 1e-6
+    r1 = fb.layernorm_ref_bound(x, w, None, 1e-12, dy=dy, dres=dres, dy_err=e)
+    assert torch.equal(r0["dx"], r1["dx"]) and bool((r1["dx_bound"] >= r0["dx_bound"]).all())
+    assert torch.equal(fb.layernorm_ref_bound(x, w, None, 1e-12, dy=dy, dres=dres, dy_err=torch.zeros_like(dy))["dx_bound"],
+                       r0["dx_bound"])
+    # a dy moved by its whole allowance, with either sign per element, stays inside the widened bound around the original dx
+    sign = torch.where(fb.rnd(7, 252, seed=60) > 0, 1.0, -1.0)
+    moved = fb.layernorm_ref_bound(x, w, None, 1e-12, dy=dy.double() + sign * e.double(), dres=dres)["dx"]
+    fb.assert_within(moved, r1["dx"], (r1["dx_bound"] - r0["dx_bound"]) * (1 + 1e-9) + 1e-300, "dy_err")
+
+
+# -------------------------------------------------------------------------------------- Q-Former training: attention dropout
+QF_SEED = 0x3C5A7E1F90B2D486              # 62 bits; | 1 << 63 takes the second draw
+
+
+def _flat_keep(idx, p, seed=QF_SEED):
+    """The keep factor at the flat mask indices idx (any shape, int64)."""
+    return fb.keep_mask_ref(seed, 1, int(idx.max()) + 1, p).reshape(-1)[idx]
+
+
+def _attn_mask_index(B, H, Sq, Sk, head=True, stride=None):
+    b, h, i, j = torch.meshgrid(torch.arange(B), torch.arange(H), torch.arange(Sq), torch.arange(Sk), indexing="ij")
+    return ((b * H + (h if head else 0)) * Sq + i) * (Sk if stride is None else stride) + j
+
+
+ATTN_DROP_MASK_MUTANTS = ["stride_rounded_to_64", "head_dropped", "transposed", "last_key_tile_unmasked", "last_query_rows_unmasked"]
+ATTN_DROP_MUTANTS = ATTN_DROP_MASK_MUTANTS + ["rowsum_after_mask", "dq_unmasked", "dk_unmasked", "dv_unmasked", "delta_from_undropped_o",
+                                              "one_element_flipped"]
+
+
+def emu_attn_dropout(q, k, v, dout, scale, p, mutant=None):
+    """The DROP instances of the tiled kernels (attn_fwd_kernel, attn_bwd_dq_kernel, attn_bwd_dkv_kernel) in fp32: online softmax
+    over 64-key tiles, the row sum of the undropped exponentials, e z one fp32 product rounded to bf16 before P V; the backward
+    from the bf16 o: delta = rowsum(dO o), dS = P (dP z - delta) scale rounded to bf16, dq / dk summed over 64-row tiles,
+    dv from bf16(P z).  q, k, v, dout [B, H, S, D] bf16.  Returns (o, lse, dq, dk, dv)."""
+    B, H, Sq, D = q.shape
+    Sk = k.shape[-2]
+    qf, kf, vf, g = q.float(), k.float(), v.float(), dout.float()
+    Z = _flat_keep(_attn_mask_index(B, H, Sq, Sk), p)
+    Zm = Z
+    if mutant == "stride_rounded_to_64":
+        Zm = _flat_keep(_attn_mask_index(B, H, Sq, Sk, stride=-(-Sk // 64) * 64), p)
+    elif mutant == "head_dropped":
+        Zm = _flat_keep(_attn_mask_index(B, H, Sq, Sk, head=False), p)
+    elif mutant == "transposed":
+        Zm = _flat_keep(_attn_mask_index(B, H, Sk, Sq), p).transpose(-1, -2)
+    elif mutant == "last_key_tile_unmasked":
+        Zm = Z.clone()
+        Zm[..., (Sk - 1) // 64 * 64:] = 1.0
+    elif mutant == "last_query_rows_unmasked":
+        Zm = Z.clone()
+        Zm[..., (Sq - 1) // 64 * 64:, :] = 1.0
+    m = torch.full((B, H, Sq, 1), float("-inf"))
+    lsum = torch.zeros(B, H, Sq, 1)
+    acc = torch.zeros(B, H, Sq, D)
+    accu = torch.zeros(B, H, Sq, D)                            # the undropped output (for the delta mutant)
+    for t0 in range(0, Sk, 64):
+        s = (qf @ kf[..., t0:t0 + 64, :].transpose(-1, -2)) * scale
+        m_new = torch.maximum(m, s.amax(-1, keepdim=True))
+        alpha = torch.exp(m - m_new)
+        e = torch.exp(s - m_new)
+        ez = e * Zm[..., t0:t0 + 64]
+        lsum = lsum * alpha + (ez if mutant == "rowsum_after_mask" else e).sum(-1, keepdim=True)
+        acc = acc * alpha + fb.bf16_round(ez) @ vf[..., t0:t0 + 64, :]
+        accu = accu * alpha + fb.bf16_round(e) @ vf[..., t0:t0 + 64, :]
+        m = m_new
+    o = (acc / lsum).to(BF16)
+    lse = (m + torch.log(lsum))[..., 0]
+    # backward, from the o and lse above
+    Zb = Zm
+    if mutant == "one_element_flipped":                        # where the row's probability is largest: the visible place
+        Zb = Z.clone()
+        j = int(torch.exp((qf[0, 1, 7] @ kf[0, 1].T) * scale - lse[0, 1, 7]).argmax())
+        Zb[0, 1, 7, j] = 0.0 if float(Zb[0, 1, 7, j]) > 0 else float(Z.max())
+    one = torch.ones_like(Z)
+    Zq, Zk, Zv = (one if mutant == f"d{n}_unmasked" else Zb for n in "qkv")
+    P = torch.exp((qf @ kf.transpose(-1, -2)) * scale - lse[..., None])
+    dp = g @ vf.transpose(-1, -2)
+    o_delta = (accu / lsum).to(BF16) if mutant == "delta_from_undropped_o" else o
+    delta = (g * o_delta.float()).sum(-1, keepdim=True)
+    dSq = fb.bf16_round(P * (dp * Zq - delta) * scale)
+    dSk = fb.bf16_round(P * (dp * Zk - delta) * scale)
+    Pv = fb.bf16_round(P * Zv)
+    dq = torch.zeros_like(qf)
+    for t0 in range(0, Sk, 64):
+        dq = dq + dSq[..., t0:t0 + 64] @ kf[..., t0:t0 + 64, :]
+    dk, dv = torch.zeros_like(kf), torch.zeros_like(vf)
+    for t0 in range(0, Sq, 64):
+        dk = dk + dSk[..., t0:t0 + 64, :].transpose(-1, -2) @ qf[..., t0:t0 + 64, :]
+        dv = dv + Pv[..., t0:t0 + 64, :].transpose(-1, -2) @ g[..., t0:t0 + 64, :]
+    return o, lse, dq.to(BF16), dk.to(BF16), dv.to(BF16)
+
+
+def _attn_dropout_case(B, H, Sq, Sk, D, p, mutant=None):
+    q, k, v, dout = (fb.rnd(B, H, S, D, seed=91 + n).to(BF16) for n, S in enumerate((Sq, Sk, Sk, Sq)))
+    scale = D ** -0.5
+    o, lse, dq, dk, dv = emu_attn_dropout(q, k, v, dout, scale, p, mutant)
+    keep = fb.keep_mask_ref(QF_SEED, B * H * Sq, Sk, p).view(B, H, Sq, Sk)
+    r = fb.attn_ref_bound(q, k, v, scale, fb.attn_mask(B, Sq, Sk, False, None, "cpu"), dout=dout, o_in=o, lse_in=lse, keep=keep)
+    got = dict(o=o, lse=lse, dq=dq, dk=dk, dv=dv)
+    ratios, fails = {}, []
+    for nm in got:
+        try:
+            ratios[nm] = fb.assert_within(got[nm], r[nm], r[nm + "_bound"], "attention dropout " + nm)
+        except AssertionError as e:
+            fails.append(str(e))
+    if fails:
+        raise AssertionError(" | ".join(fails))
+    return ratios
+
+
+ATTN_DROP_CPU_CASES = [(2, 3, 33, 65, 64), (2, 3, 81, 257, 64), (1, 2, 65, 65, 88), (2, 3, 1, 31, 128)]
+
+
+@pytest.mark.parametrize("p", [0.1, 0.5])
+@pytest.mark.parametrize("case", ATTN_DROP_CPU_CASES)
+def test_attention_dropout_emulation_is_within_the_bound(case, p):
+    ratios = _attn_dropout_case(*case, p)
+    assert min(ratios.values()) > 1e-3, ratios
+
+
+@pytest.mark.parametrize("mutant", ATTN_DROP_MUTANTS)
+def test_attention_dropout_mutant_fails_the_bound(mutant):
+    with pytest.raises(AssertionError, match="out of bound"):
+        _attn_dropout_case(2, 3, 65, 65, 64, 0.1, mutant)
+
+
+def test_attention_bound_without_a_mask_is_unchanged_and_a_mask_of_ones_adds_only_its_roundings():
+    B, H, Sq, Sk, D = 2, 2, 33, 65, 64
+    q, k, v, dout = (fb.rnd(B, H, S, D, seed=95 + n).to(BF16) for n, S in enumerate((Sq, Sk, Sk, Sq)))
+    mask = fb.attn_mask(B, Sq, Sk, False, None, "cpu")
+    e = 1e-3 * dout.float().abs()
+    r0 = fb.attn_ref_bound(q, k, v, D ** -0.5, mask, dout=dout, dout_err=e)
+    rn = fb.attn_ref_bound(q, k, v, D ** -0.5, mask, dout=dout, dout_err=e, keep=None)
+    r1 = fb.attn_ref_bound(q, k, v, D ** -0.5, mask, dout=dout, dout_err=e, keep=torch.ones(B, H, Sq, Sk))
+    assert set(r0) == set(rn) == set(r1)
+    for nm in r0:
+        assert torch.equal(r0[nm], rn[nm]), nm
+        if nm.endswith("_bound") or nm.endswith("_bound_acc"):
+            assert bool((r1[nm] >= r0[nm]).all()) and bool((r1[nm] <= r0[nm] * (1 + 1e-3)).all()), nm
+        else:
+            assert torch.equal(r0[nm], r1[nm]), nm
+
+
+# ------------------------------------------------------------------------------------ Q-Former training: LayerNorm dropout
+LN_DROP_FWD_MUTANTS = ["mask_on_the_sum", "statistics_of_the_unmasked_x", "mask_before_bias", "seed_in_for_the_output_mask",
+                       "mask_stride_256"]
+LN_DROP_BWD_MUTANTS = ["seed_in_for_the_output_mask", "mask_stride_256", "dx_masked", "dz_unmasked"]
+LN_SEED_IN, LN_SEED_OUT = QF_SEED ^ 0x1111, QF_SEED ^ 0x2222
+
+
+def _ln_masks(M, D, p_in, p_out, mutant=None):
+    idx = torch.arange(M)[:, None] * (256 if mutant == "mask_stride_256" else D) + torch.arange(D)[None]
+    ki = _flat_keep(idx, p_in, LN_SEED_IN)
+    ko = _flat_keep(idx, p_out, LN_SEED_IN if mutant == "seed_in_for_the_output_mask" else LN_SEED_OUT)
+    return ki, ko
+
+
+def emu_ln_dropout_fwd(z, res, w, b, eps, p_in, p_out, mutant=None):
+    """layernorm_fwd_dropout_kernel: thread t of 256 sums elements t, t + 256, ... serially, then block_sum; the statistics from
+    the x it wrote.  Returns (x, y f32, y bf16)."""
+    M, D = z.shape
+    ki, ko = _ln_masks(M, D, p_in, p_out, mutant)
+    x = z
+    if res is not None:
+        x = (z + res) * ki if mutant == "mask_on_the_sum" else z * ki + res
+    xs = z + res if mutant == "statistics_of_the_unmasked_x" else x
+    mean = emu_strided_sum(xs) / D
+    r = torch.rsqrt(emu_strided_sum((xs - mean) * (xs - mean)) / D + eps)
+    if mutant == "mask_before_bias":
+        y = (x - mean) * r * w * ko + b
+    else:
+        y = ((x - mean) * r * w + b) * ko
+    return x, y, y.to(BF16)
+
+
+def emu_ln_dropout_bwd(dy, x, w, eps, p_in, p_out, mutant=None):
+    """layernorm_bwd_dropout_kernel: (dx f32, dz bf16)."""
+    M, D = x.shape
+    ki, ko = _ln_masks(M, D, p_in, p_out, mutant)
+    mean = emu_strided_sum(x) / D
+    d = x - mean
+    r = torch.rsqrt(emu_strided_sum(d * d) / D + eps)
+    g = dy * ko * w
+    sg = emu_strided_sum(g) / D
+    sgx = emu_strided_sum(g * d * r) / D
+    o = r * (g - sg - d * r * sgx)
+    dx = o * ki if mutant == "dx_masked" else o
+    dz = o if mutant == "dz_unmasked" else o * ki
+    return dx, dz.to(BF16)
+
+
+def _ln_dropout_case(M, D, p_in, p_out, with_res=True, mutant=None, which="fwd"):
+    eps = 1e-12
+    res = fb.norm_rows(M, D, seed=101) if with_res else None
+    z = fb.rnd(M, D, seed=102) if with_res else fb.norm_rows(M, D, seed=101)
+    w = fb.norm_weight(D, seed=103) if D >= 8 else 1 + 0.5 * fb.rnd(D, seed=103)
+    b, dy = 0.1 * fb.rnd(D, seed=104), fb.rnd(M, D, seed=105)
+    ki = fb.keep_mask_ref(LN_SEED_IN, M, D, p_in) if with_res else None
+    ko = fb.keep_mask_ref(LN_SEED_OUT, M, D, p_out)
+    ratios = []
+    if which == "fwd":
+        x, yf, yb = emu_ln_dropout_fwd(z, res, w, b, eps, p_in if with_res else 0.0, p_out, mutant)
+        r = fb.ln_dropout_fwd_ref_bound(z, res, w, b, eps, ki, ko, x_out=x)
+        if with_res:
+            ratios.append(fb.assert_within(x, r["x"], r["x_bound"], "ln dropout x"))
+        ratios.append(fb.assert_within(yf, r["y"], r["y_bound"], "ln dropout y f32"))
+        ratios.append(fb.assert_within(yb, r["y"], r["y_bf16_bound"], "ln dropout y bf16"))
+    else:
+        x = z * ki + res if with_res else z
+        dx, dz = emu_ln_dropout_bwd(dy, x, w, eps, p_in if with_res else 0.0, p_out, mutant)
+        r = fb.ln_dropout_bwd_ref_bound(dy, x, w, eps, ki, ko)
+        fails = []
+        for nm, got in (("dx", dx), ("dz", dz)):
+            try:
+                ratios.append(fb.assert_within(got, r[nm], r[nm + "_bound"], "ln dropout " + nm))
+            except AssertionError as e:
+                fails.append(str(e))
+        if fails:
+            raise AssertionError(" | ".join(fails))
+    return ratios
+
+
+@pytest.mark.parametrize("M,D,p_in,p_out,with_res", [(13, 300, 0.1, 0.25, True), (13, 768, 0.1, 0.0, True), (7, 257, 0.0, 0.1, False),
+                                                     (13, 8, 0.5, 0.5, True), (1, 1030, 0.0, 0.0, True)])
+def test_layernorm_dropout_emulation_is_within_the_bound(M, D, p_in, p_out, with_res):
+    ratios = _ln_dropout_case(M, D, p_in, p_out, with_res, None, "fwd") + _ln_dropout_case(M, D, p_in, p_out, with_res, None, "bwd")
+    assert min(ratios) > 1e-3, ratios
+
+
+@pytest.mark.parametrize("mutant", LN_DROP_FWD_MUTANTS)
+def test_layernorm_dropout_forward_mutant_fails(mutant):
+    with pytest.raises(AssertionError, match="out of bound"):
+        _ln_dropout_case(13, 300, 0.1, 0.25, True, mutant, "fwd")
+
+
+@pytest.mark.parametrize("mutant", LN_DROP_BWD_MUTANTS)
+def test_layernorm_dropout_backward_mutant_fails(mutant):
+    with pytest.raises(AssertionError, match="out of bound"):
+        _ln_dropout_case(13, 300, 0.1, 0.25, True, mutant, "bwd")
+
+
+# ------------------------------------------------------------------------------------- Q-Former training: TN weight gradient
+TN_MUTANTS = ["rows_past_M_counted", "split_boundary_row_twice", "empty_split_unwritten", "bias_by_every_k_tile", "accumulate_overwrites"]
+
+
+def emu_tn_wgrad(dyp, xp, M, splits, prev=None, prev_bias=None, mutant=None):
+    """gemm_tn_wgrad_kernel + tn_split_reduce_kernel: split z covers rows [z rows_per, min(M, (z + 1) rows_per)), one 32-row
+    product added per step in fp32; a staging thread adds its dy values over the steps, the 32 staging rows are added in order;
+    the splits' partials (poisoned workspace) are added in split order.  dyp / xp: the parent buffers, whose rows past M hold
+    +-1e4.  Returns (dW, db)."""
+    N, K = dyp.shape[1], xp.shape[1]
+    rows_per = fb.tn_rows_per(M, splits)
+    ws, wsb = fb.poisoned((splits, N, K), F32, "cpu"), fb.poisoned((splits, N), F32, "cpu")
+    for z in range(splits):
+        m0 = z * rows_per
+        m1 = min(M, m0 + rows_per)
+        if mutant == "empty_split_unwritten" and m0 >= m1:
+            continue
+        if mutant == "split_boundary_row_twice":               # the split's end row belongs to the next split as well
+            m1 = min(M, m1 + 1)
+        acc, stage = torch.zeros(N, K), torch.zeros(fb.TN_BM, N)
+        for mb in range(m0, m1, fb.TN_BM):
+            hi = mb + fb.TN_BM if mutant == "rows_past_M_counted" else min(m1, mb + fb.TN_BM)
+            acc = acc + dyp[mb:hi].float().T @ xp[mb:hi].float()
+            stage[:hi - mb] = stage[:hi - mb] + dyp[mb:hi].float()
+        bs = torch.zeros(N)
+        for rr in range(fb.TN_BM):
+            bs = bs + stage[rr]
+        ws[z], wsb[z] = acc, bs * (K // 64 if mutant == "bias_by_every_k_tile" else 1)
+    dW, db = ws[0], wsb[0]
+    for z in range(1, splits):
+        dW, db = dW + ws[z], db + wsb[z]
+    if prev is not None and mutant != "accumulate_overwrites":
+        dW, db = prev + dW, prev_bias + db
+    return dW, db
+
+
+def _tn_case(M, N, K, splits, accumulate, mutant=None):
+    dyp = fb.lora_rows(M + 40, N, seed=111).to(BF16)
+    xp = fb.rnd(M + 40, K, seed=112).to(BF16)
+    dyp[M:], xp[M:] = 1e4, -1e4
+    prev, prev_bias = (fb.rnd(N, K, seed=113), fb.rnd(N, seed=114)) if accumulate else (None, None)
+    dW, db = emu_tn_wgrad(dyp, xp, M, splits, prev, prev_bias, mutant)
+    rW, eW, rb, eb = fb.tn_wgrad_ref_bound(dyp[:M], xp[:M], splits, prev, prev_bias)
+    fails, ratios = [], []
+    for nm, got, ref, bnd in (("dW", dW, rW, eW), ("db", db, rb, eb)):
+        try:
+            ratios.append(fb.assert_within(got, ref, bnd, "tn_wgrad " + nm))
+        except AssertionError as e:
+            fails.append(str(e))
+    if fails:
+        raise AssertionError(" | ".join(fails))
+    return ratios
+
+
+@pytest.mark.parametrize("M,N,K,splits,accumulate", [(40, 64, 128, 3, True), (33, 128, 64, 8, False), (257, 64, 64, 2, False),
+                                                     (1, 64, 64, 1, True), (31, 64, 192, 1, False)])
+def test_tn_wgrad_emulation_is_within_the_bound(M, N, K, splits, accumulate):
+    ratios = _tn_case(M, N, K, splits, accumulate)
+    assert min(ratios) > 1e-3, ratios
+
+
+@pytest.mark.parametrize("mutant", TN_MUTANTS)
+def test_tn_wgrad_mutant_fails(mutant):
+    with pytest.raises(AssertionError, match="out of bound"):
+        _tn_case(40, 64, 128, 3, True, mutant)
+
+
+def test_layernorm_dropout_generator_keeps_every_row_well_defined():
+    """The condition on the GPU module's inputs: with the residual and the masks applied (forms b - d) no row's variance is lost
+    to the mean's rounding unless the row is constant -- layernorm_ref_bound raises otherwise -- at every shape used there."""
+    for M in (13, 1):
+        for D in (1, 8, 255, 256, 257, 768, 1030):
+            for form in "abcd":
+                z, res, w, b, dy, p_in, p_out = fb.ln_dropout_inputs(M, D, form, seed=700 + D)
+                ki, ko = fb.keep_mask_ref(0x1234567811111111, M, D, p_in), fb.keep_mask_ref(0x7ABCDEF022222222, M, D, p_out)
+                x = z if res is None else z * ki + res
+                fb.ln_dropout_fwd_ref_bound(z, res, w, b, 1e-12, ki, ko, x_out=x)
+                fb.ln_dropout_bwd_ref_bound(dy, x, w, 1e-12, ki, ko)
