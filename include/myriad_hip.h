@@ -609,6 +609,32 @@ int mh_adamw_gated(float* p, const float* g, float* m, float* v, long n, double 
                    double weight_decay, double grad_scale, const float* used, const int* steps, mh_stream_t s);
 int mh_adamw_bump(const float* used, int* steps, int n, mh_stream_t s);
 
+/* Global gradient-norm clipping (torch.nn.utils.clip_grad_norm_, norm_type 2) and the non-finite step guard (the step
+   torch.cuda.amp.GradScaler skips), decided on the device through a control block `double ctl[4]`:
+     ctl[0] = s      the ONE multiplier the AdamW applies to the raw gradient, fp32-representable:
+                     (float)(grad_scale * min(1, max_norm / (grad_scale * sqrt(sumsq) + 1e-6))), computed in double, rounded once;
+                     (float)grad_scale with max_norm = +inf (no clipping)
+     ctl[1] = norm   grad_scale * sqrt(sumsq): the total norm of the scaled gradient, in double (it cannot overflow)
+     ctl[2] = apply  0 when `guard` is set and sumsq is not finite, else 1
+     ctl[3] = skipped  running count of updates not applied (the caller zeroes it once)
+   mh_grad_sumsq: sum of squares of g[0..n) in fp64 (products exact, no overflow: the sum is finite iff every element is),
+   one partial per workgroup into partials[0 .. mh_grad_sumsq_slots(n)), `slots` = the room there; nothing is read and zeros
+   are written when *used <= 0 (the module had no gradient).  Deterministic: same input, same bits.
+   mh_clip_finalize: sumsq = the partials added in index order (thread t its contiguous chunk, then the chunks in order) plus
+   rank_sums[0..world) in rank order (NULL, 0: none), then writes ctl.  mh_clip_rank_sum: the sharded data-parallel half step --
+   rank_sums[rank] = the partials' sum, the other slots 0, for a sum all-reduce that is exact.
+   mh_adamw_gated_ctl / mh_adamw_bump_ctl: mh_adamw_gated / mh_adamw_bump that return at once when ctl[2] == 0 and multiply
+   the gradient by (float)ctl[0] (in place of grad_scale).  All refuse n % 4, null pointers, max_norm <= 0 and slots too small
+   with MH_ERR_ARG before any launch. */
+long mh_grad_sumsq_slots(long n);
+int mh_grad_sumsq(const float* g, long n, const float* used, double* partials, long slots, mh_stream_t s);
+int mh_clip_rank_sum(const double* partials, long n_partials, double* rank_sums, int world, int rank, mh_stream_t s);
+int mh_clip_finalize(const double* partials, long n_partials, const double* rank_sums, int world, double max_norm,
+                     double grad_scale, int guard, double* ctl, mh_stream_t s);
+int mh_adamw_gated_ctl(float* p, const float* g, float* m, float* v, long n, double lr, double beta1, double beta2, double eps,
+                       double weight_decay, const float* used, const int* steps, const double* ctl, mh_stream_t s);
+int mh_adamw_bump_ctl(const float* used, int* steps, int n, const double* ctl, mh_stream_t s);
+
 /* K16 anomaly-map heads of the vision expert (adrefexpert_v2.py:243-301).  All f32.
  * l2norm_rows: y = x / max(||x||, eps) (bf16 and/or f32 out) -- operands of the cosine similarities (:259, :283);
  * pair_logits: out[row] = scale * [<p,t0>, <p,t1>] / ||p|| against the per-sample [normal, abnormal] text pair (:283-284);

@@ -71,6 +71,51 @@ def accum_update_due(calls_since_update: int, accum_grad_iters: int, accum_index
     return calls_since_update >= n
 
 
+def update_pieces(ranges, shard=None, exclude=(), skip_idx=()):
+    """The slices of the flat buffers one optimiser update touches, in launch order: [(module index, lo, hi, weight decay?)] --
+    every module range of `ranges`, minus the modules `skip_idx`, cut to the slices `shard` (None: everything) and with the
+    spans `exclude` taken out.  ParamStore.adamw_step walks exactly this list, and norms exactly this list when it clips."""
+    out = []
+    for mi, a0, b0, decays in ranges:
+        if mi in skip_idx:
+            continue
+        for lo, hi in (shard if shard is not None else [(a0, b0)]):
+            a, b = max(a0, lo), min(b0, hi)
+            if a >= b:
+                continue
+            todo = [(a, b)]
+            for ex_lo, ex_hi in exclude:                      # spans adamw_pieces() already updated this step
+                todo = [q for (x, y) in todo for q in ((x, min(y, ex_lo)), (max(x, ex_hi), y)) if q[0] < q[1]]
+            out.extend((mi, a, b, decays) for a, b in todo)
+    return out
+
+
+class GradClip:
+    """What ParamStore.adamw_step(clip=...) needs to clip and / or guard one update.  max_norm: clip_grad_norm_'s threshold on
+    the total 2-norm of the averaged gradient (None: no clipping); skip_nonfinite: leave parameters, moments and step counts
+    alone when the gradient holds an inf or a NaN; rank_sums = (rank, world, all_reduce): sharded data parallel ('rs_ag'), where
+    this rank norms only the slices it owns -- all_reduce(vector) sums the world-long fp64 vector of per-rank sums in place."""
+
+    def __init__(self, max_norm=None, skip_nonfinite: bool = False, rank_sums=None):
+        if max_norm is not None and not float(max_norm) > 0.0:
+            raise ValueError(f"GradClip(max_norm={max_norm!r}): a positive threshold, or None for no clipping")
+        self.max_norm = None if max_norm is None else float(max_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.rank_sums = rank_sums
+
+    @classmethod
+    def of(cls, max_grad_norm=None, skip_nonfinite: bool = False):
+        """train_step's two options -> a GradClip, or None when both are off (max_grad_norm None or <= 0 is off)."""
+        mg = None if (max_grad_norm is None or not float(max_grad_norm) > 0.0) else float(max_grad_norm)
+        return cls(mg, skip_nonfinite) if (mg is not None or skip_nonfinite) else None
+
+    def for_dp(self, dp):
+        """The same options for an update behind `dp`'s exchange: in 'rs_ag' with the per-rank sums travelling through it."""
+        if dp is None or dp.world == 1 or getattr(dp, "mode", "allreduce") != "rs_ag":
+            return self
+        return GradClip(self.max_norm, self.skip_nonfinite, (dp.rank, dp.world, dp.allreduce_sums))
+
+
 class ParamStore:
     """All trainable parameters in ONE flat fp32 buffer (+ grad, Adam m, v): a single RCCL all-reduce and a handful of
     fused AdamW launches per step.  Layout: [weight-decay group | no-decay group | per-module use flags]; inside each
@@ -130,6 +175,11 @@ class ParamStore:
             self.p[name] = self.flat_p[o:o + n].view(ishape)
             self.g[name] = self.flat_g[o:o + n].view(ishape)
             self.ref_shape[name] = rshape
+        # gradient clipping / non-finite guard (adamw_step(clip=...)): the device control block [s, norm, apply, skipped] and
+        # the fp64 partial-sum workspace of the norm, allocated on first use and then kept
+        self.ctl = None
+        self._norm_ws = None
+        self._rank_sums = None
         self.step = 0                                             # optimiser calls so far (host)
         self.version = 0                                          # bumped by every update / load of flat_p (decode sessions)
 
@@ -187,12 +237,14 @@ class ParamStore:
                                     grad_scale=grad_scale)
 
     def adamw_step(self, lr: float, weight_decay: float = 0.05, beta2: float = 0.999, grad_scale: float = 1.0, shard=None,
-                   skip=(), exclude=()):
+                   skip=(), exclude=(), clip=None):
         """torch.optim.AdamW semantics (runner_base.py:132-137), fused, on the flat buffers; modules unused on every rank
         this step are left alone (see class docstring).  `shard` = (lo, hi) or a list of such: update only those slices of the
         flat buffer (DataParallel mode 'rs_ag': each rank owns 1/world of every exchange segment's optimiser state).  `exclude`:
         spans adamw_pieces() already updated this step.  `skip`: modules adamw_module() already
-        updated this step."""
+        updated this step.  `clip` (a GradClip): the 2-norm of grad_scale * gradient over exactly the elements about to be
+        updated is taken first, on the device (_prepare_clip), and the update runs under its verdict: scaled by
+        min(1, max_norm / (norm + 1e-6)), or not at all when the guard finds a non-finite element."""
         self.step += 1
         self.version += 1
         pieces = None
@@ -201,22 +253,54 @@ class ParamStore:
             if sum(hi - lo for lo, hi in pieces) < self.total:
                 self.moments_complete = False                     # DataParallel.gather_state() restores it
         skip_idx = {self.modules.index(m) for m in skip if m in self.modules}
-        for mi, a0, b0, decays in self.ranges:
-            if mi in skip_idx:
-                continue
-            for lo, hi in (pieces if pieces is not None else [(a0, b0)]):
-                a, b = max(a0, lo), min(b0, hi)
-                if a >= b:
-                    continue
-                todo = [(a, b)]
-                for ex_lo, ex_hi in exclude:                      # spans adamw_pieces() already updated this step
-                    todo = [q for (x, y) in todo for q in ((x, min(y, ex_lo)), (max(x, ex_hi), y)) if q[0] < q[1]]
-                for a, b in todo:
-                    ops.adamw_gated(self.flat_p[a:b], self.flat_g[a:b], self.flat_m[a:b], self.flat_v[a:b], lr,
-                                    weight_decay if decays else 0.0, self.used[mi:mi + 1], self.steps_dev[mi:mi + 1], beta2=beta2,
-                                    grad_scale=grad_scale)
+        todo = update_pieces(self.ranges, pieces, exclude, skip_idx)
+        if clip is not None:
+            self._prepare_clip(todo, grad_scale, clip)
+        for mi, a, b, decays in todo:
+            if clip is None:
+                ops.adamw_gated(self.flat_p[a:b], self.flat_g[a:b], self.flat_m[a:b], self.flat_v[a:b], lr,
+                                weight_decay if decays else 0.0, self.used[mi:mi + 1], self.steps_dev[mi:mi + 1], beta2=beta2,
+                                grad_scale=grad_scale)
+            else:
+                ops.adamw_gated_ctl(self.flat_p[a:b], self.flat_g[a:b], self.flat_m[a:b], self.flat_v[a:b], lr,
+                                    weight_decay if decays else 0.0, self.used[mi:mi + 1], self.steps_dev[mi:mi + 1], self.ctl,
+                                    beta2=beta2)
         if self.modules:
-            ops.adamw_bump(self.used, self.steps_dev)
+            if clip is None:
+                ops.adamw_bump(self.used, self.steps_dev)
+            else:
+                ops.adamw_bump_ctl(self.used, self.steps_dev, self.ctl)
+
+    def _prepare_clip(self, todo, grad_scale: float, clip) -> None:
+        """Fill the control block for the update of the pieces `todo`: one sum-of-squares launch per piece (gated by its
+        module's use flag, like the update), then the one-workgroup finalise.  Sharded ('rs_ag'): this rank's sum goes into
+        its slot of a world-long vector, one small sum all-reduce, and every rank finalises from the same slots in rank order."""
+        if self.ctl is None:
+            self.ctl = torch.zeros(4, dtype=torch.float64, device=self.dev)
+        need = sum(ops.grad_sumsq_slots(b - a) for _, a, b, _ in todo)
+        if self._norm_ws is None or self._norm_ws.numel() < need:
+            # every module range whole is the usual case; shards and excluded spans cut ranges into more, shorter pieces
+            whole = sum(ops.grad_sumsq_slots(b - a) for _, a, b, _ in self.ranges)
+            self._norm_ws = torch.zeros(max(need, whole) + 64, dtype=torch.float64, device=self.dev)
+        ws, off = self._norm_ws, 0
+        for mi, a, b, _ in todo:
+            off += ops.grad_sumsq(self.flat_g[a:b], self.used[mi:mi + 1], ws[off:])
+        if clip.rank_sums is None:
+            ops.clip_finalize(ws, off, None, clip.max_norm, grad_scale, clip.skip_nonfinite, self.ctl)
+            return
+        rank, world, all_reduce = clip.rank_sums
+        if self._rank_sums is None or self._rank_sums.numel() != world:
+            self._rank_sums = torch.zeros(world, dtype=torch.float64, device=self.dev)
+        ops.clip_rank_sum(ws, off, self._rank_sums, rank)
+        all_reduce(self._rank_sums)
+        ops.clip_finalize(ws, 0, self._rank_sums, clip.max_norm, grad_scale, clip.skip_nonfinite, self.ctl)
+
+    def grad_stats(self) -> dict:
+        """The last clipped / guarded update's verdict (one small device -> host copy: logging only)."""
+        if self.ctl is None:
+            return {"grad_norm": None, "clip_scale": None, "applied": True, "skipped_steps": 0}
+        s, norm, apply, skipped = self.ctl.cpu().tolist()
+        return {"grad_norm": norm, "clip_scale": s, "applied": apply != 0.0, "skipped_steps": int(skipped)}
 
 
 def init_trainable(name: str, rshape) -> torch.Tensor:
@@ -1048,7 +1132,8 @@ class MyriadHIP(nn.Module):
         return out
 
     def train_step(self, samples, lr: float, weight_decay: float = 0.05, allreduce=None, world: int = 1, dp=None,
-                   overlap: bool = True, next_samples=None, accum_grad_iters: int = 1, accum_index=None, beta2: float = 0.999):
+                   overlap: bool = True, next_samples=None, accum_grad_iters: int = 1, accum_index=None, beta2: float = 0.999,
+                   max_grad_norm=None, skip_nonfinite: bool = False):
         """forward + backward (+ gradient all-reduce) + fused AdamW: one optimisation step of
         `BaseTask._train_inner_loop` (base_task.py:233-271) without the autograd bridge.
         With a `DataParallel` (`dp`) and overlap=True the all-reduce + AdamW of step t are hidden behind the frozen
@@ -1064,7 +1149,15 @@ class MyriadHIP(nn.Module):
         puts it, `(i + 1) % accum_grad_iters == 0` with i restarting every epoch (base_task.py:265), so when iters_per_epoch is
         not a multiple of accum_grad_iters the left-over gradients of an epoch's tail are folded into the next epoch's first
         update, as the reference's un-zeroed .grad does.  Without it the window is counted in calls.
-        `beta2`: AdamW's second-moment decay (run.beta2, runner_base.py:130-135); beta1 is 0.9 as in the reference."""
+        `beta2`: AdamW's second-moment decay (run.beta2, runner_base.py:130-135); beta1 is 0.9 as in the reference.
+        `max_grad_norm` (None or <= 0: off): torch.nn.utils.clip_grad_norm_ on the whole trainable gradient of the update -- the
+        rank average, and an accumulation window's sum, which is where the reference's loop would clip.  `skip_nonfinite`: an
+        update whose gradient holds an inf or a NaN is not applied at all (what GradScaler.step did under fp16 AMP): parameters,
+        moments and step counts keep their bits.  Both are decided on the device (ParamStore.adamw_step(clip=...)); grad_stats()
+        reads the verdict back for logging.  While either is on nothing is updated before the norm of the WHOLE gradient is
+        known: the early tokenizer update and the update behind the early exchange fall back to their late forms (the early
+        collective itself stays).  With both off the step issues exactly the launches it issued without them."""
+        clip = GradClip.of(max_grad_norm, skip_nonfinite)
         with torch.no_grad():
             vit_out = self._take_prefetched_vit(samples)
             if next_samples is not None:
@@ -1098,7 +1191,8 @@ class MyriadHIP(nn.Module):
             # no gradient exchange, no accumulation window: modules whose gradient is complete early are updated early (backward())
             # (world == 1 as well: a caller-scaled update -- `world` > 1 without dp / allreduce -- must see ONE grad_scale)
             early = (lr, weight_decay, beta2) if (due and not accumulate and (dp is None or dp.world == 1) and allreduce is None
-                                                  and world == 1 and os.environ.get("MYRIAD_EARLY_ADAMW", "1") != "0") else None
+                                                  and world == 1 and clip is None
+                                                  and os.environ.get("MYRIAD_EARLY_ADAMW", "1") != "0") else None
             if dp is not None and dp.world > 1 and self.arch == "myriad" and hasattr(dp, "set_segments"):
                 # the exchange's segmentation -- in 'rs_ag' the slices of the Adam moments each rank owns -- is fixed before the
                 # first exchange, whether or not this step overlaps it: every step then shards the optimiser state the same way
@@ -1110,7 +1204,8 @@ class MyriadHIP(nn.Module):
                     and hasattr(dp, "start_part") and os.environ.get("MYRIAD_DP_EARLY", "1") != "0"):
                 k = self._dp_segment(dp)
                 if k is not None:
-                    early_x = (dp, k, (lr, weight_decay, beta2)) if os.environ.get("MYRIAD_DP_EARLY_ADAMW", "1") != "0" else (dp, k)
+                    early_upd = clip is None and os.environ.get("MYRIAD_DP_EARLY_ADAMW", "1") != "0"
+                    early_x = (dp, k, (lr, weight_decay, beta2)) if early_upd else (dp, k)
             self.backward(accumulate=accumulate, early_adamw=early, early_exchange=early_x)
             self._accum_count += 1
             if not due:
@@ -1118,7 +1213,7 @@ class MyriadHIP(nn.Module):
             self._accum_count = 0
             if dp is not None and dp.world > 1 and overlap:
                 dp.start(self.store.flat_g_comm, self.store.total)   # RCCL exchange on the side HIP stream (grads + use flags)
-                self._pending_update = (dp, lr, weight_decay, beta2)
+                self._pending_update = (dp, lr, weight_decay, beta2, clip)
             else:
                 shard = None
                 if dp is not None and dp.world > 1:
@@ -1128,7 +1223,7 @@ class MyriadHIP(nn.Module):
                     allreduce(self.store.flat_g_comm)
                     world = max(world, 1)
                 self.store.adamw_step(lr, weight_decay, beta2=beta2, grad_scale=1.0 / (dp.world if dp is not None else world),
-                                      shard=shard, skip=self._early_done)
+                                      shard=shard, skip=self._early_done, clip=clip.for_dp(dp) if clip is not None else None)
                 if shard is not None:
                     dp.gather_params(self.store.flat_p)
         return loss
@@ -1160,18 +1255,26 @@ class MyriadHIP(nn.Module):
     def finish_update(self):
         """Apply a delayed optimiser update (overlap mode): wait for the gradient exchange, if any, then fused AdamW."""
         if self._pending_update is not None:
-            dp, lr, wd, beta2 = self._pending_update
+            dp, lr, wd, beta2, clip = self._pending_update
             self._pending_update = None
             if dp is None:
-                self.store.adamw_step(lr, wd, beta2=beta2)
+                self.store.adamw_step(lr, wd, beta2=beta2, clip=clip)
                 return
             dp.wait()
             shard = self._dp_shards(dp)
             done = dp.take_early_done() if hasattr(dp, "take_early_done") else set()      # segments updated behind their collective
             segs = dp.segments(self.store.total) if done else []
-            self.store.adamw_step(lr, wd, beta2=beta2, grad_scale=1.0 / dp.world, shard=shard, exclude=[segs[k] for k in done])
+            self.store.adamw_step(lr, wd, beta2=beta2, grad_scale=1.0 / dp.world, shard=shard, exclude=[segs[k] for k in done],
+                                  clip=clip.for_dp(dp) if clip is not None else None)
             if shard is not None:
                 dp.gather_params(self.store.flat_p, skip=done) if done else dp.gather_params(self.store.flat_p)
+
+    def grad_stats(self) -> dict:
+        """{"grad_norm", "clip_scale", "applied", "skipped_steps"} of the last update run with max_grad_norm / skip_nonfinite:
+        the total norm of the averaged gradient before clipping, the one multiplier the AdamW applied to the raw gradient
+        (grad_scale included), whether the update was applied, and how many were not so far.  One small device -> host copy,
+        for logging; the training path never calls it."""
+        return self.store.grad_stats()
 
     def _generate_args(self, generate_kwargs) -> dict:
         """generate()'s keyword arguments, checked and with their defaults (its docstring states the contract)."""

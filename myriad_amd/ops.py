@@ -1425,6 +1425,44 @@ def adamw_bump(used: torch.Tensor, steps: torch.Tensor):
     _lib.check(_L().mh_adamw_bump(_p(used), _p(steps), steps.numel(), _s()), "mh_adamw_bump")
 
 
+# ---- gradient-norm clipping / non-finite guard: the control block `ctl` (4 doubles: s, norm, apply, skipped) lives on the device
+def grad_sumsq_slots(n: int) -> int:
+    """fp64 workspace slots grad_sumsq writes for a range of n elements (one per workgroup)."""
+    return int(_L().mh_grad_sumsq_slots(int(n)))
+
+
+def grad_sumsq(g: torch.Tensor, used: torch.Tensor, partials: torch.Tensor) -> int:
+    """fp64 sum of squares of the contiguous f32 range g, per workgroup, into the head of `partials` (f64); zeros when the
+    device scalar `used` <= 0.  -> the number of slots written."""
+    _lib.check(_L().mh_grad_sumsq(_p(g), g.numel(), _p(used), _p(partials), partials.numel(), _s()), "mh_grad_sumsq")
+    return grad_sumsq_slots(g.numel())
+
+
+def clip_rank_sum(partials: torch.Tensor, n_partials: int, rank_sums: torch.Tensor, rank: int):
+    _lib.check(_L().mh_clip_rank_sum(_p(partials), int(n_partials), _p(rank_sums), rank_sums.numel(), int(rank), _s()),
+               "mh_clip_rank_sum")
+
+
+def clip_finalize(partials: torch.Tensor, n_partials: int, rank_sums: Optional[torch.Tensor], max_norm: Optional[float],
+                  grad_scale: float, guard: bool, ctl: torch.Tensor):
+    """Write ctl from the partials (and the per-rank sums).  max_norm None: no clipping, s = (float)grad_scale."""
+    if n_partials > partials.numel() or ctl.numel() < 4 or ctl.dtype != torch.float64 or partials.dtype != torch.float64:
+        raise _lib.MyriadHipError("clip_finalize: f64 partials / ctl[4] expected")
+    _lib.check(_L().mh_clip_finalize(_p(partials), int(n_partials), _p(rank_sums), 0 if rank_sums is None else rank_sums.numel(),
+                                     float("inf") if max_norm is None else float(max_norm), float(grad_scale), int(bool(guard)),
+                                     _p(ctl), _s()), "mh_clip_finalize")
+
+
+def adamw_gated_ctl(p, g, m, v, lr, wd, used: torch.Tensor, steps: torch.Tensor, ctl: torch.Tensor, beta1=0.9, beta2=0.999, eps=1e-8):
+    """adamw_gated under the control block: nothing when ctl[2] == 0, else the gradient times (float)ctl[0]."""
+    _lib.check(_L().mh_adamw_gated_ctl(_p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(beta1), float(beta2), float(eps),
+                                       float(wd), _p(used), _p(steps), _p(ctl), _s()), "mh_adamw_gated_ctl")
+
+
+def adamw_bump_ctl(used: torch.Tensor, steps: torch.Tensor, ctl: torch.Tensor):
+    _lib.check(_L().mh_adamw_bump_ctl(_p(used), _p(steps), steps.numel(), _p(ctl), _s()), "mh_adamw_bump_ctl")
+
+
 # --------------------------------------------------------------------------- vision-expert map heads (K16)
 def l2norm_rows(x: torch.Tensor, want_bf16: bool = True, want_f32: bool = False, eps: float = 1e-12):
     """y = x / max(||x||, eps) row-wise; x [M, D] f32 (row stride free)."""

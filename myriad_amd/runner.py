@@ -454,6 +454,26 @@ class DataParallel:
         self.start(flat_grad, n_grad)
         self.wait()
 
+    def allreduce_sums(self, vec: torch.Tensor) -> None:
+        """Sum over ranks, in place, of the world-long fp64 vector that holds this rank's gradient sum of squares in slot `rank`
+        and zeros elsewhere (gradient clipping in 'rs_ag', ParamStore._prepare_clip): afterwards every rank holds every rank's
+        value, exactly -- a sum against zeros rounds nothing.  It travels like the use-flag tail: through torch.distributed on
+        gloo / MYRIAD_DP_COLLECTIVE=torch, through the context otherwise -- whose verbs carry f32 and bf16 only, so there the
+        eight bytes of the own slot are all-gathered as two f32 words, which moves the same bits into the same slots without
+        any arithmetic.  Queued behind the exchange on its side stream; the current stream waits for it."""
+        if self.world == 1:
+            return
+        assert vec.dtype == torch.float64 and vec.numel() == self.world
+        if self.ctx is not None:
+            mine = self._persistent("sums_mine", 1, vec.dtype, vec.device)
+            mine.copy_(vec[self.rank:self.rank + 1])              # a copy: input and output may not alias
+            self.ctx.all_gather(mine.view(torch.float32), vec.view(torch.float32))
+            self.ctx.wait()
+            return
+        self._run(lambda: self.dist.all_reduce(vec, op=self.dist.ReduceOp.SUM))
+        if self.side is not None:
+            torch.cuda.current_stream().wait_stream(self.side)
+
     def _gather_segment(self, flat_p: torch.Tensor, k: int, wait: bool = True) -> bool:
         """All-gather of one segment's parameters in place.  -> True when a context verb was queued and nobody waited for it."""
         s_lo, s_hi = self.segments(flat_p.numel())[k]
@@ -536,11 +556,21 @@ def init_distributed(backend: Optional[str] = None):
     return rank, world, local
 
 
+def grad_clip_options(run) -> tuple:
+    """(max_grad_norm, skip_nonfinite) from a run config: `max_grad_norm` (float; absent, 0 or negative = off -> None) and
+    `skip_nonfinite_grad` (bool, default False) -- MyriadHIP.train_step's two arguments."""
+    mg = run.get("max_grad_norm", None)
+    mg = None if mg is None else float(mg)
+    return (mg if (mg is not None and mg > 0.0) else None), bool(run.get("skip_nonfinite_grad", False))
+
+
 def train_loop(model, data_iter: Callable[[], dict], n_steps: int, scheduler: LinearWarmupCosineLRScheduler,
                weight_decay: float = 0.05, dp: Optional[DataParallel] = None, epoch: int = 0,
-               log: Optional[Callable[[int, float, float], None]] = None, lookahead: bool = True):
+               log: Optional[Callable[[int, float, float], None]] = None, lookahead: bool = True,
+               max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
     """`BaseTask._train_inner_loop` for the HIP model: lr is stepped BEFORE the forward with (epoch, i)
-    (base_task.py:229), then forward/backward/all-reduce/AdamW."""
+    (base_task.py:229), then forward/backward/all-reduce/AdamW.  max_grad_norm / skip_nonfinite: see MyriadHIP.train_step."""
+    clip_kw = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite) if (max_grad_norm or skip_nonfinite) else {}
     world = dp.world if dp is not None else 1
     losses = []
     samples = data_iter() if n_steps > 0 else None
@@ -548,7 +578,7 @@ def train_loop(model, data_iter: Callable[[], dict], n_steps: int, scheduler: Li
         lr = scheduler.step(cur_epoch=epoch, cur_step=i)
         nxt = data_iter() if (i + 1 < n_steps and lookahead) else None     # one batch ahead: its frozen ViT forward is
         loss = model.train_step(samples, lr, weight_decay, dp=(dp if dp and world > 1 else None), world=world,
-                                next_samples=nxt)                           # issued beside this step (side stream)
+                                next_samples=nxt, **clip_kw)                # issued beside this step (side stream)
         losses.append(loss)
         if log is not None:
             log(i, float(loss), lr)      # device->host sync per step like metric_logger.update(loss.item())
@@ -621,6 +651,9 @@ class RunnerBase:
         self.evaluate_only = bool(run.get("evaluate", False))
         self.accum_grad_iters = max(int(run.get("accum_grad_iters", 1)), 1)      # base_task.py:262-271: step every n-th iteration
         self.beta2 = float(run.get("beta2", 0.999))                              # runner_base.py:130-135: AdamW betas (0.9, beta2)
+        # run.max_grad_norm / run.skip_nonfinite_grad: global-norm clipping and the skipped non-finite step (GradScaler's, which
+        # the reference got from fp16 AMP: base_task.py:256-268), both decided on the device; off unless configured
+        self.max_grad_norm, self.skip_nonfinite_grad = grad_clip_options(run)
         out_root = run.get("output_dir", "output")
         self.output_dir = os.path.join(out_root, job_id)
         if self.rank == 0:
@@ -691,6 +724,8 @@ class RunnerBase:
         iters = int(run.get("iters_per_epoch", len(loader)))
         wd = float(run.get("weight_decay", 0.05))
         meters = {"lr": SmoothedValue(), "loss": SmoothedValue()}
+        clip_on = self.max_grad_norm is not None or self.skip_nonfinite_grad
+        clip_kw = dict(max_grad_norm=self.max_grad_norm, skip_nonfinite=self.skip_nonfinite_grad) if clip_on else {}
         pending = []
         samples = next(loader) if iters > 0 else None
         for i in range(iters):
@@ -698,22 +733,34 @@ class RunnerBase:
             lr = sched.step(cur_epoch=epoch, cur_step=i)                                    # stepped BEFORE the forward (:229)
             nxt = next(loader) if i + 1 < iters else None                                   # one batch of lookahead: its frozen
             loss = model.train_step(samples, lr, wd, dp=self.dp, next_samples=nxt,          # ViT forward runs on a side stream
-                                    accum_grad_iters=self.accum_grad_iters, accum_index=i, beta2=self.beta2)
+                                    accum_grad_iters=self.accum_grad_iters, accum_index=i, beta2=self.beta2, **clip_kw)
             pending.append(loss)                          # the reference reads loss.item() every step (:276), which stalls the
             meters["lr"].update(lr)                       # launch thread behind the GPU; here the values are fetched at log points
             if i % self.log_freq == 0 or i == iters - 1:
                 for t in pending:
                     meters["loss"].update(float(t))
                 pending.clear()
+                extra = ""
+                if clip_on:                               # the last applied / skipped update's verdict (a delayed one: the step before)
+                    gstats = model.grad_stats()
+                    if gstats["grad_norm"] is not None:
+                        extra = f"  grad_norm: {gstats['grad_norm']:.4g}  skipped_steps: {gstats['skipped_steps']}"
                 if self.rank == 0:
-                    print(f"Train: data epoch: [{epoch}]  [{i}/{iters}]  lr: {lr:.6f}  loss: {meters['loss'].value:.4f}", flush=True)
+                    print(f"Train: data epoch: [{epoch}]  [{i}/{iters}]  lr: {lr:.6f}  loss: {meters['loss'].value:.4f}{extra}",
+                          flush=True)
             samples = nxt
         model.finish_update()
         if self.dp is not None:                                                             # logger.py:43-48 cross-rank average
             t = torch.tensor([meters["loss"].count, meters["loss"].total], dtype=torch.float64, device=self.device)
             self.dp.dist.all_reduce(t)
             meters["loss"].count, meters["loss"].total = int(t[0].item()), float(t[1].item())
-        return {k: "{:.3f}".format(m.global_avg) for k, m in meters.items()}
+        stats = {k: "{:.3f}".format(m.global_avg) for k, m in meters.items()}
+        if clip_on:
+            gstats = model.grad_stats()                   # after finish_update(): the epoch's last update included
+            if gstats["grad_norm"] is not None:
+                stats["grad_norm"] = "{:.3f}".format(gstats["grad_norm"])
+            stats["skipped_steps"] = int(gstats["skipped_steps"])
+        return stats
 
     def train(self):
         self.log_config()
