@@ -51,13 +51,26 @@ def parse_args(argv=None):
                         "(fuller packed passes at the price of occupancy)")
     parser.add_argument("--llm-score", action="store_true", help="also write llm_anomaly_score = p(Yes) / (p(Yes) + p(No)) at the "
                         "first generated token (generate(output_scores=True): the language model's own anomaly score)")
-    return parser.parse_args(argv)
+    parser.add_argument("--rank-answers", action="store_true", help="also rank the two trained answers by log-likelihood "
+                        "(model.score_answers, nothing decoded): llm_answer_score = p(abnormal answer) / (p(abnormal) + p(normal)) "
+                        "and ranked_output = the likelier answer's text")
+    parser.add_argument("--rank-only", action="store_true", help="--rank-answers without generation: output is the likelier "
+                        "answer's text")
+    args = parser.parse_args(argv)
+    args.rank_answers = args.rank_answers or args.rank_only
+    return args
 
 
 def llm_watch_ids(tokenizer):
     """The ids the training labels teach as the answer's first token: (Yes, No) of ABNORMAL_DESCRIBE / NORMAL_DESCRIBE."""
     from myriad_amd import datasets as D
     return [int(tokenizer(t, add_special_tokens=False).input_ids[0]) for t in (D.ABNORMAL_DESCRIBE, D.NORMAL_DESCRIBE)]
+
+
+def rank_texts():
+    """The candidates of --rank-answers, score_answers' default: index 0 is the abnormal answer."""
+    from myriad_amd import datasets as D
+    return [D.ABNORMAL_DESCRIBE, D.NORMAL_DESCRIBE]
 
 
 def main(argv=None):
@@ -114,7 +127,7 @@ def main(argv=None):
         generate_kwargs.update(output_scores=True, watch_ids=llm_watch_ids(model.llama_tokenizer))
 
     model.eval()
-    if args.slots > 0:
+    if args.slots > 0 and not args.rank_only:
         return save_path, _run_slots(args, model, loader, generate_kwargs, save_path)
     records, all_time, sampled = [], 0.0, 0
     for testid, data_sample in enumerate(loader):
@@ -124,19 +137,25 @@ def main(argv=None):
             break
         with torch.no_grad():
             t1 = time.time()
-            outputs = model.generate(data_sample, **generate_kwargs)
+            ranked = model.score_answers(data_sample) if args.rank_answers else None
+            outputs = ranked if args.rank_only else model.generate(data_sample, **generate_kwargs)
             torch.cuda.synchronize()
             all_time += time.time() - t1
-        sampled += model.last_generate_stats["sampled_rows"]
-        texts = EP.postprocess_generation(outputs["token_ids"], model.llama_tokenizer)
+        if args.rank_only:                               # nothing was generated: the likelier answer is the output
+            texts = [rank_texts()[int(b)] for b in ranked["best"]]
+        else:
+            sampled += model.last_generate_stats["sampled_rows"]
+            texts = EP.postprocess_generation(outputs["token_ids"], model.llama_tokenizer)
         maps = outputs.get("ve_anomaly_maps")
         for ind, text in enumerate(texts):
             amax = None
             if maps is not None:                         # anomaly_map_handler (:93-104): uint8(map * 255) then max
                 amax = float((maps[ind].detach().float().cpu() * 255.0).to(torch.uint8).max())
-            llm = EP.llm_anomaly_score(outputs["watch_logprobs"][ind, 0]) if args.llm_score else None
+            llm = EP.llm_anomaly_score(outputs["watch_logprobs"][ind, 0]) if args.llm_score and not args.rank_only else None
             records.append(EP.make_ad_record(int(data_sample["image_id"][ind]), data_sample["img_path"][ind],
                                              bool(data_sample["is_anomaly"][ind]), text, amax, llm))
+            if ranked is not None:
+                EP.add_answer_ranking(records[-1], ranked["answer_logprobs"][ind], rank_texts()[int(ranked["best"][ind])])
     EP.write_jsonl(save_path, records)
     n_batches = max(1, len(records) // max(1, args.bs))
     print("CUDA Memory:", torch.cuda.max_memory_allocated() / (1024 * 1024))
@@ -151,7 +170,7 @@ def _run_slots(args, model, loader, generate_kwargs, save_path):
     import torch
     from myriad_amd import eval_protocol as EP
 
-    meta = []                                            # per sample, in input order: what its record needs besides the text
+    meta, ranks = [], []                                 # per sample, in input order: what its record needs besides the text
 
     def batches():
         for testid, data_sample in enumerate(loader):
@@ -161,6 +180,9 @@ def _run_slots(args, model, loader, generate_kwargs, save_path):
                 break
             for ind in range(len(data_sample["image_id"])):
                 meta.append((int(data_sample["image_id"][ind]), data_sample["img_path"][ind], bool(data_sample["is_anomaly"][ind])))
+            if args.rank_answers:                        # between two token steps of the stream: a pass of its own caches
+                r = model.score_answers(data_sample)
+                ranks.extend((r["answer_logprobs"][ind], int(r["best"][ind])) for ind in range(len(data_sample["image_id"])))
             yield data_sample
 
     records = []
@@ -174,6 +196,9 @@ def _run_slots(args, model, loader, generate_kwargs, save_path):
                 amax = float((out["ve_anomaly_map"].detach().float().cpu() * 255.0).to(torch.uint8).max())
             llm = EP.llm_anomaly_score(out["watch_logprobs"][0]) if args.llm_score else None
             records.append(EP.make_ad_record(*meta[out["index"]], text, amax, llm))
+            if args.rank_answers:
+                lp, best = ranks[out["index"]]
+                EP.add_answer_ranking(records[-1], lp, rank_texts()[best])
         torch.cuda.synchronize()
         all_time = time.time() - t1
     EP.write_jsonl(save_path, records)

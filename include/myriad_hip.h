@@ -524,6 +524,17 @@ int mh_attn_prefill_ragged_past(const void* qkv, long ld_qkv, const int* pos, co
                                 void* cache, long cache_bstride, long ld_cache, int n_slots, int T_cap, const float* cos_tab,
                                 const float* sin_tab, int max_pos, void* out, long ldo, int M, int H, int D, float scale,
                                 mh_stream_t s);
+/* The _past pass for segments that continue the SAME cached prefix (the candidate answers of one prompt): the same tables
+ * int[R][4] of (row0, len, slot, past), but several segments may name one slot, with equal or different past (0 included), and
+ * the cache is only read: rows < past of a named slot, and no byte of it is written.  Segment i's out rows have the bits of
+ * mh_attn_prefill_ragged_past on that segment alone with a private copy of its slot (for len = 1 and past < 8192 the decode
+ * kernel's arithmetic, as there); qkv is only read, rows of out outside every segment are not touched.  MH_ERR_ARG /
+ * MH_ERR_UNSUPPORTED, nothing launched, as mh_attn_prefill_ragged_past, except that slots need not be distinct; the kernel
+ * repeats the per-segment bounds on the device table. */
+int mh_attn_prefill_ragged_shared(const void* qkv, long ld_qkv, const int* pos, const int* seg, const int* seg_host, int R,
+                                  const void* cache, long cache_bstride, long ld_cache, int n_slots, int T_cap,
+                                  const float* cos_tab, const float* sin_tab, int max_pos, void* out, long ldo, int M, int H, int D,
+                                  float scale, mh_stream_t s);
 /* The same token step with the keys split into chunks (attn_decode_split.hip): grid (ceil(T_cap / chunk), B*H), each workgroup
  * scores one chunk and writes fp32 (m, l, o[D]) into `partials`, a second launch merges the chunks in order and writes bf16 out
  * (bits fixed from run to run).  q is rotated in registers (qkv is not written); the cache row at pos_dev[0] gets the bits

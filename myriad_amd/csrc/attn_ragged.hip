@@ -22,6 +22,11 @@
 // nothing stale in the slot is seen.  New cache row past + c is written by the workgroup whose query tile owns chunk row c (that
 // key always lies in its causal range), exactly once; rows below past and at or above past + len are never written.
 // A segment of one row takes one_row_attention below, as mh_attn_fwd takes the decode kernel for Sq == 1.
+//
+// mh_attn_prefill_ragged_shared (PAST and SHARED) is the _past pass for segments that continue the SAME cached prefix: several
+// segments may name one slot, with equal or different past, and the cache is only read.  The _past form reads no cache row
+// >= past and takes every key at or above past from qkv (the one-row path from LDS), so its cache stores feed nothing in the
+// launch: the flag drops them and changes nothing else, and a segment's out rows have the bits _past gives it alone.
 #include "attn_tile.h"
 
 #include <algorithm>
@@ -75,17 +80,20 @@ __device__ __forceinline__ short8_t rope8(const bf16_t* head, int c, int half, c
 // fp32 throughout, 16 lanes per key for the scores, every wave its own softmax statistics, the keys dealt round-robin to 16 waves
 // for P.V (eight at a time, then a remainder of seven) and the 16 partial outputs summed in wave order.  This is that arithmetic,
 // expression for expression, with each of this workgroup's 4 waves taking 4 of the 16 in turn (ONE_ROW_WAVES is attention.hip's
-// DNW); the scores' LDS is reused for the partial outputs.  The new row's rotated k and its v are written to cache row `past` and
-// kept in LDS: key `past` is read from there, so no cache row >= past is read here either.
+// DNW); the scores' LDS is reused for the partial outputs.  The new row's rotated k and its v are written to cache row `past`
+// (not with SHARED, which writes no cache row) and kept in LDS: key `past` is read from there, so no cache row >= past is read
+// here either.
 // KEEP IN STEP with attn_decode_kernel (attention.hip): a change to its phases, to DNW, to the 8 + 7 unroll of its P.V loop or to
 // mh_attn_fwd's Sq == 1 rule (Sk <= 8192) must be made here too; tests/test_ragged_past_gpu.py (the one-row segments on long
-// prefixes) compares the two bit for bit at sizes that turn every loop.
+// prefixes) compares the two bit for bit at sizes that turn every loop, and tests/test_shared_prefix_gpu.py the SHARED form
+// with this one.
 #define ONE_ROW_WAVES 16
 #define ONE_ROW_MAX_KEYS 8192
 __host__ __device__ __forceinline__ int one_row_score_floats(int keys) {
   const int n = (keys + 63) & ~63;
   return n > ONE_ROW_WAVES * 128 ? n : ONE_ROW_WAVES * 128;
 }
+template <bool SHARED>
 __device__ __forceinline__ void one_row_attention(const RaggedParams& p, char* smem, const bf16_t* xb, bf16_t* cb, int row, int past,
                                                   int h) {
   const int tid = threadIdx.x, lane = tid & 63, rw = tid >> 6;
@@ -100,12 +108,12 @@ __device__ __forceinline__ void one_row_attention(const RaggedParams& p, char* s
   if (tid < (D >> 3)) {
     const short8_t v = rope8(xb + W, tid * 8, half, cs_row, sn_row);
     *reinterpret_cast<short8_t*>(krow + tid * 8) = v;
-    *reinterpret_cast<short8_t*>(cb + (long)past * p.ld_cache + tid * 8) = v;
+    if (!SHARED) *reinterpret_cast<short8_t*>(cb + (long)past * p.ld_cache + tid * 8) = v;
   } else if (tid >= 64 && tid - 64 < (D >> 3)) {
     const int c = (tid - 64) * 8;
     const short8_t v = *reinterpret_cast<const short8_t*>(xb + 2 * W + c);
     *reinterpret_cast<short8_t*>(vrow + c) = v;
-    *reinterpret_cast<short8_t*>(cb + (long)past * p.ld_cache + W + c) = v;
+    if (!SHARED) *reinterpret_cast<short8_t*>(cb + (long)past * p.ld_cache + W + c) = v;
   }
   __syncthreads();
   const bf16_t* kp = cb;
@@ -217,8 +225,9 @@ __device__ __forceinline__ void one_row_attention(const RaggedParams& p, char* s
   }
 }
 
-template <int DP, bool PAST>
+template <int DP, bool PAST, bool SHARED>
 __global__ __launch_bounds__(256) void attn_prefill_ragged_kernel(RaggedParams p) {
+  static_assert(PAST || !SHARED, "the shared form reads a prefix: it is a PAST form");
   constexpr int SW = PAST ? 4 : 3;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* Ks = reinterpret_cast<bf16_t*>(smem);
@@ -239,7 +248,7 @@ __global__ __launch_bounds__(256) void attn_prefill_ragged_kernel(RaggedParams p
   bf16_t* cb = p.cache + (long)slot * p.cache_bs + h * D;
   if (PAST && len == 1 && past < ONE_ROW_MAX_KEYS) {            // mh_attn_fwd's own rule for Sq == 1: the decode kernel's bits
     if (one_row_score_floats(past + 1) * 4 + 512 > p.lds_bytes) return;   // workgroup-uniform, like every test above
-    one_row_attention(p, smem, xb, cb, row0, past, h);
+    one_row_attention<SHARED>(p, smem, xb, cb, row0, past, h);
     return;
   }
   const int kv_end = past + (len < q0 + TQ ? len : q0 + TQ);  // causal: keys 0 .. the tile's last query (absolute keys)
@@ -265,7 +274,8 @@ __global__ __launch_bounds__(256) void attn_prefill_ragged_kernel(RaggedParams p
 
   for (int k0 = 0; k0 < kv_end; k0 += TK) {
     const bool diag = k0 == q0;
-    const auto own = [&](int c) { return PAST ? (c >= q0 && c < q0 + TQ) : diag; };   // this workgroup stores chunk row c
+    // this workgroup stores chunk row c; the shared form stores none
+    const auto own = [&](int c) { return SHARED ? false : PAST ? (c >= q0 && c < q0 + TQ) : diag; };
     __syncthreads();
     // K tile, rotated, row-major (stage_rowmajor's image); rows >= past + len are zero-filled.  Key k0 + row is chunk row c =
     // key - past; this workgroup stores the rows of its own query tile (without a prefix: the diagonal tile, k0 == q0)
@@ -358,19 +368,20 @@ __global__ __launch_bounds__(256) void attn_prefill_ragged_kernel(RaggedParams p
   }
 }
 
-template <int DP, bool PAST>
+template <int DP, bool PAST, bool SHARED = false>
 static int launch_ragged(RaggedParams p, int tiles, int R, hipStream_t s) {
   size_t sh = Lds<DP>::RM_BYTES + Lds<DP>::TR_BYTES;         // <= 35,840 bytes: no opt-in needed
   if (PAST && (size_t)p.lds_bytes > sh) sh = p.lds_bytes;    // a one-row segment's scores: <= 33,280 bytes
   p.lds_bytes = (int)sh;
-  hipLaunchKernelGGL((attn_prefill_ragged_kernel<DP, PAST>), dim3(tiles, R * p.H), dim3(256), sh, s, p);
+  hipLaunchKernelGGL((attn_prefill_ragged_kernel<DP, PAST, SHARED>), dim3(tiles, R * p.H), dim3(256), sh, s, p);
   MH_CHECK_LAUNCH();
   return MH_OK;
 }
 
-// Both entries: `sw` = 3 or 4 ints per segment (without / with `past`).
-static int prefill_ragged(int sw, const void* qkv, long ld_qkv, const int* pos, const int* seg, const int* seg_host, int R,
-                          void* cache, long cache_bstride, long ld_cache, int n_slots, int T_cap, const float* cos_tab,
+// All entries: `sw` = 3 or 4 ints per segment (without / with `past`); `shared` (sw = 4 only): segments may name one slot
+// several times and the cache is only read.
+static int prefill_ragged(int sw, bool shared, const void* qkv, long ld_qkv, const int* pos, const int* seg, const int* seg_host,
+                          int R, void* cache, long cache_bstride, long ld_cache, int n_slots, int T_cap, const float* cos_tab,
                           const float* sin_tab, int max_pos, void* out, long ldo, int M, int H, int D, float scale,
                           hipStream_t stream) {
   if (R == 0) return MH_OK;
@@ -383,8 +394,8 @@ static int prefill_ragged(int sw, const void* qkv, long ld_qkv, const int* pos, 
     return MH_ERR_ARG;
   if ((uintptr_t)qkv % 16 || (uintptr_t)cache % 16 || (uintptr_t)cos_tab % 16 || (uintptr_t)sin_tab % 16 || (uintptr_t)out % 8)
     return MH_ERR_ARG;
-  // the segment table: 0 < len <= T_cap, 0 <= slot < n_slots, rows inside [0, M), slots distinct, segments disjoint; with a
-  // prefix 0 <= past and past + len <= T_cap
+  // the segment table: 0 < len <= T_cap, 0 <= slot < n_slots, rows inside [0, M), slots distinct (unless `shared`), segments
+  // disjoint; with a prefix 0 <= past and past + len <= T_cap
   std::vector<std::pair<long, long>> rows(R);
   std::vector<int> slots(R);
   int max_len = 0, one_row_lds = 0;
@@ -403,7 +414,7 @@ static int prefill_ragged(int sw, const void* qkv, long ld_qkv, const int* pos, 
   std::sort(rows.begin(), rows.end());
   std::sort(slots.begin(), slots.end());
   for (int i = 1; i < R; ++i)
-    if (rows[i].first < rows[i - 1].second || slots[i] == slots[i - 1]) return MH_ERR_ARG;
+    if (rows[i].first < rows[i - 1].second || (!shared && slots[i] == slots[i - 1])) return MH_ERR_ARG;
 
   RaggedParams p = {};
   p.qkv = (const bf16_t*)qkv; p.pos = pos; p.seg = seg; p.cache = (bf16_t*)cache; p.cs = cos_tab; p.sn = sin_tab;
@@ -412,6 +423,11 @@ static int prefill_ragged(int sw, const void* qkv, long ld_qkv, const int* pos, 
   p.M = M; p.H = H; p.D = D; p.n_slots = n_slots; p.T_cap = T_cap; p.max_pos = max_pos; p.scale = scale;
   p.lds_bytes = one_row_lds;
   const int tiles = (max_len + TQ - 1) / TQ;
+  if (sw == 4 && shared) {
+    if (D <= 64) return launch_ragged<64, true, true>(p, tiles, R, stream);
+    if (D <= 96) return launch_ragged<96, true, true>(p, tiles, R, stream);
+    return launch_ragged<128, true, true>(p, tiles, R, stream);
+  }
   if (sw == 4) {
     if (D <= 64) return launch_ragged<64, true>(p, tiles, R, stream);
     if (D <= 96) return launch_ragged<96, true>(p, tiles, R, stream);
@@ -426,8 +442,8 @@ extern "C" int mh_attn_prefill_ragged(const void* qkv, long ld_qkv, const int* p
                                       void* cache, long cache_bstride, long ld_cache, int n_slots, int T_cap, const float* cos_tab,
                                       const float* sin_tab, int max_pos, void* out, long ldo, int M, int H, int D, float scale,
                                       hipStream_t stream) {
-  return prefill_ragged(3, qkv, ld_qkv, pos, seg, seg_host, R, cache, cache_bstride, ld_cache, n_slots, T_cap, cos_tab, sin_tab,
-                        max_pos, out, ldo, M, H, D, scale, stream);
+  return prefill_ragged(3, false, qkv, ld_qkv, pos, seg, seg_host, R, cache, cache_bstride, ld_cache, n_slots, T_cap, cos_tab,
+                        sin_tab, max_pos, out, ldo, M, H, D, scale, stream);
 }
 
 // The same pass on top of a cached prefix: segment tables [R, 4] = (row0, len, slot, past).
@@ -435,6 +451,18 @@ extern "C" int mh_attn_prefill_ragged_past(const void* qkv, long ld_qkv, const i
                                            int R, void* cache, long cache_bstride, long ld_cache, int n_slots, int T_cap,
                                            const float* cos_tab, const float* sin_tab, int max_pos, void* out, long ldo, int M,
                                            int H, int D, float scale, hipStream_t stream) {
-  return prefill_ragged(4, qkv, ld_qkv, pos, seg, seg_host, R, cache, cache_bstride, ld_cache, n_slots, T_cap, cos_tab, sin_tab,
-                        max_pos, out, ldo, M, H, D, scale, stream);
+  return prefill_ragged(4, false, qkv, ld_qkv, pos, seg, seg_host, R, cache, cache_bstride, ld_cache, n_slots, T_cap, cos_tab,
+                        sin_tab, max_pos, out, ldo, M, H, D, scale, stream);
+}
+
+// Several segments continuing the SAME cached prefix (the candidates of one prompt, LlamaDecode.score_continuations): the _past
+// form's tables, but slots may repeat and the cache is only read -- the kernel's SHARED flag drops every cache store, the new
+// rows' k | v are staged from qkv as before (the one-row path keeps them in LDS).  Per segment the out rows have the bits of
+// mh_attn_prefill_ragged_past on that segment alone.
+extern "C" int mh_attn_prefill_ragged_shared(const void* qkv, long ld_qkv, const int* pos, const int* seg, const int* seg_host,
+                                             int R, const void* cache, long cache_bstride, long ld_cache, int n_slots, int T_cap,
+                                             const float* cos_tab, const float* sin_tab, int max_pos, void* out, long ldo, int M,
+                                             int H, int D, float scale, hipStream_t stream) {
+  return prefill_ragged(4, true, qkv, ld_qkv, pos, seg, seg_host, R, const_cast<void*>(cache), cache_bstride, ld_cache, n_slots,
+                        T_cap, cos_tab, sin_tab, max_pos, out, ldo, M, H, D, scale, stream);
 }

@@ -11,8 +11,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .decode_host import (RefillPlanner, SessionTable, SlotScheduler, TurnPlanner, _host_draw, _request_generator, common_prefix,
-                          seeded_requests, split_kv_rows_rule, split_kv_rule)
+from .decode_host import (RefillPlanner, ScorePlan, SessionTable, SlotScheduler, TurnPlanner, _host_draw, _request_generator,
+                          common_prefix, seeded_requests, split_kv_rows_rule, split_kv_rule)
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -234,6 +234,90 @@ class LlamaDecode:
 
         h = self._decode_layers(x, self._gemm_lin, attention, self.lora)
         return self._last_rows_logits(ops.gather_rows_f32(h, ops.h2d(last, self.dev)))
+
+    def _token_logprobs(self, logits: torch.Tensor, targets) -> torch.Tensor:
+        """The log-softmax at temperature 1 of each f32 logits row at its target id, on the device (mh_token_scores_rows with no
+        watch id): f32 [R]."""
+        R = logits.shape[0]
+        out = torch.empty((ops.SCORE_ROWS, R), dtype=F32, device=self.dev)
+        watch = ops.h2d(torch.full((ops.SCORE_WATCH_MAX,), -1, dtype=torch.int32), self.dev)
+        ops.token_scores_rows(logits, ops.h2d(torch.tensor(targets, dtype=torch.long), self.dev), watch, out)
+        return out[1]
+
+    def score_continuations(self, prompt_embs, continuations, max_prompts: int = 8, max_rows: int = 2048,
+                            return_logits: bool = False):
+        """The teacher-forced token log-probs of candidate continuations of prompts, nothing decoded: `prompt_embs` is a list of
+        [S_i, D] f32 embeddings, `continuations` per prompt a list of 1-D integer id tensors (or lists).  Returns, per prompt, a
+        list of f32 [n] CPU tensors: entry j is log p(t_j | prompt, t_<j), the log-softmax at temperature 1 of the f32 logits at
+        t_j (mh_token_scores_rows; the host never recomputes a softmax).  Two passes over the decoder weights per group of at most
+        `max_prompts` prompts (decode_host.ScorePlan; more when the candidates' rows exceed `max_rows`):
+
+          1. _prefill_packed of the prompts, as it is, into the caches of _decode_workspace; its [P, V] last-row logits give every
+             candidate's first token;
+          2. the candidates' rows t_0 .. t_{n-2} of all prompts packed into one zero-padded frame of a multiple of 64 rows, the
+             prefill's own layers (_decode_layers: the bordered LoRA, norms, GEMMs, MLP) with mh_attn_prefill_ragged_shared as the
+             attention -- every candidate of a prompt continues that prompt's cached rows, attends causally to its own rows only
+             and writes no cache row -- then the final norm and the lm-head on all segment rows.
+
+        The caches must hold past + len rows for the attention entry to take a segment, so their T covers max S_i plus the longest
+        candidate; cache rows >= S_i are neither read nor written.  A decode call after this one prefills anew, as always.
+        A candidate's log-probs do not depend on its neighbours as long as the GEMMs' plans are the same: the frame's padded row
+        count and, for the lm-head, the count of scored rows (_prefill_packed's docstring).
+        This path runs on the bf16 prefill weights: MYRIAD_DECODE_FP8 / _FP4 / _MERGE_LORA concern the token step and do not
+        change it.  LoRA dropout is off, as in every decode path.  Sets `last_score_stats` (passes, packed_rows, segments,
+        prompts, candidates).  `return_logits` (debug): also returns, per prompt and candidate, the f32 [n, V] logits rows on the
+        CPU each log-prob was read from."""
+        embs = list(prompt_embs)
+        cands = [[[int(t) for t in (c.tolist() if hasattr(c, "tolist") else c)] for c in cs] for cs in continuations]
+        plan = ScorePlan([int(e.shape[0]) for e in embs], cands, self.V, self.cos.shape[0], max_prompts, max_rows)
+        if self.lora is not None:
+            self.lora.refresh(self.layers)
+        scale = 1.0 / math.sqrt(self.hd)
+        out = [[torch.zeros((len(c),), dtype=F32) for c in cs] for cs in cands]
+        rows_of = [[torch.zeros((len(c), self.V), dtype=F32) for c in cs] for cs in cands] if return_logits else None
+
+        def scatter(lp: torch.Tensor, logits: torch.Tensor, where) -> None:
+            """Rows r of `lp` (and of `logits`) to their (prompt, candidate, token index) = where[r], a candidate's run at once."""
+            lp = lp.cpu()
+            logits = logits.cpu() if return_logits else None
+            r = 0
+            while r < len(where):
+                i, c, j = where[r]
+                e = r + 1
+                while e < len(where) and where[e][:2] == (i, c):
+                    e += 1
+                out[i][c][j:j + e - r] = lp[r:e]
+                if return_logits:
+                    rows_of[i][c][j:j + e - r] = logits[r:e]
+                r = e
+
+        for g in plan.groups:
+            members = g["prompts"]
+            T_need = max(plan.prompt_lens[i] + max(len(c) for c in cands[i]) - 1 for i in members)
+            caches = self._decode_workspace(len(members), T_need, 1.0)["caches"]
+            logits0 = self._prefill_packed([embs[i] for i in members], g["slots"], caches)
+            first = ops.gather_rows_f32(logits0, ops.h2d(torch.tensor(g["first_rows"], dtype=torch.int32), self.dev))
+            scatter(self._token_logprobs(first, g["first_targets"]), first, g["first_map"])
+            for ps in g["passes"]:
+                n = len(ps["ids"])
+                x = torch.zeros((ps["M"], self.D), dtype=F32, device=self.dev)
+                self.embed_tokens_into(ops.h2d(torch.tensor(ps["ids"], dtype=torch.long), self.dev), x)
+                pos = torch.zeros((ps["M"],), dtype=torch.int32)
+                pos[:n] = torch.tensor(ps["pos"], dtype=torch.int32)
+                seg_host = torch.tensor(ps["seg"], dtype=torch.int32)
+                pos_dev, seg_dev = ops.h2d(pos, self.dev), ops.h2d(seg_host, self.dev)
+
+                def attention(li, qkv):
+                    return ops.attn_prefill_ragged_shared(qkv, pos_dev, seg_dev, seg_host, caches[li], self.cos, self.sin, self.H,
+                                                          self.hd, scale)
+
+                h = self._decode_layers(x, self._gemm_lin, attention, self.lora)
+                rows = ops.gather_rows_f32(h, ops.h2d(torch.arange(n, dtype=torch.int32), self.dev))
+                logits = self._last_rows_logits(rows)
+                scatter(self._token_logprobs(logits, ps["targets"]), logits, ps["map"])
+        self.last_score_stats = dict(passes=plan.passes, packed_rows=plan.packed_rows, segments=plan.segments,
+                                     prompts=len(embs), candidates=sum(len(cs) for cs in cands))
+        return (out, rows_of) if return_logits else out
 
     def _step_layers(self, ws: dict) -> torch.Tensor:
         """All decoder layers for one decode token per row of ws["x_in"], whose position lives in device memory (ws["pos"] /

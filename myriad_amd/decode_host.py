@@ -215,6 +215,93 @@ class TurnPlanner:
         return group
 
 
+class ScorePlan:
+    """The passes of LlamaDecode.score_continuations, fixed when the call starts, on plain Python values (no device in sight).
+
+    Prompt i has `prompt_lens[i]` rows and the candidates `candidates[i]`, each a non-empty list of ids t_0 .. t_{n-1}.  The prompts
+    go in list order into groups of at most `slots` prompts whose rows (rounded up to 64) stay within `rows` -- one packed prompt
+    prefill each, prompt i in slot `slot[i]` of its group; the first of a group always goes.  log p(t_0 | prompt) comes from the
+    prompt's LAST prefill row; log p(t_j | prompt, t_<j), j >= 1, from candidate row j - 1.  So a scoring pass packs rows
+    t_0 .. t_{n-2} of a candidate at positions S_i .. S_i + n - 2 as the segment (row0, n - 1, slot_i, S_i) of
+    mh_attn_prefill_ragged_shared, and a one-token candidate has no segment.  A group's candidates go in order into scoring passes
+    of at most `rows` packed rows (rounded up to 64); a candidate is never split, the first of a pass always goes, and a prompt
+    whose candidates overflow a pass is visited again by the next with the same slot and past -- the scoring pass writes no cache
+    row, so the prompt stays cached.
+
+    `groups` = [dict(prompts, slots, first_rows, first_targets, first_map, passes)]: `first_rows` replicates a prompt's row of
+    the prefill's [P, V] logits once per candidate (the gather list), `first_targets` the t_0 beside it and `first_map` its
+    (prompt, candidate, 0).  A pass = dict(seg, M, ids, pos, targets, map): the segment table, the padded frame's rows, and per
+    packed row (frame order, the segments back to back from row 0) the token id fed, its position, the target id scored on that
+    row's logits and its (prompt, candidate, token index).
+
+    ValueError: no prompt, a prompt without rows, an empty candidate list, an empty candidate, an id outside [0, vocab), or a
+    last fed position S_i + n - 2 outside the rotary table of `max_pos` rows (S_i + n - 1 > max_pos) -- the kernel clamps a
+    position silently, so the host refuses."""
+
+    def __init__(self, prompt_lens, candidates, vocab: int, max_pos: int, slots: int = 8, rows: int = 2048):
+        if slots < 1 or rows < 1:
+            raise ValueError(f"slots and rows must be >= 1, got {slots} and {rows}")
+        prompt_lens = [int(n) for n in prompt_lens]
+        if not prompt_lens or len(prompt_lens) != len(candidates):
+            raise ValueError("one non-empty list of candidates per prompt, at least one prompt")
+        cands = []
+        for i, (S, cs) in enumerate(zip(prompt_lens, candidates)):
+            if S < 1:
+                raise ValueError(f"prompt {i} has no rows")
+            cs = [[int(t) for t in c] for c in cs]
+            if not cs:
+                raise ValueError(f"prompt {i}: an empty candidate list")
+            for c, ids in enumerate(cs):
+                if not ids:
+                    raise ValueError(f"prompt {i}: candidate {c} is empty")
+                if any(not 0 <= t < int(vocab) for t in ids):
+                    raise ValueError(f"prompt {i}: candidate {c} has an id outside [0, {int(vocab)})")
+                if S + len(ids) - 1 > int(max_pos):
+                    raise ValueError(f"prompt {i}: candidate {c} ends at position {S + len(ids) - 2}, the rotary table has "
+                                     f"{int(max_pos)}")
+            cands.append(cs)
+        self.prompt_lens, self.candidates = prompt_lens, cands
+        self.groups, self.passes, self.packed_rows, self.segments = [], 0, 0, 0
+        members, used = [], 0
+        for i, S in enumerate(prompt_lens):
+            if members and (len(members) >= int(slots) or round_up(used + S, 64) > int(rows)):
+                self._close(members, int(rows))
+                members, used = [], 0
+            members.append(i)
+            used += S
+        self._close(members, int(rows))
+
+    def _close(self, members, rows_cap: int) -> None:
+        group = dict(prompts=list(members), slots=list(range(len(members))), first_rows=[], first_targets=[], first_map=[],
+                     passes=[])
+        cur = None
+        for slot, i in enumerate(members):
+            S = self.prompt_lens[i]
+            for c, ids in enumerate(self.candidates[i]):
+                group["first_rows"].append(slot)
+                group["first_targets"].append(ids[0])
+                group["first_map"].append((i, c, 0))
+                n = len(ids) - 1
+                if n == 0:
+                    continue
+                if cur is None or round_up(cur["used"] + n, 64) > rows_cap:
+                    cur = dict(seg=[], used=0, ids=[], pos=[], targets=[], map=[])
+                    group["passes"].append(cur)
+                cur["seg"].append((cur["used"], n, slot, S))
+                cur["used"] += n
+                cur["ids"] += ids[:-1]
+                cur["pos"] += list(range(S, S + n))
+                cur["targets"] += ids[1:]
+                cur["map"] += [(i, c, j) for j in range(1, n + 1)]
+        for ps in group["passes"]:
+            ps["M"] = round_up(ps.pop("used"), 64)
+            self.packed_rows += len(ps["ids"])
+            self.segments += len(ps["seg"])
+        self.passes += 1 + len(group["passes"])
+        self.packed_rows += sum(self.prompt_lens[i] for i in members)
+        self.groups.append(group)
+
+
 class SessionTable:
     """Which conversation lives in which decode slot, and what its slot's cache holds: the host side of SlotDecoder.run_turns, on
     plain Python values like SlotScheduler (no device in sight).

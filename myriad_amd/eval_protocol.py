@@ -134,6 +134,29 @@ def llm_anomaly_score(watch_logprobs_first) -> float:
         return float(1.0 / (1.0 + np.exp(np.float64(ln) - np.float64(ly))))
 
 
+def answer_anomaly_score(logprobs_row) -> float:
+    """The softmax over the candidates' log-likelihoods at index 0 (MyriadHIP.score_answers' "answer_logprobs"[row]): for the
+    default pair [ABNORMAL_DESCRIBE, NORMAL_DESCRIBE] p_abn / (p_abn + p_nor) with whole answers in the place of
+    llm_anomaly_score's first tokens.  Taken in float64 from the sums; a -inf entry counts as probability 0, all entries equal
+    (all -inf included) give 1 / C."""
+    lp = np.asarray([float(v) for v in logprobs_row], dtype=np.float64)
+    if lp.size == 0:
+        raise ValueError("answer_anomaly_score: no candidates")
+    m = lp.max()
+    if not np.isfinite(m) or bool((lp == m).all()):
+        return 1.0 / lp.size
+    e = np.exp(lp - m)
+    return float(e[0] / e.sum())
+
+
+def add_answer_ranking(record: dict, logprobs_row, best_text: str) -> dict:
+    """eval_aqa.py --rank-answers: "llm_answer_score" = answer_anomaly_score in the format of "anomaly_score" and
+    "ranked_output", the best candidate's text, joined to a record."""
+    record["llm_answer_score"] = str(round(answer_anomaly_score(logprobs_row), 4))
+    record["ranked_output"] = best_text
+    return record
+
+
 def write_jsonl(path: str, records: Iterable[dict]) -> None:
     with open(path, "w") as f:
         for r in records:

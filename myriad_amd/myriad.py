@@ -1416,6 +1416,85 @@ class MyriadHIP(nn.Module):
             return {"token_ids": ids, "ve_anomaly_maps": maps, **sc}
         return {"token_ids": ids, "ve_anomaly_maps": maps}
 
+    def score_answers(self, samples, candidates=None, candidate_ids=None, normalize: str = "sum", bos: bool = False):
+        """Rank candidate answers by their teacher-forced log-likelihood after the prompt, nothing decoded (closed-set
+        evaluation: BLIP-2's rank mode).  The prompt is generate()'s: finish_update, image, maps, encode_img, the stage-1 prompt
+        layout, without the BOS as generate() wraps it, or with it for `bos=True` -- the training wrap, under which the score of a
+        training answer is the training loss's own quantity.  Rows whose prompts differ in length are assembled one at a time.
+
+        `candidates`: a list of strings shared by the batch, or one list per sample, tokenised as the training targets are --
+        tok(c + end_sym, add_special_tokens=False), truncated to max_txt_len.  `candidate_ids` gives integer ids instead (a list
+        of 1-D tensors / lists shared by the batch, or one such list per sample).  With neither, the two answers the model is
+        trained on: [datasets.ABNORMAL_DESCRIBE, datasets.NORMAL_DESCRIBE].
+
+        Returns {"answer_logprobs": [B, C] float64, the sum of each candidate's token log-probs (their mean with
+        normalize="mean"; with per-sample lists of different sizes C is the largest and the missing entries are -inf),
+        "answer_token_logprobs": per sample a list of f32 [n] tensors (LlamaHIP.score_continuations), "best": [B] int64, the
+        arg-max with ties to the lower index, "candidate_ids": the ids scored, "ve_anomaly_maps": as generate() returns it}.
+        `last_score_stats` holds the engine's counters."""
+        if normalize not in ("sum", "mean"):
+            raise ValueError(f"normalize must be 'sum' or 'mean', got {normalize!r}")
+        self.finish_update()
+        stage = 1 if self.arch == "myriad" else 0
+        image = samples["image"].to(self._dev, F32)
+        maps = None
+        if self.arch == "myriad":
+            key = "oneshot_anomaly_maps" if self.k_shot > 0 else "anomaly_maps"
+            maps = self._maps_for(samples, key, image)
+        B = image.shape[0]
+        cand_ids = self._candidate_ids(B, candidates, candidate_ids)
+        before, after = self._prompt_ids_rows(samples, B, stage)
+        parts = self.encode_img(image, maps, stage, False)
+        first = 1 if not bos else 0                                      # generate() wraps without BOS (myriad.py:446-449)
+        if len({(int(b.shape[0]), int(a.shape[0])) for b, a in zip(before, after)}) == 1:
+            emb, _, _, _ = self._assemble(parts, torch.stack(list(before)), torch.stack(list(after)), None, None)
+            prompts = [emb[i, first:].contiguous() for i in range(B)]
+        else:
+            prompts = []
+            for i in range(B):
+                emb, _, _, _ = self._assemble([p[i:i + 1] for p in parts], before[i][None], after[i][None], None, None)
+                prompts.append(emb[0, first:].contiguous())
+        self.llama.decode_lora_version = self.store.version
+        token_lp = self.llama.score_continuations(prompts, cand_ids)
+        self.last_score_stats = self.llama.last_score_stats
+        C = max(len(cs) for cs in cand_ids)
+        lp = torch.full((B, C), float("-inf"), dtype=torch.float64)
+        for i, row in enumerate(token_lp):
+            for c, t in enumerate(row):
+                total = t.double().sum()
+                lp[i, c] = total / t.numel() if normalize == "mean" else total
+        return {"answer_logprobs": lp, "answer_token_logprobs": token_lp, "best": lp.argmax(1), "candidate_ids": cand_ids,
+                "ve_anomaly_maps": maps}
+
+    def _candidate_ids(self, B: int, candidates, candidate_ids):
+        """score_answers' candidates as ids: per sample a list of 1-D int64 tensors."""
+        if candidates is not None and candidate_ids is not None:
+            raise ValueError("pass candidates or candidate_ids, not both")
+        if candidate_ids is not None:
+            rows = list(candidate_ids)
+            shared = not rows or torch.is_tensor(rows[0]) or not rows[0] or not hasattr(rows[0][0], "__len__")
+            rows = [rows] * B if shared else rows
+            if len(rows) != B:
+                raise ValueError(f"candidate_ids: one list per sample, got {len(rows)} for a batch of {B}")
+            return [[torch.as_tensor(c, dtype=torch.long).reshape(-1) for c in cs] for cs in rows]
+        if candidates is None:
+            from . import datasets
+            candidates = [datasets.ABNORMAL_DESCRIBE, datasets.NORMAL_DESCRIBE]
+        rows = list(candidates)
+        rows = [rows] * B if not rows or isinstance(rows[0], str) else [list(r) for r in rows]
+        if len(rows) != B:
+            raise ValueError(f"candidates: one list per sample, got {len(rows)} for a batch of {B}")
+        tok = self.llama_tokenizer
+        if tok is None:
+            raise RuntimeError("no tokenizer: pass integer ids (candidate_ids)")
+        memo = {}
+        for cs in rows:
+            for c in cs:
+                if c not in memo:                                        # as the training targets are (myriad.py:395-405)
+                    ids = tok(c + self.end_sym, add_special_tokens=False).input_ids[:self.max_txt_len]
+                    memo[c] = torch.tensor(ids, dtype=torch.long)
+        return [[memo[c] for c in cs] for cs in rows]
+
     def _prompt_ids_rows(self, samples, B: int, stage: int):
         """_tokenize for an inference batch, one row at a time: lists of B 1-D id tensors whose lengths may differ."""
         if "before_ids" in samples:

@@ -417,9 +417,11 @@ def attn_decode_rope_rows(qkv2d: torch.Tensor, cache: torch.Tensor, pos: torch.T
     return out
 
 
-def _attn_prefill_ragged(sw: int, qkv2d, pos, seg, seg_host, cache, cos_tab, sin_tab, n_heads, head_dim, scale, out):
-    """attn_prefill_ragged (sw = 3 ints per segment) and attn_prefill_ragged_past (sw = 4): one set of checks."""
-    name_ = "attn_prefill_ragged" + ("_past" if sw == 4 else "")
+def _attn_prefill_ragged(sw: int, qkv2d, pos, seg, seg_host, cache, cos_tab, sin_tab, n_heads, head_dim, scale, out,
+                         shared: bool = False):
+    """attn_prefill_ragged (sw = 3 ints per segment), attn_prefill_ragged_past (sw = 4) and attn_prefill_ragged_shared (sw = 4,
+    `shared`): one set of checks."""
+    name_ = "attn_prefill_ragged" + (("_shared" if shared else "_past") if sw == 4 else "")
     _chk2d(qkv2d, BF16, name_ + ".qkv")
     M, W = qkv2d.shape[0], n_heads * head_dim
     if qkv2d.shape[1] < 3 * W:
@@ -446,7 +448,7 @@ def _attn_prefill_ragged(sw: int, qkv2d, pos, seg, seg_host, cache, cos_tab, sin
         if out.shape != (M, W):
             raise _lib.MyriadHipError(f"{name_}: out shape {tuple(out.shape)} != {(M, W)}")
     R = seg_host.shape[0]
-    fn = _L().mh_attn_prefill_ragged_past if sw == 4 else _L().mh_attn_prefill_ragged
+    fn = getattr(_L(), "mh_" + name_)
     _lib.check(fn(_p(qkv2d), qkv2d.stride(0), _p(pos), _p(seg), seg_host.data_ptr(), R, _p(cache), cache.stride(0), cache.stride(1),
                   cache.shape[0], cache.shape[1], _p(cos_tab), _p(sin_tab), cos_tab.shape[0], _p(out), out.stride(0), M, n_heads,
                   head_dim, float(scale), _s()), f"mh_{name_} M={M} R={R} H={n_heads} D={head_dim}")
@@ -472,6 +474,16 @@ def attn_prefill_ragged_past(qkv2d: torch.Tensor, pos: torch.Tensor, seg: torch.
     rope_ + copy3d_bf16 into cache[slot, past:past + len] + attn_fwd(causal=True) over the past + len keys, same bits; no cache
     row >= past is read, none outside [past, past + len) written.  With past = 0 everywhere it is attn_prefill_ragged's bits."""
     return _attn_prefill_ragged(4, qkv2d, pos, seg, seg_host, cache, cos_tab, sin_tab, n_heads, head_dim, scale, out)
+
+
+def attn_prefill_ragged_shared(qkv2d: torch.Tensor, pos: torch.Tensor, seg: torch.Tensor, seg_host: torch.Tensor,
+                               cache: torch.Tensor, cos_tab: torch.Tensor, sin_tab: torch.Tensor, n_heads: int, head_dim: int,
+                               scale: float, out: Optional[torch.Tensor] = None):
+    """attn_prefill_ragged_past for segments that continue the SAME cached prefix: the [R, 4] tables of (row0, len, slot, past),
+    but several segments may name one slot (equal or different past, 0 included) and `cache` is only read -- rows < past of a
+    named slot; no byte of it is written.  A segment's o rows have the bits attn_prefill_ragged_past gives it alone on a private
+    copy of its slot."""
+    return _attn_prefill_ragged(4, qkv2d, pos, seg, seg_host, cache, cos_tab, sin_tab, n_heads, head_dim, scale, out, shared=True)
 
 
 # keys per workgroup of mh_attn_decode_rope_split: 128 measured fastest at 256 / 1,024 / 2,048 cached keys, batch 1, 32 heads
