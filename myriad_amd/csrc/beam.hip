@@ -106,7 +106,9 @@ __global__ __launch_bounds__(BNT) void beam_row_topk_kernel(const float* __restr
     ti = bi;
   }
   __syncthreads();
-  // rank the BNW * K wave survivors; the row's top K are those of rank < K (ranks are distinct: indices are)
+  // rank the BNW * K wave survivors; the row's top K are those of rank < K.  Real candidates have distinct indices, so distinct
+  // ranks.  The (-inf, 0x7fffffff) entries of waves that ran out all share ONE rank, the number of real survivors -- and that is
+  // >= K, because a wave hands on min(K, its candidates) and the row has V >= K of them: none is written, every rank < K once
   const int n = BNW * K;
   for (int c = tid; c < n; c += BNT) {
     const float s = cs[c];

@@ -1347,15 +1347,37 @@ def token_scores_rows(logits: torch.Tensor, ids: torch.Tensor, watch: torch.Tens
 BEAM_MAX = 8           # most beams mh_beam_topk / mh_beam_reorder_kv take (include/myriad_hip.h)
 
 
+def _chk_flat(t, dtype, need: int, name: str):
+    """A buffer a kernel indexes linearly: a contiguous cuda tensor of `dtype` with at least `need` elements."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or t.numel() < need:
+        got = f"{t.dtype} {tuple(t.shape)} cuda={t.is_cuda} contiguous={t.is_contiguous()}" if isinstance(t, torch.Tensor) else repr(t)
+        raise _lib.MyriadHipError(f"{name}: need a contiguous cuda {dtype} tensor of at least {need} elements, got {got}")
+
+
 def beam_topk(logits: torch.Tensor, scores: torch.Tensor, part_s, part_i, out_s, out_i, B: int, nb: int, ban_id: int = -1,
               pos=None, kvlen=None):
     """The beam step's selection: per item b the top 2*nb of (scores[row] + log_softmax(logits[row])) over the item's rows
     (logits [B*rpi, V], rpi = nb, or 1 for the step after a B-row prefill), best first, ties to the lower flat index
     row_in_item * V + token, into out_s (f32) / out_i (int32) [B, 2*nb].  part_s / part_i: scratch of B*rpi*2*nb entries.
-    With pos / kvlen, every row of those buffers advances by one (the end of a token step)."""
+    With pos / kvlen (both or neither, int32, one length), every row of those buffers advances by one (the end of a token
+    step).  A buffer of the wrong type or too short for what the kernels index is refused here, before any launch."""
+    _chk2d(logits, F32, "beam_topk: logits")
     R, V = logits.shape
+    if B <= 0 or R % B != 0:
+        raise _lib.MyriadHipError(f"beam_topk: {R} logits rows do not divide into B={B} items")
     rpi = R // B
-    n_adv = 0 if pos is None else pos.numel()
+    for name, t, dtype, need in (("scores", scores, F32, R), ("part_s", part_s, F32, R * 2 * nb), ("part_i", part_i, torch.int32, R * 2 * nb),
+                                 ("out_s", out_s, F32, B * 2 * nb), ("out_i", out_i, torch.int32, B * 2 * nb)):
+        _chk_flat(t, dtype, need, f"beam_topk: {name}")
+    if (pos is None) != (kvlen is None):
+        raise _lib.MyriadHipError("beam_topk: pos and kvlen advance together: give both or neither")
+    n_adv = 0
+    if pos is not None:
+        n_adv = pos.numel()
+        _chk_flat(pos, torch.int32, n_adv, "beam_topk: pos")
+        _chk_flat(kvlen, torch.int32, n_adv, "beam_topk: kvlen")
+        if kvlen.numel() != n_adv:
+            raise _lib.MyriadHipError(f"beam_topk: pos has {n_adv} rows and kvlen {kvlen.numel()}")
     _lib.check(_L().mh_beam_topk(_p(logits), logits.stride(0), _p(scores), _p(part_s), _p(part_i), _p(out_s), _p(out_i), B, rpi, nb,
                                  V, int(ban_id), _p(pos), _p(kvlen), n_adv, _s()), "mh_beam_topk")
     return out_s, out_i
@@ -1363,7 +1385,12 @@ def beam_topk(logits: torch.Tensor, scores: torch.Tensor, part_s, part_i, out_s,
 
 def beam_reorder_kv(cache_table: torch.Tensor, L: int, B: int, nb: int, T_cap: int, C: int, src, lo, hi):
     """In place, every layer: cache[r, p] = cache[src[r], p] for p in [lo[0], hi[0]); cache_table = int64 device tensor of the L
-    [B*nb, T_cap, C] bf16 cache base pointers; src / lo / hi int32 device tensors (read by the kernel: capturable)."""
+    [B*nb, T_cap, C] bf16 cache base pointers; src / lo / hi int32 device tensors (read by the kernel: capturable).  A table
+    shorter than L, a src shorter than B*nb or a tensor of another type is refused here, before any launch."""
+    _chk_flat(cache_table, torch.long, L, "beam_reorder_kv: cache_table")
+    _chk_flat(src, torch.int32, B * nb, "beam_reorder_kv: src")
+    _chk_flat(lo, torch.int32, 1, "beam_reorder_kv: lo")
+    _chk_flat(hi, torch.int32, 1, "beam_reorder_kv: hi")
     _lib.check(_L().mh_beam_reorder_kv(_p(cache_table), L, B, nb, int(T_cap), C, _p(src), _p(lo), _p(hi), _s()),
                "mh_beam_reorder_kv")
 
