@@ -354,6 +354,28 @@ int mh_beam_topk(const float* logits, long ldl, const float* scores, float* part
    src[r] == r are not written; duplicate parents are fine (every source is read before any store of the same cell). */
 int mh_beam_reorder_kv(void* const* caches, int L, int B, int nb, long T_cap, int C, const int* src, const int* lo, const int* hi,
                        mh_stream_t s);
+/* beam-search multinomial sampling / the repetition penalty under beams: mh_beam_topk's step with HF's processor chain on the
+   log-probs and Gumbel noise on the candidates.  logits [B*nb, ldl] fp32 (nb rows per item, always), scores [B*nb].  Per row, in
+   fp32: lp = (x - max) - log(sum exp(x - max)) (NaN -> -inf); for every id in the row's bitmap seen[row] (W = ceil(V/32) words a
+   row; null: none) lp = lp < 0 ? lp*p : lp/p; lp[ban_id] = -inf (< 0: none); then with draw != 0: w = lp * inv_temp; the
+   k = max(top_k, 2) largest w stay, ties at the k-th value included; of those, in (w desc, id asc) order, candidate i stays while
+   its exclusive prefix mass of softmax(w) is < top_p * total (top_p >= 1: all), the best two always; acc = w + scores[row] for
+   what stays, -inf otherwise; key = acc - log(-log(u)), u = ((x0 >> 9) + 0.5) * 2^-23, x0 = the first word of Philox4x32-10 with
+   key = *seed and counter (t, row_in_item * V + id, item, 1), t = (step ? *step : 0) + t_add.  With draw == 0: key = acc =
+   lp + scores[row] (no temperature, cuts or noise; params only read for the penalty).  params = f32 (inv_temp, top_p, top_k,
+   penalty) in device memory, mh_sample_rows' layout.  Per item the top K = 2*nb by (key desc, flat asc), flat = row_in_item * V +
+   id: out_s = acc, out_i = flat, out_k = key (null: not written), each [B, K]; out_f [B] = 1 when a row of the item had more than
+   1024 candidates tied into its top-k set, whose top-p cut was then not applied (the indices written are valid; the host redoes
+   the item), else 0.  part_k / part_a / part_i = scratch of B*nb*K entries each, part_f of B*nb.  pos / kvlen (both or neither):
+   += 1 for rows [0, n_adv), and *step += 1 with them.  4 <= V <= 32768, V % 4 == 0, 2*nb <= V, nb <= 8, else MH_ERR_UNSUPPORTED;
+   a null required pointer, V < 1 or ldl < V is MH_ERR_ARG; both before any launch. */
+int mh_beam_sample_topk(const float* logits, long ldl, const float* scores, const unsigned* seen, float* part_k, float* part_a,
+                        int* part_i, int* part_f, float* out_s, int* out_i, int* out_f, float* out_k, int B, int nb, int V,
+                        int ban_id, int draw, const float* params, const unsigned long long* seed, int* step, int t_add, int* pos,
+                        int* kvlen, int n_adv, mh_stream_t s);
+/* the seen-id bitmaps follow their hypotheses: seen[r] = old seen[src[r]] | bit(ids[r]) over [B*nb, ceil(V/32)] words, in place
+   (every source word of an item is read before any store); src as in mh_beam_reorder_kv, ids int64 (outside [0, V): no bit). */
+int mh_beam_seen_update(unsigned* seen, const int* src, const long* ids, int B, int nb, int V, mh_stream_t s);
 
 /* K12 conv stacks of VEInstructorV2 / VETokenizer (networks.py:98-127,159-189) as im2col + mh_gemm_bf16_nt. */
 int mh_im2col_nhwc(const void* x, void* col, int B, int H, int W, int C, int kh, int kw, int pad, int Kpad,

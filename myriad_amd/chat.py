@@ -279,26 +279,38 @@ class Chat(_ChatBase):
                length_penalty=1, temperature=1.0, max_length=2000, do_sample=True, generator=None):
         """One assistant turn (conversation.py:144-178).  The context is truncated to the reference's window; the KV cache of the
         earlier turns is reused up to the first position whose token / image row differs.  `repetition_penalty` != 1 needs the
-        device sampling switch, as in generate().  num_beams > 1: beam search on the full context, no reuse."""
+        device sampling switch, as in generate().  num_beams > 1: beam search on the full context, no reuse; with the beam sampling
+        switch (MYRIAD_BEAM_SAMPLING=1 or model.llama.beam_sampling = True) it is the reference's own call -- beam-search
+        multinomial sampling with do_sample, top_p, temperature, top_k = 50, repetition_penalty and generator
+        (LlamaHIP.beam_generate) -- and last_stats gains num_beams, beam_sampled_steps and beam_host_steps; without it the
+        beams are deterministic and a penalty is refused, as before."""
         m = self.model
         m.finish_update()
         llama = m.llama
         llama.decode_lora_version = m.store.version                 # decode_merge_lora re-merges only when the LoRA weights moved
         rep = 1.0 if repetition_penalty is None else float(repetition_penalty)
-        if rep != 1.0 and not llama.device_sampling:
+        beam_sampling = bool(llama.beam_sampling and int(num_beams) > 1)
+        if rep != 1.0 and not llama.device_sampling and not beam_sampling:
             raise NotImplementedError(f"answer(repetition_penalty={rep}) needs the device sampling switch "
                                       "(MYRIAD_DEVICE_SAMPLING=1 or model.llama.device_sampling = True)")
         embs, keys, begin = self._turn_context(conv, img_list, max_new_tokens, max_length)
         S = embs.shape[1]
         if int(num_beams) > 1:
-            if rep != 1.0:
+            if rep != 1.0 and not beam_sampling:
                 raise NotImplementedError(f"answer(num_beams={num_beams}, repetition_penalty={rep}) is not implemented")
+            sample_kw = {}
+            if beam_sampling:
+                sample_kw = dict(do_sample=bool(do_sample), top_p=float(top_p), temperature=float(temperature), top_k=50,
+                                 repetition_penalty=rep, generator=generator)
             ids = llama.beam_generate(embs, int(num_beams), max_new_tokens=max_new_tokens, stop_ids=STOP_WORDS, eos_id=2,
-                                      min_length=min_length, length_penalty=float(length_penalty))
+                                      min_length=min_length, length_penalty=float(length_penalty), **sample_kw)
             st = llama.last_generate_stats
             self.last_stats = dict(context_tokens=S, reused_tokens=0, prefilled_tokens=S, steps=st["steps"],
                                    graph_captures=0 if self.session is None else self.session.graph_captures,
                                    graph_replays=st["graph_replays"], split_kv=False, full_reprefill_reason="num_beams")
+            if beam_sampling:
+                self.last_stats.update(num_beams=st["num_beams"], beam_sampled_steps=st.get("beam_sampled_steps", 0),
+                                       beam_host_steps=st.get("beam_host_steps", 0))
         else:
             if self.session is None:
                 self.session = DecodeSession(llama, max_length + max_new_tokens + 2)

@@ -15,57 +15,7 @@
 // ban (gen[r] < min_length); min_length and eos_id follow the four knobs in `params` (six floats).  The uniform entry points are
 // instances of the same bodies with the per-row reads compiled out.
 #include "common.h"
-
-#define SNT 1024                // threads per row
-#define SNW (SNT / 64)
-#define MH_SAMPLE_CAP 1024      // most candidates the sort takes; a larger tied top-k set is reported as kept = -1
-
-// ---------------------------------------------------------------------------------------------------- Philox4x32-10
-__device__ __forceinline__ void philox4x32_10(unsigned c[4], unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0];
-    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c[2];
-    const unsigned hi0 = (unsigned)(p0 >> 32), lo0 = (unsigned)p0, hi1 = (unsigned)(p1 >> 32), lo1 = (unsigned)p1;
-    c[0] = hi1 ^ c[1] ^ k0;
-    c[1] = lo1;
-    c[2] = hi0 ^ c[3] ^ k1;
-    c[3] = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-
-// order-preserving fp32 <-> u32 map: a > b (floats) <=> key(a) > key(b) (unsigned)
-__device__ __forceinline__ unsigned smp_key(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float smp_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-// inclusive prefix sum over the 64 lanes of a wave
-template <typename T>
-__device__ __forceinline__ T smp_wave_scan(T v) {
-  const int l = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const T n = __shfl_up(v, o, 64);
-    if (l >= o) v += n;
-  }
-  return v;
-}
-// inclusive prefix sum over the block (thread order); `wsum` is SNW entries of LDS
-template <typename T>
-__device__ __forceinline__ T smp_block_scan(T v, T* wsum) {
-  v = smp_wave_scan(v);
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  __syncthreads();
-  if (l == 63) wsum[w] = v;
-  __syncthreads();
-  T base = 0;
-  for (int i = 0; i < w; ++i) base += wsum[i];
-  return v + base;
-}
+#include "smp_rng.h"          // SNT / SNW / MH_SAMPLE_CAP, Philox4x32-10, the ordered keys and the prefix sums
 
 struct SmpTop { float best; int idx; float second; };
 __device__ __forceinline__ SmpTop smp_combine(const SmpTop& a, const SmpTop& b) {

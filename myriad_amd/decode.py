@@ -12,7 +12,7 @@ import torch
 
 from . import ops
 from .decode_host import (RefillPlanner, ScorePlan, SessionTable, SlotScheduler, TurnPlanner, _host_draw, _request_generator,
-                          common_prefix, seeded_requests, split_kv_rows_rule, split_kv_rule)
+                          beam_sample_select, common_prefix, seeded_requests, split_kv_rows_rule, split_kv_rule)
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -592,7 +592,9 @@ class LlamaDecode:
     @torch.no_grad()
     def beam_generate(self, inputs_embeds: torch.Tensor, num_beams: int, max_new_tokens: int = 90, stop_ids=(), eos_id: int = 2,
                       min_length: int = 1, length_penalty: float = 1.0, early_stopping=False, num_return_sequences: int = 1,
-                      use_graph: bool = True, return_scores: bool = False, pad_id: Optional[int] = None):
+                      use_graph: bool = True, return_scores: bool = False, pad_id: Optional[int] = None, do_sample: bool = False,
+                      temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, repetition_penalty: float = 1.0,
+                      generator: Optional[torch.Generator] = None):
         """Beam search from [B,S0,D] f32 embeddings: HF GenerationMixin._beam_search (tests/beam_ref.py states the rules).
         Returns [B * num_return_sequences, L] int64 (CPU), generated ids only, the hypotheses of item b at rows
         b * nrs .. b * nrs + nrs - 1 best first, right-padded with pad_id (default EOS); with return_scores also their
@@ -608,7 +610,20 @@ class LlamaDecode:
         the fed tokens, the decoder layers at B * nb rows (packed GEMV up to GEMV_MAX_ROWS), lm-head, mh_beam_topk (log-softmax +
         running score + EOS ban, per item the top 2 * nb candidates), pos / kvlen += 1.  The host reads the [2, B, 2*nb]
         record (one device->host copy), keeps the hypotheses, and writes the next step's (ids, src, running scores) with one
-        host->device copy."""
+        host->device copy.
+
+        `do_sample` / `repetition_penalty != 1` (behind `beam_sampling`, MYRIAD_BEAM_SAMPLING=1; NotImplementedError without it)
+        are HF's beam-search multinomial sampling and its penalty under beams (tests/beam_sample_ref.py states the rule): per row
+        log_softmax, the penalty on the log-probs of the ids the hypothesis generated, the EOS ban, temperature, top-k
+        (max(top_k, 2), ties kept), top-p (the best two always stay), + the running score, and the item's 2 * nb candidates are
+        drawn without replacement as the top 2 * nb of acc + Gumbel noise, one Philox4x32-10 stream per candidate keyed by one seed
+        drawn from `generator` per call.  The step selects with mh_beam_sample_topk in place of mh_beam_topk, and
+        mh_beam_seen_update carries the seen-id bitmaps to their hypotheses after the KV reorder; the workspace and the captured
+        step are this path's own, and the knobs, the seed and the step counter sit in device memory.  `select` below is unchanged:
+        the record is what HF's multinomial hands on.  do_sample=False with a penalty is the same step without temperature, cuts
+        and noise.  An item whose tied top-k set passed the device's 1024 candidates is redone on the host for that step
+        (decode_host.beam_sample_select, counted in last_generate_stats["beam_host_steps"]); with sampling, top_k outside
+        1 .. 1024 is refused (there is no host draw path under beams)."""
         B, S0, _ = inputs_embeds.shape
         nb, nrs = int(num_beams), int(num_return_sequences)
         if nb > ops.BEAM_MAX:
@@ -625,10 +640,27 @@ class LlamaDecode:
         pad = eos_id if pad_id is None else int(pad_id)
         stops = [tuple(int(t) for t in st) for st in stop_ids]
         R, K, V, NEG = B * nb, 2 * nb, self.V, np.float32(-1.0e9)
+        draw, pen = bool(do_sample), float(repetition_penalty)
+        sampled = draw or pen != 1.0                                 # the step selects with mh_beam_sample_topk
+        if sampled:
+            if not self.beam_sampling:
+                raise NotImplementedError(f"num_beams={nb} with do_sample or repetition_penalty != 1 needs the beam sampling "
+                                          "switch (MYRIAD_BEAM_SAMPLING=1 or llama.beam_sampling = True)")
+            inv_temp, top_k, _, _ = _sampling_args(self, draw, temperature, top_k, pen)
+            if draw and not 1 <= top_k <= ops.SAMPLE_CAP:
+                raise NotImplementedError(f"num_beams={nb}, do_sample=True: top_k={top_k} is outside 1..{ops.SAMPLE_CAP} "
+                                          "(beam sampling draws on the device only)")
+            if V < 3:
+                raise ValueError(f"beam sampling needs a vocabulary of at least 3 tokens, got {V}")
+            if V > 32768 or V % 4:
+                raise NotImplementedError(f"beam sampling takes a vocabulary of at most 32768 tokens, a multiple of 4, got {V}")
         stats = dict(steps=0, num_beams=nb, graph_replays=0, finished_hypotheses=0, sequences_scores=None, lengths=None)
+        if sampled:
+            stats.update(beam_sampled_steps=0, beam_host_steps=0)
         self.last_generate_stats = stats
         stats.update(self._prepare_decode_weights(R))
-        ws = self._decode_workspace(R, S0 + max_new_tokens, 1.0, num_beams=nb)
+        # the sampled step is another launch sequence (and `draw` is baked into it): a workspace and a graph of its own
+        ws = self._decode_workspace(R, S0 + max_new_tokens, 1.0, dev_sample=sampled and draw, penalty=sampled and not draw, num_beams=nb)
         caches, T_cap, C = ws["caches"], ws["T"], 2 * self.D
         dev = self.dev
 
@@ -680,17 +712,54 @@ class LlamaDecode:
             rec = ws["brec"].cpu()                                   # the one device->host copy of the step
             return rec[0].view(F32).numpy().reshape(B, K), rec[1].numpy().reshape(B, K).astype(np.int64)
 
+        if sampled:
+            if "bsrec" not in ws:                                    # the record: acc [B, K] f32 | flat [B, K] | overflow flag [B]
+                ws.update(bsrec=torch.zeros((2 * B * K + B,), dtype=torch.int32, device=dev),
+                          part_k=torch.empty((R * K,), dtype=F32, device=dev), part_f=torch.zeros((R,), dtype=torch.int32, device=dev))
+            bsrec = ws["bsrec"]
+            rec_s, rec_i, rec_f = bsrec[:B * K].view(F32), bsrec[B * K:2 * B * K], bsrec[2 * B * K:]
+            ws["prm"].copy_(torch.tensor([inv_temp, float(top_p), float(top_k), pen], dtype=F32))
+            ws["seen"].zero_()                                       # generated ids only: the prompt is embeddings
+            seed = int(torch.randint(0, 2**63 - 1, (1,), generator=generator)) if draw else 0
+            ws["seed"].fill_(seed)
+            ws["step"].zero_()
+
+            def sample_topk(logits, ban, t_add, step=None, **adv):
+                ops.beam_sample_topk(logits, ws["bscore"], ws["part_k"], ws["part_s"], ws["part_i"], ws["part_f"], rec_s, rec_i, rec_f,
+                                     B, nb, ban_id=ban, draw=draw, params=ws["prm"], seed=ws["seed"], seen=ws["seen"], step=step,
+                                     t_add=t_add, **adv)
+
+            def read_sampled(logits_of, ban):                        # the sampled step's record, the items' flags behind it
+                rec = bsrec.cpu()
+                top_s, top_i = rec[:B * K].view(F32).numpy().reshape(B, K).copy(), rec[B * K:2 * B * K].numpy().reshape(B, K).astype(np.int64)
+                stats["beam_sampled_steps"] += 1
+                for b in np.nonzero(rec[2 * B * K:].numpy())[0]:     # a tied top-k set past the device's cap: the host's rule
+                    t = stats["steps"]                               # tokens generated so far = the index of this one
+                    acc, flat, _ = beam_sample_select(logits_of()[b * nb:(b + 1) * nb].cpu().numpy(), h_sc[b * nb:(b + 1) * nb],
+                                                      run_seqs[b], ban, inv_temp, top_k, float(top_p), pen, seed, t, int(b), draw)
+                    top_s[b], top_i[b] = acc, flat
+                    stats["beam_host_steps"] += 1
+                return top_s, top_i
+
         # ---- prefill at B rows into rows b * nb, then broadcast the prompt's keys / values to the other beams
         logits0 = self._prefill(inputs_embeds, [c[::nb] for c in caches])
-        ws["bscore"].zero_()                                         # beam 0's running score; one row per item here
-        ops.beam_topk(logits0, ws["bscore"], ws["part_s"], ws["part_i"], ws["brec"][0].view(F32), ws["brec"][1], B, nb,
-                      ban_id=eos_id if 0 < min_length else -1)
+        ban0 = eos_id if 0 < min_length else -1
+        if sampled:                                                  # the prompt's row nb times, HF's initial scores (0, -1e9, ...)
+            logits0 = logits0.repeat_interleave(nb, 0)
+            h_sc[:] = NEG
+            h_sc[::nb] = 0.0
+            ws["bscore"].copy_(torch.from_numpy(h_sc))
+            sample_topk(logits0, ban0, 0)
+        else:
+            ws["bscore"].zero_()                                     # beam 0's running score; one row per item here
+            ops.beam_topk(logits0, ws["bscore"], ws["part_s"], ws["part_i"], ws["brec"][0].view(F32), ws["brec"][1], B, nb,
+                          ban_id=ban0)
         if self.layers:
             # a range of its own: ws["lo"] holds the previous call's S0 when the workspace is reused
             bsrc = torch.arange(B, dtype=torch.int32).repeat_interleave(nb).mul_(nb).to(dev)
             span = torch.tensor([0, S0], dtype=torch.int32).to(dev)
             ops.beam_reorder_kv(ws["table"], len(caches), B, nb, T_cap, C, bsrc, span[:1], span[1:])
-        going = select(*read_record(), 1)
+        going = select(*(read_sampled(lambda: logits0, ban0) if sampled else read_record()), 1)
 
         # ---- token steps
         ws["pos"].fill_(S0)
@@ -699,6 +768,11 @@ class LlamaDecode:
 
         def token_step(ban):
             ops.beam_reorder_kv(ws["table"], len(caches), B, nb, T_cap, C, ws["src"], ws["lo"], ws["pos"])
+            if sampled:                                              # the bitmaps follow their hypotheses; the fed token joins
+                ops.beam_seen_update(ws["seen"], ws["src"], ws["ids"], B, nb, V)
+                self._step_logits(ws)
+                sample_topk(ws["logits"], ban, 1, step=ws["step"], pos=ws["pos"], kvlen=ws["kvlen"])   # token s draws Philox step s
+                return
             self._step_logits(ws)
             ops.beam_topk(ws["logits"], ws["bscore"], ws["part_s"], ws["part_i"], ws["brec"][0].view(F32), ws["brec"][1], B, nb,
                           ban_id=ban, pos=ws["pos"], kvlen=ws["kvlen"])
@@ -706,9 +780,10 @@ class LlamaDecode:
         gen = 1                                                      # tokens generated so far
         while going and gen < max_new_tokens:
             ws["bupd"].copy_(ws["bupd_host"], non_blocking=True)    # ids | src | running scores: one host->device copy
-            self._launch_step(ws, token_step, eos_id if gen < min_length else -1, use_graph, stats)
+            ban = eos_id if gen < min_length else -1
+            self._launch_step(ws, token_step, ban, use_graph, stats)
             gen += 1
-            going = select(*read_record(), gen)
+            going = select(*(read_sampled(lambda: ws["logits"], ban) if sampled else read_record()), gen)
 
         seqs = [fin_seqs[b][i] for b in range(B) for i in range(nrs)]
         scores = torch.from_numpy(np.array([fin_scores[b, i] for b in range(B) for i in range(nrs)], dtype=np.float32))

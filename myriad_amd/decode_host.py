@@ -1,11 +1,13 @@
 """The host side of the decode loops, on plain Python values: nothing here sees a device or the HIP library, so a scripted run can
 drive every class.  The slot engine's bookkeeping (SlotScheduler), its refill and turn planners (RefillPlanner, TurnPlanner), the
 chat pool's session table (SessionTable), the per-request random streams (seeded_requests), the replay of a known run
-(replay_slot_run), the split-KV rules with their measurements, and the host draw of one row (_host_draw)."""
+(replay_slot_run), the split-KV rules with their measurements, the host draw of one row (_host_draw) and the beam-sampling
+step of one item (beam_sample_select)."""
 from __future__ import annotations
 
 from typing import Optional
 
+import numpy as np
 import torch
 
 
@@ -27,6 +29,74 @@ def _host_draw(logits_row: torch.Tensor, ban: int, inv_temp: float, top_k: int, 
     srt = srt.masked_fill(remove, float("-inf"))
     probs = torch.zeros_like(lg).scatter(0, idx, srt.softmax(-1))
     return int(torch.multinomial(probs, 1, generator=generator))
+
+
+def _philox_x0(seed: int, t: int, flat, item: int):
+    """The first word of Philox4x32-10 with key = the 64-bit seed and counter (t, flat[i], item, 1), for an array of flat indices
+    (uint64 arithmetic on 32-bit values, so no product overflows)."""
+    m32 = np.uint64(0xFFFFFFFF)
+    c0 = np.full(len(flat), int(t) & 0xFFFFFFFF, dtype=np.uint64)
+    c1 = np.asarray(flat, dtype=np.uint64) & m32
+    c2 = np.full(len(flat), int(item) & 0xFFFFFFFF, dtype=np.uint64)
+    c3 = np.ones(len(flat), dtype=np.uint64)
+    k0, k1 = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ np.uint64(k0), p1 & m32, (p0 >> s32) ^ c3 ^ np.uint64(k1), p0 & m32
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c0
+
+
+def beam_sample_select(logits, scores, seen_ids, ban: int, inv_temp: float, top_k: int, top_p: float, penalty: float, seed: int,
+                       t: int, item: int, draw: bool = True):
+    """One item's beam-sampling step on the host, from its nb rows of fp32 logits [nb, V], their running scores [nb] and the ids
+    each hypothesis generated (seen_ids[j]): the rule of mh_beam_sample_topk (include/myriad_hip.h) in numpy, what the decode loop
+    runs for an item whose device step raised the overflow flag.  Returns (acc [K], flat [K], key [K]), K = 2 * nb, in the
+    record's order (key desc, flat asc).  Arithmetic in fp32 in the kernel's operation order; only the top-p masses are summed in
+    fp64.  With draw = False the temperature, the cuts and the noise are left out (key = acc)."""
+    x = np.asarray(logits, dtype=np.float32)
+    nb, V = x.shape
+    f32, ninf = np.float32, np.float32(-np.inf)
+    accs, flats = [], []
+    with np.errstate(all="ignore"):
+        for j in range(nb):
+            r = x[j]
+            mx = np.max(np.where(np.isnan(r), ninf, r))
+            lp = (r - mx) - np.log(np.sum(np.exp(r - mx), dtype=f32))
+            lp = np.where(np.isnan(lp), ninf, lp).astype(f32)
+            ids = sorted({int(i) for i in seen_ids[j] if 0 <= int(i) < V})
+            if penalty != 1.0 and ids:
+                v = lp[ids]
+                lp[ids] = np.where(v < 0, v * f32(penalty), v / f32(penalty))
+            if ban >= 0:
+                lp[ban] = ninf
+            if draw:
+                w = lp * f32(inv_temp)
+                w = np.where(np.isnan(w), ninf, w).astype(f32)
+                k = min(max(int(top_k), 2), V)
+                thr = np.partition(w, V - k)[V - k]
+                tok = np.nonzero((w >= thr) & np.isfinite(w))[0]
+                tok = tok[np.lexsort((tok, -w[tok]))]                # (w desc, id asc)
+                if top_p < 1.0 and len(tok) > 2:
+                    p = np.exp(w[tok].astype(np.float64) - float(w[tok[0]]))
+                    cum = np.cumsum(p)
+                    tok = tok[:max(int(np.sum(cum - p < top_p * cum[-1])), 2)]
+            else:
+                w, tok = lp, np.arange(V)
+            a = (w[tok] + f32(scores[j])).astype(f32)
+            accs.append(np.where(np.isnan(a), ninf, a))
+            flats.append(j * V + tok.astype(np.int64))
+        acc, flat = np.concatenate(accs), np.concatenate(flats)
+        if draw:
+            x0 = _philox_x0(seed, t, flat, item)
+            u = ((x0 >> np.uint64(9)).astype(f32) + f32(0.5)) * f32(1.0 / 8388608.0)
+            key = (acc + (-np.log(-np.log(u)))).astype(f32)
+            key = np.where(np.isnan(key), ninf, key)
+        else:
+            key = acc
+    order = np.lexsort((flat, -key))[:2 * nb]
+    return acc[order], flat[order], key[order]
 
 
 # The chat session's token step uses the split-KV attention kernel (mh_attn_decode_rope_split) when the single-workgroup kernel

@@ -113,6 +113,9 @@ class LlamaHIP(LlamaDecode):
         # do_sample with 1 <= top_k <= 1024 draws on the device inside the token step (mh_sample_rows) instead of on the host;
         # off by default until it has been measured against the host draw (tools/decode_bench.py --sample)
         self.device_sampling = os.environ.get("MYRIAD_DEVICE_SAMPLING", "0") != "0"
+        # num_beams > 1 with do_sample (HF's beam-search multinomial sampling) or a repetition penalty: the beam step selects with
+        # mh_beam_sample_topk and carries the seen-id bitmaps (mh_beam_seen_update); off, generate() refuses both as before
+        self.beam_sampling = os.environ.get("MYRIAD_BEAM_SAMPLING", "0") != "0"
         self.last_layer_rows = os.environ.get("MYRIAD_LAST_LAYER_ROWS", "1") != "0"
         # the packed token step streams FP8 (e4m3fn, one fp32 scale per output row) copies of the decoder matrices instead of
         # the bf16 ones (ops.gemv_pack_fp8; half the bytes, weight rounding the only new error); off by default, the attribute

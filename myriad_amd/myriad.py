@@ -1305,7 +1305,10 @@ class MyriadHIP(nn.Module):
         rep_pen = 1.0 if rep_pen is None else float(rep_pen)
         if not rep_pen > 0:
             raise ValueError(f"generate(repetition_penalty={rep_pen}): must be > 0")
-        if rep_pen != 1.0 and not self.llama.device_sampling:
+        beams = kw.get("num_beams")
+        # the beam path's own switch (a model without the attribute has it off)
+        beam_sampling = bool(getattr(self.llama, "beam_sampling", False) and isinstance(beams, numbers.Real) and beams > 1)
+        if rep_pen != 1.0 and not self.llama.device_sampling and not beam_sampling:
             # opt-in like the device sampler itself: with the switch off generate() keeps its earlier contract and refuses it
             raise NotImplementedError(f"generate(repetition_penalty={rep_pen}) needs the device sampling switch "
                                       "(MYRIAD_DEVICE_SAMPLING=1 or model.llama.device_sampling = True)")
@@ -1317,12 +1320,17 @@ class MyriadHIP(nn.Module):
         num_beams = int(num_beams)
         beam_kw = {}
         if num_beams > 1:
-            if do_sample:
-                raise NotImplementedError(f"generate(num_beams={num_beams}, do_sample=True): beam sampling is not implemented")
-            if rep_pen != 1.0:
-                raise NotImplementedError(f"generate(num_beams={num_beams}, repetition_penalty={rep_pen}) is not implemented")
+            if do_sample and not beam_sampling:
+                raise NotImplementedError(f"generate(num_beams={num_beams}, do_sample=True): beam sampling needs its switch "
+                                          "(MYRIAD_BEAM_SAMPLING=1 or model.llama.beam_sampling = True)")
+            if rep_pen != 1.0 and not beam_sampling:
+                raise NotImplementedError(f"generate(num_beams={num_beams}, repetition_penalty={rep_pen}) needs the beam sampling "
+                                          "switch (MYRIAD_BEAM_SAMPLING=1 or model.llama.beam_sampling = True)")
             if num_beams > ops.BEAM_MAX:
                 raise NotImplementedError(f"generate(num_beams={num_beams}): at most {ops.BEAM_MAX} beams on the HIP decode path")
+            if do_sample and not 1 <= top_k <= ops.SAMPLE_CAP:
+                raise NotImplementedError(f"generate(num_beams={num_beams}, do_sample=True, top_k={top_k}): beam sampling draws on "
+                                          f"the device only, top_k in 1..{ops.SAMPLE_CAP}")
             lp = kw.pop("length_penalty", 1.0)
             nrs = kw.pop("num_return_sequences", 1)
             es = kw.pop("early_stopping", False)
@@ -1332,6 +1340,8 @@ class MyriadHIP(nn.Module):
                 raise ValueError(f"generate(num_return_sequences={nrs}) has to be between 1 and num_beams={num_beams}")
             if beam_kw["early_stopping"] not in (True, False, "never"):
                 raise ValueError(f"generate(early_stopping={es!r}): True, False or 'never'")
+            if beam_sampling:                              # switch off: beam_generate is called with today's arguments
+                beam_kw.update(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=rep_pen)
         for k, neutral in (("num_beams", 1), ("length_penalty", 1), ("num_return_sequences", 1)):
             v = kw.pop(k, neutral)
             if v not in (neutral, None):
@@ -1373,7 +1383,10 @@ class MyriadHIP(nn.Module):
         [B * num_return_sequences, L], item-major, best first, and last_generate_stats gains num_beams, sequences_scores,
         finished_hypotheses and graph_replays.  Beam search applies the stop sequences per hypothesis, greedy / sampled decoding
         keeps the reference's row-0 rule.  Refused with beams: do_sample (beam sampling), repetition_penalty != 1 and
-        num_beams > 8.  Without beams, length_penalty / num_return_sequences other than 1 raise NotImplementedError and
+        num_beams > 8.  With `self.llama.beam_sampling` (MYRIAD_BEAM_SAMPLING=1, off by default) num_beams > 1 also takes
+        do_sample, temperature, top_k (1 .. 1024 when sampling), top_p, repetition_penalty and generator: HF's beam-search
+        multinomial sampling with its processor chain on the log-probs, drawn on the device and reproducible per seed
+        (LlamaHIP.beam_generate); last_generate_stats gains beam_sampled_steps and beam_host_steps.  Without beams, length_penalty / num_return_sequences other than 1 raise NotImplementedError and
         early_stopping is an unknown argument, as before.
 
         output_scores=True (opt-in, with watch_ids = up to 8 token ids) adds "token_logprobs" [B, L] f32, the log-probability of
@@ -1403,6 +1416,8 @@ class MyriadHIP(nn.Module):
             max_new = max(1, max_len - emb.shape[1])
         self.llama.decode_lora_version = self.store.version    # decode_merge_lora re-merges only when the LoRA weights moved
         if num_beams > 1:
+            if "do_sample" in beam_kw:                     # the beam sampling switch is on: the draw's generator goes with it
+                beam_kw = dict(beam_kw, generator=generator)
             ids = self.llama.beam_generate(emb, num_beams, max_new_tokens=max_new, stop_ids=stops, eos_id=eos_id,
                                            min_length=min_length, **beam_kw)
         else:

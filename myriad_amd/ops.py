@@ -1395,6 +1395,63 @@ def beam_reorder_kv(cache_table: torch.Tensor, L: int, B: int, nb: int, T_cap: i
                "mh_beam_reorder_kv")
 
 
+def beam_sample_topk(logits: torch.Tensor, scores: torch.Tensor, part_k, part_a, part_i, part_f, out_s, out_i, out_f, B: int, nb: int,
+                     ban_id: int = -1, draw: bool = True, params=None, seed=None, seen=None, step=None, t_add: int = 0, out_k=None,
+                     pos=None, kvlen=None):
+    """beam_topk's selection with HF's processor chain on the log-probs and, with `draw`, beam-search multinomial sampling (the
+    rule is include/myriad_hip.h's): logits [B*nb, V] (nb rows per item), params = f32 (inv_temp, top_p, top_k, penalty) and seed =
+    one int64 on the device, seen = int32 [B*nb, ceil(V/32)] bitmaps or None (no penalty), Philox step t = step[0] + t_add (t_add
+    alone without `step`).  Per item the top 2*nb by (key desc, flat asc): out_s = acc, out_i = flat, out_k = key (optional),
+    out_f [B] = 1 where the host has to redo the item.  part_k / part_a / part_i: scratch of B*nb*2*nb entries, part_f of B*nb.
+    With pos / kvlen (both or neither) those rows advance by one, and step[0] with them.  A buffer of the wrong type or too short
+    for what the kernels index is refused here, before any launch."""
+    _chk2d(logits, F32, "beam_sample_topk: logits")
+    R, V = logits.shape
+    if B <= 0 or nb <= 0 or R != B * nb:
+        raise _lib.MyriadHipError(f"beam_sample_topk: {R} logits rows are not B={B} items of nb={nb} rows")
+    i32, K = torch.int32, 2 * nb
+    for name, t, dtype, need in (("scores", scores, F32, R), ("part_k", part_k, F32, R * K), ("part_a", part_a, F32, R * K),
+                                 ("part_i", part_i, i32, R * K), ("part_f", part_f, i32, R), ("out_s", out_s, F32, B * K),
+                                 ("out_i", out_i, i32, B * K), ("out_f", out_f, i32, B)):
+        _chk_flat(t, dtype, need, f"beam_sample_topk: {name}")
+    if out_k is not None:
+        _chk_flat(out_k, F32, B * K, "beam_sample_topk: out_k")
+    if draw or seen is not None:
+        _chk_flat(params, F32, 4, "beam_sample_topk: params")
+    if draw:
+        _chk_flat(seed, torch.long, 1, "beam_sample_topk: seed")
+    if seen is not None:
+        _chk_flat(seen, i32, R * ((V + 31) // 32), "beam_sample_topk: seen")
+    if step is not None:
+        _chk_flat(step, i32, 1, "beam_sample_topk: step")
+    if (pos is None) != (kvlen is None):
+        raise _lib.MyriadHipError("beam_sample_topk: pos and kvlen advance together: give both or neither")
+    n_adv = 0
+    if pos is not None:
+        n_adv = pos.numel()
+        _chk_flat(pos, i32, n_adv, "beam_sample_topk: pos")
+        _chk_flat(kvlen, i32, n_adv, "beam_sample_topk: kvlen")
+        if kvlen.numel() != n_adv:
+            raise _lib.MyriadHipError(f"beam_sample_topk: pos has {n_adv} rows and kvlen {kvlen.numel()}")
+    _lib.check(_L().mh_beam_sample_topk(_p(logits), logits.stride(0), _p(scores), _p(seen), _p(part_k), _p(part_a), _p(part_i),
+                                        _p(part_f), _p(out_s), _p(out_i), _p(out_f), _p(out_k), B, nb, V, int(ban_id), int(bool(draw)),
+                                        _p(params), _p(seed), _p(step), int(t_add), _p(pos), _p(kvlen), n_adv, _s()),
+               "mh_beam_sample_topk")
+    return out_s, out_i, out_f
+
+
+def beam_seen_update(seen: torch.Tensor, src: torch.Tensor, ids: torch.Tensor, B: int, nb: int, V: int):
+    """In place: seen[r] = seen[src[r]] | bit(ids[r]) over the int32 [B*nb, ceil(V/32)] seen-id bitmaps; src int32 (parents within
+    r's item, as beam_reorder_kv takes them), ids int64, both read by the kernel (capturable)."""
+    if B <= 0 or nb <= 0 or V <= 0:
+        raise _lib.MyriadHipError(f"beam_seen_update: B={B}, nb={nb}, V={V} must be positive")
+    _chk_flat(seen, torch.int32, B * nb * ((V + 31) // 32), "beam_seen_update: seen")
+    _chk_flat(src, torch.int32, B * nb, "beam_seen_update: src")
+    _chk_flat(ids, torch.long, B * nb, "beam_seen_update: ids")
+    _lib.check(_L().mh_beam_seen_update(_p(seen), _p(src), _p(ids), B, nb, V, _s()), "mh_beam_seen_update")
+    return seen
+
+
 # --------------------------------------------------------------------------- conv stack pieces
 def im2col(x_nhwc: torch.Tensor, kh: int, kw: int, pad: int, bias_col: bool = True):
     """[B*OH*OW, Kpad] bf16 patches, (ky, kx, c) order; with bias_col a column of ones follows the K patch columns (the bias

@@ -3,8 +3,9 @@
 python tools/decode_bench.py [--batch 1] [--new 32] [--sample] [--penalty P] [--modes greedy,host,device] [--repeats 5]
 --sample: the chat call's do_sample=True, top_p=0.9, top_k=50 (drawn on the device when MYRIAD_DEVICE_SAMPLING=1, else on the
 host); --modes times several decodes in one process, interleaved per repeat: greedy, host (sampled, host draw), device (sampled,
-device draw), beam (num_beams = --beams, which also times greedy at batch * beams: the same row count); --penalty adds
-repetition_penalty to every mode but beam.  --weights bf16,fp8,fp4 times each mode with the token step streaming bf16, FP8
+device draw), beam (num_beams = --beams, which also times greedy at batch * beams: the same row count), beam_sample (beam-search
+multinomial sampling, top_p=0.9, top_k=50, behind the beam sampling switch); --penalty adds repetition_penalty to every mode but
+beam.  --weights bf16,fp8,fp4 times each mode with the token step streaming bf16, FP8
 and MXFP4 weight copies (LlamaHIP.decode_fp8 / decode_fp4), interleaved in the same way; without it the kind is the one
 MYRIAD_DECODE_FP8 / MYRIAD_DECODE_FP4 set.  --merge 0,1 (with --lora 1)
 times each of those with the bordered LoRA qkv product and with the LoRA merged into the step's qkv copy
@@ -406,6 +407,7 @@ if a.slots or len(slot_counts) > 1 or a.scores:
 smp = make_samples(B)
 smp_rows = make_samples(B * a.beams) if "beam" in modes else None
 default_dev = model.llama.device_sampling
+default_beam_sampling = model.llama.beam_sampling
 default_fp8, default_fp4 = model.llama.decode_fp8, model.llama.decode_fp4
 default_merge = model.llama.decode_merge_lora
 
@@ -414,6 +416,9 @@ def run(n, mode, kind=None, merge=None):
     kw, sm = {}, smp
     if mode == "beam":
         kw = dict(num_beams=a.beams, early_stopping="never")    # no early stop: every run decodes n tokens
+    elif mode == "beam_sample":                                 # the chat call's knobs; the penalty rides in the same step
+        kw = dict(num_beams=a.beams, early_stopping="never", do_sample=True, top_p=0.9, top_k=50,
+                  generator=torch.Generator().manual_seed(0))
     elif mode.startswith("greedy_x"):
         sm = smp_rows
     elif mode != "greedy":
@@ -421,6 +426,7 @@ def run(n, mode, kind=None, merge=None):
     if mode != "beam":
         kw["repetition_penalty"] = a.penalty
     model.llama.device_sampling = {"host": False, "device": True}.get(mode, default_dev)
+    model.llama.beam_sampling = mode == "beam_sample" or default_beam_sampling
     model.llama.decode_fp8 = default_fp8 if kind is None else kind == "fp8"
     model.llama.decode_fp4 = default_fp4 if kind is None else kind == "fp4"
     model.llama.decode_merge_lora = default_merge if merge is None else bool(merge)
@@ -440,7 +446,7 @@ for _ in range(a.repeats):
         t_short, _ = run(a.new // 4, m, w, mg)
         t_long, out = run(a.new, m, w, mg)
         n_long, n_short = out["token_ids"].shape[1], a.new // 4
-        if m == "beam":
+        if m in ("beam", "beam_sample"):
             n_long = model.last_generate_stats["steps"]       # hypotheses may end before the last step; the step count does not
         res[(m, w, mg)].append(((t_long - t_short) / (n_long - n_short), t_long, n_long, dict(model.last_generate_stats)))
 for m, w, mg in runs:
@@ -449,7 +455,10 @@ for m, w, mg in runs:
     per_tok = ts[len(ts) // 2]                        # prefill / vision cancel: pure single-token decode steps (median)
     extra = (f" [{m}: device-drawn rows {st.get('device_sampled_rows', 0)}, host-drawn {st.get('host_sampled_rows', 0)}, "
              f"graph replays {st.get('graph_replays', 0)}]" if m != "greedy" or a.penalty != 1.0 else "")
-    rows = B * a.beams if m in ("beam", "greedy_x%d" % a.beams) else B
+    if m == "beam_sample":
+        extra = (f" [beam_sample: sampled steps {st['beam_sampled_steps']}, item-steps redone on the host {st['beam_host_steps']}, "
+                 f"graph replays {st['graph_replays']}]")
+    rows = B * a.beams if m in ("beam", "beam_sample", "greedy_x%d" % a.beams) else B
     wb = st["decode_weight_bytes"]
     lora_tag = (" +LoRA merged" if st.get("lora_merged") else " +LoRA") if a.lora else ""
     print(f"batch {B} rows {rows}{lora_tag} {m} weights {st['decode_weights']}"
