@@ -682,6 +682,27 @@ int mh_zs_accumulate(const float* logits, float* mask_acc, float* map_acc, int B
 int mh_rowmax_skip(const float* scores, long lds, float* acc, long rows, int cols, int period, float w, mh_stream_t s);
 int mh_bilinear_ac(const float* in, float* out, int B, int h, int w, int H, int W, int one_minus, mh_stream_t s);
 
+/* K16b the one-shot head against a per-class reference bank (csrc/expert_bank.hip): the references of a class are encoded once
+ * and kept as L2-normalised bf16 patch rows, one contiguous [R_total, D] bank per tap; a sample names its class by the row range
+ * [bank_off[b], bank_off[b] + bank_rows[b]) (int32 device arrays of B entries; bank_rows[b] >= 1 and the range inside the bank
+ * are the caller's contract).
+ * mh_bank_sim_max (one launch per tap, whole batch): the query row of sample b, patch l is row b * q_sample_rows + q_row0 + l
+ *   of q [*, D] bf16 (q_row0 = 1, q_sample_rows = 1 + L skips each sample's class token); part[(b * max_chunks + c) * L + l] =
+ *   max_j <q[b, l], bank[bank_off[b] + j]> over the rows j of chunk c (mh_bank_sim_chunk_rows() rows each, the last one
+ *   shorter), for c < ceil(bank_rows[b] / chunk rows); slots of later chunks are not written.  bf16 MFMA products, fp32
+ *   accumulation along D in one fixed ascending order; rows past a class's end are masked to -inf, never read from the
+ *   neighbouring class; the score matrix is never stored.  max_chunks >= the largest chunk count in the batch (workgroups past
+ *   a sample's last chunk exit at once).  Refuses D % 32, L < 1, B < 1, max_chunks < 1, q_sample_rows < q_row0 + L and null
+ *   pointers with MH_ERR_ARG before any launch.
+ * mh_bank_sim_finish (one launch): part [T, B, max_chunks, L = h h] of T taps; sim[b, l] = sum over taps in ascending order of
+ *   w * (max over the sample's chunks), as rowmax_skip accumulates it; simmask [B, h, h] = 1 - sim; amap [B, S, S] = 1 -
+ *   bilinear_ac(sim): both bit-equal to mh_bilinear_ac(sim, ..., one_minus = 1) at (h, h) and (S, S).  h <= 128, S <= 4096. */
+int mh_bank_sim_chunk_rows(void);
+int mh_bank_sim_max(const void* q, long q_row0, long q_sample_rows, const void* bank, const int* bank_off, const int* bank_rows,
+                    float* part, int B, int L, int D, int max_chunks, mh_stream_t s);
+int mh_bank_sim_finish(const float* part, const int* bank_rows, float* sim, float* simmask, float* amap, int T, int B,
+                       int max_chunks, int h, int S, float w, mh_stream_t s);
+
 /* ---- opaque context: library state the caller owns explicitly ------------------------------------------------
  * An mh_ctx holds (1) a split-K scratch record -- mh_ctx_set_workspace(ctx, NULL, ptr, bytes) the main scratch,
  * (ctx, stream, ptr, bytes) that of one more stream that may split K concurrently; library calls use the record of the context

@@ -8,6 +8,7 @@
 // fp32 arithmetic throughout; a two-way softmax is evaluated as sigmoid(l1 - l0), and interpolating the two logit planes
 // then taking the softmax equals the sigmoid of the interpolated difference (interpolation is linear).
 #include "common.h"
+#include "expert_map.h"
 
 #define EX_NT 256
 
@@ -109,22 +110,12 @@ __global__ __launch_bounds__(EX_NT) void rowmax_skip_kernel(const float* __restr
 __global__ void bilinear_ac_kernel(const float* __restrict__ in, float* __restrict__ out, int B, int h, int w_in, int H, int W,
                                    int one_minus) {
   const long total = (long)B * H * W;
-  // source position o (n_in - 1) / (n_out - 1) as one correctly rounded division of exact integers: o * fl(step) carries two
-  // roundings of a value up to n_in - 1, which a steep cell turns into the largest part of the output's error
-  const float dy = H > 1 ? (float)(H - 1) : 1.f, dx = W > 1 ? (float)(W - 1) : 1.f;
+  const float dy = bilinear_ac_div(H), dx = bilinear_ac_div(W);
   for (long it = blockIdx.x * (long)blockDim.x + threadIdx.x; it < total; it += (long)gridDim.x * blockDim.x) {
     const int b = (int)(it / ((long)H * W));
     const int rem = (int)(it - (long)b * H * W);
     const int oy = rem / W, ox = rem - oy * W;
-    const float fy = (float)(oy * (h - 1)) / dy, fx = (float)(ox * (w_in - 1)) / dx;
-    int y0 = (int)fy, x0 = (int)fx;
-    y0 = y0 < h - 1 ? y0 : (h > 1 ? h - 2 : 0);
-    x0 = x0 < w_in - 1 ? x0 : (w_in > 1 ? w_in - 2 : 0);
-    const int y1 = y0 + (h > 1), x1 = x0 + (w_in > 1);
-    const float wy = fy - y0, wx = fx - x0;
-    const float* ib = in + (long)b * h * w_in;
-    const float v = (1.f - wy) * ((1.f - wx) * ib[y0 * w_in + x0] + wx * ib[y0 * w_in + x1]) +
-                    wy * ((1.f - wx) * ib[y1 * w_in + x0] + wx * ib[y1 * w_in + x1]);
+    const float v = bilinear_ac_at(in + (long)b * h * w_in, h, w_in, oy, ox, dy, dx);   // expert_map.h
     out[it] = one_minus ? 1.f - v : v;
   }
 }

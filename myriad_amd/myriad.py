@@ -761,16 +761,25 @@ class MyriadHIP(nn.Module):
         """Optional in-model producer of the anomaly maps (`self.vision_expert` of the reference, myriad.py:83-90):
         a `myriad_amd.vision_expert.VisionExpertHIP`.  With it attached, samples may carry `expert_text_feats`
         [B,2,C] (the cached per-class [normal, abnormal] text embeddings) and `ref_images` [B*k,3,224,224] instead of
-        ready-made maps; both map pairs then come from one trunk pass (myriad.py:331-345)."""
+        ready-made maps; both map pairs then come from one trunk pass (myriad.py:331-345).  `ref_bank`, a list of B class
+        names (what a loader passes as `scene`), stands in for `ref_images` once the classes are registered with the expert's
+        `add_references`; `expert_text_feats` is then optional and wins over the bank's text pairs."""
         self.vision_expert = expert
 
     def _maps_for(self, samples, key: str, image: torch.Tensor) -> torch.Tensor:
         if key in samples:
             return samples[key].to(self._dev, F32)
         expert = getattr(self, "vision_expert", None)
+        if expert is not None and "ref_images" not in samples and "ref_bank" in samples:
+            # class names instead of reference images: the classes were registered with expert.add_references()
+            (zs, _), (os_, _) = expert.forward_banked(image, list(samples["ref_bank"]), samples.get("expert_text_feats"))
+            samples["anomaly_maps"], samples["oneshot_anomaly_maps"] = zs, os_
+            return samples[key]
         if expert is None or "expert_text_feats" not in samples or "ref_images" not in samples:
             raise KeyError(f"samples['{key}'] is required (or attach_vision_expert() + samples['expert_text_feats'] and "
-                           "samples['ref_images']): the vision expert is an upstream producer (SURVEY 2.1 row 10)")
+                           "samples['ref_images']): the vision expert is an upstream producer (SURVEY 2.1 row 10); "
+                           "samples['ref_bank'], the B class names, stands in for ref_images once the classes are registered "
+                           "with add_references()")
         (zs, _), (os_, _) = expert.forward(image, samples["expert_text_feats"], samples["ref_images"])
         samples["anomaly_maps"], samples["oneshot_anomaly_maps"] = zs, os_      # both are computed once per batch
         return samples[key]

@@ -1599,6 +1599,70 @@ def bilinear_ac(x: torch.Tensor, H: int, W: int, one_minus: bool = False):
     return out
 
 
+def bank_sim_chunks(rows: int) -> int:
+    """Chunks bank_sim_max splits a class of `rows` bank rows into (a function of the row count alone)."""
+    ch = _L().mh_bank_sim_chunk_rows()
+    return (int(rows) + ch - 1) // ch
+
+
+def bank_sim_max(q: torch.Tensor, bank: torch.Tensor, ranges, L: int, q_row0: int = 0, q_sample_rows: Optional[int] = None,
+                 out: Optional[torch.Tensor] = None, dev_ranges=None):
+    """One tap of the banked one-shot head for a whole batch.  q [*, D] bf16: the query row of sample b, patch l is row
+    b * q_sample_rows + q_row0 + l (q_row0 = 1, q_sample_rows = 1 + L skips the class tokens); bank [R, D] bf16; ranges: the B
+    host pairs (offset, rows) of each sample's class in the bank.  Returns (part [B, max_chunks, L] f32, (bank_off, bank_rows)
+    int32 device arrays): part[b, c] is the max over chunk c of sample b's rows, written for c < bank_sim_chunks(rows_b) only.
+    `dev_ranges`: the device arrays of an earlier call with the same ranges (the other taps of a batch)."""
+    for t, name in ((q, "bank_sim_max.q"), (bank, "bank_sim_max.bank")):
+        _chk2d(t, BF16, name)
+        if not t.is_contiguous():
+            raise _lib.MyriadHipError(f"{name}: need a contiguous tensor, got strides {t.stride()}")
+    ranges = [(int(o), int(r)) for o, r in ranges]
+    B, D, R = len(ranges), q.shape[1], bank.shape[0]
+    if q_sample_rows is None:
+        q_sample_rows = q_row0 + L
+    if bank.shape[1] != D:
+        raise _lib.MyriadHipError(f"bank_sim_max: q has D = {D}, bank has D = {bank.shape[1]}")
+    if B < 1 or L < 1 or q_row0 < 0 or q_sample_rows < q_row0 + L or (B - 1) * q_sample_rows + q_row0 + L > q.shape[0]:
+        raise _lib.MyriadHipError(f"bank_sim_max: {B} samples of rows [{q_row0}, {q_row0 + L}) at stride {q_sample_rows} "
+                                  f"do not fit q's {q.shape[0]} rows")
+    for b, (o, r) in enumerate(ranges):
+        if r < 1 or o < 0 or o + r > R:
+            raise _lib.MyriadHipError(f"bank_sim_max: sample {b} has the bank range [{o}, {o + r}) of a bank of {R} rows "
+                                      "(at least one row, inside the bank)")
+    max_chunks = max(bank_sim_chunks(r) for _, r in ranges)
+    if dev_ranges is None:
+        both = h2d(torch.tensor([[o for o, _ in ranges], [r for _, r in ranges]], dtype=torch.int32), q.device)
+        dev_ranges = (both[0], both[1])
+    if out is None:
+        out = torch.empty((B, max_chunks, L), dtype=F32, device=q.device)
+    elif out.dtype != F32 or tuple(out.shape) != (B, max_chunks, L) or not out.is_contiguous():
+        raise _lib.MyriadHipError(f"bank_sim_max.out: need contiguous f32 {(B, max_chunks, L)}, got {out.dtype} {tuple(out.shape)}")
+    _lib.check(_L().mh_bank_sim_max(_p(q), q_row0, q_sample_rows, _p(bank), _p(dev_ranges[0]), _p(dev_ranges[1]), _p(out), B, L,
+                                    D, max_chunks, _s()), "mh_bank_sim_max")
+    return out, dev_ranges
+
+
+def bank_sim_finish(part: torch.Tensor, bank_rows: torch.Tensor, S: int, w: Optional[float] = None):
+    """part [T, B, max_chunks, h*h] f32 (bank_sim_max's output of T taps), bank_rows [B] int32 (device) ->
+    (sim [B, h, h] = sum_t w * max over chunks (w: 1 / T), simmask [B, h, h] = 1 - sim, amap [B, S, S] = 1 - bilinear_ac(sim))."""
+    if part.dtype != F32 or not part.is_cuda or part.dim() != 4 or not part.is_contiguous():
+        raise _lib.MyriadHipError(f"bank_sim_finish.part: need contiguous cuda f32 [T, B, chunks, L], got {part.dtype} "
+                                  f"{tuple(part.shape)}")
+    T, B, max_chunks, L = part.shape
+    h = int(round(L ** 0.5))
+    if h * h != L:
+        raise _lib.MyriadHipError(f"bank_sim_finish: L = {L} patches are not a square grid")
+    if bank_rows.dtype != torch.int32 or not bank_rows.is_cuda or bank_rows.numel() != B or not bank_rows.is_contiguous():
+        raise _lib.MyriadHipError(f"bank_sim_finish.bank_rows: need {B} contiguous cuda int32, got {bank_rows.dtype} "
+                                  f"{tuple(bank_rows.shape)}")
+    sim = torch.empty((B, h, h), dtype=F32, device=part.device)
+    simmask = torch.empty((B, h, h), dtype=F32, device=part.device)
+    amap = torch.empty((B, S, S), dtype=F32, device=part.device)
+    _lib.check(_L().mh_bank_sim_finish(_p(part), _p(bank_rows), _p(sim), _p(simmask), _p(amap), T, B, max_chunks, h, S,
+                                       float(1.0 / T if w is None else w), _s()), "mh_bank_sim_finish")
+    return sim, simmask, amap
+
+
 def gemm_residual_rmsnorm(a: torch.Tensor, b: torch.Tensor, residual: torch.Tensor, norm_w: torch.Tensor, eps: float,
                           y_out: Optional[torch.Tensor] = None):
     """(h, y): h = a @ b^T + residual (f32), y = rmsnorm(h) * norm_w (bf16; y_out may be a [M, N] view of a wider buffer).

@@ -15,7 +15,9 @@ MI355X mapping: the repeated-frame Conv3d is one 14x14 patch GEMM with the two t
 table rides the residual epilogue); blocks are LN(fp32->bf16) -> qkv GEMM(+bias) -> fused attention (head_dim 80, padded to 96
 in LDS) -> out_proj GEMM(+bias +fp32 residual) -> LN -> fc1 GEMM(+bias +erf-GELU) -> fc2 GEMM(+bias +residual) -- the same
 kernels as the EVA encoder; the query x reference similarity is one bf16 MFMA GEMM per sample and tap on L2-normalised
-tokens, followed by a row-max; everything else is the small fp32 kernels of csrc/expert.hip.
+tokens, followed by a row-max; everything else is the small fp32 kernels of csrc/expert.hip.  With the references of a class
+registered once (`add_references`), the one-shot head is csrc/expert_bank.hip instead: one MFMA launch per tap for the whole
+batch against the class's stored rows, and one finishing launch.
 """
 from __future__ import annotations
 
@@ -24,6 +26,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import ops
+from .expert_bank import BankIndex
 
 BF16, F32 = torch.bfloat16, torch.float32
 PRE, TRK, HEAD = "modality_preprocessors.vision.", "modality_trunks.vision.", "modality_heads.vision."
@@ -121,6 +124,10 @@ class VisionExpertHIP:
             i += 1
         if self.dec_w and len(self.dec_w) != len(list(out_layers)):
             raise ValueError("one image_decoder.fc per tapped layer is required")
+        # the per-class reference bank (add_references): one contiguous [R, D] bf16 tensor per tap, rows located by the index
+        self._bank_index = BankIndex()
+        self._bank: List[torch.Tensor] = []
+        self._bank_text: Dict[str, torch.Tensor] = {}
 
     @torch.no_grad()
     def zero_shot(self, images: torch.Tensor, text_feats: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -186,6 +193,89 @@ class VisionExpertHIP:
         qt = [t[:B] for t in taps]
         rt = [t[B:] for t in taps]
         return self._zero_shot_from_taps(qt, text_feats), self._one_shot_from_taps(qt, rt)
+
+    # ------------------------------------------------------------------------------------------- per-class reference bank
+    # The references of a class never change (the reference model reads them from a fixed per-class list,
+    # adrefexpert_v2.py:137-160, and declares a `_ref_bank` it never fills): encode them once, keep their L2-normalised bf16
+    # patch rows, and let a batch name its classes.  A call then runs the trunk on the B queries only, and the head is one
+    # bank_sim_max launch per tap plus one bank_sim_finish (csrc/expert_bank.hip) instead of a GEMM and a row-max per sample
+    # and tap.
+    @torch.no_grad()
+    def add_references(self, name: str, ref_images: torch.Tensor, text_feats: Optional[torch.Tensor] = None,
+                       rot90: bool = False) -> None:
+        """Register the k normal references of class `name` (ref_images [k,3,224,224]): one trunk pass, every tap
+        L2-normalised as `one_shot` does, class-token rows dropped, the k*L bf16 rows appended to the tap's bank tensor.
+        `text_feats` [2, C], the class's [normal, abnormal] text pair, is kept beside them for `forward_banked`.  A name that is
+        registered already is replaced.
+        `rot90`: register each reference in its four exact quarter turns (torch.rot90 by 0, 1, 2, 3 quarter turns,
+        reference-major, then the turn), the row layout of `encode_image_for_one_shot_with_aug` (adrefexpert_v2.py:171-195).
+        The reference rotates through kornia's `rotate` (an interpolating warp with reflection padding); parity with that
+        interpolation is not claimed, only the exact quarter turns are."""
+        imgs = ref_images.to(self.dev, F32)
+        if imgs.dim() != 4 or imgs.shape[0] < 1:
+            raise ValueError(f"ref_images must be [k,3,224,224] with k >= 1, got {tuple(ref_images.shape)}")
+        if rot90:
+            imgs = torch.stack([torch.rot90(imgs, r, dims=(2, 3)) for r in range(4)], dim=1).reshape(-1, *imgs.shape[1:])
+        k = imgs.shape[0]
+        _, taps = self.trunk.forward(imgs.contiguous())
+        rows = []
+        for t in taps:
+            _, N, D = t.shape
+            rn, _ = ops.l2norm_rows(t.reshape(k * N, D), eps=1e-8)
+            rows.append(rn.view(k, N, D)[:, 1:].reshape(k * (N - 1), D))
+        if name in self._bank_index:
+            self.drop_references(name)
+        self._bank_index.append(name, rows[0].shape[0])
+        self._bank = [torch.cat([old, new], dim=0) for old, new in zip(self._bank, rows)] if self._bank else rows
+        if text_feats is not None:
+            self._bank_text[name] = text_feats.detach().to(self.dev, F32).reshape(2, -1).contiguous()
+
+    def drop_references(self, name: str) -> None:
+        """Forget a class: its rows are cut out of every tap's tensor (KeyError naming the class if it is not registered)."""
+        off, n = self._bank_index.remove(name)
+        self._bank_text.pop(name, None)
+        self._bank = [torch.cat([t[:off], t[off + n:]], dim=0) for t in self._bank] if len(self._bank_index) else []
+
+    def bank_classes(self) -> List[str]:
+        return self._bank_index.names()
+
+    def _one_shot_banked_from_taps(self, qt, names: Sequence[str]):
+        B, N, D = qt[0].shape
+        if len(names) != B:
+            raise ValueError(f"{B} images but {len(names)} class names")
+        ranges = [self._bank_index.lookup(n) for n in names]                         # KeyError names the missing class
+        L = N - 1
+        h = int(round(L ** 0.5))
+        part = torch.empty((len(qt), B, max(ops.bank_sim_chunks(r) for _, r in ranges), L), dtype=F32, device=self.dev)
+        dev_ranges = None
+        for i, (q, bank) in enumerate(zip(qt, self._bank)):
+            qn, _ = ops.l2norm_rows(q.reshape(B * N, D), eps=1e-8)                    # cosine_similarity operands
+            _, dev_ranges = ops.bank_sim_max(qn, bank, ranges, L, 1, N, out=part[i], dev_ranges=dev_ranges)
+        _, simmask, amap = ops.bank_sim_finish(part, dev_ranges[1], self.out_size)
+        return amap.view(B, 1, self.out_size, self.out_size), simmask.view(B, 1, h, h)
+
+    @torch.no_grad()
+    def one_shot_banked(self, images: torch.Tensor, names: Sequence[str]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`one_shot` against the registered references of each sample's class: images [B,3,224,224], names the B class names
+        -> (anomaly map [B,1,S,S], simmask [B,1,h,h]).  One trunk pass over the B queries."""
+        for n in names:
+            self._bank_index.lookup(n)                                                # before any work on the device
+        _, qt = self.trunk.forward(images.to(self.dev, F32))
+        return self._one_shot_banked_from_taps(qt, names)
+
+    @torch.no_grad()
+    def forward_banked(self, images: torch.Tensor, names: Sequence[str], text_feats: Optional[torch.Tensor] = None):
+        """`forward` with class names in place of reference images: ((maps, masks), (oneshot_maps, oneshot_masks)) from one
+        trunk pass over the B queries.  text_feats [B,2,C]; None takes each class's pair from the bank."""
+        for n in names:
+            self._bank_index.lookup(n)
+        if text_feats is None:
+            missing = [n for n in names if n not in self._bank_text]
+            if missing:
+                raise KeyError(f"no text pair was registered for class {missing[0]!r}: pass text_feats here or to add_references()")
+            text_feats = torch.stack([self._bank_text[n] for n in names])
+        _, qt = self.trunk.forward(images.to(self.dev, F32))
+        return self._zero_shot_from_taps(qt, text_feats), self._one_shot_banked_from_taps(qt, names)
 
 
 TPRE, TTRK, THEAD, TPOST = ("modality_preprocessors.text.", "modality_trunks.text.", "modality_heads.text.",

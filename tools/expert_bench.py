@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Vision expert at full size: ImageBind-Huge vision trunk (1280 x 32 blocks, 257 tokens, taps 7/15/23/31)
-+ zero-shot and one-shot map heads, synthetic weights.  python tools/expert_bench.py [--batch 8] [--k 1]"""
-import argparse, os, sys, time
++ zero-shot and one-shot map heads, synthetic weights.  python tools/expert_bench.py [--batch 8] [--k 1]
+--bank: the per-class reference bank against today's one_shot in one process, variants interleaved, medians of --reps:
+(a) the whole call, one_shot(images, refs) vs one_shot_banked(images, names), and add_references per class;
+(b) the head alone on identical taps, the per-sample GEMM + rowmax_skip loop vs bank_sim_max per tap + bank_sim_finish."""
+import argparse, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from myriad_amd import ops
@@ -12,6 +15,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=8)
 ap.add_argument("--k", type=int, default=1)
 ap.add_argument("--blocks", type=int, default=32)
+ap.add_argument("--bank", action="store_true", help="compare the reference bank with one_shot (see the module docstring)")
+ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--cpu", type=int, default=0, help="also time the oracle trunk (oracle/expert_ref.vision_trunk, fp32) on this many host threads, 2 images")
 a = ap.parse_args()
 dev = "cuda:0"
@@ -37,6 +42,65 @@ def timeit(fn, n=5):
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / n
 
+
+def bank_bench():
+    names = [f"class{b % 4}" for b in range(B)]                      # a batch of 4 classes, each twice at batch 8
+    k = a.k
+    per_class = {n: refs[b * k:(b + 1) * k] for b, n in reversed(list(enumerate(names)))}
+    t_add = []
+    for n, r in per_class.items():
+        ex.add_references(n, r)                                      # warm-up of this shape, then the timed replacement
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ex.add_references(n, r)
+        torch.cuda.synchronize()
+        t_add.append(time.perf_counter() - t0)
+    ref_rows = torch.cat([per_class[n] for n in names])              # what one_shot gets: each sample's own class references
+    _, qt = ex.trunk.forward(images)
+    _, rt = ex.trunk.forward(ref_rows)
+    launches = {}
+
+    def count(fn, key):
+        seen = []
+        orig = ops._lib.check
+        ops._lib.check = lambda rc, what: (seen.append(what), orig(rc, what))[1]
+        try:
+            fn()
+        finally:
+            ops._lib.check = orig
+        launches[key] = len(seen)
+
+    variants = {"one_shot": lambda: ex.one_shot(images, ref_rows), "one_shot_banked": lambda: ex.one_shot_banked(images, names),
+                "head_loop": lambda: ex._one_shot_from_taps(qt, rt), "head_banked": lambda: ex._one_shot_banked_from_taps(qt, names)}
+    for key in ("head_loop", "head_banked"):
+        count(variants[key], key)
+    times = {key: [] for key in variants}
+    for key, fn in variants.items():                                 # warm-up: every variant twice before any is timed
+        fn(); fn()
+    torch.cuda.synchronize()
+    inner = {"one_shot": 4, "one_shot_banked": 4, "head_loop": 32, "head_banked": 32}     # calls per sample: a window of tens of ms
+    for _ in range(a.reps):                                          # interleaved: one sample of every variant per round
+        for key, fn in variants.items():
+            t0 = time.perf_counter()
+            for _ in range(inner[key]):
+                fn()
+            torch.cuda.synchronize()
+            times[key].append((time.perf_counter() - t0) / inner[key])
+    med = {key: statistics.median(v) for key, v in times.items()}
+    print("  spread (min .. max of the samples, ms): " + "   ".join(f"{key} {min(v)*1e3:.3f} .. {max(v)*1e3:.3f}" for key, v in times.items()))
+    diff = max(float((x - y).abs().max()) for x, y in zip(variants["one_shot"](), variants["one_shot_banked"]()))
+    print(f"bank, batch {B}, k={k}, {a.blocks} blocks, medians of {a.reps} (interleaved):")
+    print(f"  (a) whole call  one_shot {med['one_shot']*1e3:.2f} ms ({B*(1+k)} trunk passes)   one_shot_banked "
+          f"{med['one_shot_banked']*1e3:.2f} ms ({B} trunk passes)   x{med['one_shot']/med['one_shot_banked']:.2f}   "
+          f"add_references {statistics.median(t_add)*1e3:.2f} ms per class of {k}   max |map difference| {diff:.2e}")
+    print(f"  (b) head alone  loop {med['head_loop']*1e6:.0f} us in {launches['head_loop']} library calls   bank_sim_max x{len(qt)} + "
+          f"finish {med['head_banked']*1e6:.0f} us in {launches['head_banked']} library calls   x{med['head_loop']/med['head_banked']:.2f}   "
+          f"(both include the l2norm_rows launches; the loop also normalises the reference rows)")
+
+
+if a.bank:
+    bank_bench()
+    sys.exit(0)
 
 t_trunk = timeit(lambda: ex.trunk.forward(images))
 t_zs = timeit(lambda: ex.zero_shot(images, text))
