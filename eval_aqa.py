@@ -9,6 +9,9 @@ max_new_tokens=90, stopping_criteria=[###], do_sample=True, top_p=0.01, temperat
 -> ids clamped to [1, 40000] -> batch_decode -> one jsonl record per sample (image_id, image_path, is_anomaly, error,
 output, anomaly_score) -> memory / mean latency.  `--world/--rank` shard the test set by index for multi-GPU runs
 (replicas only: no collective on the data path; merge with myriad_amd.eval_protocol.merge_shards).
+`--seg-metrics` also scores the expert's anomaly maps against the ground-truth masks on the device (myriad_amd.seg_metrics:
+pixel AUROC / AP / F1-max, AUPRO) and writes `<result>.seg.json`, or with --world > 1 the rank's state `<result>.seg.rankK.npz`
+(merge with myriad_amd.eval_protocol.merge_seg_shards).
 """
 import argparse
 import os
@@ -56,9 +59,60 @@ def parse_args(argv=None):
                         "and ranked_output = the likelier answer's text")
     parser.add_argument("--rank-only", action="store_true", help="--rank-answers without generation: output is the likelier "
                         "answer's text")
+    parser.add_argument("--seg-metrics", action="store_true", help="also score ve_anomaly_maps against the dataset's gt_mask: "
+                        "pixel AUROC / AP / F1-max and AUPRO, accumulated on the device; writes <result>.seg.json "
+                        "(--world > 1: <result>.seg.rankK.npz, to be merged with eval_protocol.merge_seg_shards)")
+    parser.add_argument("--seg-max-step", type=int, default=200, help="with --seg-metrics: thresholds of the PRO curve")
+    parser.add_argument("--seg-expect-fpr", type=float, default=0.3, help="with --seg-metrics: the PRO curve is cut at this FPR")
     args = parser.parse_args(argv)
     args.rank_answers = args.rank_answers or args.rank_only
+    if not args.seg_metrics and (args.seg_max_step != 200 or args.seg_expect_fpr != 0.3):
+        parser.error("--seg-max-step / --seg-expect-fpr need --seg-metrics")
+    if args.seg_max_step < 1:
+        parser.error(f"--seg-max-step must be at least 1, got {args.seg_max_step}")
+    if not 0.0 < args.seg_expect_fpr <= 1.0:
+        parser.error(f"--seg-expect-fpr must lie in (0, 1], got {args.seg_expect_fpr}")
     return args
+
+
+def seg_paths(save_path: str, world: int = 1, rank: int = 0):
+    """(metrics json, state npz or None) next to the result file: <result>.seg.json; a rank of a sharded run writes its state
+    <result>.seg.rankK.npz instead (<result>: the jsonl path without the suffix and without the rank's own `.rankK`)."""
+    stem = save_path[:-6] if save_path.endswith(".jsonl") else save_path
+    if world > 1:
+        if stem.endswith(f".rank{rank}"):
+            stem = stem[:-len(f".rank{rank}")]
+        return None, f"{stem}.seg.rank{rank}.npz"
+    return f"{stem}.seg.json", None
+
+
+def seg_gt(data_sample):
+    """The batch's ground-truth masks; a dataset that yields none is an error."""
+    if "gt_mask" not in data_sample:
+        raise KeyError("--seg-metrics: the dataset yields no 'gt_mask' (set with_gt_mask: True in its config; "
+                       f"the samples have {sorted(data_sample)})")
+    return data_sample["gt_mask"]
+
+
+def seg_update(seg, maps, gt_mask, device):
+    """Feed maps and their masks to the accumulator; a model without expert maps is an error."""
+    if maps is None:
+        raise KeyError("--seg-metrics: the model returned no ve_anomaly_maps (no vision expert output to score)")
+    seg.update(maps.detach().to(device), gt_mask)
+
+
+def seg_finish(seg, args, save_path):
+    import json
+    json_path, npz_path = seg_paths(save_path, args.world, args.rank)
+    if npz_path:
+        seg.save(npz_path)
+        print(f"Segmentation-metric state saved to {npz_path}")
+        return None
+    res = seg.compute(max_step=args.seg_max_step, expect_fpr=args.seg_expect_fpr)
+    with open(json_path, "w") as f:
+        json.dump(res, f)
+    print("Segmentation metrics:", res, "->", json_path)
+    return res
 
 
 def llm_watch_ids(tokenizer):
@@ -103,9 +157,14 @@ def main(argv=None):
     stop_words_ids = [torch.tensor([835]).to(model.device), torch.tensor([2277, 29937]).to(model.device)]   # '###', two encodings
     stopping_criteria = [StoppingCriteriaSub(stops=stop_words_ids)]
     if args.dataset == "synthetic":
-        ds = D.build_datasets({"synthetic": cfg.datasets_cfg.get("synthetic", {})}, split="test")["synthetic"]
+        dcfg = dict(cfg.datasets_cfg.get("synthetic", {}) or {})
+        if args.seg_metrics:
+            dcfg["with_gt_mask"] = True
+        ds = D.build_datasets({"synthetic": dcfg}, split="test")["synthetic"]
     else:
         dcfg = dict(cfg.datasets_cfg.get("anomaly_detection", {}) or {})
+        if args.seg_metrics:
+            dcfg["with_gt_mask"] = True
         dcfg["build_info"] = {"vis_root": ROOTS[args.split], "ann_paths": [ANNO_FILES[args.task_type][args.split]]}
         ds = D.build_datasets({"anomaly_detection": dcfg}, split="test")["anomaly_detection"]
     if args.world > 1:
@@ -127,8 +186,12 @@ def main(argv=None):
         generate_kwargs.update(output_scores=True, watch_ids=llm_watch_ids(model.llama_tokenizer))
 
     model.eval()
+    seg = None
+    if args.seg_metrics:
+        from myriad_amd.seg_metrics import SegMetrics
+        seg = SegMetrics(model.device)
     if args.slots > 0 and not args.rank_only:
-        return save_path, _run_slots(args, model, loader, generate_kwargs, save_path)
+        return save_path, _run_slots(args, model, loader, generate_kwargs, save_path, seg)
     records, all_time, sampled = [], 0.0, 0
     for testid, data_sample in enumerate(loader):
         if testid < args.start:
@@ -147,6 +210,8 @@ def main(argv=None):
             sampled += model.last_generate_stats["sampled_rows"]
             texts = EP.postprocess_generation(outputs["token_ids"], model.llama_tokenizer)
         maps = outputs.get("ve_anomaly_maps")
+        if seg is not None:
+            seg_update(seg, maps, seg_gt(data_sample), model.device)
         for ind, text in enumerate(texts):
             amax = None
             if maps is not None:                         # anomaly_map_handler (:93-104): uint8(map * 255) then max
@@ -157,6 +222,8 @@ def main(argv=None):
             if ranked is not None:
                 EP.add_answer_ranking(records[-1], ranked["answer_logprobs"][ind], rank_texts()[int(ranked["best"][ind])])
     EP.write_jsonl(save_path, records)
+    if seg is not None:
+        seg_finish(seg, args, save_path)
     n_batches = max(1, len(records) // max(1, args.bs))
     print("CUDA Memory:", torch.cuda.max_memory_allocated() / (1024 * 1024))
     print("Mean Time: ", all_time / n_batches)
@@ -165,12 +232,13 @@ def main(argv=None):
     return save_path, records
 
 
-def _run_slots(args, model, loader, generate_kwargs, save_path):
+def _run_slots(args, model, loader, generate_kwargs, save_path, seg=None):
     """The evaluation loop over model.generate_stream: the same records, in the dataset's order."""
     import torch
     from myriad_amd import eval_protocol as EP
 
     meta, ranks = [], []                                 # per sample, in input order: what its record needs besides the text
+    gt = {}                                              # --seg-metrics: a sample's ground-truth mask until its map arrives
 
     def batches():
         for testid, data_sample in enumerate(loader):
@@ -179,6 +247,8 @@ def _run_slots(args, model, loader, generate_kwargs, save_path):
             if args.limit and testid >= args.start + args.limit:
                 break
             for ind in range(len(data_sample["image_id"])):
+                if seg is not None:
+                    gt[len(meta)] = seg_gt(data_sample)[ind:ind + 1]
                 meta.append((int(data_sample["image_id"][ind]), data_sample["img_path"][ind], bool(data_sample["is_anomaly"][ind])))
             if args.rank_answers:                        # between two token steps of the stream: a pass of its own caches
                 r = model.score_answers(data_sample)
@@ -192,6 +262,9 @@ def _run_slots(args, model, loader, generate_kwargs, save_path):
                                          **generate_kwargs):
             text = EP.postprocess_generation(out["token_ids"][None], model.llama_tokenizer)[0]
             amax = None
+            if seg is not None:
+                m = out["ve_anomaly_map"]
+                seg_update(seg, None if m is None else m.reshape(1, *m.shape[-2:]), gt.pop(out["index"]), model.device)
             if out["ve_anomaly_map"] is not None:        # anomaly_map_handler (:93-104): uint8(map * 255) then max
                 amax = float((out["ve_anomaly_map"].detach().float().cpu() * 255.0).to(torch.uint8).max())
             llm = EP.llm_anomaly_score(out["watch_logprobs"][0]) if args.llm_score else None
@@ -202,6 +275,8 @@ def _run_slots(args, model, loader, generate_kwargs, save_path):
         torch.cuda.synchronize()
         all_time = time.time() - t1
     EP.write_jsonl(save_path, records)
+    if seg is not None:
+        seg_finish(seg, args, save_path)
     st = model.last_generate_stats
     n_batches = max(1, len(records) // max(1, args.bs))
     print("CUDA Memory:", torch.cuda.max_memory_allocated() / (1024 * 1024))

@@ -703,6 +703,25 @@ int mh_bank_sim_max(const void* q, long q_row0, long q_sample_rows, const void* 
 int mh_bank_sim_finish(const float* part, const int* bank_rows, float* sim, float* simmask, float* amap, int T, int B,
                        int max_chunks, int h, int S, float w, mh_stream_t s);
 
+/* K17 streaming localisation metrics for anomaly maps (csrc/seg_metrics.hip; seg_metrics.py, eval_protocol.seg_metrics_from_hist).
+ * mh_mask_components: 8-connected components of B binary masks [B, H, W] (one byte per pixel, nonzero = anomalous), one workgroup
+ *   per image with the union-find in LDS.  labels [B, H, W] int32: -1 on background, else the smallest linear index y W + x of
+ *   the pixel's component; area [B, H, W] int32: the component's pixel count at that pixel, 0 elsewhere; n_regions [B] int32.
+ *   Every element of the three outputs is written.  H W <= 65536 and (2 ceil(H/2) ceil(W/2) + 1) * 4 bytes of LDS <= 160 KiB (true
+ *   for every image with both sides >= 4); anything else is refused with MH_ERR_ARG before any launch.
+ *   mh_mask_components_lds_bytes: that LDS size, or -1 where the image is refused.
+ * mh_seg_hist_update: hist [3, 2^20] int64 and counters [4] int64 are added to, with integer atomics only (the result does not
+ *   depend on arrival order).  The key of a score is the top 20 bits of the order-preserving transform of its fp32 bits (-0 as +0;
+ *   negative: all bits flipped; else the sign bit set); maps [B, H, W] fp32, or bf16 (maps_bf16 = 1; keyed exactly).  Row 0 counts
+ *   the normal pixels per key, row 1 the anomalous ones, row 2 receives floor(2^40 / area of its region) per anomalous pixel
+ *   (labels / area: mh_mask_components' outputs for `masks`).  counters: pixels, anomalous pixels, regions, non-finite scores; a
+ *   NaN or +-inf score is counted there and nowhere in hist.  aggregate = 1: the lanes of a wave that share (row, key) add once;
+ *   0: one atomic per lane.  Same sums either way. */
+long mh_mask_components_lds_bytes(int H, int W);
+int mh_mask_components(const void* masks, int* labels, int* area, int* n_regions, int B, int H, int W, mh_stream_t s);
+int mh_seg_hist_update(long long* hist, long long* counters, const void* maps, int maps_bf16, const void* masks, const int* labels,
+                       const int* area, int B, int H, int W, int aggregate, mh_stream_t s);
+
 /* ---- opaque context: library state the caller owns explicitly ------------------------------------------------
  * An mh_ctx holds (1) a split-K scratch record -- mh_ctx_set_workspace(ctx, NULL, ptr, bytes) the main scratch,
  * (ctx, stream, ptr, bytes) that of one more stream that may split K concurrently; library calls use the record of the context

@@ -77,11 +77,32 @@ def sample_strings(is_aug_anomalous: Optional[bool]) -> dict:
 
 class SyntheticAnomalyDataset(Dataset):
     """Seeded random samples in the reference schema: image / aug_image N(0,1) [3,224,224] (CLIP-normalised images are
-    about unit variance), maps U[0,1) [1,224,224]."""
+    about unit variance), maps U[0,1) [1,224,224].  `with_gt_mask`: also "gt_mask" [1, S, S] uint8, one to three
+    seeded rectangles or elliptic blobs for an anomalous sample and zeros for a good one (drawn from a generator of its own: the
+    other fields do not change)."""
     DatasetName = "AnomalyDetection"          # the loader halves the batch for this name (runner_base.py:546-549)
 
-    def __init__(self, n: int = 64, seed: int = 0, train: bool = True, image_size: int = 224, scene: str = "bottle"):
+    def __init__(self, n: int = 64, seed: int = 0, train: bool = True, image_size: int = 224, scene: str = "bottle",
+                 with_gt_mask: bool = False):
         self.n, self.seed, self.train, self.size, self.scene = n, seed, train, image_size, scene
+        self.with_gt_mask = bool(with_gt_mask)
+
+    def _gt_mask(self, index, anomalous: bool) -> torch.Tensor:
+        S = self.size
+        mask = torch.zeros(1, S, S, dtype=torch.uint8)
+        if not anomalous:
+            return mask
+        g = torch.Generator().manual_seed(self.seed * 1000003 + index + 0x6D61736B)
+        yy, xx = torch.meshgrid(torch.arange(S), torch.arange(S), indexing="ij")
+        for _ in range(int(torch.randint(1, 4, (1,), generator=g))):
+            cy, cx = (int(v) for v in torch.randint(0, S, (2,), generator=g))
+            ry, rx = (int(v) for v in torch.randint(1, max(2, S // 6), (2,), generator=g))
+            if bool(torch.randint(0, 2, (1,), generator=g)):
+                hit = ((yy - cy).abs() <= ry) & ((xx - cx).abs() <= rx)
+            else:
+                hit = ((yy - cy).float() / ry) ** 2 + ((xx - cx).float() / rx) ** 2 <= 1.0
+            mask[0] |= hit.to(torch.uint8)
+        return mask
 
     def __len__(self):
         return self.n
@@ -96,6 +117,8 @@ class SyntheticAnomalyDataset(Dataset):
             ret["aug_image"] = torch.randn(3, S, S, generator=g)
             ret["aug_anomaly_maps"] = torch.rand(1, S, S, generator=g)
             ret["aug_oneshot_anomaly_maps"] = torch.rand(1, S, S, generator=g)
+        if self.with_gt_mask:
+            ret["gt_mask"] = self._gt_mask(index, ret["is_anomaly"])
         ret.update(sample_strings(True if self.train else None))
         return ret
 
@@ -103,7 +126,7 @@ class SyntheticAnomalyDataset(Dataset):
 @register_dataset("synthetic")
 def _build_synthetic(cfg, split):
     return SyntheticAnomalyDataset(n=int(cfg.get("num_samples", 64)), seed=int(cfg.get("seed", 0)), train=(split == "train"),
-                                   image_size=int(cfg.get("image_size", 224)))
+                                   image_size=int(cfg.get("image_size", 224)), with_gt_mask=bool(cfg.get("with_gt_mask", False)))
 
 
 class AnomalyDetectionDataset(Dataset):
@@ -113,10 +136,13 @@ class AnomalyDetectionDataset(Dataset):
     DatasetName = "AnomalyDetection"
 
     def __init__(self, vis_root: str, ann_paths: List[str], img_size: int = 224, crop_size: int = 224, stage: str = "train",
-                 self_sup_mode: Optional[str] = None, seed: Optional[int] = None):
+                 self_sup_mode: Optional[str] = None, seed: Optional[int] = None, with_gt_mask: bool = False):
         """self_sup_mode None = the reference's recipe (anomaly_detection.py:118-141,254-264): per-class arguments, the patch
         resampled (`resize=True`) and blended with cv2.NORMAL_CLONE.  'swap' / 'uniform' are explicit opt-outs that keep the
-        same geometry arguments but paste arithmetically without resampling (bit-pinned to the reference, no OpenCV step)."""
+        same geometry arguments but paste arithmetically without resampling (bit-pinned to the reference, no OpenCV step).
+        with_gt_mask: samples carry "gt_mask" [1, crop, crop] uint8, the ground-truth segmentation (gt_mask_path, `> 0`) resized
+        and cropped like the image with nearest sampling; zeros for a good sample."""
+        self.with_gt_mask = bool(with_gt_mask)
         self.vis_root, self.ann_paths, self.stage = vis_root, list(ann_paths), stage
         self.img_size, self.crop_size = img_size, crop_size
         self.annotation = []
@@ -138,10 +164,32 @@ class AnomalyDetectionDataset(Dataset):
     def _crop(self, index) -> np.ndarray:
         from PIL import Image
         img = Image.open(os.path.join(self.vis_root, self.annotation[index]["img_path"])).convert("RGB")
+        return self._resize_crop(img, Image.BICUBIC)
+
+    @staticmethod
+    def gt_mask_path(img_path: str) -> str:
+        """`get_gt_seg` (anomaly_detection.py:176-184): `ground_truth` goes in front of the last three path components and the
+        extension becomes png: <class>/test/<defect>/<name>.jpg -> <class>/ground_truth/test/<defect>/<name>.png."""
+        parts = img_path.split("/")
+        return "/".join(parts[:-3] + ["ground_truth"] + parts[-3:])[:-3] + "png"
+
+    def _gt_mask(self, index, anomalous: bool) -> torch.Tensor:
+        from PIL import Image
+        c = self.crop_size
+        if not anomalous:
+            return torch.zeros(1, c, c, dtype=torch.uint8)
+        path = self.gt_mask_path(os.path.join(self.vis_root, self.annotation[index]["img_path"]))
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"ground-truth mask {path} of anomalous sample {index} does not exist")
+        m = (np.array(Image.open(path).convert("L")) > 0).astype(np.uint8) * 255
+        m = self._resize_crop(Image.fromarray(m), Image.NEAREST)
+        return torch.from_numpy(np.ascontiguousarray((m > 0).astype(np.uint8)))[None]
+
+    def _resize_crop(self, img, resample) -> np.ndarray:
         w, h = img.size
         s = self.img_size                       # torchvision Resize(int): shorter side -> s, BICUBIC
         nw, nh = (s, int(s * h / w)) if w <= h else (int(s * w / h), s)
-        img = img.resize((nw, nh), Image.BICUBIC)
+        img = img.resize((nw, nh), resample)
         c = self.crop_size
         left, top = int(round((nw - c) / 2.0)), int(round((nh - c) / 2.0))
         return np.asarray(img.crop((left, top, left + c, top + c)))
@@ -156,6 +204,8 @@ class AnomalyDetectionDataset(Dataset):
         image = self._crop(index)
         ret = {"image": self._to_tensor(image), "scene": ann["img_path"].split("/")[1], "image_id": index,
                "is_anomaly": ann["is_anomaly"] == "1", "img_path": os.path.join(self.vis_root, ann["img_path"])}
+        if self.with_gt_mask:
+            ret["gt_mask"] = self._gt_mask(index, ret["is_anomaly"])
         aug_anom = None
         if self.stage == "train":
             from . import self_sup
@@ -184,7 +234,7 @@ def _build_anomaly_detection(cfg, split):
     root = info.get("vis_root", info.get("storage", "./data"))
     return AnomalyDetectionDataset(root, info.get("ann_paths", []), stage="train" if split == "train" else "test",
                                    img_size=int(cfg.get("img_size", 224)), crop_size=int(cfg.get("crop_size", 224)),
-                                   self_sup_mode=cfg.get("self_sup_mode", None))
+                                   self_sup_mode=cfg.get("self_sup_mode", None), with_gt_mask=bool(cfg.get("with_gt_mask", False)))
 
 
 def collate(batch: List[dict]) -> dict:

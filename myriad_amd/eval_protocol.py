@@ -99,6 +99,129 @@ def scene_performance(records: Iterable[dict], rules: Optional[AnswerRules] = No
     return float(np.mean(accs)), float(np.mean(aucs)), float(np.mean(th_accs))
 
 
+# ------------------------------------------------------------------------------------------------ localisation metrics
+SEG_KEY_BITS = 20
+
+
+def seg_key(scores) -> np.ndarray:
+    """The 20-bit histogram key of fp32 scores (csrc/seg_metrics.hip): -0 counts as +0; the bits of a negative value are all
+    flipped, a non-negative one gets its sign bit set (unsigned order of the result = numeric order); the top 20 bits are kept."""
+    u = np.ascontiguousarray(scores, dtype=np.float32).view(np.uint32)
+    u = np.where(u == np.uint32(0x80000000), np.uint32(0), u)
+    t = np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
+    return (t >> np.uint32(32 - SEG_KEY_BITS)).astype(np.int64)
+
+
+def seg_bin_value(keys) -> np.ndarray:
+    """The smallest fp32 value of each bin: the transform inverted on key << 12."""
+    t = (np.asarray(keys, dtype=np.uint64) << np.uint64(32 - SEG_KEY_BITS)).astype(np.uint32)
+    u = np.where(t & np.uint32(0x80000000), t ^ np.uint32(0x80000000), ~t)
+    return u.astype(np.uint32).view(np.float32)
+
+
+def _sk_auc(x: np.ndarray, y: np.ndarray) -> float:
+    """sklearn.metrics.auc: the trapezoid area, negated where x decreases; x must be monotone."""
+    if x.shape[0] < 2:
+        raise ValueError(f"At least 2 points are needed to compute area under curve, but x.shape = {x.shape}")
+    dx = np.diff(x)
+    direction = 1.0
+    if np.any(dx < 0):
+        if np.all(dx <= 0):
+            direction = -1.0
+        else:
+            raise ValueError(f"x is neither increasing nor decreasing : {x}.")
+    return float(direction * np.sum(dx * (y[1:] + y[:-1]) / 2.0))
+
+
+def seg_metrics_from_hist(neg, pos, w, n_regions: int, max_step: int = 200, expect_fpr: float = 0.3) -> dict:
+    """Pixel AUROC / AP / F1-max and AUPRO of `ALEvaluator.eval_seg` / `cal_pro_score` (scripts/eval_protocol/eval_align.py:
+    281-343) from the three histogram rows SegMetrics accumulates: per 20-bit key the count of normal pixels (`neg`), of anomalous
+    pixels (`pos`) and the sum over anomalous pixels of floor(2^40 / area of the pixel's ground-truth region) (`w`).  Device-free,
+    fp64.  A bin stands for the smallest fp32 value in it, so all four numbers are the reference's formulas applied to the maps
+    TRUNCATED to the 20-bit key (exact for non-negative bf16 maps and for fp32 scores that are their bin's smallest member):
+      auroc_px  trapezoid over the non-empty bins, descending, a bin being one tied score (roc_auc_score);
+      ap_px     sum of (R_n - R_{n-1}) P_n (average_precision_score);
+      f1_px     the finite maximum of 2 P R / (P + R) over the bins' thresholds (precision_recall_curve);
+      aupro     thresholds np.arange(min, max, (max - min) / max_step) on the fp32 extremes, strict `>`, per threshold the mean
+                over regions of tp_r / area_r = (suffix sum of w) / (n_regions 2^40), within 2^16 / 2^40 = 2^-24 of the exact
+                mean (each of a region's <= 2^16 pixels loses less than one unit of 2^-40 to the floor); the points with
+                fpr < expect_fpr, their fpr min-max normalised, sklearn's auc.  Where the reference divides by zero (one such
+                point, no region) this returns NaN as it does.
+    auroc_px_tie_bound = sum_b pos_b neg_b / (2 P N): the AUROC of the unquantised fp32 scores lies within it of auroc_px (only
+    the pairs that share a bin can be ordered differently, and each counts 1/2 here).  No such bound is claimed for the others."""
+    neg, pos, w = (np.asarray(a, dtype=np.int64).ravel() for a in (neg, pos, w))
+    if not (neg.shape == pos.shape == w.shape == (1 << SEG_KEY_BITS,)):
+        raise ValueError(f"seg_metrics_from_hist: need three rows of {1 << SEG_KEY_BITS} bins, got {neg.shape} {pos.shape} {w.shape}")
+    P, N = int(pos.sum()), int(neg.sum())
+    if P == 0 or N == 0:
+        raise ValueError(f"seg_metrics_from_hist: {P} anomalous and {N} normal pixels; the metrics need both classes")
+    keys = np.nonzero((neg + pos) > 0)[0]
+    vals = seg_bin_value(keys)                             # ascending with the key
+    nb, pb, wb = neg[keys][::-1], pos[keys][::-1], w[keys][::-1]          # descending score
+    tps, fps = np.cumsum(pb).astype(np.float64), np.cumsum(nb).astype(np.float64)
+    tpr, fpr = np.concatenate([[0.0], tps / P]), np.concatenate([[0.0], fps / N])
+    auroc_px = float(np.sum(np.diff(fpr) * (tpr[1:] + tpr[:-1]) / 2.0))
+    precision, recall = tps / (tps + fps), tps / P
+    ap_px = float(np.sum(np.diff(np.concatenate([[0.0], recall])) * precision))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        f1 = (2 * precision * recall) / (precision + recall)
+    f1_px = float(np.max(f1[np.isfinite(f1)]))
+    tie_bound = float(np.sum(pb.astype(np.float64) * nb.astype(np.float64)) / (2.0 * P * N))
+
+    # cal_pro_score.  Suffix sums over ascending bins: s[i] = total of the bins i.. ; "score > th" = the bins whose value > th
+    min_th, max_th = vals[0], vals[-1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        delta = (max_th - min_th) / max_step
+        ths = np.arange(min_th, max_th, delta)
+        first = np.searchsorted(vals.astype(np.float64), ths.astype(np.float64), side="right")
+        suf_neg = np.concatenate([np.cumsum(nb)[::-1], [0]])
+        suf_w = np.concatenate([np.cumsum(wb)[::-1], [0]])
+        pros = suf_w[first].astype(np.float64) / (float(n_regions) * float(1 << 40)) if n_regions else np.full(len(ths), np.nan)
+        fprs = suf_neg[first].astype(np.float64) / N
+        keep = fprs < expect_fpr
+        fprs = fprs[keep]
+        fprs = (fprs - fprs.min()) / (fprs.max() - fprs.min())
+        aupro = _sk_auc(fprs, pros[keep])
+    return {"auroc_px": auroc_px, "ap_px": ap_px, "f1_px": f1_px, "aupro": aupro, "auroc_px_tie_bound": tie_bound,
+            "n_pixels": P + N, "n_anomalous": P, "n_regions": int(n_regions)}
+
+
+SEG_MAX_REGIONS = 1 << 22      # a bin of row 2 holds at most n_regions * 2^40: int64 head-room
+
+
+def seg_metrics_from_state(hist, counters, max_step: int = 200, expect_fpr: float = 0.3) -> dict:
+    """The metrics of an accumulated SegMetrics state: hist [3, 2^20] int64 (rows neg / pos / w of seg_metrics_from_hist),
+    counters [4] int64 (pixels, anomalous pixels, regions, non-finite scores).  ValueError where the state cannot be scored."""
+    hist, counters = np.asarray(hist, dtype=np.int64), np.asarray(counters, dtype=np.int64).ravel()
+    if hist.shape != (3, 1 << SEG_KEY_BITS) or counters.shape != (4,):
+        raise ValueError(f"seg metrics state: need hist {(3, 1 << SEG_KEY_BITS)} and 4 counters, got {hist.shape} {counters.shape}")
+    n_pix, n_pos, n_reg, n_bad = (int(c) for c in counters)
+    if n_bad:
+        raise ValueError(f"seg metrics: {n_bad} of {n_pix} scores were NaN or infinite; they are in no histogram row")
+    if n_pos == 0 or n_pix - n_pos == 0:
+        raise ValueError(f"seg metrics: {n_pos} anomalous and {n_pix - n_pos} normal pixels; the metrics need both classes")
+    if n_reg >= SEG_MAX_REGIONS:
+        raise ValueError(f"seg metrics: {n_reg} regions >= 2^22: the region-weighted row may have overflowed int64")
+    return seg_metrics_from_hist(hist[0], hist[1], hist[2], n_reg, max_step, expect_fpr)
+
+
+def merge_seg_shards(paths: Sequence[str], out_path: Optional[str] = None, max_step: int = 200, expect_fpr: float = 0.3) -> dict:
+    """Add the per-rank `.seg.rankK.npz` states of a sharded evaluation (integer sums: any order gives the same bits) and score
+    the total; `out_path`: where to write the metrics as json."""
+    hist, counters = None, None
+    for p in paths:
+        with np.load(p) as z:
+            h, c = z["hist"].astype(np.int64), z["counters"].astype(np.int64)
+        hist, counters = (h, c) if hist is None else (hist + h, counters + c)
+    if hist is None:
+        raise ValueError("merge_seg_shards: no shard given")
+    res = seg_metrics_from_state(hist, counters, max_step, expect_fpr)
+    if out_path:
+        with open(out_path, "w") as f:
+            json.dump(res, f)
+    return res
+
+
 # ------------------------------------------------------------------------------------------------ records
 def postprocess_generation(token_ids, tokenizer) -> List[str]:
     """evaluation_aqa_dataset.py:339-341, 369: ids clamped to [1, 40000], decoded, cut at the first '###'."""

@@ -1663,6 +1663,64 @@ def bank_sim_finish(part: torch.Tensor, bank_rows: torch.Tensor, S: int, w: Opti
     return sim, simmask, amap
 
 
+SEG_HIST_BINS = 1 << 20      # keys of seg_hist_update: the top 20 bits of the order-preserving transform of the fp32 bits
+SEG_MAX_PIXELS = 65536       # mask_components keeps one image's union-find in LDS
+
+
+def _chk_masks(masks: torch.Tensor, name: str):
+    if masks.dtype not in (torch.uint8, torch.bool) or not masks.is_cuda or masks.dim() != 3 or not masks.is_contiguous():
+        raise _lib.MyriadHipError(f"{name}: need contiguous cuda uint8 / bool [B, H, W], got {masks.dtype} {tuple(masks.shape)} "
+                                  f"cuda={masks.is_cuda}")
+    B, H, W = masks.shape
+    if B < 1 or H < 1 or W < 1:
+        raise _lib.MyriadHipError(f"{name}: empty shape {tuple(masks.shape)}")
+    if H * W > SEG_MAX_PIXELS or _L().mh_mask_components_lds_bytes(H, W) < 0:
+        raise _lib.MyriadHipError(f"{name}: an image of {H} x {W} does not fit one workgroup's LDS (H * W <= {SEG_MAX_PIXELS}, "
+                                  "both sides >= 4 or few enough 2 x 2 blocks)")
+    return B, H, W
+
+
+def mask_components(masks: torch.Tensor, out=None):
+    """8-connected components of binary masks [B, H, W] (uint8 / bool, nonzero = anomalous) -> (labels [B, H, W] int32: -1 on
+    background, else the smallest linear index y * W + x of the pixel's component; area [B, H, W] int32: the component's pixel
+    count at that pixel, 0 elsewhere; n_regions [B] int32).  `out`: the three tensors to write.  H * W <= 65536."""
+    B, H, W = _chk_masks(masks, "mask_components.masks")
+    if out is None:
+        out = (torch.empty((B, H, W), dtype=torch.int32, device=masks.device),
+               torch.empty((B, H, W), dtype=torch.int32, device=masks.device),
+               torch.empty((B,), dtype=torch.int32, device=masks.device))
+    labels, area, n_regions = out
+    for t, shape, name in ((labels, (B, H, W), "labels"), (area, (B, H, W), "area"), (n_regions, (B,), "n_regions")):
+        if t.dtype != torch.int32 or not t.is_cuda or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.MyriadHipError(f"mask_components.{name}: need contiguous cuda int32 {shape}, got {t.dtype} {tuple(t.shape)}")
+    _lib.check(_L().mh_mask_components(_p(masks), _p(labels), _p(area), _p(n_regions), B, H, W, _s()), "mh_mask_components")
+    return labels, area, n_regions
+
+
+def seg_hist_update(hist: torch.Tensor, counters: torch.Tensor, maps: torch.Tensor, masks: torch.Tensor, labels: torch.Tensor,
+                    area: torch.Tensor, aggregate: bool = True) -> None:
+    """hist [3, 2^20] int64 and counters [4] int64 += the batch: maps [B, H, W] f32 / bf16 scores, masks [B, H, W] uint8 / bool,
+    labels / area: mask_components(masks).  Rows: normal pixels per key, anomalous pixels per key, floor(2^40 / region area) per
+    anomalous pixel; counters: pixels, anomalous pixels, regions, non-finite scores (those reach no histogram row).  Integer
+    atomics: bitwise reproducible.  `aggregate`: equal keys of a wave add once (False: one atomic per lane; same result)."""
+    B, H, W = _chk_masks(masks, "seg_hist_update.masks")
+    if hist.dtype != torch.int64 or not hist.is_cuda or tuple(hist.shape) != (3, SEG_HIST_BINS) or not hist.is_contiguous():
+        raise _lib.MyriadHipError(f"seg_hist_update.hist: need contiguous cuda int64 {(3, SEG_HIST_BINS)}, got {hist.dtype} "
+                                  f"{tuple(hist.shape)}")
+    if counters.dtype != torch.int64 or not counters.is_cuda or tuple(counters.shape) != (4,) or not counters.is_contiguous():
+        raise _lib.MyriadHipError(f"seg_hist_update.counters: need contiguous cuda int64 (4,), got {counters.dtype} "
+                                  f"{tuple(counters.shape)}")
+    if maps.dtype not in (F32, BF16) or not maps.is_cuda or tuple(maps.shape) != (B, H, W) or not maps.is_contiguous():
+        raise _lib.MyriadHipError(f"seg_hist_update.maps: need contiguous cuda f32 / bf16 {(B, H, W)}, got {maps.dtype} "
+                                  f"{tuple(maps.shape)}")
+    for t, name in ((labels, "labels"), (area, "area")):
+        if t.dtype != torch.int32 or not t.is_cuda or tuple(t.shape) != (B, H, W) or not t.is_contiguous():
+            raise _lib.MyriadHipError(f"seg_hist_update.{name}: need contiguous cuda int32 {(B, H, W)}, got {t.dtype} "
+                                      f"{tuple(t.shape)}")
+    _lib.check(_L().mh_seg_hist_update(_p(hist), _p(counters), _p(maps), int(maps.dtype == BF16), _p(masks), _p(labels), _p(area),
+                                       B, H, W, int(bool(aggregate)), _s()), "mh_seg_hist_update")
+
+
 def gemm_residual_rmsnorm(a: torch.Tensor, b: torch.Tensor, residual: torch.Tensor, norm_w: torch.Tensor, eps: float,
                           y_out: Optional[torch.Tensor] = None):
     """(h, y): h = a @ b^T + residual (f32), y = rmsnorm(h) * norm_w (bf16; y_out may be a [M, N] view of a wider buffer).
