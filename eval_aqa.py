@@ -48,6 +48,9 @@ def parse_args(argv=None):
     parser.add_argument("--limit", type=int, default=0, help="evaluate only the first N batches (smoke runs)")
     parser.add_argument("--slots", type=int, default=0, help="N > 0: stream the test set through N decode slots "
                         "(model.generate_stream: per-sample positions and stop rule); 0: one generate() per batch")
+    parser.add_argument("--num-beams", type=int, default=1, help="N > 1: beam search with N beams instead of the evaluation "
+                        "script's sampling (num_beams=N, do_sample=False), in either loop; with --slots the slot count must be a "
+                        "multiple of N and beam search in the decode slots needs its switch, MYRIAD_SLOT_BEAMS=1")
     parser.add_argument("--prefill-batch", type=int, default=1, help="with --slots: P > 1 prefills up to P waiting samples in one "
                         "packed pass when slots are free (1: every sample is prefilled alone)")
     parser.add_argument("--refill-min", type=int, default=1, help="with --slots: hold a refill back until this many slots are free "
@@ -182,6 +185,8 @@ def main(argv=None):
     generate_kwargs = {"max_new_tokens": 90, "stopping_criteria": stopping_criteria, "do_sample": True, "use_cache": True,
                        "min_length": 1, "top_p": 0.01, "temperature": 1.0}           # evaluation_aqa_dataset.py:289-301
 
+    if args.num_beams > 1:
+        generate_kwargs.update(num_beams=args.num_beams, do_sample=False)
     if args.llm_score:
         generate_kwargs.update(output_scores=True, watch_ids=llm_watch_ids(model.llama_tokenizer))
 
@@ -207,7 +212,7 @@ def main(argv=None):
         if args.rank_only:                               # nothing was generated: the likelier answer is the output
             texts = [rank_texts()[int(b)] for b in ranked["best"]]
         else:
-            sampled += model.last_generate_stats["sampled_rows"]
+            sampled += model.last_generate_stats.get("sampled_rows", 0)     # a beam search draws nothing
             texts = EP.postprocess_generation(outputs["token_ids"], model.llama_tokenizer)
         maps = outputs.get("ve_anomaly_maps")
         if seg is not None:

@@ -354,6 +354,21 @@ int mh_beam_topk(const float* logits, long ldl, const float* scores, float* part
    src[r] == r are not written; duplicate parents are fine (every source is read before any store of the same cell). */
 int mh_beam_reorder_kv(void* const* caches, int L, int B, int nb, long T_cap, int C, const int* src, const int* lo, const int* hi,
                        mh_stream_t s);
+/* the decode slots' beam groups: mh_beam_topk at rpi = nb for G items, one request each, with per-item state in device memory.
+   live[G], gen[G] (tokens the item's request has generated), prm[2] = (min_length, eos_id), all int32 and read by the kernels, so
+   one captured graph serves every value.  A live item (live[g] != 0) bans eos_id iff gen[g] < min_length; its K = 2*nb entries of
+   out_s / out_i [G, K] are what mh_beam_topk writes for that item alone (B = 1) with that ban; then pos[r] += 1 and kvlen[r] += 1
+   for its nb rows g*nb .. g*nb+nb-1 and gen[g] += 1.  An idle item's row workgroups leave before they load a logit, its record
+   entries are (0.0, -1) and its pos / kvlen / gen / scratch rows are not touched.  part_s / part_i = scratch of G*nb*K entries.
+   Limits as mh_beam_topk; a null pointer (pos and kvlen included), V < 1 or ldl < V is MH_ERR_ARG; both before any launch. */
+int mh_beam_topk_items(const float* logits, long ldl, const float* scores, float* part_s, int* part_i, float* out_s, int* out_i, int G,
+                       int nb, int V, const int* live, int* gen, const int* prm, int* pos, int* kvlen, mh_stream_t s);
+/* mh_beam_reorder_kv with a window and a live flag per item: item g copies positions [lo[g], hi[g]) clamped to [0, T_cap) among its
+   rows g*nb .. g*nb+nb-1; an item with live[g] == 0 and every position outside an item's window are not touched; a parent outside
+   the item is ignored.  lo / hi / live int32 [G] in device memory (capturable).  With src = each group's first row, the window
+   [0, S0_g) and live = the groups just refilled it broadcasts a prefilled prompt to its sibling rows. */
+int mh_beam_reorder_kv_items(void* const* caches, int L, int G, int nb, long T_cap, int C, const int* src, const int* lo,
+                             const int* hi, const int* live, mh_stream_t s);
 /* beam-search multinomial sampling / the repetition penalty under beams: mh_beam_topk's step with HF's processor chain on the
    log-probs and Gumbel noise on the candidates.  logits [B*nb, ldl] fp32 (nb rows per item, always), scores [B*nb].  Per row, in
    fp32: lp = (x - max) - log(sum exp(x - max)) (NaN -> -inf); for every id in the row's bitmap seen[row] (W = ceil(V/32) words a

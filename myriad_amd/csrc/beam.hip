@@ -12,6 +12,9 @@
 //                          one 16-byte cell (layer, item, position, columns) for all nb sibling rows of the item, loads every
 //                          source row of that cell, then stores -- no cell is shared between threads, so no hazard; src, lo and
 //                          hi are read from device memory so the launch can be captured in the token step's hipGraph.
+// The three kernels are templates on ITEMS (the decode slots' beam groups, one request per item): every item then has its own
+// live flag, generated count (which decides its EOS ban), position and reorder window in device memory, and an idle item's
+// workgroups leave on a scalar branch.  ITEMS = false is the code above, unchanged.
 #include "common.h"
 
 #define BNT 1024                // threads per row (beam_row_topk_kernel)
@@ -36,13 +39,23 @@ __device__ __forceinline__ float bm_wave_sum(float v) {
 }
 
 // scores [R] = each row's running beam score; part[R][K] = (score, token) of the row's top K
+// ITEMS: rows row / nb * nb .. + nb - 1 are item g's; an idle item's rows leave before they load a logit (blockIdx is uniform: a
+// scalar branch), a live one bans prm[1] while gen[g] < prm[0]
+template <bool ITEMS>
 __global__ __launch_bounds__(BNT) void beam_row_topk_kernel(const float* __restrict__ logits, long ldl,
                                                             const float* __restrict__ scores, float* __restrict__ part_s,
-                                                            int* __restrict__ part_i, int V, int K, int ban_id) {
+                                                            int* __restrict__ part_i, int V, int K, int ban_id, int nb,
+                                                            const int* __restrict__ live, const int* __restrict__ gen,
+                                                            const int* __restrict__ prm) {
   __shared__ float red[BNW];
   __shared__ float cs[BNW * BKMAX];
   __shared__ int ci[BNW * BKMAX];
   const long row = blockIdx.x;
+  if (ITEMS) {
+    const int g = blockIdx.x / nb;
+    if (!live[g]) return;
+    ban_id = gen[g] < prm[0] ? prm[1] : -1;
+  }
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const float* x = logits + row * ldl;
   const float ninf = -__builtin_inff();
@@ -122,12 +135,23 @@ __global__ __launch_bounds__(BNT) void beam_row_topk_kernel(const float* __restr
   }
 }
 
+// ITEMS (rpi = nb): an idle item records (0.0, -1) K times and keeps its state; a live one advances its own rows' pos / kvlen
+// and its gen (which the row kernel, an earlier launch, has read)
+template <bool ITEMS>
 __global__ __launch_bounds__(128) void beam_merge_kernel(const float* __restrict__ part_s, const int* __restrict__ part_i,
                                                          float* __restrict__ out_s, int* __restrict__ out_i, int rpi, int V, int K,
-                                                         int* __restrict__ pos, int* __restrict__ kvlen, int n_adv) {
+                                                         int* __restrict__ pos, int* __restrict__ kvlen, int n_adv,
+                                                         const int* __restrict__ live, int* __restrict__ gen) {
   __shared__ float cs[8 * BKMAX];
   __shared__ int ci[8 * BKMAX];
   const int b = blockIdx.x, tid = threadIdx.x, n = rpi * K;
+  if (ITEMS && !live[b]) {
+    if (tid < K) {
+      out_s[(long)b * K + tid] = 0.f;
+      out_i[(long)b * K + tid] = -1;
+    }
+    return;
+  }
   if (tid < n) {
     const long src = (long)b * n + tid;                      // row b * rpi + tid / K, its rank tid % K
     cs[tid] = part_s[src];
@@ -145,8 +169,12 @@ __global__ __launch_bounds__(128) void beam_merge_kernel(const float* __restrict
       out_i[(long)b * K + rank] = i;
     }
   }
-  if (b == 0 && pos && kvlen)
+  if (ITEMS) {
+    if (tid < rpi) { pos[b * rpi + tid] += 1; kvlen[b * rpi + tid] += 1; }
+    if (tid == 0) gen[b] += 1;
+  } else if (b == 0 && pos && kvlen) {
     for (int r = tid; r < n_adv; r += blockDim.x) { pos[r] += 1; kvlen[r] += 1; }
+  }
 }
 
 extern "C" int mh_beam_topk(const float* logits, long ldl, const float* scores, float* part_s, int* part_i, float* out_s, int* out_i,
@@ -155,9 +183,28 @@ extern "C" int mh_beam_topk(const float* logits, long ldl, const float* scores, 
   if (!logits || !scores || !part_s || !part_i || !out_s || !out_i || V <= 0 || ldl < V) return MH_ERR_ARG;
   if (nb < 1 || nb > 8 || (rpi != 1 && rpi != nb) || V > BNT * BVPT || V < 2 * nb || n_adv < 0) return MH_ERR_UNSUPPORTED;
   const int K = 2 * nb;
-  hipLaunchKernelGGL(beam_row_topk_kernel, dim3(B * rpi), dim3(BNT), 0, stream, logits, ldl, scores, part_s, part_i, V, K, ban_id);
+  hipLaunchKernelGGL(beam_row_topk_kernel<false>, dim3(B * rpi), dim3(BNT), 0, stream, logits, ldl, scores, part_s, part_i, V, K,
+                     ban_id, rpi, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr);
   MH_CHECK_LAUNCH();
-  hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(128), 0, stream, part_s, part_i, out_s, out_i, rpi, V, K, pos, kvlen, n_adv);
+  hipLaunchKernelGGL(beam_merge_kernel<false>, dim3(B), dim3(128), 0, stream, part_s, part_i, out_s, out_i, rpi, V, K, pos, kvlen,
+                     n_adv, (const int*)nullptr, (int*)nullptr);
+  MH_CHECK_LAUNCH();
+  return MH_OK;
+}
+
+extern "C" int mh_beam_topk_items(const float* logits, long ldl, const float* scores, float* part_s, int* part_i, float* out_s,
+                                  int* out_i, int G, int nb, int V, const int* live, int* gen, const int* prm, int* pos, int* kvlen,
+                                  hipStream_t stream) {
+  if (G <= 0) return MH_OK;
+  if (!logits || !scores || !part_s || !part_i || !out_s || !out_i || !live || !gen || !prm || !pos || !kvlen || V <= 0 || ldl < V)
+    return MH_ERR_ARG;
+  if (nb < 1 || nb > 8 || V > BNT * BVPT || V < 2 * nb) return MH_ERR_UNSUPPORTED;
+  const int K = 2 * nb;
+  hipLaunchKernelGGL(beam_row_topk_kernel<true>, dim3(G * nb), dim3(BNT), 0, stream, logits, ldl, scores, part_s, part_i, V, K, -1,
+                     nb, live, (const int*)gen, prm);
+  MH_CHECK_LAUNCH();
+  hipLaunchKernelGGL(beam_merge_kernel<true>, dim3(G), dim3(128), 0, stream, part_s, part_i, out_s, out_i, nb, V, K, pos, kvlen, 0,
+                     live, gen);
   MH_CHECK_LAUNCH();
   return MH_OK;
 }
@@ -169,14 +216,17 @@ extern "C" int mh_beam_topk(const float* logits, long ldl, const float* scores, 
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
 
 // grid (ceil(T_cap / RKP), ceil(C / (8 * RKT)), L * B); caches[l] = layer l's [B*nb, T_cap, C] bf16 base
+// ITEMS: item b's window is [lo_p[b], hi_p[b]) and an item with live[b] == 0 is not touched
+template <bool ITEMS>
 __global__ __launch_bounds__(RKT) void beam_reorder_kv_kernel(bf16_t* const* __restrict__ caches, int B, int nb, long T_cap, int C,
                                                               const int* __restrict__ src, const int* __restrict__ lo_p,
-                                                              const int* __restrict__ hi_p) {
-  const int lo = max(*lo_p, 0);
-  const long hi = min((long)*hi_p, T_cap);
+                                                              const int* __restrict__ hi_p, const int* __restrict__ live) {
+  const int l = blockIdx.z / B, b = blockIdx.z % B;
+  if (ITEMS && !live[b]) return;
+  const int lo = max(ITEMS ? lo_p[b] : *lo_p, 0);
+  const long hi = min((long)(ITEMS ? hi_p[b] : *hi_p), T_cap);
   const long p0 = (long)blockIdx.x * RKP;
   if (p0 >= hi || p0 + RKP <= lo) return;                   // blocks outside [lo, hi) exit at once
-  const int l = blockIdx.z / B, b = blockIdx.z % B;
   const int col = (blockIdx.y * RKT + threadIdx.x) * 8;
   if (col >= C) return;
   bf16_t* base = caches[l];
@@ -210,7 +260,20 @@ extern "C" int mh_beam_reorder_kv(void* const* caches, int L, int B, int nb, lon
   if (!caches || !src || !lo || !hi || C <= 0) return MH_ERR_ARG;
   if (nb < 1 || nb > 8 || (C % 8) != 0 || (long)L * B > 65535) return MH_ERR_UNSUPPORTED;
   const dim3 grid((unsigned)((T_cap + RKP - 1) / RKP), (unsigned)((C + 8 * RKT - 1) / (8 * RKT)), (unsigned)(L * B));
-  hipLaunchKernelGGL(beam_reorder_kv_kernel, grid, dim3(RKT), 0, stream, (bf16_t* const*)caches, B, nb, T_cap, C, src, lo, hi);
+  hipLaunchKernelGGL(beam_reorder_kv_kernel<false>, grid, dim3(RKT), 0, stream, (bf16_t* const*)caches, B, nb, T_cap, C, src, lo,
+                     hi, (const int*)nullptr);
+  MH_CHECK_LAUNCH();
+  return MH_OK;
+}
+
+extern "C" int mh_beam_reorder_kv_items(void* const* caches, int L, int G, int nb, long T_cap, int C, const int* src, const int* lo,
+                                        const int* hi, const int* live, hipStream_t stream) {
+  if (L <= 0 || G <= 0 || T_cap <= 0) return MH_OK;
+  if (!caches || !src || !lo || !hi || !live || C <= 0) return MH_ERR_ARG;
+  if (nb < 1 || nb > 8 || (C % 8) != 0 || (long)L * G > 65535) return MH_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)((T_cap + RKP - 1) / RKP), (unsigned)((C + 8 * RKT - 1) / (8 * RKT)), (unsigned)(L * G));
+  hipLaunchKernelGGL(beam_reorder_kv_kernel<true>, grid, dim3(RKT), 0, stream, (bf16_t* const*)caches, G, nb, T_cap, C, src, lo, hi,
+                     live);
   MH_CHECK_LAUNCH();
   return MH_OK;
 }

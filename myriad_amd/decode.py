@@ -11,8 +11,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .decode_host import (RefillPlanner, ScorePlan, SessionTable, SlotScheduler, TurnPlanner, _host_draw, _request_generator,
-                          beam_sample_select, common_prefix, seeded_requests, split_kv_rows_rule, split_kv_rule)
+from .decode_host import (BeamItem, BeamSlotScheduler, RefillPlanner, ScorePlan, SessionTable, SlotScheduler, TurnPlanner, _host_draw,
+                          _request_generator, beam_sample_select, common_prefix, seeded_requests, split_kv_rows_rule, split_kv_rule)
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -943,7 +943,13 @@ class SlotDecoder:
     slot caches from call to call (`sessions`, a SessionTable), a turn prefills only the rows past the prefix its new context
     shares with them -- solo with `past`, or several turns per pass through _prefill_packed(..., pasts), one
     mh_attn_prefill_ragged_past per layer -- and then decodes in the same captured step as `run`.  `run` itself starts every slot
-    at row 0, so it drops what the sessions had cached."""
+    at row 0, so it drops what the sessions had cached.
+
+    Beam search (opt-in, `run(num_beams=nb > 1)` behind `LlamaHIP.slot_beams`, MYRIAD_SLOT_BEAMS=1): the slots form G = slots / nb
+    groups of nb rows and a group holds one request's search (decode_host.BeamItem, beam_generate's rule per request), refilled
+    as soon as that request ends.  The captured step is beam_generate's with per-group state: mh_beam_reorder_kv_items over each
+    group's [lo, pos), the slot step's layers and lm-head under a per-row live mask, mh_beam_topk_items (each group's EOS ban
+    from its own gen).  One view and one graph per nb, in `beam_views`: no key of `views` changes.  See _run_beams."""
 
     def __init__(self, llama: "LlamaHIP", slots: int, capacity: int, split_kv: Optional[bool] = False):
         slots = int(slots)
@@ -958,6 +964,7 @@ class SlotDecoder:
             raise ValueError(f"capacity={capacity}: a slot holds at most 8192 positions")
         self.bufs = None                                             # the step's buffers, shared by every view
         self.views = {}                                              # inv_temp -> workspace view of bufs with its own graph
+        self.beam_views = {}                                         # (num_beams, split) -> the beam step's view (_beam_workspace)
         self.ws = None                                               # the view of the current / last run
         self._weights = None
         self.graph_captures = 0
@@ -980,6 +987,44 @@ class SlotDecoder:
             key = ("scores", key)
         return ("split", key) if split else key
 
+    def _base_buffers(self) -> dict:
+        """The step's buffers, shared by every view and kept while the decode weights stay the ones the captured graphs read."""
+        L = self.llama
+        L._prepare_decode_weights(self.slots, ops.GEMV_WIDE_MAX_ROWS)
+        if not (_packed_step(L, self.slots, ops.GEMV_WIDE_MAX_ROWS) and L.decode_fused):
+            raise ValueError("the slot engine needs the fused packed token step (MYRIAD_PACK_DECODE and MYRIAD_DECODE_FUSED on)")
+        wid = _decode_weights_id(L)
+        if self.bufs is None or self._weights != wid:
+            self.bufs, self.views, self.beam_views, self.ws = None, {}, {}, None
+            # its row limit: above GEMV_MAX_ROWS slots the step stays on the packed copies
+            self.bufs = _decode_buffers(L, self.slots, self.T_cap, row_limit=ops.GEMV_WIDE_MAX_ROWS)
+            self.bufs["live"] = torch.zeros((self.slots,), dtype=torch.int32, device=L.dev)
+            self._weights = wid
+        return self.bufs
+
+    def _beam_workspace(self, nb: int, split: bool) -> dict:
+        """The beam step's view of the buffers for groups of nb rows, with its own graph: beam_generate's buffers (`bupd` = the
+        per-step upload ids | parent rows | running scores with its pinned host twin, the top-K scratch, the record `brec`, the
+        cache pointer table) and the per-group state mh_beam_topk_items / mh_beam_reorder_kv_items read -- `lo`, `hi`, `gen`,
+        `glive` [G] and `bprm` = (min_length, eos_id) -- next to the per-row `pos` / `kvlen` / `live` every view shares.  `rec0`
+        and `zero` serve the refills' first selection, `bsrc` (every row's group's first row) the prompt broadcast."""
+        L, bufs, key = self.llama, self._base_buffers(), (int(nb), bool(split))
+        if key not in self.beam_views:
+            dev, i32, R, G, K = L.dev, torch.int32, self.slots, self.slots // nb, 2 * nb
+            bupd = torch.zeros((4 * R,), dtype=i32, device=dev)
+            view = _buffer_view(L, bufs, split)
+            view.update(bupd=bupd, bupd_host=torch.zeros((4 * R,), dtype=i32).pin_memory(), ids=bupd[:2 * R].view(torch.long),
+                        src=bupd[2 * R:3 * R], bscore=bupd[3 * R:].view(F32),
+                        part_s=torch.empty((R * K,), dtype=F32, device=dev), part_i=torch.empty((R * K,), dtype=i32, device=dev),
+                        brec=torch.zeros((2, G * K), dtype=i32, device=dev), rec0=torch.zeros((2, G * K), dtype=i32, device=dev),
+                        zero=torch.zeros((G,), dtype=F32, device=dev), bprm=torch.zeros((2,), dtype=i32, device=dev),
+                        bsrc=torch.arange(G, dtype=i32).repeat_interleave(nb).mul_(nb).to(dev),
+                        table=torch.tensor([c.data_ptr() for c in bufs["caches"]], dtype=torch.long).to(dev),
+                        **{k: torch.zeros((G,), dtype=i32, device=dev) for k in ("lo", "hi", "gen", "glive")})
+            self.beam_views[key] = view
+        self.ws = self.beam_views[key]
+        return self.ws
+
     def _workspace(self, inv_temp: float, rows_tail=None, split: bool = False, scores: bool = False) -> dict:
         """The step's buffers, kept while the decode weights stay the ones the captured graphs read, and over them one view (its
         own graph / warm flag) per inv_temp: the arg-max kernel takes inv_temp as a launch argument, so a captured step is fixed
@@ -990,16 +1035,7 @@ class SlotDecoder:
         a split view holds it and a non-split view holds None, so each (key, split) has its own graph.  `scores`: the view's step
         also writes the token scores into a record of its own (_score_buffers; `sc0` takes the refills' first picks' scores)."""
         L = self.llama
-        L._prepare_decode_weights(self.slots, ops.GEMV_WIDE_MAX_ROWS)
-        if not (_packed_step(L, self.slots, ops.GEMV_WIDE_MAX_ROWS) and L.decode_fused):
-            raise ValueError("the slot engine needs the fused packed token step (MYRIAD_PACK_DECODE and MYRIAD_DECODE_FUSED on)")
-        wid = _decode_weights_id(L)
-        if self.bufs is None or self._weights != wid:
-            self.bufs, self.views, self.ws = None, {}, None
-            # its row limit: above GEMV_MAX_ROWS slots the step stays on the packed copies
-            self.bufs = _decode_buffers(L, self.slots, self.T_cap, row_limit=ops.GEMV_WIDE_MAX_ROWS)
-            self.bufs["live"] = torch.zeros((self.slots,), dtype=torch.int32, device=L.dev)
-            self._weights = wid
+        self._base_buffers()
         if rows_tail is not None and "prm" not in self.bufs:
             n, i32 = self.slots, torch.int32
             self.bufs.update(prm=torch.zeros((6,), dtype=F32, device=L.dev), seed=torch.zeros((n,), dtype=torch.long, device=L.dev),
@@ -1021,7 +1057,9 @@ class SlotDecoder:
     def run(self, requests, max_new_tokens: int = 90, stop_ids=((835,), (2277, 29937)), eos_id: int = 2, min_length: int = 1,
             do_sample: bool = False, top_p: float = 1.0, temperature: float = 1.0, top_k: int = 50,
             generator: Optional[torch.Generator] = None, ordered: bool = False, prefill_batch: int = 1, refill_min: int = 1,
-            prefill_rows: int = 2048, repetition_penalty: float = 1.0, seeds=None, return_scores: bool = False, watch_ids=()):
+            prefill_rows: int = 2048, repetition_penalty: float = 1.0, seeds=None, return_scores: bool = False, watch_ids=(),
+            num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False, num_return_sequences: int = 1,
+            pad_id: Optional[int] = None):
         """Decode every request of `requests` (an iterable of [S0_i, D] f32 embeddings, lengths free) and yield
         (index, ids[L_i] int64 on the CPU, margins[L_i] f32) as each finishes -- or, with `ordered`, in input order.  The
         arguments are greedy_generate's; the stop rule is per request.  `last_stats` holds the run's counters: `prefills` counts
@@ -1039,8 +1077,19 @@ class SlotDecoder:
 
         `return_scores`, `watch_ids` (greedy_generate's; a view and a graph of their own): every yielded tuple gains a fourth
         item, dict(token_logprobs [L_i] f32, watch_logprobs [L_i, W] f32) of that request -- what greedy_generate returns for it
-        alone."""
+        alone.
+
+        `num_beams` = nb > 1 (behind `slot_beams`; with `length_penalty`, `early_stopping`, `num_return_sequences`, `pad_id`,
+        beam_generate's): beam search, one request per group of nb slots (_run_beams).  The run then yields (index, ids [nrs, Lmax]
+        right-padded with pad_id, sequence scores [nrs] f32, lengths [nrs]) per request -- what beam_generate returns for it
+        alone -- and `last_stats` gains `num_beams`, `groups`, `finished_hypotheses`; `occupancy` counts groups."""
         self.sessions.clear()                                        # the slots' caches are overwritten from row 0
+        if int(num_beams) != 1:
+            yield from self._run_beams(requests, int(num_beams), max_new_tokens, stop_ids, eos_id, min_length, ordered, prefill_batch,
+                                       refill_min, prefill_rows, length_penalty, early_stopping, num_return_sequences, pad_id,
+                                       refused=dict(do_sample=bool(do_sample), repetition_penalty=float(repetition_penalty) != 1.0,
+                                                    return_scores=bool(return_scores), seeds=seeds is not None))
+            return
         yield from self._run(requests, None, None, max_new_tokens, stop_ids, eos_id, min_length, do_sample, top_p, temperature,
                              top_k, generator, ordered, prefill_batch, refill_min, prefill_rows, repetition_penalty, seeds,
                              return_scores, watch_ids)
@@ -1063,6 +1112,9 @@ class SlotDecoder:
         turns = [tuple(t) for t in turns]
         if "refill_min" in kw:
             raise ValueError("run_turns: refill_min does not apply, every turn has its own slot")
+        if int(kw.pop("num_beams", 1) or 1) != 1:
+            raise NotImplementedError("run_turns: beam search runs in `run` only (a conversation would have to carry the winning "
+                                      "hypothesis's cache rows into its next turn)")
         for t in turns:
             if len(t) not in (3, 4) or t[1].dim() != 2 or len(t[2]) != t[1].shape[0]:
                 raise ValueError("run_turns: a turn is (session, emb [S0, D], keys [S0]) or (session, emb, keys, reset_reason)")
@@ -1070,6 +1122,155 @@ class SlotDecoder:
         if len(set(keys)) != len(keys):
             raise ValueError("run_turns: at most one turn per session in one call")
         return self._run(None, turns, weights_version, **kw)
+
+    def beam_args(self, nb: int, refused=None) -> int:
+        """The checks of run(num_beams = nb > 1) that need no request; returns the group count."""
+        L = self.llama
+        if nb < 1:
+            raise ValueError(f"num_beams must be >= 1, got {nb}")
+        if not getattr(L, "slot_beams", False):
+            raise NotImplementedError(f"decode slots: num_beams={nb} needs the slot beams switch (MYRIAD_SLOT_BEAMS=1 or "
+                                      "llama.slot_beams = True)")
+        if nb > ops.BEAM_MAX:
+            raise NotImplementedError(f"num_beams={nb}: at most {ops.BEAM_MAX} beams on the HIP decode path")
+        if self.slots % nb:
+            raise ValueError(f"slots={self.slots} do not divide into groups of num_beams={nb} rows")
+        for name, on in (refused or {}).items():
+            if on:
+                raise NotImplementedError(f"decode slots: num_beams={nb} with {name} is not implemented (beam sampling, the penalty "
+                                          "and token scores under beams are beam_generate's)")
+        return self.slots // nb
+
+    @torch.no_grad()
+    def _run_beams(self, requests, nb, max_new_tokens, stop_ids, eos_id, min_length, ordered, prefill_batch, refill_min, prefill_rows,
+                   length_penalty, early_stopping, num_return_sequences, pad_id, refused=None):
+        """run(num_beams = nb > 1): the slot loop over G groups of nb rows (BeamSlotScheduler, driven by RefillPlanner unchanged).
+
+        The captured step: hi = pos of each group's first row (one strided copy), mh_beam_reorder_kv_items over [lo, hi) by the
+        parent rows, the slot view's _step_logits under the per-row live mask (nb equal entries per group), mh_beam_topk_items.
+        Between two replays the host reads the [2, G, K] record with one copy and uploads (ids, src, running scores) of all rows
+        with one copy, as beam_generate does; beside that it writes a finished group's live flags and a refilled group's state.
+        min_length and eos_id sit in device memory, length_penalty / early_stopping / num_return_sequences on the host: a run
+        with other values replays the same graph.
+
+        A refill -- solo into cache row g * nb, or packed through _prefill_packed -- is: the prefill, ONE eager mh_beam_topk at
+        rpi = 1 over the refilled prompts' logits, BeamItem's first selection, one eager mh_beam_reorder_kv_items that broadcasts
+        the prompts' rows [0, S0_g) to the groups' sibling rows, then pos = S0, kvlen = S0 + 1, lo = S0, gen = 1, live = 1."""
+        L = self.llama
+        G = self.beam_args(nb, refused)
+        K, V, i32 = 2 * nb, L.V, torch.int32
+        pad = int(eos_id) if pad_id is None else int(pad_id)
+
+        def make_item():
+            return BeamItem(nb, V, max_new_tokens, stop_ids, eos_id, length_penalty, early_stopping, num_return_sequences)
+
+        make_item()                                                  # its argument checks, before any launch
+        split = self.split_kv
+        if split is None:
+            split = split_kv_rows_rule(self.slots, L.H, 0)
+        ws = self._beam_workspace(nb, split)
+        sched = BeamSlotScheduler(G, make_item, ordered=ordered)
+        plan = RefillPlanner(sched, ((emb,) for emb in requests), prefill_batch, prefill_rows, refill_min,
+                             length=lambda q: int(q[0].shape[0]))
+        packed = int(prefill_batch) != 1 or int(refill_min) != 1
+        stats = dict(steps=0, graph_replays=0, graph_captures=self.graph_captures, prefills=0, live_row_steps=0, occupancy=0.0,
+                     prefill_passes=0, packed_rows=0, split_kv=bool(split), num_beams=nb, groups=G, finished_hypotheses=0)
+        self.last_stats = stats
+        caches, nl, T_cap, C, R = ws["caches"], len(ws["caches"]), self.T_cap, 2 * L.D, self.slots
+        host = ws["bupd_host"]
+        h_ids, h_src, h_sc = host[:2 * R].view(torch.long).numpy(), host[2 * R:3 * R].numpy(), host[3 * R:].view(F32).numpy()
+        h_ids[:], h_src[:], h_sc[:] = 0, np.arange(R), 0.0           # idle rows: themselves as parents
+        ws["live"].zero_()                                           # an abandoned run may have left rows live
+        ws["glive"].zero_()
+        ws["bprm"].copy_(torch.tensor([int(min_length), int(eos_id)], dtype=i32))
+        ban0 = int(eos_id) if 0 < min_length else -1
+        room = min(T_cap, L.cos.shape[0])
+
+        def record(rec):
+            rec = rec.cpu()                                          # the one device->host copy (it also waits for the step)
+            return rec[0].view(F32).numpy().reshape(G, K), rec[1].numpy().reshape(G, K).astype(np.int64)
+
+        def feed(g):                                                 # the group's rows of the next upload
+            ids, src, run = sched.feed[g]
+            rows = slice(g * nb, (g + 1) * nb)
+            h_ids[rows], h_src[rows], h_sc[rows] = ids, g * nb + np.asarray(src), run
+
+        def refill(group):
+            lens = []
+            for _, (emb,) in group:
+                S0 = emb.shape[0] if emb.dim() == 2 else 0
+                if S0 < 1 or S0 + max_new_tokens > room:
+                    raise ValueError(f"request of shape {tuple(emb.shape)} + max_new_tokens {max_new_tokens} does not fit a slot of "
+                                     f"{room} positions")
+                lens.append(S0)
+            if packed:
+                logits0 = L._prefill_packed([req[0] for _, req in group], [g * nb for g, _ in group], caches)
+            else:
+                (g, req), = group
+                logits0 = L._prefill(req[0][None].to(L.dev), [c[g * nb:g * nb + 1] for c in caches])
+            n = len(group)
+            stats["prefills"] += n
+            ops.beam_topk(logits0, ws["zero"], ws["part_s"], ws["part_i"], ws["rec0"][0].view(F32), ws["rec0"][1], n, nb, ban_id=ban0)
+            top_s, top_i = record(ws["rec0"])
+            on = [(g, S0) for i, ((g, _), S0) in enumerate(zip(group, lens)) if sched.admit(g, top_s[i], top_i[i])]
+            if not on:
+                return
+            state = torch.zeros((3, G), dtype=i32)                   # the broadcast's lo = 0 | hi = S0 | live, per group
+            for g, S0 in on:
+                state[1, g], state[2, g] = S0, 1
+            state = ops.h2d(state, L.dev)
+            if nl:
+                ops.beam_reorder_kv_items(ws["table"], nl, G, nb, T_cap, C, ws["bsrc"], state[0], state[1], state[2])
+            for g, S0 in on:
+                rows = slice(g * nb, (g + 1) * nb)
+                ws["pos"][rows].fill_(S0)                            # position of the incoming token
+                ws["kvlen"][rows].fill_(S0 + 1)                      # valid keys after the append
+                ws["lo"][g:g + 1].fill_(S0)                          # the prompt prefix is the same in every row of the group
+                ws["gen"][g:g + 1].fill_(1)                          # the prefill's selection was token 0
+                ws["live"][rows].fill_(1)
+                ws["glive"][g:g + 1].fill_(1)
+                feed(g)
+
+        def token_step(_ban):
+            if nl:
+                ws["hi"].copy_(ws["pos"][::nb])                      # each group's position: generated rows are [lo, pos)
+                ops.beam_reorder_kv_items(ws["table"], nl, G, nb, T_cap, C, ws["src"], ws["lo"], ws["hi"], ws["glive"])
+            L._step_logits(ws)
+            ops.beam_topk_items(ws["logits"], ws["bscore"], ws["part_s"], ws["part_i"], ws["brec"][0].view(F32), ws["brec"][1], G, nb,
+                                ws["glive"], ws["gen"], ws["bprm"], ws["pos"], ws["kvlen"])
+
+        def results():
+            for index, seqs, scores in sched.pop():
+                ids = torch.full((len(seqs), max(1, max(len(q) for q in seqs))), pad, dtype=torch.long)
+                for r, q in enumerate(seqs):
+                    ids[r, :len(q)] = torch.tensor(q, dtype=torch.long)
+                yield index, ids, torch.from_numpy(np.asarray(scores, dtype=np.float32)), [len(q) for q in seqs]
+
+        try:
+            while True:
+                group = plan.next_pass()
+                while group:
+                    refill(group)
+                    group = plan.next_pass()
+                yield from results()
+                live = sched.live()
+                if not live:
+                    break
+                ws["bupd"].copy_(ws["bupd_host"], non_blocking=True)    # ids | src | running scores: one host->device copy
+                if L._launch_step(ws, token_step, -1, True, stats):
+                    self.graph_captures += 1
+                finished = sched.step(*record(ws["brec"]))
+                for g in live:
+                    if g in finished:
+                        ws["live"][g * nb:(g + 1) * nb].zero_()
+                        ws["glive"][g:g + 1].zero_()
+                    else:
+                        feed(g)
+                yield from results()
+        finally:
+            stats.update(steps=sched.steps, live_row_steps=sched.live_row_steps, occupancy=sched.occupancy,
+                         graph_captures=self.graph_captures, prefill_passes=plan.passes, packed_rows=plan.packed_rows,
+                         finished_hypotheses=sched.finished_hypotheses)
 
     @torch.no_grad()
     def _run(self, requests, turns, weights_version, max_new_tokens: int = 90, stop_ids=((835,), (2277, 29937)), eos_id: int = 2,

@@ -1,8 +1,9 @@
 """The host side of the decode loops, on plain Python values: nothing here sees a device or the HIP library, so a scripted run can
 drive every class.  The slot engine's bookkeeping (SlotScheduler), its refill and turn planners (RefillPlanner, TurnPlanner), the
 chat pool's session table (SessionTable), the per-request random streams (seeded_requests), the replay of a known run
-(replay_slot_run), the split-KV rules with their measurements, the host draw of one row (_host_draw) and the beam-sampling
-step of one item (beam_sample_select)."""
+(replay_slot_run), the split-KV rules with their measurements, the host draw of one row (_host_draw), the beam-sampling
+step of one item (beam_sample_select), and beam search in the slots: one request's search state (BeamItem) and the scheduler of
+the groups of num_beams rows (BeamSlotScheduler)."""
 from __future__ import annotations
 
 from typing import Optional
@@ -206,6 +207,140 @@ class SlotScheduler:
                 out.append(self._done.pop(self._next_out))
                 self._next_out += 1
         return out
+
+    @property
+    def occupancy(self) -> float:
+        return self.live_row_steps / (self.steps * self.slots) if self.steps else 0.0
+
+
+class BeamItem:
+    """One request's beam search on the host: the rule of LlamaDecode.beam_generate's `select` (HF GenerationMixin._beam_search;
+    tests/beam_ref.py states it) for a single item, on numpy values.  `select(top_s, top_i)` takes one step's record for the item
+    -- its K = 2 * nb best (score, flat index = row_in_item * V + token), best first -- and answers (ids [nb], src [nb], running
+    scores [nb], going): the tokens its nb rows are fed next, the row of the item each continues (0 .. nb - 1) and whether the
+    search goes on.  A candidate stops on EOS, on a stop sequence at the end of ITS ids or at max_new_tokens; a stopped candidate
+    among the best nb enters the pool at score / len ** length_penalty; `early_stopping` and the "can still improve" test are
+    HF's.  `result()` is the best num_return_sequences hypotheses: (their ids as tuples, scores f32 [nrs])."""
+
+    NEG = np.float32(-1.0e9)
+
+    def __init__(self, num_beams: int, vocab: int, max_new_tokens: int, stop_ids=(), eos_id: int = 2, length_penalty: float = 1.0,
+                 early_stopping=False, num_return_sequences: int = 1):
+        nb, nrs = int(num_beams), int(num_return_sequences)
+        if nb < 1 or int(vocab) < 2 * nb or int(max_new_tokens) < 1:
+            raise ValueError(f"num_beams={nb} needs num_beams >= 1, a vocabulary of at least {2 * nb} tokens and max_new_tokens >= 1")
+        if not 1 <= nrs <= nb:
+            raise ValueError(f"num_return_sequences={nrs} must be between 1 and num_beams={nb}")
+        if early_stopping not in (True, False, "never"):
+            raise ValueError(f"early_stopping must be True, False or 'never', got {early_stopping!r}")
+        self.nb, self.K, self.V, self.nrs = nb, 2 * nb, int(vocab), nrs
+        self.max_new_tokens, self.eos_id, self.lp, self.early_stopping = int(max_new_tokens), int(eos_id), float(length_penalty), early_stopping
+        self.stops = [tuple(int(t) for t in st) for st in stop_ids]
+        self.run_seqs = [()] * nb
+        self.fin_scores = np.full((nb,), self.NEG, dtype=np.float32)
+        self.fin_seqs = [()] * nb
+        self.is_fin = np.zeros((nb,), dtype=bool)
+        self.unsat = True                                            # the early-stop heuristic still allows an improvement
+        self.gen = 0                                                 # tokens generated so far (= selections made)
+
+    def select(self, top_s, top_i):
+        nb, K, NEG, lp = self.nb, self.K, self.NEG, self.lp
+        top_s, top_i = np.asarray(top_s, dtype=np.float32).reshape(K), np.asarray(top_i, dtype=np.int64).reshape(K)
+        self.gen += 1
+        gen_len = self.gen
+        par, tok = top_i // self.V, top_i % self.V
+        cand = [self.run_seqs[int(par[k])] + (int(tok[k]),) for k in range(K)]
+        hits = np.array([c[-1] == self.eos_id or gen_len >= self.max_new_tokens
+                         or any(len(c) >= len(st) and c[-len(st):] == st for st in self.stops) for c in cand])
+        run_lp = top_s + hits.astype(np.float32) * NEG
+        nxt = np.argsort(-run_lp, kind="stable")[:nb]
+        self.run_seqs = [cand[k] for k in nxt]
+        ids, src, run = tok[nxt], par[nxt], run_lp[nxt]
+        did = hits.copy()
+        did[nb:] = False                                             # only the top nb candidates may enter the pool
+        sc = top_s / np.float32(gen_len ** lp)
+        if self.is_fin.all() and self.early_stopping is True:
+            sc = sc + NEG
+        if not self.unsat:
+            sc = sc + NEG
+        sc = sc + (~did).astype(np.float32) * NEG
+        merged = np.concatenate([self.fin_scores, sc])
+        keep = np.argsort(-merged, kind="stable")[:nb]
+        mseqs, mfin = self.fin_seqs + cand, np.concatenate([self.is_fin, did])
+        self.fin_scores, self.fin_seqs, self.is_fin = merged[keep], [mseqs[k] for k in keep], mfin[keep]
+        best_len = self.max_new_tokens if (self.early_stopping == "never" and lp > 0.0) else gen_len
+        best_run = np.float32(run[0]) / np.float32(best_len ** lp)
+        worst = self.fin_scores.min()
+        self.unsat = self.unsat and bool(np.any(np.where(self.is_fin, best_run > worst, best_run > NEG)))
+        going = self.unsat and not (bool(self.is_fin.all()) and self.early_stopping is True) and not bool(hits.all())
+        return ids, src, run, bool(going and gen_len < self.max_new_tokens)
+
+    @property
+    def finished(self) -> int:
+        return int(self.is_fin.sum())
+
+    def result(self):
+        return [self.fin_seqs[i] for i in range(self.nrs)], self.fin_scores[:self.nrs].copy()
+
+
+class BeamSlotScheduler:
+    """SlotScheduler over G = slots / num_beams beam groups: a group of num_beams rows holds one request's search (a BeamItem
+    made by `make_item()`), and is free again as soon as its item ends.  Same round as SlotScheduler: `admit(group, top_s, top_i)`
+    with the prefill's record (the K best first tokens; the item's first selection -- False: the request ended there and never
+    occupies the group), then, while `live()`, `step(top_s [G, K], top_i [G, K])` with one token step's record (idle groups'
+    entries are ignored), which returns the groups that finished.  After either, `feed[g]` = (ids, src, running scores) is what
+    the group's rows take next, src counted within the group.  `pop()` hands out (index, sequences, scores f32 [nrs]) in
+    completion order, or with `ordered` in admission order.  `slots` counts groups: RefillPlanner drives it unchanged."""
+
+    def __init__(self, groups: int, make_item, ordered: bool = False):
+        if groups < 1:
+            raise ValueError(f"groups must be >= 1, got {groups}")
+        self.slots, self.make_item, self.ordered = int(groups), make_item, bool(ordered)
+        self.rows = [None] * self.slots                              # per group: [index, item] while it searches
+        self.feed = [None] * self.slots
+        self.admitted = 0
+        self._done, self._next_out = {}, 0
+        self.steps = self.live_row_steps = self.finished_hypotheses = 0
+
+    def free(self) -> list:
+        return [g for g in range(self.slots) if self.rows[g] is None]
+
+    def live(self) -> list:
+        return [g for g in range(self.slots) if self.rows[g] is not None]
+
+    def _finish(self, index: int, item) -> None:
+        seqs, scores = item.result()
+        self.finished_hypotheses += item.finished
+        self._done[index] = (index, seqs, scores)
+
+    def admit(self, group: int, top_s, top_i) -> bool:
+        if self.rows[group] is not None:
+            raise ValueError(f"group {group} is busy")
+        item, index = self.make_item(), self.admitted
+        self.admitted += 1
+        *feed, going = item.select(top_s, top_i)
+        if not going:
+            self._finish(index, item)
+            return False
+        self.rows[group], self.feed[group] = [index, item], tuple(feed)
+        return True
+
+    def step(self, top_s, top_i) -> list:
+        live = self.live()
+        self.steps += 1
+        self.live_row_steps += len(live)
+        finished = []
+        for g in live:
+            index, item = self.rows[g]
+            *feed, going = item.select(top_s[g], top_i[g])
+            self.feed[g] = tuple(feed)
+            if not going:
+                self._finish(index, item)
+                self.rows[g] = self.feed[g] = None
+                finished.append(g)
+        return finished
+
+    pop = SlotScheduler.pop
 
     @property
     def occupancy(self) -> float:

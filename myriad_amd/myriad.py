@@ -1542,8 +1542,12 @@ class MyriadHIP(nn.Module):
         ends on EOS, on a stop sequence at the end of ITS ids or at max_new_tokens, and its slot takes the next row at once.
 
         Yields {"index", "token_ids": [L] int64 (CPU), "ve_anomaly_map"} per sample in input order (index counts samples
-        over all batches), so a sampled run is reproducible per `generator`.  Takes generate()'s keyword arguments without beams:
-        num_beams > 1 is refused (NotImplementedError), repetition_penalty != 1 needs the device sampling switch, as in
+        over all batches), so a sampled run is reproducible per `generator`.  Takes generate()'s keyword arguments.  num_beams > 1
+        is refused (NotImplementedError) unless `self.llama.slot_beams` (MYRIAD_SLOT_BEAMS=1, off by default) is on: then every
+        sample is a beam search in its own group of num_beams slots (SlotDecoder.run; `slots` a multiple of num_beams), with
+        length_penalty, early_stopping and num_return_sequences as in generate(); "token_ids" is what generate() returns in that
+        sample's rows ([L] for one returned sequence, else [nrs, L], padded with EOS) and "sequences_scores" [nrs] comes with it;
+        do_sample, repetition_penalty != 1 and seeds are refused there.  repetition_penalty != 1 needs the device sampling switch, as in
         generate(), and so does min_length > 1 here (SlotDecoder.run itself takes it on every path).  With that switch on, a
         sampled run draws every token on the device and each sample from its own stream: sample i takes the i-th seed drawn from `generator` (or the i-th of `seeds`, an iterable of ints), so its answer does not
         depend on the slot count, the refill settings or its neighbours (SlotDecoder.run).  min_length is a per-sample EOS ban.
@@ -1554,8 +1558,18 @@ class MyriadHIP(nn.Module):
         output_scores / watch_ids as in generate(): each yielded dict gains "token_logprobs" [L] and "watch_logprobs" [L, W]."""
         self.finish_update()
         a = self._generate_args(generate_kwargs)
-        if a["num_beams"] > 1:
-            raise NotImplementedError(f"generate_stream(num_beams={a['num_beams']}): decode slots have no beam search")
+        nb, beam_kw = a["num_beams"], {}
+        if nb > 1:
+            if not getattr(self.llama, "slot_beams", False):
+                raise NotImplementedError(f"generate_stream(num_beams={nb}): beam search in the decode slots needs its switch "
+                                          "(MYRIAD_SLOT_BEAMS=1 or model.llama.slot_beams = True)")
+            if a["do_sample"] or a["rep_pen"] != 1.0 or seeds is not None:
+                raise NotImplementedError(f"generate_stream(num_beams={nb}): do_sample, repetition_penalty != 1 and seeds are not "
+                                          "implemented with beams in the decode slots")
+            if nb > ops.BEAM_MAX or int(slots) % nb:
+                raise ValueError(f"generate_stream(slots={slots}, num_beams={nb}): the slots divide into groups of num_beams <= "
+                                 f"{ops.BEAM_MAX} rows")
+            beam_kw = dict(num_beams=nb, **{k: a["beam_kw"][k] for k in ("length_penalty", "early_stopping", "num_return_sequences")})
         max_new = a["max_new"]
         if max_new is None:
             raise NotImplementedError("generate_stream(max_length=...): pass max_new_tokens, the prompts differ in length")
@@ -1590,6 +1604,20 @@ class MyriadHIP(nn.Module):
             self._slot_decoder = None
             self._slot_decoder = (key, self.llama.slot_decoder(*key))
         dec = self._slot_decoder[1]
+
+        def beam_stream():                                             # per sample what generate() returns in its rows
+            for index, ids, scores, _ in dec.run(rows(), max_new_tokens=max_new, stop_ids=a["stops"], eos_id=a["eos_id"],
+                                                 min_length=a["min_length"], ordered=True, prefill_batch=prefill_batch,
+                                                 refill_min=refill_min, **beam_kw):
+                self.last_generate_stats = dec.last_stats
+                one = beam_kw["num_return_sequences"] == 1
+                yield {"index": index, "token_ids": ids[0] if one else ids, "sequences_scores": scores,
+                       "ve_anomaly_map": side[index]}
+                side[index] = None
+            self.last_generate_stats = dec.last_stats
+
+        if nb > 1:
+            return beam_stream()
 
         def stream():
             for index, ids, _, *sc in dec.run(rows(), max_new_tokens=max_new, stop_ids=a["stops"], eos_id=a["eos_id"],

@@ -1395,6 +1395,37 @@ def beam_reorder_kv(cache_table: torch.Tensor, L: int, B: int, nb: int, T_cap: i
                "mh_beam_reorder_kv")
 
 
+def beam_topk_items(logits: torch.Tensor, scores: torch.Tensor, part_s, part_i, out_s, out_i, G: int, nb: int, live, gen, prm, pos,
+                    kvlen):
+    """beam_topk for the decode slots' G beam groups (logits [G*nb, V], one request per item): live / gen int32 [G] and prm =
+    int32 (min_length, eos_id) are read by the kernels.  A live item bans eos_id iff gen[g] < min_length, records what beam_topk
+    records for it alone, and advances its nb rows of pos / kvlen and its gen by one; an idle item records (0.0, -1) and keeps
+    everything else.  A buffer of the wrong type or too short is refused here, before any launch."""
+    _chk2d(logits, F32, "beam_topk_items: logits")
+    R, V = logits.shape
+    if G <= 0 or nb <= 0 or R != G * nb:
+        raise _lib.MyriadHipError(f"beam_topk_items: {R} logits rows are not G={G} items of nb={nb} rows")
+    i32 = torch.int32
+    for name, t, dtype, need in (("scores", scores, F32, R), ("part_s", part_s, F32, R * 2 * nb), ("part_i", part_i, i32, R * 2 * nb),
+                                 ("out_s", out_s, F32, G * 2 * nb), ("out_i", out_i, i32, G * 2 * nb), ("live", live, i32, G),
+                                 ("gen", gen, i32, G), ("prm", prm, i32, 2), ("pos", pos, i32, R), ("kvlen", kvlen, i32, R)):
+        _chk_flat(t, dtype, need, f"beam_topk_items: {name}")
+    _lib.check(_L().mh_beam_topk_items(_p(logits), logits.stride(0), _p(scores), _p(part_s), _p(part_i), _p(out_s), _p(out_i), G, nb, V,
+                                       _p(live), _p(gen), _p(prm), _p(pos), _p(kvlen), _s()), "mh_beam_topk_items")
+    return out_s, out_i
+
+
+def beam_reorder_kv_items(cache_table: torch.Tensor, L: int, G: int, nb: int, T_cap: int, C: int, src, lo, hi, live):
+    """beam_reorder_kv with a window [lo[g], hi[g]) (clamped to [0, T_cap)) and a live flag per item, int32 [G] device tensors read
+    by the kernel; an idle item and every position outside a window are not touched."""
+    _chk_flat(cache_table, torch.long, L, "beam_reorder_kv_items: cache_table")
+    _chk_flat(src, torch.int32, G * nb, "beam_reorder_kv_items: src")
+    for name, t in (("lo", lo), ("hi", hi), ("live", live)):
+        _chk_flat(t, torch.int32, G, f"beam_reorder_kv_items: {name}")
+    _lib.check(_L().mh_beam_reorder_kv_items(_p(cache_table), L, G, nb, int(T_cap), C, _p(src), _p(lo), _p(hi), _p(live), _s()),
+               "mh_beam_reorder_kv_items")
+
+
 def beam_sample_topk(logits: torch.Tensor, scores: torch.Tensor, part_k, part_a, part_i, part_f, out_s, out_i, out_f, B: int, nb: int,
                      ban_id: int = -1, draw: bool = True, params=None, seed=None, seen=None, step=None, t_add: int = 0, out_k=None,
                      pos=None, kvlen=None):

@@ -32,6 +32,10 @@ reproduce.  Give it --requests 256 or more: one wave of 64 slots would otherwise
 kind of --weights, interleaved per repeat (--repeats rounds of --step-replays replays each): up to 16 rows the 16-row kernel,
 above it ops.gemv_packed_wide.  --step-gemm 32,64 adds greedy_generate's step at those row counts: the row-major bf16 GEMMs that
 every decode loop but the slot engine runs above 16 rows.
+--slots 8,16,32 --num-beams 4 [--weights bf16,fp4] [--prefill-batch 1,8] times beam search in the slots (S / nb groups, one request
+per group, behind llama.slot_beams) against beam_generate over consecutive batches of S / nb left-padded requests and at batch 1,
+all interleaved per repeat; the stop id is then also the runner-up after every chain token, so that hypotheses finish.
+
 --scores (with --slots 8,64, the default there) measures what return_scores costs: the same request list decoded at batch 1 (the
 first --requests / 8 requests), and through each slot count, with and without the token scores (two watched ids), interleaved per
 repeat in one process, as run time and samples/s; then the captured token step of each of those views alone, every row live,
@@ -62,6 +66,9 @@ ap.add_argument("--step-gemm", default="", help="with --step-rows: row counts at
 ap.add_argument("--step-keys", type=int, default=128, help="with --step-rows: cached keys per row when the timing starts")
 ap.add_argument("--step-replays", type=int, default=40, help="with --step-rows: graph replays per timed round")
 ap.add_argument("--requests", type=int, default=64, help="requests of the --slots run")
+ap.add_argument("--num-beams", type=int, default=1, help="with --slots S[,S..]: beam search in the slots (S / nb groups, behind "
+                "llama.slot_beams) against beam_generate over batches of S / nb padded prompts and at batch 1; --weights and "
+                "--prefill-batch add their variants, all interleaved in one process")
 ap.add_argument("--prefill-batch", default="1", help="comma list: prefill_batch of the --slots run, timed interleaved")
 ap.add_argument("--refill-min", default="1", help="comma list: refill_min of the --slots run, timed interleaved")
 ap.add_argument("--scores", action="store_true", help="the cost of return_scores: batch 1 and each --slots count, with and without")
@@ -193,6 +200,73 @@ if a.slots or len(slot_counts) > 1 or a.scores:
         x[-1] = emb_rows[d]
         reqs.append(x.to(dev))
     kw = dict(max_new_tokens=new, stop_ids=((1000,),), eos_id=-5, min_length=0)
+    if a.num_beams > 1:
+        # Beams need hypotheses that finish: the stop id is also the runner-up after every chain token, so the pool fills while
+        # the chain counts down and a search ends soon after its chain does -- requests end at their own lengths, as above.
+        nb = a.num_beams
+        head = L.lm_head[1000:1001].float().cpu()
+        head[0] += 2.0 * dirs[2:].sum(0)
+        L.lm_head[1000:1001].copy_(head.to(L.lm_head.dtype).to(dev))
+        L.slot_beams = True
+        cap = 64 * ((160 + new + 2 + 63) // 64)
+        decs = {(n, kind): L.slot_decoder(n, cap) for n in slot_counts for kind in kinds}     # a kind's graphs stay its own
+        bkw = dict(kw, num_beams=nb)
+        stats = {}
+
+        def set_kind(kind):
+            L.decode_fp8, L.decode_fp4 = kind == "fp8", kind == "fp4"
+
+        def beam_slots(n, kind, pb):
+            set_kind(kind)
+            out = {i: lens_ for i, _, _, lens_ in decs[n, kind].run(reqs, prefill_batch=pb, **bkw)}
+            stats[(n, kind, pb)] = dict(decs[n, kind].last_stats)
+            return [out[i][0] for i in range(len(reqs))]
+
+        def beam_batch(n, kind):
+            set_kind(kind)
+            got, steps = [], 0
+            for g0 in range(0, len(reqs), n):
+                grp = reqs[g0:g0 + n]
+                S = max(x.shape[0] for x in grp)                   # one stacked prompt per group: left-pad with the first row
+                emb = torch.stack([torch.cat([x[:1].expand(S - x.shape[0], -1), x]) for x in grp])
+                L.beam_generate(emb, nb, **kw)
+                got += L.last_generate_stats["lengths"]
+                steps += L.last_generate_stats["steps"]
+            stats[("batch", n, kind)] = dict(steps=steps)
+            return got
+
+        pbs = [int(x) for x in a.prefill_batch.split(",")]
+        bmodes = []
+        for kind in kinds:
+            for n in slot_counts:
+                G = n // nb
+                bmodes += [(f"beam slots {n} ({G} groups) prefill_batch {pb} weights {kind or 'bf16'}", (n, kind, pb),
+                            lambda n=n, kind=kind, pb=pb: beam_slots(n, kind, pb)) for pb in pbs]
+                bmodes.append((f"beam_generate batch {G} weights {kind or 'bf16'}", ("batch", G, kind),
+                               lambda G=G, kind=kind: beam_batch(G, kind)))
+            bmodes.append((f"beam_generate batch 1 weights {kind or 'bf16'}", ("batch", 1, kind), lambda kind=kind: beam_batch(1, kind)))
+        for _, _, fn in bmodes:
+            fn()                                                   # warm-up: kernels, graphs, packed copies
+        print("warm-up done", file=sys.stderr, flush=True)
+        res = {name: [] for name, _, _ in bmodes}
+        for rep in range(max(1, a.repeats)):
+            for name, _, fn in bmodes:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                got = fn()
+                torch.cuda.synchronize()
+                res[name].append((time.perf_counter() - t0, got))
+            print(f"repeat {rep + 1} of {max(1, a.repeats)} done", file=sys.stderr, flush=True)
+        print(f"{len(reqs)} requests, prompts {min(lens)}..{max(lens)} rows, num_beams {nb}, max_new_tokens {new}")
+        for name, key, _ in bmodes:
+            ts = sorted(t for t, _ in res[name])
+            t, got, st = ts[len(ts) // 2], res[name][-1][1], stats[key]
+            tail = (f"; group occupancy {st['occupancy']:.3f}, {st['prefills']} prefills in {st['prefill_passes']} passes, "
+                    f"{st['graph_replays']} replays") if "occupancy" in st else ""
+            print(f"{name}: {t * 1e3:.1f} ms (median of {len(ts)}, min {ts[0] * 1e3:.1f}, max {ts[-1] * 1e3:.1f}) -> "
+                  f"{len(reqs) / t:.2f} samples/s; {st['steps']} steps, {t * 1e3 / st['steps']:.3f} ms per step incl. prefills; best "
+                  f"hypothesis {min(got)}..{max(got)} tokens, mean {sum(got) / len(got):.1f}{tail}")
+        sys.exit(0)
     if a.scores:
         from myriad_amd import ops
         cap, skw = 64 * ((160 + new + 63) // 64), dict(return_scores=True, watch_ids=[1000, 1001])
