@@ -293,7 +293,15 @@ int mh_decode_advance(const long* nxt, const float* margin, const float* pmax, f
    largest always stays); out[r] = the smallest i of that kept set with inclusive mass > u * (kept mass).  u from Philox4x32-10,
    key = *seed (u64 on the device), counter = ((step ? *step : 0) + t_add, 0, r, 0): u = (x0 >> 8) * 2^-24, written to u_out[r]
    when u_out is given.  margin / pmax as mh_argmax_pmax_rows (same bits); kept[r] = size of the kept set, or -1 when the tied
-   top-k set has more than 1024 members (out[r] is then the arg-max and the caller draws the row). */
+   top-k set has more than 1024 members (out[r] is then the arg-max and the caller draws the row).
+   Values that have no order of their own:
+   - -0.0 and +0.0 are one value for the top-k threshold, the tie set and the (logit desc, id asc) order.
+   - a NaN logit, of either sign, is -inf for the draw: never a candidate, no mass, never out[r].  margin / pmax stay what
+     mh_argmax_pmax_rows computes on that row (NaN does not win the arg-max there either; p_max of such a row is NaN).
+   - a row holding +inf (after the ban): out[r] = the arg-max, the lowest id holding +inf, and kept[r] = 1 whatever top_p is.  A
+     finite logit that the temperature pushes to +inf counts the same way: the lowest such id, alone.
+   - a row with nothing finite left after the ban (all -inf / NaN): kept[r] = -1 and out[r] = the arg-max rule's answer, id 0
+     for an all -inf row. */
 int mh_sample_rows(const float* logits, long ldl, long* out, float* margin, float* pmax, int* kept, float* u_out, int R, int V,
                    int ban_id, const float* params, const unsigned long long* seed, const int* step, int t_add, mh_stream_t s);
 /* HF RepetitionPenaltyLogitsProcessor in place on f32 logits [R, ldl]: seen = R x ceil(V/32) u32 bitmap of the ids generated so

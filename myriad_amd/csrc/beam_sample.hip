@@ -168,7 +168,7 @@ __global__ __launch_bounds__(SNT) void beam_sample_row_kernel(const float* __res
       prefix = sh_prefix;
       rank = sh_rank;
     }
-    const unsigned KEY_NINF = 0x007fffffu;  // smp_key(-inf)
+    const unsigned KEY_NINF = SMP_KEY_NINF;
     const unsigned thr = prefix;            // key of the k-th largest; every finite w with key >= thr is a candidate
     int mine = 0;
 #pragma unroll

@@ -6,6 +6,8 @@
 //   sample_rows_kernel         one 1024-thread workgroup per row, row resident in registers (V <= 32768): ban, temperature, top-k
 //                              threshold by a 4-pass radix select, the kept candidates (ties at the k-th value included, at most
 //                              MH_SAMPLE_CAP) sorted in LDS by (logit desc, id asc), softmax, top-p cut, inverse-CDF draw.
+//                              The two zeros are one value, a NaN logit is -inf for the draw, a +inf logit is drawn alone
+//                              (the contract is mh_sample_rows' in include/myriad_hip.h).
 // Random numbers: Philox4x32-10 (Salmon et al., SC'11), key = the 64-bit seed, counter = (t, 0, row, 0), u = (x0 >> 8) * 2^-24.
 // The seed, the step counter and (inv_temp, top_p, top_k, penalty) are read from device memory: graph replays draw fresh numbers
 // and a change of the knobs needs no re-capture.
@@ -122,15 +124,23 @@ __global__ __launch_bounds__(SNT) void sample_rows_kernel_t(const float* __restr
     }
   }
   if (!DRAW) return;
+  if (all.best == __builtin_inff()) {     // a +inf logit takes all the mass: the arg-max (its lowest id), alone, whatever top_p is
+    if (tid == 0) {
+      out[row] = all.idx;
+      kept[row] = 1;
+      if (u_out) u_out[row] = sh_u;
+    }
+    return;
+  }
 
   // 2. temperature (HF TemperatureLogitsWarper), then the k-th largest tempered logit: radix select over the ordered keys, 8 bits
   //    a pass from the top; past-V and banned entries are -inf, the smallest key, so they never move the k-th value of a row
-  //    with k <= V
+  //    with k <= V.  A NaN logit is -inf here, and here only: xv, which margin and p_max were formed from, stays as loaded
   unsigned kv[8][4];
 #pragma unroll
   for (int i = 0; i < 8; ++i)
 #pragma unroll
-    for (int e = 0; e < 4; ++e) kv[i][e] = smp_key(xv[i][e] * inv_temp);
+    for (int e = 0; e < 4; ++e) kv[i][e] = smp_key_draw(xv[i][e] * inv_temp);
   unsigned prefix = 0, rank = (unsigned)k;
 #pragma unroll 1
   for (int pass = 0; pass < 4; ++pass) {
@@ -162,7 +172,7 @@ __global__ __launch_bounds__(SNT) void sample_rows_kernel_t(const float* __restr
     prefix = sh_prefix;
     rank = sh_rank;
   }
-  const unsigned KEY_NINF = 0x007fffffu;  // smp_key(-inf)
+  const unsigned KEY_NINF = SMP_KEY_NINF;
   const unsigned thr = prefix;            // key of the k-th largest; every finite logit with key >= thr is kept (ties included)
 
   // 3. gather the candidates, (key, ~id) in one u64 so that a descending sort is (logit desc, id asc)
@@ -211,6 +221,14 @@ __global__ __launch_bounds__(SNT) void sample_rows_kernel_t(const float* __restr
 
   // 5. softmax over the top-k set, top-p cut (keep i iff its exclusive prefix mass < top_p), inverse-CDF draw
   const float vmax = smp_unkey((unsigned)(cand[0] >> 32));
+  if (vmax == __builtin_inff()) {         // a finite logit the temperature pushed to +inf: as a +inf logit, the first of the order
+    if (tid == 0) {
+      out[row] = (long)(0xffffffffu - (unsigned)(cand[0] & 0xffffffffull));
+      kept[row] = 1;
+      if (u_out) u_out[row] = sh_u;
+    }
+    return;
+  }
   const float p = tid < n ? expf(smp_unkey((unsigned)(cand[tid] >> 32)) - vmax) : 0.f;
   const float c = smp_block_scan<float>(p, fsum);
   if (tid < n) cum[tid] = c;

@@ -23,10 +23,19 @@ __device__ __forceinline__ void philox4x32_10(unsigned c[4], unsigned k0, unsign
   }
 }
 
-// order-preserving fp32 <-> u32 map: a > b (floats) <=> key(a) > key(b) (unsigned)
+// order-preserving fp32 <-> u32 map: a > b (floats) <=> key(a) > key(b) (unsigned), and a == b <=> key(a) == key(b): -0.0 takes
+// +0.0's key (a test of its bits, which no float identity the compiler may fold can undo), so the two zeros are one value for
+// the threshold, the tie set and the sort.  smp_unkey gives +0.0 back for either.  NaN has no place in the order: a sign-clear
+// NaN keys above +inf, a sign-set one below -inf, so callers map NaN away first (smp_key_draw, or the beam sampler's w == w).
+#define SMP_KEY_NINF 0x007fffffu  // smp_key(-inf)
 __device__ __forceinline__ unsigned smp_key(float f) {
-  const unsigned u = __float_as_uint(f);
+  unsigned u = __float_as_uint(f);
+  if (u == 0x80000000u) u = 0u;
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+// the key a logit draws with: NaN of either sign (exponent all ones, mantissa non-zero) is -inf
+__device__ __forceinline__ unsigned smp_key_draw(float f) {
+  return (__float_as_uint(f) & 0x7fffffffu) > 0x7f800000u ? SMP_KEY_NINF : smp_key(f);
 }
 __device__ __forceinline__ float smp_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 

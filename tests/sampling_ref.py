@@ -1,6 +1,8 @@
 """Test-side restatement of the decode sampler (mh_sample_rows / mh_repetition_penalty_rows, include/myriad_hip.h): HF's per-row
 chain RepetitionPenalty -> MinLength ban -> Temperature -> TopK (ties at the k-th value kept) -> TopP -> draw, with the kernel's
-Philox4x32-10 uniform.  Logits in float32 (the kernel's arithmetic up to the temperature), probabilities in float64."""
+Philox4x32-10 uniform.  Logits in float32 (the kernel's arithmetic up to the temperature), probabilities in float64.
+What HF leaves open is the header's contract: +0.0 and -0.0 are one value (they compare equal here as floats), a NaN logit is -inf
+before the arg-max and the top-k, and a row holding +inf after the ban is its arg-max (the lowest id holding +inf), kept = 1."""
 from __future__ import annotations
 
 import numpy as np
@@ -47,12 +49,21 @@ def sample_row(x: torch.Tensor, top_k: int, top_p: float, inv_temp: float, ban: 
     V = x.numel()
     if ban >= 0:
         x[ban] = float("-inf")
+    x[torch.isnan(x)] = float("-inf")
+    res = dict(order=None, kept=-1, probs=None, out=int(torch.argmax(x)), near=False)    # argmax: the first of equal maxima
+    if bool((x == float("inf")).any()):
+        res.update(order=np.array([res["out"]]), kept=1, probs=np.ones(1))
+        return res
     y = x * torch.tensor(np.float32(inv_temp))
+    y[torch.isnan(y)] = float("-inf")
+    if bool((y == float("inf")).any()):                                                  # pushed to +inf by the temperature
+        first = int(torch.nonzero(y == float("inf"))[0])
+        res.update(order=np.array([first]), kept=1, probs=np.ones(1), out=first)
+        return res
     k = min(max(int(top_k), 1), V)
     thr = torch.topk(y, k).values[-1]
     cand = (y >= thr) & torch.isfinite(y)
     ids = torch.nonzero(cand).flatten().numpy()
-    res = dict(order=None, kept=-1, probs=None, out=int(torch.argmax(x)), near=False)
     if len(ids) == 0 or len(ids) > CAP:
         return res
     yv = y.numpy()[ids].astype(np.float64)
