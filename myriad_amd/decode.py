@@ -12,7 +12,8 @@ import torch
 
 from . import ops
 from .decode_host import (BeamItem, BeamSlotScheduler, RefillPlanner, ScorePlan, SessionTable, SlotScheduler, TurnPlanner, _host_draw,
-                          _request_generator, beam_sample_select, common_prefix, seeded_requests, split_kv_rows_rule, split_kv_rule)
+                          _request_generator, beam_batch_going, beam_sample_select, common_prefix, seeded_requests, split_kv_rows_rule,
+                          split_kv_rule)
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -47,8 +48,7 @@ def _decode_buffers(lm: "LlamaHIP", B: int, T_cap: int, sampler: bool = False, n
     up to which the step stays on the packed copies (_packed_step).  With `sampler`
     the device sampler's and the repetition penalty's buffers join: their knobs (`prm` = inv_temp, top_p, top_k, penalty),
     the seed, the kept counts and the seen-id bitmaps.  With num_beams > 1, B counts rows (items x beams) and the beam step's
-    buffers join: `bupd` = the per-step upload (ids int64 | parent rows int32 | running scores f32) and its pinned host twin,
-    the top-K scratch and record, and the device table of the per-layer cache pointers that mh_beam_reorder_kv walks.  With
+    buffers join (_beam_buffers, and `lo`, where the generated positions start).  With
     `scores` the record is the one with the token scores' rows behind its four (_score_buffers)."""
     dev, i32 = lm.dev, torch.int32
     ws = dict(T=T_cap, graph=None, warm=False, split=None, row_limit=row_limit,
@@ -64,16 +64,53 @@ def _decode_buffers(lm: "LlamaHIP", B: int, T_cap: int, sampler: bool = False, n
                   kept=torch.zeros((B,), dtype=i32, device=dev),
                   seen=torch.zeros((B, (lm.V + 31) // 32), dtype=i32, device=dev))
     if num_beams > 1:
-        nb, K = int(num_beams), 2 * int(num_beams)
-        bupd = torch.zeros((4 * B,), dtype=i32, device=dev)
-        ws.update(bupd=bupd, bupd_host=torch.zeros((4 * B,), dtype=i32).pin_memory(),
-                  ids=bupd[:2 * B].view(torch.long), src=bupd[2 * B:3 * B], bscore=bupd[3 * B:].view(F32),
-                  part_s=torch.empty((B * K,), dtype=F32, device=dev), part_i=torch.empty((B * K,), dtype=i32, device=dev),
-                  brec=torch.zeros((2, B // nb * K), dtype=i32, device=dev), lo=torch.zeros((1,), dtype=i32, device=dev),
-                  table=torch.tensor([c.data_ptr() for c in ws["caches"]], dtype=torch.long).to(dev))
+        ws.update(_beam_buffers(lm, ws["caches"], B, int(num_beams)), lo=torch.zeros((1,), dtype=i32, device=dev))
     if scores:
         ws["rec"] = _score_buffers(lm, ws)["srec"]
     return ws
+
+
+def _beam_buffers(lm: "LlamaHIP", caches, R: int, nb: int) -> dict:
+    """The beam step's buffers for R rows in groups of nb: `bupd` = the per-step upload (ids int64 | parent rows int32 | running
+    scores f32) with its pinned host twin and the views of it the captured step reads, the top-K scratch, the [2, G * K] record
+    and the device table of the per-layer cache pointers that the KV reorder walks."""
+    dev, i32, K = lm.dev, torch.int32, 2 * nb
+    bupd = torch.zeros((4 * R,), dtype=i32, device=dev)
+    return dict(bupd=bupd, bupd_host=torch.zeros((4 * R,), dtype=i32).pin_memory(),
+                ids=bupd[:2 * R].view(torch.long), src=bupd[2 * R:3 * R], bscore=bupd[3 * R:].view(F32),
+                part_s=torch.empty((R * K,), dtype=F32, device=dev), part_i=torch.empty((R * K,), dtype=i32, device=dev),
+                brec=torch.zeros((2, R // nb * K), dtype=i32, device=dev),
+                table=torch.tensor([c.data_ptr() for c in caches], dtype=torch.long).to(dev))
+
+
+def _beam_upload(host: torch.Tensor):
+    """The pinned upload's three parts as numpy views: (ids int64 [R], parent rows int32 [R], running scores f32 [R])."""
+    R = host.shape[0] // 4
+    return host[:2 * R].view(torch.long).numpy(), host[2 * R:3 * R].numpy(), host[3 * R:].view(F32).numpy()
+
+
+def _beam_record(rec: torch.Tensor, G: int):
+    """A [2, G * K] int32 record as (top_s [G, K] f32, top_i [G, K] int64): a beam step's one device->host copy (it waits for it)."""
+    rec = rec.cpu()
+    return rec[0].view(F32).numpy().reshape(G, -1), rec[1].numpy().reshape(G, -1).astype(np.int64)
+
+
+def _pad_ids(seqs, pad: int) -> torch.Tensor:
+    """Id tuples right-padded with `pad` to a [n, max(1, Lmax)] int64 tensor."""
+    ids = torch.full((len(seqs), max(1, max(len(q) for q in seqs))), pad, dtype=torch.long)
+    for r, q in enumerate(seqs):
+        ids[r, :len(q)] = torch.tensor(q, dtype=torch.long)
+    return ids
+
+
+def _beam_checks(nb: int, V: int) -> None:
+    """The beam paths' checks of num_beams that need no request (BeamItem checks the rest of the search's arguments)."""
+    if nb > ops.BEAM_MAX:
+        raise NotImplementedError(f"num_beams={nb}: at most {ops.BEAM_MAX} beams on the HIP decode path")
+    if nb < 1:
+        raise ValueError(f"num_beams must be >= 1, got {nb}")
+    if V < 2 * nb:
+        raise ValueError(f"num_beams={nb} needs a vocabulary of at least {2 * nb} tokens")
 
 
 def _score_buffers(lm: "LlamaHIP", bufs: dict) -> dict:
@@ -595,21 +632,19 @@ class LlamaDecode:
                       use_graph: bool = True, return_scores: bool = False, pad_id: Optional[int] = None, do_sample: bool = False,
                       temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, repetition_penalty: float = 1.0,
                       generator: Optional[torch.Generator] = None):
-        """Beam search from [B,S0,D] f32 embeddings: HF GenerationMixin._beam_search (tests/beam_ref.py states the rules).
-        Returns [B * num_return_sequences, L] int64 (CPU), generated ids only, the hypotheses of item b at rows
-        b * nrs .. b * nrs + nrs - 1 best first, right-padded with pad_id (default EOS); with return_scores also their
-        sequence scores (sum log-probs / len ** length_penalty), which last_generate_stats["sequences_scores"] holds either way.
-
-        Stop rule: a hypothesis finishes when its own sequence ends with EOS or with one of `stop_ids` (per hypothesis, as
-        transformers applies a criterion that returns one bool per row), or at max_new_tokens.  greedy_generate keeps the
-        reference's rule instead (the batch stops when row 0 ends with a stop sequence).
+        """Beam search from [B,S0,D] f32 embeddings, HF GenerationMixin._beam_search: the host rule (per-hypothesis stops, where
+        greedy_generate keeps the reference's row-0 rule; running beams, finished pool, `early_stopping`) is decode_host.BeamItem's,
+        one per batch item, and the batch goes on by decode_host.beam_batch_going.  Returns [B * num_return_sequences, L] int64
+        (CPU), generated ids only, the hypotheses of item b at rows b * nrs .. b * nrs + nrs - 1 best first, right-padded with
+        pad_id (default EOS); with return_scores also their sequence scores (sum log-probs / len ** length_penalty), which
+        last_generate_stats["sequences_scores"] holds either way.
 
         Device / host split.  The prefill runs at B rows, writing its keys / values into row b * nb of the B * nb row caches,
         and one mh_beam_reorder_kv broadcasts them over [0, S0) to the item's other beams.  The token step (captured into a
         hipGraph, like greedy's) is: reorder the generated positions [S0, pos) of every cache by the parent rows `src`, embed
         the fed tokens, the decoder layers at B * nb rows (packed GEMV up to GEMV_MAX_ROWS), lm-head, mh_beam_topk (log-softmax +
         running score + EOS ban, per item the top 2 * nb candidates), pos / kvlen += 1.  The host reads the [2, B, 2*nb]
-        record (one device->host copy), keeps the hypotheses, and writes the next step's (ids, src, running scores) with one
+        record (one device->host copy), selects every item, and writes the next step's (ids, src, running scores) with one
         host->device copy.
 
         `do_sample` / `repetition_penalty != 1` (behind `beam_sampling`, MYRIAD_BEAM_SAMPLING=1; NotImplementedError without it)
@@ -619,27 +654,18 @@ class LlamaDecode:
         drawn without replacement as the top 2 * nb of acc + Gumbel noise, one Philox4x32-10 stream per candidate keyed by one seed
         drawn from `generator` per call.  The step selects with mh_beam_sample_topk in place of mh_beam_topk, and
         mh_beam_seen_update carries the seen-id bitmaps to their hypotheses after the KV reorder; the workspace and the captured
-        step are this path's own, and the knobs, the seed and the step counter sit in device memory.  `select` below is unchanged:
-        the record is what HF's multinomial hands on.  do_sample=False with a penalty is the same step without temperature, cuts
-        and noise.  An item whose tied top-k set passed the device's 1024 candidates is redone on the host for that step
-        (decode_host.beam_sample_select, counted in last_generate_stats["beam_host_steps"]); with sampling, top_k outside
-        1 .. 1024 is refused (there is no host draw path under beams)."""
+        step are this path's own, and the knobs, the seed and the step counter sit in device memory.  The items select as
+        before: the record is what HF's multinomial hands on.  do_sample=False with a penalty is the same step without
+        temperature, cuts and noise.  An item whose tied top-k set passed the device's 1024 candidates is redone on the host for
+        that step (decode_host.beam_sample_select, counted in last_generate_stats["beam_host_steps"]); with sampling, top_k
+        outside 1 .. 1024 is refused (there is no host draw path under beams)."""
         B, S0, _ = inputs_embeds.shape
-        nb, nrs = int(num_beams), int(num_return_sequences)
-        if nb > ops.BEAM_MAX:
-            raise NotImplementedError(f"num_beams={nb}: at most {ops.BEAM_MAX} beams on the HIP decode path")
-        if nb < 1:
-            raise ValueError(f"num_beams must be >= 1, got {nb}")
-        if not 1 <= nrs <= nb:
-            raise ValueError(f"num_return_sequences={nrs} must be between 1 and num_beams={nb}")
-        if early_stopping not in (True, False, "never"):
-            raise ValueError(f"early_stopping must be True, False or 'never', got {early_stopping!r}")
-        if self.V < 2 * nb:
-            raise ValueError(f"num_beams={nb} needs a vocabulary of at least {2 * nb} tokens")
-        lp = float(length_penalty)
+        nb, V = int(num_beams), self.V
+        _beam_checks(nb, V)
+        items = [BeamItem(nb, V, max_new_tokens, stop_ids, eos_id, length_penalty, early_stopping, num_return_sequences)
+                 for _ in range(B)]                                  # their argument checks, before any launch
         pad = eos_id if pad_id is None else int(pad_id)
-        stops = [tuple(int(t) for t in st) for st in stop_ids]
-        R, K, V, NEG = B * nb, 2 * nb, self.V, np.float32(-1.0e9)
+        R, K, NEG = B * nb, 2 * nb, BeamItem.NEG
         draw, pen = bool(do_sample), float(repetition_penalty)
         sampled = draw or pen != 1.0                                 # the step selects with mh_beam_sample_topk
         if sampled:
@@ -664,53 +690,16 @@ class LlamaDecode:
         caches, T_cap, C = ws["caches"], ws["T"], 2 * self.D
         dev = self.dev
 
-        # ---- host state of the search (HF's tensors, per item, as small numpy arrays / lists)
-        run_seqs = [[()] * nb for _ in range(B)]
-        fin_scores = np.full((B, nb), NEG, dtype=np.float32)
-        fin_seqs = [[()] * nb for _ in range(B)]
-        is_fin = np.zeros((B, nb), dtype=bool)
-        unsat = np.ones((B,), dtype=bool)
-        host = ws["bupd_host"]
-        h_ids, h_src, h_sc = host[:2 * R].view(torch.long).numpy(), host[2 * R:3 * R].numpy(), host[3 * R:].view(F32).numpy()
+        h_ids, h_src, h_sc = _beam_upload(ws["bupd_host"])
 
-        def select(top_s: np.ndarray, top_i: np.ndarray, gen_len: int) -> bool:
-            """One step's bookkeeping from the record (top_s / top_i [B, K]); fills the upload; True = go on."""
-            nonlocal unsat
+        def feed(top_s: np.ndarray, top_i: np.ndarray) -> bool:
+            """One step's record (top_s / top_i [B, K]) to every item, whose answer fills its rows of the upload; True = go on."""
             stats["steps"] += 1
-            all_hit = True
-            for b in range(B):
-                par, tok = top_i[b] // V, top_i[b] % V
-                cand = [run_seqs[b][int(par[k])] + (int(tok[k]),) for k in range(K)]
-                hits = np.array([c[-1] == eos_id or gen_len >= max_new_tokens
-                                 or any(len(c) >= len(st) and c[-len(st):] == st for st in stops) for c in cand])
-                all_hit &= bool(hits.all())
-                run_lp = top_s[b] + hits.astype(np.float32) * NEG
-                nxt = np.argsort(-run_lp, kind="stable")[:nb]
-                run_seqs[b] = [cand[k] for k in nxt]
-                h_ids[b * nb:(b + 1) * nb] = tok[nxt]
-                h_src[b * nb:(b + 1) * nb] = b * nb + par[nxt]
-                h_sc[b * nb:(b + 1) * nb] = run_lp[nxt]
-                did = hits.copy()
-                did[nb:] = False                                     # only the top nb candidates may enter the pool
-                sc = top_s[b] / np.float32(gen_len ** lp)
-                if is_fin[b].all() and early_stopping is True:
-                    sc = sc + NEG
-                if not unsat[b]:
-                    sc = sc + NEG
-                sc = sc + (~did).astype(np.float32) * NEG
-                merged = np.concatenate([fin_scores[b], sc])
-                keep = np.argsort(-merged, kind="stable")[:nb]
-                mseqs, mfin = fin_seqs[b] + cand, np.concatenate([is_fin[b], did])
-                fin_scores[b], fin_seqs[b], is_fin[b] = merged[keep], [mseqs[k] for k in keep], mfin[keep]
-                best_len = max_new_tokens if (early_stopping == "never" and lp > 0.0) else gen_len
-                best_run = np.float32(h_sc[b * nb]) / np.float32(best_len ** lp)
-                worst = fin_scores[b].min()
-                unsat[b] = unsat[b] and bool(np.any(np.where(is_fin[b], best_run > worst, best_run > NEG)))
-            return bool(unsat.any()) and not (bool(is_fin.all()) and early_stopping is True) and not all_hit
-
-        def read_record():
-            rec = ws["brec"].cpu()                                   # the one device->host copy of the step
-            return rec[0].view(F32).numpy().reshape(B, K), rec[1].numpy().reshape(B, K).astype(np.int64)
+            for b, item in enumerate(items):
+                rows = slice(b * nb, (b + 1) * nb)
+                ids, src, run, _ = item.select(top_s[b], top_i[b])
+                h_ids[rows], h_src[rows], h_sc[rows] = ids, b * nb + src, run
+            return beam_batch_going(items)
 
         if sampled:
             if "bsrec" not in ws:                                    # the record: acc [B, K] f32 | flat [B, K] | overflow flag [B]
@@ -736,7 +725,7 @@ class LlamaDecode:
                 for b in np.nonzero(rec[2 * B * K:].numpy())[0]:     # a tied top-k set past the device's cap: the host's rule
                     t = stats["steps"]                               # tokens generated so far = the index of this one
                     acc, flat, _ = beam_sample_select(logits_of()[b * nb:(b + 1) * nb].cpu().numpy(), h_sc[b * nb:(b + 1) * nb],
-                                                      run_seqs[b], ban, inv_temp, top_k, float(top_p), pen, seed, t, int(b), draw)
+                                                      items[b].run_seqs, ban, inv_temp, top_k, float(top_p), pen, seed, t, int(b), draw)
                     top_s[b], top_i[b] = acc, flat
                     stats["beam_host_steps"] += 1
                 return top_s, top_i
@@ -759,7 +748,7 @@ class LlamaDecode:
             bsrc = torch.arange(B, dtype=torch.int32).repeat_interleave(nb).mul_(nb).to(dev)
             span = torch.tensor([0, S0], dtype=torch.int32).to(dev)
             ops.beam_reorder_kv(ws["table"], len(caches), B, nb, T_cap, C, bsrc, span[:1], span[1:])
-        going = select(*(read_sampled(lambda: logits0, ban0) if sampled else read_record()), 1)
+        going = feed(*(read_sampled(lambda: logits0, ban0) if sampled else _beam_record(ws["brec"], B)))
 
         # ---- token steps
         ws["pos"].fill_(S0)
@@ -778,19 +767,18 @@ class LlamaDecode:
                           ban_id=ban, pos=ws["pos"], kvlen=ws["kvlen"])
 
         gen = 1                                                      # tokens generated so far
-        while going and gen < max_new_tokens:
+        while going:
             ws["bupd"].copy_(ws["bupd_host"], non_blocking=True)    # ids | src | running scores: one host->device copy
             ban = eos_id if gen < min_length else -1
             self._launch_step(ws, token_step, ban, use_graph, stats)
             gen += 1
-            going = select(*(read_sampled(lambda: ws["logits"], ban) if sampled else read_record()), gen)
+            going = feed(*(read_sampled(lambda: ws["logits"], ban) if sampled else _beam_record(ws["brec"], B)))
 
-        seqs = [fin_seqs[b][i] for b in range(B) for i in range(nrs)]
-        scores = torch.from_numpy(np.array([fin_scores[b, i] for b in range(B) for i in range(nrs)], dtype=np.float32))
-        ids = torch.full((len(seqs), max(1, max(len(q) for q in seqs))), pad, dtype=torch.long)
-        for r, q in enumerate(seqs):
-            ids[r, :len(q)] = torch.tensor(q, dtype=torch.long)
-        stats.update(sequences_scores=scores, finished_hypotheses=int(is_fin.sum()), lengths=[len(q) for q in seqs])
+        results = [item.result() for item in items]
+        seqs = [q for qs, _ in results for q in qs]
+        scores = torch.from_numpy(np.concatenate([sc for _, sc in results]))
+        stats.update(sequences_scores=scores, finished_hypotheses=sum(item.finished for item in items), lengths=[len(q) for q in seqs])
+        ids = _pad_ids(seqs, pad)
         return (ids, scores) if return_scores else ids
 
     def slot_decoder(self, slots: int, capacity: int, split_kv: Optional[bool] = False) -> "SlotDecoder":
@@ -1003,23 +991,17 @@ class SlotDecoder:
         return self.bufs
 
     def _beam_workspace(self, nb: int, split: bool) -> dict:
-        """The beam step's view of the buffers for groups of nb rows, with its own graph: beam_generate's buffers (`bupd` = the
-        per-step upload ids | parent rows | running scores with its pinned host twin, the top-K scratch, the record `brec`, the
-        cache pointer table) and the per-group state mh_beam_topk_items / mh_beam_reorder_kv_items read -- `lo`, `hi`, `gen`,
-        `glive` [G] and `bprm` = (min_length, eos_id) -- next to the per-row `pos` / `kvlen` / `live` every view shares.  `rec0`
-        and `zero` serve the refills' first selection, `bsrc` (every row's group's first row) the prompt broadcast."""
+        """The beam step's view of the buffers for groups of nb rows, with its own graph: the beam step's buffers (_beam_buffers)
+        and the per-group state mh_beam_topk_items / mh_beam_reorder_kv_items read -- `lo`, `hi`, `gen`, `glive` [G] and `bprm` =
+        (min_length, eos_id) -- next to the per-row `pos` / `kvlen` / `live` every view shares.  `rec0` and `zero` serve the
+        refills' first selection, `bsrc` (every row's group's first row) the prompt broadcast."""
         L, bufs, key = self.llama, self._base_buffers(), (int(nb), bool(split))
         if key not in self.beam_views:
-            dev, i32, R, G, K = L.dev, torch.int32, self.slots, self.slots // nb, 2 * nb
-            bupd = torch.zeros((4 * R,), dtype=i32, device=dev)
+            dev, i32, G, K = L.dev, torch.int32, self.slots // nb, 2 * nb
             view = _buffer_view(L, bufs, split)
-            view.update(bupd=bupd, bupd_host=torch.zeros((4 * R,), dtype=i32).pin_memory(), ids=bupd[:2 * R].view(torch.long),
-                        src=bupd[2 * R:3 * R], bscore=bupd[3 * R:].view(F32),
-                        part_s=torch.empty((R * K,), dtype=F32, device=dev), part_i=torch.empty((R * K,), dtype=i32, device=dev),
-                        brec=torch.zeros((2, G * K), dtype=i32, device=dev), rec0=torch.zeros((2, G * K), dtype=i32, device=dev),
+            view.update(_beam_buffers(L, bufs["caches"], self.slots, nb), rec0=torch.zeros((2, G * K), dtype=i32, device=dev),
                         zero=torch.zeros((G,), dtype=F32, device=dev), bprm=torch.zeros((2,), dtype=i32, device=dev),
                         bsrc=torch.arange(G, dtype=i32).repeat_interleave(nb).mul_(nb).to(dev),
-                        table=torch.tensor([c.data_ptr() for c in bufs["caches"]], dtype=torch.long).to(dev),
                         **{k: torch.zeros((G,), dtype=i32, device=dev) for k in ("lo", "hi", "gen", "glive")})
             self.beam_views[key] = view
         self.ws = self.beam_views[key]
@@ -1126,13 +1108,10 @@ class SlotDecoder:
     def beam_args(self, nb: int, refused=None) -> int:
         """The checks of run(num_beams = nb > 1) that need no request; returns the group count."""
         L = self.llama
-        if nb < 1:
-            raise ValueError(f"num_beams must be >= 1, got {nb}")
+        _beam_checks(nb, L.V)
         if not getattr(L, "slot_beams", False):
             raise NotImplementedError(f"decode slots: num_beams={nb} needs the slot beams switch (MYRIAD_SLOT_BEAMS=1 or "
                                       "llama.slot_beams = True)")
-        if nb > ops.BEAM_MAX:
-            raise NotImplementedError(f"num_beams={nb}: at most {ops.BEAM_MAX} beams on the HIP decode path")
         if self.slots % nb:
             raise ValueError(f"slots={self.slots} do not divide into groups of num_beams={nb} rows")
         for name, on in (refused or {}).items():
@@ -1158,7 +1137,7 @@ class SlotDecoder:
         the prompts' rows [0, S0_g) to the groups' sibling rows, then pos = S0, kvlen = S0 + 1, lo = S0, gen = 1, live = 1."""
         L = self.llama
         G = self.beam_args(nb, refused)
-        K, V, i32 = 2 * nb, L.V, torch.int32
+        V, i32 = L.V, torch.int32
         pad = int(eos_id) if pad_id is None else int(pad_id)
 
         def make_item():
@@ -1177,18 +1156,13 @@ class SlotDecoder:
                      prefill_passes=0, packed_rows=0, split_kv=bool(split), num_beams=nb, groups=G, finished_hypotheses=0)
         self.last_stats = stats
         caches, nl, T_cap, C, R = ws["caches"], len(ws["caches"]), self.T_cap, 2 * L.D, self.slots
-        host = ws["bupd_host"]
-        h_ids, h_src, h_sc = host[:2 * R].view(torch.long).numpy(), host[2 * R:3 * R].numpy(), host[3 * R:].view(F32).numpy()
+        h_ids, h_src, h_sc = _beam_upload(ws["bupd_host"])
         h_ids[:], h_src[:], h_sc[:] = 0, np.arange(R), 0.0           # idle rows: themselves as parents
         ws["live"].zero_()                                           # an abandoned run may have left rows live
         ws["glive"].zero_()
         ws["bprm"].copy_(torch.tensor([int(min_length), int(eos_id)], dtype=i32))
         ban0 = int(eos_id) if 0 < min_length else -1
         room = min(T_cap, L.cos.shape[0])
-
-        def record(rec):
-            rec = rec.cpu()                                          # the one device->host copy (it also waits for the step)
-            return rec[0].view(F32).numpy().reshape(G, K), rec[1].numpy().reshape(G, K).astype(np.int64)
 
         def feed(g):                                                 # the group's rows of the next upload
             ids, src, run = sched.feed[g]
@@ -1211,7 +1185,7 @@ class SlotDecoder:
             n = len(group)
             stats["prefills"] += n
             ops.beam_topk(logits0, ws["zero"], ws["part_s"], ws["part_i"], ws["rec0"][0].view(F32), ws["rec0"][1], n, nb, ban_id=ban0)
-            top_s, top_i = record(ws["rec0"])
+            top_s, top_i = _beam_record(ws["rec0"], G)
             on = [(g, S0) for i, ((g, _), S0) in enumerate(zip(group, lens)) if sched.admit(g, top_s[i], top_i[i])]
             if not on:
                 return
@@ -1241,10 +1215,7 @@ class SlotDecoder:
 
         def results():
             for index, seqs, scores in sched.pop():
-                ids = torch.full((len(seqs), max(1, max(len(q) for q in seqs))), pad, dtype=torch.long)
-                for r, q in enumerate(seqs):
-                    ids[r, :len(q)] = torch.tensor(q, dtype=torch.long)
-                yield index, ids, torch.from_numpy(np.asarray(scores, dtype=np.float32)), [len(q) for q in seqs]
+                yield index, _pad_ids(seqs, pad), torch.from_numpy(np.asarray(scores, dtype=np.float32)), [len(q) for q in seqs]
 
         try:
             while True:
@@ -1259,7 +1230,7 @@ class SlotDecoder:
                 ws["bupd"].copy_(ws["bupd_host"], non_blocking=True)    # ids | src | running scores: one host->device copy
                 if L._launch_step(ws, token_step, -1, True, stats):
                     self.graph_captures += 1
-                finished = sched.step(*record(ws["brec"]))
+                finished = sched.step(*_beam_record(ws["brec"], G))
                 for g in live:
                     if g in finished:
                         ws["live"][g * nb:(g + 1) * nb].zero_()

@@ -2,8 +2,8 @@
 drive every class.  The slot engine's bookkeeping (SlotScheduler), its refill and turn planners (RefillPlanner, TurnPlanner), the
 chat pool's session table (SessionTable), the per-request random streams (seeded_requests), the replay of a known run
 (replay_slot_run), the split-KV rules with their measurements, the host draw of one row (_host_draw), the beam-sampling
-step of one item (beam_sample_select), and beam search in the slots: one request's search state (BeamItem) and the scheduler of
-the groups of num_beams rows (BeamSlotScheduler)."""
+step of one item (beam_sample_select), and beam search's host rule: one request's search state (BeamItem), when a batch of them
+goes on (beam_batch_going) and the slots' scheduler of the groups of num_beams rows (BeamSlotScheduler)."""
 from __future__ import annotations
 
 from typing import Optional
@@ -214,13 +214,16 @@ class SlotScheduler:
 
 
 class BeamItem:
-    """One request's beam search on the host: the rule of LlamaDecode.beam_generate's `select` (HF GenerationMixin._beam_search;
-    tests/beam_ref.py states it) for a single item, on numpy values.  `select(top_s, top_i)` takes one step's record for the item
-    -- its K = 2 * nb best (score, flat index = row_in_item * V + token), best first -- and answers (ids [nb], src [nb], running
-    scores [nb], going): the tokens its nb rows are fed next, the row of the item each continues (0 .. nb - 1) and whether the
-    search goes on.  A candidate stops on EOS, on a stop sequence at the end of ITS ids or at max_new_tokens; a stopped candidate
-    among the best nb enters the pool at score / len ** length_penalty; `early_stopping` and the "can still improve" test are
-    HF's.  `result()` is the best num_return_sequences hypotheses: (their ids as tuples, scores f32 [nrs])."""
+    """One request's beam search on the host, on numpy values: HF GenerationMixin._beam_search's bookkeeping for a single item
+    (tests/beam_ref.py states the rules), the one place the decode loops keep it -- LlamaDecode.beam_generate drives B items under
+    beam_batch_going, the decode slots one per group under BeamSlotScheduler.  `select(top_s, top_i)` takes one step's record for
+    the item -- its K = 2 * nb best (score, flat index = row_in_item * V + token), best first -- and answers (ids [nb], src [nb],
+    running scores [nb], going): the tokens its nb rows are fed next, the row of the item each continues (0 .. nb - 1) and whether
+    the search goes on.  A candidate stops on EOS, on a stop sequence at the end of ITS ids or at max_new_tokens; a stopped
+    candidate among the best nb enters the pool at score / len ** length_penalty; `early_stopping` and the "can still improve"
+    test (`unsat`) are HF's.  `select` stays callable after going = False: in a batch the item is selected on while another item
+    runs, and a pool that was not full can still change.  `all_hit`: every candidate of the last step stopped.  `result()` is the
+    best num_return_sequences hypotheses: (their ids as tuples, scores f32 [nrs])."""
 
     NEG = np.float32(-1.0e9)
 
@@ -241,6 +244,7 @@ class BeamItem:
         self.fin_seqs = [()] * nb
         self.is_fin = np.zeros((nb,), dtype=bool)
         self.unsat = True                                            # the early-stop heuristic still allows an improvement
+        self.all_hit = False                                         # every candidate of the last step stopped
         self.gen = 0                                                 # tokens generated so far (= selections made)
 
     def select(self, top_s, top_i):
@@ -272,7 +276,8 @@ class BeamItem:
         best_run = np.float32(run[0]) / np.float32(best_len ** lp)
         worst = self.fin_scores.min()
         self.unsat = self.unsat and bool(np.any(np.where(self.is_fin, best_run > worst, best_run > NEG)))
-        going = self.unsat and not (bool(self.is_fin.all()) and self.early_stopping is True) and not bool(hits.all())
+        self.all_hit = bool(hits.all())
+        going = self.unsat and not (bool(self.is_fin.all()) and self.early_stopping is True) and not self.all_hit
         return ids, src, run, bool(going and gen_len < self.max_new_tokens)
 
     @property
@@ -281,6 +286,13 @@ class BeamItem:
 
     def result(self):
         return [self.fin_seqs[i] for i in range(self.nrs)], self.fin_scores[:self.nrs].copy()
+
+
+def beam_batch_going(items) -> bool:
+    """Whether a batch of BeamItems searched in lockstep (beam_generate's; same arguments, every item selected every step) goes
+    on: HF's rule over the whole batch, which is not any(item going) -- each clause may hold through a different item."""
+    return (any(it.unsat for it in items) and not (items[0].early_stopping is True and all(it.is_fin.all() for it in items))
+            and not all(it.all_hit for it in items) and items[0].gen < items[0].max_new_tokens)
 
 
 class BeamSlotScheduler:
