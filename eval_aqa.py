@@ -51,6 +51,11 @@ def parse_args(argv=None):
     parser.add_argument("--num-beams", type=int, default=1, help="N > 1: beam search with N beams instead of the evaluation "
                         "script's sampling (num_beams=N, do_sample=False), in either loop; with --slots the slot count must be a "
                         "multiple of N and beam search in the decode slots needs its switch, MYRIAD_SLOT_BEAMS=1")
+    parser.add_argument("--beam-sample", action="store_true", help="with --num-beams N: keep the evaluation script's do_sample=True "
+                        "with its top_p / temperature (beam-search multinomial sampling, the reference chat call's mode) instead of "
+                        "deterministic beams, in either loop; needs the beam sampling switch, MYRIAD_BEAM_SAMPLING=1")
+    parser.add_argument("--repetition-penalty", type=float, default=1.0, help="with --num-beams N: repetition_penalty of the "
+                        "beam search, in either loop; needs the beam sampling switch, MYRIAD_BEAM_SAMPLING=1")
     parser.add_argument("--prefill-batch", type=int, default=1, help="with --slots: P > 1 prefills up to P waiting samples in one "
                         "packed pass when slots are free (1: every sample is prefilled alone)")
     parser.add_argument("--refill-min", type=int, default=1, help="with --slots: hold a refill back until this many slots are free "
@@ -69,6 +74,10 @@ def parse_args(argv=None):
     parser.add_argument("--seg-expect-fpr", type=float, default=0.3, help="with --seg-metrics: the PRO curve is cut at this FPR")
     args = parser.parse_args(argv)
     args.rank_answers = args.rank_answers or args.rank_only
+    if args.beam_sample and args.num_beams <= 1:
+        parser.error("--beam-sample needs --num-beams N > 1")
+    if args.repetition_penalty != 1.0 and args.num_beams <= 1:
+        parser.error("--repetition-penalty needs --num-beams N > 1")
     if not args.seg_metrics and (args.seg_max_step != 200 or args.seg_expect_fpr != 0.3):
         parser.error("--seg-max-step / --seg-expect-fpr need --seg-metrics")
     if args.seg_max_step < 1:
@@ -186,7 +195,9 @@ def main(argv=None):
                        "min_length": 1, "top_p": 0.01, "temperature": 1.0}           # evaluation_aqa_dataset.py:289-301
 
     if args.num_beams > 1:
-        generate_kwargs.update(num_beams=args.num_beams, do_sample=False)
+        generate_kwargs.update(num_beams=args.num_beams, do_sample=bool(args.beam_sample))
+        if args.repetition_penalty != 1.0:
+            generate_kwargs.update(repetition_penalty=args.repetition_penalty)
     if args.llm_score:
         generate_kwargs.update(output_scores=True, watch_ids=llm_watch_ids(model.llama_tokenizer))
 

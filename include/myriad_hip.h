@@ -399,6 +399,25 @@ int mh_beam_sample_topk(const float* logits, long ldl, const float* scores, cons
 /* the seen-id bitmaps follow their hypotheses: seen[r] = old seen[src[r]] | bit(ids[r]) over [B*nb, ceil(V/32)] words, in place
    (every source word of an item is read before any store); src as in mh_beam_reorder_kv, ids int64 (outside [0, V): no bit). */
 int mh_beam_seen_update(unsigned* seen, const int* src, const long* ids, int B, int nb, int V, mh_stream_t s);
+/* the decode slots' beam groups: mh_beam_sample_topk for G items of nb rows, one request each, with per-item state in device
+   memory, so one captured graph serves every run.  live[G], gen[G] (tokens the item's request has generated) and bprm[2] =
+   (min_length, eos_id) are int32, seed[G] is one 64-bit Philox key per item; params (inv_temp, top_p, top_k, penalty) stays one
+   vector for the launch.  A live item (live[g] != 0) bans eos_id iff gen[g] < min_length and draws Philox step t = gen[g] + t_add
+   with key seed[g] and counter (t, row_in_item * V + id, 0, 1): the item field is 0 wherever the item sits, so its K = 2*nb
+   entries of out_s / out_i / out_k [G, K] and its out_f[g] are what mh_beam_sample_topk writes at B = 1 for its rows alone with
+   *seed = seed[g], step = null, t_add = t and that ban.  Then, when pos / kvlen are given, pos[r] += 1 and kvlen[r] += 1 for its
+   rows g*nb .. g*nb+nb-1 and gen[g] += 1; with pos and kvlen both null nothing advances, gen included (the first pick after a
+   refill, whose rows have no position yet).  An idle item's row workgroups leave before they load a logit or a bitmap word; its
+   record is (0.0, -1) K times with out_f[g] = 0, and its out_k entries, pos / kvlen / gen and scratch rows are not touched.
+   Limits and the draw / seen / params rules as mh_beam_sample_topk; a null live / gen / bprm, or only one of pos / kvlen, is
+   MH_ERR_ARG; all before any launch. */
+int mh_beam_sample_topk_items(const float* logits, long ldl, const float* scores, const unsigned* seen, float* part_k, float* part_a,
+                              int* part_i, int* part_f, float* out_s, int* out_i, int* out_f, float* out_k, int G, int nb, int V,
+                              int draw, const float* params, const unsigned long long* seed, const int* live, int* gen,
+                              const int* bprm, int t_add, int* pos, int* kvlen, mh_stream_t s);
+/* mh_beam_seen_update with a live flag per item (int32 [G], read by the kernel): an item with live[g] == 0 has its bitmap rows
+   neither read nor written; a live one is updated as mh_beam_seen_update updates it (a parent outside the item is ignored). */
+int mh_beam_seen_update_items(unsigned* seen, const int* src, const long* ids, int G, int nb, int V, const int* live, mh_stream_t s);
 
 /* K12 conv stacks of VEInstructorV2 / VETokenizer (networks.py:98-127,159-189) as im2col + mh_gemm_bf16_nt. */
 int mh_im2col_nhwc(const void* x, void* col, int B, int H, int W, int C, int kh, int kw, int pad, int Kpad,

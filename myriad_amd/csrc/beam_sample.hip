@@ -16,6 +16,10 @@
 //                            of an item, loads every source word, then stores (beam_reorder_kv_kernel's hazard argument).
 // DRAW = false compiles the temperature, the cuts and the noise out: key = acc, deterministic beam search with the penalty.
 // (inv_temp, top_p, top_k, penalty), the seed and the step counter are read from device memory, as in sample.hip.
+// The three kernels are templates on ITEMS (the decode slots' beam groups, one request per group of nb rows, as in beam.hip): group
+// g then has its own live flag, generated count gen[g] (its EOS ban and its Philox step) and seed[g] in device memory, the item
+// field of its Philox counter is 0 -- it draws what it would draw alone at B = 1 --, and an idle group's workgroups leave on a
+// scalar branch.  ITEMS = false is the code above, unchanged.
 #include "common.h"
 #include "smp_rng.h"
 
@@ -38,13 +42,27 @@ __device__ __forceinline__ float bs_wave_sum(float v) {
 
 // part_k / part_a / part_i [R][K] = (key, acc, token) of the row's top K by key; part_f [R] = 1 when the row's tied top-k set
 // passed MH_SAMPLE_CAP (the top-p cut was not applied: the host redoes the item)
-template <bool DRAW>
+// ITEMS: rows row / nb * nb .. + nb - 1 are group g's; an idle group's rows leave before they load a logit or a bitmap word
+// (blockIdx is uniform: a scalar branch), a live one bans bprm[1] while gen[g] < bprm[0] and draws Philox step gen[g] + t_add of
+// seed[g] with the counter's item field 0
+template <bool DRAW, bool ITEMS>
 __global__ __launch_bounds__(SNT) void beam_sample_row_kernel(const float* __restrict__ logits, long ldl, const float* __restrict__ scores,
                                                               const unsigned* __restrict__ seen, int W, float* __restrict__ part_k,
                                                               float* __restrict__ part_a, int* __restrict__ part_i,
                                                               int* __restrict__ part_f, int V, int nb, int K, int ban_id,
                                                               const float* __restrict__ prm, const unsigned long long* __restrict__ seed,
-                                                              const int* __restrict__ step, int t_add) {
+                                                              const int* __restrict__ step, int t_add,
+                                                              const int* __restrict__ live, const int* __restrict__ gen,
+                                                              const int* __restrict__ bprm) {
+  if (ITEMS) {
+    const int g = blockIdx.x / nb;
+    if (!live[g]) return;
+    ban_id = gen[g] < bprm[0] ? bprm[1] : -1;
+    if (DRAW) {
+      seed += g;
+      step = gen + g;
+    }
+  }
   __shared__ float red[SNW];
   __shared__ float cs[SNW * BSKMAX], ca[SNW * BSKMAX];
   __shared__ int ci[SNW * BSKMAX];
@@ -223,7 +241,7 @@ __global__ __launch_bounds__(SNT) void beam_sample_row_kernel(const float* __res
     // 7. acc = w + score for what stays; 8. key = acc + Gumbel noise from the candidate's own Philox stream
     const unsigned long long sd = *seed;
     const unsigned t = (unsigned)((step ? *step : 0) + t_add);
-    const unsigned item = (unsigned)(row / nb), base = (unsigned)(row % nb) * (unsigned)V;
+    const unsigned item = ITEMS ? 0u : (unsigned)(row / nb), base = (unsigned)(row % nb) * (unsigned)V;
 #pragma unroll
     for (int i = 0; i < BSV; ++i) {
       const int j = i * SNT + tid;
@@ -281,15 +299,27 @@ __global__ __launch_bounds__(SNT) void beam_sample_row_kernel(const float* __res
   }
 }
 
+// ITEMS: an idle group records (0.0, -1) K times and flag 0 and keeps its state; a live one advances its own rows' pos / kvlen and
+// its gen (which the row kernel, an earlier launch, has read) -- or nothing when pos / kvlen are null (a refill's first pick)
+template <bool ITEMS>
 __global__ __launch_bounds__(128) void beam_sample_merge_kernel(const float* __restrict__ part_k, const float* __restrict__ part_a,
                                                                 const int* __restrict__ part_i, const int* __restrict__ part_f,
                                                                 float* __restrict__ out_s, int* __restrict__ out_i,
                                                                 int* __restrict__ out_f, float* __restrict__ out_k, int nb, int V,
                                                                 int K, int* __restrict__ step, int* __restrict__ pos,
-                                                                int* __restrict__ kvlen, int n_adv) {
+                                                                int* __restrict__ kvlen, int n_adv,
+                                                                const int* __restrict__ live, int* __restrict__ gen) {
   __shared__ float cs[8 * BSKMAX];
   __shared__ int ci[8 * BSKMAX];
   const int b = blockIdx.x, tid = threadIdx.x, n = nb * K;
+  if (ITEMS && !live[b]) {
+    if (tid < K) {
+      out_s[(long)b * K + tid] = 0.f;
+      out_i[(long)b * K + tid] = -1;
+    }
+    if (tid == 0) out_f[b] = 0;
+    return;
+  }
   float acc = 0.f;
   if (tid < n) {
     const long src = (long)b * n + tid;                      // row b * nb + tid / K, its rank tid % K
@@ -314,7 +344,12 @@ __global__ __launch_bounds__(128) void beam_sample_merge_kernel(const float* __r
     for (int j = 0; j < nb; ++j) f |= part_f[(long)b * nb + j];
     out_f[b] = f;
   }
-  if (b == 0 && pos && kvlen) {
+  if (ITEMS) {
+    if (pos && kvlen) {
+      if (tid < nb) { pos[b * nb + tid] += 1; kvlen[b * nb + tid] += 1; }
+      if (tid == 0) gen[b] += 1;
+    }
+  } else if (b == 0 && pos && kvlen) {
     for (int r = tid; r < n_adv; r += blockDim.x) { pos[r] += 1; kvlen[r] += 1; }
     if (tid == 0 && step) *step += 1;
   }
@@ -330,14 +365,41 @@ extern "C" int mh_beam_sample_topk(const float* logits, long ldl, const float* s
   if (nb < 1 || nb > 8 || V > SNT * BSV || (V % 4) != 0 || V < 2 * nb || V < 3 || n_adv < 0) return MH_ERR_UNSUPPORTED;
   const int K = 2 * nb, W = (V + 31) / 32;
   if (draw)
-    hipLaunchKernelGGL((beam_sample_row_kernel<true>), dim3(B * nb), dim3(SNT), 0, stream, logits, ldl, scores, seen, W, part_k, part_a,
-                       part_i, part_f, V, nb, K, ban_id, params, seed, (const int*)step, t_add);
+    hipLaunchKernelGGL((beam_sample_row_kernel<true, false>), dim3(B * nb), dim3(SNT), 0, stream, logits, ldl, scores, seen, W, part_k,
+                       part_a, part_i, part_f, V, nb, K, ban_id, params, seed, (const int*)step, t_add, (const int*)nullptr,
+                       (const int*)nullptr, (const int*)nullptr);
   else
-    hipLaunchKernelGGL((beam_sample_row_kernel<false>), dim3(B * nb), dim3(SNT), 0, stream, logits, ldl, scores, seen, W, part_k, part_a,
-                       part_i, part_f, V, nb, K, ban_id, params, seed, (const int*)step, t_add);
+    hipLaunchKernelGGL((beam_sample_row_kernel<false, false>), dim3(B * nb), dim3(SNT), 0, stream, logits, ldl, scores, seen, W, part_k,
+                       part_a, part_i, part_f, V, nb, K, ban_id, params, seed, (const int*)step, t_add, (const int*)nullptr,
+                       (const int*)nullptr, (const int*)nullptr);
   MH_CHECK_LAUNCH();
-  hipLaunchKernelGGL(beam_sample_merge_kernel, dim3(B), dim3(128), 0, stream, part_k, part_a, part_i, part_f, out_s, out_i, out_f, out_k,
-                     nb, V, K, step, pos, kvlen, n_adv);
+  hipLaunchKernelGGL(beam_sample_merge_kernel<false>, dim3(B), dim3(128), 0, stream, part_k, part_a, part_i, part_f, out_s, out_i, out_f,
+                     out_k, nb, V, K, step, pos, kvlen, n_adv, (const int*)nullptr, (int*)nullptr);
+  MH_CHECK_LAUNCH();
+  return MH_OK;
+}
+
+extern "C" int mh_beam_sample_topk_items(const float* logits, long ldl, const float* scores, const unsigned* seen, float* part_k,
+                                         float* part_a, int* part_i, int* part_f, float* out_s, int* out_i, int* out_f, float* out_k,
+                                         int G, int nb, int V, int draw, const float* params, const unsigned long long* seed,
+                                         const int* live, int* gen, const int* bprm, int t_add, int* pos, int* kvlen,
+                                         hipStream_t stream) {
+  if (G <= 0) return MH_OK;
+  if (!logits || !scores || !part_k || !part_a || !part_i || !part_f || !out_s || !out_i || !out_f || !live || !gen || !bprm || V <= 0 ||
+      ldl < V)
+    return MH_ERR_ARG;
+  if ((draw && (!params || !seed)) || (seen && !params) || (!pos != !kvlen)) return MH_ERR_ARG;
+  if (nb < 1 || nb > 8 || V > SNT * BSV || (V % 4) != 0 || V < 2 * nb || V < 3) return MH_ERR_UNSUPPORTED;
+  const int K = 2 * nb, W = (V + 31) / 32;
+  if (draw)
+    hipLaunchKernelGGL((beam_sample_row_kernel<true, true>), dim3(G * nb), dim3(SNT), 0, stream, logits, ldl, scores, seen, W, part_k,
+                       part_a, part_i, part_f, V, nb, K, -1, params, seed, (const int*)nullptr, t_add, live, (const int*)gen, bprm);
+  else
+    hipLaunchKernelGGL((beam_sample_row_kernel<false, true>), dim3(G * nb), dim3(SNT), 0, stream, logits, ldl, scores, seen, W, part_k,
+                       part_a, part_i, part_f, V, nb, K, -1, params, seed, (const int*)nullptr, t_add, live, (const int*)gen, bprm);
+  MH_CHECK_LAUNCH();
+  hipLaunchKernelGGL(beam_sample_merge_kernel<true>, dim3(G), dim3(128), 0, stream, part_k, part_a, part_i, part_f, out_s, out_i, out_f,
+                     out_k, nb, V, K, (int*)nullptr, pos, kvlen, 0, live, gen);
   MH_CHECK_LAUNCH();
   return MH_OK;
 }
@@ -346,8 +408,12 @@ extern "C" int mh_beam_sample_topk(const float* logits, long ldl, const float* s
 #define BST 256
 
 // grid (ceil(W / BST), B): thread = one bitmap word of one item, for the item's nb rows
+// ITEMS: a group with live[g] == 0 leaves before it reads a word (blockIdx.y is uniform: a scalar branch)
+template <bool ITEMS>
 __global__ __launch_bounds__(BST) void beam_seen_update_kernel(unsigned* __restrict__ seen, const int* __restrict__ src,
-                                                               const long* __restrict__ ids, int nb, int W, int V) {
+                                                               const long* __restrict__ ids, int nb, int W, int V,
+                                                               const int* __restrict__ live) {
+  if (ITEMS && !live[blockIdx.y]) return;
   const int w = blockIdx.x * BST + threadIdx.x;
   if (w >= W) return;
   const long r0 = (long)blockIdx.y * nb;
@@ -372,7 +438,19 @@ extern "C" int mh_beam_seen_update(unsigned* seen, const int* src, const long* i
   if (!seen || !src || !ids || V <= 0) return MH_ERR_ARG;
   if (nb < 1 || nb > 8 || B > 65535) return MH_ERR_UNSUPPORTED;
   const int W = (V + 31) / 32;
-  hipLaunchKernelGGL(beam_seen_update_kernel, dim3((W + BST - 1) / BST, B), dim3(BST), 0, stream, seen, src, ids, nb, W, V);
+  hipLaunchKernelGGL(beam_seen_update_kernel<false>, dim3((W + BST - 1) / BST, B), dim3(BST), 0, stream, seen, src, ids, nb, W, V,
+                     (const int*)nullptr);
+  MH_CHECK_LAUNCH();
+  return MH_OK;
+}
+
+extern "C" int mh_beam_seen_update_items(unsigned* seen, const int* src, const long* ids, int G, int nb, int V, const int* live,
+                                         hipStream_t stream) {
+  if (G <= 0) return MH_OK;
+  if (!seen || !src || !ids || !live || V <= 0) return MH_ERR_ARG;
+  if (nb < 1 || nb > 8 || G > 65535) return MH_ERR_UNSUPPORTED;
+  const int W = (V + 31) / 32;
+  hipLaunchKernelGGL(beam_seen_update_kernel<true>, dim3((W + BST - 1) / BST, G), dim3(BST), 0, stream, seen, src, ids, nb, W, V, live);
   MH_CHECK_LAUNCH();
   return MH_OK;
 }

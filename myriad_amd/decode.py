@@ -95,6 +95,14 @@ def _beam_record(rec: torch.Tensor, G: int):
     return rec[0].view(F32).numpy().reshape(G, -1), rec[1].numpy().reshape(G, -1).astype(np.int64)
 
 
+def _beam_sample_record(rec: torch.Tensor, G: int, K: int):
+    """A sampled beam step's (acc [G * K] f32 | flat [G * K] | overflow flag [G]) int32 record as (top_s [G, K] f32, top_i [G, K]
+    int64, flags [G]): the step's one device->host copy (it waits for it).  top_s is a copy: a host redo writes into it."""
+    rec = rec.cpu()
+    return (rec[:G * K].view(F32).numpy().reshape(G, K).copy(), rec[G * K:2 * G * K].numpy().reshape(G, K).astype(np.int64),
+            rec[2 * G * K:2 * G * K + G].numpy())
+
+
 def _pad_ids(seqs, pad: int) -> torch.Tensor:
     """Id tuples right-padded with `pad` to a [n, max(1, Lmax)] int64 tensor."""
     ids = torch.full((len(seqs), max(1, max(len(q) for q in seqs))), pad, dtype=torch.long)
@@ -937,7 +945,10 @@ class SlotDecoder:
     groups of nb rows and a group holds one request's search (decode_host.BeamItem, beam_generate's rule per request), refilled
     as soon as that request ends.  The captured step is beam_generate's with per-group state: mh_beam_reorder_kv_items over each
     group's [lo, pos), the slot step's layers and lm-head under a per-row live mask, mh_beam_topk_items (each group's EOS ban
-    from its own gen).  One view and one graph per nb, in `beam_views`: no key of `views` changes.  See _run_beams."""
+    from its own gen).  One view and one graph per nb, in `beam_views`: no key of `views` changes.  With `LlamaHIP.beam_sampling`
+    on as well, `do_sample` / `repetition_penalty` != 1 run beam_generate's sampled step per group -- mh_beam_seen_update_items
+    and mh_beam_sample_topk_items, every group with its own seed and Philox step in device memory -- in a view and a graph of
+    its own beside the deterministic one.  See _run_beams."""
 
     def __init__(self, llama: "LlamaHIP", slots: int, capacity: int, split_kv: Optional[bool] = False):
         slots = int(slots)
@@ -952,7 +963,7 @@ class SlotDecoder:
             raise ValueError(f"capacity={capacity}: a slot holds at most 8192 positions")
         self.bufs = None                                             # the step's buffers, shared by every view
         self.views = {}                                              # inv_temp -> workspace view of bufs with its own graph
-        self.beam_views = {}                                         # (num_beams, split) -> the beam step's view (_beam_workspace)
+        self.beam_views = {}                                         # (num_beams, split[, draw]) -> the beam step's view (_beam_workspace)
         self.ws = None                                               # the view of the current / last run
         self._weights = None
         self.graph_captures = 0
@@ -990,12 +1001,19 @@ class SlotDecoder:
             self._weights = wid
         return self.bufs
 
-    def _beam_workspace(self, nb: int, split: bool) -> dict:
+    def _beam_workspace(self, nb: int, split: bool, draw: Optional[bool] = None) -> dict:
         """The beam step's view of the buffers for groups of nb rows, with its own graph: the beam step's buffers (_beam_buffers)
         and the per-group state mh_beam_topk_items / mh_beam_reorder_kv_items read -- `lo`, `hi`, `gen`, `glive` [G] and `bprm` =
         (min_length, eos_id) -- next to the per-row `pos` / `kvlen` / `live` every view shares.  `rec0` and `zero` serve the
-        refills' first selection, `bsrc` (every row's group's first row) the prompt broadcast."""
-        L, bufs, key = self.llama, self._base_buffers(), (int(nb), bool(split))
+        refills' first selection, `bsrc` (every row's group's first row) the prompt broadcast.
+
+        `draw` = True / False asks for the sampled beam step's view (mh_beam_sample_topk_items with or without the draw, which is
+        baked into the launch), keyed (nb, split, draw) beside the deterministic step's (nb, split): on top of the above it holds
+        the seen-id bitmaps `bseen` [slots, ceil(V / 32)], the groups' seeds `bseed` [G], the knobs `bsprm` (inv_temp, top_p,
+        top_k, penalty), the (acc | flat | flag) record `bsrec`, the scratch `part_k` / `part_f`, and for the refills' first
+        selection `rec0s`, `seed0`, `gen0` (zeros), `live1` (ones) and `score0` (HF's initial scores 0, -1e9, ... per group)."""
+        L, bufs = self.llama, self._base_buffers()
+        key = (int(nb), bool(split)) if draw is None else (int(nb), bool(split), bool(draw))
         if key not in self.beam_views:
             dev, i32, G, K = L.dev, torch.int32, self.slots // nb, 2 * nb
             view = _buffer_view(L, bufs, split)
@@ -1003,6 +1021,16 @@ class SlotDecoder:
                         zero=torch.zeros((G,), dtype=F32, device=dev), bprm=torch.zeros((2,), dtype=i32, device=dev),
                         bsrc=torch.arange(G, dtype=i32).repeat_interleave(nb).mul_(nb).to(dev),
                         **{k: torch.zeros((G,), dtype=i32, device=dev) for k in ("lo", "hi", "gen", "glive")})
+            if draw is not None:
+                score0 = torch.full((G, nb), float(BeamItem.NEG), dtype=F32)
+                score0[:, 0] = 0.0
+                view.update(bseen=torch.zeros((self.slots, (L.V + 31) // 32), dtype=i32, device=dev),
+                            bseed=torch.zeros((G,), dtype=torch.long, device=dev), seed0=torch.zeros((G,), dtype=torch.long, device=dev),
+                            bsprm=torch.zeros((4,), dtype=F32, device=dev), bsrec=torch.zeros((2 * G * K + G,), dtype=i32, device=dev),
+                            rec0s=torch.zeros((2 * G * K + G,), dtype=i32, device=dev),
+                            part_k=torch.empty((self.slots * K,), dtype=F32, device=dev),
+                            part_f=torch.zeros((self.slots,), dtype=i32, device=dev), gen0=torch.zeros((G,), dtype=i32, device=dev),
+                            live1=torch.ones((G,), dtype=i32, device=dev), score0=score0.reshape(-1).to(dev))
             self.beam_views[key] = view
         self.ws = self.beam_views[key]
         return self.ws
@@ -1064,13 +1092,18 @@ class SlotDecoder:
         `num_beams` = nb > 1 (behind `slot_beams`; with `length_penalty`, `early_stopping`, `num_return_sequences`, `pad_id`,
         beam_generate's): beam search, one request per group of nb slots (_run_beams).  The run then yields (index, ids [nrs, Lmax]
         right-padded with pad_id, sequence scores [nrs] f32, lengths [nrs]) per request -- what beam_generate returns for it
-        alone -- and `last_stats` gains `num_beams`, `groups`, `finished_hypotheses`; `occupancy` counts groups."""
+        alone -- and `last_stats` gains `num_beams`, `groups`, `finished_hypotheses`; `occupancy` counts groups.  With
+        `beam_sampling` on as well, `do_sample` (with `temperature`, `top_k` in 1..1024, `top_p`) and `repetition_penalty` != 1 are
+        beam_generate's beam sampling and penalty per request: request i draws from the i-th seed of `generator` or `seeds`, what
+        beam_generate draws for it alone with that seed (`beam_sampled_steps`, `beam_host_steps` join `last_stats`)."""
         self.sessions.clear()                                        # the slots' caches are overwritten from row 0
         if int(num_beams) != 1:
             yield from self._run_beams(requests, int(num_beams), max_new_tokens, stop_ids, eos_id, min_length, ordered, prefill_batch,
                                        refill_min, prefill_rows, length_penalty, early_stopping, num_return_sequences, pad_id,
                                        refused=dict(do_sample=bool(do_sample), repetition_penalty=float(repetition_penalty) != 1.0,
-                                                    return_scores=bool(return_scores), seeds=seeds is not None))
+                                                    return_scores=bool(return_scores), seeds=seeds is not None),
+                                       sampling=dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
+                                                     repetition_penalty=repetition_penalty, generator=generator, seeds=seeds))
             return
         yield from self._run(requests, None, None, max_new_tokens, stop_ids, eos_id, min_length, do_sample, top_p, temperature,
                              top_k, generator, ordered, prefill_batch, refill_min, prefill_rows, repetition_penalty, seeds,
@@ -1106,7 +1139,9 @@ class SlotDecoder:
         return self._run(None, turns, weights_version, **kw)
 
     def beam_args(self, nb: int, refused=None) -> int:
-        """The checks of run(num_beams = nb > 1) that need no request; returns the group count."""
+        """The checks of run(num_beams = nb > 1) that need no request; returns the group count.  `refused`: the arguments in use
+        that the beam groups do not take; with the beam sampling switch on, do_sample, repetition_penalty and seeds leave it
+        (_beam_sampling_args checks them)."""
         L = self.llama
         _beam_checks(nb, L.V)
         if not getattr(L, "slot_beams", False):
@@ -1114,15 +1149,39 @@ class SlotDecoder:
                                       "llama.slot_beams = True)")
         if self.slots % nb:
             raise ValueError(f"slots={self.slots} do not divide into groups of num_beams={nb} rows")
+        if getattr(L, "beam_sampling", False):
+            refused = {k: v for k, v in (refused or {}).items() if k not in ("do_sample", "repetition_penalty", "seeds")}
         for name, on in (refused or {}).items():
             if on:
                 raise NotImplementedError(f"decode slots: num_beams={nb} with {name} is not implemented (beam sampling, the penalty "
                                           "and token scores under beams are beam_generate's)")
         return self.slots // nb
 
+    def _beam_sampling_args(self, nb: int, sampling):
+        """run(num_beams = nb > 1)'s sampling arguments, checked as beam_generate checks them (beam_args has refused them with the
+        beam sampling switch off): ((inv_temp, top_k, top_p, penalty) when the step is the sampled one -- do_sample or a penalty --
+        else None, draw)."""
+        L, a = self.llama, sampling or {}
+        draw, pen = bool(a.get("do_sample", False)), float(a.get("repetition_penalty", 1.0))
+        if not getattr(L, "beam_sampling", False):
+            return None, False
+        inv_temp, top_k, _, _ = _sampling_args(L, draw, a.get("temperature", 1.0), a.get("top_k", 50), pen)
+        if a.get("seeds") is not None and not draw:
+            raise ValueError("seeds= names the beam groups' per-request streams: it needs do_sample")
+        if not draw and pen == 1.0:
+            return None, False
+        if draw and not 1 <= top_k <= ops.SAMPLE_CAP:
+            raise NotImplementedError(f"decode slots: num_beams={nb}, do_sample=True: top_k={top_k} is outside 1..{ops.SAMPLE_CAP} "
+                                      "(beam sampling draws on the device only)")
+        if L.V < 3:
+            raise ValueError(f"beam sampling needs a vocabulary of at least 3 tokens, got {L.V}")
+        if L.V > 32768 or L.V % 4:
+            raise NotImplementedError(f"beam sampling takes a vocabulary of at most 32768 tokens, a multiple of 4, got {L.V}")
+        return (inv_temp, top_k, float(a.get("top_p", 1.0)), pen), draw
+
     @torch.no_grad()
     def _run_beams(self, requests, nb, max_new_tokens, stop_ids, eos_id, min_length, ordered, prefill_batch, refill_min, prefill_rows,
-                   length_penalty, early_stopping, num_return_sequences, pad_id, refused=None):
+                   length_penalty, early_stopping, num_return_sequences, pad_id, refused=None, sampling=None):
         """run(num_beams = nb > 1): the slot loop over G groups of nb rows (BeamSlotScheduler, driven by RefillPlanner unchanged).
 
         The captured step: hi = pos of each group's first row (one strided copy), mh_beam_reorder_kv_items over [lo, hi) by the
@@ -1134,10 +1193,23 @@ class SlotDecoder:
 
         A refill -- solo into cache row g * nb, or packed through _prefill_packed -- is: the prefill, ONE eager mh_beam_topk at
         rpi = 1 over the refilled prompts' logits, BeamItem's first selection, one eager mh_beam_reorder_kv_items that broadcasts
-        the prompts' rows [0, S0_g) to the groups' sibling rows, then pos = S0, kvlen = S0 + 1, lo = S0, gen = 1, live = 1."""
+        the prompts' rows [0, S0_g) to the groups' sibling rows, then pos = S0, kvlen = S0 + 1, lo = S0, gen = 1, live = 1.
+
+        `sampling` (run's do_sample, temperature, top_k, top_p, repetition_penalty, generator, seeds) with do_sample or a penalty
+        and the beam sampling switch on: beam_generate's sampled step per group, in a view and a graph of its own.  The captured
+        step is then hi, mh_beam_reorder_kv_items, mh_beam_seen_update_items (the bitmaps follow their hypotheses, the fed token
+        joins them), _step_logits, mh_beam_sample_topk_items with t_add = 0 -- gen[g] is the index of the token being picked, so
+        group g draws Philox step gen[g] of its own seed[g] with the counter's item field 0: what beam_generate draws for the
+        request alone.  A refill's first selection is ONE eager mh_beam_sample_topk_items over the prompts' rows repeated nb
+        times under HF's initial scores (0, -1e9, ...) with gen = 0, every request's own seed and no advance; going live also
+        clears the group's bitmap rows and writes seed[g].  Seeds travel with the requests (seeded_requests).  A group whose
+        overflow flag is set (a tied top-k set past the device's 1024 candidates) is redone on the host for that selection
+        (decode_host.beam_sample_select with the group's seed, its t and item = 0), counted in last_stats["beam_host_steps"];
+        "beam_sampled_steps" counts the sampled token steps.  The knobs sit in device memory: one graph per (nb, split, draw)."""
         L = self.llama
         G = self.beam_args(nb, refused)
         V, i32 = L.V, torch.int32
+        sampled, draw = self._beam_sampling_args(nb, sampling)
         pad = int(eos_id) if pad_id is None else int(pad_id)
 
         def make_item():
@@ -1147,13 +1219,16 @@ class SlotDecoder:
         split = self.split_kv
         if split is None:
             split = split_kv_rows_rule(self.slots, L.H, 0)
-        ws = self._beam_workspace(nb, split)
+        ws = self._beam_workspace(nb, split, draw if sampled else None)
         sched = BeamSlotScheduler(G, make_item, ordered=ordered)
-        plan = RefillPlanner(sched, ((emb,) for emb in requests), prefill_batch, prefill_rows, refill_min,
-                             length=lambda q: int(q[0].shape[0]))
+        # a request travels with the seed of its own stream (None unless the groups draw)
+        reqs = seeded_requests(requests, sampling["generator"], sampling["seeds"]) if draw else ((emb, None) for emb in requests)
+        plan = RefillPlanner(sched, reqs, prefill_batch, prefill_rows, refill_min, length=lambda q: int(q[0].shape[0]))
         packed = int(prefill_batch) != 1 or int(refill_min) != 1
         stats = dict(steps=0, graph_replays=0, graph_captures=self.graph_captures, prefills=0, live_row_steps=0, occupancy=0.0,
                      prefill_passes=0, packed_rows=0, split_kv=bool(split), num_beams=nb, groups=G, finished_hypotheses=0)
+        if sampled:
+            stats.update(beam_sampled_steps=0, beam_host_steps=0)
         self.last_stats = stats
         caches, nl, T_cap, C, R = ws["caches"], len(ws["caches"]), self.T_cap, 2 * L.D, self.slots
         h_ids, h_src, h_sc = _beam_upload(ws["bupd_host"])
@@ -1163,6 +1238,22 @@ class SlotDecoder:
         ws["bprm"].copy_(torch.tensor([int(min_length), int(eos_id)], dtype=i32))
         ban0 = int(eos_id) if 0 < min_length else -1
         room = min(T_cap, L.cos.shape[0])
+        if sampled:
+            K = 2 * nb
+            inv_temp, top_k, top_p, pen = sampled
+            ws["bsprm"].copy_(torch.tensor([inv_temp, top_p, float(top_k), pen], dtype=F32))
+            rec_of = {name: (ws[name][:G * K].view(F32), ws[name][G * K:2 * G * K], ws[name][2 * G * K:]) for name in ("bsrec", "rec0s")}
+            seed_of = {}                                             # group -> its request's seed
+
+            def sample_topk(name, logits, scores, n, live, gen, seed, **kw):
+                ops.beam_sample_topk_items(logits, scores, ws["part_k"], ws["part_s"], ws["part_i"], ws["part_f"], *rec_of[name], n, nb,
+                                           live, gen, ws["bprm"], draw=draw, params=ws["bsprm"], seed=seed, t_add=0, **kw)
+
+            def host_redo(logits_rows, scores, seqs, seed, t):      # the host's rule for one flagged group's selection
+                stats["beam_host_steps"] += 1
+                acc, flat, _ = beam_sample_select(logits_rows.cpu().numpy(), scores, seqs, int(eos_id) if t < min_length else -1, inv_temp,
+                                                  top_k, top_p, pen, seed or 0, t, 0, draw)
+                return acc, flat
 
         def feed(g):                                                 # the group's rows of the next upload
             ids, src, run = sched.feed[g]
@@ -1171,7 +1262,7 @@ class SlotDecoder:
 
         def refill(group):
             lens = []
-            for _, (emb,) in group:
+            for _, (emb, _seed) in group:
                 S0 = emb.shape[0] if emb.dim() == 2 else 0
                 if S0 < 1 or S0 + max_new_tokens > room:
                     raise ValueError(f"request of shape {tuple(emb.shape)} + max_new_tokens {max_new_tokens} does not fit a slot of "
@@ -1184,23 +1275,39 @@ class SlotDecoder:
                 logits0 = L._prefill(req[0][None].to(L.dev), [c[g * nb:g * nb + 1] for c in caches])
             n = len(group)
             stats["prefills"] += n
-            ops.beam_topk(logits0, ws["zero"], ws["part_s"], ws["part_i"], ws["rec0"][0].view(F32), ws["rec0"][1], n, nb, ban_id=ban0)
-            top_s, top_i = _beam_record(ws["rec0"], G)
-            on = [(g, S0) for i, ((g, _), S0) in enumerate(zip(group, lens)) if sched.admit(g, top_s[i], top_i[i])]
+            if sampled:                                              # the prompt's row nb times, HF's initial scores, gen = 0
+                seeds_ = [req[1] for _, req in group]
+                if draw:
+                    ws["seed0"][:n].copy_(torch.tensor(seeds_, dtype=torch.long))
+                rows0 = logits0.repeat_interleave(nb, 0)
+                sample_topk("rec0s", rows0, ws["score0"], n, ws["live1"], ws["gen0"], ws["seed0"] if draw else None)
+                top_s, top_i, flags = _beam_sample_record(ws["rec0s"], G, K)
+                for i in np.nonzero(flags[:n])[0]:
+                    top_s[i], top_i[i] = host_redo(rows0[i * nb:(i + 1) * nb], ws["score0"][:nb].cpu().numpy(), [()] * nb, seeds_[i], 0)
+            else:
+                ops.beam_topk(logits0, ws["zero"], ws["part_s"], ws["part_i"], ws["rec0"][0].view(F32), ws["rec0"][1], n, nb,
+                              ban_id=ban0)
+                top_s, top_i = _beam_record(ws["rec0"], G)
+            on = [(g, S0, req[1]) for i, ((g, req), S0) in enumerate(zip(group, lens)) if sched.admit(g, top_s[i], top_i[i])]
             if not on:
                 return
             state = torch.zeros((3, G), dtype=i32)                   # the broadcast's lo = 0 | hi = S0 | live, per group
-            for g, S0 in on:
+            for g, S0, _ in on:
                 state[1, g], state[2, g] = S0, 1
             state = ops.h2d(state, L.dev)
             if nl:
                 ops.beam_reorder_kv_items(ws["table"], nl, G, nb, T_cap, C, ws["bsrc"], state[0], state[1], state[2])
-            for g, S0 in on:
+            for g, S0, seed in on:
                 rows = slice(g * nb, (g + 1) * nb)
                 ws["pos"][rows].fill_(S0)                            # position of the incoming token
                 ws["kvlen"][rows].fill_(S0 + 1)                      # valid keys after the append
                 ws["lo"][g:g + 1].fill_(S0)                          # the prompt prefix is the same in every row of the group
                 ws["gen"][g:g + 1].fill_(1)                          # the prefill's selection was token 0
+                if sampled:
+                    ws["bseen"][rows].zero_()                        # generated ids only, and the last request's are gone
+                    seed_of[g] = seed
+                    if draw:
+                        ws["bseed"][g:g + 1].fill_(seed)
                 ws["live"][rows].fill_(1)
                 ws["glive"][g:g + 1].fill_(1)
                 feed(g)
@@ -1209,9 +1316,24 @@ class SlotDecoder:
             if nl:
                 ws["hi"].copy_(ws["pos"][::nb])                      # each group's position: generated rows are [lo, pos)
                 ops.beam_reorder_kv_items(ws["table"], nl, G, nb, T_cap, C, ws["src"], ws["lo"], ws["hi"], ws["glive"])
+            if sampled:                                              # the bitmaps follow their hypotheses; the fed token joins
+                ops.beam_seen_update_items(ws["bseen"], ws["src"], ws["ids"], G, nb, V, ws["glive"])
+                L._step_logits(ws)
+                sample_topk("bsrec", ws["logits"], ws["bscore"], G, ws["glive"], ws["gen"], ws["bseed"] if draw else None,
+                            seen=ws["bseen"], pos=ws["pos"], kvlen=ws["kvlen"])
+                return
             L._step_logits(ws)
             ops.beam_topk_items(ws["logits"], ws["bscore"], ws["part_s"], ws["part_i"], ws["brec"][0].view(F32), ws["brec"][1], G, nb,
                                 ws["glive"], ws["gen"], ws["bprm"], ws["pos"], ws["kvlen"])
+
+        def read_sampled(live):                                      # the sampled step's record, flagged groups redone
+            top_s, top_i, flags = _beam_sample_record(ws["bsrec"], G, K)
+            stats["beam_sampled_steps"] += 1
+            for g in live:
+                if flags[g]:
+                    item, rows = sched.rows[g][1], slice(g * nb, (g + 1) * nb)
+                    top_s[g], top_i[g] = host_redo(ws["logits"][rows], h_sc[rows], item.run_seqs, seed_of[g], item.gen)
+            return top_s, top_i
 
         def results():
             for index, seqs, scores in sched.pop():
@@ -1230,7 +1352,7 @@ class SlotDecoder:
                 ws["bupd"].copy_(ws["bupd_host"], non_blocking=True)    # ids | src | running scores: one host->device copy
                 if L._launch_step(ws, token_step, -1, True, stats):
                     self.graph_captures += 1
-                finished = sched.step(*_beam_record(ws["brec"], G))
+                finished = sched.step(*(read_sampled(live) if sampled else _beam_record(ws["brec"], G)))
                 for g in live:
                     if g in finished:
                         ws["live"][g * nb:(g + 1) * nb].zero_()

@@ -116,7 +116,8 @@ class LlamaHIP(LlamaDecode):
         # num_beams > 1 with do_sample (HF's beam-search multinomial sampling) or a repetition penalty: the beam step selects with
         # mh_beam_sample_topk and carries the seen-id bitmaps (mh_beam_seen_update); off, generate() refuses both as before
         self.beam_sampling = os.environ.get("MYRIAD_BEAM_SAMPLING", "0") != "0"
-        # beam search in the decode slots, one request per group of num_beams rows (SlotDecoder.run(num_beams > 1)); off by default
+        # beam search in the decode slots, one request per group of num_beams rows (SlotDecoder.run(num_beams > 1)); off by default.
+        # With beam_sampling on as well the groups take do_sample and the penalty (mh_beam_sample_topk_items)
         self.slot_beams = os.environ.get("MYRIAD_SLOT_BEAMS", "0") != "0"
         self.last_layer_rows = os.environ.get("MYRIAD_LAST_LAYER_ROWS", "1") != "0"
         # the packed token step streams FP8 (e4m3fn, one fp32 scale per output row) copies of the decoder matrices instead of

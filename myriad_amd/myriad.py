@@ -1547,7 +1547,8 @@ class MyriadHIP(nn.Module):
         sample is a beam search in its own group of num_beams slots (SlotDecoder.run; `slots` a multiple of num_beams), with
         length_penalty, early_stopping and num_return_sequences as in generate(); "token_ids" is what generate() returns in that
         sample's rows ([L] for one returned sequence, else [nrs, L], padded with EOS) and "sequences_scores" [nrs] comes with it;
-        do_sample, repetition_penalty != 1 and seeds are refused there.  repetition_penalty != 1 needs the device sampling switch, as in
+        do_sample, repetition_penalty != 1 and seeds are refused there unless `self.llama.beam_sampling` is on as well: then they
+        are beam sampling and the penalty per sample, sample i drawing from the i-th seed.  repetition_penalty != 1 needs the device sampling switch, as in
         generate(), and so does min_length > 1 here (SlotDecoder.run itself takes it on every path).  With that switch on, a
         sampled run draws every token on the device and each sample from its own stream: sample i takes the i-th seed drawn from `generator` (or the i-th of `seeds`, an iterable of ints), so its answer does not
         depend on the slot count, the refill settings or its neighbours (SlotDecoder.run).  min_length is a per-sample EOS ban.
@@ -1563,13 +1564,17 @@ class MyriadHIP(nn.Module):
             if not getattr(self.llama, "slot_beams", False):
                 raise NotImplementedError(f"generate_stream(num_beams={nb}): beam search in the decode slots needs its switch "
                                           "(MYRIAD_SLOT_BEAMS=1 or model.llama.slot_beams = True)")
-            if a["do_sample"] or a["rep_pen"] != 1.0 or seeds is not None:
+            beam_sampling = bool(getattr(self.llama, "beam_sampling", False))
+            if (a["do_sample"] or a["rep_pen"] != 1.0 or seeds is not None) and not beam_sampling:
                 raise NotImplementedError(f"generate_stream(num_beams={nb}): do_sample, repetition_penalty != 1 and seeds are not "
                                           "implemented with beams in the decode slots")
             if nb > ops.BEAM_MAX or int(slots) % nb:
                 raise ValueError(f"generate_stream(slots={slots}, num_beams={nb}): the slots divide into groups of num_beams <= "
                                  f"{ops.BEAM_MAX} rows")
             beam_kw = dict(num_beams=nb, **{k: a["beam_kw"][k] for k in ("length_penalty", "early_stopping", "num_return_sequences")})
+            if beam_sampling:                                          # switch off: SlotDecoder.run is called with today's arguments
+                beam_kw.update(do_sample=a["do_sample"], temperature=a["temperature"], top_k=a["top_k"], top_p=a["top_p"],
+                               repetition_penalty=a["rep_pen"], generator=a["generator"], seeds=seeds)
         max_new = a["max_new"]
         if max_new is None:
             raise NotImplementedError("generate_stream(max_length=...): pass max_new_tokens, the prompts differ in length")

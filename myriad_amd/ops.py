@@ -1483,6 +1483,58 @@ def beam_seen_update(seen: torch.Tensor, src: torch.Tensor, ids: torch.Tensor, B
     return seen
 
 
+def beam_sample_topk_items(logits: torch.Tensor, scores: torch.Tensor, part_k, part_a, part_i, part_f, out_s, out_i, out_f, G: int,
+                           nb: int, live, gen, bprm, draw: bool = True, params=None, seed=None, seen=None, t_add: int = 0, out_k=None,
+                           pos=None, kvlen=None):
+    """beam_sample_topk for the decode slots' G beam groups (logits [G*nb, V], one request per item): live / gen int32 [G], bprm =
+    int32 (min_length, eos_id) and seed = int64 [G] (one Philox key per item) are read by the kernels.  A live item bans eos_id
+    iff gen[g] < min_length, draws Philox step gen[g] + t_add of seed[g] with the counter's item field 0 -- what beam_sample_topk
+    records for it alone at B = 1 with that seed and step -- and, with pos / kvlen (both or neither, [G*nb]), advances its nb rows
+    of them and its gen by one; without them nothing advances (a refill's first pick).  An idle item records (0.0, -1) with flag
+    0 and keeps everything else.  A buffer of the wrong type or too short is refused here, before any launch."""
+    _chk2d(logits, F32, "beam_sample_topk_items: logits")
+    R, V = logits.shape
+    if G <= 0 or nb <= 0 or R != G * nb:
+        raise _lib.MyriadHipError(f"beam_sample_topk_items: {R} logits rows are not G={G} items of nb={nb} rows")
+    i32, K = torch.int32, 2 * nb
+    for name, t, dtype, need in (("scores", scores, F32, R), ("part_k", part_k, F32, R * K), ("part_a", part_a, F32, R * K),
+                                 ("part_i", part_i, i32, R * K), ("part_f", part_f, i32, R), ("out_s", out_s, F32, G * K),
+                                 ("out_i", out_i, i32, G * K), ("out_f", out_f, i32, G), ("live", live, i32, G), ("gen", gen, i32, G),
+                                 ("bprm", bprm, i32, 2)):
+        _chk_flat(t, dtype, need, f"beam_sample_topk_items: {name}")
+    if out_k is not None:
+        _chk_flat(out_k, F32, G * K, "beam_sample_topk_items: out_k")
+    if draw or seen is not None:
+        _chk_flat(params, F32, 4, "beam_sample_topk_items: params")
+    if draw:
+        _chk_flat(seed, torch.long, G, "beam_sample_topk_items: seed")
+    if seen is not None:
+        _chk_flat(seen, i32, R * ((V + 31) // 32), "beam_sample_topk_items: seen")
+    if (pos is None) != (kvlen is None):
+        raise _lib.MyriadHipError("beam_sample_topk_items: pos and kvlen advance together: give both or neither")
+    if pos is not None:
+        _chk_flat(pos, i32, R, "beam_sample_topk_items: pos")
+        _chk_flat(kvlen, i32, R, "beam_sample_topk_items: kvlen")
+    _lib.check(_L().mh_beam_sample_topk_items(_p(logits), logits.stride(0), _p(scores), _p(seen), _p(part_k), _p(part_a), _p(part_i),
+                                              _p(part_f), _p(out_s), _p(out_i), _p(out_f), _p(out_k), G, nb, V, int(bool(draw)),
+                                              _p(params), _p(seed), _p(live), _p(gen), _p(bprm), int(t_add), _p(pos), _p(kvlen),
+                                              _s()), "mh_beam_sample_topk_items")
+    return out_s, out_i, out_f
+
+
+def beam_seen_update_items(seen: torch.Tensor, src: torch.Tensor, ids: torch.Tensor, G: int, nb: int, V: int, live: torch.Tensor):
+    """beam_seen_update with a live flag per item (int32 [G], read by the kernel): an idle item's bitmap rows are neither read nor
+    written."""
+    if G <= 0 or nb <= 0 or V <= 0:
+        raise _lib.MyriadHipError(f"beam_seen_update_items: G={G}, nb={nb}, V={V} must be positive")
+    _chk_flat(seen, torch.int32, G * nb * ((V + 31) // 32), "beam_seen_update_items: seen")
+    _chk_flat(src, torch.int32, G * nb, "beam_seen_update_items: src")
+    _chk_flat(ids, torch.long, G * nb, "beam_seen_update_items: ids")
+    _chk_flat(live, torch.int32, G, "beam_seen_update_items: live")
+    _lib.check(_L().mh_beam_seen_update_items(_p(seen), _p(src), _p(ids), G, nb, V, _p(live), _s()), "mh_beam_seen_update_items")
+    return seen
+
+
 # --------------------------------------------------------------------------- conv stack pieces
 def im2col(x_nhwc: torch.Tensor, kh: int, kw: int, pad: int, bias_col: bool = True):
     """[B*OH*OW, Kpad] bf16 patches, (ky, kx, c) order; with bias_col a column of ones follows the K patch columns (the bias

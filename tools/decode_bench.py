@@ -35,6 +35,10 @@ every decode loop but the slot engine runs above 16 rows.
 --slots 8,16,32 --num-beams 4 [--weights bf16,fp4] [--prefill-batch 1,8] times beam search in the slots (S / nb groups, one request
 per group, behind llama.slot_beams) against beam_generate over consecutive batches of S / nb left-padded requests and at batch 1,
 all interleaved per repeat; the stop id is then also the runner-up after every chain token, so that hypotheses finish.
+With --sample [--penalty P] (or --penalty alone) both sides run beam sampling instead (do_sample=True, top_p=0.9, top_k=50,
+--temperature; behind llama.beam_sampling as well): the sampled beam slots against beam_generate(do_sample=True) over the same
+padded batches, and then the captured slot step alone, sampled against deterministic at the same rows, every group live at
+--step-keys keys, --step-replays replays per round.
 
 --scores (with --slots 8,64, the default there) measures what return_scores costs: the same request list decoded at batch 1 (the
 first --requests / 8 requests), and through each slot count, with and without the token scores (two watched ids), interleaved per
@@ -212,13 +216,21 @@ if a.slots or len(slot_counts) > 1 or a.scores:
         decs = {(n, kind): L.slot_decoder(n, cap) for n in slot_counts for kind in kinds}     # a kind's graphs stay its own
         bkw = dict(kw, num_beams=nb)
         stats = {}
+        sampled = a.sample or a.penalty != 1.0                     # beam sampling / the penalty under beams, on both sides
+        skw = {}
+        if sampled:
+            L.beam_sampling = True
+            skw = dict(do_sample=a.sample, top_p=0.9, top_k=50, temperature=a.temperature, repetition_penalty=a.penalty)
+
+        def gen_kw():                                              # the same seeds every repeat: the same work every repeat
+            return dict(generator=torch.Generator().manual_seed(0)) if a.sample else {}
 
         def set_kind(kind):
             L.decode_fp8, L.decode_fp4 = kind == "fp8", kind == "fp4"
 
         def beam_slots(n, kind, pb):
             set_kind(kind)
-            out = {i: lens_ for i, _, _, lens_ in decs[n, kind].run(reqs, prefill_batch=pb, **bkw)}
+            out = {i: lens_ for i, _, _, lens_ in decs[n, kind].run(reqs, prefill_batch=pb, **bkw, **skw, **gen_kw())}
             stats[(n, kind, pb)] = dict(decs[n, kind].last_stats)
             return [out[i][0] for i in range(len(reqs))]
 
@@ -229,7 +241,7 @@ if a.slots or len(slot_counts) > 1 or a.scores:
                 grp = reqs[g0:g0 + n]
                 S = max(x.shape[0] for x in grp)                   # one stacked prompt per group: left-pad with the first row
                 emb = torch.stack([torch.cat([x[:1].expand(S - x.shape[0], -1), x]) for x in grp])
-                L.beam_generate(emb, nb, **kw)
+                L.beam_generate(emb, nb, **kw, **skw, **gen_kw())
                 got += L.last_generate_stats["lengths"]
                 steps += L.last_generate_stats["steps"]
             stats[("batch", n, kind)] = dict(steps=steps)
@@ -257,7 +269,9 @@ if a.slots or len(slot_counts) > 1 or a.scores:
                 torch.cuda.synchronize()
                 res[name].append((time.perf_counter() - t0, got))
             print(f"repeat {rep + 1} of {max(1, a.repeats)} done", file=sys.stderr, flush=True)
-        print(f"{len(reqs)} requests, prompts {min(lens)}..{max(lens)} rows, num_beams {nb}, max_new_tokens {new}")
+        mode = (f", {'sampled top_p 0.9 top_k 50 temperature %g' % a.temperature if a.sample else 'deterministic'}"
+                f"{' penalty %g' % a.penalty if a.penalty != 1.0 else ''}") if sampled else ""
+        print(f"{len(reqs)} requests, prompts {min(lens)}..{max(lens)} rows, num_beams {nb}, max_new_tokens {new}{mode}")
         for name, key, _ in bmodes:
             ts = sorted(t for t, _ in res[name])
             t, got, st = ts[len(ts) // 2], res[name][-1][1], stats[key]
@@ -266,6 +280,41 @@ if a.slots or len(slot_counts) > 1 or a.scores:
             print(f"{name}: {t * 1e3:.1f} ms (median of {len(ts)}, min {ts[0] * 1e3:.1f}, max {ts[-1] * 1e3:.1f}) -> "
                   f"{len(reqs) / t:.2f} samples/s; {st['steps']} steps, {t * 1e3 / st['steps']:.3f} ms per step incl. prefills; best "
                   f"hypothesis {min(got)}..{max(got)} tokens, mean {sum(got) / len(got):.1f}{tail}")
+        if sampled:
+            # the captured slot step alone, sampled against deterministic at the same rows: every group live, identity parents,
+            # reset to --step-keys keys before each round
+            views = []
+            for kind in kinds:
+                for n in slot_counts:
+                    set_kind(kind)
+                    list(decs[n, kind].run(reqs[:2 * (n // nb)], **bkw))       # the deterministic view's graph
+                    bv = decs[n, kind].beam_views
+                    views += [(f"slots {n} weights {kind or 'bf16'}", which, bv[key]) for which, key in
+                              (("deterministic", (nb, False)), ("sampled", (nb, False, bool(a.sample))))]
+            n_rep, step_t = a.step_replays, {}
+            for rnd in range(max(1, a.repeats) + 1):                   # round 0 warms the replays up
+                for name, which, ws in views:
+                    keys = min(a.step_keys, ws["T"] - n_rep - 2)        # the round's appends stay inside the cache
+                    assert keys > 0 and ws["graph"] is not None, (ws["T"], n_rep)
+                    R_ = ws["pos"].shape[0]
+                    ws["bupd_host"].zero_()
+                    ws["bupd_host"][2 * R_:3 * R_].copy_(torch.arange(R_, dtype=torch.int32))
+                    ws["bupd"].copy_(ws["bupd_host"])
+                    for k, v in (("pos", keys), ("kvlen", keys + 1), ("lo", keys), ("gen", 4), ("live", 1), ("glive", 1)):
+                        ws[k].fill_(v)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(n_rep):
+                        ws["graph"].replay()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    if rnd:
+                        step_t.setdefault((name, which), []).append(e0.elapsed_time(e1) / n_rep)
+            for name in dict.fromkeys(v[0] for v in views):
+                det, smp_ = sorted(step_t[(name, "deterministic")]), sorted(step_t[(name, "sampled")])
+                md, ms = det[len(det) // 2], smp_[len(smp_) // 2]
+                print(f"{name} beam step: deterministic {det[0]:.3f} / {md:.3f} / {det[-1]:.3f} ms, sampled {smp_[0]:.3f} / {ms:.3f} / "
+                      f"{smp_[-1]:.3f} ms (min / median / max, {n_rep} replays per round) -> sampled / deterministic {ms / md:.3f}")
         sys.exit(0)
     if a.scores:
         from myriad_amd import ops
