@@ -70,6 +70,11 @@ def parse_args(argv=None):
     parser.add_argument("--seg-metrics", action="store_true", help="also score ve_anomaly_maps against the dataset's gt_mask: "
                         "pixel AUROC / AP / F1-max and AUPRO, accumulated on the device; writes <result>.seg.json "
                         "(--world > 1: <result>.seg.rankK.npz, to be merged with eval_protocol.merge_seg_shards)")
+    parser.add_argument("--draft-k", type=int, default=0, help="K > 1: draft-and-verify greedy decoding with K rows per verify "
+                        "step (batch size 1, no --slots): an n-gram drafter that observes every finished answer guesses K - 1 tokens, "
+                        "one token step verifies them; the records are those of the run without it")
+    parser.add_argument("--draft-corpus", type=str, default=None, help="with --draft-k: teach the drafter up front from a results "
+                        ".jsonl of an earlier run (its `output` texts are tokenised) or a JSON list of id lists")
     parser.add_argument("--seg-max-step", type=int, default=200, help="with --seg-metrics: thresholds of the PRO curve")
     parser.add_argument("--seg-expect-fpr", type=float, default=0.3, help="with --seg-metrics: the PRO curve is cut at this FPR")
     args = parser.parse_args(argv)
@@ -78,6 +83,12 @@ def parse_args(argv=None):
         parser.error("--beam-sample needs --num-beams N > 1")
     if args.repetition_penalty != 1.0 and args.num_beams <= 1:
         parser.error("--repetition-penalty needs --num-beams N > 1")
+    if args.draft_corpus and not args.draft_k:
+        parser.error("--draft-corpus needs --draft-k K")
+    if args.draft_k and (args.draft_k < 1 or args.draft_k > 8):
+        parser.error(f"--draft-k takes 1 to 8 rows, got {args.draft_k}")
+    if args.draft_k and (args.bs != 1 or args.slots > 0 or args.num_beams > 1 or args.llm_score):
+        parser.error("--draft-k decodes one sequence at a time: it needs --bs 1 and takes no --slots, --num-beams or --llm-score")
     if not args.seg_metrics and (args.seg_max_step != 200 or args.seg_expect_fpr != 0.3):
         parser.error("--seg-max-step / --seg-expect-fpr need --seg-metrics")
     if args.seg_max_step < 1:
@@ -201,6 +212,15 @@ def main(argv=None):
     if args.llm_score:
         generate_kwargs.update(output_scores=True, watch_ids=llm_watch_ids(model.llama_tokenizer))
 
+    drafter = None
+    if args.draft_k:
+        from myriad_amd.decode_host import NgramDrafter, load_draft_corpus
+        corpus = ()
+        if args.draft_corpus:
+            corpus = load_draft_corpus(args.draft_corpus, lambda t: model.llama_tokenizer(t, add_special_tokens=False).input_ids)
+        drafter = NgramDrafter(corpus)
+        generate_kwargs.update(draft=drafter, draft_k=args.draft_k)
+
     model.eval()
     seg = None
     if args.seg_metrics:
@@ -209,6 +229,7 @@ def main(argv=None):
     if args.slots > 0 and not args.rank_only:
         return save_path, _run_slots(args, model, loader, generate_kwargs, save_path, seg)
     records, all_time, sampled = [], 0.0, 0
+    draft_stats = dict(steps=0, verify_steps=0, plain_steps=0, draft_proposed=0, draft_accepted=0)
     for testid, data_sample in enumerate(loader):
         if testid < args.start:
             continue
@@ -224,6 +245,10 @@ def main(argv=None):
             texts = [rank_texts()[int(b)] for b in ranked["best"]]
         else:
             sampled += model.last_generate_stats.get("sampled_rows", 0)     # a beam search draws nothing
+            if drafter is not None:                      # the run warms itself: every finished answer teaches the drafter
+                drafter.observe(outputs["token_ids"][0].tolist())
+                for k in draft_stats:
+                    draft_stats[k] += model.last_generate_stats.get(k, 0)
             texts = EP.postprocess_generation(outputs["token_ids"], model.llama_tokenizer)
         maps = outputs.get("ve_anomaly_maps")
         if seg is not None:
@@ -245,6 +270,9 @@ def main(argv=None):
     print("Mean Time: ", all_time / n_batches)
     if sampled:
         print(f"note: {sampled} generated tokens had p_max < top_p and were drawn, not arg-maxed (see LlamaHIP.greedy_generate)")
+    if drafter is not None:
+        print(f"draft-and-verify (K = {args.draft_k}): {draft_stats['steps']} tokens in {draft_stats['verify_steps']} verify + "
+              f"{draft_stats['plain_steps']} plain steps, {draft_stats['draft_accepted']} of {draft_stats['draft_proposed']} guesses kept")
     return save_path, records
 
 

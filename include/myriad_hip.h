@@ -563,6 +563,28 @@ int mh_attn_decode_rope(void* qkv, long ld_qkv, void* cache, long cache_bstride,
 int mh_attn_decode_rope_rows(void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
                              const int* kv_len, const int* live, const float* cos_tab, const float* sin_tab, void* out, long ldo,
                              int B, int H, int D, int T_cap, float scale, mh_stream_t s);
+/* K consecutive token steps of each of G sequences in one launch (attn_decode_draft.hip; the verify step of draft-and-verify
+ * greedy decoding).  Row g*K + j of qkv [G*K, ld_qkv] is the token at position pos[g] + j of sequence g, 1 <= K <= 8; cache
+ * [G][T_cap][2 H D]; pos and live int[G] on the device, so a captured launch replays while the position moves.  There is no kv_len:
+ * the query of row j sees keys 0 .. pos[g] + j.  For a live sequence and every j < K, q (in place) and k are rotated at pos[g] + j,
+ * k | v are appended at cache row pos[g] + j, and the out row ([G*K, ldo] bf16), the rotated q and the cache row have the bits of
+ * mh_attn_decode_rope on that row alone at that position, run after rows 0 .. j-1 were appended: K sequential one-row steps.  Cache
+ * rows < pos[g] are only read, cache rows >= pos[g] + K are not touched.  A sequence with live[g] == 0 touches nothing and gets
+ * zero out rows; a row whose position would reach T_cap (the host keeps that from happening) writes no cache row, leaves its q
+ * alone and gets a zero out row.  MH_ERR_UNSUPPORTED, nothing launched, unless D % 16 == 0, D <= 128, K <= 8 and the LDS of a
+ * workgroup -- 4 * round_up(T_cap, 64) + 8192 + 2 K D bytes -- fits gfx950's 160 KiB; a call with G = 0 answers that question and
+ * reads no pointer.  MH_ERR_ARG for misaligned strides (ld_qkv, ld_cache, cache_bstride % 8, ldo % 4) or pointers. */
+int mh_attn_decode_rope_draft(void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
+                              const int* live, const float* cos_tab, const float* sin_tab, void* out, long ldo, int G, int K,
+                              int H, int D, int T_cap, float scale, mh_stream_t s);
+/* The end of that verify step (draft.hip), after mh_argmax_pmax_rows over the G*K logit rows: nxt / margin / pmax [G*K] are the
+ * rows' picks and ids [G*K] the tokens that were fed, ids[g*K] real and the rest guesses.  n_out = 1 + the number of leading
+ * j < K - 1 with nxt[j] == ids[j + 1] and pmax[j] >= *top_p (a device float; <= 0: no row needs a draw, p_max is not looked at).
+ * Writes rec[g] = 3K + 1 floats (the K ids, margins and p_max, then n_out), ids[g*K] = nxt[n_out - 1], pos[g] += n_out,
+ * kvlen[g] = pos[g] + 1 and *step += 1 once per launch.  1 <= K <= 8 (else MH_ERR_ARG).  The cache rows of rejected guesses stay
+ * behind, stale, at pos[g] .. (old pos[g]) + K - 1: the next verify step overwrites them and a plain step's kvlen stops short. */
+int mh_draft_accept(const long* nxt, const float* margin, const float* pmax, long* ids, const float* top_p, float* rec, int* pos,
+                    int* kvlen, int* step, int G, int K, mh_stream_t s);
 /* Packed prefill of several decode slots (attn_ragged.hip): causal self-attention over R sequences packed row-wise into qkv
  * [M, ld_qkv] bf16 = [q | k | v] (pre-rotary, only read), with the rotary at pos[row] and the KV-cache write fused in.  seg is the
  * device table int[R][3] of (row0, len, slot) and seg_host the host's copy of it: segment i is rows row0 .. row0 + len - 1, its

@@ -276,14 +276,16 @@ class Chat(_ChatBase):
     # ------------------------------------------------------------------ answer
     @torch.no_grad()
     def answer(self, conv, img_list, max_new_tokens=300, num_beams=1, min_length=1, top_p=0.9, repetition_penalty=1.0,
-               length_penalty=1, temperature=1.0, max_length=2000, do_sample=True, generator=None):
+               length_penalty=1, temperature=1.0, max_length=2000, do_sample=True, generator=None, draft=None, draft_k=4):
         """One assistant turn (conversation.py:144-178).  The context is truncated to the reference's window; the KV cache of the
         earlier turns is reused up to the first position whose token / image row differs.  `repetition_penalty` != 1 needs the
         device sampling switch, as in generate().  num_beams > 1: beam search on the full context, no reuse; with the beam sampling
         switch (MYRIAD_BEAM_SAMPLING=1 or model.llama.beam_sampling = True) it is the reference's own call -- beam-search
         multinomial sampling with do_sample, top_p, temperature, top_k = 50, repetition_penalty and generator
         (LlamaHIP.beam_generate) -- and last_stats gains num_beams, beam_sampled_steps and beam_host_steps; without it the
-        beams are deterministic and a penalty is refused, as before."""
+        beams are deterministic and a penalty is refused, as before.  `draft` / `draft_k`: draft-and-verify decoding of the turn
+        (LlamaHIP.greedy_generate; the same ids in fewer token steps when the drafter guesses well), refused with beams; a turn
+        on the split-KV view decodes with plain steps and last_stats["draft_off"] says "split_kv"."""
         m = self.model
         m.finish_update()
         llama = m.llama
@@ -296,6 +298,8 @@ class Chat(_ChatBase):
         embs, keys, begin = self._turn_context(conv, img_list, max_new_tokens, max_length)
         S = embs.shape[1]
         if int(num_beams) > 1:
+            if draft is not None:
+                raise NotImplementedError(f"answer(num_beams={num_beams}, draft=...): draft decoding is greedy decoding")
             if rep != 1.0 and not beam_sampling:
                 raise NotImplementedError(f"answer(num_beams={num_beams}, repetition_penalty={rep}) is not implemented")
             sample_kw = {}
@@ -313,12 +317,12 @@ class Chat(_ChatBase):
                                        beam_host_steps=st.get("beam_host_steps", 0))
         else:
             if self.session is None:
-                self.session = DecodeSession(llama, max_length + max_new_tokens + 2)
+                self.session = DecodeSession(llama, max_length + max_new_tokens + 2 + (0 if draft is None else int(draft_k)))
             ids = self.session.generate(embs, [keys], weights_version=m.store.version,
                                         reset_reason="window" if begin > 0 else None, max_new_tokens=max_new_tokens,
                                         stop_ids=STOP_WORDS, eos_id=2, min_length=min_length, do_sample=bool(do_sample),
                                         top_p=float(top_p), temperature=float(temperature), generator=generator, top_k=50,
-                                        repetition_penalty=rep)
+                                        repetition_penalty=rep, **({} if draft is None else dict(draft=draft, draft_k=draft_k)))
             self.last_stats = dict(self.session.last_stats)
         self.last_token_ids = ids                                    # [B, L] as decoded, before the post-processing
         return self._finish_turn(conv, ids[0].tolist())

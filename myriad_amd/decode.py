@@ -11,9 +11,9 @@ import numpy as np
 import torch
 
 from . import ops
-from .decode_host import (BeamItem, BeamSlotScheduler, RefillPlanner, ScorePlan, SessionTable, SlotScheduler, TurnPlanner, _host_draw,
-                          _request_generator, beam_batch_going, beam_sample_select, common_prefix, seeded_requests, split_kv_rows_rule,
-                          split_kv_rule)
+from .decode_host import (BeamItem, BeamSlotScheduler, DraftLoop, RefillPlanner, ScorePlan, SessionTable, SlotScheduler, TurnPlanner, _host_draw,
+                          _request_generator, beam_batch_going, beam_sample_select, common_prefix, run_draft_loop, seeded_requests,
+                          split_kv_rows_rule, split_kv_rule)
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -51,10 +51,12 @@ def _decode_buffers(lm: "LlamaHIP", B: int, T_cap: int, sampler: bool = False, n
     buffers join (_beam_buffers, and `lo`, where the generated positions start).  With
     `scores` the record is the one with the token scores' rows behind its four (_score_buffers)."""
     dev, i32 = lm.dev, torch.int32
-    ws = dict(T=T_cap, graph=None, warm=False, split=None, row_limit=row_limit,
+    # `ids` is the head of `ids_k`, which the K-row verify step of draft decoding reads whole: ids_k[0] is the fed token of both
+    ids_k = torch.zeros((max(B, ops.DRAFT_MAX_K),), dtype=torch.long, device=dev)
+    ws = dict(T=T_cap, graph=None, warm=False, split=None, row_limit=row_limit, ids_k=ids_k,
               caches=[torch.zeros((B, T_cap, 2 * lm.D), dtype=BF16, device=dev) for _ in lm.layers],
               pos=torch.zeros((B,), dtype=i32, device=dev), kvlen=torch.zeros((B,), dtype=i32, device=dev),
-              ids=torch.zeros((B,), dtype=torch.long, device=dev), x_in=torch.empty((B, lm.D), dtype=F32, device=dev),
+              ids=ids_k[:B], x_in=torch.empty((B, lm.D), dtype=F32, device=dev),
               logits=torch.empty((B, lm.V), dtype=F32, device=dev),
               nxt=torch.empty((B,), dtype=torch.long, device=dev), mar=torch.empty((B,), dtype=F32, device=dev),
               pmx=torch.empty((B,), dtype=F32, device=dev), step=torch.zeros((1,), dtype=i32, device=dev),
@@ -164,6 +166,37 @@ def _buffer_view(lm: "LlamaHIP", bufs: dict, split: bool, scores: bool = False) 
     if scores:
         view.update(rec=_score_buffers(lm, bufs)["srec"], watch=bufs["watch"])
     return view
+
+
+def _draft_view(lm: "LlamaHIP", bufs: dict, K: int, inv_temp: float) -> dict:
+    """The K-row verify step's view of a B = 1 buffer set (draft decoding): the caches, `pos`, `kvlen`, `step` and the fed token
+    ids_k[0] are the set's, shared with its plain one-row step, so the host switches between the two from step to step; the K-row
+    ids / activations / logits / picks, the 3K + 1 float record `drec`, the device float `top_p` and the always-live flag are the
+    view's own, and so is its graph.  Kept in the set (one per K and inv_temp, which the arg-max launch bakes in)."""
+    if bufs["ids"].shape[0] != 1:
+        raise NotImplementedError("draft decoding runs one sequence (batch 1)")
+    views = bufs.setdefault("draft_views", {})
+    key = (int(K), float(inv_temp))
+    if key not in views:
+        dev = lm.dev
+        views[key] = dict(bufs, graph=None, warm=False, split=None, draft_k=int(K), ids=bufs["ids_k"][:K],
+                          x_in=torch.empty((K, lm.D), dtype=F32, device=dev), logits=torch.empty((K, lm.V), dtype=F32, device=dev),
+                          nxt=torch.empty((K,), dtype=torch.long, device=dev), mar=torch.empty((K,), dtype=F32, device=dev),
+                          pmx=torch.empty((K,), dtype=F32, device=dev), drec=torch.zeros((3 * K + 1,), dtype=F32, device=dev),
+                          top_p=torch.zeros((1,), dtype=F32, device=dev), live1=torch.ones((1,), dtype=torch.int32, device=dev))
+    return views[key]
+
+
+def _draft_refusals(B: int, dev_sample: bool, penalty: bool, return_scores: bool, draft_k) -> int:
+    """The arguments draft decoding does not take; returns K."""
+    K = int(draft_k)
+    if not 1 <= K <= ops.DRAFT_MAX_K:
+        raise ValueError(f"draft_k={draft_k}: 1 to {ops.DRAFT_MAX_K} rows per verify step")
+    for on, what in ((B != 1, f"batch size {B} (one sequence only)"), (dev_sample, "device sampling"),
+                     (penalty, "repetition_penalty != 1"), (return_scores, "return_scores")):
+        if on:
+            raise NotImplementedError(f"draft decoding with {what} is not implemented")
+    return K
 
 
 class LlamaDecode:
@@ -376,6 +409,8 @@ class LlamaDecode:
             return self._fused_step_layers(ws, packed, lora)
         if ws.get("live") is not None:
             raise ValueError("per-row decode state needs the fused packed token step")
+        if ws.get("draft_k"):
+            raise ValueError("draft decoding needs the fused packed token step")
         H, hd, W, pos, scale = self.H, self.hd, self.D, ws["pos"], 1.0 / math.sqrt(self.hd)
 
         def lin(li, name, x, **kw):
@@ -403,7 +438,8 @@ class LlamaDecode:
         it the rows kernel instead: every row appends at its own pos[b], idle rows are skipped; only the fused step has that
         form.  Both together: the split-KV kernel in its rows form (ops.attn_decode_rope_split_rows), at 1 to GEMV_WIDE_MAX_ROWS
         rows alike.  Above GEMV_MAX_ROWS rows (_wide_step) the products are ops.gemv_packed_wide and the norm / SiLU products take
-        their two-launch forms."""
+        their two-launch forms.  ws["draft_k"] = K (_draft_view, draft decoding's verify step): the rows are K consecutive tokens
+        of one sequence and the attention is ops.attn_decode_rope_draft, row j at position pos + j."""
         H, hd, scale, cos, sin = self.H, self.hd, 1.0 / math.sqrt(self.hd), self.cos, self.sin
         pos, kvlen, live, split = ws["pos"], ws["kvlen"], ws.get("live"), ws["split"]
         wide = _wide_step(self, ws["x_in"].shape[0], ws["row_limit"])
@@ -412,6 +448,8 @@ class LlamaDecode:
         else:                                                            # one position for all rows: (pos, pos_dev, kvlen)
             attention, state = ops.attn_decode_rope if split is None else ops.attn_decode_rope_split, (pos, pos, kvlen)
         partials = () if split is None else (split,)
+        if ws.get("draft_k"):                                            # K consecutive rows of one sequence: (pos, live), K behind
+            attention, state, partials = ops.attn_decode_rope_draft, (pos, ws["live1"]), (ws["draft_k"],)
 
         def gemv(x, w, **kw):
             return (ops.gemv_packed_wide if wide else ops.gemv_packed)(x, w, **kw)
@@ -473,7 +511,8 @@ class LlamaDecode:
                         stop_ids=((835,), (2277, 29937)), eos_id: int = 2, min_length: int = 1,
                         return_margins: bool = False, use_graph: bool = True, do_sample: bool = False,
                         top_p: float = 1.0, temperature: float = 1.0, generator: Optional[torch.Generator] = None,
-                        top_k: int = 50, repetition_penalty: float = 1.0, return_scores: bool = False, watch_ids=()):
+                        top_k: int = 50, repetition_penalty: float = 1.0, return_scores: bool = False, watch_ids=(), draft=None,
+                        draft_k: int = 4):
         """Decode from [B,S0,D] f32 embeddings with a KV cache (prefill + 1-token steps).  Same contract
         as the oracle's greedy_generate: stop when ROW 0 ends with a stop sequence (conversation.py:102-107),
         EOS banned while fewer than `min_length` tokens were generated, finished rows padded with EOS.
@@ -508,26 +547,41 @@ class LlamaDecode:
         penalty when it is on; temperature, top-k, top-p and the EOS ban do not enter -- computed inside the step
         (mh_token_scores_rows, after the pick and before the advance) into rows of the step's record, so a step is still one
         device->host copy.  Positions padded after a row finished are 0.0.  A row the host re-draws takes its log-prob from the
-        logits row the host reads for the draw and the recorded normaliser."""
+        logits row the host reads for the draw and the recorded normaliser.
+
+        `draft` (opt-in, B = 1; a drafter with `propose` / `observe`, decode_host.NgramDrafter) with `draft_k` = K rows: draft-and-
+        verify decoding (_draft_core).  Steps past `min_length` feed the last token and K - 1 guessed tokens as K rows of one token
+        step and keep the guesses the arg-max confirms plus the one token the step produces anyway.  Every row of that step has the
+        bits of the one-row step at its position, so ids and margins are those of the call without `draft`, whatever the drafter
+        proposes; it only decides how many passes over the weights the answer takes.  NotImplementedError with B > 1, device
+        sampling, `repetition_penalty` != 1 or `return_scores`."""
         B, S0, _ = inputs_embeds.shape
         inv_temp, _, dev_sample, penalty = _sampling_args(self, do_sample, temperature, top_k, repetition_penalty)
         ops.score_watch_ids(watch_ids if return_scores else (), self.V)
+        K = 0 if draft is None else _draft_refusals(B, dev_sample, penalty, bool(return_scores), draft_k)
+        if K and S0 + max_new_tokens + K > self.cos.shape[0]:        # a verify step rotates K rows past the last fed position
+            raise ValueError(f"context {S0} + max_new_tokens {max_new_tokens} + draft_k {K} passes the rotary table "
+                             f"({self.cos.shape[0]} positions)")
         weight_stats = self._prepare_decode_weights(B)
-        ws = self._decode_workspace(B, S0 + max_new_tokens, inv_temp, dev_sample, penalty, scores=bool(return_scores))
+        ws = self._decode_workspace(B, S0 + max_new_tokens + K, inv_temp, dev_sample, penalty, scores=bool(return_scores))
         return self._greedy_core(inputs_embeds, ws, 0, weight_stats, max_new_tokens, stop_ids, eos_id, min_length, return_margins,
                                  use_graph, do_sample, top_p, temperature, generator, top_k, repetition_penalty, return_scores,
-                                 watch_ids)
+                                 watch_ids, draft, draft_k)
 
     def _greedy_core(self, inputs_embeds: torch.Tensor, ws: dict, past: int, weight_stats: dict, max_new_tokens: int = 90,
                      stop_ids=((835,), (2277, 29937)), eos_id: int = 2, min_length: int = 1, return_margins: bool = False,
                      use_graph: bool = True, do_sample: bool = False, top_p: float = 1.0, temperature: float = 1.0,
                      generator: Optional[torch.Generator] = None, top_k: int = 50, repetition_penalty: float = 1.0,
-                     return_scores: bool = False, watch_ids=()):
+                     return_scores: bool = False, watch_ids=(), draft=None, draft_k: int = 4):
         """greedy_generate's body on the caller's workspace `ws` (greedy_generate's from the _decode_ws cache, a DecodeSession's
         own buffers and graphs), on top of the cached prefix `past` that is not prefilled again; `weight_stats` is what
         _prepare_decode_weights answered for this call.  The other arguments are greedy_generate's, in its order."""
         B, S0, _ = inputs_embeds.shape
         inv_temp, top_k, dev_sample, penalty = _sampling_args(self, do_sample, temperature, top_k, repetition_penalty)
+        if draft is not None:
+            K = _draft_refusals(B, dev_sample, penalty, bool(return_scores), draft_k)
+            return self._draft_core(inputs_embeds, ws, past, weight_stats, draft, K, max_new_tokens, stop_ids, eos_id, min_length,
+                                    return_margins, use_graph, do_sample, top_p, inv_temp, top_k, generator)
         out_ids, margins = [], []
         unfinished = torch.ones(B, dtype=torch.long)
         stats = dict(steps=0, sampled_rows=0, min_pmax=1.0, device_sampled_rows=0, host_sampled_rows=0, graph_replays=0, **weight_stats)
@@ -633,6 +687,93 @@ class LlamaDecode:
         if scores:
             out += (dict(token_logprobs=torch.stack(tok_lp, 1), watch_logprobs=torch.stack(watch_lp, 1)),)
         return out if len(out) > 1 else ids
+
+    def _draft_core(self, inputs_embeds: torch.Tensor, ws: dict, past: int, weight_stats: dict, draft, K: int, max_new_tokens: int,
+                    stop_ids, eos_id: int, min_length: int, return_margins: bool, use_graph: bool, do_sample: bool, top_p: float,
+                    inv_temp: float, top_k: int, generator):
+        """_greedy_core for one sequence with draft-and-verify steps (greedy_generate(draft=...)).  The prefill and its first pick
+        are _greedy_core's.  Then decode_host.DraftLoop chooses each step: while the EOS ban is on, or when the drafter proposes
+        nothing, the plain one-row step of `ws`; otherwise the host writes the K - 1 guesses (id 0 as filler) behind the fed token
+        and replays the K-row verify step of _draft_view -- embed, the fused packed layers at K rows with
+        mh_attn_decode_rope_draft, final norm and lm-head at K rows, mh_argmax_pmax_rows, mh_draft_accept, which records the K
+        picks and how many of them stand, feeds the last of those back and moves pos / kvlen past them.  Both steps read and
+        advance the same caches, pos, kvlen, ids_k[0] and step, each from a graph of its own; a row of the verify step has the bits
+        of the plain step at its position, so switching is free and the answer is the plain loop's.  Per step the host makes one
+        device->host copy (the record) and at most one small host->device copy (the guesses, with a host-drawn id in front).
+
+        The verify step is off for the whole call, and last_generate_stats["draft_off"] says why, when `ws` runs the split-KV
+        attention ("split_kv") or mh_attn_decode_rope_draft does not take the shape ("unsupported").  Stats: verify_steps,
+        plain_steps, draft_proposed, draft_accepted (DraftLoop), verify_graph_replays and plain_graph_replays beside graph_replays."""
+        _, S0, _ = inputs_embeds.shape
+        if not (_packed_step(self, K, ws["row_limit"]) and self.decode_fused):
+            raise ValueError("draft decoding needs the fused packed token step (MYRIAD_PACK_DECODE and MYRIAD_DECODE_FUSED on)")
+        if ws["T"] < S0 + max_new_tokens + K:
+            raise ValueError(f"draft decoding needs a cache of {S0 + max_new_tokens + K} positions, the workspace holds {ws['T']}")
+        stats = dict(steps=0, sampled_rows=0, min_pmax=1.0, device_sampled_rows=0, host_sampled_rows=0, graph_replays=0,
+                     verify_graph_replays=0, plain_graph_replays=0, draft_k=K, draft_off=None, **weight_stats)
+        self.last_generate_stats = stats
+        loop = DraftLoop(draft, K, max_new_tokens, stop_ids, eos_id, min_length, do_sample, top_p, stats)
+        if ws["split"] is not None:
+            stats["draft_off"] = "split_kv"
+        elif not ops.attn_decode_draft_supported(self.H, self.hd, K, ws["T"]):
+            stats["draft_off"] = "unsupported"
+        loop.use_draft = stats["draft_off"] is None
+        dv = _draft_view(self, ws, K, inv_temp) if loop.use_draft else None
+        rec, ids_k, fresh = ws["rec"][:3], ws["ids_k"], [True]
+
+        def draw_from(logits, ban):
+            return lambda j: _host_draw(logits()[j], ban, inv_temp, top_k, top_p, generator)
+
+        logits0 = self._prefill(inputs_embeds, ws["caches"], past)
+        ban0 = eos_id if 0 < min_length else -1
+        ops.argmax_pmax_rows(logits0, ws["nxt"], ws["mar"], ws["pmx"], ban_id=ban0, inv_temp=inv_temp)
+        first = (ws["nxt"].cpu().tolist(), ws["mar"].cpu().tolist(), ws["pmx"].cpu().tolist(), 1, draw_from(lambda: logits0, ban0))
+        ws["pos"].fill_(S0)                                          # position of the incoming token
+        ws["kvlen"].fill_(S0 + 1)                                    # valid keys after the append
+        ws["step"].zero_()
+        if dv is not None:
+            dv["top_p"].fill_(float(top_p) if do_sample else 0.0)    # <= 0: no row needs a draw
+
+        def feed(fed, guesses=()):
+            """The step's host->device copy: the guesses, behind the fed token when the host chose it (the prefill's pick, a draw)."""
+            lead = fresh[0] or fed is not None
+            fresh[0] = False
+            vals = ([loop.ids[-1]] if lead else []) + list(guesses)
+            if vals:
+                lo = 0 if lead else 1
+                ids_k[lo:lo + len(vals)].copy_(torch.tensor(vals, dtype=torch.long))
+
+        def launch(view, token_step, ban, counter):
+            before = stats["graph_replays"]
+            self._launch_step(view, token_step, ban, use_graph, stats)
+            stats[counter] += stats["graph_replays"] - before
+
+        def plain_token_step(ban):
+            self._step_logits(ws)
+            ops.argmax_pmax_rows(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ban_id=ban, inv_temp=inv_temp)
+            ops.decode_advance(ws["nxt"], ws["mar"], ws["pmx"], rec, ws["ids"], ws["step"], ws["pos"], ws["kvlen"])
+
+        def verify_token_step(_ban):
+            self._step_logits(dv)
+            ops.argmax_pmax_rows(dv["logits"], dv["nxt"], dv["mar"], dv["pmx"], ban_id=-1, inv_temp=inv_temp)
+            ops.draft_accept(dv["nxt"], dv["mar"], dv["pmx"], dv["ids"], dv["top_p"], dv["drec"], ws["pos"], ws["kvlen"], ws["step"], K)
+
+        def plain_step(ban, fed):
+            feed(fed)
+            launch(ws, plain_token_step, ban, "plain_graph_replays")
+            r = rec.cpu()                                            # the one device->host copy of the step (it also waits for it)
+            return r[0].long().tolist(), r[1].tolist(), r[2].tolist(), 1, draw_from(lambda: ws["logits"], ban)
+
+        def verify_step(guesses, fed):
+            feed(fed, guesses)
+            launch(dv, verify_token_step, -1, "verify_graph_replays")
+            r = dv["drec"].cpu()
+            return (r[:K].long().tolist(), r[K:2 * K].tolist(), r[2 * K:3 * K].tolist(), int(r[3 * K]),
+                    draw_from(lambda: dv["logits"], -1))
+
+        run_draft_loop(loop, first, plain_step, verify_step)
+        ids = torch.tensor([loop.ids], dtype=torch.long)
+        return (ids, torch.tensor([loop.margins], dtype=F32)) if return_margins else ids
 
     @torch.no_grad()
     def beam_generate(self, inputs_embeds: torch.Tensor, num_beams: int, max_new_tokens: int = 90, stop_ids=(), eos_id: int = 2,
@@ -825,17 +966,19 @@ class DecodeSession:
         self.last_stats = {}
 
     def _begin_turn(self, keys, version, reason, B: int, S0: int, max_new_tokens: int, inv_temp: float, dev_sample: bool,
-                    penalty: bool, scores: bool = False):
-        """A turn's setup, once the decode weights are packed: invalidation, (re)allocation, the reused prefix.
+                    penalty: bool, scores: bool = False, draft_k: int = 0):
+        """A turn's setup, once the decode weights are packed: invalidation, (re)allocation, the reused prefix.  `draft_k`: the
+        rows of a draft turn's verify step, which the capacity and the rotary table must hold past the last fed position.
         Returns (workspace, past).  `scores`: the turn's step writes the token scores -- a view (and graph) of its own, whose key
         carries one more item, so the views of turns without scores are the ones they were."""
         L = self.llama
-        if S0 + max_new_tokens > L.cos.shape[0]:
-            raise ValueError(f"context {S0} + max_new_tokens {max_new_tokens} passes the rotary table ({L.cos.shape[0]} positions)")
+        if S0 + max_new_tokens + draft_k > L.cos.shape[0]:
+            raise ValueError(f"context {S0} + max_new_tokens {max_new_tokens}{f' + draft_k {draft_k}' if draft_k else ''} passes the "
+                             f"rotary table ({L.cos.shape[0]} positions)")
         if len(keys) != B or any(len(k) != S0 for k in keys):
             raise ValueError("one key per context position and batch row is required")
         stamp = _cache_stamp(L, version)
-        need = S0 + max_new_tokens + 2
+        need = S0 + max_new_tokens + 2 + draft_k
         if self.bufs is None:
             reason = reason or "empty cache"
         elif self.B != B:
@@ -870,7 +1013,7 @@ class DecodeSession:
     def generate(self, inputs_embeds: torch.Tensor, keys, weights_version=None, reset_reason: Optional[str] = None,
                  max_new_tokens: int = 90, **kw):
         """One turn: greedy_generate's contract and arguments (`max_new_tokens`, `stop_ids`, `eos_id`, `min_length`, `do_sample`,
-        `top_p`, `temperature`, `generator`, `top_k`, `repetition_penalty`, `return_margins`, `return_scores`, `watch_ids`) on
+        `top_p`, `temperature`, `generator`, `top_k`, `repetition_penalty`, `return_margins`, `return_scores`, `watch_ids`, `draft`, `draft_k`) on
         [B, S0, D] f32 embeddings whose
         positions are named by `keys` ([B][S0]).  `weights_version`: anything that changes when the weights do."""
         L = self.llama
@@ -880,9 +1023,10 @@ class DecodeSession:
             inv_temp, _, dev_sample, penalty = _sampling_args(L, **kw)
             scores = bool(kw.get("return_scores", False))
             ops.score_watch_ids(kw.get("watch_ids", ()) if scores else (), L.V)
+            draft_k = 0 if kw.get("draft") is None else _draft_refusals(B, dev_sample, penalty, scores, kw.get("draft_k", 4))
             weight_stats = L._prepare_decode_weights(B)              # packed before the stamp, which names the packed copies
             ws, past = self._begin_turn([list(k) for k in keys], weights_version, reset_reason, B, S0, max_new_tokens, inv_temp,
-                                        dev_sample, penalty, scores)
+                                        dev_sample, penalty, scores, draft_k)
             graph = ws["graph"]
             out = L._greedy_core(inputs_embeds, ws, past, weight_stats, max_new_tokens=max_new_tokens, use_graph=True, **kw)
         except BaseException:
@@ -903,6 +1047,9 @@ class DecodeSession:
         self.keys = new_keys
         st = self.llama.last_generate_stats
         self.last_stats.update(steps=st["steps"], graph_replays=st["graph_replays"], graph_captures=self.graph_captures)
+        if "draft_k" in st:                                          # a draft turn: a split-KV view decodes with plain steps
+            self.last_stats.update({k: st[k] for k in ("draft_k", "draft_off", "verify_steps", "plain_steps", "draft_proposed",
+                                                       "draft_accepted")})
         return out
 
 

@@ -3,7 +3,9 @@ drive every class.  The slot engine's bookkeeping (SlotScheduler), its refill an
 chat pool's session table (SessionTable), the per-request random streams (seeded_requests), the replay of a known run
 (replay_slot_run), the split-KV rules with their measurements, the host draw of one row (_host_draw), the beam-sampling
 step of one item (beam_sample_select), and beam search's host rule: one request's search state (BeamItem), when a batch of them
-goes on (beam_batch_going) and the slots' scheduler of the groups of num_beams rows (BeamSlotScheduler)."""
+goes on (beam_batch_going) and the slots' scheduler of the groups of num_beams rows (BeamSlotScheduler); draft-and-verify decoding's
+drafter (NgramDrafter), the host side of its loop (DraftLoop, run_draft_loop) and the predictor of a run's step counts
+(predict_draft_run)."""
 from __future__ import annotations
 
 from typing import Optional
@@ -676,3 +678,172 @@ def replay_slot_run(lengths, ids, slots: int, max_new_tokens: int, stop_ids=(), 
         sched.step(picks, [0.0] * slots)
     return dict(prefills=prefills, prefill_passes=plan.passes, packed_rows=plan.packed_rows, steps=sched.steps,
                 live_row_steps=sched.live_row_steps, occupancy=sched.occupancy)
+
+
+# ---- draft-and-verify greedy decoding (LlamaDecode.greedy_generate(draft=...)): the drafter, the predictor of a run's step counts
+# and the host side of the loop.  The device verifies K - 1 guessed tokens in one K-row token step whose rows carry the bits of K
+# one-row steps, so whatever the drafter proposes the ids and margins are those of the plain loop; the drafter only decides how
+# many steps the answer takes.
+DRAFT_START = -1                                                     # the start sentinel in front of every answer
+
+
+class NgramDrafter:
+    """Proposes the continuation of an answer from the answers seen so far: for every context of 1 .. `max_order` ids (the start
+    sentinel counts as one) the table counts each id that followed it.  Deterministic, no device call.  Any object with `propose`
+    and `observe` serves as a drafter."""
+
+    def __init__(self, corpus=(), max_order: int = 4):
+        if int(max_order) < 1:
+            raise ValueError(f"max_order must be >= 1, got {max_order}")
+        self.max_order = int(max_order)
+        self.table = {}                                              # context tuple -> {successor: count}, in order of first sight
+        for ids in corpus:
+            self.observe(ids)
+
+    def observe(self, ids) -> None:
+        """Add a finished answer (its generated ids)."""
+        seq = [DRAFT_START] + [int(t) for t in ids]
+        for i in range(1, len(seq)):
+            for n in range(1, min(self.max_order, i) + 1):
+                succ = self.table.setdefault(tuple(seq[i - n:i]), {})
+                succ[seq[i]] = succ.get(seq[i], 0) + 1
+
+    def _next(self, h: list):
+        for n in range(min(self.max_order, len(h)), 0, -1):          # the longest suffix the table knows
+            succ = self.table.get(tuple(h[-n:]))
+            if succ:
+                return max(succ, key=succ.get)                       # most frequent; max() keeps the first of equals = first observed
+        return None
+
+    def propose(self, history, k: int) -> list:
+        """At most k ids that may follow `history` (the ids generated so far in this answer; the sentinel is put in front here):
+        the most frequent successor of the longest known suffix, ties to the one observed first, extended on its own proposals."""
+        h, out = [DRAFT_START] + [int(t) for t in history], []
+        while len(out) < int(k):
+            t = self._next(h)
+            if t is None:
+                break
+            out.append(t)
+            h.append(t)
+        return out
+
+
+def _ends_with_stop(ids: list, stop_ids) -> bool:
+    return any(len(ids) >= len(st) and ids[-len(st):] == list(st) for st in stop_ids)
+
+
+class DraftLoop:
+    """The host side of one B = 1 answer decoded with draft-and-verify steps: which step comes next and with which guesses, and
+    what a step's record adds to the answer.  `take` gets a step's record -- the K picks with their margins and p_max and n_out,
+    the count the device accepted (a plain step: one pick, n_out = 1) -- and emits n_out tokens, cut at EOS, at a stop sequence
+    ending inside the window and at max_new_tokens.  Under do_sample a row with p_max < top_p (the host-draw rule) ends the window
+    on the device already; its id is drawn here (`draw(j)`) and handed on as `fed`, the id the next step must be fed in place of
+    the one the device fed itself.  `stats` gains steps (tokens), verify_steps, plain_steps, draft_proposed (real guesses fed) and
+    draft_accepted (emitted tokens that were confirmed guesses)."""
+
+    def __init__(self, drafter, k: int, max_new_tokens: int, stop_ids=(), eos_id: int = 2, min_length: int = 1,
+                 do_sample: bool = False, top_p: float = 1.0, stats: Optional[dict] = None):
+        self.drafter, self.k = drafter, int(k)
+        self.max_new_tokens, self.stop_ids, self.eos_id, self.min_length = int(max_new_tokens), tuple(stop_ids), int(eos_id), int(min_length)
+        self.do_sample, self.top_p = bool(do_sample), float(top_p)
+        self.stats = {} if stats is None else stats
+        for name in ("steps", "verify_steps", "plain_steps", "draft_proposed", "draft_accepted", "sampled_rows", "host_sampled_rows"):
+            self.stats.setdefault(name, 0)
+        self.stats.setdefault("min_pmax", 1.0)
+        self.ids, self.margins = [], []
+        self.done, self.fed, self.use_draft = False, None, True
+
+    def ban(self) -> int:
+        """The EOS ban of the next (plain) step."""
+        return self.eos_id if len(self.ids) < self.min_length else -1
+
+    def guesses(self) -> list:
+        """The K - 1 guesses of the next step, real proposals first and id 0 as filler, or [] for a plain one-row step: while
+        the EOS ban is on, when the drafter proposes nothing, at K = 1, or with the verify step switched off (`use_draft`)."""
+        if not self.use_draft or self.k < 2 or len(self.ids) < self.min_length:
+            return []
+        prop = [int(t) for t in self.drafter.propose(list(self.ids), self.k - 1)][:self.k - 1]
+        if not prop:
+            return []
+        self.stats["draft_proposed"] += len(prop)
+        return prop + [0] * (self.k - 1 - len(prop))
+
+    def take(self, ids, margins, pmax, n_out: int, draw=None, first: bool = False) -> None:
+        """One step's record.  `first`: the prefill's pick, which counts as neither kind of step."""
+        n_out, rows = int(n_out), len(ids)
+        if not 1 <= n_out <= rows:
+            raise ValueError(f"n_out={n_out} of a {rows}-row record")
+        if not first:
+            self.stats["verify_steps" if rows > 1 else "plain_steps"] += 1
+        self.fed, taken = None, 0
+        for j in range(n_out):
+            tok, pm = int(ids[j]), float(pmax[j])
+            self.margins.append(float(margins[j]))
+            self.stats["steps"] += 1
+            if self.do_sample:
+                self.stats["min_pmax"] = min(self.stats["min_pmax"], pm)
+                if pm < self.top_p:
+                    if j != n_out - 1:
+                        raise ValueError("a row that needs a host draw must end its window")
+                    self.stats["sampled_rows"] += 1
+                    self.stats["host_sampled_rows"] += 1
+                    tok = self.fed = int(draw(j))
+            self.ids.append(tok)
+            taken += 1
+            if tok == self.eos_id or _ends_with_stop(self.ids, self.stop_ids) or len(self.ids) >= self.max_new_tokens:
+                self.done = True
+                break
+        if rows > 1:
+            self.stats["draft_accepted"] += taken - 1
+
+
+def run_draft_loop(loop: DraftLoop, first, plain_step, verify_step) -> DraftLoop:
+    """Drive `loop` to the end of its answer.  `first` = the prefill's record (ids, margins, pmax, n_out, draw);
+    `plain_step(ban, fed)` and `verify_step(guesses, fed)` run one step and return such a record, `fed` being the id the host
+    drew for the last token (else None: the device fed itself)."""
+    loop.take(*first, first=True)
+    while not loop.done:
+        g = loop.guesses()
+        loop.take(*(verify_step(g, loop.fed) if g else plain_step(loop.ban(), loop.fed)))
+    return loop
+
+
+def predict_draft_run(drafter, chain, k: int, min_length: int = 1) -> dict:
+    """The step counts of decoding the answer `chain` (every emitted id, the prefill's pick first) with `drafter` at K = k rows
+    per verify step and no host draw: verify_steps, plain_steps, draft_proposed, draft_accepted, as DraftLoop counts them."""
+    chain = [int(t) for t in chain]
+    st = dict(verify_steps=0, plain_steps=0, draft_proposed=0, draft_accepted=0)
+    n = 1
+    while n < len(chain):
+        prop = [] if k < 2 or n < min_length else [int(t) for t in drafter.propose(chain[:n], k - 1)][:k - 1]
+        if not prop:
+            st["plain_steps"] += 1
+            n += 1
+            continue
+        st["verify_steps"] += 1
+        st["draft_proposed"] += len(prop)
+        fed = prop + [0] * (k - 1 - len(prop))
+        take = 1                                                     # row j's pick is chain[n + j] while every earlier guess was right
+        while take < k and n + take < len(chain) and fed[take - 1] == chain[n + take - 1]:
+            take += 1
+        st["draft_accepted"] += take - 1
+        n += take
+    return st
+
+
+def load_draft_corpus(path: str, tokenize=None) -> list:
+    """A drafter's corpus from a file: a JSON list of id lists, or a results .jsonl of an evaluation run whose `output` texts
+    `tokenize` (text -> ids) turns into ids."""
+    import json
+    with open(path) as f:
+        text = f.read()
+    try:
+        data = json.loads(text)
+        if isinstance(data, list) and all(isinstance(r, list) for r in data):
+            return [[int(t) for t in r] for r in data]
+        data = [data]
+    except json.JSONDecodeError:
+        data = [json.loads(ln) for ln in text.splitlines() if ln.strip()]
+    if tokenize is None:
+        raise ValueError(f"{path}: a results file needs a tokenizer to turn its output texts into ids")
+    return [[int(t) for t in tokenize(r["output"])] for r in data if isinstance(r, dict) and "output" in r]

@@ -1365,9 +1365,12 @@ class MyriadHIP(nn.Module):
         if output_scores and num_beams > 1:
             raise NotImplementedError(f"generate(num_beams={num_beams}, output_scores=True): beam search reports "
                                       "sequences_scores (last_generate_stats); per-token scores are not implemented with beams")
+        draft, draft_k = kw.pop("draft", None), kw.pop("draft_k", 4)
+        if draft is not None and num_beams > 1:
+            raise NotImplementedError(f"generate(draft=..., num_beams={num_beams}): draft decoding is greedy decoding of one sequence")
         if kw:
             raise TypeError(f"generate() got unsupported arguments: {sorted(kw)}")
-        return dict(stops=stops, max_new=max_new, max_len=None if max_new is not None else max_len, do_sample=do_sample,
+        return dict(draft=draft, draft_k=draft_k, stops=stops, max_new=max_new, max_len=None if max_new is not None else max_len, do_sample=do_sample,
                     top_p=top_p, temperature=temperature, min_length=min_length, eos_id=eos_id, top_k=top_k, rep_pen=rep_pen,
                     num_beams=num_beams, beam_kw=beam_kw, generator=generator, output_scores=output_scores, watch_ids=watch_ids)
 
@@ -1404,7 +1407,13 @@ class MyriadHIP(nn.Module):
         the EOS ban do not enter), computed inside the captured token step (LlamaHIP.greedy_generate).  Positions padded after
         a row finished are 0.0.  watch_logprobs[:, 0] of the "Yes" / "No" ids is the model's own anomaly score
         (eval_aqa.py --llm-score).  With num_beams > 1 it raises NotImplementedError; more than 8 ids, a non-integer or an id
-        outside the vocabulary is a ValueError."""
+        outside the vocabulary is a ValueError.
+
+        draft=<drafter> (opt-in; decode_host.NgramDrafter or any object with propose / observe) with draft_k = K in 1 .. 8 rows:
+        draft-and-verify greedy decoding of ONE sample (LlamaHIP.greedy_generate): the same token_ids as without it, in fewer
+        passes over the decoder weights when the drafter guesses well; last_generate_stats gains verify_steps, plain_steps,
+        draft_proposed and draft_accepted.  NotImplementedError with a batch of more than one sample, beams, device sampling,
+        repetition_penalty != 1 or output_scores.  The caller teaches the drafter (drafter.observe(ids))."""
         self.finish_update()
         a = self._generate_args(generate_kwargs)
         stops, max_new, max_len, do_sample, top_p, temperature = (a[k] for k in ("stops", "max_new", "max_len", "do_sample", "top_p",
@@ -1433,7 +1442,7 @@ class MyriadHIP(nn.Module):
             ids = self.llama.greedy_generate(emb, max_new_tokens=max_new, stop_ids=stops, min_length=min_length, eos_id=eos_id,
                                              do_sample=do_sample, top_p=top_p, temperature=temperature, generator=generator,
                                              top_k=top_k, repetition_penalty=rep_pen, return_scores=a["output_scores"],
-                                             watch_ids=a["watch_ids"])
+                                             watch_ids=a["watch_ids"], draft=a["draft"], draft_k=a["draft_k"])
         self.last_generate_stats = self.llama.last_generate_stats
         if a["output_scores"]:
             ids, sc = ids
@@ -1559,6 +1568,8 @@ class MyriadHIP(nn.Module):
         output_scores / watch_ids as in generate(): each yielded dict gains "token_logprobs" [L] and "watch_logprobs" [L, W]."""
         self.finish_update()
         a = self._generate_args(generate_kwargs)
+        if a["draft"] is not None:
+            raise NotImplementedError("generate_stream(draft=...): draft decoding runs one sequence per call (generate)")
         nb, beam_kw = a["num_beams"], {}
         if nb > 1:
             if not getattr(self.llama, "slot_beams", False):

@@ -417,6 +417,56 @@ def attn_decode_rope_rows(qkv2d: torch.Tensor, cache: torch.Tensor, pos: torch.T
     return out
 
 
+DRAFT_MAX_K = 8        # most rows per sequence mh_attn_decode_rope_draft / mh_draft_accept take (include/myriad_hip.h)
+
+
+def attn_decode_draft_supported(n_heads: int, head_dim: int, K: int, T_cap: int) -> bool:
+    """Whether mh_attn_decode_rope_draft takes this shape (head dim, rows per sequence, the LDS for T_cap scores): the launcher's
+    own answer to a call with no sequence, which launches nothing."""
+    rc = _L().mh_attn_decode_rope_draft(None, 0, None, 0, 0, None, None, None, None, None, 0, 0, int(K), int(n_heads), int(head_dim),
+                                        int(T_cap), 1.0, _s())
+    if rc == -3:                                                         # MH_ERR_UNSUPPORTED
+        return False
+    _lib.check(rc, "mh_attn_decode_rope_draft (probe)")
+    return True
+
+
+def attn_decode_rope_draft(qkv2d: torch.Tensor, cache: torch.Tensor, pos: torch.Tensor, live: torch.Tensor, cos_tab: torch.Tensor,
+                           sin_tab: torch.Tensor, n_heads: int, head_dim: int, scale: float, K: int,
+                           out: Optional[torch.Tensor] = None):
+    """K consecutive token steps of each of G sequences as one launch (the verify step of draft-and-verify decoding): row g*K + j
+    of qkv2d [G*K, >=3W] is the token at position pos[g] + j, cache [G, T, 2W], pos / live int32 [G].  Every row has the bits of
+    attn_decode_rope on it alone at its position after the rows before it were appended; returns o [G*K, W] bf16."""
+    _chk2d(qkv2d, BF16, "attn_decode_rope_draft.qkv")
+    R, W, K = qkv2d.shape[0], n_heads * head_dim, int(K)
+    G = cache.shape[0]
+    if K < 1 or R != G * K or qkv2d.shape[1] < 3 * W or cache.shape[2] != 2 * W:
+        raise _lib.MyriadHipError("attn_decode_rope_draft: qkv must be [G*K, >=3W] and cache [G, T, 2W]")
+    for name, t in (("pos", pos), ("live", live)):
+        if t.dtype != torch.int32 or t.numel() != G or not t.is_contiguous():
+            raise _lib.MyriadHipError(f"attn_decode_rope_draft: {name} must be a contiguous int32 [G]")
+    if out is None:
+        out = torch.empty((R, W), dtype=BF16, device=qkv2d.device)
+    elif out.dtype != BF16 or out.shape != (R, W) or out.stride(1) != 1:
+        raise _lib.MyriadHipError("attn_decode_rope_draft: out must be bf16 [G*K, W]")
+    _lib.check(_L().mh_attn_decode_rope_draft(_p(qkv2d), qkv2d.stride(0), _p(cache), cache.stride(0), cache.stride(1), _p(pos),
+                                              _p(live), _p(cos_tab), _p(sin_tab), _p(out), out.stride(0), G, K, n_heads, head_dim,
+                                              cache.shape[1], float(scale), _s()), "mh_attn_decode_rope_draft")
+    return out
+
+
+def draft_accept(nxt, margin, pmax, ids, top_p: torch.Tensor, rec, pos, kvlen, step_dev, K: int):
+    """The end of a verify step over G = nxt.numel() / K sequences: rec[g] = (K ids, K margins, K p_max, n_out) as f32, where n_out
+    = 1 + the leading guesses ids[1..] the picks confirm (with p_max >= top_p, a device float; <= 0: not looked at);
+    ids[g*K] = the last accepted pick, pos[g] += n_out, kvlen[g] = pos[g] + 1, step += 1 -- all on the device."""
+    K = int(K)
+    G = nxt.numel() // K
+    if K < 1 or nxt.numel() != G * K or ids.numel() < G * K or rec.numel() < G * (3 * K + 1) or pos.numel() < G or kvlen.numel() < G:
+        raise _lib.MyriadHipError("draft_accept: nxt / margin / pmax / ids hold G*K rows, rec G*(3K+1) floats, pos / kvlen G ints")
+    _lib.check(_L().mh_draft_accept(_p(nxt), _p(margin), _p(pmax), _p(ids), _p(top_p), _p(rec), _p(pos), _p(kvlen), _p(step_dev), G, K,
+                                    _s()), "mh_draft_accept")
+
+
 def _attn_prefill_ragged(sw: int, qkv2d, pos, seg, seg_host, cache, cos_tab, sin_tab, n_heads, head_dim, scale, out,
                          shared: bool = False):
     """attn_prefill_ragged (sw = 3 ints per segment), attn_prefill_ragged_past (sw = 4) and attn_prefill_ragged_shared (sw = 4,

@@ -44,7 +44,13 @@ padded batches, and then the captured slot step alone, sampled against determini
 first --requests / 8 requests), and through each slot count, with and without the token scores (two watched ids), interleaved per
 repeat in one process, as run time and samples/s; then the captured token step of each of those views alone, every row live,
 replayed --step-replays times per round from --step-keys keys (fewer where the view's cache is shorter); then mh_token_scores_rows alone at 1 and 64 rows of the model's
-vocabulary.  min / median / max of both sides."""
+vocabulary.  min / median / max of both sides.
+
+--draft-k 1,2,4,8 [--weights bf16,fp8,fp4] measures draft-and-verify decoding at batch 1: the captured K-row verify step at each
+K beside the captured plain one-row step, replayed interleaved from --step-keys keys (--step-replays replays per round, median
+of --repeats rounds; every guess is wrong, so each replay moves the position by one), with the kept-guess rate at which each K
+breaks even; then greedy_generate end to end on a prompt of --step-keys rows and a countdown chain of --new tokens with a drafter
+taught the chain, one whose guesses hold in every other window, and none -- the answer is asserted to be the chain each time."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -76,6 +82,9 @@ ap.add_argument("--num-beams", type=int, default=1, help="with --slots S[,S..]: 
 ap.add_argument("--prefill-batch", default="1", help="comma list: prefill_batch of the --slots run, timed interleaved")
 ap.add_argument("--refill-min", default="1", help="comma list: refill_min of the --slots run, timed interleaved")
 ap.add_argument("--scores", action="store_true", help="the cost of return_scores: batch 1 and each --slots count, with and without")
+ap.add_argument("--draft-k", default="", help="comma list of K (1..8): time the captured K-row verify step of draft decoding against the "
+                "plain batch-1 step at --step-keys keys for each of --weights, interleaved, medians of --repeats rounds; then end-to-end "
+                "tokens/s on a countdown chain of --new tokens with a drafter taught the chain, one that confirms half of its guesses, none")
 ap.add_argument("--merge", default="", help="comma list of 0 / 1: bordered / merged LoRA qkv in the token step, timed interleaved")
 a = ap.parse_args()
 # --slots is a string so that it can be a list; from here on a.slots is the single count (0: none or a list) and slot_counts the list
@@ -104,6 +113,130 @@ def make_samples(n):
                 before_ids=torch.randint(3, 32000, (1, 4), generator=g).expand(n, -1).contiguous(),
                 after_ids=torch.randint(3, 32000, (1, 28), generator=g).expand(n, -1).contiguous())
 
+
+if a.draft_k:
+    # The verify step is assembled from the loop's own pieces (_draft_view for the buffers, LlamaHIP._step_logits, the arg-max and
+    # mh_draft_accept tail of LlamaHIP._draft_core's verify_token_step): a copy of its three lines -- change them together.  Every
+    # guess is id 0 and never confirmed, so pos moves by one per replay, as in the plain step beside it.
+    from myriad_amd import ops
+    from myriad_amd.decode_host import NgramDrafter
+    from myriad_amd.decode import _decode_buffers, _draft_view
+    L = model.llama
+    Ks = [int(x) for x in a.draft_k.split(",") if x]
+    rounds, n_rep = max(1, a.repeats) + 1, a.step_replays           # round 0 is the warm-up of the graph itself
+    T_cap = 64 * ((a.step_keys + rounds * n_rep + 16 + 63) // 64)
+    gi = torch.Generator().manual_seed(3)
+    # the countdown chain of the end-to-end runs below (token 1000+k is followed by 1000+k-1, 1000 stops), written into the
+    # embedding / lm-head rows before any packed copy of them is made
+    new, D = a.new, L.D
+    gq = torch.Generator().manual_seed(11)
+    dirs = torch.nn.functional.normalize(torch.randn(new + 1, D, generator=gq), dim=1)
+    emb_rows = dirs * (D ** 0.5) * 2.0
+    L.embed[1000:1001 + new].copy_(emb_rows.to(L.embed.dtype).to(dev))
+    head = L.lm_head[1000:1001 + new].float().cpu()
+    head[:new] += 2.5 * dirs[1:]
+    L.lm_head[1000:1001 + new].copy_(head.to(L.lm_head.dtype).to(dev))
+    configs, keep = [], []                                           # (kind, K or 0 = plain, graph, reset)
+    for kind in (kinds if kinds != [None] else ["bf16"]):
+        L.decode_fp8, L.decode_fp4 = kind == "fp8", kind == "fp4"
+        L._prepare_decode_weights(1)
+        ws = _decode_buffers(L, 1, T_cap)
+        for c in ws["caches"]:
+            c[:, :a.step_keys].normal_(0.0, 0.5)
+
+        def reset(ws=ws):
+            ws["ids_k"].copy_(torch.randint(3, 32000, (8,), generator=gi))
+            ws["pos"].fill_(a.step_keys)
+            ws["kvlen"].fill_(a.step_keys + 1)
+
+        def plain(ws=ws):
+            L._step_logits(ws)
+            ops.argmax_pmax_rows(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ban_id=-1, inv_temp=1.0)
+            ops.decode_advance(ws["nxt"], ws["mar"], ws["pmx"], ws["rec"][:3], ws["ids"], ws["step"], ws["pos"], ws["kvlen"])
+
+        steps = [(0, plain)]
+        for K in Ks:
+            dv = _draft_view(L, ws, K, 1.0)
+
+            def verify(dv=dv, ws=ws, K=K):
+                L._step_logits(dv)
+                ops.argmax_pmax_rows(dv["logits"], dv["nxt"], dv["mar"], dv["pmx"], ban_id=-1, inv_temp=1.0)
+                ops.draft_accept(dv["nxt"], dv["mar"], dv["pmx"], dv["ids"], dv["top_p"], dv["drec"], ws["pos"], ws["kvlen"], ws["step"], K)
+            steps.append((K, verify))
+        for K, step in steps:
+            reset()
+            step()                                                   # eager once: kernels loaded, attributes set
+            torch.cuda.synchronize()
+            g_ = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g_):
+                step()
+            configs.append((kind, K, g_, reset))
+        keep.append(ws)
+    res = {i: [] for i in range(len(configs))}
+    for rnd in range(rounds):
+        for i, (_, _, g_, reset) in enumerate(configs):
+            reset()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(n_rep):
+                g_.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            if rnd:
+                res[i].append(e0.elapsed_time(e1) / n_rep)
+    print(f"batch-1 token step, {a.step_keys}+ keys, {len(L.layers)} layers; median of {rounds - 1} rounds of {n_rep} replays")
+    base = {}
+    for i, (kind, K, _, _) in enumerate(configs):
+        ts = sorted(res[i])
+        t = ts[len(ts) // 2]
+        if K == 0:
+            base[kind] = t
+            print(f"weights {kind} plain step: {t:.3f} ms (min {ts[0]:.3f}, max {ts[-1]:.3f})")
+        else:                                                        # break-even: mean tokens per verify step that pays for it
+            print(f"weights {kind} verify step K={K}: {t:.3f} ms (min {ts[0]:.3f}, max {ts[-1]:.3f}), {t / base[kind]:.3f}x the plain step; "
+                  f"all {K} kept: {t / K:.3f} ms/token; breaks even at {t / base[kind]:.2f} tokens/step"
+                  + (f" = {(t / base[kind] - 1) / (K - 1):.2f} of the guesses kept" if K > 1 else ""))
+    # ---- end to end: greedy_generate at batch 1 on the countdown chain
+    x = torch.randn(1, a.step_keys, D, generator=gq) * 0.02
+    x[0, -1] = emb_rows[new]
+    x = x.to(dev)
+    kw = dict(max_new_tokens=new, stop_ids=((1000,),), eos_id=-5, min_length=0)
+    chain = list(range(1000 + new - 1, 999, -1))
+
+    class Half:
+        """Every other window's guesses are the chain's, the others are wrong: half of the guesses are confirmed."""
+        def __init__(self):
+            self.good, self.n = NgramDrafter([chain]), 0
+
+        def propose(self, history, k):
+            self.n += 1
+            return self.good.propose(history, k) if self.n % 2 else [7] * k
+
+    e2e = {}
+    drafters = [("none", None)] + [(f"{name} K={K}", mk) for K in Ks if K > 1 for name, mk in (("taught", lambda: NgramDrafter([chain])), ("half", Half))]
+    for rnd in range(rounds):
+        for kind in (kinds if kinds != [None] else ["bf16"]):
+            L.decode_fp8, L.decode_fp4 = kind == "fp8", kind == "fp4"
+            for label, mk in drafters:
+                dkw = {} if mk is None else dict(draft=mk(), draft_k=int(label.split("=")[1]))
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ids = L.greedy_generate(x, **kw, **dkw)
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                assert ids[0].tolist() == chain, (label, ids)
+                if rnd:
+                    st = L.last_generate_stats
+                    e2e.setdefault((kind, label), []).append((dt, st.get("verify_steps", 0), st.get("plain_steps", st["steps"] - 1),
+                                                              st.get("draft_accepted", 0), st.get("draft_proposed", 0)))
+    print(f"end to end, batch 1, prompt {a.step_keys} rows + {new} tokens of the countdown chain (prefill included); median of {rounds - 1}")
+    for (kind, label), rs in e2e.items():
+        rs.sort()
+        dt, vs, ps, acc, prop = rs[len(rs) // 2]
+        print(f"weights {kind} drafter {label}: {new / dt:.1f} tok/s ({dt * 1e3:.1f} ms; {vs} verify + {ps} plain steps; "
+              f"{acc} of {prop} guesses kept)")
+    L.decode_fp8 = L.decode_fp4 = False
+    sys.exit(0)
 
 if a.step_rows:
     # The timed step is assembled here from the engine's own pieces (SlotDecoder._workspace for the buffers and weights,
