@@ -71,7 +71,7 @@ def parse_args(argv=None):
                         "pixel AUROC / AP / F1-max and AUPRO, accumulated on the device; writes <result>.seg.json "
                         "(--world > 1: <result>.seg.rankK.npz, to be merged with eval_protocol.merge_seg_shards)")
     parser.add_argument("--draft-k", type=int, default=0, help="K > 1: draft-and-verify greedy decoding with K rows per verify "
-                        "step (batch size 1, no --slots): an n-gram drafter that observes every finished answer guesses K - 1 tokens, "
+                        "step (--bs 1, or --slots N with N * K <= 64 and the switch MYRIAD_SLOT_DRAFT=1): an n-gram drafter that observes every finished answer guesses K - 1 tokens, "
                         "one token step verifies them; the records are those of the run without it")
     parser.add_argument("--draft-corpus", type=str, default=None, help="with --draft-k: teach the drafter up front from a results "
                         ".jsonl of an earlier run (its `output` texts are tokenised) or a JSON list of id lists")
@@ -87,8 +87,14 @@ def parse_args(argv=None):
         parser.error("--draft-corpus needs --draft-k K")
     if args.draft_k and (args.draft_k < 1 or args.draft_k > 8):
         parser.error(f"--draft-k takes 1 to 8 rows, got {args.draft_k}")
-    if args.draft_k and (args.bs != 1 or args.slots > 0 or args.num_beams > 1 or args.llm_score):
-        parser.error("--draft-k decodes one sequence at a time: it needs --bs 1 and takes no --slots, --num-beams or --llm-score")
+    if args.draft_k and (args.num_beams > 1 or args.llm_score):
+        parser.error("--draft-k is greedy decoding: it takes no --num-beams, --beam-sample, --repetition-penalty or --llm-score")
+    if args.draft_k and args.slots <= 0 and args.bs != 1:
+        parser.error("--draft-k without --slots decodes one sequence at a time: it needs --bs 1")
+    if args.draft_k and args.slots > 0 and os.environ.get("MYRIAD_SLOT_DRAFT", "0") == "0":
+        parser.error("--draft-k with --slots: draft decoding in the decode slots needs its switch, MYRIAD_SLOT_DRAFT=1")
+    if args.draft_k and args.slots * args.draft_k > 64:
+        parser.error(f"--slots {args.slots} --draft-k {args.draft_k}: the verify step holds slots x K rows, at most 64")
     if not args.seg_metrics and (args.seg_max_step != 200 or args.seg_expect_fpr != 0.3):
         parser.error("--seg-max-step / --seg-expect-fpr need --seg-metrics")
     if args.seg_max_step < 1:
@@ -300,11 +306,14 @@ def _run_slots(args, model, loader, generate_kwargs, save_path, seg=None):
             yield data_sample
 
     records = []
+    drafter = generate_kwargs.get("draft")
     with torch.no_grad():
         t1 = time.time()
         for out in model.generate_stream(batches(), slots=args.slots, prefill_batch=args.prefill_batch, refill_min=args.refill_min,
                                          **generate_kwargs):
             text = EP.postprocess_generation(out["token_ids"][None], model.llama_tokenizer)[0]
+            if drafter is not None:                      # the run warms itself: every finished answer teaches the drafter
+                drafter.observe(out["token_ids"].tolist())
             amax = None
             if seg is not None:
                 m = out["ve_anomaly_map"]
@@ -329,6 +338,10 @@ def _run_slots(args, model, loader, generate_kwargs, save_path, seg=None):
     if st.get("host_sampled_rows"):
         print(f"note: {st['host_sampled_rows']} generated tokens had p_max < top_p and were drawn, not arg-maxed "
               "(see LlamaHIP.greedy_generate)")
+    if drafter is not None:
+        print(f"draft-and-verify (K = {args.draft_k}): {st.get('emitted', 0) + st.get('prefills', 0)} tokens in "
+              f"{st.get('verify_steps', 0)} verify + {st.get('plain_steps', 0)} plain steps, {st.get('draft_accepted', 0)} of "
+              f"{st.get('draft_proposed', 0)} guesses kept")
     return records
 
 

@@ -585,6 +585,25 @@ int mh_attn_decode_rope_draft(void* qkv, long ld_qkv, void* cache, long cache_bs
  * behind, stale, at pos[g] .. (old pos[g]) + K - 1: the next verify step overwrites them and a plain step's kvlen stops short. */
 int mh_draft_accept(const long* nxt, const float* margin, const float* pmax, long* ids, const float* top_p, float* rec, int* pos,
                     int* kvlen, int* step, int G, int K, mh_stream_t s);
+/* mh_attn_decode_rope_draft for the decode slots: the same kernel with nrow int[G] on the device beside pos and live, 1 <=
+ * nrow[g] <= K, the rows of group g that hold a token (the fed one and its real guesses).  Rows j < nrow[g] of a live group behave
+ * exactly as in mh_attn_decode_rope_draft: the out row, the rotated q and the cache row have its bits.  Rows j >= nrow[g], like
+ * every row of an idle group, read no cache row, leave q and the cache alone and get a zero out row.  The T_cap guard, the LDS rule
+ * and the refusals are mh_attn_decode_rope_draft's; nrow must be non-null and 4-byte aligned (MH_ERR_ARG). */
+int mh_attn_decode_rope_draft_rows(void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
+                                   const int* live, const int* nrow, const float* cos_tab, const float* sin_tab, void* out, long ldo,
+                                   int G, int K, int H, int D, int T_cap, float scale, mh_stream_t s);
+/* mh_draft_accept with per-group state (the decode slots' verify step): group g of K rows has nguess[g] real guesses behind its
+ * fed token ids_k[g*K] (int[G] on the device, 0 .. K - 1; the ids past them are fillers) and a flag live[g].  A live group keeps
+ * n_out = 1 + the number of leading j < nguess[g] with nxt[j] == ids_k[j + 1] and pmax[j] >= *top_p (<= 0: p_max is not looked
+ * at); a filler is never confirmed, even where it equals the pick.  It writes rec[g] = 3K + 1 floats (the K ids, margins and
+ * p_max, then n_out), ids_k[g*K] = next_ids[g] = nxt[n_out - 1] -- next_ids long[G] is the fed-id buffer of the plain one-row-per-
+ * slot step, which can follow with no host copy --, pos[g] += n_out and kvlen[g] = pos[g] + 1.  An idle group records id -1 in
+ * its K id entries, zeros elsewhere and n_out = 0, and changes none of ids_k, next_ids, pos, kvlen.  *step += 1 once per launch.
+ * 1 <= K <= 8, else MH_ERR_ARG with nothing launched. */
+int mh_draft_accept_rows(const long* nxt, const float* margin, const float* pmax, long* ids_k, long* next_ids, const int* nguess,
+                         const int* live, const float* top_p, float* rec, int* pos, int* kvlen, int* step, int G, int K,
+                         mh_stream_t s);
 /* Packed prefill of several decode slots (attn_ragged.hip): causal self-attention over R sequences packed row-wise into qkv
  * [M, ld_qkv] bf16 = [q | k | v] (pre-rotary, only read), with the rotary at pos[row] and the KV-cache write fused in.  seg is the
  * device table int[R][3] of (row0, len, slot) and seg_host the host's copy of it: segment i is rows row0 .. row0 + len - 1, its

@@ -21,6 +21,7 @@ struct DraftParams {
   bf16_t* out;          // [G*K, ldo]
   const int* pos;       // [G] position of row 0 of the group
   const int* live;      // [G] 0 = the sequence is idle
+  const int* nrow;      // [G] rows of the group that hold a token, 1 .. K; null (mh_attn_decode_rope_draft): all K
   const float* cs;
   const float* sn;
   long ld_qkv, cache_bs, ld_cache, ldo;
@@ -34,8 +35,9 @@ __global__ __launch_bounds__(DDW * 64) void attn_decode_draft_kernel(DraftParams
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int D = p.D, W = p.H * D;
   const int p0 = p.pos[g];
-  // uniform over the workgroup, ahead of the first barrier: an idle sequence, or a row whose position would leave the cache
-  if (!p.live[g] || p0 < 0 || p0 > p.T_cap - 1 - jr0) {
+  // uniform over the workgroup, ahead of the first barrier: an idle sequence, a row past the group's count (the decode slots'
+  // form: a slot with fewer than K - 1 guesses), or a row whose position would leave the cache
+  if (!p.live[g] || p0 < 0 || p0 > p.T_cap - 1 - jr0 || (p.nrow && jr0 >= p.nrow[g])) {
     if (wave == 0 && 2 * lane < D) *reinterpret_cast<unsigned*>(p.out + (size_t)row * p.ldo + h * D + 2 * lane) = 0u;
     return;
   }
@@ -196,19 +198,19 @@ static size_t draft_lds_bytes(int T_cap, int K, int D) {
   return (((size_t)T_cap + 63) & ~(size_t)63) * 4 + DDW * 128 * 4 + (size_t)K * D * 2;
 }
 
-// G sequences of K consecutive token rows in one launch: see include/myriad_hip.h.
-extern "C" int mh_attn_decode_rope_draft(void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
-                                         const int* live, const float* cos_tab, const float* sin_tab, void* out, long ldo, int G,
-                                         int K, int H, int D, int T_cap, float scale, hipStream_t stream) {
+// G sequences of K consecutive token rows in one launch: see include/myriad_hip.h.  `nrow` null: every group has K rows.
+static int draft_launch(void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos, const int* live,
+                        const int* nrow, bool rows, const float* cos_tab, const float* sin_tab, void* out, long ldo, int G, int K,
+                        int H, int D, int T_cap, float scale, hipStream_t stream) {
   if (K < 1 || H <= 0 || T_cap <= 0) return MH_ERR_ARG;
   if (D <= 0 || D % 16 || D > 128 || K > DRAFT_MAX_K) return MH_ERR_UNSUPPORTED;
   const size_t sh = draft_lds_bytes(T_cap, K, D);
   if (sh > DRAFT_LDS_LIMIT) return MH_ERR_UNSUPPORTED;
   if (G <= 0) return MH_OK;                        // nothing to do: the answer says whether the shape is supported
-  if (!qkv || !cache || !pos || !live || !cos_tab || !sin_tab || !out) return MH_ERR_ARG;
+  if (!qkv || !cache || !pos || !live || !cos_tab || !sin_tab || !out || (rows && !nrow)) return MH_ERR_ARG;
   if (ld_qkv % 8 || ld_cache % 8 || cache_bstride % 8 || ldo % 4 || ld_qkv < 3L * H * D || ld_cache < 2L * H * D) return MH_ERR_ARG;
   if ((uintptr_t)qkv % 16 || (uintptr_t)cache % 16 || (uintptr_t)cos_tab % 16 || (uintptr_t)sin_tab % 16 || (uintptr_t)out % 8 ||
-      (uintptr_t)pos % 4 || (uintptr_t)live % 4)
+      (uintptr_t)pos % 4 || (uintptr_t)live % 4 || (uintptr_t)nrow % 4)
     return MH_ERR_ARG;
   if ((long)G * K * H > 0x7fffffffL) return MH_ERR_ARG;
   // > 64 KiB of dynamic LDS needs an explicit opt-in; raised only when a launch needs more than any before it
@@ -219,10 +221,26 @@ extern "C" int mh_attn_decode_rope_draft(void* qkv, long ld_qkv, void* cache, lo
     allowed = sh;
   }
   DraftParams p;
-  p.qkv = (bf16_t*)qkv; p.cache = (bf16_t*)cache; p.out = (bf16_t*)out; p.pos = pos; p.live = live; p.cs = cos_tab; p.sn = sin_tab;
+  p.qkv = (bf16_t*)qkv; p.cache = (bf16_t*)cache; p.out = (bf16_t*)out; p.pos = pos; p.live = live; p.nrow = nrow; p.cs = cos_tab; p.sn = sin_tab;
   p.ld_qkv = ld_qkv; p.cache_bs = cache_bstride; p.ld_cache = ld_cache; p.ldo = ldo;
   p.K = K; p.H = H; p.D = D; p.T_cap = T_cap; p.scale = scale;
   hipLaunchKernelGGL(attn_decode_draft_kernel, dim3(G * K * H), dim3(DDW * 64), sh, stream, p);
   MH_CHECK_LAUNCH();
   return MH_OK;
+}
+
+extern "C" int mh_attn_decode_rope_draft(void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
+                                         const int* live, const float* cos_tab, const float* sin_tab, void* out, long ldo, int G,
+                                         int K, int H, int D, int T_cap, float scale, hipStream_t stream) {
+  return draft_launch(qkv, ld_qkv, cache, cache_bstride, ld_cache, pos, live, nullptr, false, cos_tab, sin_tab, out, ldo, G, K, H, D,
+                      T_cap, scale, stream);
+}
+
+// The decode slots' form: group g holds nrow[g] token rows (1 .. K); the rest of its K rows are skipped like an idle group's.
+extern "C" int mh_attn_decode_rope_draft_rows(void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
+                                              const int* live, const int* nrow, const float* cos_tab, const float* sin_tab,
+                                              void* out, long ldo, int G, int K, int H, int D, int T_cap, float scale,
+                                              hipStream_t stream) {
+  return draft_launch(qkv, ld_qkv, cache, cache_bstride, ld_cache, pos, live, nrow, true, cos_tab, sin_tab, out, ldo, G, K, H, D,
+                      T_cap, scale, stream);
 }

@@ -12,8 +12,8 @@ import torch
 
 from . import ops
 from .decode_host import (BeamItem, BeamSlotScheduler, DraftLoop, RefillPlanner, ScorePlan, SessionTable, SlotScheduler, TurnPlanner, _host_draw,
-                          _request_generator, beam_batch_going, beam_sample_select, common_prefix, run_draft_loop, seeded_requests,
-                          split_kv_rows_rule, split_kv_rule)
+                          _request_generator, beam_batch_going, beam_sample_select, common_prefix, run_draft_loop, f32_at_least, seeded_requests,
+                          slot_guesses, split_kv_rows_rule, split_kv_rule)
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -439,7 +439,8 @@ class LlamaDecode:
         form.  Both together: the split-KV kernel in its rows form (ops.attn_decode_rope_split_rows), at 1 to GEMV_WIDE_MAX_ROWS
         rows alike.  Above GEMV_MAX_ROWS rows (_wide_step) the products are ops.gemv_packed_wide and the norm / SiLU products take
         their two-launch forms.  ws["draft_k"] = K (_draft_view, draft decoding's verify step): the rows are K consecutive tokens
-        of one sequence and the attention is ops.attn_decode_rope_draft, row j at position pos + j."""
+        of one sequence and the attention is ops.attn_decode_rope_draft, row j at position pos + j; with ws["nrow"] beside it (the
+        slot engine's verify view) the rows are K per slot and the attention is ops.attn_decode_rope_draft_rows on (pos, live, nrow)."""
         H, hd, scale, cos, sin = self.H, self.hd, 1.0 / math.sqrt(self.hd), self.cos, self.sin
         pos, kvlen, live, split = ws["pos"], ws["kvlen"], ws.get("live"), ws["split"]
         wide = _wide_step(self, ws["x_in"].shape[0], ws["row_limit"])
@@ -448,7 +449,9 @@ class LlamaDecode:
         else:                                                            # one position for all rows: (pos, pos_dev, kvlen)
             attention, state = ops.attn_decode_rope if split is None else ops.attn_decode_rope_split, (pos, pos, kvlen)
         partials = () if split is None else (split,)
-        if ws.get("draft_k"):                                            # K consecutive rows of one sequence: (pos, live), K behind
+        if ws.get("draft_k") and ws.get("nrow") is not None:             # the slots' verify step: K rows per slot, (pos, live, nrow)
+            attention, state, partials = ops.attn_decode_rope_draft_rows, (pos, live, ws["nrow"]), (ws["draft_k"],)
+        elif ws.get("draft_k"):                                          # K consecutive rows of one sequence: (pos, live), K behind
             attention, state, partials = ops.attn_decode_rope_draft, (pos, ws["live1"]), (ws["draft_k"],)
 
         def gemv(x, w, **kw):
@@ -1095,7 +1098,14 @@ class SlotDecoder:
     from its own gen).  One view and one graph per nb, in `beam_views`: no key of `views` changes.  With `LlamaHIP.beam_sampling`
     on as well, `do_sample` / `repetition_penalty` != 1 run beam_generate's sampled step per group -- mh_beam_seen_update_items
     and mh_beam_sample_topk_items, every group with its own seed and Philox step in device memory -- in a view and a graph of
-    its own beside the deterministic one.  See _run_beams."""
+    its own beside the deterministic one.  See _run_beams.
+
+    Draft-and-verify decoding (opt-in, `run(draft=drafter, draft_k=K)` behind `LlamaHIP.slot_draft`, MYRIAD_SLOT_DRAFT=1; slots *
+    K <= GEMV_WIDE_MAX_ROWS): a verify view of the
+    buffers in `draft_views` (_draft_workspace, its own graph) runs the token step at slots * K rows, K consecutive tokens per
+    slot -- mh_attn_decode_rope_draft_rows, mh_argmax_pmax_rows, mh_draft_accept_rows -- whenever a live slot has a guess, and
+    the plain step otherwise; a request's ids and margins are exactly those of the run without `draft`.  No key of `views`
+    changes.  See `run`."""
 
     def __init__(self, llama: "LlamaHIP", slots: int, capacity: int, split_kv: Optional[bool] = False):
         slots = int(slots)
@@ -1111,6 +1121,7 @@ class SlotDecoder:
         self.bufs = None                                             # the step's buffers, shared by every view
         self.views = {}                                              # inv_temp -> workspace view of bufs with its own graph
         self.beam_views = {}                                         # (num_beams, split[, draw]) -> the beam step's view (_beam_workspace)
+        self.draft_views = {}                                        # (draft_k, inv_temp) -> the verify step's view (_draft_workspace)
         self.ws = None                                               # the view of the current / last run
         self._weights = None
         self.graph_captures = 0
@@ -1141,7 +1152,7 @@ class SlotDecoder:
             raise ValueError("the slot engine needs the fused packed token step (MYRIAD_PACK_DECODE and MYRIAD_DECODE_FUSED on)")
         wid = _decode_weights_id(L)
         if self.bufs is None or self._weights != wid:
-            self.bufs, self.views, self.beam_views, self.ws = None, {}, {}, None
+            self.bufs, self.views, self.beam_views, self.draft_views, self.ws = None, {}, {}, {}, None
             # its row limit: above GEMV_MAX_ROWS slots the step stays on the packed copies
             self.bufs = _decode_buffers(L, self.slots, self.T_cap, row_limit=ops.GEMV_WIDE_MAX_ROWS)
             self.bufs["live"] = torch.zeros((self.slots,), dtype=torch.int32, device=L.dev)
@@ -1210,13 +1221,38 @@ class SlotDecoder:
         self.ws = self.views[key]
         return self.ws
 
+    def _draft_workspace(self, K: int, inv_temp: float) -> dict:
+        """The verify step's view of the buffers (run(draft=...)): slots x K rows, K consecutive tokens per slot, with a graph of
+        its own, one per (K, inv_temp) -- the arg-max launch bakes inv_temp in.  It shares the caches, `pos`, `kvlen`, `live`,
+        `step` and the plain step's fed ids (`next_ids`, what mh_draft_accept_rows also writes its kept pick to) with the plain
+        views, so the host switches between the two steps from one launch to the next.  Its own: the fed ids `ids` [slots * K]
+        (per slot the last token, its real guesses, id 0 as filler), `x_in`, `logits`, `nxt` / `mar` / `pmx`, the counts `cnt`
+        [2, slots] = (`nguess`, `nrow`), the [slots, 3K + 1] record `drec` and the device float `top_p`.  No key of `views`
+        changes."""
+        L, bufs = self.llama, self._base_buffers()
+        key = (int(K), float(inv_temp))
+        if key not in self.draft_views:
+            if len(self.draft_views) >= 4:                           # a few (K, temperature) pairs at most: drop the oldest graph
+                self.draft_views.pop(next(iter(self.draft_views)))
+            dev, R = L.dev, self.slots * int(K)
+            cnt = torch.zeros((2, self.slots), dtype=torch.int32, device=dev)
+            view = _buffer_view(L, bufs, False)
+            view.update(draft_k=int(K), next_ids=bufs["ids"], ids=torch.zeros((R,), dtype=torch.long, device=dev),
+                        x_in=torch.empty((R, L.D), dtype=F32, device=dev), logits=torch.empty((R, L.V), dtype=F32, device=dev),
+                        nxt=torch.empty((R,), dtype=torch.long, device=dev), mar=torch.empty((R,), dtype=F32, device=dev),
+                        pmx=torch.empty((R,), dtype=F32, device=dev), cnt=cnt, nguess=cnt[0], nrow=cnt[1],
+                        drec=torch.zeros((self.slots, 3 * int(K) + 1), dtype=F32, device=dev),
+                        top_p=torch.zeros((1,), dtype=F32, device=dev))
+            self.draft_views[key] = view
+        return self.draft_views[key]
+
     @torch.no_grad()
     def run(self, requests, max_new_tokens: int = 90, stop_ids=((835,), (2277, 29937)), eos_id: int = 2, min_length: int = 1,
             do_sample: bool = False, top_p: float = 1.0, temperature: float = 1.0, top_k: int = 50,
             generator: Optional[torch.Generator] = None, ordered: bool = False, prefill_batch: int = 1, refill_min: int = 1,
             prefill_rows: int = 2048, repetition_penalty: float = 1.0, seeds=None, return_scores: bool = False, watch_ids=(),
             num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False, num_return_sequences: int = 1,
-            pad_id: Optional[int] = None):
+            pad_id: Optional[int] = None, draft=None, draft_k: int = 4):
         """Decode every request of `requests` (an iterable of [S0_i, D] f32 embeddings, lengths free) and yield
         (index, ids[L_i] int64 on the CPU, margins[L_i] f32) as each finishes -- or, with `ordered`, in input order.  The
         arguments are greedy_generate's; the stop rule is per request.  `last_stats` holds the run's counters: `prefills` counts
@@ -1242,8 +1278,28 @@ class SlotDecoder:
         alone -- and `last_stats` gains `num_beams`, `groups`, `finished_hypotheses`; `occupancy` counts groups.  With
         `beam_sampling` on as well, `do_sample` (with `temperature`, `top_k` in 1..1024, `top_p`) and `repetition_penalty` != 1 are
         beam_generate's beam sampling and penalty per request: request i draws from the i-th seed of `generator` or `seeds`, what
-        beam_generate draws for it alone with that seed (`beam_sampled_steps`, `beam_host_steps` join `last_stats`)."""
+        beam_generate draws for it alone with that seed (`beam_sampled_steps`, `beam_host_steps` join `last_stats`).
+
+        `draft` (behind `slot_draft`, MYRIAD_SLOT_DRAFT=1, off by default: NotImplementedError without it; a drafter with
+        `propose`, decode_host.NgramDrafter) with `draft_k` = K rows per slot, slots * K <=
+        GEMV_WIDE_MAX_ROWS: draft-and-verify decoding in the slots.  Before every step each live slot gets up to K - 1 guesses
+        (decode_host.slot_guesses: never past the last token the request can still emit); the step is the VERIFY step iff at least
+        one live slot has a real guess, else the plain one-row-per-slot step.  The verify step (_draft_workspace, a graph of its
+        own) is the token step at slots * K rows with mh_attn_decode_rope_draft_rows (slot g's rows at pos[g] .. pos[g] + nrow[g] -
+        1), mh_argmax_pmax_rows and mh_draft_accept_rows, which keeps per slot the guesses the picks confirm plus the one token the
+        last of them produces, feeds that one to both steps and moves pos / kvlen.  Every row has the bits of the plain step at its
+        position, so a request's ids and margins are exactly those of the run without `draft`, whatever the drafter proposes.  Per
+        verify step the host makes two small host->device copies (the fed ids and guesses; the counts) and one device->host copy
+        (the record); a plain step after it needs none.  Under do_sample a row with p_max < top_p ends its window on the device
+        and is drawn on the host from its row of the verify logits.  K = 1 runs plain steps only; so does a call on the split-KV
+        view or with a shape mh_attn_decode_rope_draft refuses, and `last_stats["draft_off"]` says "split_kv" / "unsupported".
+        `last_stats` gains draft_k, draft_off, verify_steps, plain_steps, draft_proposed, draft_accepted, emitted,
+        verify_graph_replays and plain_graph_replays.  The caller teaches the drafter.  NotImplementedError with device sampling,
+        repetition_penalty != 1, min_length > 1, return_scores and num_beams > 1; ValueError for K outside 1 .. DRAFT_MAX_K or
+        slots * K above GEMV_WIDE_MAX_ROWS."""
         self.sessions.clear()                                        # the slots' caches are overwritten from row 0
+        if draft is not None and int(num_beams) != 1:
+            raise NotImplementedError(f"decode slots: draft decoding with num_beams={num_beams} is not implemented")
         if int(num_beams) != 1:
             yield from self._run_beams(requests, int(num_beams), max_new_tokens, stop_ids, eos_id, min_length, ordered, prefill_batch,
                                        refill_min, prefill_rows, length_penalty, early_stopping, num_return_sequences, pad_id,
@@ -1254,7 +1310,7 @@ class SlotDecoder:
             return
         yield from self._run(requests, None, None, max_new_tokens, stop_ids, eos_id, min_length, do_sample, top_p, temperature,
                              top_k, generator, ordered, prefill_batch, refill_min, prefill_rows, repetition_penalty, seeds,
-                             return_scores, watch_ids)
+                             return_scores, watch_ids, draft, draft_k)
 
     def run_turns(self, turns, weights_version=None, **kw):
         """One turn each of several conversations, every one in ITS OWN slot on top of what that slot's cache holds of it
@@ -1274,6 +1330,9 @@ class SlotDecoder:
         turns = [tuple(t) for t in turns]
         if "refill_min" in kw:
             raise ValueError("run_turns: refill_min does not apply, every turn has its own slot")
+        if kw.get("draft") is not None:
+            raise NotImplementedError("run_turns: draft decoding with run_turns / ChatPool is not implemented (it runs in `run`)")
+        kw.pop("draft", None), kw.pop("draft_k", None)
         if int(kw.pop("num_beams", 1) or 1) != 1:
             raise NotImplementedError("run_turns: beam search runs in `run` only (a conversation would have to carry the winning "
                                       "hypothesis's cache rows into its next turn)")
@@ -1512,11 +1571,28 @@ class SlotDecoder:
                          graph_captures=self.graph_captures, prefill_passes=plan.passes, packed_rows=plan.packed_rows,
                          finished_hypotheses=sched.finished_hypotheses)
 
+    def _draft_args(self, draft_k, dev_sample: bool, penalty: bool, min_length: int, scores: bool, turns) -> int:
+        """run(draft=...)'s checks of its arguments; returns K."""
+        if not getattr(self.llama, "slot_draft", False):
+            raise NotImplementedError("decode slots: draft decoding needs its switch (MYRIAD_SLOT_DRAFT=1 or llama.slot_draft = True)")
+        K = int(draft_k)
+        if not 1 <= K <= ops.DRAFT_MAX_K:
+            raise ValueError(f"draft_k={draft_k}: 1 to {ops.DRAFT_MAX_K} rows per slot in a verify step")
+        if self.slots * K > ops.GEMV_WIDE_MAX_ROWS:
+            raise ValueError(f"slots={self.slots} x draft_k={K}: the verify step runs the packed token step, at most "
+                             f"{ops.GEMV_WIDE_MAX_ROWS} rows")
+        for on, what in ((dev_sample, "device sampling"), (penalty, "repetition_penalty != 1"), (int(min_length) > 1, "min_length > 1"),
+                         (scores, "return_scores"), (turns is not None, "run_turns / ChatPool")):
+            if on:
+                raise NotImplementedError(f"decode slots: draft decoding with {what} is not implemented")
+        return K
+
     @torch.no_grad()
     def _run(self, requests, turns, weights_version, max_new_tokens: int = 90, stop_ids=((835,), (2277, 29937)), eos_id: int = 2,
              min_length: int = 1, do_sample: bool = False, top_p: float = 1.0, temperature: float = 1.0, top_k: int = 50,
              generator: Optional[torch.Generator] = None, ordered: bool = False, prefill_batch: int = 1, refill_min: int = 1,
-             prefill_rows: int = 2048, repetition_penalty: float = 1.0, seeds=None, return_scores: bool = False, watch_ids=()):
+             prefill_rows: int = 2048, repetition_penalty: float = 1.0, seeds=None, return_scores: bool = False, watch_ids=(),
+             draft=None, draft_k: int = 4):
         """`run` (requests) and `run_turns` (turns + weights_version): one engine, two admission rules."""
         L = self.llama
         scores = bool(return_scores)
@@ -1528,6 +1604,7 @@ class SlotDecoder:
         if seeds is not None and not dev_sample:
             raise ValueError("seeds= names the device sampler's per-request streams: it needs do_sample with device_sampling on")
         rows_tail = dev_sample or penalty or min_length > 1          # else exactly the launches of the plain slot step
+        K = 0 if draft is None else self._draft_args(draft_k, dev_sample, penalty, min_length, scores, turns)
         # the attention kernel of every token step of this call, chosen once: `run` does not know its lengths up front
         split = self.split_kv
         if split is None:
@@ -1557,6 +1634,17 @@ class SlotDecoder:
                        rows_tail=rows_tail, generator=generator, scores=scores, W=int((watch >= 0).sum()))
         if scores:
             ws["watch"].copy_(watch)
+        dv = None
+        if K:                                                        # draft decoding: the verify view, unless the call cannot use it
+            stats.update(draft_k=K, draft_off="split_kv" if split else None, verify_steps=0, plain_steps=0, draft_proposed=0,
+                         draft_accepted=0, emitted=0, verify_graph_replays=0, plain_graph_replays=0)
+            if not split and not ops.attn_decode_draft_supported(L.H, L.hd, K, self.T_cap):
+                stats["draft_off"] = "unsupported"
+            if K > 1 and stats["draft_off"] is None:
+                dv = run.dv = self._draft_workspace(K, inv_temp)
+                # the host draws where p_max (f32) < top_p (a double): the device holds the smallest f32 >= top_p, so its
+                # p_max >= *top_p is that test's negation for every f32 p_max; <= 0: no row needs a draw
+                dv["top_p"].copy_(torch.from_numpy(np.array([f32_at_least(top_p) if do_sample else 0.0], dtype=np.float32)))
         ws["live"].zero_()                                           # an abandoned run may have left slots live
         ws["step"].zero_()
         if rows_tail:
@@ -1572,8 +1660,17 @@ class SlotDecoder:
                 live = sched.live()
                 if not live:
                     break
+                guesses = slot_guesses(sched, draft, K) if dv is not None else None
+                if guesses is not None and any(guesses.values()):    # THE RULE: a verify step iff a live slot has a real guess
+                    run.verify_step(live, guesses)
+                    yield from run.results()
+                    continue
+                replays = stats["graph_replays"]
                 if L._launch_step(ws, run.token_step, -1, True, stats):
                     self.graph_captures += 1
+                if K:
+                    stats["plain_steps"] += 1
+                    stats["plain_graph_replays"] += stats["graph_replays"] - replays
                 r = run.rec.cpu()                                    # the one device->host copy of the step (it also waits for it)
                 ids = run.host_draws(live, r)
                 run.note_scores(live, r, ids)
@@ -1587,6 +1684,8 @@ class SlotDecoder:
         finally:
             stats.update(steps=sched.steps, live_row_steps=sched.live_row_steps, occupancy=sched.occupancy,
                          graph_captures=self.graph_captures, prefill_passes=plan.passes, packed_rows=plan.packed_rows)
+            if K:
+                stats["emitted"] = sched.emitted
 
 
 class _SlotRun:
@@ -1624,6 +1723,61 @@ class _SlotRun:
             ops.token_scores_rows(ws["logits"], ws["nxt"], ws["watch"], rec[4:], ws["live"])
         ops.decode_advance_kept_rows(ws["nxt"], ws["mar"], ws["pmx"], ws["kept"] if self.dev_sample else None, rec, ws["ids"],
                                      ws["step"], ws["pos"], ws["kvlen"], ws["gen"], ws["live"])
+
+    def verify_token_step(self, _ban):
+        """The verify step of draft decoding (SlotDecoder._draft_workspace): slots x K rows, K consecutive tokens per slot."""
+        dv = self.dv
+        self.L._step_logits(dv)
+        ops.argmax_pmax_rows(dv["logits"], dv["nxt"], dv["mar"], dv["pmx"], ban_id=-1, inv_temp=self.inv_temp)
+        ops.draft_accept_rows(dv["nxt"], dv["mar"], dv["pmx"], dv["ids"], dv["next_ids"], dv["nguess"], dv["live"], dv["top_p"],
+                              dv["drec"], dv["pos"], dv["kvlen"], dv["step"], dv["draft_k"])
+
+    def verify_step(self, live, guesses) -> list:
+        """One verify step for the `live` slots with their real `guesses`: two host->device copies (per slot the fed token, its
+        guesses and id 0 as filler; the counts), the launch, one device->host copy (the record).  A slot's window is the n_out
+        picks the device kept; under do_sample a pick with p_max < top_p (it ends the window on the device) is drawn here from
+        its row of the verify logits and handed to the plain step's fed ids as well.  Returns the slots that finished."""
+        dv, ws, sched, stats = self.dv, self.ws, self.sched, self.stats
+        K, S = dv["draft_k"], self.dec.slots
+        ids_k, cnt = [0] * (S * K), [[0] * S, [1] * S]
+        for s in live:
+            g = guesses[s]
+            ids_k[s * K:s * K + 1 + len(g)] = [sched.rows[s][1][-1]] + g
+            cnt[0][s], cnt[1][s] = len(g), 1 + len(g)
+        dv["ids"].copy_(torch.tensor(ids_k, dtype=torch.long))
+        dv["cnt"].copy_(torch.tensor(cnt, dtype=torch.int32))
+        replays = stats["graph_replays"]
+        if self.L._launch_step(dv, self.verify_token_step, -1, True, stats):
+            self.dec.graph_captures += 1
+        stats["verify_steps"] += 1
+        stats["verify_graph_replays"] += stats["graph_replays"] - replays
+        stats["draft_proposed"] += sum(len(guesses[s]) for s in live)
+        r = dv["drec"].cpu().tolist()                                # the one device->host copy of the step (it also waits for it)
+        windows, drawn = {}, {}
+        for s in live:
+            n = int(r[s][3 * K])
+            if not 1 <= n <= cnt[1][s]:
+                raise RuntimeError(f"verify step: slot {s} kept {n} of {cnt[1][s]} rows")
+            hist, ids = list(sched.rows[s][1]), []
+            for j in range(n):                                       # token by token, so no draw is made past the request's end
+                tok = int(r[s][j])
+                if self.do_sample and r[s][2 * K + j] < self.top_p:  # greedy_generate's rule per row: below top_p the host draws
+                    if j != n - 1:
+                        raise RuntimeError("a row that needs a host draw must end its window")
+                    tok = drawn[s] = self.host_draw(dv["logits"][s * K + j], len(hist), None)
+                ids.append(tok)
+                hist.append(tok)
+                if sched._ended(hist):
+                    break
+            windows[s] = (ids, r[s][K:K + len(ids)])
+        finished = sched.step_windows(windows)
+        stats["draft_accepted"] += sum(sched.taken[s] - 1 for s in live)
+        for s in live:
+            if s in finished:
+                ws["live"][s:s + 1].zero_()
+            elif s in drawn:
+                ws["ids"][s:s + 1].fill_(drawn[s])                   # a host draw replaces the pick the step fed back
+        return finished
 
     def results(self):
         for index, ids, mar in self.sched.pop():

@@ -5,7 +5,8 @@ chat pool's session table (SessionTable), the per-request random streams (seeded
 step of one item (beam_sample_select), and beam search's host rule: one request's search state (BeamItem), when a batch of them
 goes on (beam_batch_going) and the slots' scheduler of the groups of num_beams rows (BeamSlotScheduler); draft-and-verify decoding's
 drafter (NgramDrafter), the host side of its loop (DraftLoop, run_draft_loop) and the predictor of a run's step counts
-(predict_draft_run)."""
+(predict_draft_run), and in the decode slots the windows a verify step gives each slot (SlotScheduler.step_windows), the guesses of
+the next step with the plain / verify rule (slot_guesses) and the predictor (replay_slot_run(draft=, draft_k=))."""
 from __future__ import annotations
 
 from typing import Optional
@@ -158,6 +159,8 @@ class SlotScheduler:
         self.admitted = 0
         self._done, self._next_out = {}, 0
         self.steps = self.live_row_steps = 0
+        self.emitted = 0                                             # tokens the steps appended (the prefill picks not counted)
+        self.taken = {}                                              # slot -> tokens the last step appended to it
 
     def free(self) -> list:
         return [s for s in range(self.slots) if self.rows[s] is None]
@@ -189,6 +192,8 @@ class SlotScheduler:
         live = self.live()
         self.steps += 1
         self.live_row_steps += len(live)
+        self.emitted += len(live)
+        self.taken = {s: 1 for s in live}
         finished = []
         for s in live:
             row = self.rows[s]
@@ -198,6 +203,35 @@ class SlotScheduler:
                 self._finish(row)
                 self.rows[s] = None
                 finished.append(s)
+        return finished
+
+    def step_windows(self, windows) -> list:
+        """One token step that gave every live slot a window of tokens (a verify step of draft decoding): `windows` = {slot: (ids,
+        margins)}, at least one token per live slot.  A slot's tokens are appended one at a time and the window is cut where its
+        request ends -- EOS, a stop sequence ending inside the window, max_new_tokens: the tokens past the cut are dropped and the
+        slot finishes.  Counts one step and one live_row_step per live slot, like `step`; `emitted` counts the tokens kept and
+        `taken[slot]` how many this step appended.  Returns the slots that finished."""
+        live = self.live()
+        for s in live:
+            if s not in windows or len(windows[s][0]) < 1 or len(windows[s][0]) != len(windows[s][1]):
+                raise ValueError(f"slot {s} is live: it needs a window of at least one (id, margin)")
+        self.steps += 1
+        self.live_row_steps += len(live)
+        self.taken = {}
+        finished = []
+        for s in live:
+            row, n = self.rows[s], 0
+            for tok, mar in zip(*windows[s]):
+                row[1].append(int(tok))
+                row[2].append(float(mar))
+                n += 1
+                if self._ended(row[1]):
+                    self._finish(row)
+                    self.rows[s] = None
+                    finished.append(s)
+                    break
+            self.taken[s] = n
+            self.emitted += n
         return finished
 
     def pop(self) -> list:
@@ -653,10 +687,38 @@ def _request_generator(seed: int, t: int) -> torch.Generator:
     return g
 
 
+def f32_at_least(x: float):
+    """The smallest float32 >= x (a numpy float32).  For every float32 p: p < x (x a double) iff p < f32_at_least(x), so a device
+    that tests p >= this value decides exactly what the host decides with p < x."""
+    t = np.float32(x)
+    return t if float(t) >= float(x) else np.nextafter(t, np.float32(np.inf))
+
+
+def slot_guesses(sched: "SlotScheduler", drafter, k: int) -> dict:
+    """The guesses of the next step of a slot run with draft decoding, {live slot: real guesses}: drafter.propose(the slot's ids
+    so far, k - 1), clamped to max_new_tokens - len(ids) - 1 guesses, so that no row is fed past the last token the request can
+    still emit (a window of 1 + n guesses emits at most 1 + n tokens) and pos + rows never leaves the slot's capacity.  [] where
+    the drafter has nothing.  THE RULE: the step is the verify step (slots x k rows) iff at least one live slot has a real guess,
+    otherwise the engine's plain one-row-per-slot step."""
+    out = {}
+    for s in sched.live():
+        ids = sched.rows[s][1]
+        room = min(int(k) - 1, sched.max_new_tokens - len(ids) - 1)
+        out[s] = [int(t) for t in drafter.propose(list(ids), room)][:room] if room > 0 else []
+    return out
+
+
 def replay_slot_run(lengths, ids, slots: int, max_new_tokens: int, stop_ids=(), eos_id: int = 2, prefill_batch: int = 1,
-                    prefill_rows: int = 2048, refill_min: int = 1) -> dict:
+                    prefill_rows: int = 2048, refill_min: int = 1, draft=None, draft_k: int = 4) -> dict:
     """The counters of a slot run whose picks are known: request i has a prompt of lengths[i] rows and generates ids[i] (which must
-    end where the stop rule ends it).  SlotScheduler + RefillPlanner driven as SlotDecoder.run drives them, without a device."""
+    end where the stop rule ends it).  SlotScheduler + RefillPlanner driven as SlotDecoder.run drives them, without a device.
+    With `draft` (a drafter nobody teaches during the run) and `draft_k` = K the run is SlotDecoder.run(draft=, draft_k=)'s with no
+    host draw: every step takes slot_guesses' guesses and is a verify step iff a live slot has one, a slot's window is its fed
+    token's pick plus the leading guesses its known answer confirms, and the answer gains verify_steps, plain_steps, draft_proposed
+    (real guesses fed), draft_accepted (emitted tokens that were confirmed guesses) and emitted."""
+    if draft is not None:
+        return _replay_draft_slot_run(lengths, ids, slots, max_new_tokens, stop_ids, eos_id, prefill_batch, prefill_rows, refill_min,
+                                      draft, int(draft_k))
     sched = SlotScheduler(slots, max_new_tokens, stop_ids, eos_id)
     plan = RefillPlanner(sched, range(len(lengths)), prefill_batch, prefill_rows, refill_min, length=lambda i: lengths[i])
     owner, prefills = [None] * slots, 0
@@ -678,6 +740,42 @@ def replay_slot_run(lengths, ids, slots: int, max_new_tokens: int, stop_ids=(), 
         sched.step(picks, [0.0] * slots)
     return dict(prefills=prefills, prefill_passes=plan.passes, packed_rows=plan.packed_rows, steps=sched.steps,
                 live_row_steps=sched.live_row_steps, occupancy=sched.occupancy)
+
+
+def _replay_draft_slot_run(lengths, ids, slots, max_new_tokens, stop_ids, eos_id, prefill_batch, prefill_rows, refill_min, draft,
+                           K: int) -> dict:
+    """replay_slot_run with a drafter: see there."""
+    sched = SlotScheduler(slots, max_new_tokens, stop_ids, eos_id)
+    plan = RefillPlanner(sched, range(len(lengths)), prefill_batch, prefill_rows, refill_min, length=lambda i: lengths[i])
+    owner, prefills = [None] * slots, 0                              # per slot: its request
+    st = dict(verify_steps=0, plain_steps=0, draft_proposed=0, draft_accepted=0)
+    while True:
+        group = plan.next_pass()
+        while group:
+            for s, i in group:
+                prefills += 1
+                if sched.admit(s, ids[i][0], 0.0):
+                    owner[s] = i
+            group = plan.next_pass()
+        live = sched.live()
+        if not live:
+            break
+        guesses = slot_guesses(sched, draft, K) if K > 1 else {s: [] for s in live}
+        verify = any(guesses[s] for s in live)
+        windows = {}
+        for s in live:
+            chain, n = ids[owner[s]], len(sched.rows[s][1])          # row j's pick is chain[n + j] while every earlier guess was right
+            take = 1
+            while take <= len(guesses[s]) and n + take < len(chain) and guesses[s][take - 1] == chain[n + take - 1]:
+                take += 1
+            windows[s] = (chain[n:n + take], [0.0] * take)
+        sched.step_windows(windows)
+        st["verify_steps" if verify else "plain_steps"] += 1
+        if verify:
+            st["draft_proposed"] += sum(len(guesses[s]) for s in live)
+            st["draft_accepted"] += sum(sched.taken[s] - 1 for s in live)
+    return dict(prefills=prefills, prefill_passes=plan.passes, packed_rows=plan.packed_rows, steps=sched.steps,
+                live_row_steps=sched.live_row_steps, occupancy=sched.occupancy, emitted=sched.emitted, **st)
 
 
 # ---- draft-and-verify greedy decoding (LlamaDecode.greedy_generate(draft=...)): the drafter, the predictor of a run's step counts

@@ -119,6 +119,9 @@ class LlamaHIP(LlamaDecode):
         # beam search in the decode slots, one request per group of num_beams rows (SlotDecoder.run(num_beams > 1)); off by default.
         # With beam_sampling on as well the groups take do_sample and the penalty (mh_beam_sample_topk_items)
         self.slot_beams = os.environ.get("MYRIAD_SLOT_BEAMS", "0") != "0"
+        # draft-and-verify decoding in the decode slots (SlotDecoder.run(draft=...), generate_stream(draft=...), eval_aqa.py --slots
+        # N --draft-k K); off by default: those entries refuse `draft` as before
+        self.slot_draft = os.environ.get("MYRIAD_SLOT_DRAFT", "0") != "0"
         self.last_layer_rows = os.environ.get("MYRIAD_LAST_LAYER_ROWS", "1") != "0"
         # the packed token step streams FP8 (e4m3fn, one fp32 scale per output row) copies of the decoder matrices instead of
         # the bf16 ones (ops.gemv_pack_fp8; half the bytes, weight rounding the only new error); off by default, the attribute

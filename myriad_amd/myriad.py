@@ -1565,11 +1565,19 @@ class MyriadHIP(nn.Module):
         graph_captures, live_row_steps, occupancy, prefill_passes, packed_rows, host_sampled_rows, device_sampled_rows) once the
         stream is exhausted.  `prefill_batch` = P > 1 prefills up to P waiting samples in one packed pass whenever slots are free
         and `refill_min` = k holds a refill back until k slots are free (SlotDecoder.run); both default to 1, the one-sample refill.
-        output_scores / watch_ids as in generate(): each yielded dict gains "token_logprobs" [L] and "watch_logprobs" [L, W]."""
+        output_scores / watch_ids as in generate(): each yielded dict gains "token_logprobs" [L] and "watch_logprobs" [L, W].
+        draft=<drafter>, draft_k=K (generate()'s; slots * K <= 64; refused with NotImplementedError unless `self.llama.slot_draft`,
+        MYRIAD_SLOT_DRAFT=1, off by default, is on): draft-and-verify decoding in the slots
+        (SlotDecoder.run): the same token_ids as the call without them, in fewer passes over the decoder weights when the drafter
+        guesses well.  `last_generate_stats` then also holds draft_k, draft_off, verify_steps, plain_steps, draft_proposed,
+        draft_accepted, emitted, verify_graph_replays and plain_graph_replays.  Refused (NotImplementedError) with beams, device
+        sampling, repetition_penalty != 1, min_length > 1 and output_scores.  The caller teaches the drafter."""
         self.finish_update()
         a = self._generate_args(generate_kwargs)
-        if a["draft"] is not None:
-            raise NotImplementedError("generate_stream(draft=...): draft decoding runs one sequence per call (generate)")
+        if a["draft"] is not None and not getattr(self.llama, "slot_draft", False):
+            raise NotImplementedError("generate_stream(draft=...): draft decoding in the decode slots needs its switch "
+                                      "(MYRIAD_SLOT_DRAFT=1 or model.llama.slot_draft = True)")
+        draft_kw = {} if a["draft"] is None else dict(draft=a["draft"], draft_k=a["draft_k"])      # without: today's arguments
         nb, beam_kw = a["num_beams"], {}
         if nb > 1:
             if not getattr(self.llama, "slot_beams", False):
@@ -1640,7 +1648,7 @@ class MyriadHIP(nn.Module):
                                               min_length=a["min_length"], do_sample=a["do_sample"], top_p=a["top_p"],
                                               temperature=a["temperature"], top_k=a["top_k"], generator=a["generator"], ordered=True,
                                               prefill_batch=prefill_batch, refill_min=refill_min, repetition_penalty=a["rep_pen"],
-                                              seeds=seeds, return_scores=a["output_scores"], watch_ids=a["watch_ids"]):
+                                              seeds=seeds, return_scores=a["output_scores"], watch_ids=a["watch_ids"], **draft_kw):
                 self.last_generate_stats = dec.last_stats
                 yield {"index": index, "token_ids": ids, "ve_anomaly_map": side[index], **(sc[0] if sc else {})}
                 side[index] = None

@@ -467,6 +467,55 @@ def draft_accept(nxt, margin, pmax, ids, top_p: torch.Tensor, rec, pos, kvlen, s
                                     _s()), "mh_draft_accept")
 
 
+def attn_decode_rope_draft_rows(qkv2d: torch.Tensor, cache: torch.Tensor, pos: torch.Tensor, live: torch.Tensor, nrow: torch.Tensor,
+                                cos_tab: torch.Tensor, sin_tab: torch.Tensor, n_heads: int, head_dim: int, scale: float, K: int,
+                                out: Optional[torch.Tensor] = None):
+    """attn_decode_rope_draft for the decode slots: group g holds nrow[g] token rows (int32 [G] on the device, 1 .. K).  Rows
+    below nrow[g] of a live group have attn_decode_rope_draft's bits; the others, and every row of an idle group, touch neither q
+    nor the cache and get a zero out row.  Returns o [G*K, W] bf16."""
+    _chk2d(qkv2d, BF16, "attn_decode_rope_draft_rows.qkv")
+    R, W, K = qkv2d.shape[0], n_heads * head_dim, int(K)
+    G = cache.shape[0]
+    if K < 1 or R != G * K or qkv2d.shape[1] < 3 * W or cache.shape[2] != 2 * W:
+        raise _lib.MyriadHipError("attn_decode_rope_draft_rows: qkv must be [G*K, >=3W] and cache [G, T, 2W]")
+    for name, t in (("pos", pos), ("live", live), ("nrow", nrow)):
+        if t.dtype != torch.int32 or t.numel() != G or not t.is_contiguous():
+            raise _lib.MyriadHipError(f"attn_decode_rope_draft_rows: {name} must be a contiguous int32 [G]")
+    if out is None:
+        out = torch.empty((R, W), dtype=BF16, device=qkv2d.device)
+    elif out.dtype != BF16 or out.shape != (R, W) or out.stride(1) != 1:
+        raise _lib.MyriadHipError("attn_decode_rope_draft_rows: out must be bf16 [G*K, W]")
+    _lib.check(_L().mh_attn_decode_rope_draft_rows(_p(qkv2d), qkv2d.stride(0), _p(cache), cache.stride(0), cache.stride(1), _p(pos),
+                                                   _p(live), _p(nrow), _p(cos_tab), _p(sin_tab), _p(out), out.stride(0), G, K,
+                                                   n_heads, head_dim, cache.shape[1], float(scale), _s()),
+               "mh_attn_decode_rope_draft_rows")
+    return out
+
+
+def draft_accept_rows(nxt, margin, pmax, ids_k, next_ids, nguess, live, top_p: torch.Tensor, rec, pos, kvlen, step_dev, K: int):
+    """draft_accept per decode slot: group g has nguess[g] real guesses (int32 [G] on the device, 0 .. K - 1) and a flag live[g].
+    A live group's rec[g] = (K ids, K margins, K p_max, n_out), ids_k[g*K] = next_ids[g] = the last kept pick, pos[g] += n_out,
+    kvlen[g] = pos[g] + 1; an idle group records ids -1, zeros and n_out = 0 and keeps its state.  step += 1."""
+    K = int(K)
+    G = nxt.numel() // max(K, 1)
+    if K >= 1 and (nxt.numel() != G * K or margin.numel() != G * K or pmax.numel() != G * K or ids_k.numel() < G * K
+                   or next_ids.numel() < G or rec.numel() < G * (3 * K + 1) or pos.numel() < G or kvlen.numel() < G):
+        raise _lib.MyriadHipError("draft_accept_rows: nxt / margin / pmax / ids_k hold G*K rows, rec G*(3K+1) floats, next_ids / "
+                                  "pos / kvlen G entries")
+    for name, t in (("nguess", nguess), ("live", live)):
+        if t.dtype != torch.int32 or t.numel() < G or not t.is_contiguous():
+            raise _lib.MyriadHipError(f"draft_accept_rows: {name} must be a contiguous int32 [G]")
+    if nxt.dtype != torch.long or ids_k.dtype != torch.long or next_ids.dtype != torch.long:
+        raise _lib.MyriadHipError("draft_accept_rows: nxt, ids_k and next_ids are int64")
+    for name, t, dt in (("margin", margin, F32), ("pmax", pmax, F32), ("rec", rec, F32), ("top_p", top_p, F32), ("pos", pos, torch.int32),
+                        ("kvlen", kvlen, torch.int32), ("step", step_dev, torch.int32), ("nxt", nxt, torch.long), ("ids_k", ids_k, torch.long),
+                        ("next_ids", next_ids, torch.long)):
+        if t.dtype != dt or not t.is_contiguous() or t.numel() < 1:
+            raise _lib.MyriadHipError(f"draft_accept_rows: {name} must be a contiguous {dt} tensor")
+    _lib.check(_L().mh_draft_accept_rows(_p(nxt), _p(margin), _p(pmax), _p(ids_k), _p(next_ids), _p(nguess), _p(live), _p(top_p),
+                                         _p(rec), _p(pos), _p(kvlen), _p(step_dev), G, K, _s()), "mh_draft_accept_rows")
+
+
 def _attn_prefill_ragged(sw: int, qkv2d, pos, seg, seg_host, cache, cos_tab, sin_tab, n_heads, head_dim, scale, out,
                          shared: bool = False):
     """attn_prefill_ragged (sw = 3 ints per segment), attn_prefill_ragged_past (sw = 4) and attn_prefill_ragged_shared (sw = 4,

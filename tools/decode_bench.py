@@ -50,7 +50,14 @@ vocabulary.  min / median / max of both sides.
 K beside the captured plain one-row step, replayed interleaved from --step-keys keys (--step-replays replays per round, median
 of --repeats rounds; every guess is wrong, so each replay moves the position by one), with the kept-guess rate at which each K
 breaks even; then greedy_generate end to end on a prompt of --step-keys rows and a countdown chain of --new tokens with a drafter
-taught the chain, one whose guesses hold in every other window, and none -- the answer is asserted to be the chain each time."""
+taught the chain, one whose guesses hold in every other window, and none -- the answer is asserted to be the chain each time.
+
+--slots S[,S..] --draft-k K[,K..] [--weights ..] measures draft decoding in the decode slots for every (S, K) with S * K <= 64,
+interleaved in one process, medians of --repeats rounds: the captured verify step at S * K rows against the plain step at S and at
+S * K slots (--step-keys keys, --step-replays replays per round) with the share of guesses kept at which it breaks even,
+(t_verify / t_plain - 1) / (K - 1); the draft-rows attention launch alone against mh_attn_decode_rope_rows at 256 and 1,024 keys;
+and samples/s on the --requests ragged countdown requests with no drafter and with one taught the chain, one right every other
+time, and an untaught one -- every answer length is asserted."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -113,6 +120,178 @@ def make_samples(n):
                 before_ids=torch.randint(3, 32000, (1, 4), generator=g).expand(n, -1).contiguous(),
                 after_ids=torch.randint(3, 32000, (1, 28), generator=g).expand(n, -1).contiguous())
 
+
+if a.draft_k and slot_counts not in ([], [0]):
+    # Draft decoding in the decode slots, --slots S[,S..] --draft-k K[,K..], every (S, K) with S * K <= 64, everything interleaved in
+    # this one process: (1) the captured verify step at S * K rows against the plain step at S and at S * K slots -- assembled from
+    # the engine's own pieces (SlotDecoder._workspace / _draft_workspace, LlamaHIP._step_logits and the three-line tails of
+    # _SlotRun.token_step / verify_token_step: copies, change them together); every guess is a random id that is never confirmed, so
+    # pos moves by one per replay in all three; (2) the draft-rows attention launch alone against mh_attn_decode_rope_rows at 256
+    # and 1,024 keys; (3) samples/s on the ragged countdown requests of the --slots run with the drafter taught, half right, untaught.
+    from myriad_amd import ops
+    from myriad_amd.decode_host import NgramDrafter
+    L, D, new = model.llama, model.llama.D, a.new
+    L.slot_draft = True                                              # the engine's switch (MYRIAD_SLOT_DRAFT), off by default
+    Ks = [int(x) for x in a.draft_k.split(",") if x]
+    pairs = [(S, K) for S in slot_counts for K in Ks if K > 1 and S * K <= ops.GEMV_WIDE_MAX_ROWS]
+    rounds, n_rep = max(1, a.repeats) + 1, a.step_replays           # round 0 is the warm-up of the graphs themselves
+    T_cap = 64 * ((max(a.step_keys, 160) + max(rounds * n_rep, new) + 16 + 63) // 64)
+    gi, gq = torch.Generator().manual_seed(3), torch.Generator().manual_seed(11)
+    lens = [int(x) for x in torch.randint(24, 161, (a.requests,), generator=gq)]
+    due = [int(x) for x in torch.randint(8, new + 1, (a.requests,), generator=gq)]
+    dirs = torch.nn.functional.normalize(torch.randn(new + 1, D, generator=gq), dim=1)      # the countdown chain of the --slots run
+    emb_rows = dirs * (D ** 0.5) * 2.0
+    L.embed[1000:1001 + new].copy_(emb_rows.to(L.embed.dtype).to(dev))
+    head = L.lm_head[1000:1001 + new].float().cpu()
+    head[:new] += 2.5 * dirs[1:]
+    L.lm_head[1000:1001 + new].copy_(head.to(L.lm_head.dtype).to(dev))
+    reqs = []
+    for n, d in zip(lens, due):
+        x = torch.randn(n, D, generator=gq) * 0.02
+        x[-1] = emb_rows[d]
+        reqs.append(x.to(dev))
+    chain = list(range(1000 + new - 1, 999, -1))
+    kw = dict(max_new_tokens=new, stop_ids=((1000,),), eos_id=-5, min_length=0)
+    wkinds = kinds if kinds != [None] else ["bf16"]
+
+    class Half:
+        """Every other call's guesses are the chain's, the others are wrong: about half of the guesses are confirmed."""
+        def __init__(self):
+            self.good, self.n = NgramDrafter([chain]), 0
+
+        def propose(self, history, k):
+            self.n += 1
+            return self.good.propose(history, k) if self.n % 2 else [7] * k
+
+    def set_kind(kind):
+        L.decode_fp8, L.decode_fp4 = kind == "fp8", kind == "fp4"
+
+    def capture(step):
+        step()                                                       # eager once: kernels loaded, attributes set
+        torch.cuda.synchronize()
+        g_ = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g_):
+            step()
+        return g_
+
+    decs, steps = {}, []                                             # (kind, S, K or 0, rows, graph, reset)
+    for kind in wkinds:
+        set_kind(kind)
+        for S in dict.fromkeys([S for S, _ in pairs] + [S * K for S, K in pairs]):
+            dec = decs[kind, S] = L.slot_decoder(S, T_cap)
+            ws = dec._workspace(1.0)
+            for c in ws["caches"]:
+                c[:, :a.step_keys].normal_(0.0, 0.5)
+
+            def reset(ws=ws, S=S):
+                ws["ids"].copy_(torch.randint(3, 32000, (S,), generator=gi))
+                ws["live"].fill_(1)
+                ws["pos"].fill_(a.step_keys)
+                ws["kvlen"].fill_(a.step_keys + 1)
+
+            def plain(ws=ws):
+                L._step_logits(ws)
+                ops.argmax_pmax_rows(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ban_id=-1, inv_temp=1.0)
+                ops.decode_advance_rows(ws["nxt"], ws["mar"], ws["pmx"], ws["rec"][:3], ws["ids"], ws["step"], ws["pos"], ws["kvlen"],
+                                        ws["live"])
+            reset()
+            steps.append((kind, S, 0, S, capture(plain), reset))
+            for K in [K for S_, K in pairs if S_ == S]:
+                dv = dec._draft_workspace(K, 1.0)
+
+                def vreset(dv=dv, reset=reset, K=K):
+                    reset()
+                    dv["ids"].copy_(torch.randint(3, 32000, (dv["ids"].shape[0],), generator=gi))
+                    dv["nguess"].fill_(K - 1)
+                    dv["nrow"].fill_(K)
+
+                def verify(dv=dv, K=K):
+                    L._step_logits(dv)
+                    ops.argmax_pmax_rows(dv["logits"], dv["nxt"], dv["mar"], dv["pmx"], ban_id=-1, inv_temp=1.0)
+                    ops.draft_accept_rows(dv["nxt"], dv["mar"], dv["pmx"], dv["ids"], dv["next_ids"], dv["nguess"], dv["live"], dv["top_p"],
+                                          dv["drec"], dv["pos"], dv["kvlen"], dv["step"], K)
+                vreset()
+                steps.append((kind, S, K, S * K, capture(verify), vreset))
+    # the attention launches alone: one graph of 16 launches each (q is rotated in place again and again: the time does not care)
+    attn, keep, W, scale = [], [], L.H * L.hd, 1.0 / L.hd ** 0.5
+    i32 = lambda v, n: torch.full((n,), v, dtype=torch.int32, device=dev)
+    for keys in (256, 1024):
+        for S, K in pairs:
+            R, T = S * K, keys + 64
+            qkv = (torch.randn(R, 3 * W, device=dev) * 0.5).to(torch.bfloat16)
+            cache_s = (torch.randn(S, T, 2 * W, device=dev) * 0.5).to(torch.bfloat16)
+            cache_r = cache_s.repeat(K, 1, 1)
+            pos_s, pos_r, kv_r, one_s, one_r, nrow = i32(keys, S), i32(keys, R), i32(keys + 1, R), i32(1, S), i32(1, R), i32(K, S)
+            out = torch.empty((R, W), dtype=torch.bfloat16, device=dev)
+
+            def draft_rows(qkv=qkv, c=cache_s, p=pos_s, lv=one_s, nr=nrow, K=K, out=out):
+                for _ in range(16):
+                    ops.attn_decode_rope_draft_rows(qkv, c, p, lv, nr, L.cos, L.sin, L.H, L.hd, scale, K, out=out)
+
+            def rows(qkv=qkv, c=cache_r, p=pos_r, kv=kv_r, lv=one_r):
+                for _ in range(16):
+                    ops.attn_decode_rope_rows(qkv, c, p, kv, lv, L.cos, L.sin, L.H, L.hd, scale)
+            attn += [(keys, S, K, "draft_rows", capture(draft_rows)), (keys, S, K, "rows", capture(rows))]
+            keep += [draft_rows, rows]                               # the graphs read these closures' tensors: they must outlive them
+    res, ares = {i: [] for i in range(len(steps))}, {i: [] for i in range(len(attn))}
+    for rnd in range(rounds):
+        for table, out_, per, reps in ((steps, res, n_rep, n_rep), (attn, ares, 16 * 8, 8)):
+            for i, cfg_ in enumerate(table):
+                if table is steps:
+                    cfg_[5]()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(reps):
+                    cfg_[4].replay()
+                e1.record()
+                torch.cuda.synchronize()
+                if rnd:
+                    out_[i].append(e0.elapsed_time(e1) / per)
+    med = lambda ts: sorted(ts)[len(ts) // 2]
+    t_of = {(kind, S, K): med(res[i]) for i, (kind, S, K, _, _, _) in enumerate(steps)}
+    print(f"slot token steps, every row live, {a.step_keys}+ keys, {len(L.layers)} layers; median of {rounds - 1} rounds of {n_rep} replays")
+    for kind in wkinds:
+        for S, K in pairs:
+            tv, tp, tw = t_of[kind, S, K], t_of[kind, S, 0], t_of[kind, S * K, 0]
+            print(f"weights {kind} slots {S} K={K} ({S * K} rows): verify {tv:.3f} ms, plain {S}-row {tp:.3f} ms, plain {S * K}-row {tw:.3f} ms; "
+                  f"verify / plain = {tv / tp:.3f}, verify / plain at {S * K} rows = {tv / tw:.3f}; breaks even at "
+                  f"{(tv / tp - 1) / (K - 1):.3f} of the guesses kept")
+    print("attention launch alone, every row live; median of the same rounds, 128 launches each")
+    for i in range(0, len(attn), 2):
+        keys, S, K = attn[i][:3]
+        td, tr = med(ares[i]), med(ares[i + 1])
+        print(f"keys {keys} slots {S} K={K}: draft_rows {td * 1e3:.1f} us, rope_rows at {S * K} rows {tr * 1e3:.1f} us, ratio {td / tr:.3f}")
+    # ---- end to end: the ragged requests through the slots
+    e2e, modes_ = {}, [("none", None, 0)] + [(name, mk, K) for name, mk in (("taught", lambda: NgramDrafter([chain])), ("half", Half),
+                                                                             ("untaught", NgramDrafter))
+                                             for K in dict.fromkeys(K for _, K in pairs)]
+    for rnd in range(rounds):
+        for kind in wkinds:
+            set_kind(kind)
+            for S in dict.fromkeys(S for S, _ in pairs):
+                for name, mk, K in modes_:
+                    if K and (S, K) not in pairs:
+                        continue
+                    dkw = {} if mk is None else dict(draft=mk(), draft_k=K)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    got = {i: len(ids) for i, ids, _ in decs[kind, S].run(reqs, **kw, **dkw)}
+                    torch.cuda.synchronize()
+                    dt = time.perf_counter() - t0
+                    assert [got[i] for i in range(len(reqs))] == due, (name, S, K)
+                    if rnd:
+                        st = decs[kind, S].last_stats
+                        e2e.setdefault((kind, S, name, K), []).append((dt, st["steps"], st.get("verify_steps", 0), st.get("draft_accepted", 0),
+                                                                       st.get("draft_proposed", 0)))
+    print(f"end to end, {len(reqs)} requests, prompts {min(lens)}..{max(lens)} rows, answers {min(due)}..{max(due)} tokens (prefills "
+          f"included); median of {rounds - 1}")
+    for (kind, S, name, K), rs in e2e.items():
+        rs.sort()
+        dt, st_, vs, acc, prop = rs[len(rs) // 2]
+        print(f"weights {kind} slots {S} drafter {name}{f' K={K}' if K else ''}: {len(reqs) / dt:.1f} samples/s ({dt * 1e3:.0f} ms, min "
+              f"{rs[0][0] * 1e3:.0f}, max {rs[-1][0] * 1e3:.0f}; {st_} steps, {vs} verify; {acc} of {prop} guesses kept)")
+    L.decode_fp8 = L.decode_fp4 = False
+    sys.exit(0)
 
 if a.draft_k:
     # The verify step is assembled from the loop's own pieces (_draft_view for the buffers, LlamaHIP._step_logits, the arg-max and
