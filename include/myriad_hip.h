@@ -104,8 +104,8 @@ int mh_gemm_bf16_nt_splitk(const void* A, int lda, const void* B, int ldb, float
 /* K3/K4/K5 fused attention.  q/k/v/o token-major [B,S,ld] bf16, head h at columns [h*D,(h+1)*D); D in
  * {<=64, <=96 (88), <=128}; lse [B,H,Sq] f32; bias optional additive [H,Sq,Sk] f32 (eva_vit.py:131-140);
  * kv_len optional [B] valid-key counts (right padding, modeling_llama.py:43-54); causal aligns the last query
- * with the last key (KV-cache decode: Sq=1).  Replaces eva_vit.py:125-145, Qformer.py:195-262,
- * modeling_llama.py:197-222 and their autograd. */
+ * with the last key (KV-cache decode: Sq=1).  With Sq = 1 a row whose kv_len[b] <= 0 gets a zero o row and lse = -inf, and a
+ * kv_len[b] > Sk counts as Sk.  Replaces eva_vit.py:125-145, Qformer.py:195-262, modeling_llama.py:197-222 and their autograd. */
 int mh_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const float* bias,
                 const int* kv_len, int B, int H, int Sq, int Sk, int D, long q_bs, int ldq, long k_bs, int ldk,
                 long v_bs, int ldv, long o_bs, int ldo, float scale, int causal, mh_stream_t s);
@@ -552,7 +552,10 @@ int mh_lora_merge_pack_fp8(const void* W, int ldw, const float* Aqv, const float
                            void* q_out, float* scale_out, mh_stream_t stream);
 /* One decode token of attention (modeling_llama.py:186-222 with the KV cache): rotary on q / k, k | v appended at cache row
  * pos_dev[0], the one query against kv_len[b] keys -- mh_rope_kv_append + mh_attn_fwd(Sq = 1) in one launch, same bits.
- * qkv [B, ld_qkv] bf16 = [q | k | v] (q rotated in place), cache [B][T_cap][2 H D] rows [k | v], out [B, H D] bf16. */
+ * qkv [B, ld_qkv] bf16 = [q | k | v] (q rotated in place), cache [B][T_cap][2 H D] rows [k | v], out [B, H D] bf16.
+ * kv_len[b] > T_cap counts as T_cap; a row with kv_len[b] <= 0 still rotates and appends and gets a zero out row.  MH_ERR_ARG,
+ * nothing launched, unless D % 8 == 0, 0 < D <= 128, H > 0, 0 < T_cap <= 8192, ld_qkv / ld_cache / cache_bstride % 8 == 0,
+ * ldo % 4 == 0, ld_qkv >= 3 H D, ld_cache >= 2 H D and ldo >= H D (mh_attn_decode_rope_rows likewise). */
 int mh_attn_decode_rope(void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
                         const int* pos_dev, const int* kv_len, const float* cos_tab, const float* sin_tab, void* out, long ldo,
                         int B, int H, int D, int T_cap, float scale, mh_stream_t s);
@@ -573,7 +576,8 @@ int mh_attn_decode_rope_rows(void* qkv, long ld_qkv, void* cache, long cache_bst
  * zero out rows; a row whose position would reach T_cap (the host keeps that from happening) writes no cache row, leaves its q
  * alone and gets a zero out row.  MH_ERR_UNSUPPORTED, nothing launched, unless D % 16 == 0, D <= 128, K <= 8 and the LDS of a
  * workgroup -- 4 * round_up(T_cap, 64) + 8192 + 2 K D bytes -- fits gfx950's 160 KiB; a call with G = 0 answers that question and
- * reads no pointer.  MH_ERR_ARG for misaligned strides (ld_qkv, ld_cache, cache_bstride % 8, ldo % 4) or pointers. */
+ * reads no pointer.  MH_ERR_ARG for misaligned strides (ld_qkv, ld_cache, cache_bstride % 8, ldo % 4) or pointers, and for
+ * strides shorter than the rows (ld_qkv < 3 H D, ld_cache < 2 H D, ldo < H D). */
 int mh_attn_decode_rope_draft(void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
                               const int* live, const float* cos_tab, const float* sin_tab, void* out, long ldo, int G, int K,
                               int H, int D, int T_cap, float scale, mh_stream_t s);

@@ -691,7 +691,8 @@ extern "C" int mh_attn_fwd(const void* q, const void* k, const void* v, void* o,
 static int launch_decode_rope(void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
                               const int* pos_dev, const int* kv_len, const int* live, const float* cos_tab, const float* sin_tab,
                               void* out, long ldo, int B, int H, int D, int T_cap, float scale, hipStream_t stream) {
-  if (D % 8 || D > 128 || (D >> 1) % 4 || ld_qkv % 8 || ld_cache % 8 || cache_bstride % 8 || ldo % 4 || T_cap <= 0 || T_cap > 8192)
+  if (D % 8 || D <= 0 || D > 128 || (D >> 1) % 4 || ld_qkv % 8 || ld_cache % 8 || cache_bstride % 8 || ldo % 4 || T_cap <= 0 ||
+      T_cap > 8192 || H <= 0 || ld_qkv < 3L * H * D || ld_cache < 2L * H * D || ldo < (long)H * D)
     return MH_ERR_ARG;
   const int W = H * D;
   AttnParams p = {};

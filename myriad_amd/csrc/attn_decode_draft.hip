@@ -208,7 +208,9 @@ static int draft_launch(void* qkv, long ld_qkv, void* cache, long cache_bstride,
   if (sh > DRAFT_LDS_LIMIT) return MH_ERR_UNSUPPORTED;
   if (G <= 0) return MH_OK;                        // nothing to do: the answer says whether the shape is supported
   if (!qkv || !cache || !pos || !live || !cos_tab || !sin_tab || !out || (rows && !nrow)) return MH_ERR_ARG;
-  if (ld_qkv % 8 || ld_cache % 8 || cache_bstride % 8 || ldo % 4 || ld_qkv < 3L * H * D || ld_cache < 2L * H * D) return MH_ERR_ARG;
+  if (ld_qkv % 8 || ld_cache % 8 || cache_bstride % 8 || ldo % 4 || ld_qkv < 3L * H * D || ld_cache < 2L * H * D ||
+      ldo < (long)H * D)
+    return MH_ERR_ARG;
   if ((uintptr_t)qkv % 16 || (uintptr_t)cache % 16 || (uintptr_t)cos_tab % 16 || (uintptr_t)sin_tab % 16 || (uintptr_t)out % 8 ||
       (uintptr_t)pos % 4 || (uintptr_t)live % 4 || (uintptr_t)nrow % 4)
     return MH_ERR_ARG;

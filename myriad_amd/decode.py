@@ -4,6 +4,7 @@ weights, their packed decode copies and the training path are myriad_amd/llama.p
 myriad_amd/decode_host.py's."""
 from __future__ import annotations
 
+import gc
 import math
 from typing import List, Optional
 
@@ -503,8 +504,18 @@ class LlamaDecode:
         if captured:
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                token_step(-1)
+            # torch.cuda.graph does not collect garbage on entry, so the cyclic collector may run in mid-capture and finalise a
+            # dead cycle that still holds an earlier loop's graph and its memory pool -- the process aborted there.  Collect
+            # before the capture begins and keep the collector off until it has ended.
+            gc_was_on = gc.isenabled()
+            gc.collect()
+            gc.disable()
+            try:
+                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    token_step(-1)
+            finally:
+                if gc_was_on:
+                    gc.enable()
             ws["graph"] = g
         ws["warm"] = True
         return captured

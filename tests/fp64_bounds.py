@@ -34,6 +34,37 @@ Attention (the kernels round rotated q / k to bf16 once, P = exp(s - m) to bf16 
          dv = bf16(P)^T dO: ((u16 + rho) P)^T |dO| + g_acc(Sq) P^T |dO|;  each + u16 (|ref| + e) for the bf16 output.
          The dS error is bounded by P |dP - delta| -- the size of dS itself -- not by P |dO||v|^T: an error in one key tile
          or one row is then out of bound (tests/test_fp64_bounds_cpu.py shows it on an emulation of the kernels).
+One-query decode attention (attn_decode_kernel, attn_decode_draft_kernel, one_row_attention; the split pair with `chunk`):
+    decode_attn_ref_bound.  These kernels keep the probabilities in fp32 -- there is no u16 term on P|V|; the only bf16
+    rounding is the output's.  With len = min(kv_len, T_cap) keys, P_j the fp64 probabilities and PV = sum_j P_j |v_j|:
+    scores: qf = bf16(q) * scale is rounded once, a lane makes 8 serial multiply-adds (a product and a sum each, or one fused
+        operation: 9 roundings with qf's at most), a 4-step butterfly over the key's 16 lanes follows:
+        ds_j = G_SCORE u32 scale (|q||k_j|), G_SCORE = 1 + 1 + 8 + 4 = 14, + scale (dq_e |k_j| + |q| dk_e,j + dq_e dk_e,j) where
+        the caller cannot read the rotated value back (q_err / k_err of rope_bf16, as in attn_ref_bound).
+    weights: the kernel's weight of key j is w_j = __expf(fl(s'_j - mx')) with s' the computed scores and mx' their maximum.  A
+        common factor of all w_j cancels between the numerator and the normaliser, so only the error relative to
+        exp(s_j - mx') counts: 1 + rho_j = exp(x_j) (1 + eta_j) with x_j = ds_j + u32 |a_j| (the score's error and the rounded
+        difference, both in the exponent) and |eta_j| <= (4 + 2 |a_j|) u32 (the __expf allowance above), |a_j| = max_i s_i - s_j
+        + ds_j + max_i ds_i.  A weight below fp32's normal range may be flushed to zero: + 2^-126 absolute on every w_j (the
+        largest is 1), 2 F32_TINY on P_j.  The same w_j enter the numerator and the normaliser, and for weights
+        P_j (1 + rho_j) the normalised sum moves by exactly sum_j P_j rho_j (v_j - o) / (1 + sum_j P_j rho_j), so
+        e_w = sum_j (P_j rho_j + 2 F32_TINY) |v_jd - o_d| / (1 - sum_j P_j rho_j): every key's error enters weighted by its own
+        P_j, never as max_j rho_j -- a spike row whose other keys are far away keeps a bound of its own size.
+    normaliser: a lane adds its ceil(len / 64) positive terms serially, then the 6-step butterfly: g_norm = (ceil(len / 64) + 6)
+        u32, relative; inv = 1 / sum: C_FN u32; the product by inv: u32.
+    PV: a wave adds its ceil(len / 16) keys serially (the product and the sum: ceil(len / 16) + 1), the 16 wave partials are added
+        in order (16): g_pv = (ceil(len / 16) + 17) u32 on PV.
+    o:  e = e_w + g_pv PV + (g_norm + (C_FN + 1) u32) (|o| + e_w), then the one bf16 rounding, e + u16 (|o| + e).
+    lse = mx' + __logf(sum') = lse + log(1 + sum_j P_j (rho_j + phi_j)) before the function's own error:
+        sum_j P_j rho_j + g_norm + C_FN u32 (|log sum| + 1) + u32 (|lse| + |max_j s_j|) -- at most max_j ds_j + the normaliser's
+        relative error + the function's (the + 1: a relative error of sum' is an absolute one of its logarithm).
+    len = 0: o is exactly 0 and lse exactly -inf (bound 0).
+    split form (chunk = 128 / 256 / 512; attn_decode_split_kernel + attn_decode_combine_kernel): a chunk of n_c keys is the
+        one-row kernel with 4 waves -- |a_j| counts from the chunk's own maximum, g_norm,c = ceil(n_c / 64) + 6, a wave adds
+        ceil(n_c / 4) keys, the four partials are added in order: g_pv,c = ceil(n_c / 4) + 1 + 4.  The merge multiplies the record
+        of chunk c by __expf(fl(m_c - M)): rho_c = (1 + 4 + 2 |m_c - M|) u32, a factor (1 + rho_c) on every weight of the chunk
+        (rho_j + rho_c + rho_j rho_c takes rho_j's place; a flushed factor loses at most 2^-126 per key: 4 F32_TINY in all), and
+        adds nc = ceil(len / chunk) products serially for L and for o: + nc + 1 on g_norm and on g_pv.
 
 Row kernels (norm.hip, loss.hip, expert.hip l2norm): one 256-thread workgroup per row sums D terms in fp32 as per-thread serial
 sums of float4 chunks (4 ceil(D/1024) terms a thread), a 64-lane butterfly (6 additions), then the wave values in order:
@@ -385,6 +416,195 @@ def attn_ref_bound(q, k, v, scale, mask, q_err=None, k_err=None, dout=None, dout
     out.update(dq=dq, dk=dk, dv=dv, dq_bound_acc=e_dq, dk_bound_acc=e_dk, dv_bound_acc=e_dv,
                dq_bound=_out_round(dq, e_dq), dk_bound=_out_round(dk, e_dk), dv_bound=_out_round(dv, e_dv))
     return out
+
+
+G_SCORE = 14               # roundings of a one-query decode score: qf, 8 products folded into 8 sums (+ 1), a 4-step butterfly
+DECODE_WAVES = 16          # attention.hip DNW / attn_decode_draft.hip DDW: waves that share the keys of a one-row workgroup
+SPLIT_WAVES = 4            # attn_decode_split.hip: waves of a chunk workgroup
+
+
+def decode_attn_ref_bound(q, k, v, scale, kv_len, q_err=None, k_err=None, chunk=None):
+    """fp64 one-query attention with fp32 probabilities (module docstring, "One-query decode attention"): q [B, H, D] and
+    k, v [B, H, T, D] bf16-valued (q, k as the kernel multiplies them: rotated and rounded; q_err [B, H, D] / k_err [B, H, T, D]
+    rope_bf16's uncertainties where the caller cannot read the device's rotation back), scale the launcher's float argument,
+    kv_len [B] ints (clamped to T here as the kernels clamp it; the keys at and past it are never read and may hold anything).
+    chunk: the split kernels' chunk size (None: the one-row kernels).  Returns a dict: o [B, H, D], lse [B, H], o_bound (after the
+    bf16 rounding), o_bound_acc (before it), lse_bound.  A row with no key: o = 0, lse = -inf, bounds 0."""
+    q, k, v = q.double(), k.double(), v.double()
+    B, H, T, D = k.shape
+    dev = k.device
+    lens = torch.as_tensor(kv_len, device=dev).long().clamp(0, T)
+    mask = (torch.arange(T, device=dev)[None] < lens[:, None])[:, None]                  # [B, 1, T]
+    live = (lens > 0)[:, None]                                                           # [B, 1]
+    k = torch.where(mask[..., None], k, torch.zeros_like(k))                             # rows past kv_len: poison, never read
+    v = torch.where(mask[..., None], v, torch.zeros_like(v))
+    qe = torch.zeros_like(q) if q_err is None else q_err.double()
+    ke = torch.zeros_like(k) if k_err is None else torch.where(mask[..., None], k_err.double(), torch.zeros_like(k))
+    sc = f32_value(scale)
+    s = torch.einsum("bhd,bhtd->bht", q, k) * sc
+    qk_abs = torch.einsum("bhd,bhtd->bht", q.abs(), k.abs())
+    ds = sc * (G_SCORE * U32 * qk_abs + torch.einsum("bhd,bhtd->bht", qe, k.abs()) + torch.einsum("bhd,bhtd->bht", q.abs(), ke)
+               + torch.einsum("bhd,bhtd->bht", qe, ke))
+    ds = ds.masked_fill(~mask, 0.0)
+    ninf = float("-inf")
+    sm = s.masked_fill(~mask, ninf)
+    m = sm.amax(-1, keepdim=True)
+    m = torch.where(live[..., None], m, torch.zeros_like(m))
+    e = torch.exp(sm - m)                                                                # masked: 0
+    S = e.sum(-1, keepdim=True).clamp_min(1e-300)
+    P = e / S
+    lse = torch.where(live, m[..., 0] + S[..., 0].log(), torch.full_like(S[..., 0], ninf))
+    o = torch.einsum("bht,bhtd->bhd", P, v)
+    n_max = int(lens.max()) if lens.numel() else 0
+    if chunk is None:
+        m_own, rho_c, tiny = m, 0.0, 2 * F32_TINY
+        n_norm = -(-n_max // 64) + 6
+        n_pv = -(-n_max // DECODE_WAVES) + 1 + DECODE_WAVES
+    else:
+        nch = -(-T // chunk)
+        pad = nch * chunk - T
+        m_c = torch.nn.functional.pad(sm, (0, pad), value=ninf).view(B, H, nch, chunk).amax(-1)          # [B, H, nch]
+        used = m_c > ninf
+        m_c = torch.where(used, m_c, m.expand_as(m_c))
+        rho_c = ((5 + 2 * (m - m_c)) * U32).repeat_interleave(chunk, -1)[..., :T]
+        m_own = m_c.repeat_interleave(chunk, -1)[..., :T]
+        tiny = 4 * F32_TINY
+        n_c, nc = min(chunk, n_max), -(-n_max // chunk)
+        n_norm = -(-n_c // 64) + 6 + nc + 1
+        n_pv = -(-n_c // SPLIT_WAVES) + 1 + SPLIT_WAVES + nc + 1
+    a_abs = ((m_own - s).clamp_min(0.0) + ds + ds.amax(-1, keepdim=True)).masked_fill(~mask, 0.0)
+    x = ds + U32 * a_abs
+    rho = torch.expm1(x) + (4 + 2 * a_abs) * U32 * torch.exp(x)
+    rho = (rho + rho_c + rho * rho_c).masked_fill(~mask, 0.0)
+    w_err = (P * rho + tiny).masked_fill(~mask, 0.0)                                     # [B, H, T]
+    r_sum = (P * rho).sum(-1)                                                            # [B, H]
+    if not bool((r_sum < 0.5).all()):
+        raise ValueError("decode_attn_ref_bound: the weights' relative error is not small (rope ambiguity on a whole row?)")
+    dev_v = (v - o[:, :, None]).abs()
+    e_w = torch.einsum("bht,bhtd->bhd", w_err, dev_v) / (1 - r_sum)[..., None]
+    PV = torch.einsum("bht,bhtd->bhd", P, v.abs())
+    e_o = e_w + n_pv * U32 * PV + (n_norm + C_FN + 1) * U32 * (o.abs() + e_w)
+    logS = S[..., 0].log()
+    e_lse = r_sum + n_norm * U32 + C_FN * U32 * (logS.abs() + 1) + U32 * (torch.where(live, lse, torch.zeros_like(lse)).abs() + m[..., 0].abs())
+    e_lse = torch.where(live, e_lse, torch.zeros_like(e_lse))
+    e_o = torch.where(live[..., None], e_o, torch.zeros_like(e_o))
+    return dict(o=o, lse=lse, o_bound_acc=e_o, o_bound=_out_round(o, e_o), lse_bound=e_lse)
+
+
+def decode_attn_inputs(B, H, D, T_cap, seed, ld_pad=8):
+    """Seeded host inputs of a one-query decode case: qkv [B, 3W + ld_pad] bf16 ~ 0.7 N(0, 1) with a border, cache
+    [B, T_cap, 2W] bf16 of the same law (the caller poisons rows past kv_len), rotary tables to T_cap + 8 positions."""
+    W = H * D
+    qkv = (rnd(B, 3 * W + ld_pad, seed=seed) * 0.7).to(torch.bfloat16)
+    cache = (rnd(B, T_cap, 2 * W, seed=seed + 1) * 0.7).to(torch.bfloat16)
+    cos, sin = rope_tables(D, max_pos=T_cap + 8)
+    return qkv, cache, cos, sin
+
+
+# The grids of tests/test_decode_attention_edges_gpu.py, here so that tests/test_fp64_bounds_cpu.py checks the emulations at the
+# same lengths and the rope ambiguity of the same seeds.  One-row kernel: 16 waves (DNW), 128 keys per score pass in two 64-key
+# halves, a 64-lane stride in the softmax, a 16-key wave round-robin with an 8 x 16 = 128-key unrolled group (taken while
+# j + 112 < len: first at len = 113) and a remainder of up to 7 keys a wave.
+DECODE_T = 257
+DECODE_LENS = (0, 1, 2, 15, 16, 17, 63, 64, 65, 112, 113, 127, 128, 129, 143, 144, 145, 255, 256, 257)
+DECODE_DS = (8, 16, 40, 64, 88, 96, 128)
+DECODE_HS = (1, 3)
+SPLIT_CHUNKS = (128, 256, 512)
+SPLIT_DS = (8, 40, 128)
+DRAFT_KS = (1, 3, 8)
+DRAFT_DS = (16, 48, 128)
+
+
+def decode_seed(D, H):
+    return 7000 + 10 * D + H
+
+
+def decode_launches():
+    """[(T_cap, kv_len[3], pos[3])] of the one-row grid: DECODE_LENS three at a time at T_cap = 257 (the last group adds
+    T_cap + 5, which the kernel clamps), then T_cap == kv_len for 1, 64 and 65 with T_cap + 5 and T_cap - 1 beside it.  pos[b] =
+    min(kv_len, T_cap) - 1 (0 for a row without a key) is row b's rotary position, and its cache row in the rows form."""
+    out = []
+    lens = list(DECODE_LENS) + [DECODE_T + 5]
+    for i in range(0, len(lens), 3):
+        out.append((DECODE_T, lens[i:i + 3]))
+    for T in (1, 64, 65):
+        out.append((T, [T, T + 5, T - 1]))
+    return [(T, ls, [max(min(n, T) - 1, 0) for n in ls]) for T, ls in out]
+
+
+DECODE_EDGE_KINDS = ("q_zero", "spike_50", "scores_200", "v_alternating")
+DECODE_EDGE_LENS = [129, 257, 17]
+DECODE_EDGE_SPIKE_ROW = 7
+
+
+def decode_edge_inputs(kind, B, H, D, T_cap, seed, pos, spike_row=DECODE_EDGE_SPIKE_ROW, spike=50.0):
+    """decode_attn_inputs with one score / value edge: q = 0 (uniform weights); cache key `spike_row` = c q_rot with c chosen so
+    that its score is `spike` (the others are ~0.5 N(0, 1)); q scaled by 400 (scores ~200 N(0, 1)); v = (-1)^j (1 + 0.01 N(0, 1))
+    so that |o| << P|V|.  pos [B]: the rotary positions of q (the spike is a multiple of the rotated q)."""
+    W = H * D
+    qkv, cache, cos, sin = decode_attn_inputs(B, H, D, T_cap, seed)
+    if kind == "q_zero":
+        qkv[:, :W] = 0
+    elif kind == "scores_200":
+        qkv[:, :W] = (qkv[:, :W].float() * 400).to(torch.bfloat16)
+    elif kind == "v_alternating":
+        sign = torch.where(torch.arange(T_cap) % 2 == 0, 1.0, -1.0)[None, :, None]
+        cache[..., W:] = (sign * (1 + 0.01 * cache[..., W:].float())).to(torch.bfloat16)
+    elif kind == "spike_50":
+        q = qkv[:, :W].float().view(B, 1, H, D).transpose(1, 2)
+        qrot = rope64(q, torch.as_tensor(pos)[:, None], cos, sin).to(torch.bfloat16).float()[:, :, 0]           # [B, H, D]
+        c = spike / (f32_value(D ** -0.5) * (qrot * qrot).sum(-1, keepdim=True))
+        cache[:, spike_row, :W] = (c * qrot).reshape(B, W).to(torch.bfloat16)
+    else:
+        raise ValueError(kind)
+    return qkv, cache, cos, sin
+
+
+def decode_rope_pair(qkv, H, D, pos, cos, sin):
+    """rope_bf16 of the q and k columns of qkv rows [R, >= 3W] at pos [R]: (qr, qe, kr, ke), each [R, H, D]."""
+    R, W = qkv.shape[0], H * D
+    pl = torch.as_tensor(pos, device=qkv.device).long()[:, None]
+    heads = lambda t: t.float().view(R, 1, H, D).transpose(1, 2)
+    qr, qe = rope_bf16(heads(qkv[:, :W]), pl, cos, sin)
+    kr, ke = rope_bf16(heads(qkv[:, W:2 * W]), pl, cos, sin)
+    return qr[:, :, 0], qe[:, :, 0], kr[:, :, 0], ke[:, :, 0]
+
+
+def split_t_cap(chunk):
+    return 2 * chunk + 37
+
+
+def split_lens(chunk):
+    """kv_len of the split grid: one key, around one chunk, two chunks, one past, and T_cap (not a multiple of 64)."""
+    return [1, chunk - 1, chunk, chunk + 1, 2 * chunk, 2 * chunk + 1, split_t_cap(chunk)]
+
+
+def split_seed(D, chunk):
+    return 9100 + 10 * D + chunk // 128
+
+
+def split_launches(chunk):
+    """[(variant, kv_len, pos)] of the split grid (per-row state: pos[b] is row b's rotary position and cache row).  "edge":
+    pos = kv_len - 1, the seven lengths in two launches.  "past": the form tests/test_split_rows_gpu.py defines -- the new row
+    lies at or past kv_len (written, not attended), in the last attended chunk (rows 0 and 3) or in a chunk none of the row's keys
+    is in (row 2); row 1 stays an edge row."""
+    ls = split_lens(chunk)
+    return [("edge", ls[:4], [n - 1 for n in ls[:4]]), ("edge", ls[4:], [n - 1 for n in ls[4:]]),
+            ("past", ls[:4], [ls[0] + 3, ls[1] - 1, 2 * chunk + 3, ls[3] + 3])]
+
+
+SPLIT_HEADS = 2
+DRAFT_HEADS = 2
+
+
+def draft_p0(K):
+    """First positions of the draft grid, two launches of three groups: rows whose keys all come from the LDS copies (0), from
+    both in one 128-key pass (1, 15, 120, 127: the pass edge falls inside the K rows for K = 8) and from the cache's end."""
+    return [[0, 1, 15], [120, 127, DECODE_T - K]]
+
+
+def draft_seed(D, K):
+    return 11000 + 10 * D + K
 
 
 # ---------------------------------------------------------------------------------------------------------------- shared

@@ -1863,3 +1863,253 @@ def test_layernorm_dropout_generator_keeps_every_row_well_defined():
                 x = z if res is None else z * ki + res
                 fb.ln_dropout_fwd_ref_bound(z, res, w, b, 1e-12, ki, ko, x_out=x)
                 fb.ln_dropout_bwd_ref_bound(dy, x, w, 1e-12, ki, ko)
+
+
+# ------------------------------------------------------------------------------------------- one-query decode attention
+def _xor_sum(x, steps):
+    """The butterfly v += shfl_xor(v, o) over the last axis (the lanes), for o in steps."""
+    idx = torch.arange(x.shape[-1])
+    for o in steps:
+        x = x + x[..., idx ^ o]
+    return x
+
+
+def _emu_scores(q, k, scale):
+    """fp32 scores of one query per row as the decode kernels form them: qf = q * scale, 16 lanes of 8 serial multiply-adds per
+    key, the xor butterfly 1, 2, 4, 8.  q [N, D], k [N, n, D] fp32 (bf16-valued) -> [N, n]."""
+    N, n, D = k.shape
+    qf = torch.zeros(N, 128)
+    qf[:, :D] = q * torch.tensor(scale, dtype=F32)
+    kp = torch.zeros(N, n, 128)
+    kp[..., :D] = k
+    qf, kp = qf.view(N, 1, 16, 8), kp.view(N, n, 16, 8)
+    s = torch.zeros(N, n, 16)
+    for e in range(8):
+        s = s + qf[..., e] * kp[..., e]
+    return _xor_sum(s, (1, 2, 4, 8))[..., 0]
+
+
+def _emu_softmax_stats(s, n_sum=None):
+    """(mx [N], e [N, n], sum [N]): every lane adds its keys j = lane, lane + 64, ... serially, then the 6-step butterfly.
+    n_sum: keys the normaliser covers (a mutant's; default all)."""
+    N, n = s.shape
+    mx = s.amax(-1)
+    e = torch.exp(s - mx[:, None])
+    n_sum = n if n_sum is None else n_sum
+    steps = -(-n // 64)
+    ep = torch.zeros(N, steps * 64)
+    ep[:, :n_sum] = e[:, :n_sum]
+    ep = ep.view(N, steps, 64)
+    acc = torch.zeros(N, 64)
+    for t in range(steps):
+        acc = acc + ep[:, t]
+    return mx, e, _xor_sum(acc, (32, 16, 8, 4, 2, 1))[:, 0]
+
+
+def _emu_pv(e, v, waves):
+    """Wave w adds the keys w, w + waves, ... serially: [N, waves, D] partial outputs."""
+    N, n, D = v.shape
+    steps = -(-n // waves)
+    ep = torch.zeros(N, steps * waves)
+    ep[:, :n] = e
+    vp = torch.zeros(N, steps * waves, D)
+    vp[:, :n] = v
+    ep, vp = ep.view(N, steps, waves), vp.view(N, steps, waves, D)
+    o = torch.zeros(N, waves, D)
+    for t in range(steps):
+        o = o + ep[:, t, :, None] * vp[:, t]
+    return o
+
+
+def emu_decode_one_row(q, k, v, scale, n, mutant=None):
+    """attn_decode_kernel's phases 1 to 3 for n keys: 16 waves, the wave partials added in order, the product by 1 / sum, one
+    bf16 rounding; lse = mx + log(sum).  q [N, D], k / v [N, T, D] fp32 -> (o [N, D] bf16, lse [N] f32)."""
+    N, D = q.shape
+    n = n + {"kv_len_plus_one": 1, "kv_len_minus_one": -1}.get(mutant, 0)
+    if n <= 0:
+        return torch.zeros(N, D).to(BF16), torch.full((N,), float("-inf"))
+    s = _emu_scores(q, k[:, :n], scale)
+    mx, e, tot = _emu_softmax_stats(s, 64 * (n // 64) if mutant == "normaliser_without_its_tail" else None)
+    if mutant == "last_key_dropped":
+        e = e.clone()
+        e[:, n - 1] = 0
+    part = _emu_pv(e, v[:, :n], 16)
+    if mutant == "one_wave_dropped":
+        part[:, 5] = 0                                      # the keys j % 16 == 5
+    r = torch.zeros(N, D)
+    for w in range(16):
+        r = r + part[:, w]
+    return (r * (1.0 / tot)[:, None]).to(BF16), mx + torch.log(tot)
+
+
+def emu_decode_split(q, k, v, scale, n, chunk, mutant=None):
+    """attn_decode_split_kernel per chunk (4 waves, ((p0 + p1) + p2) + p3, the chunk's own m and l) and the in-order merge of
+    attn_decode_combine_kernel.  Returns o [N, D] bf16."""
+    N, D = q.shape
+    nc = -(-n // chunk)
+    recs = []
+    for c in range(nc):
+        j0, j1 = c * chunk, min(n, (c + 1) * chunk)
+        mx, e, tot = _emu_softmax_stats(_emu_scores(q, k[:, j0:j1], scale))
+        p = _emu_pv(e, v[:, j0:j1], 4)
+        recs.append((mx, tot, ((p[:, 0] + p[:, 1]) + p[:, 2]) + p[:, 3]))
+    M = torch.stack([r[0] for r in recs]).amax(0)
+    L, o = torch.zeros(N), torch.zeros(N, D)
+    for c, (mx, tot, oc) in enumerate(recs):
+        if mutant == "chunk_record_skipped" and c == nc - 1:
+            continue
+        if mutant == "wrong_chunk_max":
+            mx = recs[(c + 1) % nc][0]
+        w = torch.exp(mx - M)
+        L = L + w * tot
+        o = o + w[:, None] * oc
+    return (o * (1.0 / L)[:, None]).to(BF16)
+
+
+def _decode_operands(D, H, T, lens, pos, seed, unrotated_key=False):
+    """One launch of the decode grid on the host: row b appends at cache row n_b - 1 (n_b = min(kv_len, T); row 0 when it has no
+    key) with the rotary at pos[b].  Returns the fp32 operands an emulation multiplies (its own fp32 rotation, rounded once), the
+    reference's (rope_bf16) with their uncertainties, and the clamped lengths.  Rows at and past n_b hold NaN."""
+    B, W = len(lens), H * D
+    qkv, cache, cos, sin = fb.decode_attn_inputs(B, H, D, T, seed)
+    pl = torch.tensor(pos)[:, None]
+    heads = lambda t: t.float().view(B, 1, H, D).transpose(1, 2)
+    q, kn, vn = heads(qkv[:, :W]), heads(qkv[:, W:2 * W]), heads(qkv[:, 2 * W:3 * W])
+    qr, qe = fb.rope_bf16(q, pl, cos, sin)
+    kr, ke_new = fb.rope_bf16(kn, pl, cos, sin)
+    q32 = fb.rope64(q, pl, cos, sin).to(BF16).float()
+    k32 = kn if unrotated_key else fb.rope64(kn, pl, cos, sin).to(BF16).float()
+    k = cache[..., :W].float().view(B, T, H, D).transpose(1, 2).clone()
+    v = cache[..., W:].float().view(B, T, H, D).transpose(1, 2).clone()
+    ns = [min(n, T) for n in lens]
+    kref, ke = k.double(), torch.zeros(B, H, T, D, dtype=torch.float64)
+    for b, n in enumerate(ns):
+        k[b, :, n:], v[b, :, n:], kref[b, :, n:] = float("nan"), float("nan"), float("nan")
+        a = max(n - 1, 0)
+        k[b, :, a], v[b, :, a], kref[b, :, a], ke[b, :, a] = k32[b, :, 0], vn[b, :, 0], kr[b, :, 0], ke_new[b, :, 0]
+    return dict(q=q32[:, :, 0], k=k, v=v, qr=qr[:, :, 0], qe=qe[:, :, 0], kref=kref, ke=ke, ns=ns, ke_new=ke_new)
+
+
+def _decode_check(D, H, T, lens, pos, seed, chunk=None, mutant=None):
+    c = _decode_operands(D, H, T, lens, pos, seed, unrotated_key=mutant == "appended_key_unrotated")
+    scale = D ** -0.5
+    r = fb.decode_attn_ref_bound(c["qr"], c["kref"], c["v"], scale, lens, q_err=c["qe"], k_err=c["ke"], chunk=chunk)
+    ratios = []
+    for b, n in enumerate(c["ns"]):
+        if chunk is None:
+            o, lse = emu_decode_one_row(c["q"][b], c["k"][b], c["v"][b], scale, n, mutant)
+            if n == 0 and mutant is None:
+                assert bool((o == 0).all()) and bool((lse == float("-inf")).all()) and bool((r["lse"][b] == float("-inf")).all())
+            else:
+                ratios.append(fb.assert_within(lse, r["lse"][b], r["lse_bound"][b], f"decode lse, row {b}"))
+        else:
+            o = emu_decode_split(c["q"][b], c["k"][b], c["v"][b], scale, n, chunk, mutant)
+        ratios.append(fb.assert_within(o, r["o"][b], r["o_bound"][b], f"decode o, row {b} of kv_len {lens}"))
+    return max(ratios)
+
+
+@pytest.mark.parametrize("D,H", [(8, 1), (40, 3), (64, 1), (128, 3)])
+def test_decode_one_row_emulation_is_within_the_bound_over_the_length_grid(D, H):
+    worst = max(_decode_check(D, H, T, lens, pos, fb.decode_seed(D, H)) for T, lens, pos in fb.decode_launches())
+    print(f"one-row emulation D={D} H={H}: largest err / bound {worst:.3f}")
+    assert worst > 1e-3
+
+
+def test_decode_one_row_emulation_is_within_the_bound_at_8192_keys():
+    worst = _decode_check(128, 1, 8192, [8192], [8191], fb.decode_seed(128, 1) + 5)
+    print(f"one-row emulation at 8192 keys: largest err / bound {worst:.3f}")
+
+
+@pytest.mark.parametrize("chunk", fb.SPLIT_CHUNKS)
+@pytest.mark.parametrize("D", [8, 128])
+def test_decode_split_emulation_is_within_the_bound_over_the_length_grid(D, chunk):
+    lens, T = fb.split_lens(chunk), fb.split_t_cap(chunk)
+    worst = max(_decode_check(D, 2, T, lens[i:i + 4], [min(n, T) - 1 for n in lens[i:i + 4]], fb.split_seed(D, chunk), chunk=chunk)
+                for i in (0, 4))
+    print(f"split emulation D={D} chunk={chunk}: largest err / bound {worst:.3f}")
+    assert worst > 1e-3
+
+
+DECODE_MUTANTS = ["last_key_dropped", "one_wave_dropped", "normaliser_without_its_tail", "appended_key_unrotated", "kv_len_plus_one",
+                  "kv_len_minus_one"]
+
+
+@pytest.mark.parametrize("mutant", DECODE_MUTANTS)
+def test_decode_one_row_mutant_fails_the_bound(mutant):
+    with pytest.raises(AssertionError, match="out of bound"):
+        _decode_check(64, 2, fb.DECODE_T, [200, 145, 113], [199, 150, 3], fb.decode_seed(64, 2), mutant=mutant)
+
+
+@pytest.mark.parametrize("mutant", ["chunk_record_skipped", "wrong_chunk_max"])
+def test_decode_split_mutant_fails_the_bound(mutant):
+    with pytest.raises(AssertionError, match="out of bound"):
+        _decode_check(64, 2, 293, [257, 129, 293], [256, 128, 292], fb.split_seed(64, 128), chunk=128, mutant=mutant)
+
+
+def test_decode_bound_is_tighter_than_the_tiled_bound_it_replaces():
+    """On the inputs of test_attn_decode_rope_per_row_positions_and_lengths (tests/test_attention_edges_gpu.py): the new o bound is
+    element-wise <= attn_ref_bound's o_bound, with the same rope uncertainties handed to both."""
+    B, H, D, T = 3, 4, 128, 200
+    W = H * D
+    pos_b, kv_b, app = [5, 63, 130], [65, 128, 200], 64
+    qkv = fb.rnd(B, 3 * W + 64, seed=500).to(BF16)
+    cache = fb.rnd(B, T, 2 * W, seed=501).to(BF16)
+    cos, sin = fb.rope_tables(D)
+    pl = torch.tensor(pos_b)[:, None]
+    qr, qe = fb.rope_bf16(qkv[:, :W].float().view(B, 1, H, D).transpose(1, 2), pl, cos, sin)
+    kr, ke_new = fb.rope_bf16(qkv[:, W:2 * W].float().view(B, 1, H, D).transpose(1, 2), pl, cos, sin)
+    k = cache[:, :, :W].float().view(B, T, H, D).transpose(1, 2).double()
+    ke = torch.zeros_like(k)
+    k[:, :, app], ke[:, :, app] = kr[:, :, 0], ke_new[:, :, 0]
+    v = cache[:, :, W:].float().view(B, T, H, D).transpose(1, 2).clone()
+    v[:, :, app] = qkv[:, 2 * W:3 * W].float().view(B, H, D)
+    kv_len = torch.tensor(kv_b)
+    old = fb.attn_ref_bound(qr, k, v, D ** -0.5, fb.attn_mask(B, 1, T, False, kv_len, "cpu"), q_err=qe, k_err=ke)
+    new = fb.decode_attn_ref_bound(qr[:, :, 0], k, v, D ** -0.5, kv_b, q_err=qe[:, :, 0], k_err=ke)
+    assert torch.allclose(new["o"], old["o"][:, :, 0], rtol=0, atol=1e-7)        # the same reference but for scale as the launcher's float
+    assert bool((new["o_bound"] <= old["o_bound"][:, :, 0]).all())
+    print(f"new / old o bound: median {float((new['o_bound'] / old['o_bound'][:, :, 0]).median()):.3f}")
+
+
+def test_decode_generators_keep_the_rope_ambiguity_rare():
+    """The seeds and positions tests/test_decode_attention_edges_gpu.py uses: over the launches of a case at most 1 % of the
+    rotated q and appended k elements are ambiguous, and never a whole head row."""
+    for D in fb.DECODE_DS:
+        for H in fb.DECODE_HS:
+            qe, ke = [], []
+            for T, lens, pos in fb.decode_launches():
+                c = _decode_operands(D, H, T, lens, pos, fb.decode_seed(D, H))
+                qe.append(c["qe"]), ke.append(c["ke_new"][:, :, 0])
+            fb.assert_rope_exempt_share(torch.stack(qe), f"decode q D={D} H={H}")
+            fb.assert_rope_exempt_share(torch.stack(ke), f"decode appended k D={D} H={H}")
+    for chunk in fb.SPLIT_CHUNKS:
+        for D in fb.SPLIT_DS:
+            lens, T = fb.split_lens(chunk), fb.split_t_cap(chunk)
+            qe, ke = [], []
+            for i in (0, 4):
+                c = _decode_operands(D, 2, T, lens[i:i + 4], [min(n, T) - 1 for n in lens[i:i + 4]], fb.split_seed(D, chunk))
+                qe.append(c["qe"].reshape(-1, D)), ke.append(c["ke_new"].reshape(-1, D))
+            fb.assert_rope_exempt_share(torch.cat(qe), f"split q D={D} chunk={chunk}")
+            fb.assert_rope_exempt_share(torch.cat(ke), f"split appended k D={D} chunk={chunk}")
+    # the 8192-key case, the score / value edges (q scaled or zeroed) and the draft rows at p0 + j
+    share = lambda qkv, H, D, pos, cos, sin, what, q=True: [fb.assert_rope_exempt_share(m, f"{what} {nm}") for nm, m in
+                                                            zip(("q", "k"), fb.decode_rope_pair(qkv, H, D, pos, cos, sin)[1::2]) if q or nm == "k"]
+    qkv, _, cos, sin = fb.decode_attn_inputs(1, 1, 128, 8192, fb.decode_seed(128, 1) + 5)
+    share(qkv, 1, 128, [8191], cos, sin, "8192 keys")
+    pos = [n - 1 for n in fb.DECODE_EDGE_LENS]
+    for D in (64, 128):
+        for kind in fb.DECODE_EDGE_KINDS:
+            qkv, _, cos, sin = fb.decode_edge_inputs(kind, 3, 2, D, fb.DECODE_T, fb.decode_seed(D, 2) + 7, pos)
+            share(qkv, 2, D, pos, cos, sin, f"{kind} D={D}", q=kind != "q_zero")
+    for chunk in fb.SPLIT_CHUNKS:
+        _, lens, pos = fb.split_launches(chunk)[1]
+        for D in fb.SPLIT_DS:
+            qkv, _, cos, sin = fb.decode_edge_inputs("spike_50", 3, fb.SPLIT_HEADS, D, fb.split_t_cap(chunk), fb.split_seed(D, chunk), pos,
+                                                     spike_row=chunk + 5, spike=80.0)
+            share(qkv, fb.SPLIT_HEADS, D, pos, cos, sin, f"split spike D={D} chunk={chunk}")
+    for K in fb.DRAFT_KS:
+        for D in fb.DRAFT_DS:
+            qkv, _, cos, sin = fb.decode_attn_inputs(3 * K, fb.DRAFT_HEADS, D, fb.DECODE_T, fb.draft_seed(D, K))
+            masks = [fb.decode_rope_pair(qkv, fb.DRAFT_HEADS, D, [p + j for p in p0 for j in range(K)], cos, sin)[1::2] for p0 in fb.draft_p0(K)]
+            fb.assert_rope_exempt_share(torch.cat([m[0] for m in masks]), f"draft q K={K} D={D}")
+            fb.assert_rope_exempt_share(torch.cat([m[1] for m in masks]), f"draft k K={K} D={D}")
