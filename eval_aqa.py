@@ -72,7 +72,8 @@ def parse_args(argv=None):
                         "(--world > 1: <result>.seg.rankK.npz, to be merged with eval_protocol.merge_seg_shards)")
     parser.add_argument("--draft-k", type=int, default=0, help="K > 1: draft-and-verify greedy decoding with K rows per verify "
                         "step (--bs 1, or --slots N with N * K <= 64 and the switch MYRIAD_SLOT_DRAFT=1): an n-gram drafter that observes every finished answer guesses K - 1 tokens, "
-                        "one token step verifies them; the records are those of the run without it")
+                        "one token step verifies them; the records are those of the run without it (with --llm-score behind the switch "
+                        "MYRIAD_DRAFT_SAMPLING=1)")
     parser.add_argument("--draft-corpus", type=str, default=None, help="with --draft-k: teach the drafter up front from a results "
                         ".jsonl of an earlier run (its `output` texts are tokenised) or a JSON list of id lists")
     parser.add_argument("--seg-max-step", type=int, default=200, help="with --seg-metrics: thresholds of the PRO curve")
@@ -87,7 +88,8 @@ def parse_args(argv=None):
         parser.error("--draft-corpus needs --draft-k K")
     if args.draft_k and (args.draft_k < 1 or args.draft_k > 8):
         parser.error(f"--draft-k takes 1 to 8 rows, got {args.draft_k}")
-    if args.draft_k and (args.num_beams > 1 or args.llm_score):
+    # --llm-score with --draft-k: the verify step writes the token scores behind the switch MYRIAD_DRAFT_SAMPLING=1
+    if args.draft_k and (args.num_beams > 1 or (args.llm_score and os.environ.get("MYRIAD_DRAFT_SAMPLING", "0") == "0")):
         parser.error("--draft-k is greedy decoding: it takes no --num-beams, --beam-sample, --repetition-penalty or --llm-score")
     if args.draft_k and args.slots <= 0 and args.bs != 1:
         parser.error("--draft-k without --slots decodes one sequence at a time: it needs --bs 1")

@@ -608,6 +608,40 @@ int mh_attn_decode_rope_draft_rows(void* qkv, long ld_qkv, void* cache, long cac
 int mh_draft_accept_rows(const long* nxt, const float* margin, const float* pmax, long* ids_k, long* next_ids, const int* nguess,
                          const int* live, const float* top_p, float* rec, int* pos, int* kvlen, int* step, int G, int K,
                          mh_stream_t s);
+/* The verify step under the slot engine's per-row tail (draft_sample.hip): the launches that follow the logits [G*K, ldl] f32 of
+ * a verify step when the repetition penalty, the per-request EOS ban or the device sampler is on.  Group g < G has K rows, 1 <= K
+ * <= 8 (else MH_ERR_ARG, nothing launched), nrow[g] = 1 + its real guesses of them; live[g], gen[g], seed[g] and seen[g] (ceil(V /
+ * 32) u32 words) are the slot's state as mh_sample_rows_slots / mh_repetition_penalty_rows_slots read it.  Row (g, j) is idle when
+ * live[g] == 0 or j >= nrow[g].
+ *
+ * mh_repetition_penalty_draft_rows: row (g, j), not idle, gets HF's rule (x < 0 ? x * p : x / p, p = *penalty) on every id of the
+ * bitmap seen[g] and on ids_k[g*K .. g*K + j], the tokens fed in rows 0 .. j -- each id once, also where an extra id is in the
+ * bitmap already or repeats an earlier extra; extras outside [0, V) are skipped.  The row then holds the bits
+ * mh_repetition_penalty_rows_slots leaves on it when its bitmap is seen[g] plus ids_k[g*K .. g*K + j - 1] and prev_ids is
+ * ids_k[g*K + j].  The bitmap is only read (the K workgroups of a group share it); idle rows are left alone.  MH_ERR_ARG for a
+ * null pointer, V < 1 or ldl < V. */
+int mh_repetition_penalty_draft_rows(float* logits, long ldl, const unsigned* seen, const long* ids_k, const int* nrow,
+                                     const int* live, int G, int K, int V, const float* penalty, mh_stream_t s);
+/* mh_sample_rows_slots (draw != 0) / mh_argmax_pmax_rows_slots (draw == 0) for those rows: row (g, j) reads seed[g] and t = gen[g]
+ * + j -- Philox counter (t, 0, 0, 0) -- and bans eos_id iff t < min_length (params[6] as in mh_sample_rows_slots).  Every output
+ * of a row that is not idle (out, margin, pmax, and with the draw kept and u_out) has the bits of the slot entry on that row alone
+ * with gen = gen[g] + j; an idle row writes out = -1, margin = pmax = 0 and (draw) kept = 0.  out / margin / pmax / kept / u_out
+ * hold G*K entries; kept, u_out and seed are not touched without the draw.  nrow and live are required.  The shape limits and the
+ * MH_ERR_UNSUPPORTED rules are mh_sample_rows_slots'. */
+int mh_sample_rows_draft(const float* logits, long ldl, long* out, float* margin, float* pmax, int* kept, float* u_out, int G, int K,
+                         int V, const float* params, const unsigned long long* seed, const int* gen, const int* nrow, const int* live,
+                         int draw, mh_stream_t s);
+/* mh_draft_accept_rows for those picks, with three additions.  (a) kept int[G*K] (may be null: the p_max rule of
+ * mh_draft_accept_rows): a row with kept[j] < 0 -- the host must draw it -- ends the chain, so it can be the last kept row but no
+ * guess behind it is confirmed; *top_p is not looked at then.  (b) seen (may be null): the bits of ids_k[g*K .. g*K + n_out - 1],
+ * the fed token and the confirmed guesses, are set in seen[g] (ids outside [0, V) skipped; V is unused without seen); the kept
+ * pick nxt[n_out - 1] joins when the next step feeds it, as in the plain step.  (c) gen[g] += n_out.  rec[g] = 4K + 1 floats: the
+ * K ids, the K margins, the K p_max, the K kept counts (0.0 without kept), then n_out.  An idle group (live[g] == 0) records id
+ * -1 in its K id entries, zeros elsewhere and n_out = 0, and changes none of ids_k, next_ids, pos, kvlen, gen, seen.  *step += 1
+ * once per launch. */
+int mh_draft_accept_sampled_rows(const long* nxt, const float* margin, const float* pmax, const int* kept, long* ids_k,
+                                 long* next_ids, const int* nguess, const int* live, const float* top_p, unsigned* seen, float* rec,
+                                 int* pos, int* kvlen, int* gen, int* step, int G, int K, int V, mh_stream_t s);
 /* Packed prefill of several decode slots (attn_ragged.hip): causal self-attention over R sequences packed row-wise into qkv
  * [M, ld_qkv] bf16 = [q | k | v] (pre-rotary, only read), with the rotary at pos[row] and the KV-cache write fused in.  seg is the
  * device table int[R][3] of (row0, len, slot) and seg_host the host's copy of it: segment i is rows row0 .. row0 + len - 1, its

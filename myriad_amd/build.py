@@ -14,7 +14,7 @@ LIB = os.path.join(HERE, "libmyriad_hip.so")
 # the read-out without its stores, gives wrong results on purpose); the product and the tests never load it
 LIB_DBG = os.path.join(HERE, "libmyriad_hip_dbg.so")
 DBG_SOURCES = ["gemm", "gemm_256", "gemm_x4", "attn_seq", "lora"]      # the files that hold a hook
-SOURCES = ["gemm", "gemm_256", "gemm_x4", "gemv", "attention", "attn_decode_split", "attn_decode_draft", "draft", "attn_ragged", "attn_seq", "attn_full", "norm", "elementwise", "conv", "loss", "sample", "scores", "beam", "beam_sample", "lowrank", "lora", "expert", "expert_bank", "seg_metrics", "image", "selfsup", "optim", "prof", "ctx", "wgrad", "qf_dropout", "lora_merge", "refresh", "version"]
+SOURCES = ["gemm", "gemm_256", "gemm_x4", "gemv", "attention", "attn_decode_split", "attn_decode_draft", "draft", "draft_sample", "attn_ragged", "attn_seq", "attn_full", "norm", "elementwise", "conv", "loss", "sample", "scores", "beam", "beam_sample", "lowrank", "lora", "expert", "expert_bank", "seg_metrics", "image", "selfsup", "optim", "prof", "ctx", "wgrad", "qf_dropout", "lora_merge", "refresh", "version"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast"]
 
 
@@ -28,7 +28,7 @@ def _stale(out, deps):
 def build(force: bool = False, verbose: bool = True) -> str:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(OBJ, exist_ok=True)
-    hdrs = [os.path.join(CSRC, h) for h in ("common.h", "gemv_pack.h", "attn_frag.h", "attn_tile.h", "smp_rng.h", "expert_map.h")]
+    hdrs = [os.path.join(CSRC, h) for h in ("common.h", "gemv_pack.h", "attn_frag.h", "attn_tile.h", "smp_rng.h", "smp_rows.h", "expert_map.h")]
     # the 256x256x64 GEMM's K loop is written by a generator (the schedule lives there); regenerate when it is newer
     gen, inc = os.path.join(CSRC, "gen_gemm_x4.py"), os.path.join(CSRC, "gemm_x4_loop.inc")
     if force or _stale(inc, [gen]):

@@ -284,8 +284,9 @@ class Chat(_ChatBase):
         multinomial sampling with do_sample, top_p, temperature, top_k = 50, repetition_penalty and generator
         (LlamaHIP.beam_generate) -- and last_stats gains num_beams, beam_sampled_steps and beam_host_steps; without it the
         beams are deterministic and a penalty is refused, as before.  `draft` / `draft_k`: draft-and-verify decoding of the turn
-        (LlamaHIP.greedy_generate; the same ids in fewer token steps when the drafter guesses well), refused with beams; a turn
-        on the split-KV view decodes with plain steps and last_stats["draft_off"] says "split_kv"."""
+        (LlamaHIP.greedy_generate; the same ids in fewer token steps when the drafter guesses well), refused with beams and --
+        unless model.llama.draft_sampling (MYRIAD_DRAFT_SAMPLING=1) is on -- with device sampling and `repetition_penalty` != 1;
+        a turn on the split-KV view decodes with plain steps and last_stats["draft_off"] says "split_kv"."""
         m = self.model
         m.finish_update()
         llama = m.llama

@@ -169,15 +169,29 @@ def _buffer_view(lm: "LlamaHIP", bufs: dict, split: bool, scores: bool = False) 
     return view
 
 
-def _draft_view(lm: "LlamaHIP", bufs: dict, K: int, inv_temp: float) -> dict:
+def _draft_view(lm: "LlamaHIP", bufs: dict, K: int, inv_temp: float, tail=None) -> dict:
     """The K-row verify step's view of a B = 1 buffer set (draft decoding): the caches, `pos`, `kvlen`, `step` and the fed token
     ids_k[0] are the set's, shared with its plain one-row step, so the host switches between the two from step to step; the K-row
     ids / activations / logits / picks, the 3K + 1 float record `drec`, the device float `top_p` and the always-live flag are the
-    view's own, and so is its graph.  Kept in the set (one per K and inv_temp, which the arg-max launch bakes in)."""
+    view's own, and so is its graph.  Kept in the set (one per K and inv_temp, which the arg-max launch bakes in).
+
+    `tail` = (device-sampled, penalty, scores), behind `draft_sampling`: the view of the verify step that runs the decode slots'
+    per-row tail at G = 1 (draft_sample.hip), keyed (K, inv_temp) + tail.  It adds `kept` [K], the one-group state `full` = [K]
+    (nrow: every row holds a token, fillers included), `ngs` = [K - 1] and, in the set, the token counter `gen` [1]; its record
+    `drec` is flat -- the 4K + 1 floats of mh_draft_accept_sampled_rows (`arec`), then with scores SCORE_ROWS rows of K (`sc`).
+    With the device sampler the set also gains `prm6` (the slot form's six knobs) and `plain_rows`, the view of the call's plain
+    step in the slot form: the solo step counts launches in `step`, the slot form tokens in `gen`, which both steps advance."""
     if bufs["ids"].shape[0] != 1:
         raise NotImplementedError("draft decoding runs one sequence (batch 1)")
     views = bufs.setdefault("draft_views", {})
-    key = (int(K), float(inv_temp))
+    key = (int(K), float(inv_temp)) + (() if tail is None else tuple(bool(t) for t in tail))
+    if tail is not None and "gen" not in bufs:
+        bufs["gen"] = torch.zeros((1,), dtype=torch.int32, device=lm.dev)
+    if tail is not None and tail[0] and "prm6" not in bufs:
+        bufs["prm6"] = torch.zeros((6,), dtype=F32, device=lm.dev)
+    if tail is not None and tail[0] and ("plain_rows", bool(tail[1]), bool(tail[2])) not in views:
+        views["plain_rows", bool(tail[1]), bool(tail[2])] = dict(bufs, graph=None, warm=False,
+                                                                 live1=torch.ones((1,), dtype=torch.int32, device=lm.dev))
     if key not in views:
         dev = lm.dev
         views[key] = dict(bufs, graph=None, warm=False, split=None, draft_k=int(K), ids=bufs["ids_k"][:K],
@@ -185,16 +199,23 @@ def _draft_view(lm: "LlamaHIP", bufs: dict, K: int, inv_temp: float) -> dict:
                           nxt=torch.empty((K,), dtype=torch.long, device=dev), mar=torch.empty((K,), dtype=F32, device=dev),
                           pmx=torch.empty((K,), dtype=F32, device=dev), drec=torch.zeros((3 * K + 1,), dtype=F32, device=dev),
                           top_p=torch.zeros((1,), dtype=F32, device=dev), live1=torch.ones((1,), dtype=torch.int32, device=dev))
+        if tail is not None:
+            drec = torch.zeros((4 * K + 1 + (ops.SCORE_ROWS * K if tail[2] else 0),), dtype=F32, device=dev)
+            views[key].update(kept=torch.zeros((K,), dtype=torch.int32, device=dev), drec=drec, arec=drec[:4 * K + 1],
+                              sc=drec[4 * K + 1:].view(ops.SCORE_ROWS, K) if tail[2] else None,
+                              full=torch.full((1,), K, dtype=torch.int32, device=dev),
+                              ngs=torch.full((1,), K - 1, dtype=torch.int32, device=dev))
     return views[key]
 
 
-def _draft_refusals(B: int, dev_sample: bool, penalty: bool, return_scores: bool, draft_k) -> int:
-    """The arguments draft decoding does not take; returns K."""
+def _draft_refusals(B: int, dev_sample: bool, penalty: bool, return_scores: bool, draft_k, tail: bool = False) -> int:
+    """The arguments draft decoding does not take; returns K.  `tail`: the caller's `draft_sampling` switch, behind which the
+    verify step runs the sampler, the penalty and the scores per row (_draft_core)."""
     K = int(draft_k)
     if not 1 <= K <= ops.DRAFT_MAX_K:
         raise ValueError(f"draft_k={draft_k}: 1 to {ops.DRAFT_MAX_K} rows per verify step")
-    for on, what in ((B != 1, f"batch size {B} (one sequence only)"), (dev_sample, "device sampling"),
-                     (penalty, "repetition_penalty != 1"), (return_scores, "return_scores")):
+    for on, what in ((B != 1, f"batch size {B} (one sequence only)"), (dev_sample and not tail, "device sampling"),
+                     (penalty and not tail, "repetition_penalty != 1"), (return_scores and not tail, "return_scores")):
         if on:
             raise NotImplementedError(f"draft decoding with {what} is not implemented")
     return K
@@ -567,12 +588,14 @@ class LlamaDecode:
         verify decoding (_draft_core).  Steps past `min_length` feed the last token and K - 1 guessed tokens as K rows of one token
         step and keep the guesses the arg-max confirms plus the one token the step produces anyway.  Every row of that step has the
         bits of the one-row step at its position, so ids and margins are those of the call without `draft`, whatever the drafter
-        proposes; it only decides how many passes over the weights the answer takes.  NotImplementedError with B > 1, device
-        sampling, `repetition_penalty` != 1 or `return_scores`."""
+        proposes; it only decides how many passes over the weights the answer takes.  NotImplementedError with B > 1, and -- unless
+        `draft_sampling` (MYRIAD_DRAFT_SAMPLING=1, off by default) is on -- with device sampling, `repetition_penalty` != 1 or
+        `return_scores`.  With it on the verify step draws, penalises and scores every row as the plain step would at that row's
+        token index (_draft_core), so the sampled, penalised or scored answer is again that of the call without `draft`."""
         B, S0, _ = inputs_embeds.shape
         inv_temp, _, dev_sample, penalty = _sampling_args(self, do_sample, temperature, top_k, repetition_penalty)
         ops.score_watch_ids(watch_ids if return_scores else (), self.V)
-        K = 0 if draft is None else _draft_refusals(B, dev_sample, penalty, bool(return_scores), draft_k)
+        K = 0 if draft is None else _draft_refusals(B, dev_sample, penalty, bool(return_scores), draft_k, self.draft_sampling)
         if K and S0 + max_new_tokens + K > self.cos.shape[0]:        # a verify step rotates K rows past the last fed position
             raise ValueError(f"context {S0} + max_new_tokens {max_new_tokens} + draft_k {K} passes the rotary table "
                              f"({self.cos.shape[0]} positions)")
@@ -593,9 +616,10 @@ class LlamaDecode:
         B, S0, _ = inputs_embeds.shape
         inv_temp, top_k, dev_sample, penalty = _sampling_args(self, do_sample, temperature, top_k, repetition_penalty)
         if draft is not None:
-            K = _draft_refusals(B, dev_sample, penalty, bool(return_scores), draft_k)
+            K = _draft_refusals(B, dev_sample, penalty, bool(return_scores), draft_k, self.draft_sampling)
             return self._draft_core(inputs_embeds, ws, past, weight_stats, draft, K, max_new_tokens, stop_ids, eos_id, min_length,
-                                    return_margins, use_graph, do_sample, top_p, inv_temp, top_k, generator)
+                                    return_margins, use_graph, do_sample, top_p, inv_temp, top_k, generator, dev_sample,
+                                    repetition_penalty if penalty else None, watch_ids if return_scores else None)
         out_ids, margins = [], []
         unfinished = torch.ones(B, dtype=torch.long)
         stats = dict(steps=0, sampled_rows=0, min_pmax=1.0, device_sampled_rows=0, host_sampled_rows=0, graph_replays=0, **weight_stats)
@@ -704,7 +728,7 @@ class LlamaDecode:
 
     def _draft_core(self, inputs_embeds: torch.Tensor, ws: dict, past: int, weight_stats: dict, draft, K: int, max_new_tokens: int,
                     stop_ids, eos_id: int, min_length: int, return_margins: bool, use_graph: bool, do_sample: bool, top_p: float,
-                    inv_temp: float, top_k: int, generator):
+                    inv_temp: float, top_k: int, generator, dev_sample: bool = False, repetition_penalty=None, watch_ids=None):
         """_greedy_core for one sequence with draft-and-verify steps (greedy_generate(draft=...)).  The prefill and its first pick
         are _greedy_core's.  Then decode_host.DraftLoop chooses each step: while the EOS ban is on, or when the drafter proposes
         nothing, the plain one-row step of `ws`; otherwise the host writes the K - 1 guesses (id 0 as filler) behind the fed token
@@ -714,6 +738,15 @@ class LlamaDecode:
         advance the same caches, pos, kvlen, ids_k[0] and step, each from a graph of its own; a row of the verify step has the bits
         of the plain step at its position, so switching is free and the answer is the plain loop's.  Per step the host makes one
         device->host copy (the record) and at most one small host->device copy (the guesses, with a host-drawn id in front).
+
+        `dev_sample`, `repetition_penalty` (None: off) and `watch_ids` (None: no scores), behind `draft_sampling`: the verify step
+        runs the decode slots' per-row tail at G = 1 instead (draft_sample.hip) -- mh_repetition_penalty_draft_rows,
+        mh_sample_rows_draft with the device sampler (else mh_argmax_pmax_rows: the loop drafts only past min_length),
+        mh_token_scores_rows over the K rows, mh_draft_accept_sampled_rows -- and the plain step is _greedy_core's, except with the
+        device sampler: _greedy_core's sampled step counts launches in `step`, so both steps of this call take the slot form and
+        count tokens in `gen` (mh_sample_rows_slots at one row, Philox counter (t, 0, 0, 0): the draw of the solo step for token
+        t).  Row j of the verify step draws token gen + j itself, so a guess stands iff it equals the draw and the answer is the
+        sampled answer of the call without `draft`.
 
         The verify step is off for the whole call, and last_generate_stats["draft_off"] says why, when `ws` runs the split-KV
         attention ("split_kv") or mh_attn_decode_rope_draft does not take the shape ("unsupported").  Stats: verify_steps,
@@ -726,25 +759,59 @@ class LlamaDecode:
         stats = dict(steps=0, sampled_rows=0, min_pmax=1.0, device_sampled_rows=0, host_sampled_rows=0, graph_replays=0,
                      verify_graph_replays=0, plain_graph_replays=0, draft_k=K, draft_off=None, **weight_stats)
         self.last_generate_stats = stats
+        penalty, scores = repetition_penalty is not None, watch_ids is not None
+        tail = (dev_sample, penalty, scores) if dev_sample or penalty or scores else None
         loop = DraftLoop(draft, K, max_new_tokens, stop_ids, eos_id, min_length, do_sample, top_p, stats)
         if ws["split"] is not None:
             stats["draft_off"] = "split_kv"
         elif not ops.attn_decode_draft_supported(self.H, self.hd, K, ws["T"]):
             stats["draft_off"] = "unsupported"
         loop.use_draft = stats["draft_off"] is None
-        dv = _draft_view(self, ws, K, inv_temp) if loop.use_draft else None
-        rec, ids_k, fresh = ws["rec"][:3], ws["ids_k"], [True]
+        dv = _draft_view(self, ws, K, inv_temp, tail) if loop.use_draft or dev_sample else None
+        pv = dv["draft_views"]["plain_rows", penalty, scores] if dev_sample else ws      # the view of the call's plain step
+        rec = ws["rec"] if scores else ws["rec"][:4 if dev_sample else 3]
+        ids_k, fresh, sc_rows = ws["ids_k"], [True], []
+        if scores:
+            watch = ops.score_watch_table(watch_ids, self.V)
+            if ws["rec"].shape[0] != 4 + ops.SCORE_ROWS:
+                raise ValueError("return_scores needs a workspace whose record holds the score rows")
+            ws["watch"].copy_(watch)
+            W = int((watch >= 0).sum())
+        if dev_sample or penalty:                                    # _greedy_core's: the knobs, an empty seen set, one seed per call
+            ws["prm"].copy_(torch.tensor([inv_temp, top_p, float(top_k), float(repetition_penalty or 1.0)], dtype=F32))
+            ws["seen"].zero_()
+        if dev_sample:
+            ws["seed"].fill_(int(torch.randint(0, 2**63 - 1, (1,), generator=generator)))
+            ws["prm6"].copy_(torch.tensor([inv_temp, top_p, float(top_k), float(repetition_penalty or 1.0), float(min_length),
+                                           float(eos_id)], dtype=F32))
 
         def draw_from(logits, ban):
             return lambda j: _host_draw(logits()[j], ban, inv_temp, top_k, top_p, generator)
 
+        def take(record, logits, first=False):
+            """A step's record (ids, margins, pmax, n_out, draw, kept, score rows) into the loop; with scores every token the loop
+            emitted takes its entries -- a token the host drew instead x[id] - lse from the row the draw read, as _greedy_core."""
+            n0, sc = len(loop.ids), record[6]
+            loop.take(*record[:5], first=first, kept=record[5])
+            for j, tok in enumerate(loop.ids[n0:] if scores else ()):
+                lp = sc[1][j] if tok == record[0][j] else float(logits()[j, tok].cpu() - torch.tensor(sc[0][j], dtype=F32))
+                sc_rows.append([lp] + [sc[2 + w][j] for w in range(W)])
+
         logits0 = self._prefill(inputs_embeds, ws["caches"], past)
         ban0 = eos_id if 0 < min_length else -1
-        ops.argmax_pmax_rows(logits0, ws["nxt"], ws["mar"], ws["pmx"], ban_id=ban0, inv_temp=inv_temp)
-        first = (ws["nxt"].cpu().tolist(), ws["mar"].cpu().tolist(), ws["pmx"].cpu().tolist(), 1, draw_from(lambda: logits0, ban0))
+        if dev_sample:                                               # the prefill pick is Philox step t = 0
+            ops.sample_rows(logits0, ws["nxt"], ws["mar"], ws["pmx"], ws["kept"], ws["prm"], ws["seed"], ban_id=ban0, t_add=0)
+        else:
+            ops.argmax_pmax_rows(logits0, ws["nxt"], ws["mar"], ws["pmx"], ban_id=ban0, inv_temp=inv_temp)
+        if scores:
+            ops.token_scores_rows(logits0, ws["nxt"], ws["watch"], ws["rec"][4:])
+        first = (ws["nxt"].cpu().tolist(), ws["mar"].cpu().tolist(), ws["pmx"].cpu().tolist(), 1, draw_from(lambda: logits0, ban0),
+                 ws["kept"].cpu().tolist() if dev_sample else None, ws["rec"][4:].cpu().tolist() if scores else None)
         ws["pos"].fill_(S0)                                          # position of the incoming token
         ws["kvlen"].fill_(S0 + 1)                                    # valid keys after the append
         ws["step"].zero_()
+        if tail is not None:
+            ws["gen"].fill_(1)                                       # the prefill pick was token 0
         if dv is not None:
             dv["top_p"].fill_(float(top_p) if do_sample else 0.0)    # <= 0: no row needs a draw
 
@@ -764,30 +831,66 @@ class LlamaDecode:
 
         def plain_token_step(ban):
             self._step_logits(ws)
-            ops.argmax_pmax_rows(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ban_id=ban, inv_temp=inv_temp)
-            ops.decode_advance(ws["nxt"], ws["mar"], ws["pmx"], rec, ws["ids"], ws["step"], ws["pos"], ws["kvlen"])
+            if penalty:                                              # ws["ids"] = the token fed in: it joins the seen set first
+                ops.repetition_penalty_rows(ws["logits"], ws["seen"], ws["ids"], ws["prm"][3:])
+            if dev_sample:                                           # the slot form at one row: token gen draws Philox step gen, and
+                ops.sample_rows_slots(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ws["kept"], ws["prm6"], ws["seed"], ws["gen"])
+            else:                                                    # the ban is gen < min_length (the launch's `ban` is unused)
+                ops.argmax_pmax_rows(ws["logits"], ws["nxt"], ws["mar"], ws["pmx"], ban_id=ban, inv_temp=inv_temp)
+            if scores:
+                ops.token_scores_rows(ws["logits"], ws["nxt"], ws["watch"], ws["rec"][4:])
+            if dev_sample:
+                ops.decode_advance_kept_rows(ws["nxt"], ws["mar"], ws["pmx"], ws["kept"], rec, ws["ids"], ws["step"], ws["pos"],
+                                             ws["kvlen"], ws["gen"], pv["live1"])
+            else:
+                ops.decode_advance(ws["nxt"], ws["mar"], ws["pmx"], rec, ws["ids"], ws["step"], ws["pos"], ws["kvlen"])
 
         def verify_token_step(_ban):
             self._step_logits(dv)
-            ops.argmax_pmax_rows(dv["logits"], dv["nxt"], dv["mar"], dv["pmx"], ban_id=-1, inv_temp=inv_temp)
-            ops.draft_accept(dv["nxt"], dv["mar"], dv["pmx"], dv["ids"], dv["top_p"], dv["drec"], ws["pos"], ws["kvlen"], ws["step"], K)
+            if tail is None:
+                ops.argmax_pmax_rows(dv["logits"], dv["nxt"], dv["mar"], dv["pmx"], ban_id=-1, inv_temp=inv_temp)
+                ops.draft_accept(dv["nxt"], dv["mar"], dv["pmx"], dv["ids"], dv["top_p"], dv["drec"], ws["pos"], ws["kvlen"], ws["step"], K)
+                return
+            if penalty:                                              # row j: the seen set plus the ids fed in rows 0 .. j
+                ops.repetition_penalty_draft_rows(dv["logits"], ws["seen"], dv["ids"], dv["full"], dv["live1"], ws["prm"][3:], K)
+            if dev_sample:                                           # row j draws Philox step gen + j
+                ops.sample_rows_draft(dv["logits"], dv["nxt"], dv["mar"], dv["pmx"], dv["kept"], ws["prm6"], ws["seed"], ws["gen"],
+                                      dv["full"], dv["live1"], K, True)
+            else:
+                ops.argmax_pmax_rows(dv["logits"], dv["nxt"], dv["mar"], dv["pmx"], ban_id=-1, inv_temp=inv_temp)
+            if scores:
+                ops.token_scores_rows(dv["logits"], dv["nxt"], ws["watch"], dv["sc"])
+            ops.draft_accept_sampled_rows(dv["nxt"], dv["mar"], dv["pmx"], dv["kept"] if dev_sample else None, dv["ids"], ws["ids"],
+                                          dv["ngs"], dv["live1"], dv["top_p"], ws["seen"] if penalty else None, dv["arec"], ws["pos"],
+                                          ws["kvlen"], ws["gen"], ws["step"], K, self.V)
 
         def plain_step(ban, fed):
             feed(fed)
-            launch(ws, plain_token_step, ban, "plain_graph_replays")
+            launch(pv, plain_token_step, -1 if dev_sample else ban, "plain_graph_replays")
             r = rec.cpu()                                            # the one device->host copy of the step (it also waits for it)
-            return r[0].long().tolist(), r[1].tolist(), r[2].tolist(), 1, draw_from(lambda: ws["logits"], ban)
+            return (r[0].long().tolist(), r[1].tolist(), r[2].tolist(), 1, draw_from(lambda: ws["logits"], ban),
+                    r[3].tolist() if dev_sample else None, r[4:].tolist() if scores else None), lambda: ws["logits"]
 
         def verify_step(guesses, fed):
             feed(fed, guesses)
             launch(dv, verify_token_step, -1, "verify_graph_replays")
             r = dv["drec"].cpu()
-            return (r[:K].long().tolist(), r[K:2 * K].tolist(), r[2 * K:3 * K].tolist(), int(r[3 * K]),
-                    draw_from(lambda: dv["logits"], -1))
+            out = (r[:K].long().tolist(), r[K:2 * K].tolist(), r[2 * K:3 * K].tolist())
+            if tail is None:
+                return out + (int(r[3 * K]), draw_from(lambda: dv["logits"], -1), None, None), lambda: dv["logits"]
+            return out + (int(r[4 * K]), draw_from(lambda: dv["logits"], -1), r[3 * K:4 * K].tolist() if dev_sample else None,
+                          r[4 * K + 1:].view(ops.SCORE_ROWS, K).tolist() if scores else None), lambda: dv["logits"]
 
-        run_draft_loop(loop, first, plain_step, verify_step)
+        take(first, lambda: logits0, first=True)
+        while not loop.done:
+            g = loop.guesses()
+            take(*(verify_step(g, loop.fed) if g else plain_step(loop.ban(), loop.fed)))
         ids = torch.tensor([loop.ids], dtype=torch.long)
-        return (ids, torch.tensor([loop.margins], dtype=F32)) if return_margins else ids
+        out = (ids, torch.tensor([loop.margins], dtype=F32)) if return_margins else (ids,)
+        if scores:
+            sc = torch.tensor(sc_rows, dtype=torch.float64).to(F32).view(1, len(loop.ids), 1 + W)
+            out += (dict(token_logprobs=sc[:, :, 0].contiguous(), watch_logprobs=sc[:, :, 1:].contiguous()),)
+        return out if len(out) > 1 else ids
 
     @torch.no_grad()
     def beam_generate(self, inputs_embeds: torch.Tensor, num_beams: int, max_new_tokens: int = 90, stop_ids=(), eos_id: int = 2,
@@ -1037,7 +1140,8 @@ class DecodeSession:
             inv_temp, _, dev_sample, penalty = _sampling_args(L, **kw)
             scores = bool(kw.get("return_scores", False))
             ops.score_watch_ids(kw.get("watch_ids", ()) if scores else (), L.V)
-            draft_k = 0 if kw.get("draft") is None else _draft_refusals(B, dev_sample, penalty, scores, kw.get("draft_k", 4))
+            draft_k = 0 if kw.get("draft") is None else _draft_refusals(B, dev_sample, penalty, scores, kw.get("draft_k", 4),
+                                                                                L.draft_sampling)
             weight_stats = L._prepare_decode_weights(B)              # packed before the stamp, which names the packed copies
             ws, past = self._begin_turn([list(k) for k in keys], weights_version, reset_reason, B, S0, max_new_tokens, inv_temp,
                                         dev_sample, penalty, scores, draft_k)
@@ -1116,7 +1220,9 @@ class SlotDecoder:
     buffers in `draft_views` (_draft_workspace, its own graph) runs the token step at slots * K rows, K consecutive tokens per
     slot -- mh_attn_decode_rope_draft_rows, mh_argmax_pmax_rows, mh_draft_accept_rows -- whenever a live slot has a guess, and
     the plain step otherwise; a request's ids and margins are exactly those of the run without `draft`.  No key of `views`
-    changes.  See `run`."""
+    changes.  Behind `LlamaHIP.draft_sampling` (MYRIAD_DRAFT_SAMPLING=1) the verify step also runs the per-row tail and the
+    token scores (mh_repetition_penalty_draft_rows, mh_sample_rows_draft, mh_token_scores_rows, mh_draft_accept_sampled_rows)
+    on `seen`, `gen` and `seed` shared with the plain step.  See `run`."""
 
     def __init__(self, llama: "LlamaHIP", slots: int, capacity: int, split_kv: Optional[bool] = False):
         slots = int(slots)
@@ -1232,16 +1338,23 @@ class SlotDecoder:
         self.ws = self.views[key]
         return self.ws
 
-    def _draft_workspace(self, K: int, inv_temp: float) -> dict:
+    def _draft_workspace(self, K: int, inv_temp: float, tail=None) -> dict:
         """The verify step's view of the buffers (run(draft=...)): slots x K rows, K consecutive tokens per slot, with a graph of
         its own, one per (K, inv_temp) -- the arg-max launch bakes inv_temp in.  It shares the caches, `pos`, `kvlen`, `live`,
         `step` and the plain step's fed ids (`next_ids`, what mh_draft_accept_rows also writes its kept pick to) with the plain
         views, so the host switches between the two steps from one launch to the next.  Its own: the fed ids `ids` [slots * K]
         (per slot the last token, its real guesses, id 0 as filler), `x_in`, `logits`, `nxt` / `mar` / `pmx`, the counts `cnt`
         [2, slots] = (`nguess`, `nrow`), the [slots, 3K + 1] record `drec` and the device float `top_p`.  No key of `views`
-        changes."""
+        changes.
+
+        `tail` = (device-sampled, penalty, rows_tail, scores), behind `draft_sampling`: the view of the verify step with the
+        per-row tail (_SlotRun.verify_token_step), keyed (K, inv_temp) + tail beside the plain verify view's (K, inv_temp).  It
+        reads the `prm`, `seed`, `gen`, `seen` and `watch` the call's plain view already put into the set (without the per-row
+        tail `gen` is a counter nobody reads), holds `kept` [slots * K], and its record `drec` is one flat buffer -- slots x (4K
+        + 1) floats of mh_draft_accept_sampled_rows (`arec`), then with scores SCORE_ROWS rows of slots * K floats (`sc`) -- so
+        the step still makes one device->host copy."""
         L, bufs = self.llama, self._base_buffers()
-        key = (int(K), float(inv_temp))
+        key = (int(K), float(inv_temp)) + (() if tail is None else tuple(bool(t) for t in tail))
         if key not in self.draft_views:
             if len(self.draft_views) >= 4:                           # a few (K, temperature) pairs at most: drop the oldest graph
                 self.draft_views.pop(next(iter(self.draft_views)))
@@ -1254,6 +1367,13 @@ class SlotDecoder:
                         pmx=torch.empty((R,), dtype=F32, device=dev), cnt=cnt, nguess=cnt[0], nrow=cnt[1],
                         drec=torch.zeros((self.slots, 3 * int(K) + 1), dtype=F32, device=dev),
                         top_p=torch.zeros((1,), dtype=F32, device=dev))
+            if tail is not None:
+                n_acc = self.slots * (4 * int(K) + 1)
+                drec = torch.zeros((n_acc + (ops.SCORE_ROWS * R if tail[3] else 0),), dtype=F32, device=dev)
+                view.update(kept=torch.zeros((R,), dtype=torch.int32, device=dev), drec=drec, arec=drec[:n_acc],
+                            sc=drec[n_acc:].view(ops.SCORE_ROWS, R) if tail[3] else None)
+                if not tail[2]:
+                    view["gen"] = torch.zeros((self.slots,), dtype=torch.int32, device=dev)
             self.draft_views[key] = view
         return self.draft_views[key]
 
@@ -1305,9 +1425,19 @@ class SlotDecoder:
         and is drawn on the host from its row of the verify logits.  K = 1 runs plain steps only; so does a call on the split-KV
         view or with a shape mh_attn_decode_rope_draft refuses, and `last_stats["draft_off"]` says "split_kv" / "unsupported".
         `last_stats` gains draft_k, draft_off, verify_steps, plain_steps, draft_proposed, draft_accepted, emitted,
-        verify_graph_replays and plain_graph_replays.  The caller teaches the drafter.  NotImplementedError with device sampling,
-        repetition_penalty != 1, min_length > 1, return_scores and num_beams > 1; ValueError for K outside 1 .. DRAFT_MAX_K or
-        slots * K above GEMV_WIDE_MAX_ROWS."""
+        verify_graph_replays and plain_graph_replays.  The caller teaches the drafter.  NotImplementedError with num_beams > 1
+        and -- unless `draft_sampling` (MYRIAD_DRAFT_SAMPLING=1, off by default) is on -- with device sampling, repetition_penalty
+        != 1, min_length > 1 and return_scores; ValueError for K outside 1 .. DRAFT_MAX_K or slots * K above GEMV_WIDE_MAX_ROWS.
+
+        With `draft_sampling` on, those four run in the verify step too (a view and a graph of their own; a call without them
+        replays the graphs it always did): after the layers, mh_repetition_penalty_draft_rows (row j of slot g is penalised on
+        seen[g] plus the ids fed in its rows 0 .. j), mh_sample_rows_draft (row j draws Philox step gen[g] + j of seed[g] and bans
+        EOS iff gen[g] + j < min_length; without the device sampler the same launch picks the arg-max), mh_token_scores_rows over
+        the slots * K rows into the step's record, and mh_draft_accept_sampled_rows, which ends a window at a row the host must
+        draw (kept < 0, or p_max < top_p on the host-draw path), adds the tokens that stood to seen[g] and moves gen[g].  A draw
+        depends on (logits row, seed, token index) only, so a guess stands iff it equals the draw: ids, margins, sampled-row
+        counts and scores are bit for bit those of the run without `draft`.  Both graphs share seen, gen, seed, the caches and
+        the counters; a row the host must draw is drawn as the plain step draws that token of that request."""
         self.sessions.clear()                                        # the slots' caches are overwritten from row 0
         if draft is not None and int(num_beams) != 1:
             raise NotImplementedError(f"decode slots: draft decoding with num_beams={num_beams} is not implemented")
@@ -1592,8 +1722,10 @@ class SlotDecoder:
         if self.slots * K > ops.GEMV_WIDE_MAX_ROWS:
             raise ValueError(f"slots={self.slots} x draft_k={K}: the verify step runs the packed token step, at most "
                              f"{ops.GEMV_WIDE_MAX_ROWS} rows")
-        for on, what in ((dev_sample, "device sampling"), (penalty, "repetition_penalty != 1"), (int(min_length) > 1, "min_length > 1"),
-                         (scores, "return_scores"), (turns is not None, "run_turns / ChatPool")):
+        bare = not getattr(self.llama, "draft_sampling", False)      # behind that switch the verify step runs the per-row tail
+        for on, what in ((bare and dev_sample, "device sampling"), (bare and penalty, "repetition_penalty != 1"),
+                         (bare and int(min_length) > 1, "min_length > 1"), (bare and scores, "return_scores"),
+                         (turns is not None, "run_turns / ChatPool")):
             if on:
                 raise NotImplementedError(f"decode slots: draft decoding with {what} is not implemented")
         return K
@@ -1652,7 +1784,9 @@ class SlotDecoder:
             if not split and not ops.attn_decode_draft_supported(L.H, L.hd, K, self.T_cap):
                 stats["draft_off"] = "unsupported"
             if K > 1 and stats["draft_off"] is None:
-                dv = run.dv = self._draft_workspace(K, inv_temp)
+                # the per-row tail, the scores: the verify step of draft_sampling; else exactly the launches it had before
+                dv_tail = (dev_sample, penalty, rows_tail, scores) if rows_tail or scores else None
+                dv = run.dv = self._draft_workspace(K, inv_temp, dv_tail)
                 # the host draws where p_max (f32) < top_p (a double): the device holds the smallest f32 >= top_p, so its
                 # p_max >= *top_p is that test's negation for every f32 p_max; <= 0: no row needs a draw
                 dv["top_p"].copy_(torch.from_numpy(np.array([f32_at_least(top_p) if do_sample else 0.0], dtype=np.float32)))
@@ -1738,10 +1872,27 @@ class _SlotRun:
     def verify_token_step(self, _ban):
         """The verify step of draft decoding (SlotDecoder._draft_workspace): slots x K rows, K consecutive tokens per slot."""
         dv = self.dv
+        K = dv["draft_k"]
         self.L._step_logits(dv)
-        ops.argmax_pmax_rows(dv["logits"], dv["nxt"], dv["mar"], dv["pmx"], ban_id=-1, inv_temp=self.inv_temp)
-        ops.draft_accept_rows(dv["nxt"], dv["mar"], dv["pmx"], dv["ids"], dv["next_ids"], dv["nguess"], dv["live"], dv["top_p"],
-                              dv["drec"], dv["pos"], dv["kvlen"], dv["step"], dv["draft_k"])
+        if "arec" not in dv:                                         # no per-row tail, no scores: the launches of the greedy verify step
+            ops.argmax_pmax_rows(dv["logits"], dv["nxt"], dv["mar"], dv["pmx"], ban_id=-1, inv_temp=self.inv_temp)
+            ops.draft_accept_rows(dv["nxt"], dv["mar"], dv["pmx"], dv["ids"], dv["next_ids"], dv["nguess"], dv["live"], dv["top_p"],
+                                  dv["drec"], dv["pos"], dv["kvlen"], dv["step"], K)
+            return
+        # row (g, j) is the plain step's row g at token gen[g] + j: its seen set is seen[g] + the ids fed in rows 0 .. j, its draw
+        # Philox step gen[g] + j of seed[g], its ban the one of that token index
+        if self.penalty:
+            ops.repetition_penalty_draft_rows(dv["logits"], dv["seen"], dv["ids"], dv["nrow"], dv["live"], dv["prm"][3:], K)
+        if self.rows_tail:
+            ops.sample_rows_draft(dv["logits"], dv["nxt"], dv["mar"], dv["pmx"], dv["kept"], dv["prm"],
+                                  dv["seed"] if self.dev_sample else None, dv["gen"], dv["nrow"], dv["live"], K, self.dev_sample)
+        else:
+            ops.argmax_pmax_rows(dv["logits"], dv["nxt"], dv["mar"], dv["pmx"], ban_id=-1, inv_temp=self.inv_temp)
+        if self.scores:                                              # after the penalty and the pick; an idle row's id is -1: zeros
+            ops.token_scores_rows(dv["logits"], dv["nxt"], dv["watch"], dv["sc"])
+        ops.draft_accept_sampled_rows(dv["nxt"], dv["mar"], dv["pmx"], dv["kept"] if self.dev_sample else None, dv["ids"],
+                                      dv["next_ids"], dv["nguess"], dv["live"], dv["top_p"], dv["seen"] if self.penalty else None,
+                                      dv["arec"], dv["pos"], dv["kvlen"], dv["gen"], dv["step"], K, self.L.V)
 
     def verify_step(self, live, guesses) -> list:
         """One verify step for the `live` slots with their real `guesses`: two host->device copies (per slot the fed token, its
@@ -1763,19 +1914,31 @@ class _SlotRun:
         stats["verify_steps"] += 1
         stats["verify_graph_replays"] += stats["graph_replays"] - replays
         stats["draft_proposed"] += sum(len(guesses[s]) for s in live)
-        r = dv["drec"].cpu().tolist()                                # the one device->host copy of the step (it also waits for it)
+        r = dv["drec"].cpu()                                         # the one device->host copy of the step (it also waits for it)
+        tail, sc = "arec" in dv, None
+        if tail:                                                     # (4K + 1) floats per slot, then the score rows
+            n_acc = S * (4 * K + 1)
+            r, sc = r[:n_acc].view(S, 4 * K + 1).tolist(), r[n_acc:].view(ops.SCORE_ROWS, S * K).tolist() if self.scores else None
+        else:
+            r = r.tolist()
         windows, drawn = {}, {}
         for s in live:
-            n = int(r[s][3 * K])
+            n = int(r[s][-1])
             if not 1 <= n <= cnt[1][s]:
                 raise RuntimeError(f"verify step: slot {s} kept {n} of {cnt[1][s]} rows")
             hist, ids = list(sched.rows[s][1]), []
             for j in range(n):                                       # token by token, so no draw is made past the request's end
                 tok = int(r[s][j])
-                if self.do_sample and r[s][2 * K + j] < self.top_p:  # greedy_generate's rule per row: below top_p the host draws
+                if self.dev_sample and r[s][3 * K + j] >= 0:
+                    stats["device_sampled_rows"] += 1                # drawn by the step itself
+                elif self.do_sample and (self.dev_sample or r[s][2 * K + j] < self.top_p):
+                    # the plain step's rule per row: the sampler handed the row back, or p_max is below top_p -- the host draws
                     if j != n - 1:
                         raise RuntimeError("a row that needs a host draw must end its window")
-                    tok = drawn[s] = self.host_draw(dv["logits"][s * K + j], len(hist), None)
+                    tok = drawn[s] = self.host_draw(dv["logits"][s * K + j], len(hist), self.seed_of.get(s))
+                if sc is not None:
+                    self.sc_of[sched.rows[s][0]].append(self.score_entry([row[s * K + j] for row in sc], tok != int(r[s][j]),
+                                                                         dv["logits"][s * K + j], tok))
                 ids.append(tok)
                 hist.append(tok)
                 if sched._ended(hist):

@@ -709,16 +709,17 @@ def slot_guesses(sched: "SlotScheduler", drafter, k: int) -> dict:
 
 
 def replay_slot_run(lengths, ids, slots: int, max_new_tokens: int, stop_ids=(), eos_id: int = 2, prefill_batch: int = 1,
-                    prefill_rows: int = 2048, refill_min: int = 1, draft=None, draft_k: int = 4) -> dict:
+                    prefill_rows: int = 2048, refill_min: int = 1, draft=None, draft_k: int = 4, host_drawn=None) -> dict:
     """The counters of a slot run whose picks are known: request i has a prompt of lengths[i] rows and generates ids[i] (which must
     end where the stop rule ends it).  SlotScheduler + RefillPlanner driven as SlotDecoder.run drives them, without a device.
     With `draft` (a drafter nobody teaches during the run) and `draft_k` = K the run is SlotDecoder.run(draft=, draft_k=)'s with no
     host draw: every step takes slot_guesses' guesses and is a verify step iff a live slot has one, a slot's window is its fed
     token's pick plus the leading guesses its known answer confirms, and the answer gains verify_steps, plain_steps, draft_proposed
-    (real guesses fed), draft_accepted (emitted tokens that were confirmed guesses) and emitted."""
+    (real guesses fed), draft_accepted (emitted tokens that were confirmed guesses) and emitted.  `host_drawn` (with `draft`):
+    per request the token indices the host drew; such a row ends its slot's window, whatever the guess behind it."""
     if draft is not None:
         return _replay_draft_slot_run(lengths, ids, slots, max_new_tokens, stop_ids, eos_id, prefill_batch, prefill_rows, refill_min,
-                                      draft, int(draft_k))
+                                      draft, int(draft_k), host_drawn)
     sched = SlotScheduler(slots, max_new_tokens, stop_ids, eos_id)
     plan = RefillPlanner(sched, range(len(lengths)), prefill_batch, prefill_rows, refill_min, length=lambda i: lengths[i])
     owner, prefills = [None] * slots, 0
@@ -743,8 +744,9 @@ def replay_slot_run(lengths, ids, slots: int, max_new_tokens: int, stop_ids=(), 
 
 
 def _replay_draft_slot_run(lengths, ids, slots, max_new_tokens, stop_ids, eos_id, prefill_batch, prefill_rows, refill_min, draft,
-                           K: int) -> dict:
+                           K: int, host_drawn=None) -> dict:
     """replay_slot_run with a drafter: see there."""
+    host_drawn = [set(h) for h in host_drawn] if host_drawn is not None else [()] * len(lengths)
     sched = SlotScheduler(slots, max_new_tokens, stop_ids, eos_id)
     plan = RefillPlanner(sched, range(len(lengths)), prefill_batch, prefill_rows, refill_min, length=lambda i: lengths[i])
     owner, prefills = [None] * slots, 0                              # per slot: its request
@@ -766,7 +768,8 @@ def _replay_draft_slot_run(lengths, ids, slots, max_new_tokens, stop_ids, eos_id
         for s in live:
             chain, n = ids[owner[s]], len(sched.rows[s][1])          # row j's pick is chain[n + j] while every earlier guess was right
             take = 1
-            while take <= len(guesses[s]) and n + take < len(chain) and guesses[s][take - 1] == chain[n + take - 1]:
+            while take <= len(guesses[s]) and n + take < len(chain) and n + take - 1 not in host_drawn[owner[s]] \
+                    and guesses[s][take - 1] == chain[n + take - 1]:
                 take += 1
             windows[s] = (chain[n:n + take], [0.0] * take)
         sched.step_windows(windows)
@@ -866,8 +869,10 @@ class DraftLoop:
         self.stats["draft_proposed"] += len(prop)
         return prop + [0] * (self.k - 1 - len(prop))
 
-    def take(self, ids, margins, pmax, n_out: int, draw=None, first: bool = False) -> None:
-        """One step's record.  `first`: the prefill's pick, which counts as neither kind of step."""
+    def take(self, ids, margins, pmax, n_out: int, draw=None, first: bool = False, kept=None) -> None:
+        """One step's record.  `first`: the prefill's pick, which counts as neither kind of step.  `kept` (the device sampler's
+        kept counts of the rows): the device drew every row but those with kept < 0, which the host draws -- the kept rule in
+        place of the p_max rule; such a row ended the window on the device."""
         n_out, rows = int(n_out), len(ids)
         if not 1 <= n_out <= rows:
             raise ValueError(f"n_out={n_out} of a {rows}-row record")
@@ -881,9 +886,12 @@ class DraftLoop:
             if self.do_sample:
                 self.stats["min_pmax"] = min(self.stats["min_pmax"], pm)
                 if pm < self.top_p:
+                    self.stats["sampled_rows"] += 1
+                if kept is not None and kept[j] >= 0:
+                    self.stats["device_sampled_rows"] = self.stats.get("device_sampled_rows", 0) + 1
+                elif kept is not None or pm < self.top_p:
                     if j != n_out - 1:
                         raise ValueError("a row that needs a host draw must end its window")
-                    self.stats["sampled_rows"] += 1
                     self.stats["host_sampled_rows"] += 1
                     tok = self.fed = int(draw(j))
             self.ids.append(tok)
@@ -906,10 +914,11 @@ def run_draft_loop(loop: DraftLoop, first, plain_step, verify_step) -> DraftLoop
     return loop
 
 
-def predict_draft_run(drafter, chain, k: int, min_length: int = 1) -> dict:
+def predict_draft_run(drafter, chain, k: int, min_length: int = 1, host_drawn=()) -> dict:
     """The step counts of decoding the answer `chain` (every emitted id, the prefill's pick first) with `drafter` at K = k rows
-    per verify step and no host draw: verify_steps, plain_steps, draft_proposed, draft_accepted, as DraftLoop counts them."""
-    chain = [int(t) for t in chain]
+    per verify step: verify_steps, plain_steps, draft_proposed, draft_accepted, as DraftLoop counts them.  `host_drawn`: the
+    token indices (places in `chain`) the host drew -- such a row ends its window, whatever the guess behind it."""
+    chain, host_drawn = [int(t) for t in chain], set(host_drawn)
     st = dict(verify_steps=0, plain_steps=0, draft_proposed=0, draft_accepted=0)
     n = 1
     while n < len(chain):
@@ -922,7 +931,7 @@ def predict_draft_run(drafter, chain, k: int, min_length: int = 1) -> dict:
         st["draft_proposed"] += len(prop)
         fed = prop + [0] * (k - 1 - len(prop))
         take = 1                                                     # row j's pick is chain[n + j] while every earlier guess was right
-        while take < k and n + take < len(chain) and fed[take - 1] == chain[n + take - 1]:
+        while take < k and n + take < len(chain) and n + take - 1 not in host_drawn and fed[take - 1] == chain[n + take - 1]:
             take += 1
         st["draft_accepted"] += take - 1
         n += take

@@ -122,6 +122,8 @@ class LlamaHIP(LlamaDecode):
         # draft-and-verify decoding in the decode slots (SlotDecoder.run(draft=...), generate_stream(draft=...), eval_aqa.py --slots
         # N --draft-k K); off by default: those entries refuse `draft` as before
         self.slot_draft = os.environ.get("MYRIAD_SLOT_DRAFT", "0") != "0"
+        # draft decoding under device sampling, the repetition penalty, min_length and the token scores (off by default)
+        self.draft_sampling = os.environ.get("MYRIAD_DRAFT_SAMPLING", "0") != "0"
         self.last_layer_rows = os.environ.get("MYRIAD_LAST_LAYER_ROWS", "1") != "0"
         # the packed token step streams FP8 (e4m3fn, one fp32 scale per output row) copies of the decoder matrices instead of
         # the bf16 ones (ops.gemv_pack_fp8; half the bytes, weight rounding the only new error); off by default, the attribute

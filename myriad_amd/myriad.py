@@ -1412,8 +1412,10 @@ class MyriadHIP(nn.Module):
         draft=<drafter> (opt-in; decode_host.NgramDrafter or any object with propose / observe) with draft_k = K in 1 .. 8 rows:
         draft-and-verify greedy decoding of ONE sample (LlamaHIP.greedy_generate): the same token_ids as without it, in fewer
         passes over the decoder weights when the drafter guesses well; last_generate_stats gains verify_steps, plain_steps,
-        draft_proposed and draft_accepted.  NotImplementedError with a batch of more than one sample, beams, device sampling,
-        repetition_penalty != 1 or output_scores.  The caller teaches the drafter (drafter.observe(ids))."""
+        draft_proposed and draft_accepted.  NotImplementedError with a batch of more than one sample and beams, and -- unless
+        `self.llama.draft_sampling` (MYRIAD_DRAFT_SAMPLING=1, off by default) is on -- with device sampling, repetition_penalty != 1
+        or output_scores; with it on the sampled, penalised or scored answer is that of the call without `draft`.  The caller
+        teaches the drafter (drafter.observe(ids))."""
         self.finish_update()
         a = self._generate_args(generate_kwargs)
         stops, max_new, max_len, do_sample, top_p, temperature = (a[k] for k in ("stops", "max_new", "max_len", "do_sample", "top_p",
@@ -1570,8 +1572,9 @@ class MyriadHIP(nn.Module):
         MYRIAD_SLOT_DRAFT=1, off by default, is on): draft-and-verify decoding in the slots
         (SlotDecoder.run): the same token_ids as the call without them, in fewer passes over the decoder weights when the drafter
         guesses well.  `last_generate_stats` then also holds draft_k, draft_off, verify_steps, plain_steps, draft_proposed,
-        draft_accepted, emitted, verify_graph_replays and plain_graph_replays.  Refused (NotImplementedError) with beams, device
-        sampling, repetition_penalty != 1, min_length > 1 and output_scores.  The caller teaches the drafter."""
+        draft_accepted, emitted, verify_graph_replays and plain_graph_replays.  Refused (NotImplementedError) with beams, and --
+        unless `self.llama.draft_sampling` (MYRIAD_DRAFT_SAMPLING=1, off by default) is on -- with device sampling,
+        repetition_penalty != 1, min_length > 1 and output_scores.  The caller teaches the drafter."""
         self.finish_update()
         a = self._generate_args(generate_kwargs)
         if a["draft"] is not None and not getattr(self.llama, "slot_draft", False):

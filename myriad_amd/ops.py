@@ -516,6 +516,97 @@ def draft_accept_rows(nxt, margin, pmax, ids_k, next_ids, nguess, live, top_p: t
                                          _p(rec), _p(pos), _p(kvlen), _p(step_dev), G, K, _s()), "mh_draft_accept_rows")
 
 
+def _draft_groups(name: str, K: int, rows: int, per_group, per_row=()):
+    """The checks the three draft_sample.hip wrappers share: G from `rows` = G * K, contiguous int32 [>= G] per-group state and
+    contiguous per-row buffers of G * K entries with their dtypes.  K outside 1 .. DRAFT_MAX_K goes to the launcher, which refuses
+    it with nothing launched."""
+    K = int(K)
+    G = rows // max(K, 1)
+    if K >= 1 and rows != G * K:
+        raise _lib.MyriadHipError(f"{name}: {rows} rows are not G groups of K = {K}")
+    for what, t in per_group:
+        if t.dtype != torch.int32 or t.numel() < G or not t.is_contiguous():
+            raise _lib.MyriadHipError(f"{name}: {what} must be a contiguous int32 [G]")
+    for what, t, dt in per_row:
+        if t is not None and (t.dtype != dt or t.numel() < rows or not t.is_contiguous()):
+            raise _lib.MyriadHipError(f"{name}: {what} must be a contiguous {dt} tensor of G*K entries")
+    return G, K
+
+
+def _draft_logits(name: str, logits: torch.Tensor):
+    if logits.dtype != F32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise _lib.MyriadHipError(f"{name}: logits must be f32 [G*K, V] with unit column stride")
+    return logits.shape
+
+
+def _draft_seen(name: str, seen, G: int, V: int):
+    if seen.dtype != torch.int32 or not seen.is_contiguous() or seen.numel() < G * ((V + 31) // 32):
+        raise _lib.MyriadHipError(f"{name}: seen must be a contiguous int32 [G, ceil(V / 32)] bitmap")
+
+
+def repetition_penalty_draft_rows(logits: torch.Tensor, seen: torch.Tensor, ids_k: torch.Tensor, nrow: torch.Tensor,
+                                  live: torch.Tensor, penalty: torch.Tensor, K: int):
+    """The repetition penalty on the rows of a verify step, in place on f32 logits [G*K, V]: row (g, j) with live[g] and j <
+    nrow[g] is penalised on every id of the bitmap seen[g] (int32 [G, ceil(V/32)], only read) and of ids_k[g*K .. g*K + j], each
+    once -- what repetition_penalty_rows_slots leaves on that row with the earlier fed ids in its bitmap.  Other rows are left
+    alone."""
+    name = "repetition_penalty_draft_rows"
+    R, V = _draft_logits(name, logits)
+    G, K = _draft_groups(name, K, R, (("nrow", nrow), ("live", live)), (("ids_k", ids_k, torch.long),))
+    _draft_seen(name, seen, G, V)
+    if penalty.dtype != F32 or penalty.numel() < 1:
+        raise _lib.MyriadHipError(f"{name}: penalty is a device f32 scalar")
+    _lib.check(_L().mh_repetition_penalty_draft_rows(_p(logits), logits.stride(0), _p(seen), _p(ids_k), _p(nrow), _p(live), G, K, V,
+                                                     _p(penalty), _s()), "mh_repetition_penalty_draft_rows")
+    return logits
+
+
+def sample_rows_draft(logits: torch.Tensor, out, margin_out, pmax_out, kept_out, params: torch.Tensor, seed, gen: torch.Tensor,
+                      nrow: torch.Tensor, live: torch.Tensor, K: int, draw: bool, u_out=None):
+    """sample_rows_slots (`draw`) / argmax_pmax_rows_slots (not `draw`) for the rows of a verify step: row (g, j) of f32 logits
+    [G*K, V] reads seed[g] (int64 [G]) and t = gen[g] + j, bans eos_id while t < min_length, and has the slot entry's bits on that
+    row alone at gen = t.  A row with live[g] == 0 or j >= nrow[g] gets out = -1, margin = p_max = 0, kept = 0.  Without the
+    draw kept_out, u_out and seed are not touched (they may be None)."""
+    name = "sample_rows_draft"
+    R, V = _draft_logits(name, logits)
+    G, K = _draft_groups(name, K, R, (("gen", gen), ("nrow", nrow), ("live", live)),
+                         (("out", out, torch.long), ("margin", margin_out, F32), ("pmax", pmax_out, F32),
+                          ("kept", kept_out, torch.int32), ("u_out", u_out, F32)))
+    if params.dtype != F32 or params.numel() < 6 or not params.is_contiguous():
+        raise _lib.MyriadHipError(f"{name}: params is f32 (inv_temp, top_p, top_k, penalty, min_length, eos_id)")
+    if draw and (kept_out is None or seed is None or seed.dtype != torch.long or seed.numel() < G or not seed.is_contiguous()):
+        raise _lib.MyriadHipError(f"{name}: the draw needs kept_out and a contiguous int64 seed [G]")
+    _lib.check(_L().mh_sample_rows_draft(_p(logits), logits.stride(0), _p(out), _p(margin_out), _p(pmax_out), _p(kept_out), _p(u_out),
+                                         G, K, V, _p(params), _p(seed), _p(gen), _p(nrow), _p(live), int(bool(draw)), _s()),
+               "mh_sample_rows_draft")
+    return out, kept_out
+
+
+def draft_accept_sampled_rows(nxt, margin, pmax, kept, ids_k, next_ids, nguess, live, top_p: torch.Tensor, seen, rec, pos, kvlen,
+                              gen, step_dev, K: int, V: int = 0):
+    """draft_accept_rows with the sampler's kept counts, the seen-id bitmap and the per-request token count: a row with kept[j] <
+    0 ends its group's chain (kept None: the p_max >= top_p rule); the fed token and the confirmed guesses join seen[g] (int32 [G,
+    ceil(V/32)], None: no bitmap); gen[g] += n_out.  rec[g] = (K ids, K margins, K p_max, K kept, n_out) as f32."""
+    name = "draft_accept_sampled_rows"
+    G, K = _draft_groups(name, K, nxt.numel(), (("nguess", nguess), ("live", live), ("pos", pos), ("kvlen", kvlen), ("gen", gen)),
+                         (("nxt", nxt, torch.long), ("margin", margin, F32), ("pmax", pmax, F32), ("kept", kept, torch.int32),
+                          ("ids_k", ids_k, torch.long)))
+    if next_ids.dtype != torch.long or next_ids.numel() < G or not next_ids.is_contiguous():
+        raise _lib.MyriadHipError(f"{name}: next_ids must be a contiguous int64 [G]")
+    if rec.dtype != F32 or not rec.is_contiguous() or rec.numel() < G * (4 * max(K, 0) + 1):
+        raise _lib.MyriadHipError(f"{name}: rec holds G*(4K+1) contiguous f32")
+    for what, t, dt in (("top_p", top_p, F32), ("step", step_dev, torch.int32)):
+        if t.dtype != dt or t.numel() < 1:
+            raise _lib.MyriadHipError(f"{name}: {what} must be a device {dt} scalar")
+    if seen is not None:
+        if int(V) < 1:
+            raise _lib.MyriadHipError(f"{name}: the bitmap needs V")
+        _draft_seen(name, seen, G, int(V))
+    _lib.check(_L().mh_draft_accept_sampled_rows(_p(nxt), _p(margin), _p(pmax), _p(kept), _p(ids_k), _p(next_ids), _p(nguess),
+                                                 _p(live), _p(top_p), _p(seen), _p(rec), _p(pos), _p(kvlen), _p(gen), _p(step_dev), G,
+                                                 K, int(V), _s()), "mh_draft_accept_sampled_rows")
+
+
 def _attn_prefill_ragged(sw: int, qkv2d, pos, seg, seg_host, cache, cos_tab, sin_tab, n_heads, head_dim, scale, out,
                          shared: bool = False):
     """attn_prefill_ragged (sw = 3 ints per segment), attn_prefill_ragged_past (sw = 4) and attn_prefill_ragged_shared (sw = 4,

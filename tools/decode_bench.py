@@ -52,7 +52,8 @@ of --repeats rounds; every guess is wrong, so each replay moves the position by 
 breaks even; then greedy_generate end to end on a prompt of --step-keys rows and a countdown chain of --new tokens with a drafter
 taught the chain, one whose guesses hold in every other window, and none -- the answer is asserted to be the chain each time.
 
---slots S[,S..] --draft-k K[,K..] [--weights ..] measures draft decoding in the decode slots for every (S, K) with S * K <= 64,
+--slots S[,S..] --draft-k K[,K..] [--weights ..] measures draft decoding in the decode slots for every (S, K) with S * K <= 64
+(with --sample --modes device, --penalty P and --scores also the verify and plain steps under the per-row tail, and the sampled runs),
 interleaved in one process, medians of --repeats rounds: the captured verify step at S * K rows against the plain step at S and at
 S * K slots (--step-keys keys, --step-replays replays per round) with the share of guesses kept at which it breaks even,
 (t_verify / t_plain - 1) / (K - 1); the draft-rows attention launch alone against mh_attn_decode_rope_rows at 256 and 1,024 keys;
@@ -174,7 +175,19 @@ if a.draft_k and slot_counts not in ([], [0]):
             step()
         return g_
 
-    decs, steps = {}, []                                             # (kind, S, K or 0, rows, graph, reset)
+    decs, steps, keep = {}, [], []                                   # (kind, S, K or 0, rows, graph, reset[, tail tag])
+    # the per-row tails to time beside the greedy steps: tag -> (device-sampled, penalty, scores)
+    from myriad_amd.decode import _SlotRun
+    dev_mode, inv_temp_t = a.sample and "device" in modes, 1.0 / a.temperature
+    tails = {}
+    if dev_mode:
+        tails["sampler"] = (True, False, False)
+    if dev_mode and a.penalty != 1.0:
+        tails["sampler+penalty"] = (True, True, False)
+    if a.scores:
+        tails["sampler+scores" if dev_mode else "scores"] = (dev_mode, False, True)
+    if tails:
+        L.device_sampling = L.draft_sampling = True
     for kind in wkinds:
         set_kind(kind)
         for S in dict.fromkeys([S for S, _ in pairs] + [S * K for S, K in pairs]):
@@ -212,8 +225,42 @@ if a.draft_k and slot_counts not in ([], [0]):
                                           dv["drec"], dv["pos"], dv["kvlen"], dv["step"], K)
                 vreset()
                 steps.append((kind, S, K, S * K, capture(verify), vreset))
+            # the same two steps under the per-row tail (--sample --modes device, --penalty P, --scores; behind draft_sampling): the
+            # engine's own _SlotRun.token_step / verify_token_step on its own views, so nothing is copied here
+            for tag, (dv_s, pen, sc) in tails.items():
+                if S not in [S_ for S_, _ in pairs]:
+                    continue
+                ws_t = dec._workspace(inv_temp_t, (dv_s, pen), False, sc)
+                srun = _SlotRun(dec, ws_t, None, {}, None, max_new_tokens=new, eos_id=-5, min_length=0, do_sample=dv_s, top_p=0.9,
+                                inv_temp=inv_temp_t, top_k=50, dev_sample=dv_s, penalty=pen, rows_tail=True, generator=None, scores=sc, W=0)
+
+                def treset(ws=ws_t, reset=reset, S=S):
+                    reset()
+                    ws["prm"].copy_(torch.tensor([inv_temp_t, 0.9, 50.0, a.penalty, 0.0, -5.0]))
+                    ws["seed"].copy_(torch.randint(0, 2**62, (S,), generator=gi))
+                    ws["gen"].fill_(1)
+                    ws["seen"].copy_(torch.randint(-2**31, 2**31 - 1, ws["seen"].shape, generator=gi, dtype=torch.int64).to(torch.int32)
+                                     & torch.randint(-2**31, 2**31 - 1, ws["seen"].shape, generator=gi, dtype=torch.int64).to(torch.int32)
+                                     & 0x01010101)                   # about 1 id in 128 seen
+                treset()
+                steps.append((kind, S, 0, S, capture(lambda srun=srun: srun.token_step(-1)), treset, tag))
+                keep.append(srun)
+                for K in [K for S_, K in pairs if S_ == S]:
+                    vrun = _SlotRun(dec, ws_t, None, {}, None, **{k_: getattr(srun, k_) for k_ in (
+                        "max_new_tokens", "eos_id", "min_length", "do_sample", "top_p", "inv_temp", "top_k", "dev_sample", "penalty",
+                        "rows_tail", "generator", "scores", "W")})
+                    dv = vrun.dv = dec._draft_workspace(K, inv_temp_t, (dv_s, pen, True, sc))
+
+                    def tvreset(dv=dv, treset=treset, K=K):
+                        treset()
+                        dv["ids"].copy_(torch.randint(3, 32000, (dv["ids"].shape[0],), generator=gi))
+                        dv["nguess"].fill_(K - 1)
+                        dv["nrow"].fill_(K)
+                    tvreset()
+                    steps.append((kind, S, K, S * K, capture(lambda vrun=vrun: vrun.verify_token_step(-1)), tvreset, tag))
+                    keep.append(vrun)
     # the attention launches alone: one graph of 16 launches each (q is rotated in place again and again: the time does not care)
-    attn, keep, W, scale = [], [], L.H * L.hd, 1.0 / L.hd ** 0.5
+    attn, W, scale = [], L.H * L.hd, 1.0 / L.hd ** 0.5
     i32 = lambda v, n: torch.full((n,), v, dtype=torch.int32, device=dev)
     for keys in (256, 1024):
         for S, K in pairs:
@@ -248,7 +295,7 @@ if a.draft_k and slot_counts not in ([], [0]):
                 if rnd:
                     out_[i].append(e0.elapsed_time(e1) / per)
     med = lambda ts: sorted(ts)[len(ts) // 2]
-    t_of = {(kind, S, K): med(res[i]) for i, (kind, S, K, _, _, _) in enumerate(steps)}
+    t_of = {(kind, S, K) + tuple(st_[6:]): med(res[i]) for i, st_ in enumerate(steps) for kind, S, K in [st_[:3]]}
     print(f"slot token steps, every row live, {a.step_keys}+ keys, {len(L.layers)} layers; median of {rounds - 1} rounds of {n_rep} replays")
     for kind in wkinds:
         for S, K in pairs:
@@ -256,6 +303,10 @@ if a.draft_k and slot_counts not in ([], [0]):
             print(f"weights {kind} slots {S} K={K} ({S * K} rows): verify {tv:.3f} ms, plain {S}-row {tp:.3f} ms, plain {S * K}-row {tw:.3f} ms; "
                   f"verify / plain = {tv / tp:.3f}, verify / plain at {S * K} rows = {tv / tw:.3f}; breaks even at "
                   f"{(tv / tp - 1) / (K - 1):.3f} of the guesses kept")
+            for tag in tails:                                        # against the greedy verify step and the tail's own plain step
+                tt, tpt = t_of[kind, S, K, tag], t_of[kind, S, 0, tag]
+                print(f"weights {kind} slots {S} K={K} {tag}: verify {tt:.3f} ms = {tt / tv:.3f} x the greedy verify step, {tt / tpt:.3f} x "
+                      f"its plain step ({tpt:.3f} ms); breaks even at {(tt / tpt - 1) / (K - 1):.3f} of the guesses kept")
     print("attention launch alone, every row live; median of the same rounds, 128 launches each")
     for i in range(0, len(attn), 2):
         keys, S, K = attn[i][:3]
@@ -290,6 +341,42 @@ if a.draft_k and slot_counts not in ([], [0]):
         dt, st_, vs, acc, prop = rs[len(rs) // 2]
         print(f"weights {kind} slots {S} drafter {name}{f' K={K}' if K else ''}: {len(reqs) / dt:.1f} samples/s ({dt * 1e3:.0f} ms, min "
               f"{rs[0][0] * 1e3:.0f}, max {rs[-1][0] * 1e3:.0f}; {st_} steps, {vs} verify; {acc} of {prop} guesses kept)")
+    # ---- the same requests sampled on the device (and with the penalty): the drafter is taught the sampled answers of the run
+    # without it -- same seeds, so the answers with a drafter must be those, which is checked
+    for tag, (dv_s, pen, sc) in tails.items():
+        if not dv_s or sc:
+            continue
+        skw = dict(kw, do_sample=True, top_p=0.9, top_k=50, temperature=a.temperature, repetition_penalty=a.penalty if pen else 1.0)
+        e2s = {}
+        for kind in wkinds:
+            set_kind(kind)
+            for S in dict.fromkeys(S for S, _ in pairs):
+                ref_ids = {i: ids.tolist() for i, ids, _ in decs[kind, S].run(reqs, seeds=range(len(reqs)), **skw)}
+                taught = [ref_ids[i] for i in range(len(reqs))]
+
+                class HalfS(Half):
+                    def __init__(self):
+                        self.good, self.n = NgramDrafter(taught), 0
+                for rnd in range(rounds):
+                    for name, mk, K in [("none", None, 0)] + [(n_, m_, K) for n_, m_ in (("taught", lambda: NgramDrafter(taught)), ("half", HalfS))
+                                                              for K in dict.fromkeys(K for S_, K in pairs if S_ == S)]:
+                        dkw = {} if mk is None else dict(draft=mk(), draft_k=K)
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        got = {i: ids.tolist() for i, ids, _ in decs[kind, S].run(reqs, seeds=range(len(reqs)), **skw, **dkw)}
+                        torch.cuda.synchronize()
+                        dt = time.perf_counter() - t0
+                        assert got == ref_ids, (tag, name, S, K)
+                        if rnd:
+                            st = decs[kind, S].last_stats
+                            e2s.setdefault((kind, S, name, K), []).append((dt, st["steps"], st.get("verify_steps", 0),
+                                                                           st.get("draft_accepted", 0), st.get("draft_proposed", 0)))
+        print(f"end to end, {tag} (top_p 0.9, top_k 50, temperature {a.temperature}, penalty {a.penalty if pen else 1.0}); median of {rounds - 1}")
+        for (kind, S, name, K), rs in e2s.items():
+            rs.sort()
+            dt, st_, vs, acc, prop = rs[len(rs) // 2]
+            print(f"weights {kind} slots {S} {tag} drafter {name}{f' K={K}' if K else ''}: {len(reqs) / dt:.1f} samples/s ({dt * 1e3:.0f} ms, "
+                  f"min {rs[0][0] * 1e3:.0f}, max {rs[-1][0] * 1e3:.0f}; {st_} steps, {vs} verify; {acc} of {prop} guesses kept)")
     L.decode_fp8 = L.decode_fp4 = False
     sys.exit(0)
 
