@@ -6,7 +6,9 @@
 //
 //   patch_blend:  for each operation (applied in order): dest box (y0, x0, h, w), source top-left (sy, sx), a byte mask
 //                 [h][w] and the interpolation factor.  'swap' (:258-262):  out = m ? src : out.   'uniform' (:263-268):
-//                 out = uint8(floor(x - (f m) x + (f m) s)) in float64, the reference's expression order.
+//                 out = uint8(floor(x - (f m) x + (f m) s)) in float64, the reference's expression order AND its roundings:
+//                 each product rounds before it is added (`rounded`) -- fused, x - 0.3 x + 0.3 s lands on an integer where
+//                 numpy lands just under it, and floor() makes that a whole grey level (tests/test_data_path_edges_gpu.py).
 //   label:        label_mask = medianBlur5(mean_c |M dest - M out| > tol)  (:97-98; M = union patch mask; the mean over 3
 //                 channels compares as  sum > 3 tol),  intensity = median_disk5(mean_c |lm dest - lm out|) (:103-105; the
 //                 median of 81 neighbours taken on the integer channel sums), logistic (:106-107), binary, continuous (:100-101).
@@ -20,6 +22,13 @@ struct PatchOp {          // 56 bytes; device array [n_ops]
   double factor;
   long patch_off;
 };
+
+// The value passes through an empty asm statement, so it exists as a rounded double of its own: the build's
+// -ffp-contract=fast otherwise fuses a product into the add that follows it (one rounding instead of numpy's two).
+__device__ __forceinline__ double rounded(double p) {
+  asm volatile("" : "+v"(p));
+  return p;
+}
 
 // one workgroup column per operation is wasteful for tiny patches; operations of one image must apply in order, so the
 // grid is (pixels of the largest patch, 1, 1) and every thread walks the operation list (<= a few per image, sorted by image)
@@ -44,8 +53,8 @@ __global__ void patch_blend_kernel(unsigned char* __restrict__ out, const unsign
         } else {
           const double fm = op.factor * (double)m;
           double v = (double)x;
-          v -= fm * (double)x;
-          v += fm * (double)sv;
+          v -= rounded(fm * (double)x);
+          v += rounded(fm * (double)sv);
           out[d * 3 + c] = (unsigned char)floor(v);
         }
       }
@@ -135,7 +144,7 @@ static inline int ss_grid(long n) {
   return (int)g;
 }
 
-// out [B,H,W,3] u8 (starts as a copy of dest), src [B,H,W,3] u8, ops: device array of n_ops PatchOp (48 bytes each, see
+// out [B,H,W,3] u8 (starts as a copy of dest), src [B,H,W,3] u8, ops: device array of n_ops PatchOp (56 bytes each, see
 // myriad_amd/self_sup.py for the packing), masks: device byte pool, union_mask [B,H,W] u8 (zero-filled by the caller) or NULL.
 // hs/ws: host copies of every operation's h and w (grid sizing); operations run in order, one launch each.
 extern "C" int mh_patch_blend_u8(void* out, const void* src, const void* masks, const void* ops, const int* hs, const int* ws,

@@ -11,8 +11,8 @@ resampler to the bit (torchvision's Resize on a PIL image is PIL.Image.resize): 
 the host in double precision the way Resample.c builds them (once per distinct image size, cached on the device), the kernels
 do the integer arithmetic, and ToTensor + Normalize is a 3 x 256 float32 table evaluated with torch's own float32 expressions.
 At 130-140 images/s per GPU the reference's 8 CPU workers per GPU spend ~5 ms per 1000 x 1500 image in PIL alone; here it is
-two launches.  The NSA / CutPaste blending itself (cv2.seamlessClone, datasets/self_sup_tasks.py) is not built: OpenCV is
-absent from the build container, so its Poisson solver could not be pinned.
+two launches.  The NSA / CutPaste augmentation that edits the uint8 crops in between (datasets/self_sup_tasks.py: resampled
+patch, arithmetic blends, Poisson cloning, label) runs on the device as well: myriad_amd/self_sup.py, csrc/selfsup.hip.
 """
 from __future__ import annotations
 
