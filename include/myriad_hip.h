@@ -697,6 +697,32 @@ int mh_attn_decode_rope_split_rows(const void* qkv, long ld_qkv, void* cache, lo
                                    const int* kv_len, const int* live, const float* cos_tab, const float* sin_tab, void* out,
                                    long ldo, float* partials, long partials_floats, int B, int H, int D, int T_cap, int chunk,
                                    float scale, mh_stream_t s);
+/* K consecutive split token steps of each of G sequences in one launch pair (attn_decode_split_draft.hip; the verify step of
+ * draft-and-verify decoding on the split-KV view).  The arguments are mh_attn_decode_rope_draft's -- row g*K + j of qkv is the
+ * token at position pos[g] + j of sequence g, 1 <= K <= 8, pos and live int[G] on the device -- plus partials, partials_floats and
+ * chunk as in mh_attn_decode_rope_split_rows; partials_floats >= mh_attn_decode_split_draft_ws_floats(G, K, H, T_cap, chunk) =
+ * G K H ceil(T_cap / chunk) 132.  For a live sequence and every j < K the out row and cache row pos[g] + j have the bits of the
+ * j-th of K sequential mh_attn_decode_rope_split_rows launches at B = 1 with the same chunk, pos = pos[g] + j and kv_len =
+ * pos[g] + j + 1.  Grid (ceil(T_cap / chunk), G*H): one workgroup per (chunk, sequence, head) loads every cached key and value
+ * once for all K queries; a second launch merges each row's chunks in order.  qkv is only read.  No cache row >= pos[g] is read
+ * (rows a rejected guess left there may hold anything), rows < pos[g] are only read and rows >= pos[g] + K are not touched.  A
+ * sequence with live[g] == 0 or pos[g] < 0 touches nothing and gets zero out rows; a row whose position would reach T_cap writes
+ * no cache row and no record and gets a zero out row.  MH_ERR_UNSUPPORTED, nothing launched, unless D % 16 == 0, D <= 128 and K
+ * <= 8; MH_ERR_ARG for a chunk other than 0 (= 128), 128, 256, 512, T_cap > 8192, a short partials buffer, null or misaligned
+ * pointers, misaligned strides (ld_qkv, ld_cache, cache_bstride % 8, ldo % 4) and strides shorter than the rows.  A call with G = 0
+ * answers whether the shape is supported and reads no pointer. */
+long mh_attn_decode_split_draft_ws_floats(int G, int K, int H, int T_cap, int chunk);
+int mh_attn_decode_rope_split_draft(const void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache, const int* pos,
+                                    const int* live, const float* cos_tab, const float* sin_tab, void* out, long ldo,
+                                    float* partials, long partials_floats, int G, int K, int H, int D, int T_cap, int chunk,
+                                    float scale, mh_stream_t s);
+/* The same for the decode slots: nrow int[G] on the device, 1 <= nrow[g] <= K, the rows of group g that hold a token.  Rows j <
+ * nrow[g] of a live group behave as in mh_attn_decode_rope_split_draft; rows j >= nrow[g] write no cache row and no record and get
+ * a zero out row.  nrow must be non-null and 4-byte aligned (MH_ERR_ARG). */
+int mh_attn_decode_rope_split_draft_rows(const void* qkv, long ld_qkv, void* cache, long cache_bstride, long ld_cache,
+                                         const int* pos, const int* live, const int* nrow, const float* cos_tab,
+                                         const float* sin_tab, void* out, long ldo, float* partials, long partials_floats, int G,
+                                         int K, int H, int D, int T_cap, int chunk, float scale, mh_stream_t s);
 /* K14 patch embedding operand (eva_vit.py:196-204): NCHW f32 image -> [B*np, Kpad] bf16 in (c,iy,ix) order */
 int mh_patchify_nchw(const float* img, void* out, int B, int C, int H, int W, int P, int Kpad, mh_stream_t s);
 int mh_scatter_rows_f32(const float* src, const int* rows, float* dst, long ldd, long n, int D, int accumulate,

@@ -286,7 +286,8 @@ class Chat(_ChatBase):
         beams are deterministic and a penalty is refused, as before.  `draft` / `draft_k`: draft-and-verify decoding of the turn
         (LlamaHIP.greedy_generate; the same ids in fewer token steps when the drafter guesses well), refused with beams and --
         unless model.llama.draft_sampling (MYRIAD_DRAFT_SAMPLING=1) is on -- with device sampling and `repetition_penalty` != 1;
-        a turn on the split-KV view decodes with plain steps and last_stats["draft_off"] says "split_kv"."""
+        a turn on the split-KV view decodes with plain steps and last_stats["draft_off"] says "split_kv", unless
+        model.llama.draft_split (MYRIAD_DRAFT_SPLIT=1) is on: then it drafts there too (mh_attn_decode_rope_split_draft)."""
         m = self.model
         m.finish_update()
         llama = m.llama
@@ -349,12 +350,16 @@ class ChatPool(_ChatBase):
 
     @torch.no_grad()
     def answer_many(self, items, max_new_tokens=300, num_beams=1, min_length=1, top_p=0.9, repetition_penalty=1.0, temperature=1.0,
-                    max_length=2000, do_sample=True, generator=None, seeds=None, prefill_batch=8):
+                    max_length=2000, do_sample=True, generator=None, seeds=None, prefill_batch=8, draft=None, draft_k=4):
         """One assistant turn for each (conv, img_list) of `items`, Chat.answer's per conversation (the assistant role, the
         context and its truncation window -- a moved window resets that session, reason "window" --, the post-processing, the
         answer written into conv.messages) through SlotDecoder.run_turns.  Returns [(text, ids)] in the items' order;
         `last_stats` is a list of per-conversation dicts with Chat.last_stats' keys where they apply.  `seeds`: with device
-        sampling, the i-th item's random stream (else drawn from `generator`), so an answer does not depend on its neighbours."""
+        sampling, the i-th item's random stream (else drawn from `generator`), so an answer does not depend on its neighbours.
+        `draft` / `draft_k`: draft-and-verify decoding of the call's turns (SlotDecoder.run_turns(draft=), behind
+        model.llama.slot_draft and model.llama.draft_split -- NotImplementedError without them): the same texts in fewer token
+        steps where the drafter guesses well, and every `last_stats[i]` gains the call's draft counters (draft_k, draft_off,
+        verify_steps, plain_steps, draft_proposed, draft_accepted)."""
         m = self.model
         if int(num_beams) > 1:
             raise NotImplementedError(f"answer_many(num_beams={num_beams}): decode slots have no beam search; use Chat.answer")
@@ -377,12 +382,16 @@ class ChatPool(_ChatBase):
             embs, keys, begin = self._turn_context(conv, img_list, max_new_tokens, max_length)
             turns.append((conv, embs[0], keys, "window" if begin > 0 else None))
         kw = dict(seeds=seeds) if seeds is not None else {}
+        if draft is not None:
+            kw.update(draft=draft, draft_k=draft_k)
         got = list(self.decoder.run_turns(turns, weights_version=m.store.version, max_new_tokens=max_new_tokens,
                                           stop_ids=STOP_WORDS, eos_id=2, min_length=min_length, do_sample=bool(do_sample),
                                           top_p=float(top_p), temperature=float(temperature), generator=generator, top_k=50,
                                           repetition_penalty=rep, prefill_batch=int(prefill_batch), ordered=True, **kw))
         st = self.decoder.last_stats
         shared = {k: st[k] for k in ("steps", "graph_captures", "graph_replays")}
+        if "draft_k" in st:                                          # a draft call: its counters, the same for every conversation
+            shared.update({k: st[k] for k in ("draft_k", "draft_off", "verify_steps", "plain_steps", "draft_proposed", "draft_accepted")})
         self.last_stats = [dict(t, split_kv=st["split_kv"], **shared) for t in st["turns"]]
         self.last_token_ids = [ids for _, ids, _ in got]
         return [self._finish_turn(conv, ids.tolist()) for (conv, _), (_, ids, _) in zip(items, got)]

@@ -19,6 +19,10 @@
 // and softmax order, the four-wave sum, the in-order merge -- is the ROWS = false code, so a live row has the bits of
 // mh_attn_decode_rope_split at B = 1 on that row with pos_dev[0] = pos[b].  One difference from the non-split rows kernel: that
 // one rotates q in place in qkv, this one leaves qkv alone (nothing downstream reads q after the attention).
+//
+// attn_decode_split_draft.hip (the K-row verify step of draft decoding on this view) repeats this kernel's rotary block, phases 1
+// to 3 and the merge expression for expression per row, and tests/test_split_draft_kernels_gpu.py holds its rows to the bits of
+// sequential mh_attn_decode_rope_split_rows launches: change them together.
 #include "common.h"
 
 #define SPLIT_THREADS 256

@@ -169,7 +169,7 @@ def _buffer_view(lm: "LlamaHIP", bufs: dict, split: bool, scores: bool = False) 
     return view
 
 
-def _draft_view(lm: "LlamaHIP", bufs: dict, K: int, inv_temp: float, tail=None) -> dict:
+def _draft_view(lm: "LlamaHIP", bufs: dict, K: int, inv_temp: float, tail=None, split: bool = False) -> dict:
     """The K-row verify step's view of a B = 1 buffer set (draft decoding): the caches, `pos`, `kvlen`, `step` and the fed token
     ids_k[0] are the set's, shared with its plain one-row step, so the host switches between the two from step to step; the K-row
     ids / activations / logits / picks, the 3K + 1 float record `drec`, the device float `top_p` and the always-live flag are the
@@ -180,11 +180,14 @@ def _draft_view(lm: "LlamaHIP", bufs: dict, K: int, inv_temp: float, tail=None) 
     (nrow: every row holds a token, fillers included), `ngs` = [K - 1] and, in the set, the token counter `gen` [1]; its record
     `drec` is flat -- the 4K + 1 floats of mh_draft_accept_sampled_rows (`arec`), then with scores SCORE_ROWS rows of K (`sc`).
     With the device sampler the set also gains `prm6` (the slot form's six knobs) and `plain_rows`, the view of the call's plain
-    step in the slot form: the solo step counts launches in `step`, the slot form tokens in `gen`, which both steps advance."""
+    step in the slot form: the solo step counts launches in `step`, the slot form tokens in `gen`, which both steps advance.
+
+    `split` (behind `draft_split`, for a split-KV `bufs`): the view's attention is ops.attn_decode_rope_split_draft and it holds
+    that launch's partials `split_draft`; keyed ("split",) + the above, beside the plain split step it switches with."""
     if bufs["ids"].shape[0] != 1:
         raise NotImplementedError("draft decoding runs one sequence (batch 1)")
     views = bufs.setdefault("draft_views", {})
-    key = (int(K), float(inv_temp)) + (() if tail is None else tuple(bool(t) for t in tail))
+    key = (("split",) if split else ()) + (int(K), float(inv_temp)) + (() if tail is None else tuple(bool(t) for t in tail))
     if tail is not None and "gen" not in bufs:
         bufs["gen"] = torch.zeros((1,), dtype=torch.int32, device=lm.dev)
     if tail is not None and tail[0] and "prm6" not in bufs:
@@ -195,6 +198,7 @@ def _draft_view(lm: "LlamaHIP", bufs: dict, K: int, inv_temp: float, tail=None) 
     if key not in views:
         dev = lm.dev
         views[key] = dict(bufs, graph=None, warm=False, split=None, draft_k=int(K), ids=bufs["ids_k"][:K],
+                          split_draft=ops.attn_decode_split_draft_ws(1, int(K), lm.H, bufs["T"], dev) if split else None,
                           x_in=torch.empty((K, lm.D), dtype=F32, device=dev), logits=torch.empty((K, lm.V), dtype=F32, device=dev),
                           nxt=torch.empty((K,), dtype=torch.long, device=dev), mar=torch.empty((K,), dtype=F32, device=dev),
                           pmx=torch.empty((K,), dtype=F32, device=dev), drec=torch.zeros((3 * K + 1,), dtype=F32, device=dev),
@@ -462,7 +466,9 @@ class LlamaDecode:
         rows alike.  Above GEMV_MAX_ROWS rows (_wide_step) the products are ops.gemv_packed_wide and the norm / SiLU products take
         their two-launch forms.  ws["draft_k"] = K (_draft_view, draft decoding's verify step): the rows are K consecutive tokens
         of one sequence and the attention is ops.attn_decode_rope_draft, row j at position pos + j; with ws["nrow"] beside it (the
-        slot engine's verify view) the rows are K per slot and the attention is ops.attn_decode_rope_draft_rows on (pos, live, nrow)."""
+        slot engine's verify view) the rows are K per slot and the attention is ops.attn_decode_rope_draft_rows on (pos, live, nrow).
+        ws["split_draft"] (the partials of ops.attn_decode_split_draft_ws, a verify view of the split-KV step) swaps those two for
+        ops.attn_decode_rope_split_draft[_rows], whose rows carry the split-KV kernel's bits."""
         H, hd, scale, cos, sin = self.H, self.hd, 1.0 / math.sqrt(self.hd), self.cos, self.sin
         pos, kvlen, live, split = ws["pos"], ws["kvlen"], ws.get("live"), ws["split"]
         wide = _wide_step(self, ws["x_in"].shape[0], ws["row_limit"])
@@ -475,6 +481,9 @@ class LlamaDecode:
             attention, state, partials = ops.attn_decode_rope_draft_rows, (pos, live, ws["nrow"]), (ws["draft_k"],)
         elif ws.get("draft_k"):                                          # K consecutive rows of one sequence: (pos, live), K behind
             attention, state, partials = ops.attn_decode_rope_draft, (pos, ws["live1"]), (ws["draft_k"],)
+        if ws.get("draft_k") and ws.get("split_draft") is not None:      # the same two on the split-KV view: K, then the partials
+            attention = ops.attn_decode_rope_split_draft if ws.get("nrow") is None else ops.attn_decode_rope_split_draft_rows
+            partials = (ws["draft_k"], ws["split_draft"])
 
         def gemv(x, w, **kw):
             return (ops.gemv_packed_wide if wide else ops.gemv_packed)(x, w, **kw)
@@ -749,7 +758,8 @@ class LlamaDecode:
         sampled answer of the call without `draft`.
 
         The verify step is off for the whole call, and last_generate_stats["draft_off"] says why, when `ws` runs the split-KV
-        attention ("split_kv") or mh_attn_decode_rope_draft does not take the shape ("unsupported").  Stats: verify_steps,
+        attention with `draft_split` off ("split_kv") or the verify step's attention launch -- mh_attn_decode_rope_draft, on the
+        split-KV view mh_attn_decode_rope_split_draft -- does not take the shape ("unsupported").  Stats: verify_steps,
         plain_steps, draft_proposed, draft_accepted (DraftLoop), verify_graph_replays and plain_graph_replays beside graph_replays."""
         _, S0, _ = inputs_embeds.shape
         if not (_packed_step(self, K, ws["row_limit"]) and self.decode_fused):
@@ -762,12 +772,14 @@ class LlamaDecode:
         penalty, scores = repetition_penalty is not None, watch_ids is not None
         tail = (dev_sample, penalty, scores) if dev_sample or penalty or scores else None
         loop = DraftLoop(draft, K, max_new_tokens, stop_ids, eos_id, min_length, do_sample, top_p, stats)
-        if ws["split"] is not None:
+        split = ws["split"] is not None
+        if split and not getattr(self, "draft_split", False):
             stats["draft_off"] = "split_kv"
-        elif not ops.attn_decode_draft_supported(self.H, self.hd, K, ws["T"]):
+        elif not (ops.attn_decode_split_draft_supported(self.H, self.hd, K, ws["T"]) if split else
+                  ops.attn_decode_draft_supported(self.H, self.hd, K, ws["T"])):
             stats["draft_off"] = "unsupported"
         loop.use_draft = stats["draft_off"] is None
-        dv = _draft_view(self, ws, K, inv_temp, tail) if loop.use_draft or dev_sample else None
+        dv = _draft_view(self, ws, K, inv_temp, tail, split and loop.use_draft) if loop.use_draft or dev_sample else None
         pv = dv["draft_views"]["plain_rows", penalty, scores] if dev_sample else ws      # the view of the call's plain step
         rec = ws["rec"] if scores else ws["rec"][:4 if dev_sample else 3]
         ids_k, fresh, sc_rows = ws["ids_k"], [True], []
@@ -1338,7 +1350,7 @@ class SlotDecoder:
         self.ws = self.views[key]
         return self.ws
 
-    def _draft_workspace(self, K: int, inv_temp: float, tail=None) -> dict:
+    def _draft_workspace(self, K: int, inv_temp: float, tail=None, split: bool = False) -> dict:
         """The verify step's view of the buffers (run(draft=...)): slots x K rows, K consecutive tokens per slot, with a graph of
         its own, one per (K, inv_temp) -- the arg-max launch bakes inv_temp in.  It shares the caches, `pos`, `kvlen`, `live`,
         `step` and the plain step's fed ids (`next_ids`, what mh_draft_accept_rows also writes its kept pick to) with the plain
@@ -1352,9 +1364,12 @@ class SlotDecoder:
         reads the `prm`, `seed`, `gen`, `seen` and `watch` the call's plain view already put into the set (without the per-row
         tail `gen` is a counter nobody reads), holds `kept` [slots * K], and its record `drec` is one flat buffer -- slots x (4K
         + 1) floats of mh_draft_accept_sampled_rows (`arec`), then with scores SCORE_ROWS rows of slots * K floats (`sc`) -- so
-        the step still makes one device->host copy."""
+        the step still makes one device->host copy.
+
+        `split` (behind `draft_split`, for a call on the split-KV view): the verify step's attention is
+        ops.attn_decode_rope_split_draft_rows and the view holds its partials `split_draft`; keyed ("split",) + the above."""
         L, bufs = self.llama, self._base_buffers()
-        key = (int(K), float(inv_temp)) + (() if tail is None else tuple(bool(t) for t in tail))
+        key = (("split",) if split else ()) + (int(K), float(inv_temp)) + (() if tail is None else tuple(bool(t) for t in tail))
         if key not in self.draft_views:
             if len(self.draft_views) >= 4:                           # a few (K, temperature) pairs at most: drop the oldest graph
                 self.draft_views.pop(next(iter(self.draft_views)))
@@ -1366,7 +1381,8 @@ class SlotDecoder:
                         nxt=torch.empty((R,), dtype=torch.long, device=dev), mar=torch.empty((R,), dtype=F32, device=dev),
                         pmx=torch.empty((R,), dtype=F32, device=dev), cnt=cnt, nguess=cnt[0], nrow=cnt[1],
                         drec=torch.zeros((self.slots, 3 * int(K) + 1), dtype=F32, device=dev),
-                        top_p=torch.zeros((1,), dtype=F32, device=dev))
+                        top_p=torch.zeros((1,), dtype=F32, device=dev),
+                        split_draft=ops.attn_decode_split_draft_ws(self.slots, int(K), L.H, bufs["T"], dev) if split else None)
             if tail is not None:
                 n_acc = self.slots * (4 * int(K) + 1)
                 drec = torch.zeros((n_acc + (ops.SCORE_ROWS * R if tail[3] else 0),), dtype=F32, device=dev)
@@ -1423,7 +1439,8 @@ class SlotDecoder:
         verify step the host makes two small host->device copies (the fed ids and guesses; the counts) and one device->host copy
         (the record); a plain step after it needs none.  Under do_sample a row with p_max < top_p ends its window on the device
         and is drawn on the host from its row of the verify logits.  K = 1 runs plain steps only; so does a call on the split-KV
-        view or with a shape mh_attn_decode_rope_draft refuses, and `last_stats["draft_off"]` says "split_kv" / "unsupported".
+        view (unless `draft_split`, MYRIAD_DRAFT_SPLIT=1, is on: then its verify step runs mh_attn_decode_rope_split_draft_rows) or
+        with a shape the verify step's attention launch refuses, and `last_stats["draft_off"]` says "split_kv" / "unsupported".
         `last_stats` gains draft_k, draft_off, verify_steps, plain_steps, draft_proposed, draft_accepted, emitted,
         verify_graph_replays and plain_graph_replays.  The caller teaches the drafter.  NotImplementedError with num_beams > 1
         and -- unless `draft_sampling` (MYRIAD_DRAFT_SAMPLING=1, off by default) is on -- with device sampling, repetition_penalty
@@ -1467,13 +1484,19 @@ class SlotDecoder:
         `reused_tokens`, `prefilled_tokens` and `full_reprefill_reason`.  `weights_version`: anything that changes when the
         weights do; with it, a change of the decode weights or a `run()` on this decoder drops every session's cached rows.  The
         step's attention kernel is the decoder's `split_kv` choice, made once per call (`last_stats["split_kv"]`): with None,
-        split_kv_rows_rule(turns in the call, heads, the longest context at admission)."""
+        split_kv_rows_rule(turns in the call, heads, the longest context at admission).
+        `draft` / `draft_k` (behind `slot_draft` and `draft_split`; NotImplementedError without them): `run`'s draft-and-verify
+        loop on the turns.  A window is clamped so that no row is fed past context + max_new_tokens - 1 (slot_guesses), and a
+        session records the context plus the ids that stood: the cache rows of rejected guesses lie past the recorded keys, where
+        the next turn's prefill or verify step overwrites them."""
         turns = [tuple(t) for t in turns]
         if "refill_min" in kw:
             raise ValueError("run_turns: refill_min does not apply, every turn has its own slot")
-        if kw.get("draft") is not None:
-            raise NotImplementedError("run_turns: draft decoding with run_turns / ChatPool is not implemented (it runs in `run`)")
-        kw.pop("draft", None), kw.pop("draft_k", None)
+        if kw.get("draft") is not None and not getattr(self.llama, "draft_split", False):
+            raise NotImplementedError("run_turns: draft decoding with run_turns / ChatPool is not implemented (it runs in `run`) "
+                                      "without its switch (MYRIAD_DRAFT_SPLIT=1 or llama.draft_split = True)")
+        if kw.get("draft") is None:
+            kw.pop("draft", None), kw.pop("draft_k", None)
         if int(kw.pop("num_beams", 1) or 1) != 1:
             raise NotImplementedError("run_turns: beam search runs in `run` only (a conversation would have to carry the winning "
                                       "hypothesis's cache rows into its next turn)")
@@ -1725,7 +1748,7 @@ class SlotDecoder:
         bare = not getattr(self.llama, "draft_sampling", False)      # behind that switch the verify step runs the per-row tail
         for on, what in ((bare and dev_sample, "device sampling"), (bare and penalty, "repetition_penalty != 1"),
                          (bare and int(min_length) > 1, "min_length > 1"), (bare and scores, "return_scores"),
-                         (turns is not None, "run_turns / ChatPool")):
+                         (turns is not None and not getattr(self.llama, "draft_split", False), "run_turns / ChatPool")):
             if on:
                 raise NotImplementedError(f"decode slots: draft decoding with {what} is not implemented")
         return K
@@ -1779,14 +1802,16 @@ class SlotDecoder:
             ws["watch"].copy_(watch)
         dv = None
         if K:                                                        # draft decoding: the verify view, unless the call cannot use it
-            stats.update(draft_k=K, draft_off="split_kv" if split else None, verify_steps=0, plain_steps=0, draft_proposed=0,
+            split_off = split and not getattr(L, "draft_split", False)   # the split-KV view drafts behind its switch only
+            stats.update(draft_k=K, draft_off="split_kv" if split_off else None, verify_steps=0, plain_steps=0, draft_proposed=0,
                          draft_accepted=0, emitted=0, verify_graph_replays=0, plain_graph_replays=0)
-            if not split and not ops.attn_decode_draft_supported(L.H, L.hd, K, self.T_cap):
+            if not split_off and not (ops.attn_decode_split_draft_supported(L.H, L.hd, K, self.T_cap) if split else
+                                      ops.attn_decode_draft_supported(L.H, L.hd, K, self.T_cap)):
                 stats["draft_off"] = "unsupported"
             if K > 1 and stats["draft_off"] is None:
                 # the per-row tail, the scores: the verify step of draft_sampling; else exactly the launches it had before
                 dv_tail = (dev_sample, penalty, rows_tail, scores) if rows_tail or scores else None
-                dv = run.dv = self._draft_workspace(K, inv_temp, dv_tail)
+                dv = run.dv = self._draft_workspace(K, inv_temp, dv_tail, bool(split))
                 # the host draws where p_max (f32) < top_p (a double): the device holds the smallest f32 >= top_p, so its
                 # p_max >= *top_p is that test's negation for every f32 p_max; <= 0: no row needs a draw
                 dv["top_p"].copy_(torch.from_numpy(np.array([f32_at_least(top_p) if do_sample else 0.0], dtype=np.float32)))

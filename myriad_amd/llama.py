@@ -124,6 +124,10 @@ class LlamaHIP(LlamaDecode):
         self.slot_draft = os.environ.get("MYRIAD_SLOT_DRAFT", "0") != "0"
         # draft decoding under device sampling, the repetition penalty, min_length and the token scores (off by default)
         self.draft_sampling = os.environ.get("MYRIAD_DRAFT_SAMPLING", "0") != "0"
+        # draft decoding on the split-KV view (mh_attn_decode_rope_split_draft: the chat session's long turns, a decoder built with
+        # split_kv) and in SlotDecoder.run_turns / ChatPool; off by default: the split view decodes with plain steps and run_turns
+        # refuses `draft` as before
+        self.draft_split = os.environ.get("MYRIAD_DRAFT_SPLIT", "0") != "0"
         self.last_layer_rows = os.environ.get("MYRIAD_LAST_LAYER_ROWS", "1") != "0"
         # the packed token step streams FP8 (e4m3fn, one fp32 scale per output row) copies of the decoder matrices instead of
         # the bf16 ones (ops.gemv_pack_fp8; half the bytes, weight rounding the only new error); off by default, the attribute

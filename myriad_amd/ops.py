@@ -734,6 +734,73 @@ def attn_decode_rope_split_rows(qkv2d: torch.Tensor, cache: torch.Tensor, pos: t
     return out
 
 
+def attn_decode_split_draft_supported(n_heads: int, head_dim: int, K: int, T_cap: int, chunk: int = SPLIT_KV_CHUNK) -> bool:
+    """Whether mh_attn_decode_rope_split_draft takes this shape (head dim, rows per sequence, cache length, chunk): the launcher's
+    own answer to a call with no sequence, which launches nothing."""
+    rc = _L().mh_attn_decode_rope_split_draft(None, 0, None, 0, 0, None, None, None, None, None, 0, None, 0, 0, int(K), int(n_heads),
+                                              int(head_dim), int(T_cap), int(chunk), 1.0, _s())
+    return rc == 0
+
+
+def attn_decode_split_draft_ws(G: int, K: int, n_heads: int, T_cap: int, device, chunk: int = SPLIT_KV_CHUNK) -> torch.Tensor:
+    """The fp32 partials buffer mh_attn_decode_rope_split_draft needs for G sequences of K rows on a [G, T_cap] cache."""
+    n = _L().mh_attn_decode_split_draft_ws_floats(G, K, n_heads, T_cap, chunk)
+    if n < 0:
+        raise _lib.MyriadHipError(f"attn_decode_split_draft_ws: bad shape G={G} K={K} H={n_heads} T_cap={T_cap} chunk={chunk}")
+    return torch.empty((n,), dtype=F32, device=device)
+
+
+def _attn_decode_rope_split_draft(name, qkv2d, cache, pos, live, nrow, cos_tab, sin_tab, n_heads, head_dim, scale, K, partials, chunk,
+                                  out):
+    _chk2d(qkv2d, BF16, f"{name}.qkv")
+    R, W, K = qkv2d.shape[0], n_heads * head_dim, int(K)
+    G = cache.shape[0]
+    if K < 1 or R != G * K or qkv2d.shape[1] < 3 * W or cache.shape[2] != 2 * W:
+        raise _lib.MyriadHipError(f"{name}: qkv must be [G*K, >=3W] and cache [G, T, 2W]")
+    for what, t in (("pos", pos), ("live", live)) + ((("nrow", nrow),) if nrow is not None else ()):
+        if t.dtype != torch.int32 or t.numel() != G or not t.is_contiguous():
+            raise _lib.MyriadHipError(f"{name}: {what} must be a contiguous int32 [G]")
+    if partials.dtype != F32 or not partials.is_contiguous():
+        raise _lib.MyriadHipError(f"{name}: partials must be a contiguous f32 buffer")
+    if out is None:
+        out = torch.empty((R, W), dtype=BF16, device=qkv2d.device)
+    elif out.dtype != BF16 or out.shape != (R, W) or out.stride(1) != 1:
+        raise _lib.MyriadHipError(f"{name}: out must be bf16 [G*K, W]")
+    head = (_p(qkv2d), qkv2d.stride(0), _p(cache), cache.stride(0), cache.stride(1), _p(pos), _p(live))
+    tail = (_p(cos_tab), _p(sin_tab), _p(out), out.stride(0), _p(partials), partials.numel(), G, K, n_heads, head_dim, cache.shape[1],
+            int(chunk), float(scale), _s())
+    if nrow is None:
+        _lib.check(_L().mh_attn_decode_rope_split_draft(*head, *tail), "mh_attn_decode_rope_split_draft")
+    else:
+        _lib.check(_L().mh_attn_decode_rope_split_draft_rows(*head, _p(nrow), *tail), "mh_attn_decode_rope_split_draft_rows")
+    return out
+
+
+def attn_decode_rope_split_draft(qkv2d: torch.Tensor, cache: torch.Tensor, pos: torch.Tensor, live: torch.Tensor, cos_tab: torch.Tensor,
+                                 sin_tab: torch.Tensor, n_heads: int, head_dim: int, scale: float, K: int, partials: torch.Tensor,
+                                 chunk: int = SPLIT_KV_CHUNK, out: Optional[torch.Tensor] = None):
+    """K consecutive split-KV token steps of each of G sequences as one launch pair (the verify step on the split-KV view): row
+    g*K + j of qkv2d [G*K, >=3W] is the token at position pos[g] + j, cache [G, T, 2W], pos / live int32 [G].  Every out row and
+    appended cache row has the bits of attn_decode_rope_split_rows at B = 1 on that row at its position after the rows before it
+    were appended; every cached key is loaded once for the K queries.  qkv2d is read only.  partials:
+    attn_decode_split_draft_ws().  Returns o [G*K, W] bf16."""
+    return _attn_decode_rope_split_draft("attn_decode_rope_split_draft", qkv2d, cache, pos, live, None, cos_tab, sin_tab, n_heads,
+                                         head_dim, scale, K, partials, chunk, out)
+
+
+def attn_decode_rope_split_draft_rows(qkv2d: torch.Tensor, cache: torch.Tensor, pos: torch.Tensor, live: torch.Tensor,
+                                      nrow: torch.Tensor, cos_tab: torch.Tensor, sin_tab: torch.Tensor, n_heads: int, head_dim: int,
+                                      scale: float, K: int, partials: torch.Tensor, chunk: int = SPLIT_KV_CHUNK,
+                                      out: Optional[torch.Tensor] = None):
+    """attn_decode_rope_split_draft for the decode slots: group g holds nrow[g] token rows (int32 [G] on the device, 1 .. K).
+    Rows below nrow[g] of a live group have attn_decode_rope_split_draft's bits; the others, and every row of an idle group, write
+    neither the cache nor a partial record and get a zero out row."""
+    if nrow is None:
+        raise _lib.MyriadHipError("attn_decode_rope_split_draft_rows: nrow must be a contiguous int32 [G]")
+    return _attn_decode_rope_split_draft("attn_decode_rope_split_draft_rows", qkv2d, cache, pos, live, nrow, cos_tab, sin_tab, n_heads,
+                                         head_dim, scale, K, partials, chunk, out)
+
+
 def gemm_auto_f32(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     """f32 out = a @ b^T, choosing split-K when the output is small and the reduction long (wgrad shapes)."""
     M, K = a.shape

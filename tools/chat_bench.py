@@ -18,9 +18,17 @@
     contexts in --pool-contexts (default 512,1024,2048,4096): wall ms per turn and ms per token step -- (a turn of --tokens + 1
     tokens) - (a turn of 1 token) on the cached third context --, median of --repeats (default 5 here) with min and max.  Before
     it, the two attention launches alone (32 launches = one token's layers, from a graph) at R = 1, 4, 8 live rows on 1,024 /
-    4,096 cached keys.
+    4,096 cached keys;
+  * --split-draft: draft-and-verify decoding on the split-KV view (behind llama.draft_split).  First the attention launch pair
+    alone (32 pairs = one step's layers, from a graph, interleaved per round): mh_attn_decode_rope_split_draft_rows at 1,024 /
+    2,160 keys and (G, K) = (1, 4), (1, 8), (2, 4) against K sequential mh_attn_decode_rope_split_rows launches and against
+    mh_attn_decode_rope_draft_rows at the same shape.  Then a turn of --tokens tokens on a cached context of --pool-context keys
+    (one row prefilled) with no drafter, a drafter taught the answers and an untaught one, interleaved per repeat: one
+    DecodeSession(split=True), and N conversations (--pool, default 1,2,8) through run_turns on split_kv=True and False decoders;
+    the ids are asserted equal to the run without a drafter.
 
 python tools/chat_bench.py [--layers 32] [--tokens 32] [--repeats 3] [--chunks] [--ragged-past] [--pool 1,4,8,16] [--pool-split]
+                           [--split-draft]
 -> one JSON line per measurement"""
 import argparse
 import json
@@ -49,9 +57,16 @@ ap.add_argument("--pool", default="", help="conversation counts for the pool-aga
 ap.add_argument("--pool-context", type=int, default=256, help="keys of a conversation's first context")
 ap.add_argument("--pool-split", action="store_true", help="the pool with split_kv=False against split_kv=True")
 ap.add_argument("--pool-contexts", default="512,1024,2048,4096", help="first contexts of the --pool-split comparison")
+ap.add_argument("--split-draft", action="store_true", help="draft decoding on the split-KV view: the attention pair alone, a chat "
+                "turn and the pool with a taught / an untaught drafter against no drafter")
+ap.add_argument("--draft-k", type=int, default=4, help="rows per verify step of the --split-draft turns")
 a = ap.parse_args()
 if a.repeats is None:
-    a.repeats = 5 if a.pool_split else 3
+    a.repeats = 5 if a.pool_split or a.split_draft else 3
+if a.split_draft and not a.pool:
+    a.pool = "1,2,8"
+if a.split_draft and a.pool_context == 256:
+    a.pool_context = 1136                                            # past the split-KV threshold of a solo chat turn
 if a.pool_split and not a.pool:
     a.pool = "1,2,4,7,8"
 dev = "cuda:0"
@@ -193,8 +208,70 @@ def rows_bench():
             torch.cuda.empty_cache()
 
 
-if a.chunks or (a.skip_model and not a.ragged_past and not a.pool_split):
+def split_draft_attn_bench():
+    """The split verify-step attention pair against the launches it stands for and against the non-split draft kernel."""
+    H, D = 32, 128
+    W, scale = H * D, 1.0 / D ** 0.5
+    i32 = lambda v, n: torch.full((n,), v, dtype=torch.int32, device=dev)
+    for kv in (1024, 2160):
+        T = kv + 64
+        fr = torch.arange(T).float()[:, None] * (1.0 / (10000.0 ** (torch.arange(0, D, 2).float() / D)))[None]
+        cos, sin = fr.cos().contiguous().to(dev), fr.sin().contiguous().to(dev)
+        for G, K in ((1, 4), (1, 8), (2, 4)):
+            cache = (torch.randn((G, T, 2 * W), device=dev) * 0.5).to(torch.bfloat16)
+            qkv = (torch.randn((G * K, 3 * W), device=dev) * 0.5).to(torch.bfloat16)
+            work = qkv.clone()                                       # the non-split draft kernel rotates q in place
+            pos, live, nrow = i32(kv, G), i32(1, G), i32(K, G)
+            pos_j = [i32(kv + j, G) for j in range(K)]
+            kvl_j = [i32(kv + j + 1, G) for j in range(K)]
+            part_d = ops.attn_decode_split_draft_ws(G, K, H, T, dev)
+            part_s = ops.attn_decode_split_ws(G, H, T, dev)
+            out = torch.empty((G * K, W), dtype=torch.bfloat16, device=dev)
+            rows_j = [qkv[j::K] for j in range(K)]                   # row j of every group: [G, 3W], strided
+
+            def split_draft():
+                for _ in range(32):
+                    ops.attn_decode_rope_split_draft_rows(qkv, cache, pos, live, nrow, cos, sin, H, D, scale, K, part_d, out=out)
+
+            def sequential():
+                for _ in range(32):
+                    for j in range(K):
+                        ops.attn_decode_rope_split_rows(rows_j[j], cache, pos_j[j], kvl_j[j], live, cos, sin, H, D, scale, part_s, out=out[j::K])
+
+            def draft_rows():
+                for _ in range(32):
+                    ops.attn_decode_rope_draft_rows(work, cache, pos, live, nrow, cos, sin, H, D, scale, K, out=out)
+
+            graphs = {}
+            for name, fn in (("split_draft_rows", split_draft), ("sequential_split_rows", sequential), ("draft_rows", draft_rows)):
+                fn()
+                torch.cuda.synchronize()
+                graphs[name] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[name]):
+                    fn()
+            ts = {name: [] for name in graphs}
+            for rnd in range(6):                                     # round 0 warms up; the three interleaved per round
+                for name, g in graphs.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    g.replay()
+                    e0.record()
+                    for _ in range(20):
+                        g.replay()
+                    e1.record()
+                    e1.synchronize()
+                    if rnd:
+                        ts[name].append(e0.elapsed_time(e1) / 20 / 32 * 1000.0)
+            for name in graphs:
+                emit(what="split_draft_attn_us", kernel=name, G=G, K=K, kv=kv, us_per_layer=round(statistics.median(ts[name]), 2),
+                     min=round(min(ts[name]), 2), max=round(max(ts[name]), 2))
+            del graphs, cache, part_d, part_s
+            torch.cuda.empty_cache()
+
+
+if a.chunks or (a.skip_model and not a.ragged_past and not a.pool_split and not a.split_draft):
     chunk_bench()
+if a.split_draft:
+    split_draft_attn_bench()
 if a.pool_split:
     rows_bench()
 if a.ragged_past:
@@ -316,6 +393,62 @@ def pool_split_bench(N, context):
     del decs
     torch.cuda.empty_cache()
 
+
+def split_draft_turn_bench():
+    """A turn of --tokens tokens on a cached context with no drafter, a taught one and an untaught one (see the module docstring)."""
+    from myriad_amd.decode_host import NgramDrafter
+    llama.slot_draft = llama.draft_split = True
+    n_new, K, context = a.tokens, a.draft_k, a.pool_context
+    cap = context + n_new + K + 8
+    kw = dict(max_new_tokens=n_new, stop_ids=(), eos_id=-1, min_length=0, weights_version=0)
+    cases = [("session", 1, True)] + [("pool", N, sk) for N in [int(x) for x in a.pool.split(",")] for sk in (True, False)]
+    for kind, N, sk in cases:
+        convs = [ctx(context, 4000 + c) for c in range(N)]
+        if kind == "session":
+            sess = DecodeSession(llama, cap, split=True)
+
+            def run(**dkw):
+                ids = sess.generate(convs[0][0], [convs[0][1]], **kw, **dkw)
+                return [ids[0].tolist()], dict(sess.last_stats)
+        else:
+            dec = llama.slot_decoder(N, cap, split_kv=sk)
+
+            def run(**dkw):
+                got = {c: ids.tolist() for c, ids, _ in dec.run_turns([(c, e[0], k) for c, (e, k) in enumerate(convs)], prefill_batch=8,
+                                                                      **kw, **dkw)}
+                return [got[c] for c in range(N)], dict(dec.last_stats)
+        run()                                                        # fills the caches: every later turn prefills one row ...
+        ref, _ = run()                                               # ... and so repeats this one's ids
+        modes = (("none", lambda: {}), ("taught", lambda: dict(draft=NgramDrafter(ref), draft_k=K)),
+                 ("untaught", lambda: dict(draft=NgramDrafter(), draft_k=K)))
+        ms, last = {m: [] for m, _ in modes}, {}
+        for r in range(a.repeats + 1):                               # repeat 0 warms up (graph captures)
+            for m, mk in modes:
+                dkw = mk()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ids, st = run(**dkw)
+                torch.cuda.synchronize()
+                if r:
+                    ms[m].append((time.perf_counter() - t0) * 1000.0)
+                assert ids == ref, (kind, N, sk, m)
+                last[m] = st
+        for m, _ in modes:
+            st = last[m]
+            emit(what="split_draft_turn_ms", entry=kind, conversations=N, split_kv=bool(st["split_kv"]), drafter=m, draft_k=K if m != "none" else 0,
+                 context=context, tokens=n_new, ms=round(statistics.median(ms[m]), 2), min=round(min(ms[m]), 2), max=round(max(ms[m]), 2),
+                 steps=st["steps"], verify_steps=st.get("verify_steps", 0), draft_accepted=st.get("draft_accepted", 0),
+                 draft_proposed=st.get("draft_proposed", 0), draft_off=st.get("draft_off"))
+        if kind == "session":
+            del sess
+        else:
+            del dec
+        torch.cuda.empty_cache()
+
+
+if a.split_draft:
+    split_draft_turn_bench()
+    sys.exit(0)
 
 if a.pool_split:
     for context in [int(x) for x in a.pool_contexts.split(",")]:

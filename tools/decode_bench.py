@@ -51,6 +51,9 @@ K beside the captured plain one-row step, replayed interleaved from --step-keys 
 of --repeats rounds; every guess is wrong, so each replay moves the position by one), with the kept-guess rate at which each K
 breaks even; then greedy_generate end to end on a prompt of --step-keys rows and a countdown chain of --new tokens with a drafter
 taught the chain, one whose guesses hold in every other window, and none -- the answer is asserted to be the chain each time.
+--draft-k .. --split-kv: the same on the split-KV view (behind llama.draft_split): the verify step's attention is
+mh_attn_decode_rope_split_draft, the plain step's mh_attn_decode_rope_split, and the end-to-end runs go through a
+DecodeSession(split=True); give it --step-keys 1136 or 2160.
 
 --slots S[,S..] --draft-k K[,K..] [--weights ..] measures draft decoding in the decode slots for every (S, K) with S * K <= 64
 (with --sample --modes device, --penalty P and --scores also the verify and plain steps under the per-row tail, and the sampled runs),
@@ -93,6 +96,7 @@ ap.add_argument("--scores", action="store_true", help="the cost of return_scores
 ap.add_argument("--draft-k", default="", help="comma list of K (1..8): time the captured K-row verify step of draft decoding against the "
                 "plain batch-1 step at --step-keys keys for each of --weights, interleaved, medians of --repeats rounds; then end-to-end "
                 "tokens/s on a countdown chain of --new tokens with a drafter taught the chain, one that confirms half of its guesses, none")
+ap.add_argument("--split-kv", action="store_true", help="with --draft-k (batch 1): the plain and the verify step of the split-KV view")
 ap.add_argument("--merge", default="", help="comma list of 0 / 1: bordered / merged LoRA qkv in the token step, timed interleaved")
 a = ap.parse_args()
 # --slots is a string so that it can be a list; from here on a.slots is the single count (0: none or a list) and slot_counts the list
@@ -386,11 +390,15 @@ if a.draft_k:
     # guess is id 0 and never confirmed, so pos moves by one per replay, as in the plain step beside it.
     from myriad_amd import ops
     from myriad_amd.decode_host import NgramDrafter
-    from myriad_amd.decode import _decode_buffers, _draft_view
+    from myriad_amd.decode import DecodeSession, _buffer_view, _decode_buffers, _draft_view
     L = model.llama
+    L.draft_split = bool(a.split_kv)                                 # the switch (MYRIAD_DRAFT_SPLIT), off by default
     Ks = [int(x) for x in a.draft_k.split(",") if x]
     rounds, n_rep = max(1, a.repeats) + 1, a.step_replays           # round 0 is the warm-up of the graph itself
     T_cap = 64 * ((a.step_keys + rounds * n_rep + 16 + 63) // 64)
+    if T_cap > L.cos.shape[0]:                                       # a longer rotary table (the model's default holds 2,048 positions)
+        fr = torch.einsum("i,j->ij", torch.arange(T_cap).float(), 1.0 / (10000.0 ** (torch.arange(0, L.hd, 2).float() / L.hd)))
+        L.cos, L.sin = fr.cos().contiguous().to(dev), fr.sin().contiguous().to(dev)
     gi = torch.Generator().manual_seed(3)
     # the countdown chain of the end-to-end runs below (token 1000+k is followed by 1000+k-1, 1000 stops), written into the
     # embedding / lm-head rows before any packed copy of them is made
@@ -407,6 +415,8 @@ if a.draft_k:
         L.decode_fp8, L.decode_fp4 = kind == "fp8", kind == "fp4"
         L._prepare_decode_weights(1)
         ws = _decode_buffers(L, 1, T_cap)
+        if a.split_kv:
+            ws = _buffer_view(L, ws, True)
         for c in ws["caches"]:
             c[:, :a.step_keys].normal_(0.0, 0.5)
 
@@ -422,7 +432,7 @@ if a.draft_k:
 
         steps = [(0, plain)]
         for K in Ks:
-            dv = _draft_view(L, ws, K, 1.0)
+            dv = _draft_view(L, ws, K, 1.0, None, a.split_kv)
 
             def verify(dv=dv, ws=ws, K=K):
                 L._step_logits(dv)
@@ -450,7 +460,7 @@ if a.draft_k:
             torch.cuda.synchronize()
             if rnd:
                 res[i].append(e0.elapsed_time(e1) / n_rep)
-    print(f"batch-1 token step, {a.step_keys}+ keys, {len(L.layers)} layers; median of {rounds - 1} rounds of {n_rep} replays")
+    print(f"batch-1 token step{' on the split-KV view' if a.split_kv else ''}, {a.step_keys}+ keys, {len(L.layers)} layers; median of {rounds - 1} rounds of {n_rep} replays")
     base = {}
     for i, (kind, K, _, _) in enumerate(configs):
         ts = sorted(res[i])
@@ -478,6 +488,10 @@ if a.draft_k:
             self.n += 1
             return self.good.propose(history, k) if self.n % 2 else [7] * k
 
+    # a session per kind of weights: a change of the decode weights drops a session's cache and graphs, which would charge a
+    # capture to the first run after every switch
+    sessions = {} if a.split_kv else None
+    x_keys = [[("r", j) for j in range(a.step_keys)]]
     e2e = {}
     drafters = [("none", None)] + [(f"{name} K={K}", mk) for K in Ks if K > 1 for name, mk in (("taught", lambda: NgramDrafter([chain])), ("half", Half))]
     for rnd in range(rounds):
@@ -487,12 +501,19 @@ if a.draft_k:
                 dkw = {} if mk is None else dict(draft=mk(), draft_k=int(label.split("=")[1]))
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                ids = L.greedy_generate(x, **kw, **dkw)
+                if sessions is not None and kind not in sessions:
+                    sessions[kind] = DecodeSession(L, a.step_keys + new + 16, split=True)
+                sess = None if sessions is None else sessions[kind]
+                if sess is None:
+                    ids = L.greedy_generate(x, **kw, **dkw)
+                else:                                                # a chat turn: every repeat prefills the whole context
+                    ids = sess.generate(x, x_keys, weights_version=0, reset_reason="bench", **kw, **dkw)
                 torch.cuda.synchronize()
                 dt = time.perf_counter() - t0
                 assert ids[0].tolist() == chain, (label, ids)
                 if rnd:
                     st = L.last_generate_stats
+                    assert sess is None or (sess.last_stats["split_kv"] and st.get("draft_off") is None)
                     e2e.setdefault((kind, label), []).append((dt, st.get("verify_steps", 0), st.get("plain_steps", st["steps"] - 1),
                                                               st.get("draft_accepted", 0), st.get("draft_proposed", 0)))
     print(f"end to end, batch 1, prompt {a.step_keys} rows + {new} tokens of the countdown chain (prefill included); median of {rounds - 1}")
