@@ -177,6 +177,31 @@ int mh_layernorm_bwd_dropout(const float* dy, const float* x, const float* w, fl
                              float eps, float p_in, unsigned long long seed_in, float p_out, unsigned long long seed_out,
                              mh_stream_t s);
 int mh_dropout_keep_mask(float* out, long n, float p, unsigned long long seed, mh_stream_t s);
+/* K33 stochastic depth in the trainable EVA ViT (drop_path.hip; eva_vit.py:162,173-176, timm drop_path with scale_by_keep).
+ * A branch runs on the K kept samples of the batch only: its matrices are COMPACT, [K*N, *] (N rows a sample, batch order); the
+ * residual stream stays full, [B*N, D] f32.  A map is a HOST array slot[B]: slot[b] = the compact sample index of sample b, or
+ * -1 when b is not in the set.  It is checked here (every kept sample names one of 0 .. K-1, each exactly once, K = the count
+ * given) and travels in the kernel arguments: B <= 64 (MH_ERR_UNSUPPORTED above), a bad map is MH_ERR_ARG and nothing is launched.
+ * A NULL map with K = B means every sample in order.  D % 4 == 0, D <= 8192 (the parameter gradients: D <= 4096).
+ *   residual_layernorm: h_out[r] = h[r] + scale * y[compact row] for the samples of slot_in, h[r] (same bits) for the others;
+ *       then xn = LayerNorm(h_out; w, b) as bf16 for the samples of slot_out, at their compact rows.  y == NULL (K_in = 0): no
+ *       branch, h_out may be NULL; xn == NULL (K_out = 0): no norm.  h_out must not be h.
+ *   layernorm_bwd: dx[r] = dres[r] + LayerNorm backward of dy[compact row] at x[r] for the samples of slot_in, dres[r] (same
+ *       bits) for the others; dx_bf16 (optional) = bf16(out_scale * dx) for the samples of slot_out at their compact rows.
+ *   gather_scale: dst = bf16(scale * src) for the samples of slot_out at their compact rows.
+ *   layernorm_param_grads: dgamma (+)= sum dy * xhat, dbeta (+)= sum dy over the compact rows (dy compact [K*N, D], x full); 16
+ *       rows a block, blocks reduced in order: deterministic.  ws: mh_drop_path_param_grads_ws_floats(K, N, D) floats. */
+int mh_drop_path_residual_layernorm(const float* h, const float* y, const int* slot_in, int K_in, float scale, const float* w,
+                                    const float* b, const int* slot_out, int K_out, float* h_out, void* xn_bf16, int B, int N,
+                                    int D, float eps, mh_stream_t s);
+int mh_drop_path_layernorm_bwd(const float* dy, const float* x, const float* w, const float* dres, const int* slot_in, int K_in,
+                               const int* slot_out, int K_out, float out_scale, float* dx, void* dx_bf16, int B, int N, int D,
+                               float eps, mh_stream_t s);
+int mh_drop_path_gather_scale(const float* src, const int* slot_out, int K_out, float scale, void* dst_bf16, int B, int N, int D,
+                              mh_stream_t s);
+long mh_drop_path_param_grads_ws_floats(int K, int N, int D);
+int mh_drop_path_layernorm_param_grads(const float* dy, const float* x, const int* slot_in, int K_in, float* dgamma, float* dbeta,
+                                       int B, int N, int D, float eps, int accumulate, float* ws, long ws_floats, mh_stream_t s);
 /* K30 TN weight-gradient GEMM (trainable Q-Former): out[N,K] (+)= dy^T . x with dy [M,N] (row stride lddy) and x [M,K]
  * (row stride ldx) row-major bf16, fp32 accumulation into out (row stride ldo); accumulate = 0 overwrites.  bias != NULL: the
  * fused bias gradient bias[N] (+)= sum_m dy[m,:].  N % 64 == K % 64 == 0, lddy / ldx multiples of 8, dy / x 16-byte aligned;

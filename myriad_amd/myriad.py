@@ -384,7 +384,19 @@ class MyriadHIP(nn.Module):
         # only each block's input and recomputes the block in the backward (eva_vit.py:176-180)
         self.train_vit = cfg.get("freeze_vit", True) is False
         self.vit_checkpoint = self.train_vit and bool(cfg.get("use_grad_checkpoint", False))
-        ops.ensure_workspace(self._dev)                        # scratch for the automatic split-K GEMM path
+        # drop_path_rate (from_config admits it behind vit_drop_path / MYRIAD_VIT_DROP_PATH): every training forward draws one
+        # keep bit per (block, branch, sample) on the host (eva_vit.drop_path_keep_bits: a pure integer function of the seed, the
+        # data-parallel rank, the optimiser step, the micro-step inside an accumulation window and the position) and the ViT
+        # skips the dropped samples' branches.  Like qformer_dropout_seed the seed defaults to torch's (train.py seeds it with
+        # seed + rank); the rank enters the draw as well, so ranks differ even under one explicit drop_path_seed.
+        self.drop_path_rate = float(cfg.get("drop_path_rate", 0.0)) if self.train_vit else 0.0
+        if not 0.0 <= self.drop_path_rate < 1.0:
+            raise ValueError(f"drop_path_rate {self.drop_path_rate}: must be in [0, 1)")
+        self.drop_path_seed = int(cfg.get("drop_path_seed", torch.initial_seed())) & ((1 << 63) - 1)
+        self.drop_path_rank = 0                                # train_step(dp=...) sets it to dp.rank
+        self.drop_path_step = 0                                # optimiser updates so far (a resumed run sets it to its iteration)
+        self._drop_micro = 0                                   # training forwards since the last update
+        ops.ensure_workspace(self._dev)                       # scratch for the automatic split-K GEMM path
         # the HIP encoder.  Frozen, it is also `visual_encoder`; with freeze_vit: False that name is the nn.Module node that
         # carries the visual_encoder.* parameters (named_parameters() yields the reference's names)
         self.vit = EvaViTHIP(weights, cfg.get("vit_heads", 16), self._dev)
@@ -562,7 +574,8 @@ class MyriadHIP(nn.Module):
         """`Myriad.from_config` / `MiniGPT4.from_config` (myriad.py:456-517, mini_gpt4.py:259-307) with the reference's own
         keys: vit_model, q_former_model, image_size, num_query_token, llama_model, drop_path_rate, use_grad_checkpoint,
         vit_precision, freeze_vit, freeze_qformer, freeze_llama, use_lora, k_shot, round_index, prompt_path,
-        prompt_template, max_txt_len, end_sym, low_resource, device_8bit, ckpt.  The frozen weights and the tokenizer are
+        prompt_template, max_txt_len, end_sym, low_resource, device_8bit, ckpt (drop_path_rate > 0 needs freeze_vit: False and
+        the opt-in vit_drop_path: True or MYRIAD_VIT_DROP_PATH=1; drop_path_seed seeds its draw).  The frozen weights and the tokenizer are
         loaded from the files those keys name (checkpoint.load_reference_weights); `cfg["weights"]` / `cfg["tokenizer"]`
         (an in-memory mapping keyed by the reference's state_dict names, e.g. synthetic.SyntheticWeights) replace the
         files in tests and in bench.py."""
@@ -579,9 +592,15 @@ class MyriadHIP(nn.Module):
             # which GradScaler.unscale_ refuses under amp: nothing to mirror
             raise NotImplementedError("freeze_vit: False needs vit_precision: fp32 (fp32 masters, bf16 working copies); "
                                       f"vit_precision: {get('vit_precision', 'fp16')} (fp16 masters) is not implemented")
-        if get("drop_path_rate", 0):
-            raise NotImplementedError("drop_path_rate > 0 (stochastic depth in the ViT's training forward) is not implemented"
-                                      if train_vit else "drop_path_rate only matters for an unfrozen ViT")
+        rate = get("drop_path_rate", 0)
+        if rate:
+            # stochastic depth (eva_vit.py:162,173-176,276) is opt-in: model key vit_drop_path: True or MYRIAD_VIT_DROP_PATH=1
+            drop_on = bool(get("vit_drop_path", False)) or os.environ.get("MYRIAD_VIT_DROP_PATH") == "1"
+            if not (drop_on and train_vit):
+                raise NotImplementedError("drop_path_rate > 0 (stochastic depth in the ViT's training forward) is not implemented"
+                                          if train_vit else "drop_path_rate only matters for an unfrozen ViT")
+            if not 0.0 <= float(rate) < 1.0:
+                raise ValueError(f"drop_path_rate {rate}: must be in [0, 1)")
         if get("use_grad_checkpoint", False) and not train_vit:
             raise NotImplementedError("use_grad_checkpoint only matters for an unfrozen ViT (freeze_vit: False)")
         keys = ("max_txt_len", "end_sym", "k_shot", "round_index", "fixed_stage", "fixed_taskstage", "tokenizer",
@@ -589,6 +608,10 @@ class MyriadHIP(nn.Module):
                 "lora_r", "lora_alpha", "lora_dropout", "lora_seed", "num_query_token", "llm_eps", "freeze_qformer",
                 "qformer_dropout", "qformer_dropout_seed", "freeze_vit", "use_grad_checkpoint")
         sub = {k: get(k) for k in keys if get(k) is not None}
+        if rate:                                          # accepted above: the constructor draws the keep bits from these
+            sub["drop_path_rate"] = float(rate)
+            if get("drop_path_seed") is not None:
+                sub["drop_path_seed"] = int(get("drop_path_seed"))
         if get("max_txt_len") is None:
             sub["max_txt_len"] = 32                       # from_config defaults (myriad.py:483-484)
         if get("end_sym") is None:
@@ -646,6 +669,16 @@ class MyriadHIP(nn.Module):
             tgt, tmask = enc.input_ids, enc.attention_mask
         return before, after, tgt, tmask
 
+    def _draw_drop_path(self, B: int):
+        """This training forward's stochastic-depth keep bits (host bool [depth, 2, B]) and the blocks' keep probabilities: one
+        draw per (drop_path_seed, rank, optimiser step, micro-step) -- see eva_vit.drop_path_keep_bits."""
+        from .eva_vit import drop_path_keep_bits, drop_path_keep_prob
+        depth = len(self.vit.blocks)
+        keep = drop_path_keep_bits(self.drop_path_seed, self.drop_path_rank, self.drop_path_step, self._drop_micro, depth, B,
+                                   self.drop_path_rate)
+        self._drop_micro += 1
+        return keep, drop_path_keep_prob(self.drop_path_rate, depth)
+
     def encode_img(self, image, maps, stage, save=True, vit_out=None):
         """`Myriad.encode_img` (myriad.py:241-272).  Returns img tokens [B, n_img, Dl] f32."""
         B = image.shape[0]
@@ -655,8 +688,12 @@ class MyriadHIP(nn.Module):
             # the working copies follow the fp32 masters, whoever changed them (fused AdamW, a torch optimiser through the .grad
             # views, load_state_dict): rewritten in place before every use
             self.vit.refresh()
-            x = (self.vit.forward_train(image, checkpoint=self.vit_checkpoint) if save
-                 else self.vit.forward(image))
+            if save and self.drop_path_rate > 0.0:
+                keep, keep_prob = self._draw_drop_path(B)
+                x = self.vit.forward_train(image, checkpoint=self.vit_checkpoint, keep=keep, keep_prob=keep_prob)
+            else:
+                x = (self.vit.forward_train(image, checkpoint=self.vit_checkpoint) if save
+                     else self.vit.forward(image))
         else:
             x = self.vit.forward(image)                                    # [B,257,Dv] f32, frozen
         N = x.shape[1]
@@ -1167,6 +1204,8 @@ class MyriadHIP(nn.Module):
         known: the early tokenizer update and the update behind the early exchange fall back to their late forms (the early
         collective itself stays).  With both off the step issues exactly the launches it issued without them."""
         clip = GradClip.of(max_grad_norm, skip_nonfinite)
+        if dp is not None:
+            self.drop_path_rank = int(getattr(dp, "rank", 0))     # ranks draw different stochastic-depth bits
         with torch.no_grad():
             vit_out = self._take_prefetched_vit(samples)
             if next_samples is not None:
@@ -1220,6 +1259,7 @@ class MyriadHIP(nn.Module):
             if not due:
                 return loss                                   # inside an accumulation window: no exchange, no update
             self._accum_count = 0
+            self.drop_path_step, self._drop_micro = self.drop_path_step + 1, 0
             if dp is not None and dp.world > 1 and overlap:
                 dp.start(self.store.flat_g_comm, self.store.total)   # RCCL exchange on the side HIP stream (grads + use flags)
                 self._pending_update = (dp, lr, weight_decay, beta2, clip)

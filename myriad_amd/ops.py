@@ -1097,6 +1097,207 @@ def layernorm_bwd_dropout(dy, x, w, eps: float, p_in: float = 0.0, seed_in: int 
     return dx, dzb
 
 
+# --------------------------------------------------------------------------- stochastic depth (drop_path.hip)
+DROP_PATH_MAX_B = 64
+
+
+class DropPathMap:
+    """The kept samples of one branch: slot[b] = compact sample index of sample b, or -1 (a host int32 array; the launchers read
+    it on the host and pass it in the kernel arguments).  Built from a per-sample keep sequence (`from_keep`) or from an explicit
+    slot list, which is checked: every entry -1 or in [0, K), the kept entries numbering 0 .. K-1 exactly once each."""
+
+    def __init__(self, slot):
+        if isinstance(slot, torch.Tensor):
+            if slot.is_cuda or slot.dim() != 1 or slot.dtype not in (torch.int32, torch.int64):
+                raise ValueError("DropPathMap: slot must be a 1-D host integer tensor")
+            slot = slot.tolist()
+        slot = list(slot)
+        if not all(isinstance(v, numbers.Integral) and not isinstance(v, bool) for v in slot):
+            raise ValueError("DropPathMap: slot entries must be integers")
+        B = len(slot)
+        if not 1 <= B <= DROP_PATH_MAX_B:
+            raise ValueError(f"DropPathMap: {B} samples (1 .. {DROP_PATH_MAX_B} supported)")
+        kept = [int(v) for v in slot if v >= 0]
+        K = len(kept)
+        if any(v < -1 or v >= B for v in slot):
+            raise ValueError(f"DropPathMap: slot {slot}: entries must be -1 or in [0, {B})")
+        if sorted(kept) != list(range(K)):
+            raise ValueError(f"DropPathMap: slot {slot}: the kept samples must number 0 .. {K - 1}, each once")
+        self.B, self.K = B, K
+        self.slot = torch.tensor([int(v) for v in slot], dtype=torch.int32)
+        self.samples = [b for _, b in sorted((v, b) for b, v in enumerate(slot) if v >= 0)]    # compact index -> sample
+
+    @classmethod
+    def from_keep(cls, keep) -> "DropPathMap":
+        keep = [bool(k) for k in (keep.tolist() if isinstance(keep, torch.Tensor) else keep)]
+        n, slot = 0, []
+        for k in keep:
+            slot.append(n if k else -1)
+            n += int(k)
+        return cls(slot)
+
+    @property
+    def full(self) -> bool:
+        return self.K == self.B
+
+    def ptr(self) -> int:
+        return self.slot.data_ptr()
+
+
+def _dp_map(m, B: int, name: str) -> DropPathMap:
+    if not isinstance(m, DropPathMap):
+        m = DropPathMap(m)
+    if m.B != B:
+        raise ValueError(f"{name}: the map covers {m.B} samples, the batch has {B}")
+    return m
+
+
+def _dp_dense(t, dtype, rows: int, D: int, name: str):
+    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or t.dim() != 2 or tuple(t.shape) != (rows, D)
+            or not t.is_contiguous()):
+        raise ValueError(f"{name}: need a contiguous device {dtype} [{rows}, {D}], got "
+                         f"{(t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t)}")
+
+
+def _dp_vec(t, D: int, name: str):
+    if not isinstance(t, torch.Tensor) or t.dtype != F32 or not t.is_cuda or t.numel() != D or not t.is_contiguous():
+        raise ValueError(f"{name}: need a contiguous device f32 [{D}]")
+
+
+def _dp_dims(B: int, N: int, D: int, name: str, max_d: int = 8192):
+    if N < 1 or D < 4 or D % 4 or D > max_d:
+        raise ValueError(f"{name}: N = {N}, D = {D} (N >= 1, D a multiple of 4, D <= {max_d})")
+
+
+def drop_path_residual_layernorm(h: torch.Tensor, y: Optional[torch.Tensor], keep_in, scale: float, N: int,
+                                 w: Optional[torch.Tensor] = None, b: Optional[torch.Tensor] = None, eps: float = 1e-6,
+                                 keep_out=None, want_h: bool = True):
+    """Stochastic depth, forward (mh_drop_path_residual_layernorm).  h [B*N, D] f32: the residual stream; y [K_in*N, D] f32: the
+    branch's output on the kept samples of `keep_in` (a DropPathMap or a slot list), or None = no branch (then keep_in is None).
+    Returns (h_out, xn): h_out = h + scale * y on kept samples, h's bits on the others (None when want_h is False, which needs
+    y None: h itself is the stream); xn = LayerNorm(h_out; w, b) in bf16 for the samples of `keep_out` ([K_out*N, D], compact;
+    keep_out None = all of them), or None when w is None.  Every argument is checked before the launch (ValueError)."""
+    if not isinstance(h, torch.Tensor) or h.dim() != 2 or N < 1 or h.shape[0] % N:
+        raise ValueError("drop_path_residual_layernorm: h must be [B*N, D]")
+    M, D = h.shape
+    B = M // N
+    _dp_dims(B, N, D, "drop_path_residual_layernorm")
+    _dp_dense(h, F32, M, D, "drop_path_residual_layernorm.h")
+    if not 1 <= B <= DROP_PATH_MAX_B:
+        raise ValueError(f"drop_path_residual_layernorm: {B} samples (1 .. {DROP_PATH_MAX_B} supported)")
+    m_in = m_out = None
+    if y is not None:
+        m_in = _dp_map(keep_in, B, "drop_path_residual_layernorm.keep_in")
+        if m_in.K < 1:
+            raise ValueError("drop_path_residual_layernorm: a branch that keeps nothing has no y (pass y=None)")
+        _dp_dense(y, F32, m_in.K * N, D, "drop_path_residual_layernorm.y")
+        if not want_h:
+            raise ValueError("drop_path_residual_layernorm: a branch output needs h_out")
+    elif keep_in is not None:
+        raise ValueError("drop_path_residual_layernorm: keep_in without y")
+    if (w is None) != (b is None):
+        raise ValueError("drop_path_residual_layernorm: w and b go together")
+    if w is not None:
+        _dp_vec(w, D, "drop_path_residual_layernorm.w")
+        _dp_vec(b, D, "drop_path_residual_layernorm.b")
+        if keep_out is not None:
+            m_out = _dp_map(keep_out, B, "drop_path_residual_layernorm.keep_out")
+            if m_out.K < 1:
+                raise ValueError("drop_path_residual_layernorm: keep_out keeps nothing (pass w=None)")
+    elif keep_out is not None:
+        raise ValueError("drop_path_residual_layernorm: keep_out without a norm")
+    if w is None and not (want_h and y is not None):
+        raise ValueError("drop_path_residual_layernorm: nothing to compute")
+    K_out = 0 if w is None else (B if m_out is None else m_out.K)
+    want_h = want_h and y is not None
+    h_out = torch.empty((M, D), dtype=F32, device=h.device) if want_h else None
+    xn = torch.empty((K_out * N, D), dtype=BF16, device=h.device) if w is not None else None
+    rc = _L().mh_drop_path_residual_layernorm(_p(h), _p(y), m_in.ptr() if m_in else None, m_in.K if m_in else 0, float(scale),
+                                              _p(w), _p(b), m_out.ptr() if m_out else None, K_out, _p(h_out), _p(xn), B, N, D,
+                                              float(eps), _s())
+    _lib.check(rc, "mh_drop_path_residual_layernorm")
+    return h_out, xn
+
+
+def drop_path_layernorm_bwd(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, eps: float, dres: torch.Tensor, keep_in, N: int,
+                            keep_out=None, out_scale: float = 1.0, want_bf16: bool = True):
+    """Stochastic depth, backward (mh_drop_path_layernorm_bwd).  dy [K_in*N, D] f32: the branch's dgrad on its kept samples
+    (`keep_in`); x [B*N, D] f32: the LayerNorm's input; dres [B*N, D] f32: the residual gradient.  Returns (dx f32 [B*N, D],
+    dx_bf16): dx = dres + LayerNorm backward on kept samples, dres's bits on the others; dx_bf16 = bf16(out_scale * dx) of the
+    samples of `keep_out` ([K_out*N, D]; None = all).  Checked before the launch (ValueError)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or N < 1 or x.shape[0] % N:
+        raise ValueError("drop_path_layernorm_bwd: x must be [B*N, D]")
+    M, D = x.shape
+    B = M // N
+    _dp_dims(B, N, D, "drop_path_layernorm_bwd")
+    m_in = _dp_map(keep_in, B, "drop_path_layernorm_bwd.keep_in")
+    if m_in.K < 1:
+        raise ValueError("drop_path_layernorm_bwd: a branch that keeps nothing has no backward")
+    _dp_dense(x, F32, M, D, "drop_path_layernorm_bwd.x")
+    _dp_dense(dres, F32, M, D, "drop_path_layernorm_bwd.dres")
+    _dp_dense(dy, F32, m_in.K * N, D, "drop_path_layernorm_bwd.dy")
+    _dp_vec(w, D, "drop_path_layernorm_bwd.w")
+    m_out = None
+    if keep_out is not None:
+        if not want_bf16:
+            raise ValueError("drop_path_layernorm_bwd: keep_out without the bf16 output")
+        m_out = _dp_map(keep_out, B, "drop_path_layernorm_bwd.keep_out")
+        if m_out.K < 1:
+            raise ValueError("drop_path_layernorm_bwd: keep_out keeps nothing (pass want_bf16=False)")
+    K_out = 0 if not want_bf16 else (B if m_out is None else m_out.K)
+    dx = torch.empty((M, D), dtype=F32, device=x.device)
+    dxb = torch.empty((K_out * N, D), dtype=BF16, device=x.device) if want_bf16 else None
+    rc = _L().mh_drop_path_layernorm_bwd(_p(dy), _p(x), _p(w), _p(dres), m_in.ptr(), m_in.K, m_out.ptr() if m_out else None,
+                                         K_out, float(out_scale), _p(dx), _p(dxb), B, N, D, float(eps), _s())
+    _lib.check(rc, "mh_drop_path_layernorm_bwd")
+    return dx, dxb
+
+
+def drop_path_gather_scale(src: torch.Tensor, keep_out, scale: float, N: int):
+    """bf16(scale * src) of the samples of `keep_out` (None = all), compact [K*N, D]; src [B*N, D] f32."""
+    if not isinstance(src, torch.Tensor) or src.dim() != 2 or N < 1 or src.shape[0] % N:
+        raise ValueError("drop_path_gather_scale: src must be [B*N, D]")
+    M, D = src.shape
+    B = M // N
+    _dp_dims(B, N, D, "drop_path_gather_scale")
+    _dp_dense(src, F32, M, D, "drop_path_gather_scale.src")
+    m_out = _dp_map(keep_out, B, "drop_path_gather_scale.keep_out") if keep_out is not None else None
+    if not 1 <= B <= DROP_PATH_MAX_B:
+        raise ValueError(f"drop_path_gather_scale: {B} samples (1 .. {DROP_PATH_MAX_B} supported)")
+    K = B if m_out is None else m_out.K
+    if K < 1:
+        raise ValueError("drop_path_gather_scale: keep_out keeps nothing")
+    dst = torch.empty((K * N, D), dtype=BF16, device=src.device)
+    rc = _L().mh_drop_path_gather_scale(_p(src), m_out.ptr() if m_out else None, K, float(scale), _p(dst), B, N, D, _s())
+    _lib.check(rc, "mh_drop_path_gather_scale")
+    return dst
+
+
+def drop_path_layernorm_param_grads(dy: torch.Tensor, x: torch.Tensor, eps: float, keep_in, N: int, dgamma: torch.Tensor,
+                                    dbeta: torch.Tensor, accumulate: bool = False):
+    """dgamma (+)= sum dy * xhat(x), dbeta (+)= sum dy over the rows of the kept samples only: dy [K*N, D] f32 compact, x [B*N, D]
+    f32 the LayerNorm's input.  Fixed summation order (16 compact rows a block, blocks in order)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or N < 1 or x.shape[0] % N:
+        raise ValueError("drop_path_layernorm_param_grads: x must be [B*N, D]")
+    M, D = x.shape
+    B = M // N
+    _dp_dims(B, N, D, "drop_path_layernorm_param_grads", max_d=4096)
+    m_in = _dp_map(keep_in, B, "drop_path_layernorm_param_grads.keep_in")
+    if m_in.K < 1:
+        raise ValueError("drop_path_layernorm_param_grads: nothing kept (leave the gradients alone)")
+    _dp_dense(x, F32, M, D, "drop_path_layernorm_param_grads.x")
+    _dp_dense(dy, F32, m_in.K * N, D, "drop_path_layernorm_param_grads.dy")
+    _dp_vec(dgamma, D, "drop_path_layernorm_param_grads.dgamma")
+    _dp_vec(dbeta, D, "drop_path_layernorm_param_grads.dbeta")
+    L = _L()
+    n = L.mh_drop_path_param_grads_ws_floats(m_in.K, N, D)
+    ws = torch.empty((max(n, 1),), dtype=F32, device=x.device)
+    rc = L.mh_drop_path_layernorm_param_grads(_p(dy), _p(x), m_in.ptr(), m_in.K, _p(dgamma), _p(dbeta), B, N, D, float(eps),
+                                              int(accumulate), _p(ws), n, _s())
+    _lib.check(rc, "mh_drop_path_layernorm_param_grads")
+    return dgamma, dbeta
+
+
 def dropout_keep_mask(n: int, p: float, seed: int, device):
     """The keep mask the dropout kernels use: element i = 1/(1-p) if kept, else 0 (flat index i of the masked tensor)."""
     out = torch.empty((n,), dtype=F32, device=device)

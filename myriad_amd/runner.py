@@ -727,6 +727,10 @@ class RunnerBase:
         clip_on = self.max_grad_norm is not None or self.skip_nonfinite_grad
         clip_kw = dict(max_grad_norm=self.max_grad_norm, skip_nonfinite=self.skip_nonfinite_grad) if clip_on else {}
         pending = []
+        if getattr(model, "drop_path_rate", 0.0) > 0.0:
+            # the stochastic-depth draw counts optimiser updates: the count an uninterrupted run has reached at this epoch's start,
+            # so a run resumed from a checkpoint draws the same keep bits
+            model.drop_path_step = epoch * (iters // max(int(self.accum_grad_iters), 1))
         samples = next(loader) if iters > 0 else None
         for i in range(iters):
             samples.update({"epoch": epoch, "num_iters_per_epoch": iters, "iters": i})      # base_task.py:217-223
