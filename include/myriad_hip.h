@@ -875,6 +875,25 @@ int mh_bank_sim_max(const void* q, long q_row0, long q_sample_rows, const void* 
 int mh_bank_sim_finish(const float* part, const int* bank_rows, float* sim, float* simmask, float* amap, int T, int B,
                        int max_chunks, int h, int S, float w, mh_stream_t s);
 
+/* K16c greedy k-centre (farthest-point) coreset selection over one class of the reference bank (csrc/coreset.hip;
+ * vision_expert.py: compact_references; the rule and its cover guarantee are DESIGN section 6).  taps: a HOST array of T device
+ * pointers, one row-major bf16 matrix per tap with row stride ld elements; the class is the rows [row0, row0 + rows) of each.
+ *   dist2(i, s) = sum over taps and columns of (x_t[i, k] - x_t[s, k])^2, bf16 widened to fp32, one fixed fp32 order that
+ *   depends on (D, T) alone;  sel[0] = start, radius2[0] = +inf;  step j: mind[i] = min(mind[i], dist2(i, sel[j])) for every
+ *   row of the class, mind[sel[j]] = -1;  sel[j + 1] = the lowest index among the rows of largest mind, radius2[j + 1] = that
+ *   maximum;  cover2 = max mind after the last step (-1 when n == rows).
+ * Outputs (device): sel [n] int32 (indices relative to row0), radius2 [n], mind [rows], cover2 [1]; mind need not be
+ * initialised.  2 n launches on `s`, no host synchronisation, no float atomics: bitwise reproducible, and independent of row0
+ * and of the rows outside the class, which are never read.  ws: mh_coreset_ws_bytes(rows) bytes of device scratch, 8-byte
+ * aligned (one 8-byte arg-max partial per workgroup of 64 consecutive rows).  Cover guarantee for unit rows and a head that
+ * takes the mean over taps of the per-tap maximum: 0 <= sim_full - sim_coreset <= sqrt(cover2) for any query.
+ * MH_ERR_ARG, with nothing launched and nothing written, for a null pointer (the T tap pointers included; they must be 16-byte
+ * aligned), T outside 1..8, D < 8 or D % 8, ld < D or ld % 8, row0 < 0, rows < 1, n outside 1..rows, start outside
+ * 0..rows-1, a short workspace; MH_ERR_UNSUPPORTED for T * D > 16384 (the centre row staged in LDS: T = 8, D = 2048). */
+long mh_coreset_ws_bytes(int rows);
+int mh_coreset_select(const void* const* taps, int T, long ld, int D, long row0, int rows, int n, int start, int* sel,
+                      float* radius2, float* mind, float* cover2, void* ws, long ws_bytes, mh_stream_t s);
+
 /* K17 streaming localisation metrics for anomaly maps (csrc/seg_metrics.hip; seg_metrics.py, eval_protocol.seg_metrics_from_hist).
  * mh_mask_components: 8-connected components of B binary masks [B, H, W] (one byte per pixel, nonzero = anomalous), one workgroup
  *   per image with the union-find in LDS.  labels [B, H, W] int32: -1 on background, else the smallest linear index y W + x of

@@ -14,7 +14,7 @@ LIB = os.path.join(HERE, "libmyriad_hip.so")
 # the read-out without its stores, gives wrong results on purpose); the product and the tests never load it
 LIB_DBG = os.path.join(HERE, "libmyriad_hip_dbg.so")
 DBG_SOURCES = ["gemm", "gemm_256", "gemm_x4", "attn_seq", "lora"]      # the files that hold a hook
-SOURCES = ["gemm", "gemm_256", "gemm_x4", "gemv", "attention", "attn_decode_split", "attn_decode_draft", "attn_decode_split_draft", "draft", "draft_sample", "attn_ragged", "attn_seq", "attn_full", "norm", "elementwise", "conv", "loss", "sample", "scores", "beam", "beam_sample", "lowrank", "lora", "expert", "expert_bank", "seg_metrics", "image", "selfsup", "optim", "prof", "ctx", "wgrad", "qf_dropout", "drop_path", "lora_merge", "refresh", "version"]
+SOURCES = ["gemm", "gemm_256", "gemm_x4", "gemv", "attention", "attn_decode_split", "attn_decode_draft", "attn_decode_split_draft", "draft", "draft_sample", "attn_ragged", "attn_seq", "attn_full", "norm", "elementwise", "conv", "loss", "sample", "scores", "beam", "beam_sample", "lowrank", "lora", "expert", "expert_bank", "coreset", "seg_metrics", "image", "selfsup", "optim", "prof", "ctx", "wgrad", "qf_dropout", "drop_path", "lora_merge", "refresh", "version"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast"]
 
 

@@ -1,9 +1,25 @@
 """Bookkeeping of the vision expert's per-class reference bank (vision_expert.py: add_references / one_shot_banked): which
 rows of the contiguous per-tap bank tensors belong to which class.  Device-free: the tensors live in VisionExpertHIP, this
-class only says where a class's rows are and how the tensors have to be cut when a class leaves."""
+class only says where a class's rows are and how the tensors have to be cut when a class leaves or shrinks to a coreset."""
 from __future__ import annotations
 
+import math
+import numbers
 from typing import Dict, List, Tuple
+
+
+def keep_rows(keep, rows: int) -> int:
+    """How many of a class's `rows` bank rows a coreset keeps (compact_references): an int is the row count itself, 1..rows; a
+    float in (0, 1] is the share, max(1, ceil(keep * rows)).  ValueError for anything else (1 is one row, 1.0 is every row)."""
+    if isinstance(keep, bool) or not isinstance(keep, (numbers.Integral, float)):
+        raise ValueError(f"keep must be an int row count or a float share in (0, 1], got {keep!r}")
+    if isinstance(keep, numbers.Integral):
+        if not 1 <= int(keep) <= rows:
+            raise ValueError(f"keep = {keep} rows is outside 1..{rows}")
+        return int(keep)
+    if not 0.0 < keep <= 1.0:
+        raise ValueError(f"keep = {keep} is not a share in (0, 1]")
+    return min(rows, max(1, math.ceil(keep * rows)))
 
 
 class BankIndex:
@@ -46,6 +62,16 @@ class BankIndex:
         off = self.total
         self._rows[name] = int(rows)
         return off
+
+    def resize(self, name: str, rows: int) -> Tuple[int, int]:
+        """A class keeps `rows` of its rows (compact_references); returns the (offset, rows) it held: the caller replaces
+        those rows of every tap's tensor by the `rows` kept ones and the classes behind it move down by the difference.  The
+        class keeps its place in the order."""
+        off, old = self.lookup(name)
+        if not 1 <= int(rows) <= old:
+            raise ValueError(f"class {name!r} holds {old} bank rows: cannot resize it to {rows} (1..{old})")
+        self._rows[name] = int(rows)
+        return off, old
 
     def remove(self, name: str) -> Tuple[int, int]:
         """Forget a class; returns the (offset, rows) it held: the caller cuts those rows out of every tap's tensor and the

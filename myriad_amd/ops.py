@@ -2,9 +2,10 @@
 and the current HIP stream; all arithmetic happens in libmyriad_hip.so.  No fallbacks."""
 from __future__ import annotations
 
+import ctypes
 import math
 import numbers
-from typing import Optional
+from typing import NamedTuple, Optional, Sequence
 
 import os
 
@@ -2202,6 +2203,60 @@ def bank_sim_finish(part: torch.Tensor, bank_rows: torch.Tensor, S: int, w: Opti
     _lib.check(_L().mh_bank_sim_finish(_p(part), _p(bank_rows), _p(sim), _p(simmask), _p(amap), T, B, max_chunks, h, S,
                                        float(1.0 / T if w is None else w), _s()), "mh_bank_sim_finish")
     return sim, simmask, amap
+
+
+class CoresetResult(NamedTuple):
+    """coreset_select's outputs, all device tensors: sel int32 [n] (row indices relative to row0, in selection order),
+    radius2 f32 [n] (radius2[0] = +inf), cover2 f32 [1], mind f32 [rows] (-1 on the selected rows)."""
+    sel: torch.Tensor
+    radius2: torch.Tensor
+    cover2: torch.Tensor
+    mind: torch.Tensor
+
+
+def coreset_select(taps: Sequence[torch.Tensor], n: int, *, row0: int = 0, rows: Optional[int] = None,
+                   start: int = 0) -> CoresetResult:
+    """Greedy k-centre (farthest-point) selection of n of the rows [row0, row0 + rows) of `taps`, T contiguous bf16 [R, D]
+    matrices that are summed over in the squared distance (csrc/coreset.hip; the rule is DESIGN section 6).  2 n launches, no
+    host synchronisation."""
+    return _coreset_select_into(None, taps, n, row0, rows, start)
+
+
+def _coreset_select_into(out: Optional[CoresetResult], taps, n: int, row0: int = 0, rows: Optional[int] = None, start: int = 0):
+    """coreset_select writing the four tensors of `out` (the tests frame them in poison); None allocates them."""
+    taps = list(taps)
+    if not 1 <= len(taps) <= 8:
+        raise _lib.MyriadHipError(f"coreset_select: need 1..8 taps, got {len(taps)}")
+    for t, x in enumerate(taps):
+        _chk2d(x, BF16, f"coreset_select.taps[{t}]")
+        if not x.is_contiguous():
+            raise _lib.MyriadHipError(f"coreset_select.taps[{t}]: need a contiguous tensor, got strides {x.stride()}")
+        if x.shape != taps[0].shape or x.device != taps[0].device:
+            raise _lib.MyriadHipError(f"coreset_select.taps[{t}]: {tuple(x.shape)} on {x.device}, taps[0] is "
+                                      f"{tuple(taps[0].shape)} on {taps[0].device}")
+    R, D = taps[0].shape
+    row0, start, n = int(row0), int(start), int(n)
+    rows = R - row0 if rows is None else int(rows)
+    if D < 8 or D % 8:
+        raise _lib.MyriadHipError(f"coreset_select: D = {D} is not a multiple of 8 (16-byte loads)")
+    if row0 < 0 or rows < 1 or row0 + rows > R:
+        raise _lib.MyriadHipError(f"coreset_select: the class [{row0}, {row0 + rows}) is not a non-empty range of the {R} rows")
+    if not 1 <= n <= rows or not 0 <= start < rows:
+        raise _lib.MyriadHipError(f"coreset_select: n = {n} outside 1..{rows} or start = {start} outside 0..{rows - 1}")
+    dev = taps[0].device
+    if out is None:
+        out = CoresetResult(torch.empty((n,), dtype=torch.int32, device=dev), torch.empty((n,), dtype=F32, device=dev),
+                            torch.empty((1,), dtype=F32, device=dev), torch.empty((rows,), dtype=F32, device=dev))
+    for t, dt, shape, name in ((out.sel, torch.int32, (n,), "sel"), (out.radius2, F32, (n,), "radius2"),
+                               (out.cover2, F32, (1,), "cover2"), (out.mind, F32, (rows,), "mind")):
+        if t.dtype != dt or not t.is_cuda or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.MyriadHipError(f"coreset_select.out.{name}: need contiguous cuda {dt} {shape}, got {t.dtype} {tuple(t.shape)}")
+    ws_bytes = _L().mh_coreset_ws_bytes(rows)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    ptrs = (ctypes.c_void_p * len(taps))(*(x.data_ptr() for x in taps))
+    _lib.check(_L().mh_coreset_select(ptrs, len(taps), D, D, row0, rows, n, start, _p(out.sel), _p(out.radius2), _p(out.mind),
+                                      _p(out.cover2), _p(ws), ws_bytes, _s()), f"mh_coreset_select T={len(taps)} D={D} rows={rows}")
+    return out
 
 
 SEG_HIST_BINS = 1 << 20      # keys of seg_hist_update: the top 20 bits of the order-preserving transform of the fp32 bits

@@ -17,16 +17,18 @@ in LDS) -> out_proj GEMM(+bias +fp32 residual) -> LN -> fc1 GEMM(+bias +erf-GELU
 kernels as the EVA encoder; the query x reference similarity is one bf16 MFMA GEMM per sample and tap on L2-normalised
 tokens, followed by a row-max; everything else is the small fp32 kernels of csrc/expert.hip.  With the references of a class
 registered once (`add_references`), the one-shot head is csrc/expert_bank.hip instead: one MFMA launch per tap for the whole
-batch against the class's stored rows, and one finishing launch.
+batch against the class's stored rows, and one finishing launch.  A class registered from many references can be cut down
+to a greedy k-centre coreset of its rows (`compact_references`, csrc/coreset.hip).
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 from . import ops
-from .expert_bank import BankIndex
+from .expert_bank import BankIndex, keep_rows
 
 BF16, F32 = torch.bfloat16, torch.float32
 PRE, TRK, HEAD = "modality_preprocessors.vision.", "modality_trunks.vision.", "modality_heads.vision."
@@ -128,6 +130,7 @@ class VisionExpertHIP:
         self._bank_index = BankIndex()
         self._bank: List[torch.Tensor] = []
         self._bank_text: Dict[str, torch.Tensor] = {}
+        self._bank_meta: Dict[str, dict] = {}              # rows registered, cover radius of the last compact_references
 
     @torch.no_grad()
     def zero_shot(self, images: torch.Tensor, text_feats: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -202,7 +205,7 @@ class VisionExpertHIP:
     # and tap.
     @torch.no_grad()
     def add_references(self, name: str, ref_images: torch.Tensor, text_feats: Optional[torch.Tensor] = None,
-                       rot90: bool = False) -> None:
+                       rot90: bool = False, coreset=None) -> None:
         """Register the k normal references of class `name` (ref_images [k,3,224,224]): one trunk pass, every tap
         L2-normalised as `one_shot` does, class-token rows dropped, the k*L bf16 rows appended to the tap's bank tensor.
         `text_feats` [2, C], the class's [normal, abnormal] text pair, is kept beside them for `forward_banked`.  A name that is
@@ -210,7 +213,9 @@ class VisionExpertHIP:
         `rot90`: register each reference in its four exact quarter turns (torch.rot90 by 0, 1, 2, 3 quarter turns,
         reference-major, then the turn), the row layout of `encode_image_for_one_shot_with_aug` (adrefexpert_v2.py:171-195).
         The reference rotates through kornia's `rotate` (an interpolating warp with reflection padding); parity with that
-        interpolation is not claimed, only the exact quarter turns are."""
+        interpolation is not claimed, only the exact quarter turns are.
+        `coreset`: None keeps every row; a value is handed to `compact_references(name, coreset)` after registering (a value
+        out of range raises ValueError before the bank changes: a class registered under `name` stays as it was)."""
         imgs = ref_images.to(self.dev, F32)
         if imgs.dim() != 4 or imgs.shape[0] < 1:
             raise ValueError(f"ref_images must be [k,3,224,224] with k >= 1, got {tuple(ref_images.shape)}")
@@ -223,21 +228,76 @@ class VisionExpertHIP:
             _, N, D = t.shape
             rn, _ = ops.l2norm_rows(t.reshape(k * N, D), eps=1e-8)
             rows.append(rn.view(k, N, D)[:, 1:].reshape(k * (N - 1), D))
+        if coreset is not None:
+            keep_rows(coreset, rows[0].shape[0])                                      # ValueError before the bank is touched
         if name in self._bank_index:
             self.drop_references(name)
         self._bank_index.append(name, rows[0].shape[0])
         self._bank = [torch.cat([old, new], dim=0) for old, new in zip(self._bank, rows)] if self._bank else rows
+        self._bank_meta[name] = dict(registered=rows[0].shape[0], cover_radius=None)
         if text_feats is not None:
             self._bank_text[name] = text_feats.detach().to(self.dev, F32).reshape(2, -1).contiguous()
+        if coreset is not None:
+            self.compact_references(name, coreset)
 
     def drop_references(self, name: str) -> None:
         """Forget a class: its rows are cut out of every tap's tensor (KeyError naming the class if it is not registered)."""
         off, n = self._bank_index.remove(name)
         self._bank_text.pop(name, None)
+        self._bank_meta.pop(name, None)
         self._bank = [torch.cat([t[:off], t[off + n:]], dim=0) for t in self._bank] if len(self._bank_index) else []
 
     def bank_classes(self) -> List[str]:
         return self._bank_index.names()
+
+    @staticmethod
+    def coreset_projection(proj_dim: int, D: int, seed: int) -> torch.Tensor:
+        """The random projection of one tap (host, bf16 [proj_dim, D]): randn from a CPU generator seeded with `seed`, divided
+        by sqrt(proj_dim).  compact_references seeds tap t with seed + t."""
+        g = torch.Generator("cpu").manual_seed(int(seed))
+        return (torch.randn(proj_dim, D, generator=g) / math.sqrt(proj_dim)).to(BF16)
+
+    @torch.no_grad()
+    def compact_references(self, name: str, keep, *, proj_dim: Optional[int] = None, seed: int = 0, start: int = 0) -> dict:
+        """Replace the bank rows of class `name` by a greedy k-centre (farthest-point) coreset of them (csrc/coreset.hip; the
+        rule and its guarantee are DESIGN section 6): the kept rows of every tap, in selection order, so that a later call
+        with a smaller `keep` selects the same prefix.  `keep`: an int row count, or a float share in (0, 1] meaning
+        max(1, ceil(keep * rows)).  One centre serves all taps (the squared distance sums over them), and for any query
+        0 <= sim_full - sim_coreset <= cover_radius.  Rows and maps of every other class keep their bits.
+        `proj_dim` = P (P % 8 == 0, 8 <= P <= D, D % 64 == 0): the selection runs on the bf16 products of the class's rows with
+        `coreset_projection(P, D, seed + t)` per tap (PatchCore's Johnson-Lindenstrauss step); the rows kept are the original
+        rows, `cover_radius` is then the radius in the projected space and `exact` is False.
+        Returns rows_before, rows_after, cover_radius (sqrt(max(cover2, 0))), exact, sel (host list of the kept rows' indices
+        inside the class).  KeyError for an unknown class, ValueError for `keep`, `start` or `proj_dim` out of range."""
+        off, rows = self._bank_index.lookup(name)
+        n = keep_rows(keep, rows)
+        if not 0 <= int(start) < rows:
+            raise ValueError(f"start = {start} is outside the class's rows 0..{rows - 1}")
+        D = self._bank[0].shape[1]
+        if proj_dim is None:
+            res = ops.coreset_select(self._bank, n, row0=off, rows=rows, start=start)
+        else:
+            P = int(proj_dim)
+            if P % 8 or not 8 <= P <= D:
+                raise ValueError(f"proj_dim = {proj_dim} must be a multiple of 8 in 8..{D}")
+            if D % 64:
+                raise ValueError(f"proj_dim needs a tap width that is a multiple of 64 (the GEMM's K), the bank has D = {D}")
+            proj = [ops.gemm(t[off:off + rows], self.coreset_projection(P, D, seed + i).to(self.dev))
+                    for i, t in enumerate(self._bank)]
+            res = ops.coreset_select(proj, n, start=start)
+        sel = res.sel.long()
+        self._bank = [torch.cat([t[:off], t[off:off + rows].index_select(0, sel), t[off + rows:]], dim=0) for t in self._bank]
+        self._bank_index.resize(name, n)
+        radius = math.sqrt(max(float(res.cover2), 0.0))
+        self._bank_meta.setdefault(name, dict(registered=rows, cover_radius=None))["cover_radius"] = radius
+        return dict(rows_before=rows, rows_after=n, cover_radius=radius, exact=proj_dim is None, sel=res.sel.tolist())
+
+    def bank_stats(self, name: str) -> dict:
+        """rows the class holds, rows it was registered with, and the cover_radius of its last compact_references (None if
+        it was never compacted).  KeyError for an unknown class."""
+        _, rows = self._bank_index.lookup(name)
+        meta = self._bank_meta.get(name, dict(registered=rows, cover_radius=None))
+        return dict(rows=rows, rows_registered=meta["registered"], cover_radius=meta["cover_radius"])
 
     def _one_shot_banked_from_taps(self, qt, names: Sequence[str]):
         B, N, D = qt[0].shape

@@ -3,7 +3,10 @@
 + zero-shot and one-shot map heads, synthetic weights.  python tools/expert_bench.py [--batch 8] [--k 1]
 --bank: the per-class reference bank against today's one_shot in one process, variants interleaved, medians of --reps:
 (a) the whole call, one_shot(images, refs) vs one_shot_banked(images, names), and add_references per class;
-(b) the head alone on identical taps, the per-sample GEMM + rowmax_skip loop vs bank_sim_max per tap + bank_sim_finish."""
+(b) the head alone on identical taps, the per-sample GEMM + rowmax_skip loop vs bank_sim_max per tap + bank_sim_finish.
+--coreset [--refs 200]: a full-shot class of synthetic unit rows compacted by compact_references to 10 % and 1 %, exact and with
+proj_dim 128, configurations interleaved, medians of --reps: the selection in ms and us per iteration beside its floor, the head
+alone and one_shot_banked on the full bank against each coreset, and the largest loss of similarity beside cover_radius."""
 import argparse, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -16,6 +19,8 @@ ap.add_argument("--batch", type=int, default=8)
 ap.add_argument("--k", type=int, default=1)
 ap.add_argument("--blocks", type=int, default=32)
 ap.add_argument("--bank", action="store_true", help="compare the reference bank with one_shot (see the module docstring)")
+ap.add_argument("--coreset", action="store_true", help="greedy k-centre coreset of a full-shot class (compact_references)")
+ap.add_argument("--refs", type=int, default=200, help="--coreset: references of the class (256 bank rows each)")
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--cpu", type=int, default=0, help="also time the oracle trunk (oracle/expert_ref.vision_trunk, fp32) on this many host threads, 2 images")
 a = ap.parse_args()
@@ -97,6 +102,113 @@ def bank_bench():
           f"finish {med['head_banked']*1e6:.0f} us in {launches['head_banked']} library calls   x{med['head_loop']/med['head_banked']:.2f}   "
           f"(both include the l2norm_rows launches; the loop also normalises the reference rows)")
 
+
+def coreset_bench():
+    """A full-shot class of --refs references (256 rows each) of synthetic unit rows, compacted to 10 % and 1 %, exact and with
+    a 128-wide projection: the selection's time per iteration beside its floor, what the coreset saves in the head, and what
+    it costs in similarity beside the cover radius."""
+    import math
+    from myriad_amd.expert_bank import BankIndex
+    T, rows = len(layers), a.refs * 256
+    g = torch.Generator(device=dev).manual_seed(3)
+
+    def unit(x):
+        return (x / x.norm(dim=-1, keepdim=True)).to(torch.bfloat16)
+
+    # rows scattered around 4096 directions per tap (row i around direction i % 4096 in every tap): near-duplicates, as the
+    # patches of aligned normal images are; queries around the same directions
+    centres = [torch.randn(4096, D, device=dev, generator=g) / math.sqrt(D) for _ in range(T)]
+    full = [unit(c[torch.arange(rows, device=dev) % 4096] + 0.5 * torch.randn(rows, D, device=dev, generator=g) / math.sqrt(D))
+            for c in centres]
+    nq = 64
+    qt = [(c[torch.randint(0, 4096, (nq * N,), device=dev, generator=g)]
+           + 0.5 * torch.randn(nq * N, D, device=dev, generator=g) / math.sqrt(D)).view(nq, N, D) for c in centres]
+
+    def write_full():
+        ex._bank_index, ex._bank_text, ex._bank_meta = BankIndex(), {}, {}
+        ex._bank_index.append("full", rows)
+        ex._bank = list(full)
+
+    def sims(names):
+        """The head of _one_shot_banked_from_taps on the 64 synthetic queries, keeping sim."""
+        out = []
+        for b0 in range(0, nq, 8):
+            q8 = [t[b0:b0 + 8] for t in qt]
+            L = N - 1
+            ranges = [ex._bank_index.lookup(n) for n in names]
+            part = torch.empty((T, 8, max(ops.bank_sim_chunks(r) for _, r in ranges), L), dtype=torch.float32, device=dev)
+            dr = None
+            for i, (q, bank) in enumerate(zip(q8, ex._bank)):
+                qn, _ = ops.l2norm_rows(q.reshape(8 * N, D), eps=1e-8)
+                _, dr = ops.bank_sim_max(qn, bank, ranges, L, 1, N, out=part[i], dev_ranges=dr)
+            out.append(ops.bank_sim_finish(part, dr[1], ex.out_size)[0])
+        return torch.cat(out)
+
+    names = ["full"] * B
+    write_full()
+    sim_full = sims(["full"] * 8)
+    q8 = [t[:B].contiguous() for t in qt]
+    configs = [(0.10, None), (0.01, None), (0.10, 128), (0.01, 128)]
+    t_sel = {c: [] for c in configs}
+    info = {}
+    for rep in range(a.reps + 1):                                    # round 0 warms every configuration up
+        for c in configs:
+            write_full()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            info[c] = ex.compact_references("full", c[0], proj_dim=c[1])     # returns after reading cover2: synchronised
+            if rep:
+                t_sel[c].append(time.perf_counter() - t0)
+    bank_bytes = T * rows * D * 2
+    print(f"coreset, {a.refs} references = {rows} rows x D {D} x {T} taps ({bank_bytes/1e6:.0f} MB), medians of {a.reps} (interleaved):")
+    for c in configs:
+        n = info[c]["rows_after"]
+        med = statistics.median(t_sel[c])
+        if c[1] is None:
+            floor = f"byte floor {bank_bytes/6.29e12*1e6:.1f} us (bank bytes / 6.29 TB/s)"
+        else:
+            floor = (f"floor 2 launch boundaries = 3.4-3.8 us (the projected rows, {T*rows*c[1]*2/1e6:.0f} MB, stay in the "
+                     f"Infinity Cache); includes the {T} projection GEMMs")
+        print(f"  keep {c[0]:.2f} proj {c[1]}: {n} rows  selection {med*1e3:.1f} ms ({min(t_sel[c])*1e3:.1f} .. {max(t_sel[c])*1e3:.1f})"
+              f"  {med/n*1e6:.1f} us per iteration  [{floor}]  cover_radius {info[c]['cover_radius']:.4f}")
+    # the head and the whole call on the full bank against the coresets, and what the similarity lost
+    banks = {"full": (list(full), rows)}
+    for c in configs:
+        write_full()
+        ex.compact_references("full", c[0], proj_dim=c[1])
+        banks[f"keep {c[0]:.2f} proj {c[1]}"] = (list(ex._bank), ex._bank_index.lookup("full")[1])
+
+    def use(key):
+        tensors, r = banks[key]
+        ex._bank_index = BankIndex()
+        ex._bank_index.append("full", r)
+        ex._bank = list(tensors)
+
+    times = {(key, what): [] for key in banks for what in ("head", "call")}
+    for rep in range(a.reps + 1):
+        for key in banks:
+            use(key)
+            for what, fn, inner in (("head", lambda: ex._one_shot_banked_from_taps(q8, names), 8),
+                                    ("call", lambda: ex.one_shot_banked(images, names), 2)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(inner):
+                    fn()
+                torch.cuda.synchronize()
+                if rep:
+                    times[(key, what)].append((time.perf_counter() - t0) / inner)
+    for key in banks:
+        use(key)
+        drop = float((sim_full - sims(["full"] * 8)).max()) if key != "full" else 0.0
+        c = next((info[c] for c in configs if key == f"keep {c[0]:.2f} proj {c[1]}"), None)
+        print(f"  {key}: {banks[key][1]} rows  head alone (batch {B}) {statistics.median(times[(key, 'head')])*1e6:.0f} us   "
+              f"one_shot_banked {statistics.median(times[(key, 'call')])*1e3:.2f} ms   max sim_full - sim_coreset over {nq} "
+              f"queries {drop:.4f}" + (f"   cover_radius {c['cover_radius']:.4f}" + ("" if c["exact"] else " (projected space)") if c else ""))
+
+
+if a.coreset:
+    coreset_bench()
+    sys.exit(0)
 
 if a.bank:
     bank_bench()
