@@ -28,7 +28,7 @@ def _stale(out, deps):
 def build(force: bool = False, verbose: bool = True) -> str:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(OBJ, exist_ok=True)
-    hdrs = [os.path.join(CSRC, h) for h in ("common.h", "gemv_pack.h", "attn_frag.h", "attn_tile.h", "smp_rng.h", "smp_rows.h", "expert_map.h")]
+    hdrs = [os.path.join(CSRC, h) for h in ("common.h", "gemv_pack.h", "attn_frag.h", "attn_tile.h", "attn_one_query.h", "smp_rng.h", "smp_rows.h", "expert_map.h")]
     # the 256x256x64 GEMM's K loop is written by a generator (the schedule lives there); regenerate when it is newer
     gen, inc = os.path.join(CSRC, "gen_gemm_x4.py"), os.path.join(CSRC, "gemm_x4_loop.inc")
     if force or _stale(inc, [gen]):

@@ -16,6 +16,7 @@
 //   dK/dV computes S = Q.K^T (lane owns one key column) for the same reason.  The only transposed LDS images
 //   are V^T / K^T / Q^T / dO^T, built while staging.  Softmax statistics and accumulators are fp32.
 #include "attn_tile.h"
+#include "attn_one_query.h"
 
 struct AttnParams {
   const bf16_t* q;
@@ -438,12 +439,10 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnParams p) {
 // row pos_dev[b] (< T_cap: the host's to keep) instead of the shared pos_dev[0], and a row with live[b] == 0 touches
 // neither qkv nor the cache and writes a zero output row.  live[b] is uniform over the workgroup, so the idle exit is a
 // scalar branch taken by all 16 waves, ahead of the first barrier.  ROWS = false compiles to the code it was before.
-// attn_ragged.hip (one_row_attention) repeats phases 1 to 3 expression for expression for a one-row prefill segment, and
-// tests/test_ragged_past_gpu.py holds the two to the same bits: change them together.
-#define DNW 16
+// The arithmetic is attn_one_query.h's, which the draft, ragged one-row and split kernels call too.
 template <bool ROWS>
-__global__ __launch_bounds__(DNW * 64) void attn_decode_kernel(AttnParams p) {
-  extern __shared__ float dsm[];                 // [Sk] scores, then [DNW][128] partial outputs
+__global__ __launch_bounds__(OQ_WAVES * 64) void attn_decode_kernel(AttnParams p) {
+  extern __shared__ float dsm[];                 // [Sk] scores, then [OQ_WAVES][128] partial outputs
   const int b = blockIdx.x / p.H, h = blockIdx.x % p.H;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (ROWS && !p.live[b]) {
@@ -463,17 +462,8 @@ __global__ __launch_bounds__(DNW * 64) void attn_decode_kernel(AttnParams p) {
       const int which = tid / items, i = (tid % items) * 4;
       bf16_t* e = src + which * W + h * D + i;
       const int ps = p.pos[b];
-      const float4_t c4 = *reinterpret_cast<const float4_t*>(p.cs + (size_t)ps * half + i);
-      const float4_t s4 = *reinterpret_cast<const float4_t*>(p.sn + (size_t)ps * half + i);
-      const short4_t a = *reinterpret_cast<const short4_t*>(e);
-      const short4_t bb = *reinterpret_cast<const short4_t*>(e + half);
       short4_t oa, ob;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const float x1 = bf2f((bf16_t)a[t]), x2 = bf2f((bf16_t)bb[t]);
-        oa[t] = (short)f2bf(x1 * c4[t] - x2 * s4[t]);
-        ob[t] = (short)f2bf(x2 * c4[t] + x1 * s4[t]);
-      }
+      oq_rope4(e, half, p.cs, p.sn, ps, i, oa, ob);
       bf16_t* dst = which == 0 ? e : crow + h * D + i;
       *reinterpret_cast<short4_t*>(dst) = oa;
       *reinterpret_cast<short4_t*>(dst + half) = ob;
@@ -489,7 +479,7 @@ __global__ __launch_bounds__(DNW * 64) void attn_decode_kernel(AttnParams p) {
   float* sc = dsm;
   float* part = dsm + ((p.Sk + 63) & ~63);
   // phase 1: scores
-  const int sub = lane & 15, kq = lane >> 4;     // 16 lanes per key, dims sub*8 .. +7
+  const int sub = lane & 15;                     // 16 lanes per key, dims sub*8 .. +7
   float qf[8];
   const bool dim_ok = sub * 8 < D;
   {
@@ -498,82 +488,20 @@ __global__ __launch_bounds__(DNW * 64) void attn_decode_kernel(AttnParams p) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) qf[e] = bf2f((bf16_t)qv[e]) * p.scale;
   }
-  for (int j0 = 0; j0 < len; j0 += 2 * DNW * 4) {
-    short8_t kv[2];
-    int jj[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      jj[u] = j0 + u * DNW * 4 + wave * 4 + kq;
-      kv[u] = (short8_t){0, 0, 0, 0, 0, 0, 0, 0};
-      if (jj[u] < len && dim_ok) kv[u] = *reinterpret_cast<const short8_t*>(kp + (size_t)jj[u] * p.ldk + sub * 8);
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      float s = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s += qf[e] * bf2f((bf16_t)kv[u][e]);
-      s += __shfl_xor(s, 1, 64);
-      s += __shfl_xor(s, 2, 64);
-      s += __shfl_xor(s, 4, 64);
-      s += __shfl_xor(s, 8, 64);
-      if (sub == 0 && jj[u] < len) sc[jj[u]] = s;
-    }
-  }
+  oq_scores(sc, qf, dim_ok, len, wave, lane,
+            [&](int j, int) { return *reinterpret_cast<const short8_t*>(kp + (size_t)j * p.ldk + sub * 8); });
   __syncthreads();
   // phase 2: softmax statistics (each wave for itself)
-  float mx = -INFINITY;
-  for (int j = lane; j < len; j += 64) mx = fmaxf(mx, sc[j]);
-  mx = wave_max(mx);
-  float sum = 0.f;
-  for (int j = lane; j < len; j += 64) sum += __expf(sc[j] - mx);
-  sum = wave_sum(sum);
-  // phase 3: o = sum_j p_j V[j]; lane owns dims 2*lane, 2*lane+1; wave w takes keys w, w+DNW, ...
-  float o0 = 0.f, o1 = 0.f;
+  float mx, sum;
+  oq_softmax_stats(sc, len, lane, mx, sum);
+  // phase 3: o = sum_j p_j V[j]; lane owns dims 2*lane, 2*lane+1; wave w takes keys w, w+OQ_WAVES, ...
+  float o0, o1;
   const bool own = 2 * lane < D;
-  int j = wave;
-  for (; j + 7 * DNW < len; j += 8 * DNW) {
-    unsigned vv[8];
-    float pj[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      vv[u] = own ? *reinterpret_cast<const unsigned*>(vp + (size_t)(j + DNW * u) * p.ldv + 2 * lane) : 0u;
-      pj[u] = __expf(sc[j + DNW * u] - mx);
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      o0 += pj[u] * bf2f((bf16_t)(vv[u] & 0xffffu));
-      o1 += pj[u] * bf2f((bf16_t)(vv[u] >> 16));
-    }
-  }
-  {                                              // remainder: up to 7 keys, loads issued together
-    unsigned vv[7];
-    float pj[7];
-#pragma unroll
-    for (int u = 0; u < 7; ++u) {
-      const int jr = j + DNW * u;
-      const bool ok = jr < len;
-      vv[u] = (own && ok) ? *reinterpret_cast<const unsigned*>(vp + (size_t)jr * p.ldv + 2 * lane) : 0u;
-      pj[u] = ok ? __expf(sc[jr] - mx) : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < 7; ++u) {
-      o0 += pj[u] * bf2f((bf16_t)(vv[u] & 0xffffu));
-      o1 += pj[u] * bf2f((bf16_t)(vv[u] >> 16));
-    }
-  }
+  oq_pv(sc, mx, len, wave, own, [&](int j) { return *reinterpret_cast<const unsigned*>(vp + (size_t)j * p.ldv + 2 * lane); }, o0, o1);
   part[wave * 128 + 2 * lane] = o0;
   part[wave * 128 + 2 * lane + 1] = o1;
   __syncthreads();
-  if (wave == 0 && own) {
-    const float inv = len > 0 ? 1.f / sum : 0.f;
-    float r0 = 0.f, r1 = 0.f;
-#pragma unroll
-    for (int w = 0; w < DNW; ++w) {
-      r0 += part[w * 128 + 2 * lane];
-      r1 += part[w * 128 + 2 * lane + 1];
-    }
-    *reinterpret_cast<unsigned*>(p.o + (size_t)b * p.o_bs + h * D + 2 * lane) = pack_bf2(r0 * inv, r1 * inv);
-  }
+  if (wave == 0 && own) oq_sum_store(part, lane, sum, len, p.o + (size_t)b * p.o_bs + h * D + 2 * lane);
   if (p.lse && tid == 0) p.lse[(size_t)b * p.H + h] = len > 0 ? mx + __logf(sum) : -INFINITY;
 }
 
@@ -671,8 +599,8 @@ extern "C" int mh_attn_fwd(const void* q, const void* k, const void* v, void* o,
   if (rc) return rc;
   p.bias = bias; p.kv_len = kv_len; p.causal = causal;
   if (Sq == 1 && !bias && Sk <= 8192 && (ldv % 2) == 0) {   // KV-cache decode (causal or not: the one query sees every valid key)
-    const size_t sh = (((size_t)Sk + 63) & ~(size_t)63) * 4 + DNW * 128 * 4;
-    hipLaunchKernelGGL(attn_decode_kernel<false>, dim3(B * H), dim3(DNW * 64), sh, stream, p);
+    const size_t sh = (((size_t)Sk + 63) & ~(size_t)63) * 4 + OQ_WAVES * 128 * 4;
+    hipLaunchKernelGGL(attn_decode_kernel<false>, dim3(B * H), dim3(OQ_WAVES * 64), sh, stream, p);
     MH_CHECK_LAUNCH();
     return MH_OK;
   }
@@ -702,9 +630,9 @@ static int launch_decode_rope(void* qkv, long ld_qkv, void* cache, long cache_bs
   p.ldq = (int)ld_qkv; p.ldk = (int)ld_cache; p.ldv = (int)ld_cache; p.ldo = (int)ldo;
   p.scale = scale; p.causal = 0; p.q_off = T_cap - 1;
   p.qkv = (bf16_t*)qkv; p.ld_qkv = ld_qkv; p.cs = cos_tab; p.sn = sin_tab; p.pos = pos; p.pos_dev = pos_dev; p.live = live;
-  const size_t sh = (((size_t)T_cap + 63) & ~(size_t)63) * 4 + DNW * 128 * 4;
-  if (live) hipLaunchKernelGGL(attn_decode_kernel<true>, dim3(B * H), dim3(DNW * 64), sh, stream, p);
-  else hipLaunchKernelGGL(attn_decode_kernel<false>, dim3(B * H), dim3(DNW * 64), sh, stream, p);
+  const size_t sh = (((size_t)T_cap + 63) & ~(size_t)63) * 4 + OQ_WAVES * 128 * 4;
+  if (live) hipLaunchKernelGGL(attn_decode_kernel<true>, dim3(B * H), dim3(OQ_WAVES * 64), sh, stream, p);
+  else hipLaunchKernelGGL(attn_decode_kernel<false>, dim3(B * H), dim3(OQ_WAVES * 64), sh, stream, p);
   MH_CHECK_LAUNCH();
   return MH_OK;
 }

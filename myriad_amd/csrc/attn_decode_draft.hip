@@ -1,17 +1,16 @@
 // K-row token-step attention for ONE sequence per group (draft-and-verify greedy decoding, mh_attn_decode_rope_draft): row
 // g*K + j of qkv is the token at position pos[g] + j of sequence g.  Grid = G*K*H workgroups; workgroup (g, j, h) is
-// attn_decode_kernel (attention.hip) for that row alone at position pos[g] + j, its rotary block and phases 1 to 3 repeated
-// expression for expression, so the out row, the rotated q and the cache row carry the bits of K sequential mh_attn_decode_rope
-// steps (tests/test_draft_kernels_gpu.py holds the two to the same bits: change them together).
+// attn_decode_kernel (attention.hip) for that row alone at position pos[g] + j; both call the arithmetic in attn_one_query.h, so
+// the out row, the rotated q and the cache row carry the bits of K sequential mh_attn_decode_rope steps
+// (tests/test_draft_kernels_gpu.py holds the two to the same bits).
 //
 // The K rows depend on each other: row j sees the keys of rows 0 .. j-1 of the same launch, whose cache rows sibling workgroups
 // are writing.  No workgroup reads a cache row >= pos[g].  Instead workgroup j rotates the k of rows 0 .. j itself, from qkv
 // (whose k and v columns nobody writes), into LDS -- the same fp32 rotate-half and the same one rounding to bf16 as the cache row
 // gets -- and reads those rows' v straight from qkv.  Only workgroup j writes cache row pos[g] + j and only it rotates q of row j
 // in place.  No grid-wide synchronisation.
-#include "common.h"
+#include "attn_one_query.h"
 
-#define DDW 16                                   // waves per workgroup: attn_decode_kernel's DNW
 #define DRAFT_MAX_K 8
 #define DRAFT_LDS_LIMIT (160 * 1024)             // gfx950: LDS per CU
 
@@ -29,8 +28,8 @@ struct DraftParams {
   float scale;
 };
 
-__global__ __launch_bounds__(DDW * 64) void attn_decode_draft_kernel(DraftParams p) {
-  extern __shared__ float dsm[];                 // [T_cap] scores, [DDW][128] partial outputs, then [K][D] bf16 rotated k
+__global__ __launch_bounds__(OQ_WAVES * 64) void attn_decode_draft_kernel(DraftParams p) {
+  extern __shared__ float dsm[];                 // [T_cap] scores, [OQ_WAVES][128] partial outputs, then [K][D] bf16 rotated k
   const int h = blockIdx.x % p.H, row = blockIdx.x / p.H, g = row / p.K, jr0 = row - g * p.K;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int D = p.D, W = p.H * D;
@@ -44,7 +43,7 @@ __global__ __launch_bounds__(DDW * 64) void attn_decode_draft_kernel(DraftParams
   const int ps = p0 + jr0, len = ps + 1;         // this row's position; it sees keys 0 .. ps
   float* sc = dsm;
   float* part = dsm + ((p.T_cap + 63) & ~63);
-  bf16_t* kr = reinterpret_cast<bf16_t*>(part + DDW * 128);
+  bf16_t* kr = reinterpret_cast<bf16_t*>(part + OQ_WAVES * 128);
   bf16_t* cbase = p.cache + (size_t)g * p.cache_bs;
   bf16_t* src = p.qkv + (size_t)row * p.ld_qkv;
   {
@@ -56,18 +55,8 @@ __global__ __launch_bounds__(DDW * 64) void attn_decode_draft_kernel(DraftParams
       const int r = tid / items, i = (tid % items) * 4;
       const int which = r == 0 ? 0 : 1, ri = r == 0 ? jr0 : r - 1;
       bf16_t* e = p.qkv + (size_t)(g * p.K + ri) * p.ld_qkv + which * W + h * D + i;
-      const int pp = p0 + ri;
-      const float4_t c4 = *reinterpret_cast<const float4_t*>(p.cs + (size_t)pp * half + i);
-      const float4_t s4 = *reinterpret_cast<const float4_t*>(p.sn + (size_t)pp * half + i);
-      const short4_t a = *reinterpret_cast<const short4_t*>(e);
-      const short4_t bb = *reinterpret_cast<const short4_t*>(e + half);
       short4_t oa, ob;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const float x1 = bf2f((bf16_t)a[t]), x2 = bf2f((bf16_t)bb[t]);
-        oa[t] = (short)f2bf(x1 * c4[t] - x2 * s4[t]);
-        ob[t] = (short)f2bf(x2 * c4[t] + x1 * s4[t]);
-      }
+      oq_rope4(e, half, p.cs, p.sn, p0 + ri, i, oa, ob);
       if (r == 0) {
         *reinterpret_cast<short4_t*>(e) = oa;
         *reinterpret_cast<short4_t*>(e + half) = ob;
@@ -90,7 +79,7 @@ __global__ __launch_bounds__(DDW * 64) void attn_decode_draft_kernel(DraftParams
   const bf16_t* vp = cbase + W + h * D;
   const bf16_t* vq = p.qkv + (size_t)(g * p.K) * p.ld_qkv + 2 * W + h * D;     // v of row i of this step: vq + i * ld_qkv
   // phase 1: scores
-  const int sub = lane & 15, kq = lane >> 4;     // 16 lanes per key, dims sub*8 .. +7
+  const int sub = lane & 15;                     // 16 lanes per key, dims sub*8 .. +7
   float qf[8];
   const bool dim_ok = sub * 8 < D;
   {
@@ -99,103 +88,33 @@ __global__ __launch_bounds__(DDW * 64) void attn_decode_draft_kernel(DraftParams
 #pragma unroll
     for (int e = 0; e < 8; ++e) qf[e] = bf2f((bf16_t)qv[e]) * p.scale;
   }
-  for (int j0 = 0; j0 < len; j0 += 2 * DDW * 4) {
-    short8_t kv[2];
-    int jj[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      jj[u] = j0 + u * DDW * 4 + wave * 4 + kq;
-      kv[u] = (short8_t){0, 0, 0, 0, 0, 0, 0, 0};
-      if (jj[u] < len && dim_ok) {
-        if (j0 + 2 * DDW * 4 <= p0 || jj[u] < p0)          // (the first test is uniform: a pass wholly below p0 has no select)
-          kv[u] = *reinterpret_cast<const short8_t*>(kp + (size_t)jj[u] * p.ld_cache + sub * 8);
-        else
-          kv[u] = *reinterpret_cast<const short8_t*>(kr + (jj[u] - p0) * D + sub * 8);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      float s = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s += qf[e] * bf2f((bf16_t)kv[u][e]);
-      s += __shfl_xor(s, 1, 64);
-      s += __shfl_xor(s, 2, 64);
-      s += __shfl_xor(s, 4, 64);
-      s += __shfl_xor(s, 8, 64);
-      if (sub == 0 && jj[u] < len) sc[jj[u]] = s;
-    }
-  }
+  oq_scores(sc, qf, dim_ok, len, wave, lane, [&](int j, int j0) {
+    if (j0 + 2 * OQ_WAVES * 4 <= p0 || j < p0)       // (the first test is uniform: a pass wholly below p0 has no select)
+      return *reinterpret_cast<const short8_t*>(kp + (size_t)j * p.ld_cache + sub * 8);
+    return *reinterpret_cast<const short8_t*>(kr + (j - p0) * D + sub * 8);
+  });
   __syncthreads();
   // phase 2: softmax statistics (each wave for itself)
-  float mx = -INFINITY;
-  for (int j = lane; j < len; j += 64) mx = fmaxf(mx, sc[j]);
-  mx = wave_max(mx);
-  float sum = 0.f;
-  for (int j = lane; j < len; j += 64) sum += __expf(sc[j] - mx);
-  sum = wave_sum(sum);
-  // phase 3: o = sum_j p_j V[j]; lane owns dims 2*lane, 2*lane+1; wave w takes keys w, w+DDW, ...
-  float o0 = 0.f, o1 = 0.f;
+  float mx, sum;
+  oq_softmax_stats(sc, len, lane, mx, sum);
+  // phase 3: o = sum_j p_j V[j]; lane owns dims 2*lane, 2*lane+1; wave w takes keys w, w+OQ_WAVES, ...  A group of eight keys
+  // below p0 (uniform over the wave) lies in the cache: the one-row kernel's loads
+  float o0, o1;
   const bool own = 2 * lane < D;
-  int j = wave;
-  for (; j + 7 * DDW < len; j += 8 * DDW) {
-    unsigned vv[8];
-    float pj[8];
-    if (j + 7 * DDW < p0) {                        // uniform over the wave: the group lies in the cache, the one-row kernel's loads
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        vv[u] = own ? *reinterpret_cast<const unsigned*>(vp + (size_t)(j + DDW * u) * p.ld_cache + 2 * lane) : 0u;
-        pj[u] = __expf(sc[j + DDW * u] - mx);
-      }
-    } else {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int jk = j + DDW * u;
-        const bf16_t* vrow = jk < p0 ? vp + (size_t)jk * p.ld_cache : vq + (size_t)(jk - p0) * p.ld_qkv;
-        vv[u] = own ? *reinterpret_cast<const unsigned*>(vrow + 2 * lane) : 0u;
-        pj[u] = __expf(sc[jk] - mx);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      o0 += pj[u] * bf2f((bf16_t)(vv[u] & 0xffffu));
-      o1 += pj[u] * bf2f((bf16_t)(vv[u] >> 16));
-    }
-  }
-  {                                              // remainder: up to 7 keys, loads issued together
-    unsigned vv[7];
-    float pj[7];
-#pragma unroll
-    for (int u = 0; u < 7; ++u) {
-      const int jk = j + DDW * u;
-      const bool ok = jk < len;
-      const bf16_t* vrow = jk < p0 ? vp + (size_t)jk * p.ld_cache : vq + (size_t)(jk - p0) * p.ld_qkv;
-      vv[u] = (own && ok) ? *reinterpret_cast<const unsigned*>(vrow + 2 * lane) : 0u;
-      pj[u] = ok ? __expf(sc[jk] - mx) : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < 7; ++u) {
-      o0 += pj[u] * bf2f((bf16_t)(vv[u] & 0xffffu));
-      o1 += pj[u] * bf2f((bf16_t)(vv[u] >> 16));
-    }
-  }
+  const auto vcache = [&](int j) { return *reinterpret_cast<const unsigned*>(vp + (size_t)j * p.ld_cache + 2 * lane); };
+  oq_pv(sc, mx, len, wave, own, p0, vcache, [&](int j) {
+    const bf16_t* vrow = j < p0 ? vp + (size_t)j * p.ld_cache : vq + (size_t)(j - p0) * p.ld_qkv;
+    return *reinterpret_cast<const unsigned*>(vrow + 2 * lane);
+  }, o0, o1);
   part[wave * 128 + 2 * lane] = o0;
   part[wave * 128 + 2 * lane + 1] = o1;
   __syncthreads();
-  if (wave == 0 && own) {
-    const float inv = len > 0 ? 1.f / sum : 0.f;
-    float r0 = 0.f, r1 = 0.f;
-#pragma unroll
-    for (int w = 0; w < DDW; ++w) {
-      r0 += part[w * 128 + 2 * lane];
-      r1 += part[w * 128 + 2 * lane + 1];
-    }
-    *reinterpret_cast<unsigned*>(p.out + (size_t)row * p.ldo + h * D + 2 * lane) = pack_bf2(r0 * inv, r1 * inv);
-  }
+  if (wave == 0 && own) oq_sum_store(part, lane, sum, len, p.out + (size_t)row * p.ldo + h * D + 2 * lane);
 }
 
-// LDS of one workgroup: T_cap scores (rounded up to 64) and DDW x 128 partial outputs in fp32, K x D rotated keys in bf16.
+// LDS of one workgroup: T_cap scores (rounded up to 64) and OQ_WAVES x 128 partial outputs in fp32, K x D rotated keys in bf16.
 static size_t draft_lds_bytes(int T_cap, int K, int D) {
-  return (((size_t)T_cap + 63) & ~(size_t)63) * 4 + DDW * 128 * 4 + (size_t)K * D * 2;
+  return (((size_t)T_cap + 63) & ~(size_t)63) * 4 + OQ_WAVES * 128 * 4 + (size_t)K * D * 2;
 }
 
 // G sequences of K consecutive token rows in one launch: see include/myriad_hip.h.  `nrow` null: every group has K rows.
@@ -207,14 +126,8 @@ static int draft_launch(void* qkv, long ld_qkv, void* cache, long cache_bstride,
   const size_t sh = draft_lds_bytes(T_cap, K, D);
   if (sh > DRAFT_LDS_LIMIT) return MH_ERR_UNSUPPORTED;
   if (G <= 0) return MH_OK;                        // nothing to do: the answer says whether the shape is supported
-  if (!qkv || !cache || !pos || !live || !cos_tab || !sin_tab || !out || (rows && !nrow)) return MH_ERR_ARG;
-  if (ld_qkv % 8 || ld_cache % 8 || cache_bstride % 8 || ldo % 4 || ld_qkv < 3L * H * D || ld_cache < 2L * H * D ||
-      ldo < (long)H * D)
+  if (!oq_step_args_ok(qkv, ld_qkv, cache, cache_bstride, ld_cache, pos, live, nrow, rows, cos_tab, sin_tab, out, ldo, G, K, H, D))
     return MH_ERR_ARG;
-  if ((uintptr_t)qkv % 16 || (uintptr_t)cache % 16 || (uintptr_t)cos_tab % 16 || (uintptr_t)sin_tab % 16 || (uintptr_t)out % 8 ||
-      (uintptr_t)pos % 4 || (uintptr_t)live % 4 || (uintptr_t)nrow % 4)
-    return MH_ERR_ARG;
-  if ((long)G * K * H > 0x7fffffffL) return MH_ERR_ARG;
   // > 64 KiB of dynamic LDS needs an explicit opt-in; raised only when a launch needs more than any before it
   static size_t allowed = 48 * 1024;
   if (sh > allowed) {
@@ -226,7 +139,7 @@ static int draft_launch(void* qkv, long ld_qkv, void* cache, long cache_bstride,
   p.qkv = (bf16_t*)qkv; p.cache = (bf16_t*)cache; p.out = (bf16_t*)out; p.pos = pos; p.live = live; p.nrow = nrow; p.cs = cos_tab; p.sn = sin_tab;
   p.ld_qkv = ld_qkv; p.cache_bs = cache_bstride; p.ld_cache = ld_cache; p.ldo = ldo;
   p.K = K; p.H = H; p.D = D; p.T_cap = T_cap; p.scale = scale;
-  hipLaunchKernelGGL(attn_decode_draft_kernel, dim3(G * K * H), dim3(DDW * 64), sh, stream, p);
+  hipLaunchKernelGGL(attn_decode_draft_kernel, dim3(G * K * H), dim3(OQ_WAVES * 64), sh, stream, p);
   MH_CHECK_LAUNCH();
   return MH_OK;
 }

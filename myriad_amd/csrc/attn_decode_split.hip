@@ -20,13 +20,9 @@
 // mh_attn_decode_rope_split at B = 1 on that row with pos_dev[0] = pos[b].  One difference from the non-split rows kernel: that
 // one rotates q in place in qkv, this one leaves qkv alone (nothing downstream reads q after the attention).
 //
-// attn_decode_split_draft.hip (the K-row verify step of draft decoding on this view) repeats this kernel's rotary block, phases 1
-// to 3 and the merge expression for expression per row, and tests/test_split_draft_kernels_gpu.py holds its rows to the bits of
-// sequential mh_attn_decode_rope_split_rows launches: change them together.
-#include "common.h"
-
-#define SPLIT_THREADS 256
-#define SPLIT_PSTRIDE 132   // floats per (b, h, chunk) partial: o[128] | m | l | 2 pad (16-byte aligned records)
+// The arithmetic is attn_one_query.h's, which attn_decode_split_draft.hip (the K-row verify step of draft decoding on this view)
+// calls per row too.
+#include "attn_one_query.h"
 
 struct SplitParams {
   const bf16_t* qkv;
@@ -47,7 +43,7 @@ struct SplitParams {
 };
 
 template <int CH, bool ROWS>
-__global__ __launch_bounds__(SPLIT_THREADS) void attn_decode_split_kernel(SplitParams p) {
+__global__ __launch_bounds__(OQ_SPLIT_THREADS) void attn_decode_split_kernel(SplitParams p) {
   __shared__ float sc[CH];                 // chunk scores
   __shared__ float po[4][128];             // per-wave partial outputs
   __shared__ float qs[128];                // rotated q (bf16-rounded) * scale
@@ -74,17 +70,8 @@ __global__ __launch_bounds__(SPLIT_THREADS) void attn_decode_split_kernel(SplitP
     if (which == 0 || owner) {
       const bf16_t* e = src + which * W + h * D + i;
       const int ps = p.pos[b];
-      const float4_t c4 = *reinterpret_cast<const float4_t*>(p.cs + (size_t)ps * half + i);
-      const float4_t s4 = *reinterpret_cast<const float4_t*>(p.sn + (size_t)ps * half + i);
-      const short4_t a = *reinterpret_cast<const short4_t*>(e);
-      const short4_t bb = *reinterpret_cast<const short4_t*>(e + half);
       short4_t oa, ob;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const float x1 = bf2f((bf16_t)a[t]), x2 = bf2f((bf16_t)bb[t]);
-        oa[t] = (short)f2bf(x1 * c4[t] - x2 * s4[t]);
-        ob[t] = (short)f2bf(x2 * c4[t] + x1 * s4[t]);
-      }
+      oq_rope4(e, half, p.cs, p.sn, ps, i, oa, ob);
       if (which == 0) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -134,24 +121,14 @@ __global__ __launch_bounds__(SPLIT_THREADS) void attn_decode_split_kernel(SplitP
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
       if (jj[u] == lrow && dim_ok) kv[u] = *reinterpret_cast<const short8_t*>(knew + sub * 8);
-      float s = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s += qf[e] * bf2f((bf16_t)kv[u][e]);
-      s += __shfl_xor(s, 1, 64);
-      s += __shfl_xor(s, 2, 64);
-      s += __shfl_xor(s, 4, 64);
-      s += __shfl_xor(s, 8, 64);
+      const float s = oq_score(qf, kv[u]);
       if (sub == 0 && jj[u] < n) sc[jj[u]] = s;
     }
   }
   __syncthreads();
   // phase 2: the chunk's softmax statistics (every wave for itself)
-  float mx = -INFINITY;
-  for (int j = lane; j < n; j += 64) mx = fmaxf(mx, sc[j]);
-  mx = wave_max(mx);
-  float sum = 0.f;
-  for (int j = lane; j < n; j += 64) sum += __expf(sc[j] - mx);
-  sum = wave_sum(sum);
+  float mx, sum;
+  oq_softmax_stats(sc, n, lane, mx, sum);
   // phase 3: o = sum_j p_j V[j]; lane owns dims 2*lane, 2*lane+1; wave w takes keys w, w+4, ...; 8 row loads in flight
   float o0 = 0.f, o1 = 0.f;
   const bool own = 2 * lane < D;
@@ -167,26 +144,12 @@ __global__ __launch_bounds__(SPLIT_THREADS) void attn_decode_split_kernel(SplitP
                                         : *reinterpret_cast<const unsigned*>(vp + (size_t)jr * p.ld_cache + 2 * lane);
       pj[u] = ok ? __expf(sc[jr] - mx) : 0.f;
     }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      o0 += pj[u] * bf2f((bf16_t)(vv[u] & 0xffffu));
-      o1 += pj[u] * bf2f((bf16_t)(vv[u] >> 16));
-    }
+    oq_pv_add(vv, pj, o0, o1);
   }
   po[wave][2 * lane] = o0;
   po[wave][2 * lane + 1] = o1;
   __syncthreads();
-  float* rec = p.part + ((size_t)bh * p.nch + c) * SPLIT_PSTRIDE;
-  if (wave == 0) {
-    if (own) {
-      rec[2 * lane] = ((po[0][2 * lane] + po[1][2 * lane]) + po[2][2 * lane]) + po[3][2 * lane];
-      rec[2 * lane + 1] = ((po[0][2 * lane + 1] + po[1][2 * lane + 1]) + po[2][2 * lane + 1]) + po[3][2 * lane + 1];
-    }
-    if (lane == 0) {
-      rec[128] = mx;
-      rec[129] = sum;
-    }
-  }
+  if (wave == 0) oq_split_record(p.part + ((size_t)bh * p.nch + c) * OQ_SPLIT_PSTRIDE, &po[0][0], 128, lane, own, mx, sum);
 }
 
 // merge the chunks of one (b, h) in chunk order: o = sum_c e^(m_c - M) o_c / sum_c e^(m_c - M) l_c
@@ -200,37 +163,18 @@ __global__ __launch_bounds__(64) void attn_decode_combine_kernel(SplitParams p) 
   int len = p.kv_len[b];
   len = len < p.T_cap ? len : p.T_cap;
   const int nc = len > 0 ? (len + CH - 1) / CH : 0;
-  const float* rec = p.part + (size_t)bh * p.nch * SPLIT_PSTRIDE;
-  float M = -INFINITY;
-  for (int c = 0; c < nc; ++c) M = fmaxf(M, rec[(size_t)c * SPLIT_PSTRIDE + 128]);
-  float L = 0.f, o0 = 0.f, o1 = 0.f;
-  const bool own = 2 * lane < p.D;
-  for (int c = 0; c < nc; ++c) {
-    const float* r = rec + (size_t)c * SPLIT_PSTRIDE;
-    const float w = __expf(r[128] - M);
-    L += w * r[129];
-    if (own) {
-      o0 += w * r[2 * lane];
-      o1 += w * r[2 * lane + 1];
-    }
-  }
-  if (own) {
-    const float inv = nc > 0 ? 1.f / L : 0.f;
-    *reinterpret_cast<unsigned*>(p.out + (size_t)b * p.ldo + h * p.D + 2 * lane) = pack_bf2(o0 * inv, o1 * inv);
-  }
+  oq_split_merge(p.part + (size_t)bh * p.nch * OQ_SPLIT_PSTRIDE, nc, lane, p.D, p.out + (size_t)b * p.ldo + h * p.D);
 }
 
-static int split_chunk(int chunk) { return chunk == 0 ? 128 : chunk; }
-
 extern "C" long mh_attn_decode_split_ws_floats(int B, int H, int T_cap, int chunk) {
-  const int ch = split_chunk(chunk);
-  if (B <= 0 || H <= 0 || T_cap <= 0 || (ch != 128 && ch != 256 && ch != 512)) return -1;
-  return (long)B * H * ((T_cap + ch - 1) / ch) * SPLIT_PSTRIDE;
+  const int ch = oq_split_chunk(chunk);
+  if (B <= 0 || H <= 0 || T_cap <= 0 || !oq_split_chunk_ok(ch)) return -1;
+  return (long)B * H * ((T_cap + ch - 1) / ch) * OQ_SPLIT_PSTRIDE;
 }
 
 template <int CH, bool ROWS>
 static int launch_split(const SplitParams& p, hipStream_t s) {
-  hipLaunchKernelGGL((attn_decode_split_kernel<CH, ROWS>), dim3(p.nch, p.B * p.H), dim3(SPLIT_THREADS), 0, s, p);
+  hipLaunchKernelGGL((attn_decode_split_kernel<CH, ROWS>), dim3(p.nch, p.B * p.H), dim3(OQ_SPLIT_THREADS), 0, s, p);
   MH_CHECK_LAUNCH();
   hipLaunchKernelGGL((attn_decode_combine_kernel<CH, ROWS>), dim3(p.B * p.H), dim3(64), 0, s, p);
   MH_CHECK_LAUNCH();
@@ -251,7 +195,7 @@ static int split_entry(const void* qkv, long ld_qkv, void* cache, long cache_bst
     return MH_ERR_ARG;
   const long need = mh_attn_decode_split_ws_floats(B, H, T_cap, chunk);
   if (need < 0 || partials_floats < need) return MH_ERR_ARG;
-  const int ch = split_chunk(chunk);
+  const int ch = oq_split_chunk(chunk);
   SplitParams p = {};
   p.qkv = (const bf16_t*)qkv; p.ld_qkv = ld_qkv; p.cache = (bf16_t*)cache; p.cache_bs = cache_bstride; p.ld_cache = ld_cache;
   p.pos = pos; p.pos_dev = pos_dev; p.kv_len = kv_len; p.live = live; p.cs = cos_tab; p.sn = sin_tab; p.part = partials;

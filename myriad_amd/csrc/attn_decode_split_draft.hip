@@ -1,24 +1,23 @@
 // K-row split-KV token-step attention (the verify step of draft-and-verify decoding on the split-KV view): row g*K + j of qkv is the
 // token at position pos[g] + j of sequence g, and its out row and cache row carry the bits of the j-th of nrow[g] sequential
 // mh_attn_decode_rope_split_rows launches at B = 1 with the same chunk, pos = pos[g] + j and kv_len = pos[g] + j + 1
-// (tests/test_split_draft_kernels_gpu.py holds the two to the same bits: change attn_decode_split.hip and this file together).
+// (tests/test_split_draft_kernels_gpu.py holds the two to the same bits).
 //
 // attn_decode_split.hip cuts the keys at fixed multiples of the chunk size, whatever kv_len is, so the K rows of a step share every
 // chunk boundary.  One workgroup per (chunk, sequence, head) -- grid (ceil(T_cap / CH), G*H), not K times that -- loads each cached
-// key and each cached value ONCE and serves the queries of all the group's rows; per row, every expression of the one-row split
-// kernel is repeated in its order: the 8-dim partial dot product and the shfl_xor 1, 2, 4, 8 sum, the lane-stride statistics over the
-// row's own n_j keys, wave w's keys w, w + 4, ... in groups of 8, the fixed four-wave sum.  The merge launch is
-// attn_decode_combine_kernel's body per (row, head) with nc_j = ceil((pos[g] + j + 1) / CH).
+// key and each cached value ONCE and serves the queries of all the group's rows; per row it calls what the one-row split kernel
+// calls in attn_one_query.h, in its order: the key's score, the lane-stride statistics over the row's own n_j keys, the fixed
+// four-wave sum, and in the merge launch the merge with nc_j = ceil((pos[g] + j + 1) / CH).  Phase 3 is this kernel's own loop (a
+// value row is loaded once and meets every row's stored weight) in the one-row kernel's order: wave w's keys w, w + 4, ... in
+// groups of 8.
 //
 // The rows depend on each other: row j sees the keys of rows 0 .. j-1 of the same launch.  No workgroup reads a cache row >= pos[g]
 // (a stale row a rejected guess left there may hold anything): the workgroup rotates the k of the step rows whose position falls in
 // its own chunk into LDS, with their v, and is the only one to write those cache rows.  The q of every row is rotated into LDS; qkv
 // is not written (as in the split kernel, unlike attn_decode_draft.hip).  A key at or beyond a row's n_j contributes a zero weight
 // AND a zero value to it, as in the one-row kernel.
-#include "common.h"
+#include "attn_one_query.h"
 
-#define SD_THREADS 256
-#define SD_PSTRIDE 132   // floats per (row, head, chunk) partial: attn_decode_split.hip's SPLIT_PSTRIDE
 #define SD_MAX_K 8
 
 struct SplitDraftParams {
@@ -45,7 +44,7 @@ __device__ __forceinline__ int sd_rows(const SplitDraftParams& p, int g, int p0)
 
 // KT: K rounded up to 1, 2, 4 or 8 -- the rows a workgroup holds in registers
 template <int CH, int KT>
-__global__ __launch_bounds__(SD_THREADS) void attn_decode_split_draft_kernel(SplitDraftParams p) {
+__global__ __launch_bounds__(OQ_SPLIT_THREADS) void attn_decode_split_draft_kernel(SplitDraftParams p) {
   __shared__ float sc[KT][CH];               // chunk scores per row, then the un-normalised weights e^(s - m)
   __shared__ float po[4][KT][128];           // per-wave partial outputs
   __shared__ float qs[KT][128];              // rotated q (bf16-rounded) * scale
@@ -69,24 +68,15 @@ __global__ __launch_bounds__(SD_THREADS) void attn_decode_split_draft_kernel(Spl
   {
     const int half = D >> 1, items = half >> 2, vitems = D >> 3;
     const int nrot = 2 * nr * items, total = nrot + nr * vitems;
-    for (int t = tid; t < total; t += SD_THREADS) {
+    for (int t = tid; t < total; t += OQ_SPLIT_THREADS) {
       if (t < nrot) {
         const int which = t / (nr * items), r = (t / items) % nr, i = (t % items) * 4;
         const int pp = p0 + r;
         const bool mine = pp >= j0 && pp < j0 + CH;
         if (which == 0 || mine) {
           const bf16_t* e = p.qkv + (size_t)(g * p.K + r) * p.ld_qkv + which * W + h * D + i;
-          const float4_t c4 = *reinterpret_cast<const float4_t*>(p.cs + (size_t)pp * half + i);
-          const float4_t s4 = *reinterpret_cast<const float4_t*>(p.sn + (size_t)pp * half + i);
-          const short4_t a = *reinterpret_cast<const short4_t*>(e);
-          const short4_t bb = *reinterpret_cast<const short4_t*>(e + half);
           short4_t oa, ob;
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const float x1 = bf2f((bf16_t)a[u]), x2 = bf2f((bf16_t)bb[u]);
-            oa[u] = (short)f2bf(x1 * c4[u] - x2 * s4[u]);
-            ob[u] = (short)f2bf(x2 * c4[u] + x1 * s4[u]);
-          }
+          oq_rope4(e, half, p.cs, p.sn, pp, i, oa, ob);
           if (which == 0) {
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -138,19 +128,10 @@ __global__ __launch_bounds__(SD_THREADS) void attn_decode_split_draft_kernel(Spl
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
       if (jj[u] < nmax && jj[u] >= lo && dim_ok) kv[u] = *reinterpret_cast<const short8_t*>(&knew[jj[u] - lo][sub * 8]);
-      float kf[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) kf[e] = bf2f((bf16_t)kv[u][e]);
 #pragma unroll
       for (int r = 0; r < KT; ++r) {
         if (r < nr) {
-          float s = 0.f;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) s += qf[r][e] * kf[e];
-          s += __shfl_xor(s, 1, 64);
-          s += __shfl_xor(s, 2, 64);
-          s += __shfl_xor(s, 4, 64);
-          s += __shfl_xor(s, 8, 64);
+          const float s = oq_score(qf[r], kv[u]);
           if (sub == 0 && jj[u] <= lo + r) sc[r][jj[u]] = s;      // row r sees keys 0 .. pos[g] + r
         }
       }
@@ -162,16 +143,8 @@ __global__ __launch_bounds__(SD_THREADS) void attn_decode_split_draft_kernel(Spl
   for (int r = wave; r < nr; r += 4) {
     const int n = lo + r + 1 < CH ? lo + r + 1 : CH;
     if (n <= 0) continue;
-    float mx = -INFINITY;
-    for (int j = lane; j < n; j += 64) mx = fmaxf(mx, sc[r][j]);
-    mx = wave_max(mx);
-    float sum = 0.f;
-    for (int j = lane; j < n; j += 64) {
-      const float w = __expf(sc[r][j] - mx);
-      sum += w;
-      sc[r][j] = w;
-    }
-    sum = wave_sum(sum);
+    float mx, sum;
+    oq_softmax_stats<true>(sc[r], n, lane, mx, sum);
     if (lane == 0) {
       smx[r] = mx;
       ssum[r] = sum;
@@ -217,19 +190,12 @@ __global__ __launch_bounds__(SD_THREADS) void attn_decode_split_draft_kernel(Spl
   __syncthreads();
   for (int r = wave; r < nr; r += 4) {
     if (lo + r + 1 <= 0) continue;                 // the chunk starts past this row's keys: no record
-    float* rec = p.part + (((size_t)(g * p.K + r) * p.H + h) * p.nch + c) * SD_PSTRIDE;
-    if (own) {
-      rec[2 * lane] = ((po[0][r][2 * lane] + po[1][r][2 * lane]) + po[2][r][2 * lane]) + po[3][r][2 * lane];
-      rec[2 * lane + 1] = ((po[0][r][2 * lane + 1] + po[1][r][2 * lane + 1]) + po[2][r][2 * lane + 1]) + po[3][r][2 * lane + 1];
-    }
-    if (lane == 0) {
-      rec[128] = smx[r];
-      rec[129] = ssum[r];
-    }
+    float* rec = p.part + (((size_t)(g * p.K + r) * p.H + h) * p.nch + c) * OQ_SPLIT_PSTRIDE;
+    oq_split_record(rec, &po[0][r][0], KT * 128, lane, own, smx[r], ssum[r]);
   }
 }
 
-// attn_decode_combine_kernel per (row, head): merge the row's chunks in chunk order
+// attn_decode_combine_kernel's merge per (row, head)
 template <int CH>
 __global__ __launch_bounds__(64) void attn_decode_split_draft_combine_kernel(SplitDraftParams p) {
   const int bh = blockIdx.x, row = bh / p.H, h = bh % p.H, lane = threadIdx.x;
@@ -241,37 +207,18 @@ __global__ __launch_bounds__(64) void attn_decode_split_draft_combine_kernel(Spl
   }
   const int len = p0 + jr0 + 1;
   const int nc = (len + CH - 1) / CH;
-  const float* rec = p.part + (size_t)bh * p.nch * SD_PSTRIDE;
-  float M = -INFINITY;
-  for (int c = 0; c < nc; ++c) M = fmaxf(M, rec[(size_t)c * SD_PSTRIDE + 128]);
-  float L = 0.f, o0 = 0.f, o1 = 0.f;
-  const bool own = 2 * lane < p.D;
-  for (int c = 0; c < nc; ++c) {
-    const float* r = rec + (size_t)c * SD_PSTRIDE;
-    const float w = __expf(r[128] - M);
-    L += w * r[129];
-    if (own) {
-      o0 += w * r[2 * lane];
-      o1 += w * r[2 * lane + 1];
-    }
-  }
-  if (own) {
-    const float inv = nc > 0 ? 1.f / L : 0.f;
-    *reinterpret_cast<unsigned*>(p.out + (size_t)row * p.ldo + h * p.D + 2 * lane) = pack_bf2(o0 * inv, o1 * inv);
-  }
+  oq_split_merge(p.part + (size_t)bh * p.nch * OQ_SPLIT_PSTRIDE, nc, lane, p.D, p.out + (size_t)row * p.ldo + h * p.D);
 }
 
-static int sd_chunk(int chunk) { return chunk == 0 ? 128 : chunk; }
-
 extern "C" long mh_attn_decode_split_draft_ws_floats(int G, int K, int H, int T_cap, int chunk) {
-  const int ch = sd_chunk(chunk);
-  if (G <= 0 || K <= 0 || H <= 0 || T_cap <= 0 || (ch != 128 && ch != 256 && ch != 512)) return -1;
-  return (long)G * K * H * ((T_cap + ch - 1) / ch) * SD_PSTRIDE;
+  const int ch = oq_split_chunk(chunk);
+  if (G <= 0 || K <= 0 || H <= 0 || T_cap <= 0 || !oq_split_chunk_ok(ch)) return -1;
+  return (long)G * K * H * ((T_cap + ch - 1) / ch) * OQ_SPLIT_PSTRIDE;
 }
 
 template <int CH, int KT>
 static int sd_launch(const SplitDraftParams& p, int G, hipStream_t s) {
-  hipLaunchKernelGGL((attn_decode_split_draft_kernel<CH, KT>), dim3(p.nch, G * p.H), dim3(SD_THREADS), 0, s, p);
+  hipLaunchKernelGGL((attn_decode_split_draft_kernel<CH, KT>), dim3(p.nch, G * p.H), dim3(OQ_SPLIT_THREADS), 0, s, p);
   MH_CHECK_LAUNCH();
   hipLaunchKernelGGL((attn_decode_split_draft_combine_kernel<CH>), dim3(G * p.K * p.H), dim3(64), 0, s, p);
   MH_CHECK_LAUNCH();
@@ -291,18 +238,13 @@ static int split_draft_launch(const void* qkv, long ld_qkv, void* cache, long ca
                               const int* live, const int* nrow, bool rows, const float* cos_tab, const float* sin_tab, void* out,
                               long ldo, float* partials, long partials_floats, int G, int K, int H, int D, int T_cap, int chunk,
                               float scale, hipStream_t stream) {
-  const int ch = sd_chunk(chunk);
-  if (K < 1 || H <= 0 || T_cap <= 0 || T_cap > 8192 || (ch != 128 && ch != 256 && ch != 512)) return MH_ERR_ARG;
+  const int ch = oq_split_chunk(chunk);
+  if (K < 1 || H <= 0 || T_cap <= 0 || T_cap > 8192 || !oq_split_chunk_ok(ch)) return MH_ERR_ARG;
   if (D <= 0 || D % 16 || D > 128 || K > SD_MAX_K) return MH_ERR_UNSUPPORTED;
   if (G <= 0) return MH_OK;                        // nothing to do: the answer says whether the shape is supported
-  if (!qkv || !cache || !pos || !live || !cos_tab || !sin_tab || !out || !partials || (rows && !nrow)) return MH_ERR_ARG;
-  if (ld_qkv % 8 || ld_cache % 8 || cache_bstride % 8 || ldo % 4 || ld_qkv < 3L * H * D || ld_cache < 2L * H * D ||
-      ldo < (long)H * D)
+  if (!oq_step_args_ok(qkv, ld_qkv, cache, cache_bstride, ld_cache, pos, live, nrow, rows, cos_tab, sin_tab, out, ldo, G, K, H, D))
     return MH_ERR_ARG;
-  if ((uintptr_t)qkv % 16 || (uintptr_t)cache % 16 || (uintptr_t)cos_tab % 16 || (uintptr_t)sin_tab % 16 || (uintptr_t)out % 8 ||
-      (uintptr_t)partials % 4 || (uintptr_t)pos % 4 || (uintptr_t)live % 4 || (uintptr_t)nrow % 4)
-    return MH_ERR_ARG;
-  if ((long)G * K * H > 0x7fffffffL || (long)G * H > 65535L) return MH_ERR_ARG;
+  if (!partials || (uintptr_t)partials % 4 || (long)G * H > 65535L) return MH_ERR_ARG;
   const long need = mh_attn_decode_split_draft_ws_floats(G, K, H, T_cap, chunk);
   if (need < 0 || partials_floats < need) return MH_ERR_ARG;
   SplitDraftParams p;

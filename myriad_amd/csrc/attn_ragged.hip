@@ -28,6 +28,7 @@
 // >= past and takes every key at or above past from qkv (the one-row path from LDS), so its cache stores feed nothing in the
 // launch: the flag drops them and changes nothing else, and a segment's out rows have the bits _past gives it alone.
 #include "attn_tile.h"
+#include "attn_one_query.h"
 
 #include <algorithm>
 #include <vector>
@@ -46,16 +47,9 @@ struct RaggedParams {
   int lds_bytes;        // PAST form: the launch's dynamic LDS, which a one-row segment's scores must fit
 };
 
-// One rotate-half pair in the form rope_kernel compiles to (x1 c - x2 s and x2 c + x1 s, each one product rounded and one FMA),
-// written out so that the bits do not depend on what the optimiser makes of the code around the call.
-__device__ __forceinline__ void rope_pair(float x1, float x2, float c, float s, float& lo, float& hi) {
-#pragma clang fp contract(off)
-  lo = __builtin_fmaf(x1, c, -(x2 * s));
-  hi = __builtin_fmaf(x2, c, x1 * s);
-}
 // Eight rotated elements, head columns [c, c + 8), of the head starting at `head` (c % 8 == 0 and (D / 2) % 8 == 0, so the
-// eight lie in one half): rope_kernel's expressions element by element, out[c] = x[c] cos - x[c + half] sin in the first half,
-// out[c] = x[c] cos + x[c - half] sin in the second.
+// eight lie in one half): rope_kernel's expressions element by element (rope_pair, attn_one_query.h), out[c] = x[c] cos -
+// x[c + half] sin in the first half, out[c] = x[c] cos + x[c - half] sin in the second.
 __device__ __forceinline__ short8_t rope8(const bf16_t* head, int c, int half, const float* cs_row, const float* sn_row) {
   const bool first = c < half;
   const int i = first ? c : c - half;
@@ -78,20 +72,15 @@ __device__ __forceinline__ short8_t rope8(const bf16_t* head, int c, int half, c
 // A segment of ONE new row on top of `past` cached keys.  mh_attn_fwd sends Sq == 1 (Sk <= 8192) to attn_decode_kernel
 // (attention.hip), not to the tile kernel, so the bits the prefill branch of _decode_block gives such a segment are that kernel's:
 // fp32 throughout, 16 lanes per key for the scores, every wave its own softmax statistics, the keys dealt round-robin to 16 waves
-// for P.V (eight at a time, then a remainder of seven) and the 16 partial outputs summed in wave order.  This is that arithmetic,
-// expression for expression, with each of this workgroup's 4 waves taking 4 of the 16 in turn (ONE_ROW_WAVES is attention.hip's
-// DNW); the scores' LDS is reused for the partial outputs.  The new row's rotated k and its v are written to cache row `past`
-// (not with SHARED, which writes no cache row) and kept in LDS: key `past` is read from there, so no cache row >= past is read
-// here either.
-// KEEP IN STEP with attn_decode_kernel (attention.hip): a change to its phases, to DNW, to the 8 + 7 unroll of its P.V loop or to
-// mh_attn_fwd's Sq == 1 rule (Sk <= 8192) must be made here too; tests/test_ragged_past_gpu.py (the one-row segments on long
-// prefixes) compares the two bit for bit at sizes that turn every loop, and tests/test_shared_prefix_gpu.py the SHARED form
-// with this one.
-#define ONE_ROW_WAVES 16
+// for P.V (eight at a time, then a remainder of seven) and the 16 partial outputs summed in wave order.  Both call that arithmetic
+// in attn_one_query.h; each of this workgroup's 4 waves takes 4 of the OQ_WAVES shares in turn, and the scores' LDS is reused for
+// the partial outputs.  The new row's rotated k and its v are written to cache row `past` (not with SHARED, which writes no cache
+// row) and kept in LDS: key `past` is read from there, so no cache row >= past is read here either.
+// ONE_ROW_MAX_KEYS is mh_attn_fwd's Sq == 1 rule (Sk <= 8192): a change there must be made here too.
 #define ONE_ROW_MAX_KEYS 8192
 __host__ __device__ __forceinline__ int one_row_score_floats(int keys) {
   const int n = (keys + 63) & ~63;
-  return n > ONE_ROW_WAVES * 128 ? n : ONE_ROW_WAVES * 128;
+  return n > OQ_WAVES * 128 ? n : OQ_WAVES * 128;
 }
 template <bool SHARED>
 __device__ __forceinline__ void one_row_attention(const RaggedParams& p, char* smem, const bf16_t* xb, bf16_t* cb, int row, int past,
@@ -119,7 +108,7 @@ __device__ __forceinline__ void one_row_attention(const RaggedParams& p, char* s
   const bf16_t* kp = cb;
   const bf16_t* vp = cb + W;
   // phase 1: scores
-  const int sub = lane & 15, kq = lane >> 4;
+  const int sub = lane & 15;
   float qf[8];
   const bool dim_ok = sub * 8 < D;
   {
@@ -128,80 +117,25 @@ __device__ __forceinline__ void one_row_attention(const RaggedParams& p, char* s
 #pragma unroll
     for (int e = 0; e < 8; ++e) qf[e] = bf2f((bf16_t)qv[e]) * p.scale;
   }
-  for (int i = 0; i < 4; ++i) {
-    const int wave = rw * 4 + i;
-    for (int j0 = 0; j0 < len; j0 += 2 * ONE_ROW_WAVES * 4) {
-      short8_t kv[2];
-      int jj[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        jj[u] = j0 + u * ONE_ROW_WAVES * 4 + wave * 4 + kq;
-        kv[u] = (short8_t){0, 0, 0, 0, 0, 0, 0, 0};
-        if (jj[u] < len && dim_ok)
-          kv[u] = jj[u] < past ? *reinterpret_cast<const short8_t*>(kp + (size_t)jj[u] * p.ld_cache + sub * 8)
-                               : *reinterpret_cast<const short8_t*>(krow + sub * 8);
-      }
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += qf[e] * bf2f((bf16_t)kv[u][e]);
-        s += __shfl_xor(s, 1, 64);
-        s += __shfl_xor(s, 2, 64);
-        s += __shfl_xor(s, 4, 64);
-        s += __shfl_xor(s, 8, 64);
-        if (sub == 0 && jj[u] < len) sc[jj[u]] = s;
-      }
-    }
-  }
+  for (int i = 0; i < 4; ++i)
+    oq_scores(sc, qf, dim_ok, len, rw * 4 + i, lane, [&](int j, int) {
+      return j < past ? *reinterpret_cast<const short8_t*>(kp + (size_t)j * p.ld_cache + sub * 8)
+                      : *reinterpret_cast<const short8_t*>(krow + sub * 8);
+    });
   __syncthreads();
   // phase 2: softmax statistics (the same in every wave)
-  float mx = -INFINITY;
-  for (int j = lane; j < len; j += 64) mx = fmaxf(mx, sc[j]);
-  mx = wave_max(mx);
-  float sum = 0.f;
-  for (int j = lane; j < len; j += 64) sum += __expf(sc[j] - mx);
-  sum = wave_sum(sum);
-  // phase 3: o = sum_j p_j V[j]; lane owns dims 2*lane, 2*lane+1; wave w takes keys w, w+16, ...
+  float mx, sum;
+  oq_softmax_stats(sc, len, lane, mx, sum);
+  // phase 3: o = sum_j p_j V[j]; lane owns dims 2*lane, 2*lane+1; share w takes keys w, w+16, ...
   const bool own = 2 * lane < D;
   float po0[4], po1[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    float o0 = 0.f, o1 = 0.f;
-    int j = rw * 4 + i;
-    for (; j + 7 * ONE_ROW_WAVES < len; j += 8 * ONE_ROW_WAVES) {
-      unsigned vv[8];
-      float pj[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int jr = j + ONE_ROW_WAVES * u;
-        vv[u] = own ? (jr < past ? *reinterpret_cast<const unsigned*>(vp + (size_t)jr * p.ld_cache + 2 * lane)
-                                 : *reinterpret_cast<const unsigned*>(vrow + 2 * lane)) : 0u;
-        pj[u] = __expf(sc[jr] - mx);
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        o0 += pj[u] * bf2f((bf16_t)(vv[u] & 0xffffu));
-        o1 += pj[u] * bf2f((bf16_t)(vv[u] >> 16));
-      }
-    }
-    {                                              // remainder: up to 7 keys
-      unsigned vv[7];
-      float pj[7];
-#pragma unroll
-      for (int u = 0; u < 7; ++u) {
-        const int jr = j + ONE_ROW_WAVES * u;
-        const bool ok = jr < len;
-        vv[u] = (own && ok) ? (jr < past ? *reinterpret_cast<const unsigned*>(vp + (size_t)jr * p.ld_cache + 2 * lane)
-                                         : *reinterpret_cast<const unsigned*>(vrow + 2 * lane)) : 0u;
-        pj[u] = ok ? __expf(sc[jr] - mx) : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < 7; ++u) {
-        o0 += pj[u] * bf2f((bf16_t)(vv[u] & 0xffffu));
-        o1 += pj[u] * bf2f((bf16_t)(vv[u] >> 16));
-      }
-    }
+    float o0, o1;
+    oq_pv(sc, mx, len, rw * 4 + i, own, [&](int j) {
+      return j < past ? *reinterpret_cast<const unsigned*>(vp + (size_t)j * p.ld_cache + 2 * lane)
+                      : *reinterpret_cast<const unsigned*>(vrow + 2 * lane);
+    }, o0, o1);
     po0[i] = o0;
     po1[i] = o1;
   }
@@ -213,16 +147,7 @@ __device__ __forceinline__ void one_row_attention(const RaggedParams& p, char* s
     part[(rw * 4 + i) * 128 + 2 * lane + 1] = po1[i];
   }
   __syncthreads();
-  if (rw == 0 && own) {
-    const float inv = len > 0 ? 1.f / sum : 0.f;
-    float r0 = 0.f, r1 = 0.f;
-#pragma unroll
-    for (int w = 0; w < ONE_ROW_WAVES; ++w) {
-      r0 += part[w * 128 + 2 * lane];
-      r1 += part[w * 128 + 2 * lane + 1];
-    }
-    *reinterpret_cast<unsigned*>(p.o + (long)row * p.ldo + h * D + 2 * lane) = pack_bf2(r0 * inv, r1 * inv);
-  }
+  if (rw == 0 && own) oq_sum_store(part, lane, sum, len, p.o + (long)row * p.ldo + h * D + 2 * lane);
 }
 
 template <int DP, bool PAST, bool SHARED>

@@ -419,7 +419,7 @@ def attn_ref_bound(q, k, v, scale, mask, q_err=None, k_err=None, dout=None, dout
 
 
 G_SCORE = 14               # roundings of a one-query decode score: qf, 8 products folded into 8 sums (+ 1), a 4-step butterfly
-DECODE_WAVES = 16          # attention.hip DNW / attn_decode_draft.hip DDW: waves that share the keys of a one-row workgroup
+DECODE_WAVES = 16          # attn_one_query.h OQ_WAVES: waves that share the keys of a one-row workgroup
 SPLIT_WAVES = 4            # attn_decode_split.hip: waves of a chunk workgroup
 
 
@@ -502,7 +502,7 @@ def decode_attn_inputs(B, H, D, T_cap, seed, ld_pad=8):
 
 
 # The grids of tests/test_decode_attention_edges_gpu.py, here so that tests/test_fp64_bounds_cpu.py checks the emulations at the
-# same lengths and the rope ambiguity of the same seeds.  One-row kernel: 16 waves (DNW), 128 keys per score pass in two 64-key
+# same lengths and the rope ambiguity of the same seeds.  One-row kernel: 16 waves (OQ_WAVES), 128 keys per score pass in two 64-key
 # halves, a 64-lane stride in the softmax, a 16-key wave round-robin with an 8 x 16 = 128-key unrolled group (taken while
 # j + 112 < len: first at len = 113) and a remainder of up to 7 keys a wave.
 DECODE_T = 257

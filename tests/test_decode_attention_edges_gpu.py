@@ -17,7 +17,7 @@ is unchanged; the appended v has its source's bits; the rotated q (where the ker
 fb.rope_bf16 outside its one-ulp ambiguity mask.  The attention reference is then computed from the device's own rotated q and
 the cache after the launch, so the output carries no ambiguity term; the split kernels do not write q back and take q_err.
 
-Lengths follow the kernels' constants (fb.DECODE_LENS: DNW = 16 waves, the 128-key score pass in two 64-key halves, the 64-lane
+Lengths follow the kernels' constants (fb.DECODE_LENS: OQ_WAVES = 16 waves, the 128-key score pass in two 64-key halves, the 64-lane
 softmax stride, the 8 x 16 unrolled PV group, first taken at 113 keys, and its remainder): each edge at, one below and one
 above; no key (a zero row, lse = -inf); fewer keys than waves; T_cap == kv_len for 1, 64, 65; kv_len = T_cap + 5 (clamped);
 T_cap = 257 (no multiple of 64) and 8192.  Chunks 128 / 256 / 512 at one key, CH - 1, CH, CH + 1, 2 CH, 2 CH + 1 and T_cap;
